@@ -21,12 +21,23 @@ Other workloads (second bench lines, parity-test configurations at scale):
 
 Prints ONE JSON line (rank 0).  value = logical SW Gcells/s of the whole job =
 sum_ranks(sum_queries(m) * sum(len(segment)) * 48) * K / max_rank(time) / 1e9   (SURVEY.md 8(d)).
+ms_per_step = milliseconds of one timed step (slowest rank).
 
-Kernel-quality figures ("roofline", "valu", "isolated_kernels") come from an UNTIMED extra pass with ONE batch in
-flight, so that HIP-event durations are exclusive: in the timed steps ten batches share the GPU and per-kernel
-durations overlap (their sum exceeds the step time; they are reported as "kernel_ms_overlapped" for reference only).
+A plain run sets up, warms up, times the K steps and prints the line; everything else is behind --full:
+    --full                 also the kernel-quality figures ("roofline", "valu", "isolated_kernels", "isolated_per_lncrna") and
+                           the CPU baseline (the reference binary on slices of the same kind of record; --no-cpu-baseline
+                           leaves it out).  Kernel-quality figures come from an UNTIMED extra pass with ONE batch in flight,
+                           so that HIP-event durations are exclusive: in the timed steps ten batches share the GPU and per-kernel
+                           durations overlap (their sum exceeds the step time; they are reported as "kernel_ms_overlapped"
+                           for reference only).
+    --dump-outputs DIR     after the timed steps, rank 0 writes the records of the LAST timed step (what a caller of the path
+                           receives, after the gather) as DIR/triplexes.npy (DIR/triplexes_<lncRNA>.npy per lncRNA of a batch):
+                           float64, one row per record, columns DUMP_COLUMNS; the two sequence strings of a record as their
+                           length and a 48-bit BLAKE2b digest.  Above 64 MB in all, a fixed seeded sample of rows is written,
+                           with the row numbers in DIR/<name>_rows.npy.  Inputs are seeded: equal arguments give equal inputs.
 """
 import argparse
+import hashlib
 import json
 import os
 import shutil
@@ -66,6 +77,11 @@ PMC_FILE = "r03_pmc_traffic.json"      # HBM counters of the current build (tool
 #   k_scan<RP>: perm, add, 3 x max, 3 x sat-sub, 2 x max = 10 per row pair = 5.0 per cell
 #   k_align_fwd<RP,TAINT> and k_align_band<G>: the same + the row-key OR = 11 per row pair = 5.5 per cell
 OPS_PER_CELL = {"k_scan": 5.0, "k_align_fwd": 5.5}
+# --dump-outputs: columns of DIR/<name>.npy (struct fasim_triplex, then the two sequence strings from the pool)
+DUMP_COLUMNS = ["stari", "endi", "starj", "endj", "strand", "reverse", "rule", "nt", "score", "identity", "tri_score", "seg", "enc",
+                "genome_shift", "tfo_len", "tfo_blake2b48", "tts_len", "tts_blake2b48"]
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20240601
 
 
 def host_cores_uncapped():
@@ -153,6 +169,34 @@ def cpu_baseline(rna_path, m, slices):
     return out
 
 
+def dump_outputs(outdir, mod, results, names):
+    """--dump-outputs: one float64 array per result (rows = records in the order the path returns them, DUMP_COLUMNS)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    row_bytes = (len(DUMP_COLUMNS) + 1) * 8                 # + the row number, if a sample has to be taken
+    max_rows = max(1, DUMP_MAX_BYTES // (row_bytes * len(results)))
+    tdt = np.dtype(mod.Triplex)
+    for name, r in zip(names, results):
+        recs = np.frombuffer(r.recs, dtype=tdt) if r.count else np.zeros(0, dtype=tdt)
+        rows = None
+        if len(recs) > max_rows:
+            rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(len(recs), size=max_rows, replace=False))
+            recs = recs[rows]
+        pool = r.pool
+        nul = np.flatnonzero(np.frombuffer(pool, dtype=np.uint8) == 0) if pool else np.zeros(0, dtype=np.int64)
+        out = np.empty((len(recs), len(DUMP_COLUMNS)), dtype=np.float64)
+        for c, col in enumerate(DUMP_COLUMNS[:14]):
+            out[:, c] = recs[col]
+        for c, col in ((14, "tfo_off"), (16, "tts_off")):
+            offs = recs[col].astype(np.int64)
+            ends = nul[np.searchsorted(nul, offs)] if len(offs) else offs
+            out[:, c] = ends - offs
+            out[:, c + 1] = [int.from_bytes(hashlib.blake2b(pool[a:b], digest_size=6).digest(), "little") for a, b in zip(offs, ends)]
+        np.save(os.path.join(outdir, f"{name}.npy"), out)
+        if rows is not None:
+            np.save(os.path.join(outdir, f"{name}_rows.npy"), rows.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -168,10 +212,15 @@ def main():
     ap.add_argument("--shard", action="store_true", help="one record of gpus x dna-mb, sharded by contiguous segment ranges")
     ap.add_argument("--cpu-sample-nt", type=int, default=250000)
     ap.add_argument("--cpu-cores", type=int, default=0, help="processes of the all-core CPU baseline (0 = all cores this process may use, at most 64)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse)")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal: every rank uses device 0 (needs --backend gloo)")
+    ap.add_argument("--full", action="store_true", help="also the untimed kernel-quality pass (roofline, valu, isolated kernel times) "
+                    "and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the records of the last timed step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -257,10 +306,12 @@ def main():
             res = [eng.scan(None, p, seg_first, seg_count)]
         # the path's one exchange step: gather every rank's records on rank 0 (RCCL over xGMI), per lncRNA
         nrec = 0
+        gathered = []
         for r in res:
             merged = mod.gather_results(r, dist, rank, world, xdev)
             nrec += merged.count if merged is not None else 0
-        return res, nrec
+            gathered.append(merged)
+        return res, gathered, nrec
 
     def sync():
         torch.cuda.synchronize()
@@ -274,8 +325,9 @@ def main():
     t0 = time.perf_counter()
     agg = None
     nrec = 0
-    for _ in range(args.steps):
-        res, nrec = step()
+    last = None
+    for i in range(args.steps):
+        res, gathered, nrec = step()
         for r in res:
             st = r.stats
             if agg is None:
@@ -286,7 +338,9 @@ def main():
                         agg[k] = [a + b for a, b in zip(agg[k], v)]
                     else:
                         agg[k] += v
-        del res
+        if args.dump_outputs and i == args.steps - 1:
+            last = gathered                # what the caller of the path receives (rank 0: all ranks' records)
+        del res, gathered
     sync()
     dt = time.perf_counter() - t0
     tmax = torch.tensor([dt], dtype=torch.float64, device=xdev)
@@ -296,12 +350,15 @@ def main():
         dist.all_reduce(cells, op=dist.ReduceOp.SUM)
     tmax = float(tmax.item())
     total_cells = float(cells.item())
+    if last is not None and rank == 0:
+        dump_outputs(args.dump_outputs, mod, last, ["triplexes"] if len(last) == 1 else [f"triplexes_{n}" for n in rna_names])
+    last = None
 
-    # untimed extra pass for the kernel-quality figures: ONE batch in flight, so every HIP-event duration is that of a
+    # --full: untimed extra pass for the kernel-quality figures: ONE batch in flight, so every HIP-event duration is that of a
     # kernel that has the GPU to itself (exclusive); first lncRNA of the workload, first <= 1024 segments of the shard
     iso = None
     iso_all = []
-    if rank == 0:
+    if rank == 0 and args.full:
         eng.set_option("workers", 1)
         total_seg = mod.segment_count(len(dna), p)
         have = seg_count if seg_count >= 0 else total_seg
@@ -319,9 +376,10 @@ def main():
         m = len(rnas[0])
         units_per_step = agg["units"] / args.steps
         kms = agg["kernel_ms"]
-        ik, il = iso["kernel_ms"], iso["kernel_launches"]
-        n_avg = iso["cells_stage2"] / max(1, iso["units"]) / m        # mean segment length of the isolated pass
-        fwd_cells = max(0, iso["cells_stage3"] - iso["band_cells"])   # executed by k_align_fwd (+ the few cells of the finish kernels)
+        if args.full:
+            ik, il = iso["kernel_ms"], iso["kernel_launches"]
+            n_avg = iso["cells_stage2"] / max(1, iso["units"]) / m        # mean segment length of the isolated pass
+            fwd_cells = max(0, iso["cells_stage3"] - iso["band_cells"])   # executed by k_align_fwd (+ the few cells of the finish kernels)
 
         def kernel_roofline(idx):
             """HBM roofline of one of the two DP kernels from the isolated pass: algorithmic bytes per launch / exclusive
@@ -402,39 +460,42 @@ def main():
             "per_unit": {"candidates": round(agg["candidates"] / max(1, agg["units"]), 2),
                          "hazard_units_pct": round(100.0 * agg["hazard_units"] / max(1, agg["units"]), 3),
                          "overflow_units_pct": round(100.0 * agg["stage2_overflow_units"] / max(1, agg["units"]), 3)},
-            "roofline": kernel_roofline(0),
-            "roofline_stage3": kernel_roofline(2),
-            "valu": valu(0, "k_scan", iso["cells_stage2"]),
-            "valu_stage3": valu(2, "k_align_fwd", fwd_cells),
-            "valu_band": valu(8, "k_align_fwd", iso["band_cells"]) if ik[8] > 0 else None,
-            "valu_note": "useful row work = packed 16-bit VALU instructions per DP cell x executed cells / EXCLUSIVE HIP-event time "
-                         "(isolated pass); peak = the measured sustained issue rate of a pure stream of packed 16-bit ops on this chip at "
-                         "the kernel's occupancy: 1024 SIMDs x 64 lanes / 1.81 ns (tools/valu_issue_bench.hip, "
-                         "profiles/r02_valu_issue_bench.txt; power-limited, about 1.8 GHz); each packed lane-instruction processes two cells",
         }
-        out["isolated_kernels"] = {
-            "what": f"untimed pass over {iso['segments']} segments with ONE batch in flight (kernels run alone)",
-            "units": iso["units"], "align_calls": iso["align_calls"], "hazard_units": iso["hazard_units"], "rev_exact": iso["rev_exact"],
-            "ms": {KERNEL_NAMES[i]: round(ik[i], 2) for i in KERNEL_SHOWN},
-            "band_tries": iso["band_tries"], "band_proven": iso["band_proven"], "band_cells": iso["band_cells"], "cells_stage3": iso["cells_stage3"],
-            "dominant_kernel_ms_per_step_equivalent": round(ik[0] * units_per_step / max(1, iso["units"]), 1),
-            # plan + checkpoint pass + all chunks of the stripe-faithful re-run (kernel family 1), scaled to one batch of 1024 segments
-            "hazard_reruns_ms_per_49152_units": round(ik[1] * 49152 / max(1, iso["units"]), 2),
-            "hazard_launches": int(il[1]),
-        }
-        if len(iso_all) > 1 or args.rna:
-            # per lncRNA: the same one-batch pass (exclusive kernel times) and what it says about the query
-            out["isolated_per_lncrna"] = [{
-                "lncrna": rna_names[q], "m": len(rnas[q]), "segments": st["segments"], "units": st["units"], "t_total_s": round(st["t_total_s"], 4),
-                "logical_gcells_per_s_one_batch_alone": round(st["logical_cells"] / max(1e-9, st["t_total_s"]) / 1e9, 1),
-                "candidates_per_unit": round(st["candidates"] / max(1, st["units"]), 2), "align_calls": st["align_calls"],
-                "band_tries": st["band_tries"], "band_proven": st["band_proven"], "rev_bound_passes": st["rev_bound_passes"],
-                "rev_exact": st["rev_exact"], "hazard_units": st["hazard_units"], "stage2_overflow_units": st["stage2_overflow_units"],
-                "cells_stage2": st["cells_stage2"], "cells_stage3": st["cells_stage3"],
-                "ms": {KERNEL_NAMES[i]: round(st["kernel_ms"][i], 2) for i in KERNEL_SHOWN},
-                "launches": {KERNEL_NAMES[i]: int(st["kernel_launches"][i]) for i in KERNEL_SHOWN},
-            } for q, st in enumerate(iso_all)]
-        if not args.no_cpu_baseline and world == 1:       # the CPU baseline is reported at N = 1 only
+        if args.full:
+            out.update({
+                "roofline": kernel_roofline(0),
+                "roofline_stage3": kernel_roofline(2),
+                "valu": valu(0, "k_scan", iso["cells_stage2"]),
+                "valu_stage3": valu(2, "k_align_fwd", fwd_cells),
+                "valu_band": valu(8, "k_align_fwd", iso["band_cells"]) if ik[8] > 0 else None,
+                "valu_note": "useful row work = packed 16-bit VALU instructions per DP cell x executed cells / EXCLUSIVE HIP-event time "
+                             "(isolated pass); peak = the measured sustained issue rate of a pure stream of packed 16-bit ops on this chip at "
+                             "the kernel's occupancy: 1024 SIMDs x 64 lanes / 1.81 ns (tools/valu_issue_bench.hip, "
+                             "profiles/r02_valu_issue_bench.txt; power-limited, about 1.8 GHz); each packed lane-instruction processes two cells",
+            })
+            out["isolated_kernels"] = {
+                "what": f"untimed pass over {iso['segments']} segments with ONE batch in flight (kernels run alone)",
+                "units": iso["units"], "align_calls": iso["align_calls"], "hazard_units": iso["hazard_units"], "rev_exact": iso["rev_exact"],
+                "ms": {KERNEL_NAMES[i]: round(ik[i], 2) for i in KERNEL_SHOWN},
+                "band_tries": iso["band_tries"], "band_proven": iso["band_proven"], "band_cells": iso["band_cells"], "cells_stage3": iso["cells_stage3"],
+                "dominant_kernel_ms_per_step_equivalent": round(ik[0] * units_per_step / max(1, iso["units"]), 1),
+                # plan + checkpoint pass + all chunks of the stripe-faithful re-run (kernel family 1), scaled to one batch of 1024 segments
+                "hazard_reruns_ms_per_49152_units": round(ik[1] * 49152 / max(1, iso["units"]), 2),
+                "hazard_launches": int(il[1]),
+            }
+            if len(iso_all) > 1 or args.rna:
+                # per lncRNA: the same one-batch pass (exclusive kernel times) and what it says about the query
+                out["isolated_per_lncrna"] = [{
+                    "lncrna": rna_names[q], "m": len(rnas[q]), "segments": st["segments"], "units": st["units"], "t_total_s": round(st["t_total_s"], 4),
+                    "logical_gcells_per_s_one_batch_alone": round(st["logical_cells"] / max(1e-9, st["t_total_s"]) / 1e9, 1),
+                    "candidates_per_unit": round(st["candidates"] / max(1, st["units"]), 2), "align_calls": st["align_calls"],
+                    "band_tries": st["band_tries"], "band_proven": st["band_proven"], "rev_bound_passes": st["rev_bound_passes"],
+                    "rev_exact": st["rev_exact"], "hazard_units": st["hazard_units"], "stage2_overflow_units": st["stage2_overflow_units"],
+                    "cells_stage2": st["cells_stage2"], "cells_stage3": st["cells_stage3"],
+                    "ms": {KERNEL_NAMES[i]: round(st["kernel_ms"][i], 2) for i in KERNEL_SHOWN},
+                    "launches": {KERNEL_NAMES[i]: int(st["kernel_launches"][i]) for i in KERNEL_SHOWN},
+                } for q, st in enumerate(iso_all)]
+        if args.full and not args.no_cpu_baseline and world == 1:       # the CPU baseline is reported at N = 1 only
             cores = args.cpu_cores if args.cpu_cores > 0 else host_cores()
             tmp_rna = None
             cpu_rna = rna_path

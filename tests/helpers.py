@@ -122,6 +122,32 @@ def fnv1a_ints(vals):
     return f"{h:016x}"
 
 
+def probe_random_vectors():
+    """Seeded raw-kernel vectors: a ~900-nt query, 40 planted targets (S and P requests) and 40 windows (A requests).
+    The reference probe's answers are stored in tests/golden/probe_rnd40.rsp.gz (`make_golden.py probe`)."""
+    import synth
+    rng = synth._Rng(424242)
+    q = synth.random_rna(900 + rng.below(50), 7).decode()
+    reqs, targets, wins = [], [], []
+    for k in range(40):
+        t = synth.planted_dna(300 + rng.below(900), 1000 + k, q.encode(), every=150, max_len=120).decode()
+        targets.append(t.encode())
+        reqs += [f"S {q} {t}", f"P {q} {t}"]
+        w = t[:60 + rng.below(130)]
+        wins.append(w.encode())
+        reqs.append(f"A {q} {w}")
+    return q.encode(), targets, wins, reqs
+
+
+def syn10k_ntmax_inputs():
+    """BASELINE config 5 in miniature: a 10 kb synthetic lncRNA and 12 kb of DNA planted with it (byte overflows, 16-bit
+    re-runs).  The reference probe's `scan -detail 0 -na 1000` of them: tests/golden/syn10k_na1000.scan.gz."""
+    import synth
+    rna = synth.random_rna(10000, 515)
+    dna = synth.planted_dna(12000, 516, rna, every=500, max_len=180, mut_pct=6)
+    return rna, dna
+
+
 def have_ref_probe():
     return os.access(REF_PROBE, os.X_OK)
 

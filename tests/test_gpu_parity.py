@@ -394,22 +394,15 @@ def test_cli_all_records_streams_a_multi_record_file(golden_dir, tmp_path):
     assert (tmp_path / "out1" / "hg19-H19-two-TFOsorted").read_bytes() == open(os.path.join(golden_dir, "demo_lg40.TFOsorted"), "rb").read()
 
 
-def test_live_reference_probe_random_vectors(engine, oracle_build):
-    """If the compiled reference travelled with the repo (oracle/_ref), compare fresh random vectors too."""
-    if not helpers.have_ref_probe():
-        pytest.skip("oracle/_ref/ref_probe not present")
-    rng = synth._Rng(424242)
-    q = synth.random_rna(900 + rng.below(50), 7).decode()
-    engine.set_query(q.encode())
-    reqs, targets, wins = [], [], []
-    for k in range(40):
-        t = synth.planted_dna(300 + rng.below(900), 1000 + k, q.encode(), every=150, max_len=120).decode()
-        targets.append(t.encode())
-        reqs += [f"S {q} {t}", f"P {q} {t}"]
-        w = t[:60 + rng.below(130)]
-        wins.append(w.encode())
-        reqs.append(f"A {q} {w}")
-    rsp = helpers.ref_batch(reqs)
+def test_live_reference_probe_random_vectors(engine, golden_dir):
+    """Seeded random vectors against the reference probe's answers for them (tests/golden/probe_rnd40.rsp.gz); where the
+    compiled reference travelled with the repo (oracle/_ref), the live probe must still give those answers."""
+    q, targets, wins, reqs = helpers.probe_random_vectors()
+    rsp = helpers.gunzip(os.path.join(golden_dir, "probe_rnd40.rsp.gz")).decode().splitlines()
+    assert len(rsp) == len(reqs)
+    if helpers.have_ref_probe():
+        assert helpers.ref_batch(reqs) == rsp
+    engine.set_query(q)
     cols, s1 = engine.pre_align_batch(targets)
     als = engine.align_batch(wins)
     for k in range(40):
@@ -424,17 +417,18 @@ def test_live_reference_probe_random_vectors(engine, oracle_build):
             assert (a.cigar_string() or "*") == g[6]
 
 
-def test_live_reference_10kb_query_ntmax(mod, engine, tmp_path):
+def test_live_reference_10kb_query_ntmax(mod, engine, golden_dir, tmp_path):
     """BASELINE config 5 in miniature: a 10 kb synthetic lncRNA (4 query tiles), -na 1000, planted DNA so that byte
-    overflows and 16-bit re-runs occur; compared with the compiled reference when it travelled with the repo."""
-    if not helpers.have_ref_probe():
-        pytest.skip("oracle/_ref/ref_probe not present")
-    rna = synth.random_rna(10000, 515)
-    dna = synth.planted_dna(12000, 516, rna, every=500, max_len=180, mut_pct=6)
-    (tmp_path / "rna.fa").write_bytes(b">syn10k\n" + rna + b"\n")
-    (tmp_path / "dna.fa").write_bytes(b">syn|chrT|1-12000\n" + dna + b"\n")
-    out = subprocess.run([helpers.REF_PROBE, "scan", "rna.fa", "dna.fa", "-detail", "0", "-na", "1000"], cwd=tmp_path, check=True,
-                         stdout=subprocess.PIPE).stdout
+    overflows and 16-bit re-runs occur; compared with the reference probe's scan of it (tests/golden/syn10k_na1000.scan.gz),
+    and where the compiled reference travelled with the repo, the live probe must still give that scan."""
+    rna, dna = helpers.syn10k_ntmax_inputs()
+    out = helpers.gunzip(os.path.join(golden_dir, "syn10k_na1000.scan.gz"))
+    if helpers.have_ref_probe():
+        (tmp_path / "rna.fa").write_bytes(b">syn10k\n" + rna + b"\n")
+        (tmp_path / "dna.fa").write_bytes(b">syn|chrT|1-12000\n" + dna + b"\n")
+        live = subprocess.run([helpers.REF_PROBE, "scan", "rna.fa", "dna.fa", "-detail", "0", "-na", "1000"], cwd=tmp_path, check=True,
+                              stdout=subprocess.PIPE).stdout
+        assert live == out
     _, units = helpers.parse_scan(out)
     engine.set_query(rna)
     res = engine.scan(dna, mod.default_params(cLength=20, ntMax=1000))

@@ -3,9 +3,9 @@
 
 On the GPU box (counters in their own runs, no trace domains mixed in):
     export FASIM_WORKERS=1 FASIM_SEG_BATCH=1024
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_f -- python3 bench.py --dna-mb 5 --warmup 0 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_w -- python3 bench.py --dna-mb 5 --warmup 0 --no-cpu-baseline
-    python tools/pmc_traffic.py gpurun_out/pmc_f gpurun_out/pmc_w gpurun_out/bench_pmc.json > gpurun_out/r0N_pmc_traffic.json
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/pmc_f -- python3 bench.py --full --dna-mb 5 --warmup 0 --no-cpu-baseline > /tmp/bench_pmc.json
+    rocprofv3 --pmc WRITE_SIZE --output-format csv -d /tmp/pmc_w -- python3 bench.py --full --dna-mb 5 --warmup 0 --no-cpu-baseline > /dev/null
+    python tools/pmc_traffic.py /tmp/pmc_f /tmp/pmc_w /tmp/bench_pmc.json > profiles/r0N_pmc_traffic.json
 
 FETCH_SIZE / WRITE_SIZE are reported in KB.  On gfx950 FETCH_SIZE counts 64 B per 128-B request (MI355X_MICROARCH.md,
 HBM / rocprofv3 section): fetch figures are doubled; the k_scan launch, which must read exactly units x tstride bytes
@@ -36,7 +36,7 @@ def main():
     b = json.load(open(bench_json))
     # the run = timed step(s) + warm-up + the untimed isolated pass of bench.py: count what the kernels really processed
     doc = {"command": "FASIM_WORKERS=1 FASIM_SEG_BATCH=1024 rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --output-format csv -- python3 bench.py "
-                      "--dna-mb 5 --warmup 0 --no-cpu-baseline (two separate passes)",
+                      "--full --dna-mb 5 --warmup 0 --no-cpu-baseline (two separate passes)",
            "note": "KB as reported by rocprofv3, summed over the launches of each kernel; launches counts dispatches (a long query "
                    "takes one dispatch per query tile)",
            "kernels": {}}

@@ -3,18 +3,18 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 O=gpurun_out
 # 1. default bench under the kernel trace (steps 2) + its own JSON
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r02_kt -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > $O/r02_bench50mb_profiled.json 2> $O/r02_kt.err
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r02_kt -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $O/r02_bench50mb_profiled.json 2> $O/r02_kt.err
 cp $(ls $O/r02_kt/*/*kernel_stats.csv | head -1) $O/r02_bench50mb_kernel_stats.csv; rm -rf $O/r02_kt
 echo "step 1 done"
 # 2. unprofiled second bench lines
-timeout -k 10 500 python3 bench.py --steps 3 --warmup 1 > $O/r02_bench50mb.json 2> $O/r02_b1.err; echo "step 2a done"
-timeout -k 10 500 python3 bench.py --steps 2 --warmup 1 --dna genome --no-cpu-baseline > $O/r02_bench50mb_genome.json 2> $O/r02_b2.err; echo "step 2b done"
-timeout -k 10 600 python3 bench.py --steps 2 --warmup 1 --dna planted --no-cpu-baseline > $O/r02_bench50mb_planted.json 2> $O/r02_b3.err; echo "step 2c done"
-timeout -k 10 500 python3 bench.py --steps 1 --warmup 1 --lncrnas 4 --dna-mb 25 --dna genome --no-cpu-baseline > $O/r02_bench_cfg4_4x3kb_25mb.json 2> $O/r02_b4.err; echo "step 2d done"
+timeout -k 10 500 python3 bench.py --full --steps 3 --warmup 1 > $O/r02_bench50mb.json 2> $O/r02_b1.err; echo "step 2a done"
+timeout -k 10 500 python3 bench.py --full --steps 2 --warmup 1 --dna genome --no-cpu-baseline > $O/r02_bench50mb_genome.json 2> $O/r02_b2.err; echo "step 2b done"
+timeout -k 10 600 python3 bench.py --full --steps 2 --warmup 1 --dna planted --no-cpu-baseline > $O/r02_bench50mb_planted.json 2> $O/r02_b3.err; echo "step 2c done"
+timeout -k 10 500 python3 bench.py --full --steps 1 --warmup 1 --lncrnas 4 --dna-mb 25 --dna genome --no-cpu-baseline > $O/r02_bench_cfg4_4x3kb_25mb.json 2> $O/r02_b4.err; echo "step 2d done"
 # 3. PMC traffic: two separate passes, one batch in flight
 export FASIM_WORKERS=1 FASIM_SEG_BATCH=1024
-timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_f -- python3 bench.py --dna-mb 5 --warmup 0 --no-cpu-baseline > $O/bench_pmc.json 2> $O/pmc_f.err
-timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_w -- python3 bench.py --dna-mb 5 --warmup 0 --no-cpu-baseline > $O/bench_pmc_w.json 2> $O/pmc_w.err
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_f -- python3 bench.py --full --dna-mb 5 --warmup 0 --no-cpu-baseline > $O/bench_pmc.json 2> $O/pmc_f.err
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_w -- python3 bench.py --full --dna-mb 5 --warmup 0 --no-cpu-baseline > $O/bench_pmc_w.json 2> $O/pmc_w.err
 python3 tools/pmc_traffic.py $O/pmc_f $O/pmc_w $O/bench_pmc.json > $O/r02_pmc_traffic.json; rm -rf $O/pmc_f $O/pmc_w
 unset FASIM_WORKERS FASIM_SEG_BATCH
 echo "step 3 done"
