@@ -64,7 +64,8 @@ class ScanStats(C.Structure):
                 ("kernel_ms", C.c_double * 10), ("kernel_launches", C.c_int64 * 10), ("cells_stage1", C.c_int64),
                 ("cells_stage2", C.c_int64), ("cells_stage3", C.c_int64), ("hazard_units", C.c_int64), ("rev_exact", C.c_int64),
                 ("exact_replays", C.c_int64), ("tries_skipped", C.c_int64), ("band_tries", C.c_int64), ("band_proven", C.c_int64),
-                ("band_cells", C.c_int64), ("rev_bound_passes", C.c_int64)]
+                ("band_cells", C.c_int64), ("rev_bound_passes", C.c_int64), ("striped_window_probs", C.c_int64),
+                ("striped_window_ms", C.c_double)]
 
 
 class SimNode(C.Structure):
@@ -76,6 +77,8 @@ class SimNode(C.Structure):
 
 
 SIM_K = 50
+# FASIM_MAX_QUERY (include/fasim_hip.h): longest query of the fastSIM entry points (the reference's 16-bit stage-1 workspace)
+MAX_QUERY = 92256
 
 
 class _Result(C.Structure):

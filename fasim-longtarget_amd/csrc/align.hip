@@ -72,6 +72,8 @@ constexpr int CODE_VOID = 4;                 // stream codes: A0 C1 G2 T3, 4 = v
 constexpr int CODE_SN = 5;                   // (the unit codes of kernels.h use 4 for N: k_build_stream re-codes)
 constexpr int TAG_LAST = 8;                  // bit 3 of a stream byte: last column of a window
 constexpr int TAG_HZ = 16;                   // bit 4 (in flight only): hazard seen in this column
+// per-column keys (value << 17) | (FWD_KROW - row): the 11-bit value field over a 17-bit row field (rows < 131 072 > FASIM_MAX_QUERY)
+constexpr int FWD_KROW = 0x1FFFF;
 // bits 5-6 of a stream byte: zone = how many of the candidate's LATER window tries (suffixes of this window) hold the column
 
 // ------------------------------------------------------------------------------------------------
@@ -185,7 +187,7 @@ __global__ void __launch_bounds__(FWD_THREADS) __attribute__((amdgpu_waves_per_e
 	const bool lvl2 = a.seg_len16 >= 96;      // (the 16-bit pass, !TAINT, needs no Q2 test at all: its compare is unaffected)
 	const uint8_t* pl = prof + lane * AL_LANE_STRIDE;
 	// (31 - r) tags for the row keys, and the base of the global-row key of my two virtual lanes
-	const int kbase_lo = 0xFFFF - row0[0] - 31, kbase_hi = 0xFFFF - row0[1] - 31;
+	const int kbase_lo = FWD_KROW - row0[0] - 31, kbase_hi = FWD_KROW - row0[1] - 31;
 
 	for (;;) {
 		int w = 0;
@@ -207,7 +209,7 @@ __global__ void __launch_bounds__(FWD_THREADS) __attribute__((amdgpu_waves_per_e
 		for (int r = 0; r < RP; r++) { H[r] = 0; E[r] = 0; }
 		int tc = (CODE_VOID << 16) | CODE_VOID;
 		int hbot = 0, fbot = 0, recv_h_last = 0, fpo = 0;
-		uint32_t klo = 0, khi = 0;           // (colmax << 16) | (0xFFFF - row) of my two virtual lanes' columns
+		uint32_t klo = 0, khi = 0;           // (colmax << 17) | (FWD_KROW - row) of my two virtual lanes' columns
 		int chunk = CODE_VOID;
 		// pipe-end state (meaningful in lane 63)
 		int pidx = p0, cidx = 0, runmax = 0, end_ref = -1, end_read = 0, hzflag = 0, over = 0, wtaint = 0;
@@ -388,8 +390,8 @@ __global__ void __launch_bounds__(FWD_THREADS) __attribute__((amdgpu_waves_per_e
 			}
 			// per-column (max, smallest row) keys
 			const uint32_t lk = (uint32_t)a_i(lkey);
-			const uint32_t loc_lo = (((lk & 0xFFFFu) >> 5) << 16) | (uint32_t)(kbase_lo + (int)(lk & 31u));
-			const uint32_t loc_hi = ((lk >> 21) << 16) | (uint32_t)(kbase_hi + (int)((lk >> 16) & 31u));
+			const uint32_t loc_lo = (((lk & 0xFFFFu) >> 5) << 17) | (uint32_t)(kbase_lo + (int)(lk & 31u));
+			const uint32_t loc_hi = ((lk >> 21) << 17) | (uint32_t)(kbase_hi + (int)((lk >> 16) & 31u));
 			klo = kin_lo > loc_lo ? kin_lo : loc_lo;
 			khi = kin_hi > loc_hi ? kin_hi : loc_hi;
 
@@ -407,13 +409,13 @@ __global__ void __launch_bounds__(FWD_THREADS) __attribute__((amdgpu_waves_per_e
 				const uint32_t k63 = (uint32_t)__builtin_amdgcn_readlane((int)khi, 63);
 				if ((tag & 7) != CODE_VOID) {
 					// TAINT: the key's value field is 2 * maximum + taint of the winning cell
-					const int cfield = (int)(k63 >> 16);
+					const int cfield = (int)(k63 >> 17);
 					const int colmax = TAINT ? (cfield >> 1) : cfield;
 					// 8-bit pass: the reference stops at the first column whose maximum reaches 251 (overflow -> 16-bit pass), so
 					// nothing after that column matters (in particular not the saturated, hence "tainted", values further on)
 					if (!(TAINT && over)) {
 						if (tag & TAG_HZ) hzflag = 1;
-						if (colmax > runmax) { runmax = colmax; end_ref = cidx; end_read = 0xFFFF - (int)(k63 & 0xFFFFu); wtaint = TAINT ? (cfield & 1) : 0; }
+						if (colmax > runmax) { runmax = colmax; end_ref = cidx; end_read = FWD_KROW - (int)(k63 & (uint32_t)FWD_KROW); wtaint = TAINT ? (cfield & 1) : 0; }
 						if (runmax >= 255 - BIAS) over = 1;
 					}
 					cidx++;

@@ -74,7 +74,7 @@ struct BandSelArgs {
 	int32_t debug;
 };
 
-constexpr int SEL_MAXV = 2048;           // 16 tiles x 128 virtual lanes
+constexpr int SEL_MAXV = 128 * SYSTOLIC_MAX_TILES;   // virtual lanes of the longest query
 constexpr int SEL_TRIES = 64;            // tries per workgroup (16 per wave)
 
 // adds 1 (and `extra`) per lane to counters[key] (key < 0: none) with ONE atomic per distinct key of the wave; returns the lane's
@@ -96,18 +96,18 @@ __device__ __forceinline__ uint32_t wave_key_add(uint32_t* counters, int key, in
 	return res;
 }
 
-// Dynamic LDS: per wave ub[nv] and row0[nv + 1] (u16).
+// Dynamic LDS: per wave ub[nv] (u16) and row0[nv + 1] (u32: rows reach 92 256).
 __global__ void __launch_bounds__(256) k_band_decide(BandSelArgs a)
 {
-	extern __shared__ __align__(16) uint16_t sel_lds[];
+	extern __shared__ __align__(16) uint32_t sel_lds[];
 	__shared__ int d_cls[SEL_TRIES], d_cols[SEL_TRIES];
 	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 	const int nv = 128 * a.ntiles;
-	uint16_t* ub = sel_lds + (size_t)wv * (2 * nv + 2);
-	uint16_t* r0s = ub + nv;
+	uint32_t* r0s = sel_lds + (size_t)wv * (nv / 2 + nv + 1);
+	uint16_t* ub = reinterpret_cast<uint16_t*>(r0s + nv + 1);
 	// rows of k_scan's virtual lanes (the same for every try)
-	for (int v = lane; v < nv; v += 64) { int row0, rows; scan_lane_rows(v, a.seg16, a.vs, &row0, &rows); r0s[v] = (uint16_t)row0; }
-	if (lane == 0) r0s[nv] = (uint16_t)(16 * a.seg16);
+	for (int v = lane; v < nv; v += 64) { int row0, rows; scan_lane_rows(v, a.seg16, a.vs, &row0, &rows); r0s[v] = (uint32_t)row0; }
+	if (lane == 0) r0s[nv] = (uint32_t)(16 * a.seg16);
 	const int w0 = blockIdx.x * SEL_TRIES;
 	for (int k = 0; k < SEL_TRIES / 4; k++) {
 		const int slot_k = wv * (SEL_TRIES / 4) + k, w = w0 + slot_k;
@@ -319,7 +319,11 @@ hipError_t launch_band_decide(const BandSelLaunch& L, hipStream_t st)
 	if (128 * a.ntiles > SEL_MAXV) return hipErrorInvalidValue;
 	hipError_t err = hipMemsetAsync(a.counts, 0, BAND_COUNTS * sizeof(uint32_t), st);
 	if (err != hipSuccess) return err;
-	const size_t lds = (size_t)4 * (2 * 128 * a.ntiles + 2) * sizeof(uint16_t);
+	const size_t lds = (size_t)4 * (128 * a.ntiles / 2 + 128 * a.ntiles + 1) * sizeof(uint32_t);
+	if (lds > (size_t)64 * 1024) {     // more than 21 tiles (95 KB at 31); set on every such launch: the attribute is per device
+		err = hipFuncSetAttribute(reinterpret_cast<const void*>(k_band_decide), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+		if (err != hipSuccess) return err;
+	}
 	hipLaunchKernelGGL(k_band_decide, dim3((unsigned)((L.n + SEL_TRIES - 1) / SEL_TRIES)), dim3(256), lds, st, a);
 	return hipGetLastError();
 }
@@ -528,7 +532,7 @@ size_t band_lds_bytes(int m, int G) { return (size_t)(5 * band_lc(m, G) + G) * B
 // band must be at most 3/8 of the query's height (a band of half the height costs more than it saves: measured on H19, G = 32)
 int band_classes(int m)
 {
-	if (!systolic_fits(m) || systolic_tiles(m) > 16) return 0;
+	if (!systolic_fits(m)) return 0;
 	int mask = 0;
 	const int nl = band_profile_lanes(m);
 	for (int c = 0; c < 3; c++) {

@@ -78,6 +78,8 @@ int fasim_engine_create_ex(int device, int32_t flags, fasim_engine** out)
 	E->scan_v1 = v1 && atoi(v1) != 0;
 	const char* a1 = getenv("FASIM_ALIGN_V1");
 	E->align_v1 = a1 && atoi(a1) != 0;
+	const char* sw = getenv("FASIM_STRIPED_WINDOW");
+	E->striped_window = sw && atoi(sw) != 0;
 	*out = E;
 	return FASIM_OK;
 }
@@ -95,7 +97,7 @@ void fasim_engine_destroy(fasim_engine* e)
 		&e->unit_first, &e->hz_cols, &e->hz_plan, &e->hz_base, &e->hz_items, &e->snap, &e->hz_state, &e->hz_rows, &e->hz_chunk, &e->hz_src, &e->hz_zero,
 		&e->qsim, &e->sim_min, &e->sim_row, &e->sim_ev, &e->sim_cnt, &e->sim_nodes,
 		&e->ublk, &e->btarget, &e->bidx, &e->bcounts, &e->blist[0], &e->blist[1], &e->blist[2], &e->bslots[0], &e->bslots[1], &e->bslots[2],
-		&e->bprev, &e->lane_ub, &e->fzones, &e->fubslot, &e->bdec, &e->btab };
+		&e->bprev, &e->lane_ub, &e->fzones, &e->fubslot, &e->bdec, &e->btab, &e->swin };
 	for (auto& t : e->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
 	for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
 	for (DevBuf* b : bufs) b->release();
@@ -119,14 +121,25 @@ int fasim_set_option(fasim_engine* E, const char* key, int32_t value)
 	else if (!strcmp(key, "host_threads")) { if (value > 0) { E->host_threads = value; E->host_threads_total = value; E->host_threads_explicit = true; } }   // host side of the batches (all workers together)
 	else if (!strcmp(key, "numa_affinity")) E->opt_numa = value != 0;
 	else if (!strcmp(key, "band")) E->opt_band = value;                   // banded stage-3 forward pass: 0 off, 1 on (-1: default / FASIM_BAND)
+	else if (!strcmp(key, "striped_window")) E->striped_window = value > 0;   // 1: every k_striped launch on the HBM-window variant (tests)
 	else return fail(E, FASIM_E_ARG, "unknown option %s", key);
 	return FASIM_OK;
+}
+
+// FASIM_MAX_QUERY (fasim_hip.h): above it the reference's 16-bit stage-1 pass overruns its workspace
+static int refuse_long_query(fasim_engine* E, int64_t len, int index)
+{
+	char which[32] = "";
+	if (index >= 0) snprintf(which, sizeof which, " (query %d)", index);
+	return fail(E, FASIM_E_UNSUPPORTED, "query of %lld nt%s exceeds the limit of %d nt: above it the reference's 16-bit stage-1 pass "
+		"overruns its fixed workspace (stats.h:397) and its output is undefined", (long long)len, which, FASIM_MAX_QUERY);
 }
 
 int fasim_set_query(fasim_engine* E, const char* rna, int32_t len)
 {
 	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
 	if (!rna || len <= 0) return fail(E, FASIM_E_ARG, "empty query");
+	if (len > FASIM_MAX_QUERY) return refuse_long_query(E, len, -1);
 	HIPOK(hipSetDevice(E->device));
 	E->rna.assign(rna, rna + len);
 	E->m = len;
@@ -202,6 +215,8 @@ int fasim_ssw_colmax_word(fasim_engine* E, const char* target, int32_t n, int32_
 	L.tcodes = E->tcodes.as<uint8_t>(); L.qcodes = E->q2.as<uint8_t>(); L.probs = E->probs.as<StripedProb>(); L.nprob = 1;
 	L.counter = E->counter.as<uint32_t>(); L.lut = E->lut2; L.max_qlen = E->m; L.colmax = nullptr;
 	L.colmax_w = E->colmax16.as<uint16_t>(); L.max_out = E->max_out.as<int32_t>(); L.ends = nullptr;
+	bool win = false;
+	rc = prep_striped_window(E, MODE_PRE, true, L, &win); if (rc) return rc;
 	const hipError_t he = launch_striped(MODE_PRE, true, false, L, E->st);
 	if (he == hipErrorInvalidValue) return fail(E, FASIM_E_UNSUPPORTED, "query of %d nt does not fit the LDS-resident striped kernel", E->m);
 	if (he != hipSuccess) return fail(E, FASIM_E_HIP, "striped kernel launch failed: %s", hipGetErrorString(he));
@@ -413,6 +428,7 @@ int fasim_scan_queries(fasim_engine* E, const char* const* rnas, const int32_t* 
 {
 	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
 	if (nq <= 0 || !rnas || !rna_lens || !outs) return fail(E, FASIM_E_ARG, "bad arguments");
+	for (int32_t q = 0; q < nq; q++) if (rna_lens[q] > FASIM_MAX_QUERY) return refuse_long_query(E, rna_lens[q], q);
 	return scan_core(E, rnas, rna_lens, nq, dna, dna_len, seg_first, seg_count, pp, outs);
 }
 

@@ -130,6 +130,13 @@ struct fasim_engine {
 	int ublk_units = 0, ublk_blocks = 0;         // units covered by `ublk` (0: none), blocks per (unit, tile)
 	int opt_band = -1;                           // option "band": 0 off, 1 on (-1 = default / environment FASIM_BAND)
 	int opt_numa = 1;                            // option "numa_affinity": pin the scan's host threads to the GPU's NUMA node (no-op on one node)
+	// HBM-window variant of k_striped (queries whose stripes do not fit the LDS): its scratch, the forcing switch (option
+	// "striped_window" / FASIM_STRIPED_WINDOW=1: every stripe-faithful launch takes it, for tests), problems run on it and its
+	// HIP-event time since the counters were last taken
+	DevBuf swin;
+	bool striped_window = false;
+	int64_t sw_probs = 0;
+	double sw_ms = 0.0;
 };
 
 
@@ -178,6 +185,8 @@ inline hipEvent_t get_event(fasim_engine* E)
 	if (hipEventCreate(&e) != hipSuccess) return nullptr;
 	return e;
 }
+// TimedScope family: FASIM_KERNEL_FAMILIES index, plus TIMED_WINDOW for a k_striped launch on the HBM-window variant
+constexpr int TIMED_FAMILY_MASK = 0xff, TIMED_WINDOW = 0x100;
 struct TimedScope {
 	fasim_engine* E; hipEvent_t a = nullptr, b = nullptr; int family;
 	hipStream_t s;
@@ -189,7 +198,11 @@ inline void drain_timed(fasim_engine* E)
 {
 	for (auto& t : E->timed) {
 		float ms = 0.0f;
-		if (hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) { E->kernel_ms[t.family] += ms; E->kernel_launches[t.family]++; }
+		if (hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) {
+			const int fam = t.family & TIMED_FAMILY_MASK;
+			E->kernel_ms[fam] += ms; E->kernel_launches[fam]++;
+			if (t.family & TIMED_WINDOW) E->sw_ms += ms;
+		}
 		E->ev_pool.push_back(t.a); E->ev_pool.push_back(t.b);
 	}
 	E->timed.clear();
@@ -367,6 +380,7 @@ inline const uint8_t* tcv(const fasim_engine* E) { return E->tcodes.as<uint8_t>(
 struct FwdZones { std::vector<uint32_t> zones; std::vector<int32_t> slot; };
 
 int run_striped(fasim_engine* E, StripedMode mode, bool word, const std::vector<StripedProb>& probs, bool stage1, const uint8_t* tcodes, int max_qlen);
+int prep_striped_window(fasim_engine* E, StripedMode mode, bool word, StripedLaunch& L, bool* used);
 int run_stage1(fasim_engine* E, const UnitBatch& B, std::vector<int>& score, int64_t* word_reruns);
 int run_stage2(fasim_engine* E, const UnitBatch& B);
 int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& unit_needs_stage1, ScanOut& out, fasim_scan_stats* st);

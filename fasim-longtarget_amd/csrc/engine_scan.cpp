@@ -498,6 +498,7 @@ static void add_stats(fasim_scan_stats& st, const fasim_scan_stats& x)
 	st.cells_stage2 += x.cells_stage2; st.cells_stage3 += x.cells_stage3; st.hazard_units += x.hazard_units; st.rev_exact += x.rev_exact;
 	st.exact_replays += x.exact_replays; st.tries_skipped += x.tries_skipped;
 	st.band_tries += x.band_tries; st.band_proven += x.band_proven; st.band_cells += x.band_cells; st.rev_bound_passes += x.rev_bound_passes;
+	st.striped_window_probs += x.striped_window_probs; st.striped_window_ms += x.striped_window_ms;
 	for (int k = 0; k < FASIM_KERNEL_FAMILIES; k++) { st.kernel_ms[k] += x.kernel_ms[k]; st.kernel_launches[k] += x.kernel_launches[k]; }
 }
 
@@ -587,6 +588,16 @@ int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens,
 			seg_batch = std::max<int64_t>(16, std::min<int64_t>(128, (seg_count + 7) / 8));
 			taper_pct = 0;
 		}
+		// queries beyond 16 systolic tiles: the per-batch buffers that grow with the tiles (k_scan's block maxima for the banded
+		// stage 3: ~10 KB per unit and tile; the reverse-pass lane maxima: 1 KB per candidate and tile) stay at their 16-tile size
+		if (!envb && E->opt_seg_batch <= 0 && !p.classicSim) {
+			int tiles = 1;
+			for (int q = 0; q < nquery; q++) {
+				const int mq = (int)queries[(size_t)q].size();
+				if (systolic_fits(mq)) tiles = std::max(tiles, systolic_tiles(mq));
+			}
+			if (tiles > 16) seg_batch = std::max<int64_t>(1, seg_batch * 16 / tiles);
+		}
 		std::vector<std::pair<int64_t, int64_t>> chunks;
 		{
 			int64_t b0 = seg_first; const int64_t b_end = seg_first + seg_count;
@@ -618,7 +629,7 @@ int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens,
 		}
 		for (fasim_engine* w : ws) {
 			w->gate = (ws.size() > 1 && E->own_gate.cap > 0) ? &E->own_gate : nullptr;
-			w->scan_v1 = E->scan_v1; w->align_v1 = E->align_v1;
+			w->scan_v1 = E->scan_v1; w->align_v1 = E->align_v1; w->striped_window = E->striped_window;
 			w->hz_chunks = E->hz_chunks; w->hz_snap = E->hz_snap; w->hz_target = E->hz_target; w->hz_hot_w = E->hz_hot_w; w->opt_band = E->opt_band;
 			w->host_threads = std::max(1, E->host_threads_total / nworkers);
 			w->host_threads_share_total = E->host_threads_total; w->active_workers = &active_workers; w->sim_in_flight = &sim_active; w->scan_workers = (int)ws.size();
@@ -632,6 +643,7 @@ int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens,
 			int rc = upload(w, w->enc_ids, encs.data(), sizeof(int) * nenc); if (rc) return rc;
 			drain_timed(w);
 			for (int k = 0; k < FASIM_KERNEL_FAMILIES; k++) { w->kernel_ms[k] = 0; w->kernel_launches[k] = 0; }
+			w->sw_probs = 0; w->sw_ms = 0.0;
 		}
 		std::vector<std::vector<HostTriplex>> per_item(items.size());
 		std::vector<fasim_scan_stats> ist(items.size());
@@ -663,6 +675,7 @@ int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens,
 				(void)hipStreamSynchronize(w->st);
 				drain_timed(w);
 				for (int k = 0; k < FASIM_KERNEL_FAMILIES; k++) { ist[c].kernel_ms[k] = w->kernel_ms[k]; ist[c].kernel_launches[k] = w->kernel_launches[k]; w->kernel_ms[k] = 0; w->kernel_launches[k] = 0; }
+				ist[c].striped_window_probs = w->sw_probs; ist[c].striped_window_ms = w->sw_ms; w->sw_probs = 0; w->sw_ms = 0.0;
 				if (!r) collect_batch(ctx, per_item[c]);
 				it1[c] = now_s();
 				if (r) wrc[wi] = r;

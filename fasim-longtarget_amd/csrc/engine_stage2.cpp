@@ -13,13 +13,30 @@ int run_striped(fasim_engine* E, StripedMode mode, bool word, const std::vector<
 	L.probs = E->probs.as<StripedProb>(); L.nprob = (int)probs.size(); L.counter = E->counter.as<uint32_t>();
 	L.lut = stage1 ? E->lut1 : E->lut2; L.max_qlen = max_qlen;
 	L.colmax = E->colmax.as<uint8_t>(); L.max_out = E->max_out.as<int32_t>(); L.ends = E->ends.as<AlignEnds>();
+	bool win = false;
+	rc = prep_striped_window(E, mode, word, L, &win); if (rc) return rc;
 	hipError_t he;
 	{
-		TimedScope ts(E, mode == MODE_ALIGN || mode == MODE_REV ? 5 : 1);
+		TimedScope ts(E, (mode == MODE_ALIGN || mode == MODE_REV ? 5 : 1) | (win ? TIMED_WINDOW : 0));
 		he = launch_striped(mode, word, !stage1, L, E->st);
 	}
 	if (he == hipErrorInvalidValue) return fail(E, FASIM_E_UNSUPPORTED, "query of %d nt does not fit the LDS-resident striped kernel", max_qlen);
 	if (he != hipSuccess) return fail(E, FASIM_E_HIP, "striped kernel launch failed: %s", hipGetErrorString(he));
+	return FASIM_OK;
+}
+
+// The HBM-window variant of k_striped where the LDS-resident kernel cannot hold the query's stripes (or where the option
+// "striped_window" forces it): sizes the engine's scratch and points the launch at it.  *used: the launch will take it.
+int prep_striped_window(fasim_engine* E, StripedMode mode, bool word, StripedLaunch& L, bool* used)
+{
+	*used = false;
+	const size_t need = striped_window_bytes(mode, word, L.max_qlen, L.nprob, E->striped_window);
+	if (!need) return FASIM_OK;
+	if (E->swin.ensure(need) != hipSuccess)
+		return fail(E, FASIM_E_NOMEM, "cannot allocate %zu bytes of scratch for the stripes of a %d-nt query", need, L.max_qlen);
+	L.window = E->swin.as<uint8_t>(); L.window_bytes = need;
+	E->sw_probs += L.nprob;
+	*used = true;
 	return FASIM_OK;
 }
 
@@ -194,7 +211,9 @@ int run_hazard_chunked(fasim_engine* E, const UnitBatch& B, const std::vector<in
 	SL.counter = E->counter.as<uint32_t>(); SL.lut = E->lut2; SL.max_qlen = E->m; SL.colmax = nullptr; SL.max_out = nullptr; SL.ends = nullptr;
 	SL.state = E->hz_state.as<uint16_t>(); SL.state_rows = rows_total; SL.chunk_cols = E->hz_plan.as<int32_t>(); SL.chunk_base = E->hz_base.as<int32_t>();
 	SL.chunk_rows = E->hz_rows.as<uint8_t>(); SL.row_stride = B.tstride; SL.chunk_out = E->hz_chunk.as<int32_t>(); SL.spread = spread;
-	{ TimedScope ts(E, 1); he = launch_striped(MODE_PRE, false, true, SL, E->st); }
+	bool win = false;
+	rc = prep_striped_window(E, MODE_PRE, false, SL, &win); if (rc) return rc;
+	{ TimedScope ts(E, 1 | (win ? TIMED_WINDOW : 0)); he = launch_striped(MODE_PRE, false, true, SL, E->st); }
 	if (he == hipErrorInvalidValue) return fail(E, FASIM_E_UNSUPPORTED, "query of %d nt does not fit the LDS-resident striped kernel", E->m);
 	if (he != hipSuccess) return fail(E, FASIM_E_HIP, "striped kernel launch failed: %s", hipGetErrorString(he));
 	std::vector<int32_t> co((size_t)4 * np);

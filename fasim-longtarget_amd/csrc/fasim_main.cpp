@@ -266,6 +266,11 @@ int main(int argc, char* const* argv)
 	if (!reader.open(f1)) { fprintf(stderr, "fasim: cannot read DNA file %s\n", f1.c_str()); return 1; }
 	if (!read_rnas(f2, rnas)) { fprintf(stderr, "fasim: cannot read RNA file %s\n", f2.c_str()); return 1; }
 	for (const Rna& r : rnas) if (r.seq.empty()) { fprintf(stderr, "fasim: empty RNA record '%s' in %s\n", r.name.c_str(), f2.c_str()); return 1; }
+	for (const Rna& r : rnas) if (r.seq.size() > (size_t)FASIM_MAX_QUERY) {
+		fprintf(stderr, "fasim: RNA record '%s' in %s is %zu nt long, which exceeds the limit of %d nt: above it the reference's 16-bit "
+			"stage-1 pass overruns its fixed workspace and its output is undefined\n", r.name.c_str(), f2.c_str(), r.seq.size(), FASIM_MAX_QUERY);
+		return 1;
+	}
 	std::cout << "Searching triplexes using Fasim" << std::endl;
 	for (const Rna& r : rnas) std::cout << r.name << std::endl;
 

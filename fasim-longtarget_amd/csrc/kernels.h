@@ -25,7 +25,14 @@ struct StripedLaunch {
 	const uint16_t* state = nullptr; int32_t state_rows = 0; const int32_t* chunk_cols = nullptr; const int32_t* chunk_base = nullptr; uint8_t* chunk_rows = nullptr; int32_t row_stride = 0;
 	int32_t* chunk_out = nullptr;
 	bool spread = false;        // one 256-thread workgroup per CU (LDS request padded past half a CU): every wave gets a SIMD of its own
+	// non-NULL: run the HBM-window variant (stripes in global scratch instead of LDS) with this scratch of window_bytes >=
+	// striped_window_bytes(...); the LDS-resident kernel is used otherwise
+	uint8_t* window = nullptr; size_t window_bytes = 0;
 };
+
+// scratch the HBM-window variant of k_striped needs for this launch; 0 where the LDS-resident kernel fits (and force is false).
+// Bounded by the problems in flight (at most 2048 slots, 512 MB), not by nprob.
+size_t striped_window_bytes(StripedMode mode, bool word, int max_qlen, int nprob, bool force);
 
 // word == false: 8-bit semantics (16 stripes); word == true: 16-bit semantics (8 stripes)
 // quirk: reproduce the signed lazy-F exit test of the SSW byte kernels (sswNew.cpp:369,590)
@@ -77,6 +84,7 @@ struct ScanLaunch {
 };
 constexpr int SCAN_UBLK_STEPS = 64;       // pipeline steps per block of maxima
 inline int scan_ublk_blocks(int tstride) { return (tstride + 127 + SCAN_UBLK_STEPS - 1) / SCAN_UBLK_STEPS; }
+constexpr int SYSTOLIC_MAX_TILES = 31;
 int systolic_vs(int m);
 int systolic_tiles(int m);     // query tiles of 128 virtual lanes x <= 24 rows (1 for m <= 3072)
 bool systolic_fits(int m);
@@ -116,10 +124,10 @@ hipError_t launch_finish_big(const uint8_t* tcodes, const uint8_t* qcodes, const
 // score reaches theta_min; nq = length of the try's column stream in groups of 4 columns
 struct BandTry { int32_t prob, r0, theta_min, nq; };
 constexpr int BAND_SLOT_COLS = 208;       // 16-bit stream words per try (window <= 200 columns + 2 void columns, rounded up to 4)
-constexpr int BAND_MAX_ZONES = 16;
+constexpr int BAND_MAX_ZONES = 32;          // 31 zones of 64 profile lanes hold the longest query
 // counters of one selection pass: [class * BAND_MAX_ZONES + zone] tries, then stream columns per class, then (debug) the tries left
 // unbanded because a bound reaches 148 / because no band proves the target
-constexpr int BAND_COUNT_COLS = 3 * BAND_MAX_ZONES, BAND_COUNT_HOT = BAND_COUNT_COLS + 3, BAND_COUNT_NOBAND = BAND_COUNT_COLS + 4, BAND_COUNTS = 64;
+constexpr int BAND_COUNT_COLS = 3 * BAND_MAX_ZONES, BAND_COUNT_HOT = BAND_COUNT_COLS + 3, BAND_COUNT_NOBAND = BAND_COUNT_COLS + 4, BAND_COUNTS = 128;
 struct BandSelLaunch {
 	const FwdProb* probs; const int32_t* target; const int32_t* idx; int32_t n, tstride;
 	const uint16_t* ublk; int32_t ublk_blocks; int32_t m; const uint8_t* tcodes;

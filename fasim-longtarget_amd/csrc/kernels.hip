@@ -77,6 +77,10 @@ struct StripedArgs {
 	uint8_t* chunk_rows;        // [chunk_base[unit] + chunk][row_stride]
 	int32_t row_stride;
 	int32_t* chunk_out;         // [problem][4]: {last chunk covered, overflow column or -1, ticks of 10 ns spent, start tick}
+	// HBM-window variant: one slot of slot_bytes per 16-lane group of the grid, rows per stripe padded to sg (a multiple of 16)
+	uint8_t* window;
+	int64_t slot_bytes;
+	int32_t sg;
 };
 
 __device__ __forceinline__ int group_max16(int v)
@@ -215,7 +219,161 @@ __device__ __forceinline__ int column_word(uint16_t* Hs, uint16_t* Es, const uin
 	return part ? cmax : 0;
 }
 
-template <int MODE, bool WORD, bool QUIRK>
+// ---- HBM-window variant (queries whose stripes do not fit the LDS) ---------------------------------------------------------
+// The H / E / query stripes of a problem live in a per-problem slot of global scratch (L2- and MALL-resident at these sizes),
+// interleaved in blocks of 16 rows: row j of stripe s sits at element win_ix(j) + 16 s, so that one lane moves its 16 rows of
+// a block with one (8-bit) or two (16-bit) 16-byte accesses and the 16 lanes of a problem cover one contiguous 256 / 512 bytes.
+// The arithmetic is column_byte / column_word row for row; only where the values live differs.
+__device__ __forceinline__ int win_ix(int j) { return ((j >> 4) << 8) | (j & 15); }
+
+// one block of 16 rows of HT values as dwords (4 rows per dword in 8-bit mode, 2 in 16-bit mode)
+template <typename HT> struct WinBlock {
+	static constexpr int NW = 4 * (int)sizeof(HT);
+	static constexpr int RPW = 4 / (int)sizeof(HT), BITS = 8 * (int)sizeof(HT);
+	static constexpr uint32_t MASK = sizeof(HT) == 1 ? 0xffu : 0xffffu;
+	uint32_t w[NW];
+	__device__ __forceinline__ void load(const HT* p)
+	{
+		const uint4* v = reinterpret_cast<const uint4*>(p);
+#pragma unroll
+		for (int k = 0; k < NW / 4; k++) { const uint4 x = v[k]; w[4 * k] = x.x; w[4 * k + 1] = x.y; w[4 * k + 2] = x.z; w[4 * k + 3] = x.w; }
+	}
+	__device__ __forceinline__ void store(HT* p) const
+	{
+		uint4* v = reinterpret_cast<uint4*>(p);
+#pragma unroll
+		for (int k = 0; k < NW / 4; k++) v[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+	}
+	__device__ __forceinline__ int get(int r) const { return (int)((w[r / RPW] >> (BITS * (r % RPW))) & MASK); }
+	__device__ __forceinline__ void set(int r, int v)
+	{
+		const int sh = BITS * (r % RPW);
+		w[r / RPW] = (w[r / RPW] & ~(MASK << sh)) | (((uint32_t)v & MASK) << sh);
+	}
+};
+
+// column_byte with the stripes in an HBM slot: the next block's rows are loaded before this block's are computed
+template <bool QUIRK>
+__device__ __forceinline__ int column_byte_win(uint8_t* Hs, uint8_t* Es, const uint8_t* Qs, int segLen, uint32_t lut, int s)
+{
+	int hd = __shfl_up((int)Hs[win_ix(segLen - 1)], 1, 16);
+	if (s == 0) hd = 0;
+	int f = 0, cmax = 0;
+	const int nb = (segLen + 15) >> 4;
+	WinBlock<uint8_t> hn, en, qn;
+	hn.load(Hs); en.load(Es); qn.load(Qs);
+	for (int b = 0; b < nb; b++) {
+		WinBlock<uint8_t> hb = hn, eb = en, qb = qn;
+		if (b + 1 < nb) { hn.load(Hs + (b + 1) * 256); en.load(Es + (b + 1) * 256); qn.load(Qs + (b + 1) * 256); }
+#pragma unroll
+		for (int r = 0; r < 16; r++) {
+			if (b * 16 + r < segLen) {
+				const int p = (lut >> qb.get(r)) & 0xf;
+				int e = eb.get(r);
+				const int hold = hb.get(r);
+				int h = hd + p - BIAS;
+				h = min(h, 255 - BIAS);
+				h = max(h, e);
+				h = max(h, f);
+				cmax = max(cmax, h);
+				hb.set(r, h);
+				const int ho = h - GAP_OPEN;
+				e = max(max(e - GAP_EXT, ho), 0);
+				f = max(max(f - GAP_EXT, ho), 0);
+				eb.set(r, e);
+				hd = hold;
+			}
+		}
+		hb.store(Hs + b * 256);
+		eb.store(Es + b * 256);
+	}
+	bool go = true;
+	for (int k = 0; k < 16 && go; k++) {
+		const int fs = __shfl_up(f, 1, 16);
+		f = (s == 0) ? 0 : fs;
+		for (int b = 0; b < nb && go; b++) {
+			WinBlock<uint8_t> hb;
+			hb.load(Hs + b * 256);
+#pragma unroll
+			for (int r = 0; r < 16; r++) {
+				if (go && b * 16 + r < segLen) {
+					int h = hb.get(r);
+					h = max(h, f);
+					cmax = max(cmax, h);
+					hb.set(r, h);
+					const int ho = max(h - GAP_OPEN, 0);
+					f = max(f - GAP_EXT, 0);
+					const bool c = QUIRK ? ((int)(int8_t)f > (int)(int8_t)ho) : (f > ho);
+					if (!group_any16(c) || !group_any16(f > 0)) go = false;     // (see column_byte)
+				}
+			}
+			hb.store(Hs + b * 256);
+		}
+	}
+	return cmax;
+}
+
+// column_word with the stripes in an HBM slot
+__device__ __forceinline__ int column_word_win(uint16_t* Hs, uint16_t* Es, const uint8_t* Qs, int segLen, uint32_t lut, int s, bool part)
+{
+	int hd = __shfl_up((int)(int16_t)Hs[win_ix(segLen - 1)], 1, 16);
+	if (s == 0) hd = 0;
+	int f = 0, cmax = 0;
+	const int nb = (segLen + 15) >> 4;
+	WinBlock<uint16_t> hn, en;
+	WinBlock<uint8_t> qn;
+	hn.load(Hs); en.load(Es); qn.load(Qs);
+	for (int b = 0; b < nb; b++) {
+		WinBlock<uint16_t> hb = hn, eb = en;
+		const WinBlock<uint8_t> qb = qn;
+		if (b + 1 < nb) { hn.load(Hs + (b + 1) * 256); en.load(Es + (b + 1) * 256); qn.load(Qs + (b + 1) * 256); }
+#pragma unroll
+		for (int r = 0; r < 16; r++) {
+			if (b * 16 + r < segLen) {
+				const int p = (int)((lut >> qb.get(r)) & 0xf) - BIAS;
+				int e = (int16_t)eb.get(r);
+				const int hold = (int16_t)hb.get(r);
+				int h = min(hd + p, 32767);
+				h = max(h, e);
+				h = max(h, f);
+				cmax = max(cmax, h);
+				hb.set(r, h);
+				const int ho = max(h - GAP_OPEN, 0);
+				e = max(max(e - GAP_EXT, 0), ho);
+				f = max(max(f - GAP_EXT, 0), ho);
+				eb.set(r, e);
+				hd = hold;
+			}
+		}
+		hb.store(Hs + b * 256);
+		eb.store(Es + b * 256);
+	}
+	bool go = true;
+	for (int k = 0; k < 8 && go; k++) {
+		const int fs = __shfl_up(f, 1, 16);
+		f = (s == 0) ? 0 : fs;
+		for (int b = 0; b < nb && go; b++) {
+			WinBlock<uint16_t> hb;
+			hb.load(Hs + b * 256);
+#pragma unroll
+			for (int r = 0; r < 16; r++) {
+				if (go && b * 16 + r < segLen) {
+					int h = (int16_t)hb.get(r);
+					h = max(h, f);
+					cmax = max(cmax, h);
+					hb.set(r, h);
+					const int ho = max(h - GAP_OPEN, 0);
+					f = max(f - GAP_EXT, 0);
+					if (!group_any16(part && f > ho)) go = false;
+				}
+			}
+			hb.store(Hs + b * 256);
+		}
+	}
+	return part ? cmax : 0;
+}
+
+template <int MODE, bool WORD, bool QUIRK, bool WIN = false>
 __global__ void __launch_bounds__(256) k_striped(StripedArgs a)
 {
 	extern __shared__ __align__(16) uint8_t lds[];
@@ -226,12 +384,24 @@ __global__ void __launch_bounds__(256) k_striped(StripedArgs a)
 	const int S4 = a.s4;
 	// MODE_PRE / MODE_MAX1: every problem of the launch aligns the same whole query, so its striped copy is shared by
 	// the groups of the workgroup (placed after the per-group H/E regions); the alignment modes need one per group
-	constexpr bool SHARED_Q = (MODE == MODE_PRE || MODE == MODE_MAX1);
-	const size_t gbytes = (size_t)(SHARED_Q ? (WORD ? 64 : 32) : (WORD ? 80 : 48)) * S4;
-	uint8_t* base = lds + g * gbytes;
-	HT* Hs = reinterpret_cast<HT*>(base) + (size_t)s * S4;
-	HT* Es = reinterpret_cast<HT*>(base) + (size_t)16 * S4 + (size_t)s * S4;
-	uint8_t* Qs = (SHARED_Q ? lds + (blockDim.x >> 4) * gbytes : base + (size_t)(WORD ? 64 : 32) * S4) + (size_t)s * S4;
+	// (WIN: every group has its own slot of the HBM window, query stripes included)
+	constexpr bool SHARED_Q = (MODE == MODE_PRE || MODE == MODE_MAX1) && !WIN;
+	HT* Hs; HT* Es; uint8_t* Qs;
+	if constexpr (WIN) {
+		// slot = this group: [H: 16 sg HT][E: 16 sg HT][query: 16 sg bytes], rows interleaved per win_ix
+		uint8_t* base = a.window + (size_t)(blockIdx.x * (blockDim.x >> 4) + g) * a.slot_bytes;
+		const size_t rb = (size_t)16 * a.sg;
+		Hs = reinterpret_cast<HT*>(base) + 16 * s;
+		Es = reinterpret_cast<HT*>(base + rb * sizeof(HT)) + 16 * s;
+		Qs = base + 2 * rb * sizeof(HT) + 16 * s;
+	} else {
+		const size_t gbytes = (size_t)(SHARED_Q ? (WORD ? 64 : 32) : (WORD ? 80 : 48)) * S4;
+		uint8_t* base = lds + g * gbytes;
+		Hs = reinterpret_cast<HT*>(base) + (size_t)s * S4;
+		Es = reinterpret_cast<HT*>(base) + (size_t)16 * S4 + (size_t)s * S4;
+		Qs = (SHARED_Q ? lds + (blockDim.x >> 4) * gbytes : base + (size_t)(WORD ? 64 : 32) * S4) + (size_t)s * S4;
+	}
+	auto IX = [](int j) { return WIN ? win_ix(j) : j; };
 	const bool part = s < P;
 	const uint32_t l0 = a.lut.row[0], l1 = a.lut.row[1], l2 = a.lut.row[2], l3 = a.lut.row[3], l4 = a.lut.row[4];
 
@@ -275,13 +445,13 @@ __global__ void __launch_bounds__(256) k_striped(StripedArgs a)
 				const int row = s * segLen + j;
 				int code = CODE_PAD;                 // pad rows score 0 (sswNew.cpp:195, 690): Q3
 				if (part && row < qlen) code = a.qcodes[qrev ? (qlen - 1 - row) : row];
-				if (!SHARED_Q || g == 0 || !shared_q_built) Qs[j] = (uint8_t)(code * 4);
-				Hs[j] = 0;
-				Es[j] = 0;
+				if (!SHARED_Q || g == 0 || !shared_q_built) Qs[IX(j)] = (uint8_t)(code * 4);
+				Hs[IX(j)] = 0;
+				Es[IX(j)] = 0;
 				if constexpr (MODE == MODE_PRE && !WORD) {
 					if (st_init) {                       // resume from a checkpoint: the state after column t0 - 1
 						const uint16_t* sp = a.state + (size_t)(hz_base + hz_chunk) * 2 * a.state_rows;
-						Hs[j] = (HT)(sp[row] >> 1); Es[j] = (HT)(sp[a.state_rows + row] >> 1);
+						Hs[IX(j)] = (HT)(sp[row] >> 1); Es[IX(j)] = (HT)(sp[a.state_rows + row] >> 1);
 					}
 				}
 			}
@@ -302,8 +472,13 @@ __global__ void __launch_bounds__(256) k_striped(StripedArgs a)
 			const int t = __shfl(tchunk, ci & 15, 16);
 			const uint32_t lut = t == 0 ? l0 : t == 1 ? l1 : t == 2 ? l2 : t == 3 ? l3 : l4;
 			int cmax;
-			if constexpr (WORD) cmax = column_word(Hs, Es, Qs, segLen, lut, s, part);
-			else cmax = column_byte<QUIRK>(Hs, Es, Qs, segLen, lut, s);
+			if constexpr (WIN) {
+				if constexpr (WORD) cmax = column_word_win(Hs, Es, Qs, segLen, lut, s, part);
+				else cmax = column_byte_win<QUIRK>(Hs, Es, Qs, segLen, lut, s);
+			} else {
+				if constexpr (WORD) cmax = column_word(Hs, Es, Qs, segLen, lut, s, part);
+				else cmax = column_byte<QUIRK>(Hs, Es, Qs, segLen, lut, s);
+			}
 			const int colmax = group_max16(cmax);
 			if (colmax > maxv) {
 				maxv = colmax;
@@ -315,7 +490,7 @@ __global__ void __launch_bounds__(256) k_striped(StripedArgs a)
 						int best = 0x7fffffff;
 						if (part) {
 							for (int j = 0; j < segLen; j++) {
-								if ((int)Hs[j] == colmax) { best = s * segLen + j; break; }
+								if ((int)Hs[IX(j)] == colmax) { best = s * segLen + j; break; }
 							}
 						}
 						best = group_min16(best);
@@ -350,7 +525,7 @@ __global__ void __launch_bounds__(256) k_striped(StripedArgs a)
 							bool differs = false;
 							for (int j = 0; j < segLen; j++) {
 								const int row = s * segLen + j;
-								if ((sc[row] >> 1) != (uint16_t)Hs[j] || (sc[a.state_rows + row] >> 1) != (uint16_t)Es[j]) { differs = true; break; }
+								if ((sc[row] >> 1) != (uint16_t)Hs[IX(j)] || (sc[a.state_rows + row] >> 1) != (uint16_t)Es[IX(j)]) { differs = true; break; }
 							}
 							if (group_any16(differs)) {
 								// keep going: the deviation is alive.  (the target letters of the 16-column block in flight were
@@ -401,10 +576,68 @@ __global__ void __launch_bounds__(256) k_striped(StripedArgs a)
 	}
 }
 
+// HBM-window geometry: rows per stripe (padded to whole blocks of 16) and bytes of one problem slot
+static int striped_window_sg(bool word, int max_qlen) { const int P = word ? 8 : 16; return (((max_qlen + P - 1) / P) + 15) & ~15; }
+static size_t striped_window_slot(bool word, int max_qlen) { return (size_t)16 * striped_window_sg(word, max_qlen) * (word ? 5 : 3); }
+constexpr size_t STRIPED_WINDOW_BUDGET = (size_t)512 << 20;      // scratch of all slots together (a slot of a 92 k query: 277 / 922 KB)
+constexpr int STRIPED_WINDOW_MAX_SLOTS = 2048;                   // two waves of four problems per CU
+
+// groups (problems) per workgroup of the LDS-resident kernel, < 1 where one group's stripes do not fit the 160 KB of LDS
+static int striped_lds_groups(StripedMode mode, bool word, int max_qlen)
+{
+	const int P = word ? 8 : 16;
+	const int segLen = (max_qlen + P - 1) / P;
+	int s4 = (segLen + 3) & ~3;
+	if (((s4 / 4) & 1) == 0) s4 += 4;
+	const bool shared_q = (mode == MODE_PRE || mode == MODE_MAX1);
+	const size_t qbytes = (size_t)16 * s4;
+	const size_t gbytes = (size_t)(shared_q ? (word ? 64 : 32) : (word ? 80 : 48)) * s4;
+	const size_t avail = (size_t)160 * 1024 - (shared_q ? qbytes : 0);
+	return qbytes > (size_t)160 * 1024 ? 0 : (int)(avail / gbytes);
+}
+
+static int striped_window_slots(bool word, int max_qlen, int nprob)
+{
+	const size_t slot = striped_window_slot(word, max_qlen);
+	long cap = (long)(STRIPED_WINDOW_BUDGET / slot) & ~3L;
+	if (cap < 4) cap = 4;
+	if (cap > STRIPED_WINDOW_MAX_SLOTS) cap = STRIPED_WINDOW_MAX_SLOTS;
+	const long need = ((long)nprob + 3) & ~3L;
+	return (int)(need < cap ? need : cap);
+}
+
+size_t striped_window_bytes(StripedMode mode, bool word, int max_qlen, int nprob, bool force)
+{
+	if (nprob <= 0 || max_qlen <= 0) return 0;
+	if (mode == MODE_REV) word = false;
+	if (!force && striped_lds_groups(mode, word, max_qlen) >= 1) return 0;
+	return (size_t)striped_window_slots(word, max_qlen, nprob) * striped_window_slot(word, max_qlen);
+}
+
+// the HBM-window kernel: four problems per one-wave workgroup, one slot each; the grid is bounded by the slots, the work queue
+// hands out the problems
+template <int MODE, bool WORD, bool QUIRK>
+static hipError_t launch_striped_window_t(const StripedLaunch& L, hipStream_t st)
+{
+	const int slots = striped_window_slots(WORD, L.max_qlen, L.nprob);
+	const size_t slot = striped_window_slot(WORD, L.max_qlen);
+	if (!L.window || L.window_bytes < (size_t)slots * slot) return hipErrorInvalidValue;
+	hipError_t err = hipMemsetAsync(L.counter, 0, sizeof(uint32_t), st);
+	if (err != hipSuccess) return err;
+	StripedArgs a;
+	a.tcodes = L.tcodes; a.qcodes = L.qcodes; a.probs = L.probs; a.nprob = L.nprob; a.counter = L.counter;
+	a.lut = L.lut; a.s4 = 0; a.colmax = L.colmax; a.colmax_w = L.colmax_w; a.max_out = L.max_out; a.ends = L.ends;
+	a.state = L.state; a.state_rows = L.state_rows; a.chunk_cols = L.chunk_cols; a.chunk_base = L.chunk_base; a.chunk_rows = L.chunk_rows; a.row_stride = L.row_stride; a.chunk_out = L.chunk_out;
+	a.window = L.window; a.slot_bytes = (int64_t)slot; a.sg = striped_window_sg(WORD, L.max_qlen);
+	hipLaunchKernelGGL((k_striped<MODE, WORD, QUIRK, true>), dim3((unsigned)(slots / 4)), dim3(64), 0, st, a);
+	return hipGetLastError();
+}
+
 template <int MODE, bool WORD, bool QUIRK>
 static hipError_t launch_striped_t(const StripedLaunch& L, hipStream_t st)
 {
 	if (L.nprob <= 0) return hipSuccess;
+	if (L.window) return launch_striped_window_t<MODE, WORD, QUIRK>(L, st);
 	constexpr int P = WORD ? 8 : 16;
 	int segLen = (L.max_qlen + P - 1) / P;
 	int s4 = (segLen + 3) & ~3;
@@ -420,7 +653,7 @@ static hipError_t launch_striped_t(const StripedLaunch& L, hipStream_t st)
 	const int max_groups = 4;
 	if (L.spread) { if (groups > 16) groups = 16; }        // four waves of four problems: the whole CU (see below)
 	else if (groups > max_groups) groups = max_groups;
-	if (groups < 1) return hipErrorInvalidValue;           // query too long for the LDS-resident kernel
+	if (groups < 1 || (SHARED_Q && qbytes > (size_t)160 * 1024)) return hipErrorInvalidValue;   // query too long for the LDS-resident kernel
 	size_t shmem = (size_t)groups * gbytes + (SHARED_Q ? qbytes : 0);
 	// spread: a request of more than half the CU's LDS keeps the dispatcher from packing several of these workgroups onto one
 	// CU.  A wave of this kernel alone on its SIMD issues back to back; four of them on one SIMD take four times as long.
@@ -434,6 +667,7 @@ static hipError_t launch_striped_t(const StripedLaunch& L, hipStream_t st)
 	a.tcodes = L.tcodes; a.qcodes = L.qcodes; a.probs = L.probs; a.nprob = L.nprob; a.counter = L.counter;
 	a.lut = L.lut; a.s4 = s4; a.colmax = L.colmax; a.colmax_w = L.colmax_w; a.max_out = L.max_out; a.ends = L.ends;
 	a.state = L.state; a.state_rows = L.state_rows; a.chunk_cols = L.chunk_cols; a.chunk_base = L.chunk_base; a.chunk_rows = L.chunk_rows; a.row_stride = L.row_stride; a.chunk_out = L.chunk_out;
+	a.window = nullptr; a.slot_bytes = 0; a.sg = 0;
 	// enough one-wave workgroups to fill the chip at the LDS-limited occupancy; the queue balances the rest
 	int per_cu = (int)((160 * 1024) / shmem);
 	if (per_cu < 1) per_cu = 1;

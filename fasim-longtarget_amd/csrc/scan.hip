@@ -483,7 +483,8 @@ static hipError_t launch_scan_t(const ScanArgs& a, hipStream_t st)
 int systolic_vs(int m) { const int seg = (m + 15) / 16; return 8 * ((seg + 191) / 192); }
 int systolic_tiles(int m) { return systolic_vs(m) / 8; }
 int systolic_snap_dwords(int m) { const int seg = (m + 15) / 16, vs = systolic_vs(m); return 2 * ((seg + vs - 1) / vs) + 6; }
-bool systolic_fits(int m) { const int seg = (m + 15) / 16; return seg >= 8 && systolic_tiles(m) <= 16; }
+// (31 tiles hold FASIM_MAX_QUERY = 92 256 rows: seg 5 766, vs 248, RP 24)
+bool systolic_fits(int m) { const int seg = (m + 15) / 16; return seg >= 8 && systolic_tiles(m) <= SYSTOLIC_MAX_TILES; }
 
 hipError_t launch_scan(const ScanLaunch& L, hipStream_t st)
 {

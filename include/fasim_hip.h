@@ -25,6 +25,13 @@ extern "C" {
 #define FASIM_E_UNSUPPORTED -5  /* input hits behaviour the reference leaves undefined (see DESIGN) */
 #define FASIM_E_NOMEM      -6
 
+/* Longest query of the fastSIM entry points.  The reference has no length check; its stage-1 pass (calc_score_once,
+ * stats.h:879-956) runs the 16-bit kernel whenever the 8-bit score reaches 255, in the fixed workspace of init_work
+ * (stats.h:397): 3 * 16 * (MAXTST + MAXLIB + 32) = 553 536 bytes, of which a 16-bit pass uses 3 * ceil(m / 8) vectors of
+ * 16 bytes.  That holds m <= 92 256; above it the reference overruns its heap and its output is undefined, so longer
+ * queries get FASIM_E_UNSUPPORTED before any GPU work.  (-F, classic SIM, keeps its own limit of 65 534 nt.) */
+#define FASIM_MAX_QUERY 92256
+
 typedef struct fasim_engine fasim_engine;
 
 /* Defaults of initEnv() (Fasim-LongTarget.cpp:284-303); field meaning = struct para (fastsim.h:22-45). */
@@ -64,9 +71,10 @@ void fasim_engine_destroy(fasim_engine* e);
 const char* fasim_last_error(const fasim_engine* e);   /* e may be NULL: last global error */
 
 /* Tuning knobs (optional).  key "workers": batches kept in flight by fasim_scan (default 10, env FASIM_WORKERS);
- * key "seg_batch": segments per batch (default 384, env FASIM_SEG_BATCH); value <= 0 restores the default.
+ * key "seg_batch": segments per batch (default 384; a single-lncRNA scan of >= 128 segments per worker gets batches fitted to the
+ * record instead, at most 512 segments, -F 16 ... 128; env FASIM_SEG_BATCH); value <= 0 restores the default.
  * key "taper": percent of the segments scanned in half-size batches at the end (default: 25 for a single-lncRNA scan whose batches are fitted to the record, else 0);
- * key "heavy_gate": k_scan / k_align_fwd launches in flight at once (default 3, env FASIM_HEAVY_GATE; 0 = no gate);
+ * key "heavy_gate": k_scan / k_align_fwd launches in flight at once (default 4, env FASIM_HEAVY_GATE; 0 = no gate);
  * -1 restores the default of the last two.
  * key "host_threads": host threads for the host side of the batches, all workers of this engine together (default 3/8 of the
  * cores, at most 96, env FASIM_HOST_THREADS); several engines in one process should share the cores.
@@ -75,6 +83,8 @@ const char* fasim_last_error(const fasim_engine* e);   /* e may be NULL: last gl
  * sequential run per unit), checkpoint pass continued from pipeline snapshots of the main scan (0: from column 0; the snapshots
  * cost 64 KB of HBM writes per unit), cost target of a chunk in columns, price of a column whose maximum is >= 144
  * (env FASIM_HAZARD_CHUNKS, FASIM_HAZARD_SNAP).
+ * key "striped_window" (0): 1 runs every stripe-faithful (k_striped) launch on its HBM-window variant, which otherwise serves only
+ * the queries whose stripes do not fit the LDS (env FASIM_STRIPED_WINDOW; for tests: results do not depend on it).
  * key "numa_affinity" (1): for the duration of a scan the calling thread and the threads the scan starts are pinned to the CPUs of
  * the GPU's NUMA node (/sys/bus/pci/devices/<bus id>/local_cpulist); the caller's affinity is restored afterwards; no effect on a
  * single-node machine.
@@ -181,6 +191,8 @@ typedef struct fasim_scan_stats {
 	int64_t band_proven;                /* window tries whose band result was proven to be the full-height result */
 	int64_t band_cells;                 /* DP cells executed by k_align_band (part of cells_stage3) */
 	int64_t rev_bound_passes;           /* window tries that took the full-height reverse pass (bounds for the band passes) */
+	int64_t striped_window_probs;       /* problems run on the HBM-window variant of k_striped (query stripes too long for the LDS) */
+	double  striped_window_ms;          /* HIP-event time of those launches (also counted in kernel_ms[1] / kernel_ms[5]) */
 } fasim_scan_stats;
 
 struct fasim_result {
