@@ -157,3 +157,107 @@ def ref_batch(requests):
     req = ("\n".join(requests) + "\n").encode()
     out = subprocess.run([REF_PROBE, "batch"], input=req, check=True, stdout=subprocess.PIPE).stdout
     return out.decode().splitlines()
+
+
+def expected_triplexes(units):
+    """The X lines of parsed `scan` units as ScanResult.triplexes() tuples (identity / stability as float bits)."""
+    exp = []
+    for u in units:
+        for x in u["triplexes"]:
+            f = list(x)
+            exp.append((int(f[0]), int(f[1]), int(f[2]), int(f[3]), int(f[4]), int(f[5]), int(f[6]), int(f[7]), int(f[8]),
+                        int(f[9], 16), int(f[10], 16), f[11].encode(), f[12].encode(), u["seg"], u["enc"]))
+    return exp
+
+
+def fnv1a_rows(rows):
+    """fnv1a_ints of every row (the `colhash` of the scan protocol), vectorised over the rows with numpy."""
+    import numpy as np
+    lens = np.array([len(r) for r in rows], dtype=np.int64)
+    width = int(lens.max()) if len(rows) else 0
+    a = np.zeros((len(rows), width), dtype=np.uint64)
+    for i, r in enumerate(rows):
+        a[i, :len(r)] = np.asarray(r, dtype=np.int64).astype(np.uint32)
+    h = np.full(len(rows), 1469598103934665603, dtype=np.uint64)
+    prime, mask = np.uint64(1099511628211), np.uint64(0xFF)
+    for c in range(width):
+        live = lens > c
+        x, g = a[:, c], h
+        for b in range(4):
+            g = (g ^ ((x >> np.uint64(8 * b)) & mask)) * prime
+        h = np.where(live, g, h)
+    return [f"{int(v):016x}" for v in h]
+
+
+def unit_summary_digest(units):
+    """One record's units in scan order, each (enc, stage1, thr, colhash hex, ncand), folded with fnv1a_ints."""
+    vals = []
+    for enc, s1, thr, colhash, ncand in units:
+        ch = int(colhash, 16)
+        vals += [enc, s1, thr, ch & 0xFFFFFFFF, ch >> 32, ncand]
+    return fnv1a_ints(vals)
+
+
+def triplex_digest(trips):
+    """SHA-256 prefix of ScanResult.triplexes() tuples (or expected_triplexes() of a fixture), in order."""
+    import hashlib
+    h = hashlib.sha256()
+    for t in trips:
+        h.update(" ".join(x.decode() if isinstance(x, bytes) else str(x) for x in t).encode() + b"\n")
+    return h.hexdigest()[:16]
+
+
+def file_digest(data: bytes):
+    """(line count, SHA-256 prefix) of an output file, as the peaks manifests store them."""
+    import hashlib
+    return data.count(b"\n"), hashlib.sha256(data).hexdigest()[:16]
+
+
+# ---- the reference's 532 MEG3 ChIP peaks (tests/golden/meg3_peaks.fa.gz, `make_golden.py peaks`) ----------------------------
+PEAK_QUERIES = ("MEG3", "H19", "MALAT1")
+PEAK_FILES = ("TFOsorted", "TFOclass1", "TFOclass2")
+MANIFEST_COLUMNS = ("idx", "header", "length", "TFOsorted_lines", "TFOsorted_sha", "TFOclass1_lines", "TFOclass1_sha",
+                    "TFOclass2_lines", "TFOclass2_sha", "units", "triplexes", "triplex_sha", "q1", "rev148", "q2")
+
+
+def read_peaks(path=None):
+    """[(header, sequence)] of the peaks file (one sequence line per record)."""
+    text = gunzip(path or os.path.join(GOLD, "meg3_peaks.fa.gz"))
+    recs, hdr = [], None
+    for line in text.split(b"\n"):
+        if line.startswith(b">"):
+            hdr = line[1:].decode()
+        elif line:
+            recs.append((hdr, line))
+    return recs
+
+
+def read_manifest(path):
+    """peaks_<query>.manifest.gz -> one dict per record (q2 is None where it was not counted)."""
+    out = []
+    for line in gunzip(path).decode().splitlines():
+        if line.startswith("#"):
+            continue
+        f = line.split("\t")
+        d = dict(zip(MANIFEST_COLUMNS, f))
+        for k in MANIFEST_COLUMNS:
+            if k not in ("header", "units", "triplex_sha") and not k.endswith("_sha"):
+                d[k] = None if d[k] == "-" else int(d[k])
+        out.append(d)
+    return out
+
+
+def split_sections(text: bytes):
+    """The `= <idx> <kind> <nbytes>` sections of a peaks detail file -> {(idx, kind): bytes}."""
+    out, pos = {}, 0
+    while pos < len(text):
+        eol = text.index(b"\n", pos)
+        _, idx, kind, nbytes = text[pos:eol].decode().split(" ")
+        out[(int(idx), kind)] = text[eol + 1:eol + 1 + int(nbytes)]
+        pos = eol + 1 + int(nbytes)
+    return out
+
+
+def join_sections(items):
+    """Inverse of split_sections: [(idx, kind, bytes)] -> one text."""
+    return b"".join(f"= {idx} {kind} {len(data)}\n".encode() + data for idx, kind, data in items)

@@ -49,16 +49,6 @@ def long_scans(mod, engine, golden_dir, long_dna):
     return out
 
 
-def _expected_triplexes(units):
-    exp = []
-    for u in units:
-        for x in u["triplexes"]:
-            f = list(x)
-            exp.append((int(f[0]), int(f[1]), int(f[2]), int(f[3]), int(f[4]), int(f[5]), int(f[6]), int(f[7]), int(f[8]),
-                        int(f[9], 16), int(f[10], 16), f[11].encode(), f[12].encode(), u["seg"], u["enc"]))
-    return exp
-
-
 def _gold(golden_dir, name):
     return open(os.path.join(golden_dir, name), "rb").read()
 
@@ -77,7 +67,7 @@ def test_long_query_matches_reference(mod, engine, golden_dir, long_dna, long_sc
     res = long_scans[name]
     assert res.stats["units"] == len(units)
     assert res.stats["candidates"] == sum(u["ncand"] for u in units)
-    assert res.triplexes() == _expected_triplexes(units)
+    assert res.triplexes() == helpers.expected_triplexes(units)
     assert res.stats["kernel_launches"][0] > 0, "the systolic scan kernel must have run"
     assert res.stats["band_tries"] > 0, "stage 3 must have used row bands"
     if name == "longq92k":

@@ -87,16 +87,6 @@ def test_single_call_dropins(engine, h19, oracle_build):
     assert (a.sw_score, a.ref_begin, a.ref_end, a.query_begin, a.query_end) == five and a.cigar_string() == cig
 
 
-def _expected_triplexes(units):
-    exp = []
-    for u in units:
-        for x in u["triplexes"]:
-            f = list(x)
-            exp.append((int(f[0]), int(f[1]), int(f[2]), int(f[3]), int(f[4]), int(f[5]), int(f[6]), int(f[7]), int(f[8]),
-                        int(f[9], 16), int(f[10], 16), f[11].encode(), f[12].encode(), u["seg"], u["enc"]))
-    return exp
-
-
 @pytest.mark.parametrize("scan_name,dna_name", [("demo.scan.gz", "testDNA.fa"), ("planted40k.scan.gz", "planted40k.fa")])
 def test_scan_records_match_reference_fastsim(mod, engine, h19, golden_dir, scan_name, dna_name):
     """Every triplex the reference's fastSIM() emits, unit by unit, bit for bit (identity/stability as float bits)."""
@@ -104,7 +94,7 @@ def test_scan_records_match_reference_fastsim(mod, engine, h19, golden_dir, scan
     _, units = helpers.parse_scan(helpers.gunzip(os.path.join(golden_dir, scan_name)))
     engine.set_query(h19)
     res = engine.scan(dna, mod.default_params(cLength=20))     # cLength == ntMin: LongTarget's tail filter == fastSIM's
-    assert res.triplexes() == _expected_triplexes(units)
+    assert res.triplexes() == helpers.expected_triplexes(units)
     assert res.stats["units"] == len(units)
     assert res.stats["candidates"] == sum(u["ncand"] for u in units)
 
@@ -137,7 +127,7 @@ def test_q2_units_scan(mod, engine, h19, golden_dir, oracle_build):
     engine.set_query(h19)
     res = engine.scan(dna, mod.default_params(cLength=20, overlapLength=0))
     assert res.stats["candidates"] == sum(u["ncand"] for u in units)
-    assert res.triplexes() == _expected_triplexes(units)
+    assert res.triplexes() == helpers.expected_triplexes(units)
     # every unit whose above-threshold columns really differ between the reference's signed exit and the textbook
     # recurrence must have been sent to the stripe-faithful kernel (differences below the threshold or behind the
     # overflow cut cannot matter, and the taint tracking of k_scan is allowed to ignore them)
@@ -209,7 +199,7 @@ def test_long_queries_scan(mod, engine, golden_dir, name):
     res = engine.scan(dna, mod.default_params(cLength=20))
     assert res.stats["units"] == len(units)
     assert res.stats["candidates"] == sum(u["ncand"] for u in units)
-    assert res.triplexes() == _expected_triplexes(units)
+    assert res.triplexes() == helpers.expected_triplexes(units)
     assert res.stats["kernel_launches"][0] > 0, "the systolic scan kernel must have run"
     p = mod.default_params(cLength=40)
     res = engine.scan(dna, p)
@@ -226,7 +216,7 @@ def test_untidy_input_scan(mod, engine, h19, golden_dir):
     assert res.stats["segments_skipped"] == len(meta["skipped"]) > 0
     assert res.stats["units"] == len(units)
     assert res.stats["candidates"] == sum(u["ncand"] for u in units)
-    assert res.triplexes() == _expected_triplexes(units)
+    assert res.triplexes() == helpers.expected_triplexes(units)
     assert res.stats["stage1_word_reruns"] > 0, "units with N must have taken the separate stage-1 pass"
     p = mod.default_params(cLength=30)
     res = engine.scan(dna, p)
@@ -245,7 +235,7 @@ def test_short_queries_scan(mod, golden_dir, name, systolic):
     e.set_query(rna)
     res = e.scan(dna, mod.default_params(cLength=20))
     assert res.stats["candidates"] == sum(u["ncand"] for u in units)
-    assert res.triplexes() == _expected_triplexes(units)
+    assert res.triplexes() == helpers.expected_triplexes(units)
     if systolic:
         assert res.stats["kernel_launches"][0] > 0
     p = mod.default_params(cLength=25)
@@ -268,7 +258,7 @@ def test_stage1_score_saturating_the_doubled_lanes(mod, golden_dir):
     e.set_query(rna)
     res = e.scan(dna, mod.default_params(cLength=20))
     assert res.stats["candidates"] == sum(u["ncand"] for u in units)
-    assert res.triplexes() == _expected_triplexes(units)
+    assert res.triplexes() == helpers.expected_triplexes(units)
     assert res.stats["stage1_word_reruns"] >= 1 and res.stats["kernel_launches"][0] > 0
     t, _ = mod.encode_unit(dna, max(units, key=lambda u: u["stage1"])["enc"])
     assert e.calc_score_once(t) == max(u["stage1"] for u in units)
@@ -433,7 +423,7 @@ def test_live_reference_10kb_query_ntmax(mod, engine, golden_dir, tmp_path):
     engine.set_query(rna)
     res = engine.scan(dna, mod.default_params(cLength=20, ntMax=1000))
     assert res.stats["candidates"] == sum(u["ncand"] for u in units)
-    assert res.triplexes() == _expected_triplexes(units)
+    assert res.triplexes() == helpers.expected_triplexes(units)
     assert sum(u["stage1"] >= 251 for u in units) > 0, "the case must exercise byte overflow"
 
 

@@ -181,3 +181,72 @@ def test_classic_sim_cli_files_identical(oracle_build, golden_dir):
     assert out == open(os.path.join(golden_dir, "demoF_lg40.TFOsorted"), "rb").read()
     out = helpers.oracle_cli(oracle_build, "tfoclass", rna, dna, "-lg", "40", "-F", "1", "-level", "1", "-threads", "8")
     assert out == open(os.path.join(golden_dir, "demoF_lg40.TFOclass1"), "rb").read()
+
+
+# ---- the reference's real DNA: 532 MEG3 ChIP peaks x MEG3 / H19 / MALAT1 (`make_golden.py peaks`) ---------------------------
+@pytest.fixture(scope="module")
+def peaks(golden_dir):
+    return helpers.read_peaks(os.path.join(golden_dir, "meg3_peaks.fa.gz"))
+
+
+def _peak_detail(golden_dir, query):
+    scans = helpers.split_sections(helpers.gunzip(os.path.join(golden_dir, f"peaks_{query}.detail.scan.gz")))
+    files = helpers.split_sections(helpers.gunzip(os.path.join(golden_dir, f"peaks_{query}.detail.files.gz")))
+    return {i: s for (i, _), s in scans.items()}, files
+
+
+@pytest.mark.parametrize("query", helpers.PEAK_QUERIES)
+def test_peaks_manifest_and_detail_digests(golden_dir, peaks, query):
+    """The manifest has one line per record of the reference's DNA file (headers and lengths as stored), and the selected
+    records stored in full hash to the manifest's digests: line counts and SHA-256 of the three CLI files, unit summary,
+    triplex count and digest, Q1 and 148-250 counts."""
+    man = helpers.read_manifest(os.path.join(golden_dir, f"peaks_{query}.manifest.gz"))
+    assert len(peaks) == 532 and [r["idx"] for r in man] == list(range(532))
+    assert [(r["header"], r["length"]) for r in man] == [(h, len(s)) for h, s in peaks]
+    assert all(set(s) <= set(b"ACGT") for _, s in peaks)
+    scans, files = _peak_detail(golden_dir, query)
+    assert len(scans) >= 12 and sorted({i for i, _ in files}) == sorted(scans)
+    for i, scan in scans.items():
+        r = man[i]
+        where = f"record {i} ({r['header']})"
+        for kind in helpers.PEAK_FILES:
+            assert helpers.file_digest(files[(i, kind)]) == (r[kind + "_lines"], r[kind + "_sha"]), (where, kind)
+        meta, units = helpers.parse_scan(scan)
+        assert meta["nseg"] == 1 and [u["enc"] for u in units] == list(range(48)), where
+        summary = [(u["enc"], u["stage1"], u["thr"], u["colhash"], u["ncand"]) for u in units]
+        assert helpers.unit_summary_digest(summary) == r["units"], where
+        trips = helpers.expected_triplexes(units)
+        assert (len(trips), helpers.triplex_digest(trips)) == (r["triplexes"], r["triplex_sha"]), where
+        assert sum(u["stage1"] >= 251 for u in units) == r["q1"], where
+        assert sum(148 <= u["stage1"] <= 250 for u in units) == r["rev148"], where
+    # the selection holds the extremes it is meant to cover
+    for key in ("triplexes", "q1", "length"):
+        assert max(r[key] for r in man) == max(man[i][key] for i in scans), key
+    assert min(r["length"] for r in man) == min(man[i]["length"] for i in scans)
+
+
+@pytest.mark.parametrize("query", ["H19", "MALAT1"])
+def test_peaks_fixture_covers_overflow_and_q2(golden_dir, query):
+    """With H19 and MALAT1, real DNA drives units through byte overflow (Q1), the exact-reverse range and the signed
+    lazy-F exit (Q2); a regenerated fixture must keep doing so."""
+    man = helpers.read_manifest(os.path.join(golden_dir, f"peaks_{query}.manifest.gz"))
+    assert sum(r["q1"] for r in man) > 0
+    assert sum(r["rev148"] for r in man) > 0
+    assert sum(r["q2"] for r in man) > 0
+
+
+@pytest.mark.parametrize("query", helpers.PEAK_QUERIES)
+def test_oracle_on_selected_peaks(oracle_build, golden_dir, peaks, tmp_path, query):
+    """The oracle's scan and its three CLI files equal the reference's, byte for byte, for every selected peak record."""
+    rna = os.path.join(golden_dir, query + ".fa")
+    scans, files = _peak_detail(golden_dir, query)
+    for i, scan in scans.items():
+        hdr, seq = peaks[i]
+        where = f"record {i} ({hdr})"
+        dna = str(tmp_path / f"pk{i}.fa")
+        synth.write_fasta(dna, hdr, seq)
+        assert helpers.oracle_cli(oracle_build, "scan", rna, dna, "-detail", "0", "-threads", "8") == scan, where
+        assert helpers.oracle_cli(oracle_build, "tfosorted", rna, dna, "-threads", "8") == files[(i, "TFOsorted")], where
+        for level in (1, 2):
+            out = helpers.oracle_cli(oracle_build, "tfoclass", rna, dna, "-level", str(level), "-threads", "8")
+            assert out == files[(i, f"TFOclass{level}")], (where, level)
