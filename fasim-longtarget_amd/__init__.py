@@ -29,7 +29,15 @@ LIB_PATH = os.path.join(_HERE, "libfasim_hip.so")
 
 
 class FasimError(RuntimeError):
-    pass
+    """`code` is the FASIM_E_* value of the failing call (None where the binding itself raised)."""
+
+    def __init__(self, msg="", code=None):
+        super().__init__(msg)
+        self.code = code
+
+
+E_ARG = -2              # FASIM_E_ARG
+E_UNSUPPORTED = -5      # FASIM_E_UNSUPPORTED
 
 
 class Params(C.Structure):
@@ -88,7 +96,7 @@ class _Result(C.Structure):
 
 EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_ex", "fasim_engine_destroy", "fasim_last_error", "fasim_set_option", "fasim_set_query",
            "fasim_calc_score_once", "fasim_ssw_pre_align", "fasim_ssw_colmax_word", "fasim_pick_candidates", "fasim_ssw_align", "fasim_pre_align_batch",
-           "fasim_align_batch", "fasim_encode_unit", "fasim_sim_forward_batch", "fasim_sim_finish_unit", "fasim_scan", "fasim_scan_queries", "fasim_merge_results", "fasim_rebase_offsets", "fasim_load_dna", "fasim_result_free", "fasim_segment_count",
+           "fasim_align_batch", "fasim_encode_unit", "fasim_sim_forward_batch", "fasim_sim_finish_unit", "fasim_scan", "fasim_scan_queries", "fasim_scan_records", "fasim_merge_results", "fasim_rebase_offsets", "fasim_load_dna", "fasim_result_free", "fasim_segment_count",
            "fasim_tfosorted", "fasim_tfoclass", "fasim_tfosorted_ex", "fasim_tfoclass_ex", "fasim_tail_outputs", "fasim_upper_case", "fasim_free",
            "fasim_synth_dna", "fasim_selfcheck_records",
            # the reference's own ssw.h ABI (include/ssw.h)
@@ -134,6 +142,9 @@ def lib():
     L.fasim_load_dna.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
     L.fasim_scan_queries.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p, C.c_int64,
                                      C.c_int64, C.c_int64, C.POINTER(Params), C.POINTER(C.POINTER(_Result))]
+    L.fasim_scan_records.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
+                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int64, C.c_int64, C.POINTER(Params),
+                                     C.POINTER(C.POINTER(_Result)), C.POINTER(ScanStats)]
     L.fasim_merge_results.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                                       C.c_int32, C.POINTER(C.POINTER(_Result))]
     L.fasim_rebase_offsets.argtypes = [C.c_void_p, C.c_int64, C.c_int64]
@@ -383,7 +394,7 @@ class Engine:
 
     def _check(self, rc):
         if rc != 0:
-            raise FasimError(f"libfasim_hip error {rc}: {self._L.fasim_last_error(self._h).decode()}")
+            raise FasimError(f"libfasim_hip error {rc}: {self._L.fasim_last_error(self._h).decode()}", rc)
 
     def set_option(self, key: str, value: int):
         self._check(self._L.fasim_set_option(self._h, key.encode(), value))
@@ -484,6 +495,43 @@ class Engine:
                                                seg_count, C.byref(p), outs))
         self.m = len(rnas[-1])
         return [ScanResult(stats=self._stats_dict(outs[k].contents.stats), _native=outs[k]) for k in range(n)]
+
+    def scan_records(self, dnas, params: Params | None = None, rnas=None, seg_first: int = 0, seg_count: int = -1, rec_lens=None):
+        """Record set (fasim_scan_records): many DNA records (peaks, promoter windows) scanned in shared batches.
+        `dnas`: list of bytes, one per record; None together with `rec_lens` scans the buffer made resident by load_dna() of the
+        records' concatenation.  Segments are numbered globally, record after record; seg_first / seg_count select a range.
+        rnas None: one ScanResult per record, each identical to scan() of that record alone (the engine's query).  Otherwise a
+        list per lncRNA of per-record lists, like scan_queries().  The call's totals (one stats dict per query) are left in
+        `self.last_totals`."""
+        p = params or default_params()
+        if dnas is None:
+            if rec_lens is None:
+                raise FasimError("scan_records(None, ...) needs rec_lens (the records of the resident buffer)", E_ARG)
+            lens_l, blob = [int(x) for x in rec_lens], None
+        else:
+            lens_l = [len(d) for d in dnas]
+            blob = b"".join(dnas)
+        nrec = len(lens_l)
+        offs = (C.c_int64 * max(1, nrec))()
+        lens = (C.c_int64 * max(1, nrec))()
+        o = 0
+        for i, n in enumerate(lens_l):
+            offs[i], lens[i] = o, n
+            o += n
+        nq = 0 if rnas is None else len(rnas)
+        arr = (C.c_char_p * max(1, nq))(*(rnas or []))
+        qlens = (C.c_int32 * max(1, nq))(*[len(r) for r in (rnas or [])])
+        nqo = max(1, nq)
+        outs = (C.POINTER(_Result) * (nqo * max(1, nrec)))()
+        totals = (ScanStats * nqo)()
+        self._check(self._L.fasim_scan_records(self._h, arr, qlens, nq, blob, offs, lens, nrec, seg_first, seg_count, C.byref(p),
+                                               outs, totals))
+        if nq:
+            self.m = len(rnas[-1])
+        self.last_totals = [self._stats_dict(totals[q]) for q in range(nqo)]
+        res = [[ScanResult(stats=self._stats_dict(outs[q * nrec + r].contents.stats), _native=outs[q * nrec + r]) for r in range(nrec)]
+               for q in range(nqo)]
+        return res[0] if rnas is None else res
 
 
 def sim_finish_unit(rna: bytes, seg: bytes, enc: int, dna_start: int, min_score: int, nodes, params: Params | None = None) -> "ScanResult":

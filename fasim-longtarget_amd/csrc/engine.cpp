@@ -377,7 +377,7 @@ int fasim_load_dna(fasim_engine* E, const char* dna, int64_t dna_len)
 {
 	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
 	if (!dna || dna_len <= 0) return fail(E, FASIM_E_ARG, "empty DNA");
-	if (dna_len > 0x7fffffffll) return fail(E, FASIM_E_ARG, "one record is limited to 2^31-1 nt");
+	// (a resident record set may be longer than 2^31 nt: fasim_scan refuses a single record above it, fasim_scan_records a record)
 	HIPOK(hipSetDevice(E->device));
 	E->dna_host.assign(dna, dna + dna_len);
 	int rc = upload(E, E->dna_res, dna, (size_t)dna_len);
@@ -430,6 +430,36 @@ int fasim_scan_queries(fasim_engine* E, const char* const* rnas, const int32_t* 
 	if (nq <= 0 || !rnas || !rna_lens || !outs) return fail(E, FASIM_E_ARG, "bad arguments");
 	for (int32_t q = 0; q < nq; q++) if (rna_lens[q] > FASIM_MAX_QUERY) return refuse_long_query(E, rna_lens[q], q);
 	return scan_core(E, rnas, rna_lens, nq, dna, dna_len, seg_first, seg_count, pp, outs);
+}
+
+int fasim_scan_records(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
+	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
+	fasim_result** outs, fasim_scan_stats* totals)
+{
+	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
+	if (nrec < 1) return fail(E, FASIM_E_ARG, "a record set needs at least one record (nrec = %d)", nrec);
+	if (!rec_off || !rec_len || !pp || !outs || nq < 0) return fail(E, FASIM_E_ARG, "bad arguments");
+	if (pp->cutLength <= 0 || pp->cutLength - pp->overlapLength <= 0) return fail(E, FASIM_E_ARG, "cutLength/overlapLength invalid");
+	if (nq == 0) { int rc = need_query(E); if (rc) return rc; }
+	else {
+		if (!rnas || !rna_lens) return fail(E, FASIM_E_ARG, "bad arguments");
+		for (int32_t q = 0; q < nq; q++) {
+			if (!rnas[q] || rna_lens[q] <= 0) return fail(E, FASIM_E_ARG, "empty query %d", q);
+			if (rna_lens[q] > FASIM_MAX_QUERY) return refuse_long_query(E, rna_lens[q], q);
+		}
+	}
+	// a host buffer has no length here: only the resident buffer bounds the offsets from above
+	const bool resident = dna == nullptr;
+	if (resident && E->dna_host.empty()) return fail(E, FASIM_E_ARG, "no resident DNA: call fasim_load_dna first");
+	const int64_t have = resident ? (int64_t)E->dna_host.size() : INT64_MAX;
+	for (int32_t r = 0; r < nrec; r++) {
+		if (rec_len[r] == 0) return fail(E, FASIM_E_ARG, "record %d is empty", r);
+		if (rec_off[r] < 0 || rec_len[r] < 0 || rec_off[r] > have || rec_len[r] > have - rec_off[r])
+			return fail(E, FASIM_E_ARG, "record %d: offset %lld, length %lld lies outside the DNA buffer%s", r, (long long)rec_off[r],
+				(long long)rec_len[r], resident ? " (the resident buffer of fasim_load_dna)" : "");
+		if (rec_len[r] > 0x7fffffffll) return fail(E, FASIM_E_ARG, "record %d: one record is limited to 2^31-1 nt (the reference's int positions)", r);
+	}
+	return scan_records_core(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, outs, totals);
 }
 
 // in-place variant for a gather that already placed every shard's records and pool at their final positions

@@ -359,11 +359,23 @@ inline bool hazard_snapshots_enabled(const fasim_engine* E) { static const bool 
 // What one batch leaves after its scan phase (stages 1+2) and what its stage 3 needs: host-side hit lists and segment
 // tables, plus a pointer to the target codes that stay resident on the owner engine.  Stage 3 is separable by unit range
 // (stage3_range), so near the end of a scan a batch publishes its stage 3 as sub-tasks that idle workers take over.
+// Segments of one scan call, numbered globally record after record (a single-record scan is the one-record case).  Entry k
+// is the k-th segment of the call's selected range: its record, its index within the record, its offset in the call's DNA
+// buffer and its length.
+struct SegTable {
+	std::vector<int32_t> rec, len;
+	std::vector<int64_t> idx, off;
+	int64_t size() const { return (int64_t)rec.size(); }
+};
+
 struct BatchCtx {
 	UnitBatch B;
 	int tstride = 0, nenc = 0, nseg = 0;
 	int64_t step = 0;
-	std::vector<int32_t> sstart, slen; std::vector<int64_t> sidx;
+	// per kept segment of the batch: device start (relative to the batch's DNA on the device), length, index within its record
+	// (dna_start = sidx * step, triplex `seg`), offset in the host DNA buffer, record
+	std::vector<int32_t> sstart, slen; std::vector<int64_t> sidx, soff; std::vector<int32_t> srec;
+	std::vector<int32_t> ucand, ualign;                 // per unit: candidates and window tries of stage 3 (per-record stats)
 	std::vector<int32_t> hoff, hcnt, thr; std::vector<uint32_t> hits;
 	std::vector<char> seg_acgtn;
 	const char* dna = nullptr; const fasim_params* p = nullptr; const std::vector<int>* encs = nullptr;
@@ -389,7 +401,7 @@ int need_query(fasim_engine* E);
 int run_align(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb>& W, std::vector<AlignResult>& out, std::vector<uint32_t>& cigars, fasim_scan_stats* stats);
 int run_align_v2(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb>& W, std::vector<AlignResult>& out, std::vector<uint32_t>& cigars, fasim_scan_stats* stats);
 int stage3_range(fasim_engine* E, BatchCtx& C, int ua, int ub, fasim_scan_stats& st);
-int scan_batch(fasim_engine* E, const char* dna, int64_t dna_len, const uint8_t* dna_dev, int64_t shard_lo, int64_t b0, int64_t b1,
+int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_t* dna_dev, int64_t b0, int64_t b1,
 	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st);
 int sim_forward_units(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, const int32_t* unit_len_dev, const int32_t* unit_len_host,
 	int first, int nunit, const int64_t* mins, std::atomic<int>* ready, std::vector<std::vector<fasim_sim_node>>& lists);
@@ -398,3 +410,8 @@ int sim_resweep_rounds(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, 
 int pack_result(fasim_engine* E, std::vector<HostTriplex>& all, const fasim_scan_stats& st, fasim_result** out);
 int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna, int64_t dna_len,
 	int64_t seg_first, int64_t seg_count, const fasim_params* pp, fasim_result** outs);
+// fasim_scan_records after its argument checks: records [rec_off[r], rec_off[r] + rec_len[r]) of `dna` (NULL: the resident
+// buffer); outs[q * nrec + r], totals[q] (may be NULL)
+int scan_records_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna,
+	const int64_t* rec_off, const int64_t* rec_len, int nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
+	fasim_result** outs, fasim_scan_stats* totals);

@@ -249,40 +249,67 @@ int sim_resweep_rounds(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, 
 }
 
 
-int scan_batch(fasim_engine* E, const char* dna, int64_t dna_len, const uint8_t* dna_dev, int64_t shard_lo, int64_t b0, int64_t b1,
+// Segments [b0, b1) of the call's segment table on one worker.  `dna_dev`: the resident buffer (fasim_load_dna), or NULL for a
+// host buffer.  The kernels take int32 segment starts relative to the batch's own first byte on the device, so a record set
+// longer than 2^31 nt works as long as one batch's span does.
+int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_t* dna_dev, int64_t b0, int64_t b1,
 	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st)
 {
 	int rc = FASIM_OK;
 	const int64_t step = p.cutLength - p.overlapLength;
 	const int nenc = (int)encs.size();
 	C.B = UnitBatch(); C.tstride = tstride; C.nenc = nenc; C.nseg = 0; C.step = step; C.dna = dna; C.p = &p; C.encs = &encs; C.stage3_done = false;
-	C.per_unit.clear();
+	C.per_unit.clear(); C.ucand.clear(); C.ualign.clear();
 	{
 		// segments of this batch that are not skipped by same_seq()
 		std::vector<int32_t>& sstart = C.sstart; std::vector<int32_t>& slen = C.slen; std::vector<int64_t>& sidx = C.sidx;
-		sstart.clear(); slen.clear(); sidx.clear();
-		if (!dna_dev) {
+		sstart.clear(); slen.clear(); sidx.clear(); C.soff.clear(); C.srec.clear();
+		int64_t lo = INT64_MAX, hi = 0;
+		for (int64_t s = b0; s < b1; s++) { lo = std::min(lo, T.off[(size_t)s]); hi = std::max(hi, T.off[(size_t)s] + T.len[(size_t)s]); }
+		std::vector<int64_t> dpos((size_t)(b1 - b0));       // device start of every segment, relative to the batch's DNA on the device
+		if (dna_dev && hi - lo <= 0x7fffffffll) {
+			dna_dev += lo;
+			for (int64_t s = b0; s < b1; s++) dpos[(size_t)(s - b0)] = T.off[(size_t)s] - lo;
+		} else {
 			// Streaming ingest: the record is in host memory only.  The slice this batch needs goes through the worker's
 			// pinned staging buffer and its own stream; with ~10 batches in flight the copy of one batch overlaps the kernels
-			// of the others, and HBM holds 10 slices of ~2.5 MB instead of the whole record.
-			const int64_t lo = b0 * step, hi = std::min<int64_t>(dna_len, (b1 - 1) * step + p.cutLength);
-			const size_t bytes = (size_t)(hi - lo);
+			// of the others, and HBM holds 10 slices of ~2.5 MB instead of the whole record.  The consecutive segments of one
+			// record are one run of `dna` and are copied once; the runs of a batch that crosses records are packed side by side
+			// (a single-record batch is one run).  A resident set whose batch spans more than 2^31 nt is staged the same way.
+			size_t bytes = 0;
+			for (int64_t s = b0; s < b1; ) {
+				int64_t e = s + 1;
+				while (e < b1 && T.rec[(size_t)e] == T.rec[(size_t)s]) e++;
+				bytes += (size_t)(T.off[(size_t)e - 1] + T.len[(size_t)e - 1] - T.off[(size_t)s]);
+				s = e;
+			}
+			if (bytes > 0x7fffffffull) return fail(E, FASIM_E_UNSUPPORTED, "a batch of %lld segments spans %zu nt: more than the kernels' int32 segment starts hold", (long long)(b1 - b0), bytes);
 			if (bytes > E->pin_cap) {
 				if (E->pin_dna) { (void)hipHostFree(E->pin_dna); E->pin_dna = nullptr; E->pin_cap = 0; }
 				HIPOK(hipHostMalloc(&E->pin_dna, bytes + bytes / 8, hipHostMallocDefault));
 				E->pin_cap = bytes + bytes / 8;
 			}
-			memcpy(E->pin_dna, dna + lo, bytes);
+			size_t at = 0;
+			for (int64_t s = b0; s < b1; ) {
+				int64_t e = s + 1;
+				while (e < b1 && T.rec[(size_t)e] == T.rec[(size_t)s]) e++;
+				const int64_t rlo = T.off[(size_t)s], rhi = T.off[(size_t)e - 1] + T.len[(size_t)e - 1];
+				memcpy((char*)E->pin_dna + at, dna + rlo, (size_t)(rhi - rlo));
+				for (int64_t k = s; k < e; k++) dpos[(size_t)(k - b0)] = (int64_t)at + (T.off[(size_t)k] - rlo);
+				at += (size_t)(rhi - rlo);
+				s = e;
+			}
 			HIPOK(E->dna.ensure(bytes));
 			HIPOK(hipMemcpyAsync(E->dna.p, E->pin_dna, bytes, hipMemcpyHostToDevice, E->st));
-			dna_dev = E->dna.as<uint8_t>(); shard_lo = lo;
+			dna_dev = E->dna.as<uint8_t>();
 		}
 		for (int64_t s = b0; s < b1; s++) {
-			const int64_t pos = s * step;
-			const int len = (int)std::min<int64_t>(p.cutLength, dna_len - pos);
+			const int64_t pos = T.off[(size_t)s];
+			const int len = T.len[(size_t)s];
 			st.segments++;
 			if (same_seq(dna + pos, len)) { st.segments_skipped++; continue; }
-			sstart.push_back((int32_t)(pos - shard_lo)); slen.push_back(len); sidx.push_back(s);
+			sstart.push_back((int32_t)dpos[(size_t)(s - b0)]); slen.push_back(len); sidx.push_back(T.idx[(size_t)s]);
+			C.soff.push_back(pos); C.srec.push_back(T.rec[(size_t)s]);
 			st.logical_cells += (int64_t)E->m * len * nenc;
 		}
 		const int nseg = (int)sidx.size();
@@ -291,6 +318,7 @@ int scan_batch(fasim_engine* E, const char* dna, int64_t dna_len, const uint8_t*
 		UnitBatch& B = C.B; B.nunit = nseg * nenc; B.tstride = tstride; B.unit_len.resize(B.nunit);
 		for (int s = 0; s < nseg; s++) for (int k = 0; k < nenc; k++) B.unit_len[s * nenc + k] = slen[s];
 		st.units += B.nunit;
+		C.ucand.assign((size_t)B.nunit, 0); C.ualign.assign((size_t)B.nunit, 0);
 		// executed DP cells: the fused k_scan pass serves stage 1 AND stage 2, so it is counted once (as stage 2); stage 1 is
 		// counted only where it really is a pass of its own (units with N / non-ACGT queries, the striped fallback)
 		for (int s = 0; s < nseg; s++) st.cells_stage2 += (int64_t)E->m * slen[s] * nenc;
@@ -315,7 +343,7 @@ int scan_batch(fasim_engine* E, const char* dna, int64_t dna_len, const uint8_t*
 			std::vector<char> need1(B.nunit, E->query_acgt ? 0 : 1);
 			if (E->query_acgt) {
 				for (int s = 0; s < nseg; s++) {
-					const char* sg = dna + sidx[s] * step; bool clean = true;
+					const char* sg = dna + C.soff[(size_t)s]; bool clean = true;
 					for (int i = 0; i < slen[s]; i++) { const char c = sg[i]; if (!(c == 'A' || c == 'C' || c == 'G' || c == 'T')) { clean = false; break; } }
 					if (!clean) for (int k = 0; k < nenc; k++) need1[s * nenc + k] = 1;
 				}
@@ -381,7 +409,7 @@ int scan_batch(fasim_engine* E, const char* dna, int64_t dna_len, const uint8_t*
 			parallel_units(B.nunit, E->sim_threads, [&](int u) {
 				std::string target, src;
 				const int s = u / nenc, enc = encs[(size_t)(u % nenc)];
-				encode_unit_host(dna + sidx[(size_t)s] * step, slen[(size_t)s], enc, target, src);
+				encode_unit_host(dna + C.soff[(size_t)s], slen[(size_t)s], enc, target, src);
 				units[(size_t)u].reset(new SimUnit(E->rna, target, src, (long)(sidx[(size_t)s] * step), thr[(size_t)u], enc, p, std::move(lists[(size_t)u])));
 			});
 			std::vector<SimUnit*> up((size_t)B.nunit);
@@ -400,20 +428,51 @@ int scan_batch(fasim_engine* E, const char* dna, int64_t dna_len, const uint8_t*
 		// the scan phase ends here: stage 3 runs per unit range (stage3_range), on this engine or on helpers
 		C.per_unit.assign((size_t)B.nunit, std::vector<HostTriplex>());
 		C.seg_acgtn.resize((size_t)nseg);
-		for (int s = 0; s < nseg; s++) C.seg_acgtn[(size_t)s] = only_acgtn(dna + sidx[(size_t)s] * step, slen[(size_t)s]) ? 1 : 0;
+		for (int s = 0; s < nseg; s++) C.seg_acgtn[(size_t)s] = only_acgtn(dna + C.soff[(size_t)s], slen[(size_t)s]) ? 1 : 0;
 	}
 	return FASIM_OK;
 }
 
 
-// LongTarget()'s tail filter (Fasim-LongTarget.cpp:589-597) over the units of a finished batch, in canonical order
-static void collect_batch(BatchCtx& C, std::vector<HostTriplex>& all)
+// What one work item leaves for one record: the record's triplexes from the item's segments and the per-record stats (those
+// counted per unit or candidate).  A batch that crosses records leaves one part per record, in record order.
+struct RecPart {
+	int rec = 0;
+	fasim_scan_stats st;
+	std::vector<HostTriplex> recs;
+	explicit RecPart(int r) : rec(r) { memset(&st, 0, sizeof st); }
+};
+
+// LongTarget()'s tail filter (Fasim-LongTarget.cpp:589-597) over the units of a finished batch, in canonical order, split by
+// record (unit -> segment -> record); `m` = the item's query length.  With `ok` false (the item failed) only the parts are made.
+static void collect_batch(BatchCtx& C, const SegTable& T, int64_t b0, int64_t b1, int64_t m, bool ok, std::vector<RecPart>& parts)
 {
+	parts.clear();
+	for (int64_t s = b0; s < b1; s++) {
+		if (parts.empty() || parts.back().rec != T.rec[(size_t)s]) parts.emplace_back(T.rec[(size_t)s]);
+		parts.back().st.segments++;
+	}
+	if (!ok) return;
 	const fasim_params& p = *C.p;
-	for (auto& unit : C.per_unit)
-		for (HostTriplex& t : unit)
-			if (t.score >= p.scoreMin && t.identity >= p.minIdentity && t.tri_score >= p.minStability && t.nt >= p.cLength)
-				all.push_back(std::move(t));
+	const int nenc = C.nenc;
+	size_t pi = 0;
+	for (int k = 0; k < C.nseg; k++) {
+		while (parts[pi].rec != C.srec[(size_t)k]) pi++;
+		RecPart& P = parts[pi];
+		fasim_scan_stats& st = P.st;
+		st.units += nenc;
+		st.logical_cells += m * C.slen[(size_t)k] * nenc;
+		st.cells_stage2 += m * C.slen[(size_t)k] * nenc;
+		for (int e = 0; e < nenc; e++) {
+			const size_t u = (size_t)k * nenc + e;
+			st.candidates += C.ucand[u]; st.align_calls += C.ualign[u];
+			if (u >= C.per_unit.size()) continue;
+			for (HostTriplex& t : C.per_unit[u])
+				if (t.score >= p.scoreMin && t.identity >= p.minIdentity && t.tri_score >= p.minStability && t.nt >= p.cLength)
+					P.recs.push_back(std::move(t));
+		}
+	}
+	for (RecPart& P : parts) P.st.segments_skipped = P.st.segments - P.st.units / std::max(1, nenc);
 }
 
 // pack the records of one query into the C result
@@ -502,21 +561,18 @@ static void add_stats(fasim_scan_stats& st, const fasim_scan_stats& x)
 	for (int k = 0; k < FASIM_KERNEL_FAMILIES; k++) { st.kernel_ms[k] += x.kernel_ms[k]; st.kernel_launches[k] += x.kernel_launches[k]; }
 }
 
-// The body of fasim_scan / fasim_scan_queries: every (query, batch of segments) pair is one work item; the worker engines
-// take items from one queue, so the tail of one query's scan overlaps the head of the next (no ramp-up / drain per query).
-// nq == 0: the engine's current query.
-int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna, int64_t dna_len,
-	int64_t seg_first, int64_t seg_count, const fasim_params* pp, fasim_result** outs)
+// The body of fasim_scan / fasim_scan_queries / fasim_scan_records: every (query, batch of segments) pair is one work item; the
+// worker engines take items from one queue, so the tail of one query's scan overlaps the head of the next (no ramp-up / drain
+// per query).  nq == 0: the engine's current query.  The segments of the `nrec` records are numbered globally, record after
+// record, and a batch may cross records.  `records` false (fasim_scan, fasim_scan_queries: one record): outs[q] carries the
+// whole call's stats.  `records` true: outs[q * nrec + r] carries the per-record stats, totals[q] (if given) the call's.
+static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna,
+	const int64_t* rec_off, const int64_t* rec_len, int nrec, bool records, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
+	fasim_result** outs, fasim_scan_stats* totals)
 {
 	const bool resident = (dna == nullptr);
-	if (resident) {
-		if (E->dna_host.empty()) return fail(E, FASIM_E_ARG, "no resident DNA: call fasim_load_dna first");
-		dna = E->dna_host.data(); dna_len = (int64_t)E->dna_host.size();
-	}
-	if (!dna || dna_len <= 0 || !pp || !outs) return fail(E, FASIM_E_ARG, "bad arguments");
+	if (resident) dna = E->dna_host.data();
 	const fasim_params p = *pp;
-	if (p.cutLength <= 0 || p.cutLength - p.overlapLength <= 0) return fail(E, FASIM_E_ARG, "cutLength/overlapLength invalid");
-	if (dna_len > 0x7fffffffll) return fail(E, FASIM_E_ARG, "one record is limited to 2^31-1 nt (the reference's int positions)");
 	HIPOK(hipSetDevice(E->device));
 	const double t_begin = now_s();
 	AffinityScope numa(E->device, E->opt_numa != 0);
@@ -529,26 +585,40 @@ int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens,
 		queries.emplace_back(rnas[q], rnas[q] + rna_lens[q]);
 	}
 	const int nquery = (int)queries.size();
-	for (int q = 0; q < nquery; q++) outs[q] = nullptr;
+	const size_t nout = (size_t)nquery * (size_t)nrec;
+	for (size_t k = 0; k < nout; k++) outs[k] = nullptr;
 
-	const int64_t nseg_all = fasim_segment_count(dna_len, &p);
+	// the segment table of the selected range of the global segment list (cutSequence() of every record, fastsim.h:71-90)
+	const int64_t step = p.cutLength - p.overlapLength;
+	std::vector<int64_t> rec_first((size_t)nrec + 1, 0);
+	for (int r = 0; r < nrec; r++) rec_first[(size_t)r + 1] = rec_first[(size_t)r] + fasim_segment_count(rec_len[r], &p);
+	const int64_t nseg_all = rec_first[(size_t)nrec];
 	if (seg_first < 0) seg_first = 0;
 	if (seg_count < 0 || seg_first + seg_count > nseg_all) seg_count = std::max<int64_t>(0, nseg_all - seg_first);
-	const int64_t step = p.cutLength - p.overlapLength;
+	SegTable T;
+	int64_t total_bases = 0;
+	if (seg_count > 0) {
+		T.rec.reserve((size_t)seg_count); T.len.reserve((size_t)seg_count); T.idx.reserve((size_t)seg_count); T.off.reserve((size_t)seg_count);
+		int r = (int)(std::upper_bound(rec_first.begin(), rec_first.end(), seg_first) - rec_first.begin()) - 1;
+		for (int64_t g = seg_first; g < seg_first + seg_count; g++) {
+			while (g >= rec_first[(size_t)r + 1]) r++;
+			const int64_t i = g - rec_first[(size_t)r], pos = i * step;
+			const int len = (int)std::min<int64_t>(p.cutLength, rec_len[r] - pos);
+			T.rec.push_back(r); T.idx.push_back(i); T.off.push_back(rec_off[r] + pos); T.len.push_back(len);
+			total_bases += len;
+		}
+	}
 	const std::vector<int> encs = enabled_encodings(p);
 	const int nenc = (int)encs.size();
 
-	std::vector<std::vector<HostTriplex>> all(nquery);
 	bool packed = false;
 	std::vector<fasim_scan_stats> qst(nquery);
 	for (auto& x : qst) memset(&x, 0, sizeof x);
+	std::vector<fasim_scan_stats> rst(records ? nout : 0);          // per (query, record)
+	for (auto& x : rst) memset(&x, 0, sizeof x);
 	if (seg_count > 0 && nenc > 0) {
-		// the shard's DNA stays resident for the whole scan (all queries)
-		const int64_t shard_lo = seg_first * step;
-		const int64_t shard_hi = std::min<int64_t>(dna_len, (seg_first + seg_count - 1) * step + p.cutLength);
-		// resident record: the kernels read it in place; host buffer: every batch streams its own slice (scan_batch)
-		const uint8_t* dna_dev = resident ? E->dna_res.as<uint8_t>() + shard_lo : nullptr;
-		(void)shard_hi;
+		// resident DNA: the kernels read it in place; host buffer: every batch streams its own slice (scan_batch)
+		const uint8_t* dna_dev = resident ? E->dna_res.as<uint8_t>() : nullptr;
 		const int tstride = (p.cutLength + 15) & ~15;
 		// Batches of ~384 segments x 48 encodings; several batches are in flight at once on worker engines (own HIP
 		// stream + buffers + host thread), so the latency-bound kernels (stripe-faithful re-runs, tracebacks) and the
@@ -573,7 +643,7 @@ int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens,
 		// 2.41 s against 2.61 s with fixed batches of 384 (profiles/r02_ab_batch_shape.txt: the optimum sits exactly where
 		// the batches tile the ten workers, 448 and 576 are both slower than 512; other record sizes: r02_ab_sizes.txt).
 		// A batch of several lncRNAs is one stream of items, lncRNA after lncRNA, and keeps fixed batches of 384.
-		if (!envb && E->opt_seg_batch <= 0 && nquery == 1 && seg_count >= (int64_t)128 * nworkers) {
+		if (!records && !envb && E->opt_seg_batch <= 0 && nquery == 1 && seg_count >= (int64_t)128 * nworkers) {
 			const int64_t target = 512;
 			const int64_t rounds = std::max<int64_t>(1, (seg_count + target * (int64_t)nworkers - 1) / (target * (int64_t)nworkers));
 			seg_batch = std::max<int64_t>(1, std::min<int64_t>((seg_count + rounds * nworkers - 1) / (rounds * nworkers), ((int64_t)8 << 30) / ((int64_t)4 * nenc * tstride)));
@@ -590,17 +660,33 @@ int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens,
 		}
 		// queries beyond 16 systolic tiles: the per-batch buffers that grow with the tiles (k_scan's block maxima for the banded
 		// stage 3: ~10 KB per unit and tile; the reverse-pass lane maxima: 1 KB per candidate and tile) stay at their 16-tile size
+		int tiles = 1;
+		for (int q = 0; q < nquery; q++) {
+			const int mq = (int)queries[(size_t)q].size();
+			if (systolic_fits(mq)) tiles = std::max(tiles, systolic_tiles(mq));
+		}
 		if (!envb && E->opt_seg_batch <= 0 && !p.classicSim) {
-			int tiles = 1;
-			for (int q = 0; q < nquery; q++) {
-				const int mq = (int)queries[(size_t)q].size();
-				if (systolic_fits(mq)) tiles = std::max(tiles, systolic_tiles(mq));
-			}
 			if (tiles > 16) seg_batch = std::max<int64_t>(1, seg_batch * 16 / tiles);
 		}
+		// batches of the call: ranges of the segment table (local indices; a batch may cross records)
 		std::vector<std::pair<int64_t, int64_t>> chunks;
-		{
-			int64_t b0 = seg_first; const int64_t b_end = seg_first + seg_count;
+		if (records && !envb && E->opt_seg_batch <= 0 && !p.classicSim) {
+			// A record set is cut by bases, not by segments: a batch of short records' segments would otherwise carry a fraction of a
+			// batch's work for the whole fixed latency of its chain of launches.  Target: the bases of a default batch of full-length
+			// segments, lowered so that every worker gets an item; at most 512 x 48 units (the per-unit buffers such as k_scan's
+			// block maxima keep their size), and the > 16-tile rule as above.
+			int64_t cap = std::max<int64_t>(1, std::min<int64_t>((int64_t)512 * 48 / nenc, ((int64_t)8 << 30) / ((int64_t)4 * nenc * tstride)));
+			if (tiles > 16) cap = std::max<int64_t>(1, cap * 16 / tiles);
+			const int64_t per_query = std::max<int64_t>(1, (nworkers + nquery - 1) / nquery);
+			const int64_t target = std::max<int64_t>(1, std::min<int64_t>((int64_t)384 * p.cutLength, (total_bases + per_query - 1) / per_query));
+			int64_t b0 = 0, bases = 0;
+			for (int64_t s = 0; s < seg_count; s++) {
+				bases += T.len[(size_t)s];
+				if (s + 1 - b0 >= cap || bases >= target) { chunks.push_back({ b0, s + 1 }); b0 = s + 1; bases = 0; }
+			}
+			if (b0 < seg_count) chunks.push_back({ b0, seg_count });
+		} else {
+			int64_t b0 = 0; const int64_t b_end = seg_count;
 			const int64_t taper_from = b_end - seg_count * taper_pct / 100;
 			while (b0 < b_end) {
 				int64_t len = (taper_pct > 0 && b0 >= taper_from) ? std::max<int64_t>(1, seg_batch / 2) : seg_batch;
@@ -645,7 +731,7 @@ int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens,
 			for (int k = 0; k < FASIM_KERNEL_FAMILIES; k++) { w->kernel_ms[k] = 0; w->kernel_launches[k] = 0; }
 			w->sw_probs = 0; w->sw_ms = 0.0;
 		}
-		std::vector<std::vector<HostTriplex>> per_item(items.size());
+		std::vector<std::vector<RecPart>> per_item(items.size());
 		std::vector<fasim_scan_stats> ist(items.size());
 		for (auto& x : ist) memset(&x, 0, sizeof x);
 		std::vector<double> it0(items.size(), 0.0), it1(items.size(), 0.0);
@@ -670,13 +756,13 @@ int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens,
 					r = fasim_set_query(w, rq.data(), (int)rq.size());
 					if (r && w != E) w->err = std::string("worker set_query failed: ") + w->err;
 				}
-				if (!r) r = scan_batch(w, dna, dna_len, dna_dev, shard_lo, itx.b0, itx.b1, p, encs, tstride, ctx, ist[c]);
+				if (!r) r = scan_batch(w, dna, T, dna_dev, itx.b0, itx.b1, p, encs, tstride, ctx, ist[c]);
 				if (!r && ctx.B.nunit > 0 && !ctx.stage3_done) r = stage3_range(w, ctx, 0, ctx.B.nunit, ist[c]);
 				(void)hipStreamSynchronize(w->st);
 				drain_timed(w);
 				for (int k = 0; k < FASIM_KERNEL_FAMILIES; k++) { ist[c].kernel_ms[k] = w->kernel_ms[k]; ist[c].kernel_launches[k] = w->kernel_launches[k]; w->kernel_ms[k] = 0; w->kernel_launches[k] = 0; }
 				ist[c].striped_window_probs = w->sw_probs; ist[c].striped_window_ms = w->sw_ms; w->sw_probs = 0; w->sw_ms = 0.0;
-				if (!r) collect_batch(ctx, per_item[c]);
+				if (!r) collect_batch(ctx, T, itx.b0, itx.b1, (int64_t)rq.size(), true, per_item[c]);
 				it1[c] = now_s();
 				if (r) wrc[wi] = r;
 			}
@@ -693,10 +779,14 @@ int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens,
 		if (nq > 0 && E->rna != queries.back()) { int rc = fasim_set_query(E, queries.back().data(), (int)queries.back().size()); if (rc) return rc; }
 		const double t_merge = now_s();
 		std::vector<double> q0(nquery, 1e300), q1(nquery, 0.0);
-		std::vector<std::vector<const std::vector<HostTriplex>*>> parts((size_t)nquery);
+		std::vector<std::vector<const std::vector<HostTriplex>*>> parts(nout);       // per (query, record), in batch order
 		for (size_t c = 0; c < items.size(); c++) {
 			const int q = items[c].q;
-			parts[(size_t)q].push_back(&per_item[c]);
+			for (RecPart& P : per_item[c]) {
+				const size_t o = (size_t)q * (size_t)nrec + (size_t)P.rec;
+				parts[o].push_back(&P.recs);
+				if (records) add_stats(rst[o], P.st);
+			}
 			add_stats(qst[(size_t)q], ist[c]);
 			q0[q] = std::min(q0[q], it0[c]); q1[q] = std::max(q1[q], it1[c]);
 		}
@@ -705,11 +795,23 @@ int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens,
 		if (nquery == 1) qst[0].t_total_s = now_s() - t_begin;
 		// the records go straight from the batches' lists into the C result (the batches side by side on the host threads);
 		// the lists themselves (half a million strings for a 50 Mb record) are freed behind the caller's back
-		for (int q = 0; q < nquery; q++) {
-			const int rc = pack_result_parts(E, parts[(size_t)q], qst[(size_t)q], E->host_threads_total, &outs[q]);
-			if (rc) { for (int k = 0; k < q; k++) { fasim_result_free(outs[k]); outs[k] = nullptr; } return rc; }
+		if (!records) {
+			for (int q = 0; q < nquery; q++) {
+				const int rc = pack_result_parts(E, parts[(size_t)q], qst[(size_t)q], E->host_threads_total, &outs[q]);
+				if (rc) { for (int k = 0; k < q; k++) { fasim_result_free(outs[k]); outs[k] = nullptr; } return rc; }
+			}
+			if (nquery == 1) outs[0]->stats.t_total_s = now_s() - t_begin;
+		} else {
+			// one result per (query, record), the records side by side on the host threads
+			std::atomic<int> bad(FASIM_OK);
+			parallel_units((int)nout, nout >= 256 ? std::max(1, std::min(16, E->host_threads_total)) : 1, [&](int o) {
+				const int rc = pack_result_parts(E, parts[(size_t)o], rst[(size_t)o], 1, &outs[o]);
+				if (rc) bad.store(rc);
+			});
+			if (bad.load()) { for (size_t k = 0; k < nout; k++) { fasim_result_free(outs[k]); outs[k] = nullptr; } return bad.load(); }
+			if (nquery == 1) qst[0].t_total_s = now_s() - t_begin;
+			if (totals) for (int q = 0; q < nquery; q++) totals[q] = qst[(size_t)q];
 		}
-		if (nquery == 1) outs[0]->stats.t_total_s = now_s() - t_begin;
 		if (g_prof.on) fprintf(stderr, "[fasim prof] scan tail: packing the records                        %.3f s\n", now_s() - t_merge);
 		// Free the batches' lists (half a million strings for a 50 Mb record) here, side by side on the host threads, while the
 		// GPU is idle: left to a background thread the unmapping runs into the first kernels of the caller's next scan and
@@ -717,7 +819,7 @@ int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens,
 		// profiles/r02_ab_reaper.txt).
 		{
 			std::atomic<size_t> nextf(0);
-			auto freer = [&]() { for (;;) { const size_t c = nextf.fetch_add(1); if (c >= per_item.size()) break; std::vector<HostTriplex>().swap(per_item[c]); } };
+			auto freer = [&]() { for (;;) { const size_t c = nextf.fetch_add(1); if (c >= per_item.size()) break; std::vector<RecPart>().swap(per_item[c]); } };
 			const int nt = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, E->host_threads_total), per_item.size()));
 			if (nt == 1) freer();
 			else { std::vector<std::thread> th; for (int k = 0; k < nt; k++) th.emplace_back(freer); for (auto& t : th) t.join(); }
@@ -729,11 +831,13 @@ int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens,
 	if (!packed) {
 		// (nothing to scan: empty results)
 		if (nquery == 1) qst[0].t_total_s = now_s() - t_begin;
-		for (int q = 0; q < nquery; q++) {
-			const int rc = pack_result(E, all[(size_t)q], qst[(size_t)q], &outs[q]);
-			if (rc) { for (int k = 0; k < q; k++) { fasim_result_free(outs[k]); outs[k] = nullptr; } return rc; }
+		std::vector<HostTriplex> none;
+		for (size_t k = 0; k < nout; k++) {
+			const int rc = pack_result(E, none, records ? rst[k] : qst[k], &outs[k]);
+			if (rc) { for (size_t j = 0; j < k; j++) { fasim_result_free(outs[j]); outs[j] = nullptr; } return rc; }
 		}
-		if (nquery == 1) outs[0]->stats.t_total_s = now_s() - t_begin;
+		if (!records && nquery == 1) outs[0]->stats.t_total_s = now_s() - t_begin;
+		if (records && totals) for (int q = 0; q < nquery; q++) totals[q] = qst[(size_t)q];
 	}
 	if (g_prof.on) {
 		static long seen = 0; const long now_r = g_dev_reallocs.load();
@@ -745,3 +849,23 @@ int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens,
 	return FASIM_OK;
 }
 
+int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna, int64_t dna_len,
+	int64_t seg_first, int64_t seg_count, const fasim_params* pp, fasim_result** outs)
+{
+	if (dna == nullptr) {
+		if (E->dna_host.empty()) return fail(E, FASIM_E_ARG, "no resident DNA: call fasim_load_dna first");
+		dna_len = (int64_t)E->dna_host.size();
+		if (!pp || !outs) return fail(E, FASIM_E_ARG, "bad arguments");
+	} else if (dna_len <= 0 || !pp || !outs) return fail(E, FASIM_E_ARG, "bad arguments");
+	if (pp->cutLength <= 0 || pp->cutLength - pp->overlapLength <= 0) return fail(E, FASIM_E_ARG, "cutLength/overlapLength invalid");
+	if (dna_len > 0x7fffffffll) return fail(E, FASIM_E_ARG, "one record is limited to 2^31-1 nt (the reference's int positions)");
+	const int64_t off = 0;
+	return scan_set(E, rnas, rna_lens, nq, dna, &off, &dna_len, 1, false, seg_first, seg_count, pp, outs, nullptr);
+}
+
+int scan_records_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna,
+	const int64_t* rec_off, const int64_t* rec_len, int nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
+	fasim_result** outs, fasim_scan_stats* totals)
+{
+	return scan_set(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, true, seg_first, seg_count, pp, outs, totals);
+}

@@ -612,6 +612,7 @@ int stage3_range(fasim_engine* E, BatchCtx& C, int ua, int ub, fasim_scan_stats&
 			for (auto& v : part) cs.insert(cs.end(), v.begin(), v.end());
 		}
 		st.candidates += (int64_t)cs.size();
+		for (const CandState& x : cs) C.ucand[(size_t)x.unit]++;
 		bool v2 = true;
 		{ std::vector<WindowProb> probe(1, WindowProb{ 0, 0, 1 }); v2 = align_v2_fits(E, probe); }
 		// lane maxima left by the reverse passes (start-based bounds of a candidate's tries): [candidate][4 zones][lanes]
@@ -631,6 +632,7 @@ int stage3_range(fasim_engine* E, BatchCtx& C, int ua, int ub, fasim_scan_stats&
 				}
 				if (W.empty()) break;
 				st.align_calls += (int64_t)W.size();
+				for (const WindowProb& w : W) C.ualign[(size_t)w.unit]++;
 				// Band targets.  A candidate that has been through a reverse pass has start-based bounds for all of its tries (its
 				// exact score is then known to the selection kernel); otherwise the first try aims at the candidate's own score (an
 				// accepted try reaches it), and a later try goes straight to the reverse pass, or, without reverse passes
@@ -751,7 +753,7 @@ int stage3_range(fasim_engine* E, BatchCtx& C, int ua, int ub, fasim_scan_stats&
 					who.push_back(k);
 				}
 				if (W.empty()) break;
-				st.align_calls += (int64_t)W.size(); for (const WindowProb& w : W) st.cells_stage3 += (int64_t)E->m * w.len;
+				st.align_calls += (int64_t)W.size(); for (const WindowProb& w : W) { st.cells_stage3 += (int64_t)E->m * w.len; C.ualign[(size_t)w.unit]++; }
 				std::vector<AlignResult> res;
 				rc = run_align(E, B, W, res, cigars, nullptr); if (rc) return rc;
 				for (size_t i = 0; i < who.size(); i++) {
@@ -784,7 +786,7 @@ int stage3_range(fasim_engine* E, BatchCtx& C, int ua, int ub, fasim_scan_stats&
 					if (u >= ub) break;
 					if (first[u] == first[u + 1]) continue;
 					const int s = u / nenc, enc = encs[u % nenc];
-					const char* seg = dna + sidx[s] * step;
+					const char* seg = dna + C.soff[(size_t)s];
 					const long dna_start = (long)(sidx[s] * step);
 					mine.clear(); kept.clear();
 					const bool acgtn = seg_acgtn[s] != 0;

@@ -9,6 +9,9 @@
 //                           into contiguous shards, one engine (host thread) per device, records merged in shard order
 //     --all-records         scan EVERY record of a multi-record DNA file (a genome), one record in memory at a time, and
 //                           write one set of output files per record: <species>-<lnc>-<f1 stem>.<chr>-TFOsorted / -TFOclass...
+//                           Consecutive short records (peaks, promoter windows) are scanned in groups of about
+//                           FASIM_RECORD_GROUP segments (default 5120) by one fasim_scan_records call each; a record of that
+//                           many segments or more is scanned alone; FASIM_RECORD_GROUP=0 scans every record alone
 //     --accumulate-records  bug-compatible with the reference's reader (defect B1, Fasim-LongTarget.cpp:219-262): record
 //                           k is scanned as the concatenation of records 1..k, later headers are parsed with the stale
 //                           field counter, everything is written into ONE output set named after the first record
@@ -30,7 +33,10 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <condition_variable>
 #include <deque>
+#include <functional>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <string>
@@ -210,6 +216,87 @@ static int scan_record(const std::vector<fasim_engine*>& engines, const std::vec
 	return bad;
 }
 
+// --all-records: consecutive short records scanned together, one fasim_scan_records call per group (all lncRNAs, all devices).
+// out[q][r] = the records of lncRNA q in record r of the group, exactly what scan_record gives for that record alone.  With
+// several devices, device d takes the d-th contiguous block of the group's global segment list and every record's parts are
+// merged in device order.
+static int scan_group(const std::vector<fasim_engine*>& engines, const std::vector<Rna>& rnas, const std::vector<DnaRecord>& group,
+	const fasim_params& p, std::vector<std::vector<fasim_result*>>& out)
+{
+	const int nd = (int)engines.size(), nq = (int)rnas.size(), nrec = (int)group.size();
+	std::vector<const char*> qp((size_t)nq); std::vector<int32_t> ql((size_t)nq);
+	for (int q = 0; q < nq; q++) { qp[(size_t)q] = rnas[(size_t)q].seq.data(); ql[(size_t)q] = (int32_t)rnas[(size_t)q].seq.size(); }
+	std::string dna;
+	std::vector<int64_t> off((size_t)nrec), len((size_t)nrec);
+	int64_t nseg = 0;
+	for (int r = 0; r < nrec; r++) {
+		off[(size_t)r] = (int64_t)dna.size(); len[(size_t)r] = (int64_t)group[(size_t)r].seq.size();
+		dna += group[(size_t)r].seq;
+		nseg += fasim_segment_count(len[(size_t)r], &p);
+	}
+	out.assign((size_t)nq, std::vector<fasim_result*>((size_t)nrec, nullptr));
+	std::vector<std::vector<fasim_result*>> part((size_t)nd, std::vector<fasim_result*>((size_t)nq * nrec, nullptr));
+	std::vector<int> rc((size_t)nd, 0);
+	auto run = [&](int d) {
+		const int64_t base = nseg / nd, rem = nseg % nd;
+		const int64_t first = d * base + std::min<int64_t>(d, rem), count = base + (d < rem ? 1 : 0);
+		rc[(size_t)d] = fasim_scan_records(engines[(size_t)d], qp.data(), ql.data(), nq, dna.data(), off.data(), len.data(), nrec, first, count, &p,
+			part[(size_t)d].data(), nullptr);
+	};
+	if (nd == 1) run(0);
+	else { std::vector<std::thread> th; for (int d = 0; d < nd; d++) th.emplace_back(run, d); for (auto& t : th) t.join(); }
+	int bad = 0;
+	for (int d = 0; d < nd; d++) {
+		if (rc[(size_t)d] == FASIM_OK) continue;
+		if (nd == 1) fprintf(stderr, "fasim: %s\n", fasim_last_error(engines[0]));
+		else fprintf(stderr, "fasim: device shard %d: %s\n", d, fasim_last_error(engines[(size_t)d]));
+		bad = 1;
+	}
+	for (int q = 0; q < nq && !bad; q++) for (int r = 0; r < nrec && !bad; r++) {
+		const size_t k = (size_t)q * nrec + r;
+		if (nd == 1) { out[(size_t)q][(size_t)r] = part[0][k]; part[0][k] = nullptr; continue; }
+		std::vector<const fasim_triplex*> recs((size_t)nd); std::vector<int64_t> counts((size_t)nd), plens((size_t)nd); std::vector<const char*> pools((size_t)nd);
+		for (int d = 0; d < nd; d++) { const fasim_result* x = part[(size_t)d][k]; recs[(size_t)d] = x->recs; counts[(size_t)d] = x->count; pools[(size_t)d] = x->pool; plens[(size_t)d] = x->pool_len; }
+		if (fasim_merge_results(recs.data(), counts.data(), pools.data(), plens.data(), nd, &out[(size_t)q][(size_t)r]) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); bad = 1; break; }
+		fasim_scan_stats& st = out[(size_t)q][(size_t)r]->stats;
+		for (int d = 0; d < nd; d++) {
+			const fasim_scan_stats& x = part[(size_t)d][k]->stats;
+			st.segments += x.segments; st.segments_skipped += x.segments_skipped; st.units += x.units; st.candidates += x.candidates;
+			st.align_calls += x.align_calls; st.logical_cells += x.logical_cells; st.cells_stage2 += x.cells_stage2;
+		}
+	}
+	for (auto& v : part) for (fasim_result* x : v) fasim_result_free(x);
+	if (bad) { for (auto& v : out) for (fasim_result*& x : v) { fasim_result_free(x); x = nullptr; } }
+	return bad;
+}
+
+// Host threads for the tails of grouped records (clustering, texts, file writes): FIFO, while the next group is read and scanned.
+struct TailPool {
+	std::mutex mu; std::condition_variable cv, idle;
+	std::deque<std::function<void()>> jobs;
+	std::vector<std::thread> th;
+	int running = 0; bool stop = false;
+	explicit TailPool(int n)
+	{
+		for (int k = 0; k < n; k++) th.emplace_back([this] {
+			for (;;) {
+				std::function<void()> job;
+				{
+					std::unique_lock<std::mutex> lk(mu);
+					cv.wait(lk, [&] { return stop || !jobs.empty(); });
+					if (jobs.empty()) return;
+					job = std::move(jobs.front()); jobs.pop_front(); running++;
+				}
+				job();
+				{ std::lock_guard<std::mutex> lk(mu); running--; if (jobs.empty() && !running) idle.notify_all(); }
+			}
+		});
+	}
+	void add(std::function<void()> job) { { std::lock_guard<std::mutex> lk(mu); jobs.push_back(std::move(job)); } cv.notify_one(); }
+	void drain() { std::unique_lock<std::mutex> lk(mu); idle.wait(lk, [&] { return jobs.empty() && !running; }); }
+	~TailPool() { { std::lock_guard<std::mutex> lk(mu); stop = true; } cv.notify_all(); for (auto& t : th) t.join(); }
+};
+
 int main(int argc, char* const* argv)
 {
 	fasim_params p; fasim_params_default(&p);
@@ -332,6 +419,66 @@ int main(int argc, char* const* argv)
 		}
 		for (auto& v : per_rec) for (fasim_result* r : v) fasim_result_free(r);
 	} else {
+		// FASIM_RECORD_GROUP = G (--all-records): consecutive records are scanned together, one fasim_scan_records call per group
+		// of about G segments; a record of >= G segments alone (a chromosome) is scanned as before.  0 = one scan per record.
+		// Default 5 120 = ten batches of 512 segments: one round of full batches for the ten workers of a scan.
+		long group_segs = 5120;
+		if (const char* g = getenv("FASIM_RECORD_GROUP")) group_segs = atol(g);
+		const bool grouped = all_records && group_segs > 0;
+		// grouped: the tails of thousands of records go to a pool of host threads instead of four threads in flight
+		std::unique_ptr<TailPool> pool(grouped ? new TailPool(8) : nullptr);
+		// per record: --stats lines, output stem, tail + write on a background thread (the next record is read and scanned meanwhile)
+		auto emit = [&](size_t recno, const DnaRecord& r, const std::vector<fasim_result*>& res) {
+			for (size_t q = 0; q < rnas.size(); q++) {
+				if (stats) {
+					const fasim_scan_stats& s = res[q]->stats;
+					fprintf(stderr, "[fasim] record %zu (%s) x %s: %lld segments (%lld skipped), %lld units, %lld candidates, %lld align calls, %lld records\n",
+						recno, r.chr.c_str(), rnas[q].name.c_str(), (long long)s.segments, (long long)s.segments_skipped, (long long)s.units,
+						(long long)s.candidates, (long long)s.align_calls, (long long)res[q]->count);
+				}
+				const std::string stem = outdir + "/" + r.species + "-" + rnas[q].name + "-" + base + (all_records ? "." + r.chr : std::string());
+				const bool twice = !stems_seen.insert(stem).second;
+				if (twice) fprintf(stderr, "fasim: warning: %s-TFOsorted is written twice (two lncRNAs or records of the same name): the later one wins\n", stem.c_str());
+				fasim_result* x = res[q];
+				const std::string chr = r.chr, lname = rnas[q].name; const long start = r.start; const int64_t dlen = (int64_t)r.seq.size();
+				auto job = [=, &tm, &p]() {
+					Timers mine;
+					const int bad = write_outputs(x, stem, chr, start, dlen, lname, p, tail_flags, mine);
+					fasim_result_free(x);
+					std::lock_guard<std::mutex> lk(g_out_mu);
+					tm.tail += mine.tail; tm.write += mine.write; if (bad) g_out_failed = 1;
+				};
+				if (pool) {
+					if (twice) pool->drain();         // the later one wins: the earlier file is complete before it is overwritten
+					pool->add(job);
+				} else {
+					while (pending.size() >= 4) { pending.front().join(); pending.pop_front(); }
+					pending.emplace_back(job);
+				}
+			}
+		};
+		std::vector<DnaRecord> group;
+		int64_t group_nseg = 0;
+		size_t group_first = 0, ngroups = 0;
+		auto flush = [&]() -> int {
+			if (group.empty()) return 0;
+			const double t0 = now_s();
+			std::vector<std::vector<fasim_result*>> res;
+			if (scan_group(engines, rnas, group, p, res)) return 1;
+			const double dt = now_s() - t0;
+			tm.scan += dt;
+			if (stats) fprintf(stderr, "[fasim] group %zu: %zu records, %lld segments, scan %.3f s\n", ngroups, group.size(), (long long)group_nseg, dt);
+			std::vector<fasim_result*> one(rnas.size());
+			for (size_t r = 0; r < group.size(); r++) {
+				for (size_t q = 0; q < rnas.size(); q++) one[q] = res[q][r];
+				emit(group_first + r, group[r], one);
+				total_nt += (int64_t)group[r].seq.size();
+			}
+			ngroups++; group.clear(); group_nseg = 0;
+			return 0;
+		};
+		// on an error the tails of earlier records still run on their threads: a joinable std::thread must not be destroyed
+		auto stop = [&]() { for (std::thread& t : pending) t.join(); pool.reset(); return 1; };
 		for (;;) {
 			double t0 = now_s();
 			if (!reader.next(rec)) break;
@@ -340,41 +487,31 @@ int main(int argc, char* const* argv)
 				fprintf(stderr, "fasim: %s holds more than one record: only the first one was scanned (use --all-records; see DESIGN.md, B1)\n", f1.c_str());
 				break;
 			}
+			if (grouped) {
+				const int64_t ns = fasim_segment_count((int64_t)rec.seq.size(), &p);
+				if (!rec.seq.empty() && ns < group_segs) {
+					if (group.empty()) group_first = nrec;
+					group_nseg += ns;
+					group.push_back(std::move(rec));
+					nrec++;
+					if (group_nseg >= group_segs && flush()) return stop();
+					continue;
+				}
+				if (flush()) return stop();
+			}
 			t0 = now_s();
 			std::vector<fasim_result*> res;
-			if (scan_record(engines, rnas, rec.seq, p, res)) {
-				// the tails of earlier records still run on their threads: a joinable std::thread must not be destroyed
-				for (std::thread& t : pending) t.join();
-				return 1;
-			}
+			if (scan_record(engines, rnas, rec.seq, p, res)) return stop();
 			tm.scan += now_s() - t0;
 			total_nt += (int64_t)rec.seq.size();
-			for (size_t q = 0; q < rnas.size(); q++) {
-				if (stats) {
-					const fasim_scan_stats& s = res[q]->stats;
-					fprintf(stderr, "[fasim] record %zu (%s) x %s: %lld segments (%lld skipped), %lld units, %lld candidates, %lld align calls, %lld records\n",
-						nrec, rec.chr.c_str(), rnas[q].name.c_str(), (long long)s.segments, (long long)s.segments_skipped, (long long)s.units,
-						(long long)s.candidates, (long long)s.align_calls, (long long)res[q]->count);
-				}
-				const std::string stem = outdir + "/" + rec.species + "-" + rnas[q].name + "-" + base + (all_records ? "." + rec.chr : std::string());
-				if (!stems_seen.insert(stem).second) fprintf(stderr, "fasim: warning: %s-TFOsorted is written twice (two lncRNAs or records of the same name): the later one wins\n", stem.c_str());
-				// tail + write on a background thread: the next record is parsed and scanned meanwhile
-				while (pending.size() >= 4) { pending.front().join(); pending.pop_front(); }
-				fasim_result* r = res[q];
-				const std::string chr = rec.chr, lname = rnas[q].name; const long start = rec.start; const int64_t dlen = (int64_t)rec.seq.size();
-				pending.emplace_back([=, &tm, &p]() {
-					Timers mine;
-					const int bad = write_outputs(r, stem, chr, start, dlen, lname, p, tail_flags, mine);
-					fasim_result_free(r);
-					std::lock_guard<std::mutex> lk(g_out_mu);
-					tm.tail += mine.tail; tm.write += mine.write; if (bad) g_out_failed = 1;
-				});
-			}
+			emit(nrec, rec, res);
 			nrec++;
 		}
+		if (flush()) return stop();
 		const double t_wait = now_s();
 		for (std::thread& t : pending) t.join();
 		pending.clear();
+		if (pool) pool->drain();
 		tm.tail_wait = now_s() - t_wait;
 		if (g_out_failed) return 1;
 	}

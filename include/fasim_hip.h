@@ -216,6 +216,28 @@ int fasim_scan(fasim_engine* e, const char* dna, int64_t dna_len, int64_t seg_fi
 int fasim_scan_queries(fasim_engine* e, const char* const* rnas, const int32_t* rna_lens, int32_t nq,
                        const char* dna, int64_t dna_len, int64_t seg_first, int64_t seg_count,
                        const fasim_params* p, fasim_result** out /* [nq] */);
+/* Record sets (ChIP / ChIRP peaks, promoter windows, enhancers): many short DNA records scanned in shared batches.
+ * Record r is dna[rec_off[r] .. rec_off[r] + rec_len[r]) in host memory; dna == NULL: the offsets refer to the resident buffer
+ * of fasim_load_dna.  nq == 0: the engine's current query (as fasim_scan); nq > 0: as fasim_scan_queries.
+ * Each record is cut into segments exactly as fasim_scan cuts that record alone (fasim_segment_count(rec_len[r])); the
+ * segments are then numbered globally, record after record, and [seg_first, seg_first + seg_count) picks a contiguous range of
+ * that list (seg_count < 0: to the end), so a record set is sharded like one record.  A batch may cross records.
+ * out[q * nrec + r] is, byte for byte, what fasim_scan with query q returns for record r alone, restricted to the selected
+ * segments of that record: the same triplex records in the same order, `seg` = segment index within the record,
+ * genome_shift 0, the same pool bytes.  A record with no selected segment gets an empty result.
+ * Per-record stats: segments, segments_skipped, units, candidates, align_calls, logical_cells and cells_stage2 equal the
+ * single-record scan's (all counted per unit or per candidate); every other field is zero.  totals[q] (may be NULL) holds the
+ * sums of all fields over the call and the query's wall clock in t_total_s.
+ * Refused with FASIM_E_ARG before any GPU work, the record index in fasim_last_error: nrec < 1; a negative offset; a record
+ * outside the resident buffer (a host buffer has no length here: the caller guarantees that `dna` holds every record); a
+ * record of length 0 (fasim_scan refuses it too); a record longer than 2^31 - 1 nt.  A query above FASIM_MAX_QUERY gets
+ * FASIM_E_UNSUPPORTED, and classicSim (-F) keeps its own limits.  The engine stays usable after a refusal.  The whole set
+ * may be longer than 2^31 nt; only one record is limited.  Free every result with fasim_result_free. */
+int fasim_scan_records(fasim_engine* e, const char* const* rnas, const int32_t* rna_lens, int32_t nq,
+                       const char* dna, const int64_t* rec_off, const int64_t* rec_len, int32_t nrec,
+                       int64_t seg_first, int64_t seg_count, const fasim_params* p,
+                       fasim_result** out /* [nq * nrec] (nq == 0: [nrec]), query-major */,
+                       fasim_scan_stats* totals /* [nq] (nq == 0: [1]), may be NULL */);
 /* Host half of the path's one exchange step: concatenates the records of `nparts` shards in the
  * order given and rebases their pool offsets.  Shards are contiguous segment ranges, so rank order IS the
  * reference's canonical (segment, encoding, fastSIM rank) order, which cluster_triplex()'s unstable sort needs.
@@ -227,7 +249,8 @@ int fasim_merge_results(const fasim_triplex* const* recs, const int64_t* counts,
  * precede this shard's pool) to the pool offsets of `count` records. */
 int fasim_rebase_offsets(fasim_triplex* recs, int64_t count, int64_t delta);
 /* Optional: upload a DNA record once and keep it resident in HBM (and a host copy for the string work);
- * afterwards fasim_scan(e, NULL, 0, ...) scans the resident record without any H2D copy of the sequence. */
+ * afterwards fasim_scan(e, NULL, 0, ...) scans the resident record without any H2D copy of the sequence, and
+ * fasim_scan_records(e, ..., NULL, offsets, lengths, ...) the records of a resident set (which may exceed 2^31 nt). */
 int fasim_load_dna(fasim_engine* e, const char* dna, int64_t dna_len);
 void fasim_result_free(fasim_result* r);
 int64_t fasim_segment_count(int64_t dna_len, const fasim_params* p);   /* cutSequence(): fastsim.h:71 */
