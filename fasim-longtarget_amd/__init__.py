@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple
 
 # the scan keeps ~10 batches in flight on separate HIP streams; give them more than the runtime's default of four
 # hardware queues (must be in the environment before HIP initialises, i.e. before torch touches the GPU)
@@ -89,6 +90,10 @@ SIM_K = 50
 MAX_QUERY = 92256
 
 
+class _Region(C.Structure):
+    _fields_ = [("line", C.c_int64), ("start", C.c_int64), ("end", C.c_int64), ("chrom", C.c_char_p), ("name", C.c_char_p)]
+
+
 class _Result(C.Structure):
     _fields_ = [("recs", C.POINTER(Triplex)), ("count", C.c_int64), ("pool", C.POINTER(C.c_char)), ("pool_len", C.c_int64),
                 ("stats", ScanStats)]
@@ -98,7 +103,7 @@ EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_e
            "fasim_calc_score_once", "fasim_ssw_pre_align", "fasim_ssw_colmax_word", "fasim_pick_candidates", "fasim_ssw_align", "fasim_pre_align_batch",
            "fasim_align_batch", "fasim_encode_unit", "fasim_sim_forward_batch", "fasim_sim_finish_unit", "fasim_scan", "fasim_scan_queries", "fasim_scan_records", "fasim_merge_results", "fasim_rebase_offsets", "fasim_load_dna", "fasim_result_free", "fasim_segment_count",
            "fasim_tfosorted", "fasim_tfoclass", "fasim_tfosorted_ex", "fasim_tfoclass_ex", "fasim_tail_outputs", "fasim_upper_case", "fasim_free",
-           "fasim_synth_dna", "fasim_selfcheck_records",
+           "fasim_synth_dna", "fasim_selfcheck_records", "fasim_read_bed",
            # the reference's own ssw.h ABI (include/ssw.h)
            "ssw_init", "init_destroy", "ssw_pre_align", "ssw_align", "align_destroy", "encoded_ops"]
 
@@ -169,6 +174,7 @@ def lib():
     L.fasim_free.restype = None
     L.fasim_synth_dna.argtypes = [C.c_char_p, C.c_int64, C.c_uint64]
     L.fasim_synth_dna.restype = None
+    L.fasim_read_bed.argtypes = [C.c_char_p, C.POINTER(C.POINTER(_Region)), C.POINTER(C.c_int64)]
     _lib = L
     return L
 
@@ -533,6 +539,35 @@ class Engine:
                for q in range(nqo)]
         return res[0] if rnas is None else res
 
+    def scan_regions(self, seq: bytes | None, spans, params: Params | None = None, rnas=None):
+        """BED-style regions of one sequence (fasim_scan_records with explicit offsets): `spans` are 0-based half-open
+        (start, end) pairs into `seq`, or into the buffer made resident by load_dna() when `seq` is None.  Spans may overlap,
+        nest, repeat and come in any order.  Returns what scan_records() returns, and result k is identical to
+        scan_records([seq[s:e]]) of span k.  The call's totals are left in `self.last_totals`."""
+        p = params or default_params()
+        spans = [(int(s), int(e)) for s, e in spans]
+        nrec = len(spans)
+        if nrec == 0:
+            raise FasimError("scan_regions needs at least one span", E_ARG)
+        for k, (s, e) in enumerate(spans):
+            if s < 0 or e <= s or (seq is not None and e > len(seq)):
+                raise FasimError(f"span {k}: ({s}, {e}) is not a non-empty slice of the sequence", E_ARG)
+        offs = (C.c_int64 * nrec)(*[s for s, _ in spans])
+        lens = (C.c_int64 * nrec)(*[e - s for s, e in spans])
+        nq = 0 if rnas is None else len(rnas)
+        arr = (C.c_char_p * max(1, nq))(*(rnas or []))
+        qlens = (C.c_int32 * max(1, nq))(*[len(r) for r in (rnas or [])])
+        nqo = max(1, nq)
+        outs = (C.POINTER(_Result) * (nqo * nrec))()
+        totals = (ScanStats * nqo)()
+        self._check(self._L.fasim_scan_records(self._h, arr, qlens, nq, seq, offs, lens, nrec, 0, -1, C.byref(p), outs, totals))
+        if nq:
+            self.m = len(rnas[-1])
+        self.last_totals = [self._stats_dict(totals[q]) for q in range(nqo)]
+        res = [[ScanResult(stats=self._stats_dict(outs[q * nrec + r].contents.stats), _native=outs[q * nrec + r]) for r in range(nrec)]
+               for q in range(nqo)]
+        return res[0] if rnas is None else res
+
 
 def sim_finish_unit(rna: bytes, seg: bytes, enc: int, dna_start: int, min_score: int, nodes, params: Params | None = None) -> "ScanResult":
     """Host half of the -F path for one unit (fasim_sim_finish_unit): `nodes` = 9-tuples of the forward sweep's node list."""
@@ -635,6 +670,31 @@ def tail_outputs(result: ScanResult, chr_name: str, start_genome: int, dna_len: 
     finally:
         for t in texts:
             L.fasim_free(t)
+
+
+class Region(NamedTuple):
+    """One BED interval (fasim_read_bed): 1-based line, chrom, 0-based half-open [start, end), name (column 4, else
+    <chrom>_<start+1>_<end>; a repeated (name, chrom) pair gets _<line> appended)."""
+    line: int
+    chrom: str
+    start: int
+    end: int
+    name: str
+
+
+def read_bed(path) -> list:
+    """The intervals of a BED file as `fasim --regions` reads them; a refused file raises FasimError with code E_ARG and the
+    line number in the message."""
+    L = lib()
+    out = C.POINTER(_Region)()
+    n = C.c_int64()
+    rc = L.fasim_read_bed(os.fsencode(path), C.byref(out), C.byref(n))
+    if rc != 0:
+        raise FasimError(L.fasim_last_error(None).decode(), rc)
+    try:
+        return [Region(out[k].line, out[k].chrom.decode(), out[k].start, out[k].end, out[k].name.decode()) for k in range(n.value)]
+    finally:
+        L.fasim_free(out)
 
 
 def synth_dna(n: int, seed: int) -> bytes:

@@ -12,6 +12,10 @@
 //                           Consecutive short records (peaks, promoter windows) are scanned in groups of about
 //                           FASIM_RECORD_GROUP segments (default 5120) by one fasim_scan_records call each; a record of that
 //                           many segments or more is scanned alone; FASIM_RECORD_GROUP=0 scans every record alone
+//     --regions FILE.bed    scan the BED intervals of a genome (fasim_read_bed): every interval gets the files --all-records
+//                           writes for the record >NAME|CHROM|START+1-END of its bytes, plus one index per lncRNA,
+//                           <O>/<lnc>-<f1 stem>.regions.tsv; the genome is streamed and the intervals are grouped as above.
+//                           Exit status 2 for a refused BED file (nothing written), 1 if an interval lies in no DNA record
 //     --accumulate-records  bug-compatible with the reference's reader (defect B1, Fasim-LongTarget.cpp:219-262): record
 //                           k is scanned as the concatenation of records 1..k, later headers are parsed with the stale
 //                           field counter, everything is written into ONE output set named after the first record
@@ -33,6 +37,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <map>
 #include <condition_variable>
 #include <deque>
 #include <functional>
@@ -47,7 +52,7 @@
 
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-struct DnaRecord { std::string species, chr, seq; long start = 0; };
+struct DnaRecord { std::string header, species, chr, seq; long start = 0; };
 
 static void strip_eol(std::string& s) { s.erase(std::remove(s.begin(), s.end(), '\r'), s.end()); s.erase(std::remove(s.begin(), s.end(), '\n'), s.end()); }
 
@@ -85,6 +90,7 @@ struct DnaReader {
 		r = DnaRecord();
 		if (!sticky_fields) hp = HeaderParser();
 		hp.parse(pending);
+		r.header = pending;
 		r.species = hp.species; r.chr = hp.chr; r.start = atoi(hp.start.c_str());
 		have_pending = false;
 		while (std::getline(in, line)) {
@@ -151,14 +157,16 @@ static int write_file(const std::string& path, const char* text, int64_t len)
 struct Timers { double parse = 0, scan = 0, tail = 0, write = 0, tail_wait = 0; };
 
 // -TFOsorted + the two -TFOclass files of one lncRNA (printResult(), Fasim-LongTarget.cpp:797-836): one clustering, three texts
+// (*data_lines, if given: the lines of -TFOsorted after its header line)
 static int write_outputs(const fasim_result* res, const std::string& stem, const std::string& chr, long start, int64_t dna_len,
-	const std::string& lnc_name, const fasim_params& p, int flags, Timers& tm)
+	const std::string& lnc_name, const fasim_params& p, int flags, Timers& tm, int64_t* data_lines = nullptr)
 {
 	char* text[3] = { nullptr, nullptr, nullptr }; int64_t len[3] = { 0, 0, 0 };
 	double t0 = now_s();
 	if (fasim_tail_outputs(res->recs, res->count, res->pool, res->pool_len, chr.c_str(), start, dna_len, lnc_name.c_str(), &p, flags,
 		&text[0], &len[0], &text[1], &len[1], &text[2], &len[2]) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
 	tm.tail += now_s() - t0; t0 = now_s();
+	if (data_lines) *data_lines = std::max<int64_t>(0, (int64_t)std::count(text[0], text[0] + len[0], '\n') - 1);
 	int bad = write_file(stem + "-TFOsorted", text[0], len[0]);
 	for (int level = 1; level <= 2; level++)     // print_cluster x2 (:832-836): <prefix>-TFOclass<level>-<ds>-<lg> (:706)
 		bad |= write_file(stem + "-TFOclass" + std::to_string(level) + "-" + std::to_string(p.cDistance) + "-" + std::to_string(p.cLength), text[level], len[level]);
@@ -174,7 +182,7 @@ static int g_out_failed = 0;
 
 // Scans one DNA record with every lncRNA on every device: device d takes the d-th contiguous block of segments
 // (SURVEY 8(e)); per lncRNA the shard results are merged in shard order, which is the reference's canonical order.
-static int scan_record(const std::vector<fasim_engine*>& engines, const std::vector<Rna>& rnas, const std::string& dna, const fasim_params& p,
+static int scan_record(const std::vector<fasim_engine*>& engines, const std::vector<Rna>& rnas, const char* dna, int64_t dna_len, const fasim_params& p,
 	std::vector<fasim_result*>& out)
 {
 	const int nd = (int)engines.size(), nq = (int)rnas.size();
@@ -182,10 +190,10 @@ static int scan_record(const std::vector<fasim_engine*>& engines, const std::vec
 	for (int q = 0; q < nq; q++) { qp[(size_t)q] = rnas[(size_t)q].seq.data(); ql[(size_t)q] = (int32_t)rnas[(size_t)q].seq.size(); }
 	out.assign((size_t)nq, nullptr);
 	if (nd == 1) {
-		if (fasim_scan_queries(engines[0], qp.data(), ql.data(), nq, dna.data(), (int64_t)dna.size(), 0, -1, &p, out.data()) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(engines[0])); return 1; }
+		if (fasim_scan_queries(engines[0], qp.data(), ql.data(), nq, dna, dna_len, 0, -1, &p, out.data()) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(engines[0])); return 1; }
 		return 0;
 	}
-	const int64_t nseg = fasim_segment_count((int64_t)dna.size(), &p);
+	const int64_t nseg = fasim_segment_count(dna_len, &p);
 	std::vector<std::vector<fasim_result*>> part((size_t)nd, std::vector<fasim_result*>((size_t)nq, nullptr));
 	std::vector<int> rc((size_t)nd, 0);
 	std::vector<std::thread> th;
@@ -193,7 +201,7 @@ static int scan_record(const std::vector<fasim_engine*>& engines, const std::vec
 		th.emplace_back([&, d] {
 			const int64_t base = nseg / nd, rem = nseg % nd;
 			const int64_t first = d * base + std::min<int64_t>(d, rem), count = base + (d < rem ? 1 : 0);
-			rc[(size_t)d] = fasim_scan_queries(engines[(size_t)d], qp.data(), ql.data(), nq, dna.data(), (int64_t)dna.size(), first, count, &p, part[(size_t)d].data());
+			rc[(size_t)d] = fasim_scan_queries(engines[(size_t)d], qp.data(), ql.data(), nq, dna, dna_len, first, count, &p, part[(size_t)d].data());
 		});
 	}
 	for (auto& t : th) t.join();
@@ -216,24 +224,18 @@ static int scan_record(const std::vector<fasim_engine*>& engines, const std::vec
 	return bad;
 }
 
-// --all-records: consecutive short records scanned together, one fasim_scan_records call per group (all lncRNAs, all devices).
-// out[q][r] = the records of lncRNA q in record r of the group, exactly what scan_record gives for that record alone.  With
-// several devices, device d takes the d-th contiguous block of the group's global segment list and every record's parts are
-// merged in device order.
-static int scan_group(const std::vector<fasim_engine*>& engines, const std::vector<Rna>& rnas, const std::vector<DnaRecord>& group,
-	const fasim_params& p, std::vector<std::vector<fasim_result*>>& out)
+// --all-records / --regions: consecutive short records scanned together, one fasim_scan_records call per group (all lncRNAs, all
+// devices); record r of the group is dna[off[r] .. off[r] + len[r]).  out[q][r] = the records of lncRNA q in record r of the
+// group, exactly what scan_record gives for that record alone.  With several devices, device d takes the d-th contiguous block of
+// the group's global segment list and every record's parts are merged in device order.
+static int scan_group(const std::vector<fasim_engine*>& engines, const std::vector<Rna>& rnas, const std::string& dna,
+	const std::vector<int64_t>& off, const std::vector<int64_t>& len, const fasim_params& p, std::vector<std::vector<fasim_result*>>& out)
 {
-	const int nd = (int)engines.size(), nq = (int)rnas.size(), nrec = (int)group.size();
+	const int nd = (int)engines.size(), nq = (int)rnas.size(), nrec = (int)off.size();
 	std::vector<const char*> qp((size_t)nq); std::vector<int32_t> ql((size_t)nq);
 	for (int q = 0; q < nq; q++) { qp[(size_t)q] = rnas[(size_t)q].seq.data(); ql[(size_t)q] = (int32_t)rnas[(size_t)q].seq.size(); }
-	std::string dna;
-	std::vector<int64_t> off((size_t)nrec), len((size_t)nrec);
 	int64_t nseg = 0;
-	for (int r = 0; r < nrec; r++) {
-		off[(size_t)r] = (int64_t)dna.size(); len[(size_t)r] = (int64_t)group[(size_t)r].seq.size();
-		dna += group[(size_t)r].seq;
-		nseg += fasim_segment_count(len[(size_t)r], &p);
-	}
+	for (int r = 0; r < nrec; r++) nseg += fasim_segment_count(len[(size_t)r], &p);
 	out.assign((size_t)nq, std::vector<fasim_result*>((size_t)nrec, nullptr));
 	std::vector<std::vector<fasim_result*>> part((size_t)nd, std::vector<fasim_result*>((size_t)nq * nrec, nullptr));
 	std::vector<int> rc((size_t)nd, 0);
@@ -300,7 +302,7 @@ struct TailPool {
 int main(int argc, char* const* argv)
 {
 	fasim_params p; fasim_params_default(&p);
-	std::string f1 = "./", f2 = "./", outdir = "./";
+	std::string f1 = "./", f2 = "./", outdir = "./", bed_path;
 	std::vector<int> devices(1, 0);
 	bool stats = false, all_records = false, accumulate = false, upper = false;
 	int tail_flags = 0;
@@ -311,7 +313,7 @@ int main(int argc, char* const* argv)
 		{ "cn", required_argument, NULL, 'C' }, { "ds", required_argument, NULL, 'D' }, { "lg", required_argument, NULL, 'E' },
 		{ "device", required_argument, NULL, 1001 }, { "stats", no_argument, NULL, 1002 }, { "all-records", no_argument, NULL, 1003 },
 		{ "devices", required_argument, NULL, 1004 }, { "accumulate-records", no_argument, NULL, 1005 }, { "upper", no_argument, NULL, 1006 },
-		{ "clamp-cluster", no_argument, NULL, 1007 }, { 0, 0, 0, 0 } };
+		{ "clamp-cluster", no_argument, NULL, 1007 }, { "regions", required_argument, NULL, 1008 }, { 0, 0, 0, 0 } };
 	int opt;
 	while ((opt = getopt_long_only(argc, argv, optstring, lo, NULL)) != -1) {
 		switch (opt) {
@@ -341,10 +343,17 @@ int main(int argc, char* const* argv)
 		case 1005: accumulate = true; break;
 		case 1006: upper = true; break;
 		case 1007: tail_flags |= FASIM_TAIL_CLAMP_CLUSTER; break;
-		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records] [--upper]\n"); return 2;
+		case 1008: bed_path = optarg; break;
+		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper]\n"); return 2;
 		}
 	}
 	if (all_records && accumulate) { fprintf(stderr, "fasim: --all-records and --accumulate-records exclude each other\n"); return 2; }
+	const bool regions = !bed_path.empty();
+	if (regions && (all_records || accumulate)) { fprintf(stderr, "fasim: --regions excludes --all-records and --accumulate-records\n"); return 2; }
+	// --regions: the BED file is read and checked before anything else happens (a bad file writes nothing)
+	fasim_region* reg = nullptr; int64_t nreg = 0;
+	if (regions && fasim_read_bed(bed_path.c_str(), &reg, &nreg) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 2; }
+	std::unique_ptr<fasim_region, void (*)(void*)> reg_owner(reg, fasim_free);
 	Timers tm;
 	const double t_start = now_s();
 	std::vector<Rna> rnas;
@@ -360,6 +369,29 @@ int main(int argc, char* const* argv)
 	}
 	std::cout << "Searching triplexes using Fasim" << std::endl;
 	for (const Rna& r : rnas) std::cout << r.name << std::endl;
+	const std::string base = f1.substr(0, f1.size() >= 3 ? f1.size() - 3 : 0);
+	// --regions index, one per lncRNA: <O>/<lncName>-<f1 minus 3 chars>.regions.tsv, one line per interval in BED order
+	std::vector<std::vector<int64_t>> idx_segs(rnas.size(), std::vector<int64_t>((size_t)nreg, -1)), idx_trip = idx_segs;
+	std::vector<std::vector<std::string>> idx_stem(rnas.size(), std::vector<std::string>((size_t)nreg));
+	auto write_index = [&]() -> int {
+		int bad = 0;
+		for (size_t q = 0; q < rnas.size(); q++) {
+			std::string t = "line\tname\tchrom\tstart\tend\tsegments\ttriplexes\tstem\n";
+			for (int64_t k = 0; k < nreg; k++) {
+				const fasim_region& g = reg[k];
+				t += std::to_string(g.line) + "\t" + g.name + "\t" + g.chrom + "\t" + std::to_string(g.start) + "\t" + std::to_string(g.end) + "\t";
+				if (idx_segs[q][(size_t)k] < 0) t += "NA\tNA\tNA\n";
+				else t += std::to_string(idx_segs[q][(size_t)k]) + "\t" + std::to_string(idx_trip[q][(size_t)k]) + "\t" + idx_stem[q][(size_t)k] + "\n";
+			}
+			bad |= write_file(outdir + "/" + rnas[q].name + "-" + base + ".regions.tsv", t.data(), (int64_t)t.size());
+		}
+		return bad;
+	};
+	if (regions && nreg == 0) {
+		if (write_index()) return 1;
+		std::cout << "finished normally" << std::endl;
+		return 0;
+	}
 
 	std::vector<fasim_engine*> engines;
 	for (int d : devices) {
@@ -376,8 +408,7 @@ int main(int argc, char* const* argv)
 	}
 
 	// file name: <O>/<species>-<lncName>-<f1 minus 3 chars>-TFOsorted (:123, 800-802); with --all-records the record's
-	// chr is appended to the stem so that the records of a genome do not overwrite each other
-	const std::string base = f1.substr(0, f1.size() >= 3 ? f1.size() - 3 : 0);
+	// chr is appended to the stem so that the records of a genome do not overwrite each other (--regions: <name>-...<chrom>)
 	DnaRecord rec;
 	size_t nrec = 0;
 	int64_t total_nt = 0;
@@ -398,7 +429,7 @@ int main(int argc, char* const* argv)
 			starts.push_back(rec.start);
 			t0 = now_s();
 			std::vector<fasim_result*> res;
-			if (scan_record(engines, rnas, cumulative, p, res)) return 1;
+			if (scan_record(engines, rnas, cumulative.data(), (int64_t)cumulative.size(), p, res)) return 1;
 			tm.scan += now_s() - t0;
 			total_nt += (int64_t)cumulative.size();
 			per_rec.push_back(res);
@@ -419,31 +450,36 @@ int main(int argc, char* const* argv)
 		}
 		for (auto& v : per_rec) for (fasim_result* r : v) fasim_result_free(r);
 	} else {
-		// FASIM_RECORD_GROUP = G (--all-records): consecutive records are scanned together, one fasim_scan_records call per group
-		// of about G segments; a record of >= G segments alone (a chromosome) is scanned as before.  0 = one scan per record.
-		// Default 5 120 = ten batches of 512 segments: one round of full batches for the ten workers of a scan.
+		// FASIM_RECORD_GROUP = G (--all-records, --regions): consecutive records are scanned together, one fasim_scan_records call
+		// per group of about G segments; a record of >= G segments alone (a chromosome) is scanned as before.  0 = one scan per
+		// record.  Default 5 120 = ten batches of 512 segments: one round of full batches for the ten workers of a scan.
 		long group_segs = 5120;
 		if (const char* g = getenv("FASIM_RECORD_GROUP")) group_segs = atol(g);
-		const bool grouped = all_records && group_segs > 0;
+		const bool grouped = (all_records || regions) && group_segs > 0;
 		// grouped: the tails of thousands of records go to a pool of host threads instead of four threads in flight
 		std::unique_ptr<TailPool> pool(grouped ? new TailPool(8) : nullptr);
+		// one scanned record: a DNA record, or a BED interval (species = its name, start = its 1-based start; slot = its index)
+		struct Unit { std::string species, chr; long start = 0; int64_t len = 0; size_t recno = 0; int64_t slot = -1; };
 		// per record: --stats lines, output stem, tail + write on a background thread (the next record is read and scanned meanwhile)
-		auto emit = [&](size_t recno, const DnaRecord& r, const std::vector<fasim_result*>& res) {
+		auto emit = [&](const Unit& r, const std::vector<fasim_result*>& res) {
 			for (size_t q = 0; q < rnas.size(); q++) {
 				if (stats) {
 					const fasim_scan_stats& s = res[q]->stats;
 					fprintf(stderr, "[fasim] record %zu (%s) x %s: %lld segments (%lld skipped), %lld units, %lld candidates, %lld align calls, %lld records\n",
-						recno, r.chr.c_str(), rnas[q].name.c_str(), (long long)s.segments, (long long)s.segments_skipped, (long long)s.units,
+						r.recno, r.chr.c_str(), rnas[q].name.c_str(), (long long)s.segments, (long long)s.segments_skipped, (long long)s.units,
 						(long long)s.candidates, (long long)s.align_calls, (long long)res[q]->count);
 				}
-				const std::string stem = outdir + "/" + r.species + "-" + rnas[q].name + "-" + base + (all_records ? "." + r.chr : std::string());
+				const std::string name = r.species + "-" + rnas[q].name + "-" + base + (all_records || regions ? "." + r.chr : std::string());
+				const std::string stem = outdir + "/" + name;
 				const bool twice = !stems_seen.insert(stem).second;
 				if (twice) fprintf(stderr, "fasim: warning: %s-TFOsorted is written twice (two lncRNAs or records of the same name): the later one wins\n", stem.c_str());
 				fasim_result* x = res[q];
-				const std::string chr = r.chr, lname = rnas[q].name; const long start = r.start; const int64_t dlen = (int64_t)r.seq.size();
+				int64_t* trip = nullptr;
+				if (r.slot >= 0) { idx_segs[q][(size_t)r.slot] = x->stats.segments; idx_stem[q][(size_t)r.slot] = name; trip = &idx_trip[q][(size_t)r.slot]; }
+				const std::string chr = r.chr, lname = rnas[q].name; const long start = r.start; const int64_t dlen = r.len;
 				auto job = [=, &tm, &p]() {
 					Timers mine;
-					const int bad = write_outputs(x, stem, chr, start, dlen, lname, p, tail_flags, mine);
+					const int bad = write_outputs(x, stem, chr, start, dlen, lname, p, tail_flags, mine, trip);
 					fasim_result_free(x);
 					std::lock_guard<std::mutex> lk(g_out_mu);
 					tm.tail += mine.tail; tm.write += mine.write; if (bad) g_out_failed = 1;
@@ -457,54 +493,94 @@ int main(int argc, char* const* argv)
 				}
 			}
 		};
-		std::vector<DnaRecord> group;
+		// the pending group: its records' bytes packed side by side (a group may cross DNA records)
+		std::vector<Unit> group;
+		std::string gdna;
+		std::vector<int64_t> goff, glen;
 		int64_t group_nseg = 0;
-		size_t group_first = 0, ngroups = 0;
+		size_t ngroups = 0;
 		auto flush = [&]() -> int {
 			if (group.empty()) return 0;
 			const double t0 = now_s();
 			std::vector<std::vector<fasim_result*>> res;
-			if (scan_group(engines, rnas, group, p, res)) return 1;
+			if (scan_group(engines, rnas, gdna, goff, glen, p, res)) return 1;
 			const double dt = now_s() - t0;
 			tm.scan += dt;
 			if (stats) fprintf(stderr, "[fasim] group %zu: %zu records, %lld segments, scan %.3f s\n", ngroups, group.size(), (long long)group_nseg, dt);
 			std::vector<fasim_result*> one(rnas.size());
 			for (size_t r = 0; r < group.size(); r++) {
 				for (size_t q = 0; q < rnas.size(); q++) one[q] = res[q][r];
-				emit(group_first + r, group[r], one);
-				total_nt += (int64_t)group[r].seq.size();
+				emit(group[r], one);
+				total_nt += group[r].len;
 			}
-			ngroups++; group.clear(); group_nseg = 0;
+			ngroups++; group.clear(); gdna.clear(); goff.clear(); glen.clear(); group_nseg = 0;
+			return 0;
+		};
+		// one record: into the pending group if it is short, else scanned alone (the group is scanned first, keeping record order)
+		auto add = [&](Unit u, const char* seq) -> int {
+			if (grouped) {
+				const int64_t ns = fasim_segment_count(u.len, &p);
+				if (u.len > 0 && ns < group_segs) {
+					group_nseg += ns;
+					goff.push_back((int64_t)gdna.size()); glen.push_back(u.len);
+					gdna.append(seq, (size_t)u.len);
+					group.push_back(std::move(u));
+					return group_nseg >= group_segs ? flush() : 0;
+				}
+				if (flush()) return 1;
+			}
+			const double t0 = now_s();
+			std::vector<fasim_result*> res;
+			if (scan_record(engines, rnas, seq, u.len, p, res)) return 1;
+			tm.scan += now_s() - t0;
+			total_nt += u.len;
+			emit(u, res);
 			return 0;
 		};
 		// on an error the tails of earlier records still run on their threads: a joinable std::thread must not be destroyed
 		auto stop = [&]() { for (std::thread& t : pending) t.join(); pool.reset(); return 1; };
+		// --regions: the unmatched intervals of every chromosome, by start; an interval goes to the first DNA record (file order)
+		// of its chromosome that holds it entirely.  held_start: a record held its start but ended before its end.
+		std::map<std::string, std::multimap<int64_t, int64_t>> todo;
+		std::set<std::string> chroms_seen;
+		std::vector<char> held_start((size_t)nreg, 0);
+		for (int64_t k = 0; k < nreg; k++) todo[reg[k].chrom].emplace(reg[k].start, k);
 		for (;;) {
 			double t0 = now_s();
 			if (!reader.next(rec)) break;
 			tm.parse += now_s() - t0;
+			if (regions) {
+				// '>species|chr|start-end' (a '|' in the first word; 1-based start, as the reference reads it) covers
+				// [start - 1, start - 1 + len) of chr; any other header ('>chr1 AC:CM000663.2 ...', also with a '|' in its
+				// description) names its chromosome by its first word and covers [0, len)
+				std::string chrom = rec.chr; int64_t rs = (int64_t)rec.start - 1;
+				const size_t w0 = rec.header.find_first_not_of("> \t\r");
+				const std::string word = w0 == std::string::npos ? std::string() : rec.header.substr(w0, rec.header.find_first_of(" \t\r", w0) - w0);
+				if (word.find('|') == std::string::npos) { chrom = word; rs = 0; }
+				nrec++;
+				chroms_seen.insert(chrom);
+				auto it = todo.find(chrom);
+				if (it == todo.end()) continue;
+				const int64_t re = rs + (int64_t)rec.seq.size();
+				std::vector<int64_t> mine;
+				for (auto j = it->second.lower_bound(rs); j != it->second.end() && j->first < re; ) {
+					if (reg[j->second].end <= re) { mine.push_back(j->second); j = it->second.erase(j); }
+					else { held_start[(size_t)j->second] = 1; ++j; }
+				}
+				std::sort(mine.begin(), mine.end());   // BED order within the record
+				for (int64_t k : mine) {
+					const fasim_region& g = reg[k];
+					Unit u; u.species = g.name; u.chr = g.chrom; u.start = (long)(g.start + 1); u.len = g.end - g.start; u.recno = (size_t)k; u.slot = k;
+					if (add(std::move(u), rec.seq.data() + (g.start - rs))) return stop();
+				}
+				continue;
+			}
 			if (nrec > 0 && !all_records) {
 				fprintf(stderr, "fasim: %s holds more than one record: only the first one was scanned (use --all-records; see DESIGN.md, B1)\n", f1.c_str());
 				break;
 			}
-			if (grouped) {
-				const int64_t ns = fasim_segment_count((int64_t)rec.seq.size(), &p);
-				if (!rec.seq.empty() && ns < group_segs) {
-					if (group.empty()) group_first = nrec;
-					group_nseg += ns;
-					group.push_back(std::move(rec));
-					nrec++;
-					if (group_nseg >= group_segs && flush()) return stop();
-					continue;
-				}
-				if (flush()) return stop();
-			}
-			t0 = now_s();
-			std::vector<fasim_result*> res;
-			if (scan_record(engines, rnas, rec.seq, p, res)) return stop();
-			tm.scan += now_s() - t0;
-			total_nt += (int64_t)rec.seq.size();
-			emit(nrec, rec, res);
+			Unit u; u.species = rec.species; u.chr = rec.chr; u.start = rec.start; u.len = (int64_t)rec.seq.size(); u.recno = nrec;
+			if (add(std::move(u), rec.seq.data())) return stop();
 			nrec++;
 		}
 		if (flush()) return stop();
@@ -514,6 +590,31 @@ int main(int argc, char* const* argv)
 		if (pool) pool->drain();
 		tm.tail_wait = now_s() - t_wait;
 		if (g_out_failed) return 1;
+		if (regions) {
+			if (write_index()) return 1;
+			std::vector<std::string> lost;
+			for (const auto& c : todo) for (const auto& j : c.second) {
+				const fasim_region& g = reg[j.second];
+				const char* why = held_start[(size_t)j.second] ? "runs past the end of the DNA record that holds its start"
+					: chroms_seen.count(g.chrom) ? "no DNA record of its chromosome holds it" : "no DNA record of its chromosome";
+				char buf[512];
+				snprintf(buf, sizeof buf, "fasim: BED line %lld (%s) %s:%lld-%lld: %s\n", (long long)g.line, g.name, g.chrom, (long long)g.start, (long long)g.end, why);
+				lost.emplace_back(buf);
+			}
+			if (!lost.empty()) {
+				// in BED order (the lines are numbered)
+				std::vector<std::pair<int64_t, size_t>> order;
+				size_t at = 0;
+				for (const auto& c : todo) for (const auto& j : c.second) order.emplace_back(j.second, at++);
+				std::sort(order.begin(), order.end());
+				for (size_t k = 0; k < order.size() && k < 20; k++) fputs(lost[order[k].second].c_str(), stderr);
+				if (lost.size() > 20) fprintf(stderr, "fasim: ... and %zu more\n", lost.size() - 20);
+				fprintf(stderr, "fasim: %zu of %lld BED intervals lie in no DNA record of %s: their files were not written (NA in the index)\n",
+					lost.size(), (long long)nreg, f1.c_str());
+				for (fasim_engine* e : engines) fasim_engine_destroy(e);
+				return 1;
+			}
+		}
 	}
 	if (nrec == 0) { fprintf(stderr, "fasim: no record in DNA file %s\n", f1.c_str()); return 1; }
 	for (fasim_engine* e : engines) fasim_engine_destroy(e);

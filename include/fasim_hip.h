@@ -232,7 +232,9 @@ int fasim_scan_queries(fasim_engine* e, const char* const* rnas, const int32_t* 
  * outside the resident buffer (a host buffer has no length here: the caller guarantees that `dna` holds every record); a
  * record of length 0 (fasim_scan refuses it too); a record longer than 2^31 - 1 nt.  A query above FASIM_MAX_QUERY gets
  * FASIM_E_UNSUPPORTED, and classicSim (-F) keeps its own limits.  The engine stays usable after a refusal.  The whole set
- * may be longer than 2^31 nt; only one record is limited.  Free every result with fasim_result_free. */
+ * may be longer than 2^31 nt; only one record is limited.  Free every result with fasim_result_free.
+ * The slices need not lie back to back: records may overlap, nest, repeat and come in any order, in a host buffer and in the
+ * resident buffer alike (BED intervals of one chromosome, Engine.scan_regions); each is still scanned as that slice alone. */
 int fasim_scan_records(fasim_engine* e, const char* const* rnas, const int32_t* rna_lens, int32_t nq,
                        const char* dna, const int64_t* rec_off, const int64_t* rec_len, int32_t nrec,
                        int64_t seg_first, int64_t seg_count, const fasim_params* p,
@@ -285,6 +287,20 @@ int fasim_tail_outputs(const fasim_triplex* recs, int64_t count, const char* poo
                        char** tfosorted, int64_t* tfosorted_len, char** class1, int64_t* class1_len,
                        char** class2, int64_t* class2_len);
 void fasim_free(void* p);
+/* ---- BED intervals (`fasim --regions`, read_bed() of the Python package) --------------------------------------------- */
+/* One interval of a BED file: 0-based, half-open [start, end) on `chrom`; line = its 1-based line in the file.  name = column 4,
+ * else "<chrom>_<start+1>_<end>"; an interval whose (name, chrom) pair an earlier one already has gets "_<line>" appended
+ * (repeatedly if need be), so that every interval's output stem <name>-<lnc>-<f1 stem>.<chrom> is unique. */
+typedef struct fasim_region {
+	int64_t line, start, end;
+	const char* chrom;                  /* strings live in the same block as the array */
+	const char* name;
+} fasim_region;
+/* BED3 ... BED6 and wider, whitespace-separated; columns after the 4th are ignored (the strand too: the scan covers both strands
+ * through its 48 encodings).  Blank lines, '#' lines and "track" / "browser" lines are skipped.  Refused with FASIM_E_ARG (the
+ * line number and the reason in fasim_last_error(NULL)): fewer than 3 columns, a start or end that is not an integer,
+ * start < 0, end <= start, end - start > 2^31 - 1, an unreadable file.  *out is ONE block (free it with fasim_free); *n may be 0. */
+int fasim_read_bed(const char* path, fasim_region** out, int64_t* n);
 /* ingest helper: upper-cases a DNA record in place (soft-masked genomes such as UCSC hg38 carry repeats in lower
  * case; the reference does not upper-case and treats such letters as unknown, rules.h:286-312, 82-83). */
 void fasim_upper_case(char* seq, int64_t n);
