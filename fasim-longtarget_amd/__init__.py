@@ -74,7 +74,7 @@ class ScanStats(C.Structure):
                 ("cells_stage2", C.c_int64), ("cells_stage3", C.c_int64), ("hazard_units", C.c_int64), ("rev_exact", C.c_int64),
                 ("exact_replays", C.c_int64), ("tries_skipped", C.c_int64), ("band_tries", C.c_int64), ("band_proven", C.c_int64),
                 ("band_cells", C.c_int64), ("rev_bound_passes", C.c_int64), ("striped_window_probs", C.c_int64),
-                ("striped_window_ms", C.c_double)]
+                ("striped_window_ms", C.c_double), ("dp_f16_reruns", C.c_int64)]
 
 
 class SimNode(C.Structure):
@@ -103,7 +103,7 @@ EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_e
            "fasim_calc_score_once", "fasim_ssw_pre_align", "fasim_ssw_colmax_word", "fasim_pick_candidates", "fasim_ssw_align", "fasim_pre_align_batch",
            "fasim_align_batch", "fasim_encode_unit", "fasim_sim_forward_batch", "fasim_sim_finish_unit", "fasim_scan", "fasim_scan_queries", "fasim_scan_records", "fasim_merge_results", "fasim_rebase_offsets", "fasim_load_dna", "fasim_result_free", "fasim_segment_count",
            "fasim_tfosorted", "fasim_tfoclass", "fasim_tfosorted_ex", "fasim_tfoclass_ex", "fasim_tail_outputs", "fasim_upper_case", "fasim_free",
-           "fasim_synth_dna", "fasim_selfcheck_records", "fasim_read_bed",
+           "fasim_synth_dna", "fasim_selfcheck_records", "fasim_read_bed", "fasim_maximum3_f16",
            # the reference's own ssw.h ABI (include/ssw.h)
            "ssw_init", "init_destroy", "ssw_pre_align", "ssw_align", "align_destroy", "encoded_ops"]
 
@@ -174,6 +174,7 @@ def lib():
     L.fasim_free.restype = None
     L.fasim_synth_dna.argtypes = [C.c_char_p, C.c_int64, C.c_uint64]
     L.fasim_synth_dna.restype = None
+    L.fasim_maximum3_f16.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int64]
     L.fasim_read_bed.argtypes = [C.c_char_p, C.POINTER(C.POINTER(_Region)), C.POINTER(C.c_int64)]
     _lib = L
     return L
@@ -408,6 +409,15 @@ class Engine:
     def set_query(self, rna: bytes):
         self._check(self._L.fasim_set_query(self._h, rna, len(rna)))
         self.m = len(rna)
+
+    def maximum3_f16(self, a, b, c):
+        """v_pk_maximum3_f16 on numpy uint32 arrays of packed f16 pairs: (maximum3(a, b, c), maximum3(a, b, +0))."""
+        import numpy as np
+        a, b, c = (np.ascontiguousarray(x, dtype=np.uint32) for x in (a, b, c))
+        out3, out0 = np.empty_like(a), np.empty_like(a)
+        self._check(self._L.fasim_maximum3_f16(self._h, a.ctypes.data, b.ctypes.data, c.ctypes.data, out3.ctypes.data,
+                                               out0.ctypes.data, a.size))
+        return out3, out0
 
     # --- single-problem drop-ins ------------------------------------------------------------------
     def calc_score_once(self, target: bytes) -> int:

@@ -25,6 +25,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "kernels.h"
+#include "dp_f16.h"
 
 namespace fasim {
 
@@ -68,6 +69,7 @@ constexpr int AL_LANE_STRIDE = 112;
 constexpr int AL_CODE_STRIDE = 64 * AL_LANE_STRIDE;
 constexpr int AL_SCALE = 32;                 // DP values are multiples of 32
 constexpr int AL_NEG = -32768;               // void / dead score: H <= 31360 so H + AL_NEG < 0 always
+constexpr int AL_NEG_F16 = -4096;            // the same for the f16 reverse pass (values x 1, H <= 1000)
 constexpr int CODE_VOID = 4;                 // stream codes: A0 C1 G2 T3, 4 = void column (between windows), 5 = N
 constexpr int CODE_SN = 5;                   // (the unit codes of kernels.h use 4 for N: k_build_stream re-codes)
 constexpr int TAG_LAST = 8;                  // bit 3 of a stream byte: last column of a window
@@ -152,10 +154,14 @@ __device__ __forceinline__ int fwd_cell_score(const FwdArgs& a, int t, int v, in
 constexpr int FWD_THREADS = 512;
 // REV (plain variant only): the reverse pass.  It wants the lane maxima per zone and nothing else, so the row tags of the keys,
 // the key hand-over between lanes and the whole pipe end are left out (about 35 of 380 instructions per step).
-template <int RP, bool TAINT, bool REV = false>
+// F16 (reverse pass only): the DP values are carried x 1 as f16 integers and the row pair uses v_pk_maximum3_f16 (dp_f16.h).
+// A window holds at most 200 columns, so every score is <= 1000 and every intermediate value an exact f16 integer; the
+// lane maxima leave as the same u16 integers as from the integer variant.
+template <int RP, bool TAINT, bool REV = false, bool F16 = false>
 __global__ void __launch_bounds__(FWD_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) k_align_fwd(FwdArgs a)
 {
 	static_assert(!(TAINT && REV), "the reverse pass is a plain pass");
+	static_assert(!F16 || REV, "only the reverse pass has an f16 variant");
 	constexpr int SC = TAINT ? 2 * AL_SCALE : AL_SCALE;      // value scale; TAINT: bit 5 = taint, bits 0..4 = row tag
 	extern __shared__ __align__(16) uint8_t prof[];
 	const int lane = threadIdx.x & 63;
@@ -165,7 +171,8 @@ __global__ void __launch_bounds__(FWD_THREADS) __attribute__((amdgpu_waves_per_e
 			const int r = idx % AL_RS;
 			const int v = (idx / AL_RS) % 128;
 			const int t = idx / (AL_RS * 128);
-			const int sc = fwd_cell_score(a, t, 128 * a.tile + v, r, SC);
+			int sc = fwd_cell_score(a, t, 128 * a.tile + v, r, F16 ? 1 : SC);
+			if (F16) sc = (int)(int16_t)f16_bits(sc == AL_NEG ? AL_NEG_F16 : sc);
 			*reinterpret_cast<int16_t*>(prof + t * AL_CODE_STRIDE + (v >> 1) * AL_LANE_STRIDE + (v & 1) * 48 + r * 2) = (int16_t)sc;
 		}
 	}
@@ -241,9 +248,20 @@ __global__ void __launch_bounds__(FWD_THREADS) __attribute__((amdgpu_waves_per_e
 			const uint32_t kin_lo = kup, kin_hi = klo;       // from virtual lane v-1 (same column, one step ago)
 			const v2u tt = u_from(tc) & (v2u){ 7, 7 };                       // stream codes of my two halves
 			// void columns clear E and F: the saturating subtractions use 0xFFFF instead of 4*SC / 16*SC
-			const v2u isvoid = (v2u){ 0, 0 } - __builtin_elementwise_sub_sat((v2u){ 1, 1 }, tt ^ (v2u){ CODE_VOID, CODE_VOID });
-			const v2u dec = isvoid | (v2u){ GAP_EXT * SC, GAP_EXT * SC };
-			const v2u gapo = isvoid | (v2u){ GAP_OPEN * SC, GAP_OPEN * SC };
+			v2u isvoid = (v2u){ 0, 0 }, dec, gapo, live01 = (v2u){ 0, 0 };
+			if constexpr (F16) {
+				// f16: they subtract +inf instead; E, F and H are finite, so no NaN arises, and max3(-inf, -inf, 0) = 0.
+				// (0 / 1 flags from the asm helpers and products with them: the compiler turns masks into per-half selects)
+				const v2u notvoid = tt ^ (v2u){ CODE_VOID, CODE_VOID };
+				const v2u vinf = apk_ksubs(0x00010001u, notvoid) * (v2u){ 0x7C00, 0x7C00 };
+				dec = vinf | u_from((int)f16c2(GAP_EXT));
+				gapo = vinf | u_from((int)f16c2(GAP_OPEN));
+				live01 = apk_minu_k(notvoid, 0x00010001u);
+			} else {
+				isvoid = (v2u){ 0, 0 } - __builtin_elementwise_sub_sat((v2u){ 1, 1 }, tt ^ (v2u){ CODE_VOID, CODE_VOID });
+				dec = isvoid | (v2u){ GAP_EXT * SC, GAP_EXT * SC };
+				gapo = isvoid | (v2u){ GAP_OPEN * SC, GAP_OPEN * SC };
+			}
 			const int hdiag0 = recv_h_last;
 			recv_h_last = recv_h;
 			v2u f = u_from(recv_f);
@@ -271,6 +289,35 @@ __global__ void __launch_bounds__(FWD_THREADS) __attribute__((amdgpu_waves_per_e
 				else asm("v_pk_add_i16 %0, %1, %0" : "+v"(sc) : "v"(hold));
 				return s_fromi(sc);
 			};
+			v2s lkey;
+			if constexpr (F16) {
+				// the f16 row pair (dp_f16.h): 8.5 instructions where the integer one below takes 10
+				int ff = recv_f, lk0 = 0, lk1 = 0, hprev = 0;
+				int t = hf_diag_plus_score(hdiag0, score_of(0));
+#pragma unroll
+				for (int r = 0; r < RP; r++) {
+					int tnext = t;
+					if (r + 1 < RP) tnext = hf_diag_plus_score(H[r], score_of(r + 1));
+					const int h = hf_h(H[r], t, E[r], ff, tnext);
+					H[r] = h;
+					const int ho = hf_sub(h, a_i(gapo));
+					E[r] = hf_max_floor(hf_sub(E[r], a_i(dec)), ho);
+					const int fnew = hf_max_floor(hf_sub(ff, a_i(dec)), ho);
+					int hm = h;             // what the lane maximum sees of this row
+					if (r == RP - 1) {
+						ff = (fnew & (int)act) | (ff & ~(int)act);
+						hm = h & (int)act;
+						if (RP > 1) hbot = hm | (H[RP > 1 ? RP - 2 : 0] & ~(int)act);
+						else hbot = h;
+					} else ff = fnew;
+					// one max3 per two rows, two independent chains
+					if (r & 1) { if (r & 2) lk1 = hf_max3(lk1, hprev, hm); else lk0 = hf_max3(lk0, hprev, hm); }
+					hprev = hm;
+					t = tnext;
+				}
+				lkey = s_fromi((RP & 1) ? hf_max3(lk0, lk1, hprev) : hf_max_floor(lk0, lk1));
+				f = u_from(ff);
+			} else {
 			v2s t = diag_plus_score(hdiag0, score_of(0));
 #pragma unroll
 			for (int r = 0; r < RP; r++) {
@@ -294,7 +341,8 @@ __global__ void __launch_bounds__(FWD_THREADS) __attribute__((amdgpu_waves_per_e
 				}
 				t = tnext;
 			}
-			const v2s lkey = __builtin_elementwise_max(__builtin_elementwise_max(lkx[0], lkx[1]), __builtin_elementwise_max(lkx[2], lkx[3]));
+			lkey = __builtin_elementwise_max(__builtin_elementwise_max(lkx[0], lkx[1]), __builtin_elementwise_max(lkx[2], lkx[3]));
+			}
 			asm volatile("" :: "v"(a_i(lkey)));      // pin the reduction before the hazard branch (see scan.hip)
 			fbot = a_i(f);
 			if constexpr (REV) {
@@ -303,20 +351,35 @@ __global__ void __launch_bounds__(FWD_THREADS) __attribute__((amdgpu_waves_per_e
 					const v2u tcu = u_from(tc);
 					const v2u zz = (tcu >> (v2u){ 5, 5 }) & (v2u){ 3, 3 };
 					// (not the void columns: in the first one H still shows the E values the previous window left behind)
+					v2u lastb;
+					if constexpr (F16) {
+						// the maxima are non-negative, so their bit patterns order like the values: the zone maxima stay u16 maxima of the
+						// bits and become integers at the store.  A zone takes the value times its 0 / 1 flag (zone >= 1, >= 2, == 3).
+						const v2u val = a_u(lkey) * live01;
+						const v2u ge2 = zz >> (v2u){ 1, 1 };
+						zacc0 = __builtin_elementwise_max(zacc0, val);
+						zacc1 = __builtin_elementwise_max(zacc1, val * apk_minu_k(zz, 0x00010001u));
+						zacc2 = __builtin_elementwise_max(zacc2, val * ge2);
+						zacc3 = __builtin_elementwise_max(zacc3, val * (zz & ge2));
+						lastb = tcu & (v2u){ TAG_LAST, TAG_LAST };
+					} else {
 					const v2u val = (a_u(lkey) >> (v2u){ 5, 5 }) & ~isvoid;
 					zacc0 = __builtin_elementwise_max(zacc0, val);
 					zacc1 = __builtin_elementwise_max(zacc1, val & ((v2u){ 0, 0 } - __builtin_elementwise_min(zz, (v2u){ 1, 1 })));
 					zacc2 = __builtin_elementwise_max(zacc2, val & ((v2u){ 0, 0 } - __builtin_elementwise_min(__builtin_elementwise_sub_sat(zz, (v2u){ 1, 1 }), (v2u){ 1, 1 })));
 					zacc3 = __builtin_elementwise_max(zacc3, val & ((v2u){ 0, 0 } - __builtin_elementwise_sub_sat(zz, (v2u){ 2, 2 })));
-					const v2u lastb = (tcu >> (v2u){ 3, 3 }) & (v2u){ 1, 1 };
+					lastb = (tcu >> (v2u){ 3, 3 }) & (v2u){ 1, 1 };
+					}
 					if (__builtin_amdgcn_ballot_w64(a_i(lastb) != 0) != 0ull) {
+						if (F16) lastb = lastb >> (v2u){ 3, 3 };
 #pragma unroll
 						for (int h = 0; h < 2; h++) {
 							if (lastb[h]) {
 								const int slot = a.ub_slot[p0 + (int)wcnt[h]];
 								if (slot >= 0) {
 									uint16_t* o = a.lane_ub + (size_t)slot * 4 * a.nv + 128 * a.tile + 2 * lane + h;
-									o[0] = zacc0[h]; o[a.nv] = zacc1[h]; o[2 * (size_t)a.nv] = zacc2[h]; o[3 * (size_t)a.nv] = zacc3[h];
+									if (F16) { o[0] = (uint16_t)f16_int(zacc0[h]); o[a.nv] = (uint16_t)f16_int(zacc1[h]); o[2 * (size_t)a.nv] = (uint16_t)f16_int(zacc2[h]); o[3 * (size_t)a.nv] = (uint16_t)f16_int(zacc3[h]); }
+									else { o[0] = zacc0[h]; o[a.nv] = zacc1[h]; o[2 * (size_t)a.nv] = zacc2[h]; o[3 * (size_t)a.nv] = zacc3[h]; }
 								}
 							}
 						}
@@ -434,7 +497,7 @@ __global__ void __launch_bounds__(FWD_THREADS) __attribute__((amdgpu_waves_per_e
 	}
 }
 
-template <int RP, bool TAINT, bool REV = false>
+template <int RP, bool TAINT, bool REV = false, bool F16 = false>
 static hipError_t launch_fwd_t(const FwdArgs& a, hipStream_t st)
 {
 	hipError_t err = hipMemsetAsync(a.counter, 0, sizeof(uint32_t), st);
@@ -443,7 +506,7 @@ static hipError_t launch_fwd_t(const FwdArgs& a, hipStream_t st)
 	constexpr int WPB = FWD_THREADS / 64;
 	long blocks = ((long)a.ntask + WPB - 1) / WPB;
 	if (blocks > 256 * 2) blocks = 256 * 2;
-	hipLaunchKernelGGL((k_align_fwd<RP, TAINT, REV>), dim3((unsigned)blocks), dim3(FWD_THREADS), (size_t)6 * AL_CODE_STRIDE, st, a);
+	hipLaunchKernelGGL((k_align_fwd<RP, TAINT, REV, F16>), dim3((unsigned)blocks), dim3(FWD_THREADS), (size_t)6 * AL_CODE_STRIDE, st, a);
 	return hipGetLastError();
 }
 
@@ -462,7 +525,7 @@ hipError_t launch_align_fwd(const FwdLaunch& L, hipStream_t st)
 		a.tile = t;
 		hipError_t err = hipErrorInvalidValue;
 		switch (rp) {
-#define FASIM_FWD_CASE(N) case N: err = a.lane_ub ? launch_fwd_t<N, false, true>(a, st) : (L.word ? launch_fwd_t<N, false>(a, st) : launch_fwd_t<N, true>(a, st)); break;
+#define FASIM_FWD_CASE(N) case N: err = a.lane_ub ? (L.f16 ? launch_fwd_t<N, false, true, true>(a, st) : launch_fwd_t<N, false, true>(a, st)) : (L.word ? launch_fwd_t<N, false>(a, st) : launch_fwd_t<N, true>(a, st)); break;
 		FASIM_FWD_CASE(1) FASIM_FWD_CASE(2) FASIM_FWD_CASE(3) FASIM_FWD_CASE(4) FASIM_FWD_CASE(5) FASIM_FWD_CASE(6)
 		FASIM_FWD_CASE(7) FASIM_FWD_CASE(8) FASIM_FWD_CASE(9) FASIM_FWD_CASE(10) FASIM_FWD_CASE(11) FASIM_FWD_CASE(12)
 		FASIM_FWD_CASE(13) FASIM_FWD_CASE(14) FASIM_FWD_CASE(15) FASIM_FWD_CASE(16) FASIM_FWD_CASE(17) FASIM_FWD_CASE(18)

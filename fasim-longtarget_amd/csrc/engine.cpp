@@ -97,7 +97,7 @@ void fasim_engine_destroy(fasim_engine* e)
 		&e->unit_first, &e->hz_cols, &e->hz_plan, &e->hz_base, &e->hz_items, &e->snap, &e->hz_state, &e->hz_rows, &e->hz_chunk, &e->hz_src, &e->hz_zero,
 		&e->qsim, &e->sim_min, &e->sim_row, &e->sim_ev, &e->sim_cnt, &e->sim_nodes,
 		&e->ublk, &e->btarget, &e->bidx, &e->bcounts, &e->blist[0], &e->blist[1], &e->blist[2], &e->bslots[0], &e->bslots[1], &e->bslots[2],
-		&e->bprev, &e->lane_ub, &e->fzones, &e->fubslot, &e->bdec, &e->btab, &e->swin };
+		&e->bprev, &e->lane_ub, &e->fzones, &e->fubslot, &e->bdec, &e->btab, &e->swin, &e->unit_ovf };
 	for (auto& t : e->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
 	for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
 	for (DevBuf* b : bufs) b->release();
@@ -121,6 +121,7 @@ int fasim_set_option(fasim_engine* E, const char* key, int32_t value)
 	else if (!strcmp(key, "host_threads")) { if (value > 0) { E->host_threads = value; E->host_threads_total = value; E->host_threads_explicit = true; } }   // host side of the batches (all workers together)
 	else if (!strcmp(key, "numa_affinity")) E->opt_numa = value != 0;
 	else if (!strcmp(key, "band")) E->opt_band = value;                   // banded stage-3 forward pass: 0 off, 1 on (-1: default / FASIM_BAND)
+	else if (!strcmp(key, "dp_f16")) E->opt_dp_f16 = value;               // 1: packed-f16 k_scan and reverse pass (default), 0: the integer kernels (-1: default / FASIM_DP_F16)
 	else if (!strcmp(key, "striped_window")) E->striped_window = value > 0;   // 1: every k_striped launch on the HBM-window variant (tests)
 	else return fail(E, FASIM_E_ARG, "unknown option %s", key);
 	return FASIM_OK;
@@ -400,6 +401,26 @@ void fasim_result_free(fasim_result* r)
 }
 
 void fasim_free(void* p) { free(p); }
+
+int fasim_maximum3_f16(fasim_engine* E, const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* out3, uint32_t* out0, int64_t n)
+{
+	if (!E || !a || !b || !c || !out3 || !out0 || n <= 0 || n > (1ll << 28)) return fail(E, FASIM_E_ARG, "bad arguments");
+	HIPOK(hipSetDevice(E->device));
+	const size_t bytes = sizeof(uint32_t) * (size_t)n;
+	DevBuf d[5];
+	int rc = FASIM_OK;
+	for (int k = 0; k < 5 && !rc; k++) if (d[k].ensure(bytes) != hipSuccess) rc = fail(E, FASIM_E_HIP, "out of device memory");
+	const uint32_t* src[3] = { a, b, c };
+	for (int k = 0; k < 3 && !rc; k++) if (hipMemcpyAsync(d[k].p, src[k], bytes, hipMemcpyHostToDevice, E->st) != hipSuccess) rc = fail(E, FASIM_E_HIP, "copy failed");
+	if (!rc && launch_maximum3_f16(d[0].as<uint32_t>(), d[1].as<uint32_t>(), d[2].as<uint32_t>(), d[3].as<uint32_t>(), d[4].as<uint32_t>(), n, E->st) != hipSuccess)
+		rc = fail(E, FASIM_E_HIP, "maximum3 launch failed");
+	if (!rc && (hipMemcpyAsync(out3, d[3].p, bytes, hipMemcpyDeviceToHost, E->st) != hipSuccess ||
+	            hipMemcpyAsync(out0, d[4].p, bytes, hipMemcpyDeviceToHost, E->st) != hipSuccess ||
+	            hipStreamSynchronize(E->st) != hipSuccess)) rc = fail(E, FASIM_E_HIP, "copy back failed");
+	(void)hipStreamSynchronize(E->st);
+	for (DevBuf& x : d) x.release();
+	return rc;
+}
 
 void fasim_synth_dna(char* out, int64_t n, uint64_t seed)
 {

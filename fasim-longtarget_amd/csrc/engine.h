@@ -129,6 +129,8 @@ struct fasim_engine {
 	DevBuf ublk, btarget, bidx, bcounts, blist[3], bslots[3], bprev, lane_ub, fzones, fubslot, bdec, btab;
 	int ublk_units = 0, ublk_blocks = 0;         // units covered by `ublk` (0: none), blocks per (unit, tile)
 	int opt_band = -1;                           // option "band": 0 off, 1 on (-1 = default / environment FASIM_BAND)
+	int opt_dp_f16 = -1;                         // option "dp_f16": packed-f16 k_scan and reverse pass, 0 = the integer kernels (-1 = default / environment FASIM_DP_F16)
+	DevBuf unit_ovf;                             // [unit] != 0: the f16 k_scan saw a value outside its exact range
 	int opt_numa = 1;                            // option "numa_affinity": pin the scan's host threads to the GPU's NUMA node (no-op on one node)
 	// HBM-window variant of k_striped (queries whose stripes do not fit the LDS): its scratch, the forcing switch (option
 	// "striped_window" / FASIM_STRIPED_WINDOW=1: every stripe-faithful launch takes it, for tests), problems run on it and its
@@ -293,6 +295,13 @@ inline int band_mode(const fasim_engine* E)
 {
 	static const int env = [] { const char* e = getenv("FASIM_BAND"); return e ? atoi(e) : 1; }();
 	return E->opt_band >= 0 ? E->opt_band : env;
+}
+// option dp_f16 / FASIM_DP_F16: 1 (default) = k_scan's main pass and the reverse pass of stage 3 run their packed-f16 variants
+// (dp_f16.h); 0 = the integer kernels.  The records are the same either way.
+inline bool dp_f16_mode(const fasim_engine* E)
+{
+	static const int env = [] { const char* e = getenv("FASIM_DP_F16"); return e ? atoi(e) : 1; }();
+	return (E->opt_dp_f16 >= 0 ? E->opt_dp_f16 : env) != 0;
 }
 inline int band_mask(const fasim_engine* E)
 {

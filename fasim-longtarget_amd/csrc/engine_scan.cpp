@@ -558,6 +558,7 @@ static void add_stats(fasim_scan_stats& st, const fasim_scan_stats& x)
 	st.exact_replays += x.exact_replays; st.tries_skipped += x.tries_skipped;
 	st.band_tries += x.band_tries; st.band_proven += x.band_proven; st.band_cells += x.band_cells; st.rev_bound_passes += x.rev_bound_passes;
 	st.striped_window_probs += x.striped_window_probs; st.striped_window_ms += x.striped_window_ms;
+	st.dp_f16_reruns += x.dp_f16_reruns;
 	for (int k = 0; k < FASIM_KERNEL_FAMILIES; k++) { st.kernel_ms[k] += x.kernel_ms[k]; st.kernel_launches[k] += x.kernel_launches[k]; }
 }
 
@@ -716,7 +717,7 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 		for (fasim_engine* w : ws) {
 			w->gate = (ws.size() > 1 && E->own_gate.cap > 0) ? &E->own_gate : nullptr;
 			w->scan_v1 = E->scan_v1; w->align_v1 = E->align_v1; w->striped_window = E->striped_window;
-			w->hz_chunks = E->hz_chunks; w->hz_snap = E->hz_snap; w->hz_target = E->hz_target; w->hz_hot_w = E->hz_hot_w; w->opt_band = E->opt_band;
+			w->hz_chunks = E->hz_chunks; w->hz_snap = E->hz_snap; w->hz_target = E->hz_target; w->hz_hot_w = E->hz_hot_w; w->opt_band = E->opt_band; w->opt_dp_f16 = E->opt_dp_f16;
 			w->host_threads = std::max(1, E->host_threads_total / nworkers);
 			w->host_threads_share_total = E->host_threads_total; w->active_workers = &active_workers; w->sim_in_flight = &sim_active; w->scan_workers = (int)ws.size();
 			{

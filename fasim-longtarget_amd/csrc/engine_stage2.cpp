@@ -320,12 +320,41 @@ int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& un
 			L.ublk = E->ublk.as<uint16_t>(); L.ublk_blocks = nb; E->ublk_units = nu; E->ublk_blocks = nb;
 		} else (void)hipGetLastError();
 	}
+	// the main pass in packed f16 (option dp_f16): exact while every score of a unit stays below 1 024; the kernel flags the others
+	if (dp_f16_mode(E)) {
+		HIPOK(E->unit_ovf.ensure(sizeof(int32_t) * nu));
+		HIPOK(hipMemsetAsync(E->unit_ovf.p, 0, sizeof(int32_t) * nu, E->st));
+		L.f16 = 1; L.unit_ovf = E->unit_ovf.as<int32_t>();
+	}
 	{
 		GateScope gate(E);
 		{ TimedScope ts(E, 0, E->st); he = launch_scan(L, E->st); }
 		if (he == hipErrorInvalidValue) return 1;
 		if (he != hipSuccess) return fail(E, FASIM_E_HIP, "scan launch failed: %s", hipGetErrorString(he));
 		HIPOK(hipStreamSynchronize(E->st));
+	}
+	if (L.f16) {
+		// units that left the exact range of the f16 pass: everything it wrote for them (column maxima, block maxima, snapshots,
+		// hazard flag, first hazard step) is void; the integer kernel runs them again and rewrites all of it
+		std::vector<int32_t> ovf(nu), again;
+		HIPOK(hipMemcpyAsync(ovf.data(), E->unit_ovf.p, sizeof(int32_t) * nu, hipMemcpyDeviceToHost, E->st));
+		HIPOK(hipStreamSynchronize(E->st));
+		for (int u = 0; u < nu; u++) if (ovf[u]) again.push_back(u);
+		L.f16 = 0; L.unit_ovf = nullptr;        // (L goes on to the checkpoint pass of the hazard re-run)
+		if (!again.empty()) {
+			for (int u : again) {
+				HIPOK(hipMemsetAsync(E->unit_hz.as<int32_t>() + u, 0, sizeof(int32_t), E->st));
+				HIPOK(hipMemsetAsync(E->unit_first.as<int32_t>() + u, 0x7f, sizeof(int32_t), E->st));
+			}
+			rc = upload(E, E->unit_ovf, again.data(), sizeof(int32_t) * again.size()); if (rc) return rc;      // (the flags have been read: the buffer now holds the work list)
+			ScanLaunch L2 = L;
+			L2.unit_ids = E->unit_ovf.as<int32_t>(); L2.nwork = (int)again.size();
+			GateScope gate(E);
+			{ TimedScope ts(E, 0, E->st); he = launch_scan(L2, E->st); }
+			if (he != hipSuccess) return fail(E, FASIM_E_HIP, "scan (integer re-run) launch failed: %s", hipGetErrorString(he));
+			HIPOK(hipStreamSynchronize(E->st));
+			if (st) st->dp_f16_reruns += (int64_t)again.size();      // (cells_stage2 stays the count of one pass over every unit)
+		}
 	}
 
 	HIPOK(E->hit_off.ensure(sizeof(int32_t) * nu)); HIPOK(E->hit_cnt.ensure(sizeof(int32_t) * nu));

@@ -81,6 +81,11 @@ struct ScanLaunch {
 	// block maxima for the banded stage 3 (band.hip): [unit][tile][ublk_blocks][64 lanes] x 2 bytes; NULL: not wanted
 	uint16_t* ublk = nullptr;
 	int32_t ublk_blocks = 0;
+	// packed-f16 variant of the main pass (option dp_f16; ignored by the checkpoint variant): exact while every score stays below
+	// 1 024.  unit_ovf[unit] (zeroed by the caller) is set to 1 for a unit that left that range: everything the pass wrote for it is
+	// void and the caller runs it again with f16 = 0
+	int32_t f16 = 0;
+	int32_t* unit_ovf = nullptr;
 };
 constexpr int SCAN_UBLK_STEPS = 64;       // pipeline steps per block of maxima
 inline int scan_ublk_blocks(int tstride) { return (tstride + 127 + SCAN_UBLK_STEPS - 1) / SCAN_UBLK_STEPS; }
@@ -93,6 +98,8 @@ hipError_t launch_scan(const ScanLaunch& L, hipStream_t st);      // hipErrorInv
 hipError_t launch_scan_post(const uint16_t* colmax16, const int32_t* unit_ids, int32_t nwork, const int32_t* unit_len,
 	int32_t tstride, const int32_t* stage1_in, uint32_t* hits, uint32_t hits_cap, uint32_t* hits_total, int32_t* hit_off,
 	int32_t* hit_cnt, int32_t* thr_out, int32_t* stage1_out, int32_t* flags, const int32_t* unit_hz, hipStream_t st);
+// v_pk_maximum3_f16 on n packed pairs (device pointers): out3 = maximum3(a, b, c), out0 = maximum3(a, b, +0); see dp_f16.h
+hipError_t launch_maximum3_f16(const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* out3, uint32_t* out0, int64_t n, hipStream_t st);
 hipError_t launch_max16(const uint16_t* colmax16, const int32_t* unit_ids, int32_t nwork, const int32_t* unit_len,
 	int32_t tstride, int32_t* out, hipStream_t st);
 
@@ -105,6 +112,7 @@ struct FwdLaunch {
 	// reverse pass (word == 1, lane_ub != NULL): reversed query against reversed windows; leaves per window (slot ub_slot[k], -1:
 	// none) and zone 0..3 the per-lane maxima [slot][4][128 * tiles] and writes no FwdOut
 	uint16_t* lane_ub = nullptr; const int32_t* ub_slot = nullptr;
+	int32_t f16 = 0;      // reverse pass only: 1 = the packed-f16 variant (option dp_f16), same lane maxima
 };
 // zones: NULL, or (reverse pass) per window the lengths of the candidate's next three tries (bytes 0..2; 0 = none): the stream then
 // holds the REVERSED window with the zone of every column in bits 5-6

@@ -35,6 +35,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "kernels.h"
+#include "dp_f16.h"
 
 namespace fasim {
 
@@ -88,6 +89,17 @@ constexpr int SCAN_RS = 24;                 // storage rows per virtual lane in 
 constexpr int SCAN_LANE_STRIDE = 112;       // bytes: 2 halves x 24 rows x 2 B + 16 B pad (bank-conflict-free b128)
 constexpr int SCAN_CODE_STRIDE = 64 * SCAN_LANE_STRIDE;   // 7168 B, a multiple of the 256-B bank row
 constexpr int SCAN_DEAD = -16384;           // score of rows beyond the padded query: can never be chosen
+constexpr int SCAN_DEAD_F16 = -4096;        // the same for the f16 variant, whose values stay below 2048 (far from -inf: nothing may produce inf or NaN)
+
+// a packed pair of f16 integers -> the packed pair of u16 integers (inline asm: used in rare branches only, see pk_subs; volatile:
+// the conversions of a whole H / E column must stay where they are written, one at a time, or their results all live at once
+// and the register allocator spills in the common path)
+__device__ __forceinline__ int hf_to_u16(int x)
+{
+	int r;
+	asm volatile("v_cvt_u16_f16_e32 %0, %1\n\tv_cvt_u16_f16_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1\n\ts_nop 0" : "=&v"(r) : "v"(x));
+	return r;
+}
 
 struct ScanArgs {
 	const uint8_t* tcodes;       // [unit][tstride]
@@ -123,6 +135,7 @@ struct ScanArgs {
 	// lanes and the steps of the block; virtual lane v of the tile sees column c at step c + v.  [unit][tile][block][64 lanes]; NULL: not wanted
 	uint16_t* ublk;
 	int32_t ublk_blocks;         // blocks per (unit, tile) in the buffer
+	int32_t* unit_ovf;           // F16 variant: [unit] = 1 when some H left the exact range (>= 2048 as carried): the unit's outputs are void
 };
 
 // rows owned by global virtual lane v (stripe-aligned layout): stripe s = v / vs gets its ceil(m/16) rows spread over
@@ -148,9 +161,18 @@ __device__ __forceinline__ int scan_cell_score(const ScanArgs& a, int t, int v, 
 // One 256-thread workgroup shares the per-code int16 profile (35 KB); the two halves of a lane fetch their own code's rows and a
 // v_perm_b32 per row merges them.  (A variant with the profile stored per PAIR of codes -- no perm, 109 KB of LDS, 1024-thread
 // workgroups -- was 5 % faster alone and 1-4 % slower with ten batches in flight; it was removed in round 3.)
-template <int RP, bool DUMP = false>
+//
+// F16 (main pass only): the same values, "2 x value + taint bit", carried as f16 integers, with the row pair of dp_f16.h.  An odd
+// value is tainted: doubled scores and gap costs are even, so parity rides through add and subtract as the bit does, and
+// 2h + 1 > 2h, so a maximum prefers the tainted operand.  All of it is exact while values stay <= 2047 (scores <= 1023).
+// Rounding above 2048 is monotone and every H is seen by the block maxima, so a unit that ever held a value outside the exact
+// range shows a block maximum >= 2048: it is flagged in unit_ovf, its outputs are void, and the host runs it again on the
+// integer kernel.  Everything that leaves the pipe (column maxima, block maxima, snapshots) leaves as the integers of the
+// integer kernel; the hand-over between query tiles carries the f16 bits.
+template <int RP, bool DUMP = false, bool F16 = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ? 1 : 4, DUMP ? 2 : 4))) k_scan(ScanArgs a)
 {
+	static_assert(!(F16 && DUMP), "the checkpoint pass is an integer pass");
 	extern __shared__ __align__(16) uint8_t prof[];
 	const int lane = threadIdx.x & 63;
 
@@ -162,7 +184,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 			const int r = idx % SCAN_RS;
 			const int v = (idx / SCAN_RS) % 128;
 			const int t = idx / (SCAN_RS * 128);
-			const int sc = scan_cell_score(a, t, 128 * a.tile + v, r);
+			int sc = scan_cell_score(a, t, 128 * a.tile + v, r);
+			if (F16) sc = (int)(int16_t)f16_bits(sc == SCAN_DEAD ? SCAN_DEAD_F16 : sc);
 			*reinterpret_cast<int16_t*>(prof + t * SCAN_CODE_STRIDE + (v >> 1) * SCAN_LANE_STRIDE + (v & 1) * 48 + r * 2) = (int16_t)sc;
 		}
 	}
@@ -177,7 +200,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 		const int v = 128 * a.tile + 2 * lane + h;        // global virtual lane
 		int row0, rows_v;
 		lane_rows(v, a.seg_len16, a.vs, &row0, &rows_v);
-		if (v % a.vs == 0 && v > 0) { fthr = (fthr & ~(0xFFFFu << (16 * h))) | (263u << (16 * h)); startbits |= 0xFFFFu << (16 * h); }
+		if (v % a.vs == 0 && v > 0) { fthr = (fthr & ~(0xFFFFu << (16 * h))) | ((F16 ? f16c(263u) : 263u) << (16 * h)); startbits |= 0xFFFFu << (16 * h); }
 		if (rows_v == RP) act |= 0xFFFFu << (16 * h);
 	}
 	const v2u fthr2 = __builtin_bit_cast(v2u, fthr);
@@ -214,6 +237,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 		int chunk = CODE_N;
 		int first_enter = 0x7fffffff;          // first step of this unit in which the hazard branch ran (wave-uniform)
 		v2u ubacc = (v2u){ 0, 0 };             // running maximum of the current block of steps (banded stage 3)
+		bool ovf = false;                      // F16: some block maximum of this unit reached 2048, the end of the exact range (wave-uniform)
 		// DUMP only: the reference's OWN E.  Its lazy-F loop corrects H but not E (sswNew.cpp:355: "don't update E"), so E follows
 		// the H of the main pass, which only knows the F chain restarted at the top of each stripe (Fm).  The H values are the
 		// same either way (a gap pair in the order down-right scores what right-down scores), the E array is not, and a
@@ -292,6 +316,36 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 			// (the sum is forced into the register of the score, which dies there: the compiler would otherwise add in place
 			//  over the old H, keep that register busy until the next row and have to park the new H somewhere else)
 			auto diag_plus_score = [](int hold, int sc) -> v2s { asm("v_pk_add_i16 %0, %1, %0 clamp" : "+v"(sc) : "v"(hold)); return s_from(sc); };
+			v2s lmax;
+			if constexpr (F16) {
+				// the f16 row pair (dp_f16.h): 8.5 instructions where the integer one below takes 10
+				constexpr uint32_t KEXT = f16c2(2 * GAP_EXT), KOPEN = f16c2(2 * GAP_OPEN);
+				int ff = recv_f, lm0 = 0, lm1 = 0, hprev = 0;
+				int t = hf_diag_plus_score(hdiag0, score_of(0));
+#pragma unroll
+				for (int r = 0; r < RP; r++) {
+					int tnext = t;
+					if (r + 1 < RP) tnext = hf_diag_plus_score(H[r], score_of(r + 1));
+					const int h = hf_h(H[r], t, E[r], ff, tnext);
+					H[r] = h;
+					const int ho = hf_sub_k(h, KOPEN);
+					E[r] = hf_max_floor(hf_sub_k(E[r], KEXT), ho);
+					const int fnew = hf_max_floor(hf_sub_k(ff, KEXT), ho);
+					int hm = h;             // what the lane maximum sees of this row
+					if (r == RP - 1) {
+						ff = (fnew & (int)act) | (ff & ~(int)act);
+						hm = h & (int)act;
+						if (RP > 1) hbot = hm | (H[RP > 1 ? RP - 2 : 0] & ~(int)act);
+						else hbot = h;
+					} else ff = fnew;
+					// one max3 per two rows, two independent chains
+					if (r & 1) { if (r & 2) lm1 = hf_max3(lm1, hprev, hm); else lm0 = hf_max3(lm0, hprev, hm); }
+					hprev = hm;
+					t = tnext;
+				}
+				lmax = s_from((RP & 1) ? hf_max3(lm0, lm1, hprev) : hf_max_floor(lm0, lm1));
+				f = u_fromi(ff);
+			} else {
 			v2s t = diag_plus_score(hdiag0, score_of(0));
 #pragma unroll
 			for (int r = 0; r < RP; r++) {
@@ -325,10 +379,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 				}
 				t = tnext;
 			}
-			const v2s lmax = __builtin_elementwise_max(__builtin_elementwise_max(lmx[0], lmx[1]), __builtin_elementwise_max(lmx[2], lmx[3]));
+			lmax = __builtin_elementwise_max(__builtin_elementwise_max(lmx[0], lmx[1]), __builtin_elementwise_max(lmx[2], lmx[3]));
+			}
 			// pin the reduction here: if the compiler sinks it below the hazard branch, the 22 pre-branch H values stay alive
 			// next to the (possibly tainted) ones and the common path pays a register copy per row at the join
 			asm volatile("" :: "v"(to_int(lmax)));
+			// (F16: the values are non-negative, so their bit patterns order like the values: the running maxima stay u16 maxima)
 			if constexpr (!DUMP) ubacc = __builtin_elementwise_max(ubacc, as_u(lmax));
 			fbot = to_int(f);
 			if constexpr (DUMP) fmbot = to_int(fm);
@@ -343,11 +399,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 				// fpo halves: bits 0..14 = propagated value, bit 15 = "an early exit was possible at an earlier row"
 				// cheap superset first (3 VALU): a stripe-start lane receives F >= 132, or some lane receives a live chain;
 				// the exact condition is only evaluated behind it
-				const v2u cand = pk_subs_k(__builtin_bit_cast(v2u, recv_f) & startm, 263u * 0x10001u) | __builtin_bit_cast(v2u, recv_fp);
+				// (F16: F arrives as f16 bits, and bits(F) > bits(263) iff F > 263; the chain state fpo travels as integers)
+				const v2u cand = pk_subs_k(__builtin_bit_cast(v2u, recv_f) & startm, F16 ? f16c2(263u) : 263u * 0x10001u) | __builtin_bit_cast(v2u, recv_fp);
 				bool enter = false;
 				v2u fp_in = (v2u){ 0, 0 }, arm_in = (v2u){ 0, 0 };
 				if (__builtin_amdgcn_ballot_w64(to_int(cand) != 0) != 0ull) {
-					const v2u fpraw = (__builtin_bit_cast(v2u, recv_f) & startm) | (__builtin_bit_cast(v2u, recv_fp) & ~startm);
+					const v2u fpraw = (u_fromi(F16 ? hf_to_u16(recv_f) : recv_f) & startm) | (__builtin_bit_cast(v2u, recv_fp) & ~startm);
 					fp_in = fpraw & (v2u){ 0x7fff, 0x7fff };
 					arm_in = (fpraw >> (v2u){ 15, 15 }) & ~startm;
 					const v2u hot = pk_subs_k(fp_in, 263u * 0x10001u) | pk_minu(arm_in, fp_in);
@@ -365,7 +422,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 					uint32_t dh[2] = { 0u, 0u }, de[2] = { 0u, 0u };
 #pragma unroll
 					for (int r = 0; r < RP; r++) {
-						const v2u hr = u_fromi(H[r]);
+						// (F16: the branch works on integers as before; it sets a taint by adding 1.0 to a value that is still even)
+						const v2u hr = u_fromi(F16 ? hf_to_u16(H[r]) : H[r]), er = u_fromi(F16 ? hf_to_u16(E[r]) : E[r]);
 						const v2u ge = pk_minu_k(pk_subs_k(fp, K263), K1);                     // Fp >= 132
 						// H < 144; a tainted H may be smaller in the reference, so it counts as "< 144" too
 						v2u lt = pk_minu_k(pk_ksubs(K288, hr), K1) | (hr & one);
@@ -376,16 +434,23 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 						const v2u dev = pk_minu(pk_minu(eq, fp), arm);                         // 0 / 1
 						// E of this row was just derived from the untainted H: taint it when it came from H (or ties with it)
 						const v2u ho = pk_subs_k(hr, KO);
-						const v2u efrom = pk_minu(pk_ksubs(K1, pk_subs(u_fromi(E[r]), ho)), ho);
-						dh[r >> 4] |= (uint32_t)to_int(dev) << (r & 15);
-						de[r >> 4] |= (uint32_t)to_int(pk_minu(efrom, dev)) << (r & 15);
+						const v2u efrom = pk_minu(pk_ksubs(K1, pk_subs(er, ho)), ho);
+						// (F16: only a value that is still even gets the 1.0; through the asm helper, so that the decision is taken here and
+						//  hr / er die with the row: left to the compiler, the and-not is fused into the OR tree below and keeps them alive)
+						dh[r >> 4] |= (uint32_t)to_int(F16 ? pk_subs(dev, hr & one) : dev) << (r & 15);
+						de[r >> 4] |= (uint32_t)to_int(F16 ? pk_subs(pk_minu(efrom, dev), er & one) : pk_minu(efrom, dev)) << (r & 15);
 						arm = pk_maxu(arm, pk_minu(ge, lt));
 						fp = nfp;
 					}
 #pragma unroll
 					for (int r = 0; r < RP; r++) {
-						or_in_place(H[r], (int)((dh[r >> 4] >> (r & 15)) & K1));
-						or_in_place(E[r], (int)((de[r >> 4] >> (r & 15)) & K1));
+						if (F16) {
+							hf_add_in_place(H[r], (int)(((dh[r >> 4] >> (r & 15)) & K1) * F16_ONE));
+							hf_add_in_place(E[r], (int)(((de[r >> 4] >> (r & 15)) & K1) * F16_ONE));
+						} else {
+							or_in_place(H[r], (int)((dh[r >> 4] >> (r & 15)) & K1));
+							or_in_place(E[r], (int)((de[r >> 4] >> (r & 15)) & K1));
+						}
 					}
 					if (RP > 1) hbot = (H[RP - 1] & (int)act) | (H[RP > 1 ? RP - 2 : 0] & ~(int)act);
 					else hbot = H[0];
@@ -419,7 +484,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 			cm = to_int(__builtin_elementwise_max(__builtin_bit_cast(v2u, recv_cm), as_u(lmax)));
 			const int cdone = step - 127;
 			if (lane == 63 && cdone >= 0) {
-				if (last_tile) out[cdone] = (uint16_t)((uint32_t)cm >> 16);
+				if (last_tile) out[cdone] = F16 ? (uint16_t)f16_int((uint32_t)cm >> 16) : (uint16_t)((uint32_t)cm >> 16);
 				else bnd[cdone] = make_uint2(((uint32_t)hbot >> 16) | ((uint32_t)fbot & 0xffff0000u), ((uint32_t)cm >> 16) | ((uint32_t)fpo & 0xffff0000u));
 			}
 		};
@@ -429,17 +494,20 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 				// pipeline snapshot (every SCAN_SNAP_STEPS steps, all lanes at once: ~50 stores per 1024 steps of ~230 instructions)
 				if (a.snap && step != 0 && (step & (SCAN_SNAP_STEPS - 1)) == 0 && step / SCAN_SNAP_STEPS <= a.snap_per_unit) {
 					uint32_t* sp = a.snap + ((size_t)unit * a.snap_per_unit + (step / SCAN_SNAP_STEPS - 1)) * (SNAP_DW * 64) + lane;
+					// (F16: the checkpoint pass that reads them is the integer kernel)
+					auto sv = [](int x) -> uint32_t { return (uint32_t)(F16 ? hf_to_u16(x) : x); };
 #pragma unroll
-					for (int r = 0; r < RP; r++) { sp[(2 * r) * 64] = (uint32_t)H[r]; sp[(2 * r + 1) * 64] = (uint32_t)E[r]; }
-					sp[(2 * RP) * 64] = (uint32_t)tc; sp[(2 * RP + 1) * 64] = (uint32_t)hbot; sp[(2 * RP + 2) * 64] = (uint32_t)fbot; sp[(2 * RP + 3) * 64] = (uint32_t)cm;
-					sp[(2 * RP + 4) * 64] = (uint32_t)recv_h_last; sp[(2 * RP + 5) * 64] = (uint32_t)fpo;
+					for (int r = 0; r < RP; r++) { sp[(2 * r) * 64] = sv(H[r]); sp[(2 * r + 1) * 64] = sv(E[r]); }
+					sp[(2 * RP) * 64] = (uint32_t)tc; sp[(2 * RP + 1) * 64] = sv(hbot); sp[(2 * RP + 2) * 64] = sv(fbot); sp[(2 * RP + 3) * 64] = sv(cm);
+					sp[(2 * RP + 4) * 64] = sv(recv_h_last); sp[(2 * RP + 5) * 64] = (uint32_t)fpo;
 				}
 			}
 			do_step(step); do_step(step + 1);
 			if constexpr (!DUMP) {
 				// (steps come in pairs: a block of SCAN_UBLK_STEPS steps ends after an odd step)
 				if (((step + 1) & (SCAN_UBLK_STEPS - 1)) == SCAN_UBLK_STEPS - 1) {
-					if (a.ublk) a.ublk[(((size_t)unit * a.ntiles + a.tile) * a.ublk_blocks + (step / SCAN_UBLK_STEPS)) * 64 + lane] = ublk_pack(ubacc);
+					if (F16) ovf |= __builtin_amdgcn_ballot_w64(ubacc[0] >= F16_2048 || ubacc[1] >= F16_2048) != 0ull;
+					if (a.ublk) a.ublk[(((size_t)unit * a.ntiles + a.tile) * a.ublk_blocks + (step / SCAN_UBLK_STEPS)) * 64 + lane] = ublk_pack(F16 ? u_fromi(hf_to_u16(to_int(ubacc))) : ubacc);
 					ubacc = (v2u){ 0, 0 };
 				}
 			}
@@ -447,7 +515,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 		if (step < nsteps) do_step(step);
 		if constexpr (!DUMP) {
 			// the last, partial block (nsteps - 1 is its last step unless the block was just closed)
-			if (a.ublk && (nsteps & (SCAN_UBLK_STEPS - 1)) != 0) a.ublk[(((size_t)unit * a.ntiles + a.tile) * a.ublk_blocks + ((nsteps - 1) / SCAN_UBLK_STEPS)) * 64 + lane] = ublk_pack(ubacc);
+			if (a.ublk && (nsteps & (SCAN_UBLK_STEPS - 1)) != 0) a.ublk[(((size_t)unit * a.ntiles + a.tile) * a.ublk_blocks + ((nsteps - 1) / SCAN_UBLK_STEPS)) * 64 + lane] = ublk_pack(F16 ? u_fromi(hf_to_u16(to_int(ubacc))) : ubacc);
+		}
+		if constexpr (F16) {
+			// (a block that was just closed left ubacc = 0)
+			ovf |= __builtin_amdgcn_ballot_w64(ubacc[0] >= F16_2048 || ubacc[1] >= F16_2048) != 0ull;
+			if (ovf && lane == 0) a.unit_ovf[unit] = 1;
 		}
 		if (a.unit_hz && __builtin_amdgcn_ballot_w64(to_int(hzacc) != 0) != 0ull && lane == 0) atomicOr(a.unit_hz + unit, 1);
 		if (!DUMP && a.unit_first && first_enter != 0x7fffffff && lane == 0) atomicMin(a.unit_first + unit, first_enter);
@@ -464,7 +537,7 @@ static hipError_t launch_scan_dump_t(const ScanArgs& a, hipStream_t st)
 	return hipGetLastError();
 }
 
-template <int RP>
+template <int RP, bool F16>
 static hipError_t launch_scan_t(const ScanArgs& a, hipStream_t st)
 {
 	hipError_t err = hipMemsetAsync(a.counter, 0, sizeof(uint32_t), st);
@@ -474,7 +547,7 @@ static hipError_t launch_scan_t(const ScanArgs& a, hipStream_t st)
 	// for this kernel to drain.
 	constexpr int WPB = 4, PER_WAVE = 2;                 // waves per workgroup, units per wave
 	const long blocks = ((long)a.nwork + WPB * PER_WAVE - 1) / (WPB * PER_WAVE);
-	hipLaunchKernelGGL((k_scan<RP>), dim3((unsigned)blocks), dim3(256), (size_t)5 * SCAN_CODE_STRIDE, st, a);
+	hipLaunchKernelGGL((k_scan<RP, false, F16>), dim3((unsigned)blocks), dim3(256), (size_t)5 * SCAN_CODE_STRIDE, st, a);
 	return hipGetLastError();
 }
 
@@ -498,6 +571,9 @@ hipError_t launch_scan(const ScanLaunch& L, hipStream_t st)
 	a.vs = systolic_vs(L.m); a.ntiles = a.vs / 8; a.boundary = L.boundary;
 	a.unit_first = L.unit_first; a.snap = L.snap; a.snap_per_unit = L.snap_per_unit; a.dump_items = L.dump_items; a.dump_cols = L.dump_cols; a.dump_state = L.dump_state; a.rows_total = 16 * a.seg_len16;
 	a.ublk = L.dump_items ? nullptr : L.ublk; a.ublk_blocks = L.ublk_blocks;
+	const bool f16 = L.f16 && !L.dump_items;
+	if (f16 && !L.unit_ovf) return hipErrorInvalidValue;
+	a.unit_ovf = L.unit_ovf;
 	if (a.ntiles > 1 && !a.boundary) return hipErrorInvalidValue;
 	// RP must be exactly ceil(segLen/vs): every virtual lane then owns RP or RP-1 rows.  One launch per tile of 128
 	// virtual lanes (long queries): tile t reads the bottom row tile t-1 left in `boundary` and overwrites it in place.
@@ -506,7 +582,7 @@ hipError_t launch_scan(const ScanLaunch& L, hipStream_t st)
 		a.tile = t;
 		hipError_t err = hipErrorInvalidValue;
 		switch (rp) {
-#define FASIM_SCAN_CASE(N) case N: err = L.dump_items ? launch_scan_dump_t<N>(a, st) : launch_scan_t<N>(a, st); break;
+#define FASIM_SCAN_CASE(N) case N: err = L.dump_items ? launch_scan_dump_t<N>(a, st) : (f16 ? launch_scan_t<N, true>(a, st) : launch_scan_t<N, false>(a, st)); break;
 		FASIM_SCAN_CASE(1) FASIM_SCAN_CASE(2) FASIM_SCAN_CASE(3) FASIM_SCAN_CASE(4) FASIM_SCAN_CASE(5) FASIM_SCAN_CASE(6)
 		FASIM_SCAN_CASE(7) FASIM_SCAN_CASE(8) FASIM_SCAN_CASE(9) FASIM_SCAN_CASE(10) FASIM_SCAN_CASE(11) FASIM_SCAN_CASE(12)
 		FASIM_SCAN_CASE(13) FASIM_SCAN_CASE(14) FASIM_SCAN_CASE(15) FASIM_SCAN_CASE(16) FASIM_SCAN_CASE(17) FASIM_SCAN_CASE(18)
@@ -606,6 +682,23 @@ hipError_t launch_max16(const uint16_t* colmax16, const int32_t* unit_ids, int32
 {
 	if (nwork <= 0) return hipSuccess;
 	hipLaunchKernelGGL(k_max16, dim3((unsigned)nwork), dim3(64), 0, st, colmax16, unit_ids, unit_len, tstride, out);
+	return hipGetLastError();
+}
+
+// the instruction the f16 row pair rests on, exposed for the unit test (fasim_maximum3_f16)
+__global__ void __launch_bounds__(256) k_maximum3_f16(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, const uint32_t* __restrict__ c,
+	uint32_t* __restrict__ out3, uint32_t* __restrict__ out0, int64_t n)
+{
+	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	out3[i] = (uint32_t)hf_max3((int)a[i], (int)b[i], (int)c[i]);
+	out0[i] = (uint32_t)hf_max_floor((int)a[i], (int)b[i]);
+}
+
+hipError_t launch_maximum3_f16(const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* out3, uint32_t* out0, int64_t n, hipStream_t st)
+{
+	if (n <= 0) return hipSuccess;
+	hipLaunchKernelGGL(k_maximum3_f16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, b, c, out3, out0, n);
 	return hipGetLastError();
 }
 

@@ -114,6 +114,10 @@ int fasim_pick_candidates(const int32_t* cols, int32_t n, int32_t threshold,
  * string conversion, then both record types through the dedup (sort / unique with the reference's comparators, which are
  * not strict weak orderings: the order must match exactly).  *mismatches = number of differences (0 expected).          */
 int fasim_selfcheck_records(uint64_t seed, int32_t n, int32_t* mismatches);
+/* v_pk_maximum3_f16 as the f16 DP kernels use it (option dp_f16), on the engine's device: for n packed f16 pairs
+ * out3[i] = maximum3(a[i], b[i], c[i]) and out0[i] = maximum3(a[i], b[i], +0) (the inline constant).  For tests: on
+ * integer-valued operands both must be the integer maximum, bit for bit.                                             */
+int fasim_maximum3_f16(fasim_engine* e, const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* out3, uint32_t* out0, int64_t n);
 /* ssw_align() (ssw.h:118, sswNew.cpp:1446) behind Aligner::Align (ssw_cpp.cpp:599-643).           */
 typedef struct fasim_alignment {
 	int32_t sw_score, ref_begin, ref_end, query_begin, query_end;
@@ -193,6 +197,7 @@ typedef struct fasim_scan_stats {
 	int64_t rev_bound_passes;           /* window tries that took the full-height reverse pass (bounds for the band passes) */
 	int64_t striped_window_probs;       /* problems run on the HBM-window variant of k_striped (query stripes too long for the LDS) */
 	double  striped_window_ms;          /* HIP-event time of those launches (also counted in kernel_ms[1] / kernel_ms[5]) */
+	int64_t dp_f16_reruns;              /* units whose scores left the exact range of the f16 k_scan (>= 1 024) and that the integer k_scan ran again */
 } fasim_scan_stats;
 
 struct fasim_result {
