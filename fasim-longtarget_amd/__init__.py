@@ -99,11 +99,19 @@ class _Result(C.Structure):
                 ("stats", ScanStats)]
 
 
+class _Track(C.Structure):
+    _fields_ = [("nbins", C.c_int64), ("bin", C.c_int32), ("v", C.POINTER(C.c_uint16) * 4), ("units", C.c_int64),
+                ("saturated_units", C.c_int64)]
+
+
+TRACK_CLASSES = ("ParaPlus", "ParaMinus", "AntiMinus", "AntiPlus")
+
 EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_ex", "fasim_engine_destroy", "fasim_last_error", "fasim_set_option", "fasim_set_query",
            "fasim_calc_score_once", "fasim_ssw_pre_align", "fasim_ssw_colmax_word", "fasim_pick_candidates", "fasim_ssw_align", "fasim_pre_align_batch",
            "fasim_align_batch", "fasim_encode_unit", "fasim_sim_forward_batch", "fasim_sim_finish_unit", "fasim_scan", "fasim_scan_queries", "fasim_scan_records", "fasim_merge_results", "fasim_rebase_offsets", "fasim_load_dna", "fasim_result_free", "fasim_segment_count",
            "fasim_tfosorted", "fasim_tfoclass", "fasim_tfosorted_ex", "fasim_tfoclass_ex", "fasim_tail_outputs", "fasim_upper_case", "fasim_free",
            "fasim_synth_dna", "fasim_selfcheck_records", "fasim_read_bed", "fasim_maximum3_f16",
+           "fasim_scan_track", "fasim_track_merge", "fasim_track_bedgraph", "fasim_track_free",
            # the reference's own ssw.h ABI (include/ssw.h)
            "ssw_init", "init_destroy", "ssw_pre_align", "ssw_align", "align_destroy", "encoded_ops"]
 
@@ -176,6 +184,14 @@ def lib():
     L.fasim_synth_dna.restype = None
     L.fasim_maximum3_f16.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int64]
     L.fasim_read_bed.argtypes = [C.c_char_p, C.POINTER(C.POINTER(_Region)), C.POINTER(C.c_int64)]
+    L.fasim_scan_track.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p, C.c_int64,
+                                   C.c_int64, C.c_int64, C.POINTER(Params), C.c_int32, C.POINTER(C.POINTER(_Result)),
+                                   C.POINTER(C.POINTER(_Track))]
+    L.fasim_track_merge.argtypes = [C.POINTER(C.POINTER(_Track)), C.c_int32, C.POINTER(C.POINTER(_Track))]
+    L.fasim_track_bedgraph.argtypes = [C.POINTER(_Track), C.c_char_p, C.c_int64, C.c_int64, C.c_char_p, C.c_int32,
+                                       C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.fasim_track_free.argtypes = [C.POINTER(_Track)]
+    L.fasim_track_free.restype = None
     _lib = L
     return L
 
@@ -256,6 +272,97 @@ class ScanResult:
                         C.c_uint32.from_buffer_copy(C.c_float(t.identity)).value,
                         C.c_uint32.from_buffer_copy(C.c_float(t.tri_score)).value, tfo, tts, t.seg, t.enc))
         return out
+
+
+class Track:
+    """Per-base triplex potential of one record and one lncRNA (struct fasim_track): per strand class (TRACK_CLASSES) and bin
+    of `bin` bases the best local alignment score of the lncRNA that ends in the bin, without the candidate threshold.
+    Either a native track (what scan_track() and merge_tracks() return) or one made from a (4, nbins) array:
+    `Track(values, bin, units=0, saturated_units=0)`."""
+
+    def __init__(self, values=None, bin: int = 1, units: int = 0, saturated_units: int = 0, _native=None):
+        self._native = _native
+        self._keep = None
+        if _native is None:
+            import numpy as np
+            a = np.ascontiguousarray(values, dtype=np.uint16)
+            if a.ndim != 2 or a.shape[0] != 4:
+                raise FasimError("a track is a (4, nbins) array", E_ARG)
+            t = _Track()
+            t.nbins, t.bin, t.units, t.saturated_units = a.shape[1], bin, units, saturated_units
+            for c in range(4):
+                t.v[c] = C.cast(a[c].ctypes.data, C.POINTER(C.c_uint16))
+            self._keep = (a, t)
+
+    def __del__(self):
+        try:
+            if self._native is not None:
+                lib().fasim_track_free(self._native)
+                self._native = None
+        except Exception:
+            pass
+
+    def pointer(self):
+        """POINTER(fasim_track) for the C-ABI; valid while this object lives."""
+        return self._native if self._native is not None else C.pointer(self._keep[1])
+
+    @property
+    def _t(self):
+        return self._native.contents if self._native is not None else self._keep[1]
+
+    @property
+    def bin(self) -> int:
+        return int(self._t.bin)
+
+    @property
+    def nbins(self) -> int:
+        return int(self._t.nbins)
+
+    @property
+    def units(self) -> int:
+        return int(self._t.units)
+
+    @property
+    def saturated_units(self) -> int:
+        return int(self._t.saturated_units)
+
+    def array(self):
+        """(4, nbins) numpy uint16 array (a copy), rows in TRACK_CLASSES order."""
+        import numpy as np
+        t, n = self._t, self.nbins
+        out = np.zeros((4, n), dtype=np.uint16)
+        for c in range(4):
+            if n:
+                C.memmove(out[c].ctypes.data, t.v[c], 2 * n)
+        return out
+
+
+def merge_tracks(parts) -> Track:
+    """Element-wise maximum of the tracks of one record (fasim_track_merge): shards of a segment range, devices."""
+    L = lib()
+    parts = list(parts)
+    arr = (C.POINTER(_Track) * max(1, len(parts)))(*[t.pointer() for t in parts])
+    out = C.POINTER(_Track)()
+    rc = L.fasim_track_merge(arr, len(parts), C.byref(out))
+    if rc != 0:
+        raise FasimError(f"fasim_track_merge failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
+    return Track(_native=out)
+
+
+def track_bedgraph(track: Track, chr_name: str, start_genome: int, dna_len: int, rna_name: str, min_value: int = 1) -> bytes:
+    """bedGraph bytes of a potential track (fasim_track_bedgraph): one block per strand class, runs of equal bins joined, bins
+    below `min_value` left out; what `fasim --track BIN` writes as <stem>-TFOpotential-<BIN>."""
+    L = lib()
+    text = C.c_void_p()
+    n = C.c_int64()
+    rc = L.fasim_track_bedgraph(track.pointer(), chr_name.encode(), start_genome, dna_len, rna_name.encode(), min_value,
+                                C.byref(text), C.byref(n))
+    if rc != 0:
+        raise FasimError(f"fasim_track_bedgraph failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
+    try:
+        return C.string_at(text, n.value)
+    finally:
+        L.fasim_free(text)
 
 
 def _merge_pointers(ptrs):
@@ -511,6 +618,29 @@ class Engine:
                                                seg_count, C.byref(p), outs))
         self.m = len(rnas[-1])
         return [ScanResult(stats=self._stats_dict(outs[k].contents.stats), _native=outs[k]) for k in range(n)]
+
+    def scan_track(self, dna: bytes | None, params: Params | None = None, rnas=None, bin: int = 1, records: bool = True,
+                   seg_first: int = 0, seg_count: int = -1):
+        """Potential tracks (fasim_scan_track): `(results or None, tracks)`.  rnas None: the engine's query, one ScanResult (the
+        same as scan()) and one Track; otherwise lists, one entry per lncRNA, as scan_queries().  records False: track only, stage 3
+        is not run and the first element is None.  With a segment range the tracks still span the whole record: merge the
+        shards' tracks with merge_tracks()."""
+        p = params or default_params()
+        nq = 0 if rnas is None else len(rnas)
+        nqo = max(1, nq)
+        arr = (C.c_char_p * nqo)(*(rnas or []))
+        qlens = (C.c_int32 * nqo)(*[len(r) for r in (rnas or [])])
+        outs = (C.POINTER(_Result) * nqo)() if records else None
+        trks = (C.POINTER(_Track) * nqo)()
+        self._check(self._L.fasim_scan_track(self._h, arr, qlens, nq, dna, len(dna) if dna is not None else 0, seg_first,
+                                             seg_count, C.byref(p), bin, outs, trks))
+        if nq:
+            self.m = len(rnas[-1])
+        tracks = [Track(_native=trks[k]) for k in range(nqo)]
+        res = [ScanResult(stats=self._stats_dict(outs[k].contents.stats), _native=outs[k]) for k in range(nqo)] if records else None
+        if rnas is None:
+            return (res[0] if records else None), tracks[0]
+        return res, tracks
 
     def scan_records(self, dnas, params: Params | None = None, rnas=None, seg_first: int = 0, seg_count: int = -1, rec_lens=None):
         """Record set (fasim_scan_records): many DNA records (peaks, promoter windows) scanned in shared batches.

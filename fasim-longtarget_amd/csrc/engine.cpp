@@ -97,7 +97,7 @@ void fasim_engine_destroy(fasim_engine* e)
 		&e->unit_first, &e->hz_cols, &e->hz_plan, &e->hz_base, &e->hz_items, &e->snap, &e->hz_state, &e->hz_rows, &e->hz_chunk, &e->hz_src, &e->hz_zero,
 		&e->qsim, &e->sim_min, &e->sim_row, &e->sim_ev, &e->sim_cnt, &e->sim_nodes,
 		&e->ublk, &e->btarget, &e->bidx, &e->bcounts, &e->blist[0], &e->blist[1], &e->blist[2], &e->bslots[0], &e->bslots[1], &e->bslots[2],
-		&e->bprev, &e->lane_ub, &e->fzones, &e->fubslot, &e->bdec, &e->btab, &e->swin, &e->unit_ovf };
+		&e->bprev, &e->lane_ub, &e->fzones, &e->fubslot, &e->bdec, &e->btab, &e->swin, &e->unit_ovf, &e->track, &e->track_phase, &e->track_sat };
 	for (auto& t : e->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
 	for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
 	for (DevBuf* b : bufs) b->release();
@@ -481,6 +481,123 @@ int fasim_scan_records(fasim_engine* E, const char* const* rnas, const int32_t* 
 		if (rec_len[r] > 0x7fffffffll) return fail(E, FASIM_E_ARG, "record %d: one record is limited to 2^31-1 nt (the reference's int positions)", r);
 	}
 	return scan_records_core(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, outs, totals);
+}
+
+// ---- per-base potential tracks ----------------------------------------------------------------------------------------
+static int text_out(const std::string& s, char** text, int64_t* text_len);
+static fasim_track* track_alloc(int64_t nbins, int32_t bin)
+{
+	fasim_track* t = (fasim_track*)calloc(1, sizeof(fasim_track));
+	if (!t) return nullptr;
+	t->nbins = nbins; t->bin = bin;
+	for (int c = 0; c < FASIM_TRACK_CLASSES; c++) {
+		t->v[c] = (uint16_t*)calloc((size_t)std::max<int64_t>(1, nbins), sizeof(uint16_t));
+		if (!t->v[c]) { fasim_track_free(t); return nullptr; }
+	}
+	return t;
+}
+
+void fasim_track_free(fasim_track* t)
+{
+	if (!t) return;
+	for (int c = 0; c < FASIM_TRACK_CLASSES; c++) free(t->v[c]);
+	free(t);
+}
+
+int fasim_scan_track(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna, int64_t dna_len,
+	int64_t seg_first, int64_t seg_count, const fasim_params* pp, int32_t bin, fasim_result** out_results, fasim_track** out_tracks)
+{
+	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
+	if (!out_tracks || !pp || nq < 0) return fail(E, FASIM_E_ARG, "bad arguments");
+	if (bin < 1) return fail(E, FASIM_E_ARG, "track bin width %d: must be at least 1", bin);
+	const int nquery = std::max(1, nq);
+	for (int q = 0; q < nquery; q++) out_tracks[q] = nullptr;
+	if (out_results) for (int q = 0; q < nquery; q++) out_results[q] = nullptr;
+	if (nq == 0) { int rc = need_query(E); if (rc) return rc; }
+	else {
+		if (!rnas || !rna_lens) return fail(E, FASIM_E_ARG, "bad arguments");
+		for (int32_t q = 0; q < nq; q++) {
+			if (!rnas[q] || rna_lens[q] <= 0) return fail(E, FASIM_E_ARG, "empty query %d", q);
+			if (rna_lens[q] > FASIM_MAX_QUERY) return refuse_long_query(E, rna_lens[q], q);
+		}
+	}
+	// the tracks are the column maxima of the systolic scan kernel: no other kernel leaves them
+	for (int q = 0; q < nquery; q++) {
+		const int len = nq == 0 ? E->m : rna_lens[q];
+		if (!systolic_fits(len)) return fail(E, FASIM_E_UNSUPPORTED, "potential tracks need a query of at least 113 nt (query %d has %d): shorter queries run on the striped kernels, which keep the reference's 8-bit column maxima only", q, len);
+	}
+	if (E->scan_v1) return fail(E, FASIM_E_UNSUPPORTED, "potential tracks are not available under FASIM_SCAN_V1=1 (the striped kernels keep the reference's 8-bit column maxima only)");
+	if (pp->classicSim) return fail(E, FASIM_E_UNSUPPORTED, "potential tracks are not available with classicSim (-F): that path has no stage-2 column maxima");
+	if (dna == nullptr) {
+		if (E->dna_host.empty()) return fail(E, FASIM_E_ARG, "no resident DNA: call fasim_load_dna first");
+		dna_len = (int64_t)E->dna_host.size();
+	} else if (dna_len <= 0) return fail(E, FASIM_E_ARG, "bad arguments");
+	if (dna_len > 0x7fffffffll) return fail(E, FASIM_E_ARG, "one record is limited to 2^31-1 nt (the reference's int positions)");
+	TrackReq tr;
+	tr.bin = bin; tr.only = out_results == nullptr; tr.nbins = (dna_len + bin - 1) / bin;
+	tr.sat.assign((size_t)nquery, 0); tr.mu.reset(new std::mutex[(size_t)nquery]);
+	auto drop = [&]() { for (int q = 0; q < nquery; q++) { fasim_track_free(out_tracks[q]); out_tracks[q] = nullptr; } };
+	for (int q = 0; q < nquery; q++) {
+		out_tracks[q] = track_alloc(tr.nbins, bin);
+		if (!out_tracks[q]) { drop(); return fail(E, FASIM_E_NOMEM, "out of memory"); }
+		for (int c = 0; c < FASIM_TRACK_CLASSES; c++) tr.v.push_back(out_tracks[q]->v[c]);
+	}
+	std::vector<fasim_result*> own((size_t)nquery, nullptr);
+	fasim_result** outs = out_results ? out_results : own.data();
+	const int rc = scan_core(E, nq ? rnas : nullptr, nq ? rna_lens : nullptr, nq, dna, dna_len, seg_first, seg_count, pp, outs, &tr);
+	if (rc) { drop(); return rc; }
+	for (int q = 0; q < nquery; q++) { out_tracks[q]->units = outs[q]->stats.units; out_tracks[q]->saturated_units = tr.sat[(size_t)q]; }
+	for (fasim_result* r : own) fasim_result_free(r);
+	return FASIM_OK;
+}
+
+int fasim_track_merge(const fasim_track* const* parts, int32_t nparts, fasim_track** out)
+{
+	if (!parts || nparts < 1 || !out) return fail(nullptr, FASIM_E_ARG, "bad arguments");
+	*out = nullptr;
+	for (int k = 0; k < nparts; k++) {
+		if (!parts[k] || parts[k]->bin < 1 || parts[k]->nbins < 0) return fail(nullptr, FASIM_E_ARG, "bad track %d", k);
+		if (parts[k]->bin != parts[0]->bin || parts[k]->nbins != parts[0]->nbins)
+			return fail(nullptr, FASIM_E_ARG, "track %d has bin %d and %lld bins, track 0 has bin %d and %lld bins: only tracks of one record and one bin width merge",
+				k, parts[k]->bin, (long long)parts[k]->nbins, parts[0]->bin, (long long)parts[0]->nbins);
+	}
+	fasim_track* t = track_alloc(parts[0]->nbins, parts[0]->bin);
+	if (!t) return fail(nullptr, FASIM_E_NOMEM, "out of memory");
+	for (int k = 0; k < nparts; k++) {
+		t->units += parts[k]->units; t->saturated_units += parts[k]->saturated_units;
+		for (int c = 0; c < FASIM_TRACK_CLASSES; c++) {
+			const uint16_t* src = parts[k]->v[c]; uint16_t* dst = t->v[c];
+			for (int64_t i = 0; i < t->nbins; i++) dst[i] = std::max(dst[i], src[i]);
+		}
+	}
+	*out = t;
+	return FASIM_OK;
+}
+
+int fasim_track_bedgraph(const fasim_track* t, const char* chr, int64_t start_genome, int64_t dna_len, const char* rna_name,
+	int32_t min_value, char** text, int64_t* text_len)
+{
+	if (!t || !chr || !rna_name || !text || !text_len || t->bin < 1) return fail(nullptr, FASIM_E_ARG, "bad arguments");
+	if (min_value < 1) return fail(nullptr, FASIM_E_ARG, "min_value %d: must be at least 1 (bins of value 0 are never written)", min_value);
+	if (dna_len <= 0 || (dna_len + t->bin - 1) / t->bin != t->nbins) return fail(nullptr, FASIM_E_ARG, "dna_len %lld does not match a track of %lld bins of %d", (long long)dna_len, (long long)t->nbins, t->bin);
+	static const char* const names[FASIM_TRACK_CLASSES] = { "ParaPlus", "ParaMinus", "AntiMinus", "AntiPlus" };
+	const int64_t sg = start_genome - 1;                  // 0-based genome position of the record's first base
+	std::string o;
+	char line[96];
+	for (int c = 0; c < FASIM_TRACK_CLASSES; c++) {
+		o += "track type=bedGraph name='"; o += rna_name; o += " potential ("; o += names[c]; o += ")'\n";
+		const uint16_t* v = t->v[c];
+		for (int64_t b = 0; b < t->nbins; ) {
+			int64_t e = b + 1;
+			while (e < t->nbins && v[e] == v[b]) e++;
+			if (v[b] >= min_value) {
+				const int n = snprintf(line, sizeof line, "\t%lld\t%lld\t%d\n", (long long)(sg + b * t->bin), (long long)(sg + std::min<int64_t>(e * t->bin, dna_len)), (int)v[b]);
+				o += chr; o.append(line, (size_t)n);
+			}
+			b = e;
+		}
+	}
+	return text_out(o, text, text_len);
 }
 
 // in-place variant for a gather that already placed every shard's records and pool at their final positions

@@ -131,6 +131,7 @@ struct fasim_engine {
 	int opt_band = -1;                           // option "band": 0 off, 1 on (-1 = default / environment FASIM_BAND)
 	int opt_dp_f16 = -1;                         // option "dp_f16": packed-f16 k_scan and reverse pass, 0 = the integer kernels (-1 = default / environment FASIM_DP_F16)
 	DevBuf unit_ovf;                             // [unit] != 0: the f16 k_scan saw a value outside its exact range
+	DevBuf track, track_phase, track_sat;        // fasim_scan_track only: k_track's slices, its per-segment bin phase and saturation flags of the batch
 	int opt_numa = 1;                            // option "numa_affinity": pin the scan's host threads to the GPU's NUMA node (no-op on one node)
 	// HBM-window variant of k_striped (queries whose stripes do not fit the LDS): its scratch, the forcing switch (option
 	// "striped_window" / FASIM_STRIPED_WINDOW=1: every stripe-faithful launch takes it, for tests), problems run on it and its
@@ -377,8 +378,28 @@ struct SegTable {
 	int64_t size() const { return (int64_t)rec.size(); }
 };
 
+// ---- potential tracks (fasim_scan_track, track.hip) ------------------------------------------------------------------------------
+// One call: the record's arrays (those of the fasim_track objects the call returns), which the workers fold their batches' slices
+// into as soon as a batch's scan phase ends; a bin that two batches touch (overlapping segments) is merged under the query's mutex.
+struct TrackReq {
+	int bin = 1; bool only = false;              // only: no stage 3, no records
+	int64_t nbins = 0;
+	std::vector<uint16_t*> v;                    // [query * 4 + class][nbins]
+	std::vector<int64_t> sat;                    // [query]: units with a saturated column maximum
+	std::unique_ptr<std::mutex[]> mu;            // [query]
+};
+// One batch, handed to run_scan_v2: where k_track's result goes
+struct TrackFold {
+	int bin = 1, nseg = 0, nenc = 0, nchunk = 0; bool only = false;
+	TrackTable tab;
+	const int32_t* phase = nullptr;              // [nseg] host: record position of the segment's first base, modulo bin
+	std::vector<uint16_t>* out = nullptr;        // [nseg * nchunk][4][track_slice_stride(bin)]
+	std::vector<uint8_t>* sat = nullptr;         // [unit]
+};
+
 struct BatchCtx {
 	UnitBatch B;
+	std::vector<uint16_t> track; std::vector<uint8_t> track_sat; int track_nchunk = 0;      // fasim_scan_track: k_track's slices of this batch
 	int tstride = 0, nenc = 0, nseg = 0;
 	int64_t step = 0;
 	// per kept segment of the batch: device start (relative to the batch's DNA on the device), length, index within its record
@@ -404,21 +425,21 @@ int run_striped(fasim_engine* E, StripedMode mode, bool word, const std::vector<
 int prep_striped_window(fasim_engine* E, StripedMode mode, bool word, StripedLaunch& L, bool* used);
 int run_stage1(fasim_engine* E, const UnitBatch& B, std::vector<int>& score, int64_t* word_reruns);
 int run_stage2(fasim_engine* E, const UnitBatch& B);
-int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& unit_needs_stage1, ScanOut& out, fasim_scan_stats* st);
+int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& unit_needs_stage1, ScanOut& out, fasim_scan_stats* st, const TrackFold* tf = nullptr);
 int load_raw_targets(fasim_engine* E, const char* targets, const int64_t* offsets, const int32_t* lens, int nprob, bool stage1, UnitBatch& B);
 int need_query(fasim_engine* E);
 int run_align(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb>& W, std::vector<AlignResult>& out, std::vector<uint32_t>& cigars, fasim_scan_stats* stats);
 int run_align_v2(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb>& W, std::vector<AlignResult>& out, std::vector<uint32_t>& cigars, fasim_scan_stats* stats);
 int stage3_range(fasim_engine* E, BatchCtx& C, int ua, int ub, fasim_scan_stats& st);
 int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_t* dna_dev, int64_t b0, int64_t b1,
-	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st);
+	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st, const TrackReq* tr = nullptr);
 int sim_forward_units(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, const int32_t* unit_len_dev, const int32_t* unit_len_host,
 	int first, int nunit, const int64_t* mins, std::atomic<int>* ready, std::vector<std::vector<fasim_sim_node>>& lists);
 int sim_resweep_rounds(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, const int32_t* unit_len_dev, const int32_t* unit_len_host,
 	int first, int cnt, SimUnit* const* units, int nthreads);
 int pack_result(fasim_engine* E, std::vector<HostTriplex>& all, const fasim_scan_stats& st, fasim_result** out);
 int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna, int64_t dna_len,
-	int64_t seg_first, int64_t seg_count, const fasim_params* pp, fasim_result** outs);
+	int64_t seg_first, int64_t seg_count, const fasim_params* pp, fasim_result** outs, TrackReq* tr = nullptr);
 // fasim_scan_records after its argument checks: records [rec_off[r], rec_off[r] + rec_len[r]) of `dna` (NULL: the resident
 // buffer); outs[q * nrec + r], totals[q] (may be NULL)
 int scan_records_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna,

@@ -253,7 +253,7 @@ int sim_resweep_rounds(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, 
 // host buffer.  The kernels take int32 segment starts relative to the batch's own first byte on the device, so a record set
 // longer than 2^31 nt works as long as one batch's span does.
 int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_t* dna_dev, int64_t b0, int64_t b1,
-	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st)
+	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st, const TrackReq* tr)
 {
 	int rc = FASIM_OK;
 	const int64_t step = p.cutLength - p.overlapLength;
@@ -349,7 +349,26 @@ int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_
 				}
 			}
 			ScanOut so;
-			rc = run_scan_v2(E, B, need1, so, &st);
+			TrackFold tf; std::vector<int32_t> phase;
+			if (tr) {
+				// potential tracks: class and direction of every enabled encoding (the Strand column of -TFOsorted, host_post.cpp), and
+				// where the record's bins fall in every segment
+				tf.bin = tr->bin; tf.only = tr->only; tf.nseg = nseg; tf.nenc = nenc; tf.nchunk = C.track_nchunk = track_chunks(p.cutLength);
+				int cnt = 0;
+				for (int g = 0; g < 8; g++) {
+					tf.tab.first[g] = (uint8_t)cnt;
+					for (int k = 0; k < nenc; k++) {
+						const EncInfo ei = enc_info(encs[(size_t)k]);
+						const int cls = ei.para == 1 ? (ei.strand == 0 ? 0 : 1) : (ei.strand == 1 ? 2 : 3);
+						if (cls + 4 * (ei.reversed ? 1 : 0) == g) tf.tab.k[cnt++] = (uint8_t)k;
+					}
+				}
+				tf.tab.first[8] = (uint8_t)cnt;
+				phase.resize((size_t)nseg);
+				for (int s = 0; s < nseg; s++) phase[(size_t)s] = (int32_t)((sidx[(size_t)s] * step) % tr->bin);
+				tf.phase = phase.data(); tf.out = &C.track; tf.sat = &C.track_sat;
+			}
+			rc = run_scan_v2(E, B, need1, so, &st, tr ? &tf : nullptr);
 			if (rc < 0) return rc;
 			if (rc == 0) { hoff.swap(so.hit_off); hcnt.swap(so.hit_cnt); thr.swap(so.thr); hits.swap(so.hits); done_v2 = true; }
 		}
@@ -433,6 +452,29 @@ int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_
 	return FASIM_OK;
 }
 
+
+// fasim_scan_track: the slices of a finished scan phase into the record's arrays of query q (maximum; overlapping segments and the
+// slices of one segment that share a bin meet here)
+static void merge_track(const BatchCtx& C, TrackReq& tr, int q)
+{
+	const int stride = track_slice_stride(tr.bin);
+	const int64_t bin = tr.bin;
+	std::lock_guard<std::mutex> g(tr.mu[(size_t)q]);
+	for (int s = 0; s < C.nseg; s++) {
+		const int64_t a = C.sidx[(size_t)s] * C.step;
+		const int n = C.slen[(size_t)s];
+		for (int c = 0; c * TRACK_CHUNK < n; c++) {
+			const int64_t P0 = (int64_t)c * TRACK_CHUNK, P1 = std::min<int64_t>(n, P0 + TRACK_CHUNK);
+			const int64_t b0 = (a + P0) / bin, nb = (a + P1 - 1) / bin - b0 + 1;
+			for (int cls = 0; cls < 4; cls++) {
+				const uint16_t* src = C.track.data() + (((size_t)s * C.track_nchunk + c) * 4 + cls) * stride;
+				uint16_t* dst = tr.v[(size_t)q * 4 + cls] + b0;
+				for (int64_t i = 0; i < nb; i++) dst[i] = std::max(dst[i], src[i]);
+			}
+		}
+	}
+	for (uint8_t f : C.track_sat) tr.sat[(size_t)q] += f;
+}
 
 // What one work item leaves for one record: the record's triplexes from the item's segments and the per-record stats (those
 // counted per unit or candidate).  A batch that crosses records leaves one part per record, in record order.
@@ -569,7 +611,7 @@ static void add_stats(fasim_scan_stats& st, const fasim_scan_stats& x)
 // whole call's stats.  `records` true: outs[q * nrec + r] carries the per-record stats, totals[q] (if given) the call's.
 static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int nrec, bool records, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
-	fasim_result** outs, fasim_scan_stats* totals)
+	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr = nullptr)
 {
 	const bool resident = (dna == nullptr);
 	if (resident) dna = E->dna_host.data();
@@ -757,8 +799,12 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 					r = fasim_set_query(w, rq.data(), (int)rq.size());
 					if (r && w != E) w->err = std::string("worker set_query failed: ") + w->err;
 				}
-				if (!r) r = scan_batch(w, dna, T, dna_dev, itx.b0, itx.b1, p, encs, tstride, ctx, ist[c]);
-				if (!r && ctx.B.nunit > 0 && !ctx.stage3_done) r = stage3_range(w, ctx, 0, ctx.B.nunit, ist[c]);
+				if (!r) r = scan_batch(w, dna, T, dna_dev, itx.b0, itx.b1, p, encs, tstride, ctx, ist[c], tr);
+				if (!r && tr && ctx.B.nunit > 0) {
+					if (ctx.track.empty()) r = fail(w, FASIM_E_UNSUPPORTED, "potential tracks need the systolic scan kernel");
+					else { merge_track(ctx, *tr, itx.q); std::vector<uint16_t>().swap(ctx.track); }
+				}
+				if (!r && ctx.B.nunit > 0 && !ctx.stage3_done && !(tr && tr->only)) r = stage3_range(w, ctx, 0, ctx.B.nunit, ist[c]);
 				(void)hipStreamSynchronize(w->st);
 				drain_timed(w);
 				for (int k = 0; k < FASIM_KERNEL_FAMILIES; k++) { ist[c].kernel_ms[k] = w->kernel_ms[k]; ist[c].kernel_launches[k] = w->kernel_launches[k]; w->kernel_ms[k] = 0; w->kernel_launches[k] = 0; }
@@ -851,7 +897,7 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 }
 
 int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna, int64_t dna_len,
-	int64_t seg_first, int64_t seg_count, const fasim_params* pp, fasim_result** outs)
+	int64_t seg_first, int64_t seg_count, const fasim_params* pp, fasim_result** outs, TrackReq* tr)
 {
 	if (dna == nullptr) {
 		if (E->dna_host.empty()) return fail(E, FASIM_E_ARG, "no resident DNA: call fasim_load_dna first");
@@ -861,7 +907,7 @@ int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens,
 	if (pp->cutLength <= 0 || pp->cutLength - pp->overlapLength <= 0) return fail(E, FASIM_E_ARG, "cutLength/overlapLength invalid");
 	if (dna_len > 0x7fffffffll) return fail(E, FASIM_E_ARG, "one record is limited to 2^31-1 nt (the reference's int positions)");
 	const int64_t off = 0;
-	return scan_set(E, rnas, rna_lens, nq, dna, &off, &dna_len, 1, false, seg_first, seg_count, pp, outs, nullptr);
+	return scan_set(E, rnas, rna_lens, nq, dna, &off, &dna_len, 1, false, seg_first, seg_count, pp, outs, nullptr, tr);
 }
 
 int scan_records_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna,

@@ -261,7 +261,7 @@ int run_hazard_chunked(fasim_engine* E, const UnitBatch& B, const std::vector<in
 
 // returns 1 when the query does not fit the kernel (caller falls back to the striped kernels)
 int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& unit_needs_stage1, ScanOut& out,
-	fasim_scan_stats* st)
+	fasim_scan_stats* st, const TrackFold* tf)
 {
 	const int nu = B.nunit;
 	HIPOK(E->colmax16.ensure((size_t)nu * B.tstride * sizeof(uint16_t)));
@@ -355,6 +355,25 @@ int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& un
 			HIPOK(hipStreamSynchronize(E->st));
 			if (st) st->dp_f16_reruns += (int64_t)again.size();      // (cells_stage2 stays the count of one pass over every unit)
 		}
+	}
+	if (tf) {
+		// potential tracks (fasim_scan_track): colmax16 holds the main pass of every unit now -- k_scan_post only reads it, but the
+		// checkpoint pass of the chunked hazard re-run below stores its column maxima there again.  The copies complete with the
+		// batch's other results, at the next synchronisation of the stream.
+		rc = upload(E, E->track_phase, tf->phase, sizeof(int32_t) * tf->nseg); if (rc) return rc;
+		const size_t nout = (size_t)tf->nseg * tf->nchunk * 4 * track_slice_stride(tf->bin);
+		HIPOK(E->track.ensure(nout * sizeof(uint16_t))); HIPOK(E->track_sat.ensure((size_t)nu));
+		HIPOK(hipMemsetAsync(E->track_sat.p, 0, (size_t)nu, E->st));
+		TrackLaunch T;
+		T.colmax16 = E->colmax16.as<uint16_t>(); T.seg_len = E->seg_len.as<int32_t>(); T.phase = E->track_phase.as<int32_t>();
+		T.nseg = tf->nseg; T.nenc = tf->nenc; T.tstride = B.tstride; T.nchunk = tf->nchunk; T.bin = tf->bin; T.tab = tf->tab;
+		T.out = E->track.as<uint16_t>(); T.sat = E->track_sat.as<uint8_t>();
+		{ TimedScope ts(E, 4); he = launch_track(T, E->st); }
+		if (he != hipSuccess) return fail(E, FASIM_E_HIP, "track launch failed: %s", hipGetErrorString(he));
+		tf->out->resize(nout); tf->sat->resize((size_t)nu);
+		HIPOK(hipMemcpyAsync(tf->out->data(), E->track.p, nout * sizeof(uint16_t), hipMemcpyDeviceToHost, E->st));
+		HIPOK(hipMemcpyAsync(tf->sat->data(), E->track_sat.p, (size_t)nu, hipMemcpyDeviceToHost, E->st));
+		if (tf->only) { HIPOK(hipStreamSynchronize(E->st)); return FASIM_OK; }      // track only: no hits, no hazard re-run, no stage 3
 	}
 
 	HIPOK(E->hit_off.ensure(sizeof(int32_t) * nu)); HIPOK(E->hit_cnt.ensure(sizeof(int32_t) * nu));

@@ -19,6 +19,11 @@
 //     --accumulate-records  bug-compatible with the reference's reader (defect B1, Fasim-LongTarget.cpp:219-262): record
 //                           k is scanned as the concatenation of records 1..k, later headers are parsed with the stale
 //                           field counter, everything is written into ONE output set named after the first record
+//     --track BIN           per-base triplex potential (fasim_scan_track): a fourth file <stem>-TFOpotential-<BIN> per lncRNA and
+//                           record, a bedGraph with one block per strand class and one value per BIN bases (the best local
+//                           alignment score that ends there, no candidate threshold); --track-min V leaves out bins below V
+//                           (default 1); --track-only writes only that file and skips stage 3.  With --all-records every record
+//                           is scanned on its own.  Not with --regions, --accumulate-records or -F (exit status 2)
 //     --upper               upper-case the DNA while reading (soft-masked genomes; the reference treats lower case as N)
 //     --clamp-cluster       defined behaviour where the reference's clustering does not terminate (see fasim_hip.h)
 //     --stats               timing/statistics on stderr (parse, scan, tail, write)
@@ -180,34 +185,50 @@ static int write_outputs(const fasim_result* res, const std::string& stem, const
 static std::mutex g_out_mu;
 static int g_out_failed = 0;
 
+// --track: bin width (0: no tracks), smallest value written, --track-only
+struct TrackOpt { int bin = 0, min_value = 1; bool only = false; };
+
 // Scans one DNA record with every lncRNA on every device: device d takes the d-th contiguous block of segments
 // (SURVEY 8(e)); per lncRNA the shard results are merged in shard order, which is the reference's canonical order.
+// With --track the potential tracks come back in `tracks` (shards merged by maximum); --track-only leaves `out` NULL.
 static int scan_record(const std::vector<fasim_engine*>& engines, const std::vector<Rna>& rnas, const char* dna, int64_t dna_len, const fasim_params& p,
-	std::vector<fasim_result*>& out)
+	std::vector<fasim_result*>& out, const TrackOpt& trk, std::vector<fasim_track*>& tracks)
 {
 	const int nd = (int)engines.size(), nq = (int)rnas.size();
 	std::vector<const char*> qp((size_t)nq); std::vector<int32_t> ql((size_t)nq);
 	for (int q = 0; q < nq; q++) { qp[(size_t)q] = rnas[(size_t)q].seq.data(); ql[(size_t)q] = (int32_t)rnas[(size_t)q].seq.size(); }
 	out.assign((size_t)nq, nullptr);
+	tracks.assign(trk.bin ? (size_t)nq : 0, nullptr);
+	auto scan = [&](fasim_engine* e, int64_t first, int64_t count, fasim_result** res, fasim_track** tr) {
+		if (!trk.bin) return fasim_scan_queries(e, qp.data(), ql.data(), nq, dna, dna_len, first, count, &p, res);
+		return fasim_scan_track(e, qp.data(), ql.data(), nq, dna, dna_len, first, count, &p, trk.bin, trk.only ? nullptr : res, tr);
+	};
 	if (nd == 1) {
-		if (fasim_scan_queries(engines[0], qp.data(), ql.data(), nq, dna, dna_len, 0, -1, &p, out.data()) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(engines[0])); return 1; }
+		if (scan(engines[0], 0, -1, out.data(), tracks.data()) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(engines[0])); return 1; }
 		return 0;
 	}
 	const int64_t nseg = fasim_segment_count(dna_len, &p);
 	std::vector<std::vector<fasim_result*>> part((size_t)nd, std::vector<fasim_result*>((size_t)nq, nullptr));
+	std::vector<std::vector<fasim_track*>> tpart((size_t)nd, std::vector<fasim_track*>((size_t)nq, nullptr));
 	std::vector<int> rc((size_t)nd, 0);
 	std::vector<std::thread> th;
 	for (int d = 0; d < nd; d++) {
 		th.emplace_back([&, d] {
 			const int64_t base = nseg / nd, rem = nseg % nd;
 			const int64_t first = d * base + std::min<int64_t>(d, rem), count = base + (d < rem ? 1 : 0);
-			rc[(size_t)d] = fasim_scan_queries(engines[(size_t)d], qp.data(), ql.data(), nq, dna, dna_len, first, count, &p, part[(size_t)d].data());
+			rc[(size_t)d] = scan(engines[(size_t)d], first, count, part[(size_t)d].data(), tpart[(size_t)d].data());
 		});
 	}
 	for (auto& t : th) t.join();
 	int bad = 0;
 	for (int d = 0; d < nd; d++) if (rc[(size_t)d] != FASIM_OK) { fprintf(stderr, "fasim: device shard %d: %s\n", d, fasim_last_error(engines[(size_t)d])); bad = 1; }
-	for (int q = 0; q < nq && !bad; q++) {
+	for (int q = 0; q < nq && !bad && trk.bin; q++) {
+		std::vector<const fasim_track*> tp((size_t)nd);
+		for (int d = 0; d < nd; d++) tp[(size_t)d] = tpart[(size_t)d][(size_t)q];
+		if (fasim_track_merge(tp.data(), nd, &tracks[(size_t)q]) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); bad = 1; }
+	}
+	for (auto& v : tpart) for (fasim_track* t : v) fasim_track_free(t);
+	for (int q = 0; q < nq && !bad && !trk.only; q++) {
 		std::vector<const fasim_triplex*> recs((size_t)nd); std::vector<int64_t> counts((size_t)nd), plens((size_t)nd); std::vector<const char*> pools((size_t)nd);
 		for (int d = 0; d < nd; d++) { const fasim_result* r = part[(size_t)d][(size_t)q]; recs[(size_t)d] = r->recs; counts[(size_t)d] = r->count; pools[(size_t)d] = r->pool; plens[(size_t)d] = r->pool_len; }
 		if (fasim_merge_results(recs.data(), counts.data(), pools.data(), plens.data(), nd, &out[(size_t)q]) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); bad = 1; break; }
@@ -221,6 +242,7 @@ static int scan_record(const std::vector<fasim_engine*>& engines, const std::vec
 		}
 	}
 	for (auto& v : part) for (fasim_result* r : v) fasim_result_free(r);
+	if (bad) { for (fasim_track*& t : tracks) { fasim_track_free(t); t = nullptr; } }
 	return bad;
 }
 
@@ -304,7 +326,8 @@ int main(int argc, char* const* argv)
 	fasim_params p; fasim_params_default(&p);
 	std::string f1 = "./", f2 = "./", outdir = "./", bed_path;
 	std::vector<int> devices(1, 0);
-	bool stats = false, all_records = false, accumulate = false, upper = false;
+	bool stats = false, all_records = false, accumulate = false, upper = false, track = false;
+	TrackOpt trk;
 	int tail_flags = 0;
 	const char* optstring = "f:s:r:O:c:m:t:i:S:z:Y:Z:h:C:D:E:o:y:Fd";
 	struct option lo[] = {
@@ -313,7 +336,8 @@ int main(int argc, char* const* argv)
 		{ "cn", required_argument, NULL, 'C' }, { "ds", required_argument, NULL, 'D' }, { "lg", required_argument, NULL, 'E' },
 		{ "device", required_argument, NULL, 1001 }, { "stats", no_argument, NULL, 1002 }, { "all-records", no_argument, NULL, 1003 },
 		{ "devices", required_argument, NULL, 1004 }, { "accumulate-records", no_argument, NULL, 1005 }, { "upper", no_argument, NULL, 1006 },
-		{ "clamp-cluster", no_argument, NULL, 1007 }, { "regions", required_argument, NULL, 1008 }, { 0, 0, 0, 0 } };
+		{ "clamp-cluster", no_argument, NULL, 1007 }, { "regions", required_argument, NULL, 1008 },
+		{ "track", required_argument, NULL, 1009 }, { "track-min", required_argument, NULL, 1010 }, { "track-only", no_argument, NULL, 1011 }, { 0, 0, 0, 0 } };
 	int opt;
 	while ((opt = getopt_long_only(argc, argv, optstring, lo, NULL)) != -1) {
 		switch (opt) {
@@ -344,12 +368,19 @@ int main(int argc, char* const* argv)
 		case 1006: upper = true; break;
 		case 1007: tail_flags |= FASIM_TAIL_CLAMP_CLUSTER; break;
 		case 1008: bed_path = optarg; break;
-		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper]\n"); return 2;
+		case 1009: track = true; trk.bin = atoi(optarg); break;
+		case 1010: trk.min_value = atoi(optarg); break;
+		case 1011: trk.only = true; break;
+		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]]\n"); return 2;
 		}
 	}
 	if (all_records && accumulate) { fprintf(stderr, "fasim: --all-records and --accumulate-records exclude each other\n"); return 2; }
 	const bool regions = !bed_path.empty();
 	if (regions && (all_records || accumulate)) { fprintf(stderr, "fasim: --regions excludes --all-records and --accumulate-records\n"); return 2; }
+	if (trk.only && !track) { fprintf(stderr, "fasim: --track-only needs --track BIN\n"); return 2; }
+	if (track && trk.bin < 1) { fprintf(stderr, "fasim: --track needs a bin width of at least 1\n"); return 2; }
+	if (track && trk.min_value < 1) { fprintf(stderr, "fasim: --track-min needs a value of at least 1 (bins of value 0 are never written)\n"); return 2; }
+	if (track && (regions || accumulate || p.classicSim)) { fprintf(stderr, "fasim: --track is not available with --regions, --accumulate-records or -F\n"); return 2; }
 	// --regions: the BED file is read and checked before anything else happens (a bad file writes nothing)
 	fasim_region* reg = nullptr; int64_t nreg = 0;
 	if (regions && fasim_read_bed(bed_path.c_str(), &reg, &nreg) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 2; }
@@ -429,7 +460,8 @@ int main(int argc, char* const* argv)
 			starts.push_back(rec.start);
 			t0 = now_s();
 			std::vector<fasim_result*> res;
-			if (scan_record(engines, rnas, cumulative.data(), (int64_t)cumulative.size(), p, res)) return 1;
+			std::vector<fasim_track*> none;
+			if (scan_record(engines, rnas, cumulative.data(), (int64_t)cumulative.size(), p, res, TrackOpt(), none)) return 1;
 			tm.scan += now_s() - t0;
 			total_nt += (int64_t)cumulative.size();
 			per_rec.push_back(res);
@@ -455,15 +487,15 @@ int main(int argc, char* const* argv)
 		// record.  Default 5 120 = ten batches of 512 segments: one round of full batches for the ten workers of a scan.
 		long group_segs = 5120;
 		if (const char* g = getenv("FASIM_RECORD_GROUP")) group_segs = atol(g);
-		const bool grouped = (all_records || regions) && group_segs > 0;
+		const bool grouped = (all_records || regions) && group_segs > 0 && !track;      // (tracks: every record on its own)
 		// grouped: the tails of thousands of records go to a pool of host threads instead of four threads in flight
 		std::unique_ptr<TailPool> pool(grouped ? new TailPool(8) : nullptr);
 		// one scanned record: a DNA record, or a BED interval (species = its name, start = its 1-based start; slot = its index)
 		struct Unit { std::string species, chr; long start = 0; int64_t len = 0; size_t recno = 0; int64_t slot = -1; };
 		// per record: --stats lines, output stem, tail + write on a background thread (the next record is read and scanned meanwhile)
-		auto emit = [&](const Unit& r, const std::vector<fasim_result*>& res) {
+		auto emit = [&](const Unit& r, const std::vector<fasim_result*>& res, const std::vector<fasim_track*>& tracks) {
 			for (size_t q = 0; q < rnas.size(); q++) {
-				if (stats) {
+				if (stats && res[q]) {
 					const fasim_scan_stats& s = res[q]->stats;
 					fprintf(stderr, "[fasim] record %zu (%s) x %s: %lld segments (%lld skipped), %lld units, %lld candidates, %lld align calls, %lld records\n",
 						r.recno, r.chr.c_str(), rnas[q].name.c_str(), (long long)s.segments, (long long)s.segments_skipped, (long long)s.units,
@@ -475,12 +507,22 @@ int main(int argc, char* const* argv)
 				if (twice) fprintf(stderr, "fasim: warning: %s-TFOsorted is written twice (two lncRNAs or records of the same name): the later one wins\n", stem.c_str());
 				fasim_result* x = res[q];
 				int64_t* trip = nullptr;
+				fasim_track* tk = tracks.empty() ? nullptr : tracks[q];
+				const TrackOpt topt = trk;
 				if (r.slot >= 0) { idx_segs[q][(size_t)r.slot] = x->stats.segments; idx_stem[q][(size_t)r.slot] = name; trip = &idx_trip[q][(size_t)r.slot]; }
 				const std::string chr = r.chr, lname = rnas[q].name; const long start = r.start; const int64_t dlen = r.len;
 				auto job = [=, &tm, &p]() {
 					Timers mine;
-					const int bad = write_outputs(x, stem, chr, start, dlen, lname, p, tail_flags, mine, trip);
+					int bad = x ? write_outputs(x, stem, chr, start, dlen, lname, p, tail_flags, mine, trip) : 0;
 					fasim_result_free(x);
+					if (tk) {
+						// the potential track of the record: <stem>-TFOpotential-<BIN>
+						char* text = nullptr; int64_t len = 0;
+						if (fasim_track_bedgraph(tk, chr.c_str(), start, dlen, lname.c_str(), topt.min_value, &text, &len) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); bad = 1; }
+						else bad |= write_file(stem + "-TFOpotential-" + std::to_string(topt.bin), text, len);
+						fasim_free(text);
+						fasim_track_free(tk);
+					}
 					std::lock_guard<std::mutex> lk(g_out_mu);
 					tm.tail += mine.tail; tm.write += mine.write; if (bad) g_out_failed = 1;
 				};
@@ -510,7 +552,7 @@ int main(int argc, char* const* argv)
 			std::vector<fasim_result*> one(rnas.size());
 			for (size_t r = 0; r < group.size(); r++) {
 				for (size_t q = 0; q < rnas.size(); q++) one[q] = res[q][r];
-				emit(group[r], one);
+				emit(group[r], one, std::vector<fasim_track*>());
 				total_nt += group[r].len;
 			}
 			ngroups++; group.clear(); gdna.clear(); goff.clear(); glen.clear(); group_nseg = 0;
@@ -531,10 +573,11 @@ int main(int argc, char* const* argv)
 			}
 			const double t0 = now_s();
 			std::vector<fasim_result*> res;
-			if (scan_record(engines, rnas, seq, u.len, p, res)) return 1;
+			std::vector<fasim_track*> tracks;
+			if (scan_record(engines, rnas, seq, u.len, p, res, trk, tracks)) return 1;
 			tm.scan += now_s() - t0;
 			total_nt += u.len;
-			emit(u, res);
+			emit(u, res, tracks);
 			return 0;
 		};
 		// on an error the tails of earlier records still run on their threads: a joinable std::thread must not be destroyed

@@ -103,6 +103,27 @@ hipError_t launch_maximum3_f16(const uint32_t* a, const uint32_t* b, const uint3
 hipError_t launch_max16(const uint16_t* colmax16, const int32_t* unit_ids, int32_t nwork, const int32_t* unit_len,
 	int32_t tstride, int32_t* out, hipStream_t st);
 
+// ---- track.hip: per-base potential tracks folded from the column maxima of a batch --------------------
+// One slice = TRACK_CHUNK positions of one segment: positions [c * TRACK_CHUNK, min(n, (c + 1) * TRACK_CHUNK)) of segment s are
+// slice s * nchunk + c.  A slice holds, per class, the maxima of the record bins its positions touch, first bin first.
+constexpr int TRACK_CHUNK = 2040;          // 255 lanes x 8 positions: the reversed rows of a slice then span at most 256 aligned groups of 8
+constexpr int TRACK_MAX_LDS_BINS = 1024;   // bins of a slice for bin >= 2 (at most 2039 / 2 + 2)
+// the enabled encodings by group g = class + 4 * reversed: k[first[g] .. first[g + 1]) are the indices (0 .. nenc) of group g
+struct TrackTable { uint8_t k[48]; uint8_t first[9]; };
+inline int track_chunks(int max_len) { return (max_len + TRACK_CHUNK - 1) / TRACK_CHUNK; }
+// values per class and slice in the output (a multiple of 8): every bin a slice can touch
+__host__ __device__ inline int track_slice_stride(int bin) { const int nb = bin == 1 ? TRACK_CHUNK : (TRACK_CHUNK - 1) / bin + 2; return (nb + 7) & ~7; }
+struct TrackLaunch {
+	const uint16_t* colmax16;   // [seg * nenc + k][tstride]: 2 * column maximum + taint bit, as k_scan's main pass leaves it
+	const int32_t* seg_len;     // [nseg]
+	const int32_t* phase;       // [nseg]: record position of the segment's first base, modulo bin
+	int32_t nseg, nenc, tstride, nchunk, bin;
+	TrackTable tab;
+	uint16_t* out;              // [nseg * nchunk][4][track_slice_stride(bin)]
+	uint8_t* sat;               // [nseg * nenc], zeroed by the caller: 1 = the unit holds a saturated column maximum (16 383)
+};
+hipError_t launch_track(const TrackLaunch& L, hipStream_t st);
+
 // ---- align.hip: stage 3 ---------------------------------------------------------------------------
 struct FwdLaunch {
 	const uint8_t* stream; const FwdProb* probs; const int32_t* task_first; int32_t ntask; uint32_t* counter;

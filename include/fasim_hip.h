@@ -245,6 +245,41 @@ int fasim_scan_records(fasim_engine* e, const char* const* rnas, const int32_t* 
                        int64_t seg_first, int64_t seg_count, const fasim_params* p,
                        fasim_result** out /* [nq * nrec] (nq == 0: [nrec]), query-major */,
                        fasim_scan_stats* totals /* [nq] (nq == 0: [1]), may be NULL */);
+/* ---- per-base triplex potential tracks (csrc/track.hip) ------------------------------------------------ */
+/* What the scan computes for every base and the candidate threshold (80 % of the unit's stage-1 maximum) hides: per strand class
+ * and record bin the best local alignment score of the lncRNA that ends in the bin.  Class = the Strand column of -TFOsorted.
+ * v[c][b] = maximum over the units (segment x encoding) of class c and over the record positions x in [b * bin, (b + 1) * bin) of
+ * the unit's column maximum at x: textbook Gotoh local alignment with the stage-2 scoring (+5 / -4, N = mismatch, gap 16 + 4 per
+ * further residue, the reference's zero-score pad rows), WITHOUT the reference's 8-bit overflow cut (Q1) and lazy-F deviation (Q2);
+ * 0 where no unit covers x (segments skipped as one repeated letter, disabled classes, segments outside the selected range).
+ * Scores saturate at 16 383: a unit that reaches it reports 16 383 there and lower bounds after it (saturated_units counts them). */
+#define FASIM_TRACK_CLASSES 4      /* 0 ParaPlus 1 ParaMinus 2 AntiMinus 3 AntiPlus */
+typedef struct fasim_track {
+	int64_t nbins; int32_t bin;                 /* nbins = ceil(dna_len / bin)            */
+	uint16_t* v[FASIM_TRACK_CLASSES];            /* nbins values each                      */
+	int64_t units, saturated_units;
+} fasim_track;
+/* Shape of fasim_scan_queries (nq == 0: the engine's current query; dna == NULL: the resident record).
+ * out_results == NULL: track only, stage 3 is not run.  Otherwise out_results[q] is byte for byte what
+ * fasim_scan_queries returns.  out_tracks[q]: free with fasim_track_free.
+ * With a segment range only the selected segments contribute and the arrays still span the whole record, so the tracks of shards
+ * are merged by fasim_track_merge.  The values come from the systolic scan kernel only.  Refused before any GPU work, the engine
+ * stays usable: bin < 1 or out_tracks == NULL (FASIM_E_ARG); a query shorter than 113 nt, an engine created under FASIM_SCAN_V1=1,
+ * classicSim = 1 (FASIM_E_UNSUPPORTED, the reason in fasim_last_error). */
+int  fasim_scan_track(fasim_engine* e, const char* const* rnas, const int32_t* rna_lens, int32_t nq,
+                      const char* dna, int64_t dna_len, int64_t seg_first, int64_t seg_count, const fasim_params* p,
+                      int32_t bin, fasim_result** out_results, fasim_track** out_tracks);
+/* Element-wise maximum of `nparts` tracks of one record (shards, devices); units and saturated_units are summed.  Parts whose bin
+ * or nbins differ are refused (FASIM_E_ARG).  Free the result with fasim_track_free. */
+int  fasim_track_merge(const fasim_track* const* parts, int32_t nparts, fasim_track** out);
+/* bedGraph text: four `track type=bedGraph name='<rna> potential (<class>)'` blocks in class order, 0-based half-open genome
+ * coordinates (start_genome as in fasim_tfoclass: the 1-based genome position of the record's first base), one line
+ * `<chr>\t<start>\t<end>\t<value>` per run of equal neighbouring bins, the last bin clipped to dna_len, bins below min_value
+ * (>= 1, so zeros never appear) left out.  dna_len must be the record length the track was made for.  Free with fasim_free. */
+int  fasim_track_bedgraph(const fasim_track* t, const char* chr, int64_t start_genome, int64_t dna_len,
+                          const char* rna_name, int32_t min_value, char** text, int64_t* text_len);
+void fasim_track_free(fasim_track* t);
+
 /* Host half of the path's one exchange step: concatenates the records of `nparts` shards in the
  * order given and rebases their pool offsets.  Shards are contiguous segment ranges, so rank order IS the
  * reference's canonical (segment, encoding, fastSIM rank) order, which cluster_triplex()'s unstable sort needs.
