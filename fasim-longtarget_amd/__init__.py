@@ -104,6 +104,10 @@ class _Track(C.Structure):
                 ("saturated_units", C.c_int64)]
 
 
+class _Peak(C.Structure):
+    _fields_ = [("value", C.c_int32), ("enc", C.c_int32), ("pos", C.c_int64)]
+
+
 TRACK_CLASSES = ("ParaPlus", "ParaMinus", "AntiMinus", "AntiPlus")
 
 EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_ex", "fasim_engine_destroy", "fasim_last_error", "fasim_set_option", "fasim_set_query",
@@ -112,6 +116,7 @@ EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_e
            "fasim_tfosorted", "fasim_tfoclass", "fasim_tfosorted_ex", "fasim_tfoclass_ex", "fasim_tail_outputs", "fasim_upper_case", "fasim_free",
            "fasim_synth_dna", "fasim_selfcheck_records", "fasim_read_bed", "fasim_maximum3_f16",
            "fasim_scan_track", "fasim_track_merge", "fasim_track_bedgraph", "fasim_track_free",
+           "fasim_scan_records_track", "fasim_peaks_merge", "fasim_screen_tsv",
            # the reference's own ssw.h ABI (include/ssw.h)
            "ssw_init", "init_destroy", "ssw_pre_align", "ssw_align", "align_destroy", "encoded_ops"]
 
@@ -192,6 +197,13 @@ def lib():
                                        C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.fasim_track_free.argtypes = [C.POINTER(_Track)]
     L.fasim_track_free.restype = None
+    L.fasim_scan_records_track.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
+                                           C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int64, C.c_int64,
+                                           C.POINTER(Params), C.c_int32, C.POINTER(C.POINTER(_Result)),
+                                           C.POINTER(C.POINTER(_Track)), C.POINTER(_Peak), C.POINTER(ScanStats)]
+    L.fasim_peaks_merge.argtypes = [C.POINTER(C.POINTER(_Peak)), C.c_int32, C.c_int64, C.POINTER(_Peak)]
+    L.fasim_screen_tsv.argtypes = [C.POINTER(_Region), C.POINTER(C.c_int64), C.POINTER(_Peak), C.c_int64, C.POINTER(C.c_void_p),
+                                   C.POINTER(C.c_int64)]
     _lib = L
     return L
 
@@ -361,6 +373,67 @@ def track_bedgraph(track: Track, chr_name: str, start_genome: int, dna_len: int,
         raise FasimError(f"fasim_track_bedgraph failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
     try:
         return C.string_at(text, n.value)
+    finally:
+        L.fasim_free(text)
+
+
+def _peaks_to_c(peaks):
+    """(..., 3) integer array of (value, pos, enc) -> ctypes array of fasim_peak."""
+    import numpy as np
+    a = np.ascontiguousarray(peaks, dtype=np.int64).reshape(-1, 3)
+    arr = (_Peak * max(1, len(a)))()
+    for k, (v, pos, enc) in enumerate(a.tolist()):
+        arr[k].value, arr[k].pos, arr[k].enc = v, pos, enc
+    return arr, len(a)
+
+
+def _peaks_from_c(arr, n):
+    import numpy as np
+    out = np.empty((n, 3), dtype=np.int64)
+    for k in range(n):
+        out[k] = (arr[k].value, arr[k].pos, arr[k].enc)
+    return out
+
+
+def merge_peaks(parts):
+    """Entry-wise merge of peak arrays of one record set (fasim_peaks_merge; shards of a segment range, devices): the larger
+    value wins, then the lower pos, then the lower enc.  Arrays of (value, pos, enc) rows of one shape; returns that shape."""
+    import numpy as np
+    L = lib()
+    parts = [np.asarray(x, dtype=np.int64) for x in parts]
+    if parts and any(x.shape != parts[0].shape for x in parts):
+        raise FasimError("merge_peaks: the parts differ in shape", E_ARG)
+    cs = [_peaks_to_c(x) for x in parts]
+    n = cs[0][1] if cs else 0
+    ptrs = (C.POINTER(_Peak) * max(1, len(cs)))(*[C.cast(a, C.POINTER(_Peak)) for a, _ in cs])
+    out = (_Peak * max(1, n))()
+    rc = L.fasim_peaks_merge(ptrs, len(cs), n, out)
+    if rc != 0:
+        raise FasimError(f"fasim_peaks_merge failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
+    return _peaks_from_c(out, n).reshape(parts[0].shape)
+
+
+def screen_tsv(regions, segments, peaks) -> bytes:
+    """The bytes of `fasim --screen`'s table (fasim_screen_tsv): `regions` are Region tuples (line, chrom, start, end, name),
+    segments[k] the interval's segment count (negative: not scanned, NA line), peaks a (len(regions), 4, 3) array of
+    (value, pos within the interval, enc)."""
+    L = lib()
+    n = len(regions)
+    reg = (_Region * max(1, n))()
+    for k, g in enumerate(regions):
+        reg[k].line, reg[k].start, reg[k].end = g.line, g.start, g.end
+        reg[k].chrom, reg[k].name = g.chrom.encode(), g.name.encode()
+    segs = (C.c_int64 * max(1, n))(*[int(x) for x in segments])
+    pk, npk = _peaks_to_c(peaks)
+    if npk != 4 * n:
+        raise FasimError("screen_tsv: peaks must hold four (value, pos, enc) rows per interval", E_ARG)
+    text = C.c_void_p()
+    ln = C.c_int64()
+    rc = L.fasim_screen_tsv(reg, segs, pk, n, C.byref(text), C.byref(ln))
+    if rc != 0:
+        raise FasimError(f"fasim_screen_tsv failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
+    try:
+        return C.string_at(text, ln.value)
     finally:
         L.fasim_free(text)
 
@@ -678,6 +751,72 @@ class Engine:
         res = [[ScanResult(stats=self._stats_dict(outs[q * nrec + r].contents.stats), _native=outs[q * nrec + r]) for r in range(nrec)]
                for q in range(nqo)]
         return res[0] if rnas is None else res
+
+    def _records_track(self, blob, offs, lens, nrec, p, rnas, bin, records, seg_first, seg_count):
+        nq = 0 if rnas is None else len(rnas)
+        nqo = max(1, nq)
+        arr = (C.c_char_p * nqo)(*(rnas or []))
+        qlens = (C.c_int32 * nqo)(*[len(r) for r in (rnas or [])])
+        nout = nqo * max(1, nrec)
+        outs = (C.POINTER(_Result) * nout)() if records else None
+        trks = (C.POINTER(_Track) * nout)() if bin != 0 else None
+        peaks = (_Peak * (nout * 4))()
+        totals = (ScanStats * nqo)()
+        self._check(self._L.fasim_scan_records_track(self._h, arr, qlens, nq, blob, offs, lens, nrec, seg_first, seg_count, C.byref(p),
+                                                     bin, outs, trks, peaks, totals))
+        if nq:
+            self.m = len(rnas[-1])
+        self.last_totals = [self._stats_dict(totals[q]) for q in range(nqo)]
+        res = trk = None
+        if records:
+            res = [[ScanResult(stats=self._stats_dict(outs[q * nrec + r].contents.stats), _native=outs[q * nrec + r])
+                    for r in range(nrec)] for q in range(nqo)]
+        if trks is not None:
+            trk = [[Track(_native=trks[q * nrec + r]) for r in range(nrec)] for q in range(nqo)]
+        pk = _peaks_from_c(peaks, nout * 4).reshape(nqo, nrec, 4, 3)
+        if rnas is None:
+            return (res[0] if res else None), (trk[0] if trk else None), pk[0]
+        return res, trk, pk
+
+    def scan_records_track(self, dnas, params: Params | None = None, rnas=None, bin: int = 0, records: bool = True,
+                           seg_first: int = 0, seg_count: int = -1, rec_lens=None):
+        """Record set with its potential (fasim_scan_records_track): `(results | None, tracks | None, peaks)`.  Arguments as
+        scan_records(); bin 0: peaks only (tracks is None), bin >= 1: one Track per record, what scan_track() gives for that
+        record alone.  records False: no stage 3, results is None.  peaks: (nrec, 4, 3) int64 array of (value, pos, enc) per
+        record and strand class (TRACK_CLASSES), (0, -1, -1) where the potential is zero.  rnas given: lists per lncRNA and a
+        (nq, nrec, 4, 3) array.  Shards of a segment range merge with merge_tracks() / merge_peaks().  Totals: `self.last_totals`."""
+        p = params or default_params()
+        if dnas is None:
+            if rec_lens is None:
+                raise FasimError("scan_records_track(None, ...) needs rec_lens (the records of the resident buffer)", E_ARG)
+            lens_l, blob = [int(x) for x in rec_lens], None
+        else:
+            lens_l = [len(d) for d in dnas]
+            blob = b"".join(dnas)
+        nrec = len(lens_l)
+        offs = (C.c_int64 * max(1, nrec))()
+        lens = (C.c_int64 * max(1, nrec))()
+        o = 0
+        for i, n in enumerate(lens_l):
+            offs[i], lens[i] = o, n
+            o += n
+        return self._records_track(blob, offs, lens, nrec, p, rnas, bin, records, seg_first, seg_count)
+
+    def scan_regions_track(self, seq: bytes | None, spans, params: Params | None = None, rnas=None, bin: int = 0,
+                           records: bool = True, seg_first: int = 0, seg_count: int = -1):
+        """scan_records_track() for BED-style spans of one sequence (see scan_regions()): positions of the peaks and the tracks'
+        bins are relative to each span's start."""
+        p = params or default_params()
+        spans = [(int(s), int(e)) for s, e in spans]
+        nrec = len(spans)
+        if nrec == 0:
+            raise FasimError("scan_regions_track needs at least one span", E_ARG)
+        for k, (s, e) in enumerate(spans):
+            if s < 0 or e <= s or (seq is not None and e > len(seq)):
+                raise FasimError(f"span {k}: ({s}, {e}) is not a non-empty slice of the sequence", E_ARG)
+        offs = (C.c_int64 * nrec)(*[s for s, _ in spans])
+        lens = (C.c_int64 * nrec)(*[e - s for s, e in spans])
+        return self._records_track(seq, offs, lens, nrec, p, rnas, bin, records, seg_first, seg_count)
 
     def scan_regions(self, seq: bytes | None, spans, params: Params | None = None, rnas=None):
         """BED-style regions of one sequence (fasim_scan_records with explicit offsets): `spans` are 0-based half-open

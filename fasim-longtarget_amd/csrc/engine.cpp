@@ -97,7 +97,7 @@ void fasim_engine_destroy(fasim_engine* e)
 		&e->unit_first, &e->hz_cols, &e->hz_plan, &e->hz_base, &e->hz_items, &e->snap, &e->hz_state, &e->hz_rows, &e->hz_chunk, &e->hz_src, &e->hz_zero,
 		&e->qsim, &e->sim_min, &e->sim_row, &e->sim_ev, &e->sim_cnt, &e->sim_nodes,
 		&e->ublk, &e->btarget, &e->bidx, &e->bcounts, &e->blist[0], &e->blist[1], &e->blist[2], &e->bslots[0], &e->bslots[1], &e->bslots[2],
-		&e->bprev, &e->lane_ub, &e->fzones, &e->fubslot, &e->bdec, &e->btab, &e->swin, &e->unit_ovf, &e->track, &e->track_phase, &e->track_sat };
+		&e->bprev, &e->lane_ub, &e->fzones, &e->fubslot, &e->bdec, &e->btab, &e->swin, &e->unit_ovf, &e->track, &e->track_phase, &e->track_sat, &e->track_peaks };
 	for (auto& t : e->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
 	for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
 	for (DevBuf* b : bufs) b->release();
@@ -453,13 +453,12 @@ int fasim_scan_queries(fasim_engine* E, const char* const* rnas, const int32_t* 
 	return scan_core(E, rnas, rna_lens, nq, dna, dna_len, seg_first, seg_count, pp, outs);
 }
 
-int fasim_scan_records(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
-	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
-	fasim_result** outs, fasim_scan_stats* totals)
+// argument checks of fasim_scan_records (and fasim_scan_records_track), before any GPU work
+static int check_records_args(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
+	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, const fasim_params* pp)
 {
-	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
 	if (nrec < 1) return fail(E, FASIM_E_ARG, "a record set needs at least one record (nrec = %d)", nrec);
-	if (!rec_off || !rec_len || !pp || !outs || nq < 0) return fail(E, FASIM_E_ARG, "bad arguments");
+	if (!rec_off || !rec_len || !pp || nq < 0) return fail(E, FASIM_E_ARG, "bad arguments");
 	if (pp->cutLength <= 0 || pp->cutLength - pp->overlapLength <= 0) return fail(E, FASIM_E_ARG, "cutLength/overlapLength invalid");
 	if (nq == 0) { int rc = need_query(E); if (rc) return rc; }
 	else {
@@ -480,6 +479,17 @@ int fasim_scan_records(fasim_engine* E, const char* const* rnas, const int32_t* 
 				(long long)rec_len[r], resident ? " (the resident buffer of fasim_load_dna)" : "");
 		if (rec_len[r] > 0x7fffffffll) return fail(E, FASIM_E_ARG, "record %d: one record is limited to 2^31-1 nt (the reference's int positions)", r);
 	}
+	return FASIM_OK;
+}
+
+int fasim_scan_records(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
+	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
+	fasim_result** outs, fasim_scan_stats* totals)
+{
+	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
+	if (!outs) return fail(E, FASIM_E_ARG, "bad arguments");
+	const int rc = check_records_args(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, pp);
+	if (rc) return rc;
 	return scan_records_core(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, outs, totals);
 }
 
@@ -504,6 +514,18 @@ void fasim_track_free(fasim_track* t)
 	free(t);
 }
 
+// the potential is the column maxima of the systolic scan kernel: no other kernel leaves them
+static int check_track_source(fasim_engine* E, const int32_t* rna_lens, int32_t nq, const fasim_params* pp)
+{
+	for (int q = 0; q < std::max(1, nq); q++) {
+		const int len = nq == 0 ? E->m : rna_lens[q];
+		if (!systolic_fits(len)) return fail(E, FASIM_E_UNSUPPORTED, "potential tracks need a query of at least 113 nt (query %d has %d): shorter queries run on the striped kernels, which keep the reference's 8-bit column maxima only", q, len);
+	}
+	if (E->scan_v1) return fail(E, FASIM_E_UNSUPPORTED, "potential tracks are not available under FASIM_SCAN_V1=1 (the striped kernels keep the reference's 8-bit column maxima only)");
+	if (pp->classicSim) return fail(E, FASIM_E_UNSUPPORTED, "potential tracks are not available with classicSim (-F): that path has no stage-2 column maxima");
+	return FASIM_OK;
+}
+
 int fasim_scan_track(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna, int64_t dna_len,
 	int64_t seg_first, int64_t seg_count, const fasim_params* pp, int32_t bin, fasim_result** out_results, fasim_track** out_tracks)
 {
@@ -521,24 +543,18 @@ int fasim_scan_track(fasim_engine* E, const char* const* rnas, const int32_t* rn
 			if (rna_lens[q] > FASIM_MAX_QUERY) return refuse_long_query(E, rna_lens[q], q);
 		}
 	}
-	// the tracks are the column maxima of the systolic scan kernel: no other kernel leaves them
-	for (int q = 0; q < nquery; q++) {
-		const int len = nq == 0 ? E->m : rna_lens[q];
-		if (!systolic_fits(len)) return fail(E, FASIM_E_UNSUPPORTED, "potential tracks need a query of at least 113 nt (query %d has %d): shorter queries run on the striped kernels, which keep the reference's 8-bit column maxima only", q, len);
-	}
-	if (E->scan_v1) return fail(E, FASIM_E_UNSUPPORTED, "potential tracks are not available under FASIM_SCAN_V1=1 (the striped kernels keep the reference's 8-bit column maxima only)");
-	if (pp->classicSim) return fail(E, FASIM_E_UNSUPPORTED, "potential tracks are not available with classicSim (-F): that path has no stage-2 column maxima");
+	{ const int rc = check_track_source(E, rna_lens, nq, pp); if (rc) return rc; }
 	if (dna == nullptr) {
 		if (E->dna_host.empty()) return fail(E, FASIM_E_ARG, "no resident DNA: call fasim_load_dna first");
 		dna_len = (int64_t)E->dna_host.size();
 	} else if (dna_len <= 0) return fail(E, FASIM_E_ARG, "bad arguments");
 	if (dna_len > 0x7fffffffll) return fail(E, FASIM_E_ARG, "one record is limited to 2^31-1 nt (the reference's int positions)");
 	TrackReq tr;
-	tr.bin = bin; tr.only = out_results == nullptr; tr.nbins = (dna_len + bin - 1) / bin;
+	tr.bin = bin; tr.only = out_results == nullptr; tr.nbins.assign(1, (dna_len + bin - 1) / bin);
 	tr.sat.assign((size_t)nquery, 0); tr.mu.reset(new std::mutex[(size_t)nquery]);
 	auto drop = [&]() { for (int q = 0; q < nquery; q++) { fasim_track_free(out_tracks[q]); out_tracks[q] = nullptr; } };
 	for (int q = 0; q < nquery; q++) {
-		out_tracks[q] = track_alloc(tr.nbins, bin);
+		out_tracks[q] = track_alloc(tr.nbins[0], bin);
 		if (!out_tracks[q]) { drop(); return fail(E, FASIM_E_NOMEM, "out of memory"); }
 		for (int c = 0; c < FASIM_TRACK_CLASSES; c++) tr.v.push_back(out_tracks[q]->v[c]);
 	}
@@ -549,6 +565,84 @@ int fasim_scan_track(fasim_engine* E, const char* const* rnas, const int32_t* rn
 	for (int q = 0; q < nquery; q++) { out_tracks[q]->units = outs[q]->stats.units; out_tracks[q]->saturated_units = tr.sat[(size_t)q]; }
 	for (fasim_result* r : own) fasim_result_free(r);
 	return FASIM_OK;
+}
+
+// ---- record sets screened by potential ---------------------------------------------------------
+int fasim_scan_records_track(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
+	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp, int32_t bin,
+	fasim_result** out_results, fasim_track** out_tracks, fasim_peak* out_peaks, fasim_scan_stats* totals)
+{
+	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
+	if (bin < 0) return fail(E, FASIM_E_ARG, "track bin width %d: must be at least 1, or 0 for peaks only", bin);
+	if (bin == 0 && (out_tracks || !out_peaks)) return fail(E, FASIM_E_ARG, "bin 0 is peaks only: out_tracks must be NULL and out_peaks must not");
+	if (bin >= 1 && !out_tracks) return fail(E, FASIM_E_ARG, "bin %d needs out_tracks", bin);
+	int rc = check_records_args(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, pp);
+	if (rc) return rc;
+	const int nquery = std::max(1, nq);
+	const size_t nout = (size_t)nquery * (size_t)nrec;
+	rc = check_track_source(E, rna_lens, nq, pp); if (rc) return rc;
+	if (out_tracks) for (size_t o = 0; o < nout; o++) out_tracks[o] = nullptr;
+	if (out_results) for (size_t o = 0; o < nout; o++) out_results[o] = nullptr;
+	TrackReq tr;
+	tr.bin = bin; tr.only = out_results == nullptr; tr.nrec = nrec; tr.peaks = out_peaks;
+	tr.sat.assign(nout, 0); tr.mu.reset(new std::mutex[(size_t)nquery]);
+	if (out_peaks) for (size_t k = 0; k < nout * 4; k++) { out_peaks[k].value = 0; out_peaks[k].enc = -1; out_peaks[k].pos = -1; }
+	auto drop = [&]() { if (out_tracks) for (size_t o = 0; o < nout; o++) { fasim_track_free(out_tracks[o]); out_tracks[o] = nullptr; } };
+	if (bin >= 1) {
+		tr.nbins.resize((size_t)nrec);
+		for (int r = 0; r < nrec; r++) tr.nbins[(size_t)r] = (rec_len[r] + bin - 1) / bin;
+		tr.v.reserve(nout * 4);
+		for (size_t o = 0; o < nout; o++) {
+			out_tracks[o] = track_alloc(tr.nbins[o % (size_t)nrec], bin);
+			if (!out_tracks[o]) { drop(); return fail(E, FASIM_E_NOMEM, "out of memory"); }
+			for (int c = 0; c < FASIM_TRACK_CLASSES; c++) tr.v.push_back(out_tracks[o]->v[c]);
+		}
+	}
+	std::vector<fasim_result*> own(out_results ? 0 : nout, nullptr);
+	fasim_result** outs = out_results ? out_results : own.data();
+	rc = scan_records_core(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, outs, totals, &tr);
+	if (rc) { drop(); return rc; }
+	if (out_tracks) for (size_t o = 0; o < nout; o++) { out_tracks[o]->units = outs[o]->stats.units; out_tracks[o]->saturated_units = tr.sat[o]; }
+	for (fasim_result* r : own) fasim_result_free(r);
+	return FASIM_OK;
+}
+
+int fasim_peaks_merge(const fasim_peak* const* parts, int32_t nparts, int64_t n, fasim_peak* out)
+{
+	if (!parts || nparts < 1 || n < 0 || (n > 0 && !out)) return fail(nullptr, FASIM_E_ARG, "bad arguments");
+	for (int k = 0; k < nparts; k++) if (!parts[k] && n > 0) return fail(nullptr, FASIM_E_ARG, "bad part %d", k);
+	for (int64_t i = 0; i < n; i++) {
+		fasim_peak d = parts[0][i];
+		for (int k = 1; k < nparts; k++) {
+			const fasim_peak& x = parts[k][i];
+			if (x.value > d.value || (x.value == d.value && (x.pos < d.pos || (x.pos == d.pos && x.enc < d.enc)))) d = x;
+		}
+		out[i] = d;
+	}
+	return FASIM_OK;
+}
+
+int fasim_screen_tsv(const fasim_region* regions, const int64_t* segments, const fasim_peak* peaks, int64_t n, char** text, int64_t* text_len)
+{
+	if (n < 0 || !text || !text_len || (n > 0 && (!regions || !segments || !peaks))) return fail(nullptr, FASIM_E_ARG, "bad arguments");
+	static const char* const names[FASIM_TRACK_CLASSES] = { "ParaPlus", "ParaMinus", "AntiMinus", "AntiPlus" };
+	std::string o = "line\tname\tchrom\tstart\tend\tsegments";
+	for (const char* c : names) { o += "\t"; o += c; o += "\t"; o += c; o += "_pos\t"; o += c; o += "_rule"; }
+	o += "\n";
+	for (int64_t k = 0; k < n; k++) {
+		const fasim_region& g = regions[k];
+		if (!g.name || !g.chrom) return fail(nullptr, FASIM_E_ARG, "interval %lld has no name or chromosome", (long long)k);
+		o += std::to_string(g.line); o += "\t"; o += g.name; o += "\t"; o += g.chrom; o += "\t"; o += std::to_string(g.start); o += "\t"; o += std::to_string(g.end);
+		if (segments[k] < 0) { for (int c = 0; c < 1 + 3 * FASIM_TRACK_CLASSES; c++) o += "\tNA"; o += "\n"; continue; }
+		o += "\t"; o += std::to_string(segments[k]);
+		for (int c = 0; c < FASIM_TRACK_CLASSES; c++) {
+			const fasim_peak& pk = peaks[k * FASIM_TRACK_CLASSES + c];
+			if (pk.value <= 0 || pk.enc < 0 || pk.enc >= 48) { o += "\t0\tNA\tNA"; continue; }
+			o += "\t"; o += std::to_string(pk.value); o += "\t"; o += std::to_string(g.start + pk.pos); o += "\t"; o += std::to_string(enc_info(pk.enc).rule);
+		}
+		o += "\n";
+	}
+	return text_out(o, text, text_len);
 }
 
 int fasim_track_merge(const fasim_track* const* parts, int32_t nparts, fasim_track** out)

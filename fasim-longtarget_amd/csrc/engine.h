@@ -132,6 +132,7 @@ struct fasim_engine {
 	int opt_dp_f16 = -1;                         // option "dp_f16": packed-f16 k_scan and reverse pass, 0 = the integer kernels (-1 = default / environment FASIM_DP_F16)
 	DevBuf unit_ovf;                             // [unit] != 0: the f16 k_scan saw a value outside its exact range
 	DevBuf track, track_phase, track_sat;        // fasim_scan_track only: k_track's slices, its per-segment bin phase and saturation flags of the batch
+	DevBuf track_peaks;                          // fasim_scan_records_track only: k_track's peak per slice and class
 	int opt_numa = 1;                            // option "numa_affinity": pin the scan's host threads to the GPU's NUMA node (no-op on one node)
 	// HBM-window variant of k_striped (queries whose stripes do not fit the LDS): its scratch, the forcing switch (option
 	// "striped_window" / FASIM_STRIPED_WINDOW=1: every stripe-faithful launch takes it, for tests), problems run on it and its
@@ -382,10 +383,12 @@ struct SegTable {
 // One call: the record's arrays (those of the fasim_track objects the call returns), which the workers fold their batches' slices
 // into as soon as a batch's scan phase ends; a bin that two batches touch (overlapping segments) is merged under the query's mutex.
 struct TrackReq {
-	int bin = 1; bool only = false;              // only: no stage 3, no records
-	int64_t nbins = 0;
-	std::vector<uint16_t*> v;                    // [query * 4 + class][nbins]
-	std::vector<int64_t> sat;                    // [query]: units with a saturated column maximum
+	int bin = 1; bool only = false;              // bin == 0: peaks only, no arrays; only: no stage 3, no records
+	int nrec = 1;                                // records of the call (fasim_scan_track: 1); o = query * nrec + record below
+	std::vector<int64_t> nbins;                  // [record]
+	std::vector<uint16_t*> v;                    // [o * 4 + class][nbins[record]] (empty with bin == 0)
+	fasim_peak* peaks = nullptr;                 // [o * 4 + class], preset to (0, -1, -1), or NULL: no peaks (fasim_scan_records_track)
+	std::vector<int64_t> sat;                    // [o]: units with a saturated column maximum
 	std::unique_ptr<std::mutex[]> mu;            // [query]
 };
 // One batch, handed to run_scan_v2: where k_track's result goes
@@ -393,13 +396,15 @@ struct TrackFold {
 	int bin = 1, nseg = 0, nenc = 0, nchunk = 0; bool only = false;
 	TrackTable tab;
 	const int32_t* phase = nullptr;              // [nseg] host: record position of the segment's first base, modulo bin
-	std::vector<uint16_t>* out = nullptr;        // [nseg * nchunk][4][track_slice_stride(bin)]
+	std::vector<uint16_t>* out = nullptr;        // [nseg * nchunk][4][track_slice_stride(bin)] (bin >= 1)
 	std::vector<uint8_t>* sat = nullptr;         // [unit]
+	std::vector<TrackPeak>* peaks = nullptr;     // [nseg * nchunk][4], or NULL: no peaks
 };
 
 struct BatchCtx {
 	UnitBatch B;
 	std::vector<uint16_t> track; std::vector<uint8_t> track_sat; int track_nchunk = 0;      // fasim_scan_track: k_track's slices of this batch
+	std::vector<TrackPeak> track_peaks; bool track_done = false;                            // fasim_scan_records_track: its peaks; k_track ran
 	int tstride = 0, nenc = 0, nseg = 0;
 	int64_t step = 0;
 	// per kept segment of the batch: device start (relative to the batch's DNA on the device), length, index within its record
@@ -444,4 +449,4 @@ int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens,
 // buffer); outs[q * nrec + r], totals[q] (may be NULL)
 int scan_records_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
-	fasim_result** outs, fasim_scan_stats* totals);
+	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr = nullptr);

@@ -258,7 +258,7 @@ int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_
 	int rc = FASIM_OK;
 	const int64_t step = p.cutLength - p.overlapLength;
 	const int nenc = (int)encs.size();
-	C.B = UnitBatch(); C.tstride = tstride; C.nenc = nenc; C.nseg = 0; C.step = step; C.dna = dna; C.p = &p; C.encs = &encs; C.stage3_done = false;
+	C.B = UnitBatch(); C.tstride = tstride; C.nenc = nenc; C.nseg = 0; C.step = step; C.dna = dna; C.p = &p; C.encs = &encs; C.stage3_done = false; C.track_done = false;
 	C.per_unit.clear(); C.ucand.clear(); C.ualign.clear();
 	{
 		// segments of this batch that are not skipped by same_seq()
@@ -365,12 +365,12 @@ int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_
 				}
 				tf.tab.first[8] = (uint8_t)cnt;
 				phase.resize((size_t)nseg);
-				for (int s = 0; s < nseg; s++) phase[(size_t)s] = (int32_t)((sidx[(size_t)s] * step) % tr->bin);
-				tf.phase = phase.data(); tf.out = &C.track; tf.sat = &C.track_sat;
+				for (int s = 0; s < nseg; s++) phase[(size_t)s] = tr->bin >= 1 ? (int32_t)((sidx[(size_t)s] * step) % tr->bin) : 0;
+				tf.phase = phase.data(); tf.out = &C.track; tf.sat = &C.track_sat; tf.peaks = tr->peaks ? &C.track_peaks : nullptr;
 			}
 			rc = run_scan_v2(E, B, need1, so, &st, tr ? &tf : nullptr);
 			if (rc < 0) return rc;
-			if (rc == 0) { hoff.swap(so.hit_off); hcnt.swap(so.hit_cnt); thr.swap(so.thr); hits.swap(so.hits); done_v2 = true; }
+			if (rc == 0) { hoff.swap(so.hit_off); hcnt.swap(so.hit_cnt); thr.swap(so.thr); hits.swap(so.hits); done_v2 = true; C.track_done = tr != nullptr; }
 		}
 		st.t_stage2_s += now_s() - t0;
 		if (!done_v2) {
@@ -453,27 +453,41 @@ int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_
 }
 
 
-// fasim_scan_track: the slices of a finished scan phase into the record's arrays of query q (maximum; overlapping segments and the
-// slices of one segment that share a bin meet here)
+// fasim_scan_track / fasim_scan_records_track: the slices of a finished scan phase into the arrays of query q and of every
+// segment's own record (maximum; overlapping segments and the slices of one segment that share a bin meet here), and the slices'
+// peaks into the record's peaks (larger value, then lower position, then lower encoding)
 static void merge_track(const BatchCtx& C, TrackReq& tr, int q)
 {
-	const int stride = track_slice_stride(tr.bin);
+	const int stride = tr.bin >= 1 ? track_slice_stride(tr.bin) : 0;
 	const int64_t bin = tr.bin;
 	std::lock_guard<std::mutex> g(tr.mu[(size_t)q]);
 	for (int s = 0; s < C.nseg; s++) {
+		const size_t o = (size_t)q * (size_t)tr.nrec + (size_t)C.srec[(size_t)s];
 		const int64_t a = C.sidx[(size_t)s] * C.step;
 		const int n = C.slen[(size_t)s];
 		for (int c = 0; c * TRACK_CHUNK < n; c++) {
 			const int64_t P0 = (int64_t)c * TRACK_CHUNK, P1 = std::min<int64_t>(n, P0 + TRACK_CHUNK);
-			const int64_t b0 = (a + P0) / bin, nb = (a + P1 - 1) / bin - b0 + 1;
-			for (int cls = 0; cls < 4; cls++) {
-				const uint16_t* src = C.track.data() + (((size_t)s * C.track_nchunk + c) * 4 + cls) * stride;
-				uint16_t* dst = tr.v[(size_t)q * 4 + cls] + b0;
-				for (int64_t i = 0; i < nb; i++) dst[i] = std::max(dst[i], src[i]);
+			if (bin >= 1) {
+				const int64_t b0 = (a + P0) / bin, nb = (a + P1 - 1) / bin - b0 + 1;
+				for (int cls = 0; cls < 4; cls++) {
+					const uint16_t* src = C.track.data() + (((size_t)s * C.track_nchunk + c) * 4 + cls) * stride;
+					uint16_t* dst = tr.v[o * 4 + cls] + b0;
+					for (int64_t i = 0; i < nb; i++) dst[i] = std::max(dst[i], src[i]);
+				}
+			}
+			if (tr.peaks) {
+				for (int cls = 0; cls < 4; cls++) {
+					const TrackPeak& k = C.track_peaks[((size_t)s * C.track_nchunk + c) * 4 + cls];
+					if (k.value <= 0) continue;
+					const int64_t pos = a + k.pos;
+					const int32_t enc = (*C.encs)[(size_t)k.k];
+					fasim_peak& d = tr.peaks[o * 4 + cls];
+					if (k.value > d.value || (k.value == d.value && (pos < d.pos || (pos == d.pos && enc < d.enc)))) { d.value = k.value; d.pos = pos; d.enc = enc; }
+				}
 			}
 		}
 	}
-	for (uint8_t f : C.track_sat) tr.sat[(size_t)q] += f;
+	for (size_t u = 0; u < C.track_sat.size(); u++) tr.sat[(size_t)q * (size_t)tr.nrec + (size_t)C.srec[u / (size_t)C.nenc]] += C.track_sat[u];
 }
 
 // What one work item leaves for one record: the record's triplexes from the item's segments and the per-record stats (those
@@ -801,7 +815,7 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 				}
 				if (!r) r = scan_batch(w, dna, T, dna_dev, itx.b0, itx.b1, p, encs, tstride, ctx, ist[c], tr);
 				if (!r && tr && ctx.B.nunit > 0) {
-					if (ctx.track.empty()) r = fail(w, FASIM_E_UNSUPPORTED, "potential tracks need the systolic scan kernel");
+					if (!ctx.track_done) r = fail(w, FASIM_E_UNSUPPORTED, "potential tracks need the systolic scan kernel");
 					else { merge_track(ctx, *tr, itx.q); std::vector<uint16_t>().swap(ctx.track); }
 				}
 				if (!r && ctx.B.nunit > 0 && !ctx.stage3_done && !(tr && tr->only)) r = stage3_range(w, ctx, 0, ctx.B.nunit, ist[c]);
@@ -912,7 +926,7 @@ int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens,
 
 int scan_records_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
-	fasim_result** outs, fasim_scan_stats* totals)
+	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr)
 {
-	return scan_set(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, true, seg_first, seg_count, pp, outs, totals);
+	return scan_set(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, true, seg_first, seg_count, pp, outs, totals, tr);
 }

@@ -361,18 +361,21 @@ int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& un
 		// checkpoint pass of the chunked hazard re-run below stores its column maxima there again.  The copies complete with the
 		// batch's other results, at the next synchronisation of the stream.
 		rc = upload(E, E->track_phase, tf->phase, sizeof(int32_t) * tf->nseg); if (rc) return rc;
-		const size_t nout = (size_t)tf->nseg * tf->nchunk * 4 * track_slice_stride(tf->bin);
+		const size_t nout = tf->bin >= 1 ? (size_t)tf->nseg * tf->nchunk * 4 * track_slice_stride(tf->bin) : 0;      // (bin == 0: peaks only)
+		const size_t npeak = tf->peaks ? (size_t)tf->nseg * tf->nchunk * 4 : 0;
 		HIPOK(E->track.ensure(nout * sizeof(uint16_t))); HIPOK(E->track_sat.ensure((size_t)nu));
+		if (npeak) HIPOK(E->track_peaks.ensure(npeak * sizeof(TrackPeak)));
 		HIPOK(hipMemsetAsync(E->track_sat.p, 0, (size_t)nu, E->st));
 		TrackLaunch T;
 		T.colmax16 = E->colmax16.as<uint16_t>(); T.seg_len = E->seg_len.as<int32_t>(); T.phase = E->track_phase.as<int32_t>();
 		T.nseg = tf->nseg; T.nenc = tf->nenc; T.tstride = B.tstride; T.nchunk = tf->nchunk; T.bin = tf->bin; T.tab = tf->tab;
-		T.out = E->track.as<uint16_t>(); T.sat = E->track_sat.as<uint8_t>();
+		T.out = E->track.as<uint16_t>(); T.sat = E->track_sat.as<uint8_t>(); T.peaks = npeak ? E->track_peaks.as<TrackPeak>() : nullptr;
 		{ TimedScope ts(E, 4); he = launch_track(T, E->st); }
 		if (he != hipSuccess) return fail(E, FASIM_E_HIP, "track launch failed: %s", hipGetErrorString(he));
 		tf->out->resize(nout); tf->sat->resize((size_t)nu);
-		HIPOK(hipMemcpyAsync(tf->out->data(), E->track.p, nout * sizeof(uint16_t), hipMemcpyDeviceToHost, E->st));
+		if (nout) HIPOK(hipMemcpyAsync(tf->out->data(), E->track.p, nout * sizeof(uint16_t), hipMemcpyDeviceToHost, E->st));
 		HIPOK(hipMemcpyAsync(tf->sat->data(), E->track_sat.p, (size_t)nu, hipMemcpyDeviceToHost, E->st));
+		if (npeak) { tf->peaks->resize(npeak); HIPOK(hipMemcpyAsync(tf->peaks->data(), E->track_peaks.p, npeak * sizeof(TrackPeak), hipMemcpyDeviceToHost, E->st)); }
 		if (tf->only) { HIPOK(hipStreamSynchronize(E->st)); return FASIM_OK; }      // track only: no hits, no hazard re-run, no stage 3
 	}
 

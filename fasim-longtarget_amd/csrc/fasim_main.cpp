@@ -22,8 +22,13 @@
 //     --track BIN           per-base triplex potential (fasim_scan_track): a fourth file <stem>-TFOpotential-<BIN> per lncRNA and
 //                           record, a bedGraph with one block per strand class and one value per BIN bases (the best local
 //                           alignment score that ends there, no candidate threshold); --track-min V leaves out bins below V
-//                           (default 1); --track-only writes only that file and skips stage 3.  With --all-records every record
-//                           is scanned on its own.  Not with --regions, --accumulate-records or -F (exit status 2)
+//                           (default 1); --track-only writes only that file and skips stage 3.  With --all-records the records are
+//                           grouped as above (fasim_scan_records_track).  Not with --regions, --accumulate-records or -F (exit status 2)
+//     --screen              with --regions or --all-records: one table per lncRNA, <O>/<lnc>-<f1 stem>.screen.tsv, one line per
+//                           interval (BED order) or record: per strand class the peak of its potential, where it lies (0-based
+//                           genome coordinate) and the rule of the encoding that attains it (fasim_screen_tsv, DESIGN.md section
+//                           12).  --screen-only writes nothing else and runs no stage 3.  Exit status 2, nothing written: --screen
+//                           without --regions / --all-records, with --accumulate-records or -F, --screen-only with --track
 //     --upper               upper-case the DNA while reading (soft-masked genomes; the reference treats lower case as N)
 //     --clamp-cluster       defined behaviour where the reference's clustering does not terminate (see fasim_hip.h)
 //     --stats               timing/statistics on stderr (parse, scan, tail, write)
@@ -185,8 +190,8 @@ static int write_outputs(const fasim_result* res, const std::string& stem, const
 static std::mutex g_out_mu;
 static int g_out_failed = 0;
 
-// --track: bin width (0: no tracks), smallest value written, --track-only
-struct TrackOpt { int bin = 0, min_value = 1; bool only = false; };
+// --track: bin width (0: no tracks), smallest value written, --track-only; --screen / --screen-only: peaks (no_stage3: no records)
+struct TrackOpt { int bin = 0, min_value = 1; bool only = false, peaks = false, no_stage3 = false; };
 
 // Scans one DNA record with every lncRNA on every device: device d takes the d-th contiguous block of segments
 // (SURVEY 8(e)); per lncRNA the shard results are merged in shard order, which is the reference's canonical order.
@@ -251,21 +256,33 @@ static int scan_record(const std::vector<fasim_engine*>& engines, const std::vec
 // group, exactly what scan_record gives for that record alone.  With several devices, device d takes the d-th contiguous block of
 // the group's global segment list and every record's parts are merged in device order.
 static int scan_group(const std::vector<fasim_engine*>& engines, const std::vector<Rna>& rnas, const std::string& dna,
-	const std::vector<int64_t>& off, const std::vector<int64_t>& len, const fasim_params& p, std::vector<std::vector<fasim_result*>>& out)
+	const std::vector<int64_t>& off, const std::vector<int64_t>& len, const fasim_params& p, std::vector<std::vector<fasim_result*>>& out,
+	const TrackOpt& trk, std::vector<std::vector<fasim_track*>>& tracks, std::vector<fasim_peak>& peaks)
 {
 	const int nd = (int)engines.size(), nq = (int)rnas.size(), nrec = (int)off.size();
 	std::vector<const char*> qp((size_t)nq); std::vector<int32_t> ql((size_t)nq);
 	for (int q = 0; q < nq; q++) { qp[(size_t)q] = rnas[(size_t)q].seq.data(); ql[(size_t)q] = (int32_t)rnas[(size_t)q].seq.size(); }
 	int64_t nseg = 0;
 	for (int r = 0; r < nrec; r++) nseg += fasim_segment_count(len[(size_t)r], &p);
+	const bool with_track = trk.bin > 0, with_peaks = trk.peaks, no_res = trk.no_stage3;
+	const size_t nout = (size_t)nq * nrec;
 	out.assign((size_t)nq, std::vector<fasim_result*>((size_t)nrec, nullptr));
-	std::vector<std::vector<fasim_result*>> part((size_t)nd, std::vector<fasim_result*>((size_t)nq * nrec, nullptr));
+	tracks.assign(with_track ? (size_t)nq : 0, std::vector<fasim_track*>((size_t)nrec, nullptr));
+	peaks.clear();
+	std::vector<std::vector<fasim_result*>> part((size_t)nd, std::vector<fasim_result*>(nout, nullptr));
+	std::vector<std::vector<fasim_track*>> tpart((size_t)nd, std::vector<fasim_track*>(with_track ? nout : 0, nullptr));
+	std::vector<std::vector<fasim_peak>> ppart((size_t)nd, std::vector<fasim_peak>(with_peaks ? nout * 4 : 0));
 	std::vector<int> rc((size_t)nd, 0);
 	auto run = [&](int d) {
 		const int64_t base = nseg / nd, rem = nseg % nd;
 		const int64_t first = d * base + std::min<int64_t>(d, rem), count = base + (d < rem ? 1 : 0);
-		rc[(size_t)d] = fasim_scan_records(engines[(size_t)d], qp.data(), ql.data(), nq, dna.data(), off.data(), len.data(), nrec, first, count, &p,
-			part[(size_t)d].data(), nullptr);
+		if (!with_track && !with_peaks)
+			rc[(size_t)d] = fasim_scan_records(engines[(size_t)d], qp.data(), ql.data(), nq, dna.data(), off.data(), len.data(), nrec, first, count, &p,
+				part[(size_t)d].data(), nullptr);
+		else
+			rc[(size_t)d] = fasim_scan_records_track(engines[(size_t)d], qp.data(), ql.data(), nq, dna.data(), off.data(), len.data(), nrec, first, count, &p,
+				trk.bin, no_res ? nullptr : part[(size_t)d].data(), with_track ? tpart[(size_t)d].data() : nullptr,
+				with_peaks ? ppart[(size_t)d].data() : nullptr, nullptr);
 	};
 	if (nd == 1) run(0);
 	else { std::vector<std::thread> th; for (int d = 0; d < nd; d++) th.emplace_back(run, d); for (auto& t : th) t.join(); }
@@ -276,7 +293,7 @@ static int scan_group(const std::vector<fasim_engine*>& engines, const std::vect
 		else fprintf(stderr, "fasim: device shard %d: %s\n", d, fasim_last_error(engines[(size_t)d]));
 		bad = 1;
 	}
-	for (int q = 0; q < nq && !bad; q++) for (int r = 0; r < nrec && !bad; r++) {
+	for (int q = 0; q < nq && !bad && !no_res; q++) for (int r = 0; r < nrec && !bad; r++) {
 		const size_t k = (size_t)q * nrec + r;
 		if (nd == 1) { out[(size_t)q][(size_t)r] = part[0][k]; part[0][k] = nullptr; continue; }
 		std::vector<const fasim_triplex*> recs((size_t)nd); std::vector<int64_t> counts((size_t)nd), plens((size_t)nd); std::vector<const char*> pools((size_t)nd);
@@ -289,8 +306,26 @@ static int scan_group(const std::vector<fasim_engine*>& engines, const std::vect
 			st.align_calls += x.align_calls; st.logical_cells += x.logical_cells; st.cells_stage2 += x.cells_stage2;
 		}
 	}
+	// tracks and peaks of the device shards: maximum / (value, position, encoding) order
+	for (int q = 0; q < nq && !bad && with_track; q++) for (int r = 0; r < nrec && !bad; r++) {
+		const size_t k = (size_t)q * nrec + r;
+		if (nd == 1) { tracks[(size_t)q][(size_t)r] = tpart[0][k]; tpart[0][k] = nullptr; continue; }
+		std::vector<const fasim_track*> tp((size_t)nd);
+		for (int d = 0; d < nd; d++) tp[(size_t)d] = tpart[(size_t)d][k];
+		if (fasim_track_merge(tp.data(), nd, &tracks[(size_t)q][(size_t)r]) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); bad = 1; }
+	}
+	if (!bad && with_peaks) {
+		peaks.resize(nout * 4);
+		std::vector<const fasim_peak*> pp((size_t)nd);
+		for (int d = 0; d < nd; d++) pp[(size_t)d] = ppart[(size_t)d].data();
+		if (fasim_peaks_merge(pp.data(), nd, (int64_t)(nout * 4), peaks.data()) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); bad = 1; }
+	}
 	for (auto& v : part) for (fasim_result* x : v) fasim_result_free(x);
-	if (bad) { for (auto& v : out) for (fasim_result*& x : v) { fasim_result_free(x); x = nullptr; } }
+	for (auto& v : tpart) for (fasim_track* x : v) fasim_track_free(x);
+	if (bad) {
+		for (auto& v : out) for (fasim_result*& x : v) { fasim_result_free(x); x = nullptr; }
+		for (auto& v : tracks) for (fasim_track*& x : v) { fasim_track_free(x); x = nullptr; }
+	}
 	return bad;
 }
 
@@ -326,7 +361,7 @@ int main(int argc, char* const* argv)
 	fasim_params p; fasim_params_default(&p);
 	std::string f1 = "./", f2 = "./", outdir = "./", bed_path;
 	std::vector<int> devices(1, 0);
-	bool stats = false, all_records = false, accumulate = false, upper = false, track = false;
+	bool stats = false, all_records = false, accumulate = false, upper = false, track = false, screen = false, screen_only = false;
 	TrackOpt trk;
 	int tail_flags = 0;
 	const char* optstring = "f:s:r:O:c:m:t:i:S:z:Y:Z:h:C:D:E:o:y:Fd";
@@ -337,7 +372,8 @@ int main(int argc, char* const* argv)
 		{ "device", required_argument, NULL, 1001 }, { "stats", no_argument, NULL, 1002 }, { "all-records", no_argument, NULL, 1003 },
 		{ "devices", required_argument, NULL, 1004 }, { "accumulate-records", no_argument, NULL, 1005 }, { "upper", no_argument, NULL, 1006 },
 		{ "clamp-cluster", no_argument, NULL, 1007 }, { "regions", required_argument, NULL, 1008 },
-		{ "track", required_argument, NULL, 1009 }, { "track-min", required_argument, NULL, 1010 }, { "track-only", no_argument, NULL, 1011 }, { 0, 0, 0, 0 } };
+		{ "track", required_argument, NULL, 1009 }, { "track-min", required_argument, NULL, 1010 }, { "track-only", no_argument, NULL, 1011 },
+		{ "screen", no_argument, NULL, 1012 }, { "screen-only", no_argument, NULL, 1013 }, { 0, 0, 0, 0 } };
 	int opt;
 	while ((opt = getopt_long_only(argc, argv, optstring, lo, NULL)) != -1) {
 		switch (opt) {
@@ -371,7 +407,9 @@ int main(int argc, char* const* argv)
 		case 1009: track = true; trk.bin = atoi(optarg); break;
 		case 1010: trk.min_value = atoi(optarg); break;
 		case 1011: trk.only = true; break;
-		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]]\n"); return 2;
+		case 1012: screen = true; break;
+		case 1013: screen = screen_only = true; break;
+		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only]\n"); return 2;
 		}
 	}
 	if (all_records && accumulate) { fprintf(stderr, "fasim: --all-records and --accumulate-records exclude each other\n"); return 2; }
@@ -381,6 +419,10 @@ int main(int argc, char* const* argv)
 	if (track && trk.bin < 1) { fprintf(stderr, "fasim: --track needs a bin width of at least 1\n"); return 2; }
 	if (track && trk.min_value < 1) { fprintf(stderr, "fasim: --track-min needs a value of at least 1 (bins of value 0 are never written)\n"); return 2; }
 	if (track && (regions || accumulate || p.classicSim)) { fprintf(stderr, "fasim: --track is not available with --regions, --accumulate-records or -F\n"); return 2; }
+	if (screen && !(regions || all_records)) { fprintf(stderr, "fasim: --screen needs --regions FILE.bed or --all-records\n"); return 2; }
+	if (screen && (accumulate || p.classicSim)) { fprintf(stderr, "fasim: --screen is not available with --accumulate-records or -F\n"); return 2; }
+	if (screen_only && track) { fprintf(stderr, "fasim: --screen-only writes the screen table only: not with --track\n"); return 2; }
+	trk.peaks = screen; trk.no_stage3 = screen_only || trk.only;
 	// --regions: the BED file is read and checked before anything else happens (a bad file writes nothing)
 	fasim_region* reg = nullptr; int64_t nreg = 0;
 	if (regions && fasim_read_bed(bed_path.c_str(), &reg, &nreg) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 2; }
@@ -418,8 +460,29 @@ int main(int argc, char* const* argv)
 		}
 		return bad;
 	};
+	// --screen: per lncRNA and interval (--regions: BED order; --all-records: record order) the segments and the four peaks
+	struct ScreenRow { int64_t line = 0, start = 0, end = 0, segs = -1; std::string name, chrom; };
+	std::vector<ScreenRow> scr_rows((size_t)(screen && regions ? nreg : 0));
+	for (int64_t k = 0; k < (int64_t)scr_rows.size(); k++) { ScreenRow& w = scr_rows[(size_t)k]; w.line = reg[k].line; w.start = reg[k].start; w.end = reg[k].end; w.name = reg[k].name; w.chrom = reg[k].chrom; }
+	std::vector<std::vector<fasim_peak>> scr_peaks(screen ? rnas.size() : 0, std::vector<fasim_peak>(scr_rows.size() * 4));
+	auto write_screen = [&]() -> int {
+		int bad = 0;
+		std::vector<fasim_region> rg(scr_rows.size()); std::vector<int64_t> sg(scr_rows.size());
+		for (size_t k = 0; k < scr_rows.size(); k++) {
+			const ScreenRow& w = scr_rows[k];
+			rg[k].line = w.line; rg[k].start = w.start; rg[k].end = w.end; rg[k].chrom = w.chrom.c_str(); rg[k].name = w.name.c_str(); sg[k] = w.segs;
+		}
+		for (size_t q = 0; q < scr_peaks.size(); q++) {
+			char* text = nullptr; int64_t len = 0;
+			if (fasim_screen_tsv(rg.data(), sg.data(), scr_peaks[q].data(), (int64_t)rg.size(), &text, &len) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
+			bad |= write_file(outdir + "/" + rnas[q].name + "-" + base + ".screen.tsv", text, len);
+			fasim_free(text);
+		}
+		return bad;
+	};
 	if (regions && nreg == 0) {
-		if (write_index()) return 1;
+		if (!screen_only && write_index()) return 1;
+		if (screen && write_screen()) return 1;
 		std::cout << "finished normally" << std::endl;
 		return 0;
 	}
@@ -487,13 +550,27 @@ int main(int argc, char* const* argv)
 		// record.  Default 5 120 = ten batches of 512 segments: one round of full batches for the ten workers of a scan.
 		long group_segs = 5120;
 		if (const char* g = getenv("FASIM_RECORD_GROUP")) group_segs = atol(g);
-		const bool grouped = (all_records || regions) && group_segs > 0 && !track;      // (tracks: every record on its own)
+		// (--screen always takes the record-set call, a long record or FASIM_RECORD_GROUP=0 as a group of one)
+		const bool grouped = (all_records || regions) && (group_segs > 0 || screen);
 		// grouped: the tails of thousands of records go to a pool of host threads instead of four threads in flight
 		std::unique_ptr<TailPool> pool(grouped ? new TailPool(8) : nullptr);
 		// one scanned record: a DNA record, or a BED interval (species = its name, start = its 1-based start; slot = its index)
 		struct Unit { std::string species, chr; long start = 0; int64_t len = 0; size_t recno = 0; int64_t slot = -1; };
 		// per record: --stats lines, output stem, tail + write on a background thread (the next record is read and scanned meanwhile)
-		auto emit = [&](const Unit& r, const std::vector<fasim_result*>& res, const std::vector<fasim_track*>& tracks) {
+		auto emit = [&](const Unit& r, const std::vector<fasim_result*>& res, const std::vector<fasim_track*>& tracks, const fasim_peak* const* pk = nullptr) {
+			if (screen) {
+				// the record's line of the screen tables
+				size_t row = (size_t)r.slot;
+				if (!regions) {
+					row = scr_rows.size();
+					ScreenRow w; w.line = (int64_t)r.recno + 1; w.start = (int64_t)r.start - 1; w.end = w.start + r.len; w.name = r.species; w.chrom = r.chr;
+					scr_rows.push_back(w);
+					for (auto& v : scr_peaks) v.resize(scr_rows.size() * 4);
+				}
+				scr_rows[row].segs = fasim_segment_count(r.len, &p);
+				for (size_t q = 0; q < rnas.size(); q++) for (int c = 0; c < 4; c++) scr_peaks[q][row * 4 + c] = pk[q][c];
+				if (screen_only) return;
+			}
 			for (size_t q = 0; q < rnas.size(); q++) {
 				if (stats && res[q]) {
 					const fasim_scan_stats& s = res[q]->stats;
@@ -509,7 +586,7 @@ int main(int argc, char* const* argv)
 				int64_t* trip = nullptr;
 				fasim_track* tk = tracks.empty() ? nullptr : tracks[q];
 				const TrackOpt topt = trk;
-				if (r.slot >= 0) { idx_segs[q][(size_t)r.slot] = x->stats.segments; idx_stem[q][(size_t)r.slot] = name; trip = &idx_trip[q][(size_t)r.slot]; }
+				if (r.slot >= 0 && x) { idx_segs[q][(size_t)r.slot] = x->stats.segments; idx_stem[q][(size_t)r.slot] = name; trip = &idx_trip[q][(size_t)r.slot]; }
 				const std::string chr = r.chr, lname = rnas[q].name; const long start = r.start; const int64_t dlen = r.len;
 				auto job = [=, &tm, &p]() {
 					Timers mine;
@@ -545,14 +622,20 @@ int main(int argc, char* const* argv)
 			if (group.empty()) return 0;
 			const double t0 = now_s();
 			std::vector<std::vector<fasim_result*>> res;
-			if (scan_group(engines, rnas, gdna, goff, glen, p, res)) return 1;
+			std::vector<std::vector<fasim_track*>> gtracks;
+			std::vector<fasim_peak> gpeaks;
+			if (scan_group(engines, rnas, gdna, goff, glen, p, res, trk, gtracks, gpeaks)) return 1;
 			const double dt = now_s() - t0;
 			tm.scan += dt;
 			if (stats) fprintf(stderr, "[fasim] group %zu: %zu records, %lld segments, scan %.3f s\n", ngroups, group.size(), (long long)group_nseg, dt);
 			std::vector<fasim_result*> one(rnas.size());
+			std::vector<fasim_track*> onet(gtracks.size());
+			std::vector<const fasim_peak*> onep(rnas.size(), nullptr);
 			for (size_t r = 0; r < group.size(); r++) {
 				for (size_t q = 0; q < rnas.size(); q++) one[q] = res[q][r];
-				emit(group[r], one, std::vector<fasim_track*>());
+				for (size_t q = 0; q < gtracks.size(); q++) onet[q] = gtracks[q][r];
+				if (!gpeaks.empty()) for (size_t q = 0; q < rnas.size(); q++) onep[q] = gpeaks.data() + (q * group.size() + r) * 4;
+				emit(group[r], one, onet, gpeaks.empty() ? nullptr : onep.data());
 				total_nt += group[r].len;
 			}
 			ngroups++; group.clear(); gdna.clear(); goff.clear(); glen.clear(); group_nseg = 0;
@@ -570,6 +653,12 @@ int main(int argc, char* const* argv)
 					return group_nseg >= group_segs ? flush() : 0;
 				}
 				if (flush()) return 1;
+				if (screen) {
+					// a group of one: only the record-set call gives the peaks
+					group_nseg = fasim_segment_count(u.len, &p);
+					goff.push_back(0); glen.push_back(u.len); gdna.assign(seq, (size_t)u.len); group.push_back(std::move(u));
+					return flush();
+				}
 			}
 			const double t0 = now_s();
 			std::vector<fasim_result*> res;
@@ -633,8 +722,9 @@ int main(int argc, char* const* argv)
 		if (pool) pool->drain();
 		tm.tail_wait = now_s() - t_wait;
 		if (g_out_failed) return 1;
+		if (screen && write_screen()) return 1;
 		if (regions) {
-			if (write_index()) return 1;
+			if (!screen_only && write_index()) return 1;
 			std::vector<std::string> lost;
 			for (const auto& c : todo) for (const auto& j : c.second) {
 				const fasim_region& g = reg[j.second];

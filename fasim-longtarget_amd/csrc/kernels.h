@@ -113,13 +113,17 @@ struct TrackTable { uint8_t k[48]; uint8_t first[9]; };
 inline int track_chunks(int max_len) { return (max_len + TRACK_CHUNK - 1) / TRACK_CHUNK; }
 // values per class and slice in the output (a multiple of 8): every bin a slice can touch
 __host__ __device__ inline int track_slice_stride(int bin) { const int nb = bin == 1 ? TRACK_CHUNK : (TRACK_CHUNK - 1) / bin + 2; return (nb + 7) & ~7; }
+// peak of one slice and class (k_track with PEAKS): the slice's maximum, its smallest position within the SEGMENT, and the smallest
+// index k (0 .. nenc) of an enabled encoding of the class whose unit attains it there; value 0: pos = k = -1
+struct TrackPeak { int32_t value, pos, k, pad; };
 struct TrackLaunch {
 	const uint16_t* colmax16;   // [seg * nenc + k][tstride]: 2 * column maximum + taint bit, as k_scan's main pass leaves it
 	const int32_t* seg_len;     // [nseg]
 	const int32_t* phase;       // [nseg]: record position of the segment's first base, modulo bin
-	int32_t nseg, nenc, tstride, nchunk, bin;
+	int32_t nseg, nenc, tstride, nchunk, bin;      // bin == 0: peaks only, no slices
 	TrackTable tab;
 	uint16_t* out;              // [nseg * nchunk][4][track_slice_stride(bin)]
+	TrackPeak* peaks = nullptr; // [nseg * nchunk][4], or NULL: no peaks (the slices of a segment's unused chunks are not written)
 	uint8_t* sat;               // [nseg * nenc], zeroed by the caller: 1 = the unit holds a saturated column maximum (16 383)
 };
 hipError_t launch_track(const TrackLaunch& L, hipStream_t st);

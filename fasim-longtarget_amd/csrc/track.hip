@@ -20,6 +20,11 @@
 //     runs of one bin, then the workgroup reduces in LDS (ds_max_u32) and writes each bin of the slice once.  Slices never share an
 //     output element (neighbouring slices that touch the same record bin are merged by the host, as overlapping segments are), so
 //     there are no global atomics.
+//   * peaks (fasim_scan_records_track): the variants with PEAKS also leave, per slice and class, the slice's
+//     maximum, its smallest position and the smallest encoding that attains it there.  A lane packs (maximum, 0xffff - first slot of
+//     the maximum among its 8 positions) into one word, the word's maximum is taken over the wave with __shfl_xor and over the four
+//     waves through LDS, and lane 0 of wave c then reads that one column again from the rows of class c (forward and mirrored, at
+//     most 24) for the encoding.  One 16-byte store per (slice, class).  The variant without SLICES (bin == 0) writes nothing else.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"
@@ -40,10 +45,15 @@ __device__ __forceinline__ bool track_saturated(v8u v)
 	return m[0] >= 32766 || m[1] >= 32766;
 }
 
+typedef int v4i __attribute__((ext_vector_type(4)));
+
+// SLICES: the binned slices of the tracks go to a.out (bin >= 1); PEAKS: the slice's peak per class goes to a.peaks
+template <bool SLICES, bool PEAKS>
 __global__ void __launch_bounds__(256) k_track(TrackLaunch a)
 {
 	__shared__ __align__(16) uint16_t rev[4][TRACK_CHUNK + 8];      // class maxima of the reversed rows, by position within the slice
-	__shared__ uint32_t binacc[4][TRACK_MAX_LDS_BINS];             // bin > 1: the slice's bins
+	__shared__ uint32_t binacc[4][SLICES ? TRACK_MAX_LDS_BINS : 1];  // bin > 1: the slice's bins
+	__shared__ uint32_t wkey[4][PEAKS ? 4 : 1];                     // peaks: per class the four waves' best (value, slot) words
 	const int chunk = blockIdx.x, seg = blockIdx.y, t = threadIdx.x;
 	const int n = a.seg_len[seg];
 	const int P0 = chunk * TRACK_CHUNK;
@@ -100,8 +110,8 @@ __global__ void __launch_bounds__(256) k_track(TrackLaunch a)
 			}
 		}
 	}
-	const int nbc = a.bin > 1 ? (int)(((uint32_t)a.phase[seg] + (uint32_t)(P1 - 1)) / (uint32_t)a.bin - ((uint32_t)a.phase[seg] + (uint32_t)P0) / (uint32_t)a.bin) + 1 : 0;
-	for (int i = t; i < 4 * nbc; i += 256) binacc[i / nbc][i % nbc] = 0;
+	const int nbc = SLICES && a.bin > 1 ? (int)(((uint32_t)a.phase[seg] + (uint32_t)(P1 - 1)) / (uint32_t)a.bin - ((uint32_t)a.phase[seg] + (uint32_t)P0) / (uint32_t)a.bin) + 1 : 0;
+	if constexpr (SLICES) { for (int i = t; i < 4 * nbc; i += 256) binacc[i / nbc][i % nbc] = 0; }
 	__syncthreads();
 	v8u val[4];
 #pragma unroll
@@ -112,6 +122,49 @@ __global__ void __launch_bounds__(256) k_track(TrackLaunch a)
 			val[c] = __builtin_elementwise_max(facc[c], r) >> (v8u)(1);
 		}
 	}
+	if constexpr (PEAKS) {
+		// value first, then the smaller slot: the maximum of (value << 16) | (0xffff - slot); lanes past the slice hold zeros
+		uint32_t key[4];
+#pragma unroll
+		for (int c = 0; c < 4; c++) {
+			uint32_t best = 0;
+#pragma unroll
+			for (int e = 0; e < 8; e++) best = max(best, ((uint32_t)val[c][e] << 16) | (uint32_t)(0xffff - (8 * t + e)));
+			key[c] = best;
+		}
+#pragma unroll
+		for (int d = 32; d >= 1; d >>= 1) {
+#pragma unroll
+			for (int c = 0; c < 4; c++) key[c] = max(key[c], (uint32_t)__shfl_xor((int)key[c], d));
+		}
+		if ((t & 63) == 0) {
+#pragma unroll
+			for (int c = 0; c < 4; c++) wkey[c][t >> 6] = key[c];
+		}
+		__syncthreads();
+		if ((t & 63) == 0) {
+			const int c = t >> 6;
+			const uint32_t k = max(max(wkey[c][0], wkey[c][1]), max(wkey[c][2], wkey[c][3]));
+			const int value = (int)(k >> 16);
+			v4i pk = { 0, -1, -1, 0 };
+			if (value > 0) {
+				// the column again, row by row: forward rows at the position, reversed rows at its mirror image (pos < P1 <= n <= tstride)
+				const int pos = P0 + (int)(0xffff - (k & 0xffff));
+				int enc = 0x7fffffff;
+				for (int i = a.tab.first[c]; i < a.tab.first[c + 1]; i++) {
+					const int r = a.tab.k[i];
+					if ((int)(base[(int64_t)r * a.tstride + pos] >> 1) == value) enc = min(enc, r);
+				}
+				for (int i = a.tab.first[4 + c]; i < a.tab.first[5 + c]; i++) {
+					const int r = a.tab.k[i];
+					if ((int)(base[(int64_t)r * a.tstride + (n - 1 - pos)] >> 1) == value) enc = min(enc, r);
+				}
+				pk = (v4i){ value, pos, enc, 0 };
+			}
+			*reinterpret_cast<v4i*>(a.peaks + ((int64_t)seg * a.nchunk + chunk) * 4 + c) = pk;
+		}
+	}
+	if constexpr (!SLICES) return;
 	const int stride = track_slice_stride(a.bin);
 	uint16_t* out = a.out + ((int64_t)seg * a.nchunk + chunk) * 4 * stride;
 	if (a.bin == 1) {
@@ -146,8 +199,11 @@ __global__ void __launch_bounds__(256) k_track(TrackLaunch a)
 hipError_t launch_track(const TrackLaunch& L, hipStream_t st)
 {
 	if (L.nseg <= 0 || L.nchunk <= 0) return hipSuccess;
-	if (L.bin < 1 || (L.tstride & 7) != 0 || L.nenc < 1 || L.nenc > 48) return hipErrorInvalidValue;
-	hipLaunchKernelGGL(k_track, dim3((unsigned)L.nchunk, (unsigned)L.nseg), dim3(256), 0, st, L);
+	if (L.bin < 0 || (L.bin == 0 && !L.peaks) || (L.tstride & 7) != 0 || L.nenc < 1 || L.nenc > 48) return hipErrorInvalidValue;
+	const dim3 grid((unsigned)L.nchunk, (unsigned)L.nseg);
+	if (!L.peaks) hipLaunchKernelGGL((k_track<true, false>), grid, dim3(256), 0, st, L);
+	else if (L.bin >= 1) hipLaunchKernelGGL((k_track<true, true>), grid, dim3(256), 0, st, L);
+	else hipLaunchKernelGGL((k_track<false, true>), grid, dim3(256), 0, st, L);
 	return hipGetLastError();
 }
 

@@ -279,6 +279,29 @@ int  fasim_track_merge(const fasim_track* const* parts, int32_t nparts, fasim_tr
 int  fasim_track_bedgraph(const fasim_track* t, const char* chr, int64_t start_genome, int64_t dna_len,
                           const char* rna_name, int32_t min_value, char** text, int64_t* text_len);
 void fasim_track_free(fasim_track* t);
+/* ---- record sets and BED intervals screened by potential ------------------------------------------------ */
+/* Peak of one (record, class): value = the maximum of the record's per-base potential P[c][x] (the bin = 1 track of the record
+ * scanned alone), pos = the smallest record position x (0-based) that attains it, enc = the smallest enabled encoding index of the
+ * class for which a unit covering pos attains it at pos.  value == 0: pos = enc = -1.  A function of the record and the parameters
+ * only (not of batches, workers, shards, devices or dp_f16, nor of whether tracks or stage 3 were asked for). */
+typedef struct fasim_peak { int32_t value, enc; int64_t pos; } fasim_peak;
+/* fasim_scan_records with the potential of every record: arguments, record cutting, global segment numbering and the refusals of
+ * fasim_scan_records, plus those of fasim_scan_track (a query under 113 nt, FASIM_SCAN_V1=1, classicSim: FASIM_E_UNSUPPORTED).
+ * Indexing is [q * nrec + r] (peaks: [(q * nrec + r) * 4 + c]; nq == 0: the engine's query, q = 0).
+ * bin == 0: peaks only (out_tracks must be NULL, out_peaks must not): the kernel writes no track slices and only the slices'
+ * peaks come back.  bin >= 1: out_tracks[q * nrec + r] is one fasim_track spanning record r, exactly what fasim_scan_track gives
+ * for that record alone restricted to the selected segments (free each with fasim_track_free); out_peaks may be NULL.  bin < 0:
+ * FASIM_E_ARG.  out_results == NULL: no stage 3 (the work ends after the scan kernel and k_track); otherwise out_results and
+ * totals are byte for byte those of fasim_scan_records.  With a segment range only the selected segments contribute: merge the
+ * shards with fasim_track_merge / fasim_peaks_merge.  Every refusal happens before any GPU work and leaves the engine usable. */
+int fasim_scan_records_track(fasim_engine* e, const char* const* rnas, const int32_t* rna_lens, int32_t nq,
+                             const char* dna, const int64_t* rec_off, const int64_t* rec_len, int32_t nrec,
+                             int64_t seg_first, int64_t seg_count, const fasim_params* p, int32_t bin,
+                             fasim_result** out_results /* [nq * nrec] or NULL */, fasim_track** out_tracks /* [nq * nrec] or NULL */,
+                             fasim_peak* out_peaks /* [nq * nrec * 4] or NULL */, fasim_scan_stats* totals /* [nq], may be NULL */);
+/* Entry-wise merge of `nparts` arrays of n peaks each (shards, devices): the larger value wins, then the lower pos, then the lower
+ * enc.  (0, -1, -1) entries therefore lose against every peak of value >= 1. */
+int fasim_peaks_merge(const fasim_peak* const* parts, int32_t nparts, int64_t n, fasim_peak* out);
 
 /* Host half of the path's one exchange step: concatenates the records of `nparts` shards in the
  * order given and rebases their pool offsets.  Shards are contiguous segment ranges, so rank order IS the
@@ -341,6 +364,13 @@ typedef struct fasim_region {
  * line number and the reason in fasim_last_error(NULL)): fewer than 3 columns, a start or end that is not an integer,
  * start < 0, end <= start, end - start > 2^31 - 1, an unreadable file.  *out is ONE block (free it with fasim_free); *n may be 0. */
 int fasim_read_bed(const char* path, fasim_region** out, int64_t* n);
+/* The bytes of `fasim --screen`'s table for n intervals: a header line, then one line per interval in the order given, columns
+ * line name chrom start end segments and, per class in order (ParaPlus ParaMinus AntiMinus AntiPlus), <Class> <Class>_pos
+ * <Class>_rule: the peak value, its 0-based genome coordinate regions[k].start + pos, and the Rule value -TFOsorted prints for the
+ * peak's encoding.  A zero peak has NA in its _pos and _rule columns; an interval with segments[k] < 0 (not scanned: it lies in no
+ * DNA record) has NA in every column after `end`.  peaks: [n * 4], positions relative to the interval.  Free with fasim_free. */
+int fasim_screen_tsv(const fasim_region* regions, const int64_t* segments, const fasim_peak* peaks, int64_t n,
+                     char** text, int64_t* text_len);
 /* ingest helper: upper-cases a DNA record in place (soft-masked genomes such as UCSC hg38 carry repeats in lower
  * case; the reference does not upper-case and treats such letters as unknown, rules.h:286-312, 82-83). */
 void fasim_upper_case(char* seq, int64_t n);
