@@ -104,6 +104,10 @@ class _Track(C.Structure):
                 ("saturated_units", C.c_int64)]
 
 
+class _TfoProfile(C.Structure):
+    _fields_ = [("m", C.c_int32), ("v", C.POINTER(C.c_uint16) * 4), ("units", C.c_int64), ("saturated_units", C.c_int64)]
+
+
 class _Peak(C.Structure):
     _fields_ = [("value", C.c_int32), ("enc", C.c_int32), ("pos", C.c_int64)]
 
@@ -117,6 +121,7 @@ EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_e
            "fasim_synth_dna", "fasim_selfcheck_records", "fasim_read_bed", "fasim_maximum3_f16",
            "fasim_scan_track", "fasim_track_merge", "fasim_track_bedgraph", "fasim_track_free",
            "fasim_scan_records_track", "fasim_peaks_merge", "fasim_screen_tsv",
+           "fasim_scan_tfo_profile", "fasim_tfo_profile_merge", "fasim_tfo_profile_tsv", "fasim_tfo_profile_free",
            # the reference's own ssw.h ABI (include/ssw.h)
            "ssw_init", "init_destroy", "ssw_pre_align", "ssw_align", "align_destroy", "encoded_ops"]
 
@@ -204,6 +209,14 @@ def lib():
     L.fasim_peaks_merge.argtypes = [C.POINTER(C.POINTER(_Peak)), C.c_int32, C.c_int64, C.POINTER(_Peak)]
     L.fasim_screen_tsv.argtypes = [C.POINTER(_Region), C.POINTER(C.c_int64), C.POINTER(_Peak), C.c_int64, C.POINTER(C.c_void_p),
                                    C.POINTER(C.c_int64)]
+    L.fasim_scan_tfo_profile.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
+                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int64, C.c_int64,
+                                         C.POINTER(Params), C.c_int32, C.POINTER(C.POINTER(_Result)),
+                                         C.POINTER(C.POINTER(_TfoProfile)), C.POINTER(ScanStats)]
+    L.fasim_tfo_profile_merge.argtypes = [C.POINTER(C.POINTER(_TfoProfile)), C.c_int32, C.POINTER(C.POINTER(_TfoProfile))]
+    L.fasim_tfo_profile_tsv.argtypes = [C.POINTER(_TfoProfile), C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.fasim_tfo_profile_free.argtypes = [C.POINTER(_TfoProfile)]
+    L.fasim_tfo_profile_free.restype = None
     _lib = L
     return L
 
@@ -371,6 +384,93 @@ def track_bedgraph(track: Track, chr_name: str, start_genome: int, dna_len: int,
                                 C.byref(text), C.byref(n))
     if rc != 0:
         raise FasimError(f"fasim_track_bedgraph failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
+    try:
+        return C.string_at(text, n.value)
+    finally:
+        L.fasim_free(text)
+
+
+class TfoProfile:
+    """Per-base profile of one lncRNA (struct fasim_tfo_profile): per strand class (TRACK_CLASSES) and base of the lncRNA the best
+    local alignment score that ends on that base, over the scanned records.  Either a native profile (what scan_tfo_profile()
+    and merge_tfo_profiles() return) or one made from a (4, m) array: `TfoProfile(values, units=0, saturated_units=0)`."""
+
+    def __init__(self, values=None, units: int = 0, saturated_units: int = 0, _native=None):
+        self._native = _native
+        self._keep = None
+        if _native is None:
+            import numpy as np
+            a = np.ascontiguousarray(values, dtype=np.uint16)
+            if a.ndim != 2 or a.shape[0] != 4:
+                raise FasimError("a profile is a (4, m) array", E_ARG)
+            t = _TfoProfile()
+            t.m, t.units, t.saturated_units = a.shape[1], units, saturated_units
+            for c in range(4):
+                t.v[c] = C.cast(a[c].ctypes.data, C.POINTER(C.c_uint16))
+            self._keep = (a, t)
+
+    def __del__(self):
+        try:
+            if self._native is not None:
+                lib().fasim_tfo_profile_free(self._native)
+                self._native = None
+        except Exception:
+            pass
+
+    def pointer(self):
+        """POINTER(fasim_tfo_profile) for the C-ABI; valid while this object lives."""
+        return self._native if self._native is not None else C.pointer(self._keep[1])
+
+    @property
+    def _t(self):
+        return self._native.contents if self._native is not None else self._keep[1]
+
+    @property
+    def m(self) -> int:
+        return int(self._t.m)
+
+    @property
+    def units(self) -> int:
+        return int(self._t.units)
+
+    @property
+    def saturated_units(self) -> int:
+        return int(self._t.saturated_units)
+
+    def array(self):
+        """(4, m) numpy uint16 array (a copy), rows in TRACK_CLASSES order."""
+        import numpy as np
+        t, n = self._t, self.m
+        out = np.zeros((4, n), dtype=np.uint16)
+        for c in range(4):
+            if n:
+                C.memmove(out[c].ctypes.data, t.v[c], 2 * n)
+        return out
+
+
+def merge_tfo_profiles(parts) -> TfoProfile:
+    """Element-wise maximum of the profiles of one lncRNA (fasim_tfo_profile_merge): shards of a segment range, devices."""
+    L = lib()
+    parts = list(parts)
+    arr = (C.POINTER(_TfoProfile) * max(1, len(parts)))(*[t.pointer() for t in parts])
+    out = C.POINTER(_TfoProfile)()
+    rc = L.fasim_tfo_profile_merge(arr, len(parts), C.byref(out))
+    if rc != 0:
+        raise FasimError(f"fasim_tfo_profile_merge failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
+    return TfoProfile(_native=out)
+
+
+def tfo_profile_tsv(profile: TfoProfile, rna: bytes, rna_name: str = "") -> bytes:
+    """The table `fasim --tfo-profile` writes (fasim_tfo_profile_tsv): header `pos base ParaPlus ParaMinus AntiMinus AntiPlus`,
+    then one tab-separated line per base of the lncRNA."""
+    L = lib()
+    if len(rna) != profile.m:
+        raise FasimError(f"the lncRNA has {len(rna)} bases, the profile {profile.m}", E_ARG)
+    text = C.c_void_p()
+    n = C.c_int64()
+    rc = L.fasim_tfo_profile_tsv(profile.pointer(), rna, rna_name.encode(), C.byref(text), C.byref(n))
+    if rc != 0:
+        raise FasimError(f"fasim_tfo_profile_tsv failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
     try:
         return C.string_at(text, n.value)
     finally:
@@ -751,6 +851,51 @@ class Engine:
         res = [[ScanResult(stats=self._stats_dict(outs[q * nrec + r].contents.stats), _native=outs[q * nrec + r]) for r in range(nrec)]
                for q in range(nqo)]
         return res[0] if rnas is None else res
+
+    def scan_tfo_profile(self, dnas, params: Params | None = None, rnas=None, per_record: bool = False, records: bool = True,
+                         seg_first: int = 0, seg_count: int = -1):
+        """Per-base profile of the lncRNA (fasim_scan_tfo_profile): `(results | None, profiles)`.  `dnas`: a list of records, or
+        one `bytes` (a single record).  rnas None: the engine's query; results is what scan_records() returns (one ScanResult
+        per record) and profiles one TfoProfile over the whole set, or with per_record a list, one per record, each what that
+        record scanned alone gives.  rnas given: lists per lncRNA of those.  records False: no stage 3, results is None.
+        Shards of a segment range merge with merge_tfo_profiles().  Totals: `self.last_totals`."""
+        p = params or default_params()
+        if isinstance(dnas, (bytes, bytearray)):
+            dnas = [bytes(dnas)]
+        lens_l = [len(d) for d in dnas]
+        blob = b"".join(dnas)
+        nrec = len(lens_l)
+        offs = (C.c_int64 * max(1, nrec))()
+        lens = (C.c_int64 * max(1, nrec))()
+        o = 0
+        for i, n in enumerate(lens_l):
+            offs[i], lens[i] = o, n
+            o += n
+        nq = 0 if rnas is None else len(rnas)
+        nqo = max(1, nq)
+        arr = (C.c_char_p * nqo)(*(rnas or []))
+        qlens = (C.c_int32 * nqo)(*[len(r) for r in (rnas or [])])
+        nout = nqo * max(1, nrec)
+        nprof = nout if per_record else nqo
+        outs = (C.POINTER(_Result) * nout)() if records else None
+        profs = (C.POINTER(_TfoProfile) * nprof)()
+        totals = (ScanStats * nqo)()
+        self._check(self._L.fasim_scan_tfo_profile(self._h, arr, qlens, nq, blob, offs, lens, nrec, seg_first, seg_count, C.byref(p),
+                                                   1 if per_record else 0, outs, profs, totals))
+        if nq:
+            self.m = len(rnas[-1])
+        self.last_totals = [self._stats_dict(totals[q]) for q in range(nqo)]
+        res = None
+        if records:
+            res = [[ScanResult(stats=self._stats_dict(outs[q * nrec + r].contents.stats), _native=outs[q * nrec + r])
+                    for r in range(nrec)] for q in range(nqo)]
+        if per_record:
+            prof = [[TfoProfile(_native=profs[q * nrec + r]) for r in range(nrec)] for q in range(nqo)]
+        else:
+            prof = [TfoProfile(_native=profs[q]) for q in range(nqo)]
+        if rnas is None:
+            return (res[0] if res else None), prof[0]
+        return res, prof
 
     def _records_track(self, blob, offs, lens, nrec, p, rnas, bin, records, seg_first, seg_count):
         nq = 0 if rnas is None else len(rnas)

@@ -97,7 +97,8 @@ void fasim_engine_destroy(fasim_engine* e)
 		&e->unit_first, &e->hz_cols, &e->hz_plan, &e->hz_base, &e->hz_items, &e->snap, &e->hz_state, &e->hz_rows, &e->hz_chunk, &e->hz_src, &e->hz_zero,
 		&e->qsim, &e->sim_min, &e->sim_row, &e->sim_ev, &e->sim_cnt, &e->sim_nodes,
 		&e->ublk, &e->btarget, &e->bidx, &e->bcounts, &e->blist[0], &e->blist[1], &e->blist[2], &e->bslots[0], &e->bslots[1], &e->bslots[2],
-		&e->bprev, &e->lane_ub, &e->fzones, &e->fubslot, &e->bdec, &e->btab, &e->swin, &e->unit_ovf, &e->track, &e->track_phase, &e->track_sat, &e->track_peaks };
+		&e->bprev, &e->lane_ub, &e->fzones, &e->fubslot, &e->bdec, &e->btab, &e->swin, &e->unit_ovf, &e->track, &e->track_phase, &e->track_sat, &e->track_peaks,
+		&e->rowmax16, &e->row_out, &e->row_gfirst, &e->row_sat };
 	for (auto& t : e->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
 	for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
 	for (DevBuf* b : bufs) b->release();
@@ -605,6 +606,95 @@ int fasim_scan_records_track(fasim_engine* E, const char* const* rnas, const int
 	if (out_tracks) for (size_t o = 0; o < nout; o++) { out_tracks[o]->units = outs[o]->stats.units; out_tracks[o]->saturated_units = tr.sat[o]; }
 	for (fasim_result* r : own) fasim_result_free(r);
 	return FASIM_OK;
+}
+
+// ---- per-base profile of the lncRNA ------------------------------------------------------------
+static fasim_tfo_profile* tfo_profile_alloc(int32_t m)
+{
+	fasim_tfo_profile* t = (fasim_tfo_profile*)calloc(1, sizeof(fasim_tfo_profile));
+	if (!t) return nullptr;
+	t->m = m;
+	for (int c = 0; c < FASIM_TRACK_CLASSES; c++) {
+		t->v[c] = (uint16_t*)calloc((size_t)std::max<int32_t>(1, m), sizeof(uint16_t));
+		if (!t->v[c]) { fasim_tfo_profile_free(t); return nullptr; }
+	}
+	return t;
+}
+
+void fasim_tfo_profile_free(fasim_tfo_profile* t)
+{
+	if (!t) return;
+	for (int c = 0; c < FASIM_TRACK_CLASSES; c++) free(t->v[c]);
+	free(t);
+}
+
+int fasim_scan_tfo_profile(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
+	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp, int32_t per_record,
+	fasim_result** out_results, fasim_tfo_profile** out_profiles, fasim_scan_stats* totals)
+{
+	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
+	if (!out_profiles) return fail(E, FASIM_E_ARG, "bad arguments");
+	int rc = check_records_args(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, pp);
+	if (rc) return rc;
+	const int nquery = std::max(1, nq);
+	const size_t nout = (size_t)nquery * (size_t)nrec, nprof = per_record ? nout : (size_t)nquery;
+	// the profile is the row maxima of the systolic scan kernel: the refusals are those of the potential tracks
+	rc = check_track_source(E, rna_lens, nq, pp); if (rc) return rc;
+	for (size_t o = 0; o < nprof; o++) out_profiles[o] = nullptr;
+	if (out_results) for (size_t o = 0; o < nout; o++) out_results[o] = nullptr;
+	TfoReq pr;
+	pr.only = out_results == nullptr; pr.per_record = per_record != 0; pr.nrec = nrec;
+	pr.units.assign(nprof, 0); pr.sat.assign(nprof, 0); pr.mu.reset(new std::mutex[(size_t)nquery]);
+	for (int q = 0; q < nquery; q++) pr.m.push_back(nq == 0 ? E->m : rna_lens[q]);
+	auto drop = [&]() { for (size_t o = 0; o < nprof; o++) { fasim_tfo_profile_free(out_profiles[o]); out_profiles[o] = nullptr; } };
+	pr.v.reserve(nprof * 4);
+	for (size_t o = 0; o < nprof; o++) {
+		out_profiles[o] = tfo_profile_alloc(pr.m[per_record ? o / (size_t)nrec : o]);
+		if (!out_profiles[o]) { drop(); return fail(E, FASIM_E_NOMEM, "out of memory"); }
+		for (int c = 0; c < FASIM_TRACK_CLASSES; c++) pr.v.push_back(out_profiles[o]->v[c]);
+	}
+	std::vector<fasim_result*> own(out_results ? 0 : nout, nullptr);
+	fasim_result** outs = out_results ? out_results : own.data();
+	rc = scan_records_core(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, outs, totals, nullptr, &pr);
+	for (fasim_result* r : own) fasim_result_free(r);
+	if (rc) { drop(); return rc; }
+	for (size_t o = 0; o < nprof; o++) { out_profiles[o]->units = pr.units[o]; out_profiles[o]->saturated_units = pr.sat[o]; }
+	return FASIM_OK;
+}
+
+int fasim_tfo_profile_merge(const fasim_tfo_profile* const* parts, int32_t nparts, fasim_tfo_profile** out)
+{
+	if (!parts || nparts < 1 || !out) return fail(nullptr, FASIM_E_ARG, "bad arguments");
+	*out = nullptr;
+	for (int k = 0; k < nparts; k++) {
+		if (!parts[k] || parts[k]->m < 0) return fail(nullptr, FASIM_E_ARG, "bad profile %d", k);
+		if (parts[k]->m != parts[0]->m)
+			return fail(nullptr, FASIM_E_ARG, "profile %d has %d bases, profile 0 has %d: only profiles of one lncRNA merge", k, parts[k]->m, parts[0]->m);
+	}
+	fasim_tfo_profile* t = tfo_profile_alloc(parts[0]->m);
+	if (!t) return fail(nullptr, FASIM_E_NOMEM, "out of memory");
+	for (int k = 0; k < nparts; k++) {
+		t->units += parts[k]->units; t->saturated_units += parts[k]->saturated_units;
+		for (int c = 0; c < FASIM_TRACK_CLASSES; c++) {
+			const uint16_t* src = parts[k]->v[c]; uint16_t* dst = t->v[c];
+			for (int32_t i = 0; i < t->m; i++) dst[i] = std::max(dst[i], src[i]);
+		}
+	}
+	*out = t;
+	return FASIM_OK;
+}
+
+int fasim_tfo_profile_tsv(const fasim_tfo_profile* t, const char* rna, const char* rna_name, char** text, int64_t* text_len)
+{
+	if (!t || !rna || !text || !text_len || t->m < 0) return fail(nullptr, FASIM_E_ARG, "bad arguments");
+	(void)rna_name;      // (the table itself carries no name: the caller names the file)
+	std::string o = "pos\tbase\tParaPlus\tParaMinus\tAntiMinus\tAntiPlus\n";
+	char line[96];
+	for (int32_t i = 0; i < t->m; i++) {
+		const int n = snprintf(line, sizeof line, "%d\t%c\t%d\t%d\t%d\t%d\n", i + 1, rna[i], (int)t->v[0][i], (int)t->v[1][i], (int)t->v[2][i], (int)t->v[3][i]);
+		o.append(line, (size_t)n);
+	}
+	return text_out(o, text, text_len);
 }
 
 int fasim_peaks_merge(const fasim_peak* const* parts, int32_t nparts, int64_t n, fasim_peak* out)

@@ -133,6 +133,7 @@ struct fasim_engine {
 	DevBuf unit_ovf;                             // [unit] != 0: the f16 k_scan saw a value outside its exact range
 	DevBuf track, track_phase, track_sat;        // fasim_scan_track only: k_track's slices, its per-segment bin phase and saturation flags of the batch
 	DevBuf track_peaks;                          // fasim_scan_records_track only: k_track's peak per slice and class
+	DevBuf rowmax16, row_out, row_gfirst, row_sat;   // fasim_scan_tfo_profile only: k_scan's row maxima of the batch, k_rowfold's groups, result and saturation flags
 	int opt_numa = 1;                            // option "numa_affinity": pin the scan's host threads to the GPU's NUMA node (no-op on one node)
 	// HBM-window variant of k_striped (queries whose stripes do not fit the LDS): its scratch, the forcing switch (option
 	// "striped_window" / FASIM_STRIPED_WINDOW=1: every stripe-faithful launch takes it, for tests), problems run on it and its
@@ -401,8 +402,30 @@ struct TrackFold {
 	std::vector<TrackPeak>* peaks = nullptr;     // [nseg * nchunk][4], or NULL: no peaks
 };
 
+// ---- per-base profile of the lncRNA (fasim_scan_tfo_profile, rowfold.hip) ---------------------------------------------------------
+// One call: the arrays of the fasim_tfo_profile objects the call returns, per o = query * nrec + record (per_record) or per query;
+// the workers fold their batches' groups into them under the query's mutex as soon as a batch's scan phase ends.
+struct TfoReq {
+	bool only = false, per_record = false;       // only: no stage 3, no records
+	int nrec = 1;
+	std::vector<int32_t> m;                      // [query]: rows of the result
+	std::vector<uint16_t*> v;                    // [o * 4 + class][m[query]]
+	std::vector<int64_t> units, sat;             // [o]: units folded in, units with a saturated row maximum
+	std::unique_ptr<std::mutex[]> mu;            // [query]
+};
+// One batch, handed to run_scan_v2: the groups of k_rowfold and where its result goes
+struct RowFold {
+	int nseg = 0, nenc = 0; bool only = false;
+	TrackTable tab;
+	std::vector<int32_t> gfirst;                 // [groups + 1]: group g = segments [gfirst[g], gfirst[g + 1]) of the batch
+	std::vector<uint16_t>* out = nullptr;        // [groups][4][16 * ceil(m/16)]
+	std::vector<uint8_t>* sat = nullptr;         // [unit]
+};
+
 struct BatchCtx {
 	UnitBatch B;
+	std::vector<uint16_t> rowfold; std::vector<uint8_t> row_sat; std::vector<int32_t> row_gfirst;      // fasim_scan_tfo_profile: k_rowfold's groups of this batch
+	bool rows_done = false;
 	std::vector<uint16_t> track; std::vector<uint8_t> track_sat; int track_nchunk = 0;      // fasim_scan_track: k_track's slices of this batch
 	std::vector<TrackPeak> track_peaks; bool track_done = false;                            // fasim_scan_records_track: its peaks; k_track ran
 	int tstride = 0, nenc = 0, nseg = 0;
@@ -430,14 +453,16 @@ int run_striped(fasim_engine* E, StripedMode mode, bool word, const std::vector<
 int prep_striped_window(fasim_engine* E, StripedMode mode, bool word, StripedLaunch& L, bool* used);
 int run_stage1(fasim_engine* E, const UnitBatch& B, std::vector<int>& score, int64_t* word_reruns);
 int run_stage2(fasim_engine* E, const UnitBatch& B);
-int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& unit_needs_stage1, ScanOut& out, fasim_scan_stats* st, const TrackFold* tf = nullptr);
+int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& unit_needs_stage1, ScanOut& out, fasim_scan_stats* st, const TrackFold* tf = nullptr,
+	const RowFold* rf = nullptr);
 int load_raw_targets(fasim_engine* E, const char* targets, const int64_t* offsets, const int32_t* lens, int nprob, bool stage1, UnitBatch& B);
 int need_query(fasim_engine* E);
 int run_align(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb>& W, std::vector<AlignResult>& out, std::vector<uint32_t>& cigars, fasim_scan_stats* stats);
 int run_align_v2(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb>& W, std::vector<AlignResult>& out, std::vector<uint32_t>& cigars, fasim_scan_stats* stats);
 int stage3_range(fasim_engine* E, BatchCtx& C, int ua, int ub, fasim_scan_stats& st);
 int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_t* dna_dev, int64_t b0, int64_t b1,
-	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st, const TrackReq* tr = nullptr);
+	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st, const TrackReq* tr = nullptr,
+	const TfoReq* pr = nullptr);
 int sim_forward_units(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, const int32_t* unit_len_dev, const int32_t* unit_len_host,
 	int first, int nunit, const int64_t* mins, std::atomic<int>* ready, std::vector<std::vector<fasim_sim_node>>& lists);
 int sim_resweep_rounds(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, const int32_t* unit_len_dev, const int32_t* unit_len_host,
@@ -445,8 +470,10 @@ int sim_resweep_rounds(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, 
 int pack_result(fasim_engine* E, std::vector<HostTriplex>& all, const fasim_scan_stats& st, fasim_result** out);
 int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna, int64_t dna_len,
 	int64_t seg_first, int64_t seg_count, const fasim_params* pp, fasim_result** outs, TrackReq* tr = nullptr);
+// the class tables of k_track / k_rowfold: the enabled encodings by group = class + 4 * reversed
+TrackTable class_table(const std::vector<int>& encs);
 // fasim_scan_records after its argument checks: records [rec_off[r], rec_off[r] + rec_len[r]) of `dna` (NULL: the resident
 // buffer); outs[q * nrec + r], totals[q] (may be NULL)
 int scan_records_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
-	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr = nullptr);
+	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr = nullptr, TfoReq* pr = nullptr);

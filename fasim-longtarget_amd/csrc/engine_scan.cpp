@@ -249,16 +249,33 @@ int sim_resweep_rounds(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, 
 }
 
 
+TrackTable class_table(const std::vector<int>& encs)
+{
+	TrackTable tab;
+	int cnt = 0;
+	for (int g = 0; g < 8; g++) {
+		tab.first[g] = (uint8_t)cnt;
+		for (int k = 0; k < (int)encs.size(); k++) {
+			const EncInfo ei = enc_info(encs[(size_t)k]);
+			const int cls = ei.para == 1 ? (ei.strand == 0 ? 0 : 1) : (ei.strand == 1 ? 2 : 3);
+			if (cls + 4 * (ei.reversed ? 1 : 0) == g) tab.k[cnt++] = (uint8_t)k;
+		}
+	}
+	tab.first[8] = (uint8_t)cnt;
+	for (int k = cnt; k < 48; k++) tab.k[k] = 0;
+	return tab;
+}
+
 // Segments [b0, b1) of the call's segment table on one worker.  `dna_dev`: the resident buffer (fasim_load_dna), or NULL for a
 // host buffer.  The kernels take int32 segment starts relative to the batch's own first byte on the device, so a record set
 // longer than 2^31 nt works as long as one batch's span does.
 int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_t* dna_dev, int64_t b0, int64_t b1,
-	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st, const TrackReq* tr)
+	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st, const TrackReq* tr, const TfoReq* pr)
 {
 	int rc = FASIM_OK;
 	const int64_t step = p.cutLength - p.overlapLength;
 	const int nenc = (int)encs.size();
-	C.B = UnitBatch(); C.tstride = tstride; C.nenc = nenc; C.nseg = 0; C.step = step; C.dna = dna; C.p = &p; C.encs = &encs; C.stage3_done = false; C.track_done = false;
+	C.B = UnitBatch(); C.tstride = tstride; C.nenc = nenc; C.nseg = 0; C.step = step; C.dna = dna; C.p = &p; C.encs = &encs; C.stage3_done = false; C.track_done = false; C.rows_done = false;
 	C.per_unit.clear(); C.ucand.clear(); C.ualign.clear();
 	{
 		// segments of this batch that are not skipped by same_seq()
@@ -368,9 +385,18 @@ int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_
 				for (int s = 0; s < nseg; s++) phase[(size_t)s] = tr->bin >= 1 ? (int32_t)((sidx[(size_t)s] * step) % tr->bin) : 0;
 				tf.phase = phase.data(); tf.out = &C.track; tf.sat = &C.track_sat; tf.peaks = tr->peaks ? &C.track_peaks : nullptr;
 			}
-			rc = run_scan_v2(E, B, need1, so, &st, tr ? &tf : nullptr);
+			RowFold rf;
+			if (pr) {
+				// the lncRNA's profile: one group per run of segments of one record, or the whole batch as one group
+				rf.nseg = nseg; rf.nenc = nenc; rf.only = pr->only; rf.tab = class_table(encs);
+				rf.gfirst.push_back(0);
+				if (pr->per_record) for (int s = 1; s < nseg; s++) if (C.srec[(size_t)s] != C.srec[(size_t)s - 1]) rf.gfirst.push_back(s);
+				rf.gfirst.push_back(nseg);
+				rf.out = &C.rowfold; rf.sat = &C.row_sat;
+			}
+			rc = run_scan_v2(E, B, need1, so, &st, tr ? &tf : nullptr, pr ? &rf : nullptr);
 			if (rc < 0) return rc;
-			if (rc == 0) { hoff.swap(so.hit_off); hcnt.swap(so.hit_cnt); thr.swap(so.thr); hits.swap(so.hits); done_v2 = true; C.track_done = tr != nullptr; }
+			if (rc == 0) { hoff.swap(so.hit_off); hcnt.swap(so.hit_cnt); thr.swap(so.thr); hits.swap(so.hits); done_v2 = true; C.track_done = tr != nullptr; C.rows_done = pr != nullptr; C.row_gfirst.swap(rf.gfirst); }
 		}
 		st.t_stage2_s += now_s() - t0;
 		if (!done_v2) {
@@ -488,6 +514,24 @@ static void merge_track(const BatchCtx& C, TrackReq& tr, int q)
 		}
 	}
 	for (size_t u = 0; u < C.track_sat.size(); u++) tr.sat[(size_t)q * (size_t)tr.nrec + (size_t)C.srec[u / (size_t)C.nenc]] += C.track_sat[u];
+}
+
+// fasim_scan_tfo_profile: the groups of a finished scan phase into the arrays of query q (and of the group's record), by maximum
+static void merge_rows(const BatchCtx& C, TfoReq& pr, int q)
+{
+	const int m = pr.m[(size_t)q], rows_total = 16 * ((m + 15) / 16);
+	std::lock_guard<std::mutex> g(pr.mu[(size_t)q]);
+	for (size_t gi = 0; gi + 1 < C.row_gfirst.size(); gi++) {
+		const int s0 = C.row_gfirst[gi], s1 = C.row_gfirst[gi + 1];
+		const size_t o = pr.per_record ? (size_t)q * (size_t)pr.nrec + (size_t)C.srec[(size_t)s0] : (size_t)q;
+		for (int cls = 0; cls < 4; cls++) {
+			const uint16_t* src = C.rowfold.data() + (gi * 4 + (size_t)cls) * (size_t)rows_total;      // (pad rows [m, rows_total) are not part of the result)
+			uint16_t* dst = pr.v[o * 4 + (size_t)cls];
+			for (int i = 0; i < m; i++) dst[i] = std::max(dst[i], src[i]);
+		}
+		pr.units[o] += (int64_t)(s1 - s0) * C.nenc;
+		for (int u = s0 * C.nenc; u < s1 * C.nenc; u++) pr.sat[o] += C.row_sat[(size_t)u];
+	}
 }
 
 // What one work item leaves for one record: the record's triplexes from the item's segments and the per-record stats (those
@@ -625,7 +669,7 @@ static void add_stats(fasim_scan_stats& st, const fasim_scan_stats& x)
 // whole call's stats.  `records` true: outs[q * nrec + r] carries the per-record stats, totals[q] (if given) the call's.
 static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int nrec, bool records, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
-	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr = nullptr)
+	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr = nullptr, TfoReq* pr = nullptr)
 {
 	const bool resident = (dna == nullptr);
 	if (resident) dna = E->dna_host.data();
@@ -725,6 +769,15 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 		if (!envb && E->opt_seg_batch <= 0 && !p.classicSim) {
 			if (tiles > 16) seg_batch = std::max<int64_t>(1, seg_batch * 16 / tiles);
 		}
+		// profile calls: k_scan's row maxima take 2 * 16 * ceil(m/16) bytes per unit; a batch in flight keeps them under 256 MB
+		// (H19 at the default batch: 512 x 48 units x 2 816 rows = 138 MB, no change; a 92 256 nt query: 30 segments per batch)
+		int64_t rows_cap = INT64_MAX;
+		if (pr) {
+			int mmax = 16;
+			for (int q = 0; q < nquery; q++) mmax = std::max(mmax, (int)queries[(size_t)q].size());
+			rows_cap = std::max<int64_t>(1, ((int64_t)256 << 20) / ((int64_t)nenc * 2 * 16 * ((mmax + 15) / 16)));
+			if (!envb && E->opt_seg_batch <= 0) seg_batch = std::min(seg_batch, rows_cap);
+		}
 		// batches of the call: ranges of the segment table (local indices; a batch may cross records)
 		std::vector<std::pair<int64_t, int64_t>> chunks;
 		if (records && !envb && E->opt_seg_batch <= 0 && !p.classicSim) {
@@ -734,6 +787,7 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 			// block maxima keep their size), and the > 16-tile rule as above.
 			int64_t cap = std::max<int64_t>(1, std::min<int64_t>((int64_t)512 * 48 / nenc, ((int64_t)8 << 30) / ((int64_t)4 * nenc * tstride)));
 			if (tiles > 16) cap = std::max<int64_t>(1, cap * 16 / tiles);
+			cap = std::min(cap, rows_cap);
 			const int64_t per_query = std::max<int64_t>(1, (nworkers + nquery - 1) / nquery);
 			const int64_t target = std::max<int64_t>(1, std::min<int64_t>((int64_t)384 * p.cutLength, (total_bases + per_query - 1) / per_query));
 			int64_t b0 = 0, bases = 0;
@@ -813,12 +867,16 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 					r = fasim_set_query(w, rq.data(), (int)rq.size());
 					if (r && w != E) w->err = std::string("worker set_query failed: ") + w->err;
 				}
-				if (!r) r = scan_batch(w, dna, T, dna_dev, itx.b0, itx.b1, p, encs, tstride, ctx, ist[c], tr);
+				if (!r) r = scan_batch(w, dna, T, dna_dev, itx.b0, itx.b1, p, encs, tstride, ctx, ist[c], tr, pr);
+				if (!r && pr && ctx.B.nunit > 0) {
+					if (!ctx.rows_done) r = fail(w, FASIM_E_UNSUPPORTED, "the lncRNA's profile needs the systolic scan kernel");
+					else { merge_rows(ctx, *pr, itx.q); std::vector<uint16_t>().swap(ctx.rowfold); }
+				}
 				if (!r && tr && ctx.B.nunit > 0) {
 					if (!ctx.track_done) r = fail(w, FASIM_E_UNSUPPORTED, "potential tracks need the systolic scan kernel");
 					else { merge_track(ctx, *tr, itx.q); std::vector<uint16_t>().swap(ctx.track); }
 				}
-				if (!r && ctx.B.nunit > 0 && !ctx.stage3_done && !(tr && tr->only)) r = stage3_range(w, ctx, 0, ctx.B.nunit, ist[c]);
+				if (!r && ctx.B.nunit > 0 && !ctx.stage3_done && !(tr && tr->only) && !(pr && pr->only)) r = stage3_range(w, ctx, 0, ctx.B.nunit, ist[c]);
 				(void)hipStreamSynchronize(w->st);
 				drain_timed(w);
 				for (int k = 0; k < FASIM_KERNEL_FAMILIES; k++) { ist[c].kernel_ms[k] = w->kernel_ms[k]; ist[c].kernel_launches[k] = w->kernel_launches[k]; w->kernel_ms[k] = 0; w->kernel_launches[k] = 0; }
@@ -926,7 +984,7 @@ int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens,
 
 int scan_records_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
-	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr)
+	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr, TfoReq* pr)
 {
-	return scan_set(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, true, seg_first, seg_count, pp, outs, totals, tr);
+	return scan_set(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, true, seg_first, seg_count, pp, outs, totals, tr, pr);
 }

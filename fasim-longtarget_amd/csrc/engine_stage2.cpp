@@ -261,7 +261,7 @@ int run_hazard_chunked(fasim_engine* E, const UnitBatch& B, const std::vector<in
 
 // returns 1 when the query does not fit the kernel (caller falls back to the striped kernels)
 int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& unit_needs_stage1, ScanOut& out,
-	fasim_scan_stats* st, const TrackFold* tf)
+	fasim_scan_stats* st, const TrackFold* tf, const RowFold* rf)
 {
 	const int nu = B.nunit;
 	HIPOK(E->colmax16.ensure((size_t)nu * B.tstride * sizeof(uint16_t)));
@@ -320,6 +320,13 @@ int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& un
 			L.ublk = E->ublk.as<uint16_t>(); L.ublk_blocks = nb; E->ublk_units = nu; E->ublk_blocks = nb;
 		} else (void)hipGetLastError();
 	}
+	// row maxima for the lncRNA's profile (fasim_scan_tfo_profile): the main pass and the integer re-run below take their ROWS
+	// variant; the stage-1 pass above and the checkpoint pass never write them
+	const int rows_total = 16 * ((E->m + 15) / 16);
+	if (rf) {
+		HIPOK(E->rowmax16.ensure((size_t)nu * rows_total * sizeof(uint16_t)));
+		L.rowmax16 = E->rowmax16.as<uint16_t>();
+	}
 	// the main pass in packed f16 (option dp_f16): exact while every score of a unit stays below 1 024; the kernel flags the others
 	if (dp_f16_mode(E)) {
 		HIPOK(E->unit_ovf.ensure(sizeof(int32_t) * nu));
@@ -355,6 +362,24 @@ int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& un
 			HIPOK(hipStreamSynchronize(E->st));
 			if (st) st->dp_f16_reruns += (int64_t)again.size();      // (cells_stage2 stays the count of one pass over every unit)
 		}
+	}
+	L.rowmax16 = nullptr;
+	if (rf) {
+		// the lncRNA's profile: rowmax16 holds the main pass of every unit now (the re-run has overwritten the void rows of its units)
+		const int ng = (int)rf->gfirst.size() - 1;
+		const size_t nout = (size_t)ng * 4 * rows_total;
+		rc = upload(E, E->row_gfirst, rf->gfirst.data(), sizeof(int32_t) * rf->gfirst.size()); if (rc) return rc;
+		HIPOK(E->row_out.ensure(nout * sizeof(uint16_t))); HIPOK(E->row_sat.ensure((size_t)nu));
+		HIPOK(hipMemsetAsync(E->row_sat.p, 0, (size_t)nu, E->st));
+		RowFoldLaunch R;
+		R.rowmax16 = E->rowmax16.as<uint16_t>(); R.gfirst = E->row_gfirst.as<int32_t>(); R.ngroups = ng; R.nenc = rf->nenc; R.rows_total = rows_total;
+		R.tab = rf->tab; R.out = E->row_out.as<uint16_t>(); R.sat = E->row_sat.as<uint8_t>();
+		{ TimedScope ts(E, 4); he = launch_rowfold(R, E->st); }
+		if (he != hipSuccess) return fail(E, FASIM_E_HIP, "rowfold launch failed: %s", hipGetErrorString(he));
+		rf->out->resize(nout); rf->sat->resize((size_t)nu);
+		HIPOK(hipMemcpyAsync(rf->out->data(), E->row_out.p, nout * sizeof(uint16_t), hipMemcpyDeviceToHost, E->st));
+		HIPOK(hipMemcpyAsync(rf->sat->data(), E->row_sat.p, (size_t)nu, hipMemcpyDeviceToHost, E->st));
+		if (rf->only) { HIPOK(hipStreamSynchronize(E->st)); return FASIM_OK; }      // profile only: no hits, no hazard re-run, no stage 3
 	}
 	if (tf) {
 		// potential tracks (fasim_scan_track): colmax16 holds the main pass of every unit now -- k_scan_post only reads it, but the

@@ -24,6 +24,11 @@
 //                           alignment score that ends there, no candidate threshold); --track-min V leaves out bins below V
 //                           (default 1); --track-only writes only that file and skips stage 3.  With --all-records the records are
 //                           grouped as above (fasim_scan_records_track).  Not with --regions, --accumulate-records or -F (exit status 2)
+//     --tfo-profile         per-base profile of the lncRNA (fasim_scan_tfo_profile): per strand class and base of
+//                           the lncRNA the best local alignment score that ends on that base.  A plain run writes a fourth file
+//                           <stem>-TFOprofile per lncRNA; with --all-records or --regions one whole-set table per lncRNA,
+//                           <O>/<lnc>-<f1 stem>.tfoprofile.tsv.  --tfo-profile-only writes only the table and runs no stage 3.
+//                           Not with -F, --accumulate-records, --track or --screen (exit status 2, nothing written)
 //     --screen              with --regions or --all-records: one table per lncRNA, <O>/<lnc>-<f1 stem>.screen.tsv, one line per
 //                           interval (BED order) or record: per strand class the peak of its potential, where it lies (0-based
 //                           genome coordinate) and the rule of the encoding that attains it (fasim_screen_tsv, DESIGN.md section
@@ -191,37 +196,58 @@ static std::mutex g_out_mu;
 static int g_out_failed = 0;
 
 // --track: bin width (0: no tracks), smallest value written, --track-only; --screen / --screen-only: peaks (no_stage3: no records)
-struct TrackOpt { int bin = 0, min_value = 1; bool only = false, peaks = false, no_stage3 = false; };
+// --tfo-profile / --tfo-profile-only: the lncRNA's profile (never together with tracks or peaks)
+struct TrackOpt { int bin = 0, min_value = 1; bool only = false, peaks = false, no_stage3 = false, tfo = false, tfo_only = false; };
+
+// acc = max(acc, part) by fasim_tfo_profile_merge; takes `part` over
+static int tfo_fold(fasim_tfo_profile*& acc, fasim_tfo_profile* part)
+{
+	if (!acc) { acc = part; return 0; }
+	const fasim_tfo_profile* two[2] = { acc, part };
+	fasim_tfo_profile* sum = nullptr;
+	const int rc = fasim_tfo_profile_merge(two, 2, &sum);
+	fasim_tfo_profile_free(part);
+	if (rc != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
+	fasim_tfo_profile_free(acc);
+	acc = sum;
+	return 0;
+}
 
 // Scans one DNA record with every lncRNA on every device: device d takes the d-th contiguous block of segments
 // (SURVEY 8(e)); per lncRNA the shard results are merged in shard order, which is the reference's canonical order.
 // With --track the potential tracks come back in `tracks` (shards merged by maximum); --track-only leaves `out` NULL.
 static int scan_record(const std::vector<fasim_engine*>& engines, const std::vector<Rna>& rnas, const char* dna, int64_t dna_len, const fasim_params& p,
-	std::vector<fasim_result*>& out, const TrackOpt& trk, std::vector<fasim_track*>& tracks)
+	std::vector<fasim_result*>& out, const TrackOpt& trk, std::vector<fasim_track*>& tracks, std::vector<fasim_tfo_profile*>* profs = nullptr)
 {
 	const int nd = (int)engines.size(), nq = (int)rnas.size();
+	const bool no_res = trk.only || trk.tfo_only;
+	if (profs) profs->assign((size_t)nq, nullptr);
 	std::vector<const char*> qp((size_t)nq); std::vector<int32_t> ql((size_t)nq);
 	for (int q = 0; q < nq; q++) { qp[(size_t)q] = rnas[(size_t)q].seq.data(); ql[(size_t)q] = (int32_t)rnas[(size_t)q].seq.size(); }
 	out.assign((size_t)nq, nullptr);
 	tracks.assign(trk.bin ? (size_t)nq : 0, nullptr);
-	auto scan = [&](fasim_engine* e, int64_t first, int64_t count, fasim_result** res, fasim_track** tr) {
+	auto scan = [&](fasim_engine* e, int64_t first, int64_t count, fasim_result** res, fasim_track** tr, fasim_tfo_profile** pf) {
+		// (--tfo-profile: the record as a set of one; its records are those of fasim_scan_queries)
+		const int64_t off0 = 0;
+		if (profs) return fasim_scan_tfo_profile(e, qp.data(), ql.data(), nq, dna, &off0, &dna_len, 1, first, count, &p, 0, no_res ? nullptr : res, pf, nullptr);
 		if (!trk.bin) return fasim_scan_queries(e, qp.data(), ql.data(), nq, dna, dna_len, first, count, &p, res);
 		return fasim_scan_track(e, qp.data(), ql.data(), nq, dna, dna_len, first, count, &p, trk.bin, trk.only ? nullptr : res, tr);
 	};
 	if (nd == 1) {
-		if (scan(engines[0], 0, -1, out.data(), tracks.data()) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(engines[0])); return 1; }
+		if (scan(engines[0], 0, -1, out.data(), tracks.data(), profs ? profs->data() : nullptr) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(engines[0])); return 1; }
 		return 0;
 	}
 	const int64_t nseg = fasim_segment_count(dna_len, &p);
 	std::vector<std::vector<fasim_result*>> part((size_t)nd, std::vector<fasim_result*>((size_t)nq, nullptr));
 	std::vector<std::vector<fasim_track*>> tpart((size_t)nd, std::vector<fasim_track*>((size_t)nq, nullptr));
+	std::vector<std::vector<fasim_tfo_profile*>> fpart((size_t)nd, std::vector<fasim_tfo_profile*>((size_t)nq, nullptr));
 	std::vector<int> rc((size_t)nd, 0);
 	std::vector<std::thread> th;
 	for (int d = 0; d < nd; d++) {
 		th.emplace_back([&, d] {
 			const int64_t base = nseg / nd, rem = nseg % nd;
 			const int64_t first = d * base + std::min<int64_t>(d, rem), count = base + (d < rem ? 1 : 0);
-			rc[(size_t)d] = scan(engines[(size_t)d], first, count, part[(size_t)d].data(), tpart[(size_t)d].data());
+			rc[(size_t)d] = scan(engines[(size_t)d], first, count, part[(size_t)d].data(), tpart[(size_t)d].data(), fpart[(size_t)d].data());
 		});
 	}
 	for (auto& t : th) t.join();
@@ -233,7 +259,13 @@ static int scan_record(const std::vector<fasim_engine*>& engines, const std::vec
 		if (fasim_track_merge(tp.data(), nd, &tracks[(size_t)q]) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); bad = 1; }
 	}
 	for (auto& v : tpart) for (fasim_track* t : v) fasim_track_free(t);
-	for (int q = 0; q < nq && !bad && !trk.only; q++) {
+	for (int q = 0; q < nq && !bad && profs; q++) {
+		std::vector<const fasim_tfo_profile*> fp((size_t)nd);
+		for (int d = 0; d < nd; d++) fp[(size_t)d] = fpart[(size_t)d][(size_t)q];
+		if (fasim_tfo_profile_merge(fp.data(), nd, &(*profs)[(size_t)q]) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); bad = 1; }
+	}
+	for (auto& v : fpart) for (fasim_tfo_profile* t : v) fasim_tfo_profile_free(t);
+	for (int q = 0; q < nq && !bad && !no_res; q++) {
 		std::vector<const fasim_triplex*> recs((size_t)nd); std::vector<int64_t> counts((size_t)nd), plens((size_t)nd); std::vector<const char*> pools((size_t)nd);
 		for (int d = 0; d < nd; d++) { const fasim_result* r = part[(size_t)d][(size_t)q]; recs[(size_t)d] = r->recs; counts[(size_t)d] = r->count; pools[(size_t)d] = r->pool; plens[(size_t)d] = r->pool_len; }
 		if (fasim_merge_results(recs.data(), counts.data(), pools.data(), plens.data(), nd, &out[(size_t)q]) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); bad = 1; break; }
@@ -248,6 +280,7 @@ static int scan_record(const std::vector<fasim_engine*>& engines, const std::vec
 	}
 	for (auto& v : part) for (fasim_result* r : v) fasim_result_free(r);
 	if (bad) { for (fasim_track*& t : tracks) { fasim_track_free(t); t = nullptr; } }
+	if (bad && profs) for (fasim_tfo_profile*& t : *profs) { fasim_tfo_profile_free(t); t = nullptr; }
 	return bad;
 }
 
@@ -257,7 +290,7 @@ static int scan_record(const std::vector<fasim_engine*>& engines, const std::vec
 // the group's global segment list and every record's parts are merged in device order.
 static int scan_group(const std::vector<fasim_engine*>& engines, const std::vector<Rna>& rnas, const std::string& dna,
 	const std::vector<int64_t>& off, const std::vector<int64_t>& len, const fasim_params& p, std::vector<std::vector<fasim_result*>>& out,
-	const TrackOpt& trk, std::vector<std::vector<fasim_track*>>& tracks, std::vector<fasim_peak>& peaks)
+	const TrackOpt& trk, std::vector<std::vector<fasim_track*>>& tracks, std::vector<fasim_peak>& peaks, std::vector<fasim_tfo_profile*>* profs = nullptr)
 {
 	const int nd = (int)engines.size(), nq = (int)rnas.size(), nrec = (int)off.size();
 	std::vector<const char*> qp((size_t)nq); std::vector<int32_t> ql((size_t)nq);
@@ -272,11 +305,17 @@ static int scan_group(const std::vector<fasim_engine*>& engines, const std::vect
 	std::vector<std::vector<fasim_result*>> part((size_t)nd, std::vector<fasim_result*>(nout, nullptr));
 	std::vector<std::vector<fasim_track*>> tpart((size_t)nd, std::vector<fasim_track*>(with_track ? nout : 0, nullptr));
 	std::vector<std::vector<fasim_peak>> ppart((size_t)nd, std::vector<fasim_peak>(with_peaks ? nout * 4 : 0));
+	// --tfo-profile: one profile per lncRNA over the whole group
+	std::vector<std::vector<fasim_tfo_profile*>> fpart((size_t)nd, std::vector<fasim_tfo_profile*>(profs ? (size_t)nq : 0, nullptr));
+	if (profs) profs->assign((size_t)nq, nullptr);
 	std::vector<int> rc((size_t)nd, 0);
 	auto run = [&](int d) {
 		const int64_t base = nseg / nd, rem = nseg % nd;
 		const int64_t first = d * base + std::min<int64_t>(d, rem), count = base + (d < rem ? 1 : 0);
-		if (!with_track && !with_peaks)
+		if (profs)
+			rc[(size_t)d] = fasim_scan_tfo_profile(engines[(size_t)d], qp.data(), ql.data(), nq, dna.data(), off.data(), len.data(), nrec, first, count, &p, 0,
+				no_res ? nullptr : part[(size_t)d].data(), fpart[(size_t)d].data(), nullptr);
+		else if (!with_track && !with_peaks)
 			rc[(size_t)d] = fasim_scan_records(engines[(size_t)d], qp.data(), ql.data(), nq, dna.data(), off.data(), len.data(), nrec, first, count, &p,
 				part[(size_t)d].data(), nullptr);
 		else
@@ -320,8 +359,16 @@ static int scan_group(const std::vector<fasim_engine*>& engines, const std::vect
 		for (int d = 0; d < nd; d++) pp[(size_t)d] = ppart[(size_t)d].data();
 		if (fasim_peaks_merge(pp.data(), nd, (int64_t)(nout * 4), peaks.data()) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); bad = 1; }
 	}
+	for (int q = 0; q < nq && !bad && profs; q++) {
+		if (nd == 1) { (*profs)[(size_t)q] = fpart[0][(size_t)q]; fpart[0][(size_t)q] = nullptr; continue; }
+		std::vector<const fasim_tfo_profile*> fp((size_t)nd);
+		for (int d = 0; d < nd; d++) fp[(size_t)d] = fpart[(size_t)d][(size_t)q];
+		if (fasim_tfo_profile_merge(fp.data(), nd, &(*profs)[(size_t)q]) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); bad = 1; }
+	}
+	for (auto& v : fpart) for (fasim_tfo_profile* x : v) fasim_tfo_profile_free(x);
 	for (auto& v : part) for (fasim_result* x : v) fasim_result_free(x);
 	for (auto& v : tpart) for (fasim_track* x : v) fasim_track_free(x);
+	if (bad && profs) for (fasim_tfo_profile*& x : *profs) { fasim_tfo_profile_free(x); x = nullptr; }
 	if (bad) {
 		for (auto& v : out) for (fasim_result*& x : v) { fasim_result_free(x); x = nullptr; }
 		for (auto& v : tracks) for (fasim_track*& x : v) { fasim_track_free(x); x = nullptr; }
@@ -373,7 +420,8 @@ int main(int argc, char* const* argv)
 		{ "devices", required_argument, NULL, 1004 }, { "accumulate-records", no_argument, NULL, 1005 }, { "upper", no_argument, NULL, 1006 },
 		{ "clamp-cluster", no_argument, NULL, 1007 }, { "regions", required_argument, NULL, 1008 },
 		{ "track", required_argument, NULL, 1009 }, { "track-min", required_argument, NULL, 1010 }, { "track-only", no_argument, NULL, 1011 },
-		{ "screen", no_argument, NULL, 1012 }, { "screen-only", no_argument, NULL, 1013 }, { 0, 0, 0, 0 } };
+		{ "screen", no_argument, NULL, 1012 }, { "screen-only", no_argument, NULL, 1013 },
+		{ "tfo-profile", no_argument, NULL, 1014 }, { "tfo-profile-only", no_argument, NULL, 1015 }, { 0, 0, 0, 0 } };
 	int opt;
 	while ((opt = getopt_long_only(argc, argv, optstring, lo, NULL)) != -1) {
 		switch (opt) {
@@ -409,7 +457,9 @@ int main(int argc, char* const* argv)
 		case 1011: trk.only = true; break;
 		case 1012: screen = true; break;
 		case 1013: screen = screen_only = true; break;
-		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only]\n"); return 2;
+		case 1014: trk.tfo = true; break;
+		case 1015: trk.tfo = trk.tfo_only = true; break;
+		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only]\n"); return 2;
 		}
 	}
 	if (all_records && accumulate) { fprintf(stderr, "fasim: --all-records and --accumulate-records exclude each other\n"); return 2; }
@@ -422,7 +472,8 @@ int main(int argc, char* const* argv)
 	if (screen && !(regions || all_records)) { fprintf(stderr, "fasim: --screen needs --regions FILE.bed or --all-records\n"); return 2; }
 	if (screen && (accumulate || p.classicSim)) { fprintf(stderr, "fasim: --screen is not available with --accumulate-records or -F\n"); return 2; }
 	if (screen_only && track) { fprintf(stderr, "fasim: --screen-only writes the screen table only: not with --track\n"); return 2; }
-	trk.peaks = screen; trk.no_stage3 = screen_only || trk.only;
+	if (trk.tfo && (p.classicSim || accumulate || track || screen)) { fprintf(stderr, "fasim: --tfo-profile is not available with -F, --accumulate-records, --track or --screen\n"); return 2; }
+	trk.peaks = screen; trk.no_stage3 = screen_only || trk.only || trk.tfo_only;
 	// --regions: the BED file is read and checked before anything else happens (a bad file writes nothing)
 	fasim_region* reg = nullptr; int64_t nreg = 0;
 	if (regions && fasim_read_bed(bed_path.c_str(), &reg, &nreg) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 2; }
@@ -480,8 +531,28 @@ int main(int argc, char* const* argv)
 		}
 		return bad;
 	};
+	// --tfo-profile: with --all-records / --regions one whole-set table per lncRNA, the maximum over the groups and records
+	const bool tfo_set = trk.tfo && (all_records || regions);
+	std::vector<fasim_tfo_profile*> tfo_acc(tfo_set ? rnas.size() : 0, nullptr);
+	auto write_tfo = [&](const fasim_tfo_profile* t, const Rna& r, const std::string& path) -> int {
+		// (no unit scanned: a table of zeros)
+		std::vector<uint16_t> zeros(t ? 0 : r.seq.size() + 1, 0);
+		fasim_tfo_profile z; z.m = (int32_t)r.seq.size(); z.units = z.saturated_units = 0;
+		for (int c = 0; c < FASIM_TRACK_CLASSES; c++) z.v[c] = zeros.data();
+		char* text = nullptr; int64_t len = 0;
+		if (fasim_tfo_profile_tsv(t ? t : &z, r.seq.data(), r.name.c_str(), &text, &len) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
+		const int bad = write_file(path, text, len);
+		fasim_free(text);
+		return bad;
+	};
+	auto write_tfo_set = [&]() -> int {
+		int bad = 0;
+		for (size_t q = 0; q < tfo_acc.size(); q++) { bad |= write_tfo(tfo_acc[q], rnas[q], outdir + "/" + rnas[q].name + "-" + base + ".tfoprofile.tsv"); fasim_tfo_profile_free(tfo_acc[q]); tfo_acc[q] = nullptr; }
+		return bad;
+	};
 	if (regions && nreg == 0) {
-		if (!screen_only && write_index()) return 1;
+		if (tfo_set && write_tfo_set()) return 1;
+		if (!screen_only && !trk.tfo_only && write_index()) return 1;
 		if (screen && write_screen()) return 1;
 		std::cout << "finished normally" << std::endl;
 		return 0;
@@ -571,6 +642,7 @@ int main(int argc, char* const* argv)
 				for (size_t q = 0; q < rnas.size(); q++) for (int c = 0; c < 4; c++) scr_peaks[q][row * 4 + c] = pk[q][c];
 				if (screen_only) return;
 			}
+			if (trk.tfo_only) return;
 			for (size_t q = 0; q < rnas.size(); q++) {
 				if (stats && res[q]) {
 					const fasim_scan_stats& s = res[q]->stats;
@@ -624,7 +696,9 @@ int main(int argc, char* const* argv)
 			std::vector<std::vector<fasim_result*>> res;
 			std::vector<std::vector<fasim_track*>> gtracks;
 			std::vector<fasim_peak> gpeaks;
-			if (scan_group(engines, rnas, gdna, goff, glen, p, res, trk, gtracks, gpeaks)) return 1;
+			std::vector<fasim_tfo_profile*> gprof;
+			if (scan_group(engines, rnas, gdna, goff, glen, p, res, trk, gtracks, gpeaks, trk.tfo ? &gprof : nullptr)) return 1;
+			for (size_t q = 0; q < gprof.size(); q++) { fasim_tfo_profile* t = gprof[q]; gprof[q] = nullptr; if (tfo_fold(tfo_acc[q], t)) return 1; }
 			const double dt = now_s() - t0;
 			tm.scan += dt;
 			if (stats) fprintf(stderr, "[fasim] group %zu: %zu records, %lld segments, scan %.3f s\n", ngroups, group.size(), (long long)group_nseg, dt);
@@ -663,7 +737,16 @@ int main(int argc, char* const* argv)
 			const double t0 = now_s();
 			std::vector<fasim_result*> res;
 			std::vector<fasim_track*> tracks;
-			if (scan_record(engines, rnas, seq, u.len, p, res, trk, tracks)) return 1;
+			std::vector<fasim_tfo_profile*> prof;
+			if (scan_record(engines, rnas, seq, u.len, p, res, trk, tracks, trk.tfo ? &prof : nullptr)) return 1;
+			for (size_t q = 0; q < prof.size(); q++) {
+				fasim_tfo_profile* t = prof[q]; prof[q] = nullptr;
+				if (tfo_set) { if (tfo_fold(tfo_acc[q], t)) return 1; continue; }
+				// a plain run: <stem>-TFOprofile next to -TFOsorted
+				const int bad = write_tfo(t, rnas[q], outdir + "/" + u.species + "-" + rnas[q].name + "-" + base + "-TFOprofile");
+				fasim_tfo_profile_free(t);
+				if (bad) return 1;
+			}
 			tm.scan += now_s() - t0;
 			total_nt += u.len;
 			emit(u, res, tracks);
@@ -723,8 +806,9 @@ int main(int argc, char* const* argv)
 		tm.tail_wait = now_s() - t_wait;
 		if (g_out_failed) return 1;
 		if (screen && write_screen()) return 1;
+		if (tfo_set && write_tfo_set()) return 1;
 		if (regions) {
-			if (!screen_only && write_index()) return 1;
+			if (!screen_only && !trk.tfo_only && write_index()) return 1;
 			std::vector<std::string> lost;
 			for (const auto& c : todo) for (const auto& j : c.second) {
 				const fasim_region& g = reg[j.second];

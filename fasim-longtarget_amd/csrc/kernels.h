@@ -86,6 +86,9 @@ struct ScanLaunch {
 	// void and the caller runs it again with f16 = 0
 	int32_t f16 = 0;
 	int32_t* unit_ovf = nullptr;
+	// row maxima (fasim_scan_tfo_profile; ignored by the checkpoint variant): non-NULL selects the ROWS variant of the main pass,
+	// which leaves rowmax16[unit][16 * ceil(m/16)] = 2 * (maximum of the row over the unit's real columns) + taint bit
+	uint16_t* rowmax16 = nullptr;
 };
 constexpr int SCAN_UBLK_STEPS = 64;       // pipeline steps per block of maxima
 inline int scan_ublk_blocks(int tstride) { return (tstride + 127 + SCAN_UBLK_STEPS - 1) / SCAN_UBLK_STEPS; }
@@ -127,6 +130,19 @@ struct TrackLaunch {
 	uint8_t* sat;               // [nseg * nenc], zeroed by the caller: 1 = the unit holds a saturated column maximum (16 383)
 };
 hipError_t launch_track(const TrackLaunch& L, hipStream_t st);
+
+// ---- rowfold.hip: per-base profile of the lncRNA folded from the row maxima of a batch -------------------------
+// Group g = segments [gfirst[g], gfirst[g + 1]) of the batch (the run of segments of one record, or the whole batch); the result is
+// out[g][4 classes][rows_total] = maximum over the group's units of the class, taint bit dropped.
+struct RowFoldLaunch {
+	const uint16_t* rowmax16;   // [seg * nenc + k][rows_total], as the ROWS variant of k_scan leaves it
+	const int32_t* gfirst;      // [ngroups + 1]
+	int32_t ngroups, nenc, rows_total;      // rows_total: a multiple of 16
+	TrackTable tab;
+	uint16_t* out;              // [ngroups][4][rows_total]
+	uint8_t* sat;               // [nseg * nenc], zeroed by the caller: 1 = the unit holds a saturated row maximum (16 383)
+};
+hipError_t launch_rowfold(const RowFoldLaunch& L, hipStream_t st);
 
 // ---- align.hip: stage 3 ---------------------------------------------------------------------------
 struct FwdLaunch {

@@ -34,6 +34,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <type_traits>
 #include "kernels.h"
 #include "dp_f16.h"
 
@@ -69,6 +70,10 @@ __device__ __forceinline__ v2u pk_maxu(v2u a, v2u b) { v2u r; asm("v_pk_max_u16 
 // the join with the common path (plain C would let the allocator put the two versions into different registers and
 // pay a v_mov per row in every step)
 __device__ __forceinline__ void or_in_place(int& x, int bits) { asm volatile("v_or_b32 %0, %0, %1" : "+v"(x) : "v"(bits)); }
+
+// acc = max(acc, x) on packed u16 with input and output tied to ONE register (as or_in_place: the running row maxima of the ROWS
+// variant cross the rare hazard branch and two copies of the step body, and must not be copied at any join)
+__device__ __forceinline__ void rowmax_in_place(int& acc, int x) { asm("v_pk_max_u16 %0, %0, %1" : "+v"(acc) : "v"(x)); }
 
 // the same shift with zeros entering virtual lane 0 (bound_ctrl: an out-of-range source lane reads as 0): no register has to
 // be preloaded with the value to inject
@@ -136,6 +141,9 @@ struct ScanArgs {
 	uint16_t* ublk;
 	int32_t ublk_blocks;         // blocks per (unit, tile) in the buffer
 	int32_t* unit_ovf;           // F16 variant: [unit] = 1 when some H left the exact range (>= 2048 as carried): the unit's outputs are void
+	// ROWS variant only (fasim_scan_tfo_profile): [unit][rows_total] row maxima over the unit's real columns, as carried
+	// (2 * value + taint), folded per class by k_rowfold (rowfold.hip)
+	uint16_t* rowmax16;
 };
 
 // rows owned by global virtual lane v (stripe-aligned layout): stripe s = v / vs gets its ceil(m/16) rows spread over
@@ -169,10 +177,19 @@ __device__ __forceinline__ int scan_cell_score(const ScanArgs& a, int t, int v, 
 // range shows a block maximum >= 2048: it is flagged in unit_ovf, its outputs are void, and the host runs it again on the
 // integer kernel.  Everything that leaves the pipe (column maxima, block maxima, snapshots) leaves as the integers of the
 // integer kernel; the hand-over between query tiles carries the f16 bits.
-template <int RP, bool DUMP = false, bool F16 = false>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ? 1 : 4, DUMP ? 2 : 4))) k_scan(ScanArgs a)
+//
+// ROWS (main pass only, fasim_scan_tfo_profile): the wave also keeps the running maximum of every row it
+// owns, RP more packed registers, and stores them to rowmax16[unit][row] at the end of the unit.  Rows are private to a virtual
+// lane, so nothing is handed over between lanes or tiles.  Only real columns count: in the last 127 steps of a unit a half may
+// be working on a drain column >= n (fed with code N), whose diagonal H[i-1][n-1] - 4 can exceed everything row i really holds,
+// so those steps run a second instantiation of the step body that masks such a half out of the accumulation.  The fill steps
+// need nothing (state and values are zero there).  The large RP no longer fit 128 VGPRs: they are built for 3 waves per SIMD.
+constexpr int scan_rows_waves(int RP, bool F16) { return RP >= (F16 ? 18 : 20) ? 3 : 4; }
+template <int RP, bool DUMP = false, bool F16 = false, bool ROWS = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ? 1 : (ROWS ? scan_rows_waves(RP, F16) : 4), DUMP ? 2 : 4))) k_scan(ScanArgs a)
 {
 	static_assert(!(F16 && DUMP), "the checkpoint pass is an integer pass");
+	static_assert(!(ROWS && DUMP), "the checkpoint pass keeps no row maxima");
 	extern __shared__ __align__(16) uint8_t prof[];
 	const int lane = threadIdx.x & 63;
 
@@ -210,6 +227,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 	// the refined test needs F to die inside one stripe (F <= 234 decays by 4 per row)
 	const bool lvl2 = a.seg_len16 >= 96 && !a.coarse;
 	const uint8_t* pl = prof + lane * SCAN_LANE_STRIDE;
+	// ROWS: first row of my two halves (where their row maxima go)
+	int rrow0[2] = { 0, 0 };
+	if constexpr (ROWS) { for (int h = 0; h < 2; h++) { int rows_v; lane_rows(128 * a.tile + 2 * lane + h, a.seg_len16, a.vs, &rrow0[h], &rows_v); } }
 
 	for (;;) {
 		int w = 0;
@@ -245,6 +265,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 		int Es[RP]; int fmbot = 0;
 #pragma unroll
 		for (int r = 0; r < RP; r++) Es[r] = 0;
+		// ROWS only: running maximum of each of my row pairs over the real columns (F16: the bit patterns, which order like the values)
+		int RM[ROWS ? RP : 1];
+#pragma unroll
+		for (int r = 0; r < (ROWS ? RP : 1); r++) RM[r] = 0;
 		// checkpoint columns are ascending and a half's column moves up by one per step: each half only watches its NEXT one
 		int dlast = -1, dnext[2] = { 0x7fffffff, 0x7fffffff }, dnx[2] = { 0, 0 };
 		int drow0[2] = { 0, 0 }, drows[2] = { 0, 0 };
@@ -271,7 +295,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 		// registers the profile rows were loaded into (the old H column is still being read), so consecutive steps
 		// alternate between two register banks; with a single copy of the body the compiler has to move the whole column
 		// back at the end of every step (~16 v_mov_b64 of ~230 instructions).
-		auto do_step = [&](const int step) __attribute__((always_inline)) {
+		// (DRAIN: the ROWS variant's copy of the body for the steps >= n, in which a half may be on a drain column)
+		auto do_step = [&](const int step, auto drain_c) __attribute__((always_inline)) {
+			constexpr bool DRAIN = decltype(drain_c)::value;
+			int rvalid = -1;           // ROWS, DRAIN: 0xFFFF in the halves whose column step - v is a real one (< n)
+			if constexpr (ROWS && DRAIN) { const int c_lo = step - 2 * lane; rvalid = (c_lo < n ? 0xFFFF : 0) | (c_lo - 1 < n ? (int)0xFFFF0000u : 0); }
 			if ((step & 63) == 0) {
 				const int c = step + lane;
 				chunk = c < n ? (int)tc_unit[c] : CODE_N;
@@ -328,6 +356,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 					if (r + 1 < RP) tnext = hf_diag_plus_score(H[r], score_of(r + 1));
 					const int h = hf_h(H[r], t, E[r], ff, tnext);
 					H[r] = h;
+					if constexpr (ROWS) rowmax_in_place(RM[r], DRAIN ? (h & rvalid) : h);
 					const int ho = hf_sub_k(h, KOPEN);
 					E[r] = hf_max_floor(hf_sub_k(E[r], KEXT), ho);
 					const int fnew = hf_max_floor(hf_sub_k(ff, KEXT), ho);
@@ -364,6 +393,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 				// (tnext is passed as an unused operand only to order this after the sum above, which still reads the old H[r])
 				{ int hn; asm("v_pk_max_i16 %0, %2, %3" : "=v"(hn) : "0"(H[r]), "v"(to_int(h)), "v"(to_int(f)), "v"(to_int(tnext))); h = s_from(hn); }
 				H[r] = to_int(h);
+				if constexpr (ROWS) rowmax_in_place(RM[r], DRAIN ? (to_int(h) & rvalid) : to_int(h));
 				const v2u ho = __builtin_elementwise_sub_sat(as_u(h), (v2u){ 2 * GAP_OPEN, 2 * GAP_OPEN });
 				E[r] = to_int(__builtin_elementwise_max(__builtin_elementwise_sub_sat(u_fromi(E[r]), (v2u){ 2 * GAP_EXT, 2 * GAP_EXT }), ho));
 				const v2u fnew = __builtin_elementwise_max(__builtin_elementwise_sub_sat(f, (v2u){ 2 * GAP_EXT, 2 * GAP_EXT }), ho);
@@ -489,6 +519,36 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 			}
 		};
 		int step = DUMP ? item.step0 : 0;
+		if constexpr (ROWS) {
+			// The same loop twice: steps [0, n) only see real (or fill) columns, the rest goes through the masking copy of the body.
+			// (snapshot and block maxima as below, as lambdas: two copies of the loop share them)
+			// pipeline snapshot (every SCAN_SNAP_STEPS steps, all lanes at once: ~50 stores per 1024 steps of ~230 instructions)
+			auto take_snapshot = [&]() __attribute__((always_inline)) {
+				uint32_t* sp = a.snap + ((size_t)unit * a.snap_per_unit + (step / SCAN_SNAP_STEPS - 1)) * (SNAP_DW * 64) + lane;
+				// (F16: the checkpoint pass that reads them is the integer kernel)
+				auto sv = [](int x) -> uint32_t { return (uint32_t)(F16 ? hf_to_u16(x) : x); };
+#pragma unroll
+				for (int r = 0; r < RP; r++) { sp[(2 * r) * 64] = sv(H[r]); sp[(2 * r + 1) * 64] = sv(E[r]); }
+				sp[(2 * RP) * 64] = (uint32_t)tc; sp[(2 * RP + 1) * 64] = sv(hbot); sp[(2 * RP + 2) * 64] = sv(fbot); sp[(2 * RP + 3) * 64] = sv(cm);
+				sp[(2 * RP + 4) * 64] = sv(recv_h_last); sp[(2 * RP + 5) * 64] = (uint32_t)fpo;
+			};
+			// (steps come in pairs: a block of SCAN_UBLK_STEPS steps ends after an odd step)
+			auto close_block = [&]() __attribute__((always_inline)) {
+				if (F16) ovf |= __builtin_amdgcn_ballot_w64(ubacc[0] >= F16_2048 || ubacc[1] >= F16_2048) != 0ull;
+				if (a.ublk) a.ublk[(((size_t)unit * a.ntiles + a.tile) * a.ublk_blocks + (step / SCAN_UBLK_STEPS)) * 64 + lane] = ublk_pack(F16 ? u_fromi(hf_to_u16(to_int(ubacc))) : ubacc);
+				ubacc = (v2u){ 0, 0 };
+			};
+#define FASIM_SCAN_STEPS(LIMIT, DRAIN_C) \
+			for (; step + 1 < (LIMIT); step += 2) { \
+				if (a.snap && step != 0 && (step & (SCAN_SNAP_STEPS - 1)) == 0 && step / SCAN_SNAP_STEPS <= a.snap_per_unit) take_snapshot(); \
+				do_step(step, DRAIN_C); do_step(step + 1, DRAIN_C); \
+				if (((step + 1) & (SCAN_UBLK_STEPS - 1)) == SCAN_UBLK_STEPS - 1) close_block(); \
+			}
+			FASIM_SCAN_STEPS(n, std::false_type{})
+			FASIM_SCAN_STEPS(nsteps, std::true_type{})
+#undef FASIM_SCAN_STEPS
+			if (step < nsteps) do_step(step, std::true_type{});
+		} else {
 		for (; step + 1 < nsteps; step += 2) {
 			if constexpr (!DUMP) {
 				// pipeline snapshot (every SCAN_SNAP_STEPS steps, all lanes at once: ~50 stores per 1024 steps of ~230 instructions)
@@ -502,7 +562,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 					sp[(2 * RP + 4) * 64] = sv(recv_h_last); sp[(2 * RP + 5) * 64] = (uint32_t)fpo;
 				}
 			}
-			do_step(step); do_step(step + 1);
+			do_step(step, std::false_type{}); do_step(step + 1, std::false_type{});
 			if constexpr (!DUMP) {
 				// (steps come in pairs: a block of SCAN_UBLK_STEPS steps ends after an odd step)
 				if (((step + 1) & (SCAN_UBLK_STEPS - 1)) == SCAN_UBLK_STEPS - 1) {
@@ -512,7 +572,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 				}
 			}
 		}
-		if (step < nsteps) do_step(step);
+		if (step < nsteps) do_step(step, std::false_type{});
+		}
 		if constexpr (!DUMP) {
 			// the last, partial block (nsteps - 1 is its last step unless the block was just closed)
 			if (a.ublk && (nsteps & (SCAN_UBLK_STEPS - 1)) != 0) a.ublk[(((size_t)unit * a.ntiles + a.tile) * a.ublk_blocks + ((nsteps - 1) / SCAN_UBLK_STEPS)) * 64 + lane] = ublk_pack(F16 ? u_fromi(hf_to_u16(to_int(ubacc))) : ubacc);
@@ -521,6 +582,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 			// (a block that was just closed left ubacc = 0)
 			ovf |= __builtin_amdgcn_ballot_w64(ubacc[0] >= F16_2048 || ubacc[1] >= F16_2048) != 0ull;
 			if (ovf && lane == 0) a.unit_ovf[unit] = 1;
+		}
+		if constexpr (ROWS) {
+			// every row [0, rows_total) belongs to exactly one half (row0 + rows <= rows_total: lane_rows), which owns RP or RP - 1
+			// rows: the transparent last register row of a half that owns RP - 1 (act == 0) is not stored
+			uint16_t* rp = a.rowmax16 + (size_t)unit * a.rows_total;
+#pragma unroll
+			for (int r = 0; r < RP; r++) {
+				const uint32_t x = (uint32_t)(F16 ? hf_to_u16(RM[r]) : RM[r]);
+				if (r < RP - 1 || (act & 0xFFFFu)) rp[rrow0[0] + r] = (uint16_t)x;
+				if (r < RP - 1 || (act >> 16)) rp[rrow0[1] + r] = (uint16_t)(x >> 16);
+			}
 		}
 		if (a.unit_hz && __builtin_amdgcn_ballot_w64(to_int(hzacc) != 0) != 0ull && lane == 0) atomicOr(a.unit_hz + unit, 1);
 		if (!DUMP && a.unit_first && first_enter != 0x7fffffff && lane == 0) atomicMin(a.unit_first + unit, first_enter);
@@ -537,7 +609,7 @@ static hipError_t launch_scan_dump_t(const ScanArgs& a, hipStream_t st)
 	return hipGetLastError();
 }
 
-template <int RP, bool F16>
+template <int RP, bool F16, bool ROWS>
 static hipError_t launch_scan_t(const ScanArgs& a, hipStream_t st)
 {
 	hipError_t err = hipMemsetAsync(a.counter, 0, sizeof(uint32_t), st);
@@ -547,7 +619,7 @@ static hipError_t launch_scan_t(const ScanArgs& a, hipStream_t st)
 	// for this kernel to drain.
 	constexpr int WPB = 4, PER_WAVE = 2;                 // waves per workgroup, units per wave
 	const long blocks = ((long)a.nwork + WPB * PER_WAVE - 1) / (WPB * PER_WAVE);
-	hipLaunchKernelGGL((k_scan<RP, false, F16>), dim3((unsigned)blocks), dim3(256), (size_t)5 * SCAN_CODE_STRIDE, st, a);
+	hipLaunchKernelGGL((k_scan<RP, false, F16, ROWS>), dim3((unsigned)blocks), dim3(256), (size_t)5 * SCAN_CODE_STRIDE, st, a);
 	return hipGetLastError();
 }
 
@@ -574,6 +646,8 @@ hipError_t launch_scan(const ScanLaunch& L, hipStream_t st)
 	const bool f16 = L.f16 && !L.dump_items;
 	if (f16 && !L.unit_ovf) return hipErrorInvalidValue;
 	a.unit_ovf = L.unit_ovf;
+	a.rowmax16 = L.dump_items ? nullptr : L.rowmax16;
+	const bool rows = a.rowmax16 != nullptr;
 	if (a.ntiles > 1 && !a.boundary) return hipErrorInvalidValue;
 	// RP must be exactly ceil(segLen/vs): every virtual lane then owns RP or RP-1 rows.  One launch per tile of 128
 	// virtual lanes (long queries): tile t reads the bottom row tile t-1 left in `boundary` and overwrites it in place.
@@ -582,7 +656,7 @@ hipError_t launch_scan(const ScanLaunch& L, hipStream_t st)
 		a.tile = t;
 		hipError_t err = hipErrorInvalidValue;
 		switch (rp) {
-#define FASIM_SCAN_CASE(N) case N: err = L.dump_items ? launch_scan_dump_t<N>(a, st) : (f16 ? launch_scan_t<N, true>(a, st) : launch_scan_t<N, false>(a, st)); break;
+#define FASIM_SCAN_CASE(N) case N: err = L.dump_items ? launch_scan_dump_t<N>(a, st) : (rows ? (f16 ? launch_scan_t<N, true, true>(a, st) : launch_scan_t<N, false, true>(a, st)) : (f16 ? launch_scan_t<N, true, false>(a, st) : launch_scan_t<N, false, false>(a, st))); break;
 		FASIM_SCAN_CASE(1) FASIM_SCAN_CASE(2) FASIM_SCAN_CASE(3) FASIM_SCAN_CASE(4) FASIM_SCAN_CASE(5) FASIM_SCAN_CASE(6)
 		FASIM_SCAN_CASE(7) FASIM_SCAN_CASE(8) FASIM_SCAN_CASE(9) FASIM_SCAN_CASE(10) FASIM_SCAN_CASE(11) FASIM_SCAN_CASE(12)
 		FASIM_SCAN_CASE(13) FASIM_SCAN_CASE(14) FASIM_SCAN_CASE(15) FASIM_SCAN_CASE(16) FASIM_SCAN_CASE(17) FASIM_SCAN_CASE(18)

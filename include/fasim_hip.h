@@ -302,6 +302,38 @@ int fasim_scan_records_track(fasim_engine* e, const char* const* rnas, const int
 /* Entry-wise merge of `nparts` arrays of n peaks each (shards, devices): the larger value wins, then the lower pos, then the lower
  * enc.  (0, -1, -1) entries therefore lose against every peak of value >= 1. */
 int fasim_peaks_merge(const fasim_peak* const* parts, int32_t nparts, int64_t n, fasim_peak* out);
+/* ---- per-base profile of the lncRNA (csrc/rowfold.hip) ---------------------------------------------------- */
+/* The other projection of the scan's matrices: for every base of the lncRNA and strand class the best local alignment score that
+ * ends ON THAT BASE, anywhere in the records -- which stretch of the lncRNA is the triplex-forming domain.  v[c][i] = maximum over
+ * the selected units of class c and over their real columns of H[i][j] of section 11 (the textbook values of the potential
+ * tracks: no 80 % threshold, no Q1, no Q2); 0 where no unit contributes.  The query is never reversed: row i is base i for every
+ * encoding.  Saturation at 16 383 as for the tracks.  max_i v[c][i] equals the maximum of the class's potential track. */
+typedef struct fasim_tfo_profile {
+	int32_t m;                                   /* bases of the lncRNA                    */
+	uint16_t* v[FASIM_TRACK_CLASSES];            /* m values each                          */
+	int64_t units, saturated_units;
+} fasim_tfo_profile;
+/* fasim_scan_records with the profile: arguments, record cutting, global segment numbering and the refusals of fasim_scan_records,
+ * plus those of fasim_scan_track (a query under 113 nt, FASIM_SCAN_V1=1, classicSim: FASIM_E_UNSUPPORTED), all before any GPU work;
+ * the engine stays usable.  per_record == 0: out_profiles[q] is one profile per query over the whole record set; otherwise
+ * out_profiles[q * nrec + r] is the profile of record r, exactly what that record scanned alone gives.  out_results == NULL: no
+ * stage 3 (the work ends after the scan kernel and k_rowfold); otherwise out_results and totals are byte for byte those of
+ * fasim_scan_records.  With a segment range only the selected segments contribute: merge the shards with
+ * fasim_tfo_profile_merge.  The result depends on the records and the parameters only (not on batches, workers, shards, devices or
+ * dp_f16, nor on whether stage 3 ran).  Free each profile with fasim_tfo_profile_free. */
+int  fasim_scan_tfo_profile(fasim_engine* e, const char* const* rnas, const int32_t* rna_lens, int32_t nq,
+                            const char* dna, const int64_t* rec_off, const int64_t* rec_len, int32_t nrec,
+                            int64_t seg_first, int64_t seg_count, const fasim_params* p, int32_t per_record,
+                            fasim_result** out_results /* [nq * nrec] or NULL: no stage 3 */,
+                            fasim_tfo_profile** out_profiles /* [nq] or, per_record, [nq * nrec] */,
+                            fasim_scan_stats* totals /* [nq], may be NULL */);
+/* Element-wise maximum of `nparts` profiles of one lncRNA (shards, devices); units and saturated_units are summed.  Parts whose m
+ * differ, and an empty list, are refused (FASIM_E_ARG).  Free the result with fasim_tfo_profile_free. */
+int  fasim_tfo_profile_merge(const fasim_tfo_profile* const* parts, int32_t nparts, fasim_tfo_profile** out);
+/* The table `fasim --tfo-profile` writes: the header line `pos base ParaPlus ParaMinus AntiMinus AntiPlus`, then one line per base
+ * of `rna` (t->m letters, written as given), all tab-separated, pos 1-based.  rna_name may be NULL.  Free with fasim_free. */
+int  fasim_tfo_profile_tsv(const fasim_tfo_profile* t, const char* rna, const char* rna_name, char** text, int64_t* text_len);
+void fasim_tfo_profile_free(fasim_tfo_profile* t);
 
 /* Host half of the path's one exchange step: concatenates the records of `nparts` shards in the
  * order given and rebases their pool offsets.  Shards are contiguous segment ranges, so rank order IS the
