@@ -112,6 +112,16 @@ class _Peak(C.Structure):
     _fields_ = [("value", C.c_int32), ("enc", C.c_int32), ("pos", C.c_int64)]
 
 
+class _Site(C.Structure):
+    _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("pos", C.c_int64), ("value", C.c_int32), ("enc", C.c_int32),
+                ("cls", C.c_int32), ("reserved", C.c_int32)]
+
+
+class _Sites(C.Structure):
+    _fields_ = [("n", C.c_int64), ("s", C.POINTER(_Site)), ("units", C.c_int64), ("saturated_units", C.c_int64),
+                ("raw_runs", C.c_int64), ("min_value", C.c_int32), ("max_gap", C.c_int32)]
+
+
 TRACK_CLASSES = ("ParaPlus", "ParaMinus", "AntiMinus", "AntiPlus")
 
 EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_ex", "fasim_engine_destroy", "fasim_last_error", "fasim_set_option", "fasim_set_query",
@@ -122,6 +132,7 @@ EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_e
            "fasim_scan_track", "fasim_track_merge", "fasim_track_bedgraph", "fasim_track_free",
            "fasim_scan_records_track", "fasim_peaks_merge", "fasim_screen_tsv",
            "fasim_scan_tfo_profile", "fasim_tfo_profile_merge", "fasim_tfo_profile_tsv", "fasim_tfo_profile_free",
+           "fasim_scan_records_sites", "fasim_sites_merge", "fasim_sites_bed", "fasim_sites_free",
            # the reference's own ssw.h ABI (include/ssw.h)
            "ssw_init", "init_destroy", "ssw_pre_align", "ssw_align", "align_destroy", "encoded_ops"]
 
@@ -217,6 +228,15 @@ def lib():
     L.fasim_tfo_profile_tsv.argtypes = [C.POINTER(_TfoProfile), C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.fasim_tfo_profile_free.argtypes = [C.POINTER(_TfoProfile)]
     L.fasim_tfo_profile_free.restype = None
+    L.fasim_scan_records_sites.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
+                                           C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int64, C.c_int64,
+                                           C.POINTER(Params), C.c_int32, C.c_int32, C.POINTER(C.POINTER(_Result)),
+                                           C.POINTER(C.POINTER(_Sites)), C.POINTER(ScanStats)]
+    L.fasim_sites_merge.argtypes = [C.POINTER(C.POINTER(_Sites)), C.c_int32, C.POINTER(C.POINTER(_Sites))]
+    L.fasim_sites_bed.argtypes = [C.POINTER(_Sites), C.c_char_p, C.c_int64, C.c_char_p, C.c_char_p, C.c_int32,
+                                  C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.fasim_sites_free.argtypes = [C.POINTER(_Sites)]
+    L.fasim_sites_free.restype = None
     _lib = L
     return L
 
@@ -471,6 +491,112 @@ def tfo_profile_tsv(profile: TfoProfile, rna: bytes, rna_name: str = "") -> byte
     rc = L.fasim_tfo_profile_tsv(profile.pointer(), rna, rna_name.encode(), C.byref(text), C.byref(n))
     if rc != 0:
         raise FasimError(f"fasim_tfo_profile_tsv failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
+    try:
+        return C.string_at(text, n.value)
+    finally:
+        L.fasim_free(text)
+
+
+class Sites:
+    """Sites of one record and one lncRNA above a fixed potential (struct fasim_sites): the ranges of positions whose potential
+    in one strand class reaches `min_value`, ranges at most `max_gap` apart joined, each with its peak.  Either a native list
+    (what scan_sites() and merge_sites() return) or one made from an (n, 6) array of (cls, start, end, value, pos, enc) rows:
+    `Sites(rows, min_value, max_gap=0, units=0, saturated_units=0, raw_runs=0)`."""
+
+    def __init__(self, rows=None, min_value: int = 1, max_gap: int = 0, units: int = 0, saturated_units: int = 0, raw_runs: int = 0,
+                 _native=None):
+        self._native = _native
+        self._keep = None
+        if _native is None:
+            import numpy as np
+            a = np.asarray(rows if rows is not None else [], dtype=np.int64).reshape(-1, 6)
+            arr = (_Site * max(1, len(a)))()
+            for i, (c, s, e, v, pos, enc) in enumerate(a.tolist()):
+                arr[i].cls, arr[i].start, arr[i].end, arr[i].value, arr[i].pos, arr[i].enc = c, s, e, v, pos, enc
+            t = _Sites()
+            t.n, t.s = len(a), C.cast(arr, C.POINTER(_Site))
+            t.units, t.saturated_units, t.raw_runs, t.min_value, t.max_gap = units, saturated_units, raw_runs, min_value, max_gap
+            self._keep = (arr, t)
+
+    def __del__(self):
+        try:
+            if self._native is not None:
+                lib().fasim_sites_free(self._native)
+                self._native = None
+        except Exception:
+            pass
+
+    def pointer(self):
+        """POINTER(fasim_sites) for the C-ABI; valid while this object lives."""
+        return self._native if self._native is not None else C.pointer(self._keep[1])
+
+    @property
+    def _t(self):
+        return self._native.contents if self._native is not None else self._keep[1]
+
+    @property
+    def n(self) -> int:
+        return int(self._t.n)
+
+    def __len__(self) -> int:
+        return self.n
+
+    @property
+    def units(self) -> int:
+        return int(self._t.units)
+
+    @property
+    def saturated_units(self) -> int:
+        return int(self._t.saturated_units)
+
+    @property
+    def raw_runs(self) -> int:
+        return int(self._t.raw_runs)
+
+    @property
+    def min_value(self) -> int:
+        return int(self._t.min_value)
+
+    @property
+    def max_gap(self) -> int:
+        return int(self._t.max_gap)
+
+    def array(self):
+        """(n, 6) numpy int64 array (a copy) of (cls, start, end, value, pos, enc), ordered by (start, cls)."""
+        import numpy as np
+        t, n = self._t, self.n
+        out = np.zeros((n, 6), dtype=np.int64)
+        if n:
+            raw = np.frombuffer(C.string_at(t.s, n * C.sizeof(_Site)), dtype=np.dtype(
+                [("start", "<i8"), ("end", "<i8"), ("pos", "<i8"), ("value", "<i4"), ("enc", "<i4"), ("cls", "<i4"), ("reserved", "<i4")]))
+            for k, f in enumerate(("cls", "start", "end", "value", "pos", "enc")):
+                out[:, k] = raw[f]
+        return out
+
+
+def merge_sites(parts) -> Sites:
+    """The site list of one record from those of its shards (fasim_sites_merge): union of the intervals per class, joined by
+    max_gap again; units, saturated_units and raw_runs summed."""
+    L = lib()
+    parts = list(parts)
+    arr = (C.POINTER(_Sites) * max(1, len(parts)))(*[t.pointer() for t in parts])
+    out = C.POINTER(_Sites)()
+    rc = L.fasim_sites_merge(arr, len(parts), C.byref(out))
+    if rc != 0:
+        raise FasimError(f"fasim_sites_merge failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
+    return Sites(_native=out)
+
+
+def sites_bed(sites: Sites, chr_name: str, start_genome: int, rna_name: str, record_name: str | None = None, header: bool = True) -> bytes:
+    """BED bytes of a site list (fasim_sites_bed): chrom, start, end, class, value, strand, peak, rule and, where record_name is
+    given, the record's name; what `fasim --sites V` writes."""
+    L = lib()
+    text = C.c_void_p()
+    n = C.c_int64()
+    rc = L.fasim_sites_bed(sites.pointer(), chr_name.encode(), start_genome, rna_name.encode(),
+                           record_name.encode() if record_name is not None else None, 1 if header else 0, C.byref(text), C.byref(n))
+    if rc != 0:
+        raise FasimError(f"fasim_sites_bed failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
     try:
         return C.string_at(text, n.value)
     finally:
@@ -896,6 +1022,49 @@ class Engine:
         if rnas is None:
             return (res[0] if res else None), prof[0]
         return res, prof
+
+    def scan_sites(self, dnas, params: Params | None = None, min_value: int = 1, max_gap: int = 0, records: bool = True, rnas=None,
+                   seg_first: int = 0, seg_count: int = -1):
+        """Sites above a fixed potential (fasim_scan_records_sites): `(results | None, sites)`.  `dnas`: a list of records, one
+        `bytes` (a set of one record) or None (the record made resident by load_dna()).  rnas None: the engine's query; results is
+        what scan_records() returns (one ScanResult per record) and sites one Sites per record.  rnas given: lists per lncRNA of
+        those.  records False: no stage 3, results is None.  Shards of a segment range merge with merge_sites().  Totals:
+        `self.last_totals`."""
+        p = params or default_params()
+        if isinstance(dnas, (bytes, bytearray)):
+            dnas = [bytes(dnas)]
+        if dnas is None:
+            blob, offs, lens, nrec = None, None, None, 1        # the whole resident buffer: the engine knows its length
+        else:
+            blob = b"".join(dnas)
+            nrec = len(dnas)
+            offs = (C.c_int64 * max(1, nrec))()
+            lens = (C.c_int64 * max(1, nrec))()
+            o = 0
+            for i, d in enumerate(dnas):
+                offs[i], lens[i] = o, len(d)
+                o += len(d)
+        nq = 0 if rnas is None else len(rnas)
+        nqo = max(1, nq)
+        arr = (C.c_char_p * nqo)(*(rnas or []))
+        qlens = (C.c_int32 * nqo)(*[len(r) for r in (rnas or [])])
+        nout = nqo * max(1, nrec)
+        outs = (C.POINTER(_Result) * nout)() if records else None
+        sts = (C.POINTER(_Sites) * nout)()
+        totals = (ScanStats * nqo)()
+        self._check(self._L.fasim_scan_records_sites(self._h, arr, qlens, nq, blob, offs, lens, nrec, seg_first, seg_count, C.byref(p),
+                                                     min_value, max_gap, outs, sts, totals))
+        if nq:
+            self.m = len(rnas[-1])
+        self.last_totals = [self._stats_dict(totals[q]) for q in range(nqo)]
+        res = None
+        if records:
+            res = [[ScanResult(stats=self._stats_dict(outs[q * nrec + r].contents.stats), _native=outs[q * nrec + r])
+                    for r in range(nrec)] for q in range(nqo)]
+        sites = [[Sites(_native=sts[q * nrec + r]) for r in range(nrec)] for q in range(nqo)]
+        if rnas is None:
+            return (res[0] if res else None), sites[0]
+        return res, sites
 
     def _records_track(self, blob, offs, lens, nrec, p, rnas, bin, records, seg_first, seg_count):
         nq = 0 if rnas is None else len(rnas)

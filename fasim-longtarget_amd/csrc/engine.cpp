@@ -97,7 +97,7 @@ void fasim_engine_destroy(fasim_engine* e)
 		&e->unit_first, &e->hz_cols, &e->hz_plan, &e->hz_base, &e->hz_items, &e->snap, &e->hz_state, &e->hz_rows, &e->hz_chunk, &e->hz_src, &e->hz_zero,
 		&e->qsim, &e->sim_min, &e->sim_row, &e->sim_ev, &e->sim_cnt, &e->sim_nodes,
 		&e->ublk, &e->btarget, &e->bidx, &e->bcounts, &e->blist[0], &e->blist[1], &e->blist[2], &e->bslots[0], &e->bslots[1], &e->bslots[2],
-		&e->bprev, &e->lane_ub, &e->fzones, &e->fubslot, &e->bdec, &e->btab, &e->swin, &e->unit_ovf, &e->track, &e->track_phase, &e->track_sat, &e->track_peaks,
+		&e->bprev, &e->lane_ub, &e->fzones, &e->fubslot, &e->bdec, &e->btab, &e->swin, &e->unit_ovf, &e->track, &e->track_phase, &e->track_sat, &e->track_peaks, &e->sites_counts, &e->sites_offsets, &e->sites_runs, &e->sites_sat,
 		&e->rowmax16, &e->row_out, &e->row_gfirst, &e->row_sat };
 	for (auto& t : e->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
 	for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
@@ -516,14 +516,14 @@ void fasim_track_free(fasim_track* t)
 }
 
 // the potential is the column maxima of the systolic scan kernel: no other kernel leaves them
-static int check_track_source(fasim_engine* E, const int32_t* rna_lens, int32_t nq, const fasim_params* pp)
+static int check_track_source(fasim_engine* E, const int32_t* rna_lens, int32_t nq, const fasim_params* pp, const char* what = "potential tracks")
 {
 	for (int q = 0; q < std::max(1, nq); q++) {
 		const int len = nq == 0 ? E->m : rna_lens[q];
-		if (!systolic_fits(len)) return fail(E, FASIM_E_UNSUPPORTED, "potential tracks need a query of at least 113 nt (query %d has %d): shorter queries run on the striped kernels, which keep the reference's 8-bit column maxima only", q, len);
+		if (!systolic_fits(len)) return fail(E, FASIM_E_UNSUPPORTED, "%s need a query of at least 113 nt (query %d has %d): shorter queries run on the striped kernels, which keep the reference's 8-bit column maxima only", what, q, len);
 	}
-	if (E->scan_v1) return fail(E, FASIM_E_UNSUPPORTED, "potential tracks are not available under FASIM_SCAN_V1=1 (the striped kernels keep the reference's 8-bit column maxima only)");
-	if (pp->classicSim) return fail(E, FASIM_E_UNSUPPORTED, "potential tracks are not available with classicSim (-F): that path has no stage-2 column maxima");
+	if (E->scan_v1) return fail(E, FASIM_E_UNSUPPORTED, "%s are not available under FASIM_SCAN_V1=1 (the striped kernels keep the reference's 8-bit column maxima only)", what);
+	if (pp->classicSim) return fail(E, FASIM_E_UNSUPPORTED, "%s are not available with classicSim (-F): that path has no stage-2 column maxima", what);
 	return FASIM_OK;
 }
 
@@ -780,6 +780,141 @@ int fasim_track_bedgraph(const fasim_track* t, const char* chr, int64_t start_ge
 			}
 			b = e;
 		}
+	}
+	return text_out(o, text, text_len);
+}
+
+// ---- sites above a fixed potential -------------------------------------------------------------
+void fasim_sites_free(fasim_sites* t)
+{
+	if (!t) return;
+	free(t->s);
+	free(t);
+}
+
+// Intervals of one record (the kernel's runs, or the sites of shards) -> its sites: per class sorted by start, an interval that
+// starts at most max_gap after the end of what has been united so far joins it (larger value, then smaller pos, then smaller enc);
+// the sites by (start, cls).  Consumes `v`.
+static fasim_sites* sites_build(std::vector<fasim_site>& v, int32_t min_value, int32_t max_gap)
+{
+	std::sort(v.begin(), v.end(), [](const fasim_site& a, const fasim_site& b) {
+		if (a.cls != b.cls) return a.cls < b.cls;
+		if (a.start != b.start) return a.start < b.start;
+		if (a.end != b.end) return a.end < b.end;
+		if (a.value != b.value) return a.value > b.value;
+		if (a.pos != b.pos) return a.pos < b.pos;
+		return a.enc < b.enc;
+	});
+	size_t n = 0;
+	for (size_t i = 0; i < v.size(); i++) {
+		const fasim_site x = v[i];
+		if (n > 0 && v[n - 1].cls == x.cls && x.start - v[n - 1].end <= (int64_t)max_gap) {
+			fasim_site& d = v[n - 1];
+			d.end = std::max(d.end, x.end);
+			if (x.value > d.value || (x.value == d.value && (x.pos < d.pos || (x.pos == d.pos && x.enc < d.enc)))) { d.value = x.value; d.pos = x.pos; d.enc = x.enc; }
+		} else v[n++] = x;
+	}
+	v.resize(n);
+	std::sort(v.begin(), v.end(), [](const fasim_site& a, const fasim_site& b) { return a.start != b.start ? a.start < b.start : a.cls < b.cls; });
+	fasim_sites* t = (fasim_sites*)calloc(1, sizeof(fasim_sites));
+	if (!t) return nullptr;
+	t->s = (fasim_site*)calloc(std::max<size_t>(1, n), sizeof(fasim_site));
+	if (!t->s) { free(t); return nullptr; }
+	t->n = (int64_t)n; t->min_value = min_value; t->max_gap = max_gap;
+	if (n) memcpy(t->s, v.data(), n * sizeof(fasim_site));
+	return t;
+}
+
+int fasim_scan_records_sites(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
+	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
+	int32_t min_value, int32_t max_gap, fasim_result** out_results, fasim_sites** out_sites, fasim_scan_stats* totals)
+{
+	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
+	if (!out_sites) return fail(E, FASIM_E_ARG, "bad arguments");
+	if (min_value < 1 || min_value > 16383) return fail(E, FASIM_E_ARG, "sites: min_value %d lies outside [1, 16383]", min_value);
+	if (max_gap < 0) return fail(E, FASIM_E_ARG, "sites: max_gap %d is negative", max_gap);
+	const int64_t whole_off = 0, whole_len = (int64_t)E->dna_host.size();
+	if (!dna && !rec_off && !rec_len && nrec == 1) {           // the whole resident buffer as one record: the engine knows its length
+		if (whole_len == 0) return fail(E, FASIM_E_ARG, "no resident DNA: call fasim_load_dna first");
+		rec_off = &whole_off; rec_len = &whole_len;
+	}
+	int rc = check_records_args(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, pp);
+	if (rc) return rc;
+	const int nquery = std::max(1, nq);
+	const size_t nout = (size_t)nquery * (size_t)nrec;
+	// the sites are runs of the column maxima of the systolic scan kernel: the refusals are those of the potential tracks
+	rc = check_track_source(E, rna_lens, nq, pp, "sites"); if (rc) return rc;
+	for (size_t o = 0; o < nout; o++) out_sites[o] = nullptr;
+	if (out_results) for (size_t o = 0; o < nout; o++) out_results[o] = nullptr;
+	SitesReq sr;
+	sr.min_value = min_value; sr.max_gap = max_gap; sr.only = out_results == nullptr; sr.nrec = nrec;
+	sr.runs.resize(nout); sr.sat.assign(nout, 0); sr.mu.reset(new std::mutex[(size_t)nquery]);
+	std::vector<fasim_result*> own(out_results ? 0 : nout, nullptr);
+	fasim_result** outs = out_results ? out_results : own.data();
+	rc = scan_records_core(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, outs, totals, nullptr, nullptr, &sr);
+	if (rc) { for (fasim_result* r : own) fasim_result_free(r); return rc; }
+	auto drop = [&]() {
+		for (size_t o = 0; o < nout; o++) { fasim_sites_free(out_sites[o]); out_sites[o] = nullptr; if (out_results) { fasim_result_free(out_results[o]); out_results[o] = nullptr; } }
+		for (fasim_result* r : own) fasim_result_free(r);
+	};
+	try {
+		std::vector<fasim_site> v;
+		for (size_t o = 0; o < nout; o++) {
+			const std::vector<HostRun>& runs = sr.runs[o];
+			v.clear(); v.reserve(runs.size());
+			for (const HostRun& h : runs) { fasim_site x; x.start = h.start; x.end = h.end; x.pos = h.pos; x.value = h.value; x.enc = h.enc; x.cls = h.cls; x.reserved = 0; v.push_back(x); }
+			out_sites[o] = sites_build(v, min_value, max_gap);
+			if (!out_sites[o]) { drop(); return fail(E, FASIM_E_NOMEM, "out of memory"); }
+			out_sites[o]->units = outs[o]->stats.units; out_sites[o]->saturated_units = sr.sat[o]; out_sites[o]->raw_runs = (int64_t)runs.size();
+		}
+	} catch (const std::bad_alloc&) { drop(); return fail(E, FASIM_E_NOMEM, "out of memory"); }
+	for (fasim_result* r : own) fasim_result_free(r);
+	return FASIM_OK;
+}
+
+int fasim_sites_merge(const fasim_sites* const* parts, int32_t nparts, fasim_sites** out)
+{
+	if (!parts || nparts < 1 || !out) return fail(nullptr, FASIM_E_ARG, "bad arguments");
+	*out = nullptr;
+	size_t total = 0;
+	for (int k = 0; k < nparts; k++) {
+		if (!parts[k] || parts[k]->n < 0 || (parts[k]->n > 0 && !parts[k]->s)) return fail(nullptr, FASIM_E_ARG, "bad site list %d", k);
+		if (parts[k]->min_value != parts[0]->min_value || parts[k]->max_gap != parts[0]->max_gap)
+			return fail(nullptr, FASIM_E_ARG, "site list %d has min_value %d and max_gap %d, list 0 has %d and %d: only lists of one threshold and gap merge",
+				k, parts[k]->min_value, parts[k]->max_gap, parts[0]->min_value, parts[0]->max_gap);
+		total += (size_t)parts[k]->n;
+	}
+	fasim_sites* t = nullptr;
+	try {
+		std::vector<fasim_site> v;
+		v.reserve(total);
+		for (int k = 0; k < nparts; k++) v.insert(v.end(), parts[k]->s, parts[k]->s + parts[k]->n);
+		for (fasim_site& x : v) x.reserved = 0;
+		t = sites_build(v, parts[0]->min_value, parts[0]->max_gap);
+	} catch (const std::bad_alloc&) { t = nullptr; }
+	if (!t) return fail(nullptr, FASIM_E_NOMEM, "out of memory");
+	for (int k = 0; k < nparts; k++) { t->units += parts[k]->units; t->saturated_units += parts[k]->saturated_units; t->raw_runs += parts[k]->raw_runs; }
+	*out = t;
+	return FASIM_OK;
+}
+
+int fasim_sites_bed(const fasim_sites* t, const char* chr, int64_t start_genome, const char* rna_name, const char* record_name,
+	int32_t header, char** text, int64_t* text_len)
+{
+	if (!t || !chr || !rna_name || !text || !text_len || t->n < 0 || (t->n > 0 && !t->s)) return fail(nullptr, FASIM_E_ARG, "bad arguments");
+	static const char* const names[FASIM_TRACK_CLASSES] = { "ParaPlus", "ParaMinus", "AntiMinus", "AntiPlus" };
+	const int64_t sg = start_genome - 1;                  // 0-based genome position of the record's first base
+	std::string o;
+	char line[160];
+	if (header) { o += "# fasim sites lncRNA="; o += rna_name; o += " min_value="; o += std::to_string(t->min_value); o += " max_gap="; o += std::to_string(t->max_gap); o += "\n"; }
+	for (int64_t i = 0; i < t->n; i++) {
+		const fasim_site& x = t->s[i];
+		if (x.cls < 0 || x.cls >= FASIM_TRACK_CLASSES || x.enc < 0 || x.enc >= 48) return fail(nullptr, FASIM_E_ARG, "site %lld has class %d and encoding %d", (long long)i, x.cls, x.enc);
+		const int n = snprintf(line, sizeof line, "\t%lld\t%lld\t%s\t%d\t%c\t%lld\t%d", (long long)(sg + x.start), (long long)(sg + x.end), names[x.cls], x.value,
+			(x.cls == 0 || x.cls == 3) ? '+' : '-', (long long)(sg + x.pos), enc_info(x.enc).rule);
+		o += chr; o.append(line, (size_t)n);
+		if (record_name) { o += "\t"; o += record_name; }
+		o += "\n";
 	}
 	return text_out(o, text, text_len);
 }

@@ -133,6 +133,7 @@ struct fasim_engine {
 	DevBuf unit_ovf;                             // [unit] != 0: the f16 k_scan saw a value outside its exact range
 	DevBuf track, track_phase, track_sat;        // fasim_scan_track only: k_track's slices, its per-segment bin phase and saturation flags of the batch
 	DevBuf track_peaks;                          // fasim_scan_records_track only: k_track's peak per slice and class
+	DevBuf sites_counts, sites_offsets, sites_runs, sites_sat;   // fasim_scan_records_sites only: k_sites' run counts per (slice, class), their prefix sum, the runs and saturation flags of the batch
 	DevBuf rowmax16, row_out, row_gfirst, row_sat;   // fasim_scan_tfo_profile only: k_scan's row maxima of the batch, k_rowfold's groups, result and saturation flags
 	int opt_numa = 1;                            // option "numa_affinity": pin the scan's host threads to the GPU's NUMA node (no-op on one node)
 	// HBM-window variant of k_striped (queries whose stripes do not fit the LDS): its scratch, the forcing switch (option
@@ -422,8 +423,30 @@ struct RowFold {
 	std::vector<uint8_t>* sat = nullptr;         // [unit]
 };
 
+// ---- sites above a fixed potential (fasim_scan_records_sites, sites.hip) -------------------------------------------------------------
+// One run as the workers keep it: record positions, the encoding itself
+struct HostRun { int64_t start, end, pos; int32_t value, enc, cls; };
+// One call: per o = query * nrec + record the runs of the record's slices as k_sites cut them, appended by the workers under the
+// query's mutex as soon as a batch's scan phase ends; sorted, united and joined when the call ends (sites_build in fasim_scan_records_sites, engine.cpp)
+struct SitesReq {
+	int min_value = 1, max_gap = 0; bool only = false;      // only: no stage 3, no records
+	int nrec = 1;
+	std::vector<std::vector<HostRun>> runs;      // [o]
+	std::vector<int64_t> sat;                    // [o]: units with a saturated column maximum
+	std::unique_ptr<std::mutex[]> mu;            // [query]
+};
+// One batch, handed to run_scan_v2: where k_sites' result goes
+struct SitesFold {
+	int min_value = 1, nseg = 0, nenc = 0, nchunk = 0; bool only = false;
+	TrackTable tab;
+	std::vector<uint32_t>* counts = nullptr;     // [nseg * nchunk][4]
+	std::vector<SiteRun>* runs = nullptr;        // in (slice, class, position) order
+	std::vector<uint8_t>* sat = nullptr;         // [unit]
+};
+
 struct BatchCtx {
 	UnitBatch B;
+	std::vector<uint32_t> site_counts; std::vector<SiteRun> site_runs; std::vector<uint8_t> site_sat; bool sites_done = false;      // fasim_scan_records_sites: k_sites' runs of this batch
 	std::vector<uint16_t> rowfold; std::vector<uint8_t> row_sat; std::vector<int32_t> row_gfirst;      // fasim_scan_tfo_profile: k_rowfold's groups of this batch
 	bool rows_done = false;
 	std::vector<uint16_t> track; std::vector<uint8_t> track_sat; int track_nchunk = 0;      // fasim_scan_track: k_track's slices of this batch
@@ -454,7 +477,7 @@ int prep_striped_window(fasim_engine* E, StripedMode mode, bool word, StripedLau
 int run_stage1(fasim_engine* E, const UnitBatch& B, std::vector<int>& score, int64_t* word_reruns);
 int run_stage2(fasim_engine* E, const UnitBatch& B);
 int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& unit_needs_stage1, ScanOut& out, fasim_scan_stats* st, const TrackFold* tf = nullptr,
-	const RowFold* rf = nullptr);
+	const RowFold* rf = nullptr, const SitesFold* sf = nullptr);
 int load_raw_targets(fasim_engine* E, const char* targets, const int64_t* offsets, const int32_t* lens, int nprob, bool stage1, UnitBatch& B);
 int need_query(fasim_engine* E);
 int run_align(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb>& W, std::vector<AlignResult>& out, std::vector<uint32_t>& cigars, fasim_scan_stats* stats);
@@ -462,7 +485,7 @@ int run_align_v2(fasim_engine* E, const UnitBatch& B, const std::vector<WindowPr
 int stage3_range(fasim_engine* E, BatchCtx& C, int ua, int ub, fasim_scan_stats& st);
 int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_t* dna_dev, int64_t b0, int64_t b1,
 	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st, const TrackReq* tr = nullptr,
-	const TfoReq* pr = nullptr);
+	const TfoReq* pr = nullptr, const SitesReq* sr = nullptr);
 int sim_forward_units(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, const int32_t* unit_len_dev, const int32_t* unit_len_host,
 	int first, int nunit, const int64_t* mins, std::atomic<int>* ready, std::vector<std::vector<fasim_sim_node>>& lists);
 int sim_resweep_rounds(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, const int32_t* unit_len_dev, const int32_t* unit_len_host,
@@ -476,4 +499,4 @@ TrackTable class_table(const std::vector<int>& encs);
 // buffer); outs[q * nrec + r], totals[q] (may be NULL)
 int scan_records_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
-	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr = nullptr, TfoReq* pr = nullptr);
+	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr = nullptr, TfoReq* pr = nullptr, SitesReq* sr = nullptr);

@@ -270,12 +270,12 @@ TrackTable class_table(const std::vector<int>& encs)
 // host buffer.  The kernels take int32 segment starts relative to the batch's own first byte on the device, so a record set
 // longer than 2^31 nt works as long as one batch's span does.
 int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_t* dna_dev, int64_t b0, int64_t b1,
-	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st, const TrackReq* tr, const TfoReq* pr)
+	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st, const TrackReq* tr, const TfoReq* pr, const SitesReq* sr)
 {
 	int rc = FASIM_OK;
 	const int64_t step = p.cutLength - p.overlapLength;
 	const int nenc = (int)encs.size();
-	C.B = UnitBatch(); C.tstride = tstride; C.nenc = nenc; C.nseg = 0; C.step = step; C.dna = dna; C.p = &p; C.encs = &encs; C.stage3_done = false; C.track_done = false; C.rows_done = false;
+	C.B = UnitBatch(); C.tstride = tstride; C.nenc = nenc; C.nseg = 0; C.step = step; C.dna = dna; C.p = &p; C.encs = &encs; C.stage3_done = false; C.track_done = false; C.rows_done = false; C.sites_done = false;
 	C.per_unit.clear(); C.ucand.clear(); C.ualign.clear();
 	{
 		// segments of this batch that are not skipped by same_seq()
@@ -394,9 +394,15 @@ int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_
 				rf.gfirst.push_back(nseg);
 				rf.out = &C.rowfold; rf.sat = &C.row_sat;
 			}
-			rc = run_scan_v2(E, B, need1, so, &st, tr ? &tf : nullptr, pr ? &rf : nullptr);
+			SitesFold sf;
+			if (sr) {
+				sf.min_value = sr->min_value; sf.only = sr->only; sf.nseg = nseg; sf.nenc = nenc; sf.nchunk = C.track_nchunk = track_chunks(p.cutLength);
+				sf.tab = class_table(encs);
+				sf.counts = &C.site_counts; sf.runs = &C.site_runs; sf.sat = &C.site_sat;
+			}
+			rc = run_scan_v2(E, B, need1, so, &st, tr ? &tf : nullptr, pr ? &rf : nullptr, sr ? &sf : nullptr);
 			if (rc < 0) return rc;
-			if (rc == 0) { hoff.swap(so.hit_off); hcnt.swap(so.hit_cnt); thr.swap(so.thr); hits.swap(so.hits); done_v2 = true; C.track_done = tr != nullptr; C.rows_done = pr != nullptr; C.row_gfirst.swap(rf.gfirst); }
+			if (rc == 0) { C.sites_done = sr != nullptr; hoff.swap(so.hit_off); hcnt.swap(so.hit_cnt); thr.swap(so.thr); hits.swap(so.hits); done_v2 = true; C.track_done = tr != nullptr; C.rows_done = pr != nullptr; C.row_gfirst.swap(rf.gfirst); }
 		}
 		st.t_stage2_s += now_s() - t0;
 		if (!done_v2) {
@@ -514,6 +520,31 @@ static void merge_track(const BatchCtx& C, TrackReq& tr, int q)
 		}
 	}
 	for (size_t u = 0; u < C.track_sat.size(); u++) tr.sat[(size_t)q * (size_t)tr.nrec + (size_t)C.srec[u / (size_t)C.nenc]] += C.track_sat[u];
+}
+
+// fasim_scan_records_sites: the runs of a finished scan phase, rebased from segment to record positions, onto the lists of query q
+// and of every segment's own record
+static void merge_site_runs(const BatchCtx& C, SitesReq& sr, int q)
+{
+	std::lock_guard<std::mutex> g(sr.mu[(size_t)q]);
+	size_t at = 0;
+	for (int s = 0; s < C.nseg; s++) {
+		const size_t o = (size_t)q * (size_t)sr.nrec + (size_t)C.srec[(size_t)s];
+		const int64_t a = C.sidx[(size_t)s] * C.step;
+		std::vector<HostRun>& dst = sr.runs[o];
+		for (int c = 0; c < C.track_nchunk; c++) {
+			for (int cls = 0; cls < 4; cls++) {
+				const uint32_t cnt = C.site_counts[((size_t)s * C.track_nchunk + c) * 4 + cls];
+				for (uint32_t k = 0; k < cnt; k++, at++) {
+					const SiteRun& r = C.site_runs[at];
+					HostRun h;
+					h.start = a + r.start; h.end = a + r.end; h.pos = a + r.pos; h.value = r.value_k & 0xffff; h.enc = (*C.encs)[(size_t)(r.value_k >> 16)]; h.cls = cls;
+					dst.push_back(h);
+				}
+			}
+		}
+	}
+	for (size_t u = 0; u < C.site_sat.size(); u++) sr.sat[(size_t)q * (size_t)sr.nrec + (size_t)C.srec[u / (size_t)C.nenc]] += C.site_sat[u];
 }
 
 // fasim_scan_tfo_profile: the groups of a finished scan phase into the arrays of query q (and of the group's record), by maximum
@@ -669,7 +700,7 @@ static void add_stats(fasim_scan_stats& st, const fasim_scan_stats& x)
 // whole call's stats.  `records` true: outs[q * nrec + r] carries the per-record stats, totals[q] (if given) the call's.
 static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int nrec, bool records, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
-	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr = nullptr, TfoReq* pr = nullptr)
+	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr = nullptr, TfoReq* pr = nullptr, SitesReq* sr = nullptr)
 {
 	const bool resident = (dna == nullptr);
 	if (resident) dna = E->dna_host.data();
@@ -867,7 +898,7 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 					r = fasim_set_query(w, rq.data(), (int)rq.size());
 					if (r && w != E) w->err = std::string("worker set_query failed: ") + w->err;
 				}
-				if (!r) r = scan_batch(w, dna, T, dna_dev, itx.b0, itx.b1, p, encs, tstride, ctx, ist[c], tr, pr);
+				if (!r) r = scan_batch(w, dna, T, dna_dev, itx.b0, itx.b1, p, encs, tstride, ctx, ist[c], tr, pr, sr);
 				if (!r && pr && ctx.B.nunit > 0) {
 					if (!ctx.rows_done) r = fail(w, FASIM_E_UNSUPPORTED, "the lncRNA's profile needs the systolic scan kernel");
 					else { merge_rows(ctx, *pr, itx.q); std::vector<uint16_t>().swap(ctx.rowfold); }
@@ -876,7 +907,14 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 					if (!ctx.track_done) r = fail(w, FASIM_E_UNSUPPORTED, "potential tracks need the systolic scan kernel");
 					else { merge_track(ctx, *tr, itx.q); std::vector<uint16_t>().swap(ctx.track); }
 				}
-				if (!r && ctx.B.nunit > 0 && !ctx.stage3_done && !(tr && tr->only) && !(pr && pr->only)) r = stage3_range(w, ctx, 0, ctx.B.nunit, ist[c]);
+				if (!r && sr && ctx.B.nunit > 0) {
+					if (!ctx.sites_done) r = fail(w, FASIM_E_UNSUPPORTED, "sites need the systolic scan kernel");
+					else {
+						try { merge_site_runs(ctx, *sr, itx.q); } catch (const std::bad_alloc&) { r = fail(w, FASIM_E_NOMEM, "out of memory"); }
+						std::vector<SiteRun>().swap(ctx.site_runs);
+					}
+				}
+				if (!r && ctx.B.nunit > 0 && !ctx.stage3_done && !(tr && tr->only) && !(pr && pr->only) && !(sr && sr->only)) r = stage3_range(w, ctx, 0, ctx.B.nunit, ist[c]);
 				(void)hipStreamSynchronize(w->st);
 				drain_timed(w);
 				for (int k = 0; k < FASIM_KERNEL_FAMILIES; k++) { ist[c].kernel_ms[k] = w->kernel_ms[k]; ist[c].kernel_launches[k] = w->kernel_launches[k]; w->kernel_ms[k] = 0; w->kernel_launches[k] = 0; }
@@ -984,7 +1022,7 @@ int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens,
 
 int scan_records_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
-	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr, TfoReq* pr)
+	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr, TfoReq* pr, SitesReq* sr)
 {
-	return scan_set(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, true, seg_first, seg_count, pp, outs, totals, tr, pr);
+	return scan_set(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, true, seg_first, seg_count, pp, outs, totals, tr, pr, sr);
 }

@@ -261,7 +261,7 @@ int run_hazard_chunked(fasim_engine* E, const UnitBatch& B, const std::vector<in
 
 // returns 1 when the query does not fit the kernel (caller falls back to the striped kernels)
 int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& unit_needs_stage1, ScanOut& out,
-	fasim_scan_stats* st, const TrackFold* tf, const RowFold* rf)
+	fasim_scan_stats* st, const TrackFold* tf, const RowFold* rf, const SitesFold* sf)
 {
 	const int nu = B.nunit;
 	HIPOK(E->colmax16.ensure((size_t)nu * B.tstride * sizeof(uint16_t)));
@@ -402,6 +402,46 @@ int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& un
 		HIPOK(hipMemcpyAsync(tf->sat->data(), E->track_sat.p, (size_t)nu, hipMemcpyDeviceToHost, E->st));
 		if (npeak) { tf->peaks->resize(npeak); HIPOK(hipMemcpyAsync(tf->peaks->data(), E->track_peaks.p, npeak * sizeof(TrackPeak), hipMemcpyDeviceToHost, E->st)); }
 		if (tf->only) { HIPOK(hipStreamSynchronize(E->st)); return FASIM_OK; }      // track only: no hits, no hazard re-run, no stage 3
+	}
+	if (sf) {
+		// sites (fasim_scan_records_sites): the same moment as the tracks, for the same reason.  Two launches of k_sites: the run
+		// counts per (slice, class) come back on this stream, their prefix sum places every slice's runs and sizes the buffer
+		const size_t ncnt = (size_t)sf->nseg * sf->nchunk * 4;
+		if (E->sites_counts.ensure(ncnt * sizeof(uint32_t)) != hipSuccess || E->sites_offsets.ensure(ncnt * sizeof(uint32_t)) != hipSuccess ||
+			E->sites_sat.ensure((size_t)nu) != hipSuccess) {
+			(void)hipGetLastError();
+			return fail(E, FASIM_E_NOMEM, "sites: no device memory for the run counts of %zu slices", ncnt / 4);
+		}
+		HIPOK(hipMemsetAsync(E->sites_counts.p, 0, ncnt * sizeof(uint32_t), E->st));
+		HIPOK(hipMemsetAsync(E->sites_sat.p, 0, (size_t)nu, E->st));
+		SitesLaunch S;
+		S.colmax16 = E->colmax16.as<uint16_t>(); S.seg_len = E->seg_len.as<int32_t>();
+		S.nseg = sf->nseg; S.nenc = sf->nenc; S.tstride = B.tstride; S.nchunk = sf->nchunk; S.min_value = sf->min_value; S.tab = sf->tab;
+		S.counts = E->sites_counts.as<uint32_t>(); S.offsets = nullptr; S.runs = nullptr; S.sat = E->sites_sat.as<uint8_t>();
+		{ TimedScope ts(E, 4); he = launch_sites(S, false, E->st); }
+		if (he != hipSuccess) return fail(E, FASIM_E_HIP, "sites (count) launch failed: %s", hipGetErrorString(he));
+		std::vector<uint32_t> offs;
+		try { sf->counts->resize(ncnt); sf->sat->resize((size_t)nu); offs.resize(ncnt); } catch (const std::bad_alloc&) { return fail(E, FASIM_E_NOMEM, "out of memory"); }
+		HIPOK(hipMemcpyAsync(sf->counts->data(), E->sites_counts.p, ncnt * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st));
+		HIPOK(hipMemcpyAsync(sf->sat->data(), E->sites_sat.p, (size_t)nu, hipMemcpyDeviceToHost, E->st));
+		HIPOK(hipStreamSynchronize(E->st));
+		uint64_t total = 0;
+		for (size_t k = 0; k < ncnt; k++) { offs[k] = (uint32_t)total; total += (*sf->counts)[k]; }
+		sf->runs->clear();
+		if (total > 0) {
+			if (total > 0x7fffffffull / sizeof(SiteRun)) return fail(E, FASIM_E_NOMEM, "sites: %llu runs in one batch", (unsigned long long)total);
+			if (E->sites_runs.ensure((size_t)total * sizeof(SiteRun)) != hipSuccess) {
+				(void)hipGetLastError();
+				return fail(E, FASIM_E_NOMEM, "sites: no device memory for %llu runs of a batch", (unsigned long long)total);
+			}
+			try { sf->runs->resize((size_t)total); } catch (const std::bad_alloc&) { return fail(E, FASIM_E_NOMEM, "out of memory"); }
+			rc = upload(E, E->sites_offsets, offs.data(), ncnt * sizeof(uint32_t)); if (rc) return rc;
+			S.offsets = E->sites_offsets.as<uint32_t>(); S.runs = E->sites_runs.as<SiteRun>();
+			{ TimedScope ts(E, 4); he = launch_sites(S, true, E->st); }
+			if (he != hipSuccess) return fail(E, FASIM_E_HIP, "sites (emit) launch failed: %s", hipGetErrorString(he));
+			HIPOK(hipMemcpyAsync(sf->runs->data(), E->sites_runs.p, (size_t)total * sizeof(SiteRun), hipMemcpyDeviceToHost, E->st));
+		}
+		if (sf->only) { HIPOK(hipStreamSynchronize(E->st)); return FASIM_OK; }      // sites only: no hits, no hazard re-run, no stage 3
 	}
 
 	HIPOK(E->hit_off.ensure(sizeof(int32_t) * nu)); HIPOK(E->hit_cnt.ensure(sizeof(int32_t) * nu));

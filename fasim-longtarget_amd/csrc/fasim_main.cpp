@@ -29,6 +29,13 @@
 //                           <stem>-TFOprofile per lncRNA; with --all-records or --regions one whole-set table per lncRNA,
 //                           <O>/<lnc>-<f1 stem>.tfoprofile.tsv.  --tfo-profile-only writes only the table and runs no stage 3.
 //                           Not with -F, --accumulate-records, --track or --screen (exit status 2, nothing written)
+//     --sites V             sites above a fixed potential (fasim_scan_records_sites): the ranges of positions whose
+//                           potential in one strand class reaches V (1 .. 16 383), ranges at most --sites-gap G (default 0) apart joined,
+//                           as BED lines chrom start end class value strand peak rule.  A plain run writes <stem>-TFOsites-<V> next to
+//                           -TFOsorted; with --all-records or --regions one file per lncRNA, <O>/<lnc>-<f1 stem>.sites-<V>.bed, the
+//                           records' sites in record / BED order with the record's name as a ninth column.  --sites-only writes nothing
+//                           else and runs no stage 3.  Exit status 2, nothing written: V outside [1, 16383], a negative G, --sites-gap or
+//                           --sites-only without --sites, --sites with -F, --accumulate-records, --track, --screen or --tfo-profile
 //     --screen              with --regions or --all-records: one table per lncRNA, <O>/<lnc>-<f1 stem>.screen.tsv, one line per
 //                           interval (BED order) or record: per strand class the peak of its potential, where it lies (0-based
 //                           genome coordinate) and the rule of the encoding that attains it (fasim_screen_tsv, DESIGN.md section
@@ -46,6 +53,7 @@
 #include <getopt.h>
 
 #include <algorithm>
+#include <cerrno>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -141,6 +149,16 @@ static bool read_rnas(const std::string& path, std::vector<Rna>& out)
 	return !out.empty();
 }
 
+// the whole of `s` as a decimal int; `bad` (a value the caller refuses) where it is empty, has trailing characters or does not fit
+static int strict_int(const char* s, int bad)
+{
+	char* end = nullptr;
+	errno = 0;
+	const long v = strtol(s, &end, 10);
+	if (end == s || *end != '\0' || errno == ERANGE || v < -2147483647L - 1 || v > 2147483647L) return bad;
+	return (int)v;
+}
+
 // "0-7", "0,1,2", "0,0,0"
 static std::vector<int> parse_devices(const char* s)
 {
@@ -197,7 +215,8 @@ static int g_out_failed = 0;
 
 // --track: bin width (0: no tracks), smallest value written, --track-only; --screen / --screen-only: peaks (no_stage3: no records)
 // --tfo-profile / --tfo-profile-only: the lncRNA's profile (never together with tracks or peaks)
-struct TrackOpt { int bin = 0, min_value = 1; bool only = false, peaks = false, no_stage3 = false, tfo = false, tfo_only = false; };
+// --sites V / --sites-gap G / --sites-only: the sites above a fixed potential (never together with tracks, peaks or the profile)
+struct TrackOpt { int bin = 0, min_value = 1; bool only = false, peaks = false, no_stage3 = false, tfo = false, tfo_only = false; int sites = 0, sites_gap = 0; bool sites_only = false; };
 
 // acc = max(acc, part) by fasim_tfo_profile_merge; takes `part` over
 static int tfo_fold(fasim_tfo_profile*& acc, fasim_tfo_profile* part)
@@ -290,7 +309,8 @@ static int scan_record(const std::vector<fasim_engine*>& engines, const std::vec
 // the group's global segment list and every record's parts are merged in device order.
 static int scan_group(const std::vector<fasim_engine*>& engines, const std::vector<Rna>& rnas, const std::string& dna,
 	const std::vector<int64_t>& off, const std::vector<int64_t>& len, const fasim_params& p, std::vector<std::vector<fasim_result*>>& out,
-	const TrackOpt& trk, std::vector<std::vector<fasim_track*>>& tracks, std::vector<fasim_peak>& peaks, std::vector<fasim_tfo_profile*>* profs = nullptr)
+	const TrackOpt& trk, std::vector<std::vector<fasim_track*>>& tracks, std::vector<fasim_peak>& peaks, std::vector<fasim_tfo_profile*>* profs = nullptr,
+	std::vector<std::vector<fasim_sites*>>* sites = nullptr)
 {
 	const int nd = (int)engines.size(), nq = (int)rnas.size(), nrec = (int)off.size();
 	std::vector<const char*> qp((size_t)nq); std::vector<int32_t> ql((size_t)nq);
@@ -308,11 +328,17 @@ static int scan_group(const std::vector<fasim_engine*>& engines, const std::vect
 	// --tfo-profile: one profile per lncRNA over the whole group
 	std::vector<std::vector<fasim_tfo_profile*>> fpart((size_t)nd, std::vector<fasim_tfo_profile*>(profs ? (size_t)nq : 0, nullptr));
 	if (profs) profs->assign((size_t)nq, nullptr);
+	// --sites: one list per lncRNA and record
+	std::vector<std::vector<fasim_sites*>> spart((size_t)nd, std::vector<fasim_sites*>(sites ? nout : 0, nullptr));
+	if (sites) sites->assign((size_t)nq, std::vector<fasim_sites*>((size_t)nrec, nullptr));
 	std::vector<int> rc((size_t)nd, 0);
 	auto run = [&](int d) {
 		const int64_t base = nseg / nd, rem = nseg % nd;
 		const int64_t first = d * base + std::min<int64_t>(d, rem), count = base + (d < rem ? 1 : 0);
-		if (profs)
+		if (sites)
+			rc[(size_t)d] = fasim_scan_records_sites(engines[(size_t)d], qp.data(), ql.data(), nq, dna.data(), off.data(), len.data(), nrec, first, count, &p,
+				trk.sites, trk.sites_gap, no_res ? nullptr : part[(size_t)d].data(), spart[(size_t)d].data(), nullptr);
+		else if (profs)
 			rc[(size_t)d] = fasim_scan_tfo_profile(engines[(size_t)d], qp.data(), ql.data(), nq, dna.data(), off.data(), len.data(), nrec, first, count, &p, 0,
 				no_res ? nullptr : part[(size_t)d].data(), fpart[(size_t)d].data(), nullptr);
 		else if (!with_track && !with_peaks)
@@ -365,6 +391,16 @@ static int scan_group(const std::vector<fasim_engine*>& engines, const std::vect
 		for (int d = 0; d < nd; d++) fp[(size_t)d] = fpart[(size_t)d][(size_t)q];
 		if (fasim_tfo_profile_merge(fp.data(), nd, &(*profs)[(size_t)q]) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); bad = 1; }
 	}
+	// site lists of the device shards: union of the intervals, joined again
+	for (int q = 0; q < nq && !bad && sites; q++) for (int r = 0; r < nrec && !bad; r++) {
+		const size_t k = (size_t)q * nrec + r;
+		if (nd == 1) { (*sites)[(size_t)q][(size_t)r] = spart[0][k]; spart[0][k] = nullptr; continue; }
+		std::vector<const fasim_sites*> sp((size_t)nd);
+		for (int d = 0; d < nd; d++) sp[(size_t)d] = spart[(size_t)d][k];
+		if (fasim_sites_merge(sp.data(), nd, &(*sites)[(size_t)q][(size_t)r]) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); bad = 1; }
+	}
+	for (auto& v : spart) for (fasim_sites* x : v) fasim_sites_free(x);
+	if (bad && sites) for (auto& v : *sites) for (fasim_sites*& x : v) { fasim_sites_free(x); x = nullptr; }
 	for (auto& v : fpart) for (fasim_tfo_profile* x : v) fasim_tfo_profile_free(x);
 	for (auto& v : part) for (fasim_result* x : v) fasim_result_free(x);
 	for (auto& v : tpart) for (fasim_track* x : v) fasim_track_free(x);
@@ -409,6 +445,7 @@ int main(int argc, char* const* argv)
 	std::string f1 = "./", f2 = "./", outdir = "./", bed_path;
 	std::vector<int> devices(1, 0);
 	bool stats = false, all_records = false, accumulate = false, upper = false, track = false, screen = false, screen_only = false;
+	bool sites = false, sites_gap_given = false;
 	TrackOpt trk;
 	int tail_flags = 0;
 	const char* optstring = "f:s:r:O:c:m:t:i:S:z:Y:Z:h:C:D:E:o:y:Fd";
@@ -421,7 +458,8 @@ int main(int argc, char* const* argv)
 		{ "clamp-cluster", no_argument, NULL, 1007 }, { "regions", required_argument, NULL, 1008 },
 		{ "track", required_argument, NULL, 1009 }, { "track-min", required_argument, NULL, 1010 }, { "track-only", no_argument, NULL, 1011 },
 		{ "screen", no_argument, NULL, 1012 }, { "screen-only", no_argument, NULL, 1013 },
-		{ "tfo-profile", no_argument, NULL, 1014 }, { "tfo-profile-only", no_argument, NULL, 1015 }, { 0, 0, 0, 0 } };
+		{ "tfo-profile", no_argument, NULL, 1014 }, { "tfo-profile-only", no_argument, NULL, 1015 },
+		{ "sites", required_argument, NULL, 1016 }, { "sites-gap", required_argument, NULL, 1017 }, { "sites-only", no_argument, NULL, 1018 }, { 0, 0, 0, 0 } };
 	int opt;
 	while ((opt = getopt_long_only(argc, argv, optstring, lo, NULL)) != -1) {
 		switch (opt) {
@@ -459,7 +497,10 @@ int main(int argc, char* const* argv)
 		case 1013: screen = screen_only = true; break;
 		case 1014: trk.tfo = true; break;
 		case 1015: trk.tfo = trk.tfo_only = true; break;
-		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only]\n"); return 2;
+		case 1016: sites = true; trk.sites = strict_int(optarg, 0); break;           // (0 and -1: refused below as out of range)
+		case 1017: sites_gap_given = true; trk.sites_gap = strict_int(optarg, -1); break;
+		case 1018: trk.sites_only = true; break;
+		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only]]\n"); return 2;
 		}
 	}
 	if (all_records && accumulate) { fprintf(stderr, "fasim: --all-records and --accumulate-records exclude each other\n"); return 2; }
@@ -473,7 +514,12 @@ int main(int argc, char* const* argv)
 	if (screen && (accumulate || p.classicSim)) { fprintf(stderr, "fasim: --screen is not available with --accumulate-records or -F\n"); return 2; }
 	if (screen_only && track) { fprintf(stderr, "fasim: --screen-only writes the screen table only: not with --track\n"); return 2; }
 	if (trk.tfo && (p.classicSim || accumulate || track || screen)) { fprintf(stderr, "fasim: --tfo-profile is not available with -F, --accumulate-records, --track or --screen\n"); return 2; }
-	trk.peaks = screen; trk.no_stage3 = screen_only || trk.only || trk.tfo_only;
+	if ((sites_gap_given || trk.sites_only) && !sites) { fprintf(stderr, "fasim: --sites-gap and --sites-only need --sites V\n"); return 2; }
+	if (sites && (trk.sites < 1 || trk.sites > 16383)) { fprintf(stderr, "fasim: --sites needs an integer in [1, 16383]\n"); return 2; }
+	if (sites && trk.sites_gap < 0) { fprintf(stderr, "fasim: --sites-gap needs an integer of at least 0\n"); return 2; }
+	if (sites && (p.classicSim || accumulate || track || screen || trk.tfo)) { fprintf(stderr, "fasim: --sites is not available with -F, --accumulate-records, --track, --screen or --tfo-profile\n"); return 2; }
+	if (!sites) trk.sites = 0;
+	trk.peaks = screen; trk.no_stage3 = screen_only || trk.only || trk.tfo_only || trk.sites_only;
 	// --regions: the BED file is read and checked before anything else happens (a bad file writes nothing)
 	fasim_region* reg = nullptr; int64_t nreg = 0;
 	if (regions && fasim_read_bed(bed_path.c_str(), &reg, &nreg) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 2; }
@@ -550,9 +596,27 @@ int main(int argc, char* const* argv)
 		for (size_t q = 0; q < tfo_acc.size(); q++) { bad |= write_tfo(tfo_acc[q], rnas[q], outdir + "/" + rnas[q].name + "-" + base + ".tfoprofile.tsv"); fasim_tfo_profile_free(tfo_acc[q]); tfo_acc[q] = nullptr; }
 		return bad;
 	};
+	// --sites: a plain run writes <stem>-TFOsites-<V> per record; with --all-records / --regions one file per lncRNA,
+	// <O>/<lnc>-<f1 stem>.sites-<V>.bed: one header line, then the records' sites in record / BED order, the record's name last
+	const bool sites_set = sites && (all_records || regions);
+	std::vector<std::map<int64_t, std::string>> sites_text(sites_set ? rnas.size() : 0);      // [lncRNA][record number or BED index]
+	auto write_sites_set = [&]() -> int {
+		int bad = 0;
+		for (size_t q = 0; q < sites_text.size(); q++) {
+			fasim_sites none; memset(&none, 0, sizeof none); none.min_value = trk.sites; none.max_gap = trk.sites_gap;
+			char* text = nullptr; int64_t len = 0;
+			if (fasim_sites_bed(&none, "", 1, rnas[q].name.c_str(), nullptr, 1, &text, &len) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
+			std::string t(text, (size_t)len);
+			fasim_free(text);
+			for (const auto& kv : sites_text[q]) t += kv.second;
+			bad |= write_file(outdir + "/" + rnas[q].name + "-" + base + ".sites-" + std::to_string(trk.sites) + ".bed", t.data(), (int64_t)t.size());
+		}
+		return bad;
+	};
 	if (regions && nreg == 0) {
 		if (tfo_set && write_tfo_set()) return 1;
-		if (!screen_only && !trk.tfo_only && write_index()) return 1;
+		if (sites_set && write_sites_set()) return 1;
+		if (!screen_only && !trk.tfo_only && !trk.sites_only && write_index()) return 1;
 		if (screen && write_screen()) return 1;
 		std::cout << "finished normally" << std::endl;
 		return 0;
@@ -622,13 +686,26 @@ int main(int argc, char* const* argv)
 		long group_segs = 5120;
 		if (const char* g = getenv("FASIM_RECORD_GROUP")) group_segs = atol(g);
 		// (--screen always takes the record-set call, a long record or FASIM_RECORD_GROUP=0 as a group of one)
-		const bool grouped = (all_records || regions) && (group_segs > 0 || screen);
+		const bool grouped = (all_records || regions) && (group_segs > 0 || screen || sites);
 		// grouped: the tails of thousands of records go to a pool of host threads instead of four threads in flight
 		std::unique_ptr<TailPool> pool(grouped ? new TailPool(8) : nullptr);
 		// one scanned record: a DNA record, or a BED interval (species = its name, start = its 1-based start; slot = its index)
 		struct Unit { std::string species, chr; long start = 0; int64_t len = 0; size_t recno = 0; int64_t slot = -1; };
 		// per record: --stats lines, output stem, tail + write on a background thread (the next record is read and scanned meanwhile)
-		auto emit = [&](const Unit& r, const std::vector<fasim_result*>& res, const std::vector<fasim_track*>& tracks, const fasim_peak* const* pk = nullptr) {
+		auto emit = [&](const Unit& r, const std::vector<fasim_result*>& res, const std::vector<fasim_track*>& tracks, const fasim_peak* const* pk = nullptr, fasim_sites* const* st = nullptr) {
+			if (sites && st) {
+				// the record's sites: its own file (a plain run), or its lines of the set's file
+				for (size_t q = 0; q < rnas.size(); q++) {
+					char* text = nullptr; int64_t len = 0;
+					if (fasim_sites_bed(st[q], r.chr.c_str(), r.start, rnas[q].name.c_str(), sites_set ? r.species.c_str() : nullptr, sites_set ? 0 : 1, &text, &len) != FASIM_OK) {
+						fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); g_out_failed = 1;
+					} else if (sites_set) sites_text[q][r.slot >= 0 ? r.slot : (int64_t)r.recno].assign(text, (size_t)len);
+					else if (write_file(outdir + "/" + r.species + "-" + rnas[q].name + "-" + base + "-TFOsites-" + std::to_string(trk.sites), text, len)) g_out_failed = 1;
+					fasim_free(text);
+					fasim_sites_free(st[q]);
+				}
+				if (trk.sites_only) return;
+			}
 			if (screen) {
 				// the record's line of the screen tables
 				size_t row = (size_t)r.slot;
@@ -697,7 +774,8 @@ int main(int argc, char* const* argv)
 			std::vector<std::vector<fasim_track*>> gtracks;
 			std::vector<fasim_peak> gpeaks;
 			std::vector<fasim_tfo_profile*> gprof;
-			if (scan_group(engines, rnas, gdna, goff, glen, p, res, trk, gtracks, gpeaks, trk.tfo ? &gprof : nullptr)) return 1;
+			std::vector<std::vector<fasim_sites*>> gsites;
+			if (scan_group(engines, rnas, gdna, goff, glen, p, res, trk, gtracks, gpeaks, trk.tfo ? &gprof : nullptr, sites ? &gsites : nullptr)) return 1;
 			for (size_t q = 0; q < gprof.size(); q++) { fasim_tfo_profile* t = gprof[q]; gprof[q] = nullptr; if (tfo_fold(tfo_acc[q], t)) return 1; }
 			const double dt = now_s() - t0;
 			tm.scan += dt;
@@ -705,11 +783,13 @@ int main(int argc, char* const* argv)
 			std::vector<fasim_result*> one(rnas.size());
 			std::vector<fasim_track*> onet(gtracks.size());
 			std::vector<const fasim_peak*> onep(rnas.size(), nullptr);
+			std::vector<fasim_sites*> ones(gsites.size());
 			for (size_t r = 0; r < group.size(); r++) {
+				for (size_t q = 0; q < gsites.size(); q++) ones[q] = gsites[q][r];
 				for (size_t q = 0; q < rnas.size(); q++) one[q] = res[q][r];
 				for (size_t q = 0; q < gtracks.size(); q++) onet[q] = gtracks[q][r];
 				if (!gpeaks.empty()) for (size_t q = 0; q < rnas.size(); q++) onep[q] = gpeaks.data() + (q * group.size() + r) * 4;
-				emit(group[r], one, onet, gpeaks.empty() ? nullptr : onep.data());
+				emit(group[r], one, onet, gpeaks.empty() ? nullptr : onep.data(), gsites.empty() ? nullptr : ones.data());
 				total_nt += group[r].len;
 			}
 			ngroups++; group.clear(); gdna.clear(); goff.clear(); glen.clear(); group_nseg = 0;
@@ -727,12 +807,18 @@ int main(int argc, char* const* argv)
 					return group_nseg >= group_segs ? flush() : 0;
 				}
 				if (flush()) return 1;
-				if (screen) {
-					// a group of one: only the record-set call gives the peaks
+				if (screen || sites) {
+					// a group of one: only the record-set call gives the peaks / the sites
 					group_nseg = fasim_segment_count(u.len, &p);
 					goff.push_back(0); glen.push_back(u.len); gdna.assign(seq, (size_t)u.len); group.push_back(std::move(u));
 					return flush();
 				}
+			}
+			if (sites) {
+				// a plain run: the record as a set of one (its records are those of fasim_scan_queries)
+				group_nseg = fasim_segment_count(u.len, &p);
+				goff.push_back(0); glen.push_back(u.len); gdna.assign(seq, (size_t)u.len); group.push_back(std::move(u));
+				return flush();
 			}
 			const double t0 = now_s();
 			std::vector<fasim_result*> res;
@@ -807,8 +893,9 @@ int main(int argc, char* const* argv)
 		if (g_out_failed) return 1;
 		if (screen && write_screen()) return 1;
 		if (tfo_set && write_tfo_set()) return 1;
+		if (sites_set && write_sites_set()) return 1;
 		if (regions) {
-			if (!screen_only && !trk.tfo_only && write_index()) return 1;
+			if (!screen_only && !trk.tfo_only && !trk.sites_only && write_index()) return 1;
 			std::vector<std::string> lost;
 			for (const auto& c : todo) for (const auto& j : c.second) {
 				const fasim_region& g = reg[j.second];

@@ -131,6 +131,23 @@ struct TrackLaunch {
 };
 hipError_t launch_track(const TrackLaunch& L, hipStream_t st);
 
+// ---- sites.hip: runs of positions whose potential reaches a fixed value, from the column maxima of a batch ------------------
+// One run of one slice (k_track's slices) and class: positions [start, end) of the SEGMENT, all of potential >= min_value; its largest
+// value, the smallest position that attains it, and the smallest index k (0 .. nenc) of an enabled encoding of the class whose unit
+// attains it there.
+struct alignas(16) SiteRun { int32_t start, end, value_k /* value | k << 16 */, pos; };
+struct SitesLaunch {
+	const uint16_t* colmax16;   // as TrackLaunch
+	const int32_t* seg_len;     // [nseg]
+	int32_t nseg, nenc, tstride, nchunk, min_value;      // 1 <= min_value <= 16 383
+	TrackTable tab;
+	uint32_t* counts;           // [nseg * nchunk][4], zeroed by the caller: runs per slice and class (the counting launch writes it)
+	const uint32_t* offsets;    // [nseg * nchunk][4]: exclusive prefix sum of the counts (the emitting launch reads it)
+	SiteRun* runs;              // [sum of the counts], in (slice, class, position) order (the emitting launch writes it)
+	uint8_t* sat;               // [nseg * nenc], zeroed by the caller: 1 = the unit holds a saturated column maximum (16 383)
+};
+hipError_t launch_sites(const SitesLaunch& L, bool emit, hipStream_t st);
+
 // ---- rowfold.hip: per-base profile of the lncRNA folded from the row maxima of a batch -------------------------
 // Group g = segments [gfirst[g], gfirst[g + 1]) of the batch (the run of segments of one record, or the whole batch); the result is
 // out[g][4 classes][rows_total] = maximum over the group's units of the class, taint bit dropped.

@@ -25,6 +25,9 @@
 //     the maximum among its 8 positions) into one word, the word's maximum is taken over the wave with __shfl_xor and over the four
 //     waves through LDS, and lane 0 of wave c then reads that one column again from the rows of class c (forward and mirrored, at
 //     most 24) for the encoding.  One 16-byte store per (slice, class).  The variant without SLICES (bin == 0) writes nothing else.
+//
+// k_sites (sites.hip) carries a copy of this kernel's front half (the loads, the class maxima, the mirror through LDS, sat[]), kept
+// apart so that the instantiations here compile as before: a change to the loads or to the class table belongs in both files.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"

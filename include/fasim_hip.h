@@ -334,6 +334,50 @@ int  fasim_tfo_profile_merge(const fasim_tfo_profile* const* parts, int32_t npar
  * of `rna` (t->m letters, written as given), all tab-separated, pos 1-based.  rna_name may be NULL.  Free with fasim_free. */
 int  fasim_tfo_profile_tsv(const fasim_tfo_profile* t, const char* rna, const char* rna_name, char** text, int64_t* text_len);
 void fasim_tfo_profile_free(fasim_tfo_profile* t);
+/* ---- sites above a fixed potential (csrc/sites.hip) -------------------------------------------------------- */
+/* Where in the record the potential reaches min_value.  P[c][x] is the bin = 1 track of section 11 of the record scanned alone.  A raw
+ * run of class c is a maximal range [a, b) of positions with P[c][x] >= min_value; a SITE is the union of a maximal chain of raw runs
+ * of one class in which every run starts at most max_gap positions after the end of the one before it.  start / end are 0-based
+ * half-open record positions, value the maximum of P[cls] over [start, end), pos the smallest position that attains it and enc the
+ * peak rule of section 12: the smallest enabled encoding of the class one of whose units covering pos attains value there.  The
+ * sites of a record are ordered by (start, cls).  Unlike the candidate threshold of -TFOsorted (80 % of the unit's own maximum),
+ * min_value is absolute: a site does not depend on what else lies in its segment.  A record and class have no site iff their peak
+ * (fasim_scan_records_track, bin 0) is below min_value; otherwise the site of the largest value, first on ties, carries the peak's
+ * (value, pos, enc). */
+typedef struct fasim_site  { int64_t start, end, pos; int32_t value, enc, cls, reserved; } fasim_site;
+typedef struct fasim_sites {
+	int64_t n; fasim_site* s;                    /* n sites, ordered by (start, cls)                                        */
+	int64_t units, saturated_units;              /* as fasim_track                                                          */
+	int64_t raw_runs;                            /* runs the kernel left for this record (cut at slice and segment edges)   */
+	int32_t min_value, max_gap;
+} fasim_sites;
+/* fasim_scan_records with the sites: arguments, record cutting, global segment numbering and the refusals of
+ * fasim_scan_records_track (one record is the nrec = 1 case, dna == NULL the resident buffer; with dna == NULL and nrec == 1,
+ * rec_off == NULL and rec_len == NULL stand for the whole resident buffer as one record).  In addition min_value < 1,
+ * min_value > 16383, max_gap < 0 or out_sites == NULL give FASIM_E_ARG; a query under 113 nt, FASIM_SCAN_V1=1 or classicSim give
+ * FASIM_E_UNSUPPORTED.  Every refusal happens before any GPU work and leaves the engine usable, as does FASIM_E_NOMEM when the run
+ * buffers cannot be allocated.  out_results == NULL: no stage 3 (the work ends after the scan kernel and k_sites); otherwise
+ * out_results and totals are byte for byte those of fasim_scan_records.  out_sites[q * nrec + r] depends on the record, the query,
+ * the parameters, min_value and max_gap only (not on batches, workers, shards, devices, dp_f16, resident or streamed DNA, nor on
+ * whether stage 3 ran).  With a segment range only the selected segments contribute: merge the shards of a record with
+ * fasim_sites_merge.  Free each with fasim_sites_free. */
+int  fasim_scan_records_sites(fasim_engine* e, const char* const* rnas, const int32_t* rna_lens, int32_t nq,
+                              const char* dna, const int64_t* rec_off, const int64_t* rec_len, int32_t nrec,
+                              int64_t seg_first, int64_t seg_count, const fasim_params* p, int32_t min_value, int32_t max_gap,
+                              fasim_result** out_results /* [nq * nrec] or NULL: no stage 3 */,
+                              fasim_sites** out_sites /* [nq * nrec] */, fasim_scan_stats* totals /* [nq], may be NULL */);
+/* Shards of ONE record: the union of the parts' intervals per class, joined by max_gap again -- the list of the unsharded call.
+ * Where intervals unite the larger value wins, then the smaller pos, then the smaller enc; units, saturated_units and raw_runs are
+ * summed.  Parts whose min_value or max_gap differ, and an empty list, are refused (FASIM_E_ARG). */
+int  fasim_sites_merge(const fasim_sites* const* parts, int32_t nparts, fasim_sites** out);
+/* BED text of a site list.  header != 0: first the line `# fasim sites lncRNA=<rna_name> min_value=<V> max_gap=<G>`.  Then one
+ * tab-separated line per site: chrom, start, end, class name, value, strand (+ for ParaPlus / AntiPlus, - for ParaMinus /
+ * AntiMinus), peak, rule (the Rule column of -TFOsorted for enc), and record_name as a ninth column where it is not NULL.
+ * start, end and peak are 0-based half-open genome coordinates, start_genome - 1 + x, start_genome as in fasim_tfoclass.  Free the
+ * text with fasim_free. */
+int  fasim_sites_bed(const fasim_sites* t, const char* chr, int64_t start_genome, const char* rna_name,
+                     const char* record_name /* NULL: 8 columns */, int32_t header, char** text, int64_t* text_len);
+void fasim_sites_free(fasim_sites* t);
 
 /* Host half of the path's one exchange step: concatenates the records of `nparts` shards in the
  * order given and rebases their pool offsets.  Shards are contiguous segment ranges, so rank order IS the
