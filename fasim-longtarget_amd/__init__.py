@@ -122,6 +122,13 @@ class _Sites(C.Structure):
                 ("raw_runs", C.c_int64), ("min_value", C.c_int32), ("max_gap", C.c_int32)]
 
 
+class _SiteHits(C.Structure):
+    _fields_ = [("n", C.c_int64), ("t", C.POINTER(Triplex)), ("q_begin", C.POINTER(C.c_int32)), ("q_end", C.POINTER(C.c_int32)),
+                ("t_begin", C.POINTER(C.c_int32)), ("t_end", C.POINTER(C.c_int32)), ("cigar_off", C.POINTER(C.c_int64)),
+                ("cigar_len", C.POINTER(C.c_int32)), ("cigar", C.POINTER(C.c_uint32)), ("pool", C.POINTER(C.c_char)),
+                ("pool_len", C.c_int64), ("unaligned", C.c_int64)]
+
+
 TRACK_CLASSES = ("ParaPlus", "ParaMinus", "AntiMinus", "AntiPlus")
 
 EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_ex", "fasim_engine_destroy", "fasim_last_error", "fasim_set_option", "fasim_set_query",
@@ -133,6 +140,7 @@ EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_e
            "fasim_scan_records_track", "fasim_peaks_merge", "fasim_screen_tsv",
            "fasim_scan_tfo_profile", "fasim_tfo_profile_merge", "fasim_tfo_profile_tsv", "fasim_tfo_profile_free",
            "fasim_scan_records_sites", "fasim_sites_merge", "fasim_sites_bed", "fasim_sites_free",
+           "fasim_scan_records_sites_aligned", "fasim_site_hits_merge", "fasim_site_hits_tsv", "fasim_site_hits_free",
            # the reference's own ssw.h ABI (include/ssw.h)
            "ssw_init", "init_destroy", "ssw_pre_align", "ssw_align", "align_destroy", "encoded_ops"]
 
@@ -237,6 +245,16 @@ def lib():
                                   C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.fasim_sites_free.argtypes = [C.POINTER(_Sites)]
     L.fasim_sites_free.restype = None
+    L.fasim_scan_records_sites_aligned.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
+                                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int64, C.c_int64,
+                                                   C.POINTER(Params), C.c_int32, C.c_int32, C.POINTER(C.POINTER(_Result)),
+                                                   C.POINTER(C.POINTER(_Sites)), C.POINTER(C.POINTER(_SiteHits)), C.POINTER(ScanStats)]
+    L.fasim_site_hits_merge.argtypes = [C.POINTER(C.POINTER(_Sites)), C.POINTER(C.POINTER(_SiteHits)), C.c_int32,
+                                        C.POINTER(C.POINTER(_Sites)), C.POINTER(C.POINTER(_SiteHits))]
+    L.fasim_site_hits_tsv.argtypes = [C.POINTER(_Sites), C.POINTER(_SiteHits), C.c_char_p, C.c_int64, C.c_char_p, C.c_char_p, C.c_int32,
+                                      C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.fasim_site_hits_free.argtypes = [C.POINTER(_SiteHits)]
+    L.fasim_site_hits_free.restype = None
     _lib = L
     return L
 
@@ -597,6 +615,107 @@ def sites_bed(sites: Sites, chr_name: str, start_genome: int, rna_name: str, rec
                            record_name.encode() if record_name is not None else None, 1 if header else 0, C.byref(text), C.byref(n))
     if rc != 0:
         raise FasimError(f"fasim_sites_bed failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
+    try:
+        return C.string_at(text, n.value)
+    finally:
+        L.fasim_free(text)
+
+
+class SiteHits:
+    """The hits of the sites of one record and one lncRNA (struct fasim_site_hits): hit k is the alignment behind the peak of site
+    k of the Sites object of the same call.  What scan_sites_aligned() and merge_site_hits() return."""
+
+    def __init__(self, _native, _keep=None):
+        self._native = _native
+        self._keep = _keep               # not None: a structure made by the caller, which the library must not free
+
+    def __del__(self):
+        try:
+            if self._native is not None and self._keep is None:
+                lib().fasim_site_hits_free(self._native)
+                self._native = None
+        except Exception:
+            pass
+
+    def pointer(self):
+        """POINTER(fasim_site_hits) for the C-ABI; valid while this object lives."""
+        return self._native
+
+    @property
+    def _t(self):
+        return self._native.contents
+
+    @property
+    def n(self) -> int:
+        return int(self._t.n)
+
+    def __len__(self) -> int:
+        return self.n
+
+    @property
+    def unaligned(self) -> int:
+        return int(self._t.unaligned)
+
+    def array(self):
+        """(n, 8) numpy int64 array (a copy) of (seg, enc, i0, i1, j0, j1, nt, cigar_len); i0 .. j1 are the unit-relative cells of
+        the hit's first and last pair, cigar_len -1 marks an unaligned hit."""
+        import numpy as np
+        t, n = self._t, self.n
+        out = np.zeros((n, 8), dtype=np.int64)
+        for k in range(n):
+            r = t.t[k]
+            out[k] = (r.seg, r.enc, t.q_begin[k], t.q_end[k], t.t_begin[k], t.t_end[k], r.nt, t.cigar_len[k])
+        return out
+
+    def cigars(self):
+        """One CIGAR string per hit ("40M2I40M"; I = a lncRNA base against a gap, D = a DNA base against a gap), "" when unaligned."""
+        t = self._t
+        out = []
+        for k in range(self.n):
+            n, o = int(t.cigar_len[k]), int(t.cigar_off[k])
+            out.append("".join(f"{t.cigar[o + i] >> 4}{'MID'[t.cigar[o + i] & 15]}" for i in range(max(0, n))))
+        return out
+
+    def triplexes(self):
+        """One dict per hit with the fields of a ScanResult record (stari ... tri_score, seg, enc, tfo, tts)."""
+        t = self._t
+        out = []
+        for k in range(self.n):
+            r = t.t[k]
+            d = {f: getattr(r, f) for f, _ in Triplex._fields_ if f not in ("tfo_off", "tts_off", "genome_shift")}
+            d["tfo"] = C.string_at(C.addressof(t.pool.contents) + r.tfo_off).decode()
+            d["tts"] = C.string_at(C.addressof(t.pool.contents) + r.tts_off).decode()
+            out.append(d)
+        return out
+
+
+def merge_site_hits(sites_parts, hits_parts):
+    """Shards of one record (fasim_site_hits_merge): `(Sites, SiteHits)` of the unsharded call from the shards' site lists and
+    hits.  Where intervals unite, the part whose site wins supplies the hit; on a full tie the hit of the smaller segment."""
+    L = lib()
+    sites_parts, hits_parts = list(sites_parts), list(hits_parts)
+    if len(sites_parts) != len(hits_parts):
+        raise FasimError("merge_site_hits: as many hit lists as site lists are needed", E_ARG)
+    n = len(sites_parts)
+    sa = (C.POINTER(_Sites) * max(1, n))(*[t.pointer() for t in sites_parts])
+    ha = (C.POINTER(_SiteHits) * max(1, n))(*[t.pointer() for t in hits_parts])
+    so, ho = C.POINTER(_Sites)(), C.POINTER(_SiteHits)()
+    rc = L.fasim_site_hits_merge(sa, ha, n, C.byref(so), C.byref(ho))
+    if rc != 0:
+        raise FasimError(f"fasim_site_hits_merge failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
+    return Sites(_native=so), SiteHits(ho)
+
+
+def site_hits_tsv(sites: Sites, hits: SiteHits, chr_name: str, start_genome: int, rna_name: str, record_name: str | None = None,
+                  header: bool = True) -> bytes:
+    """The table of `fasim --sites V --sites-align` (fasim_site_hits_tsv): one line per site with its hit."""
+    L = lib()
+    text = C.c_void_p()
+    n = C.c_int64()
+    rc = L.fasim_site_hits_tsv(sites.pointer(), hits.pointer(), chr_name.encode(), start_genome, rna_name.encode(),
+                               record_name.encode() if record_name is not None else None, 1 if header else 0, C.byref(text), C.byref(n))
+    if rc != 0:
+        raise FasimError(f"fasim_site_hits_tsv failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
     try:
         return C.string_at(text, n.value)
     finally:
@@ -1023,13 +1142,8 @@ class Engine:
             return (res[0] if res else None), prof[0]
         return res, prof
 
-    def scan_sites(self, dnas, params: Params | None = None, min_value: int = 1, max_gap: int = 0, records: bool = True, rnas=None,
-                   seg_first: int = 0, seg_count: int = -1):
-        """Sites above a fixed potential (fasim_scan_records_sites): `(results | None, sites)`.  `dnas`: a list of records, one
-        `bytes` (a set of one record) or None (the record made resident by load_dna()).  rnas None: the engine's query; results is
-        what scan_records() returns (one ScanResult per record) and sites one Sites per record.  rnas given: lists per lncRNA of
-        those.  records False: no stage 3, results is None.  Shards of a segment range merge with merge_sites().  Totals:
-        `self.last_totals`."""
+    def _sites_call(self, aligned, dnas, params, min_value, max_gap, records, rnas, seg_first, seg_count):
+        """Argument marshalling and result wrapping shared by scan_sites() and scan_sites_aligned()."""
         p = params or default_params()
         if isinstance(dnas, (bytes, bytearray)):
             dnas = [bytes(dnas)]
@@ -1052,8 +1166,13 @@ class Engine:
         outs = (C.POINTER(_Result) * nout)() if records else None
         sts = (C.POINTER(_Sites) * nout)()
         totals = (ScanStats * nqo)()
-        self._check(self._L.fasim_scan_records_sites(self._h, arr, qlens, nq, blob, offs, lens, nrec, seg_first, seg_count, C.byref(p),
-                                                     min_value, max_gap, outs, sts, totals))
+        if aligned:
+            hts = (C.POINTER(_SiteHits) * nout)()
+            self._check(self._L.fasim_scan_records_sites_aligned(self._h, arr, qlens, nq, blob, offs, lens, nrec, seg_first, seg_count,
+                                                                 C.byref(p), min_value, max_gap, outs, sts, hts, totals))
+        else:
+            self._check(self._L.fasim_scan_records_sites(self._h, arr, qlens, nq, blob, offs, lens, nrec, seg_first, seg_count, C.byref(p),
+                                                         min_value, max_gap, outs, sts, totals))
         if nq:
             self.m = len(rnas[-1])
         self.last_totals = [self._stats_dict(totals[q]) for q in range(nqo)]
@@ -1061,10 +1180,28 @@ class Engine:
         if records:
             res = [[ScanResult(stats=self._stats_dict(outs[q * nrec + r].contents.stats), _native=outs[q * nrec + r])
                     for r in range(nrec)] for q in range(nqo)]
-        sites = [[Sites(_native=sts[q * nrec + r]) for r in range(nrec)] for q in range(nqo)]
+        out = [res, [[Sites(_native=sts[q * nrec + r]) for r in range(nrec)] for q in range(nqo)]]
+        if aligned:
+            out.append([[SiteHits(hts[q * nrec + r]) for r in range(nrec)] for q in range(nqo)])
         if rnas is None:
-            return (res[0] if res else None), sites[0]
-        return res, sites
+            return tuple([(res[0] if res else None)] + [x[0] for x in out[1:]])
+        return tuple(out)
+
+    def scan_sites(self, dnas, params: Params | None = None, min_value: int = 1, max_gap: int = 0, records: bool = True, rnas=None,
+                   seg_first: int = 0, seg_count: int = -1):
+        """Sites above a fixed potential (fasim_scan_records_sites): `(results | None, sites)`.  `dnas`: a list of records, one
+        `bytes` (a set of one record) or None (the record made resident by load_dna()).  rnas None: the engine's query; results is
+        what scan_records() returns (one ScanResult per record) and sites one Sites per record.  rnas given: lists per lncRNA of
+        those.  records False: no stage 3, results is None.  Shards of a segment range merge with merge_sites().  Totals:
+        `self.last_totals`."""
+        return self._sites_call(False, dnas, params, min_value, max_gap, records, rnas, seg_first, seg_count)
+
+    def scan_sites_aligned(self, dnas, params: Params | None = None, min_value: int = 1, max_gap: int = 0, records: bool = True,
+                           rnas=None, seg_first: int = 0, seg_count: int = -1):
+        """scan_sites() and the hit of every site (fasim_scan_records_sites_aligned): `(results | None, sites, hits)`.  The first
+        two are exactly what scan_sites() returns; hits has the shape of sites, one SiteHits per record (per lncRNA and record
+        with rnas given).  Shards of a segment range merge with merge_site_hits()."""
+        return self._sites_call(True, dnas, params, min_value, max_gap, records, rnas, seg_first, seg_count)
 
     def _records_track(self, blob, offs, lens, nrec, p, rnas, bin, records, seg_first, seg_count):
         nq = 0 if rnas is None else len(rnas)

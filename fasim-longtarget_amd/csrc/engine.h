@@ -134,6 +134,7 @@ struct fasim_engine {
 	DevBuf track, track_phase, track_sat;        // fasim_scan_track only: k_track's slices, its per-segment bin phase and saturation flags of the batch
 	DevBuf track_peaks;                          // fasim_scan_records_track only: k_track's peak per slice and class
 	DevBuf sites_counts, sites_offsets, sites_runs, sites_sat;   // fasim_scan_records_sites only: k_sites' run counts per (slice, class), their prefix sum, the runs and saturation flags of the batch
+	DevBuf sa_q, sa_tcodes, sa_probs, sa_ends, sa_rows, sa_items, sa_dirs, sa_cigar, sa_ciglen;   // fasim_scan_records_sites_aligned only: query codes, the chunk's units, problems, end cells, row state of long queries, path items, direction bytes, CIGARs
 	DevBuf rowmax16, row_out, row_gfirst, row_sat;   // fasim_scan_tfo_profile only: k_scan's row maxima of the batch, k_rowfold's groups, result and saturation flags
 	int opt_numa = 1;                            // option "numa_affinity": pin the scan's host threads to the GPU's NUMA node (no-op on one node)
 	// HBM-window variant of k_striped (queries whose stripes do not fit the LDS): its scratch, the forcing switch (option
@@ -435,6 +436,19 @@ struct SitesReq {
 	std::vector<int64_t> sat;                    // [o]: units with a saturated column maximum
 	std::unique_ptr<std::mutex[]> mu;            // [query]
 };
+// The second phase of fasim_scan_records_sites_aligned (engine_site_align.cpp, site_align.hip): after the call's sites are final,
+// every site of (query q, record r) gets its hit.  The phase runs chunk by chunk on the engine's own stream and buffers (sa_*).
+struct SiteAlignReq {
+	const char* dna = nullptr;                   // host DNA of the call (the caller's buffer or the resident copy)
+	const int64_t* rec_off = nullptr; const int64_t* rec_len = nullptr; int nrec = 1;
+	int64_t seg_first = 0, seg_count = -1;       // the call's range of the global segment list
+	fasim_params p;
+	std::vector<std::string> queries;
+	fasim_sites* const* sites = nullptr;         // [query * nrec + record], final
+	fasim_site_hits** hits = nullptr;            // [query * nrec + record], filled by the phase
+};
+int run_site_align(fasim_engine* E, SiteAlignReq& R);
+void site_hits_free(fasim_site_hits* h);
 // One batch, handed to run_scan_v2: where k_sites' result goes
 struct SitesFold {
 	int min_value = 1, nseg = 0, nenc = 0, nchunk = 0; bool only = false;

@@ -36,6 +36,11 @@
 //                           records' sites in record / BED order with the record's name as a ninth column.  --sites-only writes nothing
 //                           else and runs no stage 3.  Exit status 2, nothing written: V outside [1, 16383], a negative G, --sites-gap or
 //                           --sites-only without --sites, --sites with -F, --accumulate-records, --track, --screen or --tfo-profile
+//     --sites-align         with --sites V: every site with its hit (fasim_scan_records_sites_aligned), the local
+//                           alignment behind the site's peak: beside the sites file <stem>-TFOsites-<V>-aligned (set mode:
+//                           <O>/<lnc>-<f1 stem>.sites-<V>.aligned.tsv, the record's name as a last column), a `# fasim site hits` line,
+//                           a header line, then one line per site in the order of the sites file: chrom tts_start tts_end class value
+//                           strand rule tfo_start tfo_end nt identity stability cigar TFO TTS.  Without --sites: status 2
 //     --screen              with --regions or --all-records: one table per lncRNA, <O>/<lnc>-<f1 stem>.screen.tsv, one line per
 //                           interval (BED order) or record: per strand class the peak of its potential, where it lies (0-based
 //                           genome coordinate) and the rule of the encoding that attains it (fasim_screen_tsv, DESIGN.md section
@@ -216,7 +221,7 @@ static int g_out_failed = 0;
 // --track: bin width (0: no tracks), smallest value written, --track-only; --screen / --screen-only: peaks (no_stage3: no records)
 // --tfo-profile / --tfo-profile-only: the lncRNA's profile (never together with tracks or peaks)
 // --sites V / --sites-gap G / --sites-only: the sites above a fixed potential (never together with tracks, peaks or the profile)
-struct TrackOpt { int bin = 0, min_value = 1; bool only = false, peaks = false, no_stage3 = false, tfo = false, tfo_only = false; int sites = 0, sites_gap = 0; bool sites_only = false; };
+struct TrackOpt { int bin = 0, min_value = 1; bool only = false, peaks = false, no_stage3 = false, tfo = false, tfo_only = false; int sites = 0, sites_gap = 0; bool sites_only = false, sites_align = false; };
 
 // acc = max(acc, part) by fasim_tfo_profile_merge; takes `part` over
 static int tfo_fold(fasim_tfo_profile*& acc, fasim_tfo_profile* part)
@@ -310,7 +315,7 @@ static int scan_record(const std::vector<fasim_engine*>& engines, const std::vec
 static int scan_group(const std::vector<fasim_engine*>& engines, const std::vector<Rna>& rnas, const std::string& dna,
 	const std::vector<int64_t>& off, const std::vector<int64_t>& len, const fasim_params& p, std::vector<std::vector<fasim_result*>>& out,
 	const TrackOpt& trk, std::vector<std::vector<fasim_track*>>& tracks, std::vector<fasim_peak>& peaks, std::vector<fasim_tfo_profile*>* profs = nullptr,
-	std::vector<std::vector<fasim_sites*>>* sites = nullptr)
+	std::vector<std::vector<fasim_sites*>>* sites = nullptr, std::vector<std::vector<fasim_site_hits*>>* hits = nullptr)
 {
 	const int nd = (int)engines.size(), nq = (int)rnas.size(), nrec = (int)off.size();
 	std::vector<const char*> qp((size_t)nq); std::vector<int32_t> ql((size_t)nq);
@@ -331,11 +336,17 @@ static int scan_group(const std::vector<fasim_engine*>& engines, const std::vect
 	// --sites: one list per lncRNA and record
 	std::vector<std::vector<fasim_sites*>> spart((size_t)nd, std::vector<fasim_sites*>(sites ? nout : 0, nullptr));
 	if (sites) sites->assign((size_t)nq, std::vector<fasim_sites*>((size_t)nrec, nullptr));
+	// --sites-align: the hits of those sites
+	std::vector<std::vector<fasim_site_hits*>> hpart((size_t)nd, std::vector<fasim_site_hits*>(sites && hits ? nout : 0, nullptr));
+	if (hits) hits->assign((size_t)nq, std::vector<fasim_site_hits*>((size_t)nrec, nullptr));
 	std::vector<int> rc((size_t)nd, 0);
 	auto run = [&](int d) {
 		const int64_t base = nseg / nd, rem = nseg % nd;
 		const int64_t first = d * base + std::min<int64_t>(d, rem), count = base + (d < rem ? 1 : 0);
-		if (sites)
+		if (sites && hits)
+			rc[(size_t)d] = fasim_scan_records_sites_aligned(engines[(size_t)d], qp.data(), ql.data(), nq, dna.data(), off.data(), len.data(), nrec, first, count, &p,
+				trk.sites, trk.sites_gap, no_res ? nullptr : part[(size_t)d].data(), spart[(size_t)d].data(), hpart[(size_t)d].data(), nullptr);
+		else if (sites)
 			rc[(size_t)d] = fasim_scan_records_sites(engines[(size_t)d], qp.data(), ql.data(), nq, dna.data(), off.data(), len.data(), nrec, first, count, &p,
 				trk.sites, trk.sites_gap, no_res ? nullptr : part[(size_t)d].data(), spart[(size_t)d].data(), nullptr);
 		else if (profs)
@@ -399,6 +410,16 @@ static int scan_group(const std::vector<fasim_engine*>& engines, const std::vect
 		for (int d = 0; d < nd; d++) sp[(size_t)d] = spart[(size_t)d][k];
 		if (fasim_sites_merge(sp.data(), nd, &(*sites)[(size_t)q][(size_t)r]) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); bad = 1; }
 	}
+	// their hits: the part whose site wins supplies the hit
+	for (int q = 0; q < nq && !bad && sites && hits; q++) for (int r = 0; r < nrec && !bad; r++) {
+		const size_t k = (size_t)q * nrec + r;
+		if (nd == 1) { (*hits)[(size_t)q][(size_t)r] = hpart[0][k]; hpart[0][k] = nullptr; continue; }
+		std::vector<const fasim_sites*> sp((size_t)nd); std::vector<const fasim_site_hits*> hp((size_t)nd);
+		for (int d = 0; d < nd; d++) { sp[(size_t)d] = spart[(size_t)d][k]; hp[(size_t)d] = hpart[(size_t)d][k]; }
+		if (fasim_site_hits_merge(sp.data(), hp.data(), nd, nullptr, &(*hits)[(size_t)q][(size_t)r]) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); bad = 1; }
+	}
+	for (auto& v : hpart) for (fasim_site_hits* x : v) fasim_site_hits_free(x);
+	if (bad && hits) for (auto& v : *hits) for (fasim_site_hits*& x : v) { fasim_site_hits_free(x); x = nullptr; }
 	for (auto& v : spart) for (fasim_sites* x : v) fasim_sites_free(x);
 	if (bad && sites) for (auto& v : *sites) for (fasim_sites*& x : v) { fasim_sites_free(x); x = nullptr; }
 	for (auto& v : fpart) for (fasim_tfo_profile* x : v) fasim_tfo_profile_free(x);
@@ -459,7 +480,7 @@ int main(int argc, char* const* argv)
 		{ "track", required_argument, NULL, 1009 }, { "track-min", required_argument, NULL, 1010 }, { "track-only", no_argument, NULL, 1011 },
 		{ "screen", no_argument, NULL, 1012 }, { "screen-only", no_argument, NULL, 1013 },
 		{ "tfo-profile", no_argument, NULL, 1014 }, { "tfo-profile-only", no_argument, NULL, 1015 },
-		{ "sites", required_argument, NULL, 1016 }, { "sites-gap", required_argument, NULL, 1017 }, { "sites-only", no_argument, NULL, 1018 }, { 0, 0, 0, 0 } };
+		{ "sites", required_argument, NULL, 1016 }, { "sites-gap", required_argument, NULL, 1017 }, { "sites-only", no_argument, NULL, 1018 }, { "sites-align", no_argument, NULL, 1019 }, { 0, 0, 0, 0 } };
 	int opt;
 	while ((opt = getopt_long_only(argc, argv, optstring, lo, NULL)) != -1) {
 		switch (opt) {
@@ -500,7 +521,8 @@ int main(int argc, char* const* argv)
 		case 1016: sites = true; trk.sites = strict_int(optarg, 0); break;           // (0 and -1: refused below as out of range)
 		case 1017: sites_gap_given = true; trk.sites_gap = strict_int(optarg, -1); break;
 		case 1018: trk.sites_only = true; break;
-		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only]]\n"); return 2;
+		case 1019: trk.sites_align = true; break;
+		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only] [--sites-align]]\n"); return 2;
 		}
 	}
 	if (all_records && accumulate) { fprintf(stderr, "fasim: --all-records and --accumulate-records exclude each other\n"); return 2; }
@@ -514,7 +536,7 @@ int main(int argc, char* const* argv)
 	if (screen && (accumulate || p.classicSim)) { fprintf(stderr, "fasim: --screen is not available with --accumulate-records or -F\n"); return 2; }
 	if (screen_only && track) { fprintf(stderr, "fasim: --screen-only writes the screen table only: not with --track\n"); return 2; }
 	if (trk.tfo && (p.classicSim || accumulate || track || screen)) { fprintf(stderr, "fasim: --tfo-profile is not available with -F, --accumulate-records, --track or --screen\n"); return 2; }
-	if ((sites_gap_given || trk.sites_only) && !sites) { fprintf(stderr, "fasim: --sites-gap and --sites-only need --sites V\n"); return 2; }
+	if ((sites_gap_given || trk.sites_only || trk.sites_align) && !sites) { fprintf(stderr, "fasim: --sites-gap, --sites-only and --sites-align need --sites V\n"); return 2; }
 	if (sites && (trk.sites < 1 || trk.sites > 16383)) { fprintf(stderr, "fasim: --sites needs an integer in [1, 16383]\n"); return 2; }
 	if (sites && trk.sites_gap < 0) { fprintf(stderr, "fasim: --sites-gap needs an integer of at least 0\n"); return 2; }
 	if (sites && (p.classicSim || accumulate || track || screen || trk.tfo)) { fprintf(stderr, "fasim: --sites is not available with -F, --accumulate-records, --track, --screen or --tfo-profile\n"); return 2; }
@@ -600,6 +622,8 @@ int main(int argc, char* const* argv)
 	// <O>/<lnc>-<f1 stem>.sites-<V>.bed: one header line, then the records' sites in record / BED order, the record's name last
 	const bool sites_set = sites && (all_records || regions);
 	std::vector<std::map<int64_t, std::string>> sites_text(sites_set ? rnas.size() : 0);      // [lncRNA][record number or BED index]
+	// --sites-align: beside every sites file the table of the sites' hits, <stem>-TFOsites-<V>-aligned or .sites-<V>.aligned.tsv
+	std::vector<std::map<int64_t, std::string>> hits_text(sites_set && trk.sites_align ? rnas.size() : 0);
 	auto write_sites_set = [&]() -> int {
 		int bad = 0;
 		for (size_t q = 0; q < sites_text.size(); q++) {
@@ -610,6 +634,13 @@ int main(int argc, char* const* argv)
 			fasim_free(text);
 			for (const auto& kv : sites_text[q]) t += kv.second;
 			bad |= write_file(outdir + "/" + rnas[q].name + "-" + base + ".sites-" + std::to_string(trk.sites) + ".bed", t.data(), (int64_t)t.size());
+			if (!trk.sites_align) continue;
+			fasim_site_hits nohits; memset(&nohits, 0, sizeof nohits);
+			if (fasim_site_hits_tsv(&none, &nohits, "", 1, rnas[q].name.c_str(), "", 1, &text, &len) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
+			std::string h(text, (size_t)len);
+			fasim_free(text);
+			for (const auto& kv : hits_text[q]) h += kv.second;
+			bad |= write_file(outdir + "/" + rnas[q].name + "-" + base + ".sites-" + std::to_string(trk.sites) + ".aligned.tsv", h.data(), (int64_t)h.size());
 		}
 		return bad;
 	};
@@ -692,7 +723,7 @@ int main(int argc, char* const* argv)
 		// one scanned record: a DNA record, or a BED interval (species = its name, start = its 1-based start; slot = its index)
 		struct Unit { std::string species, chr; long start = 0; int64_t len = 0; size_t recno = 0; int64_t slot = -1; };
 		// per record: --stats lines, output stem, tail + write on a background thread (the next record is read and scanned meanwhile)
-		auto emit = [&](const Unit& r, const std::vector<fasim_result*>& res, const std::vector<fasim_track*>& tracks, const fasim_peak* const* pk = nullptr, fasim_sites* const* st = nullptr) {
+		auto emit = [&](const Unit& r, const std::vector<fasim_result*>& res, const std::vector<fasim_track*>& tracks, const fasim_peak* const* pk = nullptr, fasim_sites* const* st = nullptr, fasim_site_hits* const* ht = nullptr) {
 			if (sites && st) {
 				// the record's sites: its own file (a plain run), or its lines of the set's file
 				for (size_t q = 0; q < rnas.size(); q++) {
@@ -702,6 +733,16 @@ int main(int argc, char* const* argv)
 					} else if (sites_set) sites_text[q][r.slot >= 0 ? r.slot : (int64_t)r.recno].assign(text, (size_t)len);
 					else if (write_file(outdir + "/" + r.species + "-" + rnas[q].name + "-" + base + "-TFOsites-" + std::to_string(trk.sites), text, len)) g_out_failed = 1;
 					fasim_free(text);
+					if (ht) {
+						// the hits of those sites, line for line beside them
+						text = nullptr;
+						if (fasim_site_hits_tsv(st[q], ht[q], r.chr.c_str(), r.start, rnas[q].name.c_str(), sites_set ? r.species.c_str() : nullptr, sites_set ? 0 : 1, &text, &len) != FASIM_OK) {
+							fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); g_out_failed = 1;
+						} else if (sites_set) hits_text[q][r.slot >= 0 ? r.slot : (int64_t)r.recno].assign(text, (size_t)len);
+						else if (write_file(outdir + "/" + r.species + "-" + rnas[q].name + "-" + base + "-TFOsites-" + std::to_string(trk.sites) + "-aligned", text, len)) g_out_failed = 1;
+						fasim_free(text);
+						fasim_site_hits_free(ht[q]);
+					}
 					fasim_sites_free(st[q]);
 				}
 				if (trk.sites_only) return;
@@ -775,7 +816,9 @@ int main(int argc, char* const* argv)
 			std::vector<fasim_peak> gpeaks;
 			std::vector<fasim_tfo_profile*> gprof;
 			std::vector<std::vector<fasim_sites*>> gsites;
-			if (scan_group(engines, rnas, gdna, goff, glen, p, res, trk, gtracks, gpeaks, trk.tfo ? &gprof : nullptr, sites ? &gsites : nullptr)) return 1;
+			std::vector<std::vector<fasim_site_hits*>> ghits;
+			if (scan_group(engines, rnas, gdna, goff, glen, p, res, trk, gtracks, gpeaks, trk.tfo ? &gprof : nullptr, sites ? &gsites : nullptr,
+				sites && trk.sites_align ? &ghits : nullptr)) return 1;
 			for (size_t q = 0; q < gprof.size(); q++) { fasim_tfo_profile* t = gprof[q]; gprof[q] = nullptr; if (tfo_fold(tfo_acc[q], t)) return 1; }
 			const double dt = now_s() - t0;
 			tm.scan += dt;
@@ -784,12 +827,14 @@ int main(int argc, char* const* argv)
 			std::vector<fasim_track*> onet(gtracks.size());
 			std::vector<const fasim_peak*> onep(rnas.size(), nullptr);
 			std::vector<fasim_sites*> ones(gsites.size());
+			std::vector<fasim_site_hits*> oneh(ghits.size());
 			for (size_t r = 0; r < group.size(); r++) {
 				for (size_t q = 0; q < gsites.size(); q++) ones[q] = gsites[q][r];
+				for (size_t q = 0; q < ghits.size(); q++) oneh[q] = ghits[q][r];
 				for (size_t q = 0; q < rnas.size(); q++) one[q] = res[q][r];
 				for (size_t q = 0; q < gtracks.size(); q++) onet[q] = gtracks[q][r];
 				if (!gpeaks.empty()) for (size_t q = 0; q < rnas.size(); q++) onep[q] = gpeaks.data() + (q * group.size() + r) * 4;
-				emit(group[r], one, onet, gpeaks.empty() ? nullptr : onep.data(), gsites.empty() ? nullptr : ones.data());
+				emit(group[r], one, onet, gpeaks.empty() ? nullptr : onep.data(), gsites.empty() ? nullptr : ones.data(), ghits.empty() ? nullptr : oneh.data());
 				total_nt += group[r].len;
 			}
 			ngroups++; group.clear(); gdna.clear(); goff.clear(); glen.clear(); group_nseg = 0;

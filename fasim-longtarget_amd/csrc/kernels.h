@@ -148,6 +148,37 @@ struct SitesLaunch {
 };
 hipError_t launch_sites(const SitesLaunch& L, bool emit, hipStream_t st);
 
+// ---- site_align.hip: the textbook local alignment behind a site's peak -----------------------------------
+// One problem: a unit (its target codes at tcodes + tbase, n columns), the column jp of the site's peak and the peak's value.
+struct SiteAlignProb { int64_t tbase; int32_t n, jp, value, pad; };
+// What k_site_ends leaves for a problem: the end cell (i1, j1) and the start cell (i0, j0) of the hit.  i1 == -1: the unit does
+// not hold `value` in column jp; i0 == -1 (with i1 >= 0): the anchored reverse pass did not reach `value`.
+struct alignas(16) SiteAlignEnds { int32_t i1, j1, i0, j0; };
+// The 16-bit row state clamps at -30 000 ("no alignment") and 32 767: +5 per column cannot climb from the clamp back to a value >= 1
+// and a local score stays below the upper clamp only while a unit has at most 6 000 columns (-c); longer units are left unaligned
+constexpr int SITE_ALIGN_MAX_COLS = 6000;
+constexpr int SITE_ALIGN_LDS_ROWS = 8192;       // query rows whose DP state (7 bytes per row) k_site_ends keeps in LDS
+constexpr int64_t SITE_ALIGN_MAX_CELLS = (int64_t)1 << 26;      // largest rectangle k_site_path takes (one direction byte per cell; 4 x 4 096 x 4 096), at most SITE_ALIGN_LDS_ROWS rows
+struct SiteEndsLaunch {
+	const uint8_t* tcodes; const uint8_t* qcodes; int32_t m;      // query codes of the stage-2 alphabet, m real rows (no pad rows)
+	int32_t npad;                 // pad rows of the scan (16 * ceil(m/16) - m): their echoes reach npad columns past the real cell
+	const SiteAlignProb* probs; int32_t nprob;
+	int16_t* rows;                // [nprob][3][m]: DP state of the queries that do not fit the LDS (m > SITE_ALIGN_LDS_ROWS), else NULL
+	SiteAlignEnds* ends;          // [nprob]
+};
+// One path: the rectangle [i0, i1] x [j0, j1] of problem `prob`; direction bytes at dirs + dir_off (rows * cols of them), the
+// CIGAR (BAM encoding, LAST operation first) at cigar + cig_off, at most cig_cap words
+struct SitePathItem { int64_t dir_off; int32_t prob, i0, i1, j0, j1, cig_off, cig_cap, pad; };
+struct SitePathLaunch {
+	const uint8_t* tcodes; const uint8_t* qcodes; const SiteAlignProb* probs;
+	const SitePathItem* items; int32_t nitem;
+	int32_t max_rows;             // the tallest rectangle of the launch, at most SITE_ALIGN_LDS_ROWS
+	uint8_t* dirs; uint32_t* cigar;
+	int32_t* cigar_len;           // [nitem]: words written, -1: the anchored pass did not give `value` or the path left the rectangle
+};
+hipError_t launch_site_ends(const SiteEndsLaunch& L, hipStream_t st);
+hipError_t launch_site_path(const SitePathLaunch& L, hipStream_t st);
+
 // ---- rowfold.hip: per-base profile of the lncRNA folded from the row maxima of a batch -------------------------
 // Group g = segments [gfirst[g], gfirst[g + 1]) of the batch (the run of segments of one record, or the whole batch); the result is
 // out[g][4 classes][rows_total] = maximum over the group's units of the class, taint bit dropped.

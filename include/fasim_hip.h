@@ -378,6 +378,54 @@ int  fasim_sites_merge(const fasim_sites* const* parts, int32_t nparts, fasim_si
 int  fasim_sites_bed(const fasim_sites* t, const char* chr, int64_t start_genome, const char* rna_name,
                      const char* record_name /* NULL: 8 columns */, int32_t header, char** text, int64_t* text_len);
 void fasim_sites_free(fasim_sites* t);
+/* ---- every site with its hit (csrc/site_align.hip) ---------------------------------------------------------- */
+/* The HIT of a site is the textbook local alignment behind its peak: H is the matrix of section 11 (plain Gotoh, +5 / -4, every
+ * non-ACGT letter -4, U read as A, gap 16 then 4, floored at 0, no Q1, no Q2).  Unit: the selected segment of the smallest index that
+ * covers pos and whose unit under `enc` has column maximum `value` at pos.  End cell (i1, j1): the largest column j1 <= the column
+ * of pos at which a real row holds H == value (a pad row only repeats row m - 1 one column later per row), the smallest such row
+ * i1.  Start cell (i0, j0): among the alignments that begin with a pair, end with the pair (i1, j1) and score `value`, the largest
+ * column j0 and then the largest row i0 -- the alignment that is shortest on the DNA side.  Path: the anchored Gotoh matrices of the
+ * rectangle, traced back from (i1, j1) with fixed priorities (in H: diagonal, then E, then F; in a gap state: extend, then open).
+ * The alignment then goes through the conversion every record of fasim_scan goes through, with -ni 1 and no -na, and is never
+ * filtered: t[k] is the fasim_triplex of site k (score = value; strings in pool), q_begin / q_end / t_begin / t_end the
+ * unit-relative cells i0, i1, j0, j1, cigar[cigar_off[k] .. + cigar_len[k]) its CIGAR ((len << 4) | op, 0 = M, 1 = I: a query
+ * base against a gap, 2 = D: a target base against a gap; first and last operation M).
+ * Limits: a site of value 16 383 (a saturated unit), a site whose unit no longer holds `value` in exact arithmetic (possible only
+ * after a saturation), an end cell that no alignment beginning and ending with a pair reaches with `value`, and a hit whose rectangle
+ * has more than 8 192 rows or 2^26 cells (4 x 4 096 x 4 096), and every site of a call with cutLength above 6 000, come back with cigar_len = -1, empty strings and whatever cells were
+ * found (-1 otherwise), and are counted in `unaligned`. */
+typedef struct fasim_site_hits {
+	int64_t n; fasim_triplex* t;                 /* n hits: hit k belongs to site k of the same (query, record)            */
+	int32_t* q_begin, *q_end, *t_begin, *t_end;  /* i0, i1, j0, j1                                                          */
+	int64_t* cigar_off; int32_t* cigar_len; uint32_t* cigar;
+	char* pool; int64_t pool_len;
+	int64_t unaligned;
+} fasim_site_hits;
+/* fasim_scan_records_sites and, as a second phase once the sites are final, the hit of every site: the arguments and refusals of
+ * fasim_scan_records_sites, plus out_hits == NULL -> FASIM_E_ARG.  out_sites, out_results and totals are byte for byte those of
+ * fasim_scan_records_sites.  out_hits[q * nrec + r] depends on the record, the query, the parameters, min_value and max_gap only.
+ * FASIM_E_NOMEM leaves the engine usable.  Free each with fasim_site_hits_free. */
+int  fasim_scan_records_sites_aligned(fasim_engine* e, const char* const* rnas, const int32_t* rna_lens, int32_t nq,
+                                      const char* dna, const int64_t* rec_off, const int64_t* rec_len, int32_t nrec,
+                                      int64_t seg_first, int64_t seg_count, const fasim_params* p, int32_t min_value, int32_t max_gap,
+                                      fasim_result** out_results /* [nq * nrec] or NULL: no stage 3 */,
+                                      fasim_sites** out_sites /* [nq * nrec] */, fasim_site_hits** out_hits /* [nq * nrec] */,
+                                      fasim_scan_stats* totals /* [nq], may be NULL */);
+/* Shards of ONE record: sites[k] / hits[k] are what shard k returned.  *out_sites (may be NULL) receives fasim_sites_merge of the
+ * site lists, *out_hits the hits of that merged list: where intervals unite, the part whose site wins (larger value, smaller pos,
+ * smaller enc) supplies the hit; on a full tie the hit of the smaller `seg` wins (an unaligned hit loses against an aligned one).
+ * Refusals: those of fasim_sites_merge, and a part whose hits->n differs from its sites->n (FASIM_E_ARG). */
+int  fasim_site_hits_merge(const fasim_sites* const* sites, const fasim_site_hits* const* hits, int32_t nparts,
+                           fasim_sites** out_sites, fasim_site_hits** out_hits);
+/* The table `fasim --sites V --sites-align` writes.  header != 0: first `# fasim site hits lncRNA=<rna_name> min_value=<V>
+ * max_gap=<G>` and the line of column names.  Then one tab-separated line per site, in the order of the site list: chrom
+ * tts_start tts_end class value strand rule tfo_start tfo_end nt identity stability cigar TFO TTS, and record_name as a last
+ * column where it is not NULL.  tts_start / tts_end: 0-based half-open genome coordinates of the DNA bases of the hit
+ * (start_genome as in fasim_sites_bed); tfo_start / tfo_end: 1-based inclusive lncRNA positions; identity and stability printed as
+ * -TFOsorted prints them.  An unaligned hit has NA from rule on (tts_start / tts_end: the site's range).  Free with fasim_free. */
+int  fasim_site_hits_tsv(const fasim_sites* s, const fasim_site_hits* h, const char* chr, int64_t start_genome, const char* rna_name,
+                         const char* record_name /* NULL: 15 columns */, int32_t header, char** text, int64_t* text_len);
+void fasim_site_hits_free(fasim_site_hits* h);
 
 /* Host half of the path's one exchange step: concatenates the records of `nparts` shards in the
  * order given and rebases their pool offsets.  Shards are contiguous segment ranges, so rank order IS the
