@@ -88,6 +88,8 @@ class SimNode(C.Structure):
 SIM_K = 50
 # FASIM_MAX_QUERY (include/fasim_hip.h): longest query of the fastSIM entry points (the reference's 16-bit stage-1 workspace)
 MAX_QUERY = 92256
+# FASIM_MAX_OLIGO (include/fasim_hip.h): longest oligo of a panel (Engine.scan_oligos)
+MAX_OLIGO = 112
 
 
 class _Region(C.Structure):
@@ -141,6 +143,7 @@ EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_e
            "fasim_scan_tfo_profile", "fasim_tfo_profile_merge", "fasim_tfo_profile_tsv", "fasim_tfo_profile_free",
            "fasim_scan_records_sites", "fasim_sites_merge", "fasim_sites_bed", "fasim_sites_free",
            "fasim_scan_records_sites_aligned", "fasim_site_hits_merge", "fasim_site_hits_tsv", "fasim_site_hits_free",
+           "fasim_scan_oligos", "fasim_oligo_panel_tsv",
            # the reference's own ssw.h ABI (include/ssw.h)
            "ssw_init", "init_destroy", "ssw_pre_align", "ssw_align", "align_destroy", "encoded_ops"]
 
@@ -255,6 +258,12 @@ def lib():
                                       C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.fasim_site_hits_free.argtypes = [C.POINTER(_SiteHits)]
     L.fasim_site_hits_free.restype = None
+    L.fasim_scan_oligos.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
+                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int64, C.c_int64, C.POINTER(Params),
+                                    C.c_int32, C.c_int32, C.POINTER(C.POINTER(_Sites)), C.c_int32, C.POINTER(C.POINTER(_Track)),
+                                    C.POINTER(ScanStats)]
+    L.fasim_oligo_panel_tsv.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.POINTER(_Sites)), C.c_int32,
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     _lib = L
     return L
 
@@ -615,6 +624,33 @@ def sites_bed(sites: Sites, chr_name: str, start_genome: int, rna_name: str, rec
                            record_name.encode() if record_name is not None else None, 1 if header else 0, C.byref(text), C.byref(n))
     if rc != 0:
         raise FasimError(f"fasim_sites_bed failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
+    try:
+        return C.string_at(text, n.value)
+    finally:
+        L.fasim_free(text)
+
+
+def oligo_panel_tsv(names, oligos, sites) -> bytes:
+    """The panel table of Engine.scan_oligos() (fasim_oligo_panel_tsv): per oligo its name, length, number of sites and covered
+    bases over all records and classes, and per strand class the number of sites and the largest value (0 without a site).
+    `sites`: the list per oligo of lists per record that scan_oligos() returns; what `fasim --oligos --sites V` writes."""
+    L = lib()
+    names, oligos, sites = list(names), list(oligos), [list(row) for row in sites]
+    nq = len(names)
+    if len(oligos) != nq or len(sites) != nq:
+        raise FasimError("oligo_panel_tsv: names, oligos and sites differ in length", E_ARG)
+    nrec = len(sites[0]) if nq else 1
+    if any(len(row) != nrec for row in sites):
+        raise FasimError("oligo_panel_tsv: every oligo needs one site list per record", E_ARG)
+    flat = [t for row in sites for t in row]
+    arr = (C.POINTER(_Sites) * max(1, len(flat)))(*[t.pointer() for t in flat])
+    nm = (C.c_char_p * max(1, nq))(*[n.encode() if isinstance(n, str) else bytes(n) for n in names])
+    lens = (C.c_int32 * max(1, nq))(*[len(o) for o in oligos])
+    text = C.c_void_p()
+    n = C.c_int64()
+    rc = L.fasim_oligo_panel_tsv(nm, lens, nq, arr, nrec, C.byref(text), C.byref(n))
+    if rc != 0:
+        raise FasimError(f"fasim_oligo_panel_tsv failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
     try:
         return C.string_at(text, n.value)
     finally:
@@ -1202,6 +1238,43 @@ class Engine:
         two are exactly what scan_sites() returns; hits has the shape of sites, one SiteHits per record (per lncRNA and record
         with rnas given).  Shards of a segment range merge with merge_site_hits()."""
         return self._sites_call(True, dnas, params, min_value, max_gap, records, rnas, seg_first, seg_count)
+
+    def scan_oligos(self, oligos, dnas, params: Params | None = None, min_value: int = 1, max_gap: int = 0, track_bin: int = 0,
+                    seg_first: int = 0, seg_count: int = -1):
+        """Sites, and with track_bin >= 1 potential tracks, of a panel of short oligos of 1 .. MAX_OLIGO nt (fasim_scan_oligos):
+        `sites`, or `(sites, tracks)`, lists per oligo of lists per record of Sites / Track objects -- what scan_sites() and
+        scan_records_track() would give for a lncRNA, with the oligo in its place.  `dnas` as for scan_sites().  The engine's own
+        query is not touched.  Shards of a segment range merge with merge_sites() / merge_tracks(); the panel table is
+        oligo_panel_tsv().  Totals per oligo: `self.last_totals`."""
+        p = params or default_params()
+        if isinstance(dnas, (bytes, bytearray)):
+            dnas = [bytes(dnas)]
+        if dnas is None:
+            blob, offs, lens, nrec = None, None, None, 1        # the whole resident buffer: the engine knows its length
+        else:
+            blob = b"".join(dnas)
+            nrec = len(dnas)
+            offs = (C.c_int64 * max(1, nrec))()
+            lens = (C.c_int64 * max(1, nrec))()
+            o = 0
+            for i, d in enumerate(dnas):
+                offs[i], lens[i] = o, len(d)
+                o += len(d)
+        oligos = [bytes(x) for x in oligos]
+        nq = len(oligos)
+        arr = (C.c_char_p * max(1, nq))(*oligos)
+        qlens = (C.c_int32 * max(1, nq))(*[len(x) for x in oligos])
+        nout = max(1, nq) * max(1, nrec)
+        sts = (C.POINTER(_Sites) * nout)()
+        trks = (C.POINTER(_Track) * nout)() if track_bin != 0 else None
+        totals = (ScanStats * max(1, nq))()
+        self._check(self._L.fasim_scan_oligos(self._h, arr, qlens, nq, blob, offs, lens, nrec, seg_first, seg_count, C.byref(p),
+                                              min_value, max_gap, sts, track_bin, trks, totals))
+        self.last_totals = [self._stats_dict(totals[q]) for q in range(nq)]
+        sites = [[Sites(_native=sts[q * nrec + r]) for r in range(nrec)] for q in range(nq)]
+        if trks is None:
+            return sites
+        return sites, [[Track(_native=trks[q * nrec + r]) for r in range(nrec)] for q in range(nq)]
 
     def _records_track(self, blob, offs, lens, nrec, p, rnas, bin, records, seg_first, seg_count):
         nq = 0 if rnas is None else len(rnas)

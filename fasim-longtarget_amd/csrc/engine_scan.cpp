@@ -266,6 +266,89 @@ TrackTable class_table(const std::vector<int>& encs)
 	return tab;
 }
 
+// The head of a batch, segments [b0, b1) of the call's segment table: the segments that same_seq() does not skip into C, their DNA
+// onto the device (the resident buffer in place, a host buffer through the worker's pinned staging buffer) and k_encode over their
+// units into E->tcodes.  C.nseg == 0 afterwards: nothing to scan.  `m`: rows of the query or queries, for the cell counts of `st`.
+int batch_encode(fasim_engine* E, const char* dna, const SegTable& T, const uint8_t* dna_dev, int64_t b0, int64_t b1,
+	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st, int64_t m)
+{
+	int rc = FASIM_OK;
+	const int64_t step = p.cutLength - p.overlapLength;
+	const int nenc = (int)encs.size();
+	C.B = UnitBatch(); C.tstride = tstride; C.nenc = nenc; C.nseg = 0; C.step = step; C.dna = dna; C.p = &p; C.encs = &encs;
+	// segments of this batch that are not skipped by same_seq()
+	std::vector<int32_t>& sstart = C.sstart; std::vector<int32_t>& slen = C.slen; std::vector<int64_t>& sidx = C.sidx;
+	sstart.clear(); slen.clear(); sidx.clear(); C.soff.clear(); C.srec.clear();
+	int64_t lo = INT64_MAX, hi = 0;
+	for (int64_t s = b0; s < b1; s++) { lo = std::min(lo, T.off[(size_t)s]); hi = std::max(hi, T.off[(size_t)s] + T.len[(size_t)s]); }
+	std::vector<int64_t> dpos((size_t)(b1 - b0));       // device start of every segment, relative to the batch's DNA on the device
+	if (dna_dev && hi - lo <= 0x7fffffffll) {
+		dna_dev += lo;
+		for (int64_t s = b0; s < b1; s++) dpos[(size_t)(s - b0)] = T.off[(size_t)s] - lo;
+	} else {
+		// Streaming ingest: the record is in host memory only.  The slice this batch needs goes through the worker's
+		// pinned staging buffer and its own stream; with ~10 batches in flight the copy of one batch overlaps the kernels
+		// of the others, and HBM holds 10 slices of ~2.5 MB instead of the whole record.  The consecutive segments of one
+		// record are one run of `dna` and are copied once; the runs of a batch that crosses records are packed side by side
+		// (a single-record batch is one run).  A resident set whose batch spans more than 2^31 nt is staged the same way.
+		size_t bytes = 0;
+		for (int64_t s = b0; s < b1; ) {
+			int64_t e = s + 1;
+			while (e < b1 && T.rec[(size_t)e] == T.rec[(size_t)s]) e++;
+			bytes += (size_t)(T.off[(size_t)e - 1] + T.len[(size_t)e - 1] - T.off[(size_t)s]);
+			s = e;
+		}
+		if (bytes > 0x7fffffffull) return fail(E, FASIM_E_UNSUPPORTED, "a batch of %lld segments spans %zu nt: more than the kernels' int32 segment starts hold", (long long)(b1 - b0), bytes);
+		if (bytes > E->pin_cap) {
+			if (E->pin_dna) { (void)hipHostFree(E->pin_dna); E->pin_dna = nullptr; E->pin_cap = 0; }
+			HIPOK(hipHostMalloc(&E->pin_dna, bytes + bytes / 8, hipHostMallocDefault));
+			E->pin_cap = bytes + bytes / 8;
+		}
+		size_t at = 0;
+		for (int64_t s = b0; s < b1; ) {
+			int64_t e = s + 1;
+			while (e < b1 && T.rec[(size_t)e] == T.rec[(size_t)s]) e++;
+			const int64_t rlo = T.off[(size_t)s], rhi = T.off[(size_t)e - 1] + T.len[(size_t)e - 1];
+			memcpy((char*)E->pin_dna + at, dna + rlo, (size_t)(rhi - rlo));
+			for (int64_t k = s; k < e; k++) dpos[(size_t)(k - b0)] = (int64_t)at + (T.off[(size_t)k] - rlo);
+			at += (size_t)(rhi - rlo);
+			s = e;
+		}
+		HIPOK(E->dna.ensure(bytes));
+		HIPOK(hipMemcpyAsync(E->dna.p, E->pin_dna, bytes, hipMemcpyHostToDevice, E->st));
+		dna_dev = E->dna.as<uint8_t>();
+	}
+	for (int64_t s = b0; s < b1; s++) {
+		const int64_t pos = T.off[(size_t)s];
+		const int len = T.len[(size_t)s];
+		st.segments++;
+		if (same_seq(dna + pos, len)) { st.segments_skipped++; continue; }
+		sstart.push_back((int32_t)dpos[(size_t)(s - b0)]); slen.push_back(len); sidx.push_back(T.idx[(size_t)s]);
+		C.soff.push_back(pos); C.srec.push_back(T.rec[(size_t)s]);
+		st.logical_cells += (int64_t)m * len * nenc;
+	}
+	const int nseg = (int)sidx.size();
+	C.nseg = nseg;
+	if (!nseg) return FASIM_OK;
+	UnitBatch& B = C.B; B.nunit = nseg * nenc; B.tstride = tstride; B.unit_len.resize(B.nunit);
+	for (int s = 0; s < nseg; s++) for (int k = 0; k < nenc; k++) B.unit_len[s * nenc + k] = slen[s];
+	st.units += B.nunit;
+	C.ucand.assign((size_t)B.nunit, 0); C.ualign.assign((size_t)B.nunit, 0);
+	// executed DP cells: the fused k_scan pass serves stage 1 AND stage 2, so it is counted once (as stage 2); stage 1 is
+	// counted only where it really is a pass of its own (units with N / non-ACGT queries, the striped fallback)
+	for (int s = 0; s < nseg; s++) st.cells_stage2 += (int64_t)m * slen[s] * nenc;
+	rc = upload(E, E->seg_start, sstart.data(), sizeof(int32_t) * nseg); if (rc) return rc;
+	rc = upload(E, E->seg_len, slen.data(), sizeof(int32_t) * nseg); if (rc) return rc;
+	rc = upload(E, E->unit_len, B.unit_len.data(), sizeof(int32_t) * B.nunit); if (rc) return rc;
+	HIPOK(E->tcodes.ensure((size_t)B.nunit * tstride));
+	hipError_t he;
+	{ TimedScope ts(E, 4);
+	he = launch_encode(dna_dev, E->seg_start.as<int32_t>(), E->seg_len.as<int32_t>(), nseg,
+		E->enc_ids.as<int32_t>(), nenc, E->enc_lut.as<uint8_t>(), E->tcodes.as<uint8_t>(), tstride, E->st); }
+	if (he != hipSuccess) return fail(E, FASIM_E_HIP, "encode launch failed: %s", hipGetErrorString(he));
+	return FASIM_OK;
+}
+
 // Segments [b0, b1) of the call's segment table on one worker.  `dna_dev`: the resident buffer (fasim_load_dna), or NULL for a
 // host buffer.  The kernels take int32 segment starts relative to the batch's own first byte on the device, so a record set
 // longer than 2^31 nt works as long as one batch's span does.
@@ -277,78 +360,13 @@ int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_
 	const int nenc = (int)encs.size();
 	C.B = UnitBatch(); C.tstride = tstride; C.nenc = nenc; C.nseg = 0; C.step = step; C.dna = dna; C.p = &p; C.encs = &encs; C.stage3_done = false; C.track_done = false; C.rows_done = false; C.sites_done = false;
 	C.per_unit.clear(); C.ucand.clear(); C.ualign.clear();
+	rc = batch_encode(E, dna, T, dna_dev, b0, b1, p, encs, tstride, C, st, E->m); if (rc) return rc;
+	if (!C.nseg) return FASIM_OK;
 	{
-		// segments of this batch that are not skipped by same_seq()
-		std::vector<int32_t>& sstart = C.sstart; std::vector<int32_t>& slen = C.slen; std::vector<int64_t>& sidx = C.sidx;
-		sstart.clear(); slen.clear(); sidx.clear(); C.soff.clear(); C.srec.clear();
-		int64_t lo = INT64_MAX, hi = 0;
-		for (int64_t s = b0; s < b1; s++) { lo = std::min(lo, T.off[(size_t)s]); hi = std::max(hi, T.off[(size_t)s] + T.len[(size_t)s]); }
-		std::vector<int64_t> dpos((size_t)(b1 - b0));       // device start of every segment, relative to the batch's DNA on the device
-		if (dna_dev && hi - lo <= 0x7fffffffll) {
-			dna_dev += lo;
-			for (int64_t s = b0; s < b1; s++) dpos[(size_t)(s - b0)] = T.off[(size_t)s] - lo;
-		} else {
-			// Streaming ingest: the record is in host memory only.  The slice this batch needs goes through the worker's
-			// pinned staging buffer and its own stream; with ~10 batches in flight the copy of one batch overlaps the kernels
-			// of the others, and HBM holds 10 slices of ~2.5 MB instead of the whole record.  The consecutive segments of one
-			// record are one run of `dna` and are copied once; the runs of a batch that crosses records are packed side by side
-			// (a single-record batch is one run).  A resident set whose batch spans more than 2^31 nt is staged the same way.
-			size_t bytes = 0;
-			for (int64_t s = b0; s < b1; ) {
-				int64_t e = s + 1;
-				while (e < b1 && T.rec[(size_t)e] == T.rec[(size_t)s]) e++;
-				bytes += (size_t)(T.off[(size_t)e - 1] + T.len[(size_t)e - 1] - T.off[(size_t)s]);
-				s = e;
-			}
-			if (bytes > 0x7fffffffull) return fail(E, FASIM_E_UNSUPPORTED, "a batch of %lld segments spans %zu nt: more than the kernels' int32 segment starts hold", (long long)(b1 - b0), bytes);
-			if (bytes > E->pin_cap) {
-				if (E->pin_dna) { (void)hipHostFree(E->pin_dna); E->pin_dna = nullptr; E->pin_cap = 0; }
-				HIPOK(hipHostMalloc(&E->pin_dna, bytes + bytes / 8, hipHostMallocDefault));
-				E->pin_cap = bytes + bytes / 8;
-			}
-			size_t at = 0;
-			for (int64_t s = b0; s < b1; ) {
-				int64_t e = s + 1;
-				while (e < b1 && T.rec[(size_t)e] == T.rec[(size_t)s]) e++;
-				const int64_t rlo = T.off[(size_t)s], rhi = T.off[(size_t)e - 1] + T.len[(size_t)e - 1];
-				memcpy((char*)E->pin_dna + at, dna + rlo, (size_t)(rhi - rlo));
-				for (int64_t k = s; k < e; k++) dpos[(size_t)(k - b0)] = (int64_t)at + (T.off[(size_t)k] - rlo);
-				at += (size_t)(rhi - rlo);
-				s = e;
-			}
-			HIPOK(E->dna.ensure(bytes));
-			HIPOK(hipMemcpyAsync(E->dna.p, E->pin_dna, bytes, hipMemcpyHostToDevice, E->st));
-			dna_dev = E->dna.as<uint8_t>();
-		}
-		for (int64_t s = b0; s < b1; s++) {
-			const int64_t pos = T.off[(size_t)s];
-			const int len = T.len[(size_t)s];
-			st.segments++;
-			if (same_seq(dna + pos, len)) { st.segments_skipped++; continue; }
-			sstart.push_back((int32_t)dpos[(size_t)(s - b0)]); slen.push_back(len); sidx.push_back(T.idx[(size_t)s]);
-			C.soff.push_back(pos); C.srec.push_back(T.rec[(size_t)s]);
-			st.logical_cells += (int64_t)E->m * len * nenc;
-		}
-		const int nseg = (int)sidx.size();
-		if (!nseg) return FASIM_OK;
-		C.nseg = nseg;
-		UnitBatch& B = C.B; B.nunit = nseg * nenc; B.tstride = tstride; B.unit_len.resize(B.nunit);
-		for (int s = 0; s < nseg; s++) for (int k = 0; k < nenc; k++) B.unit_len[s * nenc + k] = slen[s];
-		st.units += B.nunit;
-		C.ucand.assign((size_t)B.nunit, 0); C.ualign.assign((size_t)B.nunit, 0);
-		// executed DP cells: the fused k_scan pass serves stage 1 AND stage 2, so it is counted once (as stage 2); stage 1 is
-		// counted only where it really is a pass of its own (units with N / non-ACGT queries, the striped fallback)
-		for (int s = 0; s < nseg; s++) st.cells_stage2 += (int64_t)E->m * slen[s] * nenc;
-		rc = upload(E, E->seg_start, sstart.data(), sizeof(int32_t) * nseg); if (rc) return rc;
-		rc = upload(E, E->seg_len, slen.data(), sizeof(int32_t) * nseg); if (rc) return rc;
-		rc = upload(E, E->unit_len, B.unit_len.data(), sizeof(int32_t) * B.nunit); if (rc) return rc;
-		HIPOK(E->tcodes.ensure((size_t)B.nunit * tstride));
+		std::vector<int32_t>& slen = C.slen; std::vector<int64_t>& sidx = C.sidx;
+		const int nseg = C.nseg;
+		UnitBatch& B = C.B;
 		hipError_t he;
-		{ TimedScope ts(E, 4);
-		he = launch_encode(dna_dev, E->seg_start.as<int32_t>(), E->seg_len.as<int32_t>(), nseg,
-			E->enc_ids.as<int32_t>(), nenc, E->enc_lut.as<uint8_t>(), E->tcodes.as<uint8_t>(), tstride, E->st); }
-		if (he != hipSuccess) return fail(E, FASIM_E_HIP, "encode launch failed: %s", hipGetErrorString(he));
-
 		// ---- stages 1+2: fused systolic scan (scan.hip); stripe-faithful kernels for hazard units, for
 		//      queries beyond 3072 rows, or when FASIM_SCAN_V1=1
 		double t0 = now_s();
@@ -488,7 +506,7 @@ int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_
 // fasim_scan_track / fasim_scan_records_track: the slices of a finished scan phase into the arrays of query q and of every
 // segment's own record (maximum; overlapping segments and the slices of one segment that share a bin meet here), and the slices'
 // peaks into the record's peaks (larger value, then lower position, then lower encoding)
-static void merge_track(const BatchCtx& C, TrackReq& tr, int q)
+void merge_track(const BatchCtx& C, TrackReq& tr, int q)
 {
 	const int stride = tr.bin >= 1 ? track_slice_stride(tr.bin) : 0;
 	const int64_t bin = tr.bin;
@@ -524,7 +542,7 @@ static void merge_track(const BatchCtx& C, TrackReq& tr, int q)
 
 // fasim_scan_records_sites: the runs of a finished scan phase, rebased from segment to record positions, onto the lists of query q
 // and of every segment's own record
-static void merge_site_runs(const BatchCtx& C, SitesReq& sr, int q)
+void merge_site_runs(const BatchCtx& C, SitesReq& sr, int q)
 {
 	std::lock_guard<std::mutex> g(sr.mu[(size_t)q]);
 	size_t at = 0;

@@ -259,6 +259,75 @@ int run_hazard_chunked(fasim_engine* E, const UnitBatch& B, const std::vector<in
 	return FASIM_OK;
 }
 
+// k_track over the batch's column maxima in E->colmax16, into the host vectors of `tf`.  The copies complete at the next synchronisation
+// of the stream.
+int run_track_fold(fasim_engine* E, const UnitBatch& B, const TrackFold* tf)
+{
+	const int nu = B.nunit;
+	int rc; hipError_t he;
+	rc = upload(E, E->track_phase, tf->phase, sizeof(int32_t) * tf->nseg); if (rc) return rc;
+	const size_t nout = tf->bin >= 1 ? (size_t)tf->nseg * tf->nchunk * 4 * track_slice_stride(tf->bin) : 0;      // (bin == 0: peaks only)
+	const size_t npeak = tf->peaks ? (size_t)tf->nseg * tf->nchunk * 4 : 0;
+	HIPOK(E->track.ensure(nout * sizeof(uint16_t))); HIPOK(E->track_sat.ensure((size_t)nu));
+	if (npeak) HIPOK(E->track_peaks.ensure(npeak * sizeof(TrackPeak)));
+	HIPOK(hipMemsetAsync(E->track_sat.p, 0, (size_t)nu, E->st));
+	TrackLaunch T;
+	T.colmax16 = E->colmax16.as<uint16_t>(); T.seg_len = E->seg_len.as<int32_t>(); T.phase = E->track_phase.as<int32_t>();
+	T.nseg = tf->nseg; T.nenc = tf->nenc; T.tstride = B.tstride; T.nchunk = tf->nchunk; T.bin = tf->bin; T.tab = tf->tab;
+	T.out = E->track.as<uint16_t>(); T.sat = E->track_sat.as<uint8_t>(); T.peaks = npeak ? E->track_peaks.as<TrackPeak>() : nullptr;
+	{ TimedScope ts(E, 4); he = launch_track(T, E->st); }
+	if (he != hipSuccess) return fail(E, FASIM_E_HIP, "track launch failed: %s", hipGetErrorString(he));
+	tf->out->resize(nout); tf->sat->resize((size_t)nu);
+	if (nout) HIPOK(hipMemcpyAsync(tf->out->data(), E->track.p, nout * sizeof(uint16_t), hipMemcpyDeviceToHost, E->st));
+	HIPOK(hipMemcpyAsync(tf->sat->data(), E->track_sat.p, (size_t)nu, hipMemcpyDeviceToHost, E->st));
+	if (npeak) { tf->peaks->resize(npeak); HIPOK(hipMemcpyAsync(tf->peaks->data(), E->track_peaks.p, npeak * sizeof(TrackPeak), hipMemcpyDeviceToHost, E->st)); }
+	return FASIM_OK;
+}
+
+// The two launches of k_sites over the batch's column maxima in E->colmax16, into the host vectors of `sf`.  The copy of the runs
+// completes at the next synchronisation of the stream.
+int run_sites_fold(fasim_engine* E, const UnitBatch& B, const SitesFold* sf)
+{
+	const int nu = B.nunit;
+	int rc; hipError_t he;
+	const size_t ncnt = (size_t)sf->nseg * sf->nchunk * 4;
+	if (E->sites_counts.ensure(ncnt * sizeof(uint32_t)) != hipSuccess || E->sites_offsets.ensure(ncnt * sizeof(uint32_t)) != hipSuccess ||
+		E->sites_sat.ensure((size_t)nu) != hipSuccess) {
+		(void)hipGetLastError();
+		return fail(E, FASIM_E_NOMEM, "sites: no device memory for the run counts of %zu slices", ncnt / 4);
+	}
+	HIPOK(hipMemsetAsync(E->sites_counts.p, 0, ncnt * sizeof(uint32_t), E->st));
+	HIPOK(hipMemsetAsync(E->sites_sat.p, 0, (size_t)nu, E->st));
+	SitesLaunch S;
+	S.colmax16 = E->colmax16.as<uint16_t>(); S.seg_len = E->seg_len.as<int32_t>();
+	S.nseg = sf->nseg; S.nenc = sf->nenc; S.tstride = B.tstride; S.nchunk = sf->nchunk; S.min_value = sf->min_value; S.tab = sf->tab;
+	S.counts = E->sites_counts.as<uint32_t>(); S.offsets = nullptr; S.runs = nullptr; S.sat = E->sites_sat.as<uint8_t>();
+	{ TimedScope ts(E, 4); he = launch_sites(S, false, E->st); }
+	if (he != hipSuccess) return fail(E, FASIM_E_HIP, "sites (count) launch failed: %s", hipGetErrorString(he));
+	std::vector<uint32_t> offs;
+	try { sf->counts->resize(ncnt); sf->sat->resize((size_t)nu); offs.resize(ncnt); } catch (const std::bad_alloc&) { return fail(E, FASIM_E_NOMEM, "out of memory"); }
+	HIPOK(hipMemcpyAsync(sf->counts->data(), E->sites_counts.p, ncnt * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st));
+	HIPOK(hipMemcpyAsync(sf->sat->data(), E->sites_sat.p, (size_t)nu, hipMemcpyDeviceToHost, E->st));
+	HIPOK(hipStreamSynchronize(E->st));
+	uint64_t total = 0;
+	for (size_t k = 0; k < ncnt; k++) { offs[k] = (uint32_t)total; total += (*sf->counts)[k]; }
+	sf->runs->clear();
+	if (total > 0) {
+		if (total > 0x7fffffffull / sizeof(SiteRun)) return fail(E, FASIM_E_NOMEM, "sites: %llu runs in one batch", (unsigned long long)total);
+		if (E->sites_runs.ensure((size_t)total * sizeof(SiteRun)) != hipSuccess) {
+			(void)hipGetLastError();
+			return fail(E, FASIM_E_NOMEM, "sites: no device memory for %llu runs of a batch", (unsigned long long)total);
+		}
+		try { sf->runs->resize((size_t)total); } catch (const std::bad_alloc&) { return fail(E, FASIM_E_NOMEM, "out of memory"); }
+		rc = upload(E, E->sites_offsets, offs.data(), ncnt * sizeof(uint32_t)); if (rc) return rc;
+		S.offsets = E->sites_offsets.as<uint32_t>(); S.runs = E->sites_runs.as<SiteRun>();
+		{ TimedScope ts(E, 4); he = launch_sites(S, true, E->st); }
+		if (he != hipSuccess) return fail(E, FASIM_E_HIP, "sites (emit) launch failed: %s", hipGetErrorString(he));
+		HIPOK(hipMemcpyAsync(sf->runs->data(), E->sites_runs.p, (size_t)total * sizeof(SiteRun), hipMemcpyDeviceToHost, E->st));
+	}
+	return FASIM_OK;
+}
+
 // returns 1 when the query does not fit the kernel (caller falls back to the striped kernels)
 int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& unit_needs_stage1, ScanOut& out,
 	fasim_scan_stats* st, const TrackFold* tf, const RowFold* rf, const SitesFold* sf)
@@ -385,62 +454,13 @@ int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& un
 		// potential tracks (fasim_scan_track): colmax16 holds the main pass of every unit now -- k_scan_post only reads it, but the
 		// checkpoint pass of the chunked hazard re-run below stores its column maxima there again.  The copies complete with the
 		// batch's other results, at the next synchronisation of the stream.
-		rc = upload(E, E->track_phase, tf->phase, sizeof(int32_t) * tf->nseg); if (rc) return rc;
-		const size_t nout = tf->bin >= 1 ? (size_t)tf->nseg * tf->nchunk * 4 * track_slice_stride(tf->bin) : 0;      // (bin == 0: peaks only)
-		const size_t npeak = tf->peaks ? (size_t)tf->nseg * tf->nchunk * 4 : 0;
-		HIPOK(E->track.ensure(nout * sizeof(uint16_t))); HIPOK(E->track_sat.ensure((size_t)nu));
-		if (npeak) HIPOK(E->track_peaks.ensure(npeak * sizeof(TrackPeak)));
-		HIPOK(hipMemsetAsync(E->track_sat.p, 0, (size_t)nu, E->st));
-		TrackLaunch T;
-		T.colmax16 = E->colmax16.as<uint16_t>(); T.seg_len = E->seg_len.as<int32_t>(); T.phase = E->track_phase.as<int32_t>();
-		T.nseg = tf->nseg; T.nenc = tf->nenc; T.tstride = B.tstride; T.nchunk = tf->nchunk; T.bin = tf->bin; T.tab = tf->tab;
-		T.out = E->track.as<uint16_t>(); T.sat = E->track_sat.as<uint8_t>(); T.peaks = npeak ? E->track_peaks.as<TrackPeak>() : nullptr;
-		{ TimedScope ts(E, 4); he = launch_track(T, E->st); }
-		if (he != hipSuccess) return fail(E, FASIM_E_HIP, "track launch failed: %s", hipGetErrorString(he));
-		tf->out->resize(nout); tf->sat->resize((size_t)nu);
-		if (nout) HIPOK(hipMemcpyAsync(tf->out->data(), E->track.p, nout * sizeof(uint16_t), hipMemcpyDeviceToHost, E->st));
-		HIPOK(hipMemcpyAsync(tf->sat->data(), E->track_sat.p, (size_t)nu, hipMemcpyDeviceToHost, E->st));
-		if (npeak) { tf->peaks->resize(npeak); HIPOK(hipMemcpyAsync(tf->peaks->data(), E->track_peaks.p, npeak * sizeof(TrackPeak), hipMemcpyDeviceToHost, E->st)); }
+		rc = run_track_fold(E, B, tf); if (rc) return rc;
 		if (tf->only) { HIPOK(hipStreamSynchronize(E->st)); return FASIM_OK; }      // track only: no hits, no hazard re-run, no stage 3
 	}
 	if (sf) {
 		// sites (fasim_scan_records_sites): the same moment as the tracks, for the same reason.  Two launches of k_sites: the run
 		// counts per (slice, class) come back on this stream, their prefix sum places every slice's runs and sizes the buffer
-		const size_t ncnt = (size_t)sf->nseg * sf->nchunk * 4;
-		if (E->sites_counts.ensure(ncnt * sizeof(uint32_t)) != hipSuccess || E->sites_offsets.ensure(ncnt * sizeof(uint32_t)) != hipSuccess ||
-			E->sites_sat.ensure((size_t)nu) != hipSuccess) {
-			(void)hipGetLastError();
-			return fail(E, FASIM_E_NOMEM, "sites: no device memory for the run counts of %zu slices", ncnt / 4);
-		}
-		HIPOK(hipMemsetAsync(E->sites_counts.p, 0, ncnt * sizeof(uint32_t), E->st));
-		HIPOK(hipMemsetAsync(E->sites_sat.p, 0, (size_t)nu, E->st));
-		SitesLaunch S;
-		S.colmax16 = E->colmax16.as<uint16_t>(); S.seg_len = E->seg_len.as<int32_t>();
-		S.nseg = sf->nseg; S.nenc = sf->nenc; S.tstride = B.tstride; S.nchunk = sf->nchunk; S.min_value = sf->min_value; S.tab = sf->tab;
-		S.counts = E->sites_counts.as<uint32_t>(); S.offsets = nullptr; S.runs = nullptr; S.sat = E->sites_sat.as<uint8_t>();
-		{ TimedScope ts(E, 4); he = launch_sites(S, false, E->st); }
-		if (he != hipSuccess) return fail(E, FASIM_E_HIP, "sites (count) launch failed: %s", hipGetErrorString(he));
-		std::vector<uint32_t> offs;
-		try { sf->counts->resize(ncnt); sf->sat->resize((size_t)nu); offs.resize(ncnt); } catch (const std::bad_alloc&) { return fail(E, FASIM_E_NOMEM, "out of memory"); }
-		HIPOK(hipMemcpyAsync(sf->counts->data(), E->sites_counts.p, ncnt * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st));
-		HIPOK(hipMemcpyAsync(sf->sat->data(), E->sites_sat.p, (size_t)nu, hipMemcpyDeviceToHost, E->st));
-		HIPOK(hipStreamSynchronize(E->st));
-		uint64_t total = 0;
-		for (size_t k = 0; k < ncnt; k++) { offs[k] = (uint32_t)total; total += (*sf->counts)[k]; }
-		sf->runs->clear();
-		if (total > 0) {
-			if (total > 0x7fffffffull / sizeof(SiteRun)) return fail(E, FASIM_E_NOMEM, "sites: %llu runs in one batch", (unsigned long long)total);
-			if (E->sites_runs.ensure((size_t)total * sizeof(SiteRun)) != hipSuccess) {
-				(void)hipGetLastError();
-				return fail(E, FASIM_E_NOMEM, "sites: no device memory for %llu runs of a batch", (unsigned long long)total);
-			}
-			try { sf->runs->resize((size_t)total); } catch (const std::bad_alloc&) { return fail(E, FASIM_E_NOMEM, "out of memory"); }
-			rc = upload(E, E->sites_offsets, offs.data(), ncnt * sizeof(uint32_t)); if (rc) return rc;
-			S.offsets = E->sites_offsets.as<uint32_t>(); S.runs = E->sites_runs.as<SiteRun>();
-			{ TimedScope ts(E, 4); he = launch_sites(S, true, E->st); }
-			if (he != hipSuccess) return fail(E, FASIM_E_HIP, "sites (emit) launch failed: %s", hipGetErrorString(he));
-			HIPOK(hipMemcpyAsync(sf->runs->data(), E->sites_runs.p, (size_t)total * sizeof(SiteRun), hipMemcpyDeviceToHost, E->st));
-		}
+		rc = run_sites_fold(E, B, sf); if (rc) return rc;
 		if (sf->only) { HIPOK(hipStreamSynchronize(E->st)); return FASIM_OK; }      // sites only: no hits, no hazard re-run, no stage 3
 	}
 

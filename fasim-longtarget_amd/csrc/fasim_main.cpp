@@ -36,6 +36,12 @@
 //                           records' sites in record / BED order with the record's name as a ninth column.  --sites-only writes nothing
 //                           else and runs no stage 3.  Exit status 2, nothing written: V outside [1, 16383], a negative G, --sites-gap or
 //                           --sites-only without --sites, --sites with -F, --accumulate-records, --track, --screen or --tfo-profile
+//     --oligos              with --sites V: every record of -f2 is one short oligo of 1 .. 112 nt and the run is a panel scan
+//                           (fasim_scan_oligos): per oligo the sites file that --sites V --sites-only writes for a
+//                           lncRNA of that name, and one panel table <O>/<f2 stem>-<f1 stem>.oligos-<V>.tsv (per oligo: sites, covered bases,
+//                           per class sites and largest value).  Never -TFOsorted / -TFOclass.  Exit status 2, nothing written: without
+//                           --sites, with --sites-align, -F, --track, --screen, --tfo-profile or --accumulate-records, or an -f2
+//                           record that is empty or longer than 112 nt
 //     --sites-align         with --sites V: every site with its hit (fasim_scan_records_sites_aligned), the local
 //                           alignment behind the site's peak: beside the sites file <stem>-TFOsites-<V>-aligned (set mode:
 //                           <O>/<lnc>-<f1 stem>.sites-<V>.aligned.tsv, the record's name as a last column), a `# fasim site hits` line,
@@ -221,7 +227,7 @@ static int g_out_failed = 0;
 // --track: bin width (0: no tracks), smallest value written, --track-only; --screen / --screen-only: peaks (no_stage3: no records)
 // --tfo-profile / --tfo-profile-only: the lncRNA's profile (never together with tracks or peaks)
 // --sites V / --sites-gap G / --sites-only: the sites above a fixed potential (never together with tracks, peaks or the profile)
-struct TrackOpt { int bin = 0, min_value = 1; bool only = false, peaks = false, no_stage3 = false, tfo = false, tfo_only = false; int sites = 0, sites_gap = 0; bool sites_only = false, sites_align = false; };
+struct TrackOpt { int bin = 0, min_value = 1; bool only = false, peaks = false, no_stage3 = false, tfo = false, tfo_only = false; int sites = 0, sites_gap = 0; bool sites_only = false, sites_align = false, oligos = false; };
 
 // acc = max(acc, part) by fasim_tfo_profile_merge; takes `part` over
 static int tfo_fold(fasim_tfo_profile*& acc, fasim_tfo_profile* part)
@@ -343,7 +349,10 @@ static int scan_group(const std::vector<fasim_engine*>& engines, const std::vect
 	auto run = [&](int d) {
 		const int64_t base = nseg / nd, rem = nseg % nd;
 		const int64_t first = d * base + std::min<int64_t>(d, rem), count = base + (d < rem ? 1 : 0);
-		if (sites && hits)
+		if (sites && trk.oligos)
+			rc[(size_t)d] = fasim_scan_oligos(engines[(size_t)d], qp.data(), ql.data(), nq, dna.data(), off.data(), len.data(), nrec, first, count, &p,
+				trk.sites, trk.sites_gap, spart[(size_t)d].data(), 0, nullptr, nullptr);
+		else if (sites && hits)
 			rc[(size_t)d] = fasim_scan_records_sites_aligned(engines[(size_t)d], qp.data(), ql.data(), nq, dna.data(), off.data(), len.data(), nrec, first, count, &p,
 				trk.sites, trk.sites_gap, no_res ? nullptr : part[(size_t)d].data(), spart[(size_t)d].data(), hpart[(size_t)d].data(), nullptr);
 		else if (sites)
@@ -480,7 +489,7 @@ int main(int argc, char* const* argv)
 		{ "track", required_argument, NULL, 1009 }, { "track-min", required_argument, NULL, 1010 }, { "track-only", no_argument, NULL, 1011 },
 		{ "screen", no_argument, NULL, 1012 }, { "screen-only", no_argument, NULL, 1013 },
 		{ "tfo-profile", no_argument, NULL, 1014 }, { "tfo-profile-only", no_argument, NULL, 1015 },
-		{ "sites", required_argument, NULL, 1016 }, { "sites-gap", required_argument, NULL, 1017 }, { "sites-only", no_argument, NULL, 1018 }, { "sites-align", no_argument, NULL, 1019 }, { 0, 0, 0, 0 } };
+		{ "sites", required_argument, NULL, 1016 }, { "sites-gap", required_argument, NULL, 1017 }, { "sites-only", no_argument, NULL, 1018 }, { "sites-align", no_argument, NULL, 1019 }, { "oligos", no_argument, NULL, 1020 }, { 0, 0, 0, 0 } };
 	int opt;
 	while ((opt = getopt_long_only(argc, argv, optstring, lo, NULL)) != -1) {
 		switch (opt) {
@@ -522,7 +531,8 @@ int main(int argc, char* const* argv)
 		case 1017: sites_gap_given = true; trk.sites_gap = strict_int(optarg, -1); break;
 		case 1018: trk.sites_only = true; break;
 		case 1019: trk.sites_align = true; break;
-		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only] [--sites-align]]\n"); return 2;
+		case 1020: trk.oligos = true; break;
+		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only] [--sites-align] [--oligos]]\n"); return 2;
 		}
 	}
 	if (all_records && accumulate) { fprintf(stderr, "fasim: --all-records and --accumulate-records exclude each other\n"); return 2; }
@@ -540,6 +550,9 @@ int main(int argc, char* const* argv)
 	if (sites && (trk.sites < 1 || trk.sites > 16383)) { fprintf(stderr, "fasim: --sites needs an integer in [1, 16383]\n"); return 2; }
 	if (sites && trk.sites_gap < 0) { fprintf(stderr, "fasim: --sites-gap needs an integer of at least 0\n"); return 2; }
 	if (sites && (p.classicSim || accumulate || track || screen || trk.tfo)) { fprintf(stderr, "fasim: --sites is not available with -F, --accumulate-records, --track, --screen or --tfo-profile\n"); return 2; }
+	if (trk.oligos && !sites) { fprintf(stderr, "fasim: --oligos needs --sites V\n"); return 2; }
+	if (trk.oligos && (trk.sites_align || trk.tfo)) { fprintf(stderr, "fasim: --oligos is not available with --sites-align, -F, --track, --screen, --tfo-profile or --accumulate-records\n"); return 2; }
+	if (trk.oligos) trk.sites_only = true;      // a panel has no triplex records: the sites files and the panel table are all it writes
 	if (!sites) trk.sites = 0;
 	trk.peaks = screen; trk.no_stage3 = screen_only || trk.only || trk.tfo_only || trk.sites_only;
 	// --regions: the BED file is read and checked before anything else happens (a bad file writes nothing)
@@ -553,6 +566,10 @@ int main(int argc, char* const* argv)
 	reader.upper = upper; reader.sticky_fields = accumulate;
 	if (!reader.open(f1)) { fprintf(stderr, "fasim: cannot read DNA file %s\n", f1.c_str()); return 1; }
 	if (!read_rnas(f2, rnas)) { fprintf(stderr, "fasim: cannot read RNA file %s\n", f2.c_str()); return 1; }
+	if (trk.oligos) for (const Rna& r : rnas) if (r.seq.empty() || r.seq.size() > (size_t)FASIM_MAX_OLIGO) {
+		fprintf(stderr, "fasim: --oligos: record '%s' in %s has %zu nt: an oligo has 1 to %d nt (longer queries: --sites without --oligos)\n", r.name.c_str(), f2.c_str(), r.seq.size(), FASIM_MAX_OLIGO);
+		return 2;
+	}
 	for (const Rna& r : rnas) if (r.seq.empty()) { fprintf(stderr, "fasim: empty RNA record '%s' in %s\n", r.name.c_str(), f2.c_str()); return 1; }
 	for (const Rna& r : rnas) if (r.seq.size() > (size_t)FASIM_MAX_QUERY) {
 		fprintf(stderr, "fasim: RNA record '%s' in %s is %zu nt long, which exceeds the limit of %d nt: above it the reference's 16-bit "
@@ -644,9 +661,23 @@ int main(int argc, char* const* argv)
 		}
 		return bad;
 	};
+	// --oligos: the site lists of every oligo and record are kept for the panel table, <O>/<f2 stem>-<f1 stem>.oligos-<V>.tsv
+	std::vector<std::vector<fasim_sites*>> panel_sites(trk.oligos ? rnas.size() : 0);
+	auto write_panel = [&]() -> int {
+		const size_t nq = rnas.size(), nr = nq ? panel_sites[0].size() : 0;
+		std::vector<const char*> names(nq); std::vector<int32_t> lens(nq); std::vector<const fasim_sites*> flat;
+		for (size_t q = 0; q < nq; q++) { names[q] = rnas[q].name.c_str(); lens[q] = (int32_t)rnas[q].seq.size(); flat.insert(flat.end(), panel_sites[q].begin(), panel_sites[q].end()); }
+		char* text = nullptr; int64_t len = 0;
+		if (fasim_oligo_panel_tsv(names.data(), lens.data(), (int32_t)nq, flat.data(), (int32_t)nr, &text, &len) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
+		const int bad = write_file(outdir + "/" + f2.substr(0, f2.size() >= 3 ? f2.size() - 3 : 0) + "-" + base + ".oligos-" + std::to_string(trk.sites) + ".tsv", text, len);
+		fasim_free(text);
+		for (auto& v : panel_sites) { for (fasim_sites* x : v) fasim_sites_free(x); v.clear(); }
+		return bad;
+	};
 	if (regions && nreg == 0) {
 		if (tfo_set && write_tfo_set()) return 1;
 		if (sites_set && write_sites_set()) return 1;
+		if (trk.oligos && write_panel()) return 1;
 		if (!screen_only && !trk.tfo_only && !trk.sites_only && write_index()) return 1;
 		if (screen && write_screen()) return 1;
 		std::cout << "finished normally" << std::endl;
@@ -743,7 +774,8 @@ int main(int argc, char* const* argv)
 						fasim_free(text);
 						fasim_site_hits_free(ht[q]);
 					}
-					fasim_sites_free(st[q]);
+					if (trk.oligos) panel_sites[q].push_back(st[q]);
+					else fasim_sites_free(st[q]);
 				}
 				if (trk.sites_only) return;
 			}
@@ -939,6 +971,7 @@ int main(int argc, char* const* argv)
 		if (screen && write_screen()) return 1;
 		if (tfo_set && write_tfo_set()) return 1;
 		if (sites_set && write_sites_set()) return 1;
+		if (trk.oligos && write_panel()) return 1;
 		if (regions) {
 			if (!screen_only && !trk.tfo_only && !trk.sites_only && write_index()) return 1;
 			std::vector<std::string> lost;

@@ -148,6 +148,20 @@ struct SitesLaunch {
 };
 hipError_t launch_sites(const SitesLaunch& L, bool emit, hipStream_t st);
 
+// ---- scan_short.hip: column maxima of a short oligo ----------------------------------------------------
+constexpr int SCAN_SHORT_MAX = 112;        // longest oligo k_scan_short takes (FASIM_MAX_OLIGO)
+// W(m): the alignments that decide a column maximum start at most this many columns before it
+int scan_short_warmup(int m);
+struct ScanShortLaunch {
+	const uint8_t* tcodes; const int32_t* unit_len; int32_t nunit, tstride;      // as ScanLaunch: units 0 .. nunit - 1, tstride a multiple of 16
+	const uint8_t* qcodes; int32_t m;          // the oligo's codes of the stage-2 alphabet, 1 <= m <= SCAN_SHORT_MAX
+	int32_t stretch, npairs, warm;             // columns per stretch, stretch pairs per unit, warm-up columns: from scan_short_shape
+	uint16_t* colmax16;                        // [unit][tstride] = 2 * column maximum (taint bit 0) for columns < unit_len; the others are 0 or not written
+};
+// stretch length (a multiple of 16, >= warm), pairs per unit (2 * npairs * stretch >= tstride) and warm-up (W(m) rounded up to 16)
+void scan_short_shape(int m, int tstride, int nunit, int* stretch, int* npairs, int* warm);
+hipError_t launch_scan_short(const ScanShortLaunch& L, hipStream_t st);      // hipErrorInvalidValue: a shape the kernel does not take
+
 // ---- site_align.hip: the textbook local alignment behind a site's peak -----------------------------------
 // One problem: a unit (its target codes at tcodes + tbase, n columns), the column jp of the site's peak and the peak's value.
 struct SiteAlignProb { int64_t tbase; int32_t n, jp, value, pad; };

@@ -426,6 +426,35 @@ int  fasim_site_hits_merge(const fasim_sites* const* sites, const fasim_site_hit
 int  fasim_site_hits_tsv(const fasim_sites* s, const fasim_site_hits* h, const char* chr, int64_t start_genome, const char* rna_name,
                          const char* record_name /* NULL: 15 columns */, int32_t header, char** text, int64_t* text_len);
 void fasim_site_hits_free(fasim_site_hits* h);
+/* ---- panels of short oligos (csrc/scan_short.hip) ----------------------------------------------------------- */
+/* Sites and potential tracks of a panel of nq triplex-forming oligos of 1 .. FASIM_MAX_OLIGO nt against one record set.  The
+ * potential of an oligo is that of section 11 with the oligo in the lncRNA's place (plain Gotoh, +5 / -4, every non-ACGT letter -4,
+ * U read as A, gap 16 then 4, floored at 0, zero-score pad rows up to 16 * ceil(len / 16)); records are cut, numbered, sharded
+ * (seg_first, seg_count) and same-letter segments skipped exactly as in fasim_scan_records_sites, and dna == NULL with nrec == 1,
+ * rec_off == NULL and rec_len == NULL is the whole resident buffer.  out_sites[q * nrec + r] (wanted iff out_sites != NULL) is the
+ * fasim_sites that section 14 defines for oligo q and record r under min_value and max_gap: it merges with fasim_sites_merge and
+ * prints with fasim_sites_bed.  out_tracks[q * nrec + r] (wanted iff out_tracks != NULL) is the fasim_track of width `bin` of record r
+ * scanned alone against oligo q: it merges with fasim_track_merge.  totals[q] (may be NULL): segments, skipped segments, units and
+ * cells of oligo q; the kernel times of the call are shared evenly among the oligos.  No triplex records are made (no stage 3), the
+ * engine's own query (fasim_set_query) is neither used nor changed, and the results depend on the oligo, the record and the
+ * parameters only (not on the panel's order, batches, workers, shards, resident or streamed DNA).
+ * Refusals, all before any GPU work, the engine stays usable: nq < 1, an empty oligo or one above FASIM_MAX_OLIGO nt (the message
+ * names it and points to fasim_scan_records_sites), both outputs NULL, min_value outside [1, 16383] or max_gap < 0 when sites are
+ * wanted, bin < 1 when tracks are wanted, and the record refusals of fasim_scan_records give FASIM_E_ARG; classicSim gives
+ * FASIM_E_UNSUPPORTED. */
+#define FASIM_MAX_OLIGO 112
+int  fasim_scan_oligos(fasim_engine* e, const char* const* oligos, const int32_t* lens, int32_t nq,
+                       const char* dna, const int64_t* rec_off, const int64_t* rec_len, int32_t nrec,
+                       int64_t seg_first, int64_t seg_count, const fasim_params* p,
+                       int32_t min_value, int32_t max_gap, fasim_sites** out_sites /* [nq * nrec] or NULL */,
+                       int32_t bin, fasim_track** out_tracks /* [nq * nrec] or NULL; bin >= 1 */,
+                       fasim_scan_stats* totals /* [nq], may be NULL */);
+/* The panel table `fasim --oligos --sites V` writes: the line of column names, then one tab-separated line per oligo in panel order:
+ * oligo length total_sites covered_bases, then for ParaPlus ParaMinus AntiMinus AntiPlus each <Class>_sites <Class>_max.  sites is
+ * [nq * nrec] as fasim_scan_oligos fills it; the counts and covered_bases (the sum of end - start) are sums over all records and, for
+ * the first two, classes, <Class>_max the largest site value of the class over all records, 0 without a site (nrec == 0: all zeros).  Free with fasim_free. */
+int  fasim_oligo_panel_tsv(const char* const* names, const int32_t* lens, int32_t nq, const fasim_sites* const* sites, int32_t nrec,
+                           char** text, int64_t* text_len);
 
 /* Host half of the path's one exchange step: concatenates the records of `nparts` shards in the
  * order given and rebases their pool offsets.  Shards are contiguous segment ranges, so rank order IS the
