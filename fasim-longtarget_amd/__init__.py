@@ -131,6 +131,21 @@ class _SiteHits(C.Structure):
                 ("pool_len", C.c_int64), ("unaligned", C.c_int64)]
 
 
+class _HistEdge(C.Structure):
+    _fields_ = [("record", C.c_int32), ("side", C.c_int32), ("boundary", C.c_int64), ("len", C.c_int32), ("reserved", C.c_int32),
+                ("v", C.POINTER(C.c_uint16))]
+
+
+class _Hist(C.Structure):
+    _fields_ = [("n", C.POINTER(C.c_int64) * 4), ("positions", C.c_int64), ("units", C.c_int64), ("saturated_units", C.c_int64),
+                ("npending", C.c_int64), ("pending", C.POINTER(_HistEdge))]
+
+
+# FASIM_HIST_BINS (include/fasim_hip.h): values of a potential histogram; HIST_LDS_BINS (csrc/kernels.h): values below it are counted
+# in k_hist's workgroup histogram first
+HIST_BINS = 16384
+HIST_LDS_BINS = 1024
+
 TRACK_CLASSES = ("ParaPlus", "ParaMinus", "AntiMinus", "AntiPlus")
 
 EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_ex", "fasim_engine_destroy", "fasim_last_error", "fasim_set_option", "fasim_set_query",
@@ -144,6 +159,8 @@ EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_e
            "fasim_scan_records_sites", "fasim_sites_merge", "fasim_sites_bed", "fasim_sites_free",
            "fasim_scan_records_sites_aligned", "fasim_site_hits_merge", "fasim_site_hits_tsv", "fasim_site_hits_free",
            "fasim_scan_oligos", "fasim_oligo_panel_tsv",
+           "fasim_scan_records_hist", "fasim_scan_oligos_hist", "fasim_hist_merge", "fasim_hist_free", "fasim_shuffle_query",
+           "fasim_hist_threshold", "fasim_hist_tsv",
            # the reference's own ssw.h ABI (include/ssw.h)
            "ssw_init", "init_destroy", "ssw_pre_align", "ssw_align", "align_destroy", "encoded_ops"]
 
@@ -264,6 +281,21 @@ def lib():
                                     C.POINTER(ScanStats)]
     L.fasim_oligo_panel_tsv.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.POINTER(_Sites)), C.c_int32,
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.fasim_scan_records_hist.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int64, C.c_int64,
+                                          C.POINTER(Params), C.POINTER(C.POINTER(_Result)), C.POINTER(C.POINTER(_Hist)),
+                                          C.POINTER(ScanStats)]
+    L.fasim_scan_oligos_hist.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
+                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int64, C.c_int64,
+                                         C.POINTER(Params), C.POINTER(C.POINTER(_Hist)), C.POINTER(ScanStats)]
+    L.fasim_hist_merge.argtypes = [C.POINTER(C.POINTER(_Hist)), C.c_int32, C.POINTER(C.POINTER(_Hist))]
+    L.fasim_hist_free.argtypes = [C.POINTER(_Hist)]
+    L.fasim_hist_free.restype = None
+    L.fasim_shuffle_query.argtypes = [C.c_char_p, C.c_int32, C.c_uint64, C.c_int32, C.c_char_p]
+    L.fasim_hist_threshold.argtypes = [C.POINTER(_Hist), C.POINTER(C.POINTER(_Hist)), C.c_int32, C.c_double]
+    L.fasim_hist_threshold.restype = C.c_int32
+    L.fasim_hist_tsv.argtypes = [C.POINTER(_Hist), C.POINTER(C.POINTER(_Hist)), C.c_int32, C.c_uint64, C.c_double, C.c_char_p,
+                                 C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     _lib = L
     return L
 
@@ -431,6 +463,145 @@ def track_bedgraph(track: Track, chr_name: str, start_genome: int, dna_len: int,
                                 C.byref(text), C.byref(n))
     if rc != 0:
         raise FasimError(f"fasim_track_bedgraph failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
+    try:
+        return C.string_at(text, n.value)
+    finally:
+        L.fasim_free(text)
+
+
+class Hist:
+    """Histogram of the per-base potential of one lncRNA (or oligo, or shuffled control) over a record set (struct fasim_hist):
+    per strand class (TRACK_CLASSES) and value v in [0, 16383] the number of covered positions whose potential is v.  Either a
+    native histogram (what scan_hist(), scan_oligos_hist() and merge_hists() return) or one made from a (4, 16384) array:
+    `Hist(counts, positions=None, units=0, saturated_units=0, pending=())`, positions defaulting to the sum of class 0 and
+    `pending` a list of (record, boundary, side, values) with values a (4, len) array."""
+
+    def __init__(self, counts=None, positions=None, units: int = 0, saturated_units: int = 0, pending=(), _native=None):
+        self._native = _native
+        self._keep = None
+        if _native is None:
+            import numpy as np
+            a = np.ascontiguousarray(counts, dtype=np.int64)
+            if a.shape != (4, HIST_BINS):
+                raise FasimError(f"a histogram is a (4, {HIST_BINS}) array", E_ARG)
+            t = _Hist()
+            t.positions = int(a[0].sum()) if positions is None else positions
+            t.units, t.saturated_units = units, saturated_units
+            for c in range(4):
+                t.n[c] = C.cast(a[c].ctypes.data, C.POINTER(C.c_int64))
+            pend = sorted(((int(r), int(b), int(sd), np.ascontiguousarray(v, dtype=np.uint16)) for r, b, sd, v in pending),
+                          key=lambda e: e[:3])
+            edges = (_HistEdge * max(1, len(pend)))()
+            for k, (r, b, sd, v) in enumerate(pend):
+                if v.ndim != 2 or v.shape[0] != 4:
+                    raise FasimError("the values of a pending edge are a (4, len) array", E_ARG)
+                edges[k].record, edges[k].boundary, edges[k].side, edges[k].len = r, b, sd, v.shape[1]
+                edges[k].v = C.cast(v.ctypes.data, C.POINTER(C.c_uint16))
+            t.npending, t.pending = len(pend), C.cast(edges, C.POINTER(_HistEdge))
+            self._keep = (a, t, pend, edges)
+
+    def __del__(self):
+        try:
+            if self._native is not None:
+                lib().fasim_hist_free(self._native)
+                self._native = None
+        except Exception:
+            pass
+
+    def pointer(self):
+        """POINTER(fasim_hist) for the C-ABI; valid while this object lives."""
+        return self._native if self._native is not None else C.pointer(self._keep[1])
+
+    @property
+    def _t(self):
+        return self._native.contents if self._native is not None else self._keep[1]
+
+    @property
+    def positions(self) -> int:
+        return int(self._t.positions)
+
+    @property
+    def units(self) -> int:
+        return int(self._t.units)
+
+    @property
+    def saturated_units(self) -> int:
+        return int(self._t.saturated_units)
+
+    @property
+    def pending(self):
+        """[(record, boundary, side, values)]: the boundaries whose other segment lay outside the call's range, ordered; values is
+        a (4, len) uint16 array (a copy) of the potential of this range at the positions of the overlap."""
+        import numpy as np
+        t = self._t
+        out = []
+        for k in range(int(t.npending)):
+            e = t.pending[k]
+            v = np.zeros((4, e.len), dtype=np.uint16)
+            if e.len:
+                C.memmove(v.ctypes.data, e.v, 2 * 4 * e.len)
+            out.append((int(e.record), int(e.boundary), int(e.side), v))
+        return out
+
+    def array(self):
+        """(4, 16384) numpy int64 array (a copy), rows in TRACK_CLASSES order."""
+        import numpy as np
+        out = np.zeros((4, HIST_BINS), dtype=np.int64)
+        for c in range(4):
+            C.memmove(out[c].ctypes.data, self._t.n[c], 8 * HIST_BINS)
+        return out
+
+
+def merge_hists(parts) -> Hist:
+    """The histogram of a record set from those of its shards (fasim_hist_merge): counts are summed, and where both sides of a
+    boundary are pending the positions of the overlap are counted once with the maximum of the two."""
+    L = lib()
+    parts = list(parts)
+    arr = (C.POINTER(_Hist) * max(1, len(parts)))(*[t.pointer() for t in parts])
+    out = C.POINTER(_Hist)()
+    rc = L.fasim_hist_merge(arr, len(parts), C.byref(out))
+    if rc != 0:
+        raise FasimError(f"fasim_hist_merge failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
+    return Hist(_native=out)
+
+
+def shuffle_query(rna: bytes, seed: int, k: int) -> bytes:
+    """Control k (1-based) of a query under `seed` (fasim_shuffle_query): a Fisher-Yates shuffle of its bytes, splitmix64."""
+    L = lib()
+    rna = bytes(rna)
+    out = C.create_string_buffer(max(1, len(rna)))
+    rc = L.fasim_shuffle_query(rna, len(rna), seed & 0xFFFFFFFFFFFFFFFF, k, out)
+    if rc != 0:
+        raise FasimError(f"fasim_shuffle_query failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
+    return out.raw[:len(rna)]
+
+
+def _hist_ptrs(controls):
+    controls = list(controls)
+    return controls, (C.POINTER(_Hist) * max(1, len(controls)))(*[t.pointer() for t in controls])
+
+
+def hist_threshold(real: Hist, controls=(), fdr: float = 0.05) -> int:
+    """The smallest potential from which on the controls reach at most `fdr` times what the query reaches, per control
+    (fasim_hist_threshold); 0 when there is none.  What `fasim --potential-hist` reports as min_value."""
+    L = lib()
+    controls, arr = _hist_ptrs(controls)
+    v = L.fasim_hist_threshold(real.pointer(), arr, len(controls), fdr)
+    if v < 0:
+        raise FasimError(f"fasim_hist_threshold failed ({v}): {L.fasim_last_error(None).decode()}", v)
+    return int(v)
+
+
+def hist_tsv(real: Hist, rna_name: str, controls=(), seed: int = 0, fdr: float = 0.05) -> bytes:
+    """The table of `fasim --potential-hist` (fasim_hist_tsv): per value the counts and the counts at or above it per class and,
+    with controls, those of the controls and the false discovery rate."""
+    L = lib()
+    controls, arr = _hist_ptrs(controls)
+    text = C.c_void_p()
+    n = C.c_int64()
+    rc = L.fasim_hist_tsv(real.pointer(), arr, len(controls), seed & 0xFFFFFFFFFFFFFFFF, fdr, rna_name.encode(), C.byref(text), C.byref(n))
+    if rc != 0:
+        raise FasimError(f"fasim_hist_tsv failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
     try:
         return C.string_at(text, n.value)
     finally:
@@ -948,6 +1119,7 @@ class Engine:
             raise FasimError(f"fasim_engine_create({device}) failed ({rc}): {self._L.fasim_last_error(None).decode()}")
         self._h = h
         self.m = 0
+        self.rna = None                   # the query as last given to set_query() (scan_hist() shuffles it for its controls)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -970,6 +1142,7 @@ class Engine:
     def set_query(self, rna: bytes):
         self._check(self._L.fasim_set_query(self._h, rna, len(rna)))
         self.m = len(rna)
+        self.rna = bytes(rna)
 
     def maximum3_f16(self, a, b, c):
         """v_pk_maximum3_f16 on numpy uint32 arrays of packed f16 pairs: (maximum3(a, b, c), maximum3(a, b, +0))."""
@@ -1275,6 +1448,94 @@ class Engine:
         if trks is None:
             return sites
         return sites, [[Track(_native=trks[q * nrec + r]) for r in range(nrec)] for q in range(nq)]
+
+    def scan_hist(self, dnas, params: Params | None = None, controls: int = 0, seed: int = 0, records: bool = False, seg_first: int = 0,
+                  seg_count: int = -1, rnas=None):
+        """Histogram of the potential over a record set, with shuffled controls (fasim_scan_records_hist): `(results | None, hist,
+        control_hists)`.  `dnas` as for scan_sites().  rnas None: the query last given to set_query(); hist is one
+        Hist over the whole set and control_hists the Hists of shuffle_query(rna, seed, k), k = 1 .. controls, scanned as plain
+        queries of the same call.  rnas given: lists per lncRNA of those.  records True: stage 3 runs and results is what
+        scan_records() returns for the lncRNA (not for its controls).  Shards of a segment range merge with merge_hists()."""
+        p = params or default_params()
+        if isinstance(dnas, (bytes, bytearray)):
+            dnas = [bytes(dnas)]
+        if dnas is None:
+            blob, offs, lens, nrec = None, None, None, 1        # the whole resident buffer: the engine knows its length
+        else:
+            blob = b"".join(dnas)
+            nrec = len(dnas)
+            offs = (C.c_int64 * max(1, nrec))()
+            lens = (C.c_int64 * max(1, nrec))()
+            o = 0
+            for i, d in enumerate(dnas):
+                offs[i], lens[i] = o, len(d)
+                o += len(d)
+        if controls < 0:
+            raise FasimError(f"scan_hist: controls = {controls} is negative", E_ARG)
+        if rnas is None and getattr(self, "rna", None) is None:
+            raise FasimError("scan_hist: no query set: call set_query() first", E_ARG)
+        base = [self.rna] if rnas is None else [bytes(r) for r in rnas]
+        nb = len(base)
+        ctl = [shuffle_query(r, seed, k + 1) for r in base for k in range(controls)]
+
+        def call(qs, want_records):
+            nq = len(qs)
+            arr = (C.c_char_p * max(1, nq))(*qs)
+            qlens = (C.c_int32 * max(1, nq))(*[len(r) for r in qs])
+            outs = (C.POINTER(_Result) * (max(1, nq) * max(1, nrec)))() if want_records else None
+            hs = (C.POINTER(_Hist) * max(1, nq))()
+            totals = (ScanStats * max(1, nq))()
+            self._check(self._L.fasim_scan_records_hist(self._h, arr, qlens, nq, blob, offs, lens, nrec, seg_first, seg_count, C.byref(p),
+                                                        outs, hs, totals))
+            res = None
+            if want_records:
+                res = [[ScanResult(stats=self._stats_dict(outs[q * nrec + r].contents.stats), _native=outs[q * nrec + r])
+                        for r in range(nrec)] for q in range(nq)]
+            return res, [Hist(_native=hs[q]) for q in range(nq)], [self._stats_dict(totals[q]) for q in range(nq)]
+
+        if records:
+            # stage 3 for the lncRNAs only: their controls go in a histogram-only call of their own
+            res, hists, totals = call(base, True)
+            chists = call(ctl, False)[1] if ctl else []
+        else:
+            res, allh, totals = call(base + ctl, False)
+            hists, chists, totals = allh[:nb], allh[nb:], totals[:nb]
+        if ctl:
+            self._check(self._L.fasim_set_query(self._h, base[-1], len(base[-1])))      # (a call leaves the engine on its last query)
+        self.rna, self.m = base[-1], len(base[-1])
+        self.last_totals = totals
+        chists = [chists[q * controls:(q + 1) * controls] for q in range(nb)]
+        if rnas is None:
+            return (res[0] if res else None), hists[0], chists[0]
+        return res, hists, chists
+
+    def scan_oligos_hist(self, oligos, dnas, params: Params | None = None, seg_first: int = 0, seg_count: int = -1):
+        """Histograms of the potential of a panel of short oligos (fasim_scan_oligos_hist): one Hist per oligo over the record set,
+        what scan_hist() would give for a lncRNA with the oligo in its place.  `dnas` as for scan_oligos()."""
+        p = params or default_params()
+        if isinstance(dnas, (bytes, bytearray)):
+            dnas = [bytes(dnas)]
+        if dnas is None:
+            blob, offs, lens, nrec = None, None, None, 1
+        else:
+            blob = b"".join(dnas)
+            nrec = len(dnas)
+            offs = (C.c_int64 * max(1, nrec))()
+            lens = (C.c_int64 * max(1, nrec))()
+            o = 0
+            for i, d in enumerate(dnas):
+                offs[i], lens[i] = o, len(d)
+                o += len(d)
+        oligos = [bytes(x) for x in oligos]
+        nq = len(oligos)
+        arr = (C.c_char_p * max(1, nq))(*oligos)
+        qlens = (C.c_int32 * max(1, nq))(*[len(x) for x in oligos])
+        hs = (C.POINTER(_Hist) * max(1, nq))()
+        totals = (ScanStats * max(1, nq))()
+        self._check(self._L.fasim_scan_oligos_hist(self._h, arr, qlens, nq, blob, offs, lens, nrec, seg_first, seg_count, C.byref(p),
+                                                   hs, totals))
+        self.last_totals = [self._stats_dict(totals[q]) for q in range(nq)]
+        return [Hist(_native=hs[q]) for q in range(nq)]
 
     def _records_track(self, blob, offs, lens, nrec, p, rnas, bin, records, seg_first, seg_count):
         nq = 0 if rnas is None else len(rnas)

@@ -98,7 +98,7 @@ void fasim_engine_destroy(fasim_engine* e)
 		&e->qsim, &e->sim_min, &e->sim_row, &e->sim_ev, &e->sim_cnt, &e->sim_nodes,
 		&e->ublk, &e->btarget, &e->bidx, &e->bcounts, &e->blist[0], &e->blist[1], &e->blist[2], &e->bslots[0], &e->bslots[1], &e->bslots[2],
 		&e->bprev, &e->lane_ub, &e->fzones, &e->fubslot, &e->bdec, &e->btab, &e->swin, &e->unit_ovf, &e->track, &e->track_phase, &e->track_sat, &e->track_peaks, &e->sites_counts, &e->sites_offsets, &e->sites_runs, &e->sites_sat, &e->sa_q, &e->sa_tcodes, &e->sa_probs, &e->sa_ends, &e->sa_rows, &e->sa_items, &e->sa_dirs, &e->sa_cigar, &e->sa_ciglen,
-		&e->rowmax16, &e->row_out, &e->row_gfirst, &e->row_sat, &e->oligo_q };
+		&e->rowmax16, &e->row_out, &e->row_gfirst, &e->row_sat, &e->oligo_q, &e->hist, &e->hist_zone, &e->hist_zones, &e->hist_sat };
 	for (auto& t : e->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
 	for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
 	for (DevBuf* b : bufs) b->release();
@@ -455,7 +455,8 @@ int fasim_scan_queries(fasim_engine* E, const char* const* rnas, const int32_t* 
 }
 
 // argument checks of fasim_scan_records (and fasim_scan_records_track), before any GPU work
-static int check_records_args(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
+}      // (shared with engine_hist.cpp: C++ linkage, declared in engine.h)
+int check_records_args(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, const fasim_params* pp)
 {
 	if (nrec < 1) return fail(E, FASIM_E_ARG, "a record set needs at least one record (nrec = %d)", nrec);
@@ -482,6 +483,7 @@ static int check_records_args(fasim_engine* E, const char* const* rnas, const in
 	}
 	return FASIM_OK;
 }
+extern "C" {
 
 int fasim_scan_records(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
@@ -516,7 +518,8 @@ void fasim_track_free(fasim_track* t)
 }
 
 // the potential is the column maxima of the systolic scan kernel: no other kernel leaves them
-static int check_track_source(fasim_engine* E, const int32_t* rna_lens, int32_t nq, const fasim_params* pp, const char* what = "potential tracks")
+}      // (shared with engine_hist.cpp: C++ linkage, declared in engine.h)
+int check_track_source(fasim_engine* E, const int32_t* rna_lens, int32_t nq, const fasim_params* pp, const char* what)
 {
 	for (int q = 0; q < std::max(1, nq); q++) {
 		const int len = nq == 0 ? E->m : rna_lens[q];
@@ -526,6 +529,7 @@ static int check_track_source(fasim_engine* E, const int32_t* rna_lens, int32_t 
 	if (pp->classicSim) return fail(E, FASIM_E_UNSUPPORTED, "%s are not available with classicSim (-F): that path has no stage-2 column maxima", what);
 	return FASIM_OK;
 }
+extern "C" {
 
 int fasim_scan_track(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna, int64_t dna_len,
 	int64_t seg_first, int64_t seg_count, const fasim_params* pp, int32_t bin, fasim_result** out_results, fasim_track** out_tracks)

@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <map>
 #include <memory>
 #include <string>
 #include <condition_variable>
@@ -135,6 +136,7 @@ struct fasim_engine {
 	DevBuf track_peaks;                          // fasim_scan_records_track only: k_track's peak per slice and class
 	DevBuf sites_counts, sites_offsets, sites_runs, sites_sat;   // fasim_scan_records_sites only: k_sites' run counts per (slice, class), their prefix sum, the runs and saturation flags of the batch
 	DevBuf sa_q, sa_tcodes, sa_probs, sa_ends, sa_rows, sa_items, sa_dirs, sa_cigar, sa_ciglen;   // fasim_scan_records_sites_aligned only: query codes, the chunk's units, problems, end cells, row state of long queries, path items, direction bytes, CIGARs
+	DevBuf hist, hist_zone, hist_zones, hist_sat;   // fasim_scan_records_hist only: k_hist's counters of the batch, its zone bounds per segment, the zone values and saturation flags
 	DevBuf oligo_q;                              // fasim_scan_oligos only: the panel's query codes, FASIM_MAX_OLIGO bytes per oligo
 	DevBuf rowmax16, row_out, row_gfirst, row_sat;   // fasim_scan_tfo_profile only: k_scan's row maxima of the batch, k_rowfold's groups, result and saturation flags
 	int opt_numa = 1;                            // option "numa_affinity": pin the scan's host threads to the GPU's NUMA node (no-op on one node)
@@ -459,8 +461,42 @@ struct SitesFold {
 	std::vector<uint8_t>* sat = nullptr;         // [unit]
 };
 
+// ---- histogram of the potential (fasim_scan_records_hist, hist.hip, engine_hist.cpp) ---------------------------------------------
+// One side of the overlap of two neighbouring segments of a record, as the values of that segment alone: boundary b of a record is
+// the overlap of its segments b and b + 1, side 0 the tail zone of segment b, side 1 the head zone of segment b + 1.  An empty `v`
+// stands for zeros (a segment that same_seq() skips).
+struct HistSide { int32_t len = 0; std::vector<uint16_t> v; /* [4][len] */ };
+struct HistEdgeKey {
+	int32_t rec; int64_t boundary; int32_t side;
+	bool operator<(const HistEdgeKey& o) const { return rec != o.rec ? rec < o.rec : boundary != o.boundary ? boundary < o.boundary : side < o.side; }
+};
+// One call: per query the counters of the fasim_hist the call returns, and the zone sides that wait for their partner (the other
+// batch, or the merge of the shards when the partner lies outside the call's range).  The workers add under the query's mutex.
+struct HistReq {
+	bool only = false;                           // no stage 3, no records
+	int64_t step = 0, overlap = 0;               // cutLength - overlapLength, overlapLength
+	std::vector<int64_t> rec_nseg;               // [record]: segments of the whole record
+	std::vector<int32_t> qtop;                   // [query]: largest value the query can reach (the copy back stops there)
+	std::vector<int64_t*> n;                     // [query * 4 + class][HIST_BINS]
+	std::vector<int64_t> positions, units, sat;  // [query]
+	std::vector<std::map<HistEdgeKey, HistSide>> open;      // [query]: sides whose partner has not arrived
+	std::vector<std::vector<std::pair<HistEdgeKey, HistSide>>> pending;   // [query]: sides whose partner lies outside the call's range
+	std::unique_ptr<std::mutex[]> mu;            // [query]
+};
+// One batch, handed to run_scan_v2: the zone bounds of its kept segments and where k_hist's result goes
+struct HistFold {
+	int nseg = 0, nenc = 0, nchunk = 0, zstride = 0, top = HIST_BINS - 1; bool only = false;
+	TrackTable tab;
+	const int32_t* zone = nullptr;               // [nseg][2] host
+	std::vector<uint32_t>* hist = nullptr;       // [4][top + 1]
+	std::vector<uint16_t>* zones = nullptr;      // [nseg][2][4][zstride]
+	std::vector<uint8_t>* sat = nullptr;         // [unit]
+};
+
 struct BatchCtx {
 	UnitBatch B;
+	std::vector<uint32_t> hist; std::vector<uint16_t> hist_zones; std::vector<uint8_t> hist_sat; std::vector<int32_t> hist_zone;      // fasim_scan_records_hist: k_hist's counters and zones of this batch
+	int hist_zstride = 0, hist_top = 0; bool hist_done = false;
 	std::vector<uint32_t> site_counts; std::vector<SiteRun> site_runs; std::vector<uint8_t> site_sat; bool sites_done = false;      // fasim_scan_records_sites: k_sites' runs of this batch
 	std::vector<uint16_t> rowfold; std::vector<uint8_t> row_sat; std::vector<int32_t> row_gfirst;      // fasim_scan_tfo_profile: k_rowfold's groups of this batch
 	bool rows_done = false;
@@ -492,7 +528,7 @@ int prep_striped_window(fasim_engine* E, StripedMode mode, bool word, StripedLau
 int run_stage1(fasim_engine* E, const UnitBatch& B, std::vector<int>& score, int64_t* word_reruns);
 int run_stage2(fasim_engine* E, const UnitBatch& B);
 int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& unit_needs_stage1, ScanOut& out, fasim_scan_stats* st, const TrackFold* tf = nullptr,
-	const RowFold* rf = nullptr, const SitesFold* sf = nullptr);
+	const RowFold* rf = nullptr, const SitesFold* sf = nullptr, const HistFold* hf = nullptr);
 int load_raw_targets(fasim_engine* E, const char* targets, const int64_t* offsets, const int32_t* lens, int nprob, bool stage1, UnitBatch& B);
 int need_query(fasim_engine* E);
 int run_align(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb>& W, std::vector<AlignResult>& out, std::vector<uint32_t>& cigars, fasim_scan_stats* stats);
@@ -500,13 +536,23 @@ int run_align_v2(fasim_engine* E, const UnitBatch& B, const std::vector<WindowPr
 int stage3_range(fasim_engine* E, BatchCtx& C, int ua, int ub, fasim_scan_stats& st);
 int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_t* dna_dev, int64_t b0, int64_t b1,
 	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st, const TrackReq* tr = nullptr,
-	const TfoReq* pr = nullptr, const SitesReq* sr = nullptr);
+	const TfoReq* pr = nullptr, const SitesReq* sr = nullptr, const HistReq* hr = nullptr, int q = 0);
 // the head of a batch (segments kept, DNA staged, k_encode) and the folds and host merges behind a batch's column maxima in
 // E->colmax16, shared by scan_batch / run_scan_v2 and fasim_scan_oligos (engine_oligos.cpp)
 int batch_encode(fasim_engine* E, const char* dna, const SegTable& T, const uint8_t* dna_dev, int64_t b0, int64_t b1,
 	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st, int64_t m);
 int run_track_fold(fasim_engine* E, const UnitBatch& B, const TrackFold* tf);
 int run_sites_fold(fasim_engine* E, const UnitBatch& B, const SitesFold* sf);
+int run_hist_fold(fasim_engine* E, const UnitBatch& B, const HistFold* hf);
+// engine_hist.cpp: the zone bounds of a batch's kept segments into C.hist_zone and the fold that points at C's vectors; the batch's
+// counters, zones and skipped segments [b0, b1) of the call's segment table into the arrays of query q
+void hist_prepare(BatchCtx& C, const HistReq& hr, const TrackTable& tab, int q, HistFold& hf);
+void merge_hist(const BatchCtx& C, const SegTable& T, int64_t b0, int64_t b1, HistReq& hr, int q);
+bool hist_req_init(HistReq& hr, fasim_hist** out_hists, int nquery, const int32_t* qlens, const int64_t* rec_len, int nrec, const fasim_params& p, bool only);
+int hist_req_finish(fasim_engine* E, HistReq& hr, fasim_hist** out_hists, int nquery);
+int check_records_args(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
+	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, const fasim_params* pp);
+int check_track_source(fasim_engine* E, const int32_t* rna_lens, int32_t nq, const fasim_params* pp, const char* what = "potential tracks");
 void merge_track(const BatchCtx& C, TrackReq& tr, int q);
 void merge_site_runs(const BatchCtx& C, SitesReq& sr, int q);
 int sim_forward_units(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, const int32_t* unit_len_dev, const int32_t* unit_len_host,
@@ -522,4 +568,4 @@ TrackTable class_table(const std::vector<int>& encs);
 // buffer); outs[q * nrec + r], totals[q] (may be NULL)
 int scan_records_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
-	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr = nullptr, TfoReq* pr = nullptr, SitesReq* sr = nullptr);
+	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr = nullptr, TfoReq* pr = nullptr, SitesReq* sr = nullptr, HistReq* hr = nullptr);

@@ -37,10 +37,11 @@ struct PanelCall {
 	std::vector<uint8_t> codes;                  // [oligo][FASIM_MAX_OLIGO], stage-2 alphabet
 	const fasim_params* p = nullptr; const std::vector<int>* encs = nullptr;
 	SitesReq* sr = nullptr; TrackReq* tr = nullptr;
+	HistReq* hr = nullptr; const SegTable* T = nullptr;      // fasim_scan_oligos_hist: the request and the call's segment table
 };
 
 // one batch on one worker: `C` comes from batch_encode, the batch's target codes are in w->tcodes
-int panel_batch(fasim_engine* E, const PanelCall& P, BatchCtx& C)
+int panel_batch(fasim_engine* E, const PanelCall& P, BatchCtx& C, int64_t b0, int64_t b1)
 {
 	const UnitBatch& B = C.B;
 	const int nseg = C.nseg, nenc = C.nenc;
@@ -72,20 +73,23 @@ int panel_batch(fasim_engine* E, const PanelCall& P, BatchCtx& C)
 			tf.phase = phase.data(); tf.out = &C.track; tf.sat = &C.track_sat; tf.peaks = nullptr;
 			const int rc = run_track_fold(E, B, &tf); if (rc) return rc;
 		}
+		if (P.hr) {
+			HistFold hf;
+			hist_prepare(C, *P.hr, tab, q, hf);
+			const int rc = run_hist_fold(E, B, &hf); if (rc) return rc;
+		}
 		HIPOK(hipStreamSynchronize(E->st));      // the folds' copies are complete; colmax16 is free for the next oligo
+		if (P.hr) { try { merge_hist(C, *P.T, b0, b1, *P.hr, q); } catch (const std::bad_alloc&) { return fail(E, FASIM_E_NOMEM, "out of memory"); } }
 		if (P.sr) { try { merge_site_runs(C, *P.sr, q); } catch (const std::bad_alloc&) { return fail(E, FASIM_E_NOMEM, "out of memory"); } }
 		if (P.tr) merge_track(C, *P.tr, q);
 	}
 	return FASIM_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-int fasim_scan_oligos(fasim_engine* E, const char* const* oligos, const int32_t* lens, int32_t nq, const char* dna,
+// fasim_scan_oligos and fasim_scan_oligos_hist: sites, tracks and histograms (out_hists[q]) are each wanted iff their output is given
+int scan_oligos_core(fasim_engine* E, const char* const* oligos, const int32_t* lens, int32_t nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
-	int32_t min_value, int32_t max_gap, fasim_sites** out_sites, int32_t bin, fasim_track** out_tracks, fasim_scan_stats* totals)
+	int32_t min_value, int32_t max_gap, fasim_sites** out_sites, int32_t bin, fasim_track** out_tracks, fasim_hist** out_hists, fasim_scan_stats* totals)
 {
 	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
 	if (nq < 1) return fail(E, FASIM_E_ARG, "a panel needs at least one oligo (nq = %d)", nq);
@@ -95,7 +99,7 @@ int fasim_scan_oligos(fasim_engine* E, const char* const* oligos, const int32_t*
 		if (lens[q] > FASIM_MAX_OLIGO)
 			return fail(E, FASIM_E_ARG, "oligo %d has %d nt, a panel takes oligos of at most %d nt: scan longer queries with fasim_scan_records_sites", q, lens[q], FASIM_MAX_OLIGO);
 	}
-	if (!out_sites && !out_tracks) return fail(E, FASIM_E_ARG, "neither sites nor tracks are wanted");
+	if (!out_sites && !out_tracks && !out_hists) return fail(E, FASIM_E_ARG, "neither sites nor tracks are wanted");
 	if (out_sites && (min_value < 1 || min_value > 16383)) return fail(E, FASIM_E_ARG, "oligos: min_value %d lies outside [1, 16383]", min_value);
 	if (out_sites && max_gap < 0) return fail(E, FASIM_E_ARG, "oligos: max_gap %d is negative", max_gap);
 	if (out_tracks && bin < 1) return fail(E, FASIM_E_ARG, "oligos: track bin width %d: must be at least 1", bin);
@@ -120,11 +124,14 @@ int fasim_scan_oligos(fasim_engine* E, const char* const* oligos, const int32_t*
 		}
 	}
 	if (pp->classicSim) return fail(E, FASIM_E_UNSUPPORTED, "oligo panels are not available with classicSim (-F): that path has no stage-2 column maxima");
+	if (out_hists && 2 * (int64_t)pp->overlapLength > (int64_t)pp->cutLength)
+		return fail(E, FASIM_E_UNSUPPORTED, "histograms of the potential need overlapLength (%d) of at most half of cutLength (%d): a base would lie in three segments", pp->overlapLength, pp->cutLength);
 	if (resident) dna = E->dna_host.data();
 	const fasim_params p = *pp;
 	const size_t nout = (size_t)nq * (size_t)nrec;
 	if (out_sites) for (size_t o = 0; o < nout; o++) out_sites[o] = nullptr;
 	if (out_tracks) for (size_t o = 0; o < nout; o++) out_tracks[o] = nullptr;
+	if (out_hists) for (int q = 0; q < nq; q++) out_hists[q] = nullptr;
 	HIPOK(hipSetDevice(E->device));
 	const double t_begin = now_s();
 	AffinityScope numa(E->device, E->opt_numa != 0);
@@ -164,7 +171,9 @@ int fasim_scan_oligos(fasim_engine* E, const char* const* oligos, const int32_t*
 		sr.runs.resize(nout); sr.sat.assign(nout, 0); sr.mu.reset(new std::mutex[(size_t)nq]);
 		P.sr = &sr;
 	}
+	HistReq hr;
 	auto drop = [&]() {
+		if (out_hists) for (int q = 0; q < nq; q++) { fasim_hist_free(out_hists[q]); out_hists[q] = nullptr; }
 		if (out_sites) for (size_t o = 0; o < nout; o++) { fasim_sites_free(out_sites[o]); out_sites[o] = nullptr; }
 		if (out_tracks) for (size_t o = 0; o < nout; o++) { fasim_track_free(out_tracks[o]); out_tracks[o] = nullptr; }
 	};
@@ -179,6 +188,13 @@ int fasim_scan_oligos(fasim_engine* E, const char* const* oligos, const int32_t*
 			for (int c = 0; c < FASIM_TRACK_CLASSES; c++) tr.v.push_back(out_tracks[o]->v[c]);
 		}
 		P.tr = &tr;
+	}
+
+	if (out_hists) {
+		bool ok = false;
+		try { ok = hist_req_init(hr, out_hists, nq, lens, rec_len, nrec, p, true); } catch (const std::bad_alloc&) { ok = false; }
+		if (!ok) { for (int q = 0; q < nq; q++) out_hists[q] = nullptr; drop(); return fail(E, FASIM_E_NOMEM, "out of memory"); }
+		P.hr = &hr; P.T = &T;
 	}
 
 	std::vector<int64_t> rec_units((size_t)nrec, 0);      // units scanned per record (the same for every oligo)
@@ -235,7 +251,11 @@ int fasim_scan_oligos(fasim_engine* E, const char* const* oligos, const int32_t*
 				if (c >= chunks.size() || wrc[wi]) break;
 				BatchCtx ctx;
 				int r = batch_encode(w, dna, T, dna_dev, chunks[c].first, chunks[c].second, p, encs, tstride, ctx, ist[c], msum);
-				if (!r && ctx.nseg > 0) r = panel_batch(w, P, ctx);
+				if (!r && ctx.nseg > 0) r = panel_batch(w, P, ctx, chunks[c].first, chunks[c].second);
+				else if (!r && P.hr) {
+					// (a batch whose segments are all skipped still has positions to count: they lie in bin 0)
+					try { for (int q = 0; q < nq; q++) merge_hist(ctx, T, chunks[c].first, chunks[c].second, hr, q); } catch (const std::bad_alloc&) { r = fail(w, FASIM_E_NOMEM, "out of memory"); }
+				}
 				(void)hipStreamSynchronize(w->st);
 				drain_timed(w);
 				for (int k = 0; k < FASIM_KERNEL_FAMILIES; k++) { ist[c].kernel_ms[k] = w->kernel_ms[k]; ist[c].kernel_launches[k] = w->kernel_launches[k]; w->kernel_ms[k] = 0; w->kernel_launches[k] = 0; }
@@ -272,6 +292,11 @@ int fasim_scan_oligos(fasim_engine* E, const char* const* oligos, const int32_t*
 		} catch (const std::bad_alloc&) { drop(); return fail(E, FASIM_E_NOMEM, "out of memory"); }
 	}
 	if (out_tracks) for (size_t o = 0; o < nout; o++) { out_tracks[o]->units = rec_units[o % (size_t)nrec]; out_tracks[o]->saturated_units = tr.sat[o]; }
+	if (out_hists) {
+		int rc;
+		try { rc = hist_req_finish(E, hr, out_hists, nq); } catch (const std::bad_alloc&) { rc = fail(E, FASIM_E_NOMEM, "out of memory"); }
+		if (rc) { drop(); return rc; }
+	}
 	if (totals) {
 		const double t_total = now_s() - t_begin;
 		for (int q = 0; q < nq; q++) {
@@ -284,6 +309,26 @@ int fasim_scan_oligos(fasim_engine* E, const char* const* oligos, const int32_t*
 		}
 	}
 	return FASIM_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int fasim_scan_oligos(fasim_engine* E, const char* const* oligos, const int32_t* lens, int32_t nq, const char* dna,
+	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
+	int32_t min_value, int32_t max_gap, fasim_sites** out_sites, int32_t bin, fasim_track** out_tracks, fasim_scan_stats* totals)
+{
+	return scan_oligos_core(E, oligos, lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, min_value, max_gap, out_sites, bin, out_tracks, nullptr, totals);
+}
+
+int fasim_scan_oligos_hist(fasim_engine* E, const char* const* oligos, const int32_t* lens, int32_t nq, const char* dna,
+	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
+	fasim_hist** out_hists, fasim_scan_stats* totals)
+{
+	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
+	if (!out_hists) return fail(E, FASIM_E_ARG, "bad arguments");
+	return scan_oligos_core(E, oligos, lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, 1, 0, nullptr, 1, nullptr, out_hists, totals);
 }
 
 int fasim_oligo_panel_tsv(const char* const* names, const int32_t* lens, int32_t nq, const fasim_sites* const* sites, int32_t nrec,

@@ -353,12 +353,12 @@ int batch_encode(fasim_engine* E, const char* dna, const SegTable& T, const uint
 // host buffer.  The kernels take int32 segment starts relative to the batch's own first byte on the device, so a record set
 // longer than 2^31 nt works as long as one batch's span does.
 int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_t* dna_dev, int64_t b0, int64_t b1,
-	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st, const TrackReq* tr, const TfoReq* pr, const SitesReq* sr)
+	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st, const TrackReq* tr, const TfoReq* pr, const SitesReq* sr, const HistReq* hr, int q)
 {
 	int rc = FASIM_OK;
 	const int64_t step = p.cutLength - p.overlapLength;
 	const int nenc = (int)encs.size();
-	C.B = UnitBatch(); C.tstride = tstride; C.nenc = nenc; C.nseg = 0; C.step = step; C.dna = dna; C.p = &p; C.encs = &encs; C.stage3_done = false; C.track_done = false; C.rows_done = false; C.sites_done = false;
+	C.B = UnitBatch(); C.tstride = tstride; C.nenc = nenc; C.nseg = 0; C.step = step; C.dna = dna; C.p = &p; C.encs = &encs; C.stage3_done = false; C.track_done = false; C.rows_done = false; C.sites_done = false; C.hist_done = false;
 	C.per_unit.clear(); C.ucand.clear(); C.ualign.clear();
 	rc = batch_encode(E, dna, T, dna_dev, b0, b1, p, encs, tstride, C, st, E->m); if (rc) return rc;
 	if (!C.nseg) return FASIM_OK;
@@ -418,9 +418,11 @@ int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_
 				sf.tab = class_table(encs);
 				sf.counts = &C.site_counts; sf.runs = &C.site_runs; sf.sat = &C.site_sat;
 			}
-			rc = run_scan_v2(E, B, need1, so, &st, tr ? &tf : nullptr, pr ? &rf : nullptr, sr ? &sf : nullptr);
+			HistFold hf;
+			if (hr) { C.track_nchunk = track_chunks(p.cutLength); hist_prepare(C, *hr, class_table(encs), q, hf); }
+			rc = run_scan_v2(E, B, need1, so, &st, tr ? &tf : nullptr, pr ? &rf : nullptr, sr ? &sf : nullptr, hr ? &hf : nullptr);
 			if (rc < 0) return rc;
-			if (rc == 0) { C.sites_done = sr != nullptr; hoff.swap(so.hit_off); hcnt.swap(so.hit_cnt); thr.swap(so.thr); hits.swap(so.hits); done_v2 = true; C.track_done = tr != nullptr; C.rows_done = pr != nullptr; C.row_gfirst.swap(rf.gfirst); }
+			if (rc == 0) { C.sites_done = sr != nullptr; C.hist_done = hr != nullptr; hoff.swap(so.hit_off); hcnt.swap(so.hit_cnt); thr.swap(so.thr); hits.swap(so.hits); done_v2 = true; C.track_done = tr != nullptr; C.rows_done = pr != nullptr; C.row_gfirst.swap(rf.gfirst); }
 		}
 		st.t_stage2_s += now_s() - t0;
 		if (!done_v2) {
@@ -718,7 +720,7 @@ static void add_stats(fasim_scan_stats& st, const fasim_scan_stats& x)
 // whole call's stats.  `records` true: outs[q * nrec + r] carries the per-record stats, totals[q] (if given) the call's.
 static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int nrec, bool records, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
-	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr = nullptr, TfoReq* pr = nullptr, SitesReq* sr = nullptr)
+	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr = nullptr, TfoReq* pr = nullptr, SitesReq* sr = nullptr, HistReq* hr = nullptr)
 {
 	const bool resident = (dna == nullptr);
 	if (resident) dna = E->dna_host.data();
@@ -916,7 +918,7 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 					r = fasim_set_query(w, rq.data(), (int)rq.size());
 					if (r && w != E) w->err = std::string("worker set_query failed: ") + w->err;
 				}
-				if (!r) r = scan_batch(w, dna, T, dna_dev, itx.b0, itx.b1, p, encs, tstride, ctx, ist[c], tr, pr, sr);
+				if (!r) r = scan_batch(w, dna, T, dna_dev, itx.b0, itx.b1, p, encs, tstride, ctx, ist[c], tr, pr, sr, hr, itx.q);
 				if (!r && pr && ctx.B.nunit > 0) {
 					if (!ctx.rows_done) r = fail(w, FASIM_E_UNSUPPORTED, "the lncRNA's profile needs the systolic scan kernel");
 					else { merge_rows(ctx, *pr, itx.q); std::vector<uint16_t>().swap(ctx.rowfold); }
@@ -932,7 +934,15 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 						std::vector<SiteRun>().swap(ctx.site_runs);
 					}
 				}
-				if (!r && ctx.B.nunit > 0 && !ctx.stage3_done && !(tr && tr->only) && !(pr && pr->only) && !(sr && sr->only)) r = stage3_range(w, ctx, 0, ctx.B.nunit, ist[c]);
+				if (!r && hr) {
+					// (a batch whose segments are all skipped still has positions to count: they lie in bin 0)
+					if (ctx.B.nunit > 0 && !ctx.hist_done) r = fail(w, FASIM_E_UNSUPPORTED, "the histogram of the potential needs the systolic scan kernel");
+					else {
+						try { merge_hist(ctx, T, itx.b0, itx.b1, *hr, itx.q); } catch (const std::bad_alloc&) { r = fail(w, FASIM_E_NOMEM, "out of memory"); }
+						std::vector<uint16_t>().swap(ctx.hist_zones);
+					}
+				}
+				if (!r && ctx.B.nunit > 0 && !ctx.stage3_done && !(tr && tr->only) && !(pr && pr->only) && !(sr && sr->only) && !(hr && hr->only)) r = stage3_range(w, ctx, 0, ctx.B.nunit, ist[c]);
 				(void)hipStreamSynchronize(w->st);
 				drain_timed(w);
 				for (int k = 0; k < FASIM_KERNEL_FAMILIES; k++) { ist[c].kernel_ms[k] = w->kernel_ms[k]; ist[c].kernel_launches[k] = w->kernel_launches[k]; w->kernel_ms[k] = 0; w->kernel_launches[k] = 0; }
@@ -1040,7 +1050,7 @@ int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens,
 
 int scan_records_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
-	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr, TfoReq* pr, SitesReq* sr)
+	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr, TfoReq* pr, SitesReq* sr, HistReq* hr)
 {
-	return scan_set(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, true, seg_first, seg_count, pp, outs, totals, tr, pr, sr);
+	return scan_set(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, true, seg_first, seg_count, pp, outs, totals, tr, pr, sr, hr);
 }

@@ -328,9 +328,39 @@ int run_sites_fold(fasim_engine* E, const UnitBatch& B, const SitesFold* sf)
 	return FASIM_OK;
 }
 
+// k_hist over the batch's column maxima in E->colmax16, into the host vectors of `hf`: the counters of the values 0 .. hf->top per
+// class, the zone values and the saturation flags.  The copies complete at the next synchronisation of the stream.
+int run_hist_fold(fasim_engine* E, const UnitBatch& B, const HistFold* hf)
+{
+	const int nu = B.nunit;
+	int rc; hipError_t he;
+	const size_t nzone = (size_t)hf->nseg * 8 * (size_t)hf->zstride;
+	const size_t ntop = (size_t)std::min(hf->top, HIST_BINS - 1) + 1;
+	if (E->hist.ensure((size_t)4 * HIST_BINS * sizeof(uint32_t)) != hipSuccess || E->hist_zones.ensure(std::max<size_t>(1, nzone) * sizeof(uint16_t)) != hipSuccess ||
+		E->hist_sat.ensure((size_t)nu) != hipSuccess) {
+		(void)hipGetLastError();
+		return fail(E, FASIM_E_NOMEM, "histogram: no device memory for the counters and %zu zone values of a batch", nzone);
+	}
+	rc = upload(E, E->hist_zone, hf->zone, sizeof(int32_t) * 2 * (size_t)hf->nseg); if (rc) return rc;
+	HIPOK(hipMemsetAsync(E->hist.p, 0, (size_t)4 * HIST_BINS * sizeof(uint32_t), E->st));
+	HIPOK(hipMemsetAsync(E->hist_sat.p, 0, (size_t)nu, E->st));
+	HistLaunch H;
+	H.colmax16 = E->colmax16.as<uint16_t>(); H.seg_len = E->seg_len.as<int32_t>(); H.zone = E->hist_zone.as<int32_t>();
+	H.nseg = hf->nseg; H.nenc = hf->nenc; H.tstride = B.tstride; H.nchunk = hf->nchunk; H.zstride = hf->zstride; H.tab = hf->tab;
+	H.hist = E->hist.as<uint32_t>(); H.zones = E->hist_zones.as<uint16_t>(); H.sat = E->hist_sat.as<uint8_t>();
+	{ TimedScope ts(E, 4); he = launch_hist(H, E->st); }
+	if (he != hipSuccess) return fail(E, FASIM_E_HIP, "hist launch failed: %s", hipGetErrorString(he));
+	try { hf->hist->resize(4 * ntop); hf->zones->resize(nzone); hf->sat->resize((size_t)nu); } catch (const std::bad_alloc&) { return fail(E, FASIM_E_NOMEM, "out of memory"); }
+	for (int c = 0; c < 4; c++)
+		HIPOK(hipMemcpyAsync(hf->hist->data() + (size_t)c * ntop, E->hist.as<uint32_t>() + (size_t)c * HIST_BINS, ntop * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st));
+	if (nzone) HIPOK(hipMemcpyAsync(hf->zones->data(), E->hist_zones.p, nzone * sizeof(uint16_t), hipMemcpyDeviceToHost, E->st));
+	HIPOK(hipMemcpyAsync(hf->sat->data(), E->hist_sat.p, (size_t)nu, hipMemcpyDeviceToHost, E->st));
+	return FASIM_OK;
+}
+
 // returns 1 when the query does not fit the kernel (caller falls back to the striped kernels)
 int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& unit_needs_stage1, ScanOut& out,
-	fasim_scan_stats* st, const TrackFold* tf, const RowFold* rf, const SitesFold* sf)
+	fasim_scan_stats* st, const TrackFold* tf, const RowFold* rf, const SitesFold* sf, const HistFold* hf)
 {
 	const int nu = B.nunit;
 	HIPOK(E->colmax16.ensure((size_t)nu * B.tstride * sizeof(uint16_t)));
@@ -462,6 +492,11 @@ int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& un
 		// counts per (slice, class) come back on this stream, their prefix sum places every slice's runs and sizes the buffer
 		rc = run_sites_fold(E, B, sf); if (rc) return rc;
 		if (sf->only) { HIPOK(hipStreamSynchronize(E->st)); return FASIM_OK; }      // sites only: no hits, no hazard re-run, no stage 3
+	}
+	if (hf) {
+		// histogram of the potential (fasim_scan_records_hist): the same moment as the tracks, for the same reason
+		rc = run_hist_fold(E, B, hf); if (rc) return rc;
+		if (hf->only) { HIPOK(hipStreamSynchronize(E->st)); return FASIM_OK; }      // histogram only: no hits, no hazard re-run, no stage 3
 	}
 
 	HIPOK(E->hit_off.ensure(sizeof(int32_t) * nu)); HIPOK(E->hit_cnt.ensure(sizeof(int32_t) * nu));

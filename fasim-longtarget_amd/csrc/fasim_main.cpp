@@ -42,6 +42,15 @@
 //                           per class sites and largest value).  Never -TFOsorted / -TFOclass.  Exit status 2, nothing written: without
 //                           --sites, with --sites-align, -F, --track, --screen, --tfo-profile or --accumulate-records, or an -f2
 //                           record that is empty or longer than 112 nt
+//     --potential-hist      histogram of the potential with shuffled controls (fasim_scan_records_hist): per
+//                           strand class and value how many bases of the DNA reach it.  --hist-controls K (default 0) scans K
+//                           composition-preserving shuffles of every lncRNA too (--hist-seed S, default 0) and reports the false discovery
+//                           rate per value and the smallest value that keeps it at or below --hist-fdr Q (default 0.05) as min_value, a
+//                           defensible V for --sites.  A plain run writes <stem>-TFOhist next to -TFOsorted; with --all-records or
+//                           --regions one table per lncRNA over the whole set, <O>/<lnc>-<f1 stem>.hist.tsv; with --oligos one such table
+//                           per oligo and nothing else.  --potential-hist-only writes nothing else and runs no stage 3.  Exit status 2,
+//                           nothing written: with -F, --accumulate-records, --track, --screen, --tfo-profile or --sites, --hist-* or
+//                           --potential-hist-only without --potential-hist, K < 0, Q outside (0, 1], -o above half of -c
 //     --sites-align         with --sites V: every site with its hit (fasim_scan_records_sites_aligned), the local
 //                           alignment behind the site's peak: beside the sites file <stem>-TFOsites-<V>-aligned (set mode:
 //                           <O>/<lnc>-<f1 stem>.sites-<V>.aligned.tsv, the record's name as a last column), a `# fasim site hits` line,
@@ -227,7 +236,23 @@ static int g_out_failed = 0;
 // --track: bin width (0: no tracks), smallest value written, --track-only; --screen / --screen-only: peaks (no_stage3: no records)
 // --tfo-profile / --tfo-profile-only: the lncRNA's profile (never together with tracks or peaks)
 // --sites V / --sites-gap G / --sites-only: the sites above a fixed potential (never together with tracks, peaks or the profile)
-struct TrackOpt { int bin = 0, min_value = 1; bool only = false, peaks = false, no_stage3 = false, tfo = false, tfo_only = false; int sites = 0, sites_gap = 0; bool sites_only = false, sites_align = false, oligos = false; };
+struct TrackOpt { int bin = 0, min_value = 1; bool only = false, peaks = false, no_stage3 = false, tfo = false, tfo_only = false; int sites = 0, sites_gap = 0; bool sites_only = false, sites_align = false, oligos = false;
+	// --potential-hist: the histogram, K controls per lncRNA under a seed (hist_ctl: their sequences, lncRNA after lncRNA), the FDR bound
+	bool hist = false, hist_only = false; int hist_controls = 0; uint64_t hist_seed = 0; double hist_fdr = 0.05; const std::vector<std::string>* hist_ctl = nullptr; };
+
+// acc += part by fasim_hist_merge (different groups of records: nothing pairs); takes `part` over
+static int hist_fold(fasim_hist*& acc, fasim_hist* part)
+{
+	if (!acc) { acc = part; return 0; }
+	const fasim_hist* two[2] = { acc, part };
+	fasim_hist* sum = nullptr;
+	const int rc = fasim_hist_merge(two, 2, &sum);
+	fasim_hist_free(part);
+	if (rc != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
+	fasim_hist_free(acc);
+	acc = sum;
+	return 0;
+}
 
 // acc = max(acc, part) by fasim_tfo_profile_merge; takes `part` over
 static int tfo_fold(fasim_tfo_profile*& acc, fasim_tfo_profile* part)
@@ -321,9 +346,19 @@ static int scan_record(const std::vector<fasim_engine*>& engines, const std::vec
 static int scan_group(const std::vector<fasim_engine*>& engines, const std::vector<Rna>& rnas, const std::string& dna,
 	const std::vector<int64_t>& off, const std::vector<int64_t>& len, const fasim_params& p, std::vector<std::vector<fasim_result*>>& out,
 	const TrackOpt& trk, std::vector<std::vector<fasim_track*>>& tracks, std::vector<fasim_peak>& peaks, std::vector<fasim_tfo_profile*>* profs = nullptr,
-	std::vector<std::vector<fasim_sites*>>* sites = nullptr, std::vector<std::vector<fasim_site_hits*>>* hits = nullptr)
+	std::vector<std::vector<fasim_sites*>>* sites = nullptr, std::vector<std::vector<fasim_site_hits*>>* hits = nullptr,
+	std::vector<fasim_hist*>* hists = nullptr)
 {
 	const int nd = (int)engines.size(), nq = (int)rnas.size(), nrec = (int)off.size();
+	// --potential-hist: one histogram per lncRNA over the group, then those of its controls ([nq] + [nq * K], as hist_ctl)
+	const int nctl = hists && trk.hist_ctl ? (int)trk.hist_ctl->size() : 0;
+	std::vector<const char*> hq; std::vector<int32_t> hl;
+	if (hists) {
+		for (int q = 0; q < nq; q++) { hq.push_back(rnas[(size_t)q].seq.data()); hl.push_back((int32_t)rnas[(size_t)q].seq.size()); }
+		for (int k = 0; k < nctl; k++) { hq.push_back((*trk.hist_ctl)[(size_t)k].data()); hl.push_back((int32_t)(*trk.hist_ctl)[(size_t)k].size()); }
+		hists->assign((size_t)(nq + nctl), nullptr);
+	}
+	std::vector<std::vector<fasim_hist*>> gpart((size_t)nd, std::vector<fasim_hist*>(hists ? (size_t)(nq + nctl) : 0, nullptr));
 	std::vector<const char*> qp((size_t)nq); std::vector<int32_t> ql((size_t)nq);
 	for (int q = 0; q < nq; q++) { qp[(size_t)q] = rnas[(size_t)q].seq.data(); ql[(size_t)q] = (int32_t)rnas[(size_t)q].seq.size(); }
 	int64_t nseg = 0;
@@ -349,7 +384,21 @@ static int scan_group(const std::vector<fasim_engine*>& engines, const std::vect
 	auto run = [&](int d) {
 		const int64_t base = nseg / nd, rem = nseg % nd;
 		const int64_t first = d * base + std::min<int64_t>(d, rem), count = base + (d < rem ? 1 : 0);
-		if (sites && trk.oligos)
+		if (hists && trk.oligos)
+			rc[(size_t)d] = fasim_scan_oligos_hist(engines[(size_t)d], hq.data(), hl.data(), nq + nctl, dna.data(), off.data(), len.data(), nrec, first, count, &p,
+				gpart[(size_t)d].data(), nullptr);
+		else if (hists && no_res)
+			rc[(size_t)d] = fasim_scan_records_hist(engines[(size_t)d], hq.data(), hl.data(), nq + nctl, dna.data(), off.data(), len.data(), nrec, first, count, &p,
+				nullptr, gpart[(size_t)d].data(), nullptr);
+		else if (hists) {
+			// stage 3 for the lncRNAs only: their controls go in a histogram-only call of their own
+			rc[(size_t)d] = fasim_scan_records_hist(engines[(size_t)d], qp.data(), ql.data(), nq, dna.data(), off.data(), len.data(), nrec, first, count, &p,
+				part[(size_t)d].data(), gpart[(size_t)d].data(), nullptr);
+			if (rc[(size_t)d] == FASIM_OK && nctl)
+				rc[(size_t)d] = fasim_scan_records_hist(engines[(size_t)d], hq.data() + nq, hl.data() + nq, nctl, dna.data(), off.data(), len.data(), nrec, first, count, &p,
+					nullptr, gpart[(size_t)d].data() + nq, nullptr);
+		}
+		else if (sites && trk.oligos)
 			rc[(size_t)d] = fasim_scan_oligos(engines[(size_t)d], qp.data(), ql.data(), nq, dna.data(), off.data(), len.data(), nrec, first, count, &p,
 				trk.sites, trk.sites_gap, spart[(size_t)d].data(), 0, nullptr, nullptr);
 		else if (sites && hits)
@@ -411,6 +460,15 @@ static int scan_group(const std::vector<fasim_engine*>& engines, const std::vect
 		for (int d = 0; d < nd; d++) fp[(size_t)d] = fpart[(size_t)d][(size_t)q];
 		if (fasim_tfo_profile_merge(fp.data(), nd, &(*profs)[(size_t)q]) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); bad = 1; }
 	}
+	// histograms of the device shards: sums, the overlaps at the shard boundaries counted once
+	for (size_t k = 0; hists && !bad && k < hists->size(); k++) {
+		if (nd == 1) { (*hists)[k] = gpart[0][k]; gpart[0][k] = nullptr; continue; }
+		std::vector<const fasim_hist*> hp((size_t)nd);
+		for (int d = 0; d < nd; d++) hp[(size_t)d] = gpart[(size_t)d][k];
+		if (fasim_hist_merge(hp.data(), nd, &(*hists)[k]) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); bad = 1; }
+	}
+	for (auto& v : gpart) for (fasim_hist* x : v) fasim_hist_free(x);
+	if (bad && hists) for (fasim_hist*& x : *hists) { fasim_hist_free(x); x = nullptr; }
 	// site lists of the device shards: union of the intervals, joined again
 	for (int q = 0; q < nq && !bad && sites; q++) for (int r = 0; r < nrec && !bad; r++) {
 		const size_t k = (size_t)q * nrec + r;
@@ -475,7 +533,7 @@ int main(int argc, char* const* argv)
 	std::string f1 = "./", f2 = "./", outdir = "./", bed_path;
 	std::vector<int> devices(1, 0);
 	bool stats = false, all_records = false, accumulate = false, upper = false, track = false, screen = false, screen_only = false;
-	bool sites = false, sites_gap_given = false;
+	bool sites = false, sites_gap_given = false, hist_arg_given = false, hist_arg_bad = false;
 	TrackOpt trk;
 	int tail_flags = 0;
 	const char* optstring = "f:s:r:O:c:m:t:i:S:z:Y:Z:h:C:D:E:o:y:Fd";
@@ -489,7 +547,9 @@ int main(int argc, char* const* argv)
 		{ "track", required_argument, NULL, 1009 }, { "track-min", required_argument, NULL, 1010 }, { "track-only", no_argument, NULL, 1011 },
 		{ "screen", no_argument, NULL, 1012 }, { "screen-only", no_argument, NULL, 1013 },
 		{ "tfo-profile", no_argument, NULL, 1014 }, { "tfo-profile-only", no_argument, NULL, 1015 },
-		{ "sites", required_argument, NULL, 1016 }, { "sites-gap", required_argument, NULL, 1017 }, { "sites-only", no_argument, NULL, 1018 }, { "sites-align", no_argument, NULL, 1019 }, { "oligos", no_argument, NULL, 1020 }, { 0, 0, 0, 0 } };
+		{ "sites", required_argument, NULL, 1016 }, { "sites-gap", required_argument, NULL, 1017 }, { "sites-only", no_argument, NULL, 1018 }, { "sites-align", no_argument, NULL, 1019 }, { "oligos", no_argument, NULL, 1020 },
+		{ "potential-hist", no_argument, NULL, 1021 }, { "hist-controls", required_argument, NULL, 1022 }, { "hist-seed", required_argument, NULL, 1023 },
+		{ "hist-fdr", required_argument, NULL, 1024 }, { "potential-hist-only", no_argument, NULL, 1025 }, { 0, 0, 0, 0 } };
 	int opt;
 	while ((opt = getopt_long_only(argc, argv, optstring, lo, NULL)) != -1) {
 		switch (opt) {
@@ -532,7 +592,12 @@ int main(int argc, char* const* argv)
 		case 1018: trk.sites_only = true; break;
 		case 1019: trk.sites_align = true; break;
 		case 1020: trk.oligos = true; break;
-		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only] [--sites-align] [--oligos]]\n"); return 2;
+		case 1021: trk.hist = true; break;
+		case 1022: hist_arg_given = true; trk.hist_controls = strict_int(optarg, -1); break;
+		case 1023: { hist_arg_given = true; char* end = nullptr; errno = 0; trk.hist_seed = strtoull(optarg, &end, 10); if (end == optarg || *end != '\0' || errno == ERANGE || optarg[0] == '-') hist_arg_bad = true; break; }
+		case 1024: { hist_arg_given = true; char* end = nullptr; trk.hist_fdr = strtod(optarg, &end); if (end == optarg || *end != '\0') trk.hist_fdr = -1.0; break; }
+		case 1025: trk.hist_only = true; break;
+		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only] [--sites-align] [--oligos]] [--potential-hist [--hist-controls K] [--hist-seed S] [--hist-fdr Q] [--potential-hist-only]]\n"); return 2;
 		}
 	}
 	if (all_records && accumulate) { fprintf(stderr, "fasim: --all-records and --accumulate-records exclude each other\n"); return 2; }
@@ -550,11 +615,18 @@ int main(int argc, char* const* argv)
 	if (sites && (trk.sites < 1 || trk.sites > 16383)) { fprintf(stderr, "fasim: --sites needs an integer in [1, 16383]\n"); return 2; }
 	if (sites && trk.sites_gap < 0) { fprintf(stderr, "fasim: --sites-gap needs an integer of at least 0\n"); return 2; }
 	if (sites && (p.classicSim || accumulate || track || screen || trk.tfo)) { fprintf(stderr, "fasim: --sites is not available with -F, --accumulate-records, --track, --screen or --tfo-profile\n"); return 2; }
-	if (trk.oligos && !sites) { fprintf(stderr, "fasim: --oligos needs --sites V\n"); return 2; }
+	if ((hist_arg_given || trk.hist_only) && !trk.hist) { fprintf(stderr, "fasim: --hist-controls, --hist-seed, --hist-fdr and --potential-hist-only need --potential-hist\n"); return 2; }
+	if (trk.hist && (p.classicSim || accumulate || track || screen || trk.tfo || sites)) { fprintf(stderr, "fasim: --potential-hist is not available with -F, --accumulate-records, --track, --screen, --tfo-profile or --sites\n"); return 2; }
+	if (trk.hist && trk.hist_controls < 0) { fprintf(stderr, "fasim: --hist-controls needs an integer of at least 0\n"); return 2; }
+	if (trk.hist && hist_arg_bad) { fprintf(stderr, "fasim: --hist-seed needs an unsigned integer\n"); return 2; }
+	if (trk.hist && !(trk.hist_fdr > 0.0 && trk.hist_fdr <= 1.0)) { fprintf(stderr, "fasim: --hist-fdr needs a number in (0, 1]\n"); return 2; }
+	if (trk.hist && 2 * (long long)p.overlapLength > (long long)p.cutLength) { fprintf(stderr, "fasim: --potential-hist needs -o of at most half of -c (a base would lie in three segments)\n"); return 2; }
+	if (trk.oligos && !sites && !trk.hist) { fprintf(stderr, "fasim: --oligos needs --sites V or --potential-hist\n"); return 2; }
 	if (trk.oligos && (trk.sites_align || trk.tfo)) { fprintf(stderr, "fasim: --oligos is not available with --sites-align, -F, --track, --screen, --tfo-profile or --accumulate-records\n"); return 2; }
 	if (trk.oligos) trk.sites_only = true;      // a panel has no triplex records: the sites files and the panel table are all it writes
+	if (trk.oligos && trk.hist) trk.hist_only = true;      // (or the oligos' histograms)
 	if (!sites) trk.sites = 0;
-	trk.peaks = screen; trk.no_stage3 = screen_only || trk.only || trk.tfo_only || trk.sites_only;
+	trk.peaks = screen; trk.no_stage3 = screen_only || trk.only || trk.tfo_only || trk.sites_only || trk.hist_only;
 	// --regions: the BED file is read and checked before anything else happens (a bad file writes nothing)
 	fasim_region* reg = nullptr; int64_t nreg = 0;
 	if (regions && fasim_read_bed(bed_path.c_str(), &reg, &nreg) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 2; }
@@ -661,6 +733,39 @@ int main(int argc, char* const* argv)
 		}
 		return bad;
 	};
+	// --potential-hist: the controls of every lncRNA; with --all-records / --regions / --oligos one table per lncRNA over everything
+	// scanned, <O>/<lnc>-<f1 stem>.hist.tsv, summed over the groups; a plain run writes <stem>-TFOhist for its record
+	std::vector<std::string> hist_ctl;
+	if (trk.hist) {
+		for (const Rna& r : rnas) for (int k = 1; k <= trk.hist_controls; k++) {
+			std::string c(r.seq.size(), 'N');
+			if (fasim_shuffle_query(r.seq.data(), (int32_t)r.seq.size(), trk.hist_seed, k, &c[0]) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
+			hist_ctl.push_back(std::move(c));
+		}
+		trk.hist_ctl = &hist_ctl;
+	}
+	const bool hist_set = trk.hist && (all_records || regions || trk.oligos);
+	std::vector<fasim_hist*> hist_acc(hist_set ? rnas.size() + hist_ctl.size() : 0, nullptr);
+	// h: [lncRNAs] + [lncRNAs x K controls]; NULL entries (nothing scanned) stand for empty histograms
+	auto write_hist = [&](fasim_hist* const* h, size_t q, const std::string& path) -> int {
+		std::vector<int64_t> zeros(FASIM_HIST_BINS, 0);
+		fasim_hist z; memset(&z, 0, sizeof z);
+		for (int c = 0; c < FASIM_TRACK_CLASSES; c++) z.n[c] = zeros.data();
+		const size_t K = (size_t)trk.hist_controls;
+		std::vector<const fasim_hist*> ctl(K);
+		for (size_t k = 0; k < K; k++) { const fasim_hist* x = h[rnas.size() + q * K + k]; ctl[k] = x ? x : &z; }
+		char* text = nullptr; int64_t len = 0;
+		if (fasim_hist_tsv(h[q] ? h[q] : &z, ctl.data(), (int32_t)K, trk.hist_seed, trk.hist_fdr, rnas[q].name.c_str(), &text, &len) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
+		const int bad = write_file(path, text, len);
+		fasim_free(text);
+		return bad;
+	};
+	auto write_hist_set = [&]() -> int {
+		int bad = 0;
+		for (size_t q = 0; q < rnas.size(); q++) bad |= write_hist(hist_acc.data(), q, outdir + "/" + rnas[q].name + "-" + base + ".hist.tsv");
+		for (fasim_hist*& x : hist_acc) { fasim_hist_free(x); x = nullptr; }
+		return bad;
+	};
 	// --oligos: the site lists of every oligo and record are kept for the panel table, <O>/<f2 stem>-<f1 stem>.oligos-<V>.tsv
 	std::vector<std::vector<fasim_sites*>> panel_sites(trk.oligos ? rnas.size() : 0);
 	auto write_panel = [&]() -> int {
@@ -677,8 +782,9 @@ int main(int argc, char* const* argv)
 	if (regions && nreg == 0) {
 		if (tfo_set && write_tfo_set()) return 1;
 		if (sites_set && write_sites_set()) return 1;
-		if (trk.oligos && write_panel()) return 1;
-		if (!screen_only && !trk.tfo_only && !trk.sites_only && write_index()) return 1;
+		if (trk.oligos && sites && write_panel()) return 1;
+		if (hist_set && write_hist_set()) return 1;
+		if (!screen_only && !trk.tfo_only && !trk.sites_only && !trk.hist_only && write_index()) return 1;
 		if (screen && write_screen()) return 1;
 		std::cout << "finished normally" << std::endl;
 		return 0;
@@ -748,7 +854,7 @@ int main(int argc, char* const* argv)
 		long group_segs = 5120;
 		if (const char* g = getenv("FASIM_RECORD_GROUP")) group_segs = atol(g);
 		// (--screen always takes the record-set call, a long record or FASIM_RECORD_GROUP=0 as a group of one)
-		const bool grouped = (all_records || regions) && (group_segs > 0 || screen || sites);
+		const bool grouped = (all_records || regions) && (group_segs > 0 || screen || sites || trk.hist);
 		// grouped: the tails of thousands of records go to a pool of host threads instead of four threads in flight
 		std::unique_ptr<TailPool> pool(grouped ? new TailPool(8) : nullptr);
 		// one scanned record: a DNA record, or a BED interval (species = its name, start = its 1-based start; slot = its index)
@@ -779,6 +885,7 @@ int main(int argc, char* const* argv)
 				}
 				if (trk.sites_only) return;
 			}
+			if (trk.hist_only) return;
 			if (screen) {
 				// the record's line of the screen tables
 				size_t row = (size_t)r.slot;
@@ -849,8 +956,17 @@ int main(int argc, char* const* argv)
 			std::vector<fasim_tfo_profile*> gprof;
 			std::vector<std::vector<fasim_sites*>> gsites;
 			std::vector<std::vector<fasim_site_hits*>> ghits;
+			std::vector<fasim_hist*> ghist;
 			if (scan_group(engines, rnas, gdna, goff, glen, p, res, trk, gtracks, gpeaks, trk.tfo ? &gprof : nullptr, sites ? &gsites : nullptr,
-				sites && trk.sites_align ? &ghits : nullptr)) return 1;
+				sites && trk.sites_align ? &ghits : nullptr, trk.hist ? &ghist : nullptr)) return 1;
+			if (trk.hist && hist_set) { for (size_t k = 0; k < ghist.size(); k++) { fasim_hist* t = ghist[k]; ghist[k] = nullptr; if (hist_fold(hist_acc[k], t)) return 1; } }
+			else if (trk.hist) {
+				// a plain run: <stem>-TFOhist next to -TFOsorted
+				int bad = 0;
+				for (size_t q = 0; q < rnas.size(); q++) bad |= write_hist(ghist.data(), q, outdir + "/" + group[0].species + "-" + rnas[q].name + "-" + base + "-TFOhist");
+				for (fasim_hist* x : ghist) fasim_hist_free(x);
+				if (bad) return 1;
+			}
 			for (size_t q = 0; q < gprof.size(); q++) { fasim_tfo_profile* t = gprof[q]; gprof[q] = nullptr; if (tfo_fold(tfo_acc[q], t)) return 1; }
 			const double dt = now_s() - t0;
 			tm.scan += dt;
@@ -884,14 +1000,14 @@ int main(int argc, char* const* argv)
 					return group_nseg >= group_segs ? flush() : 0;
 				}
 				if (flush()) return 1;
-				if (screen || sites) {
+				if (screen || sites || trk.hist) {
 					// a group of one: only the record-set call gives the peaks / the sites
 					group_nseg = fasim_segment_count(u.len, &p);
 					goff.push_back(0); glen.push_back(u.len); gdna.assign(seq, (size_t)u.len); group.push_back(std::move(u));
 					return flush();
 				}
 			}
-			if (sites) {
+			if (sites || trk.hist) {
 				// a plain run: the record as a set of one (its records are those of fasim_scan_queries)
 				group_nseg = fasim_segment_count(u.len, &p);
 				goff.push_back(0); glen.push_back(u.len); gdna.assign(seq, (size_t)u.len); group.push_back(std::move(u));
@@ -971,9 +1087,10 @@ int main(int argc, char* const* argv)
 		if (screen && write_screen()) return 1;
 		if (tfo_set && write_tfo_set()) return 1;
 		if (sites_set && write_sites_set()) return 1;
-		if (trk.oligos && write_panel()) return 1;
+		if (trk.oligos && sites && write_panel()) return 1;
+		if (hist_set && write_hist_set()) return 1;
 		if (regions) {
-			if (!screen_only && !trk.tfo_only && !trk.sites_only && write_index()) return 1;
+			if (!screen_only && !trk.tfo_only && !trk.sites_only && !trk.hist_only && write_index()) return 1;
 			std::vector<std::string> lost;
 			for (const auto& c : todo) for (const auto& j : c.second) {
 				const fasim_region& g = reg[j.second];

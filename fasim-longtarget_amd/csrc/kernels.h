@@ -148,6 +148,24 @@ struct SitesLaunch {
 };
 hipError_t launch_sites(const SitesLaunch& L, bool emit, hipStream_t st);
 
+// ---- hist.hip: histogram of the potential over the positions of a batch -------------------------------
+constexpr int HIST_BINS = 16384;           // values 0 .. 16 383 (the saturated column maximum)
+constexpr int HIST_LDS_BINS = 1024;        // values below this are counted in the workgroup's LDS histogram first, the others straight in HBM
+// A position of a segment that a neighbouring segment of the record covers too (the head zone [0, zone[2 s]) and the tail zone
+// [zone[2 s + 1], n) of segment s) is not counted: its four values go to zones[s][head 0 / tail 1][class][zstride], slot = the
+// offset within the zone, and the host counts the maximum of the two sides once.
+struct HistLaunch {
+	const uint16_t* colmax16;   // as TrackLaunch
+	const int32_t* seg_len;     // [nseg]
+	const int32_t* zone;        // [nseg][2]: end of the head zone (0: none), begin of the tail zone (seg_len: none); head <= tail
+	int32_t nseg, nenc, tstride, nchunk, zstride;        // zstride >= the longest zone of the batch
+	TrackTable tab;
+	uint32_t* hist;             // [4][HIST_BINS], zeroed by the caller: the batch's counts per class and value
+	uint16_t* zones;            // [nseg][2][4][zstride] (zstride == 0: no zones, may be NULL)
+	uint8_t* sat;               // [nseg * nenc], zeroed by the caller: 1 = the unit holds a saturated column maximum (16 383)
+};
+hipError_t launch_hist(const HistLaunch& L, hipStream_t st);
+
 // ---- scan_short.hip: column maxima of a short oligo ----------------------------------------------------
 constexpr int SCAN_SHORT_MAX = 112;        // longest oligo k_scan_short takes (FASIM_MAX_OLIGO)
 // W(m): the alignments that decide a column maximum start at most this many columns before it

@@ -456,6 +456,68 @@ int  fasim_scan_oligos(fasim_engine* e, const char* const* oligos, const int32_t
 int  fasim_oligo_panel_tsv(const char* const* names, const int32_t* lens, int32_t nq, const fasim_sites* const* sites, int32_t nrec,
                            char** text, int64_t* text_len);
 
+/* ---- histograms of the potential with shuffled controls (csrc/hist.hip) -------------------------------------- */
+/* How much of a record set reaches potential v, for every v.  P[c][x] is the bin = 1 track of section 11 of a record scanned alone.
+ * n[c][v] is the number of COVERED positions x, over all records of the set, with P_r[c][x] == v, v in [0, 16383]; a position is
+ * covered when a selected segment contains it (a segment that the same-letter rule skips is selected: its positions have P = 0).
+ * The four classes sum to the same number, `positions`; for an unsharded call that is the total length of the records.  A position
+ * in the overlap of two segments counts once, with the maximum of the two.  With a segment range, a boundary whose other segment
+ * lies outside the range is PENDING: its positions are counted with the values of the range alone, and those values travel in
+ * `pending` so that fasim_hist_merge can count the maximum of the two sides instead.  Boundary b of a record is the overlap of its
+ * segments b and b + 1; side 0 holds the values of segment b (its last positions), side 1 those of segment b + 1 (its first). */
+#define FASIM_HIST_BINS 16384
+typedef struct fasim_hist_edge {
+	int32_t record, side;                        /* record of the call's set; 0 / 1 as above                                */
+	int64_t boundary;
+	int32_t len, reserved;                       /* positions of the overlap                                                */
+	uint16_t* v;                                 /* [4][len]: P of the range at those positions, per class                  */
+} fasim_hist_edge;
+typedef struct fasim_hist {
+	int64_t* n[FASIM_TRACK_CLASSES];             /* [FASIM_HIST_BINS]                                                       */
+	int64_t positions;                           /* covered positions = the sum of n[c][.] for every c                      */
+	int64_t units, saturated_units;              /* as fasim_track                                                          */
+	int64_t npending; fasim_hist_edge* pending;  /* ordered by (record, boundary, side)                                     */
+} fasim_hist;
+/* fasim_scan_records with one histogram per query over the whole record set: arguments, record cutting, global segment numbering
+ * and the refusals of fasim_scan_records_sites (without min_value and max_gap); out_hists == NULL gives FASIM_E_ARG, and
+ * 2 * overlapLength > cutLength gives FASIM_E_UNSUPPORTED (a base would lie in three segments).  Every refusal happens before any
+ * GPU work and leaves the engine usable, as does FASIM_E_NOMEM.  out_results == NULL: no stage 3 (the work ends after the scan
+ * kernel and k_hist); otherwise out_results and totals are byte for byte those of fasim_scan_records.  out_hists[q] depends on the
+ * records, the query and the parameters only (not on batches, workers, shards after the merge, devices, dp_f16, resident or streamed
+ * DNA, nor on whether stage 3 ran).  A control is just one more query: see fasim_shuffle_query.  Free each with fasim_hist_free. */
+int  fasim_scan_records_hist(fasim_engine* e, const char* const* rnas, const int32_t* rna_lens, int32_t nq,
+                             const char* dna, const int64_t* rec_off, const int64_t* rec_len, int32_t nrec,
+                             int64_t seg_first, int64_t seg_count, const fasim_params* p,
+                             fasim_result** out_results /* [nq * nrec] or NULL: no stage 3 */,
+                             fasim_hist** out_hists /* [nq] */, fasim_scan_stats* totals /* [nq], may be NULL */);
+/* The same for a panel of oligos: the arguments and refusals of fasim_scan_oligos (without the sites' and tracks' own), plus the
+ * 2 * overlapLength > cutLength refusal; out_hists[q] is the histogram of oligo q over the record set. */
+int  fasim_scan_oligos_hist(fasim_engine* e, const char* const* oligos, const int32_t* lens, int32_t nq,
+                            const char* dna, const int64_t* rec_off, const int64_t* rec_len, int32_t nrec,
+                            int64_t seg_first, int64_t seg_count, const fasim_params* p,
+                            fasim_hist** out_hists /* [nq] */, fasim_scan_stats* totals /* [nq], may be NULL */);
+/* Shards of ONE record set and one query (disjoint segment ranges): counts, positions, units and saturated_units are summed; where
+ * both sides of a boundary are pending, what each side counted alone is taken out, the element-wise maximum is counted once and the
+ * pair is dropped; unpaired edges stay pending.  Associative and commutative; the merge of all shards is the unsharded result with
+ * nothing pending.  An edge that is pending twice, or two sides of different length, are refused (FASIM_E_ARG). */
+int  fasim_hist_merge(const fasim_hist* const* parts, int32_t nparts, fasim_hist** out);
+void fasim_hist_free(fasim_hist* h);
+/* Control k (k >= 1) of a query under `seed`: a Fisher-Yates shuffle of the m bytes as given (case and U kept), driven by a
+ * splitmix64 whose state starts at seed ^ (k * 0xD1B54A32D192ED03) mod 2^64: for i = m - 1 down to 1, j = next() mod (i + 1), swap
+ * a[i] and a[j].  out[m] may be rna itself.  The shuffle keeps the composition exactly. */
+int  fasim_shuffle_query(const char* rna, int32_t m, uint64_t seed, int32_t k, char* out /* [m] */);
+/* With ge[v] = the sum over the classes of n[c][w], w >= v, and ctl_ge[v] the same summed over the K controls: the smallest v >= 1
+ * with ge[v] > 0 such that every w >= v with ge[w] > 0 has (double)ctl_ge[w] <= Q * (double)K * (double)ge[w]; 0 when there is none.
+ * K is ncontrols and Q is fdr.  Bad arguments (K < 0, Q outside (0, 1]) give FASIM_E_ARG (negative). */
+int32_t fasim_hist_threshold(const fasim_hist* real, const fasim_hist* const* controls, int32_t ncontrols, double fdr);
+/* The table `fasim --potential-hist` writes.  First `# fasim potential histogram lncRNA=<rna_name> positions=<n>` and, with K > 0,
+ * ` controls=<K> seed=<S> fdr=<Q> min_value=<V|NA>` (V = fasim_hist_threshold, NA for 0; Q as %g).  Then the line of column names
+ * and one tab-separated line per value v from 1 to the largest v with a count in the query or a control: value, per class <Class>
+ * (n[c][v]), <Class>_ge and with K > 0 <Class>_ctl_ge, then all_ge and with K > 0 all_ctl_ge and fdr = all_ctl_ge / (K * all_ge) as
+ * %.6g, NA where all_ge is 0 (K is ncontrols, S is seed, Q is fdr).  Free with fasim_free. */
+int  fasim_hist_tsv(const fasim_hist* real, const fasim_hist* const* controls, int32_t ncontrols, uint64_t seed, double fdr, const char* rna_name,
+                    char** text, int64_t* text_len);
+
 /* Host half of the path's one exchange step: concatenates the records of `nparts` shards in the
  * order given and rebases their pool offsets.  Shards are contiguous segment ranges, so rank order IS the
  * reference's canonical (segment, encoding, fastSIM rank) order, which cluster_triplex()'s unstable sort needs.
