@@ -261,3 +261,137 @@ def split_sections(text: bytes):
 def join_sections(items):
     """Inverse of split_sections: [(idx, kind, bytes)] -> one text."""
     return b"".join(f"= {idx} {kind} {len(data)}\n".encode() + data for idx, kind, data in items)
+
+
+# ---- the rows-per-lane sweep of the systolic kernels (test_row_layouts_cpu.py, test_gpu_row_layouts.py) -------------------------
+# k_scan and k_align_fwd are compiled once per RP = rows per virtual lane, 1 ... 24, and the query length alone picks the build.
+# Two single-tile lengths per RP: "full" (every virtual lane owns RP rows, no pad rows) and "ragged" (two lanes of a stripe own RP
+# rows, six own RP - 1, 15 zero-score pad rows).  The DNA of a case is generated, never stored.
+ROW_LAYOUT_RPS = tuple(range(1, 25))
+ROW_LAYOUT_DNA_LEN = 5000
+# plants (stripe boundary j, encoding, query rows): 48 rows [b - 42, b + 6) score 240 and stay in the byte range even when both
+# neighbours match by chance; 56 rows [b - 50, b + 6) score 280, beyond it (Q1); the rule-1 plants are 32 rows (160) of G / T.  The two long ones come last in their units (the
+# odd encodings read the record backwards), so the reference's overflow cut hides no other plant.
+ROW_LAYOUT_PLANTS = ((15, 27, 56), (8, 40, 48), (4, 41, 48), (12, 22, 48), (6, 23, 48), (10, 0, 32), (10, 13, 32), (2, 27, 48), (14, 40, 48),
+                     (3, 26, 48), (9, 41, 48), (13, 23, 48), (7, 22, 48), (10, 12, 32), (1, 26, 56))
+# gapped plants (stripe boundary j, encoding, first DNA base): rows [b - 48, b) and [b + 26, b + 47) back to back.  The best path
+# crosses the boundary as a vertical gap: F enters row b at 224 and decays by 4 per row.  The reference's lazy-F loop leaves at
+# the row where F is still 128 ... 139 while H - 16 has dropped below 128 (its exit test compares signed bytes: Q2), about 22 rows
+# down, so the F = 124 that the second part starts from (124 + 105 = 229, above the unit's threshold) is withheld there: such a
+# unit must go to the stripe-faithful re-run, also where the stripes are long enough for the row analysis (seg >= 96).  Each comes
+# first in its unit (encoding 23 reads the record backwards), before anything that could reach the overflow cut.
+ROW_LAYOUT_GAP_PLANTS = ((5, 40, 280), (11, 23, 4480), (8, 22, 40), (13, 41, 4600), (3, 26, 580), (9, 27, 4700))
+
+
+def systolic_layout(m):
+    """(seg, vs, RP) of a query of m rows: the formula of launch_scan / launch_fwd written out (not imported from the library)."""
+    seg = (m + 15) // 16
+    vs = 8 * ((seg + 191) // 192)
+    return seg, vs, (seg + vs - 1) // vs
+
+
+def row_layout_cases():
+    """[(RP, 'full' | 'ragged', m)]: 48 query lengths from 113 to 3 072."""
+    out = []
+    for k in ROW_LAYOUT_RPS:
+        out.append((k, "ragged", 128 * (k - 1) + 17 if k > 1 else 113))
+        out.append((k, "full", 128 * k))
+    return out
+
+
+def row_layout_case_id(case):
+    return f"rp{case[0]}-{case[1]}-m{case[2]}"
+
+
+def band_classes_restated(m):
+    """The band heights G of the banded stage 3 that a single-tile query of m rows gets: 8 * G <= 3 * nl, nl = ceil(16 * seg / 48)
+    (band.hip; its LDS conditions cannot fail below 3 073 rows)."""
+    nl = (16 * ((m + 15) // 16) + 47) // 48
+    return [G for G in (8, 16, 32) if 8 * G <= 3 * nl]
+
+
+def plant_window(m, seg, j, rows=56):
+    """Query rows [lo, hi) of a plant of `rows` rows at stripe boundary b = j * seg: six rows beyond b, the others before it, moved
+    into the query where it sticks out."""
+    b = j * seg
+    lo = max(0, min(b + 6 - rows, m - rows))
+    return lo, min(m, lo + rows)
+
+
+def preimage(rows: bytes, enc: int, rng):
+    """DNA whose unit of encoding `enc` reads `rows` (None where a row's letter is no output of the rule); a letter with two
+    pre-images takes either."""
+    import synth
+    pre = {}
+    for base, o in zip("ATGC", synth.RULE_OUT[enc]):
+        pre.setdefault(o, []).append(base)
+    if not set(rows.decode()) <= set(pre):
+        return None
+    tract = bytearray(ord(pre[chr(c)][rng.below(len(pre[chr(c)]))]) for c in rows)
+    if synth.enc_reversed(enc):
+        tract.reverse()
+    return bytes(tract)
+
+
+def row_layout_inputs(m):
+    """(query, DNA record, plants) of the sweep's case of m rows.
+
+    Query: seeded random ACGT, except that 32 rows around boundary 10 are random G / T, the only letters rule 1 can write (its
+    four encodings 0, 1, 12, 13 turn A, T, G, C into TGGT or GTTG), so that the rule-1 units hold a real hit too.
+    DNA: 5 000 nt of synth.planted_dna (random background with mutated, gapped pre-images of query windows under random encodings),
+    then the exact pre-images of ROW_LAYOUT_PLANTS, diagonals that run into a stripe boundary of the reference, one every 300 nt,
+    under the one-to-one encodings 22, 23, 26, 27, 40, 41 (odd ones reversed) and under the rule-1 encodings 0, 12 and 13.
+    Two more, ROW_LAYOUT_GAP_PLANTS, cross a boundary as a vertical gap.
+    plants: dicts enc, j, b (the boundary row), lo, hi (query rows), pos (first DNA base), n, and gap for the last two."""
+    import synth
+    seg = (m + 15) // 16
+    rng = synth._Rng(7700000 + m)
+    rna = bytearray(synth.random_rna(m, 7100000 + m))
+    lo, hi = plant_window(m, seg, 10, 32)
+    for i in range(lo, hi):
+        rna[i] = b"GT"[rng.below(2)]
+    rna = bytes(rna)
+    dna = bytearray(synth.planted_dna(ROW_LAYOUT_DNA_LEN, 7203000 + m, rna, every=150, min_len=35, max_len=70, mut_pct=8))
+    plants = []
+    for i, (j, enc, rows) in enumerate(ROW_LAYOUT_PLANTS):
+        lo, hi = plant_window(m, seg, j, rows)
+        tract = preimage(rna[lo:hi], enc, rng)
+        assert tract is not None, (m, j, enc)
+        pos = 150 + 300 * i
+        dna[pos:pos + len(tract)] = tract
+        plants.append({"enc": enc, "j": j, "b": j * seg, "lo": lo, "hi": hi, "pos": pos, "n": len(tract)})
+    for j, enc, pos in ROW_LAYOUT_GAP_PLANTS:
+        lo = max(0, min(j * seg - 48, m - 95))
+        tract = preimage(rna[lo:lo + 48] + rna[lo + 74:lo + 95], enc, rng)
+        dna[pos:pos + len(tract)] = tract
+        plants.append({"enc": enc, "j": j, "b": j * seg, "lo": lo, "hi": lo + 95, "pos": pos, "n": len(tract), "gap": True})
+    assert len(dna) == ROW_LAYOUT_DNA_LEN
+    return rna, bytes(dna), plants
+
+
+def oracle_scan_case(build_dir, tmp_dir, m, threads=8):
+    """The oracle's `scan` of the case of m rows (default parameters), parsed: (meta, units)."""
+    import synth
+    rna, dna, _ = row_layout_inputs(m)
+    rna_fa, dna_fa = os.path.join(str(tmp_dir), f"q{m}.fa"), os.path.join(str(tmp_dir), f"d{m}.fa")
+    synth.write_fasta(rna_fa, f"q{m}", rna)
+    synth.write_fasta(dna_fa, f"syn|chrR|1-{len(dna)}", dna)
+    return parse_scan(oracle_cli(build_dir, "scan", rna_fa, dna_fa, "-threads", str(threads)))
+
+
+def q2_units_of_gap_plants(orc, m):
+    """Encodings of the gapped plants in whose unit (first segment) the reference's signed lazy-F exit changes a column maximum
+    above the unit's threshold: the oracle's pre_align against the same with the exit made unsigned (fo_pre_align_noq2)."""
+    orc.lib.fo_pre_align_noq2.restype = None
+    orc.lib.fo_pre_align_noq2.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    rna, dna, plants = row_layout_inputs(m)
+    out = []
+    for enc in sorted({p["enc"] for p in plants if p.get("gap")}):
+        t, _ = orc.encode_unit(dna[:ROW_LAYOUT_DNA_LEN], enc)
+        ref = orc.pre_align(rna, t)
+        buf = (ctypes.c_int * len(t))()
+        orc.lib.fo_pre_align_noq2(rna, len(rna), t, len(t), buf)
+        thr = int(orc.stage1_max(rna, t) * 0.8)
+        if [(c, v) for c, v in enumerate(ref) if v > thr] != [(c, v) for c, v in enumerate(buf) if v > thr]:
+            out.append(enc)
+    return out

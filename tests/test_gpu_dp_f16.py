@@ -112,3 +112,62 @@ def test_unit_beyond_the_exact_range_is_rerun(mod, golden_dir, oracle_build):
     assert r1.stats["dp_f16_reruns"] == len(beyond)
     assert r0.count > 0 and (r1.recs, r1.pool) == (r0.recs, r0.pool)
     assert r1.stats["candidates"] == r0.stats["candidates"] and r1.stats["hazard_units"] == r0.stats["hazard_units"]
+
+
+def _edited_preimage(rows: str, enc: int, edits: str):
+    """The exact pre-image of `rows` under a one-to-one encoding with one edit every 25 bases, at offsets 25, 50, 75, ...:
+    x another base (a mismatch), i a second base behind it (an insertion), d the base left out (a deletion)."""
+    out = synth.RULE_OUT[enc]
+    assert len(set(out)) == 4 and not synth.enc_reversed(enc)
+    pre = {o: base for base, o in zip("ATGC", out)}
+    assert set(rows) <= set(pre)
+    tract = [pre[ch] for ch in rows]
+    for n, op in enumerate(edits):
+        k = 25 * (n + 1)
+        other = "ACGT"[("ACGT".index(tract[k]) + 1) % 4]
+        tract[k] = {"x": other, "i": tract[k] + other, "d": ""}[op]
+    return "".join(tract).encode()
+
+
+# (query, first planted row, planted rows, edits).  With H19 the oracle scores the unit of encoding 26 at 1 022, 1 023, 1 024, 1 025
+# and 1 031: both sides of the last exactly held score, 1 023, and the lumps next to them.  The last two are queries of the
+# rows-per-lane sweep: RP 17, and RP 2, the smallest build whose query (256 rows, 1 280 at the most) can leave the range at all
+# (RP 1 is at most 128 rows, 640).
+F16_EDGE_CASES = (("H19", 700, 200, ""), ("H19", 700, 208, "ii"), ("H19", 700, 210, "xii"), ("H19", 700, 204, "d"), ("H19", 700, 201, ""),
+                  (2176, 1000, 260, "x"), (256, 0, 256, ""))
+
+
+def test_ends_of_the_exact_range(mod, golden_dir, oracle_build):
+    """Carried values are 2 * score + taint, exact up to 2 047, and the flag fires at a block maximum of 2 048: a unit that scores
+    1 023 is NOT run again and its f16 results stand, a unit that scores 1 024 is.  For every case the oracle gives the stage-1
+    maximum of all 48 units; exactly the units at 1 024 or more are re-run, and records and pool are those of the integer kernels.
+    The cases hold a unit in [1016, 1023] and one in [1024, 1031] (asserted here, from the oracle)."""
+    orc = helpers.Oracle(oracle_build)
+    enc = 26
+    p = mod.default_params(cLength=20)
+    below, above, rps = [], [], set()
+    for query, row0, nrows, edits in F16_EDGE_CASES:
+        rna = _rna(golden_dir, query) if isinstance(query, str) else helpers.row_layout_inputs(query)[0]
+        rows = rna[row0:row0 + nrows].decode().upper().replace("U", "T")
+        assert len(rows) == nrows
+        tract = _edited_preimage(rows, enc, edits)
+        dna = bytearray(synth.random_dna(3000, 4242))
+        dna[1200:1200 + len(tract)] = tract
+        dna = bytes(dna)
+        scores = [orc.stage1_max(rna, orc.encode_unit(dna, k)[0]) for k in range(48)]
+        beyond = [k for k in range(48) if scores[k] >= 1024]
+        rp = helpers.systolic_layout(len(rna))[2]
+        print(f"{query} rows [{row0}, {row0 + nrows}) edits '{edits}': RP {rp}, encoding {enc} scores {scores[enc]}, "
+              f"units >= 1024: {({k: scores[k] for k in beyond})}")
+        below += [s for s in scores if 1016 <= s <= 1023]
+        above += [s for s in scores if 1024 <= s <= 1031]
+        if beyond:
+            rps.add(rp)
+        r0, r1 = _scan(mod, rna, dna, p, 0), _scan(mod, rna, dna, p, 1)
+        assert r0.stats["units"] == 48 and r0.stats["dp_f16_reruns"] == 0
+        assert r1.stats["dp_f16_reruns"] == len(beyond), (query, nrows, edits)
+        assert r0.count > 0 and (r1.recs, r1.pool) == (r0.recs, r0.pool), (query, nrows, edits)
+        assert r1.stats["candidates"] == r0.stats["candidates"]
+    assert below and above, (below, above)
+    print("scores in [1016, 1023]:", sorted(below), "in [1024, 1031]:", sorted(above))
+    assert min(rps) <= 2 and max(rps) >= 17 and 22 in rps, rps

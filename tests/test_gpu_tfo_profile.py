@@ -131,6 +131,24 @@ def test_row_layouts_and_tiles(mod, m):
         _same(got.array(), want, f"m {m} dp_f16 {f16}")
 
 
+@pytest.mark.parametrize("case", helpers.row_layout_cases(), ids=helpers.row_layout_case_id)
+def test_row_layouts_planted(mod, case):
+    """The ROWS and ROWS + F16 builds of every RP = 1 ... 24, in both row layouts, on the planted record of the rows-per-lane sweep
+    (helpers.row_layout_inputs): under rule 1 its units hold exact 32-row hits of encodings 0, 12 and 13 that run into a stripe
+    boundary, so the row maxima are those of real hits (148 or more), not of random DNA."""
+    k, layout, m = case
+    rna, dna, _ = helpers.row_layout_inputs(m)
+    p = mod.default_params(rule=1, strand=0)
+    want, units = expected_profile(rna, [dna], p)
+    assert units == 2 * 4
+    print(f"RP {k} {layout} m {m}: largest row maximum per class {want.max(axis=1).tolist()}")
+    assert int(want.max()) >= 148
+    for f16 in (0, 1):
+        got = _profile(mod, rna, dna, p, dp_f16=f16)
+        assert got.units == units
+        _same(got.array(), want, f"RP {k} {layout} m {m} dp_f16 {f16}")
+
+
 def test_unit_beyond_the_exact_range_is_rerun(mod, golden_dir):
     """The input of test_gpu_dp_f16.test_unit_beyond_the_exact_range_is_rerun: the f16 pass hands the units that score above
     1 023 to the integer kernel, whose ROWS variant overwrites their void rows."""
