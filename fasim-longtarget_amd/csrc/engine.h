@@ -164,7 +164,10 @@ inline int fail(fasim_engine* e, int code, const char* fmt, ...)
 
 // stage-2/3 alphabet (ssw_cpp.cpp:13-26): A,a,U,u -> 0 ; C,c -> 1 ; G,g -> 2 ; T,t -> 3 ; else 4
 inline uint8_t code2(char c) { switch (c) { case 'A': case 'a': case 'U': case 'u': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2; case 'T': case 't': return 3; default: return 4; } }
-// SIM (-F) alphabet: the score table of sim.h:464-468 knows ACGT only; every other letter is a mismatch with everything
+// SIM (-F) alphabet: upper-case ACGT; the engine's and the oracle's choice is that every other letter (U, N, IUPAC codes, lower
+// case) is a mismatch (-4) with everything.  That is NOT the reference's behaviour: its table `long V[128][128]` is a local of SIM()
+// (sim.h:419) of which only the 16 ACGT x ACGT entries are ever written (sim.h:470-473), so for any other pair it reads
+// uninitialised stack memory and its output is undefined (DESIGN sections 7 and 9)
 inline uint8_t sim_code(char c) { switch (c) { case 'A': return 0; case 'C': return 1; case 'G': return 2; case 'T': return 3; default: return 4; } }
 // stage-1 alphabet (stats.h:201-228, 306-334): U == T, everything outside ACGTU is N
 inline uint8_t code1(char c) { switch (c) { case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2; case 'T': case 't': case 'U': case 'u': return 3; default: return 4; } }

@@ -40,7 +40,7 @@ inline void take_better(Tri& a, const Tri& b)
 struct Sim {
 	const char* A; const char* B;               // 1-based: A[1..M] lncRNA, B[1..N] target
 	long M, N;
-	long sub[128][128];                         // V (sim.h:464-468): 50 on the ACGT diagonal, -40 otherwise
+	long sub[128][128];                         // V (sim.h:419, 470-473): 50 on the ACGT diagonal, -40 for the other ACGT pairs; -40 for every other pair is this project's choice (see init)
 	long Q, R;
 	std::vector<SimNode> nodes;                 // LIST
 	std::vector<long> CC, DD, RR, SS, EE, FF;   // indexed by column
@@ -205,7 +205,10 @@ struct Sim {
 	void init(const std::string& rnaA, const std::string& tgtB)
 	{
 		M = (long)rnaA.size(); N = (long)tgtB.size();
-		for (auto& r : sub) for (long& x : r) x = -40;                                      // (only ACGT x ACGT is defined in the reference)
+		// the reference writes the 16 ACGT x ACGT entries of a stack array and nothing else (sim.h:419, 470-473): for a pair with any
+		// other letter (U, N, IUPAC, lower case; a DNA N comes through the rules as N) it reads uninitialised memory.  -40 (a mismatch)
+		// there is the engine's and this oracle's defined policy, not the reference's behaviour (DESIGN sections 7 and 9)
+		for (auto& r : sub) for (long& x : r) x = -40;
 		for (char c : { 'A', 'C', 'G', 'T' }) sub[(int)c][(int)c] = 50;
 		Q = 120; R = 40;
 		CC.assign((size_t)N + 1, 0); DD = RR = SS = EE = FF = CC;

@@ -139,6 +139,225 @@ def probe_random_vectors():
     return q.encode(), targets, wins, reqs
 
 
+# ---- untidy queries: U, lower case, N and IUPAC letters (test_oracle_golden.py, test_gpu_dirty_query.py) ------------------------
+# The four query classes of DESIGN section 7: k_striped only, systolic with the coarse hazard test, one tile, two tiles.
+DIRTY_LENGTHS = (100, 700, 1300, 4000)
+DIRTY_DNA_LEN = 10000
+# query seeds (the DNA takes seed + 1), picked among a few so that the conditions of test_dirty_query_scan_and_input_conditions hold
+DIRTY_SEEDS = {100: 9101, 700: 9110, 900: 9109, 1300: 9120, 4000: 9145}
+DIRTY_Q2_UNITS = {1300: 3, 4000: 2}     # hazard (Q2) units that matter, by q2_units_that_matter (test_oracle_golden.py holds the oracle to it)
+# (segment, encoding) of the plants, all under encodings that give every query letter a pre-image (22, 23, 26, 27, 40, 41).  Plants
+# of one strength share a unit: the unit's threshold is 0.8 times its best stage-1 score.
+DIRTY_STAGE2_UNITS = ((0, 26), (0, 27), (1, 26), (1, 27), (0, 22), (1, 23))     # 30-row plants (150)
+DIRTY_STAGE1_UNITS = ((0, 40), (1, 41), (1, 40))                                # 44-row plants (220), read in full by stage 1 only
+DIRTY_GAP_UNITS = ((0, 41), (0, 23), (1, 22))                                   # gapped plants (240 and 105)
+
+
+def dirty_zones(m):
+    """((first, end) of the U stretch, (first, end) of the lower-case stretch, first row of the last third)."""
+    w = max(1, m // 6)
+    return (m // 12, m // 12 + w), (m // 3, m // 3 + w), 2 * m // 3
+
+
+def dirty_query(m, seed):
+    """A seeded random query with three untidy zones: a stretch of m / 6 rows in which every T is written U, a stretch of m / 6
+    rows in lower case, and a last third with one letter of N R Y n u every 23 ... 52 rows."""
+    import synth
+    q = bytearray(synth.random_rna(m, seed))
+    (u0, u1), (l0, l1), s0 = dirty_zones(m)
+    for i in range(u0, u1):
+        if q[i] == ord("T"):
+            q[i] = ord("U")
+    q[l0:l1] = bytes(q[l0:l1]).lower()
+    rng = synth._Rng(seed * 31 + 7)
+    i = s0 + rng.below(23)
+    while i < m:
+        q[i] = b"NRYnu"[rng.below(5)]
+        i += 23 + rng.below(30)
+    return bytes(q)
+
+
+def dirty_rows(query):
+    """{'U': rows of the U stretch that hold a U, 'lower': rows of the lower-case stretch, 'N': untidy rows of the last third}."""
+    (u0, u1), (l0, l1), s0 = dirty_zones(len(query))
+    return {"U": [i for i in range(u0, u1) if query[i] == ord("U")], "lower": list(range(l0, l1)),
+            "N": [i for i in range(s0, len(query)) if query[i] in b"NRYnu"]}
+
+
+def dirty_reading(rows: bytes, stage, rng, avoid=b""):
+    """Query rows as a stage reads them, in upper-case ACGT: stage 1 reads U as T, stages 2 and 3 read U as A (the reference's
+    quirk); a letter that matches nothing (N, R, Y) is filled arbitrarily, with no letter of `avoid`."""
+    fill = bytes(c for c in b"ACGT" if c not in avoid)
+    out = bytearray()
+    for c in rows.upper():
+        if c == ord("U"):
+            c = ord("T") if stage == 1 else ord("A")
+        elif c not in b"ACGT":
+            c = fill[rng.below(len(fill))]
+        out.append(c)
+    return bytes(out)
+
+
+def dirty_windows(query, rows, lo_bound, hi_bound, need, most, length=30):
+    """Up to three windows [lo, lo + length) within [lo_bound, hi_bound) that hold between `need` and `most` of `rows` and whose
+    stage-2 reading has no G next to a G, at least `length` / 3 apart.
+    (Under the one-to-one encodings a query G is written by a T of the strand that the triplex record shows, and two T in a row
+    there cost the record 1 000 of stability, penaltyT: such a hit is found and aligned but never becomes a triplex.)"""
+    import synth
+    rowset, out = set(rows), []
+    for lo in range(max(0, lo_bound), min(len(query), hi_bound) - length + 1):
+        held = sum(r in rowset for r in range(lo, lo + length))
+        text = dirty_reading(query[lo:lo + length], 2, synth._Rng(1), avoid=b"G")
+        if need <= held <= most and b"GG" not in text and (not out or lo - out[-1][0] >= length // 3):
+            out.append((lo, lo + length))
+    return out[:3] if len(out) <= 3 else [out[0], out[len(out) // 2], out[-1]]
+
+
+def dirty_dna(query, n, seed, with_plants=False):
+    """DNA for an untidy query: synth.planted_dna (which leaves lower-case and N rows to chance), then exact pre-images of query
+    windows, one every 230 nt in the first two segments, under the one-to-one encodings:
+      kind 'U', 'lower', 'N': 30-row windows (dirty_windows) that hold rows of the U stretch, 4 ... 9 rows of the lower-case stretch
+          (the triplex record counts a lower-case row as a mismatch: more of them and its identity falls below 60) or an untidy
+          row of the last third, as stages 2 and 3 read them (case folded, U as A), each in several units of DIRTY_STAGE2_UNITS:
+          their diagonals cross the untidy rows, and the triplexes they give overlap them;
+      kind 'stage1': 44-row windows around the U stretch as stage 1 reads them (U as T), in the units of DIRTY_STAGE1_UNITS: stage 1
+          sees up to 220 there, stage 2 a mismatch at every U, so the threshold 0.8 * stage 1 comes from a diagonal that stage 2
+          scores lower (windows with few U keep a candidate) or loses (windows inside the stretch);
+      kind 'gap' (queries of 1 300 rows and more): the construction of ROW_LAYOUT_GAP_PLANTS at stripe boundaries b of the last
+          third whose 26 gap rows [b, b + 26) hold an untidy letter, so that the vertical gap of a hazard (Q2) unit runs through it.
+    Two bases on either side of a 30-row plant mismatch the query, so that the hit rarely grows beyond it.
+    with_plants: also the list of plants (kind, seg, enc, lo, hi, pos, n)."""
+    import synth
+    m = len(query)
+    rng = synth._Rng(seed * 131 + 5)
+    dna = bytearray(synth.planted_dna(n, seed, query, every=400, min_len=25, max_len=36, mut_pct=8))
+    rows = dirty_rows(query)
+    (u0, u1), (l0, l1), s0 = dirty_zones(m)
+    L = 30
+    wanted = {"U": dirty_windows(query, rows["U"], u0 - L, u1 + L, 1, 6, L),
+              "lower": dirty_windows(query, rows["lower"], l0 - L, l0 + 9, 4, 9, L) + dirty_windows(query, rows["lower"], l1 - 9, l1 + L, 4, 9, L),
+              "N": dirty_windows(query, rows["N"], s0 - L, m, 1, 2, L)}
+    slots = {0: 0, 1: 0}
+    plants = []
+
+    def put(kind, unit, lo, hi, tract):
+        s, enc = unit
+        pos = 4900 * s + 200 + 230 * slots[s]
+        slots[s] += 1
+        assert pos + len(tract) <= 4900 * s + 4800 and pos + len(tract) <= n, (kind, unit, pos)
+        dna[pos:pos + len(tract)] = tract
+        plants.append({"kind": kind, "seg": s, "enc": enc, "lo": lo, "hi": hi, "pos": pos, "n": len(tract)})
+
+    def other(row):
+        """a letter that row `row` of the query does not match in stage 2, and no G"""
+        if not 0 <= row < m:
+            return b"A"
+        c = dirty_reading(query[row:row + 1], 2, rng, avoid=b"G")
+        return bytes([next(x for x in b"ACT" if x != c[0])])
+
+    seg = (m + 15) // 16
+    if m >= 1300:
+        untidy, gaps = rows["N"], []
+        for j in range(1, 16):
+            b = j * seg
+            if b + 47 <= m and any(b <= r < b + 26 for r in untidy):
+                gaps.append((any(b - 48 <= r < b or b + 26 <= r < b + 47 for r in untidy), j))
+        for unit, (_, j) in zip(DIRTY_GAP_UNITS, sorted(gaps)):
+            lo = j * seg - 48
+            put("gap", unit, lo, lo + 95, preimage(dirty_reading(query[lo:lo + 48] + query[lo + 74:lo + 95], 2, rng), unit[1], rng))
+    for ki, kind in enumerate(("U", "lower", "N")):
+        ws = wanted[kind]
+        for j in range(min(9, 6 * len(ws))):
+            w = j % len(ws)
+            unit = DIRTY_STAGE2_UNITS[(j // len(ws) + w + 2 * ki) % 6]
+            lo, hi = ws[w]
+            text = other(lo - 2) + other(lo - 1) + dirty_reading(query[lo:hi], 2, rng, avoid=b"G") + other(hi) + other(hi + 1)
+            put(kind, unit, lo, hi, preimage(text, unit[1], rng))
+    W = min(44, m)
+    for t in range(6):
+        lo = max(0, min(u0 - 38 + t * (u1 - u0 + 32) // 5, m - W))
+        unit = DIRTY_STAGE1_UNITS[t % len(DIRTY_STAGE1_UNITS)]
+        put("stage1", unit, lo, lo + W, preimage(dirty_reading(query[lo:lo + W], 1, rng), unit[1], rng))
+    assert len(dna) == n
+    return (bytes(dna), plants) if with_plants else bytes(dna)
+
+
+def dirty_case(m):
+    """(query, DNA) of the untidy-query case of m rows."""
+    q = dirty_query(m, DIRTY_SEEDS[m])
+    return q, dirty_dna(q, DIRTY_DNA_LEN, DIRTY_SEEDS[m] + 1)
+
+
+DIRTY_DNA_HEADER = "syn|chrD|1-%d" % DIRTY_DNA_LEN
+
+
+def dirty_case_files(tmp_dir, m):
+    """The case of m rows written as FASTA: (query path, DNA path, query, DNA)."""
+    import synth
+    rna, dna = dirty_case(m)
+    rna_fa, dna_fa = os.path.join(str(tmp_dir), f"dirtyq_{m}.fa"), os.path.join(str(tmp_dir), f"dirtyq_{m}_dna.fa")
+    synth.write_fasta(rna_fa, f"dirtyq_{m}", rna)
+    synth.write_fasta(dna_fa, DIRTY_DNA_HEADER, dna)
+    return rna_fa, dna_fa, rna, dna
+
+
+def triplex_rows_overlap(x, rows):
+    """Does the X line x (parse_scan) cover one of the query rows (0-based)?  Its first two fields are the 1-based query range."""
+    a, b = sorted((int(x[0]), int(x[1])))
+    return any(a - 1 <= r <= b - 1 for r in rows)
+
+
+def q2_units_that_matter(orc, rna, dna, cut=5000, step=4900):
+    """(segment, encoding) of the units in which the reference's signed lazy-F exit changes a column maximum above the unit's
+    threshold: the oracle's pre_align against the same with the exit made unsigned (the criterion of
+    test_gpu_parity._q2_units_that_matter, on the segments as the scan cuts them)."""
+    orc.lib.fo_pre_align_noq2.restype = None
+    orc.lib.fo_pre_align_noq2.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    out = []
+    for s, start in enumerate(range(0, max(1, len(dna) - (cut - step)), step)):
+        for enc in range(48):
+            t, _ = orc.encode_unit(dna[start:start + cut], enc)
+            ref = orc.pre_align(rna, t)
+            buf = (ctypes.c_int * len(t))()
+            orc.lib.fo_pre_align_noq2(rna, len(rna), t, len(t), buf)
+            if ref == list(buf):
+                continue
+            thr = int(orc.stage1_max(rna, t) * 0.8)
+            if [(c, v) for c, v in enumerate(ref) if v > thr] != [(c, v) for c, v in enumerate(buf) if v > thr]:
+                out.append((s, enc))
+    return out
+
+
+def probe_dirty_vectors():
+    """probe_random_vectors for an untidy query: the 900-nt dirty query, 40 targets planted with it (S and P requests; every fourth
+    holds N and lower-case letters) and 40 windows (A requests).  The reference probe's answers: tests/golden/probe_dirty40.rsp.gz
+    (`make_golden.py dirtyq`)."""
+    import synth
+    rng = synth._Rng(515151)
+    q = dirty_query(900, DIRTY_SEEDS[900])
+    rows = dirty_rows(q)
+    marks = rows["U"][::8] + rows["lower"][::12] + rows["N"]
+    reqs, targets, wins = [], [], []
+    for k in range(40):
+        t = bytearray(synth.planted_dna(300 + rng.below(900), 2000 + k, q, every=150, max_len=120))
+        # exact stage-2 and stage-1 readings of a window around an untidy row, forwards (a raw target is not rule-encoded)
+        for stage, at in ((2, 20), (1, 160)):
+            r = marks[rng.below(len(marks))]
+            lo = max(0, min(r - 10 - rng.below(25), len(q) - 44))
+            t[at:at + 44] = dirty_reading(q[lo:lo + 44], stage, rng)
+        if k % 4 == 3:
+            for _ in range(6):
+                i = rng.below(len(t))
+                t[i] = b"Nnacgt"[rng.below(6)] if t[i] != ord("A") else ord("a")
+        t = bytes(t)
+        targets.append(t)
+        reqs += [f"S {q.decode()} {t.decode()}", f"P {q.decode()} {t.decode()}"]
+        w = t[:60 + rng.below(130)]
+        wins.append(w)
+        reqs.append(f"A {q.decode()} {w.decode()}")
+    return q, targets, wins, reqs
+
+
 def syn10k_ntmax_inputs():
     """BASELINE config 5 in miniature: a 10 kb synthetic lncRNA and 12 kb of DNA planted with it (byte overflows, 16-bit
     re-runs).  The reference probe's `scan -detail 0 -na 1000` of them: tests/golden/syn10k_na1000.scan.gz."""

@@ -425,3 +425,19 @@ def test_cli_record_sets_and_oligos(mod, golden_dir, tmp_path):
     wanto = {f"{n}-recs.hist.tsv": mod.hist_tsv(hs[q], n, cs[q], seed=3) for q, n in enumerate(names)}
     assert run("oligos", "recs.fa", "panel.fa", "--oligos", *args) == wanto
     assert run("oligos2", "recs.fa", "panel.fa", "--oligos", *args, "--devices", "0,0") == wanto
+
+
+# ---- an untidy query ----------------------------------------------------------------------------------------------------------------
+def test_untidy_query(mod):
+    """helpers.dirty_case(700) (U, lower case, N R Y n u in the query) under rule 8, three segments: the histogram of the restated
+    potential (U read as A, every other letter -4)."""
+    rna, dna = helpers.dirty_case(700)
+    p = mod.default_params(rule=8, strand=0)
+    P, _ = expected_potential(rna, dna, p)
+    assert int(P.max()) >= 150
+    e = _engine(mod, rna)
+    res, h, ctl = e.scan_hist(dna, p)
+    e.close()
+    assert res is None and ctl == []
+    _same(h, bincount4(P), "untidy query")
+    assert (h.positions, h.units, h.saturated_units, h.pending) == (len(dna), 6, 0, [])

@@ -359,3 +359,28 @@ def test_cli_panel(mod, golden_dir, tmp_path):
     assert run("plain2", "testDNA.fa", "--devices", "0,0") == plain
     assert run("all", "recs.fa", "--all-records") == sets
     assert run("all2", "recs.fa", "--all-records", "--devices", "0,0") == sets
+
+
+# ---- untidy oligos -----------------------------------------------------------------------------------------------------------------
+def test_untidy_oligos(mod):
+    """A panel of 40-nt oligos cut from helpers.dirty_query(700): one from its T-to-U stretch, one around an N / IUPAC letter, one in
+    lower case, and a tidy one, against 5 kb planted with their gapped pre-images under rule 8 (encodings 26 and 27, under which
+    every letter has a pre-image): tracks and sites against the restatement (U read as A, every other letter -4)."""
+    q = helpers.dirty_query(700, helpers.DIRTY_SEEDS[700])
+    (u0, _), (l0, _), _ = helpers.dirty_zones(700)
+    n0 = helpers.dirty_rows(q)["N"][1]
+    oligos = [q[u0 + 10:u0 + 50], q[n0 - 20:n0 + 20], q[l0 + 10:l0 + 50], q[400:440]]
+    assert b"U" in oligos[0] and set(oligos[1]) & set(b"NRYnu") and oligos[2].islower() and set(oligos[3]) <= set(b"ACGT")
+    p = mod.default_params(rule=8, strand=0)
+    dna = _planted_record(oligos, p, 5000, 1610)
+    e = _engine(mod)
+    sites, tracks = e.scan_oligos(oligos, dna, p, min_value=60, track_bin=1)
+    e.close()
+    for k, o in enumerate(oligos):
+        want, top = expected_tracks(o, dna, p)
+        P, per_enc = expected_potential(o, dna, p)
+        print(f"oligo {k} ({o.decode()}): largest potential per class {top}")
+        assert max(top) >= 100
+        _same(tracks[k][0].array(), want, f"track of oligo {k}")
+        _same(sites[k][0].array(), sites_from(P, per_enc, 60), f"sites of oligo {k}")
+        assert len(sites[k][0]) >= 1 and (sites[k][0].units, sites[k][0].saturated_units) == (4, 0)

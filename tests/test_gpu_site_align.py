@@ -393,3 +393,24 @@ def test_cli_record_sets(mod, golden_dir, tmp_path):
     base = run("reg", *args)
     assert run("rega", *args, "--sites-align") == dict(base, **{tsv: want})
     assert run("rega2", *args, "--sites-align", "--devices", "0,0") == dict(base, **{tsv: want})
+
+
+# ---- an untidy query ----------------------------------------------------------------------------------------------------------------
+def test_untidy_query(mod):
+    """helpers.dirty_case(700) (U, lower case, N R Y n u in the query) under rule 8: k_site_ends and k_site_path read the query as
+    stage 3 does (U as A, every other letter -4), and the records show the query's letters as they were written, which the
+    identity counts as mismatches and the stability scores 0.  Hits over each class of untidy row."""
+    rna, dna = helpers.dirty_case(700)
+    c = Case(rna, dna, mod.default_params(rule=8, strand=0))
+    assert c.top >= 150
+    rows = helpers.dirty_rows(rna)
+    e = _engine(mod, rna)
+    for v in (c.top, int(0.8 * c.top)):
+        want_sites = c.sites(v)
+        want_hits = c.hits(want_sites)
+        _, sites, hits = e.scan_sites_aligned(dna, c.p, min_value=v, records=False)
+        _check(sites[0], hits[0], want_sites, want_hits, f"V {v}")
+    over = {k: sum(any(h["rec"]["stari"] - 1 <= r <= h["rec"]["endi"] - 1 for r in rr) for h in want_hits) for k, rr in rows.items()}
+    print("hits over untidy rows at 0.8 of the top:", over)
+    assert min(over.values()) >= 5
+    e.close()

@@ -353,3 +353,21 @@ def test_cli_record_sets(mod, golden_dir, tmp_path):
     assert run("reg2", *args, "--sites-only", "--devices", "0,0") == {fname: want}
     plain = run("plain", "genome.fa", "--regions", "g.bed")
     assert run("both", *args) == dict(plain, **{fname: want})
+
+
+# ---- an untidy query ----------------------------------------------------------------------------------------------------------------
+def test_untidy_query(mod):
+    """helpers.dirty_case(700) (U, lower case, N R Y n u in the query) under rule 8, whose units hold the plants across those rows:
+    sites at the top, at 0.8 of it and at the median against the restatement (U read as A, every other letter -4)."""
+    rna, dna = helpers.dirty_case(700)
+    p = mod.default_params(rule=8, strand=0)
+    P, per_enc = expected_potential(rna, dna, p)
+    top, median = int(P.max()), int(np.median(P[P > 0]))
+    assert top >= 150
+    e = _engine(mod, rna)
+    for v in (top, int(0.8 * top), median):
+        want = sites_from(P, per_enc, v)
+        _, sites = e.scan_sites(dna, p, min_value=v, records=False)
+        _same(sites[0].array(), want, f"V {v}")
+        assert (sites[0].units, sites[0].saturated_units, len(sites[0])) == (6, 0, len(want)) and len(want) >= 1
+    e.close()

@@ -297,3 +297,20 @@ def test_cli_writes_the_profile_table(mod, golden_dir, tmp_path):
                                ["--screen", "--regions", "r.bed"])):
         for flag in ("--tfo-profile", "--tfo-profile-only"):
             assert run(f"bad{k}{flag[-4:]}", flag, *extra, status=2) == []
+
+
+def test_untidy_query(mod):
+    """helpers.dirty_case(700): a T-to-U stretch, a lower-case stretch and scattered N R Y n u, x 10 kb whose plants cross those rows
+    (rule 8: 6 units).  The row maxima of the untidy rows themselves are part of the profile: a U row pairs like A, a lower-case row
+    like its capital, and an N / IUPAC row only carries what the diagonal brought (-4)."""
+    rna, dna = helpers.dirty_case(700)
+    p = mod.default_params(rule=8, strand=0)
+    want, units = expected_profile(rna, [dna], p)
+    rows = helpers.dirty_rows(rna)
+    tops = {k: int(want[:, r].max()) for k, r in rows.items()}
+    print("largest row maximum per class:", want.max(axis=1).tolist(), "; over the untidy rows:", tops)
+    assert units == 6 and min(tops.values()) >= 100
+    for f16 in (1, 0):
+        got = _profile(mod, rna, dna, p, dp_f16=f16)
+        assert (got.m, got.units, got.saturated_units) == (len(rna), 6, 0)
+        _same(got.array(), want, f"dp_f16 {f16}")

@@ -241,3 +241,20 @@ def test_cli_writes_the_track_file(mod, golden_dir, tmp_path):
     assert run("acc", "--track", "25", "--accumulate-records", status=2) == []
     assert run("sim", "--track", "25", "-F", status=2) == []
     assert run("alone", "--track-only", status=2) == []
+
+
+def test_untidy_query(mod):
+    """A query with a T-to-U stretch, a lower-case stretch and scattered N R Y n u (helpers.dirty_case(700)) x 10 kb whose plants
+    cross those rows at full stage-2 score; rule 8 = encodings 26 and 27, which hold most of them (6 units).  k_scan reads U as A and
+    every letter outside ACGU as -4, in the f16 and in the integer main pass; the separate stage-1 pass that such a query switches
+    on for every unit must leave the track alone."""
+    rna, dna = helpers.dirty_case(700)
+    p = mod.default_params(rule=8, strand=0)
+    want, top = expected_tracks(rna, dna, p)
+    as_t, _ = expected_tracks(rna.replace(b"U", b"T"), dna, p)
+    print("largest column maximum per class:", top, "; values that change when U is read as T:", int((as_t != want).sum()))
+    assert max(top) >= 150 and (as_t != want).sum() > 1000
+    for f16 in (1, 0):
+        t = _track(mod, rna, dna, p, dp_f16=f16)
+        assert (t.bin, t.nbins, t.units, t.saturated_units) == (1, len(dna), 6, 0)
+        _same(t.array(), want, f"dp_f16 {f16}")

@@ -250,3 +250,75 @@ def test_oracle_on_selected_peaks(oracle_build, golden_dir, peaks, tmp_path, que
         for level in (1, 2):
             out = helpers.oracle_cli(oracle_build, "tfoclass", rna, dna, "-level", str(level), "-threads", "8")
             assert out == files[(i, f"TFOclass{level}")], (where, level)
+
+
+# ---- untidy queries: U, lower case, N and IUPAC letters in the lncRNA (`make_golden.py dirtyq`) ---------------------------------
+def dirty_conditions(orc, rna, dna, units):
+    """What the inputs of helpers.dirty_case must hold, from the oracle: the triplexes over each class of untidy row, the units
+    whose stage-1 maximum exceeds every stage-2 column maximum (the two alphabets disagree about the threshold) as (segment,
+    encoding, candidates), and the hazard (Q2) units that matter."""
+    rows = helpers.dirty_rows(rna)
+    xs = [x for u in units for x in u["triplexes"]]
+    over = {k: sum(helpers.triplex_rows_overlap(x, r) for x in xs) for k, r in rows.items()}
+    disagree = []
+    for u in units:
+        t, _ = orc.encode_unit(dna[u["seg"] * 4900:u["seg"] * 4900 + 5000], u["enc"])
+        assert len(t) == u["n"]
+        assert orc.stage1_max(rna, t) == u["stage1"]
+        if u["stage1"] > max(orc.pre_align(rna, t)):
+            disagree.append((u["seg"], u["enc"], u["ncand"]))
+    return over, disagree, helpers.q2_units_that_matter(orc, rna, dna) if len(rna) >= 1300 else []
+
+
+@pytest.mark.parametrize("m", helpers.DIRTY_LENGTHS)
+def test_dirty_query_scan_and_input_conditions(oracle_build, golden_dir, tmp_path, m):
+    """The oracle equals the reference on queries with a T-to-U stretch, a lower-case stretch and scattered N R Y n u (stage 1 reads U
+    as T and the rest as N = -1; stages 2 and 3 read U as A and the rest as -4), and the generated inputs do what they are for:
+    at least 5 expected triplexes over a U row, 5 over a lower-case row and 5 over an N / IUPAC row (the 100-nt query must hold the
+    U and the lower-case class; its last third is 34 rows with one or two untidy letters), at least 3 units whose stage-1 maximum
+    exceeds every stage-2 column maximum, one of them with a candidate, and for 1 300 and 4 000 rows a hazard unit."""
+    rna_fa, dna_fa, rna, dna = helpers.dirty_case_files(tmp_path, m)
+    zones = helpers.dirty_rows(rna)
+    assert all(zones.values()) and set(rna) - set(b"ACGT") >= set(b"Uacgt") and set(rna) & set(b"NRYnu")
+    assert set(dna) <= set(b"ACGT")
+    gold = helpers.gunzip(os.path.join(golden_dir, f"dirtyq_{m}.scan.gz"))
+    assert helpers.oracle_cli(oracle_build, "scan", rna_fa, dna_fa, "-detail", "0", "-threads", "8") == gold
+    meta, units = helpers.parse_scan(gold)
+    assert meta["m"] == m and meta["nseg"] == 3 and len(units) == 144 and not meta["skipped"]
+    over, disagree, q2 = dirty_conditions(helpers.Oracle(oracle_build), rna, dna, units)
+    print(f"m {m}: triplexes over untidy rows {over}, units with stage 1 above stage 2 {len(disagree)} ({sum(c > 0 for _, _, c in disagree)} with candidates), Q2 units {q2}")
+    for kind in ("U", "lower") if m == 100 else ("U", "lower", "N"):
+        assert over[kind] >= 5, (kind, over)
+    assert len(disagree) >= 3 and any(c > 0 for _, _, c in disagree)
+    if m >= 1300:
+        assert len(q2) == helpers.DIRTY_Q2_UNITS[m] >= 1
+        out = helpers.oracle_cli(oracle_build, "tfosorted", rna_fa, dna_fa, "-lg", "30", "-threads", "8")
+        assert out == open(os.path.join(golden_dir, f"dirtyq_{m}.TFOsorted"), "rb").read()
+        for level in (1, 2):
+            out = helpers.oracle_cli(oracle_build, "tfoclass", rna_fa, dna_fa, "-lg", "30", "-level", str(level), "-threads", "8")
+            assert out == open(os.path.join(golden_dir, f"dirtyq_{m}.TFOclass{level}"), "rb").read()
+
+
+def test_dirty_query_probe_vectors(oracle_build, golden_dir):
+    """S, P and A answers of the reference probe for a 900-nt untidy query against 40 targets and windows (every fourth with N and
+    lower-case letters of its own): Oracle.stage1_max, pre_align and align."""
+    o = helpers.Oracle(oracle_build)
+    q, targets, wins, reqs = helpers.probe_dirty_vectors()
+    rsp = helpers.gunzip(os.path.join(golden_dir, "probe_dirty40.rsp.gz")).decode().splitlines()
+    assert len(rsp) == len(reqs) == 120
+    assert any(set(t) & set(b"Nn") for t in targets) and any(set(t) & set(b"acgt") for t in targets)
+    above, aligned = 0, 0
+    for k in range(40):
+        s1 = o.stage1_max(q, targets[k])
+        cols = o.pre_align(q, targets[k])
+        assert s1 == int(rsp[3 * k].split(" ")[1]), k
+        assert cols == [int(x) for x in rsp[3 * k + 1].split(" ")[2:]], k
+        above += s1 > max(cols)
+        g = rsp[3 * k + 2].split(" ")
+        five, cig = o.align(q, wins[k])
+        if int(g[1]) == 0:
+            assert five[0] == 0, k
+        else:
+            assert five == tuple(int(x) for x in g[1:6]) and (cig or "*") == g[6], k
+            aligned += 1
+    assert above >= 10 and aligned >= 30       # the alphabets disagree in many targets, and the windows do align
