@@ -497,19 +497,6 @@ int fasim_scan_records(fasim_engine* E, const char* const* rnas, const int32_t* 
 }
 
 // ---- per-base potential tracks ----------------------------------------------------------------------------------------
-static int text_out(const std::string& s, char** text, int64_t* text_len);
-static fasim_track* track_alloc(int64_t nbins, int32_t bin)
-{
-	fasim_track* t = (fasim_track*)calloc(1, sizeof(fasim_track));
-	if (!t) return nullptr;
-	t->nbins = nbins; t->bin = bin;
-	for (int c = 0; c < FASIM_TRACK_CLASSES; c++) {
-		t->v[c] = (uint16_t*)calloc((size_t)std::max<int64_t>(1, nbins), sizeof(uint16_t));
-		if (!t->v[c]) { fasim_track_free(t); return nullptr; }
-	}
-	return t;
-}
-
 void fasim_track_free(fasim_track* t)
 {
 	if (!t) return;
@@ -565,7 +552,7 @@ int fasim_scan_track(fasim_engine* E, const char* const* rnas, const int32_t* rn
 	}
 	std::vector<fasim_result*> own((size_t)nquery, nullptr);
 	fasim_result** outs = out_results ? out_results : own.data();
-	const int rc = scan_core(E, nq ? rnas : nullptr, nq ? rna_lens : nullptr, nq, dna, dna_len, seg_first, seg_count, pp, outs, &tr);
+	const int rc = scan_core(E, nq ? rnas : nullptr, nq ? rna_lens : nullptr, nq, dna, dna_len, seg_first, seg_count, pp, outs, { &tr });
 	if (rc) { drop(); return rc; }
 	for (int q = 0; q < nquery; q++) { out_tracks[q]->units = outs[q]->stats.units; out_tracks[q]->saturated_units = tr.sat[(size_t)q]; }
 	for (fasim_result* r : own) fasim_result_free(r);
@@ -605,7 +592,7 @@ int fasim_scan_records_track(fasim_engine* E, const char* const* rnas, const int
 	}
 	std::vector<fasim_result*> own(out_results ? 0 : nout, nullptr);
 	fasim_result** outs = out_results ? out_results : own.data();
-	rc = scan_records_core(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, outs, totals, &tr);
+	rc = scan_records_core(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, outs, totals, { &tr });
 	if (rc) { drop(); return rc; }
 	if (out_tracks) for (size_t o = 0; o < nout; o++) { out_tracks[o]->units = outs[o]->stats.units; out_tracks[o]->saturated_units = tr.sat[o]; }
 	for (fasim_result* r : own) fasim_result_free(r);
@@ -659,7 +646,7 @@ int fasim_scan_tfo_profile(fasim_engine* E, const char* const* rnas, const int32
 	}
 	std::vector<fasim_result*> own(out_results ? 0 : nout, nullptr);
 	fasim_result** outs = out_results ? out_results : own.data();
-	rc = scan_records_core(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, outs, totals, nullptr, &pr);
+	rc = scan_records_core(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, outs, totals, { &pr });
 	for (fasim_result* r : own) fasim_result_free(r);
 	if (rc) { drop(); return rc; }
 	for (size_t o = 0; o < nprof; o++) { out_profiles[o]->units = pr.units[o]; out_profiles[o]->saturated_units = pr.sat[o]; }
@@ -855,7 +842,7 @@ int fasim_scan_records_sites(fasim_engine* E, const char* const* rnas, const int
 	sr.runs.resize(nout); sr.sat.assign(nout, 0); sr.mu.reset(new std::mutex[(size_t)nquery]);
 	std::vector<fasim_result*> own(out_results ? 0 : nout, nullptr);
 	fasim_result** outs = out_results ? out_results : own.data();
-	rc = scan_records_core(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, outs, totals, nullptr, nullptr, &sr);
+	rc = scan_records_core(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, outs, totals, { &sr });
 	if (rc) { for (fasim_result* r : own) fasim_result_free(r); return rc; }
 	auto drop = [&]() {
 		for (size_t o = 0; o < nout; o++) { fasim_sites_free(out_sites[o]); out_sites[o] = nullptr; if (out_results) { fasim_result_free(out_results[o]); out_results[o] = nullptr; } }
@@ -984,15 +971,6 @@ static int records_to_list(const fasim_triplex* recs, int64_t count, const char*
 		if (t.nt > p->cLength && (t.stari + t.endi) / 2 - p->cDistance < 0 && !(flags & FASIM_TAIL_CLAMP_CLUSTER))
 			return fail(nullptr, FASIM_E_UNSUPPORTED, "a triplex mid-point lies within -ds of the query start: the reference's clustering does not terminate for this input (FASIM_TAIL_CLAMP_CLUSTER / fasim --clamp-cluster gives a defined result)");
 	}
-	return FASIM_OK;
-}
-
-static int text_out(const std::string& s, char** text, int64_t* text_len)
-{
-	char* buf = (char*)malloc(s.size() + 1);
-	if (!buf) return fail(nullptr, FASIM_E_NOMEM, "out of memory");
-	memcpy(buf, s.data(), s.size()); buf[s.size()] = 0;
-	*text = buf; *text_len = (int64_t)s.size();
 	return FASIM_OK;
 }
 

@@ -160,6 +160,16 @@ inline int fail(fasim_engine* e, int code, const char* fmt, ...)
 	return code;
 }
 
+// a malloc'ed, NUL-terminated copy of `s`, as the text functions of the C-ABI return it
+inline int text_out(const std::string& s, char** text, int64_t* text_len)
+{
+	char* buf = (char*)malloc(s.size() + 1);
+	if (!buf) return fail(nullptr, FASIM_E_NOMEM, "out of memory");
+	memcpy(buf, s.data(), s.size()); buf[s.size()] = 0;
+	*text = buf; *text_len = (int64_t)s.size();
+	return FASIM_OK;
+}
+
 #define HIPOK(call) do { hipError_t _e = (call); if (_e != hipSuccess) return fail(E, FASIM_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_e), __FILE__, __LINE__); } while (0)
 
 // stage-2/3 alphabet (ssw_cpp.cpp:13-26): A,a,U,u -> 0 ; C,c -> 1 ; G,g -> 2 ; T,t -> 3 ; else 4
@@ -388,46 +398,68 @@ struct SegTable {
 	int64_t size() const { return (int64_t)rec.size(); }
 };
 
+// ---- products of a scan: what a call takes from k_scan's column and row maxima besides the hits -----------------------------------
+struct BatchCtx;
+// One product of one call (potential tracks, the lncRNA's profile, sites, histogram), shared by the call's workers.  Behind the main
+// pass of a batch run_scan_v2 runs fold() of every product of the call; the worker runs merge() after the batch's next stream
+// synchronisation.  fasim_scan_oligos (engine_oligos.cpp) does the same per oligo behind k_scan_short.
+struct ScanProduct {
+	bool only = false;                           // no hits, no hazard re-run, no stage 3, no records
+	std::unique_ptr<std::mutex[]> mu;            // [query]: merge() works under the query's
+	virtual ~ScanProduct() = default;
+	virtual bool wants_rowmax() const { return false; }      // k_scan's main pass and its integer re-run leave their row maxima in E->rowmax16
+	virtual bool merges_empty() const { return false; }      // a batch whose segments are all skipped is merged too
+	virtual const char* needs_scan() const = 0;              // the refusal of a batch that did not go through the systolic scan kernel
+	// the batch's host preparation, the launches over E->colmax16 (E->rowmax16) and the copies into C's vectors for query q; the copies
+	// complete at the next synchronisation of E->st
+	virtual int fold(fasim_engine* E, BatchCtx& C, int q) const = 0;
+	// C's vectors of a finished scan phase, segments [b0, b1) of the call's table, into the call's arrays of query q (may throw std::bad_alloc)
+	virtual void merge(const BatchCtx& C, const SegTable& T, int64_t b0, int64_t b1, int q) = 0;
+};
+// the products of one call in fold and merge order; empty: a plain scan
+typedef std::vector<ScanProduct*> ScanProducts;
+inline bool any_only(const ScanProducts& ps) { for (const ScanProduct* x : ps) if (x->only) return true; return false; }
+inline bool any_rowmax(const ScanProducts& ps) { for (const ScanProduct* x : ps) if (x->wants_rowmax()) return true; return false; }
+
 // ---- potential tracks (fasim_scan_track, track.hip) ------------------------------------------------------------------------------
 // One call: the record's arrays (those of the fasim_track objects the call returns), which the workers fold their batches' slices
 // into as soon as a batch's scan phase ends; a bin that two batches touch (overlapping segments) is merged under the query's mutex.
-struct TrackReq {
-	int bin = 1; bool only = false;              // bin == 0: peaks only, no arrays; only: no stage 3, no records
+struct TrackReq : ScanProduct {
+	int bin = 1;                                 // bin == 0: peaks only, no arrays
 	int nrec = 1;                                // records of the call (fasim_scan_track: 1); o = query * nrec + record below
 	std::vector<int64_t> nbins;                  // [record]
 	std::vector<uint16_t*> v;                    // [o * 4 + class][nbins[record]] (empty with bin == 0)
 	fasim_peak* peaks = nullptr;                 // [o * 4 + class], preset to (0, -1, -1), or NULL: no peaks (fasim_scan_records_track)
 	std::vector<int64_t> sat;                    // [o]: units with a saturated column maximum
-	std::unique_ptr<std::mutex[]> mu;            // [query]
+	const char* needs_scan() const override { return "potential tracks need the systolic scan kernel"; }
+	int fold(fasim_engine* E, BatchCtx& C, int q) const override;
+	void merge(const BatchCtx& C, const SegTable& T, int64_t b0, int64_t b1, int q) override;
 };
-// One batch, handed to run_scan_v2: where k_track's result goes
-struct TrackFold {
-	int bin = 1, nseg = 0, nenc = 0, nchunk = 0; bool only = false;
-	TrackTable tab;
-	const int32_t* phase = nullptr;              // [nseg] host: record position of the segment's first base, modulo bin
-	std::vector<uint16_t>* out = nullptr;        // [nseg * nchunk][4][track_slice_stride(bin)] (bin >= 1)
-	std::vector<uint8_t>* sat = nullptr;         // [unit]
-	std::vector<TrackPeak>* peaks = nullptr;     // [nseg * nchunk][4], or NULL: no peaks
-};
+inline fasim_track* track_alloc(int64_t nbins, int32_t bin)
+{
+	fasim_track* t = (fasim_track*)calloc(1, sizeof(fasim_track));
+	if (!t) return nullptr;
+	t->nbins = nbins; t->bin = bin;
+	for (int c = 0; c < FASIM_TRACK_CLASSES; c++) {
+		t->v[c] = (uint16_t*)calloc((size_t)std::max<int64_t>(1, nbins), sizeof(uint16_t));
+		if (!t->v[c]) { fasim_track_free(t); return nullptr; }
+	}
+	return t;
+}
 
 // ---- per-base profile of the lncRNA (fasim_scan_tfo_profile, rowfold.hip) ---------------------------------------------------------
 // One call: the arrays of the fasim_tfo_profile objects the call returns, per o = query * nrec + record (per_record) or per query;
 // the workers fold their batches' groups into them under the query's mutex as soon as a batch's scan phase ends.
-struct TfoReq {
-	bool only = false, per_record = false;       // only: no stage 3, no records
+struct TfoReq : ScanProduct {
+	bool per_record = false;
 	int nrec = 1;
 	std::vector<int32_t> m;                      // [query]: rows of the result
 	std::vector<uint16_t*> v;                    // [o * 4 + class][m[query]]
 	std::vector<int64_t> units, sat;             // [o]: units folded in, units with a saturated row maximum
-	std::unique_ptr<std::mutex[]> mu;            // [query]
-};
-// One batch, handed to run_scan_v2: the groups of k_rowfold and where its result goes
-struct RowFold {
-	int nseg = 0, nenc = 0; bool only = false;
-	TrackTable tab;
-	std::vector<int32_t> gfirst;                 // [groups + 1]: group g = segments [gfirst[g], gfirst[g + 1]) of the batch
-	std::vector<uint16_t>* out = nullptr;        // [groups][4][16 * ceil(m/16)]
-	std::vector<uint8_t>* sat = nullptr;         // [unit]
+	bool wants_rowmax() const override { return true; }
+	const char* needs_scan() const override { return "the lncRNA's profile needs the systolic scan kernel"; }
+	int fold(fasim_engine* E, BatchCtx& C, int q) const override;
+	void merge(const BatchCtx& C, const SegTable& T, int64_t b0, int64_t b1, int q) override;
 };
 
 // ---- sites above a fixed potential (fasim_scan_records_sites, sites.hip) -------------------------------------------------------------
@@ -435,12 +467,14 @@ struct RowFold {
 struct HostRun { int64_t start, end, pos; int32_t value, enc, cls; };
 // One call: per o = query * nrec + record the runs of the record's slices as k_sites cut them, appended by the workers under the
 // query's mutex as soon as a batch's scan phase ends; sorted, united and joined when the call ends (sites_build in fasim_scan_records_sites, engine.cpp)
-struct SitesReq {
-	int min_value = 1, max_gap = 0; bool only = false;      // only: no stage 3, no records
+struct SitesReq : ScanProduct {
+	int min_value = 1, max_gap = 0;
 	int nrec = 1;
 	std::vector<std::vector<HostRun>> runs;      // [o]
 	std::vector<int64_t> sat;                    // [o]: units with a saturated column maximum
-	std::unique_ptr<std::mutex[]> mu;            // [query]
+	const char* needs_scan() const override { return "sites need the systolic scan kernel"; }
+	int fold(fasim_engine* E, BatchCtx& C, int q) const override;
+	void merge(const BatchCtx& C, const SegTable& T, int64_t b0, int64_t b1, int q) override;
 };
 // The second phase of fasim_scan_records_sites_aligned (engine_site_align.cpp, site_align.hip): after the call's sites are final,
 // every site of (query q, record r) gets its hit.  The phase runs chunk by chunk on the engine's own stream and buffers (sa_*).
@@ -455,14 +489,6 @@ struct SiteAlignReq {
 };
 int run_site_align(fasim_engine* E, SiteAlignReq& R);
 void site_hits_free(fasim_site_hits* h);
-// One batch, handed to run_scan_v2: where k_sites' result goes
-struct SitesFold {
-	int min_value = 1, nseg = 0, nenc = 0, nchunk = 0; bool only = false;
-	TrackTable tab;
-	std::vector<uint32_t>* counts = nullptr;     // [nseg * nchunk][4]
-	std::vector<SiteRun>* runs = nullptr;        // in (slice, class, position) order
-	std::vector<uint8_t>* sat = nullptr;         // [unit]
-};
 
 // ---- histogram of the potential (fasim_scan_records_hist, hist.hip, engine_hist.cpp) ---------------------------------------------
 // One side of the overlap of two neighbouring segments of a record, as the values of that segment alone: boundary b of a record is
@@ -475,8 +501,7 @@ struct HistEdgeKey {
 };
 // One call: per query the counters of the fasim_hist the call returns, and the zone sides that wait for their partner (the other
 // batch, or the merge of the shards when the partner lies outside the call's range).  The workers add under the query's mutex.
-struct HistReq {
-	bool only = false;                           // no stage 3, no records
+struct HistReq : ScanProduct {
 	int64_t step = 0, overlap = 0;               // cutLength - overlapLength, overlapLength
 	std::vector<int64_t> rec_nseg;               // [record]: segments of the whole record
 	std::vector<int32_t> qtop;                   // [query]: largest value the query can reach (the copy back stops there)
@@ -484,27 +509,25 @@ struct HistReq {
 	std::vector<int64_t> positions, units, sat;  // [query]
 	std::vector<std::map<HistEdgeKey, HistSide>> open;      // [query]: sides whose partner has not arrived
 	std::vector<std::vector<std::pair<HistEdgeKey, HistSide>>> pending;   // [query]: sides whose partner lies outside the call's range
-	std::unique_ptr<std::mutex[]> mu;            // [query]
-};
-// One batch, handed to run_scan_v2: the zone bounds of its kept segments and where k_hist's result goes
-struct HistFold {
-	int nseg = 0, nenc = 0, nchunk = 0, zstride = 0, top = HIST_BINS - 1; bool only = false;
-	TrackTable tab;
-	const int32_t* zone = nullptr;               // [nseg][2] host
-	std::vector<uint32_t>* hist = nullptr;       // [4][top + 1]
-	std::vector<uint16_t>* zones = nullptr;      // [nseg][2][4][zstride]
-	std::vector<uint8_t>* sat = nullptr;         // [unit]
+	bool merges_empty() const override { return true; }      // (the positions of skipped segments lie in bin 0)
+	const char* needs_scan() const override { return "the histogram of the potential needs the systolic scan kernel"; }
+	int fold(fasim_engine* E, BatchCtx& C, int q) const override;
+	void merge(const BatchCtx& C, const SegTable& T, int64_t b0, int64_t b1, int q) override;
 };
 
 struct BatchCtx {
 	UnitBatch B;
-	std::vector<uint32_t> hist; std::vector<uint16_t> hist_zones; std::vector<uint8_t> hist_sat; std::vector<int32_t> hist_zone;      // fasim_scan_records_hist: k_hist's counters and zones of this batch
-	int hist_zstride = 0, hist_top = 0; bool hist_done = false;
-	std::vector<uint32_t> site_counts; std::vector<SiteRun> site_runs; std::vector<uint8_t> site_sat; bool sites_done = false;      // fasim_scan_records_sites: k_sites' runs of this batch
-	std::vector<uint16_t> rowfold; std::vector<uint8_t> row_sat; std::vector<int32_t> row_gfirst;      // fasim_scan_tfo_profile: k_rowfold's groups of this batch
-	bool rows_done = false;
-	std::vector<uint16_t> track; std::vector<uint8_t> track_sat; int track_nchunk = 0;      // fasim_scan_track: k_track's slices of this batch
-	std::vector<TrackPeak> track_peaks; bool track_done = false;                            // fasim_scan_records_track: its peaks; k_track ran
+	// what the products' folds leave of this batch (ScanProduct::fold): `folded` once run_scan_v2 has run them
+	bool folded = false;
+	TrackTable tab; int track_nchunk = 0;              // class table of the enabled encodings, TRACK_CHUNK slices per segment (batch_encode)
+	std::vector<uint32_t> hist; std::vector<uint16_t> hist_zones; std::vector<uint8_t> hist_sat; std::vector<int32_t> hist_zone;      // fasim_scan_records_hist: k_hist's counters, zones and zone bounds
+	int hist_zstride = 0, hist_top = 0;
+	std::vector<uint32_t> site_counts; std::vector<SiteRun> site_runs; std::vector<uint8_t> site_sat;      // fasim_scan_records_sites: k_sites' runs
+	std::vector<uint16_t> rowfold; std::vector<uint8_t> row_sat; std::vector<int32_t> row_gfirst;      // fasim_scan_tfo_profile: k_rowfold's groups
+	std::vector<uint16_t> track; std::vector<uint8_t> track_sat;      // fasim_scan_track: k_track's slices
+	std::vector<TrackPeak> track_peaks;                               // fasim_scan_records_track: its peaks
+	// the folds' large vectors, once merged: the batch's stage 3 follows
+	void release_folded() { std::vector<uint16_t>().swap(rowfold); std::vector<uint16_t>().swap(track); std::vector<SiteRun>().swap(site_runs); std::vector<uint16_t>().swap(hist_zones); }
 	int tstride = 0, nenc = 0, nseg = 0;
 	int64_t step = 0;
 	// per kept segment of the batch: device start (relative to the batch's DNA on the device), length, index within its record
@@ -530,45 +553,35 @@ int run_striped(fasim_engine* E, StripedMode mode, bool word, const std::vector<
 int prep_striped_window(fasim_engine* E, StripedMode mode, bool word, StripedLaunch& L, bool* used);
 int run_stage1(fasim_engine* E, const UnitBatch& B, std::vector<int>& score, int64_t* word_reruns);
 int run_stage2(fasim_engine* E, const UnitBatch& B);
-int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& unit_needs_stage1, ScanOut& out, fasim_scan_stats* st, const TrackFold* tf = nullptr,
-	const RowFold* rf = nullptr, const SitesFold* sf = nullptr, const HistFold* hf = nullptr);
+// the products' folds run behind the main pass (and its integer re-run) of batch C, for query q; 1: the query does not fit the kernel
+int run_scan_v2(fasim_engine* E, BatchCtx& C, const std::vector<char>& unit_needs_stage1, ScanOut& out, fasim_scan_stats* st, const ScanProducts& products, int q);
 int load_raw_targets(fasim_engine* E, const char* targets, const int64_t* offsets, const int32_t* lens, int nprob, bool stage1, UnitBatch& B);
 int need_query(fasim_engine* E);
 int run_align(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb>& W, std::vector<AlignResult>& out, std::vector<uint32_t>& cigars, fasim_scan_stats* stats);
 int run_align_v2(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb>& W, std::vector<AlignResult>& out, std::vector<uint32_t>& cigars, fasim_scan_stats* stats);
 int stage3_range(fasim_engine* E, BatchCtx& C, int ua, int ub, fasim_scan_stats& st);
 int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_t* dna_dev, int64_t b0, int64_t b1,
-	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st, const TrackReq* tr = nullptr,
-	const TfoReq* pr = nullptr, const SitesReq* sr = nullptr, const HistReq* hr = nullptr, int q = 0);
-// the head of a batch (segments kept, DNA staged, k_encode) and the folds and host merges behind a batch's column maxima in
-// E->colmax16, shared by scan_batch / run_scan_v2 and fasim_scan_oligos (engine_oligos.cpp)
+	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st, const ScanProducts& products, int q);
+// the head of a batch (segments kept, DNA staged, k_encode, class table), shared by scan_batch and fasim_scan_oligos (engine_oligos.cpp)
 int batch_encode(fasim_engine* E, const char* dna, const SegTable& T, const uint8_t* dna_dev, int64_t b0, int64_t b1,
 	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st, int64_t m);
-int run_track_fold(fasim_engine* E, const UnitBatch& B, const TrackFold* tf);
-int run_sites_fold(fasim_engine* E, const UnitBatch& B, const SitesFold* sf);
-int run_hist_fold(fasim_engine* E, const UnitBatch& B, const HistFold* hf);
-// engine_hist.cpp: the zone bounds of a batch's kept segments into C.hist_zone and the fold that points at C's vectors; the batch's
-// counters, zones and skipped segments [b0, b1) of the call's segment table into the arrays of query q
-void hist_prepare(BatchCtx& C, const HistReq& hr, const TrackTable& tab, int q, HistFold& hf);
-void merge_hist(const BatchCtx& C, const SegTable& T, int64_t b0, int64_t b1, HistReq& hr, int q);
+// engine_hist.cpp: the request of a call and its results
 bool hist_req_init(HistReq& hr, fasim_hist** out_hists, int nquery, const int32_t* qlens, const int64_t* rec_len, int nrec, const fasim_params& p, bool only);
 int hist_req_finish(fasim_engine* E, HistReq& hr, fasim_hist** out_hists, int nquery);
 int check_records_args(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, const fasim_params* pp);
 int check_track_source(fasim_engine* E, const int32_t* rna_lens, int32_t nq, const fasim_params* pp, const char* what = "potential tracks");
-void merge_track(const BatchCtx& C, TrackReq& tr, int q);
-void merge_site_runs(const BatchCtx& C, SitesReq& sr, int q);
 int sim_forward_units(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, const int32_t* unit_len_dev, const int32_t* unit_len_host,
 	int first, int nunit, const int64_t* mins, std::atomic<int>* ready, std::vector<std::vector<fasim_sim_node>>& lists);
 int sim_resweep_rounds(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, const int32_t* unit_len_dev, const int32_t* unit_len_host,
 	int first, int cnt, SimUnit* const* units, int nthreads);
 int pack_result(fasim_engine* E, std::vector<HostTriplex>& all, const fasim_scan_stats& st, fasim_result** out);
 int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna, int64_t dna_len,
-	int64_t seg_first, int64_t seg_count, const fasim_params* pp, fasim_result** outs, TrackReq* tr = nullptr);
+	int64_t seg_first, int64_t seg_count, const fasim_params* pp, fasim_result** outs, const ScanProducts& products = {});
 // the class tables of k_track / k_rowfold: the enabled encodings by group = class + 4 * reversed
 TrackTable class_table(const std::vector<int>& encs);
 // fasim_scan_records after its argument checks: records [rec_off[r], rec_off[r] + rec_len[r]) of `dna` (NULL: the resident
 // buffer); outs[q * nrec + r], totals[q] (may be NULL)
 int scan_records_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
-	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr = nullptr, TfoReq* pr = nullptr, SitesReq* sr = nullptr, HistReq* hr = nullptr);
+	fasim_result** outs, fasim_scan_stats* totals, const ScanProducts& products = {});

@@ -4,20 +4,11 @@
 //
 // k_hist (hist.hip) counts the positions that one segment alone covers.  A position in the overlap of two segments counts once, with
 // the maximum of the two: the kernel leaves the zone values of every segment, and the worker that brings the second side of a
-// boundary counts it (merge_hist, under the query's mutex).  A side whose partner lies outside the call's segment range is counted
+// boundary counts it (HistReq::merge, under the query's mutex).  A side whose partner lies outside the call's segment range is counted
 // alone and travels in the result as a pending edge; fasim_hist_merge takes both sides out again and counts their maximum.
 #include "engine.h"
 
 namespace {
-
-int text_out(const std::string& s, char** text, int64_t* text_len)
-{
-	char* buf = (char*)malloc(s.size() + 1);
-	if (!buf) return fail(nullptr, FASIM_E_NOMEM, "out of memory");
-	memcpy(buf, s.data(), s.size()); buf[s.size()] = 0;
-	*text = buf; *text_len = (int64_t)s.size();
-	return FASIM_OK;
-}
 
 fasim_hist* hist_alloc()
 {
@@ -89,8 +80,14 @@ inline void zone_bounds(const HistReq& hr, int64_t i, int32_t L, int64_t nseg, i
 
 } // namespace
 
-void hist_prepare(BatchCtx& C, const HistReq& hr, const TrackTable& tab, int q, HistFold& hf)
+// The zone bounds of the batch's kept segments into C.hist_zone, and k_hist over the batch's column maxima in E->colmax16 into
+// C.hist / C.hist_zones / C.hist_sat: the counters of the values 0 .. qtop[q] per class, the zone values and the saturation flags.
+// The copies complete at the next synchronisation of the stream.
+int HistReq::fold(fasim_engine* E, BatchCtx& C, int q) const
 {
+	const HistReq& hr = *this;
+	const int nu = C.B.nunit;
+	int rc; hipError_t he;
 	C.hist_zone.resize((size_t)C.nseg * 2);
 	int zmax = 0;
 	for (int s = 0; s < C.nseg; s++) {
@@ -100,12 +97,34 @@ void hist_prepare(BatchCtx& C, const HistReq& hr, const TrackTable& tab, int q, 
 		zmax = std::max(zmax, std::max(h, C.slen[(size_t)s] - t));
 	}
 	C.hist_zstride = (zmax + 7) & ~7; C.hist_top = hr.qtop[(size_t)q];
-	hf.nseg = C.nseg; hf.nenc = C.nenc; hf.nchunk = C.track_nchunk; hf.zstride = C.hist_zstride; hf.top = C.hist_top; hf.only = hr.only; hf.tab = tab;
-	hf.zone = C.hist_zone.data(); hf.hist = &C.hist; hf.zones = &C.hist_zones; hf.sat = &C.hist_sat;
+	const size_t nzone = (size_t)C.nseg * 8 * (size_t)C.hist_zstride;
+	const size_t ntop = (size_t)std::min(C.hist_top, HIST_BINS - 1) + 1;
+	if (E->hist.ensure((size_t)4 * HIST_BINS * sizeof(uint32_t)) != hipSuccess || E->hist_zones.ensure(std::max<size_t>(1, nzone) * sizeof(uint16_t)) != hipSuccess ||
+		E->hist_sat.ensure((size_t)nu) != hipSuccess) {
+		(void)hipGetLastError();
+		return fail(E, FASIM_E_NOMEM, "histogram: no device memory for the counters and %zu zone values of a batch", nzone);
+	}
+	rc = upload(E, E->hist_zone, C.hist_zone.data(), sizeof(int32_t) * 2 * (size_t)C.nseg); if (rc) return rc;
+	HIPOK(hipMemsetAsync(E->hist.p, 0, (size_t)4 * HIST_BINS * sizeof(uint32_t), E->st));
+	HIPOK(hipMemsetAsync(E->hist_sat.p, 0, (size_t)nu, E->st));
+	HistLaunch H;
+	H.colmax16 = E->colmax16.as<uint16_t>(); H.seg_len = E->seg_len.as<int32_t>(); H.zone = E->hist_zone.as<int32_t>();
+	H.nseg = C.nseg; H.nenc = C.nenc; H.tstride = C.B.tstride; H.nchunk = C.track_nchunk; H.zstride = C.hist_zstride; H.tab = C.tab;
+	H.hist = E->hist.as<uint32_t>(); H.zones = E->hist_zones.as<uint16_t>(); H.sat = E->hist_sat.as<uint8_t>();
+	{ TimedScope ts(E, 4); he = launch_hist(H, E->st); }
+	if (he != hipSuccess) return fail(E, FASIM_E_HIP, "hist launch failed: %s", hipGetErrorString(he));
+	try { C.hist.resize(4 * ntop); C.hist_zones.resize(nzone); C.hist_sat.resize((size_t)nu); } catch (const std::bad_alloc&) { return fail(E, FASIM_E_NOMEM, "out of memory"); }
+	for (int c = 0; c < 4; c++)
+		HIPOK(hipMemcpyAsync(C.hist.data() + (size_t)c * ntop, E->hist.as<uint32_t>() + (size_t)c * HIST_BINS, ntop * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st));
+	if (nzone) HIPOK(hipMemcpyAsync(C.hist_zones.data(), E->hist_zones.p, nzone * sizeof(uint16_t), hipMemcpyDeviceToHost, E->st));
+	HIPOK(hipMemcpyAsync(C.hist_sat.data(), E->hist_sat.p, (size_t)nu, hipMemcpyDeviceToHost, E->st));
+	return FASIM_OK;
 }
 
-void merge_hist(const BatchCtx& C, const SegTable& T, int64_t b0, int64_t b1, HistReq& hr, int q)
+// the batch's counters, zones and skipped segments [b0, b1) of the call's segment table into the arrays of query q
+void HistReq::merge(const BatchCtx& C, const SegTable& T, int64_t b0, int64_t b1, int q)
 {
+	HistReq& hr = *this;
 	std::lock_guard<std::mutex> g(hr.mu[(size_t)q]);
 	int64_t* const* n = &hr.n[(size_t)q * 4];
 	if (C.nseg > 0) {
@@ -220,7 +239,7 @@ int fasim_scan_records_hist(fasim_engine* E, const char* const* rnas, const int3
 	};
 	std::vector<fasim_result*> own(out_results ? 0 : nout, nullptr);
 	fasim_result** outs = out_results ? out_results : own.data();
-	rc = scan_records_core(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, outs, totals, nullptr, nullptr, nullptr, &hr);
+	rc = scan_records_core(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, outs, totals, { &hr });
 	for (fasim_result* r : own) fasim_result_free(r);
 	if (rc) { drop(); return rc; }
 	try { rc = hist_req_finish(E, hr, out_hists, nquery); } catch (const std::bad_alloc&) { rc = fail(E, FASIM_E_NOMEM, "out of memory"); }

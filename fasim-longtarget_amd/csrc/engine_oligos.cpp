@@ -3,56 +3,26 @@
 //
 // A panel is many queries against one encoded batch and never reaches stage 3, so a work item here is a BATCH, not a (query, batch)
 // pair: the worker stages and encodes the batch once (batch_encode, the head of scan_batch) and then runs, per oligo, k_scan_short
-// into colmax16 and the folds fasim_scan_records_sites / _track run behind k_scan (run_sites_fold, run_track_fold) with their host
-// merges (merge_site_runs, merge_track).  The engine's own query is not involved.
+// into colmax16 and the folds that the products of the call (sites, tracks, histogram: ScanProduct, engine.h) run behind k_scan, with
+// their host merges.  The engine's own query is not involved.
 #include "engine.h"
 
 namespace {
-
-int text_out(const std::string& s, char** text, int64_t* text_len)
-{
-	char* buf = (char*)malloc(s.size() + 1);
-	if (!buf) return fail(nullptr, FASIM_E_NOMEM, "out of memory");
-	memcpy(buf, s.data(), s.size()); buf[s.size()] = 0;
-	*text = buf; *text_len = (int64_t)s.size();
-	return FASIM_OK;
-}
-
-fasim_track* track_alloc(int64_t nbins, int32_t bin)
-{
-	fasim_track* t = (fasim_track*)calloc(1, sizeof(fasim_track));
-	if (!t) return nullptr;
-	t->nbins = nbins; t->bin = bin;
-	for (int c = 0; c < FASIM_TRACK_CLASSES; c++) {
-		t->v[c] = (uint16_t*)calloc((size_t)std::max<int64_t>(1, nbins), sizeof(uint16_t));
-		if (!t->v[c]) { fasim_track_free(t); return nullptr; }
-	}
-	return t;
-}
 
 // what one call shares with its workers
 struct PanelCall {
 	int nq = 0, nrec = 0, tstride = 0;
 	std::vector<int32_t> m;                      // [oligo]
 	std::vector<uint8_t> codes;                  // [oligo][FASIM_MAX_OLIGO], stage-2 alphabet
-	const fasim_params* p = nullptr; const std::vector<int>* encs = nullptr;
-	SitesReq* sr = nullptr; TrackReq* tr = nullptr;
-	HistReq* hr = nullptr; const SegTable* T = nullptr;      // fasim_scan_oligos_hist: the request and the call's segment table
+	ScanProducts folds, merges;                  // the products wanted, in the order of their folds and of their merges
+	const SegTable* T = nullptr;
 };
 
 // one batch on one worker: `C` comes from batch_encode, the batch's target codes are in w->tcodes
 int panel_batch(fasim_engine* E, const PanelCall& P, BatchCtx& C, int64_t b0, int64_t b1)
 {
 	const UnitBatch& B = C.B;
-	const int nseg = C.nseg, nenc = C.nenc;
 	HIPOK(E->colmax16.ensure((size_t)B.nunit * B.tstride * sizeof(uint16_t)));
-	const TrackTable tab = class_table(*P.encs);
-	C.track_nchunk = track_chunks(P.p->cutLength);
-	std::vector<int32_t> phase;
-	if (P.tr) {
-		phase.resize((size_t)nseg);
-		for (int s = 0; s < nseg; s++) phase[(size_t)s] = (int32_t)((C.sidx[(size_t)s] * C.step) % P.tr->bin);
-	}
 	for (int q = 0; q < P.nq; q++) {
 		ScanShortLaunch L;
 		L.tcodes = E->tcodes.as<uint8_t>(); L.unit_len = E->unit_len.as<int32_t>(); L.nunit = B.nunit; L.tstride = B.tstride;
@@ -61,27 +31,9 @@ int panel_batch(fasim_engine* E, const PanelCall& P, BatchCtx& C, int64_t b0, in
 		hipError_t he;
 		{ TimedScope ts(E, 0, E->st); he = launch_scan_short(L, E->st); }
 		if (he != hipSuccess) return fail(E, FASIM_E_HIP, "scan_short launch failed: %s", hipGetErrorString(he));
-		if (P.sr) {
-			SitesFold sf;
-			sf.min_value = P.sr->min_value; sf.only = true; sf.nseg = nseg; sf.nenc = nenc; sf.nchunk = C.track_nchunk; sf.tab = tab;
-			sf.counts = &C.site_counts; sf.runs = &C.site_runs; sf.sat = &C.site_sat;
-			const int rc = run_sites_fold(E, B, &sf); if (rc) return rc;
-		}
-		if (P.tr) {
-			TrackFold tf;
-			tf.bin = P.tr->bin; tf.only = true; tf.nseg = nseg; tf.nenc = nenc; tf.nchunk = C.track_nchunk; tf.tab = tab;
-			tf.phase = phase.data(); tf.out = &C.track; tf.sat = &C.track_sat; tf.peaks = nullptr;
-			const int rc = run_track_fold(E, B, &tf); if (rc) return rc;
-		}
-		if (P.hr) {
-			HistFold hf;
-			hist_prepare(C, *P.hr, tab, q, hf);
-			const int rc = run_hist_fold(E, B, &hf); if (rc) return rc;
-		}
+		for (const ScanProduct* x : P.folds) { const int rc = x->fold(E, C, q); if (rc) return rc; }
 		HIPOK(hipStreamSynchronize(E->st));      // the folds' copies are complete; colmax16 is free for the next oligo
-		if (P.hr) { try { merge_hist(C, *P.T, b0, b1, *P.hr, q); } catch (const std::bad_alloc&) { return fail(E, FASIM_E_NOMEM, "out of memory"); } }
-		if (P.sr) { try { merge_site_runs(C, *P.sr, q); } catch (const std::bad_alloc&) { return fail(E, FASIM_E_NOMEM, "out of memory"); } }
-		if (P.tr) merge_track(C, *P.tr, q);
+		try { for (ScanProduct* x : P.merges) x->merge(C, *P.T, b0, b1, q); } catch (const std::bad_alloc&) { return fail(E, FASIM_E_NOMEM, "out of memory"); }
 	}
 	return FASIM_OK;
 }
@@ -160,7 +112,7 @@ int scan_oligos_core(fasim_engine* E, const char* const* oligos, const int32_t* 
 	const int tstride = (p.cutLength + 15) & ~15;
 
 	PanelCall P;
-	P.nq = nq; P.nrec = nrec; P.tstride = tstride; P.p = &p; P.encs = &encs;
+	P.nq = nq; P.nrec = nrec; P.tstride = tstride;
 	P.m.assign(lens, lens + nq);
 	P.codes.assign((size_t)nq * FASIM_MAX_OLIGO, 4);
 	int64_t msum = 0;
@@ -169,7 +121,7 @@ int scan_oligos_core(fasim_engine* E, const char* const* oligos, const int32_t* 
 	if (out_sites) {
 		sr.min_value = min_value; sr.max_gap = max_gap; sr.only = true; sr.nrec = nrec;
 		sr.runs.resize(nout); sr.sat.assign(nout, 0); sr.mu.reset(new std::mutex[(size_t)nq]);
-		P.sr = &sr;
+		P.folds.push_back(&sr);
 	}
 	HistReq hr;
 	auto drop = [&]() {
@@ -187,15 +139,18 @@ int scan_oligos_core(fasim_engine* E, const char* const* oligos, const int32_t* 
 			if (!out_tracks[o]) { drop(); return fail(E, FASIM_E_NOMEM, "out of memory"); }
 			for (int c = 0; c < FASIM_TRACK_CLASSES; c++) tr.v.push_back(out_tracks[o]->v[c]);
 		}
-		P.tr = &tr;
+		P.folds.push_back(&tr);
 	}
 
 	if (out_hists) {
 		bool ok = false;
 		try { ok = hist_req_init(hr, out_hists, nq, lens, rec_len, nrec, p, true); } catch (const std::bad_alloc&) { ok = false; }
 		if (!ok) { for (int q = 0; q < nq; q++) out_hists[q] = nullptr; drop(); return fail(E, FASIM_E_NOMEM, "out of memory"); }
-		P.hr = &hr; P.T = &T;
+		P.folds.push_back(&hr); P.merges.push_back(&hr);
 	}
+	if (out_sites) P.merges.push_back(&sr);
+	if (out_tracks) P.merges.push_back(&tr);
+	P.T = &T;
 
 	std::vector<int64_t> rec_units((size_t)nrec, 0);      // units scanned per record (the same for every oligo)
 	fasim_scan_stats all; memset(&all, 0, sizeof all);
@@ -252,9 +207,10 @@ int scan_oligos_core(fasim_engine* E, const char* const* oligos, const int32_t* 
 				BatchCtx ctx;
 				int r = batch_encode(w, dna, T, dna_dev, chunks[c].first, chunks[c].second, p, encs, tstride, ctx, ist[c], msum);
 				if (!r && ctx.nseg > 0) r = panel_batch(w, P, ctx, chunks[c].first, chunks[c].second);
-				else if (!r && P.hr) {
-					// (a batch whose segments are all skipped still has positions to count: they lie in bin 0)
-					try { for (int q = 0; q < nq; q++) merge_hist(ctx, T, chunks[c].first, chunks[c].second, hr, q); } catch (const std::bad_alloc&) { r = fail(w, FASIM_E_NOMEM, "out of memory"); }
+				else if (!r) {
+					// (a batch whose segments are all skipped still has positions for the histogram to count: they lie in bin 0)
+					try { for (ScanProduct* x : P.merges) if (x->merges_empty()) for (int q = 0; q < nq; q++) x->merge(ctx, T, chunks[c].first, chunks[c].second, q); }
+					catch (const std::bad_alloc&) { r = fail(w, FASIM_E_NOMEM, "out of memory"); }
 				}
 				(void)hipStreamSynchronize(w->st);
 				drain_timed(w);

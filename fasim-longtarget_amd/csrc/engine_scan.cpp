@@ -268,7 +268,8 @@ TrackTable class_table(const std::vector<int>& encs)
 
 // The head of a batch, segments [b0, b1) of the call's segment table: the segments that same_seq() does not skip into C, their DNA
 // onto the device (the resident buffer in place, a host buffer through the worker's pinned staging buffer) and k_encode over their
-// units into E->tcodes.  C.nseg == 0 afterwards: nothing to scan.  `m`: rows of the query or queries, for the cell counts of `st`.
+// units into E->tcodes; the class table and slice count of the products' folds.  C.nseg == 0 afterwards: nothing to scan.  `m`: rows
+// of the query or queries, for the cell counts of `st`.
 int batch_encode(fasim_engine* E, const char* dna, const SegTable& T, const uint8_t* dna_dev, int64_t b0, int64_t b1,
 	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st, int64_t m)
 {
@@ -276,6 +277,7 @@ int batch_encode(fasim_engine* E, const char* dna, const SegTable& T, const uint
 	const int64_t step = p.cutLength - p.overlapLength;
 	const int nenc = (int)encs.size();
 	C.B = UnitBatch(); C.tstride = tstride; C.nenc = nenc; C.nseg = 0; C.step = step; C.dna = dna; C.p = &p; C.encs = &encs;
+	C.tab = class_table(encs); C.track_nchunk = track_chunks(p.cutLength);
 	// segments of this batch that are not skipped by same_seq()
 	std::vector<int32_t>& sstart = C.sstart; std::vector<int32_t>& slen = C.slen; std::vector<int64_t>& sidx = C.sidx;
 	sstart.clear(); slen.clear(); sidx.clear(); C.soff.clear(); C.srec.clear();
@@ -353,12 +355,12 @@ int batch_encode(fasim_engine* E, const char* dna, const SegTable& T, const uint
 // host buffer.  The kernels take int32 segment starts relative to the batch's own first byte on the device, so a record set
 // longer than 2^31 nt works as long as one batch's span does.
 int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_t* dna_dev, int64_t b0, int64_t b1,
-	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st, const TrackReq* tr, const TfoReq* pr, const SitesReq* sr, const HistReq* hr, int q)
+	const fasim_params& p, const std::vector<int>& encs, int tstride, BatchCtx& C, fasim_scan_stats& st, const ScanProducts& products, int q)
 {
 	int rc = FASIM_OK;
 	const int64_t step = p.cutLength - p.overlapLength;
 	const int nenc = (int)encs.size();
-	C.B = UnitBatch(); C.tstride = tstride; C.nenc = nenc; C.nseg = 0; C.step = step; C.dna = dna; C.p = &p; C.encs = &encs; C.stage3_done = false; C.track_done = false; C.rows_done = false; C.sites_done = false; C.hist_done = false;
+	C.B = UnitBatch(); C.tstride = tstride; C.nenc = nenc; C.nseg = 0; C.step = step; C.dna = dna; C.p = &p; C.encs = &encs; C.stage3_done = false; C.folded = false;
 	C.per_unit.clear(); C.ucand.clear(); C.ualign.clear();
 	rc = batch_encode(E, dna, T, dna_dev, b0, b1, p, encs, tstride, C, st, E->m); if (rc) return rc;
 	if (!C.nseg) return FASIM_OK;
@@ -384,45 +386,9 @@ int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_
 				}
 			}
 			ScanOut so;
-			TrackFold tf; std::vector<int32_t> phase;
-			if (tr) {
-				// potential tracks: class and direction of every enabled encoding (the Strand column of -TFOsorted, host_post.cpp), and
-				// where the record's bins fall in every segment
-				tf.bin = tr->bin; tf.only = tr->only; tf.nseg = nseg; tf.nenc = nenc; tf.nchunk = C.track_nchunk = track_chunks(p.cutLength);
-				int cnt = 0;
-				for (int g = 0; g < 8; g++) {
-					tf.tab.first[g] = (uint8_t)cnt;
-					for (int k = 0; k < nenc; k++) {
-						const EncInfo ei = enc_info(encs[(size_t)k]);
-						const int cls = ei.para == 1 ? (ei.strand == 0 ? 0 : 1) : (ei.strand == 1 ? 2 : 3);
-						if (cls + 4 * (ei.reversed ? 1 : 0) == g) tf.tab.k[cnt++] = (uint8_t)k;
-					}
-				}
-				tf.tab.first[8] = (uint8_t)cnt;
-				phase.resize((size_t)nseg);
-				for (int s = 0; s < nseg; s++) phase[(size_t)s] = tr->bin >= 1 ? (int32_t)((sidx[(size_t)s] * step) % tr->bin) : 0;
-				tf.phase = phase.data(); tf.out = &C.track; tf.sat = &C.track_sat; tf.peaks = tr->peaks ? &C.track_peaks : nullptr;
-			}
-			RowFold rf;
-			if (pr) {
-				// the lncRNA's profile: one group per run of segments of one record, or the whole batch as one group
-				rf.nseg = nseg; rf.nenc = nenc; rf.only = pr->only; rf.tab = class_table(encs);
-				rf.gfirst.push_back(0);
-				if (pr->per_record) for (int s = 1; s < nseg; s++) if (C.srec[(size_t)s] != C.srec[(size_t)s - 1]) rf.gfirst.push_back(s);
-				rf.gfirst.push_back(nseg);
-				rf.out = &C.rowfold; rf.sat = &C.row_sat;
-			}
-			SitesFold sf;
-			if (sr) {
-				sf.min_value = sr->min_value; sf.only = sr->only; sf.nseg = nseg; sf.nenc = nenc; sf.nchunk = C.track_nchunk = track_chunks(p.cutLength);
-				sf.tab = class_table(encs);
-				sf.counts = &C.site_counts; sf.runs = &C.site_runs; sf.sat = &C.site_sat;
-			}
-			HistFold hf;
-			if (hr) { C.track_nchunk = track_chunks(p.cutLength); hist_prepare(C, *hr, class_table(encs), q, hf); }
-			rc = run_scan_v2(E, B, need1, so, &st, tr ? &tf : nullptr, pr ? &rf : nullptr, sr ? &sf : nullptr, hr ? &hf : nullptr);
+			rc = run_scan_v2(E, C, need1, so, &st, products, q);
 			if (rc < 0) return rc;
-			if (rc == 0) { C.sites_done = sr != nullptr; C.hist_done = hr != nullptr; hoff.swap(so.hit_off); hcnt.swap(so.hit_cnt); thr.swap(so.thr); hits.swap(so.hits); done_v2 = true; C.track_done = tr != nullptr; C.rows_done = pr != nullptr; C.row_gfirst.swap(rf.gfirst); }
+			if (rc == 0) { C.folded = true; hoff.swap(so.hit_off); hcnt.swap(so.hit_cnt); thr.swap(so.thr); hits.swap(so.hits); done_v2 = true; }
 		}
 		st.t_stage2_s += now_s() - t0;
 		if (!done_v2) {
@@ -504,86 +470,6 @@ int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_
 	return FASIM_OK;
 }
 
-
-// fasim_scan_track / fasim_scan_records_track: the slices of a finished scan phase into the arrays of query q and of every
-// segment's own record (maximum; overlapping segments and the slices of one segment that share a bin meet here), and the slices'
-// peaks into the record's peaks (larger value, then lower position, then lower encoding)
-void merge_track(const BatchCtx& C, TrackReq& tr, int q)
-{
-	const int stride = tr.bin >= 1 ? track_slice_stride(tr.bin) : 0;
-	const int64_t bin = tr.bin;
-	std::lock_guard<std::mutex> g(tr.mu[(size_t)q]);
-	for (int s = 0; s < C.nseg; s++) {
-		const size_t o = (size_t)q * (size_t)tr.nrec + (size_t)C.srec[(size_t)s];
-		const int64_t a = C.sidx[(size_t)s] * C.step;
-		const int n = C.slen[(size_t)s];
-		for (int c = 0; c * TRACK_CHUNK < n; c++) {
-			const int64_t P0 = (int64_t)c * TRACK_CHUNK, P1 = std::min<int64_t>(n, P0 + TRACK_CHUNK);
-			if (bin >= 1) {
-				const int64_t b0 = (a + P0) / bin, nb = (a + P1 - 1) / bin - b0 + 1;
-				for (int cls = 0; cls < 4; cls++) {
-					const uint16_t* src = C.track.data() + (((size_t)s * C.track_nchunk + c) * 4 + cls) * stride;
-					uint16_t* dst = tr.v[o * 4 + cls] + b0;
-					for (int64_t i = 0; i < nb; i++) dst[i] = std::max(dst[i], src[i]);
-				}
-			}
-			if (tr.peaks) {
-				for (int cls = 0; cls < 4; cls++) {
-					const TrackPeak& k = C.track_peaks[((size_t)s * C.track_nchunk + c) * 4 + cls];
-					if (k.value <= 0) continue;
-					const int64_t pos = a + k.pos;
-					const int32_t enc = (*C.encs)[(size_t)k.k];
-					fasim_peak& d = tr.peaks[o * 4 + cls];
-					if (k.value > d.value || (k.value == d.value && (pos < d.pos || (pos == d.pos && enc < d.enc)))) { d.value = k.value; d.pos = pos; d.enc = enc; }
-				}
-			}
-		}
-	}
-	for (size_t u = 0; u < C.track_sat.size(); u++) tr.sat[(size_t)q * (size_t)tr.nrec + (size_t)C.srec[u / (size_t)C.nenc]] += C.track_sat[u];
-}
-
-// fasim_scan_records_sites: the runs of a finished scan phase, rebased from segment to record positions, onto the lists of query q
-// and of every segment's own record
-void merge_site_runs(const BatchCtx& C, SitesReq& sr, int q)
-{
-	std::lock_guard<std::mutex> g(sr.mu[(size_t)q]);
-	size_t at = 0;
-	for (int s = 0; s < C.nseg; s++) {
-		const size_t o = (size_t)q * (size_t)sr.nrec + (size_t)C.srec[(size_t)s];
-		const int64_t a = C.sidx[(size_t)s] * C.step;
-		std::vector<HostRun>& dst = sr.runs[o];
-		for (int c = 0; c < C.track_nchunk; c++) {
-			for (int cls = 0; cls < 4; cls++) {
-				const uint32_t cnt = C.site_counts[((size_t)s * C.track_nchunk + c) * 4 + cls];
-				for (uint32_t k = 0; k < cnt; k++, at++) {
-					const SiteRun& r = C.site_runs[at];
-					HostRun h;
-					h.start = a + r.start; h.end = a + r.end; h.pos = a + r.pos; h.value = r.value_k & 0xffff; h.enc = (*C.encs)[(size_t)(r.value_k >> 16)]; h.cls = cls;
-					dst.push_back(h);
-				}
-			}
-		}
-	}
-	for (size_t u = 0; u < C.site_sat.size(); u++) sr.sat[(size_t)q * (size_t)sr.nrec + (size_t)C.srec[u / (size_t)C.nenc]] += C.site_sat[u];
-}
-
-// fasim_scan_tfo_profile: the groups of a finished scan phase into the arrays of query q (and of the group's record), by maximum
-static void merge_rows(const BatchCtx& C, TfoReq& pr, int q)
-{
-	const int m = pr.m[(size_t)q], rows_total = 16 * ((m + 15) / 16);
-	std::lock_guard<std::mutex> g(pr.mu[(size_t)q]);
-	for (size_t gi = 0; gi + 1 < C.row_gfirst.size(); gi++) {
-		const int s0 = C.row_gfirst[gi], s1 = C.row_gfirst[gi + 1];
-		const size_t o = pr.per_record ? (size_t)q * (size_t)pr.nrec + (size_t)C.srec[(size_t)s0] : (size_t)q;
-		for (int cls = 0; cls < 4; cls++) {
-			const uint16_t* src = C.rowfold.data() + (gi * 4 + (size_t)cls) * (size_t)rows_total;      // (pad rows [m, rows_total) are not part of the result)
-			uint16_t* dst = pr.v[o * 4 + (size_t)cls];
-			for (int i = 0; i < m; i++) dst[i] = std::max(dst[i], src[i]);
-		}
-		pr.units[o] += (int64_t)(s1 - s0) * C.nenc;
-		for (int u = s0 * C.nenc; u < s1 * C.nenc; u++) pr.sat[o] += C.row_sat[(size_t)u];
-	}
-}
 
 // What one work item leaves for one record: the record's triplexes from the item's segments and the per-record stats (those
 // counted per unit or candidate).  A batch that crosses records leaves one part per record, in record order.
@@ -720,7 +606,7 @@ static void add_stats(fasim_scan_stats& st, const fasim_scan_stats& x)
 // whole call's stats.  `records` true: outs[q * nrec + r] carries the per-record stats, totals[q] (if given) the call's.
 static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int nrec, bool records, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
-	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr = nullptr, TfoReq* pr = nullptr, SitesReq* sr = nullptr, HistReq* hr = nullptr)
+	fasim_result** outs, fasim_scan_stats* totals, const ScanProducts& products)
 {
 	const bool resident = (dna == nullptr);
 	if (resident) dna = E->dna_host.data();
@@ -823,7 +709,7 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 		// profile calls: k_scan's row maxima take 2 * 16 * ceil(m/16) bytes per unit; a batch in flight keeps them under 256 MB
 		// (H19 at the default batch: 512 x 48 units x 2 816 rows = 138 MB, no change; a 92 256 nt query: 30 segments per batch)
 		int64_t rows_cap = INT64_MAX;
-		if (pr) {
+		if (any_rowmax(products)) {
 			int mmax = 16;
 			for (int q = 0; q < nquery; q++) mmax = std::max(mmax, (int)queries[(size_t)q].size());
 			rows_cap = std::max<int64_t>(1, ((int64_t)256 << 20) / ((int64_t)nenc * 2 * 16 * ((mmax + 15) / 16)));
@@ -918,31 +804,17 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 					r = fasim_set_query(w, rq.data(), (int)rq.size());
 					if (r && w != E) w->err = std::string("worker set_query failed: ") + w->err;
 				}
-				if (!r) r = scan_batch(w, dna, T, dna_dev, itx.b0, itx.b1, p, encs, tstride, ctx, ist[c], tr, pr, sr, hr, itx.q);
-				if (!r && pr && ctx.B.nunit > 0) {
-					if (!ctx.rows_done) r = fail(w, FASIM_E_UNSUPPORTED, "the lncRNA's profile needs the systolic scan kernel");
-					else { merge_rows(ctx, *pr, itx.q); std::vector<uint16_t>().swap(ctx.rowfold); }
-				}
-				if (!r && tr && ctx.B.nunit > 0) {
-					if (!ctx.track_done) r = fail(w, FASIM_E_UNSUPPORTED, "potential tracks need the systolic scan kernel");
-					else { merge_track(ctx, *tr, itx.q); std::vector<uint16_t>().swap(ctx.track); }
-				}
-				if (!r && sr && ctx.B.nunit > 0) {
-					if (!ctx.sites_done) r = fail(w, FASIM_E_UNSUPPORTED, "sites need the systolic scan kernel");
+				if (!r) r = scan_batch(w, dna, T, dna_dev, itx.b0, itx.b1, p, encs, tstride, ctx, ist[c], products, itx.q);
+				// the products of the call: the batch's folded vectors into the call's arrays (a batch on the fallback kernels has none)
+				for (ScanProduct* x : products) {
+					if (r || !(ctx.B.nunit > 0 || x->merges_empty())) continue;
+					if (ctx.B.nunit > 0 && !ctx.folded) r = fail(w, FASIM_E_UNSUPPORTED, "%s", x->needs_scan());
 					else {
-						try { merge_site_runs(ctx, *sr, itx.q); } catch (const std::bad_alloc&) { r = fail(w, FASIM_E_NOMEM, "out of memory"); }
-						std::vector<SiteRun>().swap(ctx.site_runs);
+						try { x->merge(ctx, T, itx.b0, itx.b1, itx.q); } catch (const std::bad_alloc&) { r = fail(w, FASIM_E_NOMEM, "out of memory"); }
+						ctx.release_folded();
 					}
 				}
-				if (!r && hr) {
-					// (a batch whose segments are all skipped still has positions to count: they lie in bin 0)
-					if (ctx.B.nunit > 0 && !ctx.hist_done) r = fail(w, FASIM_E_UNSUPPORTED, "the histogram of the potential needs the systolic scan kernel");
-					else {
-						try { merge_hist(ctx, T, itx.b0, itx.b1, *hr, itx.q); } catch (const std::bad_alloc&) { r = fail(w, FASIM_E_NOMEM, "out of memory"); }
-						std::vector<uint16_t>().swap(ctx.hist_zones);
-					}
-				}
-				if (!r && ctx.B.nunit > 0 && !ctx.stage3_done && !(tr && tr->only) && !(pr && pr->only) && !(sr && sr->only) && !(hr && hr->only)) r = stage3_range(w, ctx, 0, ctx.B.nunit, ist[c]);
+				if (!r && ctx.B.nunit > 0 && !ctx.stage3_done && !any_only(products)) r = stage3_range(w, ctx, 0, ctx.B.nunit, ist[c]);
 				(void)hipStreamSynchronize(w->st);
 				drain_timed(w);
 				for (int k = 0; k < FASIM_KERNEL_FAMILIES; k++) { ist[c].kernel_ms[k] = w->kernel_ms[k]; ist[c].kernel_launches[k] = w->kernel_launches[k]; w->kernel_ms[k] = 0; w->kernel_launches[k] = 0; }
@@ -1035,7 +907,7 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 }
 
 int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna, int64_t dna_len,
-	int64_t seg_first, int64_t seg_count, const fasim_params* pp, fasim_result** outs, TrackReq* tr)
+	int64_t seg_first, int64_t seg_count, const fasim_params* pp, fasim_result** outs, const ScanProducts& products)
 {
 	if (dna == nullptr) {
 		if (E->dna_host.empty()) return fail(E, FASIM_E_ARG, "no resident DNA: call fasim_load_dna first");
@@ -1045,12 +917,12 @@ int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens,
 	if (pp->cutLength <= 0 || pp->cutLength - pp->overlapLength <= 0) return fail(E, FASIM_E_ARG, "cutLength/overlapLength invalid");
 	if (dna_len > 0x7fffffffll) return fail(E, FASIM_E_ARG, "one record is limited to 2^31-1 nt (the reference's int positions)");
 	const int64_t off = 0;
-	return scan_set(E, rnas, rna_lens, nq, dna, &off, &dna_len, 1, false, seg_first, seg_count, pp, outs, nullptr, tr);
+	return scan_set(E, rnas, rna_lens, nq, dna, &off, &dna_len, 1, false, seg_first, seg_count, pp, outs, nullptr, products);
 }
 
 int scan_records_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
-	fasim_result** outs, fasim_scan_stats* totals, TrackReq* tr, TfoReq* pr, SitesReq* sr, HistReq* hr)
+	fasim_result** outs, fasim_scan_stats* totals, const ScanProducts& products)
 {
-	return scan_set(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, true, seg_first, seg_count, pp, outs, totals, tr, pr, sr, hr);
+	return scan_set(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, true, seg_first, seg_count, pp, outs, totals, products);
 }

@@ -20,15 +20,6 @@ struct HitOut {
 	bool aligned = false;
 };
 
-int text_out_sa(const std::string& s, char** text, int64_t* text_len)
-{
-	char* b = (char*)malloc(s.size() + 1);
-	if (!b) return fail(nullptr, FASIM_E_NOMEM, "out of memory");
-	memcpy(b, s.data(), s.size()); b[s.size()] = 0;
-	*text = b; *text_len = (int64_t)s.size();
-	return FASIM_OK;
-}
-
 // the hit list of one (query, record) from its hits in site order
 fasim_site_hits* pack_hits(const std::vector<HitOut>& v)
 {
@@ -400,5 +391,5 @@ int fasim_site_hits_tsv(const fasim_sites* s, const fasim_site_hits* h, const ch
 		if (record_name) { o += "\t"; o += record_name; }
 		o += "\n";
 	}
-	return text_out_sa(o, text, text_len);
+	return text_out(o, text, text_len);
 }

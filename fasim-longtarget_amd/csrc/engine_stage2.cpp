@@ -259,38 +259,126 @@ int run_hazard_chunked(fasim_engine* E, const UnitBatch& B, const std::vector<in
 	return FASIM_OK;
 }
 
-// k_track over the batch's column maxima in E->colmax16, into the host vectors of `tf`.  The copies complete at the next synchronisation
-// of the stream.
-int run_track_fold(fasim_engine* E, const UnitBatch& B, const TrackFold* tf)
+// ---- the products' folds behind a batch's column maxima in E->colmax16 (row maxima in E->rowmax16) and their host merges -------------
+// k_rowfold over the batch's row maxima, into C.rowfold / C.row_sat: one group per run of segments of one record, or the whole batch
+// as one group.  The copies complete at the next synchronisation of the stream.
+int TfoReq::fold(fasim_engine* E, BatchCtx& C, int) const
 {
-	const int nu = B.nunit;
+	const int nu = C.B.nunit, nseg = C.nseg, rows_total = 16 * ((E->m + 15) / 16);
 	int rc; hipError_t he;
-	rc = upload(E, E->track_phase, tf->phase, sizeof(int32_t) * tf->nseg); if (rc) return rc;
-	const size_t nout = tf->bin >= 1 ? (size_t)tf->nseg * tf->nchunk * 4 * track_slice_stride(tf->bin) : 0;      // (bin == 0: peaks only)
-	const size_t npeak = tf->peaks ? (size_t)tf->nseg * tf->nchunk * 4 : 0;
+	std::vector<int32_t>& gfirst = C.row_gfirst;
+	gfirst.assign(1, 0);
+	if (per_record) for (int s = 1; s < nseg; s++) if (C.srec[(size_t)s] != C.srec[(size_t)s - 1]) gfirst.push_back(s);
+	gfirst.push_back(nseg);
+	const int ng = (int)gfirst.size() - 1;
+	const size_t nout = (size_t)ng * 4 * rows_total;
+	rc = upload(E, E->row_gfirst, gfirst.data(), sizeof(int32_t) * gfirst.size()); if (rc) return rc;
+	HIPOK(E->row_out.ensure(nout * sizeof(uint16_t))); HIPOK(E->row_sat.ensure((size_t)nu));
+	HIPOK(hipMemsetAsync(E->row_sat.p, 0, (size_t)nu, E->st));
+	RowFoldLaunch R;
+	R.rowmax16 = E->rowmax16.as<uint16_t>(); R.gfirst = E->row_gfirst.as<int32_t>(); R.ngroups = ng; R.nenc = C.nenc; R.rows_total = rows_total;
+	R.tab = C.tab; R.out = E->row_out.as<uint16_t>(); R.sat = E->row_sat.as<uint8_t>();
+	{ TimedScope ts(E, 4); he = launch_rowfold(R, E->st); }
+	if (he != hipSuccess) return fail(E, FASIM_E_HIP, "rowfold launch failed: %s", hipGetErrorString(he));
+	C.rowfold.resize(nout); C.row_sat.resize((size_t)nu);
+	HIPOK(hipMemcpyAsync(C.rowfold.data(), E->row_out.p, nout * sizeof(uint16_t), hipMemcpyDeviceToHost, E->st));
+	HIPOK(hipMemcpyAsync(C.row_sat.data(), E->row_sat.p, (size_t)nu, hipMemcpyDeviceToHost, E->st));
+	return FASIM_OK;
+}
+
+// fasim_scan_tfo_profile: the groups of a finished scan phase into the arrays of query q (and of the group's record), by maximum
+void TfoReq::merge(const BatchCtx& C, const SegTable&, int64_t, int64_t, int q)
+{
+	TfoReq& pr = *this;
+	const int m = pr.m[(size_t)q], rows_total = 16 * ((m + 15) / 16);
+	std::lock_guard<std::mutex> g(pr.mu[(size_t)q]);
+	for (size_t gi = 0; gi + 1 < C.row_gfirst.size(); gi++) {
+		const int s0 = C.row_gfirst[gi], s1 = C.row_gfirst[gi + 1];
+		const size_t o = pr.per_record ? (size_t)q * (size_t)pr.nrec + (size_t)C.srec[(size_t)s0] : (size_t)q;
+		for (int cls = 0; cls < 4; cls++) {
+			const uint16_t* src = C.rowfold.data() + (gi * 4 + (size_t)cls) * (size_t)rows_total;      // (pad rows [m, rows_total) are not part of the result)
+			uint16_t* dst = pr.v[o * 4 + (size_t)cls];
+			for (int i = 0; i < m; i++) dst[i] = std::max(dst[i], src[i]);
+		}
+		pr.units[o] += (int64_t)(s1 - s0) * C.nenc;
+		for (int u = s0 * C.nenc; u < s1 * C.nenc; u++) pr.sat[o] += C.row_sat[(size_t)u];
+	}
+}
+
+// k_track over the batch's column maxima, into C.track / C.track_sat / C.track_peaks: class and direction of every enabled encoding
+// (the Strand column of -TFOsorted, host_post.cpp) and where the record's bins fall in every segment.  The copies complete at the
+// next synchronisation of the stream.
+int TrackReq::fold(fasim_engine* E, BatchCtx& C, int) const
+{
+	const int nu = C.B.nunit, nseg = C.nseg, nchunk = C.track_nchunk;
+	int rc; hipError_t he;
+	std::vector<int32_t> phase((size_t)nseg);      // record position of the segment's first base, modulo bin
+	for (int s = 0; s < nseg; s++) phase[(size_t)s] = bin >= 1 ? (int32_t)((C.sidx[(size_t)s] * C.step) % bin) : 0;
+	rc = upload(E, E->track_phase, phase.data(), sizeof(int32_t) * nseg); if (rc) return rc;
+	const size_t nout = bin >= 1 ? (size_t)nseg * nchunk * 4 * track_slice_stride(bin) : 0;      // (bin == 0: peaks only)
+	const size_t npeak = peaks ? (size_t)nseg * nchunk * 4 : 0;
 	HIPOK(E->track.ensure(nout * sizeof(uint16_t))); HIPOK(E->track_sat.ensure((size_t)nu));
 	if (npeak) HIPOK(E->track_peaks.ensure(npeak * sizeof(TrackPeak)));
 	HIPOK(hipMemsetAsync(E->track_sat.p, 0, (size_t)nu, E->st));
 	TrackLaunch T;
 	T.colmax16 = E->colmax16.as<uint16_t>(); T.seg_len = E->seg_len.as<int32_t>(); T.phase = E->track_phase.as<int32_t>();
-	T.nseg = tf->nseg; T.nenc = tf->nenc; T.tstride = B.tstride; T.nchunk = tf->nchunk; T.bin = tf->bin; T.tab = tf->tab;
+	T.nseg = nseg; T.nenc = C.nenc; T.tstride = C.B.tstride; T.nchunk = nchunk; T.bin = bin; T.tab = C.tab;
 	T.out = E->track.as<uint16_t>(); T.sat = E->track_sat.as<uint8_t>(); T.peaks = npeak ? E->track_peaks.as<TrackPeak>() : nullptr;
 	{ TimedScope ts(E, 4); he = launch_track(T, E->st); }
 	if (he != hipSuccess) return fail(E, FASIM_E_HIP, "track launch failed: %s", hipGetErrorString(he));
-	tf->out->resize(nout); tf->sat->resize((size_t)nu);
-	if (nout) HIPOK(hipMemcpyAsync(tf->out->data(), E->track.p, nout * sizeof(uint16_t), hipMemcpyDeviceToHost, E->st));
-	HIPOK(hipMemcpyAsync(tf->sat->data(), E->track_sat.p, (size_t)nu, hipMemcpyDeviceToHost, E->st));
-	if (npeak) { tf->peaks->resize(npeak); HIPOK(hipMemcpyAsync(tf->peaks->data(), E->track_peaks.p, npeak * sizeof(TrackPeak), hipMemcpyDeviceToHost, E->st)); }
+	C.track.resize(nout); C.track_sat.resize((size_t)nu);
+	if (nout) HIPOK(hipMemcpyAsync(C.track.data(), E->track.p, nout * sizeof(uint16_t), hipMemcpyDeviceToHost, E->st));
+	HIPOK(hipMemcpyAsync(C.track_sat.data(), E->track_sat.p, (size_t)nu, hipMemcpyDeviceToHost, E->st));
+	if (npeak) { C.track_peaks.resize(npeak); HIPOK(hipMemcpyAsync(C.track_peaks.data(), E->track_peaks.p, npeak * sizeof(TrackPeak), hipMemcpyDeviceToHost, E->st)); }
 	return FASIM_OK;
 }
 
-// The two launches of k_sites over the batch's column maxima in E->colmax16, into the host vectors of `sf`.  The copy of the runs
-// completes at the next synchronisation of the stream.
-int run_sites_fold(fasim_engine* E, const UnitBatch& B, const SitesFold* sf)
+// fasim_scan_track / fasim_scan_records_track: the slices of a finished scan phase into the arrays of query q and of every
+// segment's own record (maximum; overlapping segments and the slices of one segment that share a bin meet here), and the slices'
+// peaks into the record's peaks (larger value, then lower position, then lower encoding)
+void TrackReq::merge(const BatchCtx& C, const SegTable&, int64_t, int64_t, int q)
 {
-	const int nu = B.nunit;
+	TrackReq& tr = *this;
+	const int stride = tr.bin >= 1 ? track_slice_stride(tr.bin) : 0;
+	const int64_t bin = tr.bin;
+	std::lock_guard<std::mutex> g(tr.mu[(size_t)q]);
+	for (int s = 0; s < C.nseg; s++) {
+		const size_t o = (size_t)q * (size_t)tr.nrec + (size_t)C.srec[(size_t)s];
+		const int64_t a = C.sidx[(size_t)s] * C.step;
+		const int n = C.slen[(size_t)s];
+		for (int c = 0; c * TRACK_CHUNK < n; c++) {
+			const int64_t P0 = (int64_t)c * TRACK_CHUNK, P1 = std::min<int64_t>(n, P0 + TRACK_CHUNK);
+			if (bin >= 1) {
+				const int64_t b0 = (a + P0) / bin, nb = (a + P1 - 1) / bin - b0 + 1;
+				for (int cls = 0; cls < 4; cls++) {
+					const uint16_t* src = C.track.data() + (((size_t)s * C.track_nchunk + c) * 4 + cls) * stride;
+					uint16_t* dst = tr.v[o * 4 + cls] + b0;
+					for (int64_t i = 0; i < nb; i++) dst[i] = std::max(dst[i], src[i]);
+				}
+			}
+			if (tr.peaks) {
+				for (int cls = 0; cls < 4; cls++) {
+					const TrackPeak& k = C.track_peaks[((size_t)s * C.track_nchunk + c) * 4 + cls];
+					if (k.value <= 0) continue;
+					const int64_t pos = a + k.pos;
+					const int32_t enc = (*C.encs)[(size_t)k.k];
+					fasim_peak& d = tr.peaks[o * 4 + cls];
+					if (k.value > d.value || (k.value == d.value && (pos < d.pos || (pos == d.pos && enc < d.enc)))) { d.value = k.value; d.pos = pos; d.enc = enc; }
+				}
+			}
+		}
+	}
+	for (size_t u = 0; u < C.track_sat.size(); u++) tr.sat[(size_t)q * (size_t)tr.nrec + (size_t)C.srec[u / (size_t)C.nenc]] += C.track_sat[u];
+}
+
+// The two launches of k_sites over the batch's column maxima, into C.site_counts / C.site_runs / C.site_sat: the run counts per
+// (slice, class) come back on this stream, their prefix sum places every slice's runs and sizes the buffer.  The copy of the runs
+// completes at the next synchronisation of the stream.
+int SitesReq::fold(fasim_engine* E, BatchCtx& C, int) const
+{
+	const int nu = C.B.nunit;
 	int rc; hipError_t he;
-	const size_t ncnt = (size_t)sf->nseg * sf->nchunk * 4;
+	const size_t ncnt = (size_t)C.nseg * C.track_nchunk * 4;
 	if (E->sites_counts.ensure(ncnt * sizeof(uint32_t)) != hipSuccess || E->sites_offsets.ensure(ncnt * sizeof(uint32_t)) != hipSuccess ||
 		E->sites_sat.ensure((size_t)nu) != hipSuccess) {
 		(void)hipGetLastError();
@@ -300,68 +388,65 @@ int run_sites_fold(fasim_engine* E, const UnitBatch& B, const SitesFold* sf)
 	HIPOK(hipMemsetAsync(E->sites_sat.p, 0, (size_t)nu, E->st));
 	SitesLaunch S;
 	S.colmax16 = E->colmax16.as<uint16_t>(); S.seg_len = E->seg_len.as<int32_t>();
-	S.nseg = sf->nseg; S.nenc = sf->nenc; S.tstride = B.tstride; S.nchunk = sf->nchunk; S.min_value = sf->min_value; S.tab = sf->tab;
+	S.nseg = C.nseg; S.nenc = C.nenc; S.tstride = C.B.tstride; S.nchunk = C.track_nchunk; S.min_value = min_value; S.tab = C.tab;
 	S.counts = E->sites_counts.as<uint32_t>(); S.offsets = nullptr; S.runs = nullptr; S.sat = E->sites_sat.as<uint8_t>();
 	{ TimedScope ts(E, 4); he = launch_sites(S, false, E->st); }
 	if (he != hipSuccess) return fail(E, FASIM_E_HIP, "sites (count) launch failed: %s", hipGetErrorString(he));
 	std::vector<uint32_t> offs;
-	try { sf->counts->resize(ncnt); sf->sat->resize((size_t)nu); offs.resize(ncnt); } catch (const std::bad_alloc&) { return fail(E, FASIM_E_NOMEM, "out of memory"); }
-	HIPOK(hipMemcpyAsync(sf->counts->data(), E->sites_counts.p, ncnt * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st));
-	HIPOK(hipMemcpyAsync(sf->sat->data(), E->sites_sat.p, (size_t)nu, hipMemcpyDeviceToHost, E->st));
+	try { C.site_counts.resize(ncnt); C.site_sat.resize((size_t)nu); offs.resize(ncnt); } catch (const std::bad_alloc&) { return fail(E, FASIM_E_NOMEM, "out of memory"); }
+	HIPOK(hipMemcpyAsync(C.site_counts.data(), E->sites_counts.p, ncnt * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st));
+	HIPOK(hipMemcpyAsync(C.site_sat.data(), E->sites_sat.p, (size_t)nu, hipMemcpyDeviceToHost, E->st));
 	HIPOK(hipStreamSynchronize(E->st));
 	uint64_t total = 0;
-	for (size_t k = 0; k < ncnt; k++) { offs[k] = (uint32_t)total; total += (*sf->counts)[k]; }
-	sf->runs->clear();
+	for (size_t k = 0; k < ncnt; k++) { offs[k] = (uint32_t)total; total += C.site_counts[k]; }
+	C.site_runs.clear();
 	if (total > 0) {
 		if (total > 0x7fffffffull / sizeof(SiteRun)) return fail(E, FASIM_E_NOMEM, "sites: %llu runs in one batch", (unsigned long long)total);
 		if (E->sites_runs.ensure((size_t)total * sizeof(SiteRun)) != hipSuccess) {
 			(void)hipGetLastError();
 			return fail(E, FASIM_E_NOMEM, "sites: no device memory for %llu runs of a batch", (unsigned long long)total);
 		}
-		try { sf->runs->resize((size_t)total); } catch (const std::bad_alloc&) { return fail(E, FASIM_E_NOMEM, "out of memory"); }
+		try { C.site_runs.resize((size_t)total); } catch (const std::bad_alloc&) { return fail(E, FASIM_E_NOMEM, "out of memory"); }
 		rc = upload(E, E->sites_offsets, offs.data(), ncnt * sizeof(uint32_t)); if (rc) return rc;
 		S.offsets = E->sites_offsets.as<uint32_t>(); S.runs = E->sites_runs.as<SiteRun>();
 		{ TimedScope ts(E, 4); he = launch_sites(S, true, E->st); }
 		if (he != hipSuccess) return fail(E, FASIM_E_HIP, "sites (emit) launch failed: %s", hipGetErrorString(he));
-		HIPOK(hipMemcpyAsync(sf->runs->data(), E->sites_runs.p, (size_t)total * sizeof(SiteRun), hipMemcpyDeviceToHost, E->st));
+		HIPOK(hipMemcpyAsync(C.site_runs.data(), E->sites_runs.p, (size_t)total * sizeof(SiteRun), hipMemcpyDeviceToHost, E->st));
 	}
 	return FASIM_OK;
 }
 
-// k_hist over the batch's column maxima in E->colmax16, into the host vectors of `hf`: the counters of the values 0 .. hf->top per
-// class, the zone values and the saturation flags.  The copies complete at the next synchronisation of the stream.
-int run_hist_fold(fasim_engine* E, const UnitBatch& B, const HistFold* hf)
+// fasim_scan_records_sites: the runs of a finished scan phase, rebased from segment to record positions, onto the lists of query q
+// and of every segment's own record
+void SitesReq::merge(const BatchCtx& C, const SegTable&, int64_t, int64_t, int q)
 {
-	const int nu = B.nunit;
-	int rc; hipError_t he;
-	const size_t nzone = (size_t)hf->nseg * 8 * (size_t)hf->zstride;
-	const size_t ntop = (size_t)std::min(hf->top, HIST_BINS - 1) + 1;
-	if (E->hist.ensure((size_t)4 * HIST_BINS * sizeof(uint32_t)) != hipSuccess || E->hist_zones.ensure(std::max<size_t>(1, nzone) * sizeof(uint16_t)) != hipSuccess ||
-		E->hist_sat.ensure((size_t)nu) != hipSuccess) {
-		(void)hipGetLastError();
-		return fail(E, FASIM_E_NOMEM, "histogram: no device memory for the counters and %zu zone values of a batch", nzone);
+	SitesReq& sr = *this;
+	std::lock_guard<std::mutex> g(sr.mu[(size_t)q]);
+	size_t at = 0;
+	for (int s = 0; s < C.nseg; s++) {
+		const size_t o = (size_t)q * (size_t)sr.nrec + (size_t)C.srec[(size_t)s];
+		const int64_t a = C.sidx[(size_t)s] * C.step;
+		std::vector<HostRun>& dst = sr.runs[o];
+		for (int c = 0; c < C.track_nchunk; c++) {
+			for (int cls = 0; cls < 4; cls++) {
+				const uint32_t cnt = C.site_counts[((size_t)s * C.track_nchunk + c) * 4 + cls];
+				for (uint32_t k = 0; k < cnt; k++, at++) {
+					const SiteRun& r = C.site_runs[at];
+					HostRun h;
+					h.start = a + r.start; h.end = a + r.end; h.pos = a + r.pos; h.value = r.value_k & 0xffff; h.enc = (*C.encs)[(size_t)(r.value_k >> 16)]; h.cls = cls;
+					dst.push_back(h);
+				}
+			}
+		}
 	}
-	rc = upload(E, E->hist_zone, hf->zone, sizeof(int32_t) * 2 * (size_t)hf->nseg); if (rc) return rc;
-	HIPOK(hipMemsetAsync(E->hist.p, 0, (size_t)4 * HIST_BINS * sizeof(uint32_t), E->st));
-	HIPOK(hipMemsetAsync(E->hist_sat.p, 0, (size_t)nu, E->st));
-	HistLaunch H;
-	H.colmax16 = E->colmax16.as<uint16_t>(); H.seg_len = E->seg_len.as<int32_t>(); H.zone = E->hist_zone.as<int32_t>();
-	H.nseg = hf->nseg; H.nenc = hf->nenc; H.tstride = B.tstride; H.nchunk = hf->nchunk; H.zstride = hf->zstride; H.tab = hf->tab;
-	H.hist = E->hist.as<uint32_t>(); H.zones = E->hist_zones.as<uint16_t>(); H.sat = E->hist_sat.as<uint8_t>();
-	{ TimedScope ts(E, 4); he = launch_hist(H, E->st); }
-	if (he != hipSuccess) return fail(E, FASIM_E_HIP, "hist launch failed: %s", hipGetErrorString(he));
-	try { hf->hist->resize(4 * ntop); hf->zones->resize(nzone); hf->sat->resize((size_t)nu); } catch (const std::bad_alloc&) { return fail(E, FASIM_E_NOMEM, "out of memory"); }
-	for (int c = 0; c < 4; c++)
-		HIPOK(hipMemcpyAsync(hf->hist->data() + (size_t)c * ntop, E->hist.as<uint32_t>() + (size_t)c * HIST_BINS, ntop * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st));
-	if (nzone) HIPOK(hipMemcpyAsync(hf->zones->data(), E->hist_zones.p, nzone * sizeof(uint16_t), hipMemcpyDeviceToHost, E->st));
-	HIPOK(hipMemcpyAsync(hf->sat->data(), E->hist_sat.p, (size_t)nu, hipMemcpyDeviceToHost, E->st));
-	return FASIM_OK;
+	for (size_t u = 0; u < C.site_sat.size(); u++) sr.sat[(size_t)q * (size_t)sr.nrec + (size_t)C.srec[u / (size_t)C.nenc]] += C.site_sat[u];
 }
 
 // returns 1 when the query does not fit the kernel (caller falls back to the striped kernels)
-int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& unit_needs_stage1, ScanOut& out,
-	fasim_scan_stats* st, const TrackFold* tf, const RowFold* rf, const SitesFold* sf, const HistFold* hf)
+int run_scan_v2(fasim_engine* E, BatchCtx& C, const std::vector<char>& unit_needs_stage1, ScanOut& out,
+	fasim_scan_stats* st, const ScanProducts& products, int q)
 {
+	const UnitBatch& B = C.B;
 	const int nu = B.nunit;
 	HIPOK(E->colmax16.ensure((size_t)nu * B.tstride * sizeof(uint16_t)));
 	std::vector<int32_t> ids(nu), sep;
@@ -421,9 +506,8 @@ int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& un
 	}
 	// row maxima for the lncRNA's profile (fasim_scan_tfo_profile): the main pass and the integer re-run below take their ROWS
 	// variant; the stage-1 pass above and the checkpoint pass never write them
-	const int rows_total = 16 * ((E->m + 15) / 16);
-	if (rf) {
-		HIPOK(E->rowmax16.ensure((size_t)nu * rows_total * sizeof(uint16_t)));
+	if (any_rowmax(products)) {
+		HIPOK(E->rowmax16.ensure((size_t)nu * 16 * ((E->m + 15) / 16) * sizeof(uint16_t)));
 		L.rowmax16 = E->rowmax16.as<uint16_t>();
 	}
 	// the main pass in packed f16 (option dp_f16): exact while every score of a unit stays below 1 024; the kernel flags the others
@@ -463,41 +547,11 @@ int run_scan_v2(fasim_engine* E, const UnitBatch& B, const std::vector<char>& un
 		}
 	}
 	L.rowmax16 = nullptr;
-	if (rf) {
-		// the lncRNA's profile: rowmax16 holds the main pass of every unit now (the re-run has overwritten the void rows of its units)
-		const int ng = (int)rf->gfirst.size() - 1;
-		const size_t nout = (size_t)ng * 4 * rows_total;
-		rc = upload(E, E->row_gfirst, rf->gfirst.data(), sizeof(int32_t) * rf->gfirst.size()); if (rc) return rc;
-		HIPOK(E->row_out.ensure(nout * sizeof(uint16_t))); HIPOK(E->row_sat.ensure((size_t)nu));
-		HIPOK(hipMemsetAsync(E->row_sat.p, 0, (size_t)nu, E->st));
-		RowFoldLaunch R;
-		R.rowmax16 = E->rowmax16.as<uint16_t>(); R.gfirst = E->row_gfirst.as<int32_t>(); R.ngroups = ng; R.nenc = rf->nenc; R.rows_total = rows_total;
-		R.tab = rf->tab; R.out = E->row_out.as<uint16_t>(); R.sat = E->row_sat.as<uint8_t>();
-		{ TimedScope ts(E, 4); he = launch_rowfold(R, E->st); }
-		if (he != hipSuccess) return fail(E, FASIM_E_HIP, "rowfold launch failed: %s", hipGetErrorString(he));
-		rf->out->resize(nout); rf->sat->resize((size_t)nu);
-		HIPOK(hipMemcpyAsync(rf->out->data(), E->row_out.p, nout * sizeof(uint16_t), hipMemcpyDeviceToHost, E->st));
-		HIPOK(hipMemcpyAsync(rf->sat->data(), E->row_sat.p, (size_t)nu, hipMemcpyDeviceToHost, E->st));
-		if (rf->only) { HIPOK(hipStreamSynchronize(E->st)); return FASIM_OK; }      // profile only: no hits, no hazard re-run, no stage 3
-	}
-	if (tf) {
-		// potential tracks (fasim_scan_track): colmax16 holds the main pass of every unit now -- k_scan_post only reads it, but the
-		// checkpoint pass of the chunked hazard re-run below stores its column maxima there again.  The copies complete with the
-		// batch's other results, at the next synchronisation of the stream.
-		rc = run_track_fold(E, B, tf); if (rc) return rc;
-		if (tf->only) { HIPOK(hipStreamSynchronize(E->st)); return FASIM_OK; }      // track only: no hits, no hazard re-run, no stage 3
-	}
-	if (sf) {
-		// sites (fasim_scan_records_sites): the same moment as the tracks, for the same reason.  Two launches of k_sites: the run
-		// counts per (slice, class) come back on this stream, their prefix sum places every slice's runs and sizes the buffer
-		rc = run_sites_fold(E, B, sf); if (rc) return rc;
-		if (sf->only) { HIPOK(hipStreamSynchronize(E->st)); return FASIM_OK; }      // sites only: no hits, no hazard re-run, no stage 3
-	}
-	if (hf) {
-		// histogram of the potential (fasim_scan_records_hist): the same moment as the tracks, for the same reason
-		rc = run_hist_fold(E, B, hf); if (rc) return rc;
-		if (hf->only) { HIPOK(hipStreamSynchronize(E->st)); return FASIM_OK; }      // histogram only: no hits, no hazard re-run, no stage 3
-	}
+	// the products of the call: colmax16 (rowmax16) holds the main pass of every unit now (the re-run has overwritten the void values
+	// of its units) -- k_scan_post only reads colmax16, but the checkpoint pass of the chunked hazard re-run below stores its column
+	// maxima there again.  The folds' copies complete with the batch's other results, at the next synchronisation of the stream.
+	for (const ScanProduct* x : products) { rc = x->fold(E, C, q); if (rc) return rc; }
+	if (any_only(products)) { HIPOK(hipStreamSynchronize(E->st)); return FASIM_OK; }      // no hits, no hazard re-run, no stage 3
 
 	HIPOK(E->hit_off.ensure(sizeof(int32_t) * nu)); HIPOK(E->hit_cnt.ensure(sizeof(int32_t) * nu));
 	HIPOK(E->thr.ensure(sizeof(int32_t) * nu)); HIPOK(E->hits_total.ensure(64));
