@@ -74,7 +74,8 @@ class ScanStats(C.Structure):
                 ("cells_stage2", C.c_int64), ("cells_stage3", C.c_int64), ("hazard_units", C.c_int64), ("rev_exact", C.c_int64),
                 ("exact_replays", C.c_int64), ("tries_skipped", C.c_int64), ("band_tries", C.c_int64), ("band_proven", C.c_int64),
                 ("band_cells", C.c_int64), ("rev_bound_passes", C.c_int64), ("striped_window_probs", C.c_int64),
-                ("striped_window_ms", C.c_double), ("dp_f16_reruns", C.c_int64)]
+                ("striped_window_ms", C.c_double), ("dp_f16_reruns", C.c_int64),
+                ("finish_lds16", C.c_int64), ("finish_lds64", C.c_int64), ("finish_glob16k", C.c_int64), ("finish_glob1m", C.c_int64)]
 
 
 class SimNode(C.Structure):
@@ -150,7 +151,7 @@ TRACK_CLASSES = ("ParaPlus", "ParaMinus", "AntiMinus", "AntiPlus")
 
 EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_ex", "fasim_engine_destroy", "fasim_last_error", "fasim_set_option", "fasim_set_query",
            "fasim_calc_score_once", "fasim_ssw_pre_align", "fasim_ssw_colmax_word", "fasim_pick_candidates", "fasim_ssw_align", "fasim_pre_align_batch",
-           "fasim_align_batch", "fasim_encode_unit", "fasim_sim_forward_batch", "fasim_sim_finish_unit", "fasim_scan", "fasim_scan_queries", "fasim_scan_records", "fasim_merge_results", "fasim_rebase_offsets", "fasim_load_dna", "fasim_result_free", "fasim_segment_count",
+           "fasim_align_batch", "fasim_align_batch_ex", "fasim_encode_unit", "fasim_sim_forward_batch", "fasim_sim_finish_unit", "fasim_scan", "fasim_scan_queries", "fasim_scan_records", "fasim_merge_results", "fasim_rebase_offsets", "fasim_load_dna", "fasim_result_free", "fasim_segment_count",
            "fasim_tfosorted", "fasim_tfoclass", "fasim_tfosorted_ex", "fasim_tfoclass_ex", "fasim_tail_outputs", "fasim_upper_case", "fasim_free",
            "fasim_synth_dna", "fasim_selfcheck_records", "fasim_read_bed", "fasim_maximum3_f16",
            "fasim_scan_track", "fasim_track_merge", "fasim_track_bedgraph", "fasim_track_free",
@@ -194,6 +195,7 @@ def lib():
                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.fasim_align_batch.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32,
                                     C.POINTER(Alignment)]
+    L.fasim_align_batch_ex.argtypes = L.fasim_align_batch.argtypes + [C.POINTER(C.c_int32)]
     L.fasim_encode_unit.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_char_p, C.c_char_p]
     L.fasim_sim_finish_unit.argtypes = [C.c_char_p, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.POINTER(Params),
                                         C.POINTER(SimNode), C.c_int32, C.POINTER(C.POINTER(_Result))]
@@ -1196,11 +1198,17 @@ class Engine:
                 o += len(t)
         return out_cols, (list(s1) if want_stage1 else None)
 
-    def align_batch(self, windows):
+    def align_batch(self, windows, paths=False):
+        """ssw_align of every window.  paths=True: also, per window, what produced its alignment (fasim_align_batch_ex): 0 nothing
+        aligned, 1 ... 4 the finish tier (16 KB LDS, 64 KB LDS, 16 KB and 1 MB of global scratch), 5 the stripe-faithful replay."""
         blob, offs, lens = self._pack(windows)
         out = (Alignment * len(windows))()
-        self._check(self._L.fasim_align_batch(self._h, blob, offs, lens, len(windows), out))
-        return list(out)
+        if not paths:
+            self._check(self._L.fasim_align_batch(self._h, blob, offs, lens, len(windows), out))
+            return list(out)
+        how = (C.c_int32 * len(windows))()
+        self._check(self._L.fasim_align_batch_ex(self._h, blob, offs, lens, len(windows), out, how))
+        return list(out), list(how)
 
     def sim_forward(self, targets, min_scores):
         """Forward sweep of classic SIM (-F, sim.h:506-571) for a batch of targets: per target the node list it leaves, as

@@ -336,6 +336,12 @@ int fasim_pick_candidates(const int32_t* cols, int32_t n, int32_t threshold, int
 int fasim_align_batch(fasim_engine* E, const char* windows, const int64_t* offsets, const int32_t* lens, int32_t nprob,
 	fasim_alignment* out)
 {
+	return fasim_align_batch_ex(E, windows, offsets, lens, nprob, out, nullptr);
+}
+
+int fasim_align_batch_ex(fasim_engine* E, const char* windows, const int64_t* offsets, const int32_t* lens, int32_t nprob,
+	fasim_alignment* out, int32_t* path)
+{
 	int rc = need_query(E); if (rc) return rc;
 	if (!windows || !offsets || !lens || !out || nprob <= 0) return fail(E, FASIM_E_ARG, "bad batch arguments");
 	HIPOK(hipSetDevice(E->device));
@@ -345,11 +351,14 @@ int fasim_align_batch(fasim_engine* E, const char* windows, const int64_t* offse
 	for (int i = 0; i < nprob; i++) { W[i].unit = i; W[i].t0 = 0; W[i].len = lens[i]; }
 	std::vector<AlignResult> res;
 	std::vector<uint32_t> cigars;
-	rc = run_align_v2(E, B, W, res, cigars, nullptr); if (rc) return rc;
+	std::vector<int32_t> how;
+	rc = run_align_v2(E, B, W, res, cigars, nullptr, path ? &how : nullptr); if (rc) return rc;
+	if (path) memcpy(path, how.data(), sizeof(int32_t) * (size_t)nprob);
 	for (int i = 0; i < nprob; i++) {
 		out[i].sw_score = res[i].sw_score; out[i].ref_begin = res[i].ref_begin; out[i].ref_end = res[i].ref_end;
 		out[i].query_begin = res[i].query_begin; out[i].query_end = res[i].query_end;
-		// (the device tracebacks hold at most 62 runs and fail loudly beyond that; never hand back a truncated CIGAR)
+		// (the finish kernels hold at most ALIGN_MAX_CIGAR = 48 runs and hand longer CIGARs to the replay, whose traceback holds
+		//  MAX_CIGAR_DEV = 62 and fails loudly beyond that; never hand back a truncated CIGAR)
 		if (res[i].cigar_len > 256) return fail(E, FASIM_E_UNSUPPORTED, "alignment %d has %d CIGAR runs; fasim_alignment holds 256", i, res[i].cigar_len);
 		out[i].cigar_len = res[i].cigar_len;
 		if (out[i].cigar_len) memcpy(out[i].cigar, cigars.data() + res[i].cigar_off, sizeof(uint32_t) * out[i].cigar_len);

@@ -593,6 +593,7 @@ static void add_stats(fasim_scan_stats& st, const fasim_scan_stats& x)
 	st.t_stage2_s += x.t_stage2_s; st.t_stage3_s += x.t_stage3_s; st.t_host_s += x.t_host_s; st.cells_stage1 += x.cells_stage1;
 	st.cells_stage2 += x.cells_stage2; st.cells_stage3 += x.cells_stage3; st.hazard_units += x.hazard_units; st.rev_exact += x.rev_exact;
 	st.exact_replays += x.exact_replays; st.tries_skipped += x.tries_skipped;
+	st.finish_lds16 += x.finish_lds16; st.finish_lds64 += x.finish_lds64; st.finish_glob16k += x.finish_glob16k; st.finish_glob1m += x.finish_glob1m;
 	st.band_tries += x.band_tries; st.band_proven += x.band_proven; st.band_cells += x.band_cells; st.rev_bound_passes += x.rev_bound_passes;
 	st.striped_window_probs += x.striped_window_probs; st.striped_window_ms += x.striped_window_ms;
 	st.dp_f16_reruns += x.dp_f16_reruns;

@@ -4,8 +4,11 @@
 
 
 int run_finish(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb>& W, const std::vector<FwdOut>& fo,
-	std::vector<AlignResult>& out, std::vector<uint32_t>& cigars, std::vector<char>& status);
+	std::vector<AlignResult>& out, std::vector<uint32_t>& cigars, std::vector<char>& status, std::vector<int32_t>* path = nullptr);
 bool align_v2_fits(const fasim_engine* E, const std::vector<WindowProb>& W);
+// AlignResult::cigar_len of an alignment that run_finish leaves to the stripe-faithful path with its ends filled in: the reverse pass
+// is done and only the banded part did not fit (device status 2) or the CIGAR has more than ALIGN_MAX_CIGAR runs (status 4)
+static constexpr int CIGAR_LEN_ENDS_ONLY = -2;
 int run_fwd(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb>& W, std::vector<FwdOut>& fo, bool word, const FwdZones* Z = nullptr);
 
 // a9-a11: ssw_align for a list of windows (forward + reverse on the GPU, 16-bit re-runs, banded traceback)
@@ -90,7 +93,22 @@ int run_align(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb>
 		rc = run_finish(E, B, W2, f2, fres, cigars, fst); if (rc) return rc;
 		std::vector<int> left;
 		for (size_t i = 0; i < bp.size(); i++) {
-			if (fst[i] == 2) { left.push_back((int)i); continue; }
+			if (fst[i] == 2) {
+				// ends from the systolic kernel carry no begin: k_banded must not be given the rectangle from (0, 0), whose band
+				// would be |ref_end - read_end| wide and whose traceback is another alignment's
+				const int k = bidx[i];
+				// (device status 11, a reverse pass that cannot decide, leaves no begin: there is nothing to give k_banded then)
+				if (from_sys[k] && fres[i].cigar_len != CIGAR_LEN_ENDS_ONLY)
+					return fail(E, FASIM_E_UNSUPPORTED, "window %d: the 16-bit forward pass found score %d but the reverse pass could not locate its begin", k, bp[i].score);
+				if (from_sys[k]) {
+					AlignEnds& e = ends[k];
+					e.ref_begin = fres[i].ref_begin; e.read_begin = fres[i].query_begin;
+					bp[i].tbase += e.ref_begin; bp[i].q_begin = e.read_begin;
+					bp[i].ref_len = e.ref_end - e.ref_begin + 1; bp[i].read_len = e.read_end - e.read_begin + 1;
+					from_sys[k] = 0;
+				}
+				left.push_back((int)i); continue;
+			}
 			via_finish[i] = 1;
 			bo[i].status = fst[i] == 0 ? 0 : 1;
 		}
@@ -420,12 +438,19 @@ int run_rev_exact(fasim_engine* E, const UnitBatch& B, const std::vector<WindowP
 // reverse pass + banded traceback (k_finish) of windows whose forward result is known.
 // status[k]: 0 = result valid (sw_score 0 when nothing aligned); 1 = the reference's traceback fails (NULL);
 //            2 = must be decided by the stripe-faithful path
+// path (may be null): per alignment, which pass wrote its final device status: 1 k_finish_lds<64, 2048>, 2 k_finish_lds<256, 16384>,
+//            3 k_finish with 16 KB, 4 k_finish with 1 MB (device status 0, 1 or 3 each); 5 = left to the stripe-faithful path (device
+//            status 2 after the last pass, or 4, 10, 11 from any); 0 = nothing aligned (forward score 0)
 int run_finish(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb>& W, const std::vector<FwdOut>& fo,
-	std::vector<AlignResult>& out, std::vector<uint32_t>& cigars, std::vector<char>& status)
+	std::vector<AlignResult>& out, std::vector<uint32_t>& cigars, std::vector<char>& status, std::vector<int32_t>* path)
 {
 	const int n = (int)W.size();
 	out.assign(n, AlignResult()); status.assign(n, 0);
+	if (path) path->assign(n, 0);
 	if (!n) return FASIM_OK;
+	// tier[k]: the pass whose device status stands for alignment k (0 while it is still handed on with status 2)
+	std::vector<char> tier(n, 0);
+	auto settle = [&](const std::vector<AlignOutDev>& a, int pass) { for (int k = 0; k < n; k++) if (!tier[k] && a[k].status != 2) tier[k] = (char)pass; };
 	ProfScope ps(4, "run_finish total");
 	std::vector<FwdProb> probs(n);
 	for (int k = 0; k < n; k++) { probs[k].tbase = (int64_t)W[k].unit * B.tstride + W[k].t0; probs[k].len = W[k].len; probs[k].stream_off = 0; }
@@ -458,6 +483,7 @@ int run_finish(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb
 	HIPOK(hipMemcpyAsync(ao.data(), E->aout.p, sizeof(AlignOutDev) * n, hipMemcpyDeviceToHost, E->st));
 	HIPOK(hipMemcpyAsync(&pool_used, E->cigcount.p, sizeof pool_used, hipMemcpyDeviceToHost, E->st));
 	HIPOK(hipStreamSynchronize(E->st));
+	settle(ao, 1);
 	{
 		// alignments whose band / direction matrix did not fit the LDS kernel (2.3 % on the bench): the same kernel with four times
 		// the LDS per alignment (64 KB per workgroup) first; only what does not fit that either goes to global scratch below
@@ -474,6 +500,7 @@ int run_finish(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb
 			HIPOK(hipMemcpyAsync(ao.data(), E->aout.p, sizeof(AlignOutDev) * n, hipMemcpyDeviceToHost, E->st));
 			HIPOK(hipMemcpyAsync(&pool_used, E->cigcount.p, sizeof pool_used, hipMemcpyDeviceToHost, E->st));
 			HIPOK(hipStreamSynchronize(E->st));
+			settle(ao, 2);
 		}
 	}
 	{
@@ -501,7 +528,12 @@ int run_finish(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb
 			HIPOK(hipMemcpyAsync(ao.data(), E->aout.p, sizeof(AlignOutDev) * n, hipMemcpyDeviceToHost, E->st));
 			HIPOK(hipMemcpyAsync(&pool_used, E->cigcount.p, sizeof pool_used, hipMemcpyDeviceToHost, E->st));
 			HIPOK(hipStreamSynchronize(E->st));
+			settle(ao, 3 + pass);
 		}
+	}
+	if (path) for (int k = 0; k < n; k++) {
+		const int s = ao[k].status;
+		(*path)[k] = (s == 2 || s == 4 || s == 10 || s == 11) ? 5 : (s == 0 && (fo[k].score <= 0 || fo[k].ref_end < 0)) ? 0 : tier[k];
 	}
 	if (pool_used > pool_cap) pool_used = (uint32_t)pool_cap;
 	const uint32_t pool_base = (uint32_t)cigars.size();
@@ -522,6 +554,12 @@ int run_finish(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb
 			const int si = a.status == 2 ? 0 : a.status == 4 ? 1 : a.status == 10 ? 2 : a.status == 11 ? 3 : 4;
 			g_prof.add(19 + si, nm[si], 1e-6);
 		}
+		if (a.status == 2 || a.status == 4) {
+			// the banded part did not fit, or the CIGAR has more than ALIGN_MAX_CIGAR runs: the reverse pass is done, so the begin
+			// is known (CIGAR_LEN_ENDS_ONLY marks it); run_align needs it for the windows whose ends came from the systolic kernel
+			AlignResult& r = out[k];
+			r.ref_begin = a.ref_begin; r.ref_end = a.ref_end; r.query_begin = a.query_begin; r.query_end = a.query_end; r.cigar_len = CIGAR_LEN_ENDS_ONLY;
+		}
 		if (a.status == 2 || a.status == 4 || a.status == 10 || a.status == 11) { status[k] = 2; continue; }
 		if (a.status == 1 || a.status == 3) { status[k] = 1; continue; }
 		AlignResult& r = out[k];
@@ -535,9 +573,10 @@ int run_finish(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb
 // ssw_align for a list of windows: systolic forward pass + finish kernel; everything that may hit the reference's
 // layout-dependent behaviour is re-run by run_align()
 int run_align_v2(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb>& W, std::vector<AlignResult>& out,
-	std::vector<uint32_t>& cigars, fasim_scan_stats* stats)
+	std::vector<uint32_t>& cigars, fasim_scan_stats* stats, std::vector<int32_t>* path)
 {
 	const int n = (int)W.size();
+	if (path) path->assign(n, 5);
 	if (!n) { out.clear(); return FASIM_OK; }
 	if (!align_v2_fits(E, W)) return run_align(E, B, W, out, cigars, stats);
 	std::vector<FwdOut> fo;
@@ -548,7 +587,7 @@ int run_align_v2(fasim_engine* E, const UnitBatch& B, const std::vector<WindowPr
 		rc = run_rev_exact(E, B, W, fo, rv); if (rc) return rc;
 	}
 	std::vector<char> status;
-	rc = run_finish(E, B, W, fo, out, cigars, status); if (rc) return rc;
+	rc = run_finish(E, B, W, fo, out, cigars, status, path); if (rc) return rc;
 	std::vector<int> redo;
 	for (int k = 0; k < n; k++) { if (status[k] == 2) redo.push_back(k); else if (status[k] == 1) { out[k].sw_score = 0; out[k].failed = 1; } }
 	if (!redo.empty()) {
@@ -704,9 +743,10 @@ int stage3_range(fasim_engine* E, BatchCtx& C, int ua, int ub, fasim_scan_stats&
 				if (x.fsel.score <= 0) { x.al.sw_score = 0; continue; }
 				W.push_back({ x.unit, x.c.pos - x.cut + 1, x.cut }); fsel.push_back(x.fsel); who.push_back((int)k);
 			}
-			std::vector<AlignResult> res; std::vector<char> status;
-			rc = run_finish(E, B, W, fsel, res, cigars, status); if (rc) return rc;
+			std::vector<AlignResult> res; std::vector<char> status; std::vector<int32_t> tier;
+			rc = run_finish(E, B, W, fsel, res, cigars, status, &tier); if (rc) return rc;
 			for (size_t i = 0; i < who.size(); i++) {
+				if (tier[i] == 1) st.finish_lds16++; else if (tier[i] == 2) st.finish_lds64++; else if (tier[i] == 3) st.finish_glob16k++; else if (tier[i] == 4) st.finish_glob1m++;
 				CandState& x = cs[who[i]];
 				if (status[i] != 0) { if (g_prof.on) { static const char* nm[6] = { "exact: finish status 0", "exact: finish status 1 (count)", "exact: finish status 2 (count)", "exact: finish status 3 (count)", "exact: finish status 4 (count)", "exact: finish status >= 5 (count)" }; const int si = std::min(5, (int)status[i]); g_prof.add(13 + si, nm[si], 1e-6); } x.exact = 1; continue; }
 				x.al = res[i];

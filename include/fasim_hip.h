@@ -132,6 +132,13 @@ int fasim_pre_align_batch(fasim_engine* e, const char* targets, const int64_t* o
                           int32_t nprob, int32_t* out_cols /* concatenated like targets */, int32_t* out_stage1);
 int fasim_align_batch(fasim_engine* e, const char* windows, const int64_t* offsets, const int32_t* lens,
                       int32_t nprob, fasim_alignment* out);
+/* The same call; path[i] (path may be NULL) tells which part of the engine produced alignment i:
+ *   0 nothing aligned (forward score 0);
+ *   1 k_finish_lds<64, 2048> (16 KB of LDS), 2 k_finish_lds<256, 16384> (64 KB of LDS),
+ *   3 k_finish with 16 KB of global scratch, 4 k_finish with 1 MB of global scratch;
+ *   5 the stripe-faithful replay (also every window when the query or a window does not fit the systolic kernels).  */
+int fasim_align_batch_ex(fasim_engine* e, const char* windows, const int64_t* offsets, const int32_t* lens,
+                         int32_t nprob, fasim_alignment* out, int32_t* path /* [nprob], may be NULL */);
 /* transferString()/reverseSeq()/complement() (rules.h:59-318) for encoding enc in [0,48), canonical
  * execution order of LongTarget(): target[n] and src[n] (src is NUL-padded if letters were dropped). */
 int fasim_encode_unit(const char* seg, int32_t n, int32_t enc, char* target, char* src);
@@ -198,6 +205,9 @@ typedef struct fasim_scan_stats {
 	int64_t striped_window_probs;       /* problems run on the HBM-window variant of k_striped (query stripes too long for the LDS) */
 	double  striped_window_ms;          /* HIP-event time of those launches (also counted in kernel_ms[1] / kernel_ms[5]) */
 	int64_t dp_f16_reruns;              /* units whose scores left the exact range of the f16 k_scan (>= 1 024) and that the integer k_scan ran again */
+	/* alignments of the scan's finish (run_finish) by the storage tier that answered them: k_finish_lds with 16 KB and with
+	 * 64 KB of LDS, k_finish with 16 KB and with 1 MB of global scratch per alignment */
+	int64_t finish_lds16, finish_lds64, finish_glob16k, finish_glob1m;
 } fasim_scan_stats;
 
 struct fasim_result {

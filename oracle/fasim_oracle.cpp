@@ -376,7 +376,7 @@ static inline uint32_t cigar_int(uint32_t len, char op) { return (len << 4) | (o
 // Returns false where the reference returns NULL ("Trace back error") or where it would read
 // memory it never wrote in a way that cannot be reproduced (then `tainted` is set).
 static bool banded_cigar(const int8_t* ref, const int8_t* read, int refLen, int readLen, int score,
-	int band_width, std::vector<uint32_t>& cigar, bool& tainted)
+	int band_width, std::vector<uint32_t>& cigar, bool& tainted, std::vector<int>& bands)
 {
 	std::vector<int32_t> h_b(16, 0), e_b(16, 0), h_c(16, 0);
 	std::vector<int8_t> direction;       // flat, persists across band passes like the realloc'd buffer
@@ -384,6 +384,7 @@ static bool banded_cigar(const int8_t* ref, const int8_t* read, int refLen, int 
 	int max = 0, width = 0, width_d = 0, pass = 0;
 	do {
 		pass++;
+		bands.push_back(band_width);
 		width = band_width * 2 + 3; width_d = band_width * 2 + 1;
 		if ((int)h_b.size() < width + 1) { h_b.resize(width + 1, 0); e_b.resize(width + 1, 0); h_c.resize(width + 1, 0); }
 		const size_t need = (size_t)width_d * readLen * 3 + 3;
@@ -483,7 +484,7 @@ static Alignment align_codes(const int8_t* read, int readLen, const int8_t* ref,
 	const int band = std::abs(rl - ql) + 1;
 	std::vector<uint32_t> cig;
 	bool tainted = false;
-	if (!banded_cigar(ref + ref_begin, read + read_begin, rl, ql, score1, band, cig, tainted)) {
+	if (!banded_cigar(ref + ref_begin, read + read_begin, rl, ql, score1, band, cig, tainted, al.bands)) {
 		al.sw_score = 0; al.tainted = tainted;    // NULL -> sw_score 0 (ssw_cpp.cpp:631-633)
 		return al;
 	}
@@ -902,6 +903,17 @@ int fo_align(const char* rna, int m, const char* window, int n, int* out5, uint3
 {
 	fo::Alignment a = fo::align(std::string(rna, m), std::string(window, n));
 	out5[0] = a.sw_score; out5[1] = a.ref_begin; out5[2] = a.ref_end; out5[3] = a.query_begin; out5[4] = a.query_end;
+	if ((int)a.cigar.size() > cap) return -1;
+	for (size_t i = 0; i < a.cigar.size(); i++) cigar[i] = a.cigar[i];
+	return (int)a.cigar.size();
+}
+int fo_align_ex(const char* rna, int m, const char* window, int n, int* out5, uint32_t* cigar, int cap, int* tainted, int* bands, int band_cap, int* nbands)
+{
+	fo::Alignment a = fo::align(std::string(rna, m), std::string(window, n));
+	out5[0] = a.sw_score; out5[1] = a.ref_begin; out5[2] = a.ref_end; out5[3] = a.query_begin; out5[4] = a.query_end;
+	*tainted = a.tainted ? 1 : 0;
+	*nbands = (int)a.bands.size();
+	for (int i = 0; i < (int)a.bands.size() && i < band_cap; i++) bands[i] = a.bands[i];
 	if ((int)a.cigar.size() > cap) return -1;
 	for (size_t i = 0; i < a.cigar.size(); i++) cigar[i] = a.cigar[i];
 	return (int)a.cigar.size();

@@ -41,6 +41,7 @@ struct Alignment {
 	int sw_score = 0, ref_begin = 0, ref_end = 0, query_begin = 0, query_end = 0;
 	std::vector<uint32_t> cigar;   // BAM encoding (len<<4 | op), op 0=M 1=I 2=D
 	bool tainted = false;          // traceback touched memory the reference leaves undefined
+	std::vector<int> bands;        // band widths banded_sw went through (the last one holds the traceback)
 	std::string cigar_string() const;
 };
 Alignment align(const std::string& rna, const std::string& window);
@@ -110,6 +111,8 @@ void fo_pre_align(const char* rna, int m, const char* target, int n, int* out_co
 int  fo_pick_candidates(const int* cols, int n, int thr, int* out_score, int* out_pos, int cap);
 // out[0..4] = score, ref_begin, ref_end, query_begin, query_end; returns cigar length (<= cap) or -1
 int  fo_align(const char* rna, int m, const char* window, int n, int* out5, uint32_t* cigar, int cap);
+// fo_align plus the Alignment's tainted flag and the band widths banded_sw went through: *nbands of them, the first band_cap in bands[]
+int  fo_align_ex(const char* rna, int m, const char* window, int n, int* out5, uint32_t* cigar, int cap, int* tainted, int* bands, int band_cap, int* nbands);
 void fo_encode_unit(const char* seg, int n, int enc, char* target, char* src);
 // first sweep of SIM(): out[9 * k ..] = score, stari, starj, endi, endj, top, bot, left, right of node k; returns the node count
 int  fo_sim_forward_nodes(const char* rna, int m, const char* target, int n, long min_score, long* out, int cap);

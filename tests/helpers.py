@@ -65,6 +65,20 @@ class Oracle:
         assert k >= 0
         return tuple(out5), cigar_to_string(cig[:k])
 
+    def align_ex(self, q: bytes, w: bytes):
+        """align plus the oracle's `tainted` flag (the reference's traceback reads memory it never wrote: no defined answer) and
+        the band widths its banded_sw went through: ((score, ref_begin, ref_end, q_begin, q_end), CIGAR, tainted, bands)"""
+        L = self.lib
+        L.fo_align_ex.restype = ctypes.c_int
+        L.fo_align_ex.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                  ctypes.POINTER(ctypes.c_uint32), ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                  ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        out5, cig = (ctypes.c_int * 5)(), (ctypes.c_uint32 * 4096)()
+        tainted, bands, nb = ctypes.c_int(0), (ctypes.c_int * 32)(), ctypes.c_int(0)
+        k = L.fo_align_ex(q, len(q), w, len(w), out5, cig, 4096, ctypes.byref(tainted), bands, 32, ctypes.byref(nb))
+        assert k >= 0 and nb.value <= 32
+        return tuple(out5), cigar_to_string(cig[:k]), bool(tainted.value), list(bands[:nb.value])
+
     def sim_forward_nodes(self, q: bytes, t: bytes, min_score: int):
         """node list after the first sweep of SIM() (oracle/fasim_sim_oracle.cpp), as 9-tuples in list order"""
         out = (ctypes.c_long * (9 * 50))()
@@ -614,3 +628,479 @@ def q2_units_of_gap_plants(orc, m):
         if [(c, v) for c, v in enumerate(ref) if v > thr] != [(c, v) for c, v in enumerate(buf) if v > thr]:
             out.append(enc)
     return out
+
+
+# ---- the storage tiers of the stage-3 finish (test_finish_tiers_cpu.py, test_gpu_finish_tiers.py) -------------------------------
+# run_finish (engine_stage3.cpp) offers every alignment to four passes, each handing on what it cannot hold:
+#   1  k_finish_lds<64, 2048>     reverse-pass ring of 64 rows, band arrays of 32 entries, 2 048 direction cells
+#   2  k_finish_lds<256, 16384>   ring 256, band arrays 128, 16 384 cells
+#   3  k_finish, 16 KB of global scratch per alignment (band arrays of at most 256 entries)
+#   4  k_finish, 1 MB per alignment (band arrays of at most 4 099 entries)
+#   5  the stripe-faithful replay (what no pass holds, and CIGARs of more than 48 runs)
+FT_RING_1, FT_BAND_ARRAY_1, FT_CELLS_1 = 64, 32, 2048
+FT_RING_2, FT_BAND_ARRAY_2, FT_CELLS_2 = 256, 128, 16384
+FT_SLOT_3, FT_WCAP_3 = 16384, 256
+FT_SLOT_4, FT_WCAP_4 = 1 << 20, 4099
+FT_MAX_RUNS = 48                     # ALIGN_MAX_CIGAR
+FT_GAP_OPEN, FT_GAP_EXT = 16, 4
+FT_LENGTHS = (1200, 3300)            # one and two systolic tiles
+FT_MAX_WINDOW = 200
+FT_SEED = 4242
+FT_NO_MATCH = b"N" * 24
+FT_ONE_GAP = (1, 2, 3, 8, 12, 13, 14, 15, 16, 20, 30, 31, 32, 50, 62, 63, 70, 100)
+FT_DOUBLING = (1, 2, 3, 5, 8, 9, 16, 17, 30, 40)
+
+
+def score_class(score):
+    """'lo' (the in-kernel reverse pass), 'mid' (148 ... 250: the exact reverse pass supplies the begin), 'hi' (the 16-bit pass)"""
+    return "lo" if score < 148 else "mid" if score < 251 else "hi"
+
+
+def _ft_sc(a, b):
+    return 5 if a == b and a in b"ACGT" else -4
+
+
+def _ft_ring_overflows(q, w, S, ref_end, read_end, ring):
+    """reverse_pass_lds restated: the DP anchored at (read_end, ref_end) walks back column by column and keeps the rows that can
+    still reach S (a cell is dropped when its value plus 5 per remaining diagonal step stays below S); True when the live rows
+    [lo, hi] of a column, or the row the walk has reached, no longer fit a ring of `ring` entries (device status 2)."""
+    NEG = -30000
+    R, C = read_end + 1, ref_end + 1
+    g0 = _ft_sc(q[read_end], w[ref_end])
+    if g0 <= 0 or g0 == S:
+        return False
+    lo = hi = 0
+    G, E = {0: g0}, {0: NEG}
+    for j in range(1, C):
+        t = w[ref_end - j]
+        F = diag = NEG
+        nlo = nhi = -1
+        if hi - lo + 2 >= ring:
+            return True
+        i = lo
+        while i < R:
+            inside = i <= hi
+            gp = G.get(i, NEG) if inside else NEG
+            ep = E.get(i, NEG) if inside else NEG
+            e = max(ep - FT_GAP_EXT, gp - FT_GAP_OPEN)
+            g = diag + _ft_sc(q[read_end - i], t) if diag > NEG // 2 else NEG
+            g = max(g, e, F)
+            rest = min(R - 1 - i, C - 1 - j)
+            if g <= 0 or g + 5 * rest < S:
+                g = NEG
+            if e <= 0 or e + 5 * rest < S:
+                e = NEG
+            if g == S:
+                return False
+            diag = gp
+            G[i], E[i] = g, e
+            if g > NEG // 2 or e > NEG // 2:
+                nlo = i if nlo < 0 else nlo
+                nhi = i
+            F = max(F - FT_GAP_EXT, g - FT_GAP_OPEN)
+            if F <= 0:
+                F = NEG
+            if i > hi and F <= NEG // 2 and diag <= NEG // 2:
+                break
+            if i - lo + 2 >= ring:
+                return True
+            i += 1
+        if nlo < 0:
+            return False
+        lo, hi = nlo, nhi
+    return False
+
+
+def finish_tier_restated(q, w, ends, bands, runs=0):
+    """Which pass of run_finish must answer window w of query q, from the oracle's (score, ref_begin, ref_end, query_begin,
+    query_end), the band widths its banded_sw went through and the number of runs of its CIGAR: 0 nothing aligned, 1 ... 4 the
+    tier, 5 the replay.  A pass holds an alignment when
+      LDS passes: the reverse pass fits the ring (not run for scores 148 ... 250, whose begin the exact reverse pass supplies), and
+          for every band b: 2 * b + 3 + 1 <= band array entries and (2 * b + 1) * readLen <= direction cells;
+      global passes: wcap = min(refLen + 3, FT_WCAP), the band arrays take 12 * wcap bytes of the slot and the direction rows the
+          rest; for every band: 2 * b + 3 <= wcap or refLen + 3 <= FT_WCAP, and stride * readLen <= rest, where the stride is
+          2 * b + 1, or refLen once 2 * b + 1 > refLen (dense rows, indexed by the column itself)."""
+    s, rb, re_, qb, qe = ends
+    if s <= 0:
+        return 0
+    if runs > FT_MAX_RUNS:
+        return 5
+    ref_len, read_len = re_ - rb + 1, qe - qb + 1
+    assert bands and bands[0] == abs(ref_len - read_len) + 1
+    need_rev = not 148 <= s < 251
+
+    def lds(ring, arr, cells):
+        if not all(2 * b + 3 + 1 <= arr and (2 * b + 1) * read_len <= cells for b in bands):
+            return False
+        return not (need_rev and _ft_ring_overflows(q, w, s, re_, qe, ring))
+
+    def glob(slot, wcap_max):
+        wcap = min(ref_len + 3, wcap_max)
+        rest = slot - 12 * wcap
+        if rest <= 0:
+            return False
+        for b in bands:
+            stride = ref_len if 2 * b + 1 > ref_len else 2 * b + 1
+            if (2 * b + 3 > wcap and ref_len + 3 > wcap_max) or stride * read_len > rest:
+                return False
+        return True
+
+    if lds(FT_RING_1, FT_BAND_ARRAY_1, FT_CELLS_1):
+        return 1
+    if lds(FT_RING_2, FT_BAND_ARRAY_2, FT_CELLS_2):
+        return 2
+    if glob(FT_SLOT_3, FT_WCAP_3):
+        return 3
+    if glob(FT_SLOT_4, FT_WCAP_4):
+        return 4
+    return 5
+
+
+def finish_tier_query(m):
+    """The query of the finish-tier tests: seeded random ACGT of m rows with three low-complexity tracts of 72 rows, (GA)n, (GAA)n
+    and a random homopurine run, from row m // 3 on, 150 rows apart (finish_tier_tracts)."""
+    import synth
+    q = bytearray(synth.random_rna(m, 8800000 + m))
+    rng = synth._Rng(8810000 + m)
+    for (lo, hi), unit in zip(finish_tier_tracts(m), (b"GA", b"GAA", None)):
+        q[lo:hi] = bytes(unit[i % len(unit)] if unit else b"AG"[rng.below(2)] for i in range(hi - lo))
+    return bytes(q)
+
+
+def finish_tier_tracts(m):
+    return tuple((m // 3 + 150 * k, m // 3 + 150 * k + 72) for k in range(3))
+
+
+def _ft_shadow_rows(script):
+    """Rows, relative to the first row of a planted alignment, that an F of 132 or more can reach below the planted path during
+    the 8-bit forward pass: a path cell of H >= 148 in row r opens F = H - 16 in row r + 1, which loses 4 per row.  The pass ends
+    at the first column whose maximum reaches 251, so nothing after that column counts."""
+    rows, r, h = set(), -1, 0
+    for op, n in script:
+        for _ in range(n if op in "MX" else 1):
+            if op == "M":
+                r, h = r + 1, h + 5
+            elif op == "X":
+                r, h = r + 1, max(0, h - 4)
+            else:
+                h = max(0, h - FT_GAP_OPEN - FT_GAP_EXT * (n - 1))
+                r += n if op == "I" else 0
+            if h >= 148:
+                rows.update(range(r + 1, r + 2 + (h - 148) // 4))
+            if h >= 251:
+                return rows
+    return rows
+
+
+def forward_pass_flags(q, w, r0=0, r1=None):
+    """Does the systolic 8-bit forward pass flag window w (FwdOut.flags & 1 by its coarse test, the one queries with stripes of
+    fewer than 96 rows get)?  It does when an F of 132 or more enters the first row of a stripe of the reference (rows k * ceil(m /
+    16), k >= 1) in a column up to the first one whose maximum reaches 251, where the byte pass ends.  Plain Gotoh recurrences,
+    a column at a time over query rows [r0, r1); F[i] = max over k < i of H[k] - 16 - 4 (i - k - 1) as a running maximum."""
+    import numpy as np
+    m = len(q)
+    seg = (m + 15) // 16
+    r1 = m if r1 is None else min(m, r1)
+    r0 = max(0, r0)
+    n = r1 - r0
+    qa = np.frombuffer(q, dtype=np.uint8)[r0:r1]
+    idx4 = 4 * np.arange(n, dtype=np.int64)
+    starts = np.array([i for i in range(n) if (r0 + i) % seg == 0 and r0 + i > 0], dtype=np.int64)
+    hp, ep = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    for t in w:
+        e = np.maximum(np.maximum(ep - FT_GAP_EXT, hp - FT_GAP_OPEN), 0)
+        d = np.concatenate(([0], hp[:-1])) + np.where((qa == t) & (t in b"ACGT"), 5, -4)
+        h0 = np.maximum(np.maximum(d, e), 0)
+        run = np.maximum.accumulate(h0 + idx4)                      # max over k <= i of H[k] + 4 k
+        f = np.concatenate(([0], run[:-1] - idx4[1:] - (FT_GAP_OPEN - FT_GAP_EXT)))      # F entering row i
+        f = np.maximum(f, 0)
+        if len(starts) and f[starts].max() >= 132:
+            return True
+        hp, ep = np.maximum(h0, f), e
+        if hp.max() >= 251:
+            return False
+    return False
+
+
+def planted_path_is_the_only_best(q, w, path, planted, r0=0, r1=None):
+    """Is the planted path the one best local alignment of window w against query rows [r0, r1)?  path: column -> query row of the
+    planted matches; planted: its score.  The recurrences of forward_pass_flags through every column, with all scores times 1 000
+    and one more for a match that is not on the planted path: a path that reaches the planted score, or beats it, with the help of
+    such a match (a flank that runs on into the bases next to it by chance, a cheaper way round a gap) ends above 1 000 * planted."""
+    import numpy as np
+    r1 = len(q) if r1 is None else min(len(q), r1)
+    r0 = max(0, r0)
+    n = r1 - r0
+    qa = np.frombuffer(q, dtype=np.uint8)[r0:r1]
+    idx4 = 4000 * np.arange(n, dtype=np.int64)
+    hp, ep, best = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), 0
+    for c, t in enumerate(w):
+        sc = np.where((qa == t) & (t in b"ACGT"), 5001, -4000)
+        if c in path and 0 <= path[c] - r0 < n and sc[path[c] - r0] > 0:
+            sc[path[c] - r0] = 5000
+        e = np.maximum(np.maximum(ep - 1000 * FT_GAP_EXT, hp - 1000 * FT_GAP_OPEN), 0)
+        h0 = np.maximum(np.maximum(np.concatenate(([0], hp[:-1])) + sc, e), 0)
+        run = np.maximum.accumulate(h0 + idx4)
+        f = np.maximum(np.concatenate(([0], run[:-1] - idx4[1:] - 1000 * (FT_GAP_OPEN - FT_GAP_EXT))), 0)
+        hp, ep = np.maximum(h0, f), e
+        best = max(best, int(hp.max()))
+    return best == 1000 * planted
+
+
+def finish_tier_windows(m, seed, with_scripts=False, query=None):
+    """[(group, window)] (with_scripts: [(group, window, script)], None for a window without one) for the query finish_tier_query(m): windows of at most 200 nt, each a query slice with planted edits and
+    0 ... 10 random bases on either side.  Edit scripts are lists of (op, n): 'M' n query rows copied, 'X' one row replaced by
+    another base, 'I' n query rows left out (a run of I in the CIGAR), 'D' n random columns put in (a run of D).
+    Groups: ungapped, one-gap, doubling, edges, ties, many-runs (see test_finish_tiers_cpu.py).  A 'D' gap of 100 columns is not
+    in the set: either flank must score more than the gap costs, 5 f > 12 + 4 * 100, and two flanks of 83 do not fit 200 columns.
+    Placement: the systolic 8-bit forward pass flags a window in which an F of 132 or more enters a stripe of the reference
+    (every ceil(m / 16) rows), and a flagged window is replayed whatever its alignment needs.  The slice is therefore moved until
+    no stripe boundary lies in the rows such an F can reach below the planted path (_ft_shadow_rows), and the window is kept only
+    if the forward recurrences themselves show no such F (forward_pass_flags: the diagonal that runs on past the end of a flank
+    stays above 148 for as long as chance has it); otherwise the slice moves on.  The finish kernels then get every window.
+    A window is also kept only if the planted path is its one best alignment (planted_path_is_the_only_best), so that the oracle's
+    CIGAR shows the planted gaps; the bases around the slice and at the ends of an inserted run are picked not to continue a flank.
+    A script for which 48 slices fail either test is left out (test_finish_tiers_cpu.py names the one that the set may lack).
+    Slices keep 300 rows clear of the tracts, which at 1 200 rows leaves the starts 10 ... 24 (plus up to a stripe) and 787 ... 824:
+    about half of the windows there begin within 100 rows of the query's start, where the reverse pass runs out of query before it
+    runs out of ring, so ring overflow at 1 200 rows is exercised by the other half and by the 3 300-row query."""
+    import synth
+    rng = synth._Rng(seed)
+    q = finish_tier_query(m) if query is None else query          # (another query of m rows: its ties group holds no tracts)
+    assert len(q) == m
+    seg = (m + 15) // 16
+    tracts = finish_tier_tracts(m)
+    free = [(10, tracts[0][0] - 300 - seg), (tracts[2][1] + 15, m - 300 - seg)]   # slice starts that keep 300 rows clear of the tracts
+    out = []
+
+    def rnd(n, first_not=None, last_not=None):
+        s = bytearray(b"ACGT"[rng.below(4)] for _ in range(n))
+        if n and first_not is not None:
+            s[0] = next(c for c in b"ACGT"[rng.below(4):] + b"ACGT" if c != first_not)
+        if n and last_not is not None and (n > 1 or first_not is None or s[-1] == last_not):
+            s[-1] = next(c for c in b"ACGT"[rng.below(4):] + b"ACGT" if c != last_not and (n > 1 or c != first_not))
+        return bytes(s)
+
+    def row(i):
+        return q[i] if 0 <= i < m else None
+
+    def build(script, a, left, right):
+        """the window of `script` applied to the query from row a on, with `left` / `right` random bases around it: an inserted or
+        added base never matches the query row that the alignment would reach next, so the planted ends and gaps stay put"""
+        w, i, path = bytearray(), a, {}
+        for op, n in script:
+            if op == "M":
+                path.update((left + len(w) + d, i + d) for d in range(n))
+                w += q[i:i + n]
+                i += n
+            elif op == "X":
+                w += rnd(1, first_not=q[i])
+                i += 1
+            elif op == "I":
+                i += n
+            else:
+                ins = bytearray(rnd(n, first_not=row(i), last_not=row(i - 1)))
+                # eight bases at either end that do not continue the flank next to them, straight on or after a gap of one
+                for d in range(min(8, n // 2)):
+                    ins[d] = next(c for c in b"ACGT" if c not in (row(i + d - 1), row(i + d), row(i + d + 1)))
+                    ins[n - 1 - d] = next(c for c in b"ACGT" if c not in (row(i - 2 - d), row(i - 1 - d), row(i - d)))
+                w += ins
+        assert i <= m
+        # the bases around the slice: random, but none continues the alignment straight on or after a gap of one
+        lpad, rpad = bytearray(rnd(left)), bytearray(rnd(right))
+        for d in range(left):
+            lpad[left - 1 - d] = next(c for c in b"ACGT"[rng.below(4):] + b"ACGT" if c not in (row(a - 2 - d), row(a - 1 - d), row(a - d)))
+        for d in range(right):
+            rpad[d] = next(c for c in b"ACGT"[rng.below(4):] + b"ACGT" if c not in (row(i + d - 1), row(i + d), row(i + d + 1)))
+        return bytes(lpad) + bytes(w) + bytes(rpad), path
+
+    def place(script, a=None):
+        rows = sum(n for op, n in script if op in "MI") + sum(1 for op, _ in script if op == "X")
+        shadow = _ft_shadow_rows(script)
+        if a is None:
+            lo, hi = free[rng.below(2)]
+            a = lo + rng.below(hi - lo)
+            a = next((a + d for d in range(seg + 1) if not any((a + d + r) % seg == 0 for r in shadow)), None)
+            if a is None:                # the rows such an F reaches cover a whole stripe: this script cannot avoid the flag
+                return None
+        assert a + rows <= m and not any((a + r) % seg == 0 and a + r < m for r in shadow), (script, a)
+        return a
+
+    def add(group, script, a=None, left=None, right=None):
+        fixed = a is not None
+        rows = sum(n for op, n in script if op in "MI") + sum(1 for op, _ in script if op == "X")
+        cols = sum(n for op, n in script if op in "MD") + sum(1 for op, _ in script if op == "X")
+        left = rng.below(11) if left is None else left
+        right = rng.below(11) if right is None else right
+        left, right = min(left, (FT_MAX_WINDOW - cols) // 2), min(right, (FT_MAX_WINDOW - cols + 1) // 2)
+        planted = sum(5 * n if op == "M" else -4 if op == "X" else -(FT_GAP_OPEN + FT_GAP_EXT * (n - 1)) for op, n in script)
+        a = place(script, a)
+        for _ in range(48):
+            if a is None:
+                return                   # no placement of this script escapes the flag
+            w, path = build(script, a, left, right)
+            assert 0 < len(w) <= FT_MAX_WINDOW, (group, script)
+            # kept if the byte pass does not flag it and nothing beats the planted path (a flank that runs on into the bases next
+            # to it by chance, a cheaper way round a gap); the tracts have their ties and a gap of one residue often has two places to
+            # be, so those two groups are kept as they come
+            if not forward_pass_flags(q, w, a - 12, a + rows + 80) and (group in ("ties", "many-runs") or planted_path_is_the_only_best(q, w, path, planted, a - 12, a + rows + 12)):
+                out.append((group, w, script))
+                return
+            a = a if fixed else place(script)          # (a fixed slice is tried again with other bases around it)
+
+    def spread(n, nx):
+        """n rows with nx of them replaced, evenly"""
+        if not nx:
+            return [("M", n)]
+        head = []
+        if n > 60:                       # (the first 52 rows stay whole: the byte pass is over before the first replaced row)
+            head, n = [("M", 52)], n - 52
+        nx = min(nx, n // 3)             # (at most every second row of what is left)
+        step, s = n // (nx + 1), head
+        assert step >= 2, (n, nx)
+        for _ in range(nx):
+            s += [("M", step - 1), ("X", 1)]
+        return s + [("M", n - nx * step)]
+
+    # ungapped: below 148 (up to 29 rows), 148 ... 250 (30 ... 50 rows), 251 and more; the replaced rows lower the score below
+    # 5 per column, which is what lets the reverse pass keep many rows alive (and leave the 64-row ring)
+    for n in (20, 24, 27, 29, 30, 33, 40, 45, 50, 51, 60, 64, 65, 66, 80, 100, 128, 150, 190):
+        add("ungapped", [("M", n)])
+    for n, nx in ((40, 6), (44, 7), (60, 4), (60, 11), (64, 12), (80, 6), (80, 15), (100, 8), (100, 20), (128, 12), (150, 14), (150, 30), (190, 10), (190, 20), (190, 40)):
+        add("ungapped", spread(n, nx))
+    # 251 and more that stay in the 64-row ring: the F chain below a cell of value g lives for (g - 16) / 4 rows of the reverse pass,
+    # pruned or not, and walks out of the ring unless the query ends first, so these start less than 60 rows into the query
+    for i, n in enumerate((55, 60, 70, 80, 90, 100, 110, 120, 52, 57, 65, 75)):
+        add("ungapped", [("M", n)], a=46 + i if m < 3072 else 5 + 4 * i)
+    # one gap: the shortest flanks that still make the joined alignment beat either flank, and long flanks
+    for k in FT_ONE_GAP:
+        for op in "ID":
+            room = 190 if op == "I" else 198 - k             # (a long gap leaves little for the random bases around the slice)
+            if 2 * ((12 + 4 * k) // 5 + 1) > room:
+                assert (op, k) == ("D", 100)
+                continue
+            fmin = min((12 + 4 * k) // 5 + 9, room // 2)         # 40 above the gap's cost: more than a flank gains by running on by chance
+            for f in sorted({fmin, min(room // 2, max(fmin + 12, 32)), min(90, room // 2)}):
+                add("one-gap", [("M", f), (op, k), ("M", f)])
+    # below 148 with a band of 15 ... 17: out of the 16 KB LDS pass by the band array alone
+    for f1, op, k, f2 in ((18, "I", 14, 18), (19, "I", 15, 19), (20, "D", 14, 20), (18, "D", 15, 19), (20, "I", 16, 20), (21, "D", 16, 21), (19, "D", 14, 18), (20, "I", 15, 21)):
+        add("one-gap", [("M", f1), (op, k), ("M", f2)])
+    # a 'D' gap of 62 or 63 columns between flanks of 54 ... 58: band 63 or 64 is too wide for the 64 KB LDS pass (2 b + 4 > 128)
+    # while (2 b + 1) * readLen still fits the 16 KB slot next to its band arrays, which sends the window to the 16 KB global pass
+    for k, f1, f2 in [(62, f1, f2) for f1 in range(54, 59) for f2 in range(54, 59) if f1 + f2 <= 112] + [(63, f1, f2) for f1 in range(54, 57) for f2 in range(54, 57) if f1 + f2 <= 110]:
+        add("one-gap", [("M", f1), ("D", k), ("M", f2)])
+    # doubling: refLen == readLen, the band starts at 1 and doubles until it holds both gaps
+    # Each outer flank pays for the gap next to it with 40 to spare.  The middle flank has to outweigh BOTH gaps (24 + 8 k) against the
+    # path that stays near the diagonal through the f + k unrelated columns between the outer flanks, which chance makes cheaper than
+    # 1.75 a column: it gets what 200 columns leave, up to 70 rows.  Up to k = 9 also three short flanks (below 251).
+    for k in FT_DOUBLING:
+        fmin = max(20, (12 + 4 * k) // 5 + 9)
+        for ops in ("ID", "DI"):
+            for f, mid in sorted({(fmin, fmin) if k <= 9 else (fmin, min(70, 190 - k - 2 * fmin)), (fmin, min(70, 190 - k - 2 * fmin))}):
+                add("doubling", [("M", f), (ops[0], k), ("M", mid), (ops[1], k), ("M", f)])
+    # edges
+    add("edges", [("M", 28)], a=0)
+    add("edges", [("M", 34)], a=0, left=0)
+    add("edges", [("M", 20), ("D", 3), ("M", 22)], left=0)
+    add("edges", [("M", 26)], a=m - 26)
+    add("edges", [("M", 60)], a=m - 60, right=0)
+    add("edges", [("M", 22), ("I", 2), ("M", 24)], right=0)
+    add("edges", [("M", 70)], left=0, right=0)
+    out.append(("edges", q[m // 2:m // 2 + 1], None))            # one column
+    out.append(("edges", FT_NO_MATCH, None))                     # no match at all
+    # ties: slices of the low-complexity tracts with small indels, below 148 (no F of 132 anywhere, so any rows will do)
+    for t, (lo, hi) in enumerate(tracts):
+        for j, (f1, op, k, f2) in enumerate(((12, "I", 1, 12), (10, "D", 1, 14), (13, "I", 2, 13), (12, "D", 2, 13), (14, "I", 3, 12), (11, "D", 3, 14),
+                                              (27, "M", 0, 0), (9, "D", 1, 9))):
+            script = [("M", f1)] + ([(op, k), ("M", f2)] if k else [])
+            add("ties", script, a=lo + 3 + 5 * j + t)
+    # many runs: 7-row blocks separated by 1-residue gaps of one kind, every gap pays (35 > 16): 51, 49, 53 and 51 runs
+    for pattern, blocks in (("I", 26), ("D", 25), ("I", 27), ("I", 26)):
+        script = [("M", 7)]
+        for g in range(blocks - 1):
+            script += [(pattern[g % len(pattern)], 1), ("M", 7)]
+        add("many-runs", script)
+    return out if with_scripts else [(g, w) for g, w, _ in out]
+
+
+_FT_CENSUS = {}
+
+
+def finish_tier_census(orc, m):
+    """The windows of query length m with the oracle's answer and the restated tier, computed once and shared: dicts group, window,
+    script, ends (score, ref_begin, ref_end, query_begin, query_end), cigar, tainted, bands, runs, cls, tier."""
+    if m not in _FT_CENSUS:
+        q, rows = finish_tier_query(m), []
+        for g, w, script in finish_tier_windows(m, FT_SEED + m, with_scripts=True):
+            ends, cig, tainted, bands = orc.align_ex(q, w)
+            runs = sum(c in "MID" for c in cig)
+            rows.append({"group": g, "window": w, "script": script, "ends": ends, "cigar": cig, "tainted": tainted, "bands": bands, "runs": runs,
+                         "cls": score_class(ends[0]), "tier": finish_tier_restated(q, w, ends, bands, runs)})
+        _FT_CENSUS[m] = (q, rows)
+    return _FT_CENSUS[m]
+
+
+FT_SCAN_M = 1200
+FT_SCAN_ENCS = (22, 23, 26, 27, 40, 41)      # one-to-one encodings: every query letter has a pre-image
+
+
+def finish_tier_scan_case(orc):
+    """(query, 10 kb DNA record of two segments, plants) for the scan-level finish test: random DNA with the pre-images of 24 gapped
+    windows planted in it, all below 251 (a scan never finishes an alignment of 251 or more): first those with a band too wide for the
+    16 KB LDS pass (restated tier 2), those without inserted columns before the others.  The query is random without two equal letters in a
+    row: under the one-to-one encodings a repeated query letter is a TT or CC of the strand a triplex record shows, which costs the
+    record 1 000 of stability (penaltyT, penaltyC), and no record would come of the plants.  Two plants of neighbouring scores
+    share a unit, so that neither falls below the unit's threshold of 0.8 times its best stage-1 score.
+    plants: dicts seg, enc, pos, n, qb, qe (query rows), cigar."""
+    import synth
+    rng = synth._Rng(8820000)
+    q = bytearray(b"A")
+    while len(q) < FT_SCAN_M:
+        q.append([c for c in b"ACGT" if c != q[-1]][rng.below(3)])
+    q = bytes(q)
+    rows = []
+    for g, w, script in finish_tier_windows(FT_SCAN_M, FT_SEED + 7, with_scripts=True, query=q):
+        if g not in ("one-gap", "doubling"):
+            continue
+        ends, cig, tainted, bands = orc.align_ex(q, w)
+        if score_class(ends[0]) != "hi" and not tainted:
+            rows.append({"window": w, "ends": ends, "cigar": cig, "inserted": any(op == "D" for op, _ in script),
+                         "tier": finish_tier_restated(q, w, ends, bands, sum(c in "MID" for c in cig))})
+    rows.sort(key=lambda r: (r["tier"] != 2, r["inserted"], -r["ends"][0]))
+    picked = sorted(rows[:24], key=lambda r: r["ends"][0])
+    assert len(picked) == 24, len(rows)
+    dna = bytearray(synth.random_dna(10000, 8830000))
+    plants = []
+    for i, r in enumerate(picked):
+        unit, slot = i // 2, i % 2
+        s, enc = unit // 6, FT_SCAN_ENCS[unit % 6]
+        tract = preimage(r["window"], enc, rng)
+        pos = 4900 * s + 300 + 2100 * slot + 150 * (unit % 6)
+        dna[pos:pos + len(tract)] = tract
+        plants.append({"seg": s, "enc": enc, "pos": pos, "n": len(tract), "qb": r["ends"][3], "qe": r["ends"][4], "cigar": r["cigar"]})
+    assert len(dna) == 10000
+    return q, bytes(dna), plants
+
+
+def finish_tier_oracle_scan(build_dir, tmp_dir, q, dna):
+    """the oracle's `scan` of the scan-level case (cLength 20 = ntMin), parsed: (meta, units)"""
+    import synth
+    rna_fa, dna_fa = os.path.join(str(tmp_dir), "ftq.fa"), os.path.join(str(tmp_dir), "ftd.fa")
+    synth.write_fasta(rna_fa, "ftq", q)
+    synth.write_fasta(dna_fa, f"syn|chrT|1-{len(dna)}", dna)
+    return parse_scan(oracle_cli(build_dir, "scan", rna_fa, dna_fa, "-threads", "8"))
+
+
+def finish_tier_planted_records(units, plants):
+    """plants whose unit holds a triplex record over at least 30 of the plant's query rows"""
+    hit = []
+    for p in plants:
+        for u in units:
+            if (u["seg"], u["enc"]) != (p["seg"], p["enc"]):
+                continue
+            for x in u["triplexes"]:
+                a, b = sorted((int(x[0]), int(x[1])))
+                if min(b - 1, p["qe"]) - max(a - 1, p["qb"]) + 1 >= 30:
+                    hit.append(p)
+                    break
+    return hit
