@@ -159,7 +159,7 @@ EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_e
            "fasim_scan_tfo_profile", "fasim_tfo_profile_merge", "fasim_tfo_profile_tsv", "fasim_tfo_profile_free",
            "fasim_scan_records_sites", "fasim_sites_merge", "fasim_sites_bed", "fasim_sites_free",
            "fasim_scan_records_sites_aligned", "fasim_site_hits_merge", "fasim_site_hits_tsv", "fasim_site_hits_free",
-           "fasim_scan_oligos", "fasim_oligo_panel_tsv",
+           "fasim_scan_oligos", "fasim_oligo_panel_tsv", "fasim_scan_oligos_aligned",
            "fasim_scan_records_hist", "fasim_scan_oligos_hist", "fasim_hist_merge", "fasim_hist_free", "fasim_shuffle_query",
            "fasim_hist_threshold", "fasim_hist_tsv",
            # the reference's own ssw.h ABI (include/ssw.h)
@@ -281,6 +281,10 @@ def lib():
                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int64, C.c_int64, C.POINTER(Params),
                                     C.c_int32, C.c_int32, C.POINTER(C.POINTER(_Sites)), C.c_int32, C.POINTER(C.POINTER(_Track)),
                                     C.POINTER(ScanStats)]
+    L.fasim_scan_oligos_aligned.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
+                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int64, C.c_int64, C.POINTER(Params),
+                                            C.c_int32, C.c_int32, C.POINTER(C.POINTER(_Sites)), C.POINTER(C.POINTER(_SiteHits)),
+                                            C.POINTER(ScanStats)]
     L.fasim_oligo_panel_tsv.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.POINTER(_Sites)), C.c_int32,
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.fasim_scan_records_hist.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
@@ -1456,6 +1460,40 @@ class Engine:
         if trks is None:
             return sites
         return sites, [[Track(_native=trks[q * nrec + r]) for r in range(nrec)] for q in range(nq)]
+
+    def scan_oligos_aligned(self, oligos, dnas, params: Params | None = None, min_value: int = 1, max_gap: int = 0,
+                            seg_first: int = 0, seg_count: int = -1):
+        """The sites of a panel of short oligos and the hit of every site (fasim_scan_oligos_aligned): `(sites, hits)`, lists per
+        oligo of lists per record of Sites and SiteHits.  sites is exactly what scan_oligos() returns; a hit is what
+        scan_sites_aligned() would give for a lncRNA, with the oligo in its place.  `dnas` as for scan_oligos().  Shards of a
+        segment range merge with merge_site_hits().  Option site_short = 0 runs the hits on the lncRNAs' kernel (same results)."""
+        p = params or default_params()
+        if isinstance(dnas, (bytes, bytearray)):
+            dnas = [bytes(dnas)]
+        if dnas is None:
+            blob, offs, lens, nrec = None, None, None, 1        # the whole resident buffer: the engine knows its length
+        else:
+            blob = b"".join(dnas)
+            nrec = len(dnas)
+            offs = (C.c_int64 * max(1, nrec))()
+            lens = (C.c_int64 * max(1, nrec))()
+            o = 0
+            for i, d in enumerate(dnas):
+                offs[i], lens[i] = o, len(d)
+                o += len(d)
+        oligos = [bytes(x) for x in oligos]
+        nq = len(oligos)
+        arr = (C.c_char_p * max(1, nq))(*oligos)
+        qlens = (C.c_int32 * max(1, nq))(*[len(x) for x in oligos])
+        nout = max(1, nq) * max(1, nrec)
+        sts = (C.POINTER(_Sites) * nout)()
+        hts = (C.POINTER(_SiteHits) * nout)()
+        totals = (ScanStats * max(1, nq))()
+        self._check(self._L.fasim_scan_oligos_aligned(self._h, arr, qlens, nq, blob, offs, lens, nrec, seg_first, seg_count, C.byref(p),
+                                                      min_value, max_gap, sts, hts, totals))
+        self.last_totals = [self._stats_dict(totals[q]) for q in range(nq)]
+        return ([[Sites(_native=sts[q * nrec + r]) for r in range(nrec)] for q in range(nq)],
+                [[SiteHits(hts[q * nrec + r]) for r in range(nrec)] for q in range(nq)])
 
     def scan_hist(self, dnas, params: Params | None = None, controls: int = 0, seed: int = 0, records: bool = False, seg_first: int = 0,
                   seg_count: int = -1, rnas=None):

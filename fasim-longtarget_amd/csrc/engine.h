@@ -137,6 +137,8 @@ struct fasim_engine {
 	DevBuf sites_counts, sites_offsets, sites_runs, sites_sat;   // fasim_scan_records_sites only: k_sites' run counts per (slice, class), their prefix sum, the runs and saturation flags of the batch
 	DevBuf sa_q, sa_tcodes, sa_probs, sa_ends, sa_rows, sa_items, sa_dirs, sa_cigar, sa_ciglen;   // fasim_scan_records_sites_aligned only: query codes, the chunk's units, problems, end cells, row state of long queries, path items, direction bytes, CIGARs
 	DevBuf hist, hist_zone, hist_zones, hist_sat;   // fasim_scan_records_hist only: k_hist's counters of the batch, its zone bounds per segment, the zone values and saturation flags
+	int opt_site_short = -1;                     // option "site_short": 1 = the hits of oligo sites end on k_site_ends_short (default), 0 = on k_site_ends (-1 = default / environment FASIM_SITE_SHORT)
+	int opt_site_chunk = 0;                      // option "site_chunk": problems per chunk of the hits phase where lower than the phase's own limit (0 = that limit)
 	DevBuf oligo_q;                              // fasim_scan_oligos only: the panel's query codes, FASIM_MAX_OLIGO bytes per oligo
 	DevBuf rowmax16, row_out, row_gfirst, row_sat;   // fasim_scan_tfo_profile only: k_scan's row maxima of the batch, k_rowfold's groups, result and saturation flags
 	int opt_numa = 1;                            // option "numa_affinity": pin the scan's host threads to the GPU's NUMA node (no-op on one node)
@@ -317,6 +319,13 @@ inline int band_mode(const fasim_engine* E)
 	static const int env = [] { const char* e = getenv("FASIM_BAND"); return e ? atoi(e) : 1; }();
 	return E->opt_band >= 0 ? E->opt_band : env;
 }
+// option site_short / FASIM_SITE_SHORT: 1 (default) = fasim_scan_oligos_aligned finds the end and start cells with k_site_ends_short,
+// 0 = with k_site_ends (the A/B arm and the fallback; the results are the same)
+inline bool site_short_enabled(const fasim_engine* E)
+{
+	static const int env = [] { const char* e = getenv("FASIM_SITE_SHORT"); return e ? atoi(e) : 1; }();
+	return (E->opt_site_short >= 0 ? E->opt_site_short : env) != 0;
+}
 // option dp_f16 / FASIM_DP_F16: 1 (default) = k_scan's main pass and the reverse pass of stage 3 run their packed-f16 variants
 // (dp_f16.h); 0 = the integer kernels.  The records are the same either way.
 inline bool dp_f16_mode(const fasim_engine* E)
@@ -486,6 +495,9 @@ struct SiteAlignReq {
 	std::vector<std::string> queries;
 	fasim_sites* const* sites = nullptr;         // [query * nrec + record], final
 	fasim_site_hits** hits = nullptr;            // [query * nrec + record], filled by the phase
+	// fasim_scan_oligos_aligned (section 18): every query has at most SCAN_SHORT_MAX nt and the ends launch is k_site_ends_short --
+	// a problem is a lane, not a workgroup, so a chunk takes 262 144 problems and no row state.  false: everything as it was
+	bool short_query = false;
 };
 int run_site_align(fasim_engine* E, SiteAlignReq& R);
 void site_hits_free(fasim_site_hits* h);

@@ -5,6 +5,7 @@
 // pair: the worker stages and encodes the batch once (batch_encode, the head of scan_batch) and then runs, per oligo, k_scan_short
 // into colmax16 and the folds that the products of the call (sites, tracks, histogram: ScanProduct, engine.h) run behind k_scan, with
 // their host merges.  The engine's own query is not involved.
+// fasim_scan_oligos_aligned: the same call for sites, then the hit of every site (run_site_align with k_site_ends_short, section 18).
 #include "engine.h"
 
 namespace {
@@ -276,6 +277,37 @@ int fasim_scan_oligos(fasim_engine* E, const char* const* oligos, const int32_t*
 	int32_t min_value, int32_t max_gap, fasim_sites** out_sites, int32_t bin, fasim_track** out_tracks, fasim_scan_stats* totals)
 {
 	return scan_oligos_core(E, oligos, lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, min_value, max_gap, out_sites, bin, out_tracks, nullptr, totals);
+}
+
+int fasim_scan_oligos_aligned(fasim_engine* E, const char* const* oligos, const int32_t* lens, int32_t nq, const char* dna,
+	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
+	int32_t min_value, int32_t max_gap, fasim_sites** out_sites, fasim_site_hits** out_hits, fasim_scan_stats* totals)
+{
+	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
+	if (!out_sites || !out_hits) return fail(E, FASIM_E_ARG, "bad arguments");
+	// first phase: the sites call itself, refusals included (its sites and totals are this call's)
+	int rc = scan_oligos_core(E, oligos, lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, min_value, max_gap, out_sites, 1, nullptr, nullptr, totals);
+	if (rc) return rc;
+	const size_t nout = (size_t)nq * (size_t)nrec;
+	for (size_t o = 0; o < nout; o++) out_hits[o] = nullptr;
+	const int64_t whole_off = 0, whole_len = (int64_t)E->dna_host.size();
+	if (!dna && !rec_off && !rec_len && nrec == 1) { rec_off = &whole_off; rec_len = &whole_len; }
+	// second phase: the hits, oligo by oligo, on the engine's own stream (section 18)
+	SiteAlignReq R;
+	R.dna = dna ? dna : E->dna_host.data(); R.rec_off = rec_off; R.rec_len = rec_len; R.nrec = nrec; R.seg_first = seg_first; R.seg_count = seg_count;
+	R.p = *pp; R.sites = out_sites; R.hits = out_hits; R.short_query = site_short_enabled(E);
+	try {
+		for (int q = 0; q < nq; q++) R.queries.emplace_back(oligos[q], oligos[q] + lens[q]);
+		rc = run_site_align(E, R);
+	} catch (const std::bad_alloc&) { rc = fail(E, FASIM_E_NOMEM, "out of memory"); }
+	if (rc) {
+		(void)hipStreamSynchronize(E->st);
+		for (size_t o = 0; o < nout; o++) {
+			site_hits_free(out_hits[o]); out_hits[o] = nullptr;
+			fasim_sites_free(out_sites[o]); out_sites[o] = nullptr;
+		}
+	}
+	return rc;
 }
 
 int fasim_scan_oligos_hist(fasim_engine* E, const char* const* oligos, const int32_t* lens, int32_t nq, const char* dna,

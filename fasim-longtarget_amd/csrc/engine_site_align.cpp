@@ -6,6 +6,7 @@
 // (unit, column of the peak, value) -- one per selected segment that covers the peak, so that the smallest segment that holds the
 // value can be chosen afterwards --, the list is cut into chunks, and a chunk is: encode its units on the host and upload them,
 // k_site_ends, the end and start cells back, k_site_path for the rectangles, the CIGARs back, convert_triplex on the host.
+// The hits of oligo sites (fasim_scan_oligos_aligned, section 18) are the same phase with k_site_ends_short in k_site_ends' place.
 #include <climits>
 #include <unordered_map>
 
@@ -125,10 +126,12 @@ int run_site_align(fasim_engine* E, SiteAlignReq& R)
 				}
 			}
 			nsites += (int64_t)flat.size(); 
-			// chunks of problems: at most 4 096 problems, 256 MB of units, 512 MB of row state
+			// chunks of problems: at most 4 096 problems (short_query: 262 144, a problem is a lane there), 256 MB of units, 512 MB of row state
 			const size_t max_units = std::max<size_t>(1, ((size_t)256 << 20) / (size_t)tstride);
 			const bool rows_hbm = m > SITE_ALIGN_LDS_ROWS;
-			const size_t max_probs = rows_hbm ? std::max<size_t>(1, std::min<size_t>(4096, ((size_t)512 << 20) / ((size_t)6 * m))) : 4096;
+			size_t max_probs = R.short_query ? (size_t)262144 : rows_hbm ? std::max<size_t>(1, std::min<size_t>(4096, ((size_t)512 << 20) / ((size_t)6 * m))) : 4096;
+			if (E->opt_site_chunk > 0) max_probs = std::min<size_t>(max_probs, (size_t)E->opt_site_chunk);      // (option site_chunk: tests of the chunk loop)
+			const int64_t short_cells = R.short_query ? (int64_t)(m + npad) * (site_short_warm(m) + 16) : 0;      // pass (i) of k_site_ends_short: the same for every problem
 			std::vector<char> done(flat.size(), 0);      // the site has its unit: later (larger) segments are not looked at
 			// level by level: the second covering segment of a site is a problem only where the first does not hold the value;
 			// within a level by (unit, column), so that the problems of a unit share its upload
@@ -160,7 +163,7 @@ int run_site_align(fasim_engine* E, SiteAlignReq& R)
 					w.unit = it->second;
 					SiteAlignProb P; P.tbase = (int64_t)w.unit * tstride; P.n = w.n; P.jp = w.jp; P.value = w.value; P.pad = 0;
 					probs.push_back(P);
-					cells += (int64_t)m * (w.jp + 1);
+					cells += R.short_query ? short_cells : (int64_t)m * (w.jp + 1);
 				}
 				const int np = (int)probs.size();
 				if (E->sa_tcodes.ensure(tcodes.size()) != hipSuccess || E->sa_probs.ensure((size_t)np * sizeof(SiteAlignProb)) != hipSuccess ||
@@ -175,7 +178,7 @@ int run_site_align(fasim_engine* E, SiteAlignReq& R)
 				L.probs = E->sa_probs.as<SiteAlignProb>(); L.nprob = np; L.rows = rows_hbm ? E->sa_rows.as<int16_t>() : nullptr;
 				L.ends = E->sa_ends.as<SiteAlignEnds>();
 				hipError_t he;
-				{ TimedScope ts(E, 4); he = launch_site_ends(L, E->st); }
+				{ TimedScope ts(E, 4); he = R.short_query ? launch_site_ends_short(L, E->st) : launch_site_ends(L, E->st); }
 				if (he != hipSuccess) return fail(E, FASIM_E_HIP, "site hits (ends) launch failed: %s", hipGetErrorString(he));
 				std::vector<SiteAlignEnds> ends((size_t)np);
 				HIPOK(hipMemcpyAsync(ends.data(), E->sa_ends.p, (size_t)np * sizeof(SiteAlignEnds), hipMemcpyDeviceToHost, E->st));

@@ -42,6 +42,11 @@
 //                           per class sites and largest value).  Never -TFOsorted / -TFOclass.  Exit status 2, nothing written: without
 //                           --sites, with --sites-align, -F, --track, --screen, --tfo-profile or --accumulate-records, or an -f2
 //                           record that is empty or longer than 112 nt
+//     --oligo-hits          with --oligos --sites V: every site of every oligo with its hit (fasim_scan_oligos_aligned, DESIGN.md section
+//                           18): beside each oligo's sites file the table that --sites V --sites-only --sites-align writes for a lncRNA
+//                           of that name (<stem>-TFOsites-<V>-aligned; set mode <O>/<oligo>-<f1 stem>.sites-<V>.aligned.tsv).  The sites
+//                           files and the panel table are what they are without it.  Exit status 2, nothing written: without --oligos,
+//                           without --sites, with --potential-hist
 //     --potential-hist      histogram of the potential with shuffled controls (fasim_scan_records_hist): per
 //                           strand class and value how many bases of the DNA reach it.  --hist-controls K (default 0) scans K
 //                           composition-preserving shuffles of every lncRNA too (--hist-seed S, default 0) and reports the false discovery
@@ -236,7 +241,8 @@ static int g_out_failed = 0;
 // --track: bin width (0: no tracks), smallest value written, --track-only; --screen / --screen-only: peaks (no_stage3: no records)
 // --tfo-profile / --tfo-profile-only: the lncRNA's profile (never together with tracks or peaks)
 // --sites V / --sites-gap G / --sites-only: the sites above a fixed potential (never together with tracks, peaks or the profile)
-struct TrackOpt { int bin = 0, min_value = 1; bool only = false, peaks = false, no_stage3 = false, tfo = false, tfo_only = false; int sites = 0, sites_gap = 0; bool sites_only = false, sites_align = false, oligos = false;
+struct TrackOpt { int bin = 0, min_value = 1; bool only = false, peaks = false, no_stage3 = false, tfo = false, tfo_only = false; int sites = 0, sites_gap = 0; bool sites_only = false, sites_align = false, oligos = false, oligo_hits = false;
+	bool hits() const { return sites_align || oligo_hits; }      // the sites' hits are wanted (--sites-align, or --oligo-hits of a panel)
 	// --potential-hist: the histogram, K controls per lncRNA under a seed (hist_ctl: their sequences, lncRNA after lncRNA), the FDR bound
 	bool hist = false, hist_only = false; int hist_controls = 0; uint64_t hist_seed = 0; double hist_fdr = 0.05; const std::vector<std::string>* hist_ctl = nullptr; };
 
@@ -398,6 +404,9 @@ static int scan_group(const std::vector<fasim_engine*>& engines, const std::vect
 				rc[(size_t)d] = fasim_scan_records_hist(engines[(size_t)d], hq.data() + nq, hl.data() + nq, nctl, dna.data(), off.data(), len.data(), nrec, first, count, &p,
 					nullptr, gpart[(size_t)d].data() + nq, nullptr);
 		}
+		else if (sites && trk.oligos && hits)
+			rc[(size_t)d] = fasim_scan_oligos_aligned(engines[(size_t)d], qp.data(), ql.data(), nq, dna.data(), off.data(), len.data(), nrec, first, count, &p,
+				trk.sites, trk.sites_gap, spart[(size_t)d].data(), hpart[(size_t)d].data(), nullptr);
 		else if (sites && trk.oligos)
 			rc[(size_t)d] = fasim_scan_oligos(engines[(size_t)d], qp.data(), ql.data(), nq, dna.data(), off.data(), len.data(), nrec, first, count, &p,
 				trk.sites, trk.sites_gap, spart[(size_t)d].data(), 0, nullptr, nullptr);
@@ -547,7 +556,7 @@ int main(int argc, char* const* argv)
 		{ "track", required_argument, NULL, 1009 }, { "track-min", required_argument, NULL, 1010 }, { "track-only", no_argument, NULL, 1011 },
 		{ "screen", no_argument, NULL, 1012 }, { "screen-only", no_argument, NULL, 1013 },
 		{ "tfo-profile", no_argument, NULL, 1014 }, { "tfo-profile-only", no_argument, NULL, 1015 },
-		{ "sites", required_argument, NULL, 1016 }, { "sites-gap", required_argument, NULL, 1017 }, { "sites-only", no_argument, NULL, 1018 }, { "sites-align", no_argument, NULL, 1019 }, { "oligos", no_argument, NULL, 1020 },
+		{ "sites", required_argument, NULL, 1016 }, { "sites-gap", required_argument, NULL, 1017 }, { "sites-only", no_argument, NULL, 1018 }, { "sites-align", no_argument, NULL, 1019 }, { "oligos", no_argument, NULL, 1020 }, { "oligo-hits", no_argument, NULL, 1026 },
 		{ "potential-hist", no_argument, NULL, 1021 }, { "hist-controls", required_argument, NULL, 1022 }, { "hist-seed", required_argument, NULL, 1023 },
 		{ "hist-fdr", required_argument, NULL, 1024 }, { "potential-hist-only", no_argument, NULL, 1025 }, { 0, 0, 0, 0 } };
 	int opt;
@@ -592,12 +601,13 @@ int main(int argc, char* const* argv)
 		case 1018: trk.sites_only = true; break;
 		case 1019: trk.sites_align = true; break;
 		case 1020: trk.oligos = true; break;
+		case 1026: trk.oligo_hits = true; break;
 		case 1021: trk.hist = true; break;
 		case 1022: hist_arg_given = true; trk.hist_controls = strict_int(optarg, -1); break;
 		case 1023: { hist_arg_given = true; char* end = nullptr; errno = 0; trk.hist_seed = strtoull(optarg, &end, 10); if (end == optarg || *end != '\0' || errno == ERANGE || optarg[0] == '-') hist_arg_bad = true; break; }
 		case 1024: { hist_arg_given = true; char* end = nullptr; trk.hist_fdr = strtod(optarg, &end); if (end == optarg || *end != '\0') trk.hist_fdr = -1.0; break; }
 		case 1025: trk.hist_only = true; break;
-		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only] [--sites-align] [--oligos]] [--potential-hist [--hist-controls K] [--hist-seed S] [--hist-fdr Q] [--potential-hist-only]]\n"); return 2;
+		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only] [--sites-align] [--oligos [--oligo-hits]]] [--potential-hist [--hist-controls K] [--hist-seed S] [--hist-fdr Q] [--potential-hist-only]]\n"); return 2;
 		}
 	}
 	if (all_records && accumulate) { fprintf(stderr, "fasim: --all-records and --accumulate-records exclude each other\n"); return 2; }
@@ -623,6 +633,7 @@ int main(int argc, char* const* argv)
 	if (trk.hist && 2 * (long long)p.overlapLength > (long long)p.cutLength) { fprintf(stderr, "fasim: --potential-hist needs -o of at most half of -c (a base would lie in three segments)\n"); return 2; }
 	if (trk.oligos && !sites && !trk.hist) { fprintf(stderr, "fasim: --oligos needs --sites V or --potential-hist\n"); return 2; }
 	if (trk.oligos && (trk.sites_align || trk.tfo)) { fprintf(stderr, "fasim: --oligos is not available with --sites-align, -F, --track, --screen, --tfo-profile or --accumulate-records\n"); return 2; }
+	if (trk.oligo_hits && (!trk.oligos || !sites || trk.hist)) { fprintf(stderr, "fasim: --oligo-hits needs --oligos --sites V (and is not available with --potential-hist)\n"); return 2; }
 	if (trk.oligos) trk.sites_only = true;      // a panel has no triplex records: the sites files and the panel table are all it writes
 	if (trk.oligos && trk.hist) trk.hist_only = true;      // (or the oligos' histograms)
 	if (!sites) trk.sites = 0;
@@ -712,7 +723,7 @@ int main(int argc, char* const* argv)
 	const bool sites_set = sites && (all_records || regions);
 	std::vector<std::map<int64_t, std::string>> sites_text(sites_set ? rnas.size() : 0);      // [lncRNA][record number or BED index]
 	// --sites-align: beside every sites file the table of the sites' hits, <stem>-TFOsites-<V>-aligned or .sites-<V>.aligned.tsv
-	std::vector<std::map<int64_t, std::string>> hits_text(sites_set && trk.sites_align ? rnas.size() : 0);
+	std::vector<std::map<int64_t, std::string>> hits_text(sites_set && trk.hits() ? rnas.size() : 0);
 	auto write_sites_set = [&]() -> int {
 		int bad = 0;
 		for (size_t q = 0; q < sites_text.size(); q++) {
@@ -723,7 +734,7 @@ int main(int argc, char* const* argv)
 			fasim_free(text);
 			for (const auto& kv : sites_text[q]) t += kv.second;
 			bad |= write_file(outdir + "/" + rnas[q].name + "-" + base + ".sites-" + std::to_string(trk.sites) + ".bed", t.data(), (int64_t)t.size());
-			if (!trk.sites_align) continue;
+			if (!trk.hits()) continue;
 			fasim_site_hits nohits; memset(&nohits, 0, sizeof nohits);
 			if (fasim_site_hits_tsv(&none, &nohits, "", 1, rnas[q].name.c_str(), "", 1, &text, &len) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
 			std::string h(text, (size_t)len);
@@ -958,7 +969,7 @@ int main(int argc, char* const* argv)
 			std::vector<std::vector<fasim_site_hits*>> ghits;
 			std::vector<fasim_hist*> ghist;
 			if (scan_group(engines, rnas, gdna, goff, glen, p, res, trk, gtracks, gpeaks, trk.tfo ? &gprof : nullptr, sites ? &gsites : nullptr,
-				sites && trk.sites_align ? &ghits : nullptr, trk.hist ? &ghist : nullptr)) return 1;
+				sites && trk.hits() ? &ghits : nullptr, trk.hist ? &ghist : nullptr)) return 1;
 			if (trk.hist && hist_set) { for (size_t k = 0; k < ghist.size(); k++) { fasim_hist* t = ghist[k]; ghist[k] = nullptr; if (hist_fold(hist_acc[k], t)) return 1; } }
 			else if (trk.hist) {
 				// a plain run: <stem>-TFOhist next to -TFOsorted

@@ -211,6 +211,12 @@ struct SitePathLaunch {
 hipError_t launch_site_ends(const SiteEndsLaunch& L, hipStream_t st);
 hipError_t launch_site_path(const SitePathLaunch& L, hipStream_t st);
 
+// ---- site_short.hip: k_site_ends for an oligo, one problem per lane over a window of the unit ------------
+// k_site_ends_short<ROWS>, ROWS = 16 * ceil(m / 16) in {16, ..., 112}: the same problems in, the same SiteAlignEnds out as
+// k_site_ends, for queries of 1 <= m <= SCAN_SHORT_MAX nt (L.rows is not used; L.npad must be 16 * ceil(m / 16) - m)
+int site_short_warm(int m);             // columns before (jp & ~15) at which pass (i) starts from zeros: W(m) + 16 rounded up to 16
+hipError_t launch_site_ends_short(const SiteEndsLaunch& L, hipStream_t st);      // hipErrorInvalidValue: a query the kernel does not take
+
 // ---- rowfold.hip: per-base profile of the lncRNA folded from the row maxima of a batch -------------------------
 // Group g = segments [gfirst[g], gfirst[g + 1]) of the batch (the run of segments of one record, or the whole batch); the result is
 // out[g][4 classes][rows_total] = maximum over the group's units of the class, taint bit dropped.

@@ -85,6 +85,11 @@ const char* fasim_last_error(const fasim_engine* e);   /* e may be NULL: last gl
  * (env FASIM_HAZARD_CHUNKS, FASIM_HAZARD_SNAP).
  * key "striped_window" (0): 1 runs every stripe-faithful (k_striped) launch on its HBM-window variant, which otherwise serves only
  * the queries whose stripes do not fit the LDS (env FASIM_STRIPED_WINDOW; for tests: results do not depend on it).
+ * key "site_short" (1): fasim_scan_oligos_aligned finds the end and start cell of every hit with k_site_ends_short, one problem per
+ * lane over a window of the unit (csrc/site_short.hip); 0 = with k_site_ends, one workgroup per problem over the unit's prefix (env
+ * FASIM_SITE_SHORT; results do not depend on it).  key "site_chunk" (0): problems per chunk of the hits phase of
+ * fasim_scan_records_sites_aligned and fasim_scan_oligos_aligned where it is lower than the phase's own limit (4 096, oligos 262 144;
+ * value <= 0 restores those; results do not depend on it).
  * key "numa_affinity" (1): for the duration of a scan the calling thread and the threads the scan starts are pinned to the CPUs of
  * the GPU's NUMA node (/sys/bus/pci/devices/<bus id>/local_cpulist); the caller's affinity is restored afterwards; no effect on a
  * single-node machine.
@@ -465,6 +470,19 @@ int  fasim_scan_oligos(fasim_engine* e, const char* const* oligos, const int32_t
  * the first two, classes, <Class>_max the largest site value of the class over all records, 0 without a site (nrec == 0: all zeros).  Free with fasim_free. */
 int  fasim_oligo_panel_tsv(const char* const* names, const int32_t* lens, int32_t nq, const fasim_sites* const* sites, int32_t nrec,
                            char** text, int64_t* text_len);
+/* The sites of a panel and the hit of every site (csrc/site_short.hip): fasim_scan_oligos with sites wanted
+ * (its arguments, refusals and totals; out_sites is byte for byte what it returns), then per oligo q and record r the hit list
+ * out_hits[q * nrec + r] of out_sites[q * nrec + r]: section 15's definition with the oligo in the lncRNA's place.  The hit lists
+ * are fasim_site_hits: they merge with fasim_site_hits_merge, print with fasim_site_hits_tsv and free with fasim_site_hits_free.
+ * Every site of a call with cutLength above 6 000 keeps cigar_len = -1.  out_sites == NULL or out_hits == NULL: FASIM_E_ARG.  On
+ * failure both outputs are freed and NULL; FASIM_E_NOMEM (no device memory for a chunk of the hits phase) leaves the engine usable.
+ * Option site_short / FASIM_SITE_SHORT = 0 finds the end and start cells with k_site_ends instead of k_site_ends_short: the same
+ * results, slower. */
+int  fasim_scan_oligos_aligned(fasim_engine* e, const char* const* oligos, const int32_t* lens, int32_t nq,
+                               const char* dna, const int64_t* rec_off, const int64_t* rec_len, int32_t nrec,
+                               int64_t seg_first, int64_t seg_count, const fasim_params* p, int32_t min_value, int32_t max_gap,
+                               fasim_sites** out_sites /* [nq * nrec] */, fasim_site_hits** out_hits /* [nq * nrec] */,
+                               fasim_scan_stats* totals /* [nq], may be NULL */);
 
 /* ---- histograms of the potential with shuffled controls (csrc/hist.hip) -------------------------------------- */
 /* How much of a record set reaches potential v, for every v.  P[c][x] is the bin = 1 track of section 11 of a record scanned alone.
