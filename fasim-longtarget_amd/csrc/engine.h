@@ -553,6 +553,32 @@ struct BatchCtx {
 	bool stage3_done = false;                           // -F: the whole batch was finished in the scan phase
 };
 
+// ---- what the folds of the products share (engine_stage2.cpp, engine_hist.cpp) -----------------------------------------------------
+// the front half's arguments of a column fold over batch C, its saturation flags in `sat`
+inline void class_fold_fill(ClassFoldLaunch& L, const fasim_engine* E, const BatchCtx& C, const DevBuf& sat)
+{
+	L.colmax16 = E->colmax16.as<uint16_t>(); L.seg_len = E->seg_len.as<int32_t>();
+	L.nseg = C.nseg; L.nenc = C.nenc; L.tstride = C.B.tstride; L.nchunk = C.track_nchunk; L.tab = C.tab; L.sat = sat.as<uint8_t>();
+}
+// a fold's saturation flags, one per unit: ensured and zeroed on the stream ahead of the launch ...
+inline int sat_begin(fasim_engine* E, DevBuf& dev, size_t nu)
+{
+	HIPOK(dev.ensure(nu));
+	HIPOK(hipMemsetAsync(dev.p, 0, nu, E->st));
+	return FASIM_OK;
+}
+// ... and their copy into the batch's vector (sized by the caller) queued behind it
+inline int sat_end(fasim_engine* E, const DevBuf& dev, std::vector<uint8_t>& host)
+{
+	HIPOK(hipMemcpyAsync(host.data(), dev.p, host.size(), hipMemcpyDeviceToHost, E->st));
+	return FASIM_OK;
+}
+// a batch's flags onto the counts per o = q * nrec + record of the unit's segment
+inline void sat_add(std::vector<int64_t>& sat, const std::vector<uint8_t>& flags, const BatchCtx& C, int q, int nrec)
+{
+	for (size_t u = 0; u < flags.size(); u++) sat[(size_t)q * (size_t)nrec + (size_t)C.srec[u / (size_t)C.nenc]] += flags[u];
+}
+
 // ---- internals shared by the engine's translation units (engine.cpp: C-ABI; engine_stage2.cpp: stages 1+2; engine_stage3.cpp:
 //      stage 3; engine_scan.cpp: batches, workers, result packing) ------------------------------------------------------------
 struct WindowProb { int unit, t0, len; };

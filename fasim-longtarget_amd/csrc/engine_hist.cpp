@@ -106,19 +106,17 @@ int HistReq::fold(fasim_engine* E, BatchCtx& C, int q) const
 	}
 	rc = upload(E, E->hist_zone, C.hist_zone.data(), sizeof(int32_t) * 2 * (size_t)C.nseg); if (rc) return rc;
 	HIPOK(hipMemsetAsync(E->hist.p, 0, (size_t)4 * HIST_BINS * sizeof(uint32_t), E->st));
-	HIPOK(hipMemsetAsync(E->hist_sat.p, 0, (size_t)nu, E->st));
+	rc = sat_begin(E, E->hist_sat, (size_t)nu); if (rc) return rc;
 	HistLaunch H;
-	H.colmax16 = E->colmax16.as<uint16_t>(); H.seg_len = E->seg_len.as<int32_t>(); H.zone = E->hist_zone.as<int32_t>();
-	H.nseg = C.nseg; H.nenc = C.nenc; H.tstride = C.B.tstride; H.nchunk = C.track_nchunk; H.zstride = C.hist_zstride; H.tab = C.tab;
-	H.hist = E->hist.as<uint32_t>(); H.zones = E->hist_zones.as<uint16_t>(); H.sat = E->hist_sat.as<uint8_t>();
+	class_fold_fill(H, E, C, E->hist_sat);
+	H.zone = E->hist_zone.as<int32_t>(); H.zstride = C.hist_zstride; H.hist = E->hist.as<uint32_t>(); H.zones = E->hist_zones.as<uint16_t>();
 	{ TimedScope ts(E, 4); he = launch_hist(H, E->st); }
 	if (he != hipSuccess) return fail(E, FASIM_E_HIP, "hist launch failed: %s", hipGetErrorString(he));
 	try { C.hist.resize(4 * ntop); C.hist_zones.resize(nzone); C.hist_sat.resize((size_t)nu); } catch (const std::bad_alloc&) { return fail(E, FASIM_E_NOMEM, "out of memory"); }
 	for (int c = 0; c < 4; c++)
 		HIPOK(hipMemcpyAsync(C.hist.data() + (size_t)c * ntop, E->hist.as<uint32_t>() + (size_t)c * HIST_BINS, ntop * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st));
 	if (nzone) HIPOK(hipMemcpyAsync(C.hist_zones.data(), E->hist_zones.p, nzone * sizeof(uint16_t), hipMemcpyDeviceToHost, E->st));
-	HIPOK(hipMemcpyAsync(C.hist_sat.data(), E->hist_sat.p, (size_t)nu, hipMemcpyDeviceToHost, E->st));
-	return FASIM_OK;
+	return sat_end(E, E->hist_sat, C.hist_sat);
 }
 
 // the batch's counters, zones and skipped segments [b0, b1) of the call's segment table into the arrays of query q

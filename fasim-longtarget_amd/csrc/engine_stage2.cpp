@@ -273,8 +273,8 @@ int TfoReq::fold(fasim_engine* E, BatchCtx& C, int) const
 	const int ng = (int)gfirst.size() - 1;
 	const size_t nout = (size_t)ng * 4 * rows_total;
 	rc = upload(E, E->row_gfirst, gfirst.data(), sizeof(int32_t) * gfirst.size()); if (rc) return rc;
-	HIPOK(E->row_out.ensure(nout * sizeof(uint16_t))); HIPOK(E->row_sat.ensure((size_t)nu));
-	HIPOK(hipMemsetAsync(E->row_sat.p, 0, (size_t)nu, E->st));
+	HIPOK(E->row_out.ensure(nout * sizeof(uint16_t)));
+	rc = sat_begin(E, E->row_sat, (size_t)nu); if (rc) return rc;
 	RowFoldLaunch R;
 	R.rowmax16 = E->rowmax16.as<uint16_t>(); R.gfirst = E->row_gfirst.as<int32_t>(); R.ngroups = ng; R.nenc = C.nenc; R.rows_total = rows_total;
 	R.tab = C.tab; R.out = E->row_out.as<uint16_t>(); R.sat = E->row_sat.as<uint8_t>();
@@ -282,8 +282,7 @@ int TfoReq::fold(fasim_engine* E, BatchCtx& C, int) const
 	if (he != hipSuccess) return fail(E, FASIM_E_HIP, "rowfold launch failed: %s", hipGetErrorString(he));
 	C.rowfold.resize(nout); C.row_sat.resize((size_t)nu);
 	HIPOK(hipMemcpyAsync(C.rowfold.data(), E->row_out.p, nout * sizeof(uint16_t), hipMemcpyDeviceToHost, E->st));
-	HIPOK(hipMemcpyAsync(C.row_sat.data(), E->row_sat.p, (size_t)nu, hipMemcpyDeviceToHost, E->st));
-	return FASIM_OK;
+	return sat_end(E, E->row_sat, C.row_sat);
 }
 
 // fasim_scan_tfo_profile: the groups of a finished scan phase into the arrays of query q (and of the group's record), by maximum
@@ -317,18 +316,18 @@ int TrackReq::fold(fasim_engine* E, BatchCtx& C, int) const
 	rc = upload(E, E->track_phase, phase.data(), sizeof(int32_t) * nseg); if (rc) return rc;
 	const size_t nout = bin >= 1 ? (size_t)nseg * nchunk * 4 * track_slice_stride(bin) : 0;      // (bin == 0: peaks only)
 	const size_t npeak = peaks ? (size_t)nseg * nchunk * 4 : 0;
-	HIPOK(E->track.ensure(nout * sizeof(uint16_t))); HIPOK(E->track_sat.ensure((size_t)nu));
+	HIPOK(E->track.ensure(nout * sizeof(uint16_t)));
 	if (npeak) HIPOK(E->track_peaks.ensure(npeak * sizeof(TrackPeak)));
-	HIPOK(hipMemsetAsync(E->track_sat.p, 0, (size_t)nu, E->st));
+	rc = sat_begin(E, E->track_sat, (size_t)nu); if (rc) return rc;
 	TrackLaunch T;
-	T.colmax16 = E->colmax16.as<uint16_t>(); T.seg_len = E->seg_len.as<int32_t>(); T.phase = E->track_phase.as<int32_t>();
-	T.nseg = nseg; T.nenc = C.nenc; T.tstride = C.B.tstride; T.nchunk = nchunk; T.bin = bin; T.tab = C.tab;
-	T.out = E->track.as<uint16_t>(); T.sat = E->track_sat.as<uint8_t>(); T.peaks = npeak ? E->track_peaks.as<TrackPeak>() : nullptr;
+	class_fold_fill(T, E, C, E->track_sat);
+	T.phase = E->track_phase.as<int32_t>(); T.bin = bin;
+	T.out = E->track.as<uint16_t>(); T.peaks = npeak ? E->track_peaks.as<TrackPeak>() : nullptr;
 	{ TimedScope ts(E, 4); he = launch_track(T, E->st); }
 	if (he != hipSuccess) return fail(E, FASIM_E_HIP, "track launch failed: %s", hipGetErrorString(he));
 	C.track.resize(nout); C.track_sat.resize((size_t)nu);
 	if (nout) HIPOK(hipMemcpyAsync(C.track.data(), E->track.p, nout * sizeof(uint16_t), hipMemcpyDeviceToHost, E->st));
-	HIPOK(hipMemcpyAsync(C.track_sat.data(), E->track_sat.p, (size_t)nu, hipMemcpyDeviceToHost, E->st));
+	rc = sat_end(E, E->track_sat, C.track_sat); if (rc) return rc;
 	if (npeak) { C.track_peaks.resize(npeak); HIPOK(hipMemcpyAsync(C.track_peaks.data(), E->track_peaks.p, npeak * sizeof(TrackPeak), hipMemcpyDeviceToHost, E->st)); }
 	return FASIM_OK;
 }
@@ -368,7 +367,7 @@ void TrackReq::merge(const BatchCtx& C, const SegTable&, int64_t, int64_t, int q
 			}
 		}
 	}
-	for (size_t u = 0; u < C.track_sat.size(); u++) tr.sat[(size_t)q * (size_t)tr.nrec + (size_t)C.srec[u / (size_t)C.nenc]] += C.track_sat[u];
+	sat_add(tr.sat, C.track_sat, C, q, tr.nrec);
 }
 
 // The two launches of k_sites over the batch's column maxima, into C.site_counts / C.site_runs / C.site_sat: the run counts per
@@ -385,17 +384,16 @@ int SitesReq::fold(fasim_engine* E, BatchCtx& C, int) const
 		return fail(E, FASIM_E_NOMEM, "sites: no device memory for the run counts of %zu slices", ncnt / 4);
 	}
 	HIPOK(hipMemsetAsync(E->sites_counts.p, 0, ncnt * sizeof(uint32_t), E->st));
-	HIPOK(hipMemsetAsync(E->sites_sat.p, 0, (size_t)nu, E->st));
+	rc = sat_begin(E, E->sites_sat, (size_t)nu); if (rc) return rc;
 	SitesLaunch S;
-	S.colmax16 = E->colmax16.as<uint16_t>(); S.seg_len = E->seg_len.as<int32_t>();
-	S.nseg = C.nseg; S.nenc = C.nenc; S.tstride = C.B.tstride; S.nchunk = C.track_nchunk; S.min_value = min_value; S.tab = C.tab;
-	S.counts = E->sites_counts.as<uint32_t>(); S.offsets = nullptr; S.runs = nullptr; S.sat = E->sites_sat.as<uint8_t>();
+	class_fold_fill(S, E, C, E->sites_sat);
+	S.min_value = min_value; S.counts = E->sites_counts.as<uint32_t>(); S.offsets = nullptr; S.runs = nullptr;
 	{ TimedScope ts(E, 4); he = launch_sites(S, false, E->st); }
 	if (he != hipSuccess) return fail(E, FASIM_E_HIP, "sites (count) launch failed: %s", hipGetErrorString(he));
 	std::vector<uint32_t> offs;
 	try { C.site_counts.resize(ncnt); C.site_sat.resize((size_t)nu); offs.resize(ncnt); } catch (const std::bad_alloc&) { return fail(E, FASIM_E_NOMEM, "out of memory"); }
 	HIPOK(hipMemcpyAsync(C.site_counts.data(), E->sites_counts.p, ncnt * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st));
-	HIPOK(hipMemcpyAsync(C.site_sat.data(), E->sites_sat.p, (size_t)nu, hipMemcpyDeviceToHost, E->st));
+	rc = sat_end(E, E->sites_sat, C.site_sat); if (rc) return rc;
 	HIPOK(hipStreamSynchronize(E->st));
 	uint64_t total = 0;
 	for (size_t k = 0; k < ncnt; k++) { offs[k] = (uint32_t)total; total += C.site_counts[k]; }
@@ -439,7 +437,7 @@ void SitesReq::merge(const BatchCtx& C, const SegTable&, int64_t, int64_t, int q
 			}
 		}
 	}
-	for (size_t u = 0; u < C.site_sat.size(); u++) sr.sat[(size_t)q * (size_t)sr.nrec + (size_t)C.srec[u / (size_t)C.nenc]] += C.site_sat[u];
+	sat_add(sr.sat, C.site_sat, C, q, sr.nrec);
 }
 
 // returns 1 when the query does not fit the kernel (caller falls back to the striped kernels)

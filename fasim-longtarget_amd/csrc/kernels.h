@@ -1,6 +1,7 @@
 // Host-callable launchers of the gfx950 kernels (defined in kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include <vector>
 #include "device_types.h"
 
@@ -119,15 +120,27 @@ __host__ __device__ inline int track_slice_stride(int bin) { const int nb = bin 
 // peak of one slice and class (k_track with PEAKS): the slice's maximum, its smallest position within the SEGMENT, and the smallest
 // index k (0 .. nenc) of an enabled encoding of the class whose unit attains it there; value 0: pos = k = -1
 struct TrackPeak { int32_t value, pos, k, pad; };
-struct TrackLaunch {
+// What the three column folds (k_track, k_sites, k_hist) share: their front half (class_fold.h) reads nothing else
+struct ClassFoldLaunch {
 	const uint16_t* colmax16;   // [seg * nenc + k][tstride]: 2 * column maximum + taint bit, as k_scan's main pass leaves it
 	const int32_t* seg_len;     // [nseg]
-	const int32_t* phase;       // [nseg]: record position of the segment's first base, modulo bin
-	int32_t nseg, nenc, tstride, nchunk, bin;      // bin == 0: peaks only, no slices
+	int32_t nseg, nenc, tstride, nchunk;
 	TrackTable tab;
+	uint8_t* sat;               // [nseg * nenc], zeroed by the caller: 1 = the unit holds a saturated column maximum (16 383)
+};
+// What every launcher of a column fold asks first.  true: return *rc (hipSuccess: nothing to launch; hipErrorInvalidValue: a row
+// stride that is no multiple of 8, or not 1 .. 48 encodings)
+inline bool class_fold_done(const ClassFoldLaunch& L, hipError_t* rc)
+{
+	if (L.nseg <= 0 || L.nchunk <= 0) { *rc = hipSuccess; return true; }
+	if ((L.tstride & 7) != 0 || L.nenc < 1 || L.nenc > 48) { *rc = hipErrorInvalidValue; return true; }
+	return false;
+}
+struct TrackLaunch : ClassFoldLaunch {
+	const int32_t* phase;       // [nseg]: record position of the segment's first base, modulo bin
+	int32_t bin;                // bin == 0: peaks only, no slices
 	uint16_t* out;              // [nseg * nchunk][4][track_slice_stride(bin)]
 	TrackPeak* peaks = nullptr; // [nseg * nchunk][4], or NULL: no peaks (the slices of a segment's unused chunks are not written)
-	uint8_t* sat;               // [nseg * nenc], zeroed by the caller: 1 = the unit holds a saturated column maximum (16 383)
 };
 hipError_t launch_track(const TrackLaunch& L, hipStream_t st);
 
@@ -136,15 +149,11 @@ hipError_t launch_track(const TrackLaunch& L, hipStream_t st);
 // value, the smallest position that attains it, and the smallest index k (0 .. nenc) of an enabled encoding of the class whose unit
 // attains it there.
 struct alignas(16) SiteRun { int32_t start, end, value_k /* value | k << 16 */, pos; };
-struct SitesLaunch {
-	const uint16_t* colmax16;   // as TrackLaunch
-	const int32_t* seg_len;     // [nseg]
-	int32_t nseg, nenc, tstride, nchunk, min_value;      // 1 <= min_value <= 16 383
-	TrackTable tab;
+struct SitesLaunch : ClassFoldLaunch {
+	int32_t min_value;          // 1 <= min_value <= 16 383
 	uint32_t* counts;           // [nseg * nchunk][4], zeroed by the caller: runs per slice and class (the counting launch writes it)
 	const uint32_t* offsets;    // [nseg * nchunk][4]: exclusive prefix sum of the counts (the emitting launch reads it)
 	SiteRun* runs;              // [sum of the counts], in (slice, class, position) order (the emitting launch writes it)
-	uint8_t* sat;               // [nseg * nenc], zeroed by the caller: 1 = the unit holds a saturated column maximum (16 383)
 };
 hipError_t launch_sites(const SitesLaunch& L, bool emit, hipStream_t st);
 
@@ -154,16 +163,13 @@ constexpr int HIST_LDS_BINS = 1024;        // values below this are counted in t
 // A position of a segment that a neighbouring segment of the record covers too (the head zone [0, zone[2 s]) and the tail zone
 // [zone[2 s + 1], n) of segment s) is not counted: its four values go to zones[s][head 0 / tail 1][class][zstride], slot = the
 // offset within the zone, and the host counts the maximum of the two sides once.
-struct HistLaunch {
-	const uint16_t* colmax16;   // as TrackLaunch
-	const int32_t* seg_len;     // [nseg]
+struct HistLaunch : ClassFoldLaunch {
 	const int32_t* zone;        // [nseg][2]: end of the head zone (0: none), begin of the tail zone (seg_len: none); head <= tail
-	int32_t nseg, nenc, tstride, nchunk, zstride;        // zstride >= the longest zone of the batch
-	TrackTable tab;
+	int32_t zstride;            // >= the longest zone of the batch
 	uint32_t* hist;             // [4][HIST_BINS], zeroed by the caller: the batch's counts per class and value
 	uint16_t* zones;            // [nseg][2][4][zstride] (zstride == 0: no zones, may be NULL)
-	uint8_t* sat;               // [nseg * nenc], zeroed by the caller: 1 = the unit holds a saturated column maximum (16 383)
 };
+static_assert(std::is_trivially_copyable<TrackLaunch>::value && std::is_trivially_copyable<SitesLaunch>::value && std::is_trivially_copyable<HistLaunch>::value, "kernel arguments");
 hipError_t launch_hist(const HistLaunch& L, hipStream_t st);
 
 // ---- scan_short.hip: column maxima of a short oligo ----------------------------------------------------

@@ -15,23 +15,9 @@
 //   * one 16-byte store per (group, class, lane): every output element has one writer, no global atomics.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "kernels.h"
+#include "class_fold.h"
 
 namespace fasim {
-
-typedef unsigned short r8u __attribute__((ext_vector_type(8)));
-typedef unsigned short r2u __attribute__((ext_vector_type(2)));
-typedef unsigned int r4w __attribute__((ext_vector_type(4)));
-
-// != 0 when one of the 8 raw values is a saturated row maximum (2 * 16 383 + taint)
-__device__ __forceinline__ bool rowfold_saturated(r8u v)
-{
-	const r4w w = __builtin_bit_cast(r4w, v);
-	const r2u a = __builtin_elementwise_max(__builtin_bit_cast(r2u, w[0]), __builtin_bit_cast(r2u, w[1]));
-	const r2u b = __builtin_elementwise_max(__builtin_bit_cast(r2u, w[2]), __builtin_bit_cast(r2u, w[3]));
-	const r2u m = __builtin_elementwise_max(a, b);
-	return m[0] >= 32766 || m[1] >= 32766;
-}
 
 __global__ void __launch_bounds__(256) k_rowfold(RowFoldLaunch a)
 {
@@ -39,9 +25,9 @@ __global__ void __launch_bounds__(256) k_rowfold(RowFoldLaunch a)
 	const int r0 = (blockIdx.x * 256 + threadIdx.x) * 8;          // my rows r0 .. r0 + 7 (rows_total is a multiple of 8)
 	if (r0 >= a.rows_total) return;
 	const int s0 = a.gfirst[g], s1 = a.gfirst[g + 1];
-	r8u acc[4];
+	v8u acc[4];
 #pragma unroll
-	for (int c = 0; c < 4; c++) acc[c] = (r8u)(0);
+	for (int c = 0; c < 4; c++) acc[c] = (v8u)(0);
 	for (int s = s0; s < s1; s++) {
 		const uint16_t* base = a.rowmax16 + (int64_t)s * a.nenc * a.rows_total + r0;
 		uint8_t* sat = a.sat + (int64_t)s * a.nenc;
@@ -51,16 +37,16 @@ __global__ void __launch_bounds__(256) k_rowfold(RowFoldLaunch a)
 			for (int half = 0; half < 2; half++) {
 				for (int i = a.tab.first[4 * half + c]; i < a.tab.first[4 * half + c + 1]; i++) {
 					const int k = a.tab.k[i];
-					const r8u v = *reinterpret_cast<const r8u*>(base + (int64_t)k * a.rows_total);
+					const v8u v = *reinterpret_cast<const v8u*>(base + (int64_t)k * a.rows_total);
 					acc[c] = __builtin_elementwise_max(acc[c], v);
-					if (rowfold_saturated(v)) sat[k] = 1;
+					if (fold_saturated(v)) sat[k] = 1;
 				}
 			}
 		}
 	}
 	uint16_t* out = a.out + (int64_t)g * 4 * a.rows_total + r0;
 #pragma unroll
-	for (int c = 0; c < 4; c++) *reinterpret_cast<r8u*>(out + (int64_t)c * a.rows_total) = acc[c] >> (r8u)(1);
+	for (int c = 0; c < 4; c++) *reinterpret_cast<v8u*>(out + (int64_t)c * a.rows_total) = acc[c] >> (v8u)(1);
 }
 
 hipError_t launch_rowfold(const RowFoldLaunch& L, hipStream_t st)

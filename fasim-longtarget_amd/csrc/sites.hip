@@ -6,10 +6,8 @@
 // largest value, the smallest position that attains it and the smallest encoding that attains it there.
 // The slice edge cuts runs; the host joins them again by their coordinates, as it joins the runs of overlapping segments.
 //
-//   * the front half is k_track's: one 256-thread workgroup per slice of TRACK_CHUNK = 2 040 positions, a lane owns 8
-//     consecutive positions, aligned 16-byte loads of the forward rows, the reversed rows read along their columns and mirrored
-//     once through LDS, v_pk_max_u16 on the raw values through the class table in the kernel arguments, the taint bit shifted out
-//     at the end, sat[unit] set;
+//   * the front half is the one k_track uses (class_fold.h): one 256-thread workgroup per slice of TRACK_CHUNK = 2 040 positions,
+//     a lane owns 8 consecutive positions;
 //   * a lane walks its own 8 slots only.  What a run needs from the lanes before it -- whether it is still open at the lane's
 //     first slot, where it started and the best (value << 16) | (0xffff - slot) word so far -- is a carry (open, start, key), and
 //     the carries are combined by a segmented max-scan: __shfl_up over the wave (6 steps), then the four waves' totals through
@@ -25,23 +23,9 @@
 //     for the encoding, as k_track's peak variant does.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "kernels.h"
+#include "class_fold.h"
 
 namespace fasim {
-
-typedef unsigned short v8u __attribute__((ext_vector_type(8)));
-typedef unsigned short v2us __attribute__((ext_vector_type(2)));
-typedef unsigned int v4w __attribute__((ext_vector_type(4)));
-
-// != 0 when one of the 8 raw values is a saturated column maximum (2 * 16 383 + taint)
-__device__ __forceinline__ bool sites_saturated(v8u v)
-{
-	const v4w w = __builtin_bit_cast(v4w, v);
-	const v2us a = __builtin_elementwise_max(__builtin_bit_cast(v2us, w[0]), __builtin_bit_cast(v2us, w[1]));
-	const v2us b = __builtin_elementwise_max(__builtin_bit_cast(v2us, w[2]), __builtin_bit_cast(v2us, w[3]));
-	const v2us m = __builtin_elementwise_max(a, b);
-	return m[0] >= 32766 || m[1] >= 32766;
-}
 
 // The carry of the segmented scan, for a range of slots: `key` = the best word of the flagged stretch that ends on the range's last
 // slot, `info` = its first slot | OPEN (the last slot is flagged) | FULL (every slot of the range is flagged; the empty range is FULL
@@ -59,8 +43,6 @@ __device__ __forceinline__ SitesCarry sites_join(SitesCarry l, SitesCarry r)
 	return o;
 }
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-
 // EMIT false: a.counts[slice * 4 + class] = runs of the slice; EMIT true: the runs themselves at a.offsets[slice * 4 + class]
 template <bool EMIT>
 __global__ void __launch_bounds__(256) k_sites(SitesLaunch a)
@@ -70,71 +52,14 @@ __global__ void __launch_bounds__(256) k_sites(SitesLaunch a)
 	__shared__ uint32_t wcount[4][2];                               // the four waves' run counts, classes 0|1 and 2|3 packed
 	__shared__ uint8_t first_flag[256 + 4];                         // per lane: bit c = the lane's first slot is flagged in class c
 	const int chunk = blockIdx.x, seg = blockIdx.y, t = threadIdx.x;
-	const int n = a.seg_len[seg];
-	const int P0 = chunk * TRACK_CHUNK;
-	if (P0 >= n) return;                                            // (uniform: the whole workgroup; the caller zeroed the counts)
-	const int P1 = min(n, P0 + TRACK_CHUNK);
-	const uint16_t* base = a.colmax16 + (int64_t)seg * a.nenc * a.tstride;
-	uint8_t* sat = a.sat + (int64_t)seg * a.nenc;
-
-	// forward rows: positions p0 .. p0 + 7 (p0 + 7 < tstride: P0 and tstride are multiples of 8 and p0 < n <= tstride)
-	const int p0 = P0 + 8 * t;
-	const bool fwd_on = p0 < P1;
-	// reversed rows: columns jg .. jg + 7 of the aligned groups that cover [n - P1, n - P0) (jg + 7 < tstride as above)
-	const int jlo = n - P1, jhi = n - P0;
-	const int jg = (jlo & ~7) + 8 * t;
-	const bool rev_on = jg < jhi;
-	// columns from n on hold whatever an earlier batch left there; reversed columns outside the slice belong to its neighbours
-	v8u fmask, rmask;
-#pragma unroll
-	for (int e = 0; e < 8; e++) {
-		fmask[e] = (p0 + e < P1) ? 0xffff : 0;
-		rmask[e] = (jg + e >= jlo && jg + e < jhi) ? 0xffff : 0;
-	}
-	v8u facc[4], racc[4];
-#pragma unroll
-	for (int c = 0; c < 4; c++) {
-		facc[c] = (v8u)(0); racc[c] = (v8u)(0);
-		if (fwd_on) {
-			for (int i = a.tab.first[c]; i < a.tab.first[c + 1]; i++) {
-				const int k = a.tab.k[i];
-				const v8u v = *reinterpret_cast<const v8u*>(base + (int64_t)k * a.tstride + p0) & fmask;
-				facc[c] = __builtin_elementwise_max(facc[c], v);
-				if (sites_saturated(v)) sat[k] = 1;
-			}
-		}
-		if (rev_on) {
-			for (int i = a.tab.first[4 + c]; i < a.tab.first[5 + c]; i++) {
-				const int k = a.tab.k[i];
-				const v8u v = *reinterpret_cast<const v8u*>(base + (int64_t)k * a.tstride + jg) & rmask;
-				racc[c] = __builtin_elementwise_max(racc[c], v);
-				if (sites_saturated(v)) sat[k] = 1;
-			}
-		}
-	}
-	// mirror the reversed maxima: column j is position n - 1 - j, slot n - 1 - j - P0 of the slice (every slot of [0, P1 - P0) is
-	// written: its column lies in [jlo, jhi))
-	if (rev_on) {
-#pragma unroll
-		for (int e = 0; e < 8; e++) {
-			const int j = jg + e;
-			if (j >= jlo && j < jhi) {
-				const int slot = n - 1 - j - P0;
-#pragma unroll
-				for (int c = 0; c < 4; c++) rev[c][slot] = racc[c][e];
-			}
-		}
-	}
+	ClassFold f(a);
+	if (f.P0 >= f.n) return;                                        // (uniform: the whole workgroup; the caller zeroed the counts)
+	const int P0 = f.P0;
+	f.load(a, rev);
 	__syncthreads();
 	v8u val[4];
 #pragma unroll
-	for (int c = 0; c < 4; c++) {
-		val[c] = (v8u)(0);
-		if (fwd_on) {
-			const v8u r = *reinterpret_cast<const v8u*>(&rev[c][8 * t]) & fmask;      // (slots from P1 - P0 on were never written)
-			val[c] = __builtin_elementwise_max(facc[c], r) >> (v8u)(1);
-		}
-	}
+	for (int c = 0; c < 4; c++) val[c] = f.value(rev, c);
 
 	// ---- the lane's own slots: flags (bit e = slot 8 t + e reaches min_value; slots past the slice hold 0 < min_value), the
 	//      carry of its 8 slots and the number of runs that end in them
@@ -235,19 +160,10 @@ __global__ void __launch_bounds__(256) k_sites(SitesLaunch a)
 				if (!open) { open = true; start = (uint32_t)(8 * t + e); key = 0; }
 				key = max(key, ((uint32_t)val[c][e] << 16) | (uint32_t)(0xffff - (8 * t + e)));
 				if (!((ends[c] >> e) & 1)) continue;
-				// the run [start, 8 t + e] of the slice: its peak column again, row by row: forward rows at the position, reversed
-				// rows at its mirror image (pos < P1 <= n <= tstride)
+				// the run [start, 8 t + e] of the slice
 				const int value = (int)(key >> 16);
 				const int pos = P0 + (int)(0xffff - (key & 0xffff));
-				int enc = 0x7fffffff;
-				for (int i = a.tab.first[c]; i < a.tab.first[c + 1]; i++) {
-					const int r = a.tab.k[i];
-					if ((int)(base[(int64_t)r * a.tstride + pos] >> 1) == value) enc = min(enc, r);
-				}
-				for (int i = a.tab.first[4 + c]; i < a.tab.first[5 + c]; i++) {
-					const int r = a.tab.k[i];
-					if ((int)(base[(int64_t)r * a.tstride + (n - 1 - pos)] >> 1) == value) enc = min(enc, r);
-				}
+				const int enc = class_peak_encoding(a.tab, f.base, a.tstride, f.n, c, pos, value);
 				const v4i rec = { P0 + (int)start, P0 + 8 * t + e + 1, value | (enc << 16), pos };
 				*reinterpret_cast<v4i*>(a.runs + at) = rec;
 				at++;
@@ -258,8 +174,9 @@ __global__ void __launch_bounds__(256) k_sites(SitesLaunch a)
 
 hipError_t launch_sites(const SitesLaunch& L, bool emit, hipStream_t st)
 {
-	if (L.nseg <= 0 || L.nchunk <= 0) return hipSuccess;
-	if ((L.tstride & 7) != 0 || L.nenc < 1 || L.nenc > 48 || L.min_value < 1 || L.min_value > 16383) return hipErrorInvalidValue;
+	hipError_t rc;
+	if (class_fold_done(L, &rc)) return rc;
+	if (L.min_value < 1 || L.min_value > 16383) return hipErrorInvalidValue;
 	if (emit ? (!L.offsets || !L.runs) : !L.counts) return hipErrorInvalidValue;
 	const dim3 grid((unsigned)L.nchunk, (unsigned)L.nseg);
 	if (emit) hipLaunchKernelGGL((k_sites<true>), grid, dim3(256), 0, st, L);
