@@ -137,6 +137,7 @@ struct fasim_engine {
 	DevBuf sites_counts, sites_offsets, sites_runs, sites_sat;   // fasim_scan_records_sites only: k_sites' run counts per (slice, class), their prefix sum, the runs and saturation flags of the batch
 	DevBuf sa_q, sa_tcodes, sa_probs, sa_ends, sa_rows, sa_items, sa_dirs, sa_cigar, sa_ciglen;   // fasim_scan_records_sites_aligned only: query codes, the chunk's units, problems, end cells, row state of long queries, path items, direction bytes, CIGARs
 	DevBuf hist, hist_zone, hist_zones, hist_sat;   // fasim_scan_records_hist only: k_hist's counters of the batch, its zone bounds per segment, the zone values and saturation flags
+	int opt_sim_lds = -1;                        // option "sim_lds": -F re-sweeps always on the L2 variant (0) / the LDS variant where the state fits (1); -1 = by the units in flight
 	int opt_site_short = -1;                     // option "site_short": 1 = the hits of oligo sites end on k_site_ends_short (default), 0 = on k_site_ends (-1 = default / environment FASIM_SITE_SHORT)
 	int opt_site_chunk = 0;                      // option "site_chunk": problems per chunk of the hits phase where lower than the phase's own limit (0 = that limit)
 	DevBuf oligo_q;                              // fasim_scan_oligos only: the panel's query codes, FASIM_MAX_OLIGO bytes per oligo
@@ -614,7 +615,7 @@ int check_track_source(fasim_engine* E, const int32_t* rna_lens, int32_t nq, con
 int sim_forward_units(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, const int32_t* unit_len_dev, const int32_t* unit_len_host,
 	int first, int nunit, const int64_t* mins, std::atomic<int>* ready, std::vector<std::vector<fasim_sim_node>>& lists);
 int sim_resweep_rounds(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, const int32_t* unit_len_dev, const int32_t* unit_len_host,
-	int first, int cnt, SimUnit* const* units, int nthreads);
+	int first, int cnt, SimUnit* const* units, int nthreads, fasim_scan_stats* st);
 int pack_result(fasim_engine* E, std::vector<HostTriplex>& all, const fasim_scan_stats& st, fasim_result** out);
 int scan_core(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int nq, const char* dna, int64_t dna_len,
 	int64_t seg_first, int64_t seg_count, const fasim_params* pp, fasim_result** outs, const ScanProducts& products = {});

@@ -86,7 +86,7 @@ template <typename F> static void parallel_units(int n, int nthreads, F&& fn)
 // column / row and the used pairs; the node lists travel both ways each round (3.6 KB per unit).
 // FASIM_SIM_RESWEEP=host keeps the re-sweeps on the host threads (A/B); =check runs both and compares every round.
 int sim_resweep_rounds(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, const int32_t* unit_len_dev, const int32_t* unit_len_host,
-	int first, int cnt, SimUnit* const* units, int nthreads)
+	int first, int cnt, SimUnit* const* units, int nthreads, fasim_scan_stats* st)
 {
 	if (cnt <= 0) return FASIM_OK;
 	const char* mode_env = getenv("FASIM_SIM_RESWEEP");      // read per call: the tests switch it
@@ -126,6 +126,7 @@ int sim_resweep_rounds(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, 
 	std::vector<SimRoundReq> rq;
 	std::vector<SimRoundOut> ho;
 	std::vector<char> pend((size_t)slice);
+	std::vector<char> pend_lds((size_t)slice);               // the variant that suspended a pending unit (1 = LDS, 0 = L2)
 	// A unit's share of a launch: a time slice (50 ms while more than 1 024 units are active, 60 ms for the tail; the kernel reads
 	// the clock every eighth line), or a number of 64-cell steps when FASIM_SIM_BUDGET is set (tests).  A unit that needs more (a
 	// re-sweep of most of the matrix) carries on in the next launch: the average round of H19 x 5 kb takes 10 k steps, the heaviest
@@ -206,8 +207,14 @@ int sim_resweep_rounds(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, 
 			a.state = E->sim_state.as<SimSweepState>(); a.budget = budget_env ? budget_env : (1 << 20); a.slice_ticks = budget_env ? ((int64_t)1 << 40) : (int64_t)(everywhere > 1024 ? 50 : 60) * wall_khz; a.debug = debug ? E->sim_debug.as<uint64_t>() : nullptr;
 			const double tl0 = now_s();
 			hipError_t he;
-			{ TimedScope ts(E, 7); he = launch_sim_resweep(a, active, everywhere <= 256 /* one unit per CU: all at once */, E->st); }
+			const bool few_units = E->opt_sim_lds >= 0 ? E->opt_sim_lds != 0 : everywhere <= 256 /* one unit per CU: all at once */;
+			const bool in_lds = sim_resweep_in_lds(a, few_units);
+			{ TimedScope ts(E, 7); he = launch_sim_resweep(a, active, few_units, E->st); }
 			if (he != hipSuccess) return fail(E, FASIM_E_HIP, "sim_resweep launch failed: %s", hipGetErrorString(he));
+			if (st) {
+				(in_lds ? st->sim_resweep_lds : st->sim_resweep_l2)++;
+				for (int s = 0; s < active; s++) st->sim_handover += rq[(size_t)s].active == 2 && (pend_lds[(size_t)act[(size_t)s]] != 0) != in_lds;
+			}
 			ho.resize((size_t)active);
 			HIPOK(hipMemcpyAsync(ho.data(), E->sim_out.p, sizeof(SimRoundOut) * active, hipMemcpyDeviceToHost, E->st));
 			HIPOK(hipMemcpyAsync(hn, E->sim_nodes_out.p, sizeof(fasim_sim_node) * (size_t)active * FASIM_SIM_K, hipMemcpyDeviceToHost, E->st));
@@ -216,8 +223,10 @@ int sim_resweep_rounds(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, 
 			for (int s = 0; s < active; s++) {
 				if (ho[(size_t)s].node_count < 0 || ho[(size_t)s].node_count > FASIM_SIM_K) return fail(E, FASIM_E_HIP, "sim_resweep: bad node count");
 				pend[(size_t)act[(size_t)s]] = ho[(size_t)s].pending != 0;
+				pend_lds[(size_t)act[(size_t)s]] = in_lds;
 				suspended += ho[(size_t)s].pending != 0;
 			}
+			if (st) st->sim_suspended += suspended;
 			if (debug) fprintf(stderr, "[fasim sim] launch %ld: %d active, %d suspended, %.1f ms\n", launches, active, suspended, 1e3 * (now_s() - tl0));
 			if (mode == 2) {
 				std::atomic<int> bad(-1);
@@ -451,7 +460,7 @@ int scan_batch(fasim_engine* E, const char* dna, const SegTable& T, const uint8_
 			});
 			std::vector<SimUnit*> up((size_t)B.nunit);
 			for (int u = 0; u < B.nunit; u++) up[(size_t)u] = units[(size_t)u].get();
-			rc = sim_resweep_rounds(E, E->tcodes.as<uint8_t>(), tstride, E->unit_len.as<int32_t>(), B.unit_len.data(), 0, B.nunit, up.data(), E->sim_threads);
+			rc = sim_resweep_rounds(E, E->tcodes.as<uint8_t>(), tstride, E->unit_len.as<int32_t>(), B.unit_len.data(), 0, B.nunit, up.data(), E->sim_threads, &st);
 			if (rc) return rc;
 			for (int u = 0; u < B.nunit; u++) {
 				const int s = u / nenc, enc = encs[(size_t)(u % nenc)];
@@ -597,6 +606,7 @@ static void add_stats(fasim_scan_stats& st, const fasim_scan_stats& x)
 	st.band_tries += x.band_tries; st.band_proven += x.band_proven; st.band_cells += x.band_cells; st.rev_bound_passes += x.rev_bound_passes;
 	st.striped_window_probs += x.striped_window_probs; st.striped_window_ms += x.striped_window_ms;
 	st.dp_f16_reruns += x.dp_f16_reruns;
+	st.sim_resweep_lds += x.sim_resweep_lds; st.sim_resweep_l2 += x.sim_resweep_l2; st.sim_suspended += x.sim_suspended; st.sim_handover += x.sim_handover;
 	for (int k = 0; k < FASIM_KERNEL_FAMILIES; k++) { st.kernel_ms[k] += x.kernel_ms[k]; st.kernel_launches[k] += x.kernel_launches[k]; }
 }
 
@@ -765,7 +775,7 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 		for (fasim_engine* w : ws) {
 			w->gate = (ws.size() > 1 && E->own_gate.cap > 0) ? &E->own_gate : nullptr;
 			w->scan_v1 = E->scan_v1; w->align_v1 = E->align_v1; w->striped_window = E->striped_window;
-			w->hz_chunks = E->hz_chunks; w->hz_snap = E->hz_snap; w->hz_target = E->hz_target; w->hz_hot_w = E->hz_hot_w; w->opt_band = E->opt_band; w->opt_dp_f16 = E->opt_dp_f16;
+			w->hz_chunks = E->hz_chunks; w->hz_snap = E->hz_snap; w->hz_target = E->hz_target; w->hz_hot_w = E->hz_hot_w; w->opt_band = E->opt_band; w->opt_dp_f16 = E->opt_dp_f16; w->opt_sim_lds = E->opt_sim_lds;
 			w->host_threads = std::max(1, E->host_threads_total / nworkers);
 			w->host_threads_share_total = E->host_threads_total; w->active_workers = &active_workers; w->sim_in_flight = &sim_active; w->scan_workers = (int)ws.size();
 			{

@@ -297,5 +297,6 @@ hipError_t launch_align_band(const BandLaunch& L, hipStream_t st);
 // ---- sim.hip: forward sweep of classic SIM (-F), one wave per unit ---------------------------------------
 hipError_t launch_sim_forward(const SimFwdArgs& a, int32_t nunit, hipStream_t st);
 hipError_t launch_sim_resweep(const SimResweepArgs& a, int32_t nunit, bool few_units, hipStream_t st);
+bool sim_resweep_in_lds(const SimResweepArgs& a, bool few_units);      // the variant that launch takes: k_sim_resweep<true> (lines' states in LDS) or <false>
 
 } // namespace fasim

@@ -647,14 +647,17 @@ hipError_t launch_sim_forward(const SimFwdArgs& a, int32_t nunit, hipStream_t st
 	return hipGetLastError();
 }
 
+// the lines' states of one unit: 16 B per target column and per query row; in LDS when that fits one CU's 160 KB (minus a margin)
+static size_t sim_resweep_lds_bytes(const SimResweepArgs& a) { return (size_t)(2 * a.col_stride + 2 * a.row_stride) * sizeof(uint64_t); }
+bool sim_resweep_in_lds(const SimResweepArgs& a, bool few_units) { return few_units && sim_resweep_lds_bytes(a) <= 150 * 1024; }
+
 hipError_t launch_sim_resweep(const SimResweepArgs& a, int32_t nunit, bool few_units, hipStream_t st)
 {
 	if (nunit <= 0) return hipSuccess;
-	// the lines' states of one unit: 16 B per target column and per query row; in LDS when that fits one CU's 160 KB (minus a margin)
-	const size_t lds = (size_t)(2 * a.col_stride + 2 * a.row_stride) * sizeof(uint64_t);
+	const size_t lds = sim_resweep_lds_bytes(a);
 	// LDS variant: one unit per CU at a time, each 3-5 x faster -- for the launches in which few units are left (the tail of the
 	// heaviest units); with thousands of units active the 4-units-per-workgroup variant keeps every wave slot of the chip busy
-	if (few_units && lds <= 150 * 1024) {
+	if (sim_resweep_in_lds(a, few_units)) {
 		static bool attr_set = false;
 		if (!attr_set) { (void)hipFuncSetAttribute((const void*)k_sim_resweep<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); attr_set = true; }
 		hipLaunchKernelGGL(k_sim_resweep<true>, dim3((unsigned)nunit), dim3(64), lds, st, a, nunit);

@@ -94,6 +94,9 @@ const char* fasim_last_error(const fasim_engine* e);   /* e may be NULL: last gl
  * the GPU's NUMA node (/sys/bus/pci/devices/<bus id>/local_cpulist); the caller's affinity is restored afterwards; no effect on a
  * single-node machine.
  * key "band" (1): the banded forward pass of stage 3 (csrc/band.hip); 0 = every window try runs over the whole query (env FASIM_BAND).
+ * key "sim_lds" (-1): which storage variant of k_sim_resweep the -F rounds launch.  -1 = by the units in flight (the LDS variant
+ * once at most 256 are left over all workers); 0 = always the variant that keeps the lines' states in L2; 1 = always the LDS variant
+ * (the kernel still takes the L2 variant when the states of a unit exceed 150 KB).  No environment variable (for tests).
  * Results do not depend on any of them. */
 int fasim_set_option(fasim_engine* e, const char* key, int32_t value);
 
@@ -213,6 +216,10 @@ typedef struct fasim_scan_stats {
 	/* alignments of the scan's finish (run_finish) by the storage tier that answered them: k_finish_lds with 16 KB and with
 	 * 64 KB of LDS, k_finish with 16 KB and with 1 MB of global scratch per alignment */
 	int64_t finish_lds16, finish_lds64, finish_glob16k, finish_glob1m;
+	/* -F: launches of k_sim_resweep by storage variant (lines' states in LDS / in L2); unit-launches that came back suspended (budget
+	 * or time slice spent before the re-sweep ended); suspended units that were resumed by the other variant than the one that
+	 * suspended them */
+	int64_t sim_resweep_lds, sim_resweep_l2, sim_suspended, sim_handover;
 } fasim_scan_stats;
 
 struct fasim_result {

@@ -1104,3 +1104,206 @@ def finish_tier_planted_records(units, plants):
                     hit.append(p)
                     break
     return hit
+
+
+# ---- classic SIM (-F) at strip, chunk and node-list edges (test_sim_edges_cpu.py, test_gpu_sim_edges.py) ------------------------
+# Triplex targets are purine tracts: repeats and homopolymers give many cells of one score and many nodes tied for the lowest score,
+# which is where addnode()'s "first node of lowest score gives way" and the prefix maxima of the re-sweeps can go wrong unnoticed.
+SIM_K = 50
+SIM_EDGE_HEADER = "syn|chrE|1-%d"
+
+
+def _sim_edge_stretches(n, rng):
+    """n letters in stretches of 8 ... 40 nt: random ACGT, a GA repeat, a homopolymer or a TC repeat (either phase)"""
+    out = bytearray()
+    while len(out) < n:
+        ln, kind = 8 + rng.below(33), rng.below(4)
+        if kind == 0:
+            out += bytes(b"ACGT"[rng.below(4)] for _ in range(ln))
+        elif kind == 2:
+            out += bytes([b"AGTC"[rng.below(4)]]) * ln
+        else:
+            ph = rng.below(2)
+            out += ((b"GA" if kind == 1 else b"TC") * 21)[ph:ph + ln]
+    return out[:n]
+
+
+def sim_edge_query(m, seed):
+    """A query of m rows, upper-case ACGT, in stretches of random letters, GA repeats, homopolymers and TC repeats."""
+    import synth
+    return bytes(_sim_edge_stretches(m, synth._Rng(seed * 2654435761 + 11)))
+
+
+def sim_edge_dna(n, seed):
+    """DNA of n letters built like sim_edge_query, with an N every 40 ... 99 letters (none in a record shorter than that)."""
+    import synth
+    rng = synth._Rng(seed * 40503 + 29)
+    dna = _sim_edge_stretches(n, rng)
+    i = 40 + rng.below(60)
+    while i < n:
+        dna[i] = ord("N")
+        i += 40 + rng.below(60)
+    return bytes(dna)
+
+
+# -- (a) the forward sweep called directly: queries x targets x compositions x thresholds
+SIM_FWD_M = (1, 2, 63, 64, 65, 127, 128, 129, 200)          # zero, one or two full strips of 64 rows, last_lane 0 and 63
+SIM_FWD_N = (1, 2, 63, 64, 65, 127, 128, 129, 257)          # shorter than a 64-column prefetch chunk, and ending at 64 k +- 1
+SIM_FWD_COMPOSITIONS = ("random", "AG", "homopolymer", "GA/AG", "withN")
+SIM_FWD_THRESHOLDS = ("0", "50", "140", "near-best", "100000")
+SIM_FWD_BATCHES = (1, 5, 7)                                 # targets per call, in turn: not multiples of the 4 units of a workgroup
+
+
+def sim_forward_inputs(comp, m):
+    """(query of m rows, one target per length of SIM_FWD_N) of a composition.  The targets are what k_sim_forward compares with the
+    query letter by letter (no rule encoding in between)."""
+    import synth
+    k = SIM_FWD_COMPOSITIONS.index(comp)
+    seed = 7000 + 100 * k + m
+
+    def two_letter(n, s, ab):
+        return bytes(ab[c in b"AC"] for c in synth.random_dna(n, s))
+
+    if comp == "random":
+        return synth.random_rna(m, seed), [synth.random_dna(n, seed + 1000 + n) for n in SIM_FWD_N]
+    if comp == "AG":
+        return two_letter(m, seed, b"AG"), [two_letter(n, seed + 1000 + n, b"AG") for n in SIM_FWD_N]
+    if comp == "homopolymer":
+        return b"A" * m, [b"A" * n for n in SIM_FWD_N]
+    if comp == "GA/AG":
+        return (b"GA" * m)[:m], [(b"AG" * n)[:n] for n in SIM_FWD_N]
+    return sim_edge_query(m, seed), [sim_edge_dna(n, seed + n) for n in SIM_FWD_N]
+
+
+def sim_forward_problems(orc, comp, m):
+    """(query, [(target, threshold name, min_score)]) of one query: every target at every threshold of SIM_FWD_THRESHOLDS, the
+    lengths in turn, so that a batch holds targets of different lengths.  `near-best` is 60 below the best x10 score of the pair (the
+    largest node score at threshold 0; the best node never gives way, being the lowest only when all 50 are equal): the cells within
+    one match of the best, a handful."""
+    q, targets = sim_forward_inputs(comp, m)
+    out = []
+    for name in SIM_FWD_THRESHOLDS:
+        for t in targets:
+            if name == "near-best":
+                best = max([x[0] for x in orc.sim_forward_nodes(q, t, 0)], default=0)
+                thr = max(0, best - 60)
+            else:
+                thr = int(name)
+            out.append((t, name, thr))
+    return q, out
+
+
+def sim_forward_batches(problems):
+    """the problems of one query cut into calls of 1, 5, 7, 1, 5, 7 ... targets"""
+    out, i, k = [], 0, 0
+    while i < len(problems):
+        n = SIM_FWD_BATCHES[k % len(SIM_FWD_BATCHES)]
+        out.append(problems[i:i + n])
+        i, k = i + n, k + 1
+    return out
+
+
+def sim_list_state(nodes):
+    return "empty" if not nodes else "full" if len(nodes) == SIM_K else "partial"
+
+
+def sim_tied_lowest(nodes):
+    """nodes of a FULL list that share its lowest score (1: no tie); 0 for a list that is not full"""
+    if len(nodes) < SIM_K:
+        return 0
+    low = min(x[0] for x in nodes)
+    return sum(x[0] == low for x in nodes)
+
+
+def sim_row_events_at_least(q, t):
+    """A lower bound of the largest number of cells of one row above a threshold below 50: a cell whose letters match scores 50 or more."""
+    return max(sum(c == a and c in b"ACGT" for c in t) for a in set(q))
+
+
+# -- (b) ... (e) whole scans.  A numbered table of named cases: id -> (query rows, query seed, record lengths, first record seed)
+SIM_SCAN_M = (63, 64, 65, 128, 129, 200)
+SIM_SCAN_N = (63, 65, 129, 300)
+SIM_EDGE_CASES = {}
+for _i, _m in enumerate(SIM_SCAN_M):
+    for _j, _n in enumerate(SIM_SCAN_N):
+        SIM_EDGE_CASES[f"b{4 * _i + _j:02d}-m{_m}-n{_n}"] = (_m, 300 + _m, (_n,), 500 + 10 * _m + _n)
+SIM_EDGE_CASES["b09-m65-n65"] = (65, 365, (65,), 1217)        # (the record of seed 1215 leaves nothing above the tail filter)
+SIM_SUSPEND_CASES =("b00-m63-n63", "b05-m64-n65", "b10-m65-n129", "b12-m128-n63")          # (c)
+SIM_EDGE_CASES["d-m64-8rec"] = (64, 364, (63, 300, 97, 211, 65, 158, 129, 263), 900)       # (d) 8 records x 48 units in one batch
+# (e) lists that stay partial; the seeds are ones whose record is not a single repeated letter (such a segment is skipped)
+for _k, (_m, _n, _s) in enumerate(((20, 6, 907), (20, 10, 915), (20, 16, 919), (65, 6, 1357), (65, 10, 1362))):
+    SIM_EDGE_CASES[f"e{_k}-m{_m}-n{_n}"] = (_m, 300 + _m, (_n,), _s)
+SIM_PARTIAL_CASES = tuple(k for k in SIM_EDGE_CASES if k.startswith("e"))
+
+
+def sim_edge_case(name):
+    """(query, [record, ...]) of a case of SIM_EDGE_CASES"""
+    m, qseed, lens, dseed = SIM_EDGE_CASES[name]
+    return sim_edge_query(m, qseed), [sim_edge_dna(n, dseed + r) for r, n in enumerate(lens)]
+
+
+def simscan_units(text):
+    """`simscan` lines -> per unit, in file order, {'seg', 'enc', 'n', 'thr', 'x': the 13-field X tuples as scan() gives them}"""
+    units = []
+    for line in text.decode().splitlines():
+        f = line.split(" ")
+        if f[0] == "V":
+            units.append({"seg": int(f[1]), "enc": int(f[2]), "n": int(f[7]), "thr": int(f[9]), "x": []})
+        elif f[0] == "X":
+            units[-1]["x"].append((int(f[1]), int(f[2]), int(f[3]), int(f[4]), int(f[5]), int(f[6]), int(f[7]), int(f[8]), int(f[9]),
+                                   int(f[10], 16), int(f[11], 16), f[12].encode(), f[13].encode()))
+    return units
+
+
+def simscan_triplexes(text, c_length, min_identity=60.0, min_stability=1.0):
+    """X lines of `simscan` with LongTarget()'s tail filter (Fasim-LongTarget.cpp:589-597; SIM() itself only filters on nt), as
+    scan() tuples"""
+    import struct
+    out = []
+    for u in simscan_units(text):
+        for x in u["x"]:
+            ident = struct.unpack("<f", struct.pack("<I", x[9]))[0]
+            tri = struct.unpack("<f", struct.pack("<I", x[10]))[0]
+            if float(x[8]) >= 0.0 and ident >= min_identity and tri >= min_stability and x[7] >= c_length:
+                out.append(x + (u["seg"], u["enc"]))
+    return out
+
+
+_SIM_EDGE_SIMSCAN = {}
+
+
+def sim_edge_simscan(build_dir, tmp_dir, q, dna, c_length=10):
+    """the oracle's `simscan -lg c_length` of one record (made once per query and record, and left unchanged)"""
+    import synth
+    key = (q, dna, c_length)
+    if key not in _SIM_EDGE_SIMSCAN:
+        rna_fa, dna_fa = os.path.join(str(tmp_dir), "simq.fa"), os.path.join(str(tmp_dir), "simd.fa")
+        synth.write_fasta(rna_fa, "simq", q)
+        synth.write_fasta(dna_fa, SIM_EDGE_HEADER % len(dna), dna)
+        _SIM_EDGE_SIMSCAN[key] = oracle_cli(build_dir, "simscan", rna_fa, dna_fa, "-lg", str(c_length), "-threads", "8")
+    return _SIM_EDGE_SIMSCAN[key]
+
+
+def sim_edge_census(orc, build_dir, tmp_dir, name, c_length=10):
+    """Per record of a case: the units' forward-sweep lists by state, the X records of the oracle and those left by the tail filter.
+    [{'units', 'empty', 'partial', 'full', 'two_nodes', 'tied': full lists with two or more nodes of the lowest score, 'sweeps': units
+    whose first round ends in a re-sweep, 'partial_sweeps': those of them with a partial list, 'x', 'kept'}]"""
+    q, recs = sim_edge_case(name)
+    rows = []
+    for dna in recs:
+        text = sim_edge_simscan(build_dir, tmp_dir, q, dna, c_length)
+        units = simscan_units(text)
+        row = {"units": len(units), "empty": 0, "partial": 0, "full": 0, "two_nodes": 0, "tied": 0, "sweeps": 0, "partial_sweeps": 0,
+               "x": sum(len(u["x"]) for u in units), "kept": len(simscan_triplexes(text, c_length))}
+        for u in units:
+            t, _ = orc.encode_unit(dna, u["enc"])
+            nodes = orc.sim_forward_nodes(q, t, u["thr"])
+            row[sim_list_state(nodes)] += 1
+            row["two_nodes"] += len(nodes) >= 2
+            row["tied"] += sim_tied_lowest(nodes) >= 2
+            # the first round ends in a re-sweep when its node passes the threshold and is not the only one (sim.h:594, 884)
+            sweeps = len(nodes) >= 2 and max(x[0] for x in nodes) / 10.0 > u["thr"]
+            row["sweeps"] += sweeps
+            row["partial_sweeps"] += sweeps and len(nodes) < SIM_K
+        rows.append(row)
+    return rows
