@@ -2,8 +2,8 @@
 //
 //   k_build_stream  concatenates the target codes of all windows of a round into one column stream
 //                   [void, void, c0 .. cL-1(last)] per window
-//   k_align_fwd     forward pass of ssw_align (sswNew.cpp:1470-1495) as the same systolic wave pipeline as
-//                   scan.hip, fed by the window stream WITHOUT draining between windows: two "void" columns
+//   k_align_fwd     forward pass of ssw_align (sswNew.cpp:1470-1495) on the systolic wave pipeline of systolic.h, as
+//                   k_scan, fed by the window stream WITHOUT draining between windows: two "void" columns
 //                   (score -inf, gap registers = 0xFFFF so that the saturating subtractions clear E and F)
 //                   reset the DP state in flight.  DP values are kept scaled by 32 so that the low 5 bits of
 //                   every H can carry (31 - row-in-lane): one v_pk_max then yields, per column, the maximum
@@ -25,51 +25,12 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "kernels.h"
-#include "dp_f16.h"
+#include "systolic.h"
 
 namespace fasim {
 
-typedef short v2s __attribute__((ext_vector_type(2)));
-typedef unsigned short v2u __attribute__((ext_vector_type(2)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ v2s a_s(v2u x) { return __builtin_bit_cast(v2s, x); }
-__device__ __forceinline__ v2u a_u(v2s x) { return __builtin_bit_cast(v2u, x); }
-__device__ __forceinline__ int a_i(v2s x) { return __builtin_bit_cast(int, x); }
-__device__ __forceinline__ int a_i(v2u x) { return __builtin_bit_cast(int, x); }
-__device__ __forceinline__ v2u u_from(int x) { return __builtin_bit_cast(v2u, x); }
-__device__ __forceinline__ v2s s_fromi(int x) { return __builtin_bit_cast(v2s, x); }
-
-// packed 16-bit helpers as inline asm for the (rare) hazard branch: keeps the compiler from rewriting them into
-// per-half compares/selects and from hoisting them into every step (see scan.hip)
-__device__ __forceinline__ v2u apk_subs(v2u a, v2u b) { v2u r; asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ v2u apk_subs_k(v2u a, uint32_t k) { v2u r; asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "s"(k)); return r; }
-__device__ __forceinline__ v2u apk_ksubs(uint32_t k, v2u a) { v2u r; asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(r) : "s"(k), "v"(a)); return r; }
-__device__ __forceinline__ v2u apk_minu(v2u a, v2u b) { v2u r; asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ v2u apk_minu_k(v2u a, uint32_t k) { v2u r; asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "s"(k)); return r; }
-__device__ __forceinline__ v2u apk_maxu(v2u a, v2u b) { v2u r; asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-
-// x |= bits with input and output tied to one register (see scan.hip)
-__device__ __forceinline__ void a_or_in_place(int& x, int bits) { asm volatile("v_or_b32 %0, %0, %1" : "+v"(x) : "v"(bits)); }
-// the pipeline shift with zeros entering virtual lane 0 (no register to preload)
-__device__ __forceinline__ int vshift2_zero(int x)
-{
-	const int up = __builtin_amdgcn_mov_dpp(x, 0x138 /* wave_shr:1 */, 0xf, 0xf, true);
-	return __builtin_amdgcn_alignbit(x, up, 16);
-}
-
-__device__ __forceinline__ int vshift2(int x, int inject_hi)
-{
-	const int up = __builtin_amdgcn_update_dpp(inject_hi, x, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-	return __builtin_amdgcn_alignbit(x, up, 16);
-}
-
-constexpr int AL_RS = 24;
-constexpr int AL_LANE_STRIDE = 112;
-constexpr int AL_CODE_STRIDE = 64 * AL_LANE_STRIDE;
 constexpr int AL_SCALE = 32;                 // DP values are multiples of 32
 constexpr int AL_NEG = -32768;               // void / dead score: H <= 31360 so H + AL_NEG < 0 always
-constexpr int AL_NEG_F16 = -4096;            // the same for the f16 reverse pass (values x 1, H <= 1000)
 constexpr int CODE_VOID = 4;                 // stream codes: A0 C1 G2 T3, 4 = void column (between windows), 5 = N
 constexpr int CODE_SN = 5;                   // (the unit codes of kernels.h use 4 for N: k_build_stream re-codes)
 constexpr int TAG_LAST = 8;                  // bit 3 of a stream byte: last column of a window
@@ -120,7 +81,7 @@ struct FwdArgs {
 	const uint8_t* qcodes;
 	int32_t m, m_pad, seg_len16;
 	FwdOut* out;
-	int32_t vs, tile, ntiles;      // query tiling as in scan.hip
+	int32_t vs, tile, ntiles;      // query tiling as in k_scan
 	uint4* boundary;               // [stream position]: {hbot | fbot<<16, fpo | hazard<<16, key, 0} between tiles
 	// reverse pass (plain variant only; lane_ub != NULL): the query is staged reversed and the stream holds reversed windows, so H
 	// of a cell = the best alignment that STARTS there.  Per window and zone z = 0..3 the maximum of every virtual lane over the
@@ -128,18 +89,11 @@ struct FwdArgs {
 	uint16_t* lane_ub; const int32_t* ub_slot; int32_t nv;
 };
 
-__device__ __forceinline__ void lane_rows_a(int v, int seg_len, int vs, int* row0, int* rows)
-{
-	const int s = v / vs, j = v - s * vs, q = seg_len / vs, rem = seg_len - q * vs;
-	*rows = q + (j < rem ? 1 : 0);
-	*row0 = s * seg_len + j * q + (j < rem ? j : rem);
-}
-
 // score of stream code t (0..3 bases, 4 void, 5 N) against the r-th row of global virtual lane v, scaled by sc
 __device__ __forceinline__ int fwd_cell_score(const FwdArgs& a, int t, int v, int r, int sc)
 {
 	int row0v, rows_v;
-	lane_rows_a(v, a.seg_len16, a.vs, &row0v, &rows_v);
+	lane_rows(v, a.seg_len16, a.vs, &row0v, &rows_v);
 	if (t == CODE_VOID || r >= rows_v) return AL_NEG;
 	const int row = row0v + r;
 	if (row >= a.m) return 0;                 // zero-score pad rows (Q3)
@@ -166,35 +120,17 @@ __global__ void __launch_bounds__(FWD_THREADS) __attribute__((amdgpu_waves_per_e
 	extern __shared__ __align__(16) uint8_t prof[];
 	const int lane = threadIdx.x & 63;
 
-	{
-		for (int idx = threadIdx.x; idx < 6 * 128 * AL_RS; idx += blockDim.x) {
-			const int r = idx % AL_RS;
-			const int v = (idx / AL_RS) % 128;
-			const int t = idx / (AL_RS * 128);
-			int sc = fwd_cell_score(a, t, 128 * a.tile + v, r, F16 ? 1 : SC);
-			if (F16) sc = (int)(int16_t)f16_bits(sc == AL_NEG ? AL_NEG_F16 : sc);
-			*reinterpret_cast<int16_t*>(prof + t * AL_CODE_STRIDE + (v >> 1) * AL_LANE_STRIDE + (v & 1) * 48 + r * 2) = (int16_t)sc;
-		}
-	}
+	stage_profile<F16, AL_NEG>(prof, 6, a.tile, [&](int t, int v, int r) { return fwd_cell_score(a, t, v, r, F16 ? 1 : SC); });
 	__syncthreads();
 
-	// stripe-aligned layout (see scan.hip): virtual lane 8k starts the reference's stripe k
-	uint32_t fthr = 0xFFFFFFFFu, act = 0, startbits = 0;
-	int row0[2];
-	for (int h = 0; h < 2; h++) {
-		const int v = 128 * a.tile + 2 * lane + h;
-		int rows_v;
-		lane_rows_a(v, a.seg_len16, a.vs, &row0[h], &rows_v);
-		if (v % a.vs == 0 && v > 0) { fthr = (fthr & ~(0xFFFFu << (16 * h))) | ((131u * SC + (SC - 1)) << (16 * h)); startbits |= 0xFFFFu << (16 * h); }
-		if (rows_v == RP) act |= 0xFFFFu << (16 * h);
-	}
-	const v2u fthr2 = u_from((int)fthr);
-	const v2u actm = u_from((int)act);
-	const v2u startm = u_from((int)startbits);
+	// stripe-aligned layout (systolic.h): virtual lane vs * k starts the reference's stripe k
+	const StripeLane ln(128 * a.tile + 2 * lane, a.seg_len16, a.vs, RP, 132u * SC - 1u);
+	const uint32_t act = ln.act;
+	const v2u actm = ln.actm, startm = ln.startm;
 	const bool lvl2 = a.seg_len16 >= 96;      // (the 16-bit pass, !TAINT, needs no Q2 test at all: its compare is unaffected)
-	const uint8_t* pl = prof + lane * AL_LANE_STRIDE;
+	const uint8_t* pl = prof + lane * PROF_LANE_STRIDE;
 	// (31 - r) tags for the row keys, and the base of the global-row key of my two virtual lanes
-	const int kbase_lo = FWD_KROW - row0[0] - 31, kbase_hi = FWD_KROW - row0[1] - 31;
+	const int kbase_lo = FWD_KROW - ln.row0[0] - 31, kbase_hi = FWD_KROW - ln.row0[1] - 31;
 
 	for (;;) {
 		int w = 0;
@@ -211,7 +147,7 @@ __global__ void __launch_bounds__(FWD_THREADS) __attribute__((amdgpu_waves_per_e
 		const bool first_tile = a.tile == 0, last_tile = a.tile == a.ntiles - 1;
 		uint4 bchunk = make_uint4(0u, 0u, 0u, 0u);
 
-		int H[RP], E[RP];                // packed u16 pairs, kept as plain 32-bit registers (see scan.hip)
+		int H[RP], E[RP];                // packed u16 pairs, kept as plain 32-bit registers (see systolic.h)
 #pragma unroll
 		for (int r = 0; r < RP; r++) { H[r] = 0; E[r] = 0; }
 		int tc = (CODE_VOID << 16) | CODE_VOID;
@@ -233,17 +169,17 @@ __global__ void __launch_bounds__(FWD_THREADS) __attribute__((amdgpu_waves_per_e
 			uint32_t kup;
 			if (first_tile) {
 				// zeros enter virtual lane 0 (bound_ctrl): nothing to preload
-				tc = vshift2(tc, newcode << 16);
-				recv_h = vshift2_zero(hbot); recv_f = vshift2_zero(fbot); recv_fp = vshift2_zero(fpo);
-				kup = (uint32_t)__builtin_amdgcn_mov_dpp((int)khi, 0x138, 0xf, 0xf, true);
+				tc = vshift(tc, newcode << 16);
+				recv_h = vshift0(hbot); recv_f = vshift0(fbot); recv_fp = vshift0(fpo);
+				kup = (uint32_t)vprev0((int)khi);
 			} else {
 				const uint32_t bx = (uint32_t)__builtin_amdgcn_readlane((int)bchunk.x, step & 63);
 				const uint32_t by = (uint32_t)__builtin_amdgcn_readlane((int)bchunk.y, step & 63);
 				const int in_k = __builtin_amdgcn_readlane((int)bchunk.z, step & 63);
 				newcode |= (int)((by >> 16) & TAG_HZ);              // hazard seen by the tiles above
-				tc = vshift2(tc, newcode << 16);
-				recv_h = vshift2(hbot, (int)(bx << 16)); recv_f = vshift2(fbot, (int)(bx & 0xffff0000u)); recv_fp = vshift2(fpo, (int)(by << 16));
-				kup = (uint32_t)__builtin_amdgcn_update_dpp(in_k, (int)khi, 0x138, 0xf, 0xf, false);
+				tc = vshift(tc, newcode << 16);
+				recv_h = vshift(hbot, (int)(bx << 16)); recv_f = vshift(fbot, (int)(bx & 0xffff0000u)); recv_fp = vshift(fpo, (int)(by << 16));
+				kup = (uint32_t)vprev((int)khi, in_k);
 			}
 			const uint32_t kin_lo = kup, kin_hi = klo;       // from virtual lane v-1 (same column, one step ago)
 			const v2u tt = u_from(tc) & (v2u){ 7, 7 };                       // stream codes of my two halves
@@ -253,10 +189,10 @@ __global__ void __launch_bounds__(FWD_THREADS) __attribute__((amdgpu_waves_per_e
 				// f16: they subtract +inf instead; E, F and H are finite, so no NaN arises, and max3(-inf, -inf, 0) = 0.
 				// (0 / 1 flags from the asm helpers and products with them: the compiler turns masks into per-half selects)
 				const v2u notvoid = tt ^ (v2u){ CODE_VOID, CODE_VOID };
-				const v2u vinf = apk_ksubs(0x00010001u, notvoid) * (v2u){ 0x7C00, 0x7C00 };
+				const v2u vinf = pk_ksubs(0x00010001u, notvoid) * (v2u){ 0x7C00, 0x7C00 };
 				dec = vinf | u_from((int)f16c2(GAP_EXT));
 				gapo = vinf | u_from((int)f16c2(GAP_OPEN));
-				live01 = apk_minu_k(notvoid, 0x00010001u);
+				live01 = pk_minu_k(notvoid, 0x00010001u);
 			} else {
 				isvoid = (v2u){ 0, 0 } - __builtin_elementwise_sub_sat((v2u){ 1, 1 }, tt ^ (v2u){ CODE_VOID, CODE_VOID });
 				dec = isvoid | (v2u){ GAP_EXT * SC, GAP_EXT * SC };
@@ -265,86 +201,19 @@ __global__ void __launch_bounds__(FWD_THREADS) __attribute__((amdgpu_waves_per_e
 			const int hdiag0 = recv_h_last;
 			recv_h_last = recv_h;
 			v2u f = u_from(recv_f);
-			v2s lkx[4] = { (v2s){ 0, 0 }, (v2s){ 0, 0 }, (v2s){ 0, 0 }, (v2s){ 0, 0 } };      // independent max chains
-			constexpr int ROWS_PER_LOAD = 8;
-			constexpr int NLOAD = (RP + ROWS_PER_LOAD - 1) / ROWS_PER_LOAD;
-			v4i PA[NLOAD], PB[NLOAD];
-			{
-				const int t_lo = tc & 7, t_hi = (tc >> 16) & 7;
-				const uint8_t* pa = pl + t_lo * AL_CODE_STRIDE;
-				const uint8_t* pb = pl + t_hi * AL_CODE_STRIDE + 48;
-#pragma unroll
-				for (int g = 0; g < NLOAD; g++) {
-					PA[g] = *reinterpret_cast<const v4i*>(pa + 16 * g);
-					PB[g] = *reinterpret_cast<const v4i*>(pb + 16 * g);
-				}
-			}
-			auto score_of = [&](int r) -> int {
-				const int g = r >> 3, k = r & 7; return __builtin_amdgcn_perm(PB[g][k >> 1], PA[g][k >> 1], (k & 1) ? 0x07060302 : 0x05040100);
-			};
-			// (see scan.hip: the diagonal sum goes into the register of the score, the new H into the register of the old
-			//  H, so the H column needs no second copy and no moves at the end of the step)
-			auto diag_plus_score = [](int hold, int sc) -> v2s {
-				if (TAINT) asm("v_pk_add_i16 %0, %1, %0 clamp" : "+v"(sc) : "v"(hold));
-				else asm("v_pk_add_i16 %0, %1, %0" : "+v"(sc) : "v"(hold));
-				return s_fromi(sc);
-			};
+			const ProfileRows<RP> rows(pl + (tc & 7) * PROF_CODE_STRIDE, pl + ((tc >> 16) & 7) * PROF_CODE_STRIDE + PROF_HALF);
+			auto no_hook = [](int, auto) {};
 			v2s lkey;
 			if constexpr (F16) {
-				// the f16 row pair (dp_f16.h): 8.5 instructions where the integer one below takes 10
-				int ff = recv_f, lk0 = 0, lk1 = 0, hprev = 0;
-				int t = hf_diag_plus_score(hdiag0, score_of(0));
-#pragma unroll
-				for (int r = 0; r < RP; r++) {
-					int tnext = t;
-					if (r + 1 < RP) tnext = hf_diag_plus_score(H[r], score_of(r + 1));
-					const int h = hf_h(H[r], t, E[r], ff, tnext);
-					H[r] = h;
-					const int ho = hf_sub(h, a_i(gapo));
-					E[r] = hf_max_floor(hf_sub(E[r], a_i(dec)), ho);
-					const int fnew = hf_max_floor(hf_sub(ff, a_i(dec)), ho);
-					int hm = h;             // what the lane maximum sees of this row
-					if (r == RP - 1) {
-						ff = (fnew & (int)act) | (ff & ~(int)act);
-						hm = h & (int)act;
-						if (RP > 1) hbot = hm | (H[RP > 1 ? RP - 2 : 0] & ~(int)act);
-						else hbot = h;
-					} else ff = fnew;
-					// one max3 per two rows, two independent chains
-					if (r & 1) { if (r & 2) lk1 = hf_max3(lk1, hprev, hm); else lk0 = hf_max3(lk0, hprev, hm); }
-					hprev = hm;
-					t = tnext;
-				}
-				lkey = s_fromi((RP & 1) ? hf_max3(lk0, lk1, hprev) : hf_max_floor(lk0, lk1));
+				int ff = recv_f;
+				lkey = s_from(f16_row_pair(H, E, hbot, ff, hdiag0, rows, HfGapReg{ to_int(gapo), to_int(dec) }, act, no_hook));
 				f = u_from(ff);
 			} else {
-			v2s t = diag_plus_score(hdiag0, score_of(0));
-#pragma unroll
-			for (int r = 0; r < RP; r++) {
-				v2s tnext = t;
-				if (r + 1 < RP) tnext = diag_plus_score(H[r], score_of(r + 1));
-				v2s h = __builtin_elementwise_max(t, s_fromi(E[r]));
-				{ int hn; asm("v_pk_max_i16 %0, %2, %3" : "=v"(hn) : "0"(H[r]), "v"(a_i(h)), "v"(a_i(f)), "v"(a_i(tnext))); h = s_fromi(hn); }
-				H[r] = a_i(h);
-				const v2u ho = __builtin_elementwise_sub_sat(a_u(h), gapo);
-				E[r] = a_i(__builtin_elementwise_max(__builtin_elementwise_sub_sat(u_from(E[r]), dec), ho));
-				const v2u fnew = __builtin_elementwise_max(__builtin_elementwise_sub_sat(f, dec), ho);
-				const v2s key = REV ? h : (h | (v2s){ (short)(31 - r), (short)(31 - r) });
-				if (r == RP - 1) {
-					f = (fnew & actm) | (f & ~actm);
-					lkx[r & 3] = __builtin_elementwise_max(lkx[r & 3], a_s(a_u(key) & actm));
-					if (RP > 1) hbot = (a_i(h) & (int)act) | (H[RP > 1 ? RP - 2 : 0] & ~(int)act);
-					else hbot = a_i(h);
-				} else {
-					f = fnew;
-					lkx[r & 3] = __builtin_elementwise_max(lkx[r & 3], key);
-				}
-				t = tnext;
+				// REV: the lane maximum is of the values; else of value | (31 - r), the maximum and the smallest row that holds it
+				lkey = int_row_pair<IntRowPolicy<TAINT, !REV>>(H, E, hbot, f, hdiag0, rows, gapo, dec, act, no_hook, no_hook);
 			}
-			lkey = __builtin_elementwise_max(__builtin_elementwise_max(lkx[0], lkx[1]), __builtin_elementwise_max(lkx[2], lkx[3]));
-			}
-			asm volatile("" :: "v"(a_i(lkey)));      // pin the reduction before the hazard branch (see scan.hip)
-			fbot = a_i(f);
+			asm volatile("" :: "v"(to_int(lkey)));      // pin the reduction before the hazard branch (see k_scan)
+			fbot = to_int(f);
 			if constexpr (REV) {
 				{
 					// reverse pass: my two columns' maxima (value = key >> 5) go into the running maxima of the zones that hold the column
@@ -355,22 +224,22 @@ __global__ void __launch_bounds__(FWD_THREADS) __attribute__((amdgpu_waves_per_e
 					if constexpr (F16) {
 						// the maxima are non-negative, so their bit patterns order like the values: the zone maxima stay u16 maxima of the
 						// bits and become integers at the store.  A zone takes the value times its 0 / 1 flag (zone >= 1, >= 2, == 3).
-						const v2u val = a_u(lkey) * live01;
+						const v2u val = as_u(lkey) * live01;
 						const v2u ge2 = zz >> (v2u){ 1, 1 };
 						zacc0 = __builtin_elementwise_max(zacc0, val);
-						zacc1 = __builtin_elementwise_max(zacc1, val * apk_minu_k(zz, 0x00010001u));
+						zacc1 = __builtin_elementwise_max(zacc1, val * pk_minu_k(zz, 0x00010001u));
 						zacc2 = __builtin_elementwise_max(zacc2, val * ge2);
 						zacc3 = __builtin_elementwise_max(zacc3, val * (zz & ge2));
 						lastb = tcu & (v2u){ TAG_LAST, TAG_LAST };
 					} else {
-					const v2u val = (a_u(lkey) >> (v2u){ 5, 5 }) & ~isvoid;
+					const v2u val = (as_u(lkey) >> (v2u){ 5, 5 }) & ~isvoid;
 					zacc0 = __builtin_elementwise_max(zacc0, val);
 					zacc1 = __builtin_elementwise_max(zacc1, val & ((v2u){ 0, 0 } - __builtin_elementwise_min(zz, (v2u){ 1, 1 })));
 					zacc2 = __builtin_elementwise_max(zacc2, val & ((v2u){ 0, 0 } - __builtin_elementwise_min(__builtin_elementwise_sub_sat(zz, (v2u){ 1, 1 }), (v2u){ 1, 1 })));
 					zacc3 = __builtin_elementwise_max(zacc3, val & ((v2u){ 0, 0 } - __builtin_elementwise_sub_sat(zz, (v2u){ 2, 2 })));
 					lastb = (tcu >> (v2u){ 3, 3 }) & (v2u){ 1, 1 };
 					}
-					if (__builtin_amdgcn_ballot_w64(a_i(lastb) != 0) != 0ull) {
+					if (__builtin_amdgcn_ballot_w64(to_int(lastb) != 0) != 0ull) {
 						if (F16) lastb = lastb >> (v2u){ 3, 3 };
 #pragma unroll
 						for (int h = 0; h < 2; h++) {
@@ -390,56 +259,15 @@ __global__ void __launch_bounds__(FWD_THREADS) __attribute__((amdgpu_waves_per_e
 				}
 			}
 			// Q2 (8-bit pass only).  Short queries: any F[b] >= 132 entering a stripe flags the column (TAG_HZ).  Otherwise the
-			// row analysis of scan.hip marks the cells the reference's early lazy-F exit would have left smaller (taint bit).
+			// row analysis (q2_rows) marks the cells the reference's early lazy-F exit would have left smaller (taint bit).
 			fpo = 0;
-			if (TAINT) {
+			if constexpr (TAINT) {
 				if (lvl2) {
-					constexpr uint32_t K1 = 0x00010001u, KGE = (uint32_t)(132 * SC - 1) * 0x10001u, KLT = (uint32_t)(144 * SC) * 0x10001u,
-						KE = (uint32_t)(GAP_EXT * SC) * 0x10001u, KO = (uint32_t)(GAP_OPEN * SC) * 0x10001u;
-					// cheap superset first: a stripe-start lane receives F >= 132, or some lane receives a live chain
-					const v2u cand = apk_subs_k(u_from(recv_f) & startm, KGE) | u_from(recv_fp);
-					bool enter = false;
-					v2u fp_in = (v2u){ 0, 0 }, arm_in = (v2u){ 0, 0 };
-					if (__builtin_amdgcn_ballot_w64(a_i(cand) != 0) != 0ull) {
-						const v2u fpraw = ((u_from(recv_f) & startm) | (u_from(recv_fp) & ~startm)) & ~isvoid;
-						fp_in = fpraw & (v2u){ 0x7fff, 0x7fff };
-						arm_in = (fpraw >> (v2u){ 15, 15 }) & ~startm;
-						const v2u hot = apk_subs_k(fp_in, KGE) | apk_minu(arm_in, fp_in);
-						enter = __builtin_amdgcn_ballot_w64(a_i(hot) != 0) != 0ull;
-					}
-					if (enter) {
-						v2u fp = fp_in, arm = arm_in;
-						const v2u one = (v2u){ 1, 1 };
-						// pass 1 reads H / E and collects the decisions as bit r of (dh, de)[r / 16]; pass 2 ORs the taint bit in
-						uint32_t dh[2] = { 0u, 0u }, de[2] = { 0u, 0u };
-#pragma unroll
-						for (int r = 0; r < RP; r++) {
-							const v2u hr = u_from(H[r]);
-							const v2u ge = apk_minu_k(apk_subs_k(fp, KGE), K1);                         // Fp >= 132
-							v2u lt = apk_minu_k(apk_ksubs(KLT, hr), K1) | ((hr >> (v2u){ 5, 5 }) & one);      // H < 144, or tainted
-							v2u eq = apk_ksubs(K1, apk_subs(hr, fp));                                   // H == Fp (H >= Fp always)
-							v2u nfp = apk_subs_k(fp, KE);
-							if (r == RP - 1) { lt &= actm; eq &= actm; nfp = (nfp & actm) | (fp & ~actm); }
-							const v2u dev = apk_minu(apk_minu(eq, fp), arm);                            // 0 / 1
-							const v2u ho = apk_subs_k(hr, KO);
-							const v2u efrom = apk_minu(apk_ksubs(K1, apk_subs(u_from(E[r]), ho)), ho);
-							dh[r >> 4] |= (uint32_t)a_i(dev) << (r & 15);
-							de[r >> 4] |= (uint32_t)a_i(apk_minu(efrom, dev)) << (r & 15);
-							arm = apk_maxu(arm, apk_minu(ge, lt));
-							fp = nfp;
-						}
-#pragma unroll
-						for (int r = 0; r < RP; r++) {
-							a_or_in_place(H[r], (int)(((dh[r >> 4] >> (r & 15)) & K1) << 5));
-							a_or_in_place(E[r], (int)(((de[r >> 4] >> (r & 15)) & K1) << 5));
-						}
-						if (RP > 1) hbot = (H[RP - 1] & (int)act) | (H[RP > 1 ? RP - 2 : 0] & ~(int)act);
-						else hbot = H[0];
-						fpo = a_i(fp | (arm << (v2u){ 15, 15 }));
-					}
+					// (void columns neither start nor carry a chain)
+					q2_rows<SC, false>(H, E, hbot, fpo, recv_f, recv_fp, startm, actm, act, ~isvoid);
 				} else {
-					const v2u hz_b = __builtin_elementwise_sub_sat(u_from(recv_f), fthr2);
-					tc |= a_i(__builtin_elementwise_min(hz_b, (v2u){ 1, 1 }) << (v2u){ 4, 4 });
+					const v2u hz_b = __builtin_elementwise_sub_sat(u_from(recv_f), ln.fthr2);
+					tc |= to_int(__builtin_elementwise_min(hz_b, (v2u){ 1, 1 }) << (v2u){ 4, 4 });
 				}
 			}
 			if constexpr (REV) {
@@ -452,7 +280,7 @@ __global__ void __launch_bounds__(FWD_THREADS) __attribute__((amdgpu_waves_per_e
 				continue;
 			}
 			// per-column (max, smallest row) keys
-			const uint32_t lk = (uint32_t)a_i(lkey);
+			const uint32_t lk = (uint32_t)to_int(lkey);
 			const uint32_t loc_lo = (((lk & 0xFFFFu) >> 5) << 17) | (uint32_t)(kbase_lo + (int)(lk & 31u));
 			const uint32_t loc_hi = ((lk >> 21) << 17) | (uint32_t)(kbase_hi + (int)((lk >> 16) & 31u));
 			klo = kin_lo > loc_lo ? kin_lo : loc_lo;
@@ -506,7 +334,7 @@ static hipError_t launch_fwd_t(const FwdArgs& a, hipStream_t st)
 	constexpr int WPB = FWD_THREADS / 64;
 	long blocks = ((long)a.ntask + WPB - 1) / WPB;
 	if (blocks > 256 * 2) blocks = 256 * 2;
-	hipLaunchKernelGGL((k_align_fwd<RP, TAINT, REV, F16>), dim3((unsigned)blocks), dim3(FWD_THREADS), (size_t)6 * AL_CODE_STRIDE, st, a);
+	hipLaunchKernelGGL((k_align_fwd<RP, TAINT, REV, F16>), dim3((unsigned)blocks), dim3(FWD_THREADS), (size_t)6 * PROF_CODE_STRIDE, st, a);
 	return hipGetLastError();
 }
 

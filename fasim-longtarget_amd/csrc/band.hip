@@ -13,7 +13,7 @@
 //                   below the band's first row (it spans at most L + (5L - theta - 12) / 4 rows: L diagonal steps and
 //                   the vertical gap residues the score can pay for).  It also writes the try's column stream: one
 //                   16-bit word per column = LDS address of the column's profile rows for the band | void | last.
-//   k_align_band<G> the systolic pipeline of align.hip cut into 64 / G sub-pipelines per wave.  Each sub-pipeline sweeps
+//   k_align_band<G> the systolic pipeline of k_align_fwd (systolic.h) cut into 64 / G sub-pipelines per wave.  Each sub-pipeline sweeps
 //                   its own windows over its own 48 G rows; uniform 24 rows per virtual lane; the per-column bookkeeping of
 //                   the 64 / G pipe ends runs as vector code.  A result with score >= theta_min is the reference's
 //                   (score, ref_end, read_end) bit for bit ("Banded stage 3", has the argument);
@@ -23,36 +23,17 @@
 #include <stdint.h>
 #include <vector>
 #include "kernels.h"
+#include "systolic.h"
 
 namespace fasim {
 
-typedef short b2s __attribute__((ext_vector_type(2)));
-typedef unsigned short b2u __attribute__((ext_vector_type(2)));
-typedef int b4i __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ b2s bs(b2u x) { return __builtin_bit_cast(b2s, x); }
-__device__ __forceinline__ b2u bu(b2s x) { return __builtin_bit_cast(b2u, x); }
-__device__ __forceinline__ int bi(b2s x) { return __builtin_bit_cast(int, x); }
-__device__ __forceinline__ int bi(b2u x) { return __builtin_bit_cast(int, x); }
-__device__ __forceinline__ b2u bu_from(int x) { return __builtin_bit_cast(b2u, x); }
-__device__ __forceinline__ b2s bs_from(int x) { return __builtin_bit_cast(b2s, x); }
-
-constexpr int BAND_RPB = 24;                 // rows per virtual lane (uniform; two virtual lanes = 48 rows per lane)
-constexpr int BAND_LANE_STRIDE = 112;        // bytes per lane in the LDS profile: 2 x 24 x int16 + 16 (bank-conflict-free b128)
+constexpr int BAND_RPB = PROF_RS;            // rows per virtual lane (uniform; two virtual lanes = 48 rows per lane): a lane of the profile is full
 constexpr int BAND_SC = 32;                  // value scale: the low 5 bits of every H carry (31 - row in lane)
 constexpr int BAND_NEG = -32768;
 // windows in flight per sub-pipeline: a window is at least 4 stream columns and the pipe is 2 G columns deep -> at most G / 2 + 2;
 // the descriptor FIFO of a sub-pipeline holds G entries
 constexpr int BAND_VOID_BIT = 0x4000, BAND_LAST_BIT = 0x8000;
 constexpr int BAND_THREADS = 512;
-
-// rows owned by k_scan's virtual lane v (scan.hip lane_rows)
-__device__ __forceinline__ void scan_lane_rows(int v, int seg_len, int vs, int* row0, int* rows)
-{
-	const int s = v / vs, j = v - s * vs, q = seg_len / vs, rem = seg_len - q * vs;
-	*rows = q + (j < rem ? 1 : 0);
-	*row0 = s * seg_len + j * q + (j < rem ? j : rem);
-}
 
 // ------------------------------------------------------------------------------------------------
 // k_band_decide / k_band_emit
@@ -106,7 +87,7 @@ __global__ void __launch_bounds__(256) k_band_decide(BandSelArgs a)
 	uint32_t* r0s = sel_lds + (size_t)wv * (nv / 2 + nv + 1);
 	uint16_t* ub = reinterpret_cast<uint16_t*>(r0s + nv + 1);
 	// rows of k_scan's virtual lanes (the same for every try)
-	for (int v = lane; v < nv; v += 64) { int row0, rows; scan_lane_rows(v, a.seg16, a.vs, &row0, &rows); r0s[v] = (uint32_t)row0; }
+	for (int v = lane; v < nv; v += 64) { int row0, rows; lane_rows(v, a.seg16, a.vs, &row0, &rows); r0s[v] = (uint32_t)row0; }
 	if (lane == 0) r0s[nv] = (uint32_t)(16 * a.seg16);
 	const int w0 = blockIdx.x * SEL_TRIES;
 	for (int k = 0; k < SEL_TRIES / 4; k++) {
@@ -348,29 +329,6 @@ struct BandArgs {
 	FwdOut* out;
 };
 
-template <int G>
-__device__ __forceinline__ int gshift(int x, int inject, bool is_start)
-{
-	// out.lo = x.hi of lane - 1 (first lane of a sub-pipeline: `inject`'s hi half), out.hi = x.lo
-	int up = __builtin_amdgcn_update_dpp(inject, x, G == 32 ? 0x138 /* wave_shr:1 */ : 0x111 /* row_shr:1 */, 0xf, 0xf, false);
-	if (G != 16) up = is_start ? inject : up;
-	return __builtin_amdgcn_alignbit(x, up, 16);
-}
-template <int G>
-__device__ __forceinline__ int gshift0(int x, bool is_start)
-{
-	int up = __builtin_amdgcn_mov_dpp(x, G == 32 ? 0x138 : 0x111, 0xf, 0xf, true);
-	if (G != 16) up = is_start ? 0 : up;
-	return __builtin_amdgcn_alignbit(x, up, 16);
-}
-template <int G>
-__device__ __forceinline__ uint32_t gprev(uint32_t x, bool is_start)
-{
-	int up = __builtin_amdgcn_mov_dpp((int)x, G == 32 ? 0x138 : 0x111, 0xf, 0xf, true);
-	if (G != 16) up = is_start ? 0 : up;
-	return (uint32_t)up;
-}
-
 __device__ __forceinline__ int band_cell_score(const BandArgs& a, int t, int row)
 {
 	if (row >= 16 * ((a.m + 15) / 16)) return BAND_NEG;      // below the padded query: dead rows (never the column maximum)
@@ -384,15 +342,19 @@ __global__ void __launch_bounds__(BAND_THREADS) __attribute__((amdgpu_waves_per_
 {
 	constexpr int NG = 64 / G;                               // sub-pipelines per wave
 	constexpr int SC = BAND_SC;
+	// the hand-over inside a sub-pipeline of G lanes: G = 32 shifts along the wave, G = 8 / 16 along the DPP rows of 16 lanes; only
+	// a sub-pipeline that is exactly one DPP row starts where DPP itself injects
+	constexpr int CTRL = G == 32 ? DPP_WAVE_SHR1 : DPP_ROW_SHR1;
+	constexpr bool FIX = G != 16;
 	extern __shared__ __align__(16) uint8_t lds[];
 	uint8_t* prof = lds;                                     // [5 codes][lc lanes][112] | void block [G][112]
-	const int code_stride = a.lc * BAND_LANE_STRIDE;
+	const int code_stride = a.lc * PROF_LANE_STRIDE;
 	const BandZoneTab zt = a.tab[blockIdx.x];
-	uint4* fifo = reinterpret_cast<uint4*>(lds + 5 * code_stride + G * BAND_LANE_STRIDE);     // [wave][NG][G]
+	uint4* fifo = reinterpret_cast<uint4*>(lds + 5 * code_stride + G * PROF_LANE_STRIDE);     // [wave][NG][G]
 	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 	for (int idx = threadIdx.x; idx < 5 * a.lc * 48; idx += blockDim.x) {
 		const int r = idx % 48, l = (idx / 48) % a.lc, t = idx / (48 * a.lc);
-		*reinterpret_cast<int16_t*>(prof + t * code_stride + l * BAND_LANE_STRIDE + r * 2) = (int16_t)band_cell_score(a, t, 48 * (zt.zbase + l) + r);
+		*reinterpret_cast<int16_t*>(prof + t * code_stride + l * PROF_LANE_STRIDE + r * 2) = (int16_t)band_cell_score(a, t, 48 * (zt.zbase + l) + r);
 	}
 	for (int idx = threadIdx.x; idx < G * 56; idx += blockDim.x)
 		*reinterpret_cast<int16_t*>(prof + 5 * code_stride + idx * 2) = (int16_t)BAND_NEG;
@@ -402,7 +364,7 @@ __global__ void __launch_bounds__(BAND_THREADS) __attribute__((amdgpu_waves_per_
 	const bool is_start = j == 0, is_end = j == G - 1;
 	constexpr int FIFO = G;
 	uint4* myfifo = fifo + ((size_t)wv * NG + grp) * FIFO;
-	const uint8_t* pl = prof + j * BAND_LANE_STRIDE;
+	const uint8_t* pl = prof + j * PROF_LANE_STRIDE;
 	// row keys: (column maximum << 16) | (0xFFFF - row relative to the band's first row)
 	const int kbase_lo = 0xFFFF - (2 * j) * BAND_RPB - 31, kbase_hi = 0xFFFF - (2 * j + 1) * BAND_RPB - 31;
 	const uint32_t voidw = (uint32_t)(BAND_VOID_BIT | (5 * a.lc * 7));
@@ -452,44 +414,40 @@ __global__ void __launch_bounds__(BAND_THREADS) __attribute__((amdgpu_waves_per_
 #pragma unroll
 		for (int k = 0; k < 4; k++) {
 			const int inj = (int)((k < 2 ? feed.x : feed.y) >> (16 * (k & 1))) << 16;
-			tc = gshift<G>(tc, inj, is_start);
-			const int recv_h = gshift0<G>(hbot, is_start), recv_f = gshift0<G>(fbot, is_start);
-			const uint32_t kin_lo = gprev<G>(khi, is_start), kin_hi = klo;
-			const b2u tcu = bu_from(tc);
+			tc = vshift<CTRL, FIX>(tc, inj, is_start);
+			const int recv_h = vshift0<CTRL, FIX>(hbot, is_start), recv_f = vshift0<CTRL, FIX>(fbot, is_start);
+			const uint32_t kin_lo = (uint32_t)vprev0<CTRL, FIX>((int)khi, is_start), kin_hi = klo;
+			const v2u tcu = u_from(tc);
 			// void columns clear E and F (the saturating subtractions use 0xFFFF) and score -inf
-			const b2u isvoid = bu(bs(tcu << (b2u){ 1, 1 }) >> (b2s){ 15, 15 });
-			const b2u dec = isvoid | (b2u){ GAP_EXT * SC, GAP_EXT * SC };
-			const b2u gapo = isvoid | (b2u){ GAP_OPEN * SC, GAP_OPEN * SC };
-			const uint8_t* pa = pl + ((tc & 0x3fff) << 4);
-			const uint8_t* pbp = pl + (((tc >> 16) & 0x3fff) << 4) + 48;
-			b4i PA[3], PB[3];
-#pragma unroll
-			for (int g = 0; g < 3; g++) { PA[g] = *reinterpret_cast<const b4i*>(pa + 16 * g); PB[g] = *reinterpret_cast<const b4i*>(pbp + 16 * g); }
-			auto score_of = [&](int r) -> int { const int g = r >> 3, kk = r & 7; return __builtin_amdgcn_perm(PB[g][kk >> 1], PA[g][kk >> 1], (kk & 1) ? 0x07060302 : 0x05040100); };
-			auto diag_plus_score = [](int hold, int sc) -> b2s { asm("v_pk_add_i16 %0, %1, %0" : "+v"(sc) : "v"(hold)); return bs_from(sc); };
+			const v2u isvoid = as_u(as_s(tcu << (v2u){ 1, 1 }) >> (v2s){ 15, 15 });
+			const v2u dec = isvoid | (v2u){ GAP_EXT * SC, GAP_EXT * SC };
+			const v2u gapo = isvoid | (v2u){ GAP_OPEN * SC, GAP_OPEN * SC };
+			const ProfileRows<BAND_RPB> rows(pl + ((tc & 0x3fff) << 4), pl + (((tc >> 16) & 0x3fff) << 4) + PROF_HALF);
 			const int hdiag0 = recv_h_last;
 			recv_h_last = recv_h;
-			b2u f = bu_from(recv_f);
-			b2s lkx[4] = { (b2s){ 0, 0 }, (b2s){ 0, 0 }, (b2s){ 0, 0 }, (b2s){ 0, 0 } };
-			b2s t = diag_plus_score(hdiag0, score_of(0));
+			v2u f = u_from(recv_f);
+			// The integer row pair of systolic.h (plain sums, every half owns all 24 rows, row tags), written out: through int_row_pair
+			// the compiler schedules this 4-step loop differently (19 more s_nop per loop, one hand-over shift selected as v_perm_b32)
+			v2s lkx[4] = { (v2s){ 0, 0 }, (v2s){ 0, 0 }, (v2s){ 0, 0 }, (v2s){ 0, 0 } };
+			v2s t = diag_plus_score<false>(hdiag0, rows.score_of(0));
 #pragma unroll
 			for (int r = 0; r < BAND_RPB; r++) {
-				b2s tnext = t;
-				if (r + 1 < BAND_RPB) tnext = diag_plus_score(H[r], score_of(r + 1));
-				b2s h = __builtin_elementwise_max(t, bs_from(E[r]));
-				{ int hn; asm("v_pk_max_i16 %0, %2, %3" : "=v"(hn) : "0"(H[r]), "v"(bi(h)), "v"(bi(f)), "v"(bi(tnext))); h = bs_from(hn); }
-				H[r] = bi(h);
-				const b2u ho = __builtin_elementwise_sub_sat(bu(h), gapo);
-				E[r] = bi(__builtin_elementwise_max(__builtin_elementwise_sub_sat(bu_from(E[r]), dec), ho));
+				v2s tnext = t;
+				if (r + 1 < BAND_RPB) tnext = diag_plus_score<false>(H[r], rows.score_of(r + 1));
+				v2s h = __builtin_elementwise_max(t, s_from(E[r]));
+				h = s_from(h_in_place(H[r], to_int(h), to_int(f), to_int(tnext)));
+				H[r] = to_int(h);
+				const v2u ho = __builtin_elementwise_sub_sat(as_u(h), gapo);
+				E[r] = to_int(__builtin_elementwise_max(__builtin_elementwise_sub_sat(u_from(E[r]), dec), ho));
 				f = __builtin_elementwise_max(__builtin_elementwise_sub_sat(f, dec), ho);
-				const b2s key = h | (b2s){ (short)(31 - r), (short)(31 - r) };
+				const v2s key = h | (v2s){ (short)(31 - r), (short)(31 - r) };
 				lkx[r & 3] = __builtin_elementwise_max(lkx[r & 3], key);
 				t = tnext;
 			}
 			hbot = H[BAND_RPB - 1];
-			fbot = bi(f);
-			const b2s lkey = __builtin_elementwise_max(__builtin_elementwise_max(lkx[0], lkx[1]), __builtin_elementwise_max(lkx[2], lkx[3]));
-			const uint32_t lk = (uint32_t)bi(lkey);
+			const v2s lkey = __builtin_elementwise_max(__builtin_elementwise_max(lkx[0], lkx[1]), __builtin_elementwise_max(lkx[2], lkx[3]));
+			fbot = to_int(f);
+			const uint32_t lk = (uint32_t)to_int(lkey);
 			const uint32_t loc_lo = (((lk & 0xFFFFu) >> 5) << 16) | (uint32_t)(kbase_lo + (int)(lk & 31u));
 			const uint32_t loc_hi = ((lk >> 21) << 16) | (uint32_t)(kbase_hi + (int)((lk >> 16) & 31u));
 			klo = kin_lo > loc_lo ? kin_lo : loc_lo;
@@ -527,7 +485,7 @@ int band_profile_lanes(int m) { return (16 * ((m + 15) / 16) + 47) / 48; }
 // the lanes of ONE zone (zs lanes plus one band height) and works on the tries whose band starts in that zone.
 int band_zone_stride(int m) { const int nl = band_profile_lanes(m); int zs = 64; while ((nl + zs - 1) / zs > BAND_MAX_ZONES) zs *= 2; return nl <= zs ? nl : zs; }
 static int band_lc(int m, int G) { const int nl = band_profile_lanes(m), zs = band_zone_stride(m); return zs + G < nl ? zs + G : nl; }
-size_t band_lds_bytes(int m, int G) { return (size_t)(5 * band_lc(m, G) + G) * BAND_LANE_STRIDE + (size_t)(BAND_THREADS / 64) * 64 * sizeof(uint4); }
+size_t band_lds_bytes(int m, int G) { return (size_t)(5 * band_lc(m, G) + G) * PROF_LANE_STRIDE + (size_t)(BAND_THREADS / 64) * 64 * sizeof(uint4); }
 // classes (bit c: G = 8 << c) the band kernel runs for a query of m rows: the profile lanes of a zone must fit the LDS budget and the
 // band must be at most 3/8 of the query's height (a band of half the height costs more than it saves: measured on H19, G = 32)
 int band_classes(int m)

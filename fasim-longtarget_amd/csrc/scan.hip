@@ -1,17 +1,9 @@
 // fasim-longtarget_amd/csrc/scan.hip -- the fused stage-1 + stage-2 "scan" kernel for gfx950.
 //
 // Textbook Gotoh recurrence over the whole (query x 5 kb segment) matrix of a
-// unit, as a systolic pipeline inside ONE wave64:
-//   * 128 virtual lanes = 64 lanes x 2 packed 16-bit halves; virtual lane v owns RP consecutive query
-//     rows (H and E of those rows live in VGPRs as packed u16 pairs) and processes column (step - v)
-//     at pipeline step `step`, so every dependency (diagonal H, vertical F, running column maximum,
-//     target code) arrives from virtual lane v-1 one step earlier: one DPP wave_shr + v_alignbit each.
-//   * all cell arithmetic is packed 16-bit VALU (v_pk_add_u16 / v_pk_max_i16 / v_pk_sub_u16 clamp):
-//     two DP cells per instruction, ~10 instructions per pair.  No MFMA: this is integer DP.
-//   * the int16 query profile (5 target codes x rows) is staged once per workgroup in LDS, laid out
-//     [code][lane][half][24 rows] with a 112-byte lane stride so the ds_read_b128 fetches (8 rows each)
-//     are bank-conflict free; the two halves of a lane sit on different columns, so each fetches its own
-//     code's rows and a v_perm_b32 merges them.
+// unit, as the systolic pipeline of systolic.h inside ONE wave64 (128 virtual lanes of RP rows each, packed
+// 16-bit VALU, ~10 instructions per pair of cells; no MFMA: this is integer DP):
+//   * the int16 query profile (5 target codes x rows) is staged once per workgroup in LDS;
 //   * the segment's target codes are read 64 columns at a time (one coalesced byte per lane) and fed to
 //     virtual lane 0 with v_readlane; per-column maxima leave virtual lane 127 as one u16 per step.
 //
@@ -36,52 +28,9 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "kernels.h"
-#include "dp_f16.h"
+#include "systolic.h"
 
 namespace fasim {
-
-typedef short v2s __attribute__((ext_vector_type(2)));
-typedef unsigned short v2u __attribute__((ext_vector_type(2)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ v2s as_s(v2u x) { return __builtin_bit_cast(v2s, x); }
-__device__ __forceinline__ v2u as_u(v2s x) { return __builtin_bit_cast(v2u, x); }
-__device__ __forceinline__ v2s s_from(int x) { return __builtin_bit_cast(v2s, x); }
-__device__ __forceinline__ int to_int(v2s x) { return __builtin_bit_cast(int, x); }
-__device__ __forceinline__ int to_int(v2u x) { return __builtin_bit_cast(int, x); }
-__device__ __forceinline__ v2u u_fromi(int x) { return __builtin_bit_cast(v2u, x); }
-
-// shift a packed pair down the virtual-lane pipeline: out.lo = x.hi of lane-1 (lane 0: inject), out.hi = x.lo
-__device__ __forceinline__ int vshift(int x, int inject_hi)
-{
-	const int up = __builtin_amdgcn_update_dpp(inject_hi, x, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-	return __builtin_amdgcn_alignbit(x, up, 16);
-}
-
-// Packed 16-bit helpers for the (rare) hazard branch, written as inline asm so that the compiler neither rewrites
-// them into per-half compares/selects nor hoists them into the main path of every step.
-__device__ __forceinline__ v2u pk_subs(v2u a, v2u b) { v2u r; asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ v2u pk_subs_k(v2u a, uint32_t k) { v2u r; asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "s"(k)); return r; }
-__device__ __forceinline__ v2u pk_ksubs(uint32_t k, v2u a) { v2u r; asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(r) : "s"(k), "v"(a)); return r; }
-__device__ __forceinline__ v2u pk_minu(v2u a, v2u b) { v2u r; asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ v2u pk_minu_k(v2u a, uint32_t k) { v2u r; asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "s"(k)); return r; }
-__device__ __forceinline__ v2u pk_maxu(v2u a, v2u b) { v2u r; asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-// x |= bits with input and output tied to ONE register: a value that the rare branch may modify then needs no copy at
-// the join with the common path (plain C would let the allocator put the two versions into different registers and
-// pay a v_mov per row in every step)
-__device__ __forceinline__ void or_in_place(int& x, int bits) { asm volatile("v_or_b32 %0, %0, %1" : "+v"(x) : "v"(bits)); }
-
-// acc = max(acc, x) on packed u16 with input and output tied to ONE register (as or_in_place: the running row maxima of the ROWS
-// variant cross the rare hazard branch and two copies of the step body, and must not be copied at any join)
-__device__ __forceinline__ void rowmax_in_place(int& acc, int x) { asm("v_pk_max_u16 %0, %0, %1" : "+v"(acc) : "v"(x)); }
-
-// the same shift with zeros entering virtual lane 0 (bound_ctrl: an out-of-range source lane reads as 0): no register has to
-// be preloaded with the value to inject
-__device__ __forceinline__ int vshift0(int x)
-{
-	const int up = __builtin_amdgcn_mov_dpp(x, 0x138 /* wave_shr:1 */, 0xf, 0xf, true);
-	return __builtin_amdgcn_alignbit(x, up, 16);
-}
 
 // two carried maxima (2 * value + taint each) -> two bytes min(value, 255)
 __device__ __forceinline__ uint16_t ublk_pack(v2u acc)
@@ -90,21 +39,7 @@ __device__ __forceinline__ uint16_t ublk_pack(v2u acc)
 	return (uint16_t)(v[0] | (v[1] << 8));
 }
 
-constexpr int SCAN_RS = 24;                 // storage rows per virtual lane in the LDS profile
-constexpr int SCAN_LANE_STRIDE = 112;       // bytes: 2 halves x 24 rows x 2 B + 16 B pad (bank-conflict-free b128)
-constexpr int SCAN_CODE_STRIDE = 64 * SCAN_LANE_STRIDE;   // 7168 B, a multiple of the 256-B bank row
 constexpr int SCAN_DEAD = -16384;           // score of rows beyond the padded query: can never be chosen
-constexpr int SCAN_DEAD_F16 = -4096;        // the same for the f16 variant, whose values stay below 2048 (far from -inf: nothing may produce inf or NaN)
-
-// a packed pair of f16 integers -> the packed pair of u16 integers (inline asm: used in rare branches only, see pk_subs; volatile:
-// the conversions of a whole H / E column must stay where they are written, one at a time, or their results all live at once
-// and the register allocator spills in the common path)
-__device__ __forceinline__ int hf_to_u16(int x)
-{
-	int r;
-	asm volatile("v_cvt_u16_f16_e32 %0, %1\n\tv_cvt_u16_f16_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1\n\ts_nop 0" : "=&v"(r) : "v"(x));
-	return r;
-}
 
 struct ScanArgs {
 	const uint8_t* tcodes;       // [unit][tstride]
@@ -146,15 +81,6 @@ struct ScanArgs {
 	uint16_t* rowmax16;
 };
 
-// rows owned by global virtual lane v (stripe-aligned layout): stripe s = v / vs gets its ceil(m/16) rows spread over
-// vs virtual lanes, the first (segLen % vs) of them one row longer
-__device__ __forceinline__ void lane_rows(int v, int seg_len, int vs, int* row0, int* rows)
-{
-	const int s = v / vs, j = v - s * vs, q = seg_len / vs, rem = seg_len - q * vs;
-	*rows = q + (j < rem ? 1 : 0);
-	*row0 = s * seg_len + j * q + (j < rem ? j : rem);
-}
-
 // score of target code t against the r-th row of global virtual lane v (doubled: bit 0 is the taint bit)
 __device__ __forceinline__ int scan_cell_score(const ScanArgs& a, int t, int v, int r)
 {
@@ -193,43 +119,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 	extern __shared__ __align__(16) uint8_t prof[];
 	const int lane = threadIdx.x & 63;
 
-	{
-		// ---- stage the int16 profile: prof[t][lane][half][r] -------------------------------------------
-		// stripe-aligned layout: the reference's stripe s = rows [s*segLen, (s+1)*segLen) is spread over `vs` virtual
-		// lanes, so every stripe boundary is a virtual-lane boundary; this launch stages the rows of its tile only
-		for (int idx = threadIdx.x; idx < 5 * 128 * SCAN_RS; idx += blockDim.x) {
-			const int r = idx % SCAN_RS;
-			const int v = (idx / SCAN_RS) % 128;
-			const int t = idx / (SCAN_RS * 128);
-			int sc = scan_cell_score(a, t, 128 * a.tile + v, r);
-			if (F16) sc = (int)(int16_t)f16_bits(sc == SCAN_DEAD ? SCAN_DEAD_F16 : sc);
-			*reinterpret_cast<int16_t*>(prof + t * SCAN_CODE_STRIDE + (v >> 1) * SCAN_LANE_STRIDE + (v & 1) * 48 + r * 2) = (int16_t)sc;
-		}
-	}
+	// ---- stage the int16 profile: this launch stages the rows of its tile only -------------------------
+	stage_profile<F16, SCAN_DEAD>(prof, 5, a.tile, [&](int t, int v, int r) { return scan_cell_score(a, t, v, r); });
 	__syncthreads();
 
-	// ---- per-lane constants ---------------------------------------------------------------------------
-	// fthr: a half whose virtual lane starts a stripe (v = vs*k, k >= 1) sees F[b] of the boundary row b directly as
-	//       its incoming F; Q2 needs F[b] >= 132 (doubled: > 263), other halves never flag.
-	// act : 0xFFFF where the half owns RP rows, 0 where it owns RP-1 (its last register row is transparent)
-	uint32_t fthr = 0xFFFFFFFFu, act = 0, startbits = 0;
-	for (int h = 0; h < 2; h++) {
-		const int v = 128 * a.tile + 2 * lane + h;        // global virtual lane
-		int row0, rows_v;
-		lane_rows(v, a.seg_len16, a.vs, &row0, &rows_v);
-		if (v % a.vs == 0 && v > 0) { fthr = (fthr & ~(0xFFFFu << (16 * h))) | ((F16 ? f16c(263u) : 263u) << (16 * h)); startbits |= 0xFFFFu << (16 * h); }
-		if (rows_v == RP) act |= 0xFFFFu << (16 * h);
-	}
-	const v2u fthr2 = __builtin_bit_cast(v2u, fthr);
-	const v2u actm = __builtin_bit_cast(v2u, act);
-	// stripe-start halves take the crossing F as the start of a propagation chain
-	const v2u startm = __builtin_bit_cast(v2u, startbits);
+	// ---- per-lane constants: Q2 needs F[b] >= 132 (doubled: > 263) ---------------------------------------
+	const StripeLane ln(128 * a.tile + 2 * lane, a.seg_len16, a.vs, RP, F16 ? f16c(263u) : 263u);
+	const uint32_t act = ln.act;
+	const v2u actm = ln.actm, startm = ln.startm;
 	// the refined test needs F to die inside one stripe (F <= 234 decays by 4 per row)
 	const bool lvl2 = a.seg_len16 >= 96 && !a.coarse;
-	const uint8_t* pl = prof + lane * SCAN_LANE_STRIDE;
-	// ROWS: first row of my two halves (where their row maxima go)
-	int rrow0[2] = { 0, 0 };
-	if constexpr (ROWS) { for (int h = 0; h < 2; h++) { int rows_v; lane_rows(128 * a.tile + 2 * lane + h, a.seg_len16, a.vs, &rrow0[h], &rows_v); } }
+	const uint8_t* pl = prof + lane * PROF_LANE_STRIDE;
 
 	for (;;) {
 		int w = 0;
@@ -318,98 +218,32 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 				recv_cm = vshift(cm, (int)(by << 16)); recv_fp = vshift(fpo, (int)(by & 0xffff0000u));
 			}
 			const int t_lo = tc & 0xff, t_hi = (tc >> 16) & 0xff;
-			const uint8_t* pa = pl + t_lo * SCAN_CODE_STRIDE;
-			const uint8_t* pb = pl + t_hi * SCAN_CODE_STRIDE + 48;
+			const ProfileRows<RP> rows(pl + t_lo * PROF_CODE_STRIDE, pl + t_hi * PROF_CODE_STRIDE + PROF_HALF);
 			const int hdiag0 = recv_h_last;           // H[i0-1][c-1]
 			recv_h_last = recv_h;
-			v2u f = __builtin_bit_cast(v2u, recv_f);
+			v2u f = u_from(recv_f);
 			v2u fm = (v2u){ 0, 0 };
-			if constexpr (DUMP) fm = __builtin_bit_cast(v2u, vshift0(fmbot)) & ~startm;      // the main pass starts every stripe with F = 0
-			v2s lmx[4] = { (v2s){ 0, 0 }, (v2s){ 0, 0 }, (v2s){ 0, 0 }, (v2s){ 0, 0 } };   // independent chains: no back-to-back dependent v_pk_max
-			constexpr int ROWS_PER_LOAD = 8;
-			constexpr int NLOAD = (RP + ROWS_PER_LOAD - 1) / ROWS_PER_LOAD;
-			v4i PA[NLOAD], PB[NLOAD];
-#pragma unroll
-			for (int g = 0; g < NLOAD; g++) {
-				PA[g] = *reinterpret_cast<const v4i*>(pa + 16 * g);
-				PB[g] = *reinterpret_cast<const v4i*>(pb + 16 * g);
-			}
-			auto score_of = [&](int r) -> int {
-				const int g = r / ROWS_PER_LOAD, k = r % ROWS_PER_LOAD;
-				return __builtin_amdgcn_perm(PB[g][k >> 1], PA[g][k >> 1], (k & 1) ? 0x07060302 : 0x05040100);
-			};
-			// Row r needs the OLD H[r-1] (diagonal) and writes the NEW H[r].  The add of row r+1 (old H[r] + its score) is
-			// issued before H[r] is overwritten, so the new value can go into the same register: no second copy of the H
-			// column and no register moves at the end of the step.
-			// (the sum is forced into the register of the score, which dies there: the compiler would otherwise add in place
-			//  over the old H, keep that register busy until the next row and have to park the new H somewhere else)
-			auto diag_plus_score = [](int hold, int sc) -> v2s { asm("v_pk_add_i16 %0, %1, %0 clamp" : "+v"(sc) : "v"(hold)); return s_from(sc); };
+			if constexpr (DUMP) fm = u_from(vshift0(fmbot)) & ~startm;      // the main pass starts every stripe with F = 0
+			// ROWS: the running maximum of the row takes the new H (DRAIN: of the halves on a real column)
+			auto row_hook = [&](int r, int h) __attribute__((always_inline)) { if constexpr (ROWS) rowmax_in_place(RM[r], DRAIN ? (h & rvalid) : h); };
 			v2s lmax;
 			if constexpr (F16) {
-				// the f16 row pair (dp_f16.h): 8.5 instructions where the integer one below takes 10
-				constexpr uint32_t KEXT = f16c2(2 * GAP_EXT), KOPEN = f16c2(2 * GAP_OPEN);
-				int ff = recv_f, lm0 = 0, lm1 = 0, hprev = 0;
-				int t = hf_diag_plus_score(hdiag0, score_of(0));
-#pragma unroll
-				for (int r = 0; r < RP; r++) {
-					int tnext = t;
-					if (r + 1 < RP) tnext = hf_diag_plus_score(H[r], score_of(r + 1));
-					const int h = hf_h(H[r], t, E[r], ff, tnext);
-					H[r] = h;
-					if constexpr (ROWS) rowmax_in_place(RM[r], DRAIN ? (h & rvalid) : h);
-					const int ho = hf_sub_k(h, KOPEN);
-					E[r] = hf_max_floor(hf_sub_k(E[r], KEXT), ho);
-					const int fnew = hf_max_floor(hf_sub_k(ff, KEXT), ho);
-					int hm = h;             // what the lane maximum sees of this row
-					if (r == RP - 1) {
-						ff = (fnew & (int)act) | (ff & ~(int)act);
-						hm = h & (int)act;
-						if (RP > 1) hbot = hm | (H[RP > 1 ? RP - 2 : 0] & ~(int)act);
-						else hbot = h;
-					} else ff = fnew;
-					// one max3 per two rows, two independent chains
-					if (r & 1) { if (r & 2) lm1 = hf_max3(lm1, hprev, hm); else lm0 = hf_max3(lm0, hprev, hm); }
-					hprev = hm;
-					t = tnext;
-				}
-				lmax = s_from((RP & 1) ? hf_max3(lm0, lm1, hprev) : hf_max_floor(lm0, lm1));
-				f = u_fromi(ff);
+				int ff = recv_f;
+				lmax = s_from(f16_row_pair(H, E, hbot, ff, hdiag0, rows, HfGapConst<f16c2(2 * GAP_OPEN), f16c2(2 * GAP_EXT)>(), act, row_hook));
+				f = u_from(ff);
 			} else {
-			v2s t = diag_plus_score(hdiag0, score_of(0));
-#pragma unroll
-			for (int r = 0; r < RP; r++) {
-				v2s tnext = t;
-				if (r + 1 < RP) tnext = diag_plus_score(H[r], score_of(r + 1));
-				if constexpr (DUMP) {
-					const v2s hm = __builtin_elementwise_max(__builtin_elementwise_max(t, s_from(Es[r])), as_s(fm));
-					const v2u hom = __builtin_elementwise_sub_sat(as_u(hm), (v2u){ 2 * GAP_OPEN, 2 * GAP_OPEN });
-					Es[r] = to_int(__builtin_elementwise_max(__builtin_elementwise_sub_sat(u_fromi(Es[r]), (v2u){ 2 * GAP_EXT, 2 * GAP_EXT }), hom));
-					const v2u fmn = __builtin_elementwise_max(__builtin_elementwise_sub_sat(fm, (v2u){ 2 * GAP_EXT, 2 * GAP_EXT }), hom);
-					fm = (r == RP - 1) ? ((fmn & actm) | (fm & ~actm)) : fmn;
-				}
-				v2s h = __builtin_elementwise_max(t, s_from(E[r]));
-				// h = max(h, f), written into the register that held the OLD H[r] (tied dummy operand; its last real use was
-				// the sum for row r+1 above): the H column stays where it is from step to step
-				// (tnext is passed as an unused operand only to order this after the sum above, which still reads the old H[r])
-				{ int hn; asm("v_pk_max_i16 %0, %2, %3" : "=v"(hn) : "0"(H[r]), "v"(to_int(h)), "v"(to_int(f)), "v"(to_int(tnext))); h = s_from(hn); }
-				H[r] = to_int(h);
-				if constexpr (ROWS) rowmax_in_place(RM[r], DRAIN ? (to_int(h) & rvalid) : to_int(h));
-				const v2u ho = __builtin_elementwise_sub_sat(as_u(h), (v2u){ 2 * GAP_OPEN, 2 * GAP_OPEN });
-				E[r] = to_int(__builtin_elementwise_max(__builtin_elementwise_sub_sat(u_fromi(E[r]), (v2u){ 2 * GAP_EXT, 2 * GAP_EXT }), ho));
-				const v2u fnew = __builtin_elementwise_max(__builtin_elementwise_sub_sat(f, (v2u){ 2 * GAP_EXT, 2 * GAP_EXT }), ho);
-				if (r == RP - 1) {
-					// a half that owns only RP-1 rows passes F and its bottom H through unchanged
-					f = (fnew & actm) | (f & ~actm);
-					lmx[r & 3] = __builtin_elementwise_max(lmx[r & 3], as_s(as_u(h) & actm));
-					if (RP > 1) hbot = (to_int(h) & (int)act) | (H[RP > 1 ? RP - 2 : 0] & ~(int)act);
-					else hbot = to_int(h);
-				} else {
-					f = fnew;
-					lmx[r & 3] = __builtin_elementwise_max(lmx[r & 3], h);
-				}
-				t = tnext;
-			}
-			lmax = __builtin_elementwise_max(__builtin_elementwise_max(lmx[0], lmx[1]), __builtin_elementwise_max(lmx[2], lmx[3]));
+				const v2u KOPEN = (v2u){ 2 * GAP_OPEN, 2 * GAP_OPEN }, KEXT = (v2u){ 2 * GAP_EXT, 2 * GAP_EXT };
+				// DUMP: the reference's own E and the F chain restarted at the top of each stripe
+				auto dump_hook = [&](int r, v2s t) __attribute__((always_inline)) {
+					if constexpr (DUMP) {
+						const v2s hm = __builtin_elementwise_max(__builtin_elementwise_max(t, s_from(Es[r])), as_s(fm));
+						const v2u hom = __builtin_elementwise_sub_sat(as_u(hm), KOPEN);
+						Es[r] = to_int(__builtin_elementwise_max(__builtin_elementwise_sub_sat(u_from(Es[r]), KEXT), hom));
+						const v2u fmn = __builtin_elementwise_max(__builtin_elementwise_sub_sat(fm, KEXT), hom);
+						fm = (r == RP - 1) ? ((fmn & actm) | (fm & ~actm)) : fmn;
+					}
+				};
+				lmax = int_row_pair<IntRowPolicy<true, false>>(H, E, hbot, f, hdiag0, rows, KOPEN, KEXT, act, row_hook, dump_hook);
 			}
 			// pin the reduction here: if the compiler sinks it below the hazard branch, the 22 pre-branch H values stay alive
 			// next to the (possibly tainted) ones and the common path pays a register copy per row at the join
@@ -418,78 +252,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 			if constexpr (!DUMP) ubacc = __builtin_elementwise_max(ubacc, as_u(lmax));
 			fbot = to_int(f);
 			if constexpr (DUMP) fmbot = to_int(fm);
-			// ---- Q2 hazard.  The reference's lazy-F loop leaves early (signed compare, sswNew.cpp:369) only while a
-			// stripe's propagated boundary value Fp = F[b] - 4j is >= 132 and the H it has just corrected is < 144
-			// (then vF >= 128 reads as negative, vH < 128 as positive).  From then on the rows of that stripe whose H is
-			// exactly the propagated value hold something smaller in the reference: those cells get the taint bit.
-			// fp = F crossing a stripe start, carried down the rows of the stripe; the row loop runs only in the (rare)
-			// steps where some lane holds fp >= 132 or an armed chain.  All values are doubled (see the header).
+			// ---- Q2 hazard (q2_rows of systolic.h; values doubled, taint in bit 0) -------------------------------
 			fpo = 0;
 			if (lvl2) {
-				// fpo halves: bits 0..14 = propagated value, bit 15 = "an early exit was possible at an earlier row"
-				// cheap superset first (3 VALU): a stripe-start lane receives F >= 132, or some lane receives a live chain;
-				// the exact condition is only evaluated behind it
-				// (F16: F arrives as f16 bits, and bits(F) > bits(263) iff F > 263; the chain state fpo travels as integers)
-				const v2u cand = pk_subs_k(__builtin_bit_cast(v2u, recv_f) & startm, F16 ? f16c2(263u) : 263u * 0x10001u) | __builtin_bit_cast(v2u, recv_fp);
-				bool enter = false;
-				v2u fp_in = (v2u){ 0, 0 }, arm_in = (v2u){ 0, 0 };
-				if (__builtin_amdgcn_ballot_w64(to_int(cand) != 0) != 0ull) {
-					const v2u fpraw = (u_fromi(F16 ? hf_to_u16(recv_f) : recv_f) & startm) | (__builtin_bit_cast(v2u, recv_fp) & ~startm);
-					fp_in = fpraw & (v2u){ 0x7fff, 0x7fff };
-					arm_in = (fpraw >> (v2u){ 15, 15 }) & ~startm;
-					const v2u hot = pk_subs_k(fp_in, 263u * 0x10001u) | pk_minu(arm_in, fp_in);
-					enter = __builtin_amdgcn_ballot_w64(to_int(hot) != 0) != 0ull;
-				}
-				if (enter) {
+				if (q2_rows<2, F16>(H, E, hbot, fpo, recv_f, recv_fp, startm, actm, act, (v2u){ 0xffff, 0xffff }))
 					first_enter = first_enter < step ? first_enter : step;
-					v2u fp = fp_in, arm = arm_in;
-					const v2u one = (v2u){ 1, 1 };
-					constexpr uint32_t K1 = 0x00010001u, K263 = 263u * 0x10001u, K288 = 288u * 0x10001u, KE = (2u * GAP_EXT) * 0x10001u,
-						KO = (2u * GAP_OPEN) * 0x10001u;
-					// pass 1 only READS H and E and collects the taint decisions as bit r of (dh, de)[r / 16]; pass 2 ORs them
-					// in.  Every read of the old value thus precedes the in-place update, so H[r] / E[r] stay in the registers
-					// the common path uses and the join needs no copies.
-					uint32_t dh[2] = { 0u, 0u }, de[2] = { 0u, 0u };
-#pragma unroll
-					for (int r = 0; r < RP; r++) {
-						// (F16: the branch works on integers as before; it sets a taint by adding 1.0 to a value that is still even)
-						const v2u hr = u_fromi(F16 ? hf_to_u16(H[r]) : H[r]), er = u_fromi(F16 ? hf_to_u16(E[r]) : E[r]);
-						const v2u ge = pk_minu_k(pk_subs_k(fp, K263), K1);                     // Fp >= 132
-						// H < 144; a tainted H may be smaller in the reference, so it counts as "< 144" too
-						v2u lt = pk_minu_k(pk_ksubs(K288, hr), K1) | (hr & one);
-						// the reference keeps a smaller H only where, after a possible early exit, H is exactly the propagated value
-						v2u eq = pk_ksubs(K1, pk_subs(hr, fp));                                // H <= Fp (H >= Fp always)
-						v2u nfp = pk_subs_k(fp, KE);
-						if (r == RP - 1) { lt &= actm; eq &= actm; nfp = (nfp & actm) | (fp & ~actm); }
-						const v2u dev = pk_minu(pk_minu(eq, fp), arm);                         // 0 / 1
-						// E of this row was just derived from the untainted H: taint it when it came from H (or ties with it)
-						const v2u ho = pk_subs_k(hr, KO);
-						const v2u efrom = pk_minu(pk_ksubs(K1, pk_subs(er, ho)), ho);
-						// (F16: only a value that is still even gets the 1.0; through the asm helper, so that the decision is taken here and
-						//  hr / er die with the row: left to the compiler, the and-not is fused into the OR tree below and keeps them alive)
-						dh[r >> 4] |= (uint32_t)to_int(F16 ? pk_subs(dev, hr & one) : dev) << (r & 15);
-						de[r >> 4] |= (uint32_t)to_int(F16 ? pk_subs(pk_minu(efrom, dev), er & one) : pk_minu(efrom, dev)) << (r & 15);
-						arm = pk_maxu(arm, pk_minu(ge, lt));
-						fp = nfp;
-					}
-#pragma unroll
-					for (int r = 0; r < RP; r++) {
-						if (F16) {
-							hf_add_in_place(H[r], (int)(((dh[r >> 4] >> (r & 15)) & K1) * F16_ONE));
-							hf_add_in_place(E[r], (int)(((de[r >> 4] >> (r & 15)) & K1) * F16_ONE));
-						} else {
-							or_in_place(H[r], (int)((dh[r >> 4] >> (r & 15)) & K1));
-							or_in_place(E[r], (int)((de[r >> 4] >> (r & 15)) & K1));
-						}
-					}
-					if (RP > 1) hbot = (H[RP - 1] & (int)act) | (H[RP > 1 ? RP - 2 : 0] & ~(int)act);
-					else hbot = H[0];
-					fpo = to_int(fp | (arm << (v2u){ 15, 15 }));
-				}
 			} else {
 				// short stripes (ceil(m/16) < 96): a chain may cross several stripes, the row analysis does not hold; any
 				// F[b] >= 132 sends the unit to the stripe-faithful kernel
-				hzacc |= __builtin_elementwise_sub_sat(__builtin_bit_cast(v2u, recv_f), fthr2);
+				hzacc |= __builtin_elementwise_sub_sat(u_from(recv_f), ln.fthr2);
 			}
 			if constexpr (DUMP) {
 				// my lo half has just finished column step - 2*lane, my hi half column step - 2*lane - 1
@@ -519,64 +290,37 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 			}
 		};
 		int step = DUMP ? item.step0 : 0;
-		if constexpr (ROWS) {
-			// The same loop twice: steps [0, n) only see real (or fill) columns, the rest goes through the masking copy of the body.
-			// (snapshot and block maxima as below, as lambdas: two copies of the loop share them)
-			// pipeline snapshot (every SCAN_SNAP_STEPS steps, all lanes at once: ~50 stores per 1024 steps of ~230 instructions)
-			auto take_snapshot = [&]() __attribute__((always_inline)) {
-				uint32_t* sp = a.snap + ((size_t)unit * a.snap_per_unit + (step / SCAN_SNAP_STEPS - 1)) * (SNAP_DW * 64) + lane;
-				// (F16: the checkpoint pass that reads them is the integer kernel)
-				auto sv = [](int x) -> uint32_t { return (uint32_t)(F16 ? hf_to_u16(x) : x); };
+		// pipeline snapshot (every SCAN_SNAP_STEPS steps, all lanes at once: ~50 stores per 1024 steps of ~230 instructions)
+		auto take_snapshot = [&]() __attribute__((always_inline)) {
+			uint32_t* sp = a.snap + ((size_t)unit * a.snap_per_unit + (step / SCAN_SNAP_STEPS - 1)) * (SNAP_DW * 64) + lane;
+			// (F16: the checkpoint pass that reads them is the integer kernel)
+			auto sv = [](int x) -> uint32_t { return (uint32_t)(F16 ? hf_to_u16(x) : x); };
 #pragma unroll
-				for (int r = 0; r < RP; r++) { sp[(2 * r) * 64] = sv(H[r]); sp[(2 * r + 1) * 64] = sv(E[r]); }
-				sp[(2 * RP) * 64] = (uint32_t)tc; sp[(2 * RP + 1) * 64] = sv(hbot); sp[(2 * RP + 2) * 64] = sv(fbot); sp[(2 * RP + 3) * 64] = sv(cm);
-				sp[(2 * RP + 4) * 64] = sv(recv_h_last); sp[(2 * RP + 5) * 64] = (uint32_t)fpo;
-			};
-			// (steps come in pairs: a block of SCAN_UBLK_STEPS steps ends after an odd step)
-			auto close_block = [&]() __attribute__((always_inline)) {
-				if (F16) ovf |= __builtin_amdgcn_ballot_w64(ubacc[0] >= F16_2048 || ubacc[1] >= F16_2048) != 0ull;
-				if (a.ublk) a.ublk[(((size_t)unit * a.ntiles + a.tile) * a.ublk_blocks + (step / SCAN_UBLK_STEPS)) * 64 + lane] = ublk_pack(F16 ? u_fromi(hf_to_u16(to_int(ubacc))) : ubacc);
-				ubacc = (v2u){ 0, 0 };
-			};
+			for (int r = 0; r < RP; r++) { sp[(2 * r) * 64] = sv(H[r]); sp[(2 * r + 1) * 64] = sv(E[r]); }
+			sp[(2 * RP) * 64] = (uint32_t)tc; sp[(2 * RP + 1) * 64] = sv(hbot); sp[(2 * RP + 2) * 64] = sv(fbot); sp[(2 * RP + 3) * 64] = sv(cm);
+			sp[(2 * RP + 4) * 64] = sv(recv_h_last); sp[(2 * RP + 5) * 64] = (uint32_t)fpo;
+		};
+		auto close_block = [&]() __attribute__((always_inline)) {
+			if (F16) ovf |= __builtin_amdgcn_ballot_w64(ubacc[0] >= F16_2048 || ubacc[1] >= F16_2048) != 0ull;
+			if (a.ublk) a.ublk[(((size_t)unit * a.ntiles + a.tile) * a.ublk_blocks + (step / SCAN_UBLK_STEPS)) * 64 + lane] = ublk_pack(F16 ? u_from(hf_to_u16(to_int(ubacc))) : ubacc);
+			ubacc = (v2u){ 0, 0 };
+		};
+		// steps come in pairs (a block of SCAN_UBLK_STEPS steps ends after an odd step); the checkpoint pass takes no snapshots and
+		// keeps no block maxima
 #define FASIM_SCAN_STEPS(LIMIT, DRAIN_C) \
-			for (; step + 1 < (LIMIT); step += 2) { \
-				if (a.snap && step != 0 && (step & (SCAN_SNAP_STEPS - 1)) == 0 && step / SCAN_SNAP_STEPS <= a.snap_per_unit) take_snapshot(); \
-				do_step(step, DRAIN_C); do_step(step + 1, DRAIN_C); \
-				if (((step + 1) & (SCAN_UBLK_STEPS - 1)) == SCAN_UBLK_STEPS - 1) close_block(); \
-			}
-			FASIM_SCAN_STEPS(n, std::false_type{})
-			FASIM_SCAN_STEPS(nsteps, std::true_type{})
+		for (; step + 1 < (LIMIT); step += 2) { \
+			if constexpr (!DUMP) { if (a.snap && step != 0 && (step & (SCAN_SNAP_STEPS - 1)) == 0 && step / SCAN_SNAP_STEPS <= a.snap_per_unit) take_snapshot(); } \
+			do_step(step, DRAIN_C); do_step(step + 1, DRAIN_C); \
+			if constexpr (!DUMP) { if (((step + 1) & (SCAN_UBLK_STEPS - 1)) == SCAN_UBLK_STEPS - 1) close_block(); } \
+		}
+		// ROWS: the same loop twice: steps [0, n) only see real (or fill) columns, the rest goes through the masking copy of the body
+		if constexpr (ROWS) FASIM_SCAN_STEPS(n, std::false_type{})
+		FASIM_SCAN_STEPS(nsteps, std::bool_constant<ROWS>{})
 #undef FASIM_SCAN_STEPS
-			if (step < nsteps) do_step(step, std::true_type{});
-		} else {
-		for (; step + 1 < nsteps; step += 2) {
-			if constexpr (!DUMP) {
-				// pipeline snapshot (every SCAN_SNAP_STEPS steps, all lanes at once: ~50 stores per 1024 steps of ~230 instructions)
-				if (a.snap && step != 0 && (step & (SCAN_SNAP_STEPS - 1)) == 0 && step / SCAN_SNAP_STEPS <= a.snap_per_unit) {
-					uint32_t* sp = a.snap + ((size_t)unit * a.snap_per_unit + (step / SCAN_SNAP_STEPS - 1)) * (SNAP_DW * 64) + lane;
-					// (F16: the checkpoint pass that reads them is the integer kernel)
-					auto sv = [](int x) -> uint32_t { return (uint32_t)(F16 ? hf_to_u16(x) : x); };
-#pragma unroll
-					for (int r = 0; r < RP; r++) { sp[(2 * r) * 64] = sv(H[r]); sp[(2 * r + 1) * 64] = sv(E[r]); }
-					sp[(2 * RP) * 64] = (uint32_t)tc; sp[(2 * RP + 1) * 64] = sv(hbot); sp[(2 * RP + 2) * 64] = sv(fbot); sp[(2 * RP + 3) * 64] = sv(cm);
-					sp[(2 * RP + 4) * 64] = sv(recv_h_last); sp[(2 * RP + 5) * 64] = (uint32_t)fpo;
-				}
-			}
-			do_step(step, std::false_type{}); do_step(step + 1, std::false_type{});
-			if constexpr (!DUMP) {
-				// (steps come in pairs: a block of SCAN_UBLK_STEPS steps ends after an odd step)
-				if (((step + 1) & (SCAN_UBLK_STEPS - 1)) == SCAN_UBLK_STEPS - 1) {
-					if (F16) ovf |= __builtin_amdgcn_ballot_w64(ubacc[0] >= F16_2048 || ubacc[1] >= F16_2048) != 0ull;
-					if (a.ublk) a.ublk[(((size_t)unit * a.ntiles + a.tile) * a.ublk_blocks + (step / SCAN_UBLK_STEPS)) * 64 + lane] = ublk_pack(F16 ? u_fromi(hf_to_u16(to_int(ubacc))) : ubacc);
-					ubacc = (v2u){ 0, 0 };
-				}
-			}
-		}
-		if (step < nsteps) do_step(step, std::false_type{});
-		}
+		if (step < nsteps) do_step(step, std::bool_constant<ROWS>{});
 		if constexpr (!DUMP) {
 			// the last, partial block (nsteps - 1 is its last step unless the block was just closed)
-			if (a.ublk && (nsteps & (SCAN_UBLK_STEPS - 1)) != 0) a.ublk[(((size_t)unit * a.ntiles + a.tile) * a.ublk_blocks + ((nsteps - 1) / SCAN_UBLK_STEPS)) * 64 + lane] = ublk_pack(F16 ? u_fromi(hf_to_u16(to_int(ubacc))) : ubacc);
+			if (a.ublk && (nsteps & (SCAN_UBLK_STEPS - 1)) != 0) a.ublk[(((size_t)unit * a.ntiles + a.tile) * a.ublk_blocks + ((nsteps - 1) / SCAN_UBLK_STEPS)) * 64 + lane] = ublk_pack(F16 ? u_from(hf_to_u16(to_int(ubacc))) : ubacc);
 		}
 		if constexpr (F16) {
 			// (a block that was just closed left ubacc = 0)
@@ -590,8 +334,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 #pragma unroll
 			for (int r = 0; r < RP; r++) {
 				const uint32_t x = (uint32_t)(F16 ? hf_to_u16(RM[r]) : RM[r]);
-				if (r < RP - 1 || (act & 0xFFFFu)) rp[rrow0[0] + r] = (uint16_t)x;
-				if (r < RP - 1 || (act >> 16)) rp[rrow0[1] + r] = (uint16_t)(x >> 16);
+				if (r < RP - 1 || (act & 0xFFFFu)) rp[ln.row0[0] + r] = (uint16_t)x;
+				if (r < RP - 1 || (act >> 16)) rp[ln.row0[1] + r] = (uint16_t)(x >> 16);
 			}
 		}
 		if (a.unit_hz && __builtin_amdgcn_ballot_w64(to_int(hzacc) != 0) != 0ull && lane == 0) atomicOr(a.unit_hz + unit, 1);
@@ -605,7 +349,7 @@ static hipError_t launch_scan_dump_t(const ScanArgs& a, hipStream_t st)
 	hipError_t err = hipMemsetAsync(a.counter, 0, sizeof(uint32_t), st);
 	if (err != hipSuccess) return err;
 	const long blocks = ((long)a.nwork + 3) / 4;              // one work item per wave
-	hipLaunchKernelGGL((k_scan<RP, true>), dim3((unsigned)blocks), dim3(256), (size_t)5 * SCAN_CODE_STRIDE, st, a);
+	hipLaunchKernelGGL((k_scan<RP, true>), dim3((unsigned)blocks), dim3(256), (size_t)5 * PROF_CODE_STRIDE, st, a);
 	return hipGetLastError();
 }
 
@@ -619,7 +363,7 @@ static hipError_t launch_scan_t(const ScanArgs& a, hipStream_t st)
 	// for this kernel to drain.
 	constexpr int WPB = 4, PER_WAVE = 2;                 // waves per workgroup, units per wave
 	const long blocks = ((long)a.nwork + WPB * PER_WAVE - 1) / (WPB * PER_WAVE);
-	hipLaunchKernelGGL((k_scan<RP, false, F16, ROWS>), dim3((unsigned)blocks), dim3(256), (size_t)5 * SCAN_CODE_STRIDE, st, a);
+	hipLaunchKernelGGL((k_scan<RP, false, F16, ROWS>), dim3((unsigned)blocks), dim3(256), (size_t)5 * PROF_CODE_STRIDE, st, a);
 	return hipGetLastError();
 }
 

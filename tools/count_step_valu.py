@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Count the VALU instructions of the step loop of a systolic DP kernel (k_scan, k_align_fwd) in gfx950 assembly.
+"""Count the VALU instructions of the step loop of a systolic DP kernel (k_scan of scan.hip, k_align_fwd of align.hip,
+k_align_band of band.hip with --rows 24; the step body they share is csrc/systolic.h) in gfx950 assembly.
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math --cuda-device-only -S -o scan.s scan.hip
-    tools/count_step_valu.py scan.s _ZN5fasim6k_scanILi22ELb0ELb1EEEvNS_8ScanArgsE [--rows 22] [--blocks]
+    tools/count_step_valu.py scan.s _ZN5fasim6k_scanILi22ELb0ELb1ELb0EEEvNS_8ScanArgsE [--rows 22] [--blocks]
 
 The step loop is the innermost loop (backward branch) that holds at least `rows` v_perm_b32 (one per DP row and step).  Its
 basic blocks are split into the common path and the rare ones: a block is rare when it holds an instruction that only the
