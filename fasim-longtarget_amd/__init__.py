@@ -92,10 +92,26 @@ SIM_K = 50
 MAX_QUERY = 92256
 # FASIM_MAX_OLIGO (include/fasim_hip.h): longest oligo of a panel (Engine.scan_oligos)
 MAX_OLIGO = 112
+# FASIM_MAX_ALLELE / FASIM_MAX_FLANK (include/fasim_hip.h): longest allele and widest flank of a scored variant (Engine.score_variants)
+MAX_ALLELE = 1024
+MAX_FLANK = 2048
 
 
 class _Region(C.Structure):
     _fields_ = [("line", C.c_int64), ("start", C.c_int64), ("end", C.c_int64), ("chrom", C.c_char_p), ("name", C.c_char_p)]
+
+
+class _Variant(C.Structure):
+    _fields_ = [("line", C.c_int64), ("pos", C.c_int64), ("rec", C.c_int32), ("ref_len", C.c_int32), ("alt_len", C.c_int32),
+                ("chrom", C.c_char_p), ("id", C.c_char_p), ("ref", C.c_char_p), ("alt", C.c_char_p)]
+
+
+class _VariantScore(C.Structure):
+    _fields_ = [("value", (C.c_int32 * 4) * 2), ("enc", (C.c_int32 * 4) * 2), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class _VariantStats(C.Structure):
+    _fields_ = [("problems", C.c_int64), ("cells", C.c_int64), ("kernel_s", C.c_double), ("total_s", C.c_double)]
 
 
 class _Result(C.Structure):
@@ -163,6 +179,7 @@ EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_e
            "fasim_scan_oligos", "fasim_oligo_panel_tsv", "fasim_scan_oligos_aligned",
            "fasim_scan_records_hist", "fasim_scan_oligos_hist", "fasim_hist_merge", "fasim_hist_free", "fasim_shuffle_query",
            "fasim_hist_threshold", "fasim_hist_tsv",
+           "fasim_read_vcf", "fasim_score_variants", "fasim_variants_tsv",
            # the reference's own ssw.h ABI (include/ssw.h)
            "ssw_init", "init_destroy", "ssw_pre_align", "ssw_align", "align_destroy", "encoded_ops"]
 
@@ -303,6 +320,12 @@ def lib():
     L.fasim_hist_threshold.restype = C.c_int32
     L.fasim_hist_tsv.argtypes = [C.POINTER(_Hist), C.POINTER(C.POINTER(_Hist)), C.c_int32, C.c_uint64, C.c_double, C.c_char_p,
                                  C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.fasim_read_vcf.argtypes = [C.c_char_p, C.POINTER(C.POINTER(_Variant)), C.POINTER(C.c_int64)]
+    L.fasim_score_variants.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
+                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.POINTER(_Variant), C.c_int64, C.c_int32,
+                                       C.POINTER(Params), C.POINTER(_VariantScore), C.POINTER(_VariantStats)]
+    L.fasim_variants_tsv.argtypes = [C.POINTER(_Variant), C.POINTER(_VariantScore), C.c_int64, C.c_int32, C.c_char_p,
+                                     C.POINTER(C.c_uint8), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     _lib = L
     return L
 
@@ -1227,9 +1250,14 @@ class Engine:
         return [[nodes[k * SIM_K + x].astuple() for x in range(counts[k])] for k in range(n)]
 
     # --- the LongTarget() body ----------------------------------------------------------------------
+    def resident_len(self) -> int:
+        """Length of the record set last given to load_dna() (0: none)."""
+        return getattr(self, "_resident_len", 0)
+
     def load_dna(self, dna: bytes):
         """Upload one DNA record and keep it resident in HBM; scan(None, ...) then scans it without H2D copies."""
         self._check(self._L.fasim_load_dna(self._h, dna, len(dna)))
+        self._resident_len = len(dna)
 
     @staticmethod
     def _stats_dict(st) -> dict:
@@ -1584,6 +1612,52 @@ class Engine:
         self.last_totals = [self._stats_dict(totals[q]) for q in range(nq)]
         return [Hist(_native=hs[q]) for q in range(nq)]
 
+    def score_variants(self, variants, dnas, p: Params | None = None, flank: int = 300, queries=None):
+        """The triplex potential through variants (fasim_score_variants): `(values, encs, flags)`, int32 arrays of shape
+        (nq, nvar, 2, 4), the same, and (nq, nvar): per query, variant, allele (0 REF, 1 ALT) and strand class (TRACK_CLASSES) the best
+        score of a local alignment through the allele within `flank` bases of it, the smallest encoding that attains it (-1: value 0),
+        and bit 0 `clipped` (an alignment of the variant's largest value may continue past the flank).  `variants`: Variant tuples
+        (read_vcf()), pos 0-based within record `rec` of `dnas` (a list of records, one bytes object, or None with the whole resident
+        buffer as record 0); an unusable variant gets zeros and -1.  queries None: the lncRNA last given to set_query() -- the
+        engine's own query is neither used nor changed by the call.  REF is not compared with the record.  Counters of the call:
+        `self.last_variant_stats`."""
+        import numpy as np
+        p = p or default_params()
+        if queries is None:
+            if self.rna is None:
+                raise FasimError("score_variants: no queries given and no query set", E_ARG)
+            queries = [self.rna]
+        queries = [bytes(x) for x in queries]
+        nq = len(queries)
+        if isinstance(dnas, (bytes, bytearray)):
+            dnas = [bytes(dnas)]
+        if dnas is None:
+            blob, nrec = None, 1
+            offs = (C.c_int64 * 1)(0)
+            lens = (C.c_int64 * 1)(self.resident_len())
+        else:
+            blob = b"".join(dnas)
+            nrec = len(dnas)
+            offs = (C.c_int64 * max(1, nrec))()
+            lens = (C.c_int64 * max(1, nrec))()
+            o = 0
+            for i, d in enumerate(dnas):
+                offs[i], lens[i] = o, len(d)
+                o += len(d)
+        arr = (C.c_char_p * max(1, nq))(*queries)
+        qlens = (C.c_int32 * max(1, nq))(*[len(x) for x in queries])
+        vs, _keep = _variants_to_c(variants)
+        nvar = len(variants)
+        out = (_VariantScore * max(1, nq * nvar))()
+        st = _VariantStats()
+        self._check(self._L.fasim_score_variants(self._h, arr, qlens, nq, blob, offs, lens, nrec, vs, nvar, flank, C.byref(p), out, C.byref(st)))
+        self.last_variant_stats = dict(problems=st.problems, cells=st.cells, kernel_s=st.kernel_s, total_s=st.total_s)
+        flat = np.frombuffer(out, dtype=np.int32).reshape(max(1, nq * nvar), 18)[:nq * nvar]
+        values = flat[:, 0:8].reshape(nq, nvar, 2, 4).copy()
+        encs = flat[:, 8:16].reshape(nq, nvar, 2, 4).copy()
+        flags = flat[:, 16].reshape(nq, nvar).copy()
+        return values, encs, flags
+
     def _records_track(self, blob, offs, lens, nrec, p, rnas, bin, records, seg_first, seg_count):
         nq = 0 if rnas is None else len(rnas)
         nqo = max(1, nq)
@@ -1806,6 +1880,73 @@ def read_bed(path) -> list:
         return [Region(out[k].line, out[k].chrom.decode(), out[k].start, out[k].end, out[k].name.decode()) for k in range(n.value)]
     finally:
         L.fasim_free(out)
+
+
+class Variant(NamedTuple):
+    """One (VCF line, ALT allele) pair (fasim_read_vcf): 1-based line, chrom, 0-based pos of REF's first letter, id, ref, alt
+    (upper case), the record it lies in (read_vcf: 0) and whether its alleles can be scored (1 .. MAX_ALLELE letters of ACGTN)."""
+    line: int
+    chrom: str
+    pos: int
+    id: str
+    ref: str
+    alt: str
+    rec: int = 0
+    usable: bool = True
+
+
+def read_vcf(path) -> list:
+    """The variants of a VCF file as `fasim --variants` reads them, one Variant per ALT allele; a refused file raises FasimError
+    with code E_ARG and the line number in the message."""
+    L = lib()
+    out = C.POINTER(_Variant)()
+    n = C.c_int64()
+    rc = L.fasim_read_vcf(os.fsencode(path), C.byref(out), C.byref(n))
+    if rc != 0:
+        raise FasimError(L.fasim_last_error(None).decode(), rc)
+    try:
+        return [Variant(out[k].line, out[k].chrom.decode(), out[k].pos, out[k].id.decode(), out[k].ref.decode(), out[k].alt.decode(),
+                        out[k].rec, out[k].alt_len >= 0) for k in range(n.value)]
+    finally:
+        L.fasim_free(out)
+
+
+def _variants_to_c(variants):
+    n = len(variants)
+    vs = (_Variant * max(1, n))()
+    keep = []
+    for k, v in enumerate(variants):
+        strs = [x.encode() if isinstance(x, str) else bytes(x) for x in (v.chrom, v.id, v.ref, v.alt)]
+        keep.append(strs)
+        vs[k].line, vs[k].pos, vs[k].rec = v.line, v.pos, v.rec
+        vs[k].ref_len, vs[k].alt_len = len(strs[2]), (len(strs[3]) if v.usable else -1)
+        vs[k].chrom, vs[k].id, vs[k].ref, vs[k].alt = strs
+    return vs, keep
+
+
+def variants_tsv(variants, values, encs, flags, flank: int, rna_name: str, matched=None) -> bytes:
+    """The bytes of `fasim --variants`' table for one query (fasim_variants_tsv): values and encs (nvar, 2, 4), flags (nvar) as
+    Engine.score_variants() returns them per query; matched[k] false (or an unusable variant): an NA line."""
+    import numpy as np
+    L = lib()
+    n = len(variants)
+    vs, _keep = _variants_to_c(variants)
+    values = np.asarray(values, dtype=np.int32).reshape(n, 8)
+    encs = np.asarray(encs, dtype=np.int32).reshape(n, 8)
+    flags = np.asarray(flags, dtype=np.int32).reshape(n)
+    sc = (_VariantScore * max(1, n))()
+    flat = np.frombuffer(sc, dtype=np.int32).reshape(max(1, n), 18)
+    flat[:n, 0:8], flat[:n, 8:16], flat[:n, 16] = values, encs, flags
+    mt = None if matched is None else (C.c_uint8 * max(1, n))(*[1 if x else 0 for x in matched])
+    text = C.c_void_p()
+    ln = C.c_int64()
+    rc = L.fasim_variants_tsv(vs, sc, n, flank, rna_name.encode(), mt, C.byref(text), C.byref(ln))
+    if rc != 0:
+        raise FasimError(f"fasim_variants_tsv failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
+    try:
+        return C.string_at(text, ln.value)
+    finally:
+        L.fasim_free(text)
 
 
 def synth_dna(n: int, seed: int) -> bytes:

@@ -137,6 +137,7 @@ struct fasim_engine {
 	DevBuf sites_counts, sites_offsets, sites_runs, sites_sat;   // fasim_scan_records_sites only: k_sites' run counts per (slice, class), their prefix sum, the runs and saturation flags of the batch
 	DevBuf sa_q, sa_tcodes, sa_probs, sa_ends, sa_rows, sa_items, sa_dirs, sa_cigar, sa_ciglen;   // fasim_scan_records_sites_aligned only: query codes, the chunk's units, problems, end cells, row state of long queries, path items, direction bytes, CIGARs
 	DevBuf hist, hist_zone, hist_zones, hist_sat;   // fasim_scan_records_hist only: k_hist's counters of the batch, its zone bounds per segment, the zone values and saturation flags
+	DevBuf vr_q, vr_dna, vr_alt, vr_wins, vr_probs, vr_tcodes, vr_rows, vr_touch, vr_out;   // fasim_score_variants only: query codes, streamed window letters, ALT letters, windows, problems, target codes, row state of long queries, k_touch's words, k_touch_reduce's words
 	int opt_sim_lds = -1;                        // option "sim_lds": -F re-sweeps always on the L2 variant (0) / the LDS variant where the state fits (1); -1 = by the units in flight
 	int opt_site_short = -1;                     // option "site_short": 1 = the hits of oligo sites end on k_site_ends_short (default), 0 = on k_site_ends (-1 = default / environment FASIM_SITE_SHORT)
 	int opt_site_chunk = 0;                      // option "site_chunk": problems per chunk of the hits phase where lower than the phase's own limit (0 = that limit)

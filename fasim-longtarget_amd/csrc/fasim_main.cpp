@@ -61,6 +61,12 @@
 //                           <O>/<lnc>-<f1 stem>.sites-<V>.aligned.tsv, the record's name as a last column), a `# fasim site hits` line,
 //                           a header line, then one line per site in the order of the sites file: chrom tts_start tts_end class value
 //                           strand rule tfo_start tfo_end nt identity stability cigar TFO TTS.  Without --sites: status 2
+//     --variants FILE.vcf   every (VCF line, ALT allele) scored by the triplex potential through it, for REF and for ALT, within
+//                           --variant-flank F (default 300, at most 2048) bases: one table per lncRNA,
+//                           <O>/<lnc>-<f1 minus 3 chars>.variants.tsv, and nothing else (fasim_score_variants).
+//                           Exit status 2, nothing written: a malformed VCF, --variant-flank outside [0, 2048] or without
+//                           --variants, --variants with --regions, --all-records, --accumulate-records, -F, --track, --screen,
+//                           --tfo-profile, --sites, --oligos, --potential-hist or --devices
 //     --screen              with --regions or --all-records: one table per lncRNA, <O>/<lnc>-<f1 stem>.screen.tsv, one line per
 //                           interval (BED order) or record: per strand class the peak of its potential, where it lies (0-based
 //                           genome coordinate) and the rule of the encoding that attains it (fasim_screen_tsv, DESIGN.md section
@@ -536,10 +542,108 @@ struct TailPool {
 	~TailPool() { { std::lock_guard<std::mutex> lk(mu); stop = true; } cv.notify_all(); for (auto& t : th) t.join(); }
 };
 
+// --variants: every (VCF line, ALT allele) scored by the triplex potential through it (fasim_score_variants).
+// The genome is streamed record by record; a variant goes to the first record of its chromosome (file order, the header rules of
+// --regions) that contains [POS - 1, POS - 1 + len(REF)), and the record's letters there must equal REF.  Per lncRNA one table,
+// <O>/<lnc>-<f1 minus 3 chars>.variants.tsv.  Exit status 2: a malformed VCF (nothing written, no device opened); 1: variants that no
+// record contains, whose REF differs or whose alleles cannot be scored (NA lines; listed on stderr).
+static int run_variants(const std::string& vcf_path, int flank, const std::string& f1, const std::string& f2, const std::string& outdir, int device,
+	bool upper, const fasim_params& p)
+{
+	fasim_variant* vars = nullptr; int64_t nvar = 0;
+	if (fasim_read_vcf(vcf_path.c_str(), &vars, &nvar) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 2; }
+	std::unique_ptr<fasim_variant, void (*)(void*)> owner(vars, fasim_free);
+	std::vector<Rna> rnas;
+	DnaReader reader;
+	reader.upper = upper;
+	if (!reader.open(f1)) { fprintf(stderr, "fasim: cannot read DNA file %s\n", f1.c_str()); return 1; }
+	if (!read_rnas(f2, rnas)) { fprintf(stderr, "fasim: cannot read RNA file %s\n", f2.c_str()); return 1; }
+	for (const Rna& r : rnas) if (r.seq.empty() || r.seq.size() > (size_t)FASIM_MAX_QUERY) {
+		fprintf(stderr, "fasim: RNA record '%s' in %s has %zu nt: a query has 1 to %d nt\n", r.name.c_str(), f2.c_str(), r.seq.size(), FASIM_MAX_QUERY);
+		return 1;
+	}
+	std::cout << "Searching triplexes using Fasim" << std::endl;
+	for (const Rna& r : rnas) std::cout << r.name << std::endl;
+	const int nq = (int)rnas.size();
+	std::vector<const char*> qp((size_t)nq); std::vector<int32_t> ql((size_t)nq);
+	for (int q = 0; q < nq; q++) { qp[(size_t)q] = rnas[(size_t)q].seq.data(); ql[(size_t)q] = (int32_t)rnas[(size_t)q].seq.size(); }
+	// state of an entry: 0 not met, 1 scored, 2 REF differs, 3 unusable alleles
+	std::vector<uint8_t> state((size_t)nvar, 0);
+	std::vector<std::vector<fasim_variant_score>> scores((size_t)nq, std::vector<fasim_variant_score>((size_t)nvar));
+	std::map<std::string, std::multimap<int64_t, int64_t>> todo;
+	std::set<std::string> chroms_seen;
+	for (int64_t k = 0; k < nvar; k++) {
+		if (vars[k].alt_len < 0) state[(size_t)k] = 3;
+		else todo[vars[k].chrom].emplace(vars[k].pos, k);
+	}
+	fasim_engine* eng = nullptr;
+	DnaRecord rec;
+	size_t nrec = 0;
+	while (reader.next(rec)) {
+		std::string chrom = rec.chr; int64_t rs = (int64_t)rec.start - 1;
+		const size_t w0 = rec.header.find_first_not_of("> \t\r");
+		const std::string word = w0 == std::string::npos ? std::string() : rec.header.substr(w0, rec.header.find_first_of(" \t\r", w0) - w0);
+		if (word.find('|') == std::string::npos) { chrom = word; rs = 0; }
+		nrec++;
+		chroms_seen.insert(chrom);
+		auto it = todo.find(chrom);
+		if (it == todo.end()) continue;
+		const int64_t re = rs + (int64_t)rec.seq.size();
+		std::vector<int64_t> mine;
+		for (auto j = it->second.lower_bound(rs); j != it->second.end() && j->first < re; ) {
+			const fasim_variant& x = vars[j->second];
+			if (x.pos + x.ref_len > re) { ++j; continue; }
+			if (memcmp(rec.seq.data() + (x.pos - rs), x.ref, (size_t)x.ref_len) != 0) state[(size_t)j->second] = 2;
+			else mine.push_back(j->second);
+			j = it->second.erase(j);
+		}
+		if (mine.empty()) continue;
+		std::sort(mine.begin(), mine.end());
+		std::vector<fasim_variant> loc(mine.size());
+		for (size_t k = 0; k < mine.size(); k++) { loc[k] = vars[mine[k]]; loc[k].pos -= rs; loc[k].rec = 0; }
+		if (!eng && fasim_engine_create(device, &eng) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
+		const int64_t off0 = 0, len0 = (int64_t)rec.seq.size();
+		std::vector<fasim_variant_score> got((size_t)nq * mine.size());
+		if (fasim_score_variants(eng, qp.data(), ql.data(), nq, rec.seq.data(), &off0, &len0, 1, loc.data(), (int64_t)loc.size(), flank, &p, got.data(), nullptr) != FASIM_OK) {
+			fprintf(stderr, "fasim: %s\n", fasim_last_error(eng));
+			fasim_engine_destroy(eng);
+			return 1;
+		}
+		for (int q = 0; q < nq; q++) for (size_t k = 0; k < mine.size(); k++) scores[(size_t)q][(size_t)mine[k]] = got[(size_t)q * mine.size() + k];
+		for (int64_t k : mine) state[(size_t)k] = 1;
+	}
+	if (eng) fasim_engine_destroy(eng);
+	if (nrec == 0) { fprintf(stderr, "fasim: no record in DNA file %s\n", f1.c_str()); return 1; }
+	const std::string base = f1.substr(0, f1.size() >= 3 ? f1.size() - 3 : 0);
+	std::vector<uint8_t> matched((size_t)nvar);
+	for (int64_t k = 0; k < nvar; k++) matched[(size_t)k] = state[(size_t)k] == 1;
+	int bad = 0;
+	for (int q = 0; q < nq; q++) {
+		char* text = nullptr; int64_t len = 0;
+		if (fasim_variants_tsv(vars, scores[(size_t)q].data(), nvar, flank, rnas[(size_t)q].name.c_str(), matched.data(), &text, &len) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
+		bad |= write_file(outdir + "/" + rnas[(size_t)q].name + "-" + base + ".variants.tsv", text, len);
+		fasim_free(text);
+	}
+	if (bad) return 1;
+	size_t lost = 0;
+	for (int64_t k = 0; k < nvar; k++) {
+		if (state[(size_t)k] == 1) continue;
+		const fasim_variant& x = vars[k];
+		const char* why = state[(size_t)k] == 3 ? "its alleles cannot be scored (1 to 1024 letters of ACGTN each)" : state[(size_t)k] == 2 ? "REF differs from the DNA record"
+			: chroms_seen.count(x.chrom) ? "no DNA record of its chromosome contains it" : "no DNA record of its chromosome";
+		if (lost++ < 20) fprintf(stderr, "fasim: VCF line %lld %s:%lld: %s\n", (long long)x.line, x.chrom, (long long)(x.pos + 1), why);
+	}
+	if (lost > 20) fprintf(stderr, "fasim: ... and %zu more\n", lost - 20);
+	if (lost) { fprintf(stderr, "fasim: %zu of %lld variants were not scored (NA in the table)\n", lost, (long long)nvar); return 1; }
+	std::cout << "finished normally" << std::endl;
+	return 0;
+}
+
 int main(int argc, char* const* argv)
 {
 	fasim_params p; fasim_params_default(&p);
-	std::string f1 = "./", f2 = "./", outdir = "./", bed_path;
+	std::string f1 = "./", f2 = "./", outdir = "./", bed_path, vcf_path;
+	bool devices_given = false, flank_given = false; int variant_flank = 300;
 	std::vector<int> devices(1, 0);
 	bool stats = false, all_records = false, accumulate = false, upper = false, track = false, screen = false, screen_only = false;
 	bool sites = false, sites_gap_given = false, hist_arg_given = false, hist_arg_bad = false;
@@ -558,7 +662,8 @@ int main(int argc, char* const* argv)
 		{ "tfo-profile", no_argument, NULL, 1014 }, { "tfo-profile-only", no_argument, NULL, 1015 },
 		{ "sites", required_argument, NULL, 1016 }, { "sites-gap", required_argument, NULL, 1017 }, { "sites-only", no_argument, NULL, 1018 }, { "sites-align", no_argument, NULL, 1019 }, { "oligos", no_argument, NULL, 1020 }, { "oligo-hits", no_argument, NULL, 1026 },
 		{ "potential-hist", no_argument, NULL, 1021 }, { "hist-controls", required_argument, NULL, 1022 }, { "hist-seed", required_argument, NULL, 1023 },
-		{ "hist-fdr", required_argument, NULL, 1024 }, { "potential-hist-only", no_argument, NULL, 1025 }, { 0, 0, 0, 0 } };
+		{ "hist-fdr", required_argument, NULL, 1024 }, { "potential-hist-only", no_argument, NULL, 1025 },
+		{ "variants", required_argument, NULL, 1027 }, { "variant-flank", required_argument, NULL, 1028 }, { 0, 0, 0, 0 } };
 	int opt;
 	while ((opt = getopt_long_only(argc, argv, optstring, lo, NULL)) != -1) {
 		switch (opt) {
@@ -584,7 +689,9 @@ int main(int argc, char* const* argv)
 		case 1001: devices.assign(1, atoi(optarg)); break;
 		case 1002: stats = true; break;
 		case 1003: all_records = true; break;
-		case 1004: devices = parse_devices(optarg); if (devices.empty()) { fprintf(stderr, "fasim: bad --devices list\n"); return 2; } break;
+		case 1027: vcf_path = optarg; break;
+		case 1028: flank_given = true; variant_flank = strict_int(optarg, -1); break;
+		case 1004: devices_given = true; devices = parse_devices(optarg); if (devices.empty()) { fprintf(stderr, "fasim: bad --devices list\n"); return 2; } break;
 		case 1005: accumulate = true; break;
 		case 1006: upper = true; break;
 		case 1007: tail_flags |= FASIM_TAIL_CLAMP_CLUSTER; break;
@@ -607,7 +714,7 @@ int main(int argc, char* const* argv)
 		case 1023: { hist_arg_given = true; char* end = nullptr; errno = 0; trk.hist_seed = strtoull(optarg, &end, 10); if (end == optarg || *end != '\0' || errno == ERANGE || optarg[0] == '-') hist_arg_bad = true; break; }
 		case 1024: { hist_arg_given = true; char* end = nullptr; trk.hist_fdr = strtod(optarg, &end); if (end == optarg || *end != '\0') trk.hist_fdr = -1.0; break; }
 		case 1025: trk.hist_only = true; break;
-		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only] [--sites-align] [--oligos [--oligo-hits]]] [--potential-hist [--hist-controls K] [--hist-seed S] [--hist-fdr Q] [--potential-hist-only]]\n"); return 2;
+		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only] [--sites-align] [--oligos [--oligo-hits]]] [--potential-hist [--hist-controls K] [--hist-seed S] [--hist-fdr Q] [--potential-hist-only]] [--variants FILE.vcf [--variant-flank F]]\n"); return 2;
 		}
 	}
 	if (all_records && accumulate) { fprintf(stderr, "fasim: --all-records and --accumulate-records exclude each other\n"); return 2; }
@@ -634,6 +741,14 @@ int main(int argc, char* const* argv)
 	if (trk.oligos && !sites && !trk.hist) { fprintf(stderr, "fasim: --oligos needs --sites V or --potential-hist\n"); return 2; }
 	if (trk.oligos && (trk.sites_align || trk.tfo)) { fprintf(stderr, "fasim: --oligos is not available with --sites-align, -F, --track, --screen, --tfo-profile or --accumulate-records\n"); return 2; }
 	if (trk.oligo_hits && (!trk.oligos || !sites || trk.hist)) { fprintf(stderr, "fasim: --oligo-hits needs --oligos --sites V (and is not available with --potential-hist)\n"); return 2; }
+	const bool variants = !vcf_path.empty();
+	if (flank_given && !variants) { fprintf(stderr, "fasim: --variant-flank needs --variants FILE.vcf\n"); return 2; }
+	if (variants && (variant_flank < 0 || variant_flank > FASIM_MAX_FLANK)) { fprintf(stderr, "fasim: --variant-flank needs an integer in [0, %d]\n", FASIM_MAX_FLANK); return 2; }
+	if (variants && (regions || all_records || accumulate || p.classicSim || track || screen || trk.tfo || sites || trk.oligos || trk.hist || devices_given)) {
+		fprintf(stderr, "fasim: --variants is not available with --regions, --all-records, --accumulate-records, -F, --track, --screen, --tfo-profile, --sites, --oligos, --potential-hist or --devices\n");
+		return 2;
+	}
+	if (variants) return run_variants(vcf_path, variant_flank, f1, f2, outdir, devices[0], upper, p);
 	if (trk.oligos) trk.sites_only = true;      // a panel has no triplex records: the sites files and the panel table are all it writes
 	if (trk.oligos && trk.hist) trk.hist_only = true;      // (or the oligos' histograms)
 	if (!sites) trk.sites = 0;

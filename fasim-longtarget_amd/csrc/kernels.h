@@ -223,6 +223,31 @@ hipError_t launch_site_path(const SitePathLaunch& L, hipStream_t st);
 int site_short_warm(int m);             // columns before (jp & ~15) at which pass (i) starts from zeros: W(m) + 16 rounded up to 16
 hipError_t launch_site_ends_short(const SiteEndsLaunch& L, hipStream_t st);      // hipErrorInvalidValue: a query the kernel does not take
 
+// ---- variant.hip: the best local alignment through a variant, per allele window and encoding ------------
+constexpr int TOUCH_MAX_COLS = 5120;            // columns of an allele window: FASIM_MAX_ALLELE + 2 * FASIM_MAX_FLANK (the 16-bit row state holds 2 * 5 * 5 120 + 1)
+constexpr int TOUCH_LDS_ROWS = 8192;            // query rows whose DP state (7 bytes per row) k_touch keeps in LDS
+// One allele window in record letters: `pre` letters from dna + src, then the allele (alt_len < 0: the ref_len letters that follow in
+// the record, else alt_len letters from alts + alt_off), then `post` letters from dna + src + pre + ref_len
+struct VarWindow { int64_t src; int32_t pre, ref_len, post, alt_off, alt_len, pad; };
+// One problem: window `win` under encoding `enc`; its n target codes at tcodes + tbase, the allele's columns [v0, v1) (mirrored for an
+// odd encoding, as the codes are), edge bit 0 / 1: the unit's first / last column is an end that the flank cut
+struct TouchProb { int64_t tbase; int32_t n, v0, v1, edge, win, enc; };
+struct VarEncodeLaunch { const uint8_t* dna; const uint8_t* alts; const VarWindow* wins; const TouchProb* probs; int32_t nprob; const uint8_t* enc_lut /*[48][256] -> code*/; uint8_t* tcodes; };
+struct TouchLaunch {
+	const uint8_t* tcodes; const uint8_t* qcodes; int32_t m;      // query codes of the stage-2 alphabet, m real rows (no pad rows)
+	const TouchProb* probs; int32_t nprob;
+	uint16_t* rows;               // [nprob][3][touch_state_rows(m)]: DP state of the queries that do not fit the LDS (m > TOUCH_LDS_ROWS), else NULL
+	uint32_t* out;                // [nprob]: 2 * value + clip bit
+};
+// problems of a launch in (variant, allele, k) order, k = index into enc[0 .. nenc); out[variant][9]: per (allele, class) word
+// (2 * value + b) << 8 | smallest encoding that attains the value (0xff: value 0), then the variant's clipped flag
+struct TouchReduceLaunch { const uint32_t* touch; int32_t nvar, nenc; uint8_t enc[48]; uint32_t* out; };
+hipError_t launch_var_encode(const VarEncodeLaunch& L, hipStream_t st);
+int touch_threads(int m);        // threads of k_touch's workgroup: 64, 128 or 256
+int touch_state_rows(int m);     // 16-bit words per array of a problem's row state: m rounded up to whole rows-per-thread x threads
+hipError_t launch_touch(const TouchLaunch& L, hipStream_t st);
+hipError_t launch_touch_reduce(const TouchReduceLaunch& L, hipStream_t st);
+
 // ---- rowfold.hip: per-base profile of the lncRNA folded from the row maxima of a batch -------------------------
 // Group g = segments [gfirst[g], gfirst[g + 1]) of the batch (the run of segments of one record, or the whole batch); the result is
 // out[g][4 classes][rows_total] = maximum over the group's units of the class, taint bit dropped.

@@ -85,3 +85,77 @@ int fasim_read_bed(const char* path, fasim_region** out, int64_t* n)
 	*out = reg; *n = (int64_t)rows.size();
 	return FASIM_OK;
 }
+
+// ---- variants (`fasim --variants`, read_vcf() of the Python package): fasim_read_vcf ------------------------------------------------
+namespace {
+
+struct VcfRow { int64_t line, pos; std::string chrom, id, ref, alt; bool usable; };
+
+// an allele fasim_score_variants takes: 1 .. FASIM_MAX_ALLELE letters of ACGTN (symbolic alleles, `*`, `.` and breakends fail on
+// their first odd letter)
+bool plain_allele(const std::string& a)
+{
+	if (a.empty() || a.size() > (size_t)FASIM_MAX_ALLELE) return false;
+	for (char c : a) if (!(c == 'A' || c == 'C' || c == 'G' || c == 'T' || c == 'N')) return false;
+	return true;
+}
+
+}  // namespace
+
+int fasim_read_vcf(const char* path, fasim_variant** out, int64_t* n)
+{
+	if (!path || !out || !n) return fail(nullptr, FASIM_E_ARG, "bad arguments");
+	*out = nullptr; *n = 0;
+	std::ifstream in(path);
+	if (!in) return fail(nullptr, FASIM_E_ARG, "cannot read VCF file %s", path);
+	std::vector<VcfRow> rows;
+	std::string line;
+	int64_t ln = 0;
+	size_t strbytes = 0;
+	while (std::getline(in, line)) {
+		ln++;
+		while (!line.empty() && (line.back() == '\r' || line.back() == '\n')) line.pop_back();
+		if (line.empty() || line[0] == '#' || line.find_first_not_of(" \t") == std::string::npos) continue;
+		std::vector<std::string> f;
+		for (size_t b = 0; f.size() < 5; ) {
+			const size_t e = line.find('\t', b);
+			f.emplace_back(line, b, e == std::string::npos ? std::string::npos : e - b);
+			if (e == std::string::npos) break;
+			b = e + 1;
+		}
+		if (f.size() < 5) return fail(nullptr, FASIM_E_ARG, "%s line %lld: fewer than 5 columns", path, (long long)ln);
+		int64_t pos = 0;
+		if (!parse_int(f[1], pos)) return fail(nullptr, FASIM_E_ARG, "%s line %lld: POS '%s' is not an integer", path, (long long)ln, f[1].c_str());
+		if (pos < 1) return fail(nullptr, FASIM_E_ARG, "%s line %lld: POS %lld < 1", path, (long long)ln, (long long)pos);
+		if (f[3].empty()) return fail(nullptr, FASIM_E_ARG, "%s line %lld: empty REF", path, (long long)ln);
+		if (f[4].empty()) return fail(nullptr, FASIM_E_ARG, "%s line %lld: empty ALT", path, (long long)ln);
+		for (char& c : f[3]) c = (char)toupper((unsigned char)c);
+		for (char& c : f[4]) c = (char)toupper((unsigned char)c);
+		for (size_t b = 0; ; ) {
+			const size_t e = f[4].find(',', b);
+			VcfRow r;
+			r.line = ln; r.pos = pos - 1; r.chrom = f[0]; r.id = f[2]; r.ref = f[3];
+			r.alt = f[4].substr(b, e == std::string::npos ? std::string::npos : e - b);
+			if (r.alt.empty()) return fail(nullptr, FASIM_E_ARG, "%s line %lld: empty ALT", path, (long long)ln);
+			r.usable = plain_allele(r.ref) && plain_allele(r.alt);
+			strbytes += r.chrom.size() + r.id.size() + r.ref.size() + r.alt.size() + 4;
+			rows.push_back(std::move(r));
+			if (e == std::string::npos) break;
+			b = e + 1;
+		}
+	}
+	const size_t head = rows.size() * sizeof(fasim_variant);
+	char* block = (char*)malloc(head + strbytes + 1);
+	if (!block) return fail(nullptr, FASIM_E_NOMEM, "out of host memory for %zu variants", rows.size());
+	fasim_variant* v = (fasim_variant*)block;
+	char* s = block + head;
+	auto put = [&s](const std::string& x) { const char* at = s; memcpy(s, x.c_str(), x.size() + 1); s += x.size() + 1; return at; };
+	for (size_t k = 0; k < rows.size(); k++) {
+		const VcfRow& r = rows[k];
+		v[k].line = r.line; v[k].pos = r.pos; v[k].rec = 0;
+		v[k].ref_len = (int32_t)std::min<size_t>(r.ref.size(), 0x7fffffff); v[k].alt_len = r.usable ? (int32_t)r.alt.size() : -1;
+		v[k].chrom = put(r.chrom); v[k].id = put(r.id); v[k].ref = put(r.ref); v[k].alt = put(r.alt);
+	}
+	*out = v; *n = (int64_t)rows.size();
+	return FASIM_OK;
+}

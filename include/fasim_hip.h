@@ -621,6 +621,54 @@ int fasim_read_bed(const char* path, fasim_region** out, int64_t* n);
  * DNA record) has NA in every column after `end`.  peaks: [n * 4], positions relative to the interval.  Free with fasim_free. */
 int fasim_screen_tsv(const fasim_region* regions, const int64_t* segments, const fasim_peak* peaks, int64_t n,
                      char** text, int64_t* text_len);
+/* ---- variants scored by the triplex potential through them (csrc/variant.hip) ------------------------------- */
+/* Does a variant make or break a triplex site?  Per variant, allele (0 = REF, 1 = ALT) and strand class: the best score of a local
+ * alignment of the query that passes through the allele, in the allele's window of the record.  With flank F the window of a variant
+ * at record offset pos is record[lo, hi), lo = max(0, pos - F), hi = min(record length, pos + ref_len + F), with the allele in the
+ * place of REF; its own columns are the mark.  Scoring is that of section 11 (plain Gotoh, +5 / -4 over ACGT, every other letter -4,
+ * U read as A, gap 16 then 4, the units of fasim_encode_unit, enabled encodings and classes as everywhere) with three differences:
+ * no pad rows, no same-letter skip, no saturation (int32 values; a window has at most 5 120 columns).  The touching matrix T is the
+ * plain local recurrence in the columns before the mark's end and from there on the same with a diagonal term that only continues
+ * (Hdiag > 0 ? Hdiag + s : 0); the value of a unit is the maximum of T over the columns from the mark's first on.  value[a][c] is the
+ * maximum over the class's enabled encodings, enc[a][c] the smallest encoding that attains it (-1: value 0).  flags bit 0, `clipped`:
+ * an alignment of the largest value over both alleles and all classes may continue past an end of the window that the flank cut (not
+ * the record's end): lengthen the flank. */
+#define FASIM_MAX_ALLELE 1024
+#define FASIM_MAX_FLANK  2048
+typedef struct fasim_variant {
+	int64_t line, pos;                  /* 1-based line of the VCF; 0-based offset of REF's first letter within record `rec`       */
+	int32_t rec, ref_len, alt_len;      /* alt_len < 0: an allele that cannot be scored (the entry gets zeros and enc = -1)         */
+	const char* chrom; const char* id; const char* ref; const char* alt;      /* strings live in the same block as the array */
+} fasim_variant;
+typedef struct fasim_variant_score {
+	int32_t value[2][FASIM_TRACK_CLASSES], enc[2][FASIM_TRACK_CLASSES];
+	int32_t flags, reserved;
+} fasim_variant_score;
+typedef struct fasim_variant_stats { int64_t problems, cells; double kernel_s, total_s; } fasim_variant_stats;
+/* VCF text, tab-separated: CHROM POS ID REF ALT, further columns ignored, '#' lines and blank lines skipped.  An ALT with commas
+ * gives one entry per allele with the same `line`; alleles are upper-cased; pos = POS - 1 and rec = 0.  Kept with alt_len = -1 (the
+ * caller reports NA): a symbolic allele (<DEL>), a `*` or `.` allele, a breakend, an allele with letters outside ACGTN or longer
+ * than FASIM_MAX_ALLELE.  Refused with FASIM_E_ARG (the line number and the reason in fasim_last_error(NULL)): fewer than 5 columns,
+ * a POS that is not an integer or below 1, an empty REF or ALT, an unreadable file.  *out is ONE block (fasim_free); *n may be 0. */
+int fasim_read_vcf(const char* path, fasim_variant** out, int64_t* n);
+/* Scores nvar variants of the records dna[rec_off[r] .. rec_off[r] + rec_len[r]) (dna == NULL: the resident buffer of fasim_load_dna)
+ * for nq >= 1 queries; out[q * nvar + v].  The engine's own query (fasim_set_query), its scan buffers and its workers are neither read
+ * nor changed.  The result of a variant depends on the record, the variant, the flank, the query and the parameters only (not on the
+ * other variants, their order or the launches).  REF is not compared with the record: that is the caller's business.  Refused before
+ * any GPU work, the engine stays usable: a variant outside its record, ref_len < 1, an allele above FASIM_MAX_ALLELE or of length 0,
+ * a flank outside [0, FASIM_MAX_FLANK], the record refusals of fasim_scan_records (FASIM_E_ARG); a query above FASIM_MAX_QUERY,
+ * classicSim (FASIM_E_UNSUPPORTED). */
+int fasim_score_variants(fasim_engine* e, const char* const* rnas, const int32_t* rna_lens, int32_t nq,
+                         const char* dna, const int64_t* rec_off, const int64_t* rec_len, int32_t nrec,
+                         const fasim_variant* vars, int64_t nvar, int32_t flank, const fasim_params* p,
+                         fasim_variant_score* out /* [nq * nvar] */, fasim_variant_stats* stats /* may be NULL */);
+/* The table `fasim --variants` writes for one query: `# fasim variants lncRNA=<rna_name> flank=<F>`, the line of column names, then
+ * one tab-separated line per entry: line chrom pos id ref alt, per class <Class>_ref <Class>_alt, then max_ref max_alt delta
+ * rule_ref rule_alt clipped.  pos is 1-based as in the VCF; delta = max_alt - max_ref; rule_* is the Rule value -TFOsorted prints for
+ * the smallest class, then the smallest encoding, that attains the maximum, NA where it is 0.  An entry with matched[k] == 0
+ * (matched may be NULL: all matched) or alt_len < 0 has NA in every column after alt.  Free with fasim_free. */
+int fasim_variants_tsv(const fasim_variant* vars, const fasim_variant_score* scores, int64_t nvar, int32_t flank, const char* rna_name,
+                       const uint8_t* matched /* [nvar] or NULL */, char** text, int64_t* text_len);
 /* ingest helper: upper-cases a DNA record in place (soft-masked genomes such as UCSC hg38 carry repeats in lower
  * case; the reference does not upper-case and treats such letters as unknown, rules.h:286-312, 82-83). */
 void fasim_upper_case(char* seq, int64_t n);
