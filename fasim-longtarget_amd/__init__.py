@@ -340,6 +340,91 @@ def default_params(**kw) -> Params:
     return p
 
 
+class _Native:
+    """What the objects over a structure of the library share.  `_native`: a POINTER the library made, released with the class's
+    `_free` when the object dies; otherwise `_keep` holds the structure made in Python (at index 1) and the arrays it points into.
+    `_keep` set beside `_native` (SiteHits): a structure of the caller's, which the library must not free."""
+    _free = None              # name of the library's free function
+    _native = None
+    _keep = None
+
+    def __del__(self):
+        try:
+            if self._native is not None and self._keep is None:
+                getattr(lib(), self._free)(self._native)
+                self._native = None
+        except Exception:
+            pass
+
+    def pointer(self):
+        """POINTER(struct) for the C-ABI; valid while this object lives."""
+        return self._native if self._native is not None else C.pointer(self._keep[1])
+
+    @property
+    def _t(self):
+        return self._native.contents if self._native is not None else self._keep[1]
+
+
+def _text_call(fn, *args, name=None, code=True):
+    """A library function whose last two parameters are (char** text, int64_t* text_len): its text as bytes."""
+    L = lib()
+    text = C.c_void_p()
+    n = C.c_int64()
+    rc = fn(*args, C.byref(text), C.byref(n))
+    if rc != 0:
+        msg = f"{name or fn.__name__} failed ({rc}): {L.fasim_last_error(None).decode()}"
+        raise FasimError(msg, rc) if code else FasimError(msg)
+    try:
+        return C.string_at(text, n.value)
+    finally:
+        L.fasim_free(text)
+
+
+def _pack_records(dnas, rec_lens=None, resident_ok=False):
+    """The record set of a call as (blob, offs, lens, nrec): `dnas` a list of records or one bytes object (a set of one record).
+    dnas None: the resident buffer -- cut into records of rec_lens, or (resident_ok) whole, as the one record the engine knows."""
+    if isinstance(dnas, (bytes, bytearray)):
+        dnas = [bytes(dnas)]
+    if dnas is None and rec_lens is None:
+        if not resident_ok:
+            raise FasimError("this call needs its records: dnas is None", E_ARG)
+        return None, None, None, 1
+    lens_l = [len(d) for d in dnas] if dnas is not None else [int(x) for x in rec_lens]
+    nrec = len(lens_l)
+    offs = (C.c_int64 * max(1, nrec))()
+    lens = (C.c_int64 * max(1, nrec))()
+    o = 0
+    for i, n in enumerate(lens_l):
+        offs[i], lens[i] = o, n
+        o += n
+    return (b"".join(dnas) if dnas is not None else None), offs, lens, nrec
+
+
+def _pack_spans(seq, spans, who):
+    """0-based half-open (start, end) spans of `seq` (None: of the resident buffer) as the records (offs, lens, nrec) of a call."""
+    spans = [(int(s), int(e)) for s, e in spans]
+    nrec = len(spans)
+    if nrec == 0:
+        raise FasimError(f"{who} needs at least one span", E_ARG)
+    for k, (s, e) in enumerate(spans):
+        if s < 0 or e <= s or (seq is not None and e > len(seq)):
+            raise FasimError(f"span {k}: ({s}, {e}) is not a non-empty slice of the sequence", E_ARG)
+    return (C.c_int64 * nrec)(*[s for s, _ in spans]), (C.c_int64 * nrec)(*[e - s for s, e in spans]), nrec
+
+
+def _pack_queries(rnas):
+    """The queries of a call as (arr, qlens, nq, nqo): rnas None is the engine's own query (nq 0); nqo = max(1, nq) outputs."""
+    rnas = list(rnas or [])
+    nq = len(rnas)
+    nqo = max(1, nq)
+    return (C.c_char_p * nqo)(*rnas), (C.c_int32 * nqo)(*[len(r) for r in rnas]), nq, nqo
+
+
+def _grid(cls, ptrs, nq, nrec):
+    """ptrs[q * nrec + r] as objects of `cls`: a list per query of lists per record."""
+    return [[cls(_native=ptrs[q * nrec + r]) for r in range(nrec)] for q in range(nq)]
+
+
 class ScanResult:
     """Records of one scan (or of one shard, or of a merge).  Either a view of a native `fasim_result` (what scan() and
     merge_results() return: nothing is copied) or two Python byte strings (`ScanResult(recs, pool, stats)`)."""
@@ -408,11 +493,13 @@ class ScanResult:
         return out
 
 
-class Track:
+class Track(_Native):
     """Per-base triplex potential of one record and one lncRNA (struct fasim_track): per strand class (TRACK_CLASSES) and bin
     of `bin` bases the best local alignment score of the lncRNA that ends in the bin, without the candidate threshold.
     Either a native track (what scan_track() and merge_tracks() return) or one made from a (4, nbins) array:
     `Track(values, bin, units=0, saturated_units=0)`."""
+
+    _free = "fasim_track_free"
 
     def __init__(self, values=None, bin: int = 1, units: int = 0, saturated_units: int = 0, _native=None):
         self._native = _native
@@ -427,22 +514,6 @@ class Track:
             for c in range(4):
                 t.v[c] = C.cast(a[c].ctypes.data, C.POINTER(C.c_uint16))
             self._keep = (a, t)
-
-    def __del__(self):
-        try:
-            if self._native is not None:
-                lib().fasim_track_free(self._native)
-                self._native = None
-        except Exception:
-            pass
-
-    def pointer(self):
-        """POINTER(fasim_track) for the C-ABI; valid while this object lives."""
-        return self._native if self._native is not None else C.pointer(self._keep[1])
-
-    @property
-    def _t(self):
-        return self._native.contents if self._native is not None else self._keep[1]
 
     @property
     def bin(self) -> int:
@@ -487,24 +558,18 @@ def track_bedgraph(track: Track, chr_name: str, start_genome: int, dna_len: int,
     """bedGraph bytes of a potential track (fasim_track_bedgraph): one block per strand class, runs of equal bins joined, bins
     below `min_value` left out; what `fasim --track BIN` writes as <stem>-TFOpotential-<BIN>."""
     L = lib()
-    text = C.c_void_p()
-    n = C.c_int64()
-    rc = L.fasim_track_bedgraph(track.pointer(), chr_name.encode(), start_genome, dna_len, rna_name.encode(), min_value,
-                                C.byref(text), C.byref(n))
-    if rc != 0:
-        raise FasimError(f"fasim_track_bedgraph failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
-    try:
-        return C.string_at(text, n.value)
-    finally:
-        L.fasim_free(text)
+    return _text_call(L.fasim_track_bedgraph, track.pointer(), chr_name.encode(), start_genome, dna_len, rna_name.encode(),
+                      min_value)
 
 
-class Hist:
+class Hist(_Native):
     """Histogram of the per-base potential of one lncRNA (or oligo, or shuffled control) over a record set (struct fasim_hist):
     per strand class (TRACK_CLASSES) and value v in [0, 16383] the number of covered positions whose potential is v.  Either a
     native histogram (what scan_hist(), scan_oligos_hist() and merge_hists() return) or one made from a (4, 16384) array:
     `Hist(counts, positions=None, units=0, saturated_units=0, pending=())`, positions defaulting to the sum of class 0 and
     `pending` a list of (record, boundary, side, values) with values a (4, len) array."""
+
+    _free = "fasim_hist_free"
 
     def __init__(self, counts=None, positions=None, units: int = 0, saturated_units: int = 0, pending=(), _native=None):
         self._native = _native
@@ -529,22 +594,6 @@ class Hist:
                 edges[k].v = C.cast(v.ctypes.data, C.POINTER(C.c_uint16))
             t.npending, t.pending = len(pend), C.cast(edges, C.POINTER(_HistEdge))
             self._keep = (a, t, pend, edges)
-
-    def __del__(self):
-        try:
-            if self._native is not None:
-                lib().fasim_hist_free(self._native)
-                self._native = None
-        except Exception:
-            pass
-
-    def pointer(self):
-        """POINTER(fasim_hist) for the C-ABI; valid while this object lives."""
-        return self._native if self._native is not None else C.pointer(self._keep[1])
-
-    @property
-    def _t(self):
-        return self._native.contents if self._native is not None else self._keep[1]
 
     @property
     def positions(self) -> int:
@@ -627,21 +676,15 @@ def hist_tsv(real: Hist, rna_name: str, controls=(), seed: int = 0, fdr: float =
     with controls, those of the controls and the false discovery rate."""
     L = lib()
     controls, arr = _hist_ptrs(controls)
-    text = C.c_void_p()
-    n = C.c_int64()
-    rc = L.fasim_hist_tsv(real.pointer(), arr, len(controls), seed & 0xFFFFFFFFFFFFFFFF, fdr, rna_name.encode(), C.byref(text), C.byref(n))
-    if rc != 0:
-        raise FasimError(f"fasim_hist_tsv failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
-    try:
-        return C.string_at(text, n.value)
-    finally:
-        L.fasim_free(text)
+    return _text_call(L.fasim_hist_tsv, real.pointer(), arr, len(controls), seed & 0xFFFFFFFFFFFFFFFF, fdr, rna_name.encode())
 
 
-class TfoProfile:
+class TfoProfile(_Native):
     """Per-base profile of one lncRNA (struct fasim_tfo_profile): per strand class (TRACK_CLASSES) and base of the lncRNA the best
     local alignment score that ends on that base, over the scanned records.  Either a native profile (what scan_tfo_profile()
     and merge_tfo_profiles() return) or one made from a (4, m) array: `TfoProfile(values, units=0, saturated_units=0)`."""
+
+    _free = "fasim_tfo_profile_free"
 
     def __init__(self, values=None, units: int = 0, saturated_units: int = 0, _native=None):
         self._native = _native
@@ -656,22 +699,6 @@ class TfoProfile:
             for c in range(4):
                 t.v[c] = C.cast(a[c].ctypes.data, C.POINTER(C.c_uint16))
             self._keep = (a, t)
-
-    def __del__(self):
-        try:
-            if self._native is not None:
-                lib().fasim_tfo_profile_free(self._native)
-                self._native = None
-        except Exception:
-            pass
-
-    def pointer(self):
-        """POINTER(fasim_tfo_profile) for the C-ABI; valid while this object lives."""
-        return self._native if self._native is not None else C.pointer(self._keep[1])
-
-    @property
-    def _t(self):
-        return self._native.contents if self._native is not None else self._keep[1]
 
     @property
     def m(self) -> int:
@@ -714,22 +741,16 @@ def tfo_profile_tsv(profile: TfoProfile, rna: bytes, rna_name: str = "") -> byte
     L = lib()
     if len(rna) != profile.m:
         raise FasimError(f"the lncRNA has {len(rna)} bases, the profile {profile.m}", E_ARG)
-    text = C.c_void_p()
-    n = C.c_int64()
-    rc = L.fasim_tfo_profile_tsv(profile.pointer(), rna, rna_name.encode(), C.byref(text), C.byref(n))
-    if rc != 0:
-        raise FasimError(f"fasim_tfo_profile_tsv failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
-    try:
-        return C.string_at(text, n.value)
-    finally:
-        L.fasim_free(text)
+    return _text_call(L.fasim_tfo_profile_tsv, profile.pointer(), rna, rna_name.encode())
 
 
-class Sites:
+class Sites(_Native):
     """Sites of one record and one lncRNA above a fixed potential (struct fasim_sites): the ranges of positions whose potential
     in one strand class reaches `min_value`, ranges at most `max_gap` apart joined, each with its peak.  Either a native list
     (what scan_sites() and merge_sites() return) or one made from an (n, 6) array of (cls, start, end, value, pos, enc) rows:
     `Sites(rows, min_value, max_gap=0, units=0, saturated_units=0, raw_runs=0)`."""
+
+    _free = "fasim_sites_free"
 
     def __init__(self, rows=None, min_value: int = 1, max_gap: int = 0, units: int = 0, saturated_units: int = 0, raw_runs: int = 0,
                  _native=None):
@@ -745,22 +766,6 @@ class Sites:
             t.n, t.s = len(a), C.cast(arr, C.POINTER(_Site))
             t.units, t.saturated_units, t.raw_runs, t.min_value, t.max_gap = units, saturated_units, raw_runs, min_value, max_gap
             self._keep = (arr, t)
-
-    def __del__(self):
-        try:
-            if self._native is not None:
-                lib().fasim_sites_free(self._native)
-                self._native = None
-        except Exception:
-            pass
-
-    def pointer(self):
-        """POINTER(fasim_sites) for the C-ABI; valid while this object lives."""
-        return self._native if self._native is not None else C.pointer(self._keep[1])
-
-    @property
-    def _t(self):
-        return self._native.contents if self._native is not None else self._keep[1]
 
     @property
     def n(self) -> int:
@@ -819,16 +824,8 @@ def sites_bed(sites: Sites, chr_name: str, start_genome: int, rna_name: str, rec
     """BED bytes of a site list (fasim_sites_bed): chrom, start, end, class, value, strand, peak, rule and, where record_name is
     given, the record's name; what `fasim --sites V` writes."""
     L = lib()
-    text = C.c_void_p()
-    n = C.c_int64()
-    rc = L.fasim_sites_bed(sites.pointer(), chr_name.encode(), start_genome, rna_name.encode(),
-                           record_name.encode() if record_name is not None else None, 1 if header else 0, C.byref(text), C.byref(n))
-    if rc != 0:
-        raise FasimError(f"fasim_sites_bed failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
-    try:
-        return C.string_at(text, n.value)
-    finally:
-        L.fasim_free(text)
+    return _text_call(L.fasim_sites_bed, sites.pointer(), chr_name.encode(), start_genome, rna_name.encode(),
+                      record_name.encode() if record_name is not None else None, 1 if header else 0)
 
 
 def oligo_panel_tsv(names, oligos, sites) -> bytes:
@@ -847,40 +844,18 @@ def oligo_panel_tsv(names, oligos, sites) -> bytes:
     arr = (C.POINTER(_Sites) * max(1, len(flat)))(*[t.pointer() for t in flat])
     nm = (C.c_char_p * max(1, nq))(*[n.encode() if isinstance(n, str) else bytes(n) for n in names])
     lens = (C.c_int32 * max(1, nq))(*[len(o) for o in oligos])
-    text = C.c_void_p()
-    n = C.c_int64()
-    rc = L.fasim_oligo_panel_tsv(nm, lens, nq, arr, nrec, C.byref(text), C.byref(n))
-    if rc != 0:
-        raise FasimError(f"fasim_oligo_panel_tsv failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
-    try:
-        return C.string_at(text, n.value)
-    finally:
-        L.fasim_free(text)
+    return _text_call(L.fasim_oligo_panel_tsv, nm, lens, nq, arr, nrec)
 
 
-class SiteHits:
+class SiteHits(_Native):
     """The hits of the sites of one record and one lncRNA (struct fasim_site_hits): hit k is the alignment behind the peak of site
     k of the Sites object of the same call.  What scan_sites_aligned() and merge_site_hits() return."""
+
+    _free = "fasim_site_hits_free"
 
     def __init__(self, _native, _keep=None):
         self._native = _native
         self._keep = _keep               # not None: a structure made by the caller, which the library must not free
-
-    def __del__(self):
-        try:
-            if self._native is not None and self._keep is None:
-                lib().fasim_site_hits_free(self._native)
-                self._native = None
-        except Exception:
-            pass
-
-    def pointer(self):
-        """POINTER(fasim_site_hits) for the C-ABI; valid while this object lives."""
-        return self._native
-
-    @property
-    def _t(self):
-        return self._native.contents
 
     @property
     def n(self) -> int:
@@ -947,16 +922,8 @@ def site_hits_tsv(sites: Sites, hits: SiteHits, chr_name: str, start_genome: int
                   header: bool = True) -> bytes:
     """The table of `fasim --sites V --sites-align` (fasim_site_hits_tsv): one line per site with its hit."""
     L = lib()
-    text = C.c_void_p()
-    n = C.c_int64()
-    rc = L.fasim_site_hits_tsv(sites.pointer(), hits.pointer(), chr_name.encode(), start_genome, rna_name.encode(),
-                               record_name.encode() if record_name is not None else None, 1 if header else 0, C.byref(text), C.byref(n))
-    if rc != 0:
-        raise FasimError(f"fasim_site_hits_tsv failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
-    try:
-        return C.string_at(text, n.value)
-    finally:
-        L.fasim_free(text)
+    return _text_call(L.fasim_site_hits_tsv, sites.pointer(), hits.pointer(), chr_name.encode(), start_genome,
+                      rna_name.encode(), record_name.encode() if record_name is not None else None, 1 if header else 0)
 
 
 def _peaks_to_c(peaks):
@@ -1009,15 +976,7 @@ def screen_tsv(regions, segments, peaks) -> bytes:
     pk, npk = _peaks_to_c(peaks)
     if npk != 4 * n:
         raise FasimError("screen_tsv: peaks must hold four (value, pos, enc) rows per interval", E_ARG)
-    text = C.c_void_p()
-    ln = C.c_int64()
-    rc = L.fasim_screen_tsv(reg, segs, pk, n, C.byref(text), C.byref(ln))
-    if rc != 0:
-        raise FasimError(f"fasim_screen_tsv failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
-    try:
-        return C.string_at(text, ln.value)
-    finally:
-        L.fasim_free(text)
+    return _text_call(L.fasim_screen_tsv, reg, segs, pk, n)
 
 
 def _merge_pointers(ptrs):
@@ -1267,6 +1226,15 @@ class Engine:
             stats[k] = list(v) if hasattr(v, "__len__") else v
         return stats
 
+    def _wrap_results(self, outs, nqo, nrec):
+        """outs[q * nrec + r] as ScanResults that own them: a list per query of lists per record."""
+        return [[ScanResult(stats=self._stats_dict(outs[q * nrec + r].contents.stats), _native=outs[q * nrec + r]) for r in range(nrec)]
+                for q in range(nqo)]
+
+    def _totals(self, totals, nq):
+        """The call's totals, one stats dict per query, into `self.last_totals`."""
+        self.last_totals = [self._stats_dict(totals[q]) for q in range(nq)]
+
     def scan(self, dna: bytes | None, params: Params | None = None, seg_first: int = 0, seg_count: int = -1) -> ScanResult:
         p = params or default_params()
         res = C.POINTER(_Result)()
@@ -1278,9 +1246,7 @@ class Engine:
         """Multi-lncRNA batch (fasim_scan_queries): one ScanResult per lncRNA, each identical to what scan() returns for
         that lncRNA alone; the DNA record stays resident and the lncRNAs share one work queue."""
         p = params or default_params()
-        n = len(rnas)
-        arr = (C.c_char_p * n)(*rnas)
-        lens = (C.c_int32 * n)(*[len(r) for r in rnas])
+        arr, lens, n, _ = _pack_queries(rnas)
         outs = (C.POINTER(_Result) * n)()
         self._check(self._L.fasim_scan_queries(self._h, arr, lens, n, dna, len(dna) if dna is not None else 0, seg_first,
                                                seg_count, C.byref(p), outs))
@@ -1294,10 +1260,7 @@ class Engine:
         is not run and the first element is None.  With a segment range the tracks still span the whole record: merge the
         shards' tracks with merge_tracks()."""
         p = params or default_params()
-        nq = 0 if rnas is None else len(rnas)
-        nqo = max(1, nq)
-        arr = (C.c_char_p * nqo)(*(rnas or []))
-        qlens = (C.c_int32 * nqo)(*[len(r) for r in (rnas or [])])
+        arr, qlens, nq, nqo = _pack_queries(rnas)
         outs = (C.POINTER(_Result) * nqo)() if records else None
         trks = (C.POINTER(_Track) * nqo)()
         self._check(self._L.fasim_scan_track(self._h, arr, qlens, nq, dna, len(dna) if dna is not None else 0, seg_first,
@@ -1318,33 +1281,18 @@ class Engine:
         list per lncRNA of per-record lists, like scan_queries().  The call's totals (one stats dict per query) are left in
         `self.last_totals`."""
         p = params or default_params()
-        if dnas is None:
-            if rec_lens is None:
-                raise FasimError("scan_records(None, ...) needs rec_lens (the records of the resident buffer)", E_ARG)
-            lens_l, blob = [int(x) for x in rec_lens], None
-        else:
-            lens_l = [len(d) for d in dnas]
-            blob = b"".join(dnas)
-        nrec = len(lens_l)
-        offs = (C.c_int64 * max(1, nrec))()
-        lens = (C.c_int64 * max(1, nrec))()
-        o = 0
-        for i, n in enumerate(lens_l):
-            offs[i], lens[i] = o, n
-            o += n
-        nq = 0 if rnas is None else len(rnas)
-        arr = (C.c_char_p * max(1, nq))(*(rnas or []))
-        qlens = (C.c_int32 * max(1, nq))(*[len(r) for r in (rnas or [])])
-        nqo = max(1, nq)
+        if dnas is None and rec_lens is None:
+            raise FasimError("scan_records(None, ...) needs rec_lens (the records of the resident buffer)", E_ARG)
+        blob, offs, lens, nrec = _pack_records(dnas, rec_lens)
+        arr, qlens, nq, nqo = _pack_queries(rnas)
         outs = (C.POINTER(_Result) * (nqo * max(1, nrec)))()
         totals = (ScanStats * nqo)()
         self._check(self._L.fasim_scan_records(self._h, arr, qlens, nq, blob, offs, lens, nrec, seg_first, seg_count, C.byref(p),
                                                outs, totals))
         if nq:
             self.m = len(rnas[-1])
-        self.last_totals = [self._stats_dict(totals[q]) for q in range(nqo)]
-        res = [[ScanResult(stats=self._stats_dict(outs[q * nrec + r].contents.stats), _native=outs[q * nrec + r]) for r in range(nrec)]
-               for q in range(nqo)]
+        self._totals(totals, nqo)
+        res = self._wrap_results(outs, nqo, nrec)
         return res[0] if rnas is None else res
 
     def scan_tfo_profile(self, dnas, params: Params | None = None, rnas=None, per_record: bool = False, records: bool = True,
@@ -1355,21 +1303,8 @@ class Engine:
         record scanned alone gives.  rnas given: lists per lncRNA of those.  records False: no stage 3, results is None.
         Shards of a segment range merge with merge_tfo_profiles().  Totals: `self.last_totals`."""
         p = params or default_params()
-        if isinstance(dnas, (bytes, bytearray)):
-            dnas = [bytes(dnas)]
-        lens_l = [len(d) for d in dnas]
-        blob = b"".join(dnas)
-        nrec = len(lens_l)
-        offs = (C.c_int64 * max(1, nrec))()
-        lens = (C.c_int64 * max(1, nrec))()
-        o = 0
-        for i, n in enumerate(lens_l):
-            offs[i], lens[i] = o, n
-            o += n
-        nq = 0 if rnas is None else len(rnas)
-        nqo = max(1, nq)
-        arr = (C.c_char_p * nqo)(*(rnas or []))
-        qlens = (C.c_int32 * nqo)(*[len(r) for r in (rnas or [])])
+        blob, offs, lens, nrec = _pack_records(dnas)
+        arr, qlens, nq, nqo = _pack_queries(rnas)
         nout = nqo * max(1, nrec)
         nprof = nout if per_record else nqo
         outs = (C.POINTER(_Result) * nout)() if records else None
@@ -1379,13 +1314,12 @@ class Engine:
                                                    1 if per_record else 0, outs, profs, totals))
         if nq:
             self.m = len(rnas[-1])
-        self.last_totals = [self._stats_dict(totals[q]) for q in range(nqo)]
+        self._totals(totals, nqo)
         res = None
         if records:
-            res = [[ScanResult(stats=self._stats_dict(outs[q * nrec + r].contents.stats), _native=outs[q * nrec + r])
-                    for r in range(nrec)] for q in range(nqo)]
+            res = self._wrap_results(outs, nqo, nrec)
         if per_record:
-            prof = [[TfoProfile(_native=profs[q * nrec + r]) for r in range(nrec)] for q in range(nqo)]
+            prof = _grid(TfoProfile, profs, nqo, nrec)
         else:
             prof = [TfoProfile(_native=profs[q]) for q in range(nqo)]
         if rnas is None:
@@ -1395,23 +1329,8 @@ class Engine:
     def _sites_call(self, aligned, dnas, params, min_value, max_gap, records, rnas, seg_first, seg_count):
         """Argument marshalling and result wrapping shared by scan_sites() and scan_sites_aligned()."""
         p = params or default_params()
-        if isinstance(dnas, (bytes, bytearray)):
-            dnas = [bytes(dnas)]
-        if dnas is None:
-            blob, offs, lens, nrec = None, None, None, 1        # the whole resident buffer: the engine knows its length
-        else:
-            blob = b"".join(dnas)
-            nrec = len(dnas)
-            offs = (C.c_int64 * max(1, nrec))()
-            lens = (C.c_int64 * max(1, nrec))()
-            o = 0
-            for i, d in enumerate(dnas):
-                offs[i], lens[i] = o, len(d)
-                o += len(d)
-        nq = 0 if rnas is None else len(rnas)
-        nqo = max(1, nq)
-        arr = (C.c_char_p * nqo)(*(rnas or []))
-        qlens = (C.c_int32 * nqo)(*[len(r) for r in (rnas or [])])
+        blob, offs, lens, nrec = _pack_records(dnas, resident_ok=True)
+        arr, qlens, nq, nqo = _pack_queries(rnas)
         nout = nqo * max(1, nrec)
         outs = (C.POINTER(_Result) * nout)() if records else None
         sts = (C.POINTER(_Sites) * nout)()
@@ -1425,14 +1344,13 @@ class Engine:
                                                          min_value, max_gap, outs, sts, totals))
         if nq:
             self.m = len(rnas[-1])
-        self.last_totals = [self._stats_dict(totals[q]) for q in range(nqo)]
+        self._totals(totals, nqo)
         res = None
         if records:
-            res = [[ScanResult(stats=self._stats_dict(outs[q * nrec + r].contents.stats), _native=outs[q * nrec + r])
-                    for r in range(nrec)] for q in range(nqo)]
-        out = [res, [[Sites(_native=sts[q * nrec + r]) for r in range(nrec)] for q in range(nqo)]]
+            res = self._wrap_results(outs, nqo, nrec)
+        out = [res, _grid(Sites, sts, nqo, nrec)]
         if aligned:
-            out.append([[SiteHits(hts[q * nrec + r]) for r in range(nrec)] for q in range(nqo)])
+            out.append(_grid(SiteHits, hts, nqo, nrec))
         if rnas is None:
             return tuple([(res[0] if res else None)] + [x[0] for x in out[1:]])
         return tuple(out)
@@ -1461,34 +1379,19 @@ class Engine:
         query is not touched.  Shards of a segment range merge with merge_sites() / merge_tracks(); the panel table is
         oligo_panel_tsv().  Totals per oligo: `self.last_totals`."""
         p = params or default_params()
-        if isinstance(dnas, (bytes, bytearray)):
-            dnas = [bytes(dnas)]
-        if dnas is None:
-            blob, offs, lens, nrec = None, None, None, 1        # the whole resident buffer: the engine knows its length
-        else:
-            blob = b"".join(dnas)
-            nrec = len(dnas)
-            offs = (C.c_int64 * max(1, nrec))()
-            lens = (C.c_int64 * max(1, nrec))()
-            o = 0
-            for i, d in enumerate(dnas):
-                offs[i], lens[i] = o, len(d)
-                o += len(d)
-        oligos = [bytes(x) for x in oligos]
-        nq = len(oligos)
-        arr = (C.c_char_p * max(1, nq))(*oligos)
-        qlens = (C.c_int32 * max(1, nq))(*[len(x) for x in oligos])
+        blob, offs, lens, nrec = _pack_records(dnas, resident_ok=True)
+        arr, qlens, nq, _ = _pack_queries([bytes(x) for x in oligos])
         nout = max(1, nq) * max(1, nrec)
         sts = (C.POINTER(_Sites) * nout)()
         trks = (C.POINTER(_Track) * nout)() if track_bin != 0 else None
         totals = (ScanStats * max(1, nq))()
         self._check(self._L.fasim_scan_oligos(self._h, arr, qlens, nq, blob, offs, lens, nrec, seg_first, seg_count, C.byref(p),
                                               min_value, max_gap, sts, track_bin, trks, totals))
-        self.last_totals = [self._stats_dict(totals[q]) for q in range(nq)]
-        sites = [[Sites(_native=sts[q * nrec + r]) for r in range(nrec)] for q in range(nq)]
+        self._totals(totals, nq)
+        sites = _grid(Sites, sts, nq, nrec)
         if trks is None:
             return sites
-        return sites, [[Track(_native=trks[q * nrec + r]) for r in range(nrec)] for q in range(nq)]
+        return sites, _grid(Track, trks, nq, nrec)
 
     def scan_oligos_aligned(self, oligos, dnas, params: Params | None = None, min_value: int = 1, max_gap: int = 0,
                             seg_first: int = 0, seg_count: int = -1):
@@ -1497,32 +1400,16 @@ class Engine:
         scan_sites_aligned() would give for a lncRNA, with the oligo in its place.  `dnas` as for scan_oligos().  Shards of a
         segment range merge with merge_site_hits().  Option site_short = 0 runs the hits on the lncRNAs' kernel (same results)."""
         p = params or default_params()
-        if isinstance(dnas, (bytes, bytearray)):
-            dnas = [bytes(dnas)]
-        if dnas is None:
-            blob, offs, lens, nrec = None, None, None, 1        # the whole resident buffer: the engine knows its length
-        else:
-            blob = b"".join(dnas)
-            nrec = len(dnas)
-            offs = (C.c_int64 * max(1, nrec))()
-            lens = (C.c_int64 * max(1, nrec))()
-            o = 0
-            for i, d in enumerate(dnas):
-                offs[i], lens[i] = o, len(d)
-                o += len(d)
-        oligos = [bytes(x) for x in oligos]
-        nq = len(oligos)
-        arr = (C.c_char_p * max(1, nq))(*oligos)
-        qlens = (C.c_int32 * max(1, nq))(*[len(x) for x in oligos])
+        blob, offs, lens, nrec = _pack_records(dnas, resident_ok=True)
+        arr, qlens, nq, _ = _pack_queries([bytes(x) for x in oligos])
         nout = max(1, nq) * max(1, nrec)
         sts = (C.POINTER(_Sites) * nout)()
         hts = (C.POINTER(_SiteHits) * nout)()
         totals = (ScanStats * max(1, nq))()
         self._check(self._L.fasim_scan_oligos_aligned(self._h, arr, qlens, nq, blob, offs, lens, nrec, seg_first, seg_count, C.byref(p),
                                                       min_value, max_gap, sts, hts, totals))
-        self.last_totals = [self._stats_dict(totals[q]) for q in range(nq)]
-        return ([[Sites(_native=sts[q * nrec + r]) for r in range(nrec)] for q in range(nq)],
-                [[SiteHits(hts[q * nrec + r]) for r in range(nrec)] for q in range(nq)])
+        self._totals(totals, nq)
+        return _grid(Sites, sts, nq, nrec), _grid(SiteHits, hts, nq, nrec)
 
     def scan_hist(self, dnas, params: Params | None = None, controls: int = 0, seed: int = 0, records: bool = False, seg_first: int = 0,
                   seg_count: int = -1, rnas=None):
@@ -1532,19 +1419,7 @@ class Engine:
         queries of the same call.  rnas given: lists per lncRNA of those.  records True: stage 3 runs and results is what
         scan_records() returns for the lncRNA (not for its controls).  Shards of a segment range merge with merge_hists()."""
         p = params or default_params()
-        if isinstance(dnas, (bytes, bytearray)):
-            dnas = [bytes(dnas)]
-        if dnas is None:
-            blob, offs, lens, nrec = None, None, None, 1        # the whole resident buffer: the engine knows its length
-        else:
-            blob = b"".join(dnas)
-            nrec = len(dnas)
-            offs = (C.c_int64 * max(1, nrec))()
-            lens = (C.c_int64 * max(1, nrec))()
-            o = 0
-            for i, d in enumerate(dnas):
-                offs[i], lens[i] = o, len(d)
-                o += len(d)
+        blob, offs, lens, nrec = _pack_records(dnas, resident_ok=True)
         if controls < 0:
             raise FasimError(f"scan_hist: controls = {controls} is negative", E_ARG)
         if rnas is None and getattr(self, "rna", None) is None:
@@ -1554,9 +1429,7 @@ class Engine:
         ctl = [shuffle_query(r, seed, k + 1) for r in base for k in range(controls)]
 
         def call(qs, want_records):
-            nq = len(qs)
-            arr = (C.c_char_p * max(1, nq))(*qs)
-            qlens = (C.c_int32 * max(1, nq))(*[len(r) for r in qs])
+            arr, qlens, nq, _ = _pack_queries(qs)
             outs = (C.POINTER(_Result) * (max(1, nq) * max(1, nrec)))() if want_records else None
             hs = (C.POINTER(_Hist) * max(1, nq))()
             totals = (ScanStats * max(1, nq))()
@@ -1564,8 +1437,7 @@ class Engine:
                                                         outs, hs, totals))
             res = None
             if want_records:
-                res = [[ScanResult(stats=self._stats_dict(outs[q * nrec + r].contents.stats), _native=outs[q * nrec + r])
-                        for r in range(nrec)] for q in range(nq)]
+                res = self._wrap_results(outs, nq, nrec)
             return res, [Hist(_native=hs[q]) for q in range(nq)], [self._stats_dict(totals[q]) for q in range(nq)]
 
         if records:
@@ -1588,28 +1460,13 @@ class Engine:
         """Histograms of the potential of a panel of short oligos (fasim_scan_oligos_hist): one Hist per oligo over the record set,
         what scan_hist() would give for a lncRNA with the oligo in its place.  `dnas` as for scan_oligos()."""
         p = params or default_params()
-        if isinstance(dnas, (bytes, bytearray)):
-            dnas = [bytes(dnas)]
-        if dnas is None:
-            blob, offs, lens, nrec = None, None, None, 1
-        else:
-            blob = b"".join(dnas)
-            nrec = len(dnas)
-            offs = (C.c_int64 * max(1, nrec))()
-            lens = (C.c_int64 * max(1, nrec))()
-            o = 0
-            for i, d in enumerate(dnas):
-                offs[i], lens[i] = o, len(d)
-                o += len(d)
-        oligos = [bytes(x) for x in oligos]
-        nq = len(oligos)
-        arr = (C.c_char_p * max(1, nq))(*oligos)
-        qlens = (C.c_int32 * max(1, nq))(*[len(x) for x in oligos])
+        blob, offs, lens, nrec = _pack_records(dnas, resident_ok=True)
+        arr, qlens, nq, _ = _pack_queries([bytes(x) for x in oligos])
         hs = (C.POINTER(_Hist) * max(1, nq))()
         totals = (ScanStats * max(1, nq))()
         self._check(self._L.fasim_scan_oligos_hist(self._h, arr, qlens, nq, blob, offs, lens, nrec, seg_first, seg_count, C.byref(p),
                                                    hs, totals))
-        self.last_totals = [self._stats_dict(totals[q]) for q in range(nq)]
+        self._totals(totals, nq)
         return [Hist(_native=hs[q]) for q in range(nq)]
 
     def score_variants(self, variants, dnas, p: Params | None = None, flank: int = 300, queries=None):
@@ -1628,24 +1485,9 @@ class Engine:
                 raise FasimError("score_variants: no queries given and no query set", E_ARG)
             queries = [self.rna]
         queries = [bytes(x) for x in queries]
-        nq = len(queries)
-        if isinstance(dnas, (bytes, bytearray)):
-            dnas = [bytes(dnas)]
-        if dnas is None:
-            blob, nrec = None, 1
-            offs = (C.c_int64 * 1)(0)
-            lens = (C.c_int64 * 1)(self.resident_len())
-        else:
-            blob = b"".join(dnas)
-            nrec = len(dnas)
-            offs = (C.c_int64 * max(1, nrec))()
-            lens = (C.c_int64 * max(1, nrec))()
-            o = 0
-            for i, d in enumerate(dnas):
-                offs[i], lens[i] = o, len(d)
-                o += len(d)
-        arr = (C.c_char_p * max(1, nq))(*queries)
-        qlens = (C.c_int32 * max(1, nq))(*[len(x) for x in queries])
+        # (dnas None: the whole resident buffer as record 0)
+        blob, offs, lens, nrec = _pack_records(dnas, rec_lens=[self.resident_len()] if dnas is None else None)
+        arr, qlens, nq, _ = _pack_queries(queries)
         vs, _keep = _variants_to_c(variants)
         nvar = len(variants)
         out = (_VariantScore * max(1, nq * nvar))()
@@ -1659,10 +1501,7 @@ class Engine:
         return values, encs, flags
 
     def _records_track(self, blob, offs, lens, nrec, p, rnas, bin, records, seg_first, seg_count):
-        nq = 0 if rnas is None else len(rnas)
-        nqo = max(1, nq)
-        arr = (C.c_char_p * nqo)(*(rnas or []))
-        qlens = (C.c_int32 * nqo)(*[len(r) for r in (rnas or [])])
+        arr, qlens, nq, nqo = _pack_queries(rnas)
         nout = nqo * max(1, nrec)
         outs = (C.POINTER(_Result) * nout)() if records else None
         trks = (C.POINTER(_Track) * nout)() if bin != 0 else None
@@ -1672,13 +1511,12 @@ class Engine:
                                                      bin, outs, trks, peaks, totals))
         if nq:
             self.m = len(rnas[-1])
-        self.last_totals = [self._stats_dict(totals[q]) for q in range(nqo)]
+        self._totals(totals, nqo)
         res = trk = None
         if records:
-            res = [[ScanResult(stats=self._stats_dict(outs[q * nrec + r].contents.stats), _native=outs[q * nrec + r])
-                    for r in range(nrec)] for q in range(nqo)]
+            res = self._wrap_results(outs, nqo, nrec)
         if trks is not None:
-            trk = [[Track(_native=trks[q * nrec + r]) for r in range(nrec)] for q in range(nqo)]
+            trk = _grid(Track, trks, nqo, nrec)
         pk = _peaks_from_c(peaks, nout * 4).reshape(nqo, nrec, 4, 3)
         if rnas is None:
             return (res[0] if res else None), (trk[0] if trk else None), pk[0]
@@ -1692,20 +1530,9 @@ class Engine:
         record and strand class (TRACK_CLASSES), (0, -1, -1) where the potential is zero.  rnas given: lists per lncRNA and a
         (nq, nrec, 4, 3) array.  Shards of a segment range merge with merge_tracks() / merge_peaks().  Totals: `self.last_totals`."""
         p = params or default_params()
-        if dnas is None:
-            if rec_lens is None:
-                raise FasimError("scan_records_track(None, ...) needs rec_lens (the records of the resident buffer)", E_ARG)
-            lens_l, blob = [int(x) for x in rec_lens], None
-        else:
-            lens_l = [len(d) for d in dnas]
-            blob = b"".join(dnas)
-        nrec = len(lens_l)
-        offs = (C.c_int64 * max(1, nrec))()
-        lens = (C.c_int64 * max(1, nrec))()
-        o = 0
-        for i, n in enumerate(lens_l):
-            offs[i], lens[i] = o, n
-            o += n
+        if dnas is None and rec_lens is None:
+            raise FasimError("scan_records_track(None, ...) needs rec_lens (the records of the resident buffer)", E_ARG)
+        blob, offs, lens, nrec = _pack_records(dnas, rec_lens)
         return self._records_track(blob, offs, lens, nrec, p, rnas, bin, records, seg_first, seg_count)
 
     def scan_regions_track(self, seq: bytes | None, spans, params: Params | None = None, rnas=None, bin: int = 0,
@@ -1713,15 +1540,7 @@ class Engine:
         """scan_records_track() for BED-style spans of one sequence (see scan_regions()): positions of the peaks and the tracks'
         bins are relative to each span's start."""
         p = params or default_params()
-        spans = [(int(s), int(e)) for s, e in spans]
-        nrec = len(spans)
-        if nrec == 0:
-            raise FasimError("scan_regions_track needs at least one span", E_ARG)
-        for k, (s, e) in enumerate(spans):
-            if s < 0 or e <= s or (seq is not None and e > len(seq)):
-                raise FasimError(f"span {k}: ({s}, {e}) is not a non-empty slice of the sequence", E_ARG)
-        offs = (C.c_int64 * nrec)(*[s for s, _ in spans])
-        lens = (C.c_int64 * nrec)(*[e - s for s, e in spans])
+        offs, lens, nrec = _pack_spans(seq, spans, "scan_regions_track")
         return self._records_track(seq, offs, lens, nrec, p, rnas, bin, records, seg_first, seg_count)
 
     def scan_regions(self, seq: bytes | None, spans, params: Params | None = None, rnas=None):
@@ -1730,27 +1549,15 @@ class Engine:
         nest, repeat and come in any order.  Returns what scan_records() returns, and result k is identical to
         scan_records([seq[s:e]]) of span k.  The call's totals are left in `self.last_totals`."""
         p = params or default_params()
-        spans = [(int(s), int(e)) for s, e in spans]
-        nrec = len(spans)
-        if nrec == 0:
-            raise FasimError("scan_regions needs at least one span", E_ARG)
-        for k, (s, e) in enumerate(spans):
-            if s < 0 or e <= s or (seq is not None and e > len(seq)):
-                raise FasimError(f"span {k}: ({s}, {e}) is not a non-empty slice of the sequence", E_ARG)
-        offs = (C.c_int64 * nrec)(*[s for s, _ in spans])
-        lens = (C.c_int64 * nrec)(*[e - s for s, e in spans])
-        nq = 0 if rnas is None else len(rnas)
-        arr = (C.c_char_p * max(1, nq))(*(rnas or []))
-        qlens = (C.c_int32 * max(1, nq))(*[len(r) for r in (rnas or [])])
-        nqo = max(1, nq)
+        offs, lens, nrec = _pack_spans(seq, spans, "scan_regions")
+        arr, qlens, nq, nqo = _pack_queries(rnas)
         outs = (C.POINTER(_Result) * (nqo * nrec))()
         totals = (ScanStats * nqo)()
         self._check(self._L.fasim_scan_records(self._h, arr, qlens, nq, seq, offs, lens, nrec, 0, -1, C.byref(p), outs, totals))
         if nq:
             self.m = len(rnas[-1])
-        self.last_totals = [self._stats_dict(totals[q]) for q in range(nqo)]
-        res = [[ScanResult(stats=self._stats_dict(outs[q * nrec + r].contents.stats), _native=outs[q * nrec + r]) for r in range(nrec)]
-               for q in range(nqo)]
+        self._totals(totals, nqo)
+        res = self._wrap_results(outs, nqo, nrec)
         return res[0] if rnas is None else res
 
 
@@ -1804,17 +1611,9 @@ def tfosorted(result: ScanResult, chr_name: str, start_genome: int, params: Para
     """-TFOsorted bytes for the (merged) records; host-side tail of the path."""
     L = lib()
     p = params or default_params()
-    text = C.c_void_p()
-    n = C.c_int64()
     rp, cnt, pp, plen = result.pointers()
-    rc = L.fasim_tfosorted_ex(rp or None, cnt, pp or C.addressof(_EMPTY_POOL), max(1, plen), chr_name.encode(),
-                              start_genome, C.byref(p), flags, C.byref(text), C.byref(n))
-    if rc != 0:
-        raise FasimError(f"fasim_tfosorted failed ({rc}): {L.fasim_last_error(None).decode()}")
-    try:
-        return C.string_at(text, n.value)
-    finally:
-        L.fasim_free(text)
+    return _text_call(L.fasim_tfosorted_ex, rp or None, cnt, pp or C.addressof(_EMPTY_POOL), max(1, plen), chr_name.encode(),
+                      start_genome, C.byref(p), flags, name="fasim_tfosorted", code=False)
 
 
 def tfoclass(result: ScanResult, level: int, chr_name: str, start_genome: int, dna_len: int, rna_name: str,
@@ -1822,17 +1621,9 @@ def tfoclass(result: ScanResult, level: int, chr_name: str, start_genome: int, d
     """-TFOclass<level>-<ds>-<lg> bedGraph bytes (print_cluster, Fasim-LongTarget.cpp:694) for the merged records."""
     L = lib()
     p = params or default_params()
-    text = C.c_void_p()
-    n = C.c_int64()
     rp, cnt, _, _ = result.pointers()
-    rc = L.fasim_tfoclass_ex(rp or None, cnt, level, chr_name.encode(), start_genome, dna_len, rna_name.encode(), C.byref(p),
-                             flags, C.byref(text), C.byref(n))
-    if rc != 0:
-        raise FasimError(f"fasim_tfoclass failed ({rc}): {L.fasim_last_error(None).decode()}")
-    try:
-        return C.string_at(text, n.value)
-    finally:
-        L.fasim_free(text)
+    return _text_call(L.fasim_tfoclass_ex, rp or None, cnt, level, chr_name.encode(), start_genome, dna_len, rna_name.encode(),
+                      C.byref(p), flags, name="fasim_tfoclass", code=False)
 
 
 def tail_outputs(result: ScanResult, chr_name: str, start_genome: int, dna_len: int, rna_name: str, params: Params | None = None,
@@ -1938,15 +1729,7 @@ def variants_tsv(variants, values, encs, flags, flank: int, rna_name: str, match
     flat = np.frombuffer(sc, dtype=np.int32).reshape(max(1, n), 18)
     flat[:n, 0:8], flat[:n, 8:16], flat[:n, 16] = values, encs, flags
     mt = None if matched is None else (C.c_uint8 * max(1, n))(*[1 if x else 0 for x in matched])
-    text = C.c_void_p()
-    ln = C.c_int64()
-    rc = L.fasim_variants_tsv(vs, sc, n, flank, rna_name.encode(), mt, C.byref(text), C.byref(ln))
-    if rc != 0:
-        raise FasimError(f"fasim_variants_tsv failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
-    try:
-        return C.string_at(text, ln.value)
-    finally:
-        L.fasim_free(text)
+    return _text_call(L.fasim_variants_tsv, vs, sc, n, flank, rna_name.encode(), mt)
 
 
 def synth_dna(n: int, seed: int) -> bytes:

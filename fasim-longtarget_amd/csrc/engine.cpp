@@ -3,6 +3,244 @@
 #include "engine.h"
 
 // =====================================================================================================
+// The frame of a call (declared in engine.h): what the record-set entry points share before and after their scan
+// =====================================================================================================
+// FASIM_MAX_QUERY (fasim_hip.h): above it the reference's 16-bit stage-1 pass overruns its workspace
+static int refuse_long_query(fasim_engine* E, int64_t len, int index)
+{
+	char which[32] = "";
+	if (index >= 0) snprintf(which, sizeof which, " (query %d)", index);
+	return fail(E, FASIM_E_UNSUPPORTED, "query of %lld nt%s exceeds the limit of %d nt: above it the reference's 16-bit stage-1 pass "
+		"overruns its fixed workspace (stats.h:397) and its output is undefined", (long long)len, which, FASIM_MAX_QUERY);
+}
+
+int record_set_open(fasim_engine* E, const char* dna, const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, bool whole_ok, RecordSet& rs)
+{
+	rs.dna = dna; rs.rec_off = rec_off; rs.rec_len = rec_len; rs.nrec = nrec; rs.resident = dna == nullptr;
+	if (whole_ok && !dna && !rec_off && !rec_len && nrec == 1) {           // the whole resident buffer as one record: the engine knows its length
+		rs.whole_off = 0; rs.whole_len = (int64_t)E->dna_host.size();
+		if (rs.whole_len == 0) return fail(E, FASIM_E_ARG, "no resident DNA: call fasim_load_dna first");
+		rs.rec_off = &rs.whole_off; rs.rec_len = &rs.whole_len;
+	}
+	if (nrec < 1) return fail(E, FASIM_E_ARG, "a record set needs at least one record (nrec = %d)", nrec);
+	if (!rs.rec_off || !rs.rec_len) return fail(E, FASIM_E_ARG, "bad arguments");
+	return FASIM_OK;
+}
+
+int record_set_bounds(fasim_engine* E, const RecordSet& rs)
+{
+	// a host buffer has no length here: only the resident buffer bounds the offsets from above
+	if (rs.resident && E->dna_host.empty()) return fail(E, FASIM_E_ARG, "no resident DNA: call fasim_load_dna first");
+	const int64_t have = rs.resident ? (int64_t)E->dna_host.size() : INT64_MAX;
+	for (int32_t r = 0; r < rs.nrec; r++) {
+		const int64_t off = rs.rec_off[r], len = rs.rec_len[r];
+		if (len == 0) return fail(E, FASIM_E_ARG, "record %d is empty", r);
+		if (off < 0 || len < 0 || off > have || len > have - off)
+			return fail(E, FASIM_E_ARG, "record %d: offset %lld, length %lld lies outside the DNA buffer%s", r, (long long)off,
+				(long long)len, rs.resident ? " (the resident buffer of fasim_load_dna)" : "");
+		if (len > 0x7fffffffll) return fail(E, FASIM_E_ARG, "record %d: one record is limited to 2^31-1 nt (the reference's int positions)", r);
+	}
+	return FASIM_OK;
+}
+
+// argument checks of fasim_scan_records and the calls built on it, before any GPU work
+int check_records_args(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
+	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, const fasim_params* pp, bool whole_ok, RecordSet& rs)
+{
+	int rc = record_set_open(E, dna, rec_off, rec_len, nrec, whole_ok, rs); if (rc) return rc;
+	if (!pp || nq < 0) return fail(E, FASIM_E_ARG, "bad arguments");
+	if (pp->cutLength <= 0 || pp->cutLength - pp->overlapLength <= 0) return fail(E, FASIM_E_ARG, "cutLength/overlapLength invalid");
+	if (nq == 0) { rc = need_query(E); if (rc) return rc; }
+	else {
+		if (!rnas || !rna_lens) return fail(E, FASIM_E_ARG, "bad arguments");
+		for (int32_t q = 0; q < nq; q++) {
+			if (!rnas[q] || rna_lens[q] <= 0) return fail(E, FASIM_E_ARG, "empty query %d", q);
+			if (rna_lens[q] > FASIM_MAX_QUERY) return refuse_long_query(E, rna_lens[q], q);
+		}
+	}
+	return record_set_bounds(E, rs);
+}
+
+// the potential is the column maxima of the systolic scan kernel: no other kernel leaves them
+int check_track_source(fasim_engine* E, const int32_t* rna_lens, int32_t nq, const fasim_params* pp, const char* what)
+{
+	for (int q = 0; q < std::max(1, nq); q++) {
+		const int len = nq == 0 ? E->m : rna_lens[q];
+		if (!systolic_fits(len)) return fail(E, FASIM_E_UNSUPPORTED, "%s need a query of at least 113 nt (query %d has %d): shorter queries run on the striped kernels, which keep the reference's 8-bit column maxima only", what, q, len);
+	}
+	if (E->scan_v1) return fail(E, FASIM_E_UNSUPPORTED, "%s are not available under FASIM_SCAN_V1=1 (the striped kernels keep the reference's 8-bit column maxima only)", what);
+	if (pp->classicSim) return fail(E, FASIM_E_UNSUPPORTED, "%s are not available with classicSim (-F): that path has no stage-2 column maxima", what);
+	return FASIM_OK;
+}
+
+int workers_wanted(const fasim_engine* E)
+{
+	int nworkers = 10;
+	const char* envw = getenv("FASIM_WORKERS");
+	if (envw) nworkers = std::max(1, std::min(16, atoi(envw)));
+	if (E->opt_workers > 0) nworkers = std::min(16, E->opt_workers);
+	return nworkers;
+}
+
+int64_t seg_batch_given(const fasim_engine* E)
+{
+	const char* envb = getenv("FASIM_SEG_BATCH");
+	int64_t seg_batch = envb ? std::max(1, atoi(envb)) : 0;
+	if (E->opt_seg_batch > 0) seg_batch = E->opt_seg_batch;
+	return seg_batch;
+}
+
+int worker_set(fasim_engine* E, int wanted, std::vector<fasim_engine*>& ws)
+{
+	// worker 0 is this engine; the others are lazily created engines on the same device
+	while ((int)E->workers.size() < wanted - 1) {
+		fasim_engine* w = nullptr;
+		const int rc = fasim_engine_create(E->device, &w); if (rc) return fail(E, rc, "cannot create worker engine: %s", fasim_last_error(nullptr));
+		E->workers.push_back(w);
+	}
+	ws.assign(1, E);
+	for (int k = 0; k < wanted - 1; k++) ws.push_back(E->workers[(size_t)k]);
+	return FASIM_OK;
+}
+
+int worker_begin(fasim_engine* E, fasim_engine* w, const std::vector<int>& encs)
+{
+	HIPOK(hipSetDevice(E->device));
+	const int rc = upload(w, w->enc_ids, encs.data(), sizeof(int) * encs.size());
+	if (rc) { if (w != E) E->err = w->err; return rc; }
+	drain_timed(w);
+	for (int k = 0; k < FASIM_KERNEL_FAMILIES; k++) { w->kernel_ms[k] = 0; w->kernel_launches[k] = 0; }
+	w->sw_probs = 0; w->sw_ms = 0.0;
+	return FASIM_OK;
+}
+
+void worker_item_end(fasim_engine* w, fasim_scan_stats& st)
+{
+	(void)hipStreamSynchronize(w->st);
+	drain_timed(w);
+	for (int k = 0; k < FASIM_KERNEL_FAMILIES; k++) { st.kernel_ms[k] = w->kernel_ms[k]; st.kernel_launches[k] = w->kernel_launches[k]; w->kernel_ms[k] = 0; w->kernel_launches[k] = 0; }
+	st.striped_window_probs = w->sw_probs; st.striped_window_ms = w->sw_ms; w->sw_probs = 0; w->sw_ms = 0.0;
+}
+
+int workers_result(fasim_engine* E, const std::vector<fasim_engine*>& ws, const std::vector<int>& wrc)
+{
+	for (size_t wi = 0; wi < ws.size(); wi++) if (wrc[wi]) { if (ws[wi] != E) E->err = ws[wi]->err; return wrc[wi]; }
+	return FASIM_OK;
+}
+
+void tracks_drop(fasim_track** out_tracks, size_t nout)
+{
+	if (out_tracks) for (size_t o = 0; o < nout; o++) { fasim_track_free(out_tracks[o]); out_tracks[o] = nullptr; }
+}
+
+int track_req_init(fasim_engine* E, TrackReq& tr, int32_t bin, bool only, int nquery, const int64_t* rec_len, int nrec, fasim_track** out_tracks, fasim_peak* peaks)
+{
+	const size_t nout = (size_t)nquery * (size_t)nrec;
+	tr.bin = bin; tr.only = only; tr.nrec = nrec; tr.peaks = peaks;
+	tr.sat.assign(nout, 0); tr.mu.reset(new std::mutex[(size_t)nquery]);
+	if (peaks) for (size_t k = 0; k < nout * 4; k++) { peaks[k].value = 0; peaks[k].enc = -1; peaks[k].pos = -1; }
+	if (bin < 1) return FASIM_OK;
+	tr.nbins.resize((size_t)nrec);
+	for (int r = 0; r < nrec; r++) tr.nbins[(size_t)r] = (rec_len[r] + bin - 1) / bin;
+	tr.v.reserve(nout * 4);
+	for (size_t o = 0; o < nout; o++) {
+		out_tracks[o] = track_alloc(tr.nbins[o % (size_t)nrec], bin);
+		if (!out_tracks[o]) { tracks_drop(out_tracks, nout); return fail(E, FASIM_E_NOMEM, "out of memory"); }
+		for (int c = 0; c < FASIM_TRACK_CLASSES; c++) tr.v.push_back(out_tracks[o]->v[c]);
+	}
+	return FASIM_OK;
+}
+
+void sites_req_init(SitesReq& sr, int32_t min_value, int32_t max_gap, bool only, int nquery, int nrec)
+{
+	const size_t nout = (size_t)nquery * (size_t)nrec;
+	sr.min_value = min_value; sr.max_gap = max_gap; sr.only = only; sr.nrec = nrec;
+	sr.runs.resize(nout); sr.sat.assign(nout, 0); sr.mu.reset(new std::mutex[(size_t)nquery]);
+}
+
+void sites_drop(fasim_sites** out_sites, size_t nout)
+{
+	if (out_sites) for (size_t o = 0; o < nout; o++) { fasim_sites_free(out_sites[o]); out_sites[o] = nullptr; }
+}
+
+// Intervals of one record (the kernel's runs, or the sites of shards) -> its sites: per class sorted by start, an interval that
+// starts at most max_gap after the end of what has been united so far joins it (larger value, then smaller pos, then smaller enc);
+// the sites by (start, cls).  Consumes `v`.
+static fasim_sites* sites_build(std::vector<fasim_site>& v, int32_t min_value, int32_t max_gap)
+{
+	std::sort(v.begin(), v.end(), [](const fasim_site& a, const fasim_site& b) {
+		if (a.cls != b.cls) return a.cls < b.cls;
+		if (a.start != b.start) return a.start < b.start;
+		if (a.end != b.end) return a.end < b.end;
+		if (a.value != b.value) return a.value > b.value;
+		if (a.pos != b.pos) return a.pos < b.pos;
+		return a.enc < b.enc;
+	});
+	size_t n = 0;
+	for (size_t i = 0; i < v.size(); i++) {
+		const fasim_site x = v[i];
+		if (n > 0 && v[n - 1].cls == x.cls && x.start - v[n - 1].end <= (int64_t)max_gap) {
+			fasim_site& d = v[n - 1];
+			d.end = std::max(d.end, x.end);
+			if (x.value > d.value || (x.value == d.value && (x.pos < d.pos || (x.pos == d.pos && x.enc < d.enc)))) { d.value = x.value; d.pos = x.pos; d.enc = x.enc; }
+		} else v[n++] = x;
+	}
+	v.resize(n);
+	std::sort(v.begin(), v.end(), [](const fasim_site& a, const fasim_site& b) { return a.start != b.start ? a.start < b.start : a.cls < b.cls; });
+	fasim_sites* t = (fasim_sites*)calloc(1, sizeof(fasim_sites));
+	if (!t) return nullptr;
+	t->s = (fasim_site*)calloc(std::max<size_t>(1, n), sizeof(fasim_site));
+	if (!t->s) { free(t); return nullptr; }
+	t->n = (int64_t)n; t->min_value = min_value; t->max_gap = max_gap;
+	if (n) memcpy(t->s, v.data(), n * sizeof(fasim_site));
+	return t;
+}
+
+int sites_req_finish(fasim_engine* E, const SitesReq& sr, fasim_sites** out_sites, const std::function<int64_t(size_t)>& units)
+{
+	const size_t nout = sr.runs.size();
+	try {
+		std::vector<fasim_site> v;
+		for (size_t o = 0; o < nout; o++) {
+			const std::vector<HostRun>& runs = sr.runs[o];
+			v.clear(); v.reserve(runs.size());
+			for (const HostRun& h : runs) { fasim_site x; x.start = h.start; x.end = h.end; x.pos = h.pos; x.value = h.value; x.enc = h.enc; x.cls = h.cls; x.reserved = 0; v.push_back(x); }
+			out_sites[o] = sites_build(v, sr.min_value, sr.max_gap);
+			if (!out_sites[o]) { sites_drop(out_sites, nout); return fail(E, FASIM_E_NOMEM, "out of memory"); }
+			out_sites[o]->units = units(o); out_sites[o]->saturated_units = sr.sat[o]; out_sites[o]->raw_runs = (int64_t)runs.size();
+		}
+	} catch (const std::bad_alloc&) { sites_drop(out_sites, nout); return fail(E, FASIM_E_NOMEM, "out of memory"); }
+	return FASIM_OK;
+}
+
+// fasim_scan_records_sites; `rs` hands the resolved record set to fasim_scan_records_sites_aligned (engine_site_align.cpp)
+int scan_records_sites(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
+	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
+	int32_t min_value, int32_t max_gap, fasim_result** out_results, fasim_sites** out_sites, fasim_scan_stats* totals, RecordSet& rs)
+{
+	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
+	if (!out_sites) return fail(E, FASIM_E_ARG, "bad arguments");
+	if (min_value < 1 || min_value > 16383) return fail(E, FASIM_E_ARG, "sites: min_value %d lies outside [1, 16383]", min_value);
+	if (max_gap < 0) return fail(E, FASIM_E_ARG, "sites: max_gap %d is negative", max_gap);
+	int rc = check_records_args(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, pp, true, rs);
+	if (rc) return rc;
+	const int nquery = std::max(1, nq);
+	const size_t nout = (size_t)nquery * (size_t)nrec;
+	// the sites are runs of the column maxima of the systolic scan kernel: the refusals are those of the potential tracks
+	rc = check_track_source(E, rna_lens, nq, pp, "sites"); if (rc) return rc;
+	for (size_t o = 0; o < nout; o++) out_sites[o] = nullptr;
+	if (out_results) for (size_t o = 0; o < nout; o++) out_results[o] = nullptr;
+	SitesReq sr;
+	sites_req_init(sr, min_value, max_gap, out_results == nullptr, nquery, nrec);
+	OwnResults res(out_results, nout);
+	rc = scan_records_core(E, rnas, rna_lens, nq, dna, rs.rec_off, rs.rec_len, nrec, seg_first, seg_count, pp, res.outs, totals, { &sr });
+	if (rc) return rc;
+	rc = sites_req_finish(E, sr, out_sites, [&](size_t o) { return res.outs[o]->stats.units; });
+	if (rc && out_results) for (size_t o = 0; o < nout; o++) { fasim_result_free(out_results[o]); out_results[o] = nullptr; }
+	return rc;
+}
+
+// =====================================================================================================
 // C-ABI
 // =====================================================================================================
 extern "C" {
@@ -130,15 +368,6 @@ int fasim_set_option(fasim_engine* E, const char* key, int32_t value)
 	else if (!strcmp(key, "striped_window")) E->striped_window = value > 0;   // 1: every k_striped launch on the HBM-window variant (tests)
 	else return fail(E, FASIM_E_ARG, "unknown option %s", key);
 	return FASIM_OK;
-}
-
-// FASIM_MAX_QUERY (fasim_hip.h): above it the reference's 16-bit stage-1 pass overruns its workspace
-static int refuse_long_query(fasim_engine* E, int64_t len, int index)
-{
-	char which[32] = "";
-	if (index >= 0) snprintf(which, sizeof which, " (query %d)", index);
-	return fail(E, FASIM_E_UNSUPPORTED, "query of %lld nt%s exceeds the limit of %d nt: above it the reference's 16-bit stage-1 pass "
-		"overruns its fixed workspace (stats.h:397) and its output is undefined", (long long)len, which, FASIM_MAX_QUERY);
 }
 
 int fasim_set_query(fasim_engine* E, const char* rna, int32_t len)
@@ -400,13 +629,7 @@ int fasim_load_dna(fasim_engine* E, const char* dna, int64_t dna_len)
 	return FASIM_OK;
 }
 
-int64_t fasim_segment_count(int64_t dna_len, const fasim_params* p)
-{
-	// cutSequence (fastsim.h:71-90): pos += cut - overlap while pos < size
-	if (dna_len <= 0 || !p || p->cutLength - p->overlapLength <= 0) return 0;
-	const int64_t step = p->cutLength - p->overlapLength;
-	return (dna_len + step - 1) / step;
-}
+int64_t fasim_segment_count(int64_t dna_len, const fasim_params* p) { return segment_count(dna_len, p); }
 
 void fasim_result_free(fasim_result* r)
 {
@@ -467,44 +690,14 @@ int fasim_scan_queries(fasim_engine* E, const char* const* rnas, const int32_t* 
 	return scan_core(E, rnas, rna_lens, nq, dna, dna_len, seg_first, seg_count, pp, outs);
 }
 
-// argument checks of fasim_scan_records (and fasim_scan_records_track), before any GPU work
-}      // (shared with engine_hist.cpp: C++ linkage, declared in engine.h)
-int check_records_args(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
-	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, const fasim_params* pp)
-{
-	if (nrec < 1) return fail(E, FASIM_E_ARG, "a record set needs at least one record (nrec = %d)", nrec);
-	if (!rec_off || !rec_len || !pp || nq < 0) return fail(E, FASIM_E_ARG, "bad arguments");
-	if (pp->cutLength <= 0 || pp->cutLength - pp->overlapLength <= 0) return fail(E, FASIM_E_ARG, "cutLength/overlapLength invalid");
-	if (nq == 0) { int rc = need_query(E); if (rc) return rc; }
-	else {
-		if (!rnas || !rna_lens) return fail(E, FASIM_E_ARG, "bad arguments");
-		for (int32_t q = 0; q < nq; q++) {
-			if (!rnas[q] || rna_lens[q] <= 0) return fail(E, FASIM_E_ARG, "empty query %d", q);
-			if (rna_lens[q] > FASIM_MAX_QUERY) return refuse_long_query(E, rna_lens[q], q);
-		}
-	}
-	// a host buffer has no length here: only the resident buffer bounds the offsets from above
-	const bool resident = dna == nullptr;
-	if (resident && E->dna_host.empty()) return fail(E, FASIM_E_ARG, "no resident DNA: call fasim_load_dna first");
-	const int64_t have = resident ? (int64_t)E->dna_host.size() : INT64_MAX;
-	for (int32_t r = 0; r < nrec; r++) {
-		if (rec_len[r] == 0) return fail(E, FASIM_E_ARG, "record %d is empty", r);
-		if (rec_off[r] < 0 || rec_len[r] < 0 || rec_off[r] > have || rec_len[r] > have - rec_off[r])
-			return fail(E, FASIM_E_ARG, "record %d: offset %lld, length %lld lies outside the DNA buffer%s", r, (long long)rec_off[r],
-				(long long)rec_len[r], resident ? " (the resident buffer of fasim_load_dna)" : "");
-		if (rec_len[r] > 0x7fffffffll) return fail(E, FASIM_E_ARG, "record %d: one record is limited to 2^31-1 nt (the reference's int positions)", r);
-	}
-	return FASIM_OK;
-}
-extern "C" {
-
 int fasim_scan_records(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
 	fasim_result** outs, fasim_scan_stats* totals)
 {
 	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
 	if (!outs) return fail(E, FASIM_E_ARG, "bad arguments");
-	const int rc = check_records_args(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, pp);
+	RecordSet rs;
+	const int rc = check_records_args(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, pp, false, rs);
 	if (rc) return rc;
 	return scan_records_core(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, outs, totals);
 }
@@ -516,20 +709,6 @@ void fasim_track_free(fasim_track* t)
 	for (int c = 0; c < FASIM_TRACK_CLASSES; c++) free(t->v[c]);
 	free(t);
 }
-
-// the potential is the column maxima of the systolic scan kernel: no other kernel leaves them
-}      // (shared with engine_hist.cpp: C++ linkage, declared in engine.h)
-int check_track_source(fasim_engine* E, const int32_t* rna_lens, int32_t nq, const fasim_params* pp, const char* what)
-{
-	for (int q = 0; q < std::max(1, nq); q++) {
-		const int len = nq == 0 ? E->m : rna_lens[q];
-		if (!systolic_fits(len)) return fail(E, FASIM_E_UNSUPPORTED, "%s need a query of at least 113 nt (query %d has %d): shorter queries run on the striped kernels, which keep the reference's 8-bit column maxima only", what, q, len);
-	}
-	if (E->scan_v1) return fail(E, FASIM_E_UNSUPPORTED, "%s are not available under FASIM_SCAN_V1=1 (the striped kernels keep the reference's 8-bit column maxima only)", what);
-	if (pp->classicSim) return fail(E, FASIM_E_UNSUPPORTED, "%s are not available with classicSim (-F): that path has no stage-2 column maxima", what);
-	return FASIM_OK;
-}
-extern "C" {
 
 int fasim_scan_track(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna, int64_t dna_len,
 	int64_t seg_first, int64_t seg_count, const fasim_params* pp, int32_t bin, fasim_result** out_results, fasim_track** out_tracks)
@@ -555,20 +734,11 @@ int fasim_scan_track(fasim_engine* E, const char* const* rnas, const int32_t* rn
 	} else if (dna_len <= 0) return fail(E, FASIM_E_ARG, "bad arguments");
 	if (dna_len > 0x7fffffffll) return fail(E, FASIM_E_ARG, "one record is limited to 2^31-1 nt (the reference's int positions)");
 	TrackReq tr;
-	tr.bin = bin; tr.only = out_results == nullptr; tr.nbins.assign(1, (dna_len + bin - 1) / bin);
-	tr.sat.assign((size_t)nquery, 0); tr.mu.reset(new std::mutex[(size_t)nquery]);
-	auto drop = [&]() { for (int q = 0; q < nquery; q++) { fasim_track_free(out_tracks[q]); out_tracks[q] = nullptr; } };
-	for (int q = 0; q < nquery; q++) {
-		out_tracks[q] = track_alloc(tr.nbins[0], bin);
-		if (!out_tracks[q]) { drop(); return fail(E, FASIM_E_NOMEM, "out of memory"); }
-		for (int c = 0; c < FASIM_TRACK_CLASSES; c++) tr.v.push_back(out_tracks[q]->v[c]);
-	}
-	std::vector<fasim_result*> own((size_t)nquery, nullptr);
-	fasim_result** outs = out_results ? out_results : own.data();
-	const int rc = scan_core(E, nq ? rnas : nullptr, nq ? rna_lens : nullptr, nq, dna, dna_len, seg_first, seg_count, pp, outs, { &tr });
-	if (rc) { drop(); return rc; }
-	for (int q = 0; q < nquery; q++) { out_tracks[q]->units = outs[q]->stats.units; out_tracks[q]->saturated_units = tr.sat[(size_t)q]; }
-	for (fasim_result* r : own) fasim_result_free(r);
+	int rc = track_req_init(E, tr, bin, out_results == nullptr, nquery, &dna_len, 1, out_tracks, nullptr); if (rc) return rc;
+	OwnResults res(out_results, (size_t)nquery);
+	rc = scan_core(E, nq ? rnas : nullptr, nq ? rna_lens : nullptr, nq, dna, dna_len, seg_first, seg_count, pp, res.outs, { &tr });
+	if (rc) { tracks_drop(out_tracks, (size_t)nquery); return rc; }
+	for (int q = 0; q < nquery; q++) { out_tracks[q]->units = res.outs[q]->stats.units; out_tracks[q]->saturated_units = tr.sat[(size_t)q]; }
 	return FASIM_OK;
 }
 
@@ -581,7 +751,8 @@ int fasim_scan_records_track(fasim_engine* E, const char* const* rnas, const int
 	if (bin < 0) return fail(E, FASIM_E_ARG, "track bin width %d: must be at least 1, or 0 for peaks only", bin);
 	if (bin == 0 && (out_tracks || !out_peaks)) return fail(E, FASIM_E_ARG, "bin 0 is peaks only: out_tracks must be NULL and out_peaks must not");
 	if (bin >= 1 && !out_tracks) return fail(E, FASIM_E_ARG, "bin %d needs out_tracks", bin);
-	int rc = check_records_args(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, pp);
+	RecordSet rs;
+	int rc = check_records_args(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, pp, false, rs);
 	if (rc) return rc;
 	const int nquery = std::max(1, nq);
 	const size_t nout = (size_t)nquery * (size_t)nrec;
@@ -589,26 +760,11 @@ int fasim_scan_records_track(fasim_engine* E, const char* const* rnas, const int
 	if (out_tracks) for (size_t o = 0; o < nout; o++) out_tracks[o] = nullptr;
 	if (out_results) for (size_t o = 0; o < nout; o++) out_results[o] = nullptr;
 	TrackReq tr;
-	tr.bin = bin; tr.only = out_results == nullptr; tr.nrec = nrec; tr.peaks = out_peaks;
-	tr.sat.assign(nout, 0); tr.mu.reset(new std::mutex[(size_t)nquery]);
-	if (out_peaks) for (size_t k = 0; k < nout * 4; k++) { out_peaks[k].value = 0; out_peaks[k].enc = -1; out_peaks[k].pos = -1; }
-	auto drop = [&]() { if (out_tracks) for (size_t o = 0; o < nout; o++) { fasim_track_free(out_tracks[o]); out_tracks[o] = nullptr; } };
-	if (bin >= 1) {
-		tr.nbins.resize((size_t)nrec);
-		for (int r = 0; r < nrec; r++) tr.nbins[(size_t)r] = (rec_len[r] + bin - 1) / bin;
-		tr.v.reserve(nout * 4);
-		for (size_t o = 0; o < nout; o++) {
-			out_tracks[o] = track_alloc(tr.nbins[o % (size_t)nrec], bin);
-			if (!out_tracks[o]) { drop(); return fail(E, FASIM_E_NOMEM, "out of memory"); }
-			for (int c = 0; c < FASIM_TRACK_CLASSES; c++) tr.v.push_back(out_tracks[o]->v[c]);
-		}
-	}
-	std::vector<fasim_result*> own(out_results ? 0 : nout, nullptr);
-	fasim_result** outs = out_results ? out_results : own.data();
-	rc = scan_records_core(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, outs, totals, { &tr });
-	if (rc) { drop(); return rc; }
-	if (out_tracks) for (size_t o = 0; o < nout; o++) { out_tracks[o]->units = outs[o]->stats.units; out_tracks[o]->saturated_units = tr.sat[o]; }
-	for (fasim_result* r : own) fasim_result_free(r);
+	rc = track_req_init(E, tr, bin, out_results == nullptr, nquery, rec_len, nrec, out_tracks, out_peaks); if (rc) return rc;
+	OwnResults res(out_results, nout);
+	rc = scan_records_core(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, res.outs, totals, { &tr });
+	if (rc) { tracks_drop(out_tracks, nout); return rc; }
+	if (out_tracks) for (size_t o = 0; o < nout; o++) { out_tracks[o]->units = res.outs[o]->stats.units; out_tracks[o]->saturated_units = tr.sat[o]; }
 	return FASIM_OK;
 }
 
@@ -638,7 +794,8 @@ int fasim_scan_tfo_profile(fasim_engine* E, const char* const* rnas, const int32
 {
 	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
 	if (!out_profiles) return fail(E, FASIM_E_ARG, "bad arguments");
-	int rc = check_records_args(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, pp);
+	RecordSet rs;
+	int rc = check_records_args(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, pp, false, rs);
 	if (rc) return rc;
 	const int nquery = std::max(1, nq);
 	const size_t nout = (size_t)nquery * (size_t)nrec, nprof = per_record ? nout : (size_t)nquery;
@@ -657,10 +814,8 @@ int fasim_scan_tfo_profile(fasim_engine* E, const char* const* rnas, const int32
 		if (!out_profiles[o]) { drop(); return fail(E, FASIM_E_NOMEM, "out of memory"); }
 		for (int c = 0; c < FASIM_TRACK_CLASSES; c++) pr.v.push_back(out_profiles[o]->v[c]);
 	}
-	std::vector<fasim_result*> own(out_results ? 0 : nout, nullptr);
-	fasim_result** outs = out_results ? out_results : own.data();
-	rc = scan_records_core(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, outs, totals, { &pr });
-	for (fasim_result* r : own) fasim_result_free(r);
+	OwnResults res(out_results, nout);
+	rc = scan_records_core(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, res.outs, totals, { &pr });
 	if (rc) { drop(); return rc; }
 	for (size_t o = 0; o < nprof; o++) { out_profiles[o]->units = pr.units[o]; out_profiles[o]->saturated_units = pr.sat[o]; }
 	return FASIM_OK;
@@ -719,9 +874,8 @@ int fasim_peaks_merge(const fasim_peak* const* parts, int32_t nparts, int64_t n,
 int fasim_screen_tsv(const fasim_region* regions, const int64_t* segments, const fasim_peak* peaks, int64_t n, char** text, int64_t* text_len)
 {
 	if (n < 0 || !text || !text_len || (n > 0 && (!regions || !segments || !peaks))) return fail(nullptr, FASIM_E_ARG, "bad arguments");
-	static const char* const names[FASIM_TRACK_CLASSES] = { "ParaPlus", "ParaMinus", "AntiMinus", "AntiPlus" };
 	std::string o = "line\tname\tchrom\tstart\tend\tsegments";
-	for (const char* c : names) { o += "\t"; o += c; o += "\t"; o += c; o += "_pos\t"; o += c; o += "_rule"; }
+	for (const char* c : CLASS_NAMES) { o += "\t"; o += c; o += "\t"; o += c; o += "_pos\t"; o += c; o += "_rule"; }
 	o += "\n";
 	for (int64_t k = 0; k < n; k++) {
 		const fasim_region& g = regions[k];
@@ -768,12 +922,11 @@ int fasim_track_bedgraph(const fasim_track* t, const char* chr, int64_t start_ge
 	if (!t || !chr || !rna_name || !text || !text_len || t->bin < 1) return fail(nullptr, FASIM_E_ARG, "bad arguments");
 	if (min_value < 1) return fail(nullptr, FASIM_E_ARG, "min_value %d: must be at least 1 (bins of value 0 are never written)", min_value);
 	if (dna_len <= 0 || (dna_len + t->bin - 1) / t->bin != t->nbins) return fail(nullptr, FASIM_E_ARG, "dna_len %lld does not match a track of %lld bins of %d", (long long)dna_len, (long long)t->nbins, t->bin);
-	static const char* const names[FASIM_TRACK_CLASSES] = { "ParaPlus", "ParaMinus", "AntiMinus", "AntiPlus" };
 	const int64_t sg = start_genome - 1;                  // 0-based genome position of the record's first base
 	std::string o;
 	char line[96];
 	for (int c = 0; c < FASIM_TRACK_CLASSES; c++) {
-		o += "track type=bedGraph name='"; o += rna_name; o += " potential ("; o += names[c]; o += ")'\n";
+		o += "track type=bedGraph name='"; o += rna_name; o += " potential ("; o += CLASS_NAMES[c]; o += ")'\n";
 		const uint16_t* v = t->v[c];
 		for (int64_t b = 0; b < t->nbins; ) {
 			int64_t e = b + 1;
@@ -796,84 +949,12 @@ void fasim_sites_free(fasim_sites* t)
 	free(t);
 }
 
-// Intervals of one record (the kernel's runs, or the sites of shards) -> its sites: per class sorted by start, an interval that
-// starts at most max_gap after the end of what has been united so far joins it (larger value, then smaller pos, then smaller enc);
-// the sites by (start, cls).  Consumes `v`.
-static fasim_sites* sites_build(std::vector<fasim_site>& v, int32_t min_value, int32_t max_gap)
-{
-	std::sort(v.begin(), v.end(), [](const fasim_site& a, const fasim_site& b) {
-		if (a.cls != b.cls) return a.cls < b.cls;
-		if (a.start != b.start) return a.start < b.start;
-		if (a.end != b.end) return a.end < b.end;
-		if (a.value != b.value) return a.value > b.value;
-		if (a.pos != b.pos) return a.pos < b.pos;
-		return a.enc < b.enc;
-	});
-	size_t n = 0;
-	for (size_t i = 0; i < v.size(); i++) {
-		const fasim_site x = v[i];
-		if (n > 0 && v[n - 1].cls == x.cls && x.start - v[n - 1].end <= (int64_t)max_gap) {
-			fasim_site& d = v[n - 1];
-			d.end = std::max(d.end, x.end);
-			if (x.value > d.value || (x.value == d.value && (x.pos < d.pos || (x.pos == d.pos && x.enc < d.enc)))) { d.value = x.value; d.pos = x.pos; d.enc = x.enc; }
-		} else v[n++] = x;
-	}
-	v.resize(n);
-	std::sort(v.begin(), v.end(), [](const fasim_site& a, const fasim_site& b) { return a.start != b.start ? a.start < b.start : a.cls < b.cls; });
-	fasim_sites* t = (fasim_sites*)calloc(1, sizeof(fasim_sites));
-	if (!t) return nullptr;
-	t->s = (fasim_site*)calloc(std::max<size_t>(1, n), sizeof(fasim_site));
-	if (!t->s) { free(t); return nullptr; }
-	t->n = (int64_t)n; t->min_value = min_value; t->max_gap = max_gap;
-	if (n) memcpy(t->s, v.data(), n * sizeof(fasim_site));
-	return t;
-}
-
 int fasim_scan_records_sites(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
 	int32_t min_value, int32_t max_gap, fasim_result** out_results, fasim_sites** out_sites, fasim_scan_stats* totals)
 {
-	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
-	if (!out_sites) return fail(E, FASIM_E_ARG, "bad arguments");
-	if (min_value < 1 || min_value > 16383) return fail(E, FASIM_E_ARG, "sites: min_value %d lies outside [1, 16383]", min_value);
-	if (max_gap < 0) return fail(E, FASIM_E_ARG, "sites: max_gap %d is negative", max_gap);
-	const int64_t whole_off = 0, whole_len = (int64_t)E->dna_host.size();
-	if (!dna && !rec_off && !rec_len && nrec == 1) {           // the whole resident buffer as one record: the engine knows its length
-		if (whole_len == 0) return fail(E, FASIM_E_ARG, "no resident DNA: call fasim_load_dna first");
-		rec_off = &whole_off; rec_len = &whole_len;
-	}
-	int rc = check_records_args(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, pp);
-	if (rc) return rc;
-	const int nquery = std::max(1, nq);
-	const size_t nout = (size_t)nquery * (size_t)nrec;
-	// the sites are runs of the column maxima of the systolic scan kernel: the refusals are those of the potential tracks
-	rc = check_track_source(E, rna_lens, nq, pp, "sites"); if (rc) return rc;
-	for (size_t o = 0; o < nout; o++) out_sites[o] = nullptr;
-	if (out_results) for (size_t o = 0; o < nout; o++) out_results[o] = nullptr;
-	SitesReq sr;
-	sr.min_value = min_value; sr.max_gap = max_gap; sr.only = out_results == nullptr; sr.nrec = nrec;
-	sr.runs.resize(nout); sr.sat.assign(nout, 0); sr.mu.reset(new std::mutex[(size_t)nquery]);
-	std::vector<fasim_result*> own(out_results ? 0 : nout, nullptr);
-	fasim_result** outs = out_results ? out_results : own.data();
-	rc = scan_records_core(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, outs, totals, { &sr });
-	if (rc) { for (fasim_result* r : own) fasim_result_free(r); return rc; }
-	auto drop = [&]() {
-		for (size_t o = 0; o < nout; o++) { fasim_sites_free(out_sites[o]); out_sites[o] = nullptr; if (out_results) { fasim_result_free(out_results[o]); out_results[o] = nullptr; } }
-		for (fasim_result* r : own) fasim_result_free(r);
-	};
-	try {
-		std::vector<fasim_site> v;
-		for (size_t o = 0; o < nout; o++) {
-			const std::vector<HostRun>& runs = sr.runs[o];
-			v.clear(); v.reserve(runs.size());
-			for (const HostRun& h : runs) { fasim_site x; x.start = h.start; x.end = h.end; x.pos = h.pos; x.value = h.value; x.enc = h.enc; x.cls = h.cls; x.reserved = 0; v.push_back(x); }
-			out_sites[o] = sites_build(v, min_value, max_gap);
-			if (!out_sites[o]) { drop(); return fail(E, FASIM_E_NOMEM, "out of memory"); }
-			out_sites[o]->units = outs[o]->stats.units; out_sites[o]->saturated_units = sr.sat[o]; out_sites[o]->raw_runs = (int64_t)runs.size();
-		}
-	} catch (const std::bad_alloc&) { drop(); return fail(E, FASIM_E_NOMEM, "out of memory"); }
-	for (fasim_result* r : own) fasim_result_free(r);
-	return FASIM_OK;
+	RecordSet rs;
+	return scan_records_sites(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, min_value, max_gap, out_results, out_sites, totals, rs);
 }
 
 int fasim_sites_merge(const fasim_sites* const* parts, int32_t nparts, fasim_sites** out)
@@ -906,7 +987,6 @@ int fasim_sites_bed(const fasim_sites* t, const char* chr, int64_t start_genome,
 	int32_t header, char** text, int64_t* text_len)
 {
 	if (!t || !chr || !rna_name || !text || !text_len || t->n < 0 || (t->n > 0 && !t->s)) return fail(nullptr, FASIM_E_ARG, "bad arguments");
-	static const char* const names[FASIM_TRACK_CLASSES] = { "ParaPlus", "ParaMinus", "AntiMinus", "AntiPlus" };
 	const int64_t sg = start_genome - 1;                  // 0-based genome position of the record's first base
 	std::string o;
 	char line[160];
@@ -914,7 +994,7 @@ int fasim_sites_bed(const fasim_sites* t, const char* chr, int64_t start_genome,
 	for (int64_t i = 0; i < t->n; i++) {
 		const fasim_site& x = t->s[i];
 		if (x.cls < 0 || x.cls >= FASIM_TRACK_CLASSES || x.enc < 0 || x.enc >= 48) return fail(nullptr, FASIM_E_ARG, "site %lld has class %d and encoding %d", (long long)i, x.cls, x.enc);
-		const int n = snprintf(line, sizeof line, "\t%lld\t%lld\t%s\t%d\t%c\t%lld\t%d", (long long)(sg + x.start), (long long)(sg + x.end), names[x.cls], x.value,
+		const int n = snprintf(line, sizeof line, "\t%lld\t%lld\t%s\t%d\t%c\t%lld\t%d", (long long)(sg + x.start), (long long)(sg + x.end), CLASS_NAMES[x.cls], x.value,
 			(x.cls == 0 || x.cls == 3) ? '+' : '-', (long long)(sg + x.pos), enc_info(x.enc).rule);
 		o += chr; o.append(line, (size_t)n);
 		if (record_name) { o += "\t"; o += record_name; }

@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <map>
 #include <memory>
 #include <string>
@@ -29,6 +30,7 @@
 #include <vector>
 
 #include "../../include/fasim_hip.h"
+#include "call_plan.h"
 #include "device_types.h"
 #include "host_post.h"
 #include "kernels.h"
@@ -400,14 +402,7 @@ inline bool hazard_snapshots_enabled(const fasim_engine* E) { static const bool 
 // What one batch leaves after its scan phase (stages 1+2) and what its stage 3 needs: host-side hit lists and segment
 // tables, plus a pointer to the target codes that stay resident on the owner engine.  Stage 3 is separable by unit range
 // (stage3_range), so near the end of a scan a batch publishes its stage 3 as sub-tasks that idle workers take over.
-// Segments of one scan call, numbered globally record after record (a single-record scan is the one-record case).  Entry k
-// is the k-th segment of the call's selected range: its record, its index within the record, its offset in the call's DNA
-// buffer and its length.
-struct SegTable {
-	std::vector<int32_t> rec, len;
-	std::vector<int64_t> idx, off;
-	int64_t size() const { return (int64_t)rec.size(); }
-};
+// (the segment table of a call, SegTable, and the cuts into batches: call_plan.h)
 
 // ---- products of a scan: what a call takes from k_scan's column and row maxima besides the hits -----------------------------------
 struct BatchCtx;
@@ -610,9 +605,61 @@ int batch_encode(fasim_engine* E, const char* dna, const SegTable& T, const uint
 // engine_hist.cpp: the request of a call and its results
 bool hist_req_init(HistReq& hr, fasim_hist** out_hists, int nquery, const int32_t* qlens, const int64_t* rec_len, int nrec, const fasim_params& p, bool only);
 int hist_req_finish(fasim_engine* E, HistReq& hr, fasim_hist** out_hists, int nquery);
+
+// ---- the frame of a call (engine.cpp; the pure part is call_plan.h; DESIGN.md "the frame of a call") ----------------------------------
+// The record set of a call as its entry point got it, resolved: `dna` NULL stands for the resident buffer, and an entry point that
+// takes "dna, rec_off and rec_len all NULL, nrec 1" as the whole resident buffer gets that record from here (whole_off, whole_len).
+struct RecordSet {
+	const char* dna = nullptr; const int64_t* rec_off = nullptr; const int64_t* rec_len = nullptr; int32_t nrec = 0;
+	bool resident = false;
+	int64_t whole_off = 0, whole_len = 0;
+	RecordSet() = default;
+	RecordSet(const RecordSet&) = delete;
+	RecordSet& operator=(const RecordSet&) = delete;
+	const char* host(const fasim_engine* E) const { return dna ? dna : E->dna_host.data(); }
+};
+// The record-set check of every entry point, in two steps, because the callers' own checks (cutLength, queries, ...) have always
+// stood between them.  record_set_open: the whole-resident-buffer record (whole_ok), nrec, the arrays.  record_set_bounds: resident
+// DNA present, no empty record, every record inside the (resident) buffer and at most 2^31-1 nt.
+int record_set_open(fasim_engine* E, const char* dna, const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, bool whole_ok, RecordSet& rs);
+int record_set_bounds(fasim_engine* E, const RecordSet& rs);
+// both steps around the checks of the lncRNA entry points (pp, nq, cutLength / overlapLength, the queries or the engine's own)
 int check_records_args(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
-	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, const fasim_params* pp);
+	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, const fasim_params* pp, bool whole_ok, RecordSet& rs);
 int check_track_source(fasim_engine* E, const int32_t* rna_lens, int32_t nq, const fasim_params* pp, const char* what = "potential tracks");
+// the call's option / environment: worker engines wanted (FASIM_WORKERS, option workers) and a fixed batch (FASIM_SEG_BATCH, option
+// seg_batch; 0: none given)
+int workers_wanted(const fasim_engine* E);
+int64_t seg_batch_given(const fasim_engine* E);
+// ws = E and its first wanted - 1 worker engines on the same device, created where missing
+int worker_set(fasim_engine* E, int wanted, std::vector<fasim_engine*>& ws);
+// worker w of E's call before its first item: the encodings up, the kernel timers drained and zeroed
+int worker_begin(fasim_engine* E, fasim_engine* w, const std::vector<int>& encs);
+// ... after each item: the stream synchronised, the timers into the item's stats and zeroed
+void worker_item_end(fasim_engine* w, fasim_scan_stats& st);
+// ... and when all have joined: the first worker's error wins, with its text on E
+int workers_result(fasim_engine* E, const std::vector<fasim_engine*>& ws, const std::vector<int>& wrc);
+// The results a call needs but its caller did not ask for: `outs` is the caller's array or one of `n` that dies with this object.
+struct OwnResults {
+	std::vector<fasim_result*> own;
+	fasim_result** outs;
+	OwnResults(fasim_result** wanted, size_t n) : own(wanted ? 0 : n, nullptr), outs(wanted ? wanted : own.data()) {}
+	~OwnResults() { for (fasim_result* r : own) fasim_result_free(r); }
+	OwnResults(const OwnResults&) = delete;
+	OwnResults& operator=(const OwnResults&) = delete;
+};
+// a TrackReq over nquery x nrec outputs: with bin >= 1 out_tracks[o] is allocated (all released and NULL again on failure) and tr.v
+// points into them; bin 0: peaks only
+int track_req_init(fasim_engine* E, TrackReq& tr, int32_t bin, bool only, int nquery, const int64_t* rec_len, int nrec, fasim_track** out_tracks, fasim_peak* peaks);
+void tracks_drop(fasim_track** out_tracks, size_t nout);
+// a SitesReq over nquery x nrec outputs, and its runs as site lists: out_sites[o] with units(o) units (all released and NULL again on failure)
+void sites_req_init(SitesReq& sr, int32_t min_value, int32_t max_gap, bool only, int nquery, int nrec);
+int sites_req_finish(fasim_engine* E, const SitesReq& sr, fasim_sites** out_sites, const std::function<int64_t(size_t)>& units);
+void sites_drop(fasim_sites** out_sites, size_t nout);
+// fasim_scan_records_sites; `rs` hands the resolved record set to fasim_scan_records_sites_aligned (engine_site_align.cpp)
+int scan_records_sites(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
+	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
+	int32_t min_value, int32_t max_gap, fasim_result** out_results, fasim_sites** out_sites, fasim_scan_stats* totals, RecordSet& rs);
 int sim_forward_units(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, const int32_t* unit_len_dev, const int32_t* unit_len_host,
 	int first, int nunit, const int64_t* mins, std::atomic<int>* ready, std::vector<std::vector<fasim_sim_node>>& lists);
 int sim_resweep_rounds(fasim_engine* E, const uint8_t* tcodes_dev, int tstride, const int32_t* unit_len_dev, const int32_t* unit_len_host,

@@ -212,13 +212,10 @@ int fasim_scan_records_hist(fasim_engine* E, const char* const* rnas, const int3
 {
 	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
 	if (!out_hists) return fail(E, FASIM_E_ARG, "bad arguments");
-	const int64_t whole_off = 0, whole_len = (int64_t)E->dna_host.size();
-	if (!dna && !rec_off && !rec_len && nrec == 1) {           // the whole resident buffer as one record: the engine knows its length
-		if (whole_len == 0) return fail(E, FASIM_E_ARG, "no resident DNA: call fasim_load_dna first");
-		rec_off = &whole_off; rec_len = &whole_len;
-	}
-	int rc = check_records_args(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, pp);
+	RecordSet rs;
+	int rc = check_records_args(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, pp, true, rs);
 	if (rc) return rc;
+	rec_off = rs.rec_off; rec_len = rs.rec_len;
 	const int nquery = std::max(1, nq);
 	const size_t nout = (size_t)nquery * (size_t)nrec;
 	rc = check_track_source(E, rna_lens, nq, pp, "histograms of the potential"); if (rc) return rc;
@@ -235,10 +232,8 @@ int fasim_scan_records_hist(fasim_engine* E, const char* const* rnas, const int3
 		for (int q = 0; q < nquery; q++) { fasim_hist_free(out_hists[q]); out_hists[q] = nullptr; }
 		if (out_results) for (size_t o = 0; o < nout; o++) { fasim_result_free(out_results[o]); out_results[o] = nullptr; }
 	};
-	std::vector<fasim_result*> own(out_results ? 0 : nout, nullptr);
-	fasim_result** outs = out_results ? out_results : own.data();
-	rc = scan_records_core(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, outs, totals, { &hr });
-	for (fasim_result* r : own) fasim_result_free(r);
+	OwnResults res(out_results, nout);
+	rc = scan_records_core(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, res.outs, totals, { &hr });
 	if (rc) { drop(); return rc; }
 	try { rc = hist_req_finish(E, hr, out_hists, nquery); } catch (const std::bad_alloc&) { rc = fail(E, FASIM_E_NOMEM, "out of memory"); }
 	if (rc) { drop(); return rc; }
@@ -365,7 +360,6 @@ int fasim_hist_tsv(const fasim_hist* real, const fasim_hist* const* controls, in
 	if (!hist_ok(real) || !rna_name || !text || !text_len || K < 0 || (K > 0 && !controls)) return fail(nullptr, FASIM_E_ARG, "bad arguments");
 	if (K > 0 && (!(Q > 0.0) || Q > 1.0)) return fail(nullptr, FASIM_E_ARG, "fdr %g lies outside (0, 1]", Q);
 	for (int32_t k = 0; k < K; k++) if (!hist_ok(controls[k])) return fail(nullptr, FASIM_E_ARG, "bad control %d", k);
-	static const char* const names[FASIM_TRACK_CLASSES] = { "ParaPlus", "ParaMinus", "AntiMinus", "AntiPlus" };
 	try {
 		std::vector<int64_t> ge[4], cge[4];
 		hist_ge(&real, 1, ge); hist_ge(controls, K, cge);
@@ -377,7 +371,7 @@ int fasim_hist_tsv(const fasim_hist* real, const fasim_hist* const* controls, in
 			o += line; o += v ? std::to_string(v) : std::string("NA");
 		}
 		o += "\nvalue";
-		for (const char* c : names) { o += "\t"; o += c; o += "\t"; o += c; o += "_ge"; if (K > 0) { o += "\t"; o += c; o += "_ctl_ge"; } }
+		for (const char* c : CLASS_NAMES) { o += "\t"; o += c; o += "\t"; o += c; o += "_ge"; if (K > 0) { o += "\t"; o += c; o += "_ctl_ge"; } }
 		o += "\tall_ge";
 		if (K > 0) o += "\tall_ctl_ge\tfdr";
 		o += "\n";

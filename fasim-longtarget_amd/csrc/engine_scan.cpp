@@ -638,25 +638,9 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 	for (size_t k = 0; k < nout; k++) outs[k] = nullptr;
 
 	// the segment table of the selected range of the global segment list (cutSequence() of every record, fastsim.h:71-90)
-	const int64_t step = p.cutLength - p.overlapLength;
-	std::vector<int64_t> rec_first((size_t)nrec + 1, 0);
-	for (int r = 0; r < nrec; r++) rec_first[(size_t)r + 1] = rec_first[(size_t)r] + fasim_segment_count(rec_len[r], &p);
-	const int64_t nseg_all = rec_first[(size_t)nrec];
-	if (seg_first < 0) seg_first = 0;
-	if (seg_count < 0 || seg_first + seg_count > nseg_all) seg_count = std::max<int64_t>(0, nseg_all - seg_first);
-	SegTable T;
-	int64_t total_bases = 0;
-	if (seg_count > 0) {
-		T.rec.reserve((size_t)seg_count); T.len.reserve((size_t)seg_count); T.idx.reserve((size_t)seg_count); T.off.reserve((size_t)seg_count);
-		int r = (int)(std::upper_bound(rec_first.begin(), rec_first.end(), seg_first) - rec_first.begin()) - 1;
-		for (int64_t g = seg_first; g < seg_first + seg_count; g++) {
-			while (g >= rec_first[(size_t)r + 1]) r++;
-			const int64_t i = g - rec_first[(size_t)r], pos = i * step;
-			const int len = (int)std::min<int64_t>(p.cutLength, rec_len[r] - pos);
-			T.rec.push_back(r); T.idx.push_back(i); T.off.push_back(rec_off[r] + pos); T.len.push_back(len);
-			total_bases += len;
-		}
-	}
+	const SegPlan plan = segment_plan(rec_off, rec_len, nrec, seg_first, seg_count, p);
+	const SegTable& T = plan.T;
+	seg_count = plan.seg_count;
 	const std::vector<int> encs = enabled_encodings(p);
 	const int nenc = (int)encs.size();
 
@@ -675,13 +659,9 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 		// (384 rather than 512: a 50 Mb record then gives 27 batches for the 10 workers instead of exactly two rounds of ten, which
 		//  made all workers finish their last batch together: tools/sweep_sched.py, profiles/r02_sched_sweep.txt)
 		int64_t seg_batch = std::max<int64_t>(1, std::min<int64_t>(384, ((int64_t)8 << 30) / ((int64_t)4 * nenc * tstride)));
-		const char* envb = getenv("FASIM_SEG_BATCH");
-		if (envb) seg_batch = std::max(1, atoi(envb));
-		if (E->opt_seg_batch > 0) seg_batch = E->opt_seg_batch;
-		int nworkers = 10;
-		const char* envw = getenv("FASIM_WORKERS");
-		if (envw) nworkers = std::max(1, std::min(16, atoi(envw)));
-		if (E->opt_workers > 0) nworkers = std::min(16, E->opt_workers);
+		const bool batch_given = seg_batch_given(E) > 0;      // FASIM_SEG_BATCH / option seg_batch: no fitting below
+		if (batch_given) seg_batch = seg_batch_given(E);
+		int nworkers = workers_wanted(E);
 		// option taper = t (percent): the last t % of the segments go in half-size batches, so that the workers do not all finish
 		// their last batch at the same moment (shorter drain at the end of a scan)
 		int taper_pct = E->opt_taper >= 0 ? E->opt_taper : 0;
@@ -692,13 +672,13 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 		// 2.41 s against 2.61 s with fixed batches of 384 (profiles/r02_ab_batch_shape.txt: the optimum sits exactly where
 		// the batches tile the ten workers, 448 and 576 are both slower than 512; other record sizes: r02_ab_sizes.txt).
 		// A batch of several lncRNAs is one stream of items, lncRNA after lncRNA, and keeps fixed batches of 384.
-		if (!records && !envb && E->opt_seg_batch <= 0 && nquery == 1 && seg_count >= (int64_t)128 * nworkers) {
+		if (!records && !batch_given && nquery == 1 && seg_count >= (int64_t)128 * nworkers) {
 			const int64_t target = 512;
 			const int64_t rounds = std::max<int64_t>(1, (seg_count + target * (int64_t)nworkers - 1) / (target * (int64_t)nworkers));
 			seg_batch = std::max<int64_t>(1, std::min<int64_t>((seg_count + rounds * nworkers - 1) / (rounds * nworkers), ((int64_t)8 << 30) / ((int64_t)4 * nenc * tstride)));
 			if (E->opt_taper < 0) taper_pct = 25;
 		}
-		if (p.classicSim && !envb && E->opt_seg_batch <= 0) {
+		if (p.classicSim && !batch_given) {
 			// -F: a batch's rounds advance launch by launch and end with the tail of its heaviest unit, so several
 			// batches should be in flight -- but each batch's host half runs on its worker's share of the cores, so not too many
 			// either: about eight batches per record, 16 ... 128 segments (768 ... 6 144 units) each.  Measured with step-count launches
@@ -714,7 +694,7 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 			const int mq = (int)queries[(size_t)q].size();
 			if (systolic_fits(mq)) tiles = std::max(tiles, systolic_tiles(mq));
 		}
-		if (!envb && E->opt_seg_batch <= 0 && !p.classicSim) {
+		if (!batch_given && !p.classicSim) {
 			if (tiles > 16) seg_batch = std::max<int64_t>(1, seg_batch * 16 / tiles);
 		}
 		// profile calls: k_scan's row maxima take 2 * 16 * ceil(m/16) bytes per unit; a batch in flight keeps them under 256 MB
@@ -724,50 +704,29 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 			int mmax = 16;
 			for (int q = 0; q < nquery; q++) mmax = std::max(mmax, (int)queries[(size_t)q].size());
 			rows_cap = std::max<int64_t>(1, ((int64_t)256 << 20) / ((int64_t)nenc * 2 * 16 * ((mmax + 15) / 16)));
-			if (!envb && E->opt_seg_batch <= 0) seg_batch = std::min(seg_batch, rows_cap);
+			if (!batch_given) seg_batch = std::min(seg_batch, rows_cap);
 		}
 		// batches of the call: ranges of the segment table (local indices; a batch may cross records)
-		std::vector<std::pair<int64_t, int64_t>> chunks;
-		if (records && !envb && E->opt_seg_batch <= 0 && !p.classicSim) {
-			// A record set is cut by bases, not by segments: a batch of short records' segments would otherwise carry a fraction of a
-			// batch's work for the whole fixed latency of its chain of launches.  Target: the bases of a default batch of full-length
+		Chunks chunks;
+		if (records && !batch_given && !p.classicSim) {
+			// A record set is cut by bases, not by segments (cut_by_bases).  Target: the bases of a default batch of full-length
 			// segments, lowered so that every worker gets an item; at most 512 x 48 units (the per-unit buffers such as k_scan's
 			// block maxima keep their size), and the > 16-tile rule as above.
 			int64_t cap = std::max<int64_t>(1, std::min<int64_t>((int64_t)512 * 48 / nenc, ((int64_t)8 << 30) / ((int64_t)4 * nenc * tstride)));
 			if (tiles > 16) cap = std::max<int64_t>(1, cap * 16 / tiles);
 			cap = std::min(cap, rows_cap);
 			const int64_t per_query = std::max<int64_t>(1, (nworkers + nquery - 1) / nquery);
-			const int64_t target = std::max<int64_t>(1, std::min<int64_t>((int64_t)384 * p.cutLength, (total_bases + per_query - 1) / per_query));
-			int64_t b0 = 0, bases = 0;
-			for (int64_t s = 0; s < seg_count; s++) {
-				bases += T.len[(size_t)s];
-				if (s + 1 - b0 >= cap || bases >= target) { chunks.push_back({ b0, s + 1 }); b0 = s + 1; bases = 0; }
-			}
-			if (b0 < seg_count) chunks.push_back({ b0, seg_count });
-		} else {
-			int64_t b0 = 0; const int64_t b_end = seg_count;
-			const int64_t taper_from = b_end - seg_count * taper_pct / 100;
-			while (b0 < b_end) {
-				int64_t len = (taper_pct > 0 && b0 >= taper_from) ? std::max<int64_t>(1, seg_batch / 2) : seg_batch;
-				len = std::min(len, b_end - b0);
-				chunks.push_back({ b0, b0 + len });
-				b0 += len;
-			}
-		}
+			const int64_t target = std::max<int64_t>(1, std::min<int64_t>((int64_t)384 * p.cutLength, (plan.total_bases + per_query - 1) / per_query));
+			chunks = cut_by_bases(T, seg_count, cap, target);
+		} else chunks = cut_fixed(seg_count, seg_batch, taper_pct);
 		struct Item { int q; int64_t b0, b1; };
 		std::vector<Item> items;
 		items.reserve(chunks.size() * (size_t)nquery);
 		for (int q = 0; q < nquery; q++) for (const auto& c : chunks) items.push_back({ q, c.first, c.second });
 		nworkers = (int)std::min<size_t>((size_t)nworkers, items.size());
-		// worker 0 is this engine; the others are lazily created engines on the same device
-		while ((int)E->workers.size() < nworkers - 1) {
-			fasim_engine* w = nullptr;
-			int rc = fasim_engine_create(E->device, &w); if (rc) return fail(E, rc, "cannot create worker engine: %s", fasim_last_error(nullptr));
-			E->workers.push_back(w);
-		}
+		std::vector<fasim_engine*> ws;
+		{ const int rc = worker_set(E, nworkers, ws); if (rc) return rc; }
 		std::atomic<int> active_workers(nworkers), sim_active(0);
-		std::vector<fasim_engine*> ws(1, E);
-		for (int k = 0; k < nworkers - 1; k++) ws.push_back(E->workers[k]);
 		{
 			const char* envg = getenv("FASIM_HEAVY_GATE");      // heavy kernels in flight at once (0 = no gate)
 			E->own_gate.cap = E->opt_gate >= 0 ? E->opt_gate : (envg ? atoi(envg) : 4);
@@ -784,11 +743,7 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 				// (the batches' host halves rarely coincide: a quarter of the workers share the cores; 5 Mb: 38.4 -> 35.2 s, all cores each: 36.1 s)
 				w->sim_threads = std::max(1, all / (int)std::max<size_t>(1, std::min<size_t>((size_t)nworkers, items.size()) / 4));
 			}
-			HIPOK(hipSetDevice(E->device));
-			int rc = upload(w, w->enc_ids, encs.data(), sizeof(int) * nenc); if (rc) return rc;
-			drain_timed(w);
-			for (int k = 0; k < FASIM_KERNEL_FAMILIES; k++) { w->kernel_ms[k] = 0; w->kernel_launches[k] = 0; }
-			w->sw_probs = 0; w->sw_ms = 0.0;
+			const int rc = worker_begin(E, w, encs); if (rc) return rc;
 		}
 		std::vector<std::vector<RecPart>> per_item(items.size());
 		std::vector<fasim_scan_stats> ist(items.size());
@@ -826,10 +781,7 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 					}
 				}
 				if (!r && ctx.B.nunit > 0 && !ctx.stage3_done && !any_only(products)) r = stage3_range(w, ctx, 0, ctx.B.nunit, ist[c]);
-				(void)hipStreamSynchronize(w->st);
-				drain_timed(w);
-				for (int k = 0; k < FASIM_KERNEL_FAMILIES; k++) { ist[c].kernel_ms[k] = w->kernel_ms[k]; ist[c].kernel_launches[k] = w->kernel_launches[k]; w->kernel_ms[k] = 0; w->kernel_launches[k] = 0; }
-				ist[c].striped_window_probs = w->sw_probs; ist[c].striped_window_ms = w->sw_ms; w->sw_probs = 0; w->sw_ms = 0.0;
+				worker_item_end(w, ist[c]);
 				if (!r) collect_batch(ctx, T, itx.b0, itx.b1, (int64_t)rq.size(), true, per_item[c]);
 				it1[c] = now_s();
 				if (r) wrc[wi] = r;
@@ -842,7 +794,7 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 		else { std::vector<std::thread> th; for (size_t wi = 0; wi < ws.size(); wi++) th.emplace_back(run, wi); for (auto& t : th) t.join(); }
 		for (fasim_engine* w : ws) { w->active_workers = nullptr; w->sim_in_flight = nullptr; w->scan_workers = 1; }
 		if (g_prof.on) fprintf(stderr, "[fasim prof] scan workers                                  %.3f s\n", now_s() - t_workers);
-		for (size_t wi = 0; wi < ws.size(); wi++) if (wrc[wi]) { if (ws[wi] != E) E->err = ws[wi]->err; return wrc[wi]; }
+		{ const int rc = workers_result(E, ws, wrc); if (rc) return rc; }
 		// a multi-query call leaves the engine on its LAST query (documented in fasim_hip.h)
 		if (nq > 0 && E->rna != queries.back()) { int rc = fasim_set_query(E, queries.back().data(), (int)queries.back().size()); if (rc) return rc; }
 		const double t_merge = now_s();

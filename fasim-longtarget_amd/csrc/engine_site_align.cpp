@@ -74,10 +74,9 @@ int run_site_align(fasim_engine* E, SiteAlignReq& R)
 	const int nrec = R.nrec, nquery = (int)R.queries.size();
 	const int64_t step = p.cutLength - p.overlapLength;
 	const int tstride = (p.cutLength + 15) & ~15;
-	std::vector<int64_t> rec_first((size_t)nrec + 1, 0);
-	for (int r = 0; r < nrec; r++) rec_first[(size_t)r + 1] = rec_first[(size_t)r] + fasim_segment_count(R.rec_len[r], &p);
-	int64_t seg_first = std::max<int64_t>(0, R.seg_first), seg_count = R.seg_count;
-	if (seg_count < 0 || seg_first + seg_count > rec_first[(size_t)nrec]) seg_count = std::max<int64_t>(0, rec_first[(size_t)nrec] - seg_first);
+	const SegRange range = segment_range(R.rec_len, nrec, R.seg_first, R.seg_count, p);
+	const std::vector<int64_t>& rec_first = range.rec_first;
+	const int64_t seg_first = range.seg_first, seg_count = range.seg_count;
 	static const std::vector<uint8_t> lut = [] { std::vector<uint8_t> v(48 * 256); build_enc_lut(v.data()); return v; }();
 	fasim_params pc = p; pc.ntMin = 1; pc.ntMax = INT_MAX;      // hits are never filtered by length
 	const bool prof = [] { const char* e = getenv("FASIM_PROFILE"); return e && atoi(e) != 0; }();
@@ -272,15 +271,14 @@ int fasim_scan_records_sites_aligned(fasim_engine* E, const char* const* rnas, c
 	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
 	if (!out_hits) return fail(E, FASIM_E_ARG, "bad arguments");
 	// first phase: the sites call itself, refusals included (its results, sites and totals are this call's)
-	int rc = fasim_scan_records_sites(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, min_value, max_gap, out_results, out_sites, totals);
+	RecordSet rs;
+	int rc = scan_records_sites(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, min_value, max_gap, out_results, out_sites, totals, rs);
 	if (rc) return rc;
 	const int nquery = std::max(1, nq);
 	const size_t nout = (size_t)nquery * (size_t)nrec;
 	for (size_t o = 0; o < nout; o++) out_hits[o] = nullptr;
-	const int64_t whole_off = 0, whole_len = (int64_t)E->dna_host.size();
-	if (!dna && !rec_off && !rec_len && nrec == 1) { rec_off = &whole_off; rec_len = &whole_len; }
 	SiteAlignReq R;
-	R.dna = dna ? dna : E->dna_host.data(); R.rec_off = rec_off; R.rec_len = rec_len; R.nrec = nrec; R.seg_first = seg_first; R.seg_count = seg_count;
+	R.dna = rs.host(E); R.rec_off = rs.rec_off; R.rec_len = rs.rec_len; R.nrec = nrec; R.seg_first = seg_first; R.seg_count = seg_count;
 	R.p = *pp; R.sites = out_sites; R.hits = out_hits;
 	try {
 		if (nq == 0) R.queries.push_back(E->rna);
@@ -359,7 +357,6 @@ int fasim_site_hits_tsv(const fasim_sites* s, const fasim_site_hits* h, const ch
 	const char* record_name, int32_t header, char** text, int64_t* text_len)
 {
 	if (!s || !h || !chr || !rna_name || !text || !text_len || s->n < 0 || (s->n > 0 && !s->s) || h->n != s->n) return fail(nullptr, FASIM_E_ARG, "bad arguments");
-	static const char* const names[FASIM_TRACK_CLASSES] = { "ParaPlus", "ParaMinus", "AntiMinus", "AntiPlus" };
 	const int64_t sg = start_genome - 1;                  // 0-based genome position of the record's first base
 	std::string o;
 	char b[96];
@@ -378,7 +375,7 @@ int fasim_site_hits_tsv(const fasim_sites* s, const fasim_site_hits* h, const ch
 		int64_t a = x.start, e = x.end;
 		if (al) { if (t.enc & 1) { a = t.starj; e = (int64_t)t.endj + 1; } else { a = (int64_t)t.starj - 1; e = t.endj; } }
 		o += chr;
-		int n = snprintf(b, sizeof b, "\t%lld\t%lld\t%s\t%d\t%c", (long long)(sg + a), (long long)(sg + e), names[x.cls], x.value, (x.cls == 0 || x.cls == 3) ? '+' : '-');
+		int n = snprintf(b, sizeof b, "\t%lld\t%lld\t%s\t%d\t%c", (long long)(sg + a), (long long)(sg + e), CLASS_NAMES[x.cls], x.value, (x.cls == 0 || x.cls == 3) ? '+' : '-');
 		o.append(b, (size_t)n);
 		if (!al) o += "\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA";
 		else {

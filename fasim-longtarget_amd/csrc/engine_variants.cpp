@@ -23,24 +23,16 @@ int fasim_score_variants(fasim_engine* E, const char* const* rnas, const int32_t
 {
 	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
 	if (nq < 1 || !rnas || !rna_lens || nvar < 0 || (nvar > 0 && (!vars || !out)) || !pp) return fail(E, FASIM_E_ARG, "bad arguments");
-	if (nrec < 1) return fail(E, FASIM_E_ARG, "a record set needs at least one record (nrec = %d)", nrec);
-	if (!rec_off || !rec_len) return fail(E, FASIM_E_ARG, "bad arguments");
+	RecordSet rs;
+	int rc = record_set_open(E, dna, rec_off, rec_len, nrec, false, rs); if (rc) return rc;
 	for (int32_t q = 0; q < nq; q++) {
 		if (!rnas[q] || rna_lens[q] <= 0) return fail(E, FASIM_E_ARG, "empty query %d", q);
 		if (rna_lens[q] > FASIM_MAX_QUERY) return fail(E, FASIM_E_UNSUPPORTED, "query %d has %d nt: the limit is %d", q, rna_lens[q], FASIM_MAX_QUERY);
 	}
 	if (pp->classicSim) return fail(E, FASIM_E_UNSUPPORTED, "variants are scored with the fastSIM scoring only: not with classicSim (-F)");
 	if (flank < 0 || flank > FASIM_MAX_FLANK) return fail(E, FASIM_E_ARG, "flank %d lies outside [0, %d]", flank, FASIM_MAX_FLANK);
-	const bool resident = dna == nullptr;
-	if (resident && E->dna_host.empty()) return fail(E, FASIM_E_ARG, "no resident DNA: call fasim_load_dna first");
-	const int64_t have = resident ? (int64_t)E->dna_host.size() : INT64_MAX;
-	for (int32_t r = 0; r < nrec; r++) {
-		if (rec_len[r] == 0) return fail(E, FASIM_E_ARG, "record %d is empty", r);
-		if (rec_off[r] < 0 || rec_len[r] < 0 || rec_off[r] > have || rec_len[r] > have - rec_off[r])
-			return fail(E, FASIM_E_ARG, "record %d: offset %lld, length %lld lies outside the DNA buffer%s", r, (long long)rec_off[r],
-				(long long)rec_len[r], resident ? " (the resident buffer of fasim_load_dna)" : "");
-		if (rec_len[r] > 0x7fffffffll) return fail(E, FASIM_E_ARG, "record %d: one record is limited to 2^31-1 nt", r);
-	}
+	rc = record_set_bounds(E, rs); if (rc) return rc;
+	const bool resident = rs.resident;
 	for (int64_t v = 0; v < nvar; v++) {
 		const fasim_variant& x = vars[v];
 		if (x.alt_len < 0) continue;
@@ -71,7 +63,7 @@ int fasim_score_variants(fasim_engine* E, const char* const* rnas, const int32_t
 			const int m = rna_lens[q];
 			std::vector<uint8_t> qc((size_t)m);
 			for (int i = 0; i < m; i++) qc[(size_t)i] = code2(rnas[q][i]);
-			int rc = upload(E, E->vr_q, qc.data(), qc.size()); if (rc) return rc;
+			rc = upload(E, E->vr_q, qc.data(), qc.size()); if (rc) return rc;
 			const bool rows_hbm = m > TOUCH_LDS_ROWS;
 			const size_t row_bytes = (size_t)6 * (size_t)touch_state_rows(m);      // of one problem
 			for (size_t w0 = 0; w0 < todo.size(); ) {
@@ -163,10 +155,9 @@ int fasim_variants_tsv(const fasim_variant* vars, const fasim_variant_score* sco
 	const uint8_t* matched, char** text, int64_t* text_len)
 {
 	if (nvar < 0 || !rna_name || !text || !text_len || (nvar > 0 && (!vars || !scores))) return fail(nullptr, FASIM_E_ARG, "bad arguments");
-	static const char* const names[FASIM_TRACK_CLASSES] = { "ParaPlus", "ParaMinus", "AntiMinus", "AntiPlus" };
 	std::string o = "# fasim variants lncRNA="; o += rna_name; o += " flank="; o += std::to_string(flank); o += "\n";
 	o += "line\tchrom\tpos\tid\tref\talt";
-	for (const char* c : names) { o += "\t"; o += c; o += "_ref\t"; o += c; o += "_alt"; }
+	for (const char* c : CLASS_NAMES) { o += "\t"; o += c; o += "_ref\t"; o += c; o += "_alt"; }
 	o += "\tmax_ref\tmax_alt\tdelta\trule_ref\trule_alt\tclipped\n";
 	for (int64_t k = 0; k < nvar; k++) {
 		const fasim_variant& x = vars[k];
