@@ -110,6 +110,10 @@ class _VariantScore(C.Structure):
     _fields_ = [("value", (C.c_int32 * 4) * 2), ("enc", (C.c_int32 * 4) * 2), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+class _VariantWindow(C.Structure):
+    _fields_ = [("pre", C.c_int32), ("post", C.c_int32), ("edge", C.c_int32), ("reserved", C.c_int32)]
+
+
 class _VariantStats(C.Structure):
     _fields_ = [("problems", C.c_int64), ("cells", C.c_int64), ("kernel_s", C.c_double), ("total_s", C.c_double)]
 
@@ -180,6 +184,7 @@ EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_e
            "fasim_scan_records_hist", "fasim_scan_oligos_hist", "fasim_hist_merge", "fasim_hist_free", "fasim_shuffle_query",
            "fasim_hist_threshold", "fasim_hist_tsv",
            "fasim_read_vcf", "fasim_score_variants", "fasim_variants_tsv",
+           "fasim_score_variants_aligned", "fasim_variant_hit_span", "fasim_variant_hits_tsv",
            # the reference's own ssw.h ABI (include/ssw.h)
            "ssw_init", "init_destroy", "ssw_pre_align", "ssw_align", "align_destroy", "encoded_ops"]
 
@@ -324,6 +329,15 @@ def lib():
     L.fasim_score_variants.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.POINTER(_Variant), C.c_int64, C.c_int32,
                                        C.POINTER(Params), C.POINTER(_VariantScore), C.POINTER(_VariantStats)]
+    L.fasim_score_variants_aligned.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
+                                               C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.POINTER(_Variant), C.c_int64,
+                                               C.c_int32, C.POINTER(Params), C.POINTER(_VariantScore), C.POINTER(_VariantStats),
+                                               C.POINTER(_VariantWindow), C.POINTER(C.POINTER(_SiteHits))]
+    L.fasim_variant_hit_span.argtypes = [C.POINTER(_Variant), C.POINTER(_VariantWindow), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    L.fasim_variant_hits_tsv.argtypes = [C.POINTER(_Variant), C.POINTER(_VariantScore), C.POINTER(_VariantWindow), C.POINTER(_SiteHits),
+                                         C.c_int64, C.c_int32, C.c_char_p, C.POINTER(C.c_uint8), C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_int64)]
     L.fasim_variants_tsv.argtypes = [C.POINTER(_Variant), C.POINTER(_VariantScore), C.c_int64, C.c_int32, C.c_char_p,
                                      C.POINTER(C.c_uint8), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     _lib = L
@@ -1469,7 +1483,7 @@ class Engine:
         self._totals(totals, nq)
         return [Hist(_native=hs[q]) for q in range(nq)]
 
-    def score_variants(self, variants, dnas, p: Params | None = None, flank: int = 300, queries=None):
+    def score_variants(self, variants, dnas, p: Params | None = None, flank: int = 300, queries=None, _aligned: bool = False):
         """The triplex potential through variants (fasim_score_variants): `(values, encs, flags)`, int32 arrays of shape
         (nq, nvar, 2, 4), the same, and (nq, nvar): per query, variant, allele (0 REF, 1 ALT) and strand class (TRACK_CLASSES) the best
         score of a local alignment through the allele within `flank` bases of it, the smallest encoding that attains it (-1: value 0),
@@ -1492,13 +1506,31 @@ class Engine:
         nvar = len(variants)
         out = (_VariantScore * max(1, nq * nvar))()
         st = _VariantStats()
-        self._check(self._L.fasim_score_variants(self._h, arr, qlens, nq, blob, offs, lens, nrec, vs, nvar, flank, C.byref(p), out, C.byref(st)))
+        if _aligned:
+            win = (_VariantWindow * max(1, nvar))()
+            hts = (C.POINTER(_SiteHits) * max(1, nq))()
+            self._check(self._L.fasim_score_variants_aligned(self._h, arr, qlens, nq, blob, offs, lens, nrec, vs, nvar, flank, C.byref(p), out,
+                                                             C.byref(st), win, hts))
+        else:
+            self._check(self._L.fasim_score_variants(self._h, arr, qlens, nq, blob, offs, lens, nrec, vs, nvar, flank, C.byref(p), out, C.byref(st)))
         self.last_variant_stats = dict(problems=st.problems, cells=st.cells, kernel_s=st.kernel_s, total_s=st.total_s)
         flat = np.frombuffer(out, dtype=np.int32).reshape(max(1, nq * nvar), 18)[:nq * nvar]
         values = flat[:, 0:8].reshape(nq, nvar, 2, 4).copy()
         encs = flat[:, 8:16].reshape(nq, nvar, 2, 4).copy()
         flags = flat[:, 16].reshape(nq, nvar).copy()
+        if _aligned:
+            windows = np.frombuffer(win, dtype=np.int32).reshape(max(1, nvar), 4)[:nvar, :3].copy()
+            return values, encs, flags, windows, [SiteHits(hts[q]) for q in range(nq)]
         return values, encs, flags
+
+    def score_variants_aligned(self, variants, dnas, p: Params | None = None, flank: int = 300, queries=None):
+        """score_variants() and the alignment behind every score (fasim_score_variants_aligned): `(values, encs, flags, windows,
+        hits)`.  The first three are exactly what score_variants() returns.  windows: (nvar, 3) int32 rows of (pre, post, edge) --
+        the record's letters before and after REF inside the flank, edge bit 0 / 1: the lower / upper end of the window was cut by
+        the flank.  hits: one SiteHits per query with 8 * nvar hits, hit variant_hit_index(v, allele, cls): the cells i0, i1, j0, j1
+        of the path through the touching matrix in the unit of encs[q, v, allele, cls], its CIGAR and its triplex record (seg = v);
+        a slot without a value has cigar_len 0, an unaligned one (more than 2^26 cells) -1."""
+        return self.score_variants(variants, dnas, p, flank, queries, _aligned=True)
 
     def _records_track(self, blob, offs, lens, nrec, p, rnas, bin, records, seg_first, seg_count):
         arr, qlens, nq, nqo = _pack_queries(rnas)
@@ -1730,6 +1762,67 @@ def variants_tsv(variants, values, encs, flags, flank: int, rna_name: str, match
     flat[:n, 0:8], flat[:n, 8:16], flat[:n, 16] = values, encs, flags
     mt = None if matched is None else (C.c_uint8 * max(1, n))(*[1 if x else 0 for x in matched])
     return _text_call(L.fasim_variants_tsv, vs, sc, n, flank, rna_name.encode(), mt)
+
+
+def variant_hit_index(v: int, allele: int, cls: int) -> int:
+    """Index of the hit of variant v, allele (0 REF, 1 ALT) and strand class cls in the SiteHits of score_variants_aligned()."""
+    return (v * 2 + allele) * 4 + cls
+
+
+def _variant_hit_span(variant, window, allele: int, enc: int, j0: int, j1: int):
+    L = lib()
+    vs, _keep = _variants_to_c([variant])
+    w = _VariantWindow(int(window[0]), int(window[1]), int(window[2]), 0)
+    a, b, c = C.c_int64(), C.c_int64(), C.c_int32()
+    rc = L.fasim_variant_hit_span(vs, C.byref(w), allele, enc, j0, j1, C.byref(a), C.byref(b), C.byref(c))
+    if rc != 0:
+        raise FasimError(L.fasim_last_error(None).decode(), rc)
+    return a.value, b.value, bool(c.value)
+
+
+def variant_hit_span(variant, window, allele: int, enc: int, j0: int, j1: int):
+    """The reference bases `(start, end)`, 0-based half-open in the coordinates of variant.pos, that the unit columns [j0, j1] of a
+    hit of `allele` under `enc` cover (fasim_variant_hit_span); window: (pre, post, edge) of score_variants_aligned().  Letters of
+    the allele map to REF's range, letters behind it are shifted by the difference of the alleles' lengths."""
+    return _variant_hit_span(variant, window, allele, enc, j0, j1)[:2]
+
+
+def variant_hit_clipped(variant, window, allele: int, enc: int, j0: int, j1: int) -> bool:
+    """The path of a hit lies in the unit's first or last column and that end of the window was cut by the flank."""
+    return _variant_hit_span(variant, window, allele, enc, j0, j1)[2]
+
+
+def variant_hits_tsv(variants, values, encs, windows, hits, flank: int, rna_name: str, matched=None) -> bytes:
+    """The bytes of `fasim --variants --variant-hits`' second table for one query (fasim_variant_hits_tsv): values and encs
+    (nvar, 2, 4), windows (nvar, 3) and hits (one SiteHits) as Engine.score_variants_aligned() returns them per query."""
+    import numpy as np
+    L = lib()
+    n = len(variants)
+    vs, _keep = _variants_to_c(variants)
+    sc = (_VariantScore * max(1, n))()
+    flat = np.frombuffer(sc, dtype=np.int32).reshape(max(1, n), 18)
+    flat[:n, 0:8] = np.asarray(values, dtype=np.int32).reshape(n, 8)
+    flat[:n, 8:16] = np.asarray(encs, dtype=np.int32).reshape(n, 8)
+    win = (_VariantWindow * max(1, n))()
+    wflat = np.frombuffer(win, dtype=np.int32).reshape(max(1, n), 4)
+    wflat[:n, 0:3] = np.asarray(windows, dtype=np.int32).reshape(n, 3)
+    mt = None if matched is None else (C.c_uint8 * max(1, n))(*[1 if x else 0 for x in matched])
+    return _text_call(L.fasim_variant_hits_tsv, vs, sc, win, hits.pointer(), n, flank, rna_name.encode(), mt)
+
+
+def empty_variant_hits(nvar: int) -> SiteHits:
+    """8 * nvar hits without a value (cigar_len 0, cells -1, empty strings): what score_variants_aligned() returns where nothing
+    scores; a structure of the caller's."""
+    n = 8 * nvar
+    k = max(1, n)
+    keep = dict(t=(Triplex * k)(), qb=(C.c_int32 * k)(*[-1] * k), qe=(C.c_int32 * k)(*[-1] * k), tb=(C.c_int32 * k)(*[-1] * k),
+                te=(C.c_int32 * k)(*[-1] * k), coff=(C.c_int64 * k)(), clen=(C.c_int32 * k)(), cig=(C.c_uint32 * 1)(),
+                pool=C.create_string_buffer(1))
+    for i in range(n):
+        keep["t"][i].seg, keep["t"][i].enc = i // 8, -1
+    h = _SiteHits(n, keep["t"], keep["qb"], keep["qe"], keep["tb"], keep["te"], keep["coff"], keep["clen"], keep["cig"],
+                  C.cast(keep["pool"], C.POINTER(C.c_char)), 1, 0)
+    return SiteHits(C.pointer(h), _keep=(h, keep))
 
 
 def synth_dna(n: int, seed: int) -> bytes:

@@ -140,6 +140,7 @@ struct fasim_engine {
 	DevBuf sa_q, sa_tcodes, sa_probs, sa_ends, sa_rows, sa_items, sa_dirs, sa_cigar, sa_ciglen;   // fasim_scan_records_sites_aligned only: query codes, the chunk's units, problems, end cells, row state of long queries, path items, direction bytes, CIGARs
 	DevBuf hist, hist_zone, hist_zones, hist_sat;   // fasim_scan_records_hist only: k_hist's counters of the batch, its zone bounds per segment, the zone values and saturation flags
 	DevBuf vr_q, vr_dna, vr_alt, vr_wins, vr_probs, vr_tcodes, vr_rows, vr_touch, vr_out;   // fasim_score_variants only: query codes, streamed window letters, ALT letters, windows, problems, target codes, row state of long queries, k_touch's words, k_touch_reduce's words
+	DevBuf vr_items, vr_dirs, vr_cigar, vr_paths;   // fasim_score_variants_aligned only: k_touch_path's items, direction bytes, CIGAR words and results
 	int opt_sim_lds = -1;                        // option "sim_lds": -F re-sweeps always on the L2 variant (0) / the LDS variant where the state fits (1); -1 = by the units in flight
 	int opt_site_short = -1;                     // option "site_short": 1 = the hits of oligo sites end on k_site_ends_short (default), 0 = on k_site_ends (-1 = default / environment FASIM_SITE_SHORT)
 	int opt_site_chunk = 0;                      // option "site_chunk": problems per chunk of the hits phase where lower than the phase's own limit (0 = that limit)
@@ -498,6 +499,16 @@ struct SiteAlignReq {
 };
 int run_site_align(fasim_engine* E, SiteAlignReq& R);
 void site_hits_free(fasim_site_hits* h);
+// One hit on its way into a fasim_site_hits.  aligned: cigar and strings are there; otherwise cigar_len = -1 and the hit counts as
+// unaligned, except an `empty` one (a slot of fasim_score_variants_aligned without a value): cigar_len = 0, not counted
+struct HitOut {
+	HostTriplex t;
+	int32_t i0 = -1, i1 = -1, j0 = -1, j1 = -1;
+	std::vector<uint32_t> cigar;
+	bool aligned = false, empty = false;
+};
+void hit_clear(HitOut& H, int enc);                            // the numbers of a hit that has no alignment (yet): zeros, seg -1
+fasim_site_hits* pack_hits(const std::vector<HitOut>& v);      // NULL: out of memory
 
 // ---- histogram of the potential (fasim_scan_records_hist, hist.hip, engine_hist.cpp) ---------------------------------------------
 // One side of the overlap of two neighbouring segments of a record, as the values of that segment alone: boundary b of a record is

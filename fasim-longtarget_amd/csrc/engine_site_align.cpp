@@ -14,12 +14,15 @@
 
 namespace {
 
-struct HitOut {
-	HostTriplex t;
-	int32_t i0 = -1, i1 = -1, j0 = -1, j1 = -1;
-	std::vector<uint32_t> cigar;
-	bool aligned = false;
-};
+struct Work { int32_t site, unit, n, jp, value, enc, level; int64_t seg, soff, key; };      // one problem: site index in the query's flat list; level = its rank among the site's covering segments; key = the unit
+
+} // namespace
+
+void hit_clear(HitOut& H, int enc)
+{
+	H.t = HostTriplex(); H.t.stari = H.t.endi = H.t.starj = H.t.endj = H.t.strand = H.t.reverse = H.t.rule = H.t.nt = 0;
+	H.t.score = H.t.identity = H.t.tri_score = 0.0f; H.t.seg = -1; H.t.enc = enc;
+}
 
 // the hit list of one (query, record) from its hits in site order
 fasim_site_hits* pack_hits(const std::vector<HitOut>& v)
@@ -47,6 +50,7 @@ fasim_site_hits* pack_hits(const std::vector<HitOut>& v)
 		r.rule = t.rule; r.nt = t.nt; r.score = t.score; r.identity = t.identity; r.tri_score = t.tri_score; r.seg = t.seg; r.enc = t.enc;
 		h->q_begin[i] = x.i0; h->q_end[i] = x.i1; h->t_begin[i] = x.j0; h->t_end[i] = x.j1;
 		h->cigar_off[i] = (int64_t)coff;
+		if (x.empty) continue;                        // (cigar_len 0, the empty string)
 		if (!x.aligned) { h->cigar_len[i] = -1; h->unaligned++; continue; }
 		h->cigar_len[i] = (int32_t)x.cigar.size();
 		memcpy(h->cigar + coff, x.cigar.data(), x.cigar.size() * sizeof(uint32_t)); coff += x.cigar.size();
@@ -55,10 +59,6 @@ fasim_site_hits* pack_hits(const std::vector<HitOut>& v)
 	}
 	return h;
 }
-
-struct Work { int32_t site, unit, n, jp, value, enc, level; int64_t seg, soff, key; };      // one problem: site index in the query's flat list; level = its rank among the site's covering segments; key = the unit
-
-} // namespace
 
 void site_hits_free(fasim_site_hits* h)
 {

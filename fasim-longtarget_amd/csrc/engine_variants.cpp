@@ -1,10 +1,16 @@
 // fasim-longtarget_amd/csrc/engine_variants.cpp -- fasim_score_variants: the triplex potential through variants (DESIGN.md section 19;
-// kernels: variant.hip), and the table of `fasim --variants` (fasim_variants_tsv).
+// kernels: variant.hip), and the table of `fasim --variants` (fasim_variants_tsv); fasim_score_variants_aligned: the same call with
+// the alignment behind every score (section 21; kernel: variant_path.hip), its projection to the reference and its table.
 //
 // A variant is two allele windows, a window under an enabled encoding is a problem.  Per query the variants are cut into chunks by a
 // fixed bound on buffer bytes; a chunk is: the windows' descriptions (and, for a streamed record, their letters) and the ALT letters
 // up, k_var_encode, k_touch, k_touch_reduce, nine words per variant back.  Everything runs on the engine's own stream and in buffers
 // of its own (vr_*): the engine's query, its scan buffers and its workers are not touched.
+// The aligned call adds per chunk, after the nine words are back: the slots with a value become path items over the target codes
+// that are still in vr_tcodes, k_touch_path in launches of at most 512 MB of direction bytes, cells and CIGARs back, convert_triplex
+// (on the host while the next launch's kernel runs).
+#include <climits>
+
 #include "engine.h"
 
 namespace {
@@ -15,11 +21,126 @@ constexpr int64_t VR_MAX_PROBS = 1 << 20;                // problems of a chunk
 
 inline int pad16(int n) { return (n + 15) & ~15; }
 
-}  // namespace
+constexpr int64_t VR_DIR_BYTES = (int64_t)512 << 20;      // direction bytes of a path launch
+constexpr int64_t VR_CIG_WORDS = (int64_t)1 << 26;        // CIGAR words of a path launch
 
-int fasim_score_variants(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
+// the window of a variant: [lo, hi) of its record
+inline void window_of(const fasim_variant& x, int64_t len, int32_t flank, int64_t& lo, int64_t& hi)
+{
+	lo = std::max<int64_t>(0, x.pos - flank); hi = std::min<int64_t>(len, x.pos + x.ref_len + flank);
+}
+
+// What the path phase of a chunk needs of its call
+struct PathCtx {
+	fasim_engine* E; std::string rna; int m; std::vector<int> encs; const char* host; const int64_t* rec_off; const int64_t* rec_len;
+	const fasim_variant* vars; int32_t flank; fasim_params pc; bool rows_hbm; size_t row_bytes;
+};
+
+// The hits of the chunk's variants todo[0 .. nv): probs are the chunk's problems in (variant, allele, encoding) order, still on the
+// device with their target codes; scores the query's row of the call's results; H the query's 8 * nvar hits
+int trace_chunk(const PathCtx& C, const std::vector<TouchProb>& probs, const int64_t* todo, int nv, const fasim_variant_score* scores,
+	std::vector<HitOut>& H)
+{
+	fasim_engine* E = C.E;
+	const int nenc = (int)C.encs.size(), m = C.m;
+	const int64_t rows = touch_state_rows(m);
+	struct Want { size_t slot; int64_t v; int al, enc, value; };
+	std::vector<TouchPathItem> items;
+	std::vector<Want> wants;
+	for (int k = 0; k < nv; k++) {
+		const int64_t v = todo[k];
+		const fasim_variant_score& s = scores[v];
+		for (int al = 0; al < 2; al++) for (int c = 0; c < FASIM_TRACK_CLASSES; c++) {
+			if (s.value[al][c] <= 0) continue;
+			const size_t slot = ((size_t)v * 2 + (size_t)al) * 4 + (size_t)c;
+			HitOut& h = H[slot];
+			h.empty = false; h.t.enc = s.enc[al][c];
+			const auto it = std::find(C.encs.begin(), C.encs.end(), s.enc[al][c]);
+			if (it == C.encs.end()) continue;
+			const int prob = (k * 2 + al) * nenc + (int)(it - C.encs.begin());
+			const TouchProb& P = probs[(size_t)prob];
+			if ((int64_t)m * P.n > TOUCH_PATH_MAX_CELLS) continue;      // left unaligned
+			TouchPathItem I; I.dir_off = 0; I.prob = prob; I.value = s.value[al][c]; I.cig_off = 0; I.cig_cap = 2 * P.n + 1;
+			items.push_back(I);
+			wants.push_back({ slot, v, al, s.enc[al][c], s.value[al][c] });
+		}
+	}
+	std::string alt_win;
+	// the host's half of a launch: cells and CIGARs into hits.  It runs while the next launch's kernel does
+	struct Done { size_t a = 0; int ni = 0; std::vector<TouchPathOut> outs; std::vector<uint32_t> cig; } prev;
+	auto finish = [&](const Done& D) {
+		const size_t a = D.a; const int ni = D.ni;
+		const std::vector<TouchPathOut>& outs = D.outs; const std::vector<uint32_t>& cig = D.cig;
+		for (int k = 0; k < ni; k++) {
+			const TouchPathItem& I = items[a + (size_t)k];
+			const Want& w = wants[a + (size_t)k];
+			const TouchPathOut& o = outs[(size_t)k];
+			const int n = probs[(size_t)I.prob].n;
+			HitOut& h = H[w.slot];
+			h.i0 = o.i0; h.i1 = o.i1; h.j0 = o.j0; h.j1 = o.j1;
+			if (o.cigar_len < 1 || o.cigar_len > I.cig_cap || o.i0 < 0 || o.j0 < 0 || o.i0 > o.i1 || o.j0 > o.j1 || o.i1 >= m || o.j1 >= n) continue;
+			h.cigar.assign(cig.begin() + I.cig_off, cig.begin() + I.cig_off + o.cigar_len);
+			std::reverse(h.cigar.begin(), h.cigar.end());      // the traceback wrote the last operation first
+			// the window's letters: the record's own, or the ALT window assembled here
+			const fasim_variant& x = C.vars[w.v];
+			int64_t lo, hi;
+			window_of(x, C.rec_len[x.rec], C.flank, lo, hi);
+			const char* seg = C.host + C.rec_off[x.rec] + lo;
+			if (w.al) {
+				alt_win.assign(seg, (size_t)(x.pos - lo));
+				alt_win.append(x.alt, (size_t)x.alt_len);
+				alt_win.append(C.host + C.rec_off[x.rec] + x.pos + x.ref_len, (size_t)(hi - x.pos - x.ref_len));
+				seg = alt_win.data();
+			}
+			AlignResult al;
+			al.sw_score = w.value; al.ref_begin = o.j0; al.ref_end = o.j1; al.query_begin = o.i0; al.query_end = o.i1; al.cigar_len = (int)h.cigar.size();
+			std::vector<HostTriplex> one;
+			convert_triplex(al, h.cigar.data(), C.rna, seg, n, w.enc, (long)lo, C.pc, one, only_acgtn(seg, n), true);
+			if (one.empty()) { h.cigar.clear(); continue; }
+			h.t = std::move(one[0]); h.t.seg = (int)w.v; h.t.enc = w.enc; h.aligned = true;
+		}
+	};
+	for (size_t a = 0; a < items.size(); ) {
+		size_t b = a; int64_t dir_total = 0, cig_total = 0;
+		for (; b < items.size(); b++) {
+			TouchPathItem& I = items[b];
+			const int64_t bytes = rows * probs[(size_t)I.prob].n;
+			if (b > a && (dir_total + bytes > VR_DIR_BYTES || cig_total + I.cig_cap > VR_CIG_WORDS)) break;
+			I.dir_off = dir_total; I.cig_off = (int32_t)cig_total;
+			dir_total += bytes; cig_total += I.cig_cap;
+		}
+		const int ni = (int)(b - a);
+		if (E->vr_items.ensure((size_t)ni * sizeof(TouchPathItem)) != hipSuccess || E->vr_dirs.ensure((size_t)dir_total) != hipSuccess ||
+			E->vr_cigar.ensure((size_t)cig_total * sizeof(uint32_t)) != hipSuccess || E->vr_paths.ensure((size_t)ni * sizeof(TouchPathOut)) != hipSuccess ||
+			(C.rows_hbm && E->vr_rows.ensure((size_t)ni * C.row_bytes) != hipSuccess)) {
+			(void)hipGetLastError();
+			return fail(E, FASIM_E_NOMEM, "variant hits: no device memory for the direction bytes of %d paths (%lld bytes)", ni, (long long)dir_total);
+		}
+		HIPOK(hipMemcpyAsync(E->vr_items.p, items.data() + a, (size_t)ni * sizeof(TouchPathItem), hipMemcpyHostToDevice, E->st));
+		TouchPathLaunch PL;
+		PL.tcodes = E->vr_tcodes.as<uint8_t>(); PL.qcodes = E->vr_q.as<uint8_t>(); PL.m = m; PL.probs = E->vr_probs.as<TouchProb>();
+		PL.items = E->vr_items.as<TouchPathItem>(); PL.nitem = ni; PL.rows = C.rows_hbm ? E->vr_rows.as<uint16_t>() : nullptr;
+		PL.dirs = E->vr_dirs.as<uint8_t>(); PL.cigar = E->vr_cigar.as<uint32_t>(); PL.out = E->vr_paths.as<TouchPathOut>();
+		hipError_t he;
+		{ TimedScope ts(E, 4); he = launch_touch_path(PL, E->st); }
+		if (he != hipSuccess) return fail(E, FASIM_E_HIP, "variant hits (path) launch failed: %s", hipGetErrorString(he));
+		if (prev.ni) finish(prev);      // (before the copies back: they wait for the kernel)
+		Done cur; cur.a = a; cur.ni = ni; cur.outs.resize((size_t)ni); cur.cig.resize((size_t)cig_total);
+		HIPOK(hipMemcpyAsync(cur.outs.data(), E->vr_paths.p, (size_t)ni * sizeof(TouchPathOut), hipMemcpyDeviceToHost, E->st));
+		HIPOK(hipMemcpyAsync(cur.cig.data(), E->vr_cigar.p, (size_t)cig_total * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st));
+		HIPOK(hipStreamSynchronize(E->st));
+		drain_timed(E);
+		prev = std::move(cur);
+		a = b;
+	}
+	if (prev.ni) finish(prev);
+	return FASIM_OK;
+}
+
+// fasim_score_variants; with `hits` (and `windows`) fasim_score_variants_aligned
+int score_variants_impl(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, const fasim_variant* vars, int64_t nvar, int32_t flank,
-	const fasim_params* pp, fasim_variant_score* out, fasim_variant_stats* stats)
+	const fasim_params* pp, fasim_variant_score* out, fasim_variant_stats* stats, fasim_variant_window* windows, fasim_site_hits** hits)
 {
 	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
 	if (nq < 1 || !rnas || !rna_lens || nvar < 0 || (nvar > 0 && (!vars || !out)) || !pp) return fail(E, FASIM_E_ARG, "bad arguments");
@@ -46,6 +167,22 @@ int fasim_score_variants(fasim_engine* E, const char* const* rnas, const int32_t
 	}
 	const double t0 = now_s();
 	if (stats) memset(stats, 0, sizeof *stats);
+	if (hits) {
+		for (int64_t v = 0; v < nvar; v++) {
+			const fasim_variant& x = vars[v];
+			memset(&windows[v], 0, sizeof windows[v]);
+			if (x.alt_len < 0 || x.rec < 0 || x.rec >= nrec || x.pos < 0 || x.pos > rec_len[x.rec] - x.ref_len) continue;
+			int64_t lo, hi;
+			window_of(x, rec_len[x.rec], flank, lo, hi);
+			windows[v].pre = (int32_t)(x.pos - lo); windows[v].post = (int32_t)(hi - x.pos - x.ref_len);
+			windows[v].edge = (lo > 0 ? 1 : 0) | (hi < rec_len[x.rec] ? 2 : 0);
+		}
+	}
+	// the hits of a query before any path is traced: every slot empty
+	auto blank_hits = [&](std::vector<HitOut>& H) {
+		H.assign((size_t)nvar * 8, HitOut());
+		for (size_t k = 0; k < H.size(); k++) { hit_clear(H[k], -1); H[k].t.seg = (int)(k / 8); H[k].empty = true; }
+	};
 	for (int64_t k = 0; k < (int64_t)nq * nvar; k++) {
 		memset(&out[k], 0, sizeof out[k]);
 		for (int a = 0; a < 2; a++) for (int c = 0; c < FASIM_TRACK_CLASSES; c++) out[k].enc[a][c] = -1;
@@ -54,7 +191,17 @@ int fasim_score_variants(fasim_engine* E, const char* const* rnas, const int32_t
 	const int nenc = (int)encs.size();
 	std::vector<int64_t> todo;                    // the variants that are scored
 	for (int64_t v = 0; v < nvar; v++) if (vars[v].alt_len >= 0) todo.push_back(v);
-	if (todo.empty() || nenc == 0) { if (stats) stats->total_s = now_s() - t0; return FASIM_OK; }
+	if (todo.empty() || nenc == 0) {
+		if (hits) {
+			try {
+				std::vector<HitOut> H;
+				blank_hits(H);
+				for (int q = 0; q < nq; q++) if (!(hits[q] = pack_hits(H))) return fail(E, FASIM_E_NOMEM, "out of memory");
+			} catch (const std::bad_alloc&) { return fail(E, FASIM_E_NOMEM, "out of memory"); }
+		}
+		if (stats) stats->total_s = now_s() - t0;
+		return FASIM_OK;
+	}
 	HIPOK(hipSetDevice(E->device));
 	const double ms0 = E->kernel_ms[4];
 	int64_t nprobs = 0, cells = 0;
@@ -66,6 +213,13 @@ int fasim_score_variants(fasim_engine* E, const char* const* rnas, const int32_t
 			rc = upload(E, E->vr_q, qc.data(), qc.size()); if (rc) return rc;
 			const bool rows_hbm = m > TOUCH_LDS_ROWS;
 			const size_t row_bytes = (size_t)6 * (size_t)touch_state_rows(m);      // of one problem
+			std::vector<HitOut> H;
+			PathCtx PC;
+			if (hits) {
+				blank_hits(H);
+				PC.E = E; PC.rna.assign(rnas[q], rnas[q] + m); PC.m = m; PC.encs = encs; PC.host = rs.host(E); PC.rec_off = rec_off; PC.rec_len = rec_len;
+				PC.vars = vars; PC.flank = flank; PC.pc = *pp; PC.pc.ntMin = 1; PC.pc.ntMax = INT_MAX; PC.rows_hbm = rows_hbm; PC.row_bytes = row_bytes;
+			}
 			for (size_t w0 = 0; w0 < todo.size(); ) {
 				std::vector<VarWindow> wins;
 				std::vector<TouchProb> probs;
@@ -143,12 +297,95 @@ int fasim_score_variants(fasim_engine* E, const char* const* rnas, const int32_t
 					}
 					s.flags = (int32_t)(words[(size_t)k * 9 + 8] & 1);
 				}
+				if (hits) { rc = trace_chunk(PC, probs, todo.data() + w0, nv, out + (size_t)q * (size_t)nvar, H); if (rc) return rc; }
 				w0 = w1;
 			}
+			if (hits && !(hits[q] = pack_hits(H))) return fail(E, FASIM_E_NOMEM, "out of memory");
 		}
 	} catch (const std::bad_alloc&) { (void)hipStreamSynchronize(E->st); return fail(E, FASIM_E_NOMEM, "out of memory"); }
 	if (stats) { stats->problems = nprobs; stats->cells = cells; stats->kernel_s = (E->kernel_ms[4] - ms0) * 1e-3; stats->total_s = now_s() - t0; }
 	return FASIM_OK;
+}
+
+}  // namespace
+
+int fasim_score_variants(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
+	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, const fasim_variant* vars, int64_t nvar, int32_t flank,
+	const fasim_params* pp, fasim_variant_score* out, fasim_variant_stats* stats)
+{
+	return score_variants_impl(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, vars, nvar, flank, pp, out, stats, nullptr, nullptr);
+}
+
+int fasim_score_variants_aligned(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
+	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, const fasim_variant* vars, int64_t nvar, int32_t flank,
+	const fasim_params* pp, fasim_variant_score* out, fasim_variant_stats* stats, fasim_variant_window* windows, fasim_site_hits** hits)
+{
+	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
+	if (!hits || (nvar > 0 && !windows)) return fail(E, FASIM_E_ARG, "bad arguments");
+	for (int32_t q = 0; q < nq; q++) hits[q] = nullptr;
+	const int rc = score_variants_impl(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, vars, nvar, flank, pp, out, stats, windows, hits);
+	if (rc) {
+		(void)hipStreamSynchronize(E->st);
+		for (int32_t q = 0; q < nq; q++) { site_hits_free(hits[q]); hits[q] = nullptr; }
+	}
+	return rc;
+}
+
+int fasim_variant_hit_span(const fasim_variant* v, const fasim_variant_window* w, int32_t allele, int32_t enc, int32_t j0, int32_t j1,
+	int64_t* start, int64_t* end, int32_t* clipped)
+{
+	if (!v || !w || !start || !end || allele < 0 || allele > 1 || enc < 0 || enc >= 48) return fail(nullptr, FASIM_E_ARG, "bad arguments");
+	const int64_t pre = w->pre, alen = allele ? v->alt_len : v->ref_len, n = pre + alen + w->post;
+	if (alen < 1 || pre < 0 || w->post < 0 || j0 < 0 || j0 > j1 || j1 >= n) return fail(nullptr, FASIM_E_ARG, "columns [%d, %d] lie outside the window of %lld letters", j0, j1, (long long)n);
+	const int64_t w0 = (enc & 1) ? n - 1 - j1 : j0, w1 = (enc & 1) ? n - 1 - j0 : j1;
+	const int64_t a = v->pos;
+	*start = w0 < pre ? a - pre + w0 : (w0 < pre + alen ? a : a + v->ref_len + (w0 - pre - alen));
+	*end = w1 < pre ? a - pre + w1 + 1 : (w1 < pre + alen ? a + v->ref_len : a + v->ref_len + (w1 - pre - alen) + 1);
+	if (clipped) {
+		const int first = (enc & 1) ? (w->edge >> 1) & 1 : w->edge & 1, last = (enc & 1) ? w->edge & 1 : (w->edge >> 1) & 1;      // the unit's ends
+		*clipped = ((j0 == 0 && first) || (j1 == n - 1 && last)) ? 1 : 0;
+	}
+	return FASIM_OK;
+}
+
+int fasim_variant_hits_tsv(const fasim_variant* vars, const fasim_variant_score* scores, const fasim_variant_window* windows,
+	const fasim_site_hits* hits, int64_t nvar, int32_t flank, const char* rna_name, const uint8_t* matched, char** text, int64_t* text_len)
+{
+	if (nvar < 0 || !rna_name || !text || !text_len || !hits || hits->n != 8 * nvar || (nvar > 0 && (!vars || !scores || !windows)))
+		return fail(nullptr, FASIM_E_ARG, "bad arguments");
+	std::string o = "# fasim variant hits lncRNA="; o += rna_name; o += " flank="; o += std::to_string(flank); o += "\n";
+	o += "line\tchrom\tpos\tid\tref\talt\tallele\tclass\tvalue\trule\tstrand\ttts_start\ttts_end\ttfo_start\ttfo_end\tnt\tidentity\tstability\tcigar\tclipped\tTFO\tTTS\n";
+	char b[128];
+	for (int64_t k = 0; k < nvar; k++) {
+		const fasim_variant& x = vars[k];
+		if (!x.chrom || !x.id || !x.ref || !x.alt) return fail(nullptr, FASIM_E_ARG, "variant %lld lacks a string", (long long)k);
+		if ((matched && !matched[k]) || x.alt_len < 0) continue;
+		const fasim_variant_score& s = scores[k];
+		for (int a = 0; a < 2; a++) for (int c = 0; c < FASIM_TRACK_CLASSES; c++) {
+			if (s.value[a][c] <= 0) continue;
+			const int64_t i = (k * 2 + a) * 4 + c;
+			const fasim_triplex& t = hits->t[i];
+			const int enc = s.enc[a][c];
+			o += std::to_string(x.line); o += "\t"; o += x.chrom; o += "\t"; o += std::to_string(x.pos + 1); o += "\t"; o += x.id; o += "\t"; o += x.ref; o += "\t"; o += x.alt;
+			int n = snprintf(b, sizeof b, "\t%s\t%s\t%d\t", a ? "alt" : "ref", CLASS_NAMES[c], s.value[a][c]);
+			o.append(b, (size_t)n);
+			o += (enc >= 0 && enc < 48) ? std::to_string(enc_info(enc).rule) : std::string("NA");
+			o += (c == 0 || c == 3) ? "\t+" : "\t-";
+			int64_t st = 0, en = 0; int32_t clip = 0;
+			const bool al = hits->cigar_len[i] > 0 && enc >= 0 && enc < 48 &&
+				fasim_variant_hit_span(&x, &windows[k], a, enc, hits->t_begin[i], hits->t_end[i], &st, &en, &clip) == FASIM_OK;
+			if (!al) { o += "\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\n"; continue; }
+			n = snprintf(b, sizeof b, "\t%lld\t%lld\t%d\t%d\t%d\t%g\t%g\t", (long long)st, (long long)en, t.stari, t.endi, t.nt, (double)t.identity, (double)t.tri_score);
+			o.append(b, (size_t)n);
+			for (int32_t j = 0; j < hits->cigar_len[i]; j++) {
+				const uint32_t w = hits->cigar[hits->cigar_off[i] + j];
+				n = snprintf(b, sizeof b, "%u%c", w >> 4, "MID"[(w & 15) < 3 ? (w & 15) : 0]);
+				o.append(b, (size_t)n);
+			}
+			o += clip ? "\t1\t" : "\t0\t"; o += hits->pool + t.tfo_off; o += "\t"; o += hits->pool + t.tts_off; o += "\n";
+		}
+	}
+	return text_out(o, text, text_len);
 }
 
 int fasim_variants_tsv(const fasim_variant* vars, const fasim_variant_score* scores, int64_t nvar, int32_t flank, const char* rna_name,

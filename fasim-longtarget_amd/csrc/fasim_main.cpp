@@ -67,6 +67,11 @@
 //                           Exit status 2, nothing written: a malformed VCF, --variant-flank outside [0, 2048] or without
 //                           --variants, --variants with --regions, --all-records, --accumulate-records, -F, --track, --screen,
 //                           --tfo-profile, --sites, --oligos, --potential-hist or --devices
+//     --variant-hits        with --variants: the alignment behind every score as well, a second table per lncRNA,
+//                           <O>/<lnc>-<f1 minus 3 chars>.variants.hits.tsv (fasim_score_variants_aligned): a
+//                           header line, then one line per (VCF line, ALT, allele, class) with a value: line chrom pos id ref alt
+//                           allele class value rule strand tts_start tts_end tfo_start tfo_end nt identity stability cigar clipped
+//                           TFO TTS.  The .variants.tsv file does not change.  Without --variants: status 2
 //     --screen              with --regions or --all-records: one table per lncRNA, <O>/<lnc>-<f1 stem>.screen.tsv, one line per
 //                           interval (BED order) or record: per strand class the peak of its potential, where it lies (0-based
 //                           genome coordinate) and the rule of the encoding that attains it (fasim_screen_tsv, DESIGN.md section
@@ -547,8 +552,41 @@ struct TailPool {
 // --regions) that contains [POS - 1, POS - 1 + len(REF)), and the record's letters there must equal REF.  Per lncRNA one table,
 // <O>/<lnc>-<f1 minus 3 chars>.variants.tsv.  Exit status 2: a malformed VCF (nothing written, no device opened); 1: variants that no
 // record contains, whose REF differs or whose alleles cannot be scored (NA lines; listed on stderr).
+// --variant-hits: the alignment behind every score as well (fasim_score_variants_aligned, section 21), one more table per lncRNA,
+// <O>/<lnc>-<f1 minus 3 chars>.variants.hits.tsv; the hits of the records' calls are gathered into one list in the VCF's order.
+struct HitGather {
+	std::vector<fasim_triplex> t; std::vector<int32_t> qb, qe, tb, te, clen; std::vector<int64_t> coff; std::vector<uint32_t> cigar; std::vector<char> pool;
+	int64_t unaligned = 0;
+	explicit HitGather(int64_t nvar) : t((size_t)nvar * 8), qb((size_t)nvar * 8, -1), qe((size_t)nvar * 8, -1), tb((size_t)nvar * 8, -1), te((size_t)nvar * 8, -1),
+		clen((size_t)nvar * 8, 0), coff((size_t)nvar * 8, 0), pool(1, '\0') { if (!t.empty()) memset(t.data(), 0, t.size() * sizeof(fasim_triplex)); }
+	// the eight hits of variant `from` of h become those of variant `to`
+	void take(const fasim_site_hits* h, int64_t from, int64_t to)
+	{
+		for (int s = 0; s < 8; s++) {
+			const size_t a = (size_t)from * 8 + (size_t)s, b = (size_t)to * 8 + (size_t)s;
+			t[b] = h->t[a]; t[b].seg = (int32_t)to;
+			qb[b] = h->q_begin[a]; qe[b] = h->q_end[a]; tb[b] = h->t_begin[a]; te[b] = h->t_end[a]; clen[b] = h->cigar_len[a];
+			coff[b] = (int64_t)cigar.size();
+			if (h->cigar_len[a] < 0) unaligned++;
+			if (h->cigar_len[a] <= 0) { t[b].tfo_off = t[b].tts_off = 0; continue; }
+			cigar.insert(cigar.end(), h->cigar + h->cigar_off[a], h->cigar + h->cigar_off[a] + h->cigar_len[a]);
+			const char* tfo = h->pool + h->t[a].tfo_off; const char* tts = h->pool + h->t[a].tts_off;
+			t[b].tfo_off = (int64_t)pool.size(); pool.insert(pool.end(), tfo, tfo + strlen(tfo) + 1);
+			t[b].tts_off = (int64_t)pool.size(); pool.insert(pool.end(), tts, tts + strlen(tts) + 1);
+		}
+	}
+	fasim_site_hits view()
+	{
+		if (cigar.empty()) cigar.push_back(0);
+		fasim_site_hits h;
+		h.n = (int64_t)t.size(); h.t = t.data(); h.q_begin = qb.data(); h.q_end = qe.data(); h.t_begin = tb.data(); h.t_end = te.data();
+		h.cigar_off = coff.data(); h.cigar_len = clen.data(); h.cigar = cigar.data(); h.pool = pool.data(); h.pool_len = (int64_t)pool.size(); h.unaligned = unaligned;
+		return h;
+	}
+};
+
 static int run_variants(const std::string& vcf_path, int flank, const std::string& f1, const std::string& f2, const std::string& outdir, int device,
-	bool upper, const fasim_params& p)
+	bool upper, const fasim_params& p, bool want_hits)
 {
 	fasim_variant* vars = nullptr; int64_t nvar = 0;
 	if (fasim_read_vcf(vcf_path.c_str(), &vars, &nvar) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 2; }
@@ -570,6 +608,9 @@ static int run_variants(const std::string& vcf_path, int flank, const std::strin
 	// state of an entry: 0 not met, 1 scored, 2 REF differs, 3 unusable alleles
 	std::vector<uint8_t> state((size_t)nvar, 0);
 	std::vector<std::vector<fasim_variant_score>> scores((size_t)nq, std::vector<fasim_variant_score>((size_t)nvar));
+	std::vector<fasim_variant_window> windows(want_hits ? (size_t)nvar : 0);
+	std::vector<HitGather> gathered;
+	if (want_hits) { memset(windows.data(), 0, windows.size() * sizeof(fasim_variant_window)); for (int q = 0; q < nq; q++) gathered.emplace_back(nvar); }
 	std::map<std::string, std::multimap<int64_t, int64_t>> todo;
 	std::set<std::string> chroms_seen;
 	for (int64_t k = 0; k < nvar; k++) {
@@ -604,10 +645,22 @@ static int run_variants(const std::string& vcf_path, int flank, const std::strin
 		if (!eng && fasim_engine_create(device, &eng) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
 		const int64_t off0 = 0, len0 = (int64_t)rec.seq.size();
 		std::vector<fasim_variant_score> got((size_t)nq * mine.size());
-		if (fasim_score_variants(eng, qp.data(), ql.data(), nq, rec.seq.data(), &off0, &len0, 1, loc.data(), (int64_t)loc.size(), flank, &p, got.data(), nullptr) != FASIM_OK) {
+		std::vector<fasim_variant_window> wloc(want_hits ? mine.size() : 0);
+		std::vector<fasim_site_hits*> hloc(want_hits ? (size_t)nq : 0, nullptr);
+		const int rc = want_hits
+			? fasim_score_variants_aligned(eng, qp.data(), ql.data(), nq, rec.seq.data(), &off0, &len0, 1, loc.data(), (int64_t)loc.size(), flank, &p, got.data(), nullptr, wloc.data(), hloc.data())
+			: fasim_score_variants(eng, qp.data(), ql.data(), nq, rec.seq.data(), &off0, &len0, 1, loc.data(), (int64_t)loc.size(), flank, &p, got.data(), nullptr);
+		if (rc != FASIM_OK) {
 			fprintf(stderr, "fasim: %s\n", fasim_last_error(eng));
 			fasim_engine_destroy(eng);
 			return 1;
+		}
+		if (want_hits) {
+			for (size_t k = 0; k < mine.size(); k++) windows[(size_t)mine[k]] = wloc[k];
+			for (int q = 0; q < nq; q++) {
+				for (size_t k = 0; k < mine.size(); k++) gathered[(size_t)q].take(hloc[(size_t)q], (int64_t)k, mine[k]);
+				fasim_site_hits_free(hloc[(size_t)q]);
+			}
 		}
 		for (int q = 0; q < nq; q++) for (size_t k = 0; k < mine.size(); k++) scores[(size_t)q][(size_t)mine[k]] = got[(size_t)q * mine.size() + k];
 		for (int64_t k : mine) state[(size_t)k] = 1;
@@ -622,6 +675,12 @@ static int run_variants(const std::string& vcf_path, int flank, const std::strin
 		char* text = nullptr; int64_t len = 0;
 		if (fasim_variants_tsv(vars, scores[(size_t)q].data(), nvar, flank, rnas[(size_t)q].name.c_str(), matched.data(), &text, &len) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
 		bad |= write_file(outdir + "/" + rnas[(size_t)q].name + "-" + base + ".variants.tsv", text, len);
+		fasim_free(text);
+		if (!want_hits) continue;
+		const fasim_site_hits view = gathered[(size_t)q].view();
+		text = nullptr; len = 0;
+		if (fasim_variant_hits_tsv(vars, scores[(size_t)q].data(), windows.data(), &view, nvar, flank, rnas[(size_t)q].name.c_str(), matched.data(), &text, &len) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
+		bad |= write_file(outdir + "/" + rnas[(size_t)q].name + "-" + base + ".variants.hits.tsv", text, len);
 		fasim_free(text);
 	}
 	if (bad) return 1;
@@ -643,7 +702,7 @@ int main(int argc, char* const* argv)
 {
 	fasim_params p; fasim_params_default(&p);
 	std::string f1 = "./", f2 = "./", outdir = "./", bed_path, vcf_path;
-	bool devices_given = false, flank_given = false; int variant_flank = 300;
+	bool devices_given = false, flank_given = false, variant_hits = false; int variant_flank = 300;
 	std::vector<int> devices(1, 0);
 	bool stats = false, all_records = false, accumulate = false, upper = false, track = false, screen = false, screen_only = false;
 	bool sites = false, sites_gap_given = false, hist_arg_given = false, hist_arg_bad = false;
@@ -663,7 +722,8 @@ int main(int argc, char* const* argv)
 		{ "sites", required_argument, NULL, 1016 }, { "sites-gap", required_argument, NULL, 1017 }, { "sites-only", no_argument, NULL, 1018 }, { "sites-align", no_argument, NULL, 1019 }, { "oligos", no_argument, NULL, 1020 }, { "oligo-hits", no_argument, NULL, 1026 },
 		{ "potential-hist", no_argument, NULL, 1021 }, { "hist-controls", required_argument, NULL, 1022 }, { "hist-seed", required_argument, NULL, 1023 },
 		{ "hist-fdr", required_argument, NULL, 1024 }, { "potential-hist-only", no_argument, NULL, 1025 },
-		{ "variants", required_argument, NULL, 1027 }, { "variant-flank", required_argument, NULL, 1028 }, { 0, 0, 0, 0 } };
+		{ "variants", required_argument, NULL, 1027 }, { "variant-flank", required_argument, NULL, 1028 },
+		{ "variant-hits", no_argument, NULL, 1029 }, { 0, 0, 0, 0 } };
 	int opt;
 	while ((opt = getopt_long_only(argc, argv, optstring, lo, NULL)) != -1) {
 		switch (opt) {
@@ -691,6 +751,7 @@ int main(int argc, char* const* argv)
 		case 1003: all_records = true; break;
 		case 1027: vcf_path = optarg; break;
 		case 1028: flank_given = true; variant_flank = strict_int(optarg, -1); break;
+		case 1029: variant_hits = true; break;
 		case 1004: devices_given = true; devices = parse_devices(optarg); if (devices.empty()) { fprintf(stderr, "fasim: bad --devices list\n"); return 2; } break;
 		case 1005: accumulate = true; break;
 		case 1006: upper = true; break;
@@ -714,7 +775,7 @@ int main(int argc, char* const* argv)
 		case 1023: { hist_arg_given = true; char* end = nullptr; errno = 0; trk.hist_seed = strtoull(optarg, &end, 10); if (end == optarg || *end != '\0' || errno == ERANGE || optarg[0] == '-') hist_arg_bad = true; break; }
 		case 1024: { hist_arg_given = true; char* end = nullptr; trk.hist_fdr = strtod(optarg, &end); if (end == optarg || *end != '\0') trk.hist_fdr = -1.0; break; }
 		case 1025: trk.hist_only = true; break;
-		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only] [--sites-align] [--oligos [--oligo-hits]]] [--potential-hist [--hist-controls K] [--hist-seed S] [--hist-fdr Q] [--potential-hist-only]] [--variants FILE.vcf [--variant-flank F]]\n"); return 2;
+		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only] [--sites-align] [--oligos [--oligo-hits]]] [--potential-hist [--hist-controls K] [--hist-seed S] [--hist-fdr Q] [--potential-hist-only]] [--variants FILE.vcf [--variant-flank F] [--variant-hits]]\n"); return 2;
 		}
 	}
 	if (all_records && accumulate) { fprintf(stderr, "fasim: --all-records and --accumulate-records exclude each other\n"); return 2; }
@@ -743,12 +804,13 @@ int main(int argc, char* const* argv)
 	if (trk.oligo_hits && (!trk.oligos || !sites || trk.hist)) { fprintf(stderr, "fasim: --oligo-hits needs --oligos --sites V (and is not available with --potential-hist)\n"); return 2; }
 	const bool variants = !vcf_path.empty();
 	if (flank_given && !variants) { fprintf(stderr, "fasim: --variant-flank needs --variants FILE.vcf\n"); return 2; }
+	if (variant_hits && !variants) { fprintf(stderr, "fasim: --variant-hits needs --variants FILE.vcf\n"); return 2; }
 	if (variants && (variant_flank < 0 || variant_flank > FASIM_MAX_FLANK)) { fprintf(stderr, "fasim: --variant-flank needs an integer in [0, %d]\n", FASIM_MAX_FLANK); return 2; }
 	if (variants && (regions || all_records || accumulate || p.classicSim || track || screen || trk.tfo || sites || trk.oligos || trk.hist || devices_given)) {
 		fprintf(stderr, "fasim: --variants is not available with --regions, --all-records, --accumulate-records, -F, --track, --screen, --tfo-profile, --sites, --oligos, --potential-hist or --devices\n");
 		return 2;
 	}
-	if (variants) return run_variants(vcf_path, variant_flank, f1, f2, outdir, devices[0], upper, p);
+	if (variants) return run_variants(vcf_path, variant_flank, f1, f2, outdir, devices[0], upper, p, variant_hits);
 	if (trk.oligos) trk.sites_only = true;      // a panel has no triplex records: the sites files and the panel table are all it writes
 	if (trk.oligos && trk.hist) trk.hist_only = true;      // (or the oligos' histograms)
 	if (!sites) trk.sites = 0;

@@ -247,6 +247,19 @@ int touch_threads(int m);        // threads of k_touch's workgroup: 64, 128 or 2
 int touch_state_rows(int m);     // 16-bit words per array of a problem's row state: m rounded up to whole rows-per-thread x threads
 hipError_t launch_touch(const TouchLaunch& L, hipStream_t st);
 hipError_t launch_touch_reduce(const TouchReduceLaunch& L, hipStream_t st);
+// k_touch_path: the path behind a value.  One item = problem `prob` of the launch that k_var_encode served,
+// with the plain value its unit attains; its direction bytes at dirs + dir_off ([n][touch_state_rows(m)]), its CIGAR words (last
+// operation first, (len << 4) | op) at cigar + cig_off, at most cig_cap of them
+constexpr int64_t TOUCH_PATH_MAX_CELLS = (int64_t)1 << 26;      // m * n of a problem that is traced
+struct TouchPathItem { int64_t dir_off; int32_t prob, value, cig_off, cig_cap; };
+struct TouchPathOut { int32_t i1, j1, i0, j0, cigar_len, pad[3]; };      // cigar_len -1: no path (cells as far as they were found, else -1)
+struct TouchPathLaunch {
+	const uint8_t* tcodes; const uint8_t* qcodes; int32_t m;
+	const TouchProb* probs; const TouchPathItem* items; int32_t nitem;
+	uint16_t* rows;               // [nitem][3][touch_state_rows(m)] where m > TOUCH_LDS_ROWS, else NULL
+	uint8_t* dirs; uint32_t* cigar; TouchPathOut* out;      // out[nitem]
+};
+hipError_t launch_touch_path(const TouchPathLaunch& L, hipStream_t st);
 
 // ---- rowfold.hip: per-base profile of the lncRNA folded from the row maxima of a batch -------------------------
 // Group g = segments [gfirst[g], gfirst[g + 1]) of the batch (the run of segments of one record, or the whole batch); the result is

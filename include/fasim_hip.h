@@ -669,6 +669,48 @@ int fasim_score_variants(fasim_engine* e, const char* const* rnas, const int32_t
  * (matched may be NULL: all matched) or alt_len < 0 has NA in every column after alt.  Free with fasim_free. */
 int fasim_variants_tsv(const fasim_variant* vars, const fasim_variant_score* scores, int64_t nvar, int32_t flank, const char* rna_name,
                        const uint8_t* matched /* [nvar] or NULL */, char** text, int64_t* text_len);
+/* ---- the alignment behind every variant score (csrc/variant_path.hip) ---------------------------------------- */
+/* The HIT of a slot (variant, allele, class) with value > 0 is the alignment the touching matrix T counted, in the unit of the
+ * encoding fasim_score_variants reports for the slot.  End cell (i1, j1): the smallest column j1 >= v0 at which a real row holds
+ * T == value, the smallest such row i1.  Path: traced back in T from (i1, j1) in state H with fixed priorities -- with d the diagonal
+ * neighbour's T (0 outside the matrix) and s the pair's score: d > 0 and T == d + s: diagonal; else d == 0, j < v1 and T == s: the
+ * alignment's first pair (i0, j0), stop; else T == E: state E; else state F; in a gap state extend before open.  E consumes a target
+ * column (CIGAR D), F a query row (CIGAR I).  The CIGAR begins with M; it ends with M, or with one D run where the allele is reached
+ * only through a gap.  The record is that of section 15: the alignment goes through the conversion of fasim_scan with -ni 1 and no
+ * -na over the window's letters (the ALT window for allele 1), dna_start = the window's first record offset, t.seg = the variant's
+ * index in the call, t.score = value.
+ * fasim_variant_window: the letters of the record before (pre) and after (post) REF inside the flank; edge bit 0 / 1: the lower /
+ * upper end of the window was cut by the flank and not by the record's end. */
+typedef struct fasim_variant_window { int32_t pre, post, edge, reserved; } fasim_variant_window;
+/* fasim_score_variants and the hit of every slot: the arguments, refusals and -- byte for byte -- the scores of fasim_score_variants,
+ * then windows[v] and hits[q] (both required, else FASIM_E_ARG): hits[q]->n = 8 * nvar, hit (v * 2 + allele) * 4 + class; q_begin,
+ * q_end, t_begin, t_end = i0, i1, j0, j1 in the unit.  A slot without a value has cigar_len 0, nt 0, cells -1 and empty strings.  A
+ * slot whose problem has more than 2^26 cells (query length x window length), or whose path the kernel did not find, has
+ * cigar_len -1 and is counted in `unaligned`.  Hits are never filtered.  The hit depends on the record, the variant, the flank, the
+ * query and the parameters only.  FASIM_E_NOMEM leaves the engine usable.  Free each hits[q] with fasim_site_hits_free. */
+int fasim_score_variants_aligned(fasim_engine* e, const char* const* rnas, const int32_t* rna_lens, int32_t nq,
+                                 const char* dna, const int64_t* rec_off, const int64_t* rec_len, int32_t nrec,
+                                 const fasim_variant* vars, int64_t nvar, int32_t flank, const fasim_params* p,
+                                 fasim_variant_score* out /* [nq * nvar] */, fasim_variant_stats* stats /* may be NULL */,
+                                 fasim_variant_window* windows /* [nvar] */, fasim_site_hits** hits /* [nq] */);
+/* Pure host code: the reference bases [*start, *end) (0-based, in the coordinates of v->pos) that the unit columns [j0, j1] of a hit
+ * of `allele` under `enc` cover.  The columns are window letters [w0, w1] in forward orientation (w = n - 1 - j for an odd
+ * encoding); letters before the allele map to themselves, letters of the allele to REF's range (start: its first base, end: its
+ * last), letters behind it are shifted by the difference of the alleles' lengths.  For allele 0 this is the identity.  *clipped
+ * (may be NULL): the columns include the unit's first column and that end of the window was cut by the flank, or its last column
+ * and that end was cut.  FASIM_E_ARG: a NULL pointer, an allele outside {0, 1}, an encoding outside [0, 48), columns outside the
+ * window. */
+int fasim_variant_hit_span(const fasim_variant* v, const fasim_variant_window* w, int32_t allele, int32_t enc, int32_t j0, int32_t j1,
+                           int64_t* start, int64_t* end, int32_t* clipped);
+/* The table `fasim --variants --variant-hits` writes for one query: `# fasim variant hits lncRNA=<rna_name> flank=<F>`, the line of
+ * column names, then one tab-separated line per (entry, allele, class) with value > 0, ref before alt, classes in their order: line
+ * chrom pos id ref alt allele class value rule strand tts_start tts_end tfo_start tfo_end nt identity stability cigar clipped TFO
+ * TTS.  tts_start / tts_end: fasim_variant_hit_span; tfo_start / tfo_end: 1-based inclusive query positions; rule, strand, identity,
+ * stability and cigar as fasim_site_hits_tsv prints them.  An unaligned hit has NA from tts_start on.  An entry with matched[k] == 0
+ * or alt_len < 0 gets no lines.  hits->n must be 8 * nvar.  Free with fasim_free. */
+int fasim_variant_hits_tsv(const fasim_variant* vars, const fasim_variant_score* scores, const fasim_variant_window* windows,
+                           const fasim_site_hits* hits, int64_t nvar, int32_t flank, const char* rna_name,
+                           const uint8_t* matched /* [nvar] or NULL */, char** text, int64_t* text_len);
 /* ingest helper: upper-cases a DNA record in place (soft-masked genomes such as UCSC hg38 carry repeats in lower
  * case; the reference does not upper-case and treats such letters as unknown, rules.h:286-312, 82-83). */
 void fasim_upper_case(char* seq, int64_t n);
