@@ -509,6 +509,25 @@ struct HitOut {
 };
 void hit_clear(HitOut& H, int enc);                            // the numbers of a hit that has no alignment (yet): zeros, seg -1
 fasim_site_hits* pack_hits(const std::vector<HitOut>& v);      // NULL: out of memory
+// The path k_site_path / k_touch_path returned between the cells H already carries, as a hit: `len` CIGAR words, last operation first,
+// over the n letters `seg` from `origin` of their record.  Where convert_triplex gives no record, H stays unaligned as it was.
+void path_hit(HitOut& H, const uint32_t* cig, int len, int value, const std::string& rna, const char* seg, int n, int enc, long origin, const fasim_params& pc, int seg_id);
+// One launch of path items (SitePathItem, TouchPathItem): items[a .. end) get their dir_off and cig_off, up to the item that would
+// take the direction bytes past dir_cap or the CIGAR words past cig_cap (the first always fits); dims(item) = its {rows, columns}.
+struct LaunchCut { size_t end; int64_t dir_total, cig_total; int max_rows; };
+template <class Item, class Dims>
+LaunchCut cut_launch(std::vector<Item>& items, size_t a, int64_t dir_cap, int64_t cig_cap, Dims dims)
+{
+	LaunchCut c = { a, 0, 0, 1 };
+	for (; c.end < items.size(); c.end++) {
+		Item& I = items[c.end];
+		const std::pair<int64_t, int64_t> d = dims(I);
+		if (c.end > a && (c.dir_total + d.first * d.second > dir_cap || c.cig_total + I.cig_cap > cig_cap)) break;
+		I.dir_off = c.dir_total; I.cig_off = (int32_t)c.cig_total;
+		c.dir_total += d.first * d.second; c.cig_total += I.cig_cap; c.max_rows = std::max(c.max_rows, (int)d.first);
+	}
+	return c;
+}
 
 // ---- histogram of the potential (fasim_scan_records_hist, hist.hip, engine_hist.cpp) ---------------------------------------------
 // One side of the overlap of two neighbouring segments of a record, as the values of that segment alone: boundary b of a record is

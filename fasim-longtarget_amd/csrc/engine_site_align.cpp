@@ -24,6 +24,18 @@ void hit_clear(HitOut& H, int enc)
 	H.t.score = H.t.identity = H.t.tri_score = 0.0f; H.t.seg = -1; H.t.enc = enc;
 }
 
+void path_hit(HitOut& H, const uint32_t* cig, int len, int value, const std::string& rna, const char* seg, int n, int enc, long origin, const fasim_params& pc, int seg_id)
+{
+	H.cigar.assign(cig, cig + len);
+	std::reverse(H.cigar.begin(), H.cigar.end());      // the traceback wrote the last operation first
+	AlignResult al;
+	al.sw_score = value; al.ref_begin = H.j0; al.ref_end = H.j1; al.query_begin = H.i0; al.query_end = H.i1; al.cigar_len = len;
+	std::vector<HostTriplex> one;
+	convert_triplex(al, H.cigar.data(), rna, seg, n, enc, origin, pc, one, only_acgtn(seg, n), true);
+	if (one.empty()) { H.cigar.clear(); return; }
+	H.t = std::move(one[0]); H.t.seg = seg_id; H.t.enc = enc; H.aligned = true;
+}
+
 // the hit list of one (query, record) from its hits in site order
 fasim_site_hits* pack_hits(const std::vector<HitOut>& v)
 {
@@ -101,8 +113,7 @@ int run_site_align(fasim_engine* E, SiteAlignReq& R)
 				for (int64_t k = 0; k < S->n; k++) {
 					const fasim_site& x = S->s[k];
 					HitOut& H = hits[(size_t)r][(size_t)k];
-					H.t = HostTriplex(); H.t.stari = H.t.endi = H.t.starj = H.t.endj = H.t.strand = H.t.reverse = H.t.rule = H.t.nt = 0;
-					H.t.score = H.t.identity = H.t.tri_score = 0.0f; H.t.seg = -1; H.t.enc = x.enc;
+					hit_clear(H, x.enc);
 					const int site = (int)flat.size();
 					flat.emplace_back(r, (int)k);
 					if (x.value >= 16383 || x.value < 1 || x.enc < 0 || x.enc >= 48) continue;      // a saturated unit: no hit
@@ -202,32 +213,25 @@ int run_site_align(fasim_engine* E, SiteAlignReq& R)
 				}
 				// path launches: at most 512 MB of direction bytes each
 				for (size_t a = 0; a < items.size(); ) {
-					size_t b = a; int64_t dir_total = 0, cig_total = 0; int max_rows = 1;
-					for (; b < items.size(); b++) {
-						SitePathItem& I = items[b];
-						const int64_t rows = I.i1 - I.i0 + 1, cols = I.j1 - I.j0 + 1;
-						if (b > a && (dir_total + rows * cols > ((int64_t)512 << 20) || cig_total + I.cig_cap > ((int64_t)1 << 28))) break;
-						I.dir_off = dir_total; I.cig_off = (int32_t)cig_total;
-						dir_total += rows * cols; cig_total += I.cig_cap; max_rows = std::max(max_rows, (int)rows);
-						cells += rows * cols;
-					}
-					const int ni = (int)(b - a);
-					if (E->sa_items.ensure((size_t)ni * sizeof(SitePathItem)) != hipSuccess || E->sa_dirs.ensure((size_t)dir_total) != hipSuccess ||
-						E->sa_cigar.ensure((size_t)cig_total * sizeof(uint32_t)) != hipSuccess || E->sa_ciglen.ensure((size_t)ni * sizeof(int32_t)) != hipSuccess) {
+					const LaunchCut cut = cut_launch(items, a, (int64_t)512 << 20, (int64_t)1 << 28, [](const SitePathItem& I) { return std::pair<int64_t, int64_t>(I.i1 - I.i0 + 1, I.j1 - I.j0 + 1); });
+					cells += cut.dir_total;
+					const int ni = (int)(cut.end - a);
+					if (E->sa_items.ensure((size_t)ni * sizeof(SitePathItem)) != hipSuccess || E->sa_dirs.ensure((size_t)cut.dir_total) != hipSuccess ||
+						E->sa_cigar.ensure((size_t)cut.cig_total * sizeof(uint32_t)) != hipSuccess || E->sa_ciglen.ensure((size_t)ni * sizeof(int32_t)) != hipSuccess) {
 						(void)hipGetLastError();
-						return fail(E, FASIM_E_NOMEM, "site hits: no device memory for the direction bytes of %d paths (%lld bytes)", ni, (long long)dir_total);
+						return fail(E, FASIM_E_NOMEM, "site hits: no device memory for the direction bytes of %d paths (%lld bytes)", ni, (long long)cut.dir_total);
 					}
 					HIPOK(hipMemcpyAsync(E->sa_items.p, items.data() + a, (size_t)ni * sizeof(SitePathItem), hipMemcpyHostToDevice, E->st));
 					SitePathLaunch PL;
 					PL.tcodes = E->sa_tcodes.as<uint8_t>(); PL.qcodes = E->sa_q.as<uint8_t>(); PL.probs = E->sa_probs.as<SiteAlignProb>();
-					PL.items = E->sa_items.as<SitePathItem>(); PL.nitem = ni; PL.max_rows = max_rows;
+					PL.items = E->sa_items.as<SitePathItem>(); PL.nitem = ni; PL.max_rows = cut.max_rows;
 					PL.dirs = E->sa_dirs.as<uint8_t>(); PL.cigar = E->sa_cigar.as<uint32_t>(); PL.cigar_len = E->sa_ciglen.as<int32_t>();
 					{ TimedScope ts(E, 4); he = launch_site_path(PL, E->st); }
 					if (he != hipSuccess) return fail(E, FASIM_E_HIP, "site hits (path) launch failed: %s", hipGetErrorString(he));
 					std::vector<int32_t> clen((size_t)ni);
-					std::vector<uint32_t> cig((size_t)cig_total);
+					std::vector<uint32_t> cig((size_t)cut.cig_total);
 					HIPOK(hipMemcpyAsync(clen.data(), E->sa_ciglen.p, (size_t)ni * sizeof(int32_t), hipMemcpyDeviceToHost, E->st));
-					HIPOK(hipMemcpyAsync(cig.data(), E->sa_cigar.p, (size_t)cig_total * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st));
+					HIPOK(hipMemcpyAsync(cig.data(), E->sa_cigar.p, (size_t)cut.cig_total * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st));
 					HIPOK(hipStreamSynchronize(E->st));
 					drain_timed(E);
 					for (int k = 0; k < ni; k++) {
@@ -235,17 +239,9 @@ int run_site_align(fasim_engine* E, SiteAlignReq& R)
 						const Work& w = work[item_work[a + (size_t)k]];
 						if (clen[(size_t)k] < 1 || clen[(size_t)k] > I.cig_cap) continue;
 						HitOut& H = hits[(size_t)flat[(size_t)w.site].first][(size_t)flat[(size_t)w.site].second];
-						H.cigar.assign(cig.begin() + I.cig_off, cig.begin() + I.cig_off + clen[(size_t)k]);
-						std::reverse(H.cigar.begin(), H.cigar.end());      // the traceback wrote the last operation first
-						AlignResult al;
-						al.sw_score = w.value; al.ref_begin = I.j0; al.ref_end = I.j1; al.query_begin = I.i0; al.query_end = I.i1; al.cigar_len = (int)H.cigar.size();
-						std::vector<HostTriplex> one;
-						const char* seg = R.dna + w.soff;
-						convert_triplex(al, H.cigar.data(), rna, seg, w.n, w.enc, (long)(w.seg * step), pc, one, only_acgtn(seg, w.n), true);
-						if (one.empty()) { H.cigar.clear(); continue; }
-						H.t = std::move(one[0]); H.t.seg = (int)w.seg; H.t.enc = w.enc; H.aligned = true;
+						path_hit(H, cig.data() + I.cig_off, clen[(size_t)k], w.value, rna, R.dna + w.soff, w.n, w.enc, (long)(w.seg * step), pc, (int)w.seg);
 					}
-					a = b;
+					a = cut.end;
 				}
 				w0 = w1;
 			}
@@ -319,8 +315,7 @@ int fasim_site_hits_merge(const fasim_sites* const* sites, const fasim_site_hits
 		for (int64_t i = 0; i < M->n; i++) {
 			const fasim_site& x = M->s[i];
 			HitOut& H = v[(size_t)i];
-			H.t = HostTriplex(); H.t.stari = H.t.endi = H.t.starj = H.t.endj = H.t.strand = H.t.reverse = H.t.rule = H.t.nt = 0;
-			H.t.score = H.t.identity = H.t.tri_score = 0.0f; H.t.seg = -1; H.t.enc = x.enc;
+			hit_clear(H, x.enc);
 			auto it = std::lower_bound(refs.begin(), refs.end(), x, [](const Ref& a, const fasim_site& s) { return a.cls != s.cls ? a.cls < s.cls : a.start < s.start; });
 			int bp = -1; int64_t bi = -1;
 			for (; it != refs.end() && it->cls == x.cls && it->start < x.end; ++it) {

@@ -79,8 +79,6 @@ int trace_chunk(const PathCtx& C, const std::vector<TouchProb>& probs, const int
 			HitOut& h = H[w.slot];
 			h.i0 = o.i0; h.i1 = o.i1; h.j0 = o.j0; h.j1 = o.j1;
 			if (o.cigar_len < 1 || o.cigar_len > I.cig_cap || o.i0 < 0 || o.j0 < 0 || o.i0 > o.i1 || o.j0 > o.j1 || o.i1 >= m || o.j1 >= n) continue;
-			h.cigar.assign(cig.begin() + I.cig_off, cig.begin() + I.cig_off + o.cigar_len);
-			std::reverse(h.cigar.begin(), h.cigar.end());      // the traceback wrote the last operation first
 			// the window's letters: the record's own, or the ALT window assembled here
 			const fasim_variant& x = C.vars[w.v];
 			int64_t lo, hi;
@@ -92,29 +90,17 @@ int trace_chunk(const PathCtx& C, const std::vector<TouchProb>& probs, const int
 				alt_win.append(C.host + C.rec_off[x.rec] + x.pos + x.ref_len, (size_t)(hi - x.pos - x.ref_len));
 				seg = alt_win.data();
 			}
-			AlignResult al;
-			al.sw_score = w.value; al.ref_begin = o.j0; al.ref_end = o.j1; al.query_begin = o.i0; al.query_end = o.i1; al.cigar_len = (int)h.cigar.size();
-			std::vector<HostTriplex> one;
-			convert_triplex(al, h.cigar.data(), C.rna, seg, n, w.enc, (long)lo, C.pc, one, only_acgtn(seg, n), true);
-			if (one.empty()) { h.cigar.clear(); continue; }
-			h.t = std::move(one[0]); h.t.seg = (int)w.v; h.t.enc = w.enc; h.aligned = true;
+			path_hit(h, cig.data() + I.cig_off, o.cigar_len, w.value, C.rna, seg, n, w.enc, (long)lo, C.pc, (int)w.v);
 		}
 	};
 	for (size_t a = 0; a < items.size(); ) {
-		size_t b = a; int64_t dir_total = 0, cig_total = 0;
-		for (; b < items.size(); b++) {
-			TouchPathItem& I = items[b];
-			const int64_t bytes = rows * probs[(size_t)I.prob].n;
-			if (b > a && (dir_total + bytes > VR_DIR_BYTES || cig_total + I.cig_cap > VR_CIG_WORDS)) break;
-			I.dir_off = dir_total; I.cig_off = (int32_t)cig_total;
-			dir_total += bytes; cig_total += I.cig_cap;
-		}
-		const int ni = (int)(b - a);
-		if (E->vr_items.ensure((size_t)ni * sizeof(TouchPathItem)) != hipSuccess || E->vr_dirs.ensure((size_t)dir_total) != hipSuccess ||
-			E->vr_cigar.ensure((size_t)cig_total * sizeof(uint32_t)) != hipSuccess || E->vr_paths.ensure((size_t)ni * sizeof(TouchPathOut)) != hipSuccess ||
+		const LaunchCut cut = cut_launch(items, a, VR_DIR_BYTES, VR_CIG_WORDS, [&](const TouchPathItem& I) { return std::pair<int64_t, int64_t>(rows, probs[(size_t)I.prob].n); });
+		const int ni = (int)(cut.end - a);
+		if (E->vr_items.ensure((size_t)ni * sizeof(TouchPathItem)) != hipSuccess || E->vr_dirs.ensure((size_t)cut.dir_total) != hipSuccess ||
+			E->vr_cigar.ensure((size_t)cut.cig_total * sizeof(uint32_t)) != hipSuccess || E->vr_paths.ensure((size_t)ni * sizeof(TouchPathOut)) != hipSuccess ||
 			(C.rows_hbm && E->vr_rows.ensure((size_t)ni * C.row_bytes) != hipSuccess)) {
 			(void)hipGetLastError();
-			return fail(E, FASIM_E_NOMEM, "variant hits: no device memory for the direction bytes of %d paths (%lld bytes)", ni, (long long)dir_total);
+			return fail(E, FASIM_E_NOMEM, "variant hits: no device memory for the direction bytes of %d paths (%lld bytes)", ni, (long long)cut.dir_total);
 		}
 		HIPOK(hipMemcpyAsync(E->vr_items.p, items.data() + a, (size_t)ni * sizeof(TouchPathItem), hipMemcpyHostToDevice, E->st));
 		TouchPathLaunch PL;
@@ -125,13 +111,13 @@ int trace_chunk(const PathCtx& C, const std::vector<TouchProb>& probs, const int
 		{ TimedScope ts(E, 4); he = launch_touch_path(PL, E->st); }
 		if (he != hipSuccess) return fail(E, FASIM_E_HIP, "variant hits (path) launch failed: %s", hipGetErrorString(he));
 		if (prev.ni) finish(prev);      // (before the copies back: they wait for the kernel)
-		Done cur; cur.a = a; cur.ni = ni; cur.outs.resize((size_t)ni); cur.cig.resize((size_t)cig_total);
+		Done cur; cur.a = a; cur.ni = ni; cur.outs.resize((size_t)ni); cur.cig.resize((size_t)cut.cig_total);
 		HIPOK(hipMemcpyAsync(cur.outs.data(), E->vr_paths.p, (size_t)ni * sizeof(TouchPathOut), hipMemcpyDeviceToHost, E->st));
-		HIPOK(hipMemcpyAsync(cur.cig.data(), E->vr_cigar.p, (size_t)cig_total * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st));
+		HIPOK(hipMemcpyAsync(cur.cig.data(), E->vr_cigar.p, (size_t)cut.cig_total * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st));
 		HIPOK(hipStreamSynchronize(E->st));
 		drain_timed(E);
 		prev = std::move(cur);
-		a = b;
+		a = cut.end;
 	}
 	if (prev.ni) finish(prev);
 	return FASIM_OK;

@@ -17,18 +17,17 @@
 // hand to the row below them (opened in the thread's own rows; a gap never opens better from a cell that a gap reached), the scan
 //   F_in(t) = max over t' < t of out(t') - 4 * rows * (t - 1 - t')
 // gives every thread the gap value that enters its first row, and the second walk is the plain sequential recurrence from it.
-// Passes (i) and (ii) scan with __shfl_up and one LDS word per wave; pass (iii) also needs to know whether the entering gap was
+// Passes (i) and (ii) scan with colstep.h's scan_excl; pass (iii) also needs to know whether the entering gap was
 // extended or opened in the row above, so there every thread folds the (at most 256) outputs before it from LDS in order.
 // No atomics on global memory, plain vector stores only; every output word has one writer.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "kernels.h"
+#include "colstep.h"
 
 namespace fasim {
 
 constexpr int SA_THREADS = 256;
 constexpr int SA_NEG = -30000;                 // "no alignment" in the 16-bit state (real scores of a path stay above -16 384); safe for units of at most SITE_ALIGN_MAX_COLS columns: -30 000 + 5 * 6 000 < 1 and 5 * 6 000 < 32 767
-constexpr int SA_NEG32 = -(1 << 28);           // the same in the scans
 
 struct SaState {
 	int16_t* h[2];                              // [rows]: H of the previous / this column, swapped every column
@@ -36,25 +35,7 @@ struct SaState {
 	const uint8_t* q;                           // query codes in natural order (LDS copy or HBM)
 };
 
-__device__ __forceinline__ int sa_score(int qc, int tc) { return (qc == tc && tc < 4) ? 5 : -4; }
 __device__ __forceinline__ int16_t sa_store(int x) { return (int16_t)min(max(x, SA_NEG), 32767); }
-
-// exclusive max-scan of b over the workgroup (thread order); wtot: 4 words of LDS.  Contains one __syncthreads.
-__device__ __forceinline__ int sa_scan_excl(int b, int* wtot, int lane, int wave)
-{
-	int inc = b;
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) {
-		const int x = __shfl_up(inc, d);
-		if (lane >= d) inc = max(inc, x);
-	}
-	if (lane == 63) wtot[wave] = inc;
-	int ex = __shfl_up(inc, 1);
-	if (lane == 0) ex = SA_NEG32;
-	__syncthreads();
-	for (int w = 0; w < wave; w++) ex = max(ex, wtot[w]);
-	return ex;
-}
 
 // MODE 0: local (floored at 0), forward: rows 0 .. R - 1 are query rows q0 + r, columns 0 .. C - 1 target columns t0 + c.
 //         Result: res[0] = key of the end cell ((column - c_lo + 1) << 20 | (0xfffff - row), 0: none), res[1] = the unit attains
@@ -87,15 +68,15 @@ __device__ void sa_pass(const SaState& S, const uint8_t* tc, int t0, int q0, int
 		const int tcode = tc[t0 + DIR * c];
 		const int top = MODE == 0 ? 0 : (c == 0 ? 0 : SA_NEG);      // the diagonal neighbour of row 0
 		// first walk: what the thread's own rows hand down
-		int oa = SA_NEG32, ob = SA_NEG32;
+		int oa = NEG32, ob = NEG32;
 		if (first < last) {
 			int hd = first == 0 ? top : (int)cur[first - 1];
-			int f = SA_NEG32, hn = 0;
+			int f = NEG32, hn = 0;
 			for (int r = first; r < last; r++) {
 				const int hc = cur[r];
 				const int e = max((int)S.e[r] - 4, hc - 16);
 				if (r > first) f = max(f - 4, hn - 16);
-				int h = max(max(hd + sa_score(S.q[q0 + DIR * r], tcode), e), f);
+				int h = max(max(hd + col_score<1>(S.q[q0 + DIR * r], tcode), e), f);
 				if (MODE == 0) h = max(h, 0);
 				hd = hc; hn = h;
 			}
@@ -106,17 +87,17 @@ __device__ void sa_pass(const SaState& S, const uint8_t* tc, int t0, int q0, int
 			outa[t] = oa; outb[t] = ob;
 			__syncthreads();
 			const int nact = (R + rpt - 1) / rpt;
-			fin = SA_NEG32;
+			fin = NEG32;
 			for (int k = 0; k < nact; k++) {
 				if (k >= t) break;
 				const int ext = max(fin - 4 * rpt, outa[k]), opn = outb[k];
 				fin = max(ext, opn); fin_ext = ext >= opn;
 			}
 		} else {
-			const int ex = sa_scan_excl(max(oa, ob) + 4 * rpt * t, wtot, lane, wave);
-			fin = t == 0 ? SA_NEG32 : ex - 4 * rpt * (t - 1);
+			const int ex = scan_excl<SA_THREADS>(max(oa, ob) + 4 * rpt * t, wtot, lane, wave);
+			fin = t == 0 ? NEG32 : ex - 4 * rpt * (t - 1);
 		}
-		fin = max(fin, SA_NEG32);
+		fin = max(fin, NEG32);
 		// second walk: the recurrence itself
 		int hit = 0, hit_row = 0x7fffffff;
 		if (first < last) {
@@ -127,7 +108,7 @@ __device__ void sa_pass(const SaState& S, const uint8_t* tc, int t0, int q0, int
 				const int e = max(eo - 4, hc - 16);
 				int fext = fin_ext;
 				if (r > first) { fext = f - 4 >= hn - 16; f = max(f - 4, hn - 16); }
-				const int dg = hd + sa_score(S.q[q0 + DIR * r], tcode);
+				const int dg = hd + col_score<1>(S.q[q0 + DIR * r], tcode);
 				int h = max(max(dg, e), f);
 				if (MODE == 0) h = max(h, 0);
 				if (MODE == 0) {
@@ -226,8 +207,8 @@ __global__ void __launch_bounds__(SA_THREADS) k_site_path(SitePathLaunch a, int 
 	// traceback by one lane (the direction bytes of the workgroup are visible after the barrier that ended the pass)
 	int len = -1;
 	if (res[0] == P.value) {
-		uint32_t* cig = a.cigar + I.cig_off;
-		int r = R - 1, c = C - 1, state = 0, nops = 0, run_op = 0, run = 0;
+		CigarRun cig(a.cigar + I.cig_off, I.cig_cap);
+		int r = R - 1, c = C - 1, state = 0;
 		bool bad = false;
 		for (int step = 0; step < 2 * (R + C) + 4; step++) {
 			if (r < 0 || c < 0) { bad = !(r == -1 && c == -1 && state == 0); break; }
@@ -240,20 +221,14 @@ __global__ void __launch_bounds__(SA_THREADS) k_site_path(SitePathLaunch a, int 
 				op = 0; r--; c--;
 			} else if (state == 1) { op = 2; if (!(d & 4)) state = 0; c--; }
 			else { op = 1; if (!(d & 8)) state = 0; r--; }
-			if (run > 0 && op != run_op) {
-				if (nops >= I.cig_cap) { bad = true; break; }
-				cig[nops++] = ((uint32_t)run << 4) | (uint32_t)run_op; run = 0;
-			}
-			run_op = op; run++;
+			if (!cig.push(op)) { bad = true; break; }
 		}
 		if (!bad && !(r == -1 && c == -1 && state == 0)) bad = true;
-		if (!bad && run > 0) { if (nops >= I.cig_cap) bad = true; else cig[nops++] = ((uint32_t)run << 4) | (uint32_t)run_op; }
-		len = bad ? -1 : nops;
+		if (!bad && !cig.flush()) bad = true;
+		len = bad ? -1 : cig.nops;
 	}
 	a.cigar_len[k] = len;
 }
-
-static size_t sa_lds_bytes(int rows) { return (size_t)rows * 7 + 16; }
 
 hipError_t launch_site_ends(const SiteEndsLaunch& L, hipStream_t st)
 {
@@ -262,7 +237,7 @@ hipError_t launch_site_ends(const SiteEndsLaunch& L, hipStream_t st)
 	const bool lds = L.m <= SITE_ALIGN_LDS_ROWS;
 	if (!lds && !L.rows) return hipErrorInvalidValue;
 	const int lds_rows = lds ? ((L.m + 7) & ~7) : 0;
-	hipLaunchKernelGGL(k_site_ends, dim3((unsigned)L.nprob), dim3(SA_THREADS), lds ? sa_lds_bytes(lds_rows) : 0, st, L, lds_rows);
+	hipLaunchKernelGGL(k_site_ends, dim3((unsigned)L.nprob), dim3(SA_THREADS), lds ? lds_bytes(lds_rows) : 0, st, L, lds_rows);
 	return hipGetLastError();
 }
 

@@ -8,53 +8,17 @@
 // 2 * value + b (scores and gap costs doubled): b, the clip bit, is set on the positive cells of a first or last column that the flank
 // cut and travels through every maximum and every add; 0 means "no alignment" and carries no bit.
 //
-// The column step is the one of site_align.hip, passes (i) and (ii): one workgroup of 256 threads per problem (64 or 128 for queries of
-// at most that many rows), a thread owns a contiguous block of query rows, a column is a walk of the thread's rows, an exclusive
-// max-scan (__shfl_up and one LDS word per wave) of the vertical gap value the thread hands down, and a second walk that continues the
-// gap that enters from above.  The state of a row (H of the previous column, H of this column, E) is 16-bit, unsigned here, in LDS or,
-// for queries above TOUCH_LDS_ROWS rows, in HBM; the arithmetic is 32-bit.
+// The column step is colstep.h's, in doubled values: one workgroup of touch_threads(m) threads per problem, the 16-bit row state in
+// LDS or, for queries above TOUCH_LDS_ROWS rows, in HBM; the arithmetic is 32-bit.
 // k_var_encode assembles and encodes the windows from the record on the device; k_touch_reduce folds the problems of a variant into
 // nine words.  No atomics on global memory, plain vector stores only; every output word has one writer.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "kernels.h"
+#include "colstep.h"
 
 namespace fasim {
 
 constexpr int VT_THREADS = 256;
-constexpr int VT_NEG32 = -(1 << 28);           // "nothing handed down" in the scan
-
-struct VtState {
-	uint16_t* h[2];                             // [rows]: H of the previous / this column, swapped every column
-	uint16_t* e;                                // [rows]
-	const uint8_t* q;                           // query codes (LDS copy or HBM)
-};
-
-__device__ __forceinline__ int vt_score2(int qc, int tc) { return (qc == tc && tc < 4) ? 10 : -8; }
-__device__ __forceinline__ int vt_floor(int x) { return x < 2 ? 0 : x; }      // value 0: no alignment, no bit
-
-constexpr int VT_UNROLL = 4;                   // rows whose state is loaded ahead of their cells
-
-// exclusive max-scan of b over the NT threads of the workgroup (thread order); wtot: one word of LDS per wave.  Contains one
-// __syncthreads where the workgroup has more than one wave.
-template <int NT>
-__device__ __forceinline__ int vt_scan_excl(int b, int* wtot, int lane, int wave)
-{
-	int inc = b;
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) {
-		const int x = __shfl_up(inc, d);
-		if (lane >= d) inc = max(inc, x);
-	}
-	int ex = __shfl_up(inc, 1);
-	if (lane == 0) ex = VT_NEG32;
-	if (NT > 64) {
-		if (lane == 63) wtot[wave] = inc;
-		__syncthreads();
-		for (int w = 0; w < wave; w++) ex = max(ex, wtot[w]);
-	}
-	return ex;
-}
 
 // tcodes[tbase + c], c in [0, n): the code of window letter c (n - 1 - c for an odd encoding) under the problem's encoding
 __global__ void __launch_bounds__(VT_THREADS) k_var_encode(VarEncodeLaunch a)
@@ -76,11 +40,7 @@ __global__ void __launch_bounds__(VT_THREADS) k_var_encode(VarEncodeLaunch a)
 	}
 }
 
-// One workgroup of NT threads per problem (NT = 64 or 128 for queries of at most that many rows, else 256).  Thread t owns rows
-// [t * rpt, (t + 1) * rpt); the state of its i-th row lives at [i * NT + t], so that the lanes of a wave read and write neighbouring
-// 16-bit words (no LDS bank conflicts, coalesced in HBM).
-// IN_LDS: dynamic LDS of [lds_rows] x (3 x uint16 + 1 code byte), lds_rows = rpt * NT (every pointer of the column step is then an LDS
-// pointer at compile time: ds_read_u16, not a flat load); otherwise the row state lives in a.rows and the codes are read from HBM
+// One workgroup of NT threads per problem; rows, LDS and IN_LDS as ColState has them
 template <int NT, bool IN_LDS>
 __global__ void __launch_bounds__(NT) k_touch(TouchLaunch a, int lds_rows)
 {
@@ -90,26 +50,9 @@ __global__ void __launch_bounds__(NT) k_touch(TouchLaunch a, int lds_rows)
 	const int p = blockIdx.x;
 	if (p >= a.nprob) return;
 	const TouchProb P = a.probs[p];
-	const int m = a.m, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-	const int rpt = (m + NT - 1) / NT;
-	const int first = min(m, t * rpt), cnt = min(m, first + rpt) - first;
-	VtState S;
-	if (IN_LDS) {
-		uint16_t* b = reinterpret_cast<uint16_t*>(vt_lds);
-		S.h[0] = b; S.h[1] = b + lds_rows; S.e = b + 2 * lds_rows;
-		uint8_t* qc = reinterpret_cast<uint8_t*>(b + 3 * lds_rows);
-		for (int i = 0; i < rpt; i++) qc[i * NT + t] = i < cnt ? a.qcodes[first + i] : 4;
-		S.q = qc;
-	} else {
-		uint16_t* b = a.rows + (int64_t)p * 3 * rpt * NT;
-		S.h[0] = b; S.h[1] = b + rpt * NT; S.e = b + 2 * rpt * NT;
-		S.q = a.qcodes;
-	}
-	// Every thread walks rpt rows: the rows from m on (the last rows of the last threads) lie below every real row, so nothing of
-	// them reaches a real cell; they are only kept out of the maximum.  The code of the thread's i-th row: S.q[q0 + i * qstep]
-	const int qstep = IN_LDS ? NT : 1, q0 = IN_LDS ? t : min(first, m - 1), qlast = IN_LDS ? rpt - 1 : m - 1 - q0;
-	const int above = (rpt - 1) * NT + t - 1;                                      // the last row of the thread before this one
-	for (int i = 0; i < rpt; i++) { S.h[0][i * NT + t] = 0; S.e[i * NT + t] = 0; }
+	ColState<NT, IN_LDS> S;
+	S.open(vt_lds, lds_rows, a.rows, p, a.qcodes, a.m);
+	const int t = S.t, rpt = S.rpt;
 	if (t == 0) best_sh = 0;
 	__syncthreads();
 	const bool ok = P.n >= 1 && P.n <= TOUCH_MAX_COLS && P.v0 >= 0 && P.v0 < P.v1 && P.v1 <= P.n;      // (uniform)
@@ -121,46 +64,33 @@ __global__ void __launch_bounds__(NT) k_touch(TouchLaunch a, int lds_rows)
 		const int tcode = tc[c];
 		const bool cont = c >= P.v1;                 // behind the allele the diagonal only continues an alignment
 		const int mark = ((c == 0 && (P.edge & 1)) || (c == P.n - 1 && (P.edge & 2))) ? 1 : 0;
-		const int top = t > 0 ? (int)cur[above] : 0;      // H of the previous column in the row above the thread's first
+		const int top = t > 0 ? (int)cur[S.above] : 0;      // H of the previous column in the row above the thread's first
 		// first walk: E, and H with the vertical gaps that open in the thread's own rows (hl); what these rows hand to the row below
 		// them.  A gap never opens better from a cell that a gap reached (h - 32 < f - 8 where h = f), so the gap value of a row is
 		// max(f - 8, h - 32) whichever h, the final one or hl, stands in it.
 		const bool counts = c >= P.v0;
-		int out;
-		{
-			int hd = top, f = 0, hn = 0;
-			for (int i0 = 0; i0 < rpt; i0 += VT_UNROLL) {
-				int hc[VT_UNROLL], ein[VT_UNROLL], sc[VT_UNROLL];
+		int hd = top, f = 0, hn = 0;
+		for (int i0 = 0; i0 < rpt; i0 += COL_UNROLL) {
+			int hc[COL_UNROLL], ein[COL_UNROLL], sc[COL_UNROLL];
+			col_load<2>(S, cur, i0, tcode, hc, ein, sc);
 #pragma unroll
-				for (int k = 0; k < VT_UNROLL; k++) {      // (the loads of a short last group repeat its last row: no branch around a load)
-					const int i = min(i0 + k, rpt - 1);
-					hc[k] = cur[i * NT + t]; ein[k] = S.e[i * NT + t]; sc[k] = vt_score2(S.q[q0 + min(i, qlast) * qstep], tcode);
-				}
-#pragma unroll
-				for (int k = 0; k < VT_UNROLL; k++) if (i0 + k < rpt) {
-					const int e = vt_floor(max(ein[k] - 8, hc[k] - 32));
-					if (i0 + k > 0) f = vt_floor(max(f - 8, hn - 32));
-					int dg = hd + sc[k];
-					if (cont) dg = hd ? dg : 0;
-					int h = max(vt_floor(max(dg, e)), f);
-					if (mark && h) h |= 1;
-					if (counts && i0 + k < cnt) best = max(best, h);
-					nxt[(i0 + k) * NT + t] = (uint16_t)h; S.e[(i0 + k) * NT + t] = (uint16_t)e;
-					hd = hc[k]; hn = h;
-				}
+			for (int k = 0; k < COL_UNROLL; k++) if (i0 + k < rpt) {
+				int e, h = col_cell<2>(hd, hc[k], ein[k], sc[k], cont, i0 + k > 0, hn, f, e);
+				if (mark && h) h |= 1;
+				if (counts && i0 + k < S.cnt) best = max(best, h);
+				nxt[S.at(i0 + k)] = (uint16_t)h; S.e[S.at(i0 + k)] = (uint16_t)e;
+				hd = hc[k]; hn = h;
 			}
-			out = max(f - 8, hn - 32);
 		}
-		const int ex = vt_scan_excl<NT>(out + 8 * rpt * t, wtot, lane, wave);
-		const int fin = t == 0 ? 0 : vt_floor(max(ex, VT_NEG32) - 8 * rpt * (t - 1));
+		const int fin = col_gap_in<2>(S, col_gap<2>(f, hn), wtot);
 		// second walk, where a gap enters a thread of the wave from above: H = max(hl, the gap continued from fin)
 		if (__any(fin > 0)) {
-			int f = fin, hn = 0;
+			f = fin;
 			for (int i = 0; i < rpt; i++) {
-				if (i > 0) f = vt_floor(max(f - 8, hn - 32));
-				const int h = max((int)nxt[i * NT + t], f);      // (f carries the bit of the marked cell it comes from)
-				if (counts && i < cnt) best = max(best, h);
-				nxt[i * NT + t] = (uint16_t)h;
+				if (i > 0) f = col_floor<2>(col_gap<2>(f, hn));
+				const int h = max((int)nxt[S.at(i)], f);      // (f carries the bit of the marked cell it comes from)
+				if (counts && i < S.cnt) best = max(best, h);
+				nxt[S.at(i)] = (uint16_t)h;
 				hn = h;
 			}
 		}
@@ -196,8 +126,6 @@ __global__ void __launch_bounds__(VT_THREADS) k_touch_reduce(TouchReduceLaunch a
 	a.out[(int64_t)v * 9 + 8] = top & 1;
 }
 
-static size_t vt_lds_bytes(int rows) { return (size_t)rows * 7 + 16; }
-
 hipError_t launch_var_encode(const VarEncodeLaunch& L, hipStream_t st)
 {
 	if (L.nprob <= 0) return hipSuccess;
@@ -213,16 +141,7 @@ hipError_t launch_touch(const TouchLaunch& L, hipStream_t st)
 {
 	if (L.nprob <= 0) return hipSuccess;
 	if (L.m < 1 || !L.tcodes || !L.qcodes || !L.probs || !L.out) return hipErrorInvalidValue;
-	const bool lds = L.m <= TOUCH_LDS_ROWS;
-	if (!lds && !L.rows) return hipErrorInvalidValue;
-	const int nt = touch_threads(L.m);
-	const int lds_rows = lds ? touch_state_rows(L.m) : 0;
-	const dim3 grid((unsigned)L.nprob);
-	if (!lds) hipLaunchKernelGGL((k_touch<VT_THREADS, false>), grid, dim3(VT_THREADS), 0, st, L, 0);
-	else if (nt == 64) hipLaunchKernelGGL((k_touch<64, true>), grid, dim3(64), vt_lds_bytes(lds_rows), st, L, lds_rows);
-	else if (nt == 128) hipLaunchKernelGGL((k_touch<128, true>), grid, dim3(128), vt_lds_bytes(lds_rows), st, L, lds_rows);
-	else hipLaunchKernelGGL((k_touch<VT_THREADS, true>), grid, dim3(VT_THREADS), vt_lds_bytes(lds_rows), st, L, lds_rows);
-	return hipGetLastError();
+	return launch_cols(L, L.nprob, st, [](auto nt, auto lds) { return k_touch<decltype(nt)::value, decltype(lds)::value>; });
 }
 
 hipError_t launch_touch_reduce(const TouchReduceLaunch& L, hipStream_t st)
