@@ -363,6 +363,7 @@ int fasim_set_option(fasim_engine* E, const char* key, int32_t value)
 	else if (!strcmp(key, "numa_affinity")) E->opt_numa = value != 0;
 	else if (!strcmp(key, "band")) E->opt_band = value;                   // banded stage-3 forward pass: 0 off, 1 on (-1: default / FASIM_BAND)
 	else if (!strcmp(key, "dp_f16")) E->opt_dp_f16 = value;               // 1: packed-f16 k_scan and reverse pass (default), 0: the integer kernels (-1: default / FASIM_DP_F16)
+	else if (!strcmp(key, "q2_past_cut")) E->opt_q2_past_cut = value;     // 0: k_scan stops tracking Q2 taints behind a proven overflow cut (default), 1: tracks to the end of the unit (-1: default / FASIM_Q2_PAST_CUT)
 	else if (!strcmp(key, "site_short")) E->opt_site_short = value;       // 1: the hits of oligo sites end on k_site_ends_short (default), 0: on k_site_ends (-1: default / FASIM_SITE_SHORT)
 	else if (!strcmp(key, "sim_lds")) E->opt_sim_lds = value < 0 ? -1 : value != 0;   // -F re-sweeps: 0 the L2 variant, 1 the LDS variant where the state fits, -1 by the units in flight (tests)
 	else if (!strcmp(key, "site_chunk")) E->opt_site_chunk = value > 0 ? value : 0;   // problems per chunk of the site hits phase (0: the phase's own limit)

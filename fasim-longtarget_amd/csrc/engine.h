@@ -133,6 +133,7 @@ struct fasim_engine {
 	int ublk_units = 0, ublk_blocks = 0;         // units covered by `ublk` (0: none), blocks per (unit, tile)
 	int opt_band = -1;                           // option "band": 0 off, 1 on (-1 = default / environment FASIM_BAND)
 	int opt_dp_f16 = -1;                         // option "dp_f16": packed-f16 k_scan and reverse pass, 0 = the integer kernels (-1 = default / environment FASIM_DP_F16)
+	int opt_q2_past_cut = -1;                    // option "q2_past_cut": 1 = k_scan tracks Q2 taints to the end of every unit, 0 = up to a proven overflow cut (-1 = default / environment FASIM_Q2_PAST_CUT)
 	DevBuf unit_ovf;                             // [unit] != 0: the f16 k_scan saw a value outside its exact range
 	DevBuf track, track_phase, track_sat;        // fasim_scan_track only: k_track's slices, its per-segment bin phase and saturation flags of the batch
 	DevBuf track_peaks;                          // fasim_scan_records_track only: k_track's peak per slice and class
@@ -337,6 +338,14 @@ inline bool dp_f16_mode(const fasim_engine* E)
 {
 	static const int env = [] { const char* e = getenv("FASIM_DP_F16"); return e ? atoi(e) : 1; }();
 	return (E->opt_dp_f16 >= 0 ? E->opt_dp_f16 : env) != 0;
+}
+// option q2_past_cut / FASIM_Q2_PAST_CUT: 0 (default) = the k_scan passes of run_scan_v2 stop the Q2 taint tracking of a unit once a
+// clean block maximum >= 251 has proven its overflow cut (scan.hip); 1 = they track to the end of the unit.  The records, the
+// hazard units and every statistic are the same either way: only bit 0 of column maxima behind the cut differs.
+inline bool q2_past_cut_mode(const fasim_engine* E)
+{
+	static const int env = [] { const char* e = getenv("FASIM_Q2_PAST_CUT"); return e ? atoi(e) : 0; }();
+	return (E->opt_q2_past_cut >= 0 ? E->opt_q2_past_cut : env) != 0;
 }
 inline int band_mask(const fasim_engine* E)
 {

@@ -734,7 +734,7 @@ static int scan_set(fasim_engine* E, const char* const* rnas, const int32_t* rna
 		for (fasim_engine* w : ws) {
 			w->gate = (ws.size() > 1 && E->own_gate.cap > 0) ? &E->own_gate : nullptr;
 			w->scan_v1 = E->scan_v1; w->align_v1 = E->align_v1; w->striped_window = E->striped_window;
-			w->hz_chunks = E->hz_chunks; w->hz_snap = E->hz_snap; w->hz_target = E->hz_target; w->hz_hot_w = E->hz_hot_w; w->opt_band = E->opt_band; w->opt_dp_f16 = E->opt_dp_f16; w->opt_sim_lds = E->opt_sim_lds;
+			w->hz_chunks = E->hz_chunks; w->hz_snap = E->hz_snap; w->hz_target = E->hz_target; w->hz_hot_w = E->hz_hot_w; w->opt_band = E->opt_band; w->opt_dp_f16 = E->opt_dp_f16; w->opt_q2_past_cut = E->opt_q2_past_cut; w->opt_sim_lds = E->opt_sim_lds;
 			w->host_threads = std::max(1, E->host_threads_total / nworkers);
 			w->host_threads_share_total = E->host_threads_total; w->active_workers = &active_workers; w->sim_in_flight = &sim_active; w->scan_workers = (int)ws.size();
 			{

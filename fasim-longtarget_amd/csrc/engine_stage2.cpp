@@ -456,6 +456,8 @@ int run_scan_v2(fasim_engine* E, BatchCtx& C, const std::vector<char>& unit_need
 	L.counter = E->counter.as<uint32_t>(); L.m = E->m; L.colmax16 = E->colmax16.as<uint16_t>();
 	L.boundary = nullptr; L.unit_hz = nullptr;
 	L.coarse = 0;
+	// every pass launched from here feeds k_scan_post, k_max16 or a fold that drops bit 0: none reads a taint behind the overflow cut
+	L.q2_past_cut = q2_past_cut_mode(E) ? 1 : 0;
 	if (systolic_fits(E->m) && systolic_tiles(E->m) > 1) {
 		HIPOK(E->boundary.ensure((size_t)nu * B.tstride * sizeof(uint2)));
 		L.boundary = E->boundary.as<uint2>();

@@ -90,6 +90,10 @@ struct ScanLaunch {
 	// row maxima (fasim_scan_tfo_profile; ignored by the checkpoint variant): non-NULL selects the ROWS variant of the main pass,
 	// which leaves rowmax16[unit][16 * ceil(m/16)] = 2 * (maximum of the row over the unit's real columns) + taint bit
 	uint16_t* rowmax16 = nullptr;
+	// Q2 tracking past a unit's overflow cut: 1 = to the end of the unit; 0 = the plain main pass (neither checkpoint nor ROWS variant,
+	// ceil(m/16) >= 96) stops it 128 steps after a block of steps whose maximum is >= 251 and clean.  From there on only bit 0 of the
+	// column maxima can differ, at columns behind the cut, where k_scan_post does not read it
+	int32_t q2_past_cut = 1;
 };
 constexpr int SCAN_UBLK_STEPS = 64;       // pipeline steps per block of maxima
 inline int scan_ublk_blocks(int tstride) { return (tstride + 127 + SCAN_UBLK_STEPS - 1) / SCAN_UBLK_STEPS; }

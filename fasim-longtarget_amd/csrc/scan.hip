@@ -79,6 +79,9 @@ struct ScanArgs {
 	// ROWS variant only (fasim_scan_tfo_profile): [unit][rows_total] row maxima over the unit's real columns, as carried
 	// (2 * value + taint), folded per class by k_rowfold (rowfold.hip)
 	uint16_t* rowmax16;
+	// 0: Q2 tracking stops once a block maximum proves the unit's overflow cut (below); 1: tracking runs to the end of the unit.
+	// Only the plain main-pass builds (neither DUMP nor ROWS, RP >= 12) with long stripes (ceil(m/16) >= 96) look at it.
+	int32_t q2_past_cut;
 };
 
 // score of target code t against the r-th row of global virtual lane v (doubled: bit 0 is the taint bit)
@@ -110,6 +113,13 @@ __device__ __forceinline__ int scan_cell_score(const ScanArgs& a, int t, int v, 
 // be working on a drain column >= n (fed with code N), whose diagonal H[i-1][n-1] - 4 can exceed everything row i really holds,
 // so those steps run a second instantiation of the step body that masks such a half out of the accumulation.  The fill steps
 // need nothing (state and values are zero there).  The large RP no longer fit 128 VGPRs: they are built for 3 waves per SIMD.
+//
+// Q2 past the cut (plain main pass, q2_past_cut = 0).  k_scan_post reads the taint bit of a column maximum
+// only at columns <= cut, the first column whose (textbook) maximum reaches 251.  A block maximum that is >= 251 and clean is such
+// a value, and the reference's own: it sits in a column c' <= the block's last step, so cut <= c'.  Virtual lane 127 finishes
+// column c' at step c' + 127; from 128 steps after the block's last step on every lane works on a column > c', whose taints
+// nothing reads, and the steps leave the hazard branch out (fpo = 0, as when its superset test is false).  The decision is a
+// scalar one, taken where the block closes; a step pays a scalar compare for it.
 constexpr int scan_rows_waves(int RP, bool F16) { return RP >= (F16 ? 18 : 20) ? 3 : 4; }
 template <int RP, bool DUMP = false, bool F16 = false, bool ROWS = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ? 1 : (ROWS ? scan_rows_waves(RP, F16) : 4), DUMP ? 2 : 4))) k_scan(ScanArgs a)
@@ -129,6 +139,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 	const v2u actm = ln.actm, startm = ln.startm;
 	// the refined test needs F to die inside one stripe (F <= 234 decays by 4 per row)
 	const bool lvl2 = a.seg_len16 >= 96 && !a.coarse;
+	// the builds that may stop the tracking behind a proven cut, and whether this launch asks for it
+	// (long stripes take 12 rows per lane or more: ceil(m/16) >= 96 with 8 virtual lanes per stripe up to 192)
+	constexpr bool PAST_CUT = !DUMP && !ROWS && RP >= 12;
+	const bool cut_stops = PAST_CUT && lvl2 && a.q2_past_cut == 0;
 	const uint8_t* pl = prof + lane * PROF_LANE_STRIDE;
 
 	for (;;) {
@@ -158,6 +172,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 		int first_enter = 0x7fffffff;          // first step of this unit in which the hazard branch ran (wave-uniform)
 		v2u ubacc = (v2u){ 0, 0 };             // running maximum of the current block of steps (banded stage 3)
 		bool ovf = false;                      // F16: some block maximum of this unit reached 2048, the end of the exact range (wave-uniform)
+		// PAST_CUT: the row analysis runs in the steps < q2_until: none with short stripes, all until a clean block maximum has proven the cut (wave-uniform)
+		int q2_until = lvl2 ? 0x7fffffff : (int)0x80000000;
 		// DUMP only: the reference's OWN E.  Its lazy-F loop corrects H but not E (sswNew.cpp:355: "don't update E"), so E follows
 		// the H of the main pass, which only knows the F chain restarted at the top of each stripe (Fm).  The H values are the
 		// same either way (a gap pair in the order down-right scores what right-down scores), the E array is not, and a
@@ -254,10 +270,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 			if constexpr (DUMP) fmbot = to_int(fm);
 			// ---- Q2 hazard (q2_rows of systolic.h; values doubled, taint in bit 0) -------------------------------
 			fpo = 0;
-			if (lvl2) {
+			// (PAST_CUT: one scalar compare says both "long stripes" and "the cut is not proven yet")
+			const bool rows_tracked = PAST_CUT ? step < q2_until : lvl2;
+			if (rows_tracked) {
 				if (q2_rows<2, F16>(H, E, hbot, fpo, recv_f, recv_fp, startm, actm, act, (v2u){ 0xffff, 0xffff }))
 					first_enter = first_enter < step ? first_enter : step;
-			} else {
+			} else if (!PAST_CUT || !lvl2) {
 				// short stripes (ceil(m/16) < 96): a chain may cross several stripes, the row analysis does not hold; any
 				// F[b] >= 132 sends the unit to the stripe-faithful kernel
 				hzacc |= __builtin_elementwise_sub_sat(u_from(recv_f), ln.fthr2);
@@ -302,7 +320,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DUMP ?
 		};
 		auto close_block = [&]() __attribute__((always_inline)) {
 			if (F16) ovf |= __builtin_amdgcn_ballot_w64(ubacc[0] >= F16_2048 || ubacc[1] >= F16_2048) != 0ull;
-			if (a.ublk) a.ublk[(((size_t)unit * a.ntiles + a.tile) * a.ublk_blocks + (step / SCAN_UBLK_STEPS)) * 64 + lane] = ublk_pack(F16 ? u_from(hf_to_u16(to_int(ubacc))) : ubacc);
+			const v2u ub = F16 ? u_from(hf_to_u16(to_int(ubacc))) : ubacc;
+			if (a.ublk) a.ublk[(((size_t)unit * a.ntiles + a.tile) * a.ublk_blocks + (step / SCAN_UBLK_STEPS)) * 64 + lane] = ublk_pack(ub);
+			if constexpr (PAST_CUT) {
+				// a clean (even) maximum >= 2 * 251 in either half: the block ended with step + 1
+				if (cut_stops && q2_until == 0x7fffffff) {
+					constexpr unsigned CUT2 = 2 * (255 - BIAS);
+					if (__builtin_amdgcn_ballot_w64((ub[0] >= CUT2 && !(ub[0] & 1)) || (ub[1] >= CUT2 && !(ub[1] & 1))) != 0ull) q2_until = step + 1 + 128;
+				}
+			}
 			ubacc = (v2u){ 0, 0 };
 		};
 		// steps come in pairs (a block of SCAN_UBLK_STEPS steps ends after an odd step); the checkpoint pass takes no snapshots and
@@ -391,6 +417,7 @@ hipError_t launch_scan(const ScanLaunch& L, hipStream_t st)
 	if (f16 && !L.unit_ovf) return hipErrorInvalidValue;
 	a.unit_ovf = L.unit_ovf;
 	a.rowmax16 = L.dump_items ? nullptr : L.rowmax16;
+	a.q2_past_cut = L.q2_past_cut;
 	const bool rows = a.rowmax16 != nullptr;
 	if (a.ntiles > 1 && !a.boundary) return hipErrorInvalidValue;
 	// RP must be exactly ceil(segLen/vs): every virtual lane then owns RP or RP-1 rows.  One launch per tile of 128

@@ -305,7 +305,8 @@ __device__ __forceinline__ int f16_row_pair(int (&H)[RP], int (&E)[RP], int& hbo
 // Fp = F[b] - 4j is >= 132 and the H it has just corrected is < 144 (then vF >= 128 reads as negative, vH < 128 as positive).
 // From then on the rows of that stripe whose H is exactly the propagated value hold something smaller in the reference: those
 // cells get the taint bit.  fp = F crossing a stripe start, carried down the rows of the stripe; the row loop runs only in the
-// (rare) steps where some lane holds fp >= 132 or an armed chain.
+// steps where some lane holds fp >= 132 or an armed chain (4 - 5 % of k_scan's steps on random DNA, most of them behind a unit's
+// overflow cut, where k_scan does not call this any more: scan.hip, q2_past_cut).
 //
 // All values are carried x SC with the taint in bit SC / 2 (k_scan: SC = 2, bit 0; k_align_fwd<TAINT>: SC = 64, bit 5).  Scores
 // and gap costs are multiples of SC, so the bit rides through add / saturating subtract for free.

@@ -94,6 +94,11 @@ const char* fasim_last_error(const fasim_engine* e);   /* e may be NULL: last gl
  * the GPU's NUMA node (/sys/bus/pci/devices/<bus id>/local_cpulist); the caller's affinity is restored afterwards; no effect on a
  * single-node machine.
  * key "band" (1): the banded forward pass of stage 3 (csrc/band.hip); 0 = every window try runs over the whole query (env FASIM_BAND).
+ * key "q2_past_cut" (0): 0 = k_scan stops tracking the taints of the reference's signed lazy-F exit (Q2) in a unit 128 pipeline
+ * steps after a block of 64 steps whose maximum is >= 251 and clean: such a value proves the unit's overflow cut, and no taint behind
+ * the cut is ever read (csrc/scan.hip); 1 = it tracks to the end of every unit, as before the option existed;
+ * -1 restores the default (env FASIM_Q2_PAST_CUT).  Results, hazard units and every counter do not depend on it: only bit 0 of
+ * k_scan's column maxima behind the cut does (tests/test_gpu_q2_past_cut.py).
  * key "sim_lds" (-1): which storage variant of k_sim_resweep the -F rounds launch.  -1 = by the units in flight (the LDS variant
  * once at most 256 are left over all workers); 0 = always the variant that keeps the lines' states in L2; 1 = always the LDS variant
  * (the kernel still takes the L2 variant when the states of a unit exceed 150 KB).  No environment variable (for tests).
