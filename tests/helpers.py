@@ -1307,3 +1307,81 @@ def sim_edge_census(orc, build_dir, tmp_dir, name, c_length=10):
             row["partial_sweeps"] += sweeps and len(nodes) < SIM_K
         rows.append(row)
     return rows
+
+
+# ---- the triplex scan off its default parameters (test_scan_params_cpu.py, test_gpu_scan_params.py) -----------------------------
+# With the defaults penaltyT = -1000 takes 1 000 of stability from every alignment that shows two T in a row, and minStability = 1,
+# minIdentity = 60 and ntMin = 20 then drop it: most of what stage 3 computes never becomes a record.  "Open" filters keep them all.
+SCAN_OPEN = ("-pt", "0", "-pc", "0", "-S", "-100000", "-i", "0", "-ni", "1")
+SCAN_Q2_SEGMENTS = 12          # open_q2 scans the first 12 of q2cat.fa's 19 segments: the whole file's scan is too large to commit
+# name -> (query, DNA file, options of `scan`, which are the reference CLI's); ref_probe `scan -detail 0` of each is
+# tests/golden/params_<name>.scan.gz (`make_golden.py params`)
+SCAN_PARAM_PINNED = {
+    "open": ("H19", "planted40k.fa", SCAN_OPEN),
+    "open_meg3": ("MEG3", "planted40k.fa", SCAN_OPEN),
+    "open_demo": ("H19", "testDNA.fa", SCAN_OPEN),
+    "open_q2": ("H19", "q2cat.fa", SCAN_OPEN + ("-o", "0")),
+    "pen": ("H19", "planted40k.fa", ("-pt", "-3", "-pc", "-2", "-S", "-50")),
+    # -S -50 drops nothing (a mean stability is never below the penalties), so in `pen` the penalties only show in the records'
+    # stability; with -S 1 they also decide which alignments become records.  The engine filters twice, on the numbers-only
+    # conversion before it builds a record's strings and on the record itself: only a stability that the first conversion puts
+    # too low loses a record, so each penalty is once the milder of the two
+    "pen_stab": ("H19", "planted40k.fa", ("-pt", "-3", "-pc", "-2", "-S", "1", "-i", "0", "-ni", "1")),
+    "pen_stab_swapped": ("H19", "planted40k.fa", ("-pt", "-2", "-pc", "-3", "-S", "1", "-i", "0", "-ni", "1")),
+    "ntmax": ("H19", "planted40k.fa", ("-na", "40", "-ni", "30")),
+    "thresholds": ("H19", "planted40k.fa", ("-i", "70", "-S", "2")),
+    "cut5001": ("H19", "planted40k.fa", SCAN_OPEN + ("-c", "5001", "-o", "100")),
+    "cut12345": ("H19", "planted40k.fa", SCAN_OPEN + ("-c", "12345", "-o", "2000")),
+    "cut20000": ("H19", "planted40k.fa", SCAN_OPEN + ("-c", "20000", "-o", "0")),
+    "cut40000": ("H19", "planted40k.fa", SCAN_OPEN + ("-c", "40000", "-o", "100")),
+}
+SCAN_THRESHOLD_CASES = ("thresholds",)
+SCAN_CUT_CASES = ("cut5001", "cut12345", "cut20000", "cut40000")
+# the two smallest cut lengths take their expectation from the live oracle (3 312 and 480 units)
+SCAN_PARAM_LIVE_CUTS = {
+    "cut64": ("MEG3", "testDNA.fa", SCAN_OPEN + ("-c", "64", "-o", "0")),
+    "cut777": ("H19", "testDNA.fa", SCAN_OPEN + ("-c", "777", "-o", "333")),
+}
+# (rule, strand) -> number of encodings enabled
+SCAN_RULE_STRAND = {(6, 1): 2, (7, 0): 2, (18, -1): 2, (1, -1): 2, (3, 0): 4}
+SCAN_NO_ENCODINGS = ((7, 1), (19, 0))
+_SCAN_OPTION_FIELDS = {"-r": "rule", "-t": "strand", "-c": "cutLength", "-o": "overlapLength", "-i": "minIdentity", "-S": "minStability",
+                       "-ni": "ntMin", "-na": "ntMax", "-pc": "penaltyC", "-pt": "penaltyT", "-ds": "cDistance", "-lg": "cLength"}
+
+
+def scan_option_fields(options):
+    """Options of the reference CLI as fields of the parameter structure: {'penaltyT': 0, ...}."""
+    assert len(options) % 2 == 0
+    return {_SCAN_OPTION_FIELDS[k]: int(v) for k, v in zip(options[::2], options[1::2])}
+
+
+def scan_param_dna(golden_dir, name, dna_file):
+    """(header, DNA) of a case: the fixture's record, for open_q2 its first SCAN_Q2_SEGMENTS whole segments."""
+    import synth
+    hdr, dna = synth.read_fasta(os.path.join(golden_dir, dna_file))
+    if name == "open_q2":
+        dna = dna[:SCAN_Q2_SEGMENTS * 5000]
+        hdr = "syn|chrQ|1-%d" % len(dna)
+    return hdr, dna
+
+
+def scan_param_files(golden_dir, tmp_dir, name, case):
+    """(query path, DNA path) of a case for the oracle's command line; a shortened record is written under tmp_dir."""
+    import synth
+    query, dna_file, _ = case
+    dna_fa = os.path.join(golden_dir, dna_file)
+    if name == "open_q2":
+        hdr, dna = scan_param_dna(golden_dir, name, dna_file)
+        dna_fa = os.path.join(str(tmp_dir), "q2cat_%d.fa" % SCAN_Q2_SEGMENTS)
+        synth.write_fasta(dna_fa, hdr, dna)
+    return os.path.join(golden_dir, query + ".fa"), dna_fa
+
+
+_SCAN_PARAM_FIXTURES = {}
+
+
+def scan_param_fixture(golden_dir, name):
+    """(meta, units) of tests/golden/params_<name>.scan.gz, parsed once and left unchanged."""
+    if name not in _SCAN_PARAM_FIXTURES:
+        _SCAN_PARAM_FIXTURES[name] = parse_scan(gunzip(os.path.join(golden_dir, f"params_{name}.scan.gz")))
+    return _SCAN_PARAM_FIXTURES[name]
