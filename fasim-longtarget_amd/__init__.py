@@ -76,7 +76,8 @@ class ScanStats(C.Structure):
                 ("band_cells", C.c_int64), ("rev_bound_passes", C.c_int64), ("striped_window_probs", C.c_int64),
                 ("striped_window_ms", C.c_double), ("dp_f16_reruns", C.c_int64),
                 ("finish_lds16", C.c_int64), ("finish_lds64", C.c_int64), ("finish_glob16k", C.c_int64), ("finish_glob1m", C.c_int64),
-                ("sim_resweep_lds", C.c_int64), ("sim_resweep_l2", C.c_int64), ("sim_suspended", C.c_int64), ("sim_handover", C.c_int64)]
+                ("sim_resweep_lds", C.c_int64), ("sim_resweep_l2", C.c_int64), ("sim_suspended", C.c_int64), ("sim_handover", C.c_int64),
+                ("finish_skipped", C.c_int64), ("finish_skip_violations", C.c_int64)]
 
 
 class SimNode(C.Structure):

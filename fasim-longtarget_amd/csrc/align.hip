@@ -18,6 +18,10 @@
 //                   the SMALLEST such row), so the reverse pass only has to follow paths that start in that
 //                   corner: a pruned origin-anchored DP over a few hundred cells instead of (read_end+1) x
 //                   (ref_end+1).  See DESIGN.md "reverse pass" for the argument.
+//   k_finish_rev, k_finish_compact, k_finish_trace
+//                   the first finish tier of the scan, split behind the reverse pass: alignments whose record the
+//                   stability filter is certain to drop (doomed.h) end there with their ends and score, the
+//                   others are listed and traced.
 //
 // Windows in which the reference's signed lazy-F exit (Q2) could fire are flagged and re-run by the
 // stripe-faithful kernel (kernels.hip).
@@ -602,18 +606,28 @@ __device__ int reverse_pass_lds(const uint8_t* __restrict__ tw, const uint8_t* _
 	int lo = 0, hi = 0;
 	A.set(0, g0, GL_NEG);
 	// (a vertical gap straight out of the corner cell scores 5 - 16 < 0: column 0 holds row 0 only)
+	// The cells of a column form one dependent chain per thread, so what a cell reads from memory is fetched one cell ahead: the
+	// ring entry of row i + 1 (still the previous column's: this column has written rows lo .. i only, and i + 1 - lo < FL_RING),
+	// the query code of row i + 1 and the target code of the next column.
+	int tnext = C > 1 ? tw[ref_end - 1] : 0;
 	for (int j = 1; j < C; j++) {
-		const int tcode = tw[ref_end - j];
+		const int tcode = tnext;
+		if (j + 1 < C) tnext = tw[ref_end - j - 1];
 		int F = GL_NEG, diag = GL_NEG, nlo = -1, nhi = -1;
 		const int colrest = C - 1 - j;
 		if (hi - lo + 2 >= FL_RING) return 2;             // band wider than the ring: finish in global memory
+		uint32_t wnext = A.base[(lo & (FL_RING - 1)) * 64];
+		int qnext = q[read_end - lo];
 		for (int i = lo; i < R; i++) {
 			const bool in = (i <= hi);
 			const int k = i & (FL_RING - 1);
-			const int gp = in ? A.lo(k) : GL_NEG;
-			const int ep = in ? A.hi(k) : GL_NEG;
+			const uint32_t w = wnext;
+			const int qcode = qnext;
+			if (i + 1 < R) { wnext = A.base[((i + 1) & (FL_RING - 1)) * 64]; qnext = q[read_end - i - 1]; }
+			const int gp = in ? (int)(int16_t)(w & 0xffffu) : GL_NEG;
+			const int ep = in ? (int)(int16_t)(w >> 16) : GL_NEG;
 			int e = max(ep - GAP_EXT, gp - GAP_OPEN);
-			int g = diag > GL_NEG / 2 ? diag + swsc(q[read_end - i], tcode) : GL_NEG;
+			int g = diag > GL_NEG / 2 ? diag + swsc(qcode, tcode) : GL_NEG;
 			g = max(g, max(e, F));
 			const int rest = min(R - 1 - i, colrest);
 			if (g <= 0 || g + 5 * rest < S) g = GL_NEG;
@@ -633,39 +647,32 @@ __device__ int reverse_pass_lds(const uint8_t* __restrict__ tw, const uint8_t* _
 	return 1;
 }
 
-template <int FL_WORDS, int FL_CELLS>
-__global__ void __launch_bounds__(64) k_finish_lds(const uint8_t* __restrict__ tcodes, const uint8_t* __restrict__ qcodes,
-	const FwdProb* __restrict__ probs, const FwdOut* __restrict__ fwd, const int32_t* __restrict__ order, int32_t nprob,
-	uint8_t* __restrict__ dirs, AlignOutDev* __restrict__ out, uint32_t* __restrict__ cigar_pool, uint32_t pool_cap,
-	uint32_t* __restrict__ pool_count)
+// The rule of doomed.h for an alignment whose reverse pass on this kernel has just given its begin.  Never true for flags != 0 (begin
+// from the exact reverse pass, taints), scores >= 148, segments with letters that complement() drops under a strand-1 encoding, spans
+// that leave the segment.
+__device__ __forceinline__ bool finish_doomed(const FwdProb& pb, const FwdOut& fo, int ref_begin, int read_begin, const FinishSkip& fs)
 {
-	constexpr int FL_RING = FL_WORDS, FL_W = FL_WORDS / 2;      // ring of the reverse pass; max band array width (2*band+3), h_c behind h_b/e_b
-	__shared__ uint32_t lds[FL_WORDS * 64];
-	const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-	if (gid >= nprob) return;
-	const int pi = order ? order[gid] : gid;              // alignments are processed in an order that groups similar sizes
-	LdsArena A; A.base = lds + threadIdx.x;
-	uint8_t* dir = dirs + (int64_t)blockIdx.x * (64 * FL_CELLS) + threadIdx.x;    // cell c at dir[c * 64]
-	const FwdProb pb = probs[pi];
-	const FwdOut fo = fwd[pi];
-	AlignOutDev* o = out + pi;
-	o->sw_score = 0; o->ref_begin = 0; o->ref_end = fo.ref_end; o->query_begin = 0; o->query_end = fo.read_end; o->cigar_len = 0;
-	o->cigar_off = 0;
-	if (fo.flags & 1) { o->status = 10; return; }
-	if (fo.score <= 0 || fo.ref_end < 0) { o->status = 0; return; }
-	const uint8_t* tw = tcodes + pb.tbase;
-	int ref_begin = fo.ref_begin, read_begin = fo.read_begin;
-	if (!(fo.flags & 2)) {
-		// 148..250: an F >= 132 is possible in the reverse pass of the 8-bit kernel; >= 251 runs on the reference's
-		// 16-bit kernels, whose compare is not affected
-		if (fo.score >= 148 && fo.score < 255 - BIAS) { o->status = 11; return; }
-		const int r = reverse_pass_lds<FL_RING>(tw, qcodes, fo.score, fo.ref_end, fo.read_end, A, &ref_begin, &read_begin);
-		if (r) { o->status = r == 2 ? 2 : 11; return; }
-	}
-	o->ref_begin = ref_begin; o->query_begin = read_begin;
+	if (fo.flags != 0 || fo.score >= 148) return false;
+	const int refspan = fo.ref_end - ref_begin + 1, readspan = fo.read_end - read_begin + 1;
+	if (!length_known(fs.dp.ntMin, refspan, readspan) || !stability_doomed(fs.dp, refspan, readspan, true)) return false;
+	const int64_t unit = pb.tbase / fs.tstride;
+	const int t0 = (int)(pb.tbase - unit * fs.tstride);
+	const int seg = (int)(unit / fs.nenc), enc = fs.enc_ids[unit - (int64_t)seg * fs.nenc];
+	if (!fs.seg_clean[seg] && enc_strand(enc) == 1) return false;
+	const int n = fs.seg_len[seg], q0 = t0 + ref_begin, q1 = t0 + fo.ref_end;
+	if (q0 < 0 || q1 >= n) return false;
+	return span_has_tt(fs.dna + fs.seg_start[seg], n, enc, q0, q1);
+}
+
+// banded_sw + traceback of one alignment whose begin is known: band arrays in the arena, direction bytes at dir[cell * 64]
+template <int FL_W, int FL_CELLS>
+__device__ __forceinline__ void finish_trace_lds(const LdsArena& A, uint8_t* __restrict__ dir, const uint8_t* __restrict__ tw,
+	const uint8_t* __restrict__ qcodes, int ref_end, int read_end, int score, int ref_begin, int read_begin, AlignOutDev* __restrict__ o,
+	uint32_t* __restrict__ cigar_pool, uint32_t pool_cap, uint32_t* __restrict__ pool_count)
+{
 	const uint8_t* ref = tw + ref_begin;
 	const uint8_t* read = qcodes + read_begin;
-	const int refLen = fo.ref_end - ref_begin + 1, readLen = fo.read_end - read_begin + 1, score = fo.score;
+	const int refLen = ref_end - ref_begin + 1, readLen = read_end - read_begin + 1;
 	int band = (refLen > readLen ? refLen - readLen : readLen - refLen) + 1;
 	int maxv = 0, width = 0, width_d = 0;
 	do {
@@ -753,6 +760,153 @@ __global__ void __launch_bounds__(64) k_finish_lds(const uint8_t* __restrict__ t
 	o->cigar_len = l;
 }
 
+template <int FL_WORDS, int FL_CELLS>
+__global__ void __launch_bounds__(64) k_finish_lds(const uint8_t* __restrict__ tcodes, const uint8_t* __restrict__ qcodes,
+	const FwdProb* __restrict__ probs, const FwdOut* __restrict__ fwd, const int32_t* __restrict__ order, int32_t nprob,
+	uint8_t* __restrict__ dirs, AlignOutDev* __restrict__ out, uint32_t* __restrict__ cigar_pool, uint32_t pool_cap,
+	uint32_t* __restrict__ pool_count, int32_t skip, FinishSkip fs, uint8_t* __restrict__ marks)
+{
+	constexpr int FL_RING = FL_WORDS, FL_W = FL_WORDS / 2;      // ring of the reverse pass; max band array width (2*band+3), h_c behind h_b/e_b
+	__shared__ uint32_t lds[FL_WORDS * 64];
+	const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+	if (gid >= nprob) return;
+	const int pi = order ? order[gid] : gid;              // alignments are processed in an order that groups similar sizes
+	LdsArena A; A.base = lds + threadIdx.x;
+	uint8_t* dir = dirs + (int64_t)blockIdx.x * (64 * FL_CELLS) + threadIdx.x;    // cell c at dir[c * 64]
+	const FwdProb pb = probs[pi];
+	const FwdOut fo = fwd[pi];
+	AlignOutDev* o = out + pi;
+	o->sw_score = 0; o->ref_begin = 0; o->ref_end = fo.ref_end; o->query_begin = 0; o->query_end = fo.read_end; o->cigar_len = 0;
+	o->cigar_off = 0;
+	if (fo.flags & 1) { o->status = 10; return; }
+	if (fo.score <= 0 || fo.ref_end < 0) { o->status = 0; return; }
+	const uint8_t* tw = tcodes + pb.tbase;
+	int ref_begin = fo.ref_begin, read_begin = fo.read_begin;
+	if (!(fo.flags & 2)) {
+		// 148..250: an F >= 132 is possible in the reverse pass of the 8-bit kernel; >= 251 runs on the reference's
+		// 16-bit kernels, whose compare is not affected
+		if (fo.score >= 148 && fo.score < 255 - BIAS) { o->status = 11; return; }
+		const int r = reverse_pass_lds<FL_RING>(tw, qcodes, fo.score, fo.ref_end, fo.read_end, A, &ref_begin, &read_begin);
+		if (r) { o->status = r == 2 ? 2 : 11; return; }
+	}
+	o->ref_begin = ref_begin; o->query_begin = read_begin;
+	if (skip && finish_doomed(pb, fo, ref_begin, read_begin, fs)) {      // (skip = 0: fs is not read)
+		if (fs.check) marks[pi] = 1;
+		else { o->sw_score = fo.score; o->status = 5; return; }
+	}
+	finish_trace_lds<FL_W, FL_CELLS>(A, dir, tw, qcodes, fo.ref_end, fo.read_end, fo.score, ref_begin, read_begin, o, cigar_pool, pool_cap, pool_count);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The split tier 1 (option finish_skip): k_finish_rev = the early statuses and the reverse pass of k_finish_lds<64, 2048>, then
+// the rule of doomed.h on the span it found.  An alignment that is certain to fail the stability filter ends here with status 5,
+// its ends and its score, and no CIGAR.  Every other one that got its begin sets its bit in the wave's ballot mask;
+// k_finish_compact turns the masks into the list of those alignments in the order of order[] (score-grouped: a wave's 64 DPs stay
+// of similar length), and k_finish_trace, launched for all nprob, runs banded_sw + traceback over the list's device count.
+// The 64 KB tier (k_finish_lds<256, 16384> over what comes back with status 2) takes the same test as a per-thread exit behind its own
+// reverse pass; the global-scratch tiers trace everything they get.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool finish_rev_one(const uint8_t* __restrict__ tcodes, const uint8_t* __restrict__ qcodes, const FwdProb& pb,
+	const FwdOut& fo, const LdsArena& A, AlignOutDev* __restrict__ o, const FinishSkip& fs, uint8_t* __restrict__ mark)
+{
+	o->sw_score = 0; o->ref_begin = 0; o->ref_end = fo.ref_end; o->query_begin = 0; o->query_end = fo.read_end; o->cigar_len = 0;
+	o->cigar_off = 0;
+	if (fo.flags & 1) { o->status = 10; return false; }
+	if (fo.score <= 0 || fo.ref_end < 0) { o->status = 0; return false; }
+	const uint8_t* tw = tcodes + pb.tbase;
+	int ref_begin = fo.ref_begin, read_begin = fo.read_begin;
+	if (!(fo.flags & 2)) {
+		if (fo.score >= 148 && fo.score < 255 - BIAS) { o->status = 11; return false; }
+		const int r = reverse_pass_lds<64>(tw, qcodes, fo.score, fo.ref_end, fo.read_end, A, &ref_begin, &read_begin);
+		if (r) { o->status = r == 2 ? 2 : 11; return false; }
+	}
+	o->ref_begin = ref_begin; o->query_begin = read_begin;
+	o->status = 2;                    // (stands only if k_finish_trace never reaches it: handed on like an alignment that does not fit)
+	if (!finish_doomed(pb, fo, ref_begin, read_begin, fs)) return true;
+	if (fs.check) { *mark = 1; return true; }
+	o->sw_score = fo.score; o->status = 5;
+	return false;
+}
+
+__global__ void __launch_bounds__(64) k_finish_rev(const uint8_t* __restrict__ tcodes, const uint8_t* __restrict__ qcodes,
+	const FwdProb* __restrict__ probs, const FwdOut* __restrict__ fwd, const int32_t* __restrict__ order, int32_t nprob,
+	AlignOutDev* __restrict__ out, FinishSkip fs, uint64_t* __restrict__ masks, uint8_t* __restrict__ marks)
+{
+	__shared__ uint32_t lds[64 * 64];
+	const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+	bool trace = false;
+	if (gid < nprob) {
+		const int pi = order[gid];
+		LdsArena A; A.base = lds + threadIdx.x;
+		const FwdProb pb = probs[pi];
+		const FwdOut fo = fwd[pi];
+		trace = finish_rev_one(tcodes, qcodes, pb, fo, A, out + pi, fs, marks + pi);
+	}
+	const uint64_t m = __ballot(trace);
+	if (threadIdx.x == 0) masks[blockIdx.x] = m;
+}
+
+// one workgroup: exclusive scan of the masks' bit counts, then list[] = order[] of the set bits, in order; *count = their number
+__global__ void __launch_bounds__(1024) k_finish_compact(const uint64_t* __restrict__ masks, int32_t nwave, const int32_t* __restrict__ order,
+	int32_t* __restrict__ list, uint32_t* __restrict__ count)
+{
+	__shared__ uint32_t sum[1024];
+	const int t = threadIdx.x;
+	const int per = (nwave + 1023) / 1024;
+	const int w0 = min(nwave, t * per), w1 = min(nwave, w0 + per);
+	uint32_t mine = 0;
+	for (int w = w0; w < w1; w++) mine += (uint32_t)__popcll(masks[w]);
+	sum[t] = mine;
+	__syncthreads();
+	for (int d = 1; d < 1024; d <<= 1) {
+		const uint32_t add = t >= d ? sum[t - d] : 0u;
+		__syncthreads();
+		sum[t] += add;
+		__syncthreads();
+	}
+	uint32_t at = sum[t] - mine;
+	if (t == 1023) *count = sum[t];
+	for (int w = w0; w < w1; w++) {
+		uint64_t m = masks[w];
+		while (m) { const int b = __ffsll((long long)m) - 1; m &= m - 1; list[at++] = order[w * 64 + b]; }
+	}
+}
+
+__global__ void __launch_bounds__(64) k_finish_trace(const uint8_t* __restrict__ tcodes, const uint8_t* __restrict__ qcodes,
+	const FwdProb* __restrict__ probs, const FwdOut* __restrict__ fwd, const int32_t* __restrict__ list, const uint32_t* __restrict__ count,
+	uint8_t* __restrict__ dirs, AlignOutDev* __restrict__ out, uint32_t* __restrict__ cigar_pool, uint32_t pool_cap,
+	uint32_t* __restrict__ pool_count)
+{
+	__shared__ uint32_t lds[64 * 64];
+	const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+	if (gid >= *count) return;
+	const int pi = list[gid];
+	LdsArena A; A.base = lds + threadIdx.x;
+	uint8_t* dir = dirs + (int64_t)blockIdx.x * (64 * 2048) + threadIdx.x;
+	const FwdProb pb = probs[pi];
+	const FwdOut fo = fwd[pi];
+	AlignOutDev* o = out + pi;
+	finish_trace_lds<32, 2048>(A, dir, tcodes + pb.tbase, qcodes, fo.ref_end, fo.read_end, fo.score, o->ref_begin, o->query_begin, o,
+		cigar_pool, pool_cap, pool_count);
+}
+
+// `masks`: ceil(nprob/64) words; `list`: nprob entries; `marks` (fs.check only): nprob bytes; `dirs` as for launch_finish
+hipError_t launch_finish_split(const uint8_t* tcodes, const uint8_t* qcodes, const FwdProb* probs, const FwdOut* fwd, const int32_t* order,
+	int32_t nprob, uint8_t* dirs, AlignOutDev* out, uint32_t* cigar_pool, uint32_t pool_cap, uint32_t* pool_count, const FinishSkip& fs,
+	uint64_t* masks, int32_t* list, uint32_t* list_count, uint8_t* marks, hipStream_t st)
+{
+	if (nprob <= 0) return hipSuccess;
+	hipError_t err = hipMemsetAsync(pool_count, 0, sizeof(uint32_t), st);
+	if (err == hipSuccess && fs.check) err = hipMemsetAsync(marks, 0, (size_t)nprob, st);
+	if (err != hipSuccess) return err;
+	const int nwave = (nprob + 63) / 64;
+	hipLaunchKernelGGL(k_finish_rev, dim3(nwave), dim3(64), 0, st, tcodes, qcodes, probs, fwd, order, nprob, out, fs, masks, marks);
+	hipLaunchKernelGGL(k_finish_compact, dim3(1), dim3(1024), 0, st, masks, nwave, order, list, list_count);
+	hipLaunchKernelGGL(k_finish_trace, dim3(nwave), dim3(64), 0, st, tcodes, qcodes, probs, fwd, list, list_count, dirs, out, cigar_pool,
+		pool_cap, pool_count);
+	return hipGetLastError();
+}
+
 hipError_t launch_finish(const uint8_t* tcodes, const uint8_t* qcodes, const FwdProb* probs, const FwdOut* fwd, const int32_t* order,
 	int32_t nprob, uint8_t* dirs, AlignOutDev* out, uint32_t* cigar_pool, uint32_t pool_cap, uint32_t* pool_count, hipStream_t st)
 {
@@ -762,20 +916,21 @@ hipError_t launch_finish(const uint8_t* tcodes, const uint8_t* qcodes, const Fwd
 	hipError_t err = hipMemsetAsync(pool_count, 0, sizeof(uint32_t), st);
 	if (err != hipSuccess) return err;
 	hipLaunchKernelGGL((k_finish_lds<64, 2048>), dim3((nprob + 63) / 64), dim3(64), 0, st, tcodes, qcodes, probs, fwd, order, nprob, dirs, out,
-		cigar_pool, pool_cap, pool_count);
+		cigar_pool, pool_cap, pool_count, 0, FinishSkip(), nullptr);
 	return hipGetLastError();
 }
 
 // the same kernel with four times the LDS per alignment for the listed ones (results to out[idx_list[k]], cigars appended to the
 // same pool); `dirs` must hold ceil(nlist/64) * 64 * 16384 bytes
 hipError_t launch_finish_mid(const uint8_t* tcodes, const uint8_t* qcodes, const FwdProb* probs, const FwdOut* fwd, const int32_t* idx_list,
-	int32_t nlist, uint8_t* dirs, AlignOutDev* out, uint32_t* cigar_pool, uint32_t pool_cap, uint32_t* pool_count, hipStream_t st)
+	int32_t nlist, uint8_t* dirs, AlignOutDev* out, uint32_t* cigar_pool, uint32_t pool_cap, uint32_t* pool_count, hipStream_t st,
+	const FinishSkip* fs, uint8_t* marks)
 {
 	if (nlist <= 0) return hipSuccess;
 	static bool attr_set = false;                   // (benign race: the call is idempotent)
 	if (!attr_set) { (void)hipFuncSetAttribute((const void*)k_finish_lds<256, 16384>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024); attr_set = true; }
 	hipLaunchKernelGGL((k_finish_lds<256, 16384>), dim3((nlist + 63) / 64), dim3(64), 0, st, tcodes, qcodes, probs, fwd, idx_list, nlist, dirs, out,
-		cigar_pool, pool_cap, pool_count);
+		cigar_pool, pool_cap, pool_count, fs ? 1 : 0, fs ? *fs : FinishSkip(), marks);
 	return hipGetLastError();
 }
 

@@ -338,7 +338,7 @@ void fasim_engine_destroy(fasim_engine* e)
 		&e->bprev, &e->lane_ub, &e->fzones, &e->fubslot, &e->bdec, &e->btab, &e->swin, &e->unit_ovf, &e->track, &e->track_phase, &e->track_sat, &e->track_peaks, &e->sites_counts, &e->sites_offsets, &e->sites_runs, &e->sites_sat, &e->sa_q, &e->sa_tcodes, &e->sa_probs, &e->sa_ends, &e->sa_rows, &e->sa_items, &e->sa_dirs, &e->sa_cigar, &e->sa_ciglen,
 		&e->rowmax16, &e->row_out, &e->row_gfirst, &e->row_sat, &e->oligo_q, &e->hist, &e->hist_zone, &e->hist_zones, &e->hist_sat,
 		&e->vr_q, &e->vr_dna, &e->vr_alt, &e->vr_wins, &e->vr_probs, &e->vr_tcodes, &e->vr_rows, &e->vr_touch, &e->vr_out,
-		&e->vr_items, &e->vr_dirs, &e->vr_cigar, &e->vr_paths };
+		&e->vr_items, &e->vr_dirs, &e->vr_cigar, &e->vr_paths, &e->fmask, &e->flist, &e->fmarks, &e->seg_clean };
 	for (auto& t : e->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
 	for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
 	for (DevBuf* b : bufs) b->release();
@@ -364,6 +364,7 @@ int fasim_set_option(fasim_engine* E, const char* key, int32_t value)
 	else if (!strcmp(key, "band")) E->opt_band = value;                   // banded stage-3 forward pass: 0 off, 1 on (-1: default / FASIM_BAND)
 	else if (!strcmp(key, "dp_f16")) E->opt_dp_f16 = value;               // 1: packed-f16 k_scan and reverse pass (default), 0: the integer kernels (-1: default / FASIM_DP_F16)
 	else if (!strcmp(key, "q2_past_cut")) E->opt_q2_past_cut = value;     // 0: k_scan stops tracking Q2 taints behind a proven overflow cut (default), 1: tracks to the end of the unit (-1: default / FASIM_Q2_PAST_CUT)
+	else if (!strcmp(key, "finish_skip")) E->opt_finish_skip = value;     // 1: alignments the stability filter must drop get no CIGAR (default), 0: k_finish_lds traces all, 2: trace all and check the rule (-1: default / FASIM_FINISH_SKIP)
 	else if (!strcmp(key, "site_short")) E->opt_site_short = value;       // 1: the hits of oligo sites end on k_site_ends_short (default), 0: on k_site_ends (-1: default / FASIM_SITE_SHORT)
 	else if (!strcmp(key, "sim_lds")) E->opt_sim_lds = value < 0 ? -1 : value != 0;   // -F re-sweeps: 0 the L2 variant, 1 the LDS variant where the state fits, -1 by the units in flight (tests)
 	else if (!strcmp(key, "site_chunk")) E->opt_site_chunk = value > 0 ? value : 0;   // problems per chunk of the site hits phase (0: the phase's own limit)

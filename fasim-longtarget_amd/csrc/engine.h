@@ -134,6 +134,8 @@ struct fasim_engine {
 	int opt_band = -1;                           // option "band": 0 off, 1 on (-1 = default / environment FASIM_BAND)
 	int opt_dp_f16 = -1;                         // option "dp_f16": packed-f16 k_scan and reverse pass, 0 = the integer kernels (-1 = default / environment FASIM_DP_F16)
 	int opt_q2_past_cut = -1;                    // option "q2_past_cut": 1 = k_scan tracks Q2 taints to the end of every unit, 0 = up to a proven overflow cut (-1 = default / environment FASIM_Q2_PAST_CUT)
+	int opt_finish_skip = -1;                    // option "finish_skip": 1 = the split finish leaves alignments the stability filter must drop without a CIGAR, 0 = k_finish_lds traces all, 2 = trace all and check the rule (-1 = default / environment FASIM_FINISH_SKIP)
+	DevBuf fmask, flist, fmarks, seg_clean;      // the split finish: ballot masks per wave, the list of alignments to trace, mode 2's marks; per segment of the batch 1 = only ACGTN
 	DevBuf unit_ovf;                             // [unit] != 0: the f16 k_scan saw a value outside its exact range
 	DevBuf track, track_phase, track_sat;        // fasim_scan_track only: k_track's slices, its per-segment bin phase and saturation flags of the batch
 	DevBuf track_peaks;                          // fasim_scan_records_track only: k_track's peak per slice and class
@@ -346,6 +348,15 @@ inline bool q2_past_cut_mode(const fasim_engine* E)
 {
 	static const int env = [] { const char* e = getenv("FASIM_Q2_PAST_CUT"); return e ? atoi(e) : 0; }();
 	return (E->opt_q2_past_cut >= 0 ? E->opt_q2_past_cut : env) != 0;
+}
+// option finish_skip / FASIM_FINISH_SKIP: 1 (default) = the scan's finish runs k_finish_rev / k_finish_trace and leaves the alignments
+// that doomed.h proves to fail the stability filter without a CIGAR; 0 = k_finish_lds traces every alignment; 2 = every alignment is
+// traced and the rule is checked against the full conversion (stats finish_skip_violations).  The records are the same in all three.
+inline int finish_skip_mode(const fasim_engine* E)
+{
+	static const int env = [] { const char* e = getenv("FASIM_FINISH_SKIP"); return e ? atoi(e) : 1; }();
+	const int v = E->opt_finish_skip >= 0 ? E->opt_finish_skip : env;
+	return v < 0 || v > 2 ? 1 : v;
 }
 inline int band_mask(const fasim_engine* E)
 {
@@ -584,6 +595,7 @@ struct BatchCtx {
 	std::vector<int32_t> ucand, ualign;                 // per unit: candidates and window tries of stage 3 (per-record stats)
 	std::vector<int32_t> hoff, hcnt, thr; std::vector<uint32_t> hits;
 	std::vector<char> seg_acgtn;
+	const uint8_t* dna_dev = nullptr;                   // the batch's DNA on the device: E->seg_start counts from here (batch_encode)
 	const char* dna = nullptr; const fasim_params* p = nullptr; const std::vector<int>* encs = nullptr;
 	std::vector<std::vector<HostTriplex>> per_unit;     // [unit]: records of the unit after fastSIM's own filter
 	bool stage3_done = false;                           // -F: the whole batch was finished in the scan phase

@@ -286,7 +286,7 @@ int batch_encode(fasim_engine* E, const char* dna, const SegTable& T, const uint
 	const int64_t step = p.cutLength - p.overlapLength;
 	const int nenc = (int)encs.size();
 	C.B = UnitBatch(); C.tstride = tstride; C.nenc = nenc; C.nseg = 0; C.step = step; C.dna = dna; C.p = &p; C.encs = &encs;
-	C.tab = class_table(encs); C.track_nchunk = track_chunks(p.cutLength);
+	C.tab = class_table(encs); C.track_nchunk = track_chunks(p.cutLength); C.dna_dev = nullptr;
 	// segments of this batch that are not skipped by same_seq()
 	std::vector<int32_t>& sstart = C.sstart; std::vector<int32_t>& slen = C.slen; std::vector<int64_t>& sidx = C.sidx;
 	sstart.clear(); slen.clear(); sidx.clear(); C.soff.clear(); C.srec.clear();
@@ -357,6 +357,7 @@ int batch_encode(fasim_engine* E, const char* dna, const SegTable& T, const uint
 	he = launch_encode(dna_dev, E->seg_start.as<int32_t>(), E->seg_len.as<int32_t>(), nseg,
 		E->enc_ids.as<int32_t>(), nenc, E->enc_lut.as<uint8_t>(), E->tcodes.as<uint8_t>(), tstride, E->st); }
 	if (he != hipSuccess) return fail(E, FASIM_E_HIP, "encode launch failed: %s", hipGetErrorString(he));
+	C.dna_dev = dna_dev;
 	return FASIM_OK;
 }
 
@@ -603,6 +604,7 @@ static void add_stats(fasim_scan_stats& st, const fasim_scan_stats& x)
 	st.cells_stage2 += x.cells_stage2; st.cells_stage3 += x.cells_stage3; st.hazard_units += x.hazard_units; st.rev_exact += x.rev_exact;
 	st.exact_replays += x.exact_replays; st.tries_skipped += x.tries_skipped;
 	st.finish_lds16 += x.finish_lds16; st.finish_lds64 += x.finish_lds64; st.finish_glob16k += x.finish_glob16k; st.finish_glob1m += x.finish_glob1m;
+	st.finish_skipped += x.finish_skipped; st.finish_skip_violations += x.finish_skip_violations;
 	st.band_tries += x.band_tries; st.band_proven += x.band_proven; st.band_cells += x.band_cells; st.rev_bound_passes += x.rev_bound_passes;
 	st.striped_window_probs += x.striped_window_probs; st.striped_window_ms += x.striped_window_ms;
 	st.dp_f16_reruns += x.dp_f16_reruns;

@@ -1,10 +1,12 @@
 // fasim-longtarget_amd/csrc/engine_stage3.cpp -- stage 3 of the host engine: window tries (band passes, reverse pass, full-height
 // passes), exact replays, finish kernels, and the per-batch driver stage3_range (candidates -> triplex records).
 #include "engine.h"
+#include <cassert>
 
 
 int run_finish(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb>& W, const std::vector<FwdOut>& fo,
-	std::vector<AlignResult>& out, std::vector<uint32_t>& cigars, std::vector<char>& status, std::vector<int32_t>* path = nullptr);
+	std::vector<AlignResult>& out, std::vector<uint32_t>& cigars, std::vector<char>& status, std::vector<int32_t>* path = nullptr,
+	const BatchCtx* skip_ctx = nullptr, std::vector<char>* marks = nullptr);
 bool align_v2_fits(const fasim_engine* E, const std::vector<WindowProb>& W);
 // AlignResult::cigar_len of an alignment that run_finish leaves to the stripe-faithful path with its ends filled in: the reverse pass
 // is done and only the banded part did not fit (device status 2) or the CIGAR has more than ALIGN_MAX_CIGAR runs (status 4)
@@ -441,13 +443,20 @@ int run_rev_exact(fasim_engine* E, const UnitBatch& B, const std::vector<WindowP
 // path (may be null): per alignment, which pass wrote its final device status: 1 k_finish_lds<64, 2048>, 2 k_finish_lds<256, 16384>,
 //            3 k_finish with 16 KB, 4 k_finish with 1 MB (device status 0, 1 or 3 each); 5 = left to the stripe-faithful path (device
 //            status 2 after the last pass, or 4, 10, 11 from any); 0 = nothing aligned (forward score 0)
+// skip_ctx (the scan only; NULL: every alignment gets its CIGAR): the batch of the windows.  With option finish_skip != 0 tier 1 is
+//            the split one (launch_finish_split), and an alignment whose record the stability filter is certain to drop (doomed.h)
+//            comes back with status 0, its ends and score, and cigar_len CIGAR_LEN_SKIPPED.  Mode 2: none is left out, and marks[k]
+//            (may be null otherwise) = 1 where the rule would have.
 int run_finish(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb>& W, const std::vector<FwdOut>& fo,
-	std::vector<AlignResult>& out, std::vector<uint32_t>& cigars, std::vector<char>& status, std::vector<int32_t>* path)
+	std::vector<AlignResult>& out, std::vector<uint32_t>& cigars, std::vector<char>& status, std::vector<int32_t>* path,
+	const BatchCtx* skip_ctx, std::vector<char>* marks)
 {
 	const int n = (int)W.size();
 	out.assign(n, AlignResult()); status.assign(n, 0);
 	if (path) path->assign(n, 0);
+	if (marks) marks->assign(n, 0);
 	if (!n) return FASIM_OK;
+	const int skip_mode = skip_ctx && skip_ctx->dna_dev ? finish_skip_mode(E) : 0;
 	// tier[k]: the pass whose device status stands for alignment k (0 while it is still handed on with status 2)
 	std::vector<char> tier(n, 0);
 	auto settle = [&](const std::vector<AlignOutDev>& a, int pass) { for (int k = 0; k < n; k++) if (!tier[k] && a[k].status != 2) tier[k] = (char)pass; };
@@ -473,6 +482,26 @@ int run_finish(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb
 		rc = upload_async(E, E->forder, order.data(), sizeof(int32_t) * n); if (rc) return rc;
 	}
 	HIPOK(E->scratch.ensure((size_t)((n + 63) / 64) * 64 * 2048));
+	std::vector<uint8_t> clean;
+	FinishSkip fs = FinishSkip();
+	if (skip_mode) {
+		const BatchCtx& C = *skip_ctx;
+		const fasim_params& p = *C.p;
+		fs.dna = C.dna_dev; fs.seg_start = E->seg_start.as<int32_t>(); fs.seg_len = E->seg_len.as<int32_t>(); fs.enc_ids = E->enc_ids.as<int32_t>();
+		fs.nenc = C.nenc; fs.tstride = B.tstride; fs.check = skip_mode == 2;
+		fs.dp = DoomedParams{ p.penaltyT, p.penaltyC, p.ntMin, p.ntMax, p.minStability };
+		clean.assign(C.seg_acgtn.begin(), C.seg_acgtn.end());
+		rc = upload_async(E, E->seg_clean, clean.data(), clean.size()); if (rc) return rc;      // (outlives the first synchronisation below)
+		fs.seg_clean = E->seg_clean.as<uint8_t>();
+		HIPOK(E->fmask.ensure(sizeof(uint64_t) * (size_t)((n + 63) / 64)));
+		HIPOK(E->flist.ensure(sizeof(int32_t) * (size_t)n));
+		if (fs.check) HIPOK(E->fmarks.ensure((size_t)n));
+		{ TimedScope ts(E, 3);
+		he = launch_finish_split(tcv(E), E->q2.as<uint8_t>(), E->fprobs.as<FwdProb>(), E->fout.as<FwdOut>(), E->forder.as<int32_t>(), n,
+			E->scratch.as<uint8_t>(), E->aout.as<AlignOutDev>(), E->cigpool.as<uint32_t>(), (uint32_t)pool_cap, E->cigcount.as<uint32_t>(), fs,
+			E->fmask.as<uint64_t>(), E->flist.as<int32_t>(), E->cigcount.as<uint32_t>() + 1, fs.check ? E->fmarks.as<uint8_t>() : nullptr, E->st); }
+		if (he == hipSuccess && fs.check && marks) he = hipMemcpyAsync(marks->data(), E->fmarks.p, (size_t)n, hipMemcpyDeviceToHost, E->st);
+	} else
 	{ TimedScope ts(E, 3);
 	he = launch_finish(tcv(E), E->q2.as<uint8_t>(), E->fprobs.as<FwdProb>(), E->fout.as<FwdOut>(),
 		E->forder.as<int32_t>(), n, E->scratch.as<uint8_t>(), E->aout.as<AlignOutDev>(), E->cigpool.as<uint32_t>(), (uint32_t)pool_cap,
@@ -495,7 +524,9 @@ int run_finish(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb
 			HIPOK(E->scratch2.ensure((size_t)((mid.size() + 63) / 64) * 64 * 16384));
 			{ TimedScope ts(E, 3);
 			he = launch_finish_mid(tcv(E), E->q2.as<uint8_t>(), E->fprobs.as<FwdProb>(), E->fout.as<FwdOut>(), E->unit_ids.as<int32_t>(), (int)mid.size(),
-				E->scratch2.as<uint8_t>(), E->aout.as<AlignOutDev>(), E->cigpool.as<uint32_t>(), (uint32_t)pool_cap, E->cigcount.as<uint32_t>(), E->st); }
+				E->scratch2.as<uint8_t>(), E->aout.as<AlignOutDev>(), E->cigpool.as<uint32_t>(), (uint32_t)pool_cap, E->cigcount.as<uint32_t>(), E->st,
+					skip_mode ? &fs : nullptr, skip_mode == 2 ? E->fmarks.as<uint8_t>() : nullptr); }
+			if (he == hipSuccess && skip_mode == 2 && marks) he = hipMemcpyAsync(marks->data(), E->fmarks.p, (size_t)n, hipMemcpyDeviceToHost, E->st);
 			if (he != hipSuccess) return fail(E, FASIM_E_HIP, "finish (64 KB LDS) launch failed: %s", hipGetErrorString(he));
 			HIPOK(hipMemcpyAsync(ao.data(), E->aout.p, sizeof(AlignOutDev) * n, hipMemcpyDeviceToHost, E->st));
 			HIPOK(hipMemcpyAsync(&pool_used, E->cigcount.p, sizeof pool_used, hipMemcpyDeviceToHost, E->st));
@@ -563,6 +594,12 @@ int run_finish(fasim_engine* E, const UnitBatch& B, const std::vector<WindowProb
 		if (a.status == 2 || a.status == 4 || a.status == 10 || a.status == 11) { status[k] = 2; continue; }
 		if (a.status == 1 || a.status == 3) { status[k] = 1; continue; }
 		AlignResult& r = out[k];
+		if (a.status == 5) {
+			// certain to fail the stability filter (k_finish_rev): the ends and the score are all its record is ever asked for
+			r.sw_score = a.sw_score; r.ref_begin = a.ref_begin; r.ref_end = a.ref_end; r.query_begin = a.query_begin; r.query_end = a.query_end;
+			r.cigar_len = CIGAR_LEN_SKIPPED;
+			continue;
+		}
 		if (a.sw_score <= 0) { r.sw_score = 0; continue; }
 		r.sw_score = a.sw_score; r.ref_begin = a.ref_begin; r.ref_end = a.ref_end; r.query_begin = a.query_begin; r.query_end = a.query_end;
 		r.cigar_len = a.cigar_len; r.cigar_off = pool_base + a.cigar_off;
@@ -625,7 +662,7 @@ int stage3_range(fasim_engine* E, BatchCtx& C, int ua, int ub, fasim_scan_stats&
 		//      the reference's layout-dependent behaviour, or whose traceback fails in the reference (NULL ->
 		//      score 0 -> the loop would have continued), are replayed try by try on the stripe-faithful path.
 		t0 = now_s();
-		struct CandState { int unit; Cand c; AlignResult al, best; FwdOut fsel, fbest; int cut, bestcut; char done, flag, exact, ru_it; };
+		struct CandState { int unit; Cand c; AlignResult al, best; FwdOut fsel, fbest; int cut, bestcut; char done, flag, exact, ru_it, mark; };
 		std::vector<uint32_t> cigars;
 		std::vector<CandState> cs;
 		{
@@ -640,7 +677,7 @@ int stage3_range(fasim_engine* E, BatchCtx& C, int ua, int ub, fasim_scan_stats&
 				for (int u = u0; u < u1; u++) {
 					pick_candidates(hits.data() + hoff[u], hcnt[u], tmp);
 					for (const Cand& c : tmp) { CandState x; memset(&x.fsel, 0, sizeof x.fsel); memset(&x.fbest, 0, sizeof x.fbest);
-						x.unit = u; x.c = c; x.done = 0; x.cut = 0; x.bestcut = 0; x.flag = 0; x.exact = 0; x.ru_it = -1; part[ti].push_back(x); }
+						x.unit = u; x.c = c; x.done = 0; x.cut = 0; x.bestcut = 0; x.flag = 0; x.exact = 0; x.ru_it = -1; x.mark = 0; part[ti].push_back(x); }
 				}
 			};
 			if (nt == 1) work(0);
@@ -743,9 +780,12 @@ int stage3_range(fasim_engine* E, BatchCtx& C, int ua, int ub, fasim_scan_stats&
 				if (x.fsel.score <= 0) { x.al.sw_score = 0; continue; }
 				W.push_back({ x.unit, x.c.pos - x.cut + 1, x.cut }); fsel.push_back(x.fsel); who.push_back((int)k);
 			}
-			std::vector<AlignResult> res; std::vector<char> status; std::vector<int32_t> tier;
-			rc = run_finish(E, B, W, fsel, res, cigars, status, &tier); if (rc) return rc;
+			std::vector<AlignResult> res; std::vector<char> status, marks; std::vector<int32_t> tier;
+			rc = run_finish(E, B, W, fsel, res, cigars, status, &tier, &C, &marks); if (rc) return rc;
 			for (size_t i = 0; i < who.size(); i++) {
+				if (marks[i] || (status[i] == 0 && res[i].cigar_len == CIGAR_LEN_SKIPPED)) st.finish_skipped++;
+				if (marks[i] && status[i] != 0) st.finish_skip_violations++;      // finish_skip = 2: the traced path must end with device status 0
+				cs[who[i]].mark = marks[i];
 				if (tier[i] == 1) st.finish_lds16++; else if (tier[i] == 2) st.finish_lds64++; else if (tier[i] == 3) st.finish_glob16k++; else if (tier[i] == 4) st.finish_glob1m++;
 				CandState& x = cs[who[i]];
 				if (status[i] != 0) { if (g_prof.on) { static const char* nm[6] = { "exact: finish status 0", "exact: finish status 1 (count)", "exact: finish status 2 (count)", "exact: finish status 3 (count)", "exact: finish status 4 (count)", "exact: finish status >= 5 (count)" }; const int si = std::min(5, (int)status[i]); g_prof.add(13 + si, nm[si], 1e-6); } x.exact = 1; continue; }
@@ -817,6 +857,7 @@ int stage3_range(fasim_engine* E, BatchCtx& C, int ua, int ub, fasim_scan_stats&
 			for (const CandState& x : cs) first[x.unit + 1]++;
 			for (int u = ua; u < ub; u++) first[u + 1] += first[u];
 			std::atomic<int> next(ua);
+			std::atomic<int64_t> violations(0);
 			auto work = [&]() {
 				CpuScope cpu(26, "CPU seconds: records (convert_triplex, dedup)");
 				std::vector<TriplexNum> mine, kept;
@@ -836,8 +877,11 @@ int stage3_range(fasim_engine* E, BatchCtx& C, int ua, int ub, fasim_scan_stats&
 						if (al.sw_score == 0) continue;                                                    // fastsim.h:253
 						al.ref_begin += x.c.pos - cut + 1; al.ref_end += x.c.pos - cut + 1;                // :254-255
 						const size_t before = mine.size();
-						convert_triplex_num(al, cigars.data() + al.cigar_off, E->rna, seg, slen[s], enc, dna_start, p, mine, acgtn);
+						if (al.cigar_len == CIGAR_LEN_SKIPPED) push_doomed_num(al, slen[s], enc, dna_start, mine);
+						else convert_triplex_num(al, cigars.data() + al.cigar_off, E->rna, seg, slen[s], enc, dna_start, p, mine, acgtn);
 						if (mine.size() > before) mine.back().cand = (int)k;
+						// finish_skip = 2: what the rule would have left out must be a record (total >= ntMin) that fails the stability filter
+						if (x.mark && !x.exact && !(mine.size() > before && mine.back().tri_score < p.minStability)) violations.fetch_add(1);
 					}
 					dedup_top_num(mine, p, kept);
 					for (const TriplexNum& tn : kept) {
@@ -846,6 +890,7 @@ int stage3_range(fasim_engine* E, BatchCtx& C, int ua, int ub, fasim_scan_stats&
 						// a surviving record: the same conversion once more, this time with its TFO / TTS strings
 						const CandState& x = cs[(size_t)tn.cand];
 						AlignResult al = x.al;
+						assert(al.cigar_len != CIGAR_LEN_SKIPPED);      // tri_score = -infinity passes no filter
 						al.ref_begin += x.c.pos - x.cut + 1; al.ref_end += x.c.pos - x.cut + 1;
 						one.clear();
 						convert_triplex(al, cigars.data() + al.cigar_off, E->rna, seg, slen[s], enc, dna_start, p, one, acgtn, true);
@@ -859,6 +904,7 @@ int stage3_range(fasim_engine* E, BatchCtx& C, int ua, int ub, fasim_scan_stats&
 			const int nt = std::max(1, std::min(share, ub - ua));
 			if (nt == 1) work();
 			else { std::vector<std::thread> th; for (int k = 0; k < nt; k++) th.emplace_back(work); for (auto& t : th) t.join(); }
+			st.finish_skip_violations += violations.load();
 		}
 		st.t_host_s += now_s() - t0;
 	}

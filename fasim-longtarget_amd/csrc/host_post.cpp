@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <sstream>
 #include <thread>
 
@@ -305,6 +306,20 @@ void convert_triplex_num(const AlignResult& al, const uint32_t* cigar, const std
 	t.starj = (int)(rs + dna_start); t.endj = (int)(re + dna_start);
 	t.nt = nt; t.cand = -1;
 	t.score = (float)al.sw_score; t.tri_score = tri;
+	list.push_back(t);
+}
+
+void push_doomed_num(const AlignResult& al, int n, int enc, long dna_start, std::vector<TriplexNum>& list)
+{
+	const EncInfo e = enc_info(enc);
+	TriplexNum t;
+	int rs, re;
+	if ((e.para > 0 && e.strand == 1) || (e.para < 0 && e.strand == 0)) { rs = n - al.ref_end - 1; re = n - al.ref_begin - 1; }   // fastsim.h:389-396
+	else { rs = al.ref_begin + 1; re = al.ref_end + 1; }
+	t.stari = al.query_begin + 1; t.endi = al.query_end + 1;
+	t.starj = (int)(rs + dna_start); t.endj = (int)(re + dna_start);
+	t.nt = std::max(al.ref_end - al.ref_begin, al.query_end - al.query_begin) + 1; t.cand = -1;
+	t.score = (float)al.sw_score; t.identity = 0.0f; t.tri_score = -std::numeric_limits<float>::infinity();
 	list.push_back(t);
 }
 

@@ -27,6 +27,10 @@ struct AlignResult {            // CIGAR ops live in a pool owned by the caller:
 	int failed = 0;             // 1: the reference's ssw_align returns NULL here (banded_sw found no path): sw_score is 0
 };
 
+// AlignResult::cigar_len of an alignment of the scan that was left without a CIGAR because the stability filter is certain to drop its
+// record (doomed.h; option finish_skip): ends and score are valid, cigar_off is not
+constexpr int CIGAR_LEN_SKIPPED = -3;
+
 // window length tried at iteration `it` (0..3) for a candidate (fastsim.h:204-211); returns false when the
 // loop `while (Iden <= 1)` has ended
 bool window_for_try(int it, int cand_score, int cand_pos, int* cutlength);
@@ -83,6 +87,10 @@ void dedup_top(std::vector<HostTriplex>& mine, const fasim_params& p, std::vecto
 struct TriplexNum { int stari, endi, starj, endj, nt, cand; float score, identity, tri_score; };
 void convert_triplex_num(const AlignResult& al, const uint32_t* cigar, const std::string& rna, const char* seg, int n, int enc,
 	long dna_start, const fasim_params& p, std::vector<TriplexNum>& list, bool seg_acgtn);
+// the record of a CIGAR_LEN_SKIPPED alignment: the coordinates and the score as convert_triplex_num gives them, nt = the longer span
+// (>= ntMin, length_known), identity 0 and tri_score = -infinity.  The de-duplication and the top 50 read the first five only, and
+// no filter lets the record through.
+void push_doomed_num(const AlignResult& al, int n, int enc, long dna_start, std::vector<TriplexNum>& list);
 void dedup_top_num(std::vector<TriplexNum>& mine, const fasim_params& p, std::vector<TriplexNum>& out);
 
 void cluster_triplex(int dd, int length, std::vector<HostTriplex>& list);

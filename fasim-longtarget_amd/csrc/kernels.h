@@ -4,6 +4,7 @@
 #include <type_traits>
 #include <vector>
 #include "device_types.h"
+#include "doomed.h"
 
 namespace fasim {
 
@@ -295,9 +296,21 @@ hipError_t launch_build_stream(const uint8_t* tcodes, const FwdProb* probs, int3
 hipError_t launch_align_fwd(const FwdLaunch& L, hipStream_t st);     // hipErrorInvalidValue: query too long
 hipError_t launch_finish(const uint8_t* tcodes, const uint8_t* qcodes, const FwdProb* probs, const FwdOut* fwd, const int32_t* order,
 	int32_t nprob, uint8_t* dirs, AlignOutDev* out, uint32_t* cigar_pool, uint32_t pool_cap, uint32_t* pool_count, hipStream_t st);
+// The split tier 1 (k_finish_rev, k_finish_compact, k_finish_trace): what the rule of doomed.h needs on the device.  The batch's DNA
+// letters with the segment starts and lengths k_encode read them by, the enabled encodings, per segment 1 = only ACGTN (complement()
+// drops nothing).  check: 1 = mark the alignments the rule would skip in marks[] and trace them all the same (option finish_skip = 2).
+struct FinishSkip {
+	const uint8_t* dna; const int32_t* seg_start; const int32_t* seg_len; const int32_t* enc_ids; const uint8_t* seg_clean;
+	int32_t nenc, tstride, check;
+	DoomedParams dp;
+};
+hipError_t launch_finish_split(const uint8_t* tcodes, const uint8_t* qcodes, const FwdProb* probs, const FwdOut* fwd, const int32_t* order,
+	int32_t nprob, uint8_t* dirs, AlignOutDev* out, uint32_t* cigar_pool, uint32_t pool_cap, uint32_t* pool_count, const FinishSkip& fs,
+	uint64_t* masks, int32_t* list, uint32_t* list_count, uint8_t* marks, hipStream_t st);
 
 hipError_t launch_finish_mid(const uint8_t* tcodes, const uint8_t* qcodes, const FwdProb* probs, const FwdOut* fwd, const int32_t* idx_list,
-	int32_t nlist, uint8_t* dirs, AlignOutDev* out, uint32_t* cigar_pool, uint32_t pool_cap, uint32_t* pool_count, hipStream_t st);
+	int32_t nlist, uint8_t* dirs, AlignOutDev* out, uint32_t* cigar_pool, uint32_t pool_cap, uint32_t* pool_count, hipStream_t st,
+	const FinishSkip* fs = nullptr /* non-NULL: the rule of doomed.h as an exit behind the reverse pass */, uint8_t* marks = nullptr /* fs->check */);
 hipError_t launch_finish_big(const uint8_t* tcodes, const uint8_t* qcodes, const FwdProb* probs, const FwdOut* fwd,
 	const int32_t* idx_list, int32_t nlist, uint8_t* scratch, int32_t scratch_cap, AlignOutDev* out, uint32_t* cigar_pool,
 	uint32_t pool_cap, uint32_t* pool_count, hipStream_t st);

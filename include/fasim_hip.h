@@ -99,6 +99,12 @@ const char* fasim_last_error(const fasim_engine* e);   /* e may be NULL: last gl
  * the cut is ever read (csrc/scan.hip); 1 = it tracks to the end of every unit, as before the option existed;
  * -1 restores the default (env FASIM_Q2_PAST_CUT).  Results, hazard units and every counter do not depend on it: only bit 0 of
  * k_scan's column maxima behind the cut does (tests/test_gpu_q2_past_cut.py).
+ * key "finish_skip" (1): 1 = the finish of fasim_scan and its kin (k_finish_rev / k_finish_trace, csrc/align.hip) leaves an alignment
+ * without its CIGAR when its record is certain to fail the stability filter (csrc/doomed.h, DESIGN.md section 2: a TT pair on the
+ * display strand inside the alignment's span under penaltyT < 0, minStability > 0), counted in stats.finish_skipped; 0 = k_finish_lds
+ * traces every alignment, as before the option existed; 2 = every alignment is traced and the rule is checked against the full
+ * conversion, misses counted in stats.finish_skip_violations; -1 restores the default (env FASIM_FINISH_SKIP).  The records do not
+ * depend on it (tests/test_gpu_finish_skip.py).  fasim_align_batch* return CIGARs and never skip.
  * key "sim_lds" (-1): which storage variant of k_sim_resweep the -F rounds launch.  -1 = by the units in flight (the LDS variant
  * once at most 256 are left over all workers); 0 = always the variant that keeps the lines' states in L2; 1 = always the LDS variant
  * (the kernel still takes the L2 variant when the states of a unit exceed 150 KB).  No environment variable (for tests).
@@ -225,6 +231,9 @@ typedef struct fasim_scan_stats {
 	 * or time slice spent before the re-sweep ended); suspended units that were resumed by the other variant than the one that
 	 * suspended them */
 	int64_t sim_resweep_lds, sim_resweep_l2, sim_suspended, sim_handover;
+	/* option finish_skip: alignments of the scan's finish left without a CIGAR because the stability filter is certain to drop
+	 * their record (mode 2: that would have been left); mode 2 only: those for which the full conversion did not confirm it */
+	int64_t finish_skipped, finish_skip_violations;
 } fasim_scan_stats;
 
 struct fasim_result {
