@@ -164,10 +164,21 @@ class _Hist(C.Structure):
                 ("npending", C.c_int64), ("pending", C.POINTER(_HistEdge))]
 
 
+class _SiteCountsEdge(C.Structure):
+    _fields_ = [("record", C.c_int32), ("side", C.c_int32), ("boundary", C.c_int64), ("len", C.c_int32), ("link", C.c_int32),
+                ("nb", C.c_uint16 * 4), ("v", C.POINTER(C.c_uint16))]
+
+
+class _SiteCounts(C.Structure):
+    _fields_ = [("n", C.POINTER(C.c_int64) * 4), ("pairs", C.POINTER(C.c_int64) * 4), ("positions", C.c_int64), ("npairs", C.c_int64),
+                ("units", C.c_int64), ("saturated_units", C.c_int64), ("npending", C.c_int64), ("pending", C.POINTER(_SiteCountsEdge))]
+
+
 # FASIM_HIST_BINS (include/fasim_hip.h): values of a potential histogram; HIST_LDS_BINS (csrc/kernels.h): values below it are counted
-# in k_hist's workgroup histogram first
+# in k_hist's workgroup histogram first, HIST_PAIR_LDS_BINS the same for the two histograms of k_hist_pairs
 HIST_BINS = 16384
 HIST_LDS_BINS = 1024
+HIST_PAIR_LDS_BINS = 512
 
 TRACK_CLASSES = ("ParaPlus", "ParaMinus", "AntiMinus", "AntiPlus")
 
@@ -184,6 +195,8 @@ EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_e
            "fasim_scan_oligos", "fasim_oligo_panel_tsv", "fasim_scan_oligos_aligned",
            "fasim_scan_records_hist", "fasim_scan_oligos_hist", "fasim_hist_merge", "fasim_hist_free", "fasim_shuffle_query",
            "fasim_hist_threshold", "fasim_hist_tsv",
+           "fasim_scan_records_site_counts", "fasim_scan_oligos_site_counts", "fasim_site_counts_merge", "fasim_site_counts_free",
+           "fasim_shuffle_query_dinuc", "fasim_site_counts_threshold", "fasim_site_counts_tsv",
            "fasim_read_vcf", "fasim_score_variants", "fasim_variants_tsv",
            "fasim_score_variants_aligned", "fasim_variant_hit_span", "fasim_variant_hits_tsv",
            # the reference's own ssw.h ABI (include/ssw.h)
@@ -326,6 +339,21 @@ def lib():
     L.fasim_hist_threshold.restype = C.c_int32
     L.fasim_hist_tsv.argtypes = [C.POINTER(_Hist), C.POINTER(C.POINTER(_Hist)), C.c_int32, C.c_uint64, C.c_double, C.c_char_p,
                                  C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.fasim_scan_records_site_counts.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
+                                                 C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int64, C.c_int64,
+                                                 C.POINTER(Params), C.POINTER(C.POINTER(_Result)), C.POINTER(C.POINTER(_SiteCounts)),
+                                                 C.POINTER(ScanStats)]
+    L.fasim_scan_oligos_site_counts.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
+                                                C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int64, C.c_int64,
+                                                C.POINTER(Params), C.POINTER(C.POINTER(_SiteCounts)), C.POINTER(ScanStats)]
+    L.fasim_site_counts_merge.argtypes = [C.POINTER(C.POINTER(_SiteCounts)), C.c_int32, C.POINTER(C.POINTER(_SiteCounts))]
+    L.fasim_site_counts_free.argtypes = [C.POINTER(_SiteCounts)]
+    L.fasim_site_counts_free.restype = None
+    L.fasim_shuffle_query_dinuc.argtypes = [C.c_char_p, C.c_int32, C.c_uint64, C.c_int32, C.c_char_p]
+    L.fasim_site_counts_threshold.argtypes = [C.POINTER(_SiteCounts), C.POINTER(C.POINTER(_SiteCounts)), C.c_int32, C.c_double]
+    L.fasim_site_counts_threshold.restype = C.c_int32
+    L.fasim_site_counts_tsv.argtypes = [C.POINTER(_SiteCounts), C.POINTER(C.POINTER(_SiteCounts)), C.c_int32, C.c_uint64, C.c_int32,
+                                        C.c_double, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.fasim_read_vcf.argtypes = [C.c_char_p, C.POINTER(C.POINTER(_Variant)), C.POINTER(C.c_int64)]
     L.fasim_score_variants.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.POINTER(_Variant), C.c_int64, C.c_int32,
@@ -692,6 +720,132 @@ def hist_tsv(real: Hist, rna_name: str, controls=(), seed: int = 0, fdr: float =
     L = lib()
     controls, arr = _hist_ptrs(controls)
     return _text_call(L.fasim_hist_tsv, real.pointer(), arr, len(controls), seed & 0xFFFFFFFFFFFFFFFF, fdr, rna_name.encode())
+
+
+class SiteCounts(_Native):
+    """Positions and pairs of neighbouring positions per strand class and potential of one lncRNA (or oligo, or control) over a
+    record set (struct fasim_site_counts): n is Hist's, pairs[c][w] the number of pairs (x - 1, x) of one record with
+    min(P[x - 1], P[x]) == w, and sites()[c][v] the number of sites `scan_sites(min_value=v, max_gap=0)` reports for class c.  Either
+    native (what scan_site_counts(), scan_oligos_site_counts() and merge_site_counts() return) or made from a (2, 4, 16384) array:
+    `SiteCounts(counts, positions=None, npairs=None, units=0, saturated_units=0, pending=())`, positions and npairs defaulting to
+    the sums of class 0 and `pending` a list of (record, boundary, side, values, nb, link): values a (4, len) array, nb the four
+    values of the position next to the zone and link 0 / 1 / 2 (fasim_site_counts_edge)."""
+
+    _free = "fasim_site_counts_free"
+
+    def __init__(self, counts=None, positions=None, npairs=None, units: int = 0, saturated_units: int = 0, pending=(), _native=None):
+        self._native = _native
+        self._keep = None
+        if _native is None:
+            import numpy as np
+            a = np.ascontiguousarray(counts, dtype=np.int64)
+            if a.shape != (2, 4, HIST_BINS):
+                raise FasimError(f"site counts are a (2, 4, {HIST_BINS}) array", E_ARG)
+            t = _SiteCounts()
+            t.positions = int(a[0, 0].sum()) if positions is None else positions
+            t.npairs = int(a[1, 0].sum()) if npairs is None else npairs
+            t.units, t.saturated_units = units, saturated_units
+            for c in range(4):
+                t.n[c] = C.cast(a[0, c].ctypes.data, C.POINTER(C.c_int64))
+                t.pairs[c] = C.cast(a[1, c].ctypes.data, C.POINTER(C.c_int64))
+            pend = sorted(((int(r), int(b), int(sd), np.ascontiguousarray(v, dtype=np.uint16), [int(x) for x in nb], int(link))
+                           for r, b, sd, v, nb, link in pending), key=lambda e: e[:3])
+            edges = (_SiteCountsEdge * max(1, len(pend)))()
+            for k, (r, b, sd, v, nb, link) in enumerate(pend):
+                if v.ndim != 2 or v.shape[0] != 4 or len(nb) != 4:
+                    raise FasimError("the values of a pending edge are a (4, len) array and four neighbour values", E_ARG)
+                edges[k].record, edges[k].boundary, edges[k].side, edges[k].len, edges[k].link = r, b, sd, v.shape[1], link
+                for c in range(4):
+                    edges[k].nb[c] = nb[c]
+                edges[k].v = C.cast(v.ctypes.data, C.POINTER(C.c_uint16))
+            t.npending, t.pending = len(pend), C.cast(edges, C.POINTER(_SiteCountsEdge))
+            self._keep = (a, t, pend, edges)
+
+    positions = property(lambda self: int(self._t.positions))
+    npairs = property(lambda self: int(self._t.npairs))
+    units = property(lambda self: int(self._t.units))
+    saturated_units = property(lambda self: int(self._t.saturated_units))
+
+    @property
+    def pending(self):
+        """[(record, boundary, side, values, nb, link)]: the boundaries whose other segment lay outside the call's range, ordered."""
+        import numpy as np
+        t = self._t
+        out = []
+        for k in range(int(t.npending)):
+            e = t.pending[k]
+            v = np.zeros((4, e.len), dtype=np.uint16)
+            if e.len:
+                C.memmove(v.ctypes.data, e.v, 2 * 4 * e.len)
+            out.append((int(e.record), int(e.boundary), int(e.side), v, [int(e.nb[c]) for c in range(4)], int(e.link)))
+        return out
+
+    def array(self):
+        """(2, 4, 16384) numpy int64 array (a copy): [0] the positions (Hist.array()), [1] the pairs; rows in TRACK_CLASSES order."""
+        import numpy as np
+        out = np.zeros((2, 4, HIST_BINS), dtype=np.int64)
+        for c in range(4):
+            C.memmove(out[0, c].ctypes.data, self._t.n[c], 8 * HIST_BINS)
+            C.memmove(out[1, c].ctypes.data, self._t.pairs[c], 8 * HIST_BINS)
+        return out
+
+    def sites(self):
+        """(4, 16384) int64: sites()[c][v] = the sum over w >= v of n[c][w] - pairs[c][w], the sites of class c at threshold v >= 1
+        with max_gap 0 (column 0 counts the records' covered stretches)."""
+        import numpy as np
+        a = self.array()
+        return np.cumsum((a[0] - a[1])[:, ::-1], axis=1)[:, ::-1].copy()
+
+
+def merge_site_counts(parts) -> SiteCounts:
+    """The site counts of a record set from those of its shards (fasim_site_counts_merge): as merge_hists(), with the pairs inside
+    and across the borders of every overlap whose two sides are there."""
+    L = lib()
+    parts = list(parts)
+    arr = (C.POINTER(_SiteCounts) * max(1, len(parts)))(*[t.pointer() for t in parts])
+    out = C.POINTER(_SiteCounts)()
+    rc = L.fasim_site_counts_merge(arr, len(parts), C.byref(out))
+    if rc != 0:
+        raise FasimError(f"fasim_site_counts_merge failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
+    return SiteCounts(_native=out)
+
+
+def shuffle_query_dinuc(rna: bytes, seed: int, k: int) -> bytes:
+    """Control k (1-based) of a query under `seed` that keeps every dinucleotide count and both end bytes
+    (fasim_shuffle_query_dinuc): a random Euler path, splitmix64 as shuffle_query()."""
+    L = lib()
+    rna = bytes(rna)
+    out = C.create_string_buffer(max(1, len(rna)))
+    rc = L.fasim_shuffle_query_dinuc(rna, len(rna), seed & 0xFFFFFFFFFFFFFFFF, k, out)
+    if rc != 0:
+        raise FasimError(f"fasim_shuffle_query_dinuc failed ({rc}): {L.fasim_last_error(None).decode()}", rc)
+    return out.raw[:len(rna)]
+
+
+def _site_counts_ptrs(controls):
+    controls = list(controls)
+    return controls, (C.POINTER(_SiteCounts) * max(1, len(controls)))(*[t.pointer() for t in controls])
+
+
+def site_counts_threshold(real: SiteCounts, controls=(), fdr: float = 0.05) -> int:
+    """hist_threshold() on sites instead of positions (fasim_site_counts_threshold); 0 when there is none."""
+    L = lib()
+    controls, arr = _site_counts_ptrs(controls)
+    v = L.fasim_site_counts_threshold(real.pointer(), arr, len(controls), fdr)
+    if v < 0:
+        raise FasimError(f"fasim_site_counts_threshold failed ({v}): {L.fasim_last_error(None).decode()}", v)
+    return int(v)
+
+
+def site_counts_tsv(real: SiteCounts, rna_name: str, controls=(), seed: int = 0, fdr: float = 0.05, shuffle: str = "mono") -> bytes:
+    """The table of `fasim --potential-hist --hist-sites` (fasim_site_counts_tsv): per value the sites per class and, with controls,
+    those of the controls and the false discovery rate per site."""
+    L = lib()
+    if shuffle not in ("mono", "di"):
+        raise FasimError(f"site_counts_tsv: shuffle = {shuffle!r} is neither 'mono' nor 'di'", E_ARG)
+    controls, arr = _site_counts_ptrs(controls)
+    return _text_call(L.fasim_site_counts_tsv, real.pointer(), arr, len(controls), seed & 0xFFFFFFFFFFFFFFFF, int(shuffle == "di"), fdr,
+                      rna_name.encode())
 
 
 class TfoProfile(_Native):
@@ -1483,6 +1637,64 @@ class Engine:
                                                    hs, totals))
         self._totals(totals, nq)
         return [Hist(_native=hs[q]) for q in range(nq)]
+
+    def scan_site_counts(self, dnas, params: Params | None = None, controls: int = 0, seed: int = 0, shuffle: str = "mono",
+                         records: bool = False, seg_first: int = 0, seg_count: int = -1, rnas=None):
+        """Sites per threshold over a record set, with shuffled controls (fasim_scan_records_site_counts): `(results | None, counts,
+        control_counts)`, everything as scan_hist() with SiteCounts in the place of the Hists.  shuffle "mono": the controls are
+        shuffle_query(rna, seed, k); "di": shuffle_query_dinuc(rna, seed, k), which keep the dinucleotide counts.  Shards of a
+        segment range merge with merge_site_counts()."""
+        p = params or default_params()
+        blob, offs, lens, nrec = _pack_records(dnas, resident_ok=True)
+        if controls < 0:
+            raise FasimError(f"scan_site_counts: controls = {controls} is negative", E_ARG)
+        if shuffle not in ("mono", "di"):
+            raise FasimError(f"scan_site_counts: shuffle = {shuffle!r} is neither 'mono' nor 'di'", E_ARG)
+        if rnas is None and getattr(self, "rna", None) is None:
+            raise FasimError("scan_site_counts: no query set: call set_query() first", E_ARG)
+        base = [self.rna] if rnas is None else [bytes(r) for r in rnas]
+        nb = len(base)
+        shuf = shuffle_query_dinuc if shuffle == "di" else shuffle_query
+        ctl = [shuf(r, seed, k + 1) for r in base for k in range(controls)]
+
+        def call(qs, want_records):
+            arr, qlens, nq, _ = _pack_queries(qs)
+            outs = (C.POINTER(_Result) * (max(1, nq) * max(1, nrec)))() if want_records else None
+            cs = (C.POINTER(_SiteCounts) * max(1, nq))()
+            totals = (ScanStats * max(1, nq))()
+            self._check(self._L.fasim_scan_records_site_counts(self._h, arr, qlens, nq, blob, offs, lens, nrec, seg_first, seg_count,
+                                                               C.byref(p), outs, cs, totals))
+            res = self._wrap_results(outs, nq, nrec) if want_records else None
+            return res, [SiteCounts(_native=cs[q]) for q in range(nq)], [self._stats_dict(totals[q]) for q in range(nq)]
+
+        if records:
+            # stage 3 for the lncRNAs only: their controls go in a counts-only call of their own
+            res, counts, totals = call(base, True)
+            ccounts = call(ctl, False)[1] if ctl else []
+        else:
+            res, allc, totals = call(base + ctl, False)
+            counts, ccounts, totals = allc[:nb], allc[nb:], totals[:nb]
+        if ctl:
+            self._check(self._L.fasim_set_query(self._h, base[-1], len(base[-1])))      # (a call leaves the engine on its last query)
+        self.rna, self.m = base[-1], len(base[-1])
+        self.last_totals = totals
+        ccounts = [ccounts[q * controls:(q + 1) * controls] for q in range(nb)]
+        if rnas is None:
+            return (res[0] if res else None), counts[0], ccounts[0]
+        return res, counts, ccounts
+
+    def scan_oligos_site_counts(self, oligos, dnas, params: Params | None = None, seg_first: int = 0, seg_count: int = -1):
+        """Sites per threshold of a panel of short oligos (fasim_scan_oligos_site_counts): one SiteCounts per oligo over the record
+        set.  `dnas` as for scan_oligos()."""
+        p = params or default_params()
+        blob, offs, lens, nrec = _pack_records(dnas, resident_ok=True)
+        arr, qlens, nq, _ = _pack_queries([bytes(x) for x in oligos])
+        cs = (C.POINTER(_SiteCounts) * max(1, nq))()
+        totals = (ScanStats * max(1, nq))()
+        self._check(self._L.fasim_scan_oligos_site_counts(self._h, arr, qlens, nq, blob, offs, lens, nrec, seg_first, seg_count,
+                                                          C.byref(p), cs, totals))
+        self._totals(totals, nq)
+        return [SiteCounts(_native=cs[q]) for q in range(nq)]
 
     def score_variants(self, variants, dnas, p: Params | None = None, flank: int = 300, queries=None, _aligned: bool = False):
         """The triplex potential through variants (fasim_score_variants): `(values, encs, flags)`, int32 arrays of shape

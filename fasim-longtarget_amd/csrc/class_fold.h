@@ -12,6 +12,9 @@
 //     whatever an earlier batch left there) and the reversed columns outside [n - P1, n - P0) (they belong to the neighbouring slices);
 //   * load() writes slots [0, P1 - P0) of rev[c][] and no other: slot s is the class maximum of the reversed rows at position P0 + s
 //     (column n - 1 - P0 - s).  value() reads slots 8 t .. 8 t + 7 and masks those from P1 - P0 on, which were never written;
+//   * slots TRACK_CHUNK .. TRACK_CHUNK + 7 of every row of rev[][] are the caller's: TRACK_CHUNK = 8 x 255, so only lane 255 owns them,
+//     it never holds a position (fwd_on is false, value() returns before it reads) and load() writes below P1 - P0 <= TRACK_CHUNK.
+//     k_hist_pairs (hist_pairs.hip) keeps its wave-boundary words there; a change to either function must keep this true;
 //   * sat[k] = 1 for every unit of the segment with a saturated column maximum among the slice's positions;
 //   * all maxima are taken on the raw values (v_pk_max_u16); the taint bit goes with one shift in value(), since
 //     max(a, b) >> 1 == max(a >> 1, b >> 1).
@@ -37,6 +40,8 @@ __device__ __forceinline__ bool fold_saturated(v8u v)
 	const v2us m = __builtin_elementwise_max(a, b);
 	return m[0] >= 32766 || m[1] >= 32766;
 }
+
+static_assert(TRACK_CHUNK == 8 * 255, "lane 255 owns no position: rev[][TRACK_CHUNK ..] is the caller's (see above)");
 
 struct ClassFold {
 	int n, P0, P1;            // the segment's length and the slice's positions [P0, P1); P0 >= n: no such slice, the workgroup returns

@@ -142,6 +142,7 @@ struct fasim_engine {
 	DevBuf sites_counts, sites_offsets, sites_runs, sites_sat;   // fasim_scan_records_sites only: k_sites' run counts per (slice, class), their prefix sum, the runs and saturation flags of the batch
 	DevBuf sa_q, sa_tcodes, sa_probs, sa_ends, sa_rows, sa_items, sa_dirs, sa_cigar, sa_ciglen;   // fasim_scan_records_sites_aligned only: query codes, the chunk's units, problems, end cells, row state of long queries, path items, direction bytes, CIGARs
 	DevBuf hist, hist_zone, hist_zones, hist_sat;   // fasim_scan_records_hist only: k_hist's counters of the batch, its zone bounds per segment, the zone values and saturation flags
+	DevBuf hist_pairs, hist_border;                 // fasim_scan_records_site_counts only (it uses the four above too): k_hist_pairs' pair counters and slice borders
 	DevBuf vr_q, vr_dna, vr_alt, vr_wins, vr_probs, vr_tcodes, vr_rows, vr_touch, vr_out;   // fasim_score_variants only: query codes, streamed window letters, ALT letters, windows, problems, target codes, row state of long queries, k_touch's words, k_touch_reduce's words
 	DevBuf vr_items, vr_dirs, vr_cigar, vr_paths;   // fasim_score_variants_aligned only: k_touch_path's items, direction bytes, CIGAR words and results
 	int opt_sim_lds = -1;                        // option "sim_lds": -F re-sweeps always on the L2 variant (0) / the LDS variant where the state fits (1); -1 = by the units in flight
@@ -574,6 +575,29 @@ struct HistReq : ScanProduct {
 	void merge(const BatchCtx& C, const SegTable& T, int64_t b0, int64_t b1, int q) override;
 };
 
+// ---- sites per threshold (fasim_scan_records_site_counts, hist_pairs.hip, engine_site_counts.cpp) -----------
+// One side of a boundary as a HistSide, with the values of the position next to the zone on the interior side of its segment
+// (fasim_site_counts_edge: nb, link).  An empty `v` stands for zeros.
+struct PairSide { int32_t len = 0, link = 0; uint16_t nb[4] = { 0, 0, 0, 0 }; std::vector<uint16_t> v; /* [4][len] */ };
+// The counters of one query and the sides that have no partner yet.  Every side is counted alone when it comes in and the two of a
+// boundary are re-counted as their maximum when they meet: a batch in a call and a shard in a merge are the same thing.
+struct PairBook {
+	int64_t* n[4] = { nullptr, nullptr, nullptr, nullptr }; int64_t* pairs[4] = { nullptr, nullptr, nullptr, nullptr };
+	int64_t positions = 0, npairs = 0;
+	std::map<HistEdgeKey, PairSide> open;
+};
+struct SiteCountsReq : ScanProduct {
+	int64_t step = 0, overlap = 0;               // cutLength - overlapLength, overlapLength
+	std::vector<int64_t> rec_nseg;               // [record]: segments of the whole record
+	std::vector<int32_t> qtop;                   // [query]: largest value the query can reach (the copy back stops there)
+	std::vector<PairBook> book;                  // [query]
+	std::vector<int64_t> units, sat;             // [query]
+	bool merges_empty() const override { return true; }      // (the positions of skipped segments lie in bin 0)
+	const char* needs_scan() const override { return "site counts need the systolic scan kernel"; }
+	int fold(fasim_engine* E, BatchCtx& C, int q) const override;
+	void merge(const BatchCtx& C, const SegTable& T, int64_t b0, int64_t b1, int q) override;
+};
+
 struct BatchCtx {
 	UnitBatch B;
 	// what the products' folds leave of this batch (ScanProduct::fold): `folded` once run_scan_v2 has run them
@@ -581,6 +605,7 @@ struct BatchCtx {
 	TrackTable tab; int track_nchunk = 0;              // class table of the enabled encodings, TRACK_CHUNK slices per segment (batch_encode)
 	std::vector<uint32_t> hist; std::vector<uint16_t> hist_zones; std::vector<uint8_t> hist_sat; std::vector<int32_t> hist_zone;      // fasim_scan_records_hist: k_hist's counters, zones and zone bounds
 	int hist_zstride = 0, hist_top = 0;
+	std::vector<uint32_t> hist_pairs; std::vector<uint16_t> hist_border;      // fasim_scan_records_site_counts (with the four above): k_hist_pairs' pair counters and slice borders
 	std::vector<uint32_t> site_counts; std::vector<SiteRun> site_runs; std::vector<uint8_t> site_sat;      // fasim_scan_records_sites: k_sites' runs
 	std::vector<uint16_t> rowfold; std::vector<uint8_t> row_sat; std::vector<int32_t> row_gfirst;      // fasim_scan_tfo_profile: k_rowfold's groups
 	std::vector<uint16_t> track; std::vector<uint8_t> track_sat;      // fasim_scan_track: k_track's slices
@@ -607,6 +632,26 @@ inline void class_fold_fill(ClassFoldLaunch& L, const fasim_engine* E, const Bat
 {
 	L.colmax16 = E->colmax16.as<uint16_t>(); L.seg_len = E->seg_len.as<int32_t>();
 	L.nseg = C.nseg; L.nenc = C.nenc; L.tstride = C.B.tstride; L.nchunk = C.track_nchunk; L.tab = C.tab; L.sat = sat.as<uint8_t>();
+}
+// The zones of k_hist and k_hist_pairs: head-zone end and tail-zone begin of segment i (length L) of a record of `nseg` segments cut
+// with step = cutLength - overlapLength.  The one place that states which positions two segments share
+inline void hist_zone_bounds(int64_t step, int64_t overlap, int64_t i, int32_t L, int64_t nseg, int32_t* head, int32_t* tail)
+{
+	*head = i > 0 ? (int32_t)std::min<int64_t>(overlap, L) : 0;
+	*tail = i + 1 < nseg ? (int32_t)step : L;      // (a segment with a successor is longer than the step)
+}
+// the zone bounds of the batch's kept segments into C.hist_zone ([nseg][2], what both kernels read); returns the longest zone
+inline int hist_zone_table(BatchCtx& C, int64_t step, int64_t overlap, const std::vector<int64_t>& rec_nseg)
+{
+	C.hist_zone.resize((size_t)C.nseg * 2);
+	int zmax = 0;
+	for (int s = 0; s < C.nseg; s++) {
+		int32_t h, t;
+		hist_zone_bounds(step, overlap, C.sidx[(size_t)s], C.slen[(size_t)s], rec_nseg[(size_t)C.srec[(size_t)s]], &h, &t);
+		C.hist_zone[(size_t)2 * s] = h; C.hist_zone[(size_t)2 * s + 1] = t;
+		zmax = std::max(zmax, std::max(h, C.slen[(size_t)s] - t));
+	}
+	return zmax;
 }
 // a fold's saturation flags, one per unit: ensured and zeroed on the stream ahead of the launch ...
 inline int sat_begin(fasim_engine* E, DevBuf& dev, size_t nu)
@@ -656,6 +701,9 @@ int batch_encode(fasim_engine* E, const char* dna, const SegTable& T, const uint
 // engine_hist.cpp: the request of a call and its results
 bool hist_req_init(HistReq& hr, fasim_hist** out_hists, int nquery, const int32_t* qlens, const int64_t* rec_len, int nrec, const fasim_params& p, bool only);
 int hist_req_finish(fasim_engine* E, HistReq& hr, fasim_hist** out_hists, int nquery);
+// engine_site_counts.cpp: the same for the site counts
+bool site_counts_req_init(SiteCountsReq& sr, fasim_site_counts** outs, int nquery, const int32_t* qlens, const int64_t* rec_len, int nrec, const fasim_params& p, bool only);
+int site_counts_req_finish(fasim_engine* E, SiteCountsReq& sr, fasim_site_counts** outs, int nquery);
 
 // ---- the frame of a call (engine.cpp; the pure part is call_plan.h; DESIGN.md "the frame of a call") ----------------------------------
 // The record set of a call as its entry point got it, resolved: `dna` NULL stands for the resident buffer, and an entry point that

@@ -74,8 +74,7 @@ void side_arrives(HistReq& hr, int q, const HistEdgeKey& key, HistSide&& side, b
 // head-zone end and tail-zone begin of segment i (length L) of a record of `nseg` segments
 inline void zone_bounds(const HistReq& hr, int64_t i, int32_t L, int64_t nseg, int32_t* head, int32_t* tail)
 {
-	*head = i > 0 ? (int32_t)std::min<int64_t>(hr.overlap, L) : 0;
-	*tail = i + 1 < nseg ? (int32_t)hr.step : L;      // (a segment with a successor is longer than the step)
+	hist_zone_bounds(hr.step, hr.overlap, i, L, nseg, head, tail);
 }
 
 } // namespace
@@ -88,14 +87,7 @@ int HistReq::fold(fasim_engine* E, BatchCtx& C, int q) const
 	const HistReq& hr = *this;
 	const int nu = C.B.nunit;
 	int rc; hipError_t he;
-	C.hist_zone.resize((size_t)C.nseg * 2);
-	int zmax = 0;
-	for (int s = 0; s < C.nseg; s++) {
-		int32_t h, t;
-		zone_bounds(hr, C.sidx[(size_t)s], C.slen[(size_t)s], hr.rec_nseg[(size_t)C.srec[(size_t)s]], &h, &t);
-		C.hist_zone[(size_t)2 * s] = h; C.hist_zone[(size_t)2 * s + 1] = t;
-		zmax = std::max(zmax, std::max(h, C.slen[(size_t)s] - t));
-	}
+	const int zmax = hist_zone_table(C, hr.step, hr.overlap, hr.rec_nseg);
 	C.hist_zstride = (zmax + 7) & ~7; C.hist_top = hr.qtop[(size_t)q];
 	const size_t nzone = (size_t)C.nseg * 8 * (size_t)C.hist_zstride;
 	const size_t ntop = (size_t)std::min(C.hist_top, HIST_BINS - 1) + 1;

@@ -39,11 +39,12 @@ int panel_batch(fasim_engine* E, const PanelCall& P, BatchCtx& C, int64_t b0, in
 	return FASIM_OK;
 }
 
-// fasim_scan_oligos and fasim_scan_oligos_hist: sites, tracks and histograms (out_hists[q]) are each wanted iff their output is given;
+// fasim_scan_oligos, fasim_scan_oligos_hist and fasim_scan_oligos_site_counts: sites, tracks, histograms (out_hists[q]) and site counts
+// (out_counts[q]) are each wanted iff their output is given;
 // `rs` hands the resolved record set to the second phase of fasim_scan_oligos_aligned
 int scan_oligos_core(fasim_engine* E, const char* const* oligos, const int32_t* lens, int32_t nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
-	int32_t min_value, int32_t max_gap, fasim_sites** out_sites, int32_t bin, fasim_track** out_tracks, fasim_hist** out_hists, fasim_scan_stats* totals, RecordSet& rs)
+	int32_t min_value, int32_t max_gap, fasim_sites** out_sites, int32_t bin, fasim_track** out_tracks, fasim_hist** out_hists, fasim_site_counts** out_counts, fasim_scan_stats* totals, RecordSet& rs)
 {
 	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
 	if (nq < 1) return fail(E, FASIM_E_ARG, "a panel needs at least one oligo (nq = %d)", nq);
@@ -53,7 +54,7 @@ int scan_oligos_core(fasim_engine* E, const char* const* oligos, const int32_t* 
 		if (lens[q] > FASIM_MAX_OLIGO)
 			return fail(E, FASIM_E_ARG, "oligo %d has %d nt, a panel takes oligos of at most %d nt: scan longer queries with fasim_scan_records_sites", q, lens[q], FASIM_MAX_OLIGO);
 	}
-	if (!out_sites && !out_tracks && !out_hists) return fail(E, FASIM_E_ARG, "neither sites nor tracks are wanted");
+	if (!out_sites && !out_tracks && !out_hists && !out_counts) return fail(E, FASIM_E_ARG, "neither sites nor tracks are wanted");
 	if (out_sites && (min_value < 1 || min_value > 16383)) return fail(E, FASIM_E_ARG, "oligos: min_value %d lies outside [1, 16383]", min_value);
 	if (out_sites && max_gap < 0) return fail(E, FASIM_E_ARG, "oligos: max_gap %d is negative", max_gap);
 	if (out_tracks && bin < 1) return fail(E, FASIM_E_ARG, "oligos: track bin width %d: must be at least 1", bin);
@@ -65,12 +66,15 @@ int scan_oligos_core(fasim_engine* E, const char* const* oligos, const int32_t* 
 	if (pp->classicSim) return fail(E, FASIM_E_UNSUPPORTED, "oligo panels are not available with classicSim (-F): that path has no stage-2 column maxima");
 	if (out_hists && 2 * (int64_t)pp->overlapLength > (int64_t)pp->cutLength)
 		return fail(E, FASIM_E_UNSUPPORTED, "histograms of the potential need overlapLength (%d) of at most half of cutLength (%d): a base would lie in three segments", pp->overlapLength, pp->cutLength);
+	if (out_counts && 2 * (int64_t)pp->overlapLength > (int64_t)pp->cutLength)
+		return fail(E, FASIM_E_UNSUPPORTED, "site counts need overlapLength (%d) of at most half of cutLength (%d): a base would lie in three segments", pp->overlapLength, pp->cutLength);
 	dna = rs.host(E);
 	const fasim_params p = *pp;
 	const size_t nout = (size_t)nq * (size_t)nrec;
 	if (out_sites) for (size_t o = 0; o < nout; o++) out_sites[o] = nullptr;
 	if (out_tracks) for (size_t o = 0; o < nout; o++) out_tracks[o] = nullptr;
 	if (out_hists) for (int q = 0; q < nq; q++) out_hists[q] = nullptr;
+	if (out_counts) for (int q = 0; q < nq; q++) out_counts[q] = nullptr;
 	HIPOK(hipSetDevice(E->device));
 	const double t_begin = now_s();
 	AffinityScope numa(E->device, E->opt_numa != 0);
@@ -91,8 +95,9 @@ int scan_oligos_core(fasim_engine* E, const char* const* oligos, const int32_t* 
 	for (int q = 0; q < nq; q++) { msum += lens[q]; for (int i = 0; i < lens[q]; i++) P.codes[(size_t)q * FASIM_MAX_OLIGO + i] = code2(oligos[q][i]); }
 	SitesReq sr; TrackReq tr;
 	if (out_sites) { sites_req_init(sr, min_value, max_gap, true, nq, nrec); P.folds.push_back(&sr); }
-	HistReq hr;
+	HistReq hr; SiteCountsReq cr;
 	auto drop = [&]() {
+		if (out_counts) for (int q = 0; q < nq; q++) { fasim_site_counts_free(out_counts[q]); out_counts[q] = nullptr; }
 		if (out_hists) for (int q = 0; q < nq; q++) { fasim_hist_free(out_hists[q]); out_hists[q] = nullptr; }
 		sites_drop(out_sites, nout);
 		tracks_drop(out_tracks, nout);
@@ -107,6 +112,12 @@ int scan_oligos_core(fasim_engine* E, const char* const* oligos, const int32_t* 
 		try { ok = hist_req_init(hr, out_hists, nq, lens, rec_len, nrec, p, true); } catch (const std::bad_alloc&) { ok = false; }
 		if (!ok) { for (int q = 0; q < nq; q++) out_hists[q] = nullptr; drop(); return fail(E, FASIM_E_NOMEM, "out of memory"); }
 		P.folds.push_back(&hr); P.merges.push_back(&hr);
+	}
+	if (out_counts) {
+		bool ok = false;
+		try { ok = site_counts_req_init(cr, out_counts, nq, lens, rec_len, nrec, p, true); } catch (const std::bad_alloc&) { ok = false; }
+		if (!ok) { for (int q = 0; q < nq; q++) out_counts[q] = nullptr; drop(); return fail(E, FASIM_E_NOMEM, "out of memory"); }
+		P.folds.push_back(&cr); P.merges.push_back(&cr);
 	}
 	if (out_sites) P.merges.push_back(&sr);
 	if (out_tracks) P.merges.push_back(&tr);
@@ -181,6 +192,10 @@ int scan_oligos_core(fasim_engine* E, const char* const* oligos, const int32_t* 
 		try { rc = hist_req_finish(E, hr, out_hists, nq); } catch (const std::bad_alloc&) { rc = fail(E, FASIM_E_NOMEM, "out of memory"); }
 		if (rc) { drop(); return rc; }
 	}
+	if (out_counts) {
+		try { rc = site_counts_req_finish(E, cr, out_counts, nq); } catch (const std::bad_alloc&) { rc = fail(E, FASIM_E_NOMEM, "out of memory"); }
+		if (rc) { drop(); return rc; }
+	}
 	if (totals) {
 		const double t_total = now_s() - t_begin;
 		for (int q = 0; q < nq; q++) {
@@ -204,7 +219,7 @@ int fasim_scan_oligos(fasim_engine* E, const char* const* oligos, const int32_t*
 	int32_t min_value, int32_t max_gap, fasim_sites** out_sites, int32_t bin, fasim_track** out_tracks, fasim_scan_stats* totals)
 {
 	RecordSet rs;
-	return scan_oligos_core(E, oligos, lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, min_value, max_gap, out_sites, bin, out_tracks, nullptr, totals, rs);
+	return scan_oligos_core(E, oligos, lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, min_value, max_gap, out_sites, bin, out_tracks, nullptr, nullptr, totals, rs);
 }
 
 int fasim_scan_oligos_aligned(fasim_engine* E, const char* const* oligos, const int32_t* lens, int32_t nq, const char* dna,
@@ -215,7 +230,7 @@ int fasim_scan_oligos_aligned(fasim_engine* E, const char* const* oligos, const 
 	if (!out_sites || !out_hits) return fail(E, FASIM_E_ARG, "bad arguments");
 	// first phase: the sites call itself, refusals included (its sites and totals are this call's)
 	RecordSet rs;
-	int rc = scan_oligos_core(E, oligos, lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, min_value, max_gap, out_sites, 1, nullptr, nullptr, totals, rs);
+	int rc = scan_oligos_core(E, oligos, lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, min_value, max_gap, out_sites, 1, nullptr, nullptr, nullptr, totals, rs);
 	if (rc) return rc;
 	const size_t nout = (size_t)nq * (size_t)nrec;
 	for (size_t o = 0; o < nout; o++) out_hits[o] = nullptr;
@@ -244,7 +259,17 @@ int fasim_scan_oligos_hist(fasim_engine* E, const char* const* oligos, const int
 	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
 	if (!out_hists) return fail(E, FASIM_E_ARG, "bad arguments");
 	RecordSet rs;
-	return scan_oligos_core(E, oligos, lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, 1, 0, nullptr, 1, nullptr, out_hists, totals, rs);
+	return scan_oligos_core(E, oligos, lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, 1, 0, nullptr, 1, nullptr, out_hists, nullptr, totals, rs);
+}
+
+int fasim_scan_oligos_site_counts(fasim_engine* E, const char* const* oligos, const int32_t* lens, int32_t nq, const char* dna,
+	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
+	fasim_site_counts** out_counts, fasim_scan_stats* totals)
+{
+	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
+	if (!out_counts) return fail(E, FASIM_E_ARG, "bad arguments");
+	RecordSet rs;
+	return scan_oligos_core(E, oligos, lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, 1, 0, nullptr, 1, nullptr, nullptr, out_counts, totals, rs);
 }
 
 int fasim_oligo_panel_tsv(const char* const* names, const int32_t* lens, int32_t nq, const fasim_sites* const* sites, int32_t nrec,

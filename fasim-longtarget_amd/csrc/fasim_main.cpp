@@ -56,6 +56,13 @@
 //                           per oligo and nothing else.  --potential-hist-only writes nothing else and runs no stage 3.  Exit status 2,
 //                           nothing written: with -F, --accumulate-records, --track, --screen, --tfo-profile or --sites, --hist-* or
 //                           --potential-hist-only without --potential-hist, K < 0, Q outside (0, 1], -o above half of -c
+//     --hist-sites          with --potential-hist: the sites per threshold too (fasim_scan_records_site_counts).
+//                           Beside the unchanged hist table <stem>-TFOsitecounts (set mode <O>/<lnc>-<f1 stem>.sitecounts.tsv, with
+//                           --oligos one per oligo): per value the number of sites --sites V --sites-gap 0 would report, per class,
+//                           with the controls' and the false discovery rate per site.  --hist-shuffle mono|di (default mono) draws
+//                           the controls of both tables with fasim_shuffle_query or, keeping the dinucleotide counts, with
+//                           fasim_shuffle_query_dinuc.  Exit status 2, nothing written: either without --potential-hist, a value
+//                           other than mono / di
 //     --sites-align         with --sites V: every site with its hit (fasim_scan_records_sites_aligned), the local
 //                           alignment behind the site's peak: beside the sites file <stem>-TFOsites-<V>-aligned (set mode:
 //                           <O>/<lnc>-<f1 stem>.sites-<V>.aligned.tsv, the record's name as a last column), a `# fasim site hits` line,
@@ -255,7 +262,9 @@ static int g_out_failed = 0;
 struct TrackOpt { int bin = 0, min_value = 1; bool only = false, peaks = false, no_stage3 = false, tfo = false, tfo_only = false; int sites = 0, sites_gap = 0; bool sites_only = false, sites_align = false, oligos = false, oligo_hits = false;
 	bool hits() const { return sites_align || oligo_hits; }      // the sites' hits are wanted (--sites-align, or --oligo-hits of a panel)
 	// --potential-hist: the histogram, K controls per lncRNA under a seed (hist_ctl: their sequences, lncRNA after lncRNA), the FDR bound
-	bool hist = false, hist_only = false; int hist_controls = 0; uint64_t hist_seed = 0; double hist_fdr = 0.05; const std::vector<std::string>* hist_ctl = nullptr; };
+	bool hist = false, hist_only = false; int hist_controls = 0; uint64_t hist_seed = 0; double hist_fdr = 0.05; const std::vector<std::string>* hist_ctl = nullptr;
+	// --hist-sites: site counts in the place of the histograms (their n[][] is the histogram); --hist-shuffle di: dinucleotide controls
+	bool hist_sites = false, hist_dinuc = false; };
 
 // acc += part by fasim_hist_merge (different groups of records: nothing pairs); takes `part` over
 static int hist_fold(fasim_hist*& acc, fasim_hist* part)
@@ -267,6 +276,20 @@ static int hist_fold(fasim_hist*& acc, fasim_hist* part)
 	fasim_hist_free(part);
 	if (rc != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
 	fasim_hist_free(acc);
+	acc = sum;
+	return 0;
+}
+
+// the same for site counts (--hist-sites)
+static int counts_fold(fasim_site_counts*& acc, fasim_site_counts* part)
+{
+	if (!acc) { acc = part; return 0; }
+	const fasim_site_counts* two[2] = { acc, part };
+	fasim_site_counts* sum = nullptr;
+	const int rc = fasim_site_counts_merge(two, 2, &sum);
+	fasim_site_counts_free(part);
+	if (rc != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
+	fasim_site_counts_free(acc);
 	acc = sum;
 	return 0;
 }
@@ -364,17 +387,20 @@ static int scan_group(const std::vector<fasim_engine*>& engines, const std::vect
 	const std::vector<int64_t>& off, const std::vector<int64_t>& len, const fasim_params& p, std::vector<std::vector<fasim_result*>>& out,
 	const TrackOpt& trk, std::vector<std::vector<fasim_track*>>& tracks, std::vector<fasim_peak>& peaks, std::vector<fasim_tfo_profile*>* profs = nullptr,
 	std::vector<std::vector<fasim_sites*>>* sites = nullptr, std::vector<std::vector<fasim_site_hits*>>* hits = nullptr,
-	std::vector<fasim_hist*>* hists = nullptr)
+	std::vector<fasim_hist*>* hists = nullptr, std::vector<fasim_site_counts*>* counts = nullptr)
 {
 	const int nd = (int)engines.size(), nq = (int)rnas.size(), nrec = (int)off.size();
 	// --potential-hist: one histogram per lncRNA over the group, then those of its controls ([nq] + [nq * K], as hist_ctl)
-	const int nctl = hists && trk.hist_ctl ? (int)trk.hist_ctl->size() : 0;
+	// (--hist-sites: `counts` in the place of `hists`, the same queries)
+	const int nctl = (hists || counts) && trk.hist_ctl ? (int)trk.hist_ctl->size() : 0;
 	std::vector<const char*> hq; std::vector<int32_t> hl;
-	if (hists) {
+	if (hists || counts) {
 		for (int q = 0; q < nq; q++) { hq.push_back(rnas[(size_t)q].seq.data()); hl.push_back((int32_t)rnas[(size_t)q].seq.size()); }
 		for (int k = 0; k < nctl; k++) { hq.push_back((*trk.hist_ctl)[(size_t)k].data()); hl.push_back((int32_t)(*trk.hist_ctl)[(size_t)k].size()); }
-		hists->assign((size_t)(nq + nctl), nullptr);
+		if (hists) hists->assign((size_t)(nq + nctl), nullptr);
+		if (counts) counts->assign((size_t)(nq + nctl), nullptr);
 	}
+	std::vector<std::vector<fasim_site_counts*>> cpart((size_t)nd, std::vector<fasim_site_counts*>(counts ? (size_t)(nq + nctl) : 0, nullptr));
 	std::vector<std::vector<fasim_hist*>> gpart((size_t)nd, std::vector<fasim_hist*>(hists ? (size_t)(nq + nctl) : 0, nullptr));
 	std::vector<const char*> qp((size_t)nq); std::vector<int32_t> ql((size_t)nq);
 	for (int q = 0; q < nq; q++) { qp[(size_t)q] = rnas[(size_t)q].seq.data(); ql[(size_t)q] = (int32_t)rnas[(size_t)q].seq.size(); }
@@ -401,7 +427,20 @@ static int scan_group(const std::vector<fasim_engine*>& engines, const std::vect
 	auto run = [&](int d) {
 		const int64_t base = nseg / nd, rem = nseg % nd;
 		const int64_t first = d * base + std::min<int64_t>(d, rem), count = base + (d < rem ? 1 : 0);
-		if (hists && trk.oligos)
+		if (counts && trk.oligos)
+			rc[(size_t)d] = fasim_scan_oligos_site_counts(engines[(size_t)d], hq.data(), hl.data(), nq + nctl, dna.data(), off.data(), len.data(), nrec, first, count, &p,
+				cpart[(size_t)d].data(), nullptr);
+		else if (counts && no_res)
+			rc[(size_t)d] = fasim_scan_records_site_counts(engines[(size_t)d], hq.data(), hl.data(), nq + nctl, dna.data(), off.data(), len.data(), nrec, first, count, &p,
+				nullptr, cpart[(size_t)d].data(), nullptr);
+		else if (counts) {
+			rc[(size_t)d] = fasim_scan_records_site_counts(engines[(size_t)d], qp.data(), ql.data(), nq, dna.data(), off.data(), len.data(), nrec, first, count, &p,
+				part[(size_t)d].data(), cpart[(size_t)d].data(), nullptr);
+			if (rc[(size_t)d] == FASIM_OK && nctl)
+				rc[(size_t)d] = fasim_scan_records_site_counts(engines[(size_t)d], hq.data() + nq, hl.data() + nq, nctl, dna.data(), off.data(), len.data(), nrec, first, count, &p,
+					nullptr, cpart[(size_t)d].data() + nq, nullptr);
+		}
+		else if (hists && trk.oligos)
 			rc[(size_t)d] = fasim_scan_oligos_hist(engines[(size_t)d], hq.data(), hl.data(), nq + nctl, dna.data(), off.data(), len.data(), nrec, first, count, &p,
 				gpart[(size_t)d].data(), nullptr);
 		else if (hists && no_res)
@@ -489,6 +528,14 @@ static int scan_group(const std::vector<fasim_engine*>& engines, const std::vect
 	}
 	for (auto& v : gpart) for (fasim_hist* x : v) fasim_hist_free(x);
 	if (bad && hists) for (fasim_hist*& x : *hists) { fasim_hist_free(x); x = nullptr; }
+	for (size_t k = 0; counts && !bad && k < counts->size(); k++) {
+		if (nd == 1) { (*counts)[k] = cpart[0][k]; cpart[0][k] = nullptr; continue; }
+		std::vector<const fasim_site_counts*> cp((size_t)nd);
+		for (int d = 0; d < nd; d++) cp[(size_t)d] = cpart[(size_t)d][k];
+		if (fasim_site_counts_merge(cp.data(), nd, &(*counts)[k]) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); bad = 1; }
+	}
+	for (auto& v : cpart) for (fasim_site_counts* x : v) fasim_site_counts_free(x);
+	if (bad && counts) for (fasim_site_counts*& x : *counts) { fasim_site_counts_free(x); x = nullptr; }
 	// site lists of the device shards: union of the intervals, joined again
 	for (int q = 0; q < nq && !bad && sites; q++) for (int r = 0; r < nrec && !bad; r++) {
 		const size_t k = (size_t)q * nrec + r;
@@ -705,7 +752,7 @@ int main(int argc, char* const* argv)
 	bool devices_given = false, flank_given = false, variant_hits = false; int variant_flank = 300;
 	std::vector<int> devices(1, 0);
 	bool stats = false, all_records = false, accumulate = false, upper = false, track = false, screen = false, screen_only = false;
-	bool sites = false, sites_gap_given = false, hist_arg_given = false, hist_arg_bad = false;
+	bool sites = false, sites_gap_given = false, hist_arg_given = false, hist_arg_bad = false, hist_shuffle_bad = false;
 	TrackOpt trk;
 	int tail_flags = 0;
 	const char* optstring = "f:s:r:O:c:m:t:i:S:z:Y:Z:h:C:D:E:o:y:Fd";
@@ -722,6 +769,7 @@ int main(int argc, char* const* argv)
 		{ "sites", required_argument, NULL, 1016 }, { "sites-gap", required_argument, NULL, 1017 }, { "sites-only", no_argument, NULL, 1018 }, { "sites-align", no_argument, NULL, 1019 }, { "oligos", no_argument, NULL, 1020 }, { "oligo-hits", no_argument, NULL, 1026 },
 		{ "potential-hist", no_argument, NULL, 1021 }, { "hist-controls", required_argument, NULL, 1022 }, { "hist-seed", required_argument, NULL, 1023 },
 		{ "hist-fdr", required_argument, NULL, 1024 }, { "potential-hist-only", no_argument, NULL, 1025 },
+		{ "hist-sites", no_argument, NULL, 1030 }, { "hist-shuffle", required_argument, NULL, 1031 },
 		{ "variants", required_argument, NULL, 1027 }, { "variant-flank", required_argument, NULL, 1028 },
 		{ "variant-hits", no_argument, NULL, 1029 }, { 0, 0, 0, 0 } };
 	int opt;
@@ -775,7 +823,9 @@ int main(int argc, char* const* argv)
 		case 1023: { hist_arg_given = true; char* end = nullptr; errno = 0; trk.hist_seed = strtoull(optarg, &end, 10); if (end == optarg || *end != '\0' || errno == ERANGE || optarg[0] == '-') hist_arg_bad = true; break; }
 		case 1024: { hist_arg_given = true; char* end = nullptr; trk.hist_fdr = strtod(optarg, &end); if (end == optarg || *end != '\0') trk.hist_fdr = -1.0; break; }
 		case 1025: trk.hist_only = true; break;
-		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only] [--sites-align] [--oligos [--oligo-hits]]] [--potential-hist [--hist-controls K] [--hist-seed S] [--hist-fdr Q] [--potential-hist-only]] [--variants FILE.vcf [--variant-flank F] [--variant-hits]]\n"); return 2;
+		case 1030: hist_arg_given = true; trk.hist_sites = true; break;
+		case 1031: hist_arg_given = true; if (!strcmp(optarg, "di")) trk.hist_dinuc = true; else if (strcmp(optarg, "mono")) hist_shuffle_bad = true; break;
+		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only] [--sites-align] [--oligos [--oligo-hits]]] [--potential-hist [--hist-controls K] [--hist-seed S] [--hist-fdr Q] [--potential-hist-only] [--hist-sites] [--hist-shuffle mono|di]] [--variants FILE.vcf [--variant-flank F] [--variant-hits]]\n"); return 2;
 		}
 	}
 	if (all_records && accumulate) { fprintf(stderr, "fasim: --all-records and --accumulate-records exclude each other\n"); return 2; }
@@ -793,7 +843,8 @@ int main(int argc, char* const* argv)
 	if (sites && (trk.sites < 1 || trk.sites > 16383)) { fprintf(stderr, "fasim: --sites needs an integer in [1, 16383]\n"); return 2; }
 	if (sites && trk.sites_gap < 0) { fprintf(stderr, "fasim: --sites-gap needs an integer of at least 0\n"); return 2; }
 	if (sites && (p.classicSim || accumulate || track || screen || trk.tfo)) { fprintf(stderr, "fasim: --sites is not available with -F, --accumulate-records, --track, --screen or --tfo-profile\n"); return 2; }
-	if ((hist_arg_given || trk.hist_only) && !trk.hist) { fprintf(stderr, "fasim: --hist-controls, --hist-seed, --hist-fdr and --potential-hist-only need --potential-hist\n"); return 2; }
+	if ((hist_arg_given || trk.hist_only) && !trk.hist) { fprintf(stderr, "fasim: --hist-controls, --hist-seed, --hist-fdr, --hist-sites, --hist-shuffle and --potential-hist-only need --potential-hist\n"); return 2; }
+	if (hist_shuffle_bad) { fprintf(stderr, "fasim: --hist-shuffle needs mono or di\n"); return 2; }
 	if (trk.hist && (p.classicSim || accumulate || track || screen || trk.tfo || sites)) { fprintf(stderr, "fasim: --potential-hist is not available with -F, --accumulate-records, --track, --screen, --tfo-profile or --sites\n"); return 2; }
 	if (trk.hist && trk.hist_controls < 0) { fprintf(stderr, "fasim: --hist-controls needs an integer of at least 0\n"); return 2; }
 	if (trk.hist && hist_arg_bad) { fprintf(stderr, "fasim: --hist-seed needs an unsigned integer\n"); return 2; }
@@ -927,13 +978,14 @@ int main(int argc, char* const* argv)
 	if (trk.hist) {
 		for (const Rna& r : rnas) for (int k = 1; k <= trk.hist_controls; k++) {
 			std::string c(r.seq.size(), 'N');
-			if (fasim_shuffle_query(r.seq.data(), (int32_t)r.seq.size(), trk.hist_seed, k, &c[0]) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
+			if ((trk.hist_dinuc ? fasim_shuffle_query_dinuc : fasim_shuffle_query)(r.seq.data(), (int32_t)r.seq.size(), trk.hist_seed, k, &c[0]) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
 			hist_ctl.push_back(std::move(c));
 		}
 		trk.hist_ctl = &hist_ctl;
 	}
 	const bool hist_set = trk.hist && (all_records || regions || trk.oligos);
-	std::vector<fasim_hist*> hist_acc(hist_set ? rnas.size() + hist_ctl.size() : 0, nullptr);
+	std::vector<fasim_hist*> hist_acc(hist_set && !trk.hist_sites ? rnas.size() + hist_ctl.size() : 0, nullptr);
+	std::vector<fasim_site_counts*> counts_acc(hist_set && trk.hist_sites ? rnas.size() + hist_ctl.size() : 0, nullptr);
 	// h: [lncRNAs] + [lncRNAs x K controls]; NULL entries (nothing scanned) stand for empty histograms
 	auto write_hist = [&](fasim_hist* const* h, size_t q, const std::string& path) -> int {
 		std::vector<int64_t> zeros(FASIM_HIST_BINS, 0);
@@ -948,10 +1000,40 @@ int main(int argc, char* const* argv)
 		fasim_free(text);
 		return bad;
 	};
+	// --hist-sites: s as h above.  The hist table from the counts' n[][] (what --potential-hist alone writes), then the site counts
+	auto write_counts = [&](fasim_site_counts* const* s, size_t q, const std::string& hist_path, const std::string& counts_path) -> int {
+		std::vector<int64_t> zeros(FASIM_HIST_BINS, 0);
+		fasim_site_counts z; memset(&z, 0, sizeof z);
+		for (int c = 0; c < FASIM_TRACK_CLASSES; c++) { z.n[c] = zeros.data(); z.pairs[c] = zeros.data(); }
+		const size_t K = (size_t)trk.hist_controls;
+		std::vector<const fasim_site_counts*> all(1 + K);
+		all[0] = s[q] ? s[q] : &z;
+		for (size_t k = 0; k < K; k++) { const fasim_site_counts* x = s[rnas.size() + q * K + k]; all[1 + k] = x ? x : &z; }
+		std::vector<fasim_hist> view(1 + K);
+		std::vector<const fasim_hist*> vp(1 + K);
+		for (size_t k = 0; k <= K; k++) {
+			memset(&view[k], 0, sizeof view[k]);
+			for (int c = 0; c < FASIM_TRACK_CLASSES; c++) view[k].n[c] = all[k]->n[c];
+			view[k].positions = all[k]->positions; view[k].units = all[k]->units; view[k].saturated_units = all[k]->saturated_units;
+			vp[k] = &view[k];
+		}
+		char* text = nullptr; int64_t len = 0;
+		if (fasim_hist_tsv(vp[0], vp.data() + 1, (int32_t)K, trk.hist_seed, trk.hist_fdr, rnas[q].name.c_str(), &text, &len) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
+		int bad = write_file(hist_path, text, len);
+		fasim_free(text);
+		if (fasim_site_counts_tsv(all[0], all.data() + 1, (int32_t)K, trk.hist_seed, trk.hist_dinuc ? 1 : 0, trk.hist_fdr, rnas[q].name.c_str(), &text, &len) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
+		bad |= write_file(counts_path, text, len);
+		fasim_free(text);
+		return bad;
+	};
 	auto write_hist_set = [&]() -> int {
 		int bad = 0;
-		for (size_t q = 0; q < rnas.size(); q++) bad |= write_hist(hist_acc.data(), q, outdir + "/" + rnas[q].name + "-" + base + ".hist.tsv");
+		for (size_t q = 0; q < rnas.size(); q++) {
+			const std::string stem = outdir + "/" + rnas[q].name + "-" + base;
+			bad |= trk.hist_sites ? write_counts(counts_acc.data(), q, stem + ".hist.tsv", stem + ".sitecounts.tsv") : write_hist(hist_acc.data(), q, stem + ".hist.tsv");
+		}
 		for (fasim_hist*& x : hist_acc) { fasim_hist_free(x); x = nullptr; }
+		for (fasim_site_counts*& x : counts_acc) { fasim_site_counts_free(x); x = nullptr; }
 		return bad;
 	};
 	// --oligos: the site lists of every oligo and record are kept for the panel table, <O>/<f2 stem>-<f1 stem>.oligos-<V>.tsv
@@ -1145,9 +1227,20 @@ int main(int argc, char* const* argv)
 			std::vector<std::vector<fasim_sites*>> gsites;
 			std::vector<std::vector<fasim_site_hits*>> ghits;
 			std::vector<fasim_hist*> ghist;
+			std::vector<fasim_site_counts*> gcounts;
 			if (scan_group(engines, rnas, gdna, goff, glen, p, res, trk, gtracks, gpeaks, trk.tfo ? &gprof : nullptr, sites ? &gsites : nullptr,
-				sites && trk.hits() ? &ghits : nullptr, trk.hist ? &ghist : nullptr)) return 1;
-			if (trk.hist && hist_set) { for (size_t k = 0; k < ghist.size(); k++) { fasim_hist* t = ghist[k]; ghist[k] = nullptr; if (hist_fold(hist_acc[k], t)) return 1; } }
+				sites && trk.hits() ? &ghits : nullptr, trk.hist && !trk.hist_sites ? &ghist : nullptr, trk.hist_sites ? &gcounts : nullptr)) return 1;
+			if (trk.hist_sites && hist_set) { for (size_t k = 0; k < gcounts.size(); k++) { fasim_site_counts* t = gcounts[k]; gcounts[k] = nullptr; if (counts_fold(counts_acc[k], t)) return 1; } }
+			else if (trk.hist_sites) {
+				int bad = 0;
+				for (size_t q = 0; q < rnas.size(); q++) {
+					const std::string stem = outdir + "/" + group[0].species + "-" + rnas[q].name + "-" + base;
+					bad |= write_counts(gcounts.data(), q, stem + "-TFOhist", stem + "-TFOsitecounts");
+				}
+				for (fasim_site_counts* x : gcounts) fasim_site_counts_free(x);
+				if (bad) return 1;
+			}
+			else if (trk.hist && hist_set) { for (size_t k = 0; k < ghist.size(); k++) { fasim_hist* t = ghist[k]; ghist[k] = nullptr; if (hist_fold(hist_acc[k], t)) return 1; } }
 			else if (trk.hist) {
 				// a plain run: <stem>-TFOhist next to -TFOsorted
 				int bad = 0;

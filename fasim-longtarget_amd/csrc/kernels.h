@@ -176,6 +176,19 @@ struct HistLaunch : ClassFoldLaunch {
 };
 static_assert(std::is_trivially_copyable<TrackLaunch>::value && std::is_trivially_copyable<SitesLaunch>::value && std::is_trivially_copyable<HistLaunch>::value, "kernel arguments");
 hipError_t launch_hist(const HistLaunch& L, hipStream_t st);
+// k_hist_pairs: k_hist's counts and, beside them, pairs[class][min(P[x - 1], P[x])] for every pair of
+// neighbouring positions that lie outside the zones and in one slice.  Two LDS histograms of HIST_PAIR_LDS_BINS values each.
+// The zones grow by one position on their interior side: the head zone of segment s is [0, zone[2 s]] (slot = the position), its
+// tail zone [zone[2 s + 1] - 1, n) (slot = the position - (zone[2 s + 1] - 1)), so zstride > the longest zone; both are written
+// whether the segment has such a neighbour or not.  border[s][chunk][first 0 / last 1][class] is the potential at the first and
+// last position of every slice that has positions: the host counts the pairs across the slice borders and the zone borders.
+constexpr int HIST_PAIR_LDS_BINS = 512;
+struct HistPairsLaunch : HistLaunch {
+	uint32_t* pairs;            // [4][HIST_BINS], zeroed by the caller
+	uint16_t* border;           // [nseg][nchunk][2][4]
+};
+static_assert(std::is_trivially_copyable<HistPairsLaunch>::value, "kernel arguments");
+hipError_t launch_hist_pairs(const HistPairsLaunch& L, hipStream_t st);
 
 // ---- scan_short.hip: column maxima of a short oligo ----------------------------------------------------
 constexpr int SCAN_SHORT_MAX = 112;        // longest oligo k_scan_short takes (FASIM_MAX_OLIGO)

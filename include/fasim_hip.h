@@ -567,6 +567,75 @@ int32_t fasim_hist_threshold(const fasim_hist* real, const fasim_hist* const* co
 int  fasim_hist_tsv(const fasim_hist* real, const fasim_hist* const* controls, int32_t ncontrols, uint64_t seed, double fdr, const char* rna_name,
                     char** text, int64_t* text_len);
 
+/* ---- sites per threshold, with dinucleotide controls (csrc/hist_pairs.hip) --------------------------------- */
+/* How many sites a record set has at every threshold.  Beside fasim_hist's n[c][v], pairs[c][w] is the number of pairs (x - 1, x) of
+ * neighbouring covered positions of ONE record with min(P_r[c][x - 1], P_r[c][x]) == w, w in [0, 16383]; pairs never span two
+ * records.  The number of maximal runs of positions with P >= v, which is the number of class-c sites that fasim_scan_records_sites
+ * reports over the set with min_value v and max_gap 0, is
+ *     sites[c][v] = the sum over w >= v of (n[c][w] - pairs[c][w]),   v >= 1,
+ * since the runs of a threshold number its positions minus its adjacent pairs.  It is not monotone in v (a site can split as v
+ * rises), hence two histograms.  `npairs` is the sum of pairs[c][.] for every c; for an unsharded call that is the total length of
+ * the records minus their number.  Overlaps, skipped segments, saturation, units and the meaning of PENDING are fasim_hist's.  A
+ * pending edge carries, beside the zone values, `nb`: the values of the range at the position next to the zone on the side of the
+ * segment's interior (before the zone for side 0, after it for side 1), and `link`: 0 there is no such position (the record ends
+ * with the zone), 1 it lies in one segment only, 2 it is the first (last) position of the segment's other zone, whose values change
+ * when that boundary is merged (2 * overlapLength == cutLength only).  A zone of length 0 (overlapLength 0) still has its two nb. */
+typedef struct fasim_site_counts_edge {
+	int32_t record, side;                        /* as fasim_hist_edge                                                      */
+	int64_t boundary;
+	int32_t len, link;
+	uint16_t nb[FASIM_TRACK_CLASSES];
+	uint16_t* v;                                 /* [4][len]                                                                */
+} fasim_site_counts_edge;
+typedef struct fasim_site_counts {
+	int64_t* n[FASIM_TRACK_CLASSES];             /* [FASIM_HIST_BINS]: fasim_hist's                                         */
+	int64_t* pairs[FASIM_TRACK_CLASSES];         /* [FASIM_HIST_BINS]                                                       */
+	int64_t positions, npairs;
+	int64_t units, saturated_units;              /* as fasim_track                                                          */
+	int64_t npending; fasim_site_counts_edge* pending;   /* ordered by (record, boundary, side)                             */
+} fasim_site_counts;
+/* fasim_scan_records_hist with site counts in the place of the histograms: the same arguments and refusals (out_counts == NULL:
+ * FASIM_E_ARG; 2 * overlapLength > cutLength: FASIM_E_UNSUPPORTED; queries below 113 nt), the same meaning of out_results and
+ * totals, the same independence of batches, workers, shards after the merge, dp_f16 and resident or streamed DNA.  n[][] is what
+ * fasim_scan_records_hist counts.  Free each with fasim_site_counts_free. */
+int  fasim_scan_records_site_counts(fasim_engine* e, const char* const* rnas, const int32_t* rna_lens, int32_t nq,
+                                    const char* dna, const int64_t* rec_off, const int64_t* rec_len, int32_t nrec,
+                                    int64_t seg_first, int64_t seg_count, const fasim_params* p,
+                                    fasim_result** out_results /* [nq * nrec] or NULL: no stage 3 */,
+                                    fasim_site_counts** out_counts /* [nq] */, fasim_scan_stats* totals /* [nq], may be NULL */);
+/* The same for a panel of oligos: the arguments and refusals of fasim_scan_oligos_hist. */
+int  fasim_scan_oligos_site_counts(fasim_engine* e, const char* const* oligos, const int32_t* lens, int32_t nq,
+                                   const char* dna, const int64_t* rec_off, const int64_t* rec_len, int32_t nrec,
+                                   int64_t seg_first, int64_t seg_count, const fasim_params* p,
+                                   fasim_site_counts** out_counts /* [nq] */, fasim_scan_stats* totals /* [nq], may be NULL */);
+/* Shards of ONE record set and one query (disjoint segment ranges), as fasim_hist_merge: everything is summed; where both sides of a
+ * boundary are pending, the positions of the zone and the pairs of the chain nb(side 0), zone, nb(side 1) that each side counted
+ * alone are taken out and those of the element-wise maximum are counted instead, the pair that straddles the far border of the zone
+ * included.  Unpaired edges stay pending.  Associative and commutative; the merge of all shards is the unsharded result with
+ * nothing pending.  An edge that is pending twice, or two sides of different length, are refused (FASIM_E_ARG). */
+int  fasim_site_counts_merge(const fasim_site_counts* const* parts, int32_t nparts, fasim_site_counts** out);
+void fasim_site_counts_free(fasim_site_counts* s);
+/* Control k (k >= 1) of a query under `seed` that keeps every dinucleotide count, the first and the last byte (Altschul-Erickson):
+ * a random Euler path through the graph of the query's bytes as given (case and U kept).  The splitmix64 state starts as in
+ * fasim_shuffle_query.  m < 3 returns a copy.  Otherwise, with z = rna[m - 1]: (1) for each distinct byte value a in ascending
+ * order, the list of the successors of a in order of occurrence; (2) for each a != z with a non-empty list, in ascending order, a
+ * last edge j = next() mod len; (3) if following the last edges from every such a does not reach z, all of them are drawn again;
+ * (4) each chosen last edge moves to the end of its list (the entries behind it move up by one) and the len' entries before it are
+ * shuffled by fasim_shuffle_query's loop (for i = len' - 1 down to 1: j = next() mod (i + 1), swap), in ascending order of a; z's
+ * whole list is shuffled; (5) the walk from rna[0] consumes each list in order.  out[m] may be rna itself. */
+int  fasim_shuffle_query_dinuc(const char* rna, int32_t m, uint64_t seed, int32_t k, char* out /* [m] */);
+/* fasim_hist_threshold on sites: with s[v] = the sum over the classes of sites[c][v] and ctl_s[v] the same summed over the K
+ * controls, the smallest v >= 1 with s[v] > 0 such that every w >= v with s[w] > 0 has (double)ctl_s[w] <= Q * K * (double)s[w];
+ * 0 when there is none.  Bad arguments give FASIM_E_ARG (negative). */
+int32_t fasim_site_counts_threshold(const fasim_site_counts* real, const fasim_site_counts* const* controls, int32_t ncontrols, double fdr);
+/* The table `fasim --potential-hist --hist-sites` writes.  First `# fasim site counts lncRNA=<rna_name> positions=<n>` and, with
+ * K > 0, ` controls=<K> seed=<S> shuffle=<mono|di> fdr=<Q> min_value=<V|NA>` (V = fasim_site_counts_threshold; dinuc != 0: di).
+ * Then the column names and one tab-separated line per value v from 1 to the largest v with a site in the query or a control:
+ * value, per class <Class>_sites and with K > 0 <Class>_ctl_sites, then all_sites and with K > 0 all_ctl_sites and
+ * fdr = all_ctl_sites / (K * all_sites) as %.6g, NA where all_sites is 0.  Free with fasim_free. */
+int  fasim_site_counts_tsv(const fasim_site_counts* real, const fasim_site_counts* const* controls, int32_t ncontrols, uint64_t seed,
+                           int32_t dinuc, double fdr, const char* rna_name, char** text, int64_t* text_len);
+
 /* Host half of the path's one exchange step: concatenates the records of `nparts` shards in the
  * order given and rebases their pool offsets.  Shards are contiguous segment ranges, so rank order IS the
  * reference's canonical (segment, encoding, fastSIM rank) order, which cluster_triplex()'s unstable sort needs.
