@@ -192,7 +192,7 @@ EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_e
            "fasim_scan_tfo_profile", "fasim_tfo_profile_merge", "fasim_tfo_profile_tsv", "fasim_tfo_profile_free",
            "fasim_scan_records_sites", "fasim_sites_merge", "fasim_sites_bed", "fasim_sites_free",
            "fasim_scan_records_sites_aligned", "fasim_site_hits_merge", "fasim_site_hits_tsv", "fasim_site_hits_free",
-           "fasim_scan_oligos", "fasim_oligo_panel_tsv", "fasim_scan_oligos_aligned",
+           "fasim_scan_oligos", "fasim_oligo_panel_tsv", "fasim_scan_oligos_aligned", "fasim_scan_oligos_profile", "fasim_scan_oligos_peaks",
            "fasim_scan_records_hist", "fasim_scan_oligos_hist", "fasim_hist_merge", "fasim_hist_free", "fasim_shuffle_query",
            "fasim_hist_threshold", "fasim_hist_tsv",
            "fasim_scan_records_site_counts", "fasim_scan_oligos_site_counts", "fasim_site_counts_merge", "fasim_site_counts_free",
@@ -322,6 +322,12 @@ def lib():
                                             C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int64, C.c_int64, C.POINTER(Params),
                                             C.c_int32, C.c_int32, C.POINTER(C.POINTER(_Sites)), C.POINTER(C.POINTER(_SiteHits)),
                                             C.POINTER(ScanStats)]
+    L.fasim_scan_oligos_profile.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
+                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int64, C.c_int64, C.POINTER(Params),
+                                            C.c_int32, C.POINTER(C.POINTER(_TfoProfile)), C.POINTER(ScanStats)]
+    L.fasim_scan_oligos_peaks.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int64, C.c_int64, C.POINTER(Params),
+                                          C.c_int32, C.POINTER(C.POINTER(_Track)), C.POINTER(_Peak), C.POINTER(ScanStats)]
     L.fasim_oligo_panel_tsv.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.POINTER(_Sites)), C.c_int32,
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.fasim_scan_records_hist.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
@@ -1579,6 +1585,47 @@ class Engine:
                                                       min_value, max_gap, sts, hts, totals))
         self._totals(totals, nq)
         return _grid(Sites, sts, nq, nrec), _grid(SiteHits, hts, nq, nrec)
+
+    def scan_oligos_profile(self, oligos, dnas, params: Params | None = None, per_record: bool = False, seg_first: int = 0,
+                            seg_count: int = -1):
+        """The per-base profile of every oligo of a panel (fasim_scan_oligos_profile): a list per oligo of TfoProfile -- what
+        scan_tfo_profile() would give for a lncRNA, with the oligo in its place -- over the whole record set, or with per_record
+        lists per record, each what that record scanned alone gives.  `dnas` as for scan_oligos().  The engine's own query is not
+        touched.  Shards of a segment range merge with merge_tfo_profiles(); the table is tfo_profile_tsv().  Totals per oligo:
+        `self.last_totals`."""
+        p = params or default_params()
+        blob, offs, lens, nrec = _pack_records(dnas, resident_ok=True)
+        arr, qlens, nq, _ = _pack_queries([bytes(x) for x in oligos])
+        nprof = max(1, nq) * (max(1, nrec) if per_record else 1)
+        profs = (C.POINTER(_TfoProfile) * nprof)()
+        totals = (ScanStats * max(1, nq))()
+        self._check(self._L.fasim_scan_oligos_profile(self._h, arr, qlens, nq, blob, offs, lens, nrec, seg_first, seg_count, C.byref(p),
+                                                      1 if per_record else 0, profs, totals))
+        self._totals(totals, nq)
+        if per_record:
+            return _grid(TfoProfile, profs, nq, nrec)
+        return [TfoProfile(_native=profs[q]) for q in range(nq)]
+
+    def scan_oligos_peaks(self, oligos, dnas, params: Params | None = None, bin: int = 0, seg_first: int = 0, seg_count: int = -1):
+        """The screen of a panel (fasim_scan_oligos_peaks): an (nq, nrec, 4, 3) int64 array of (value, pos, enc) per oligo, record and
+        strand class (TRACK_CLASSES) -- what scan_records_track() gives for a lncRNA, from the oligo's potential -- (0, -1, -1)
+        where the potential is zero.  bin >= 1: `(tracks, peaks)`, tracks being scan_oligos()' tracks of that width.  `dnas` as for
+        scan_oligos().  Shards of a segment range merge with merge_peaks() / merge_tracks(); the table is screen_tsv().  Totals per
+        oligo: `self.last_totals`."""
+        p = params or default_params()
+        blob, offs, lens, nrec = _pack_records(dnas, resident_ok=True)
+        arr, qlens, nq, _ = _pack_queries([bytes(x) for x in oligos])
+        nout = max(1, nq) * max(1, nrec)
+        trks = (C.POINTER(_Track) * nout)() if bin != 0 else None
+        peaks = (_Peak * (nout * 4))()
+        totals = (ScanStats * max(1, nq))()
+        self._check(self._L.fasim_scan_oligos_peaks(self._h, arr, qlens, nq, blob, offs, lens, nrec, seg_first, seg_count, C.byref(p),
+                                                    bin, trks, peaks, totals))
+        self._totals(totals, nq)
+        pk = _peaks_from_c(peaks, nout * 4).reshape(nq, nrec, 4, 3)
+        if trks is None:
+            return pk
+        return _grid(Track, trks, nq, nrec), pk
 
     def scan_hist(self, dnas, params: Params | None = None, controls: int = 0, seed: int = 0, records: bool = False, seg_first: int = 0,
                   seg_count: int = -1, rnas=None):

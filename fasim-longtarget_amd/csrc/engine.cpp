@@ -336,7 +336,7 @@ void fasim_engine_destroy(fasim_engine* e)
 		&e->qsim, &e->sim_min, &e->sim_row, &e->sim_ev, &e->sim_cnt, &e->sim_nodes,
 		&e->ublk, &e->btarget, &e->bidx, &e->bcounts, &e->blist[0], &e->blist[1], &e->blist[2], &e->bslots[0], &e->bslots[1], &e->bslots[2],
 		&e->bprev, &e->lane_ub, &e->fzones, &e->fubslot, &e->bdec, &e->btab, &e->swin, &e->unit_ovf, &e->track, &e->track_phase, &e->track_sat, &e->track_peaks, &e->sites_counts, &e->sites_offsets, &e->sites_runs, &e->sites_sat, &e->sa_q, &e->sa_tcodes, &e->sa_probs, &e->sa_ends, &e->sa_rows, &e->sa_items, &e->sa_dirs, &e->sa_cigar, &e->sa_ciglen,
-		&e->rowmax16, &e->row_out, &e->row_gfirst, &e->row_sat, &e->oligo_q, &e->hist, &e->hist_zone, &e->hist_zones, &e->hist_sat, &e->hist_pairs, &e->hist_border,
+		&e->rowmax16, &e->row_out, &e->row_gfirst, &e->row_sat, &e->oligo_q, &e->rowpart16, &e->hist, &e->hist_zone, &e->hist_zones, &e->hist_sat, &e->hist_pairs, &e->hist_border,
 		&e->vr_q, &e->vr_dna, &e->vr_alt, &e->vr_wins, &e->vr_probs, &e->vr_tcodes, &e->vr_rows, &e->vr_touch, &e->vr_out,
 		&e->vr_items, &e->vr_dirs, &e->vr_cigar, &e->vr_paths, &e->fmask, &e->flist, &e->fmarks, &e->seg_clean };
 	for (auto& t : e->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
@@ -772,18 +772,6 @@ int fasim_scan_records_track(fasim_engine* E, const char* const* rnas, const int
 }
 
 // ---- per-base profile of the lncRNA ------------------------------------------------------------
-static fasim_tfo_profile* tfo_profile_alloc(int32_t m)
-{
-	fasim_tfo_profile* t = (fasim_tfo_profile*)calloc(1, sizeof(fasim_tfo_profile));
-	if (!t) return nullptr;
-	t->m = m;
-	for (int c = 0; c < FASIM_TRACK_CLASSES; c++) {
-		t->v[c] = (uint16_t*)calloc((size_t)std::max<int32_t>(1, m), sizeof(uint16_t));
-		if (!t->v[c]) { fasim_tfo_profile_free(t); return nullptr; }
-	}
-	return t;
-}
-
 void fasim_tfo_profile_free(fasim_tfo_profile* t)
 {
 	if (!t) return;

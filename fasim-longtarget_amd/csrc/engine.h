@@ -149,6 +149,7 @@ struct fasim_engine {
 	int opt_site_short = -1;                     // option "site_short": 1 = the hits of oligo sites end on k_site_ends_short (default), 0 = on k_site_ends (-1 = default / environment FASIM_SITE_SHORT)
 	int opt_site_chunk = 0;                      // option "site_chunk": problems per chunk of the hits phase where lower than the phase's own limit (0 = that limit)
 	DevBuf oligo_q;                              // fasim_scan_oligos only: the panel's query codes, FASIM_MAX_OLIGO bytes per oligo
+	DevBuf rowpart16;                            // fasim_scan_oligos_profile only: k_scan_short_rows' row maxima per (unit, stretch pair) of the batch (row_out and row_gfirst serve its fold)
 	DevBuf rowmax16, row_out, row_gfirst, row_sat;   // fasim_scan_tfo_profile only: k_scan's row maxima of the batch, k_rowfold's groups, result and saturation flags
 	int opt_numa = 1;                            // option "numa_affinity": pin the scan's host threads to the GPU's NUMA node (no-op on one node)
 	// HBM-window variant of k_striped (queries whose stripes do not fit the LDS): its scratch, the forcing switch (option
@@ -489,6 +490,24 @@ struct TfoReq : ScanProduct {
 	int fold(fasim_engine* E, BatchCtx& C, int q) const override;
 	void merge(const BatchCtx& C, const SegTable& T, int64_t b0, int64_t b1, int q) override;
 };
+// The profile of an oligo of a panel (fasim_scan_oligos_profile, engine_oligos.cpp): the same arrays and the same merge, but the rows
+// are the oligo's own m[q] -- the engine's query is not involved -- and fold() runs k_rowfold_parts over E->rowpart16, which
+// panel_batch has k_scan_short_rows fill.  No value reaches saturation (5 * 112 = 560).
+struct OligoTfoReq : TfoReq {
+	const char* needs_scan() const override { return "an oligo's profile needs k_scan_short"; }
+	int fold(fasim_engine* E, BatchCtx& C, int q) const override;
+};
+inline fasim_tfo_profile* tfo_profile_alloc(int32_t m)
+{
+	fasim_tfo_profile* t = (fasim_tfo_profile*)calloc(1, sizeof(fasim_tfo_profile));
+	if (!t) return nullptr;
+	t->m = m;
+	for (int c = 0; c < FASIM_TRACK_CLASSES; c++) {
+		t->v[c] = (uint16_t*)calloc((size_t)std::max<int32_t>(1, m), sizeof(uint16_t));
+		if (!t->v[c]) { fasim_tfo_profile_free(t); return nullptr; }
+	}
+	return t;
+}
 
 // ---- sites above a fixed potential (fasim_scan_records_sites, sites.hip) -------------------------------------------------------------
 // One run as the workers keep it: record positions, the encoding itself

@@ -6,6 +6,8 @@
 // into colmax16 and the folds that the products of the call (sites, tracks, histogram: ScanProduct, engine.h) run behind k_scan, with
 // their host merges.  The engine's own query is not involved.
 // fasim_scan_oligos_aligned: the same call for sites, then the hit of every site (run_site_align with k_site_ends_short, section 18).
+// fasim_scan_oligos_profile / fasim_scan_oligos_peaks: the same call with k_scan_short_rows and k_rowfold_parts behind it for the
+// per-base profiles, and with k_track's peak variant for the screen (section 24).
 #include "engine.h"
 
 namespace {
@@ -24,11 +26,17 @@ int panel_batch(fasim_engine* E, const PanelCall& P, BatchCtx& C, int64_t b0, in
 {
 	const UnitBatch& B = C.B;
 	HIPOK(E->colmax16.ensure((size_t)B.nunit * B.tstride * sizeof(uint16_t)));
+	const bool rows = any_rowmax(P.folds);       // a product of the call wants the row maxima: k_scan_short_rows
 	for (int q = 0; q < P.nq; q++) {
 		ScanShortLaunch L;
 		L.tcodes = E->tcodes.as<uint8_t>(); L.unit_len = E->unit_len.as<int32_t>(); L.nunit = B.nunit; L.tstride = B.tstride;
 		L.qcodes = E->oligo_q.as<uint8_t>() + (size_t)q * FASIM_MAX_OLIGO; L.m = P.m[(size_t)q]; L.colmax16 = E->colmax16.as<uint16_t>();
 		scan_short_shape(L.m, B.tstride, B.nunit, &L.stretch, &L.npairs, &L.warm);
+		L.rowpart16 = nullptr;
+		if (rows) {
+			HIPOK(E->rowpart16.ensure((size_t)B.nunit * L.npairs * (16 * ((L.m + 15) / 16)) * sizeof(uint16_t)));
+			L.rowpart16 = E->rowpart16.as<uint16_t>();
+		}
 		hipError_t he;
 		{ TimedScope ts(E, 0, E->st); he = launch_scan_short(L, E->st); }
 		if (he != hipSuccess) return fail(E, FASIM_E_HIP, "scan_short launch failed: %s", hipGetErrorString(he));
@@ -39,12 +47,17 @@ int panel_batch(fasim_engine* E, const PanelCall& P, BatchCtx& C, int64_t b0, in
 	return FASIM_OK;
 }
 
+// what the profile and the peaks calls add to the outputs of scan_oligos_core: profiles per oligo, or per (oligo, record), and the
+// peaks of k_track per (oligo, record, class)
+struct PanelExtra { int32_t per_record = 0; fasim_tfo_profile** profiles = nullptr; fasim_peak* peaks = nullptr; };
+
 // fasim_scan_oligos, fasim_scan_oligos_hist and fasim_scan_oligos_site_counts: sites, tracks, histograms (out_hists[q]) and site counts
-// (out_counts[q]) are each wanted iff their output is given;
+// (out_counts[q]) are each wanted iff their output is given, and so are the profiles and peaks of `extra`; with peaks and no tracks
+// k_track runs for its peaks alone (bin 0);
 // `rs` hands the resolved record set to the second phase of fasim_scan_oligos_aligned
 int scan_oligos_core(fasim_engine* E, const char* const* oligos, const int32_t* lens, int32_t nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
-	int32_t min_value, int32_t max_gap, fasim_sites** out_sites, int32_t bin, fasim_track** out_tracks, fasim_hist** out_hists, fasim_site_counts** out_counts, fasim_scan_stats* totals, RecordSet& rs)
+	int32_t min_value, int32_t max_gap, fasim_sites** out_sites, int32_t bin, fasim_track** out_tracks, fasim_hist** out_hists, fasim_site_counts** out_counts, fasim_scan_stats* totals, RecordSet& rs, const PanelExtra& extra = PanelExtra())
 {
 	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
 	if (nq < 1) return fail(E, FASIM_E_ARG, "a panel needs at least one oligo (nq = %d)", nq);
@@ -54,7 +67,8 @@ int scan_oligos_core(fasim_engine* E, const char* const* oligos, const int32_t* 
 		if (lens[q] > FASIM_MAX_OLIGO)
 			return fail(E, FASIM_E_ARG, "oligo %d has %d nt, a panel takes oligos of at most %d nt: scan longer queries with fasim_scan_records_sites", q, lens[q], FASIM_MAX_OLIGO);
 	}
-	if (!out_sites && !out_tracks && !out_hists && !out_counts) return fail(E, FASIM_E_ARG, "neither sites nor tracks are wanted");
+	fasim_tfo_profile** out_profiles = extra.profiles; fasim_peak* out_peaks = extra.peaks;
+	if (!out_sites && !out_tracks && !out_hists && !out_counts && !out_profiles && !out_peaks) return fail(E, FASIM_E_ARG, "neither sites nor tracks are wanted");
 	if (out_sites && (min_value < 1 || min_value > 16383)) return fail(E, FASIM_E_ARG, "oligos: min_value %d lies outside [1, 16383]", min_value);
 	if (out_sites && max_gap < 0) return fail(E, FASIM_E_ARG, "oligos: max_gap %d is negative", max_gap);
 	if (out_tracks && bin < 1) return fail(E, FASIM_E_ARG, "oligos: track bin width %d: must be at least 1", bin);
@@ -75,6 +89,8 @@ int scan_oligos_core(fasim_engine* E, const char* const* oligos, const int32_t* 
 	if (out_tracks) for (size_t o = 0; o < nout; o++) out_tracks[o] = nullptr;
 	if (out_hists) for (int q = 0; q < nq; q++) out_hists[q] = nullptr;
 	if (out_counts) for (int q = 0; q < nq; q++) out_counts[q] = nullptr;
+	const size_t nprof = out_profiles ? (extra.per_record ? nout : (size_t)nq) : 0;
+	for (size_t o = 0; o < nprof; o++) out_profiles[o] = nullptr;
 	HIPOK(hipSetDevice(E->device));
 	const double t_begin = now_s();
 	AffinityScope numa(E->device, E->opt_numa != 0);
@@ -95,16 +111,28 @@ int scan_oligos_core(fasim_engine* E, const char* const* oligos, const int32_t* 
 	for (int q = 0; q < nq; q++) { msum += lens[q]; for (int i = 0; i < lens[q]; i++) P.codes[(size_t)q * FASIM_MAX_OLIGO + i] = code2(oligos[q][i]); }
 	SitesReq sr; TrackReq tr;
 	if (out_sites) { sites_req_init(sr, min_value, max_gap, true, nq, nrec); P.folds.push_back(&sr); }
-	HistReq hr; SiteCountsReq cr;
+	HistReq hr; SiteCountsReq cr; OligoTfoReq pf;
 	auto drop = [&]() {
+		for (size_t o = 0; o < nprof; o++) { fasim_tfo_profile_free(out_profiles[o]); out_profiles[o] = nullptr; }
 		if (out_counts) for (int q = 0; q < nq; q++) { fasim_site_counts_free(out_counts[q]); out_counts[q] = nullptr; }
 		if (out_hists) for (int q = 0; q < nq; q++) { fasim_hist_free(out_hists[q]); out_hists[q] = nullptr; }
 		sites_drop(out_sites, nout);
 		tracks_drop(out_tracks, nout);
 	};
-	if (out_tracks) {
-		rc = track_req_init(E, tr, bin, true, nq, rec_len, nrec, out_tracks, nullptr); if (rc) return rc;
+	if (out_tracks || out_peaks) {
+		rc = track_req_init(E, tr, out_tracks ? bin : 0, true, nq, rec_len, nrec, out_tracks, out_peaks); if (rc) return rc;
 		P.folds.push_back(&tr);
+	}
+	if (out_profiles) {
+		pf.only = true; pf.per_record = extra.per_record != 0; pf.nrec = nrec; pf.m = P.m;
+		pf.units.assign(nprof, 0); pf.sat.assign(nprof, 0); pf.mu.reset(new std::mutex[(size_t)nq]);
+		pf.v.reserve(nprof * 4);
+		for (size_t o = 0; o < nprof; o++) {
+			out_profiles[o] = tfo_profile_alloc(P.m[extra.per_record ? o / (size_t)nrec : o]);
+			if (!out_profiles[o]) { drop(); return fail(E, FASIM_E_NOMEM, "out of memory"); }
+			for (int c = 0; c < FASIM_TRACK_CLASSES; c++) pf.v.push_back(out_profiles[o]->v[c]);
+		}
+		P.folds.push_back(&pf); P.merges.push_back(&pf);
 	}
 
 	if (out_hists) {
@@ -120,7 +148,7 @@ int scan_oligos_core(fasim_engine* E, const char* const* oligos, const int32_t* 
 		P.folds.push_back(&cr); P.merges.push_back(&cr);
 	}
 	if (out_sites) P.merges.push_back(&sr);
-	if (out_tracks) P.merges.push_back(&tr);
+	if (out_tracks || out_peaks) P.merges.push_back(&tr);
 	P.T = &T;
 
 	std::vector<int64_t> rec_units((size_t)nrec, 0);      // units scanned per record (the same for every oligo)
@@ -188,6 +216,7 @@ int scan_oligos_core(fasim_engine* E, const char* const* oligos, const int32_t* 
 		if (rc) { drop(); return rc; }
 	}
 	if (out_tracks) for (size_t o = 0; o < nout; o++) { out_tracks[o]->units = rec_units[o % (size_t)nrec]; out_tracks[o]->saturated_units = tr.sat[o]; }
+	for (size_t o = 0; o < nprof; o++) { out_profiles[o]->units = pf.units[o]; out_profiles[o]->saturated_units = pf.sat[o]; }
 	if (out_hists) {
 		try { rc = hist_req_finish(E, hr, out_hists, nq); } catch (const std::bad_alloc&) { rc = fail(E, FASIM_E_NOMEM, "out of memory"); }
 		if (rc) { drop(); return rc; }
@@ -212,7 +241,59 @@ int scan_oligos_core(fasim_engine* E, const char* const* oligos, const int32_t* 
 
 } // namespace
 
+// k_rowfold_parts over the parts k_scan_short_rows left of oligo q in E->rowpart16, into C.rowfold: the groups are TfoReq::fold's, one
+// per run of segments of one record, or the whole batch.  The shape of the parts is the one panel_batch launched the scan with.  The
+// copy completes at the next synchronisation of the stream; TfoReq::merge then takes C.rowfold as k_rowfold's.
+int OligoTfoReq::fold(fasim_engine* E, BatchCtx& C, int q) const
+{
+	const int nu = C.B.nunit, nseg = C.nseg, mq = m[(size_t)q], rows = 16 * ((mq + 15) / 16);
+	int rc; hipError_t he;
+	std::vector<int32_t>& gfirst = C.row_gfirst;
+	gfirst.assign(1, 0);
+	if (per_record) for (int s = 1; s < nseg; s++) if (C.srec[(size_t)s] != C.srec[(size_t)s - 1]) gfirst.push_back(s);
+	gfirst.push_back(nseg);
+	const int ng = (int)gfirst.size() - 1;
+	const size_t nout = (size_t)ng * 4 * rows;
+	rc = upload(E, E->row_gfirst, gfirst.data(), sizeof(int32_t) * gfirst.size()); if (rc) return rc;
+	HIPOK(E->row_out.ensure(nout * sizeof(uint16_t)));
+	RowPartFoldLaunch R;
+	int warm;
+	scan_short_shape(mq, C.B.tstride, nu, &R.stretch, &R.npairs, &warm);
+	R.rowpart16 = E->rowpart16.as<uint16_t>(); R.unit_len = E->unit_len.as<int32_t>(); R.gfirst = E->row_gfirst.as<int32_t>();
+	R.ngroups = ng; R.nenc = C.nenc; R.rows = rows; R.tab = C.tab; R.out = E->row_out.as<uint16_t>();
+	{ TimedScope ts(E, 4); he = launch_rowfold_parts(R, E->st); }
+	if (he != hipSuccess) return fail(E, FASIM_E_HIP, "rowfold launch failed: %s", hipGetErrorString(he));
+	C.rowfold.resize(nout); C.row_sat.assign((size_t)nu, 0);      // (no row maximum of an oligo saturates)
+	HIPOK(hipMemcpyAsync(C.rowfold.data(), E->row_out.p, nout * sizeof(uint16_t), hipMemcpyDeviceToHost, E->st));
+	return FASIM_OK;
+}
+
 extern "C" {
+
+int fasim_scan_oligos_profile(fasim_engine* E, const char* const* oligos, const int32_t* lens, int32_t nq, const char* dna,
+	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
+	int32_t per_record, fasim_tfo_profile** out_profiles, fasim_scan_stats* totals)
+{
+	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
+	if (!out_profiles) return fail(E, FASIM_E_ARG, "bad arguments");
+	RecordSet rs;
+	PanelExtra x; x.per_record = per_record; x.profiles = out_profiles;
+	return scan_oligos_core(E, oligos, lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, 1, 0, nullptr, 1, nullptr, nullptr, nullptr, totals, rs, x);
+}
+
+int fasim_scan_oligos_peaks(fasim_engine* E, const char* const* oligos, const int32_t* lens, int32_t nq, const char* dna,
+	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,
+	int32_t bin, fasim_track** out_tracks, fasim_peak* out_peaks, fasim_scan_stats* totals)
+{
+	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
+	if (!out_peaks) return fail(E, FASIM_E_ARG, "bad arguments");
+	if (bin < 0) return fail(E, FASIM_E_ARG, "oligos: track bin width %d: must be at least 1, or 0 for peaks only", bin);
+	if (bin == 0 && out_tracks) return fail(E, FASIM_E_ARG, "oligos: bin 0 is peaks only: out_tracks must be NULL");
+	if (bin >= 1 && !out_tracks) return fail(E, FASIM_E_ARG, "oligos: bin %d needs out_tracks", bin);
+	RecordSet rs;
+	PanelExtra x; x.peaks = out_peaks;
+	return scan_oligos_core(E, oligos, lens, nq, dna, rec_off, rec_len, nrec, seg_first, seg_count, pp, 1, 0, nullptr, bin, out_tracks, nullptr, nullptr, totals, rs, x);
+}
 
 int fasim_scan_oligos(fasim_engine* E, const char* const* oligos, const int32_t* lens, int32_t nq, const char* dna,
 	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, int64_t seg_first, int64_t seg_count, const fasim_params* pp,

@@ -40,13 +40,22 @@
 //                           (fasim_scan_oligos): per oligo the sites file that --sites V --sites-only writes for a
 //                           lncRNA of that name, and one panel table <O>/<f2 stem>-<f1 stem>.oligos-<V>.tsv (per oligo: sites, covered bases,
 //                           per class sites and largest value).  Never -TFOsorted / -TFOclass.  Exit status 2, nothing written: without
-//                           --sites, with --sites-align, -F, --track, --screen, --tfo-profile or --accumulate-records, or an -f2
+//                           --sites (or --potential-hist, --oligo-profile, --oligo-screen), with --sites-align, -F, --track, --screen, --tfo-profile or --accumulate-records, or an -f2
 //                           record that is empty or longer than 112 nt
 //     --oligo-hits          with --oligos --sites V: every site of every oligo with its hit (fasim_scan_oligos_aligned, DESIGN.md section
 //                           18): beside each oligo's sites file the table that --sites V --sites-only --sites-align writes for a lncRNA
 //                           of that name (<stem>-TFOsites-<V>-aligned; set mode <O>/<oligo>-<f1 stem>.sites-<V>.aligned.tsv).  The sites
 //                           files and the panel table are what they are without it.  Exit status 2, nothing written: without --oligos,
 //                           without --sites, with --potential-hist
+//     --oligo-profile       with --oligos: the per-base profile of every oligo (fasim_scan_oligos_profile), the table
+//                           --tfo-profile writes for a lncRNA of that name: a plain run <stem>-TFOprofile (the stem of the oligo's
+//                           -TFOsites-<V> file), with --all-records or --regions one whole-set table <O>/<oligo>-<f1 stem>.tfoprofile.tsv
+//     --oligo-screen        with --oligos and --all-records or --regions: the screen of every oligo (fasim_scan_oligos_peaks),
+//                           <O>/<oligo>-<f1 stem>.screen.tsv, the table --screen-only writes for a lncRNA of that name.  --oligos is
+//                           satisfied by --sites V, --potential-hist, --oligo-profile or --oligo-screen; the two may be given together
+//                           and with --sites V [--sites-gap G], whose files are then what they are without them.  Exit status 2, nothing
+//                           written: either without --oligos, --oligo-screen without --all-records / --regions, either with
+//                           --potential-hist or --oligo-hits
 //     --potential-hist      histogram of the potential with shuffled controls (fasim_scan_records_hist): per
 //                           strand class and value how many bases of the DNA reach it.  --hist-controls K (default 0) scans K
 //                           composition-preserving shuffles of every lncRNA too (--hist-seed S, default 0) and reports the false discovery
@@ -259,7 +268,7 @@ static int g_out_failed = 0;
 // --track: bin width (0: no tracks), smallest value written, --track-only; --screen / --screen-only: peaks (no_stage3: no records)
 // --tfo-profile / --tfo-profile-only: the lncRNA's profile (never together with tracks or peaks)
 // --sites V / --sites-gap G / --sites-only: the sites above a fixed potential (never together with tracks, peaks or the profile)
-struct TrackOpt { int bin = 0, min_value = 1; bool only = false, peaks = false, no_stage3 = false, tfo = false, tfo_only = false; int sites = 0, sites_gap = 0; bool sites_only = false, sites_align = false, oligos = false, oligo_hits = false;
+struct TrackOpt { int bin = 0, min_value = 1; bool only = false, peaks = false, no_stage3 = false, tfo = false, tfo_only = false; int sites = 0, sites_gap = 0; bool sites_only = false, sites_align = false, oligos = false, oligo_hits = false, oligo_profile = false, oligo_screen = false;
 	bool hits() const { return sites_align || oligo_hits; }      // the sites' hits are wanted (--sites-align, or --oligo-hits of a panel)
 	// --potential-hist: the histogram, K controls per lncRNA under a seed (hist_ctl: their sequences, lncRNA after lncRNA), the FDR bound
 	bool hist = false, hist_only = false; int hist_controls = 0; uint64_t hist_seed = 0; double hist_fdr = 0.05; const std::vector<std::string>* hist_ctl = nullptr;
@@ -427,7 +436,8 @@ static int scan_group(const std::vector<fasim_engine*>& engines, const std::vect
 	auto run = [&](int d) {
 		const int64_t base = nseg / nd, rem = nseg % nd;
 		const int64_t first = d * base + std::min<int64_t>(d, rem), count = base + (d < rem ? 1 : 0);
-		if (counts && trk.oligos)
+		if ((trk.oligo_profile || trk.oligo_screen) && !sites) rc[(size_t)d] = FASIM_OK;      // a panel's profiles / peaks alone: their calls below
+		else if (counts && trk.oligos)
 			rc[(size_t)d] = fasim_scan_oligos_site_counts(engines[(size_t)d], hq.data(), hl.data(), nq + nctl, dna.data(), off.data(), len.data(), nrec, first, count, &p,
 				cpart[(size_t)d].data(), nullptr);
 		else if (counts && no_res)
@@ -476,6 +486,13 @@ static int scan_group(const std::vector<fasim_engine*>& engines, const std::vect
 			rc[(size_t)d] = fasim_scan_records_track(engines[(size_t)d], qp.data(), ql.data(), nq, dna.data(), off.data(), len.data(), nrec, first, count, &p,
 				trk.bin, no_res ? nullptr : part[(size_t)d].data(), with_track ? tpart[(size_t)d].data() : nullptr,
 				with_peaks ? ppart[(size_t)d].data() : nullptr, nullptr);
+		// --oligos --oligo-profile / --oligo-screen: one more call per product
+		if (rc[(size_t)d] == FASIM_OK && trk.oligo_profile)
+			rc[(size_t)d] = fasim_scan_oligos_profile(engines[(size_t)d], qp.data(), ql.data(), nq, dna.data(), off.data(), len.data(), nrec, first, count, &p, 0,
+				fpart[(size_t)d].data(), nullptr);
+		if (rc[(size_t)d] == FASIM_OK && trk.oligo_screen)
+			rc[(size_t)d] = fasim_scan_oligos_peaks(engines[(size_t)d], qp.data(), ql.data(), nq, dna.data(), off.data(), len.data(), nrec, first, count, &p, 0,
+				nullptr, ppart[(size_t)d].data(), nullptr);
 	};
 	if (nd == 1) run(0);
 	else { std::vector<std::thread> th; for (int d = 0; d < nd; d++) th.emplace_back(run, d); for (auto& t : th) t.join(); }
@@ -766,7 +783,7 @@ int main(int argc, char* const* argv)
 		{ "track", required_argument, NULL, 1009 }, { "track-min", required_argument, NULL, 1010 }, { "track-only", no_argument, NULL, 1011 },
 		{ "screen", no_argument, NULL, 1012 }, { "screen-only", no_argument, NULL, 1013 },
 		{ "tfo-profile", no_argument, NULL, 1014 }, { "tfo-profile-only", no_argument, NULL, 1015 },
-		{ "sites", required_argument, NULL, 1016 }, { "sites-gap", required_argument, NULL, 1017 }, { "sites-only", no_argument, NULL, 1018 }, { "sites-align", no_argument, NULL, 1019 }, { "oligos", no_argument, NULL, 1020 }, { "oligo-hits", no_argument, NULL, 1026 },
+		{ "sites", required_argument, NULL, 1016 }, { "sites-gap", required_argument, NULL, 1017 }, { "sites-only", no_argument, NULL, 1018 }, { "sites-align", no_argument, NULL, 1019 }, { "oligos", no_argument, NULL, 1020 }, { "oligo-hits", no_argument, NULL, 1026 }, { "oligo-profile", no_argument, NULL, 1032 }, { "oligo-screen", no_argument, NULL, 1033 },
 		{ "potential-hist", no_argument, NULL, 1021 }, { "hist-controls", required_argument, NULL, 1022 }, { "hist-seed", required_argument, NULL, 1023 },
 		{ "hist-fdr", required_argument, NULL, 1024 }, { "potential-hist-only", no_argument, NULL, 1025 },
 		{ "hist-sites", no_argument, NULL, 1030 }, { "hist-shuffle", required_argument, NULL, 1031 },
@@ -818,6 +835,8 @@ int main(int argc, char* const* argv)
 		case 1019: trk.sites_align = true; break;
 		case 1020: trk.oligos = true; break;
 		case 1026: trk.oligo_hits = true; break;
+		case 1032: trk.oligo_profile = true; break;
+		case 1033: trk.oligo_screen = true; break;
 		case 1021: trk.hist = true; break;
 		case 1022: hist_arg_given = true; trk.hist_controls = strict_int(optarg, -1); break;
 		case 1023: { hist_arg_given = true; char* end = nullptr; errno = 0; trk.hist_seed = strtoull(optarg, &end, 10); if (end == optarg || *end != '\0' || errno == ERANGE || optarg[0] == '-') hist_arg_bad = true; break; }
@@ -825,7 +844,7 @@ int main(int argc, char* const* argv)
 		case 1025: trk.hist_only = true; break;
 		case 1030: hist_arg_given = true; trk.hist_sites = true; break;
 		case 1031: hist_arg_given = true; if (!strcmp(optarg, "di")) trk.hist_dinuc = true; else if (strcmp(optarg, "mono")) hist_shuffle_bad = true; break;
-		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only] [--sites-align] [--oligos [--oligo-hits]]] [--potential-hist [--hist-controls K] [--hist-seed S] [--hist-fdr Q] [--potential-hist-only] [--hist-sites] [--hist-shuffle mono|di]] [--variants FILE.vcf [--variant-flank F] [--variant-hits]]\n"); return 2;
+		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only] [--sites-align] [--oligos [--oligo-hits]]] [--oligos [--oligo-profile] [--oligo-screen]] [--potential-hist [--hist-controls K] [--hist-seed S] [--hist-fdr Q] [--potential-hist-only] [--hist-sites] [--hist-shuffle mono|di]] [--variants FILE.vcf [--variant-flank F] [--variant-hits]]\n"); return 2;
 		}
 	}
 	if (all_records && accumulate) { fprintf(stderr, "fasim: --all-records and --accumulate-records exclude each other\n"); return 2; }
@@ -850,8 +869,12 @@ int main(int argc, char* const* argv)
 	if (trk.hist && hist_arg_bad) { fprintf(stderr, "fasim: --hist-seed needs an unsigned integer\n"); return 2; }
 	if (trk.hist && !(trk.hist_fdr > 0.0 && trk.hist_fdr <= 1.0)) { fprintf(stderr, "fasim: --hist-fdr needs a number in (0, 1]\n"); return 2; }
 	if (trk.hist && 2 * (long long)p.overlapLength > (long long)p.cutLength) { fprintf(stderr, "fasim: --potential-hist needs -o of at most half of -c (a base would lie in three segments)\n"); return 2; }
-	if (trk.oligos && !sites && !trk.hist) { fprintf(stderr, "fasim: --oligos needs --sites V or --potential-hist\n"); return 2; }
-	if (trk.oligos && (trk.sites_align || trk.tfo)) { fprintf(stderr, "fasim: --oligos is not available with --sites-align, -F, --track, --screen, --tfo-profile or --accumulate-records\n"); return 2; }
+	const bool panel_extra = trk.oligo_profile || trk.oligo_screen;
+	if (panel_extra && !trk.oligos) { fprintf(stderr, "fasim: --oligo-profile and --oligo-screen need --oligos\n"); return 2; }
+	if (trk.oligo_screen && !(regions || all_records)) { fprintf(stderr, "fasim: --oligo-screen needs --regions FILE.bed or --all-records\n"); return 2; }
+	if (panel_extra && (trk.hist || trk.oligo_hits)) { fprintf(stderr, "fasim: --oligo-profile and --oligo-screen are not available with --potential-hist or --oligo-hits\n"); return 2; }
+	if (trk.oligos && !sites && !trk.hist && !panel_extra) { fprintf(stderr, "fasim: --oligos needs --sites V, --potential-hist, --oligo-profile or --oligo-screen\n"); return 2; }
+	if (trk.oligos && (trk.sites_align || trk.tfo || p.classicSim || track || screen || accumulate)) { fprintf(stderr, "fasim: --oligos is not available with --sites-align, -F, --track, --screen, --tfo-profile or --accumulate-records\n"); return 2; }
 	if (trk.oligo_hits && (!trk.oligos || !sites || trk.hist)) { fprintf(stderr, "fasim: --oligo-hits needs --oligos --sites V (and is not available with --potential-hist)\n"); return 2; }
 	const bool variants = !vcf_path.empty();
 	if (flank_given && !variants) { fprintf(stderr, "fasim: --variant-flank needs --variants FILE.vcf\n"); return 2; }
@@ -865,7 +888,7 @@ int main(int argc, char* const* argv)
 	if (trk.oligos) trk.sites_only = true;      // a panel has no triplex records: the sites files and the panel table are all it writes
 	if (trk.oligos && trk.hist) trk.hist_only = true;      // (or the oligos' histograms)
 	if (!sites) trk.sites = 0;
-	trk.peaks = screen; trk.no_stage3 = screen_only || trk.only || trk.tfo_only || trk.sites_only || trk.hist_only;
+	trk.peaks = screen || trk.oligo_screen; trk.no_stage3 = screen_only || trk.only || trk.tfo_only || trk.sites_only || trk.hist_only;
 	// --regions: the BED file is read and checked before anything else happens (a bad file writes nothing)
 	fasim_region* reg = nullptr; int64_t nreg = 0;
 	if (regions && fasim_read_bed(bed_path.c_str(), &reg, &nreg) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 2; }
@@ -909,9 +932,9 @@ int main(int argc, char* const* argv)
 	};
 	// --screen: per lncRNA and interval (--regions: BED order; --all-records: record order) the segments and the four peaks
 	struct ScreenRow { int64_t line = 0, start = 0, end = 0, segs = -1; std::string name, chrom; };
-	std::vector<ScreenRow> scr_rows((size_t)(screen && regions ? nreg : 0));
+	std::vector<ScreenRow> scr_rows((size_t)(trk.peaks && regions ? nreg : 0));
 	for (int64_t k = 0; k < (int64_t)scr_rows.size(); k++) { ScreenRow& w = scr_rows[(size_t)k]; w.line = reg[k].line; w.start = reg[k].start; w.end = reg[k].end; w.name = reg[k].name; w.chrom = reg[k].chrom; }
-	std::vector<std::vector<fasim_peak>> scr_peaks(screen ? rnas.size() : 0, std::vector<fasim_peak>(scr_rows.size() * 4));
+	std::vector<std::vector<fasim_peak>> scr_peaks(trk.peaks ? rnas.size() : 0, std::vector<fasim_peak>(scr_rows.size() * 4));
 	auto write_screen = [&]() -> int {
 		int bad = 0;
 		std::vector<fasim_region> rg(scr_rows.size()); std::vector<int64_t> sg(scr_rows.size());
@@ -928,7 +951,7 @@ int main(int argc, char* const* argv)
 		return bad;
 	};
 	// --tfo-profile: with --all-records / --regions one whole-set table per lncRNA, the maximum over the groups and records
-	const bool tfo_set = trk.tfo && (all_records || regions);
+	const bool tfo_set = (trk.tfo || trk.oligo_profile) && (all_records || regions);
 	std::vector<fasim_tfo_profile*> tfo_acc(tfo_set ? rnas.size() : 0, nullptr);
 	auto write_tfo = [&](const fasim_tfo_profile* t, const Rna& r, const std::string& path) -> int {
 		// (no unit scanned: a table of zeros)
@@ -1055,7 +1078,7 @@ int main(int argc, char* const* argv)
 		if (trk.oligos && sites && write_panel()) return 1;
 		if (hist_set && write_hist_set()) return 1;
 		if (!screen_only && !trk.tfo_only && !trk.sites_only && !trk.hist_only && write_index()) return 1;
-		if (screen && write_screen()) return 1;
+		if (trk.peaks && write_screen()) return 1;
 		std::cout << "finished normally" << std::endl;
 		return 0;
 	}
@@ -1124,13 +1147,26 @@ int main(int argc, char* const* argv)
 		long group_segs = 5120;
 		if (const char* g = getenv("FASIM_RECORD_GROUP")) group_segs = atol(g);
 		// (--screen always takes the record-set call, a long record or FASIM_RECORD_GROUP=0 as a group of one)
-		const bool grouped = (all_records || regions) && (group_segs > 0 || screen || sites || trk.hist);
+		const bool grouped = (all_records || regions) && (group_segs > 0 || screen || sites || trk.hist || panel_extra);
 		// grouped: the tails of thousands of records go to a pool of host threads instead of four threads in flight
 		std::unique_ptr<TailPool> pool(grouped ? new TailPool(8) : nullptr);
 		// one scanned record: a DNA record, or a BED interval (species = its name, start = its 1-based start; slot = its index)
 		struct Unit { std::string species, chr; long start = 0; int64_t len = 0; size_t recno = 0; int64_t slot = -1; };
 		// per record: --stats lines, output stem, tail + write on a background thread (the next record is read and scanned meanwhile)
+		// the record's line of the screen tables
+		auto screen_row = [&](const Unit& r, const fasim_peak* const* pk) {
+			size_t row = (size_t)r.slot;
+			if (!regions) {
+				row = scr_rows.size();
+				ScreenRow w; w.line = (int64_t)r.recno + 1; w.start = (int64_t)r.start - 1; w.end = w.start + r.len; w.name = r.species; w.chrom = r.chr;
+				scr_rows.push_back(w);
+				for (auto& v : scr_peaks) v.resize(scr_rows.size() * 4);
+			}
+			scr_rows[row].segs = fasim_segment_count(r.len, &p);
+			for (size_t q = 0; q < rnas.size(); q++) for (int c = 0; c < 4; c++) scr_peaks[q][row * 4 + c] = pk[q][c];
+		};
 		auto emit = [&](const Unit& r, const std::vector<fasim_result*>& res, const std::vector<fasim_track*>& tracks, const fasim_peak* const* pk = nullptr, fasim_sites* const* st = nullptr, fasim_site_hits* const* ht = nullptr) {
+			if (trk.oligo_screen) screen_row(r, pk);
 			if (sites && st) {
 				// the record's sites: its own file (a plain run), or its lines of the set's file
 				for (size_t q = 0; q < rnas.size(); q++) {
@@ -1156,17 +1192,9 @@ int main(int argc, char* const* argv)
 				if (trk.sites_only) return;
 			}
 			if (trk.hist_only) return;
+			if (trk.oligos) return;      // (a panel has no triplex records)
 			if (screen) {
-				// the record's line of the screen tables
-				size_t row = (size_t)r.slot;
-				if (!regions) {
-					row = scr_rows.size();
-					ScreenRow w; w.line = (int64_t)r.recno + 1; w.start = (int64_t)r.start - 1; w.end = w.start + r.len; w.name = r.species; w.chrom = r.chr;
-					scr_rows.push_back(w);
-					for (auto& v : scr_peaks) v.resize(scr_rows.size() * 4);
-				}
-				scr_rows[row].segs = fasim_segment_count(r.len, &p);
-				for (size_t q = 0; q < rnas.size(); q++) for (int c = 0; c < 4; c++) scr_peaks[q][row * 4 + c] = pk[q][c];
+				screen_row(r, pk);
 				if (screen_only) return;
 			}
 			if (trk.tfo_only) return;
@@ -1228,7 +1256,7 @@ int main(int argc, char* const* argv)
 			std::vector<std::vector<fasim_site_hits*>> ghits;
 			std::vector<fasim_hist*> ghist;
 			std::vector<fasim_site_counts*> gcounts;
-			if (scan_group(engines, rnas, gdna, goff, glen, p, res, trk, gtracks, gpeaks, trk.tfo ? &gprof : nullptr, sites ? &gsites : nullptr,
+			if (scan_group(engines, rnas, gdna, goff, glen, p, res, trk, gtracks, gpeaks, trk.tfo || trk.oligo_profile ? &gprof : nullptr, sites ? &gsites : nullptr,
 				sites && trk.hits() ? &ghits : nullptr, trk.hist && !trk.hist_sites ? &ghist : nullptr, trk.hist_sites ? &gcounts : nullptr)) return 1;
 			if (trk.hist_sites && hist_set) { for (size_t k = 0; k < gcounts.size(); k++) { fasim_site_counts* t = gcounts[k]; gcounts[k] = nullptr; if (counts_fold(counts_acc[k], t)) return 1; } }
 			else if (trk.hist_sites) {
@@ -1248,7 +1276,14 @@ int main(int argc, char* const* argv)
 				for (fasim_hist* x : ghist) fasim_hist_free(x);
 				if (bad) return 1;
 			}
-			for (size_t q = 0; q < gprof.size(); q++) { fasim_tfo_profile* t = gprof[q]; gprof[q] = nullptr; if (tfo_fold(tfo_acc[q], t)) return 1; }
+			for (size_t q = 0; q < gprof.size(); q++) {
+				fasim_tfo_profile* t = gprof[q]; gprof[q] = nullptr;
+				if (tfo_set) { if (tfo_fold(tfo_acc[q], t)) return 1; continue; }
+				// --oligos --oligo-profile on a plain run: <stem>-TFOprofile, the stem of the oligo's -TFOsites-<V> file
+				const int bad = write_tfo(t, rnas[q], outdir + "/" + group[0].species + "-" + rnas[q].name + "-" + base + "-TFOprofile");
+				fasim_tfo_profile_free(t);
+				if (bad) return 1;
+			}
 			const double dt = now_s() - t0;
 			tm.scan += dt;
 			if (stats) fprintf(stderr, "[fasim] group %zu: %zu records, %lld segments, scan %.3f s\n", ngroups, group.size(), (long long)group_nseg, dt);
@@ -1281,14 +1316,14 @@ int main(int argc, char* const* argv)
 					return group_nseg >= group_segs ? flush() : 0;
 				}
 				if (flush()) return 1;
-				if (screen || sites || trk.hist) {
+				if (screen || sites || trk.hist || panel_extra) {
 					// a group of one: only the record-set call gives the peaks / the sites
 					group_nseg = fasim_segment_count(u.len, &p);
 					goff.push_back(0); glen.push_back(u.len); gdna.assign(seq, (size_t)u.len); group.push_back(std::move(u));
 					return flush();
 				}
 			}
-			if (sites || trk.hist) {
+			if (sites || trk.hist || panel_extra) {
 				// a plain run: the record as a set of one (its records are those of fasim_scan_queries)
 				group_nseg = fasim_segment_count(u.len, &p);
 				goff.push_back(0); glen.push_back(u.len); gdna.assign(seq, (size_t)u.len); group.push_back(std::move(u));
@@ -1365,7 +1400,7 @@ int main(int argc, char* const* argv)
 		if (pool) pool->drain();
 		tm.tail_wait = now_s() - t_wait;
 		if (g_out_failed) return 1;
-		if (screen && write_screen()) return 1;
+		if (trk.peaks && write_screen()) return 1;
 		if (tfo_set && write_tfo_set()) return 1;
 		if (sites_set && write_sites_set()) return 1;
 		if (trk.oligos && sites && write_panel()) return 1;

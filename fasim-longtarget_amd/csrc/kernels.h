@@ -199,6 +199,9 @@ struct ScanShortLaunch {
 	const uint8_t* qcodes; int32_t m;          // the oligo's codes of the stage-2 alphabet, 1 <= m <= SCAN_SHORT_MAX
 	int32_t stretch, npairs, warm;             // columns per stretch, stretch pairs per unit, warm-up columns: from scan_short_shape
 	uint16_t* colmax16;                        // [unit][tstride] = 2 * column maximum (taint bit 0) for columns < unit_len; the others are 0 or not written
+	// non-NULL selects k_scan_short_rows: [unit][pair][16 * ceil(m / 16)] = 2 * row maximum over the real columns of
+	// the pair's two stretches; the parts of pairs with 2 * pair * stretch >= unit_len are not written
+	uint16_t* rowpart16;
 };
 // stretch length (a multiple of 16, >= warm), pairs per unit (2 * npairs * stretch >= tstride) and warm-up (W(m) rounded up to 16)
 void scan_short_shape(int m, int tstride, int nunit, int* stretch, int* npairs, int* warm);
@@ -291,6 +294,17 @@ struct RowFoldLaunch {
 	uint8_t* sat;               // [nseg * nenc], zeroed by the caller: 1 = the unit holds a saturated row maximum (16 383)
 };
 hipError_t launch_rowfold(const RowFoldLaunch& L, hipStream_t st);
+// k_rowfold_parts: the same result from the parts k_scan_short_rows leaves, out[g][4 classes][rows] = maximum over the group's units of
+// the class and over their written parts, taint bit dropped
+struct RowPartFoldLaunch {
+	const uint16_t* rowpart16;  // [(seg * nenc + k) * npairs + pair][rows]
+	const int32_t* unit_len;    // [nseg * nenc]
+	const int32_t* gfirst;      // [ngroups + 1]
+	int32_t ngroups, nenc, rows, npairs, stretch;      // rows: a multiple of 16, at most 112; npairs and stretch: the scan's
+	TrackTable tab;
+	uint16_t* out;              // [ngroups][4][rows]
+};
+hipError_t launch_rowfold_parts(const RowPartFoldLaunch& L, hipStream_t st);
 
 // ---- align.hip: stage 3 ---------------------------------------------------------------------------
 struct FwdLaunch {

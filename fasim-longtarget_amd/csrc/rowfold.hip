@@ -13,6 +13,7 @@
 //     (max(a, b) >> 1 == max(a >> 1, b >> 1));
 //   * the encodings of a class come from the table k_track uses, ordered by class, so the accumulators are never indexed dynamically;
 //   * one 16-byte store per (group, class, lane): every output element has one writer, no global atomics.
+// k_rowfold_parts, below it, gives the same result for an oligo of a panel from the parts of k_scan_short_rows.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "class_fold.h"
@@ -47,6 +48,50 @@ __global__ void __launch_bounds__(256) k_rowfold(RowFoldLaunch a)
 	uint16_t* out = a.out + (int64_t)g * 4 * a.rows_total + r0;
 #pragma unroll
 	for (int c = 0; c < 4; c++) *reinterpret_cast<v8u*>(out + (int64_t)c * a.rows_total) = acc[c] >> (v8u)(1);
+}
+
+// ---- k_rowfold_parts: the profile of an oligo from the parts of k_scan_short_rows -----------------------------
+// An oligo has at most 112 rows, 14 chunks of 8, and a group has tens of thousands of parts (units x stretch pairs): the parallel
+// axis is the parts.  One 256-thread workgroup per (group, class); lane t owns row chunk t % nchunk of the parts slice, slice + nslice,
+// ... of the class, slice = t / nchunk, so the lanes of neighbouring chunks read one part's neighbouring 16 bytes.  The parts of a
+// class are (segment of the group) x (encoding of the class, forward and reversed alike: the query is never mirrored) x (pair); a
+// part whose lane returned before it wrote (2 * pair * stretch >= unit_len) is skipped.  v_pk_max_u16 on the raw values, an LDS tree
+// over the slices, the taint bit dropped with one shift, one 16-byte store per (group, class, row chunk): one writer per element.
+__global__ void __launch_bounds__(256) k_rowfold_parts(RowPartFoldLaunch a)
+{
+	__shared__ v8u red[256];
+	const int g = blockIdx.x, c = blockIdx.y, t = threadIdx.x;
+	const int nchunk = a.rows / 8, nslice = 256 / nchunk;
+	const int slice = t / nchunk, chunk = t - slice * nchunk;
+	const int s0 = a.gfirst[g], s1 = a.gfirst[g + 1];
+	const int f0 = a.tab.first[c], nf = a.tab.first[c + 1] - f0, r0 = a.tab.first[4 + c], nk = nf + a.tab.first[5 + c] - r0;
+	v8u acc = (v8u)(0);
+	if (slice < nslice) {
+		const int nparts = (s1 - s0) * nk * a.npairs;
+		for (int p = slice; p < nparts; p += nslice) {
+			const int x = p / a.npairs, pair = p - x * a.npairs, s = x / nk, kk = x - s * nk;
+			const int unit = (s0 + s) * a.nenc + a.tab.k[kk < nf ? f0 + kk : r0 + kk - nf];
+			if (2 * pair * a.stretch >= a.unit_len[unit]) continue;
+			const v8u v = *reinterpret_cast<const v8u*>(a.rowpart16 + ((int64_t)unit * a.npairs + pair) * a.rows + 8 * chunk);
+			acc = __builtin_elementwise_max(acc, v);
+		}
+	}
+	red[t] = acc;
+	__syncthreads();
+	// slices [h, nslice) onto [0, nslice - h): nslice <= 2 h at the first h that does anything
+	for (int h = 128; h >= 1; h >>= 1) {
+		if (slice < h && slice + h < nslice) red[t] = __builtin_elementwise_max(red[t], red[t + h * nchunk]);
+		__syncthreads();
+	}
+	if (slice == 0) *reinterpret_cast<v8u*>(a.out + ((int64_t)g * 4 + c) * a.rows + 8 * chunk) = red[t] >> (v8u)(1);
+}
+
+hipError_t launch_rowfold_parts(const RowPartFoldLaunch& L, hipStream_t st)
+{
+	if (L.ngroups <= 0) return hipSuccess;
+	if (L.rows < 16 || L.rows > 112 || (L.rows & 15) != 0 || L.nenc < 1 || L.nenc > 48 || L.npairs < 1 || L.stretch < 16) return hipErrorInvalidValue;
+	hipLaunchKernelGGL(k_rowfold_parts, dim3((unsigned)L.ngroups, 4), dim3(256), 0, st, L);
+	return hipGetLastError();
 }
 
 hipError_t launch_rowfold(const RowFoldLaunch& L, hipStream_t st)

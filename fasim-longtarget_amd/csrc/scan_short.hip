@@ -43,6 +43,12 @@ constexpr uint32_t SS_N4 = 0x04040404u;          // four columns of code N
 constexpr uint32_t SS_F16_NEG4 = 0xC400u;        // f16 -4.0
 
 __device__ __forceinline__ uint32_t ss_add(uint32_t a, uint32_t b) { uint32_t r; asm("v_pk_add_f16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+typedef unsigned short ss_v2us __attribute__((ext_vector_type(2)));
+// v_pk_max_u16 (a builtin, not an asm: the accumulators may then stay in AGPRs between their uses)
+__device__ __forceinline__ uint32_t ss_umax(uint32_t a, uint32_t b)
+{
+	return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(ss_v2us, a), __builtin_bit_cast(ss_v2us, b)));
+}
 
 template <int ROWS>
 __global__ void __launch_bounds__(256) k_scan_short(ScanShortLaunch a)
@@ -123,11 +129,117 @@ __global__ void __launch_bounds__(256) k_scan_short(ScanShortLaunch a)
 	}
 }
 
+// ---- k_scan_short_rows: the same pass, which also leaves the row maxima of the lane's two stretches ------------
+// One more packed accumulator per row, R[i] = v_pk_max_u16(R[i], H[i] & mk) on the f16 bit patterns: the values are non-negative
+// integers, so the bits order like the values.  mk is the validity mask of the column pair: only the REAL columns of the lane's own
+// stretches count, g >= 0 and column < n.  A column of code N behind the unit's last continues the diagonal at -4 per step and can
+// exceed everything its row really holds; a warm-up column is a real column of the neighbouring stretch, or code N ahead of the unit,
+// and holds a lower bound of what the neighbour computes there, so leaving it out changes nothing.  One body for all groups: choosing
+// among an unmasked and a masked body per group costs the compiler the registers (section 24 has the numbers).
+// At its end the lane folds the two halves and writes rowpart16[unit][pair][ROWS] = 2 * value with plain 16-byte stores.  A lane that
+// returns early writes nothing: the fold (k_rowfold_parts, rowfold.hip) skips the parts with 2 * pair * L >= n.
+template <int ROWS>
+__global__ void __launch_bounds__(256) k_scan_short_rows(ScanShortLaunch a)
+{
+	__shared__ uint32_t prof[ROWS * 25];
+	for (int idx = threadIdx.x; idx < ROWS * 25; idx += 256) {
+		const int row = idx / 25, combo = idx - row * 25, clo = combo / 5, chi = combo - clo * 5;
+		uint32_t lo = 0, hi = 0;                 // pad rows score 0
+		if (row < a.m) {
+			const int q = a.qcodes[row];
+			lo = (q == clo && q < 4) ? f16c(5) : SS_F16_NEG4;
+			hi = (q == chi && q < 4) ? f16c(5) : SS_F16_NEG4;
+		}
+		prof[idx] = lo | (hi << 16);
+	}
+	__syncthreads();
+
+	const int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x;
+	const int unit = (int)(item / a.npairs), pair = (int)(item - (int64_t)unit * a.npairs);
+	if (unit >= a.nunit) return;
+	const int n = a.unit_len[unit], n16 = min((n + 15) & ~15, a.tstride), L = a.stretch, tstride = a.tstride;
+	const int sA = 2 * pair * L, sB = sA + L;     // first columns of the two stretches
+	if (sA >= n) return;
+	const uint8_t* trow = a.tcodes + (int64_t)unit * tstride;
+	uint16_t* orow = a.colmax16 + (int64_t)unit * tstride;
+	const uint32_t k4 = f16c2(4), k16 = f16c2(16), k1024 = f16c2(1024);
+
+	uint32_t H[ROWS], E[ROWS], R[ROWS];
+#pragma unroll
+	for (int i = 0; i < ROWS; i++) { H[i] = 0; E[i] = 0; R[i] = 0; }
+
+#pragma unroll 1
+	for (int g = -a.warm; g < L; g += 16) {
+		const int cA = sA + g, cB = sB + g;       // multiples of 16, like tstride: a group lies inside the unit's row or outside it
+		uint4 wa = make_uint4(SS_N4, SS_N4, SS_N4, SS_N4), wb = wa;
+		if (cA >= 0 && cA < tstride) wa = *reinterpret_cast<const uint4*>(trow + cA);
+		if (cB >= 0 && cB < tstride) wb = *reinterpret_cast<const uint4*>(trow + cB);
+		const int nv = g >= 0 ? n : 0;            // columns below nv count for the row maxima
+#pragma unroll 1
+		for (int q4 = 0; q4 < 4; q4++) {
+			uint32_t xa = wa.x, xb = wb.x;
+			uint32_t oa0 = 0, oa1 = 0, ob0 = 0, ob1 = 0;
+			const int ca = cA + 4 * q4, cb = cB + 4 * q4;
+#pragma unroll 1
+			for (int k = 0; k < 4; k++) {
+				const uint32_t* pr = prof + (min(xa & 0xffu, 4u) * 5u + min(xb & 0xffu, 4u));
+				xa >>= 8; xb >>= 8;
+				const uint32_t mk = (ca + k < nv ? 0x0000ffffu : 0u) | (cb + k < nv ? 0xffff0000u : 0u);
+				uint32_t diag = 0, f = 0, cm = 0;
+#pragma unroll
+				for (int i = 0; i < ROWS; i += 2) {
+					const uint32_t t0 = ss_add(diag, pr[i * 25]);
+					const uint32_t t1 = ss_add(H[i], pr[(i + 1) * 25]);
+					diag = H[i + 1];
+					const uint32_t h0 = (uint32_t)hf_max3((int)t0, (int)E[i], (int)f);
+					const uint32_t ho0 = (uint32_t)hf_sub_k((int)h0, k16);
+					E[i] = (uint32_t)hf_max_floor(hf_sub_k((int)E[i], k4), (int)ho0);
+					f = (uint32_t)hf_max_floor(hf_sub_k((int)f, k4), (int)ho0);
+					H[i] = h0;
+					R[i] = ss_umax(R[i], h0 & mk);
+					const uint32_t h1 = (uint32_t)hf_max3((int)t1, (int)E[i + 1], (int)f);
+					const uint32_t ho1 = (uint32_t)hf_sub_k((int)h1, k16);
+					E[i + 1] = (uint32_t)hf_max_floor(hf_sub_k((int)E[i + 1], k4), (int)ho1);
+					f = (uint32_t)hf_max_floor(hf_sub_k((int)f, k4), (int)ho1);
+					H[i + 1] = h1;
+					R[i + 1] = ss_umax(R[i + 1], h1 & mk);
+					cm = (uint32_t)hf_max3((int)cm, (int)h0, (int)h1);
+				}
+				// M < 1 024: the f16 bits of M + 1 024 are 0x6400 + M
+				uint32_t x = (ss_add(cm, k1024) & 0x03ff03ffu) << 1;
+				if (ca + k >= n) x &= 0xffff0000u;
+				if (cb + k >= n) x &= 0x0000ffffu;
+				oa0 = __builtin_amdgcn_alignbit(oa1, oa0, 16); oa1 = (oa1 >> 16) | (x << 16);
+				ob0 = __builtin_amdgcn_alignbit(ob1, ob0, 16); ob1 = (ob1 >> 16) | (x & 0xffff0000u);
+			}
+			if (g >= 0) {
+				if (ca < n16) *reinterpret_cast<uint2*>(orow + ca) = make_uint2(oa0, oa1);
+				if (cb < n16) *reinterpret_cast<uint2*>(orow + cb) = make_uint2(ob0, ob1);
+			}
+			wa = make_uint4(wa.y, wa.z, wa.w, wa.x); wb = make_uint4(wb.y, wb.z, wb.w, wb.x);
+		}
+	}
+
+	// the two stretches of a lane belong to one unit: the larger half, as 2 * value, eight rows per store
+	uint16_t* prow = a.rowpart16 + item * ROWS;
+#pragma unroll
+	for (int i = 0; i < ROWS; i += 8) {
+		uint32_t w[4];
+#pragma unroll
+		for (int j = 0; j < 4; j++) {
+			const uint32_t x0 = ss_add(R[i + 2 * j], k1024) & 0x03ff03ffu, x1 = ss_add(R[i + 2 * j + 1], k1024) & 0x03ff03ffu;
+			w[j] = (max(x0 & 0xffffu, x0 >> 16) << 1) | (max(x1 & 0xffffu, x1 >> 16) << 17);
+		}
+		*reinterpret_cast<uint4*>(prow + i) = make_uint4(w[0], w[1], w[2], w[3]);
+	}
+}
+
 template <int ROWS>
 hipError_t ss_launch(const ScanShortLaunch& L, hipStream_t st)
 {
 	const int64_t items = (int64_t)L.nunit * L.npairs;
-	hipLaunchKernelGGL(k_scan_short<ROWS>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, L);
+	if (L.rowpart16) hipLaunchKernelGGL(k_scan_short_rows<ROWS>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, L);
+	else hipLaunchKernelGGL(k_scan_short<ROWS>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, L);
 	return hipGetLastError();
 }
 

@@ -504,6 +504,29 @@ int  fasim_scan_oligos_aligned(fasim_engine* e, const char* const* oligos, const
                                int64_t seg_first, int64_t seg_count, const fasim_params* p, int32_t min_value, int32_t max_gap,
                                fasim_sites** out_sites /* [nq * nrec] */, fasim_site_hits** out_hits /* [nq * nrec] */,
                                fasim_scan_stats* totals /* [nq], may be NULL */);
+/* The per-base profile of every oligo of a panel (csrc/scan_short.hip k_scan_short_rows, csrc/rowfold.hip k_rowfold_parts, DESIGN.md
+ * section 24): fasim_scan_tfo_profile's R[c][i] with the oligo in the lncRNA's place -- the largest local alignment score that ends
+ * on base i of the oligo, over the selected units of class c and their real columns, under the scoring of fasim_scan_oligos; the pad
+ * rows are not part of the result.  out_profiles[q], or with per_record out_profiles[q * nrec + r] (what record r scanned alone
+ * gives), are fasim_tfo_profile objects: they merge with fasim_tfo_profile_merge (shards: element-wise maximum), print with
+ * fasim_tfo_profile_tsv and free with fasim_tfo_profile_free.  No value exceeds 5 * 112 = 560: saturated_units is 0.  Arguments,
+ * totals and refusals as fasim_scan_oligos (without the sites' and tracks' own); out_profiles == NULL: FASIM_E_ARG. */
+int  fasim_scan_oligos_profile(fasim_engine* e, const char* const* oligos, const int32_t* lens, int32_t nq,
+                               const char* dna, const int64_t* rec_off, const int64_t* rec_len, int32_t nrec,
+                               int64_t seg_first, int64_t seg_count, const fasim_params* p, int32_t per_record,
+                               fasim_tfo_profile** out_profiles /* [nq] or, per_record, [nq * nrec] */,
+                               fasim_scan_stats* totals /* [nq], may be NULL */);
+/* The screen of a panel (DESIGN.md section 12 with the oligo's potential): out_peaks[(q * nrec + r) * 4 + c] is the (value, pos, enc)
+ * of fasim_scan_records_track for oligo q, record r and class c -- the largest potential, its first position, the smallest encoding
+ * that attains it there, (0, -1, -1) where the potential is zero -- copied as 64 bytes per slice, not as tracks.  bin == 0: peaks only,
+ * out_tracks must be NULL; bin >= 1: out_tracks[q * nrec + r] is fasim_scan_oligos' track as well.  Peaks of shards merge with
+ * fasim_peaks_merge and print with fasim_screen_tsv.  Arguments, totals and refusals as fasim_scan_oligos (without the sites' own);
+ * out_peaks == NULL, bin < 0, bin == 0 with out_tracks, bin >= 1 without: FASIM_E_ARG. */
+int  fasim_scan_oligos_peaks(fasim_engine* e, const char* const* oligos, const int32_t* lens, int32_t nq,
+                             const char* dna, const int64_t* rec_off, const int64_t* rec_len, int32_t nrec,
+                             int64_t seg_first, int64_t seg_count, const fasim_params* p, int32_t bin,
+                             fasim_track** out_tracks /* [nq * nrec]; NULL with bin 0 */, fasim_peak* out_peaks /* [nq * nrec * 4] */,
+                             fasim_scan_stats* totals /* [nq], may be NULL */);
 
 /* ---- histograms of the potential with shuffled controls (csrc/hist.hip) -------------------------------------- */
 /* How much of a record set reaches potential v, for every v.  P[c][x] is the bin = 1 track of section 11 of a record scanned alone.
