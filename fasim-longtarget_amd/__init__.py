@@ -115,6 +115,14 @@ class _VariantWindow(C.Structure):
     _fields_ = [("pre", C.c_int32), ("post", C.c_int32), ("edge", C.c_int32), ("reserved", C.c_int32)]
 
 
+class _Genotype(C.Structure):
+    _fields_ = [("hap", C.c_int8 * 2), ("phased", C.c_uint8), ("pad", C.c_uint8)]
+
+
+class _HapScore(C.Structure):
+    _fields_ = [("hap", _VariantScore * 2), ("carried", C.c_int32 * 2), ("applied", C.c_int32 * 2), ("flags", C.c_int32 * 2)]
+
+
 class _VariantStats(C.Structure):
     _fields_ = [("problems", C.c_int64), ("cells", C.c_int64), ("kernel_s", C.c_double), ("total_s", C.c_double)]
 
@@ -199,6 +207,7 @@ EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_e
            "fasim_shuffle_query_dinuc", "fasim_site_counts_threshold", "fasim_site_counts_tsv",
            "fasim_read_vcf", "fasim_score_variants", "fasim_variants_tsv",
            "fasim_score_variants_aligned", "fasim_variant_hit_span", "fasim_variant_hits_tsv",
+           "fasim_read_vcf_sample", "fasim_haplotype_window", "fasim_haplotype_info", "fasim_score_haplotypes", "fasim_haplotypes_tsv",
            # the reference's own ssw.h ABI (include/ssw.h)
            "ssw_init", "init_destroy", "ssw_pre_align", "ssw_align", "align_destroy", "encoded_ops"]
 
@@ -375,6 +384,19 @@ def lib():
                                          C.POINTER(C.c_int64)]
     L.fasim_variants_tsv.argtypes = [C.POINTER(_Variant), C.POINTER(_VariantScore), C.c_int64, C.c_int32, C.c_char_p,
                                      C.POINTER(C.c_uint8), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.fasim_read_vcf_sample.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.POINTER(_Variant)), C.POINTER(C.c_int64),
+                                        C.POINTER(C.POINTER(_Genotype))]
+    L.fasim_haplotype_window.argtypes = [C.POINTER(_Variant), C.POINTER(_Genotype), C.c_int64, C.POINTER(C.c_uint8), C.c_int64, C.c_char_p,
+                                         C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.fasim_haplotype_info.argtypes = [C.POINTER(_Variant), C.POINTER(_Genotype), C.c_int64, C.POINTER(C.c_uint8), C.c_int64, C.c_char_p,
+                                       C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.fasim_score_haplotypes.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
+                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.POINTER(_Variant), C.POINTER(_Genotype),
+                                         C.POINTER(C.c_uint8), C.c_int64, C.c_int32, C.POINTER(Params), C.POINTER(_HapScore),
+                                         C.POINTER(_VariantStats)]
+    L.fasim_haplotypes_tsv.argtypes = [C.POINTER(_Variant), C.POINTER(_Genotype), C.POINTER(_HapScore), C.c_int64, C.c_int32, C.c_char_p,
+                                       C.c_char_p, C.POINTER(C.c_uint8), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     _lib = L
     return L
 
@@ -1783,6 +1805,40 @@ class Engine:
             return values, encs, flags, windows, [SiteHits(hts[q]) for q in range(nq)]
         return values, encs, flags
 
+    def score_haplotypes(self, variants, genotypes, dnas, p: Params | None = None, flank: int = 300, queries=None, matched=None):
+        """Variants scored on a sample's two haplotypes (fasim_score_haplotypes): `(values, encs, info)`.  values and encs are int32
+        arrays of shape (nq, nvar, 2, 2, 4): per query, entry, haplotype, allele (0 REF, 1 ALT) and strand class what score_variants()
+        gives for the entry in a record that carries the haplotype's other variants (`genotypes`: (nvar, 3) rows of hap[0], hap[1],
+        phased, as read_vcf(path, sample) returns them).  info (nq, nvar, 2, 3): per haplotype `carried` (1 this ALT, 0 REF, 2 another
+        ALT of the line, -1 missing), `applied` (neighbours with a letter in the windows) and `flags` (bit 0 clipped, bit 1 an
+        unphased heterozygote in reach was left out, bit 2 an entry in reach was rejected for overlap, bit 3 both haplotypes have
+        the same windows).  matched[k] false keeps entry k from being applied as a neighbour.  `dnas` and `queries` as for
+        score_variants().  Counters of the call: `self.last_variant_stats`."""
+        import numpy as np
+        p = p or default_params()
+        if queries is None:
+            if self.rna is None:
+                raise FasimError("score_haplotypes: no queries given and no query set", E_ARG)
+            queries = [self.rna]
+        queries = [bytes(x) for x in queries]
+        blob, offs, lens, nrec = _pack_records(dnas, rec_lens=[self.resident_len()] if dnas is None else None)
+        arr, qlens, nq, _ = _pack_queries(queries)
+        vs, _keep = _variants_to_c(variants)
+        nvar = len(variants)
+        gs = _genotypes_to_c(genotypes, nvar)
+        mt = None if matched is None else (C.c_uint8 * max(1, nvar))(*[1 if x else 0 for x in matched])
+        out = (_HapScore * max(1, nq * nvar))()
+        st = _VariantStats()
+        self._check(self._L.fasim_score_haplotypes(self._h, arr, qlens, nq, blob, offs, lens, nrec, vs, gs, mt, nvar, flank, C.byref(p), out,
+                                                   C.byref(st)))
+        self.last_variant_stats = dict(problems=st.problems, cells=st.cells, kernel_s=st.kernel_s, total_s=st.total_s)
+        flat = np.frombuffer(out, dtype=np.int32).reshape(max(1, nq * nvar), 42)[:nq * nvar]
+        per = flat[:, :36].reshape(nq, nvar, 2, 18)
+        values = per[..., 0:8].reshape(nq, nvar, 2, 2, 4).copy()
+        encs = per[..., 8:16].reshape(nq, nvar, 2, 2, 4).copy()
+        info = np.stack([flat[:, 36:38], flat[:, 38:40], flat[:, 40:42]], axis=-1).reshape(nq, nvar, 2, 3).copy()
+        return values, encs, info
+
     def score_variants_aligned(self, variants, dnas, p: Params | None = None, flank: int = 300, queries=None):
         """score_variants() and the alignment behind every score (fasim_score_variants_aligned): `(values, encs, flags, windows,
         hits)`.  The first three are exactly what score_variants() returns.  windows: (nvar, 3) int32 rows of (pre, post, edge) --
@@ -1978,20 +2034,33 @@ class Variant(NamedTuple):
     usable: bool = True
 
 
-def read_vcf(path) -> list:
+def read_vcf(path, sample=None):
     """The variants of a VCF file as `fasim --variants` reads them, one Variant per ALT allele; a refused file raises FasimError
-    with code E_ARG and the line number in the message."""
+    with code E_ARG and the line number in the message.  With `sample` (a name of the #CHROM line; fasim_read_vcf_sample):
+    `(variants, genotypes)`, genotypes an (n, 3) int8 array of hap[0], hap[1] (1 the entry's ALT, 0 not, -1 missing) and phased."""
     L = lib()
     out = C.POINTER(_Variant)()
+    gts = C.POINTER(_Genotype)()
     n = C.c_int64()
-    rc = L.fasim_read_vcf(os.fsencode(path), C.byref(out), C.byref(n))
+    if sample is None:
+        rc = L.fasim_read_vcf(os.fsencode(path), C.byref(out), C.byref(n))
+    else:
+        rc = L.fasim_read_vcf_sample(os.fsencode(path), sample.encode() if isinstance(sample, str) else bytes(sample), C.byref(out),
+                                     C.byref(n), C.byref(gts))
     if rc != 0:
         raise FasimError(L.fasim_last_error(None).decode(), rc)
     try:
-        return [Variant(out[k].line, out[k].chrom.decode(), out[k].pos, out[k].id.decode(), out[k].ref.decode(), out[k].alt.decode(),
-                        out[k].rec, out[k].alt_len >= 0) for k in range(n.value)]
+        variants = [Variant(out[k].line, out[k].chrom.decode(), out[k].pos, out[k].id.decode(), out[k].ref.decode(), out[k].alt.decode(),
+                            out[k].rec, out[k].alt_len >= 0) for k in range(n.value)]
+        if sample is None:
+            return variants
+        import numpy as np
+        g = np.array([[gts[k].hap[0], gts[k].hap[1], gts[k].phased] for k in range(n.value)], dtype=np.int8).reshape(n.value, 3)
+        return variants, g
     finally:
         L.fasim_free(out)
+        if sample is not None:
+            L.fasim_free(gts)
 
 
 def _variants_to_c(variants):
@@ -2005,6 +2074,73 @@ def _variants_to_c(variants):
         vs[k].ref_len, vs[k].alt_len = len(strs[2]), (len(strs[3]) if v.usable else -1)
         vs[k].chrom, vs[k].id, vs[k].ref, vs[k].alt = strs
     return vs, keep
+
+
+def _genotypes_to_c(genotypes, n):
+    import numpy as np
+    g = np.asarray(genotypes, dtype=np.int8).reshape(n, 3)
+    gs = (_Genotype * max(1, n))()
+    for k in range(n):
+        gs[k].hap[0], gs[k].hap[1], gs[k].phased = int(g[k, 0]), int(g[k, 1]), 1 if g[k, 2] else 0
+    return gs
+
+
+def haplotype_window(variants, genotypes, dna: bytes, v: int, hap: int, allele: int, flank: int, matched=None):
+    """`(letters, v0, edge)`: the window of entry v on haplotype `hap` for `allele` (0 REF, 1 ALT) in haplotype letters, as the
+    planner of Engine.score_haplotypes() builds it (fasim_haplotype_window, pure host code); `dna` is the record of variants[v].  The
+    allele's letters start at v0; edge bit 0 / 1: the lower / upper end was cut by the flank."""
+    L = lib()
+    n = len(variants)
+    vs, _keep = _variants_to_c(variants)
+    gs = _genotypes_to_c(genotypes, n)
+    mt = None if matched is None else (C.c_uint8 * max(1, n))(*[1 if x else 0 for x in matched])
+    text = C.c_void_p()
+    ln, v0, edge = C.c_int32(), C.c_int32(), C.c_int32()
+    dna = bytes(dna)
+    rc = L.fasim_haplotype_window(vs, gs, n, mt, len(dna), dna, v, hap, allele, flank, C.byref(text), C.byref(ln), C.byref(v0), C.byref(edge))
+    if rc != 0:
+        raise FasimError(L.fasim_last_error(None).decode(), rc)
+    try:
+        return C.string_at(text, ln.value), v0.value, edge.value
+    finally:
+        L.fasim_free(text)
+
+
+def haplotype_info(variants, genotypes, dna: bytes, v: int, flank: int, matched=None):
+    """A (2, 3) int32 array: per haplotype carried, applied and flags (without bit 0, clipped) of entry v as Engine.score_haplotypes()
+    reports them in `info` -- the part of the result that the host planner decides (fasim_haplotype_info, pure host code)."""
+    import numpy as np
+    L = lib()
+    n = len(variants)
+    vs, _keep = _variants_to_c(variants)
+    gs = _genotypes_to_c(genotypes, n)
+    mt = None if matched is None else (C.c_uint8 * max(1, n))(*[1 if x else 0 for x in matched])
+    c, a, f = (C.c_int32 * 2)(), (C.c_int32 * 2)(), (C.c_int32 * 2)()
+    dna = bytes(dna)
+    rc = L.fasim_haplotype_info(vs, gs, n, mt, len(dna), dna, v, flank, c, a, f)
+    if rc != 0:
+        raise FasimError(L.fasim_last_error(None).decode(), rc)
+    return np.array([[c[h], a[h], f[h]] for h in range(2)], dtype=np.int32)
+
+
+def haplotypes_tsv(variants, genotypes, values, encs, info, flank: int, rna_name: str, sample: str, matched=None) -> bytes:
+    """The bytes of `fasim --variants --sample`'s table for one query (fasim_haplotypes_tsv): values and encs (nvar, 2, 2, 4), info
+    (nvar, 2, 3) as Engine.score_haplotypes() returns them per query."""
+    import numpy as np
+    L = lib()
+    n = len(variants)
+    vs, _keep = _variants_to_c(variants)
+    gs = _genotypes_to_c(genotypes, n)
+    sc = (_HapScore * max(1, n))()
+    flat = np.frombuffer(sc, dtype=np.int32).reshape(max(1, n), 42)
+    info = np.asarray(info, dtype=np.int32).reshape(n, 2, 3)
+    per = flat[:n, :36].reshape(n, 2, 18)
+    per[..., 0:8] = np.asarray(values, dtype=np.int32).reshape(n, 2, 8)
+    per[..., 8:16] = np.asarray(encs, dtype=np.int32).reshape(n, 2, 8)
+    per[..., 16] = info[..., 2] & 1
+    flat[:n, 36:38], flat[:n, 38:40], flat[:n, 40:42] = info[..., 0], info[..., 1], info[..., 2]
+    mt = None if matched is None else (C.c_uint8 * max(1, n))(*[1 if x else 0 for x in matched])
+    return _text_call(L.fasim_haplotypes_tsv, vs, gs, sc, n, flank, rna_name.encode(), sample.encode(), mt)
 
 
 def variants_tsv(variants, values, encs, flags, flank: int, rna_name: str, matched=None) -> bytes:

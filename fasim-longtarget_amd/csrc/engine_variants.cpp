@@ -1,6 +1,7 @@
 // fasim-longtarget_amd/csrc/engine_variants.cpp -- fasim_score_variants: the triplex potential through variants (DESIGN.md section 19;
 // kernels: variant.hip), and the table of `fasim --variants` (fasim_variants_tsv); fasim_score_variants_aligned: the same call with
-// the alignment behind every score (section 21; kernel: variant_path.hip), its projection to the reference and its table.
+// the alignment behind every score (section 21; kernel: variant_path.hip), its projection to the reference and its table;
+// fasim_score_haplotypes: every entry on the two haplotypes of a sample (section 25; kernel: haplotype.hip), its planner and its table.
 //
 // A variant is two allele windows, a window under an enabled encoding is a problem.  Per query the variants are cut into chunks by a
 // fixed bound on buffer bytes; a chunk is: the windows' descriptions (and, for a streamed record, their letters) and the ALT letters
@@ -396,6 +397,457 @@ int fasim_variants_tsv(const fasim_variant* vars, const fasim_variant_score* sco
 		o += "\t"; o += std::to_string(top[0]); o += "\t"; o += std::to_string(top[1]); o += "\t"; o += std::to_string(top[1] - top[0]);
 		for (int a = 0; a < 2; a++) { o += "\t"; o += (top[a] > 0 && rule[a] >= 0) ? std::to_string(rule[a]) : std::string("NA"); }
 		o += "\t"; o += std::to_string(s.flags & 1); o += "\n";
+	}
+	return text_out(o, text, text_len);
+}
+
+// ---- variants on a sample's phased haplotypes (kernel: haplotype.hip) ------------------------------------------
+// The planner: per record the consistent sets A_0 and A_1, per (focus, haplotype) a walk outwards from the focus through the applied
+// neighbours until `flank` haplotype letters are collected on each side.  The window is never materialised for the device: it goes
+// there as pieces (HapPiece) over the record and the uploaded ALT letters.  A haplotype whose walk met no neighbour has the plain
+// windows and goes through fasim_score_variants; the others are units of (entry, haplotype) in chunks of their own, cut as there.
+namespace {
+
+struct HPiece { int64_t src; int32_t len; int64_t ent; };      // ent < 0: record letters [src, src + len); else letters [src, src + len) of entry ent's ALT
+struct HapSides { std::vector<HPiece> left, right; int32_t applied = 0; bool edge_lo = false, edge_hi = false; };
+// per haplotype and entry: 1 in A_h, 2 qualified but rejected for overlap, 3 qualifies but for its phase (an unphased heterozygote), else 0
+struct HapSets { std::vector<uint8_t> status[2]; std::vector<int64_t> acc[2]; };
+
+inline bool spans_meet(const fasim_variant& a, const fasim_variant& b) { return a.pos < b.pos + b.ref_len && b.pos < a.pos + a.ref_len; }
+
+// the entries of record `rec` in the order (pos, line, index)
+std::vector<int64_t> hap_order(const fasim_variant* vars, int64_t nvar, int32_t rec)
+{
+	std::vector<int64_t> ord;
+	for (int64_t k = 0; k < nvar; k++) if (vars[k].rec == rec) ord.push_back(k);
+	std::sort(ord.begin(), ord.end(), [&](int64_t a, int64_t b) {
+		return vars[a].pos != vars[b].pos ? vars[a].pos < vars[b].pos : vars[a].line != vars[b].line ? vars[a].line < vars[b].line : a < b; });
+	return ord;
+}
+
+// A_h of both haplotypes over one record's entries `ord`; status is indexed by entry (sized by the caller, zeros)
+void hap_sets(const fasim_variant* vars, const fasim_genotype* gts, const uint8_t* matched, const std::vector<int64_t>& ord, HapSets& S)
+{
+	for (int h = 0; h < 2; h++) {
+		int64_t end = INT64_MIN;      // of the last accepted span: the accepted spans are disjoint and sorted, so it is the largest
+		for (int64_t k : ord) {
+			const fasim_genotype& g = gts[k];
+			if (g.hap[h] != 1) continue;
+			if (vars[k].alt_len < 0 || (matched && !matched[k])) continue;
+			if (!g.phased && !(g.hap[0] == 1 && g.hap[1] == 1)) { S.status[h][(size_t)k] = 3; continue; }
+			if (vars[k].pos < end) { S.status[h][(size_t)k] = 2; continue; }
+			S.status[h][(size_t)k] = 1; S.acc[h].push_back(k); end = vars[k].pos + vars[k].ref_len;
+		}
+	}
+}
+
+// the flanks of focus v on the haplotype whose consistent set is acc, in a record of len letters
+void hap_walk(const fasim_variant* vars, const std::vector<int64_t>& acc, int64_t v, int64_t len, int32_t flank, HapSides& S)
+{
+	const fasim_variant& x = vars[v];
+	auto skip = [&](int64_t u) { return vars[u].line == x.line || spans_meet(vars[u], x); };      // not an applied neighbour of v
+	const int64_t first = std::lower_bound(acc.begin(), acc.end(), x.pos, [&](int64_t u, int64_t p) { return vars[u].pos < p; }) - acc.begin();
+	int64_t need = flank, at = x.pos;
+	bool cut = false;
+	for (int64_t i = first - 1; need > 0; i--) {
+		while (i >= 0 && skip(acc[(size_t)i])) i--;
+		if (i < 0) { const int64_t take = std::min(need, at); if (take) S.left.push_back({ at - take, (int32_t)take, -1 }); at -= take; break; }
+		const fasim_variant& y = vars[acc[(size_t)i]];
+		const int64_t take = std::min(need, at - (y.pos + y.ref_len));
+		if (take) { S.left.push_back({ at - take, (int32_t)take, -1 }); at -= take; need -= take; }
+		if (!need) break;
+		const int64_t t = std::min<int64_t>(need, y.alt_len);
+		S.left.push_back({ y.alt_len - t, (int32_t)t, acc[(size_t)i] }); need -= t; S.applied++;
+		if (t < y.alt_len) { cut = true; break; }
+		at = y.pos;
+	}
+	S.edge_lo = cut || at > 0;
+	std::reverse(S.left.begin(), S.left.end());
+	need = flank; at = x.pos + x.ref_len; cut = false;
+	for (size_t i = (size_t)first; need > 0; i++) {
+		while (i < acc.size() && skip(acc[i])) i++;
+		if (i >= acc.size()) { const int64_t take = std::min(need, len - at); if (take) S.right.push_back({ at, (int32_t)take, -1 }); at += take; break; }
+		const fasim_variant& y = vars[acc[i]];
+		const int64_t take = std::min(need, y.pos - at);
+		if (take) { S.right.push_back({ at, (int32_t)take, -1 }); at += take; need -= take; }
+		if (!need) break;
+		const int64_t t = std::min<int64_t>(need, y.alt_len);
+		S.right.push_back({ 0, (int32_t)t, acc[i] }); need -= t; S.applied++;
+		if (t < y.alt_len) { cut = true; break; }
+		at = y.pos + y.ref_len;
+	}
+	S.edge_hi = cut || at < len;
+}
+
+inline int32_t pieces_len(const std::vector<HPiece>& p) { int32_t n = 0; for (const HPiece& q : p) n += q.len; return n; }
+
+void pieces_letters(const fasim_variant* vars, const char* record, const std::vector<HPiece>& p, std::string& o)
+{
+	for (const HPiece& q : p) o.append(q.ent < 0 ? record + q.src : vars[q.ent].alt + q.src, (size_t)q.len);
+}
+
+inline bool pieces_equal(const std::vector<HPiece>& a, const std::vector<HPiece>& b)
+{
+	if (a.size() != b.size()) return false;
+	for (size_t k = 0; k < a.size(); k++) if (a[k].src != b[k].src || a[k].len != b[k].len || a[k].ent != b[k].ent) return false;
+	return true;
+}
+
+// do both haplotypes of a focus have the same windows?  The same pieces, or other pieces with the same letters and the same ends
+bool hap_sides_equal(const fasim_variant* vars, const char* record, const HapSides* W, std::string (&w)[2])
+{
+	if (W[0].applied == 0 && W[1].applied == 0) return true;
+	if (pieces_equal(W[0].left, W[1].left) && pieces_equal(W[0].right, W[1].right)) return true;
+	if (W[0].edge_lo != W[1].edge_lo || W[0].edge_hi != W[1].edge_hi || pieces_len(W[0].left) != pieces_len(W[1].left) ||
+		pieces_len(W[0].right) != pieces_len(W[1].right)) return false;
+	for (int h = 0; h < 2; h++) { w[h].clear(); pieces_letters(vars, record, W[h].left, w[h]); pieces_letters(vars, record, W[h].right, w[h]); }
+	return w[0] == w[1];
+}
+
+// the refusals of fasim_score_variants for the entries themselves
+int check_variant_entries(fasim_engine* E, const fasim_variant* vars, int64_t nvar, const int64_t* rec_len, int32_t nrec)
+{
+	for (int64_t v = 0; v < nvar; v++) {
+		const fasim_variant& x = vars[v];
+		if (x.alt_len < 0) continue;
+		if (x.ref_len < 1) return fail(E, FASIM_E_ARG, "variant %lld: ref_len %d < 1", (long long)v, x.ref_len);
+		if (x.ref_len > FASIM_MAX_ALLELE || x.alt_len < 1 || x.alt_len > FASIM_MAX_ALLELE || !x.alt)
+			return fail(E, FASIM_E_ARG, "variant %lld: an allele has 1 to %d letters (REF %d, ALT %d)", (long long)v, FASIM_MAX_ALLELE, x.ref_len, x.alt_len);
+		if (x.rec < 0 || x.rec >= nrec) return fail(E, FASIM_E_ARG, "variant %lld: record %d of %d", (long long)v, x.rec, nrec);
+		if (x.pos < 0 || x.pos > rec_len[x.rec] - x.ref_len)
+			return fail(E, FASIM_E_ARG, "variant %lld: [%lld, %lld) lies outside record %d of %lld nt", (long long)v, (long long)x.pos,
+				(long long)(x.pos + x.ref_len), x.rec, (long long)rec_len[x.rec]);
+	}
+	return FASIM_OK;
+}
+
+// carried, and flag bits 1 and 2, of focus v on haplotype h: one look at the record's entries within reach
+void hap_context(const fasim_variant* vars, const fasim_genotype* gts, const std::vector<int64_t>& ord, const HapSets& S, int64_t v, int h,
+	int32_t flank, int32_t& carried, int32_t& flags)
+{
+	const fasim_variant& x = vars[v];
+	const int64_t reach = (int64_t)flank + FASIM_MAX_ALLELE;
+	bool other_alt = false;
+	auto it = std::lower_bound(ord.begin(), ord.end(), x.pos - reach, [&](int64_t u, int64_t p) { return vars[u].pos < p; });
+	for (; it != ord.end() && vars[*it].pos <= x.pos + reach; ++it) {
+		const int64_t u = *it;
+		if (vars[u].line == x.line) { if (u != v && vars[u].pos == x.pos && gts[u].hap[h] == 1) other_alt = true; continue; }
+		const uint8_t st = S.status[h][(size_t)u];
+		if (st == 3) flags |= 2;
+		if (st == 2 || (st == 1 && spans_meet(vars[u], x))) flags |= 4;
+	}
+	carried = gts[v].hap[h] == 1 ? 1 : gts[v].hap[h] < 0 ? -1 : other_alt ? 2 : 0;
+}
+
+}  // namespace
+
+int fasim_haplotype_window(const fasim_variant* vars, const fasim_genotype* gts, int64_t nvar, const uint8_t* matched, int64_t rec_len,
+	const char* record, int64_t v, int32_t hap, int32_t allele, int32_t flank, char** letters, int32_t* n, int32_t* v0, int32_t* edge)
+{
+	if (!vars || !gts || !record || !letters || !n || !v0 || !edge || v < 0 || v >= nvar || hap < 0 || hap > 1 || allele < 0 || allele > 1)
+		return fail(nullptr, FASIM_E_ARG, "bad arguments");
+	if (flank < 0 || flank > FASIM_MAX_FLANK) return fail(nullptr, FASIM_E_ARG, "flank %d lies outside [0, %d]", flank, FASIM_MAX_FLANK);
+	const fasim_variant& x = vars[v];
+	if (x.alt_len < 0) return fail(nullptr, FASIM_E_ARG, "variant %lld cannot be scored", (long long)v);
+	for (int64_t k = 0; k < nvar; k++) {
+		const fasim_variant& y = vars[k];
+		if (y.rec != x.rec || y.alt_len < 0) continue;
+		if (y.ref_len < 1 || y.ref_len > FASIM_MAX_ALLELE || y.alt_len < 1 || y.alt_len > FASIM_MAX_ALLELE || !y.alt || y.pos < 0 || y.pos > rec_len - y.ref_len)
+			return fail(nullptr, FASIM_E_ARG, "variant %lld: alleles of 1 to %d letters inside the record of %lld nt", (long long)k, FASIM_MAX_ALLELE, (long long)rec_len);
+	}
+	try {
+		const std::vector<int64_t> ord = hap_order(vars, nvar, x.rec);
+		HapSets S;
+		S.status[0].assign((size_t)nvar, 0); S.status[1].assign((size_t)nvar, 0);
+		hap_sets(vars, gts, matched, ord, S);
+		HapSides W;
+		hap_walk(vars, S.acc[hap], v, rec_len, flank, W);
+		std::string o;
+		pieces_letters(vars, record, W.left, o);
+		*v0 = (int32_t)o.size();
+		if (allele) o.append(x.alt, (size_t)x.alt_len); else o.append(record + x.pos, (size_t)x.ref_len);
+		pieces_letters(vars, record, W.right, o);
+		*edge = (W.edge_lo ? 1 : 0) | (W.edge_hi ? 2 : 0);
+		int64_t len = 0;
+		const int rc = text_out(o, letters, &len);
+		*n = (int32_t)len;
+		return rc;
+	} catch (const std::bad_alloc&) { return fail(nullptr, FASIM_E_NOMEM, "out of memory"); }
+}
+
+int fasim_haplotype_info(const fasim_variant* vars, const fasim_genotype* gts, int64_t nvar, const uint8_t* matched, int64_t rec_len,
+	const char* record, int64_t v, int32_t flank, int32_t* carried, int32_t* applied, int32_t* flags)
+{
+	if (!vars || !gts || !record || !carried || !applied || !flags || v < 0 || v >= nvar) return fail(nullptr, FASIM_E_ARG, "bad arguments");
+	// (the checks of fasim_haplotype_window)
+	char* letters = nullptr; int32_t n = 0, v0 = 0, edge = 0;
+	const int rc = fasim_haplotype_window(vars, gts, nvar, matched, rec_len, record, v, 0, 0, flank, &letters, &n, &v0, &edge); if (rc) return rc;
+	free(letters);
+	try {
+		const std::vector<int64_t> ord = hap_order(vars, nvar, vars[v].rec);
+		HapSets S;
+		S.status[0].assign((size_t)nvar, 0); S.status[1].assign((size_t)nvar, 0);
+		hap_sets(vars, gts, matched, ord, S);
+		HapSides W[2];
+		std::string w[2];
+		for (int h = 0; h < 2; h++) {
+			flags[h] = 0;
+			hap_context(vars, gts, ord, S, v, h, flank, carried[h], flags[h]);
+			hap_walk(vars, S.acc[h], v, rec_len, flank, W[h]);
+			applied[h] = W[h].applied;
+		}
+		if (hap_sides_equal(vars, record, W, w)) { flags[0] |= 8; flags[1] |= 8; }
+		return FASIM_OK;
+	} catch (const std::bad_alloc&) { return fail(nullptr, FASIM_E_NOMEM, "out of memory"); }
+}
+
+int fasim_score_haplotypes(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna,
+	const int64_t* rec_off, const int64_t* rec_len, int32_t nrec, const fasim_variant* vars, const fasim_genotype* gts, const uint8_t* matched,
+	int64_t nvar, int32_t flank, const fasim_params* pp, fasim_hap_score* out, fasim_variant_stats* stats)
+{
+	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
+	if (nvar < 0 || (nvar > 0 && (!vars || !gts || !out))) return fail(E, FASIM_E_ARG, "bad arguments");
+	// the refusals of fasim_score_variants: the call's own with no entry (no GPU work), then the entries'
+	fasim_variant_stats st0;
+	int rc = fasim_score_variants(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, vars, 0, flank, pp, nullptr, &st0); if (rc) return rc;
+	rc = check_variant_entries(E, vars, nvar, rec_len, nrec); if (rc) return rc;
+	RecordSet rs;
+	rc = record_set_open(E, dna, rec_off, rec_len, nrec, false, rs); if (rc) return rc;
+	const bool resident = rs.resident;
+	const char* host = rs.host(E);
+	const double t0 = now_s();
+	if (stats) memset(stats, 0, sizeof *stats);
+	for (int64_t k = 0; k < (int64_t)nq * nvar; k++) {
+		memset(&out[k], 0, sizeof out[k]);
+		for (int h = 0; h < 2; h++) for (int a = 0; a < 2; a++) for (int c = 0; c < FASIM_TRACK_CLASSES; c++) out[k].hap[h].enc[a][c] = -1;
+	}
+	const std::vector<int> encs = enabled_encodings(*pp);
+	const int nenc = (int)encs.size();
+	struct Unit { int64_t v; int h; };
+	try {
+		// ---- the plan ----
+		std::vector<HapSides> sides((size_t)nvar * 2);
+		std::vector<uint8_t> same((size_t)nvar, 0);
+		std::vector<int64_t> plain;                    // entries with a haplotype on the plain windows
+		std::vector<int64_t> plain_at((size_t)nvar, -1);
+		std::vector<Unit> units;
+		std::vector<int64_t> unit_at((size_t)nvar * 2, -1);
+		{
+			std::vector<std::vector<int64_t>> by_rec((size_t)nrec);
+			for (int64_t k = 0; k < nvar; k++) if (vars[k].rec >= 0 && vars[k].rec < nrec) by_rec[(size_t)vars[k].rec].push_back(k);
+			HapSets S;
+			S.status[0].assign((size_t)nvar, 0); S.status[1].assign((size_t)nvar, 0);
+			std::string w[2];
+			for (int32_t r = 0; r < nrec; r++) {
+				std::vector<int64_t>& ord = by_rec[(size_t)r];
+				if (ord.empty()) continue;
+				std::sort(ord.begin(), ord.end(), [&](int64_t a, int64_t b) {
+					return vars[a].pos != vars[b].pos ? vars[a].pos < vars[b].pos : vars[a].line != vars[b].line ? vars[a].line < vars[b].line : a < b; });
+				S.acc[0].clear(); S.acc[1].clear();
+				hap_sets(vars, gts, matched, ord, S);
+				const char* record = host + rec_off[r];
+				for (int64_t v : ord) {
+					int32_t carried[2] = { 0, 0 }, flags[2] = { 0, 0 };
+					for (int h = 0; h < 2; h++) hap_context(vars, gts, ord, S, v, h, flank, carried[h], flags[h]);
+					for (int q = 0; q < nq; q++) for (int h = 0; h < 2; h++) { out[(size_t)q * (size_t)nvar + (size_t)v].carried[h] = carried[h]; out[(size_t)q * (size_t)nvar + (size_t)v].flags[h] = vars[v].alt_len < 0 ? 0 : flags[h]; }
+					if (vars[v].alt_len < 0) continue;
+					HapSides* W = &sides[(size_t)v * 2];
+					for (int h = 0; h < 2; h++) hap_walk(vars, S.acc[h], v, rec_len[r], flank, W[h]);
+					const bool eq = hap_sides_equal(vars, record, W, w);
+					same[(size_t)v] = eq;
+					for (int h = 0; h < (eq ? 1 : 2); h++) {
+						if (W[h].applied == 0) { if (plain_at[(size_t)v] < 0) { plain_at[(size_t)v] = (int64_t)plain.size(); plain.push_back(v); } }
+						else { unit_at[(size_t)v * 2 + (size_t)h] = (int64_t)units.size(); units.push_back({ v, h }); }
+					}
+					for (int q = 0; q < nq; q++) for (int h = 0; h < 2; h++) out[(size_t)q * (size_t)nvar + (size_t)v].applied[h] = W[h].applied;
+				}
+			}
+		}
+		// ---- the plain windows: fasim_score_variants itself ----
+		std::vector<fasim_variant> pv(plain.size());
+		for (size_t k = 0; k < plain.size(); k++) pv[k] = vars[plain[k]];
+		std::vector<fasim_variant_score> ps((size_t)nq * plain.size());
+		fasim_variant_stats pst;
+		memset(&pst, 0, sizeof pst);
+		if (!plain.empty()) {
+			rc = fasim_score_variants(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, pv.data(), (int64_t)pv.size(), flank, pp, ps.data(), &pst);
+			if (rc) return rc;
+		}
+		// ---- the units with neighbours: k_hap_encode, then the kernels of section 19 ----
+		std::vector<fasim_variant_score> us((size_t)nq * units.size());
+		for (fasim_variant_score& s : us) { memset(&s, 0, sizeof s); for (int a = 0; a < 2; a++) for (int c = 0; c < FASIM_TRACK_CLASSES; c++) s.enc[a][c] = -1; }
+		int64_t nprobs = 0, cells = 0;
+		const double ms0 = E->kernel_ms[4];
+		if (!units.empty() && nenc > 0) {
+			HIPOK(hipSetDevice(E->device));
+			for (int q = 0; q < nq; q++) {
+				const int m = rna_lens[q];
+				std::vector<uint8_t> qc((size_t)m);
+				for (int i = 0; i < m; i++) qc[(size_t)i] = code2(rnas[q][i]);
+				rc = upload(E, E->vr_q, qc.data(), qc.size()); if (rc) return rc;
+				const bool rows_hbm = m > TOUCH_LDS_ROWS;
+				const size_t row_bytes = (size_t)6 * (size_t)touch_state_rows(m);      // of one problem
+				for (size_t u0 = 0; u0 < units.size(); ) {
+					std::vector<HapWindow> wins;
+					std::vector<HapPiece> pieces;
+					std::vector<int32_t> ends;
+					std::vector<TouchProb> probs;
+					std::vector<uint8_t> alts, letters;
+					size_t tbytes = 0, u1 = u0;
+					for (; u1 < units.size(); u1++) {
+						const Unit& U = units[u1];
+						const fasim_variant& x = vars[U.v];
+						const HapSides& W = sides[(size_t)U.v * 2 + (size_t)U.h];
+						const int pre = pieces_len(W.left), post = pieces_len(W.right);
+						const int n_al[2] = { pre + x.ref_len + post, pre + x.alt_len + post };
+						const size_t need = (size_t)nenc * (size_t)(pad16(n_al[0]) + pad16(n_al[1]));
+						if (u1 > u0 && (tbytes + need > VR_TCODE_BYTES || (int64_t)probs.size() + 2 * nenc > VR_MAX_PROBS ||
+							(rows_hbm && (probs.size() + 2 * (size_t)nenc) * row_bytes > VR_ROW_BYTES))) break;
+						// the unit's pieces for the device: record letters in the resident buffer or staged for this chunk, ALT letters uploaded
+						auto device_piece = [&](const HPiece& p) {
+							HapPiece D; D.pad = 0;
+							if (p.ent < 0) {
+								D.alt = 0; D.src = rec_off[x.rec] + p.src;
+								if (!resident) { D.src = (int64_t)letters.size(); letters.insert(letters.end(), dna + rec_off[x.rec] + p.src, dna + rec_off[x.rec] + p.src + p.len); }
+							} else {
+								D.alt = 1; D.src = (int64_t)alts.size();
+								alts.insert(alts.end(), vars[p.ent].alt + p.src, vars[p.ent].alt + p.src + p.len);
+							}
+							return D;
+						};
+						std::vector<HapPiece> dl, dr;
+						for (const HPiece& p : W.left) dl.push_back(device_piece(p));
+						for (const HPiece& p : W.right) dr.push_back(device_piece(p));
+						const HPiece focus[2] = { { x.pos, x.ref_len, -1 }, { 0, x.alt_len, U.v } };
+						const int edge_lo = W.edge_lo, edge_hi = W.edge_hi;
+						for (int al = 0; al < 2; al++) {
+							HapWindow H; H.piece0 = (int64_t)pieces.size(); H.npiece = (int32_t)(dl.size() + 1 + dr.size()); H.pad = 0;
+							int32_t run = 0;
+							for (size_t k = 0; k < dl.size(); k++) { pieces.push_back(dl[k]); run += W.left[k].len; ends.push_back(run); }
+							pieces.push_back(device_piece(focus[al])); run += focus[al].len; ends.push_back(run);
+							for (size_t k = 0; k < dr.size(); k++) { pieces.push_back(dr[k]); run += W.right[k].len; ends.push_back(run); }
+							const int n = n_al[al], v0 = pre, v1 = pre + focus[al].len;
+							if (run != n || n > TOUCH_MAX_COLS) return fail(E, FASIM_E_ARG, "haplotypes: a window of %d letters in pieces of %d", n, run);
+							for (int k = 0; k < nenc; k++) {
+								const int enc = encs[(size_t)k];
+								TouchProb P; P.tbase = (int64_t)tbytes; P.n = n; P.win = (int32_t)wins.size(); P.enc = enc;
+								if (enc & 1) { P.v0 = n - v1; P.v1 = n - v0; P.edge = edge_hi | (edge_lo << 1); }
+								else { P.v0 = v0; P.v1 = v1; P.edge = edge_lo | (edge_hi << 1); }
+								probs.push_back(P);
+								tbytes += (size_t)pad16(n);
+								cells += (int64_t)m * n;
+							}
+							wins.push_back(H);
+						}
+					}
+					const int np = (int)probs.size(), nu = (int)(u1 - u0);
+					nprobs += np;
+					if (alts.empty()) alts.push_back(0);
+					if (E->vr_hwins.ensure(wins.size() * sizeof(HapWindow)) != hipSuccess || E->vr_pieces.ensure(pieces.size() * sizeof(HapPiece)) != hipSuccess ||
+						E->vr_ends.ensure(ends.size() * sizeof(int32_t)) != hipSuccess || E->vr_probs.ensure((size_t)np * sizeof(TouchProb)) != hipSuccess ||
+						E->vr_alt.ensure(alts.size()) != hipSuccess || E->vr_tcodes.ensure(tbytes) != hipSuccess || E->vr_touch.ensure((size_t)np * sizeof(uint32_t)) != hipSuccess ||
+						E->vr_out.ensure((size_t)nu * 9 * sizeof(uint32_t)) != hipSuccess || (!resident && E->vr_dna.ensure(letters.size() + 1) != hipSuccess) ||
+						(rows_hbm && E->vr_rows.ensure((size_t)np * row_bytes) != hipSuccess)) {
+						(void)hipGetLastError();
+						return fail(E, FASIM_E_NOMEM, "haplotypes: no device memory for a chunk of %d problems", np);
+					}
+					HIPOK(hipMemcpyAsync(E->vr_hwins.p, wins.data(), wins.size() * sizeof(HapWindow), hipMemcpyHostToDevice, E->st));
+					HIPOK(hipMemcpyAsync(E->vr_pieces.p, pieces.data(), pieces.size() * sizeof(HapPiece), hipMemcpyHostToDevice, E->st));
+					HIPOK(hipMemcpyAsync(E->vr_ends.p, ends.data(), ends.size() * sizeof(int32_t), hipMemcpyHostToDevice, E->st));
+					HIPOK(hipMemcpyAsync(E->vr_probs.p, probs.data(), (size_t)np * sizeof(TouchProb), hipMemcpyHostToDevice, E->st));
+					HIPOK(hipMemcpyAsync(E->vr_alt.p, alts.data(), alts.size(), hipMemcpyHostToDevice, E->st));
+					if (!resident && !letters.empty()) HIPOK(hipMemcpyAsync(E->vr_dna.p, letters.data(), letters.size(), hipMemcpyHostToDevice, E->st));
+					HapEncodeLaunch EL;
+					EL.dna = resident ? E->dna_res.as<uint8_t>() : E->vr_dna.as<uint8_t>(); EL.alts = E->vr_alt.as<uint8_t>(); EL.wins = E->vr_hwins.as<HapWindow>();
+					EL.pieces = E->vr_pieces.as<HapPiece>(); EL.ends = E->vr_ends.as<int32_t>();
+					EL.probs = E->vr_probs.as<TouchProb>(); EL.nprob = np; EL.enc_lut = E->enc_lut.as<uint8_t>(); EL.tcodes = E->vr_tcodes.as<uint8_t>();
+					hipError_t he = launch_hap_encode(EL, E->st);
+					if (he != hipSuccess) return fail(E, FASIM_E_HIP, "haplotypes (encode) launch failed: %s", hipGetErrorString(he));
+					TouchLaunch TL;
+					TL.tcodes = E->vr_tcodes.as<uint8_t>(); TL.qcodes = E->vr_q.as<uint8_t>(); TL.m = m; TL.probs = E->vr_probs.as<TouchProb>(); TL.nprob = np;
+					TL.rows = rows_hbm ? E->vr_rows.as<uint16_t>() : nullptr; TL.out = E->vr_touch.as<uint32_t>();
+					{ TimedScope ts(E, 4); he = launch_touch(TL, E->st); }
+					if (he != hipSuccess) return fail(E, FASIM_E_HIP, "haplotypes (touch) launch failed: %s", hipGetErrorString(he));
+					TouchReduceLaunch RL;
+					RL.touch = E->vr_touch.as<uint32_t>(); RL.nvar = nu; RL.nenc = nenc; RL.out = E->vr_out.as<uint32_t>();
+					memset(RL.enc, 0, sizeof RL.enc);
+					for (int k = 0; k < nenc; k++) RL.enc[k] = (uint8_t)encs[(size_t)k];
+					he = launch_touch_reduce(RL, E->st);
+					if (he != hipSuccess) return fail(E, FASIM_E_HIP, "haplotypes (reduce) launch failed: %s", hipGetErrorString(he));
+					std::vector<uint32_t> words((size_t)nu * 9);
+					HIPOK(hipMemcpyAsync(words.data(), E->vr_out.p, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st));
+					HIPOK(hipStreamSynchronize(E->st));
+					drain_timed(E);
+					for (int k = 0; k < nu; k++) {
+						fasim_variant_score& s = us[(size_t)q * units.size() + u0 + (size_t)k];
+						for (int a = 0; a < 2; a++) for (int c = 0; c < FASIM_TRACK_CLASSES; c++) {
+							const uint32_t w = words[(size_t)k * 9 + (size_t)a * 4 + (size_t)c];
+							s.value[a][c] = (int32_t)(w >> 9);
+							s.enc[a][c] = (w >> 9) ? (int32_t)(w & 0xff) : -1;
+						}
+						s.flags = (int32_t)(words[(size_t)k * 9 + 8] & 1);
+					}
+					u0 = u1;
+				}
+			}
+		}
+		// ---- both parts into the entries ----
+		for (int q = 0; q < nq; q++) for (int64_t v = 0; v < nvar; v++) {
+			if (vars[v].alt_len < 0 || vars[v].rec < 0 || vars[v].rec >= nrec) continue;
+			fasim_hap_score& o = out[(size_t)q * (size_t)nvar + (size_t)v];
+			for (int h = 0; h < 2; h++) {
+				const int hs = same[(size_t)v] ? 0 : h;      // the haplotype that was computed
+				const int64_t u = unit_at[(size_t)v * 2 + (size_t)hs];
+				o.hap[h] = u >= 0 ? us[(size_t)q * units.size() + (size_t)u] : ps[(size_t)q * plain.size() + (size_t)plain_at[(size_t)v]];
+				o.flags[h] |= (o.hap[h].flags & 1) | (same[(size_t)v] ? 8 : 0);
+			}
+		}
+		if (stats) {
+			stats->problems = pst.problems + nprobs; stats->cells = pst.cells + cells;
+			stats->kernel_s = pst.kernel_s + (units.empty() ? 0.0 : (E->kernel_ms[4] - ms0) * 1e-3); stats->total_s = now_s() - t0;
+		}
+	} catch (const std::bad_alloc&) { (void)hipStreamSynchronize(E->st); return fail(E, FASIM_E_NOMEM, "out of memory"); }
+	return FASIM_OK;
+}
+
+int fasim_haplotypes_tsv(const fasim_variant* vars, const fasim_genotype* gts, const fasim_hap_score* scores, int64_t nvar, int32_t flank,
+	const char* rna_name, const char* sample, const uint8_t* matched, char** text, int64_t* text_len)
+{
+	if (nvar < 0 || !rna_name || !sample || !text || !text_len || (nvar > 0 && (!vars || !gts || !scores))) return fail(nullptr, FASIM_E_ARG, "bad arguments");
+	std::string o = "# fasim haplotypes lncRNA="; o += rna_name; o += " sample="; o += sample; o += " flank="; o += std::to_string(flank); o += "\n";
+	o += "line\tchrom\tpos\tid\tref\talt\tgt";
+	for (const char* h : { "h1", "h2" }) {
+		const std::string pre = std::string("\t") + h + "_";
+		o += pre + "carried" + pre + "applied";
+		for (const char* c : CLASS_NAMES) { o += pre + c + "_ref" + pre + c + "_alt"; }
+		for (const char* c : { "max_ref", "max_alt", "delta", "rule_ref", "rule_alt", "value", "flags" }) o += pre + c;
+	}
+	o += "\tdiplotype_max\n";
+	const int ncol = 2 * (2 + 2 * FASIM_TRACK_CLASSES + 7) + 1;
+	for (int64_t k = 0; k < nvar; k++) {
+		const fasim_variant& x = vars[k];
+		if (!x.chrom || !x.id || !x.ref || !x.alt) return fail(nullptr, FASIM_E_ARG, "variant %lld lacks a string", (long long)k);
+		o += std::to_string(x.line); o += "\t"; o += x.chrom; o += "\t"; o += std::to_string(x.pos + 1); o += "\t"; o += x.id; o += "\t"; o += x.ref; o += "\t"; o += x.alt;
+		const fasim_genotype& g = gts[k];
+		o += "\t"; o += g.hap[0] < 0 ? "." : g.hap[0] ? "1" : "0"; o += g.phased ? "|" : "/"; o += g.hap[1] < 0 ? "." : g.hap[1] ? "1" : "0";
+		if ((matched && !matched[k]) || x.alt_len < 0) { for (int c = 0; c < ncol; c++) o += "\tNA"; o += "\n"; continue; }
+		const fasim_hap_score& S = scores[k];
+		int value[2] = { -1, -1 };
+		for (int h = 0; h < 2; h++) {
+			const fasim_variant_score& s = S.hap[h];
+			o += "\t"; o += std::to_string(S.carried[h]); o += "\t"; o += std::to_string(S.applied[h]);
+			int top[2] = { 0, 0 }, rule[2] = { -1, -1 };
+			for (int c = 0; c < FASIM_TRACK_CLASSES; c++) {
+				o += "\t"; o += std::to_string(s.value[0][c]); o += "\t"; o += std::to_string(s.value[1][c]);
+				for (int a = 0; a < 2; a++) if (s.value[a][c] > top[a]) { top[a] = s.value[a][c]; rule[a] = (s.enc[a][c] >= 0 && s.enc[a][c] < 48) ? enc_info(s.enc[a][c]).rule : -1; }
+			}
+			o += "\t"; o += std::to_string(top[0]); o += "\t"; o += std::to_string(top[1]); o += "\t"; o += std::to_string(top[1] - top[0]);
+			for (int a = 0; a < 2; a++) { o += "\t"; o += (top[a] > 0 && rule[a] >= 0) ? std::to_string(rule[a]) : std::string("NA"); }
+			if (S.carried[h] == 0 || S.carried[h] == 1) value[h] = top[S.carried[h]];
+			o += "\t"; o += value[h] >= 0 ? std::to_string(value[h]) : std::string("NA");
+			o += "\t"; o += std::to_string(S.flags[h]);
+		}
+		o += "\t"; o += (value[0] >= 0 && value[1] >= 0) ? std::to_string(std::max(value[0], value[1])) : std::string("NA"); o += "\n";
 	}
 	return text_out(o, text, text_len);
 }

@@ -88,6 +88,12 @@
 //                           header line, then one line per (VCF line, ALT, allele, class) with a value: line chrom pos id ref alt
 //                           allele class value rule strand tts_start tts_end tfo_start tfo_end nt identity stability cigar clipped
 //                           TFO TTS.  The .variants.tsv file does not change.  Without --variants: status 2
+//     --sample NAME         with --variants: every entry scored on the two haplotypes of sample NAME of the VCF as well (GT through
+//                           FORMAT, the sample by its name in the #CHROM line): the haplotype's other variants, where they are
+//                           phased or homozygous, stand in the window.  One more table per lncRNA,
+//                           <O>/<lnc>-<f1 minus 3 chars>.haplotypes.tsv (fasim_score_haplotypes); the other
+//                           tables do not change.  Status 2, nothing written: without --variants, a sample the VCF does not name,
+//                           a line without its column, no GT in FORMAT, a malformed GT
 //     --screen              with --regions or --all-records: one table per lncRNA, <O>/<lnc>-<f1 stem>.screen.tsv, one line per
 //                           interval (BED order) or record: per strand class the peak of its potential, where it lies (0-based
 //                           genome coordinate) and the rule of the encoding that attains it (fasim_screen_tsv, DESIGN.md section
@@ -650,11 +656,16 @@ struct HitGather {
 };
 
 static int run_variants(const std::string& vcf_path, int flank, const std::string& f1, const std::string& f2, const std::string& outdir, int device,
-	bool upper, const fasim_params& p, bool want_hits)
+	bool upper, const fasim_params& p, bool want_hits, const std::string& sample)
 {
 	fasim_variant* vars = nullptr; int64_t nvar = 0;
-	if (fasim_read_vcf(vcf_path.c_str(), &vars, &nvar) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 2; }
+	fasim_genotype* gts = nullptr;
+	const bool want_haps = !sample.empty();
+	if ((want_haps ? fasim_read_vcf_sample(vcf_path.c_str(), sample.c_str(), &vars, &nvar, &gts) : fasim_read_vcf(vcf_path.c_str(), &vars, &nvar)) != FASIM_OK) {
+		fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 2;
+	}
 	std::unique_ptr<fasim_variant, void (*)(void*)> owner(vars, fasim_free);
+	std::unique_ptr<fasim_genotype, void (*)(void*)> gowner(gts, fasim_free);
 	std::vector<Rna> rnas;
 	DnaReader reader;
 	reader.upper = upper;
@@ -672,6 +683,7 @@ static int run_variants(const std::string& vcf_path, int flank, const std::strin
 	// state of an entry: 0 not met, 1 scored, 2 REF differs, 3 unusable alleles
 	std::vector<uint8_t> state((size_t)nvar, 0);
 	std::vector<std::vector<fasim_variant_score>> scores((size_t)nq, std::vector<fasim_variant_score>((size_t)nvar));
+	std::vector<std::vector<fasim_hap_score>> haps(want_haps ? (size_t)nq : 0, std::vector<fasim_hap_score>((size_t)nvar));
 	std::vector<fasim_variant_window> windows(want_hits ? (size_t)nvar : 0);
 	std::vector<HitGather> gathered;
 	if (want_hits) { memset(windows.data(), 0, windows.size() * sizeof(fasim_variant_window)); for (int q = 0; q < nq; q++) gathered.emplace_back(nvar); }
@@ -679,7 +691,8 @@ static int run_variants(const std::string& vcf_path, int flank, const std::strin
 	std::set<std::string> chroms_seen;
 	for (int64_t k = 0; k < nvar; k++) {
 		if (vars[k].alt_len < 0) state[(size_t)k] = 3;
-		else todo[vars[k].chrom].emplace(vars[k].pos, k);
+		// (an entry that cannot be scored still says what a haplotype carries on its line: --sample hands it on, unscored)
+		if (vars[k].alt_len >= 0 || want_haps) todo[vars[k].chrom].emplace(vars[k].pos, k);
 	}
 	fasim_engine* eng = nullptr;
 	DnaRecord rec;
@@ -698,7 +711,7 @@ static int run_variants(const std::string& vcf_path, int flank, const std::strin
 		for (auto j = it->second.lower_bound(rs); j != it->second.end() && j->first < re; ) {
 			const fasim_variant& x = vars[j->second];
 			if (x.pos + x.ref_len > re) { ++j; continue; }
-			if (memcmp(rec.seq.data() + (x.pos - rs), x.ref, (size_t)x.ref_len) != 0) state[(size_t)j->second] = 2;
+			if (x.alt_len >= 0 && memcmp(rec.seq.data() + (x.pos - rs), x.ref, (size_t)x.ref_len) != 0) state[(size_t)j->second] = 2;
 			else mine.push_back(j->second);
 			j = it->second.erase(j);
 		}
@@ -727,7 +740,19 @@ static int run_variants(const std::string& vcf_path, int flank, const std::strin
 			}
 		}
 		for (int q = 0; q < nq; q++) for (size_t k = 0; k < mine.size(); k++) scores[(size_t)q][(size_t)mine[k]] = got[(size_t)q * mine.size() + k];
-		for (int64_t k : mine) state[(size_t)k] = 1;
+		if (want_haps) {
+			// the record's matched entries with their genotypes: nothing else is ever applied as a neighbour
+			std::vector<fasim_genotype> gloc(mine.size());
+			for (size_t k = 0; k < mine.size(); k++) gloc[k] = gts[mine[k]];
+			std::vector<fasim_hap_score> hgot((size_t)nq * mine.size());
+			if (fasim_score_haplotypes(eng, qp.data(), ql.data(), nq, rec.seq.data(), &off0, &len0, 1, loc.data(), gloc.data(), nullptr, (int64_t)loc.size(), flank, &p, hgot.data(), nullptr) != FASIM_OK) {
+				fprintf(stderr, "fasim: %s\n", fasim_last_error(eng));
+				fasim_engine_destroy(eng);
+				return 1;
+			}
+			for (int q = 0; q < nq; q++) for (size_t k = 0; k < mine.size(); k++) haps[(size_t)q][(size_t)mine[k]] = hgot[(size_t)q * mine.size() + k];
+		}
+		for (int64_t k : mine) if (state[(size_t)k] != 3) state[(size_t)k] = 1;
 	}
 	if (eng) fasim_engine_destroy(eng);
 	if (nrec == 0) { fprintf(stderr, "fasim: no record in DNA file %s\n", f1.c_str()); return 1; }
@@ -740,6 +765,12 @@ static int run_variants(const std::string& vcf_path, int flank, const std::strin
 		if (fasim_variants_tsv(vars, scores[(size_t)q].data(), nvar, flank, rnas[(size_t)q].name.c_str(), matched.data(), &text, &len) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
 		bad |= write_file(outdir + "/" + rnas[(size_t)q].name + "-" + base + ".variants.tsv", text, len);
 		fasim_free(text);
+		if (want_haps) {
+			text = nullptr; len = 0;
+			if (fasim_haplotypes_tsv(vars, gts, haps[(size_t)q].data(), nvar, flank, rnas[(size_t)q].name.c_str(), sample.c_str(), matched.data(), &text, &len) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
+			bad |= write_file(outdir + "/" + rnas[(size_t)q].name + "-" + base + ".haplotypes.tsv", text, len);
+			fasim_free(text);
+		}
 		if (!want_hits) continue;
 		const fasim_site_hits view = gathered[(size_t)q].view();
 		text = nullptr; len = 0;
@@ -765,7 +796,8 @@ static int run_variants(const std::string& vcf_path, int flank, const std::strin
 int main(int argc, char* const* argv)
 {
 	fasim_params p; fasim_params_default(&p);
-	std::string f1 = "./", f2 = "./", outdir = "./", bed_path, vcf_path;
+	std::string f1 = "./", f2 = "./", outdir = "./", bed_path, vcf_path, sample;
+	bool sample_given = false;
 	bool devices_given = false, flank_given = false, variant_hits = false; int variant_flank = 300;
 	std::vector<int> devices(1, 0);
 	bool stats = false, all_records = false, accumulate = false, upper = false, track = false, screen = false, screen_only = false;
@@ -788,7 +820,7 @@ int main(int argc, char* const* argv)
 		{ "hist-fdr", required_argument, NULL, 1024 }, { "potential-hist-only", no_argument, NULL, 1025 },
 		{ "hist-sites", no_argument, NULL, 1030 }, { "hist-shuffle", required_argument, NULL, 1031 },
 		{ "variants", required_argument, NULL, 1027 }, { "variant-flank", required_argument, NULL, 1028 },
-		{ "variant-hits", no_argument, NULL, 1029 }, { 0, 0, 0, 0 } };
+		{ "variant-hits", no_argument, NULL, 1029 }, { "sample", required_argument, NULL, 1034 }, { 0, 0, 0, 0 } };
 	int opt;
 	while ((opt = getopt_long_only(argc, argv, optstring, lo, NULL)) != -1) {
 		switch (opt) {
@@ -817,6 +849,7 @@ int main(int argc, char* const* argv)
 		case 1027: vcf_path = optarg; break;
 		case 1028: flank_given = true; variant_flank = strict_int(optarg, -1); break;
 		case 1029: variant_hits = true; break;
+		case 1034: sample_given = true; sample = optarg; break;
 		case 1004: devices_given = true; devices = parse_devices(optarg); if (devices.empty()) { fprintf(stderr, "fasim: bad --devices list\n"); return 2; } break;
 		case 1005: accumulate = true; break;
 		case 1006: upper = true; break;
@@ -844,7 +877,7 @@ int main(int argc, char* const* argv)
 		case 1025: trk.hist_only = true; break;
 		case 1030: hist_arg_given = true; trk.hist_sites = true; break;
 		case 1031: hist_arg_given = true; if (!strcmp(optarg, "di")) trk.hist_dinuc = true; else if (strcmp(optarg, "mono")) hist_shuffle_bad = true; break;
-		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only] [--sites-align] [--oligos [--oligo-hits]]] [--oligos [--oligo-profile] [--oligo-screen]] [--potential-hist [--hist-controls K] [--hist-seed S] [--hist-fdr Q] [--potential-hist-only] [--hist-sites] [--hist-shuffle mono|di]] [--variants FILE.vcf [--variant-flank F] [--variant-hits]]\n"); return 2;
+		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only] [--sites-align] [--oligos [--oligo-hits]]] [--oligos [--oligo-profile] [--oligo-screen]] [--potential-hist [--hist-controls K] [--hist-seed S] [--hist-fdr Q] [--potential-hist-only] [--hist-sites] [--hist-shuffle mono|di]] [--variants FILE.vcf [--variant-flank F] [--variant-hits] [--sample NAME]]\n"); return 2;
 		}
 	}
 	if (all_records && accumulate) { fprintf(stderr, "fasim: --all-records and --accumulate-records exclude each other\n"); return 2; }
@@ -879,12 +912,14 @@ int main(int argc, char* const* argv)
 	const bool variants = !vcf_path.empty();
 	if (flank_given && !variants) { fprintf(stderr, "fasim: --variant-flank needs --variants FILE.vcf\n"); return 2; }
 	if (variant_hits && !variants) { fprintf(stderr, "fasim: --variant-hits needs --variants FILE.vcf\n"); return 2; }
+	if (sample_given && !variants) { fprintf(stderr, "fasim: --sample needs --variants FILE.vcf\n"); return 2; }
+	if (sample_given && sample.empty()) { fprintf(stderr, "fasim: --sample needs the name of a sample of the VCF\n"); return 2; }
 	if (variants && (variant_flank < 0 || variant_flank > FASIM_MAX_FLANK)) { fprintf(stderr, "fasim: --variant-flank needs an integer in [0, %d]\n", FASIM_MAX_FLANK); return 2; }
 	if (variants && (regions || all_records || accumulate || p.classicSim || track || screen || trk.tfo || sites || trk.oligos || trk.hist || devices_given)) {
 		fprintf(stderr, "fasim: --variants is not available with --regions, --all-records, --accumulate-records, -F, --track, --screen, --tfo-profile, --sites, --oligos, --potential-hist or --devices\n");
 		return 2;
 	}
-	if (variants) return run_variants(vcf_path, variant_flank, f1, f2, outdir, devices[0], upper, p, variant_hits);
+	if (variants) return run_variants(vcf_path, variant_flank, f1, f2, outdir, devices[0], upper, p, variant_hits, sample);
 	if (trk.oligos) trk.sites_only = true;      // a panel has no triplex records: the sites files and the panel table are all it writes
 	if (trk.oligos && trk.hist) trk.hist_only = true;      // (or the oligos' histograms)
 	if (!sites) trk.sites = 0;

@@ -282,6 +282,20 @@ struct TouchPathLaunch {
 };
 hipError_t launch_touch_path(const TouchPathLaunch& L, hipStream_t st);
 
+// ---- haplotype.hip: allele windows in the letters of a haplotype, assembled from pieces ------------------
+// A window is npiece pieces in window order, pieces[piece0 .. piece0 + npiece): a stretch of the record (alt 0: letters from dna +
+// src) or of an uploaded ALT string (alt 1: from alts + src); ends[piece0 + k] is the number of window letters up to and including
+// piece k, so the last one is the window's length.  A problem is a TouchProb whose `win` names a HapWindow: k_hap_encode fills the
+// tcodes k_var_encode would fill for the same letters.
+constexpr int HAP_LDS_PIECES = 64;              // piece ends of a window that k_hap_encode searches in LDS; the rest it searches in HBM
+struct HapPiece { int64_t src; int32_t alt, pad; };
+struct HapWindow { int64_t piece0; int32_t npiece, pad; };
+struct HapEncodeLaunch {
+	const uint8_t* dna; const uint8_t* alts; const HapWindow* wins; const HapPiece* pieces; const int32_t* ends;
+	const TouchProb* probs; int32_t nprob; const uint8_t* enc_lut /*[48][256] -> code*/; uint8_t* tcodes;
+};
+hipError_t launch_hap_encode(const HapEncodeLaunch& L, hipStream_t st);
+
 // ---- rowfold.hip: per-base profile of the lncRNA folded from the row maxima of a batch -------------------------
 // Group g = segments [gfirst[g], gfirst[g + 1]) of the batch (the run of segments of one record, or the whole batch); the result is
 // out[g][4 classes][rows_total] = maximum over the group's units of the class, taint bit dropped.

@@ -100,24 +100,47 @@ bool plain_allele(const std::string& a)
 	return true;
 }
 
-}  // namespace
-
-int fasim_read_vcf(const char* path, fasim_variant** out, int64_t* n)
+// one GT allele: `.` (-1) or an index of the line's alleles
+bool gt_allele(const std::string& a, int64_t nalt, int64_t& x)
 {
-	if (!path || !out || !n) return fail(nullptr, FASIM_E_ARG, "bad arguments");
+	if (a == ".") { x = -1; return true; }
+	for (char c : a) if (!isdigit((unsigned char)c)) return false;
+	return parse_int(a, x) && x <= nalt;
+}
+
+// fasim_read_vcf; with `sample` the genotypes of that sample as well (fasim_read_vcf_sample)
+int read_vcf_impl(const char* path, const char* sample, fasim_variant** out, int64_t* n, fasim_genotype** gts)
+{
+	if (!path || !out || !n || (sample && !gts)) return fail(nullptr, FASIM_E_ARG, "bad arguments");
 	*out = nullptr; *n = 0;
+	if (gts) *gts = nullptr;
 	std::ifstream in(path);
 	if (!in) return fail(nullptr, FASIM_E_ARG, "cannot read VCF file %s", path);
 	std::vector<VcfRow> rows;
+	std::vector<fasim_genotype> calls;
 	std::string line;
 	int64_t ln = 0;
 	size_t strbytes = 0;
+	int64_t sample_col = -1;            // column of the sample (>= 9) once the #CHROM line was read
 	while (std::getline(in, line)) {
 		ln++;
 		while (!line.empty() && (line.back() == '\r' || line.back() == '\n')) line.pop_back();
+		if (sample && line.compare(0, 6, "#CHROM") == 0) {
+			int64_t col = 0;
+			for (size_t b = 0; ; col++) {
+				const size_t e = line.find('\t', b);
+				if (col >= 9 && line.compare(b, e == std::string::npos ? std::string::npos : e - b, sample) == 0) { sample_col = col; break; }
+				if (e == std::string::npos) break;
+				b = e + 1;
+			}
+			if (sample_col < 0) return fail(nullptr, FASIM_E_ARG, "%s line %lld: the #CHROM line names no sample '%s'", path, (long long)ln, sample);
+			continue;
+		}
 		if (line.empty() || line[0] == '#' || line.find_first_not_of(" \t") == std::string::npos) continue;
+		if (sample && sample_col < 0) return fail(nullptr, FASIM_E_ARG, "%s line %lld: no #CHROM line before the first data line: sample '%s' is unknown", path, (long long)ln, sample);
+		const size_t want = sample ? (size_t)sample_col + 1 : 5;
 		std::vector<std::string> f;
-		for (size_t b = 0; f.size() < 5; ) {
+		for (size_t b = 0; f.size() < want; ) {
 			const size_t e = line.find('\t', b);
 			f.emplace_back(line, b, e == std::string::npos ? std::string::npos : e - b);
 			if (e == std::string::npos) break;
@@ -131,6 +154,30 @@ int fasim_read_vcf(const char* path, fasim_variant** out, int64_t* n)
 		if (f[4].empty()) return fail(nullptr, FASIM_E_ARG, "%s line %lld: empty ALT", path, (long long)ln);
 		for (char& c : f[3]) c = (char)toupper((unsigned char)c);
 		for (char& c : f[4]) c = (char)toupper((unsigned char)c);
+		// the call of the sample on this line: up to two alleles, each `.` or an index of the line's alleles
+		int64_t call[2] = { -1, -1 }; bool phased = false;
+		if (sample) {
+			if (f.size() < want) return fail(nullptr, FASIM_E_ARG, "%s line %lld: no column of sample '%s' (%zu columns)", path, (long long)ln, sample, f.size());
+			int64_t gi = -1, k = 0;
+			for (size_t b = 0; ; k++) {
+				const size_t e = f[8].find(':', b);
+				if (f[8].compare(b, e == std::string::npos ? std::string::npos : e - b, "GT") == 0) { gi = k; break; }
+				if (e == std::string::npos) break;
+				b = e + 1;
+			}
+			if (gi < 0) return fail(nullptr, FASIM_E_ARG, "%s line %lld: no GT in FORMAT '%s'", path, (long long)ln, f[8].c_str());
+			const std::string& col = f[(size_t)sample_col];
+			size_t b = 0;
+			for (k = 0; k < gi && b != std::string::npos; k++) { b = col.find(':', b); if (b != std::string::npos) b++; }
+			const std::string gt = b == std::string::npos ? std::string() : col.substr(b, col.find(':', b) == std::string::npos ? std::string::npos : col.find(':', b) - b);
+			const int64_t nalt = (int64_t)std::count(f[4].begin(), f[4].end(), ',') + 1;
+			const size_t sep = gt.find_first_of("|/");
+			bool ok = !gt.empty();
+			if (ok && sep == std::string::npos) { ok = gt_allele(gt, nalt, call[0]); call[1] = call[0]; phased = true; }      // haploid
+			else if (ok) { ok = gt_allele(gt.substr(0, sep), nalt, call[0]) && gt_allele(gt.substr(sep + 1), nalt, call[1]); phased = gt[sep] == '|'; }
+			if (!ok) return fail(nullptr, FASIM_E_ARG, "%s line %lld: malformed GT '%s' of sample '%s'", path, (long long)ln, gt.c_str(), sample);
+		}
+		const int64_t first_call = (int64_t)calls.size();
 		for (size_t b = 0; ; ) {
 			const size_t e = f[4].find(',', b);
 			VcfRow r;
@@ -140,6 +187,13 @@ int fasim_read_vcf(const char* path, fasim_variant** out, int64_t* n)
 			r.usable = plain_allele(r.ref) && plain_allele(r.alt);
 			strbytes += r.chrom.size() + r.id.size() + r.ref.size() + r.alt.size() + 4;
 			rows.push_back(std::move(r));
+			if (sample) {
+				const int64_t a = (int64_t)calls.size() - first_call + 1;      // this ALT's index on its line
+				fasim_genotype g;
+				for (int h = 0; h < 2; h++) g.hap[h] = (int8_t)(call[h] < 0 ? -1 : call[h] == a ? 1 : 0);
+				g.phased = phased ? 1 : 0; g.pad = 0;
+				calls.push_back(g);
+			}
 			if (e == std::string::npos) break;
 			b = e + 1;
 		}
@@ -156,6 +210,22 @@ int fasim_read_vcf(const char* path, fasim_variant** out, int64_t* n)
 		v[k].ref_len = (int32_t)std::min<size_t>(r.ref.size(), 0x7fffffff); v[k].alt_len = r.usable ? (int32_t)r.alt.size() : -1;
 		v[k].chrom = put(r.chrom); v[k].id = put(r.id); v[k].ref = put(r.ref); v[k].alt = put(r.alt);
 	}
+	if (sample) {
+		fasim_genotype* g = (fasim_genotype*)malloc((calls.size() + 1) * sizeof(fasim_genotype));
+		if (!g) { free(block); return fail(nullptr, FASIM_E_NOMEM, "out of host memory for %zu genotypes", calls.size()); }
+		if (!calls.empty()) memcpy(g, calls.data(), calls.size() * sizeof(fasim_genotype));
+		*gts = g;
+	}
 	*out = v; *n = (int64_t)rows.size();
 	return FASIM_OK;
+}
+
+}  // namespace
+
+int fasim_read_vcf(const char* path, fasim_variant** out, int64_t* n) { return read_vcf_impl(path, nullptr, out, n, nullptr); }
+
+int fasim_read_vcf_sample(const char* path, const char* sample, fasim_variant** out, int64_t* n, fasim_genotype** gts)
+{
+	if (!sample || !*sample) return fail(nullptr, FASIM_E_ARG, "no sample name given");
+	return read_vcf_impl(path, sample, out, n, gts);
 }

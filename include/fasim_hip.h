@@ -817,6 +817,60 @@ int fasim_variant_hit_span(const fasim_variant* v, const fasim_variant_window* w
 int fasim_variant_hits_tsv(const fasim_variant* vars, const fasim_variant_score* scores, const fasim_variant_window* windows,
                            const fasim_site_hits* hits, int64_t nvar, int32_t flank, const char* rna_name,
                            const uint8_t* matched /* [nvar] or NULL */, char** text, int64_t* text_len);
+/* ---- variants scored on a sample's phased haplotypes (csrc/haplotype.hip) ----------------------------------- */
+/* fasim_score_variants exchanges REF for ALT in a window of reference letters; a person carries the window with their other variants
+ * in it.  Entries are those of fasim_read_vcf; a genotype per entry says which haplotype of one sample carries its ALT:
+ * hap[h] 1 = this ALT, 0 = REF or another ALT of the line, -1 = missing (`.`); phased 1 = the GT separator is `|`, or the call is
+ * haploid (which counts as both haplotypes alike).
+ * The consistent set A_h of haplotype h in a record: over the record's entries in the order (pos, line, entry index), an entry
+ * qualifies with alt_len >= 0, matched, hap[h] == 1 and (phased or hap[0] == hap[1] == 1), and a qualifying entry is accepted iff its
+ * REF span [pos, pos + ref_len) intersects no accepted span (touching spans do not intersect).  The applied neighbours of a focus
+ * entry v are A_h without the entries of v's own line and without entries whose REF span intersects v's.  R_h(v) is the record with
+ * every applied neighbour's REF span replaced by its ALT, a' = v.pos plus the sum of alt_len - ref_len over the applied neighbours
+ * before v.  The result of (v, h) is what fasim_score_variants defines for the variant (a', ref_len, alt) on the record R_h(v) with
+ * the same flank: window, mark, values, encodings and clip bit; the flank counts letters of the haplotype, R_h's ends are the
+ * record's ends.  Where nothing is applied it is today's score byte for byte. */
+typedef struct fasim_genotype { int8_t hap[2]; uint8_t phased, pad; } fasim_genotype;
+/* carried[h]: 1 = this ALT, 0 = REF, 2 = another ALT of the line, -1 = missing.  applied[h]: the applied neighbours with at least one
+ * letter in the windows.  flags[h]: bit 0 the clip bit of fasim_variant_score over both alleles on this haplotype; bit 1 an entry of
+ * another line within |pos - v.pos| <= flank + FASIM_MAX_ALLELE has hap[h] == 1 but is an unphased heterozygote (it was not applied;
+ * an entry that is unmatched or cannot be scored is never applied and sets no bit);
+ * bit 2 an entry of another line within the same distance qualified but was rejected for overlap (with A_h, or with the focus); bit 3
+ * the windows of haplotype 1 equal those of haplotype 0 letter for letter, so they were computed once (set on both). */
+typedef struct fasim_hap_score { fasim_variant_score hap[2]; int32_t carried[2], applied[2], flags[2]; } fasim_hap_score;
+/* fasim_read_vcf with the genotypes of one sample: the same entries in the same order, (*gts)[k] the genotype of entry k (a block of
+ * its own: fasim_free).  GT is found through the FORMAT column (the 9th), the sample by its name in the #CHROM line.  Refused with
+ * FASIM_E_ARG and the reason, besides fasim_read_vcf's refusals: a sample the #CHROM line does not name (or no #CHROM line before
+ * the first data line), a data line without the sample's column, no GT in FORMAT, a malformed GT (an allele that is neither `.` nor
+ * an index of the line's alleles, more than two alleles). */
+int fasim_read_vcf_sample(const char* path, const char* sample, fasim_variant** out, int64_t* n, fasim_genotype** gts);
+/* Pure host code: the window of entry v on haplotype hap (0 / 1) for `allele` (0 REF, 1 ALT) in haplotype letters, as the planner of
+ * fasim_score_haplotypes builds it from pieces.  Only the entries of v's record (vars[k].rec == vars[v].rec) are looked at;
+ * `record` are that record's rec_len letters.  *letters (fasim_free) holds *n letters, the allele's are [*v0, *v0 + allele length);
+ * *edge bit 0 / 1: the lower / upper end was cut by the flank and not by the haplotype's end. */
+int fasim_haplotype_window(const fasim_variant* vars, const fasim_genotype* gts, int64_t nvar, const uint8_t* matched /* or NULL */,
+                           int64_t rec_len, const char* record, int64_t v, int32_t hap, int32_t allele, int32_t flank,
+                           char** letters, int32_t* n, int32_t* v0, int32_t* edge);
+/* Pure host code: what the planner decides for entry v before any score exists: carried[2], applied[2] and flags[2] of
+ * fasim_hap_score, flags without bit 0. */
+int fasim_haplotype_info(const fasim_variant* vars, const fasim_genotype* gts, int64_t nvar, const uint8_t* matched /* or NULL */,
+                         int64_t rec_len, const char* record, int64_t v, int32_t flank, int32_t* carried, int32_t* applied, int32_t* flags);
+/* Scores every entry on both haplotypes: out[q * nvar + v].  Arguments and refusals as fasim_score_variants; matched[k] == 0 (NULL:
+ * all matched) keeps entry k from being applied as a neighbour (it is still scored).  A haplotype without an applied neighbour in
+ * reach takes the plain windows of fasim_score_variants; two haplotypes with equal windows are computed once.  The result of (v, h)
+ * depends on the record, the entries with their genotypes, the flank, the query and the parameters only.  stats: both parts added. */
+int fasim_score_haplotypes(fasim_engine* e, const char* const* rnas, const int32_t* rna_lens, int32_t nq,
+                           const char* dna, const int64_t* rec_off, const int64_t* rec_len, int32_t nrec,
+                           const fasim_variant* vars, const fasim_genotype* gts, const uint8_t* matched /* [nvar] or NULL */, int64_t nvar,
+                           int32_t flank, const fasim_params* p, fasim_hap_score* out /* [nq * nvar] */, fasim_variant_stats* stats /* may be NULL */);
+/* The table `fasim --variants --sample` writes for one query: `# fasim haplotypes lncRNA=<rna_name> sample=<sample> flank=<F>`, the
+ * line of column names, then one line per entry: line chrom pos id ref alt gt, then for h1 and h2: carried applied, per class
+ * <Class>_ref <Class>_alt, max_ref max_alt delta rule_ref rule_alt value, flags; then diplotype_max.  gt is the entry's own genotype
+ * (1 = this ALT, 0 = not, . = missing; `|` phased, `/` not).  value is the maximum of the allele the haplotype carries (max_alt for
+ * carried 1, max_ref for carried 0), NA for carried 2 or -1; diplotype_max the larger of the two values, NA unless both are numbers.
+ * An entry with matched[k] == 0 or alt_len < 0 has NA in every column after gt.  Free with fasim_free. */
+int fasim_haplotypes_tsv(const fasim_variant* vars, const fasim_genotype* gts, const fasim_hap_score* scores, int64_t nvar, int32_t flank,
+                         const char* rna_name, const char* sample, const uint8_t* matched /* [nvar] or NULL */, char** text, int64_t* text_len);
 /* ingest helper: upper-cases a DNA record in place (soft-masked genomes such as UCSC hg38 carry repeats in lower
  * case; the reference does not upper-case and treats such letters as unknown, rules.h:286-312, 82-83). */
 void fasim_upper_case(char* seq, int64_t n);
