@@ -337,7 +337,7 @@ void fasim_engine_destroy(fasim_engine* e)
 		&e->ublk, &e->btarget, &e->bidx, &e->bcounts, &e->blist[0], &e->blist[1], &e->blist[2], &e->bslots[0], &e->bslots[1], &e->bslots[2],
 		&e->bprev, &e->lane_ub, &e->fzones, &e->fubslot, &e->bdec, &e->btab, &e->swin, &e->unit_ovf, &e->track, &e->track_phase, &e->track_sat, &e->track_peaks, &e->sites_counts, &e->sites_offsets, &e->sites_runs, &e->sites_sat, &e->sa_q, &e->sa_tcodes, &e->sa_probs, &e->sa_ends, &e->sa_rows, &e->sa_items, &e->sa_dirs, &e->sa_cigar, &e->sa_ciglen,
 		&e->rowmax16, &e->row_out, &e->row_gfirst, &e->row_sat, &e->oligo_q, &e->rowpart16, &e->hist, &e->hist_zone, &e->hist_zones, &e->hist_sat, &e->hist_pairs, &e->hist_border,
-		&e->vr_q, &e->vr_dna, &e->vr_alt, &e->vr_wins, &e->vr_probs, &e->vr_tcodes, &e->vr_rows, &e->vr_touch, &e->vr_out,
+		&e->vr_q, &e->vr_dna, &e->vr_alt, &e->vr_probs, &e->vr_tcodes, &e->vr_rows, &e->vr_touch, &e->vr_out,
 		&e->vr_items, &e->vr_dirs, &e->vr_cigar, &e->vr_paths, &e->vr_hwins, &e->vr_pieces, &e->vr_ends, &e->fmask, &e->flist, &e->fmarks, &e->seg_clean };
 	for (auto& t : e->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
 	for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);

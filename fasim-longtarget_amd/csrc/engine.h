@@ -143,9 +143,9 @@ struct fasim_engine {
 	DevBuf sa_q, sa_tcodes, sa_probs, sa_ends, sa_rows, sa_items, sa_dirs, sa_cigar, sa_ciglen;   // fasim_scan_records_sites_aligned only: query codes, the chunk's units, problems, end cells, row state of long queries, path items, direction bytes, CIGARs
 	DevBuf hist, hist_zone, hist_zones, hist_sat;   // fasim_scan_records_hist only: k_hist's counters of the batch, its zone bounds per segment, the zone values and saturation flags
 	DevBuf hist_pairs, hist_border;                 // fasim_scan_records_site_counts only (it uses the four above too): k_hist_pairs' pair counters and slice borders
-	DevBuf vr_q, vr_dna, vr_alt, vr_wins, vr_probs, vr_tcodes, vr_rows, vr_touch, vr_out;   // fasim_score_variants only: query codes, streamed window letters, ALT letters, windows, problems, target codes, row state of long queries, k_touch's words, k_touch_reduce's words
+	DevBuf vr_q, vr_dna, vr_alt, vr_probs, vr_tcodes, vr_rows, vr_touch, vr_out;   // the chunks of fasim_score_variants and fasim_score_haplotypes only: query codes, streamed window letters, ALT letters, problems, target codes, row state of long queries, k_touch's words, k_touch_reduce's words
 	DevBuf vr_items, vr_dirs, vr_cigar, vr_paths;   // fasim_score_variants_aligned only: k_touch_path's items, direction bytes, CIGAR words and results
-	DevBuf vr_hwins, vr_pieces, vr_ends;           // fasim_score_haplotypes only: the windows, pieces and piece ends of k_hap_encode
+	DevBuf vr_hwins, vr_pieces, vr_ends;           // the same chunks: the windows, pieces and piece ends of k_hap_encode
 	int opt_sim_lds = -1;                        // option "sim_lds": -F re-sweeps always on the L2 variant (0) / the LDS variant where the state fits (1); -1 = by the units in flight
 	int opt_site_short = -1;                     // option "site_short": 1 = the hits of oligo sites end on k_site_ends_short (default), 0 = on k_site_ends (-1 = default / environment FASIM_SITE_SHORT)
 	int opt_site_chunk = 0;                      // option "site_chunk": problems per chunk of the hits phase where lower than the phase's own limit (0 = that limit)

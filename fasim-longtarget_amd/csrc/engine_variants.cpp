@@ -1,12 +1,15 @@
 // fasim-longtarget_amd/csrc/engine_variants.cpp -- fasim_score_variants: the triplex potential through variants (DESIGN.md section 19;
-// kernels: variant.hip), and the table of `fasim --variants` (fasim_variants_tsv); fasim_score_variants_aligned: the same call with
+// kernels: haplotype.hip, variant.hip), and the table of `fasim --variants` (fasim_variants_tsv); fasim_score_variants_aligned: the same call with
 // the alignment behind every score (section 21; kernel: variant_path.hip), its projection to the reference and its table;
 // fasim_score_haplotypes: every entry on the two haplotypes of a sample (section 25; kernel: haplotype.hip), its planner and its table.
 //
-// A variant is two allele windows, a window under an enabled encoding is a problem.  Per query the variants are cut into chunks by a
-// fixed bound on buffer bytes; a chunk is: the windows' descriptions (and, for a streamed record, their letters) and the ALT letters
-// up, k_var_encode, k_touch, k_touch_reduce, nine words per variant back.  Everything runs on the engine's own stream and in buffers
-// of its own (vr_*): the engine's query, its scan buffers and its workers are not touched.
+// What is scored is a unit: two allele windows that share their sides -- the left pieces, the REF letters in the record or the ALT
+// string, the right pieces -- and a window under an enabled encoding is a problem.  A variant of section 19 is the unit whose sides are
+// the record stretches of its flanks; an (entry, haplotype) of section 25 is the unit whose sides the planner walked.  Per query the
+// units are cut into chunks by a fixed bound on buffer bytes, by run_units alone; a chunk is: the windows as pieces (and, for a
+// streamed record, their letters) and the ALT letters up, k_hap_encode, k_touch, k_touch_reduce, nine words per unit back.
+// Everything runs on the engine's own stream and in buffers of its own (vr_*): the engine's query, its scan buffers and its workers
+// are not touched.
 // The aligned call adds per chunk, after the nine words are back: the slots with a value become path items over the target codes
 // that are still in vr_tcodes, k_touch_path in launches of at most 512 MB of direction bytes, cells and CIGARs back, convert_triplex
 // (on the host while the next launch's kernel runs).
@@ -29,6 +32,197 @@ constexpr int64_t VR_CIG_WORDS = (int64_t)1 << 26;        // CIGAR words of a pa
 inline void window_of(const fasim_variant& x, int64_t len, int32_t flank, int64_t& lo, int64_t& hi)
 {
 	lo = std::max<int64_t>(0, x.pos - flank); hi = std::min<int64_t>(len, x.pos + x.ref_len + flank);
+}
+
+inline void blank_score(fasim_variant_score& s)
+{
+	memset(&s, 0, sizeof s);
+	for (int a = 0; a < 2; a++) for (int c = 0; c < FASIM_TRACK_CLASSES; c++) s.enc[a][c] = -1;
+}
+
+// the refusals of a call that scores variants, before its entries are looked at
+int check_variant_call(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna, const int64_t* rec_off,
+	const int64_t* rec_len, int32_t nrec, int32_t flank, const fasim_params* pp, RecordSet& rs)
+{
+	if (nq < 1 || !rnas || !rna_lens || !pp) return fail(E, FASIM_E_ARG, "bad arguments");
+	int rc = record_set_open(E, dna, rec_off, rec_len, nrec, false, rs); if (rc) return rc;
+	for (int32_t q = 0; q < nq; q++) {
+		if (!rnas[q] || rna_lens[q] <= 0) return fail(E, FASIM_E_ARG, "empty query %d", q);
+		if (rna_lens[q] > FASIM_MAX_QUERY) return fail(E, FASIM_E_UNSUPPORTED, "query %d has %d nt: the limit is %d", q, rna_lens[q], FASIM_MAX_QUERY);
+	}
+	if (pp->classicSim) return fail(E, FASIM_E_UNSUPPORTED, "variants are scored with the fastSIM scoring only: not with classicSim (-F)");
+	if (flank < 0 || flank > FASIM_MAX_FLANK) return fail(E, FASIM_E_ARG, "flank %d lies outside [0, %d]", flank, FASIM_MAX_FLANK);
+	return record_set_bounds(E, rs);
+}
+
+// the refusals for the entries themselves
+int check_variant_entries(fasim_engine* E, const fasim_variant* vars, int64_t nvar, const int64_t* rec_len, int32_t nrec)
+{
+	for (int64_t v = 0; v < nvar; v++) {
+		const fasim_variant& x = vars[v];
+		if (x.alt_len < 0) continue;
+		if (x.ref_len < 1) return fail(E, FASIM_E_ARG, "variant %lld: ref_len %d < 1", (long long)v, x.ref_len);
+		if (x.ref_len > FASIM_MAX_ALLELE || x.alt_len < 1 || x.alt_len > FASIM_MAX_ALLELE || !x.alt)
+			return fail(E, FASIM_E_ARG, "variant %lld: an allele has 1 to %d letters (REF %d, ALT %d)", (long long)v, FASIM_MAX_ALLELE, x.ref_len, x.alt_len);
+		if (x.rec < 0 || x.rec >= nrec) return fail(E, FASIM_E_ARG, "variant %lld: record %d of %d", (long long)v, x.rec, nrec);
+		if (x.pos < 0 || x.pos > rec_len[x.rec] - x.ref_len)
+			return fail(E, FASIM_E_ARG, "variant %lld: [%lld, %lld) lies outside record %d of %lld nt", (long long)v, (long long)x.pos,
+				(long long)(x.pos + x.ref_len), x.rec, (long long)rec_len[x.rec]);
+	}
+	return FASIM_OK;
+}
+
+// ---- scoring units and their chunks --------------------------------------------------------------------------------------------------
+struct HPiece { int64_t src; int32_t len; int64_t ent; };      // ent < 0: record letters [src, src + len); else letters [src, src + len) of entry ent's ALT
+struct HapSides { std::vector<HPiece> left, right; int32_t applied = 0; bool edge_lo = false, edge_hi = false; };
+// One unit: the focus entry v between its sides; `out` takes its score
+struct ScoreUnit { int64_t v; const HapSides* sides; fasim_variant_score* out; };
+
+inline int32_t pieces_len(const std::vector<HPiece>& p) { int32_t n = 0; for (const HPiece& q : p) n += q.len; return n; }
+
+// the sides of a variant of section 19: the record stretches of its window; a side of no letters is no piece
+void plain_sides(const fasim_variant& x, int64_t len, int32_t flank, HapSides& S)
+{
+	int64_t lo, hi;
+	window_of(x, len, flank, lo, hi);
+	S.left.clear(); S.right.clear();
+	if (lo < x.pos) S.left.push_back({ lo, (int32_t)(x.pos - lo), -1 });
+	if (x.pos + x.ref_len < hi) S.right.push_back({ x.pos + x.ref_len, (int32_t)(hi - x.pos - x.ref_len), -1 });
+	S.edge_lo = lo > 0; S.edge_hi = hi < len;      // cut by the flank, not by the record's end
+}
+
+// What the chunks of a call need of it: `who` is the call's word in the error texts; the query is the one open_query uploaded last;
+// nprobs and cells count over the whole call
+struct UnitRun {
+	fasim_engine* E; const char* who; const char* dna; bool resident; const int64_t* rec_off; const fasim_variant* vars; const std::vector<int>* encs;
+	int m = 0; bool rows_hbm = false; size_t row_bytes = 0;      // row_bytes: of one problem
+	int64_t nprobs = 0, cells = 0;
+};
+
+int open_query(UnitRun& R, const char* rna, int m)
+{
+	std::vector<uint8_t> qc((size_t)m);
+	for (int i = 0; i < m; i++) qc[(size_t)i] = code2(rna[i]);
+	R.m = m; R.rows_hbm = m > TOUCH_LDS_ROWS; R.row_bytes = (size_t)6 * (size_t)touch_state_rows(m);
+	return upload(R.E, R.E->vr_q, qc.data(), qc.size());
+}
+
+// The units unit_at(0 .. nunit) against the open query, in chunks.  After a chunk's scores are in place and while its problems -- in
+// (unit, allele, encoding) order -- and their target codes are still on the device: chunk_done(first unit, units, problems)
+template <class UnitAt, class ChunkDone>
+int run_units(UnitRun& R, size_t nunit, UnitAt unit_at, ChunkDone chunk_done)
+{
+	fasim_engine* E = R.E;
+	const std::vector<int>& encs = *R.encs;
+	const int nenc = (int)encs.size(), m = R.m;
+	std::vector<HapPiece> dl, dr;
+	for (size_t u0 = 0; u0 < nunit; ) {
+		std::vector<HapWindow> wins;
+		std::vector<HapPiece> pieces;
+		std::vector<int32_t> ends;
+		std::vector<TouchProb> probs;
+		std::vector<uint8_t> alts, letters;
+		std::vector<fasim_variant_score*> outs;
+		size_t tbytes = 0, u1 = u0;
+		for (; u1 < nunit; u1++) {
+			const ScoreUnit U = unit_at(u1);
+			const fasim_variant& x = R.vars[U.v];
+			const HapSides& W = *U.sides;
+			const int pre = pieces_len(W.left), post = pieces_len(W.right);
+			const int n_al[2] = { pre + x.ref_len + post, pre + x.alt_len + post };
+			const size_t need = (size_t)nenc * (size_t)(pad16(n_al[0]) + pad16(n_al[1]));
+			if (u1 > u0 && (tbytes + need > VR_TCODE_BYTES || (int64_t)probs.size() + 2 * nenc > VR_MAX_PROBS ||
+				(R.rows_hbm && (probs.size() + 2 * (size_t)nenc) * R.row_bytes > VR_ROW_BYTES))) break;
+			// the unit's pieces for the device: record letters in the resident buffer or staged for this chunk, ALT letters uploaded
+			auto device_piece = [&](const HPiece& p) {
+				HapPiece D; D.pad = 0;
+				if (p.ent < 0) {
+					D.alt = 0; D.src = R.rec_off[x.rec] + p.src;
+					if (!R.resident) { D.src = (int64_t)letters.size(); letters.insert(letters.end(), R.dna + R.rec_off[x.rec] + p.src, R.dna + R.rec_off[x.rec] + p.src + p.len); }
+				} else {
+					D.alt = 1; D.src = (int64_t)alts.size();
+					alts.insert(alts.end(), R.vars[p.ent].alt + p.src, R.vars[p.ent].alt + p.src + p.len);
+				}
+				return D;
+			};
+			// (the sides go up once for both alleles: of a streamed record every letter of the windows is staged once)
+			dl.clear(); dr.clear();
+			for (const HPiece& p : W.left) dl.push_back(device_piece(p));
+			for (const HPiece& p : W.right) dr.push_back(device_piece(p));
+			const HPiece focus[2] = { { x.pos, x.ref_len, -1 }, { 0, x.alt_len, U.v } };
+			const int edge_lo = W.edge_lo, edge_hi = W.edge_hi;
+			for (int al = 0; al < 2; al++) {
+				HapWindow H; H.piece0 = (int64_t)pieces.size(); H.npiece = (int32_t)(dl.size() + 1 + dr.size()); H.pad = 0;
+				int32_t run = 0;
+				for (size_t k = 0; k < dl.size(); k++) { pieces.push_back(dl[k]); run += W.left[k].len; ends.push_back(run); }
+				pieces.push_back(device_piece(focus[al])); run += focus[al].len; ends.push_back(run);
+				for (size_t k = 0; k < dr.size(); k++) { pieces.push_back(dr[k]); run += W.right[k].len; ends.push_back(run); }
+				const int n = n_al[al], v0 = pre, v1 = pre + focus[al].len;
+				if (run != n || n > TOUCH_MAX_COLS) return fail(E, FASIM_E_ARG, "%s: a window of %d letters in pieces of %d", R.who, n, run);
+				for (int k = 0; k < nenc; k++) {
+					const int enc = encs[(size_t)k];
+					TouchProb P; P.tbase = (int64_t)tbytes; P.n = n; P.win = (int32_t)wins.size(); P.enc = enc;
+					if (enc & 1) { P.v0 = n - v1; P.v1 = n - v0; P.edge = edge_hi | (edge_lo << 1); }
+					else { P.v0 = v0; P.v1 = v1; P.edge = edge_lo | (edge_hi << 1); }
+					probs.push_back(P);
+					tbytes += (size_t)pad16(n);
+					R.cells += (int64_t)m * n;
+				}
+				wins.push_back(H);
+			}
+			outs.push_back(U.out);
+		}
+		const int np = (int)probs.size(), nu = (int)(u1 - u0);
+		R.nprobs += np;
+		if (alts.empty()) alts.push_back(0);
+		if (E->vr_hwins.ensure(wins.size() * sizeof(HapWindow)) != hipSuccess || E->vr_pieces.ensure(pieces.size() * sizeof(HapPiece)) != hipSuccess ||
+			E->vr_ends.ensure(ends.size() * sizeof(int32_t)) != hipSuccess || E->vr_probs.ensure((size_t)np * sizeof(TouchProb)) != hipSuccess ||
+			E->vr_alt.ensure(alts.size()) != hipSuccess || E->vr_tcodes.ensure(tbytes) != hipSuccess || E->vr_touch.ensure((size_t)np * sizeof(uint32_t)) != hipSuccess ||
+			E->vr_out.ensure((size_t)nu * 9 * sizeof(uint32_t)) != hipSuccess || (!R.resident && E->vr_dna.ensure(letters.size() + 1) != hipSuccess) ||
+			(R.rows_hbm && E->vr_rows.ensure((size_t)np * R.row_bytes) != hipSuccess)) {
+			(void)hipGetLastError();
+			return fail(E, FASIM_E_NOMEM, "%s: no device memory for a chunk of %d problems", R.who, np);
+		}
+		HIPOK(hipMemcpyAsync(E->vr_hwins.p, wins.data(), wins.size() * sizeof(HapWindow), hipMemcpyHostToDevice, E->st));
+		HIPOK(hipMemcpyAsync(E->vr_pieces.p, pieces.data(), pieces.size() * sizeof(HapPiece), hipMemcpyHostToDevice, E->st));
+		HIPOK(hipMemcpyAsync(E->vr_ends.p, ends.data(), ends.size() * sizeof(int32_t), hipMemcpyHostToDevice, E->st));
+		HIPOK(hipMemcpyAsync(E->vr_probs.p, probs.data(), (size_t)np * sizeof(TouchProb), hipMemcpyHostToDevice, E->st));
+		HIPOK(hipMemcpyAsync(E->vr_alt.p, alts.data(), alts.size(), hipMemcpyHostToDevice, E->st));
+		if (!R.resident && !letters.empty()) HIPOK(hipMemcpyAsync(E->vr_dna.p, letters.data(), letters.size(), hipMemcpyHostToDevice, E->st));
+		HapEncodeLaunch EL;
+		EL.dna = R.resident ? E->dna_res.as<uint8_t>() : E->vr_dna.as<uint8_t>(); EL.alts = E->vr_alt.as<uint8_t>(); EL.wins = E->vr_hwins.as<HapWindow>();
+		EL.pieces = E->vr_pieces.as<HapPiece>(); EL.ends = E->vr_ends.as<int32_t>();
+		EL.probs = E->vr_probs.as<TouchProb>(); EL.nprob = np; EL.enc_lut = E->enc_lut.as<uint8_t>(); EL.tcodes = E->vr_tcodes.as<uint8_t>();
+		hipError_t he = launch_hap_encode(EL, E->st);
+		if (he != hipSuccess) return fail(E, FASIM_E_HIP, "%s (encode) launch failed: %s", R.who, hipGetErrorString(he));
+		TouchLaunch TL;
+		TL.tcodes = E->vr_tcodes.as<uint8_t>(); TL.qcodes = E->vr_q.as<uint8_t>(); TL.m = m; TL.probs = E->vr_probs.as<TouchProb>(); TL.nprob = np;
+		TL.rows = R.rows_hbm ? E->vr_rows.as<uint16_t>() : nullptr; TL.out = E->vr_touch.as<uint32_t>();
+		{ TimedScope ts(E, 4); he = launch_touch(TL, E->st); }
+		if (he != hipSuccess) return fail(E, FASIM_E_HIP, "%s (touch) launch failed: %s", R.who, hipGetErrorString(he));
+		TouchReduceLaunch RL;
+		RL.touch = E->vr_touch.as<uint32_t>(); RL.nvar = nu; RL.nenc = nenc; RL.out = E->vr_out.as<uint32_t>();
+		memset(RL.enc, 0, sizeof RL.enc);
+		for (int k = 0; k < nenc; k++) RL.enc[k] = (uint8_t)encs[(size_t)k];
+		he = launch_touch_reduce(RL, E->st);
+		if (he != hipSuccess) return fail(E, FASIM_E_HIP, "%s (reduce) launch failed: %s", R.who, hipGetErrorString(he));
+		std::vector<uint32_t> words((size_t)nu * 9);
+		HIPOK(hipMemcpyAsync(words.data(), E->vr_out.p, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st));
+		HIPOK(hipStreamSynchronize(E->st));
+		drain_timed(E);
+		for (int k = 0; k < nu; k++) {
+			fasim_variant_score& s = *outs[(size_t)k];
+			for (int a = 0; a < 2; a++) for (int c = 0; c < FASIM_TRACK_CLASSES; c++) {
+				const uint32_t w = words[(size_t)k * 9 + (size_t)a * 4 + (size_t)c];
+				s.value[a][c] = (int32_t)(w >> 9);
+				s.enc[a][c] = (w >> 9) ? (int32_t)(w & 0xff) : -1;
+			}
+			s.flags = (int32_t)(words[(size_t)k * 9 + 8] & 1);
+		}
+		const int rc = chunk_done(u0, nu, probs); if (rc) return rc;
+		u0 = u1;
+	}
+	return FASIM_OK;
 }
 
 // What the path phase of a chunk needs of its call
@@ -130,28 +324,10 @@ int score_variants_impl(fasim_engine* E, const char* const* rnas, const int32_t*
 	const fasim_params* pp, fasim_variant_score* out, fasim_variant_stats* stats, fasim_variant_window* windows, fasim_site_hits** hits)
 {
 	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
-	if (nq < 1 || !rnas || !rna_lens || nvar < 0 || (nvar > 0 && (!vars || !out)) || !pp) return fail(E, FASIM_E_ARG, "bad arguments");
+	if (nvar < 0 || (nvar > 0 && (!vars || !out))) return fail(E, FASIM_E_ARG, "bad arguments");
 	RecordSet rs;
-	int rc = record_set_open(E, dna, rec_off, rec_len, nrec, false, rs); if (rc) return rc;
-	for (int32_t q = 0; q < nq; q++) {
-		if (!rnas[q] || rna_lens[q] <= 0) return fail(E, FASIM_E_ARG, "empty query %d", q);
-		if (rna_lens[q] > FASIM_MAX_QUERY) return fail(E, FASIM_E_UNSUPPORTED, "query %d has %d nt: the limit is %d", q, rna_lens[q], FASIM_MAX_QUERY);
-	}
-	if (pp->classicSim) return fail(E, FASIM_E_UNSUPPORTED, "variants are scored with the fastSIM scoring only: not with classicSim (-F)");
-	if (flank < 0 || flank > FASIM_MAX_FLANK) return fail(E, FASIM_E_ARG, "flank %d lies outside [0, %d]", flank, FASIM_MAX_FLANK);
-	rc = record_set_bounds(E, rs); if (rc) return rc;
-	const bool resident = rs.resident;
-	for (int64_t v = 0; v < nvar; v++) {
-		const fasim_variant& x = vars[v];
-		if (x.alt_len < 0) continue;
-		if (x.ref_len < 1) return fail(E, FASIM_E_ARG, "variant %lld: ref_len %d < 1", (long long)v, x.ref_len);
-		if (x.ref_len > FASIM_MAX_ALLELE || x.alt_len < 1 || x.alt_len > FASIM_MAX_ALLELE || !x.alt)
-			return fail(E, FASIM_E_ARG, "variant %lld: an allele has 1 to %d letters (REF %d, ALT %d)", (long long)v, FASIM_MAX_ALLELE, x.ref_len, x.alt_len);
-		if (x.rec < 0 || x.rec >= nrec) return fail(E, FASIM_E_ARG, "variant %lld: record %d of %d", (long long)v, x.rec, nrec);
-		if (x.pos < 0 || x.pos > rec_len[x.rec] - x.ref_len)
-			return fail(E, FASIM_E_ARG, "variant %lld: [%lld, %lld) lies outside record %d of %lld nt", (long long)v, (long long)x.pos,
-				(long long)(x.pos + x.ref_len), x.rec, (long long)rec_len[x.rec]);
-	}
+	int rc = check_variant_call(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, flank, pp, rs); if (rc) return rc;
+	rc = check_variant_entries(E, vars, nvar, rec_len, nrec); if (rc) return rc;
 	const double t0 = now_s();
 	if (stats) memset(stats, 0, sizeof *stats);
 	if (hits) {
@@ -170,13 +346,10 @@ int score_variants_impl(fasim_engine* E, const char* const* rnas, const int32_t*
 		H.assign((size_t)nvar * 8, HitOut());
 		for (size_t k = 0; k < H.size(); k++) { hit_clear(H[k], -1); H[k].t.seg = (int)(k / 8); H[k].empty = true; }
 	};
-	for (int64_t k = 0; k < (int64_t)nq * nvar; k++) {
-		memset(&out[k], 0, sizeof out[k]);
-		for (int a = 0; a < 2; a++) for (int c = 0; c < FASIM_TRACK_CLASSES; c++) out[k].enc[a][c] = -1;
-	}
+	for (int64_t k = 0; k < (int64_t)nq * nvar; k++) blank_score(out[k]);
 	const std::vector<int> encs = enabled_encodings(*pp);
 	const int nenc = (int)encs.size();
-	std::vector<int64_t> todo;                    // the variants that are scored
+	std::vector<int64_t> todo;                  // the variants that are scored
 	for (int64_t v = 0; v < nvar; v++) if (vars[v].alt_len >= 0) todo.push_back(v);
 	if (todo.empty() || nenc == 0) {
 		if (hits) {
@@ -191,106 +364,27 @@ int score_variants_impl(fasim_engine* E, const char* const* rnas, const int32_t*
 	}
 	HIPOK(hipSetDevice(E->device));
 	const double ms0 = E->kernel_ms[4];
-	int64_t nprobs = 0, cells = 0;
+	UnitRun R{ E, "variants", dna, rs.resident, rec_off, vars, &encs };
 	try {
 		for (int q = 0; q < nq; q++) {
-			const int m = rna_lens[q];
-			std::vector<uint8_t> qc((size_t)m);
-			for (int i = 0; i < m; i++) qc[(size_t)i] = code2(rnas[q][i]);
-			rc = upload(E, E->vr_q, qc.data(), qc.size()); if (rc) return rc;
-			const bool rows_hbm = m > TOUCH_LDS_ROWS;
-			const size_t row_bytes = (size_t)6 * (size_t)touch_state_rows(m);      // of one problem
+			rc = open_query(R, rnas[q], rna_lens[q]); if (rc) return rc;
+			fasim_variant_score* row = out + (size_t)q * (size_t)nvar;
 			std::vector<HitOut> H;
 			PathCtx PC;
 			if (hits) {
 				blank_hits(H);
-				PC.E = E; PC.rna.assign(rnas[q], rnas[q] + m); PC.m = m; PC.encs = encs; PC.host = rs.host(E); PC.rec_off = rec_off; PC.rec_len = rec_len;
-				PC.vars = vars; PC.flank = flank; PC.pc = *pp; PC.pc.ntMin = 1; PC.pc.ntMax = INT_MAX; PC.rows_hbm = rows_hbm; PC.row_bytes = row_bytes;
+				PC.E = E; PC.rna.assign(rnas[q], rnas[q] + R.m); PC.m = R.m; PC.encs = encs; PC.host = rs.host(E); PC.rec_off = rec_off; PC.rec_len = rec_len;
+				PC.vars = vars; PC.flank = flank; PC.pc = *pp; PC.pc.ntMin = 1; PC.pc.ntMax = INT_MAX; PC.rows_hbm = R.rows_hbm; PC.row_bytes = R.row_bytes;
 			}
-			for (size_t w0 = 0; w0 < todo.size(); ) {
-				std::vector<VarWindow> wins;
-				std::vector<TouchProb> probs;
-				std::vector<uint8_t> alts, letters;
-				size_t tbytes = 0, w1 = w0;
-				for (; w1 < todo.size(); w1++) {
-					const fasim_variant& x = vars[todo[w1]];
-					const int64_t len = rec_len[x.rec];
-					const int64_t lo = std::max<int64_t>(0, x.pos - flank), hi = std::min<int64_t>(len, x.pos + x.ref_len + flank);
-					const int pre = (int)(x.pos - lo), post = (int)(hi - x.pos - x.ref_len);
-					const int n_al[2] = { pre + x.ref_len + post, pre + x.alt_len + post };
-					const size_t need = (size_t)nenc * (size_t)(pad16(n_al[0]) + pad16(n_al[1]));
-					if (w1 > w0 && (tbytes + need > VR_TCODE_BYTES || (int64_t)probs.size() + 2 * nenc > VR_MAX_PROBS ||
-						(rows_hbm && (probs.size() + 2 * (size_t)nenc) * row_bytes > VR_ROW_BYTES))) break;
-					// the record's letters of the window: in the resident buffer, or staged for this chunk
-					int64_t src = rec_off[x.rec] + lo;
-					if (!resident) { src = (int64_t)letters.size(); letters.insert(letters.end(), dna + rec_off[x.rec] + lo, dna + rec_off[x.rec] + hi); }
-					const int edge_lo = lo > 0, edge_hi = hi < len;      // cut by the flank, not by the record's end
-					for (int al = 0; al < 2; al++) {
-						VarWindow W; W.src = src; W.pre = pre; W.ref_len = x.ref_len; W.post = post; W.alt_off = 0; W.alt_len = -1; W.pad = 0;
-						if (al) { W.alt_off = (int32_t)alts.size(); W.alt_len = x.alt_len; alts.insert(alts.end(), x.alt, x.alt + x.alt_len); }
-						const int n = n_al[al], v0 = pre, v1 = pre + (al ? x.alt_len : x.ref_len);
-						for (int k = 0; k < nenc; k++) {
-							const int enc = encs[(size_t)k];
-							TouchProb P; P.tbase = (int64_t)tbytes; P.n = n; P.win = (int32_t)wins.size(); P.enc = enc;
-							if (enc & 1) { P.v0 = n - v1; P.v1 = n - v0; P.edge = edge_hi | (edge_lo << 1); }
-							else { P.v0 = v0; P.v1 = v1; P.edge = edge_lo | (edge_hi << 1); }
-							probs.push_back(P);
-							tbytes += (size_t)pad16(n);
-							cells += (int64_t)m * n;
-						}
-						wins.push_back(W);
-					}
-				}
-				const int np = (int)probs.size(), nv = (int)(w1 - w0);
-				nprobs += np;
-				if (alts.empty()) alts.push_back(0);
-				if (E->vr_wins.ensure(wins.size() * sizeof(VarWindow)) != hipSuccess || E->vr_probs.ensure((size_t)np * sizeof(TouchProb)) != hipSuccess ||
-					E->vr_alt.ensure(alts.size()) != hipSuccess || E->vr_tcodes.ensure(tbytes) != hipSuccess || E->vr_touch.ensure((size_t)np * sizeof(uint32_t)) != hipSuccess ||
-					E->vr_out.ensure((size_t)nv * 9 * sizeof(uint32_t)) != hipSuccess || (!resident && E->vr_dna.ensure(letters.size() + 1) != hipSuccess) ||
-					(rows_hbm && E->vr_rows.ensure((size_t)np * row_bytes) != hipSuccess)) {
-					(void)hipGetLastError();
-					return fail(E, FASIM_E_NOMEM, "variants: no device memory for a chunk of %d problems", np);
-				}
-				HIPOK(hipMemcpyAsync(E->vr_wins.p, wins.data(), wins.size() * sizeof(VarWindow), hipMemcpyHostToDevice, E->st));
-				HIPOK(hipMemcpyAsync(E->vr_probs.p, probs.data(), (size_t)np * sizeof(TouchProb), hipMemcpyHostToDevice, E->st));
-				HIPOK(hipMemcpyAsync(E->vr_alt.p, alts.data(), alts.size(), hipMemcpyHostToDevice, E->st));
-				if (!resident && !letters.empty()) HIPOK(hipMemcpyAsync(E->vr_dna.p, letters.data(), letters.size(), hipMemcpyHostToDevice, E->st));
-				VarEncodeLaunch EL;
-				EL.dna = resident ? E->dna_res.as<uint8_t>() : E->vr_dna.as<uint8_t>(); EL.alts = E->vr_alt.as<uint8_t>(); EL.wins = E->vr_wins.as<VarWindow>();
-				EL.probs = E->vr_probs.as<TouchProb>(); EL.nprob = np; EL.enc_lut = E->enc_lut.as<uint8_t>(); EL.tcodes = E->vr_tcodes.as<uint8_t>();
-				hipError_t he = launch_var_encode(EL, E->st);
-				if (he != hipSuccess) return fail(E, FASIM_E_HIP, "variants (encode) launch failed: %s", hipGetErrorString(he));
-				TouchLaunch TL;
-				TL.tcodes = E->vr_tcodes.as<uint8_t>(); TL.qcodes = E->vr_q.as<uint8_t>(); TL.m = m; TL.probs = E->vr_probs.as<TouchProb>(); TL.nprob = np;
-				TL.rows = rows_hbm ? E->vr_rows.as<uint16_t>() : nullptr; TL.out = E->vr_touch.as<uint32_t>();
-				{ TimedScope ts(E, 4); he = launch_touch(TL, E->st); }
-				if (he != hipSuccess) return fail(E, FASIM_E_HIP, "variants (touch) launch failed: %s", hipGetErrorString(he));
-				TouchReduceLaunch RL;
-				RL.touch = E->vr_touch.as<uint32_t>(); RL.nvar = nv; RL.nenc = nenc; RL.out = E->vr_out.as<uint32_t>();
-				memset(RL.enc, 0, sizeof RL.enc);
-				for (int k = 0; k < nenc; k++) RL.enc[k] = (uint8_t)encs[(size_t)k];
-				he = launch_touch_reduce(RL, E->st);
-				if (he != hipSuccess) return fail(E, FASIM_E_HIP, "variants (reduce) launch failed: %s", hipGetErrorString(he));
-				std::vector<uint32_t> words((size_t)nv * 9);
-				HIPOK(hipMemcpyAsync(words.data(), E->vr_out.p, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st));
-				HIPOK(hipStreamSynchronize(E->st));
-				drain_timed(E);
-				for (int k = 0; k < nv; k++) {
-					fasim_variant_score& s = out[(size_t)q * (size_t)nvar + (size_t)todo[w0 + (size_t)k]];
-					for (int a = 0; a < 2; a++) for (int c = 0; c < FASIM_TRACK_CLASSES; c++) {
-						const uint32_t w = words[(size_t)k * 9 + (size_t)a * 4 + (size_t)c];
-						s.value[a][c] = (int32_t)(w >> 9);
-						s.enc[a][c] = (w >> 9) ? (int32_t)(w & 0xff) : -1;
-					}
-					s.flags = (int32_t)(words[(size_t)k * 9 + 8] & 1);
-				}
-				if (hits) { rc = trace_chunk(PC, probs, todo.data() + w0, nv, out + (size_t)q * (size_t)nvar, H); if (rc) return rc; }
-				w0 = w1;
-			}
+			HapSides W;      // of the unit asked for last
+			rc = run_units(R, todo.size(),
+				[&](size_t k) { const int64_t v = todo[k]; plain_sides(vars[v], rec_len[vars[v].rec], flank, W); return ScoreUnit{ v, &W, &row[v] }; },
+				[&](size_t u0, int nu, const std::vector<TouchProb>& probs) { return hits ? trace_chunk(PC, probs, todo.data() + u0, nu, row, H) : FASIM_OK; });
+			if (rc) return rc;
 			if (hits && !(hits[q] = pack_hits(H))) return fail(E, FASIM_E_NOMEM, "out of memory");
 		}
 	} catch (const std::bad_alloc&) { (void)hipStreamSynchronize(E->st); return fail(E, FASIM_E_NOMEM, "out of memory"); }
-	if (stats) { stats->problems = nprobs; stats->cells = cells; stats->kernel_s = (E->kernel_ms[4] - ms0) * 1e-3; stats->total_s = now_s() - t0; }
+	if (stats) { stats->problems = R.nprobs; stats->cells = R.cells; stats->kernel_s = (E->kernel_ms[4] - ms0) * 1e-3; stats->total_s = now_s() - t0; }
 	return FASIM_OK;
 }
 
@@ -404,12 +498,10 @@ int fasim_variants_tsv(const fasim_variant* vars, const fasim_variant_score* sco
 // ---- variants on a sample's phased haplotypes (kernel: haplotype.hip) ------------------------------------------
 // The planner: per record the consistent sets A_0 and A_1, per (focus, haplotype) a walk outwards from the focus through the applied
 // neighbours until `flank` haplotype letters are collected on each side.  The window is never materialised for the device: it goes
-// there as pieces (HapPiece) over the record and the uploaded ALT letters.  A haplotype whose walk met no neighbour has the plain
-// windows and goes through fasim_score_variants; the others are units of (entry, haplotype) in chunks of their own, cut as there.
+// there as pieces (HapPiece) over the record and the uploaded ALT letters.  Every computed (entry, haplotype) is a unit of run_units,
+// whether its walk met a neighbour or not: without one its sides are the plain windows' (plain_sides).
 namespace {
 
-struct HPiece { int64_t src; int32_t len; int64_t ent; };      // ent < 0: record letters [src, src + len); else letters [src, src + len) of entry ent's ALT
-struct HapSides { std::vector<HPiece> left, right; int32_t applied = 0; bool edge_lo = false, edge_hi = false; };
 // per haplotype and entry: 1 in A_h, 2 qualified but rejected for overlap, 3 qualifies but for its phase (an unphased heterozygote), else 0
 struct HapSets { std::vector<uint8_t> status[2]; std::vector<int64_t> acc[2]; };
 
@@ -479,8 +571,6 @@ void hap_walk(const fasim_variant* vars, const std::vector<int64_t>& acc, int64_
 	S.edge_hi = cut || at < len;
 }
 
-inline int32_t pieces_len(const std::vector<HPiece>& p) { int32_t n = 0; for (const HPiece& q : p) n += q.len; return n; }
-
 void pieces_letters(const fasim_variant* vars, const char* record, const std::vector<HPiece>& p, std::string& o)
 {
 	for (const HPiece& q : p) o.append(q.ent < 0 ? record + q.src : vars[q.ent].alt + q.src, (size_t)q.len);
@@ -502,23 +592,6 @@ bool hap_sides_equal(const fasim_variant* vars, const char* record, const HapSid
 		pieces_len(W[0].right) != pieces_len(W[1].right)) return false;
 	for (int h = 0; h < 2; h++) { w[h].clear(); pieces_letters(vars, record, W[h].left, w[h]); pieces_letters(vars, record, W[h].right, w[h]); }
 	return w[0] == w[1];
-}
-
-// the refusals of fasim_score_variants for the entries themselves
-int check_variant_entries(fasim_engine* E, const fasim_variant* vars, int64_t nvar, const int64_t* rec_len, int32_t nrec)
-{
-	for (int64_t v = 0; v < nvar; v++) {
-		const fasim_variant& x = vars[v];
-		if (x.alt_len < 0) continue;
-		if (x.ref_len < 1) return fail(E, FASIM_E_ARG, "variant %lld: ref_len %d < 1", (long long)v, x.ref_len);
-		if (x.ref_len > FASIM_MAX_ALLELE || x.alt_len < 1 || x.alt_len > FASIM_MAX_ALLELE || !x.alt)
-			return fail(E, FASIM_E_ARG, "variant %lld: an allele has 1 to %d letters (REF %d, ALT %d)", (long long)v, FASIM_MAX_ALLELE, x.ref_len, x.alt_len);
-		if (x.rec < 0 || x.rec >= nrec) return fail(E, FASIM_E_ARG, "variant %lld: record %d of %d", (long long)v, x.rec, nrec);
-		if (x.pos < 0 || x.pos > rec_len[x.rec] - x.ref_len)
-			return fail(E, FASIM_E_ARG, "variant %lld: [%lld, %lld) lies outside record %d of %lld nt", (long long)v, (long long)x.pos,
-				(long long)(x.pos + x.ref_len), x.rec, (long long)rec_len[x.rec]);
-	}
-	return FASIM_OK;
 }
 
 // carried, and flag bits 1 and 2, of focus v on haplotype h: one look at the record's entries within reach
@@ -607,31 +680,23 @@ int fasim_score_haplotypes(fasim_engine* E, const char* const* rnas, const int32
 {
 	if (!E) return fail(nullptr, FASIM_E_ARG, "null engine");
 	if (nvar < 0 || (nvar > 0 && (!vars || !gts || !out))) return fail(E, FASIM_E_ARG, "bad arguments");
-	// the refusals of fasim_score_variants: the call's own with no entry (no GPU work), then the entries'
-	fasim_variant_stats st0;
-	int rc = fasim_score_variants(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, vars, 0, flank, pp, nullptr, &st0); if (rc) return rc;
-	rc = check_variant_entries(E, vars, nvar, rec_len, nrec); if (rc) return rc;
 	RecordSet rs;
-	rc = record_set_open(E, dna, rec_off, rec_len, nrec, false, rs); if (rc) return rc;
-	const bool resident = rs.resident;
+	int rc = check_variant_call(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, flank, pp, rs); if (rc) return rc;
+	rc = check_variant_entries(E, vars, nvar, rec_len, nrec); if (rc) return rc;
 	const char* host = rs.host(E);
 	const double t0 = now_s();
 	if (stats) memset(stats, 0, sizeof *stats);
 	for (int64_t k = 0; k < (int64_t)nq * nvar; k++) {
 		memset(&out[k], 0, sizeof out[k]);
-		for (int h = 0; h < 2; h++) for (int a = 0; a < 2; a++) for (int c = 0; c < FASIM_TRACK_CLASSES; c++) out[k].hap[h].enc[a][c] = -1;
+		for (int h = 0; h < 2; h++) blank_score(out[k].hap[h]);
 	}
 	const std::vector<int> encs = enabled_encodings(*pp);
-	const int nenc = (int)encs.size();
 	struct Unit { int64_t v; int h; };
 	try {
-		// ---- the plan ----
+		// ---- the plan: the sides of every (entry, haplotype), and as units those that are computed ----
 		std::vector<HapSides> sides((size_t)nvar * 2);
-		std::vector<uint8_t> same((size_t)nvar, 0);
-		std::vector<int64_t> plain;                    // entries with a haplotype on the plain windows
-		std::vector<int64_t> plain_at((size_t)nvar, -1);
+		std::vector<uint8_t> same((size_t)nvar, 0);      // both haplotypes have the windows of haplotype 0, which alone is computed
 		std::vector<Unit> units;
-		std::vector<int64_t> unit_at((size_t)nvar * 2, -1);
 		{
 			std::vector<std::vector<int64_t>> by_rec((size_t)nrec);
 			for (int64_t k = 0; k < nvar; k++) if (vars[k].rec >= 0 && vars[k].rec < nrec) by_rec[(size_t)vars[k].rec].push_back(k);
@@ -655,157 +720,32 @@ int fasim_score_haplotypes(fasim_engine* E, const char* const* rnas, const int32
 					for (int h = 0; h < 2; h++) hap_walk(vars, S.acc[h], v, rec_len[r], flank, W[h]);
 					const bool eq = hap_sides_equal(vars, record, W, w);
 					same[(size_t)v] = eq;
-					for (int h = 0; h < (eq ? 1 : 2); h++) {
-						if (W[h].applied == 0) { if (plain_at[(size_t)v] < 0) { plain_at[(size_t)v] = (int64_t)plain.size(); plain.push_back(v); } }
-						else { unit_at[(size_t)v * 2 + (size_t)h] = (int64_t)units.size(); units.push_back({ v, h }); }
-					}
+					for (int h = 0; h < (eq ? 1 : 2); h++) units.push_back({ v, h });
 					for (int q = 0; q < nq; q++) for (int h = 0; h < 2; h++) out[(size_t)q * (size_t)nvar + (size_t)v].applied[h] = W[h].applied;
 				}
 			}
 		}
-		// ---- the plain windows: fasim_score_variants itself ----
-		std::vector<fasim_variant> pv(plain.size());
-		for (size_t k = 0; k < plain.size(); k++) pv[k] = vars[plain[k]];
-		std::vector<fasim_variant_score> ps((size_t)nq * plain.size());
-		fasim_variant_stats pst;
-		memset(&pst, 0, sizeof pst);
-		if (!plain.empty()) {
-			rc = fasim_score_variants(E, rnas, rna_lens, nq, dna, rec_off, rec_len, nrec, pv.data(), (int64_t)pv.size(), flank, pp, ps.data(), &pst);
+		// ---- the units: k_hap_encode, then the kernels of section 19 ----
+		UnitRun R{ E, "haplotypes", dna, rs.resident, rec_off, vars, &encs };
+		const double ms0 = E->kernel_ms[4];
+		const bool run = !units.empty() && !encs.empty();
+		if (run) HIPOK(hipSetDevice(E->device));
+		for (int q = 0; run && q < nq; q++) {
+			rc = open_query(R, rnas[q], rna_lens[q]); if (rc) return rc;
+			fasim_hap_score* row = out + (size_t)q * (size_t)nvar;
+			rc = run_units(R, units.size(),
+				[&](size_t k) { const Unit& U = units[k]; return ScoreUnit{ U.v, &sides[(size_t)U.v * 2 + (size_t)U.h], &row[U.v].hap[U.h] }; },
+				[](size_t, int, const std::vector<TouchProb>&) { return FASIM_OK; });
 			if (rc) return rc;
 		}
-		// ---- the units with neighbours: k_hap_encode, then the kernels of section 19 ----
-		std::vector<fasim_variant_score> us((size_t)nq * units.size());
-		for (fasim_variant_score& s : us) { memset(&s, 0, sizeof s); for (int a = 0; a < 2; a++) for (int c = 0; c < FASIM_TRACK_CLASSES; c++) s.enc[a][c] = -1; }
-		int64_t nprobs = 0, cells = 0;
-		const double ms0 = E->kernel_ms[4];
-		if (!units.empty() && nenc > 0) {
-			HIPOK(hipSetDevice(E->device));
-			for (int q = 0; q < nq; q++) {
-				const int m = rna_lens[q];
-				std::vector<uint8_t> qc((size_t)m);
-				for (int i = 0; i < m; i++) qc[(size_t)i] = code2(rnas[q][i]);
-				rc = upload(E, E->vr_q, qc.data(), qc.size()); if (rc) return rc;
-				const bool rows_hbm = m > TOUCH_LDS_ROWS;
-				const size_t row_bytes = (size_t)6 * (size_t)touch_state_rows(m);      // of one problem
-				for (size_t u0 = 0; u0 < units.size(); ) {
-					std::vector<HapWindow> wins;
-					std::vector<HapPiece> pieces;
-					std::vector<int32_t> ends;
-					std::vector<TouchProb> probs;
-					std::vector<uint8_t> alts, letters;
-					size_t tbytes = 0, u1 = u0;
-					for (; u1 < units.size(); u1++) {
-						const Unit& U = units[u1];
-						const fasim_variant& x = vars[U.v];
-						const HapSides& W = sides[(size_t)U.v * 2 + (size_t)U.h];
-						const int pre = pieces_len(W.left), post = pieces_len(W.right);
-						const int n_al[2] = { pre + x.ref_len + post, pre + x.alt_len + post };
-						const size_t need = (size_t)nenc * (size_t)(pad16(n_al[0]) + pad16(n_al[1]));
-						if (u1 > u0 && (tbytes + need > VR_TCODE_BYTES || (int64_t)probs.size() + 2 * nenc > VR_MAX_PROBS ||
-							(rows_hbm && (probs.size() + 2 * (size_t)nenc) * row_bytes > VR_ROW_BYTES))) break;
-						// the unit's pieces for the device: record letters in the resident buffer or staged for this chunk, ALT letters uploaded
-						auto device_piece = [&](const HPiece& p) {
-							HapPiece D; D.pad = 0;
-							if (p.ent < 0) {
-								D.alt = 0; D.src = rec_off[x.rec] + p.src;
-								if (!resident) { D.src = (int64_t)letters.size(); letters.insert(letters.end(), dna + rec_off[x.rec] + p.src, dna + rec_off[x.rec] + p.src + p.len); }
-							} else {
-								D.alt = 1; D.src = (int64_t)alts.size();
-								alts.insert(alts.end(), vars[p.ent].alt + p.src, vars[p.ent].alt + p.src + p.len);
-							}
-							return D;
-						};
-						std::vector<HapPiece> dl, dr;
-						for (const HPiece& p : W.left) dl.push_back(device_piece(p));
-						for (const HPiece& p : W.right) dr.push_back(device_piece(p));
-						const HPiece focus[2] = { { x.pos, x.ref_len, -1 }, { 0, x.alt_len, U.v } };
-						const int edge_lo = W.edge_lo, edge_hi = W.edge_hi;
-						for (int al = 0; al < 2; al++) {
-							HapWindow H; H.piece0 = (int64_t)pieces.size(); H.npiece = (int32_t)(dl.size() + 1 + dr.size()); H.pad = 0;
-							int32_t run = 0;
-							for (size_t k = 0; k < dl.size(); k++) { pieces.push_back(dl[k]); run += W.left[k].len; ends.push_back(run); }
-							pieces.push_back(device_piece(focus[al])); run += focus[al].len; ends.push_back(run);
-							for (size_t k = 0; k < dr.size(); k++) { pieces.push_back(dr[k]); run += W.right[k].len; ends.push_back(run); }
-							const int n = n_al[al], v0 = pre, v1 = pre + focus[al].len;
-							if (run != n || n > TOUCH_MAX_COLS) return fail(E, FASIM_E_ARG, "haplotypes: a window of %d letters in pieces of %d", n, run);
-							for (int k = 0; k < nenc; k++) {
-								const int enc = encs[(size_t)k];
-								TouchProb P; P.tbase = (int64_t)tbytes; P.n = n; P.win = (int32_t)wins.size(); P.enc = enc;
-								if (enc & 1) { P.v0 = n - v1; P.v1 = n - v0; P.edge = edge_hi | (edge_lo << 1); }
-								else { P.v0 = v0; P.v1 = v1; P.edge = edge_lo | (edge_hi << 1); }
-								probs.push_back(P);
-								tbytes += (size_t)pad16(n);
-								cells += (int64_t)m * n;
-							}
-							wins.push_back(H);
-						}
-					}
-					const int np = (int)probs.size(), nu = (int)(u1 - u0);
-					nprobs += np;
-					if (alts.empty()) alts.push_back(0);
-					if (E->vr_hwins.ensure(wins.size() * sizeof(HapWindow)) != hipSuccess || E->vr_pieces.ensure(pieces.size() * sizeof(HapPiece)) != hipSuccess ||
-						E->vr_ends.ensure(ends.size() * sizeof(int32_t)) != hipSuccess || E->vr_probs.ensure((size_t)np * sizeof(TouchProb)) != hipSuccess ||
-						E->vr_alt.ensure(alts.size()) != hipSuccess || E->vr_tcodes.ensure(tbytes) != hipSuccess || E->vr_touch.ensure((size_t)np * sizeof(uint32_t)) != hipSuccess ||
-						E->vr_out.ensure((size_t)nu * 9 * sizeof(uint32_t)) != hipSuccess || (!resident && E->vr_dna.ensure(letters.size() + 1) != hipSuccess) ||
-						(rows_hbm && E->vr_rows.ensure((size_t)np * row_bytes) != hipSuccess)) {
-						(void)hipGetLastError();
-						return fail(E, FASIM_E_NOMEM, "haplotypes: no device memory for a chunk of %d problems", np);
-					}
-					HIPOK(hipMemcpyAsync(E->vr_hwins.p, wins.data(), wins.size() * sizeof(HapWindow), hipMemcpyHostToDevice, E->st));
-					HIPOK(hipMemcpyAsync(E->vr_pieces.p, pieces.data(), pieces.size() * sizeof(HapPiece), hipMemcpyHostToDevice, E->st));
-					HIPOK(hipMemcpyAsync(E->vr_ends.p, ends.data(), ends.size() * sizeof(int32_t), hipMemcpyHostToDevice, E->st));
-					HIPOK(hipMemcpyAsync(E->vr_probs.p, probs.data(), (size_t)np * sizeof(TouchProb), hipMemcpyHostToDevice, E->st));
-					HIPOK(hipMemcpyAsync(E->vr_alt.p, alts.data(), alts.size(), hipMemcpyHostToDevice, E->st));
-					if (!resident && !letters.empty()) HIPOK(hipMemcpyAsync(E->vr_dna.p, letters.data(), letters.size(), hipMemcpyHostToDevice, E->st));
-					HapEncodeLaunch EL;
-					EL.dna = resident ? E->dna_res.as<uint8_t>() : E->vr_dna.as<uint8_t>(); EL.alts = E->vr_alt.as<uint8_t>(); EL.wins = E->vr_hwins.as<HapWindow>();
-					EL.pieces = E->vr_pieces.as<HapPiece>(); EL.ends = E->vr_ends.as<int32_t>();
-					EL.probs = E->vr_probs.as<TouchProb>(); EL.nprob = np; EL.enc_lut = E->enc_lut.as<uint8_t>(); EL.tcodes = E->vr_tcodes.as<uint8_t>();
-					hipError_t he = launch_hap_encode(EL, E->st);
-					if (he != hipSuccess) return fail(E, FASIM_E_HIP, "haplotypes (encode) launch failed: %s", hipGetErrorString(he));
-					TouchLaunch TL;
-					TL.tcodes = E->vr_tcodes.as<uint8_t>(); TL.qcodes = E->vr_q.as<uint8_t>(); TL.m = m; TL.probs = E->vr_probs.as<TouchProb>(); TL.nprob = np;
-					TL.rows = rows_hbm ? E->vr_rows.as<uint16_t>() : nullptr; TL.out = E->vr_touch.as<uint32_t>();
-					{ TimedScope ts(E, 4); he = launch_touch(TL, E->st); }
-					if (he != hipSuccess) return fail(E, FASIM_E_HIP, "haplotypes (touch) launch failed: %s", hipGetErrorString(he));
-					TouchReduceLaunch RL;
-					RL.touch = E->vr_touch.as<uint32_t>(); RL.nvar = nu; RL.nenc = nenc; RL.out = E->vr_out.as<uint32_t>();
-					memset(RL.enc, 0, sizeof RL.enc);
-					for (int k = 0; k < nenc; k++) RL.enc[k] = (uint8_t)encs[(size_t)k];
-					he = launch_touch_reduce(RL, E->st);
-					if (he != hipSuccess) return fail(E, FASIM_E_HIP, "haplotypes (reduce) launch failed: %s", hipGetErrorString(he));
-					std::vector<uint32_t> words((size_t)nu * 9);
-					HIPOK(hipMemcpyAsync(words.data(), E->vr_out.p, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, E->st));
-					HIPOK(hipStreamSynchronize(E->st));
-					drain_timed(E);
-					for (int k = 0; k < nu; k++) {
-						fasim_variant_score& s = us[(size_t)q * units.size() + u0 + (size_t)k];
-						for (int a = 0; a < 2; a++) for (int c = 0; c < FASIM_TRACK_CLASSES; c++) {
-							const uint32_t w = words[(size_t)k * 9 + (size_t)a * 4 + (size_t)c];
-							s.value[a][c] = (int32_t)(w >> 9);
-							s.enc[a][c] = (w >> 9) ? (int32_t)(w & 0xff) : -1;
-						}
-						s.flags = (int32_t)(words[(size_t)k * 9 + 8] & 1);
-					}
-					u0 = u1;
-				}
-			}
-		}
-		// ---- both parts into the entries ----
+		// ---- the computed haplotype into both, and the flags that the scores bring ----
 		for (int q = 0; q < nq; q++) for (int64_t v = 0; v < nvar; v++) {
 			if (vars[v].alt_len < 0 || vars[v].rec < 0 || vars[v].rec >= nrec) continue;
 			fasim_hap_score& o = out[(size_t)q * (size_t)nvar + (size_t)v];
-			for (int h = 0; h < 2; h++) {
-				const int hs = same[(size_t)v] ? 0 : h;      // the haplotype that was computed
-				const int64_t u = unit_at[(size_t)v * 2 + (size_t)hs];
-				o.hap[h] = u >= 0 ? us[(size_t)q * units.size() + (size_t)u] : ps[(size_t)q * plain.size() + (size_t)plain_at[(size_t)v]];
-				o.flags[h] |= (o.hap[h].flags & 1) | (same[(size_t)v] ? 8 : 0);
-			}
+			if (same[(size_t)v]) o.hap[1] = o.hap[0];
+			for (int h = 0; h < 2; h++) o.flags[h] |= (o.hap[h].flags & 1) | (same[(size_t)v] ? 8 : 0);
 		}
-		if (stats) {
-			stats->problems = pst.problems + nprobs; stats->cells = pst.cells + cells;
-			stats->kernel_s = pst.kernel_s + (units.empty() ? 0.0 : (E->kernel_ms[4] - ms0) * 1e-3); stats->total_s = now_s() - t0;
-		}
+		if (stats) { stats->problems = R.nprobs; stats->cells = R.cells; stats->kernel_s = run ? (E->kernel_ms[4] - ms0) * 1e-3 : 0.0; stats->total_s = now_s() - t0; }
 	} catch (const std::bad_alloc&) { (void)hipStreamSynchronize(E->st); return fail(E, FASIM_E_NOMEM, "out of memory"); }
 	return FASIM_OK;
 }

@@ -1,12 +1,13 @@
-// fasim-longtarget_amd/csrc/haplotype.hip -- k_hap_encode: the target codes of allele windows written in the letters of a haplotype,
-// for gfx950.
+// fasim-longtarget_amd/csrc/haplotype.hip -- k_hap_encode: the target codes of allele windows written in the letters of the record or
+// of a haplotype, for gfx950 (DESIGN.md sections 19 and 25).
 //
 // The window of a variant on a haplotype is the record with the haplotype's other variants applied, which nobody materialises: the
-// host describes it as pieces (stretches of the record and of uploaded ALT strings) with their running ends.  One workgroup per
-// problem (window x encoding), as k_var_encode: the first HAP_LDS_PIECES ends of the window are staged in LDS, every thread maps its
+// host describes it as pieces (stretches of the record and of uploaded ALT strings) with their running ends.  The plain window of
+// section 19 -- flank, allele, flank -- is the same thing in at most three pieces, so this kernel encodes those as well.  One workgroup
+// per problem (window x encoding): the first HAP_LDS_PIECES ends of the window are staged in LDS, every thread maps its
 // column (mirrored for an odd encoding) to a piece and an offset by binary search -- in LDS, or in HBM for the pieces behind the
-// stage -- fetches the letter and writes its code.  The layout is k_var_encode's, so k_touch and k_touch_reduce (variant.hip) run on
-// it unchanged.  Plain vector stores only, one writer per byte, no atomics.
+// stage -- fetches the letter and writes its code: tcodes[tbase + c] is the code of window letter c, or of letter n - 1 - c
+// for an odd encoding, which is what k_touch and k_touch_reduce (variant.hip) read.  Plain vector stores only, one writer per byte, no atomics.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"

@@ -247,13 +247,9 @@ hipError_t launch_site_ends_short(const SiteEndsLaunch& L, hipStream_t st);     
 // ---- variant.hip: the best local alignment through a variant, per allele window and encoding ------------
 constexpr int TOUCH_MAX_COLS = 5120;            // columns of an allele window: FASIM_MAX_ALLELE + 2 * FASIM_MAX_FLANK (the 16-bit row state holds 2 * 5 * 5 120 + 1)
 constexpr int TOUCH_LDS_ROWS = 8192;            // query rows whose DP state (7 bytes per row) k_touch keeps in LDS
-// One allele window in record letters: `pre` letters from dna + src, then the allele (alt_len < 0: the ref_len letters that follow in
-// the record, else alt_len letters from alts + alt_off), then `post` letters from dna + src + pre + ref_len
-struct VarWindow { int64_t src; int32_t pre, ref_len, post, alt_off, alt_len, pad; };
-// One problem: window `win` under encoding `enc`; its n target codes at tcodes + tbase, the allele's columns [v0, v1) (mirrored for an
+// One problem: window `win` (a HapWindow, below) under encoding `enc`; its n target codes at tcodes + tbase, the allele's columns [v0, v1) (mirrored for an
 // odd encoding, as the codes are), edge bit 0 / 1: the unit's first / last column is an end that the flank cut
 struct TouchProb { int64_t tbase; int32_t n, v0, v1, edge, win, enc; };
-struct VarEncodeLaunch { const uint8_t* dna; const uint8_t* alts; const VarWindow* wins; const TouchProb* probs; int32_t nprob; const uint8_t* enc_lut /*[48][256] -> code*/; uint8_t* tcodes; };
 struct TouchLaunch {
 	const uint8_t* tcodes; const uint8_t* qcodes; int32_t m;      // query codes of the stage-2 alphabet, m real rows (no pad rows)
 	const TouchProb* probs; int32_t nprob;
@@ -263,12 +259,11 @@ struct TouchLaunch {
 // problems of a launch in (variant, allele, k) order, k = index into enc[0 .. nenc); out[variant][9]: per (allele, class) word
 // (2 * value + b) << 8 | smallest encoding that attains the value (0xff: value 0), then the variant's clipped flag
 struct TouchReduceLaunch { const uint32_t* touch; int32_t nvar, nenc; uint8_t enc[48]; uint32_t* out; };
-hipError_t launch_var_encode(const VarEncodeLaunch& L, hipStream_t st);
 int touch_threads(int m);        // threads of k_touch's workgroup: 64, 128 or 256
 int touch_state_rows(int m);     // 16-bit words per array of a problem's row state: m rounded up to whole rows-per-thread x threads
 hipError_t launch_touch(const TouchLaunch& L, hipStream_t st);
 hipError_t launch_touch_reduce(const TouchReduceLaunch& L, hipStream_t st);
-// k_touch_path: the path behind a value.  One item = problem `prob` of the launch that k_var_encode served,
+// k_touch_path: the path behind a value.  One item = problem `prob` of the launch that k_hap_encode served,
 // with the plain value its unit attains; its direction bytes at dirs + dir_off ([n][touch_state_rows(m)]), its CIGAR words (last
 // operation first, (len << 4) | op) at cigar + cig_off, at most cig_cap of them
 constexpr int64_t TOUCH_PATH_MAX_CELLS = (int64_t)1 << 26;      // m * n of a problem that is traced
@@ -282,11 +277,11 @@ struct TouchPathLaunch {
 };
 hipError_t launch_touch_path(const TouchPathLaunch& L, hipStream_t st);
 
-// ---- haplotype.hip: allele windows in the letters of a haplotype, assembled from pieces ------------------
+// ---- haplotype.hip: allele windows assembled from pieces, in the letters of the record or of a haplotype (DESIGN.md sections 19, 25) --
 // A window is npiece pieces in window order, pieces[piece0 .. piece0 + npiece): a stretch of the record (alt 0: letters from dna +
 // src) or of an uploaded ALT string (alt 1: from alts + src); ends[piece0 + k] is the number of window letters up to and including
-// piece k, so the last one is the window's length.  A problem is a TouchProb whose `win` names a HapWindow: k_hap_encode fills the
-// tcodes k_var_encode would fill for the same letters.
+// piece k, so the last one is the window's length.  A problem is a TouchProb whose `win` names a HapWindow: k_hap_encode fills
+// tcodes[tbase + c], c in [0, n), with the code of window letter c (n - 1 - c for an odd encoding) under the problem's encoding.
 constexpr int HAP_LDS_PIECES = 64;              // piece ends of a window that k_hap_encode searches in LDS; the rest it searches in HBM
 struct HapPiece { int64_t src; int32_t alt, pad; };
 struct HapWindow { int64_t piece0; int32_t npiece, pad; };

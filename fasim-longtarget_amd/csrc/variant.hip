@@ -10,7 +10,7 @@
 //
 // The column step is colstep.h's, in doubled values: one workgroup of touch_threads(m) threads per problem, the 16-bit row state in
 // LDS or, for queries above TOUCH_LDS_ROWS rows, in HBM; the arithmetic is 32-bit.
-// k_var_encode assembles and encodes the windows from the record on the device; k_touch_reduce folds the problems of a variant into
+// k_hap_encode (haplotype.hip) assembles and encodes the windows on the device; k_touch_reduce folds the problems of a variant into
 // nine words.  No atomics on global memory, plain vector stores only; every output word has one writer.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -19,26 +19,6 @@
 namespace fasim {
 
 constexpr int VT_THREADS = 256;
-
-// tcodes[tbase + c], c in [0, n): the code of window letter c (n - 1 - c for an odd encoding) under the problem's encoding
-__global__ void __launch_bounds__(VT_THREADS) k_var_encode(VarEncodeLaunch a)
-{
-	const int p = blockIdx.x;
-	if (p >= a.nprob) return;
-	const TouchProb P = a.probs[p];
-	const VarWindow W = a.wins[P.win];
-	const uint8_t* lut = a.enc_lut + P.enc * 256;
-	const uint8_t* src = a.dna + W.src;
-	const int alen = W.alt_len < 0 ? W.ref_len : W.alt_len;
-	for (int c = threadIdx.x; c < P.n; c += VT_THREADS) {
-		const int j = (P.enc & 1) ? P.n - 1 - c : c;
-		uint8_t letter;
-		if (j < W.pre) letter = src[j];
-		else if (j < W.pre + alen) letter = W.alt_len < 0 ? src[j] : a.alts[W.alt_off + (j - W.pre)];
-		else letter = src[W.pre + W.ref_len + (j - W.pre - alen)];
-		a.tcodes[P.tbase + c] = lut[letter];
-	}
-}
 
 // One workgroup of NT threads per problem; rows, LDS and IN_LDS as ColState has them
 template <int NT, bool IN_LDS>
@@ -124,14 +104,6 @@ __global__ void __launch_bounds__(VT_THREADS) k_touch_reduce(TouchReduceLaunch a
 		}
 	}
 	a.out[(int64_t)v * 9 + 8] = top & 1;
-}
-
-hipError_t launch_var_encode(const VarEncodeLaunch& L, hipStream_t st)
-{
-	if (L.nprob <= 0) return hipSuccess;
-	if (!L.dna || !L.alts || !L.wins || !L.probs || !L.enc_lut || !L.tcodes) return hipErrorInvalidValue;
-	hipLaunchKernelGGL(k_var_encode, dim3((unsigned)L.nprob), dim3(VT_THREADS), 0, st, L);
-	return hipGetLastError();
 }
 
 int touch_threads(int m) { return m <= 64 ? 64 : (m <= 128 ? 128 : VT_THREADS); }

@@ -1,7 +1,7 @@
 // fasim-longtarget_amd/csrc/variant_path.hip -- the alignment behind a variant score: the path through the touching matrix T of
 // variant.hip, traced in T itself, for gfx950.
 //
-// An item is one problem of the launch that k_var_encode and k_touch served (its target codes are still in place) together with the
+// An item is one problem of the launch that k_hap_encode and k_touch served (its target codes are still in place) together with the
 // plain value its unit attains.  k_touch_path runs k_touch's column step over it once more -- the same ColState, col_row and col_cell
 // of colstep.h, uniform loops --, in plain values (the clip bit is dropped), and keeps one direction byte per cell:
 //     bits 0-1  where H came from: 0 the diagonal (Hdiag > 0), 1 a first pair (Hdiag == 0, before v1), 2 E, 3 F

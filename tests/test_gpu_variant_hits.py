@@ -12,7 +12,7 @@ import pytest
 import synth
 import __graft_entry__ as entry
 from test_track_cpu import enabled_encodings, encode_unit
-from test_gpu_variants import EXE, LDS_ROWS, _h19, _other, _query, _records, _variants
+from test_gpu_variants import EXE, LDS_ROWS, _end_cases, _h19, _other, _query, _records, _variants
 from test_variant_hits_cpu import expected_hits, span_ref
 
 pytestmark = pytest.mark.gpu
@@ -138,6 +138,14 @@ def test_all_48_encodings_and_the_flanks(mod, eng, golden_dir, flank):
         assert any(clipped) and not all(clipped)
     if flank == 2048:
         assert not any(s["clipped"] for (v, _, _), s in slots.items() if v in (0, 1, 2, 3, 8))
+
+
+@pytest.mark.parametrize("flank", [0, 10])
+def test_windows_with_an_empty_side(mod, eng, golden_dir, flank):
+    """The variants on the record's first and last letters (test_gpu_variants): hits over windows of one or two pieces."""
+    query, rec, variants, p = _end_cases(mod, golden_dir)
+    _, slots = _check(mod, eng, query, [rec], variants, flank, p, f"ends, flank={flank}")
+    assert {v for (v, _, _) in slots} == set(range(len(variants)))
 
 
 def test_a_hit_that_reaches_the_allele_only_through_a_gap_ends_in_d(mod, eng):

@@ -151,6 +151,48 @@ def test_all_48_encodings_and_the_flanks(mod, eng, golden_dir, flank):
         assert not flags[[0, 1, 2, 3, 8]].any()              # their windows are whole records: no end is cut by the flank
 
 
+def _end_cases(mod, golden_dir):
+    """(20-nt query, a 301-nt record with pre-images of the query on its first and its last letters, an SNV, an insertion and a
+    deletion at position 0 and the same three ending on the record's last letter): windows with an empty side."""
+    p = mod.default_params()
+    query = _query(golden_dir, 20)
+    rng = np.random.default_rng(27)
+    rec = bytearray(synth.random_dna(301, 27))
+    encs = enabled_encodings(p)
+    head, tail = _pre_image(query, encs[0], rng), _pre_image(query, next(e for e in encs if e & 1), rng)
+    rec[:len(head)] = head
+    rec[len(rec) - len(tail):] = tail
+    rec, n, V = bytes(rec), len(rec), mod.Variant
+
+    def ref(a, k):
+        return rec[a:a + k].decode()
+    variants = [V(1, "c", 0, "snv0", ref(0, 1), _other(rec[0:1])),
+                V(2, "c", 0, "ins0", ref(0, 1), ref(0, 1) + "GA"),
+                V(3, "c", 0, "del0", ref(0, 4), ref(0, 1)),
+                V(4, "c", n - 1, "snvN", ref(n - 1, 1), _other(rec[n - 1:n])),
+                V(5, "c", n - 1, "insN", ref(n - 1, 1), ref(n - 1, 1) + "GA"),
+                V(6, "c", n - 4, "delN", ref(n - 4, 4), ref(n - 4, 1))]
+    return query, rec, variants, p
+
+
+@pytest.mark.parametrize("flank", [0, 10])
+def test_windows_with_an_empty_side(mod, golden_dir, flank):
+    """Variants on the record's first and last letters: the window has no left or no right side (with flank 0 neither: the allele is
+    the whole window), so it is two pieces or one.  All 48 encodings, streamed and resident, equal to the restatement."""
+    query, rec, variants, p = _end_cases(mod, golden_dir)
+    assert len(enabled_encodings(p)) == 48
+    e = mod.Engine(0)
+    want = _check(e, query, [rec], variants, flank, p, f"streamed, flank={flank}")
+    assert want[0][:3].max() > 0 and want[0][3:].max() > 0
+    streamed = e.score_variants(variants, [rec], p, flank=flank, queries=[query])
+    e.load_dna(rec)
+    resident = e.score_variants(variants, None, p, flank=flank, queries=[query])
+    for a, b in zip(streamed, resident):
+        assert np.array_equal(a, b)
+    assert e.last_variant_stats["problems"] == 2 * 48 * len(variants)
+    e.close()
+
+
 def test_resident_record_and_several_queries(mod, golden_dir):
     e = mod.Engine(0)
     p = mod.default_params(rule=2)
