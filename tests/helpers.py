@@ -1385,3 +1385,215 @@ def scan_param_fixture(golden_dir, name):
     if name not in _SCAN_PARAM_FIXTURES:
         _SCAN_PARAM_FIXTURES[name] = parse_scan(gunzip(os.path.join(golden_dir, f"params_{name}.scan.gz")))
     return _SCAN_PARAM_FIXTURES[name]
+
+
+# ---- the banded stage 3 at class, zone and bound edges (test_band_edges_cpu.py, test_gpu_band_edges.py) --------------------------
+# The smallest query lengths at which each band class, zone count and tile count of band.hip first occurs (1 008: no band yet;
+# 6 000: the tile boundary, row 3 000, is not the zone boundary, row 3 072).
+BAND_EDGE_LENGTHS = (1008, 1009, 2017, 3073, 4081, 6000)
+# segments [0, 5 000) and [4 900, 9 900) at the default 5 000 / 100, and the short tail segment [9 800, 9 900) of 100 columns
+BAND_EDGE_DNA_LEN = 9900
+BAND_EDGE_SEGMENTS = ((0, 5000), (4900, 5000), (9800, 100))
+BAND_EDGE_ENCS = (22, 23, 26, 27, 40, 41)       # one-to-one encodings, as in the row-layout sweep: a plant reads in one unit only
+BAND_EDGE_LOW_ENCS = (26, 40, 41)                # their units hold the plants of 120 to 130, the others those of 135 to 145
+BAND_EDGE_FLANK = 40                            # N on either side of every plant
+BAND_EDGE_JOINT = 12                            # N between a candidate and the neighbour that ends just after its window
+BAND_EDGE_HOT_ENC = 22                          # the first segment's unit of this encoding holds the 160-point plant and two of 145
+# twins (name, first row of the upper copy, distance to the lower copy, rows, which copy is one match longer).  Every copy starts
+# at a row = 14 (mod 48), so that none contains a whole 24-row plant around a multiple of 48.  With a window of about 110 columns a
+# path of 130 may span 212 rows, so twins 96 rows apart still fit 384 rows, 432 apart only 768, 1 008 apart only 1 536.
+BAND_EDGE_TWINS = (("twin-96", 62, 96, 26, None), ("twin-432", 302, 432, 26, None), ("twin-1008", 398, 1008, 26, None),
+                   ("twin-1728", 446, 1728, 26, None), ("near-twin-upper", 110, 96, 26, "upper"), ("near-twin-lower", 254, 96, 26, "lower"))
+# tall plants: skipped query rows g -> rows of the two exact parts, as long as keeps 5 (a + b) - 12 - 4 g below 148 (141 ... 145)
+BAND_EDGE_TALL = {1: (16, 16), 4: (17, 17), 8: (18, 19), 12: (20, 21), 16: (22, 22)}
+BAND_EDGE_WIDE = (1, 4, 8)                      # the mirror image: g extra DNA letters between the parts
+BAND_EDGE_TALL_EDGES = (10, 11, 12, 13, 17, 18, 19, 20)    # multiples of 48 (rows 480 ... 960) that the tall and wide plants cross
+
+
+def band_layout_restated(m):
+    """(profile lanes nl, zone stride, zones, classes G) of the banded stage 3 for a query of m rows: band_profile_lanes,
+    band_zone_stride and band_classes of band.hip written out (not imported from the library), with the 72 KB LDS condition and the
+    14-bit stream-word condition."""
+    seg = (m + 15) // 16
+    nl = (16 * seg + 47) // 48
+    zs = 64
+    while (nl + zs - 1) // zs > 32:
+        zs *= 2
+    zs = min(zs, nl)
+    classes = []
+    if seg >= 8 and (seg + 191) // 192 <= 31:
+        for G in (8, 16, 32):
+            lc = min(zs + G, nl)
+            lds = (5 * lc + G) * 112 + 8 * 64 * 16
+            if 8 * G <= 3 * nl and lds <= 72 * 1024 and (5 * lc + G) * 7 < 0x4000:
+                classes.append(G)
+    return nl, zs, (nl + zs - 1) // zs, classes
+
+
+def scan_lane_of_row(m, row):
+    """Global virtual lane of k_scan that owns query row `row` (lane_rows of systolic.h, inverted)."""
+    seg, vs, _ = systolic_layout(m)
+    s, off = divmod(row, seg)
+    q, rem = divmod(seg, vs)
+    j = off // (q + 1) if off < rem * (q + 1) else rem + (off - rem * (q + 1)) // q
+    return s * vs + j
+
+
+def _band_edge_other(avoid):
+    return next(c for c in b"ACGT" if c not in avoid)
+
+
+def band_edge_inputs(m):
+    """(query, DNA record, plants) of the band-edge sweep's case of m rows.
+
+    Query: seeded random ACGT with the copies of BAND_EDGE_TWINS written in.  DNA: synth.random_dna of BAND_EDGE_DNA_LEN with exact
+    and gapped pre-images of query rows under BAND_EDGE_ENCS, those of one unit at least 250 columns apart unless they are meant as
+    neighbours.  Each lies between two runs of BAND_EDGE_FLANK N (-4 against every row in stages 2 and 3, -1 in stage 1): with a
+    query of thousands of rows the background offers a piece of 17 or more beside almost any cell, and without the N every second
+    plant grows by a gapped or mismatched extension; crossing forty N costs 160 in a window and 40 in stage 1, which sets the
+    unit's threshold.  (Between a candidate and the neighbour that must end just after its window there are BAND_EDGE_JOINT.)  Every plant
+    scores below 148 in its own window: 24 rows (120) as a rule, twins 26 or 27, the candidates beside the 160-point plant 27, the
+    long neighbour 29.
+    plants: dicts name, kind, enc, pos / n (DNA), rows [(lo, hi)] of the exact parts in path order, score and q_end (the row the
+    deciding try must end at); gap = skipped query rows (tall), ins = extra DNA letters (wide), hot = the 160-point plant."""
+    import synth
+    nl, zs, zones, classes = band_layout_restated(m)
+    seg = (m + 15) // 16
+    rng = synth._Rng(8800000 + m)
+    q = bytearray(synth.random_rna(m, 8100000 + m))
+    twins = []
+    for name, r, delta, rows, longer in BAND_EDGE_TWINS:
+        if r + delta + rows + 2 > m:
+            continue
+        q[r + delta - 1:r + delta + rows + 1] = q[r - 1:r + rows + 1]
+        if longer:       # the longer copy's extra row; the other copy must not have it
+            q[(r if longer == "lower" else r + delta) + rows] = _band_edge_other({q[(r + delta if longer == "lower" else r) + rows]})
+        twins.append((name, r, delta, rows, longer))
+    q = bytes(q)
+    dna = bytearray(synth.random_dna(BAND_EDGE_DNA_LEN, 8200000 + m))
+    plants = []
+
+    def put(name, kind, enc, pos, parts, ins=0, before=BAND_EDGE_FLANK, after=BAND_EDGE_FLANK, **extra):
+        """writes the pre-image of the rows `parts` (ranges in path order) at DNA base `pos`, between runs of `before` and `after` N"""
+        text = bytearray(q[parts[0][0]:parts[0][1]])
+        for a, b in parts[1:]:
+            # (wide) extra letters that match neither the row before nor the row after the break
+            text += bytes(_band_edge_other({q[a - 1], q[a]}) for _ in range(ins))
+            text += q[a:b]
+        tract = preimage(bytes(text), enc, rng)
+        n = len(tract)
+        assert pos >= 0 and pos + n <= len(dna), (name, pos)
+        lo, hi = max(0, pos - before), min(len(dna), pos + n + after)
+        dna[lo:hi] = b"N" * (pos - lo) + tract + b"N" * (hi - pos - n)
+        nrows = sum(b - a for a, b in parts)
+        gap = parts[1][0] - parts[0][1] if len(parts) > 1 else 0
+        score = 5 * nrows - (12 + 4 * max(gap, ins) if len(parts) > 1 else 0)
+        p = {"name": name, "kind": kind, "enc": enc, "pos": pos, "n": n, "rows": list(parts), "score": score, "q_end": parts[-1][1] - 1}
+        if ins:
+            p["ins"] = ins
+        p.update(extra)
+        plants.append(p)
+        return p
+
+    # ---- the plants that go wherever there is room: units of the five other encodings in both long segments
+    free = []
+    def room(name, kind, parts, **kw):
+        free.append((name, kind, parts, kw))
+
+    room("top", "top", [(0, 24)])
+    room("bottom", "bottom", [(m - 24, m)])
+    ks = {16: "lane-edge-mid"}
+    for G in classes:
+        ks.setdefault(nl - G, f"lane-edge-last-start-G{G}")
+        ks.setdefault(nl - G + 1, f"lane-edge-past-last-start-G{G}")
+    for k, name in sorted(ks.items()):
+        if 48 * k + 12 <= m:
+            room(name, "lane-edge", [(48 * k - 12, 48 * k + 12)])
+    if m >= 3073:
+        for lo in (3060, 3048, 3072):
+            if lo + 24 <= m:
+                room(f"zone-edge-{lo}", "zone-edge", [(lo, lo + 24)])
+        room("tile-edge", "tile-edge", [(8 * seg - 12, 8 * seg + 12)])
+    for name, r, delta, rows, longer in twins:
+        if longer == "lower":
+            room(name, "twin", [(r + delta, r + delta + rows + 1)], upper=r, delta=delta)
+        else:
+            room(name, "twin", [(r, r + rows + (1 if longer else 0))], upper=r, delta=delta)
+    edges = list(BAND_EDGE_TALL_EDGES)
+    for g, (a, b) in sorted(BAND_EDGE_TALL.items()):
+        e = 48 * edges.pop(0)
+        lo = e - a - g // 2
+        room(f"tall-{g}", "tall", [(lo, lo + a), (lo + a + g, lo + a + g + b)], gap=g, edge=e)
+        if m >= 3072 + g + b + 1:
+            lo = 3072 - a - g // 2
+            room(f"tall-{g}-zone-edge", "tall", [(lo, lo + a), (lo + a + g, lo + a + g + b)], gap=g, edge=3072)
+    for g in BAND_EDGE_WIDE:
+        a, b = BAND_EDGE_TALL[g]
+        e = 48 * edges.pop(0)
+        room(f"wide-{g}", "wide", [(e - a, e), (e, e + b)], ins=g, edge=e)
+    # Stage 1 scores N as -1, so a unit's maximum is its best plant plus up to about 15 of background from across the N, and a
+    # candidate must beat 0.8 of that: plants of 120 to 130 share units (encodings BAND_EDGE_LOW_ENCS), plants of 135 to 145 share
+    # the others.  Alternately in the two long segments, 150 bases apart, each class's encodings in turn: 300 columns or more
+    # between plants of one unit.
+    turn = {}
+    for i, (name, kind, parts, kw) in enumerate(free):
+        s, j = i % 2, i // 2
+        low = 5 * sum(b - a for a, b in parts) <= 130
+        encs = [enc for enc in BAND_EDGE_ENCS if (enc in BAND_EDGE_LOW_ENCS) == low and (s, enc) != (0, BAND_EDGE_HOT_ENC)]
+        k = turn[(s, low)] = turn.get((s, low), -1) + 1
+        put(name, kind, encs[k % len(encs)], BAND_EDGE_SEGMENTS[s][0] + 200 + 150 * j + (7 * i) % 13, parts, **kw)
+
+    # ---- column edges (even encodings: a DNA base is its unit's column)
+    put("first-columns", "column-edge", 26, 2, [(700, 724)])
+    put("overlap", "column-edge", 40, 4930, [(710, 734)])
+    put("tail-segment", "column-edge", 40, 9805, [(730, 754)])
+    put("last-columns", "column-edge", 26, 9873, [(740, 764)])
+
+    def block_pos(base, row):
+        """the first column pe >= base with (pe + lane of `row` inside its tile) % 64 == 10: k_scan's step of that lane at column pe
+        and at the 53 columns after it lie in one block of 64 steps"""
+        v = scan_lane_of_row(m, row) % 128
+        return base + (10 - (base + v)) % 64
+
+    # ---- hot neighbour: a 29-row candidate and, after the run of N that ends it, 32 rows (160) far below: they end 44 columns
+    #      after the candidate's window, in the same 64-step block of their last lane.  The same candidate rows again 600 columns on.
+    #      (Two alignments of one unit cannot share columns, so a neighbour ends at least its own length after the window.)
+    pe = block_pos(4000, 881)
+    put("hot-neighbour-near", "hot-neighbour", BAND_EDGE_HOT_ENC, pe - 28, [(600, 629)], after=BAND_EDGE_JOINT)
+    put("hot", "hot", BAND_EDGE_HOT_ENC, pe + 1 + BAND_EDGE_JOINT, [(850, 882)], before=0, hot=True)
+    put("hot-neighbour-far", "hot-neighbour", BAND_EDGE_HOT_ENC, pe + 600, [(640, 669)])
+    # ---- loose neighbour: A (27 rows) and, after the run of N that ends it, B (29 rows, 145) more than the tallest band below A:
+    #      B ends 41 columns after A's window in the same block of its last lane
+    if classes:
+        d = 48 * classes[-1] + 60
+        pe = BAND_EDGE_SEGMENTS[1][0] + block_pos(4700, 520 + d + 28)      # (in the second segment's unit)
+        put("loose-A", "loose-neighbour", 22, pe - 26, [(520, 547)], after=BAND_EDGE_JOINT)
+        put("loose-B", "loose-neighbour", 22, pe + 1 + BAND_EDGE_JOINT, [(520 + d, 520 + d + 29)], before=0)
+    assert len(dna) == BAND_EDGE_DNA_LEN
+    return q, bytes(dna), plants
+
+
+def band_edge_unit_columns(p):
+    """[(segment, last column of the plant in that segment's unit of its encoding)] for the segments that hold the whole plant"""
+    out = []
+    for s, (start, n) in enumerate(BAND_EDGE_SEGMENTS):
+        if start <= p["pos"] and p["pos"] + p["n"] <= start + n:
+            first = p["pos"] - start
+            out.append((s, n - 1 - first if p["enc"] & 1 else first + p["n"] - 1))
+    return out
+
+
+def band_edge_files(tmp_dir, m):
+    """Writes the case of m rows as two FASTA files under tmp_dir: (query path, DNA path, query, DNA, plants)."""
+    import synth
+    rna, dna, plants = band_edge_inputs(m)
+    rna_fa, dna_fa = os.path.join(str(tmp_dir), f"bandq{m}.fa"), os.path.join(str(tmp_dir), f"bandd{m}.fa")
+    synth.write_fasta(rna_fa, f"bandq{m}", rna)
+    synth.write_fasta(dna_fa, f"syn|chrB|1-{len(dna)}", dna)
+    return rna_fa, dna_fa, rna, dna, plants
+
+
+def band_edge_oracle_scan(build_dir, tmp_dir, m, detail=1, threads=8):
+    """The oracle's `scan` of the case with open filters (SCAN_OPEN): raw text."""
+    rna_fa, dna_fa, _, _, _ = band_edge_files(tmp_dir, m)
+    return oracle_cli(build_dir, "scan", rna_fa, dna_fa, "-detail", str(detail), "-threads", str(threads), *SCAN_OPEN)
