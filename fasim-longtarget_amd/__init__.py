@@ -127,6 +127,20 @@ class _VariantStats(C.Structure):
     _fields_ = [("problems", C.c_int64), ("cells", C.c_int64), ("kernel_s", C.c_double), ("total_s", C.c_double)]
 
 
+class _Interval(C.Structure):
+    _fields_ = [("rec", C.c_int32), ("reserved", C.c_int32), ("start", C.c_int64), ("end", C.c_int64)]
+
+
+class _MutScore(C.Structure):
+    _fields_ = [("value", (C.c_int32 * 4) * 4), ("enc", (C.c_int8 * 4) * 4), ("ref", C.c_int8), ("clipped", C.c_uint8 * 4),
+                ("reserved", C.c_uint8 * 3)]
+
+
+class _MutagenesisStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("intervals", "positions", "prefix_problems", "problems", "launches", "prefix_cols", "cont_cols",
+                                         "cont_cols_bound")] + [(k, C.c_double) for k in ("prefix_s", "cont_s", "total_s")]
+
+
 class _Result(C.Structure):
     _fields_ = [("recs", C.POINTER(Triplex)), ("count", C.c_int64), ("pool", C.POINTER(C.c_char)), ("pool_len", C.c_int64),
                 ("stats", ScanStats)]
@@ -208,6 +222,7 @@ EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_e
            "fasim_read_vcf", "fasim_score_variants", "fasim_variants_tsv",
            "fasim_score_variants_aligned", "fasim_variant_hit_span", "fasim_variant_hits_tsv",
            "fasim_read_vcf_sample", "fasim_haplotype_window", "fasim_haplotype_info", "fasim_score_haplotypes", "fasim_haplotypes_tsv",
+           "fasim_score_mutagenesis", "fasim_mutagenesis_tsv",
            # the reference's own ssw.h ABI (include/ssw.h)
            "ssw_init", "init_destroy", "ssw_pre_align", "ssw_align", "align_destroy", "encoded_ops"]
 
@@ -397,6 +412,11 @@ def lib():
                                          C.POINTER(_VariantStats)]
     L.fasim_haplotypes_tsv.argtypes = [C.POINTER(_Variant), C.POINTER(_Genotype), C.POINTER(_HapScore), C.c_int64, C.c_int32, C.c_char_p,
                                        C.c_char_p, C.POINTER(C.c_uint8), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.fasim_score_mutagenesis.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.POINTER(_Interval), C.c_int64, C.c_int32,
+                                          C.POINTER(Params), C.POINTER(_MutScore), C.POINTER(_MutagenesisStats)]
+    L.fasim_mutagenesis_tsv.argtypes = [C.POINTER(_Region), C.POINTER(C.c_int64), C.c_int64, C.POINTER(_MutScore), C.c_int32, C.c_char_p,
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     _lib = L
     return L
 
@@ -1848,6 +1868,35 @@ class Engine:
         a slot without a value has cigar_len 0, an unaligned one (more than 2^26 cells) -1."""
         return self.score_variants(variants, dnas, p, flank, queries, _aligned=True)
 
+    def score_mutagenesis(self, intervals, dnas, p: Params | None = None, flank: int = 300, queries=None):
+        """Every substitution at every position of intervals, from one shared pass per interval (fasim_score_mutagenesis):
+        `(values, encs, ref, clipped, offsets)`.  `intervals`: (rec, start, end) triples, 0-based half-open stretches of record `rec`
+        of `dnas` (as for score_variants()), at most 5 120 - 2 * flank positions each.  values and encs (nq, npos, 4, 4): per query,
+        position, letter of ACGT and strand class the value of the position with that letter in it -- what score_variants() defines
+        for the window [start - flank, end + flank) of the record, the same for every position of the interval -- and the smallest
+        encoding that attains it (-1: value 0).  ref (npos,): the index in ACGT of the record's own byte, -1 for any other byte.
+        clipped (nq, npos, 4): bit 0 of the letter's largest 2 * value + bit.  offsets (nint + 1,): the positions of interval k are
+        [offsets[k], offsets[k + 1]), ascending.  queries as for score_variants().  Counters of the call:
+        `self.last_mutagenesis_stats`."""
+        import numpy as np
+        p = p or default_params()
+        if queries is None:
+            if self.rna is None:
+                raise FasimError("score_mutagenesis: no queries given and no query set", E_ARG)
+            queries = [self.rna]
+        queries = [bytes(x) for x in queries]
+        blob, offs, lens, nrec = _pack_records(dnas, rec_lens=[self.resident_len()] if dnas is None else None)
+        arr, qlens, nq, _ = _pack_queries(queries)
+        ivs, offsets = _intervals_to_c(intervals)
+        nint, npos = len(intervals), int(offsets[-1])
+        out = (_MutScore * max(1, nq * npos))()
+        st = _MutagenesisStats()
+        self._check(self._L.fasim_score_mutagenesis(self._h, arr, qlens, nq, blob, offs, lens, nrec, ivs, nint, flank, C.byref(p), out, C.byref(st)))
+        self.last_mutagenesis_stats = {k: getattr(st, k) for k, _ in _MutagenesisStats._fields_}
+        flat = np.frombuffer(out, dtype=_mut_dtype())[:nq * npos].reshape(nq, npos)
+        ref = flat["ref"][0].copy() if nq else np.zeros(npos, dtype=np.int8)
+        return flat["value"].copy(), flat["enc"].copy(), ref, flat["clipped"].copy(), offsets
+
     def _records_track(self, blob, offs, lens, nrec, p, rnas, bin, records, seg_first, seg_count):
         arr, qlens, nq, nqo = _pack_queries(rnas)
         nout = nqo * max(1, nrec)
@@ -2158,6 +2207,64 @@ def variants_tsv(variants, values, encs, flags, flank: int, rna_name: str, match
     flat[:n, 0:8], flat[:n, 8:16], flat[:n, 16] = values, encs, flags
     mt = None if matched is None else (C.c_uint8 * max(1, n))(*[1 if x else 0 for x in matched])
     return _text_call(L.fasim_variants_tsv, vs, sc, n, flank, rna_name.encode(), mt)
+
+
+def _mut_dtype():
+    """fasim_mut_score as a numpy record."""
+    import numpy as np
+    return np.dtype([("value", "<i4", (4, 4)), ("enc", "i1", (4, 4)), ("ref", "i1"), ("clipped", "u1", (4,)), ("reserved", "u1", (3,))])
+
+
+def _intervals_to_c(intervals):
+    """(rec, start, end) triples as fasim_interval[] and the positions' offsets (nint + 1,)."""
+    import numpy as np
+    n = len(intervals)
+    ivs = (_Interval * max(1, n))()
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    for k, (rec, start, end) in enumerate(intervals):
+        ivs[k].rec, ivs[k].start, ivs[k].end = int(rec), int(start), int(end)
+        offsets[k + 1] = offsets[k] + max(0, int(end) - int(start))
+    return ivs, offsets
+
+
+def mutagenesis_variants(intervals, dnas) -> list:
+    """The SNVs that Engine.score_mutagenesis() scores for `intervals` ((rec, start, end) triples of the records `dnas`), as Variants
+    in its order -- per position the three letters of ACGT that differ from the record's, none where the record's byte is not one
+    of the four (ref -1) -- with line = the interval's index + 1, chrom = "rec<rec>" and id ".".  Any of them can go to
+    Engine.score_variants_aligned() for the alignment behind its value."""
+    if isinstance(dnas, (bytes, bytearray)):
+        dnas = [bytes(dnas)]
+    out = []
+    for k, (rec, start, end) in enumerate(intervals):
+        for x in range(start, end):
+            r = chr(dnas[rec][x])
+            if r not in "ACGT":
+                continue
+            out.extend(Variant(k + 1, f"rec{rec}", x, ".", r, b, rec) for b in "ACGT" if b != r)
+    return out
+
+
+def mutagenesis_tsv(regions, values, encs, ref, clipped, offsets, flank: int, rna_name: str) -> bytes:
+    """The bytes of `fasim --mutagenesis`' table for one query (fasim_mutagenesis_tsv): `regions` the intervals as Region tuples
+    (read_bed()), values and encs (npos, 4, 4), ref (npos,), clipped (npos, 4) and offsets (len(regions) + 1,) as
+    Engine.score_mutagenesis() returns them per query; an interval without positions in offsets gets no lines."""
+    import numpy as np
+    L = lib()
+    n = len(regions)
+    rg = (_Region * max(1, n))()
+    keep = []
+    for k, r in enumerate(regions):
+        keep.append((r.chrom.encode(), r.name.encode()))
+        rg[k].line, rg[k].start, rg[k].end, rg[k].chrom, rg[k].name = r.line, r.start, r.end, keep[-1][0], keep[-1][1]
+    offs = np.ascontiguousarray(offsets, dtype=np.int64).reshape(n + 1)
+    npos = int(offs[-1])
+    sc = (_MutScore * max(1, npos))()
+    flat = np.frombuffer(sc, dtype=_mut_dtype())
+    flat["value"][:npos] = np.asarray(values, dtype=np.int32).reshape(npos, 4, 4)
+    flat["enc"][:npos] = np.asarray(encs, dtype=np.int8).reshape(npos, 4, 4)
+    flat["ref"][:npos] = np.asarray(ref, dtype=np.int8).reshape(npos)
+    flat["clipped"][:npos] = np.asarray(clipped, dtype=np.uint8).reshape(npos, 4)
+    return _text_call(L.fasim_mutagenesis_tsv, rg, offs.ctypes.data_as(C.POINTER(C.c_int64)), n, sc, flank, rna_name.encode())
 
 
 def variant_hit_index(v: int, allele: int, cls: int) -> int:

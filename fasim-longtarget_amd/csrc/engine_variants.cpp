@@ -40,6 +40,8 @@ inline void blank_score(fasim_variant_score& s)
 	for (int a = 0; a < 2; a++) for (int c = 0; c < FASIM_TRACK_CLASSES; c++) s.enc[a][c] = -1;
 }
 
+}  // namespace
+
 // the refusals of a call that scores variants, before its entries are looked at
 int check_variant_call(fasim_engine* E, const char* const* rnas, const int32_t* rna_lens, int32_t nq, const char* dna, const int64_t* rec_off,
 	const int64_t* rec_len, int32_t nrec, int32_t flank, const fasim_params* pp, RecordSet& rs)
@@ -54,6 +56,8 @@ int check_variant_call(fasim_engine* E, const char* const* rnas, const int32_t* 
 	if (flank < 0 || flank > FASIM_MAX_FLANK) return fail(E, FASIM_E_ARG, "flank %d lies outside [0, %d]", flank, FASIM_MAX_FLANK);
 	return record_set_bounds(E, rs);
 }
+
+namespace {
 
 // the refusals for the entries themselves
 int check_variant_entries(fasim_engine* E, const fasim_variant* vars, int64_t nvar, const int64_t* rec_len, int32_t nrec)

@@ -94,6 +94,13 @@
 //                           <O>/<lnc>-<f1 minus 3 chars>.haplotypes.tsv (fasim_score_haplotypes); the other
 //                           tables do not change.  Status 2, nothing written: without --variants, a sample the VCF does not name,
 //                           a line without its column, no GT in FORMAT, a malformed GT
+//     --mutagenesis FILE.bed  every substitution at every position of the BED intervals, scored by the triplex potential through it
+//                           from one shared pass per interval (fasim_score_mutagenesis): per lncRNA one table,
+//                           <O>/<lnc>-<f1 minus 3 chars>.mutagenesis.tsv, and nothing else; --mutagenesis-flank F (default 300, 0 to
+//                           2048) is the context on either side of an interval, which may have 5120 - 2 F positions.  Status 2,
+//                           nothing written: a bad BED file, an interval too long, a flank out of range or without --mutagenesis,
+//                           --mutagenesis with --variants, --regions, --all-records, --accumulate-records, -F, --track, --screen,
+//                           --tfo-profile, --sites, --oligos, --potential-hist or --devices
 //     --screen              with --regions or --all-records: one table per lncRNA, <O>/<lnc>-<f1 stem>.screen.tsv, one line per
 //                           interval (BED order) or record: per strand class the peak of its potential, where it lies (0-based
 //                           genome coordinate) and the rule of the encoding that attains it (fasim_screen_tsv, DESIGN.md section
@@ -793,12 +800,130 @@ static int run_variants(const std::string& vcf_path, int flank, const std::strin
 	return 0;
 }
 
+// --mutagenesis: every substitution at every position of the BED intervals (fasim_score_mutagenesis).  The BED
+// file is read and checked before anything else; the genome is streamed record by record and an interval goes to the first record of
+// its chromosome that holds it entirely (the rules of --regions).  Per lncRNA one table, <O>/<lnc>-<f1 minus 3 chars>.mutagenesis.tsv.
+// Exit status 2: a bad BED file or an interval too long for the flank (nothing written, no device opened); 1: intervals that no
+// record contains (listed as --regions lists them; the others are written).
+static int run_mutagenesis(const std::string& bed_path, int flank, const std::string& f1, const std::string& f2, const std::string& outdir, int device,
+	bool upper, const fasim_params& p)
+{
+	fasim_region* reg = nullptr; int64_t nreg = 0;
+	if (fasim_read_bed(bed_path.c_str(), &reg, &nreg) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 2; }
+	std::unique_ptr<fasim_region, void (*)(void*)> owner(reg, fasim_free);
+	for (int64_t k = 0; k < nreg; k++) if (reg[k].end - reg[k].start + 2 * (int64_t)flank > 5120) {
+		fprintf(stderr, "fasim: BED line %lld (%s): %lld positions and two flanks of %d are more than 5120 columns: --mutagenesis takes intervals of at most %d nt with this flank\n",
+			(long long)reg[k].line, reg[k].name, (long long)(reg[k].end - reg[k].start), flank, 5120 - 2 * flank);
+		return 2;
+	}
+	std::vector<Rna> rnas;
+	DnaReader reader;
+	reader.upper = upper;
+	if (!reader.open(f1)) { fprintf(stderr, "fasim: cannot read DNA file %s\n", f1.c_str()); return 1; }
+	if (!read_rnas(f2, rnas)) { fprintf(stderr, "fasim: cannot read RNA file %s\n", f2.c_str()); return 1; }
+	for (const Rna& r : rnas) if (r.seq.empty() || r.seq.size() > (size_t)FASIM_MAX_QUERY) {
+		fprintf(stderr, "fasim: RNA record '%s' in %s has %zu nt: a query has 1 to %d nt\n", r.name.c_str(), f2.c_str(), r.seq.size(), FASIM_MAX_QUERY);
+		return 1;
+	}
+	std::cout << "Searching triplexes using Fasim" << std::endl;
+	for (const Rna& r : rnas) std::cout << r.name << std::endl;
+	const int nq = (int)rnas.size();
+	std::vector<const char*> qp((size_t)nq); std::vector<int32_t> ql((size_t)nq);
+	for (int q = 0; q < nq; q++) { qp[(size_t)q] = rnas[(size_t)q].seq.data(); ql[(size_t)q] = (int32_t)rnas[(size_t)q].seq.size(); }
+	// per lncRNA and interval the scores of its positions; empty: not met
+	std::vector<std::vector<std::vector<fasim_mut_score>>> scores((size_t)nq, std::vector<std::vector<fasim_mut_score>>((size_t)nreg));
+	std::map<std::string, std::multimap<int64_t, int64_t>> todo;
+	std::set<std::string> chroms_seen;
+	std::vector<char> held_start((size_t)nreg, 0);
+	for (int64_t k = 0; k < nreg; k++) todo[reg[k].chrom].emplace(reg[k].start, k);
+	fasim_engine* eng = nullptr;
+	DnaRecord rec;
+	size_t nrec = 0;
+	while (reader.next(rec)) {
+		std::string chrom = rec.chr; int64_t rs = (int64_t)rec.start - 1;
+		const size_t w0 = rec.header.find_first_not_of("> \t\r");
+		const std::string word = w0 == std::string::npos ? std::string() : rec.header.substr(w0, rec.header.find_first_of(" \t\r", w0) - w0);
+		if (word.find('|') == std::string::npos) { chrom = word; rs = 0; }
+		nrec++;
+		chroms_seen.insert(chrom);
+		auto it = todo.find(chrom);
+		if (it == todo.end()) continue;
+		const int64_t re = rs + (int64_t)rec.seq.size();
+		std::vector<int64_t> mine;
+		for (auto j = it->second.lower_bound(rs); j != it->second.end() && j->first < re; ) {
+			if (reg[j->second].end <= re) { mine.push_back(j->second); j = it->second.erase(j); }
+			else { held_start[(size_t)j->second] = 1; ++j; }
+		}
+		if (mine.empty()) continue;
+		std::sort(mine.begin(), mine.end());
+		std::vector<fasim_interval> loc(mine.size());
+		int64_t npos = 0;
+		for (size_t k = 0; k < mine.size(); k++) {
+			const fasim_region& g = reg[mine[k]];
+			loc[k].rec = 0; loc[k].reserved = 0; loc[k].start = g.start - rs; loc[k].end = g.end - rs;
+			npos += g.end - g.start;
+		}
+		if (!eng && fasim_engine_create(device, &eng) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
+		const int64_t off0 = 0, len0 = (int64_t)rec.seq.size();
+		std::vector<fasim_mut_score> got((size_t)nq * (size_t)npos);
+		if (fasim_score_mutagenesis(eng, qp.data(), ql.data(), nq, rec.seq.data(), &off0, &len0, 1, loc.data(), (int64_t)loc.size(), flank, &p, got.data(), nullptr) != FASIM_OK) {
+			fprintf(stderr, "fasim: %s\n", fasim_last_error(eng));
+			fasim_engine_destroy(eng);
+			return 1;
+		}
+		for (int q = 0; q < nq; q++) {
+			size_t at = (size_t)q * (size_t)npos;
+			for (size_t k = 0; k < mine.size(); k++) {
+				const size_t len = (size_t)(reg[mine[k]].end - reg[mine[k]].start);
+				scores[(size_t)q][(size_t)mine[k]].assign(got.begin() + (ptrdiff_t)at, got.begin() + (ptrdiff_t)(at + len));
+				at += len;
+			}
+		}
+	}
+	if (eng) fasim_engine_destroy(eng);
+	if (nrec == 0) { fprintf(stderr, "fasim: no record in DNA file %s\n", f1.c_str()); return 1; }
+	const std::string base = f1.substr(0, f1.size() >= 3 ? f1.size() - 3 : 0);
+	int bad = 0;
+	for (int q = 0; q < nq; q++) {
+		std::vector<int64_t> offsets((size_t)nreg + 1, 0);
+		std::vector<fasim_mut_score> all;
+		for (int64_t k = 0; k < nreg; k++) {
+			all.insert(all.end(), scores[(size_t)q][(size_t)k].begin(), scores[(size_t)q][(size_t)k].end());
+			offsets[(size_t)k + 1] = (int64_t)all.size();
+		}
+		char* text = nullptr; int64_t len = 0;
+		if (fasim_mutagenesis_tsv(reg, offsets.data(), nreg, all.data(), flank, rnas[(size_t)q].name.c_str(), &text, &len) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
+		bad |= write_file(outdir + "/" + rnas[(size_t)q].name + "-" + base + ".mutagenesis.tsv", text, len);
+		fasim_free(text);
+	}
+	if (bad) return 1;
+	std::vector<std::pair<int64_t, std::string>> lost;
+	for (const auto& c : todo) for (const auto& j : c.second) {
+		const fasim_region& g = reg[j.second];
+		const char* why = held_start[(size_t)j.second] ? "runs past the end of the DNA record that holds its start"
+			: chroms_seen.count(g.chrom) ? "no DNA record of its chromosome holds it" : "no DNA record of its chromosome";
+		char buf[512];
+		snprintf(buf, sizeof buf, "fasim: BED line %lld (%s) %s:%lld-%lld: %s\n", (long long)g.line, g.name, g.chrom, (long long)g.start, (long long)g.end, why);
+		lost.emplace_back(j.second, buf);
+	}
+	if (!lost.empty()) {
+		std::sort(lost.begin(), lost.end());      // in BED order
+		for (size_t k = 0; k < lost.size() && k < 20; k++) fputs(lost[k].second.c_str(), stderr);
+		if (lost.size() > 20) fprintf(stderr, "fasim: ... and %zu more\n", lost.size() - 20);
+		fprintf(stderr, "fasim: %zu of %lld BED intervals lie in no DNA record of %s: they have no lines in the table\n", lost.size(), (long long)nreg, f1.c_str());
+		return 1;
+	}
+	std::cout << "finished normally" << std::endl;
+	return 0;
+}
+
 int main(int argc, char* const* argv)
 {
 	fasim_params p; fasim_params_default(&p);
 	std::string f1 = "./", f2 = "./", outdir = "./", bed_path, vcf_path, sample;
 	bool sample_given = false;
 	bool devices_given = false, flank_given = false, variant_hits = false; int variant_flank = 300;
+	std::string mut_path; bool mut_flank_given = false; int mut_flank = 300;
 	std::vector<int> devices(1, 0);
 	bool stats = false, all_records = false, accumulate = false, upper = false, track = false, screen = false, screen_only = false;
 	bool sites = false, sites_gap_given = false, hist_arg_given = false, hist_arg_bad = false, hist_shuffle_bad = false;
@@ -820,7 +945,8 @@ int main(int argc, char* const* argv)
 		{ "hist-fdr", required_argument, NULL, 1024 }, { "potential-hist-only", no_argument, NULL, 1025 },
 		{ "hist-sites", no_argument, NULL, 1030 }, { "hist-shuffle", required_argument, NULL, 1031 },
 		{ "variants", required_argument, NULL, 1027 }, { "variant-flank", required_argument, NULL, 1028 },
-		{ "variant-hits", no_argument, NULL, 1029 }, { "sample", required_argument, NULL, 1034 }, { 0, 0, 0, 0 } };
+		{ "variant-hits", no_argument, NULL, 1029 }, { "sample", required_argument, NULL, 1034 },
+		{ "mutagenesis", required_argument, NULL, 1035 }, { "mutagenesis-flank", required_argument, NULL, 1036 }, { 0, 0, 0, 0 } };
 	int opt;
 	while ((opt = getopt_long_only(argc, argv, optstring, lo, NULL)) != -1) {
 		switch (opt) {
@@ -850,6 +976,8 @@ int main(int argc, char* const* argv)
 		case 1028: flank_given = true; variant_flank = strict_int(optarg, -1); break;
 		case 1029: variant_hits = true; break;
 		case 1034: sample_given = true; sample = optarg; break;
+		case 1035: mut_path = optarg; break;
+		case 1036: mut_flank_given = true; mut_flank = strict_int(optarg, -1); break;
 		case 1004: devices_given = true; devices = parse_devices(optarg); if (devices.empty()) { fprintf(stderr, "fasim: bad --devices list\n"); return 2; } break;
 		case 1005: accumulate = true; break;
 		case 1006: upper = true; break;
@@ -877,7 +1005,7 @@ int main(int argc, char* const* argv)
 		case 1025: trk.hist_only = true; break;
 		case 1030: hist_arg_given = true; trk.hist_sites = true; break;
 		case 1031: hist_arg_given = true; if (!strcmp(optarg, "di")) trk.hist_dinuc = true; else if (strcmp(optarg, "mono")) hist_shuffle_bad = true; break;
-		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only] [--sites-align] [--oligos [--oligo-hits]]] [--oligos [--oligo-profile] [--oligo-screen]] [--potential-hist [--hist-controls K] [--hist-seed S] [--hist-fdr Q] [--potential-hist-only] [--hist-sites] [--hist-shuffle mono|di]] [--variants FILE.vcf [--variant-flank F] [--variant-hits] [--sample NAME]]\n"); return 2;
+		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only] [--sites-align] [--oligos [--oligo-hits]]] [--oligos [--oligo-profile] [--oligo-screen]] [--potential-hist [--hist-controls K] [--hist-seed S] [--hist-fdr Q] [--potential-hist-only] [--hist-sites] [--hist-shuffle mono|di]] [--variants FILE.vcf [--variant-flank F] [--variant-hits] [--sample NAME]] [--mutagenesis FILE.bed [--mutagenesis-flank F]]\n"); return 2;
 		}
 	}
 	if (all_records && accumulate) { fprintf(stderr, "fasim: --all-records and --accumulate-records exclude each other\n"); return 2; }
@@ -919,6 +1047,14 @@ int main(int argc, char* const* argv)
 		fprintf(stderr, "fasim: --variants is not available with --regions, --all-records, --accumulate-records, -F, --track, --screen, --tfo-profile, --sites, --oligos, --potential-hist or --devices\n");
 		return 2;
 	}
+	const bool mutagenesis = !mut_path.empty();
+	if (mut_flank_given && !mutagenesis) { fprintf(stderr, "fasim: --mutagenesis-flank needs --mutagenesis FILE.bed\n"); return 2; }
+	if (mutagenesis && (mut_flank < 0 || mut_flank > FASIM_MAX_FLANK)) { fprintf(stderr, "fasim: --mutagenesis-flank needs an integer in [0, %d]\n", FASIM_MAX_FLANK); return 2; }
+	if (mutagenesis && (variants || regions || all_records || accumulate || p.classicSim || track || screen || trk.tfo || sites || trk.oligos || trk.hist || devices_given)) {
+		fprintf(stderr, "fasim: --mutagenesis is not available with --variants, --regions, --all-records, --accumulate-records, -F, --track, --screen, --tfo-profile, --sites, --oligos, --potential-hist or --devices\n");
+		return 2;
+	}
+	if (mutagenesis) return run_mutagenesis(mut_path, mut_flank, f1, f2, outdir, devices[0], upper, p);
 	if (variants) return run_variants(vcf_path, variant_flank, f1, f2, outdir, devices[0], upper, p, variant_hits, sample);
 	if (trk.oligos) trk.sites_only = true;      // a panel has no triplex records: the sites files and the panel table are all it writes
 	if (trk.oligos && trk.hist) trk.hist_only = true;      // (or the oligos' histograms)

@@ -291,6 +291,33 @@ struct HapEncodeLaunch {
 };
 hipError_t launch_hap_encode(const HapEncodeLaunch& L, hipStream_t st);
 
+// ---- mutagenesis.hip: every substitution at every position of an interval from one shared pass -------------
+// A unit is one context (interval and flanks) under one encoding with a range of its columns: a TouchProb whose n codes k_hap_encode
+// wrote, whose [v0, v1) are the columns of the range's positions (mirrored for an odd encoding, as the codes are) and whose edge bits
+// are section 19's.  first[u] counts the columns of the units before u: column v0 + s of unit u has snapshot first[u] + s
+// ([2][touch_state_rows(m)] 16-bit words: H of the column before it, then E, in ColState's order) and, for letter b of ACGT, problem
+// 4 * (first[u] + s) + b.  k_mut_prefix (one workgroup per unit) writes the snapshots, k_mut_touch (one per problem) out[problem] =
+// 2 * value + clip bit and cols[problem] = the columns it ran.
+struct MutLaunch {
+	const uint8_t* tcodes; const uint8_t* qcodes; int32_t m;
+	const TouchProb* units; const int32_t* first /*[nunit + 1]*/; int32_t nunit, ncol /* = first[nunit] */;
+	const uint8_t* enc_lut /*[48][256] -> code*/;
+	uint16_t* rows;               // [max(nunit, problems)][3][touch_state_rows(m)] where m > TOUCH_LDS_ROWS, else NULL
+	uint16_t* snap; uint32_t* out; uint32_t* cols;
+};
+// A group is the nenc units [unit0, unit0 + nenc) of one context and one range of npos positions, in the order of enc[]; the group's
+// position j is column v0 + j of an even and v1 - 1 - j of an odd encoding.  out[(pos0 + j)][20]: per (letter, class) k_touch_reduce's
+// word, then per letter the columns its problems ran.
+struct MutGroup { int32_t unit0, pos0, npos, pad; };
+struct MutReduceLaunch {
+	const uint32_t* touch; const uint32_t* cols; const int32_t* first; const MutGroup* groups; int32_t ngroup, npos, nenc; uint8_t enc[48];
+	uint32_t* out;
+};
+constexpr int MUT_WORDS = 20;
+hipError_t launch_mut_prefix(const MutLaunch& L, hipStream_t st);
+hipError_t launch_mut_touch(const MutLaunch& L, hipStream_t st);      // 4 * ncol problems
+hipError_t launch_mut_reduce(const MutReduceLaunch& L, hipStream_t st);
+
 // ---- rowfold.hip: per-base profile of the lncRNA folded from the row maxima of a batch -------------------------
 // Group g = segments [gfirst[g], gfirst[g + 1]) of the batch (the run of segments of one record, or the whole batch); the result is
 // out[g][4 classes][rows_total] = maximum over the group's units of the class, taint bit dropped.

@@ -871,6 +871,50 @@ int fasim_score_haplotypes(fasim_engine* e, const char* const* rnas, const int32
  * An entry with matched[k] == 0 or alt_len < 0 has NA in every column after gt.  Free with fasim_free. */
 int fasim_haplotypes_tsv(const fasim_variant* vars, const fasim_genotype* gts, const fasim_hap_score* scores, int64_t nvar, int32_t flank,
                          const char* rna_name, const char* sample, const uint8_t* matched /* [nvar] or NULL */, char** text, int64_t* text_len);
+/* ---- every SNV of an interval from one shared pass (csrc/mutagenesis.hip) ------------------------------------- */
+/* Which bases of an interval matter?  An interval is [start, end) of record `rec`, 0-based, at least one base.  With flank F its
+ * context is C = record[lo, hi), lo = max(0, start - F), hi = min(record length, end + F).  For a position x of the interval and a
+ * letter b of ACGT, C(x, b) is C with byte x - lo replaced by the upper-case byte b, and the result of (x, b) under an encoding is
+ * what fasim_score_variants defines for the window C(x, b) with the mark [x - lo, x - lo + 1) and the edges (lo > 0, hi < record
+ * length): scoring, touching matrix, 2 * value + clip bit and the reduction over classes and encodings are section 19's word for
+ * word.  All positions of an interval share the one context, where fasim_score_variants gives every variant a flank of its own:
+ * the window [start - F, end + F) is never smaller than the SNV's own [x - F, x + 1 + F), so a value here is never below
+ * fasim_score_variants' value for the same SNV and flank.
+ * value[b][c], enc[b][c]: letter b, strand class c (enc -1: value 0).  ref: the index in ACGT of the record's byte at x if it is
+ * one of those four upper-case bytes, else -1 (all four letters are still scored).  clipped[b]: bit 0 of the largest 2 * value + bit
+ * of letter b over all classes and encodings; the clip flag of the SNV ref -> b is the bit of the larger of the two letters' words
+ * 2 * max value + clipped (ties go to the bit). */
+typedef struct fasim_interval { int32_t rec, reserved; int64_t start, end; } fasim_interval;
+typedef struct fasim_mut_score {
+	int32_t value[4][FASIM_TRACK_CLASSES];
+	int8_t enc[4][FASIM_TRACK_CLASSES];
+	int8_t ref; uint8_t clipped[4]; uint8_t reserved[3];
+} fasim_mut_score;
+/* prefix_problems: (context, encoding, position range) runs of the shared pass and the columns they ran; problems: (position,
+ * letter, encoding) continuations and the columns they ran until their dead column; cont_cols_bound: what cont_cols would be with no
+ * early stop, the sum of n - c over the problems; prefix_s, cont_s: HIP-event seconds of k_mut_prefix and k_mut_touch. */
+typedef struct fasim_mutagenesis_stats {
+	int64_t intervals, positions, prefix_problems, problems, launches, prefix_cols, cont_cols, cont_cols_bound;
+	double prefix_s, cont_s, total_s;
+} fasim_mutagenesis_stats;
+/* Scores every position of nint intervals for nq >= 1 queries (1 to FASIM_MAX_QUERY nt): out[q * npos + k], npos the sum of the
+ * intervals' lengths, the positions in interval order and ascending within an interval.  Records, engine state and stream as
+ * fasim_score_variants.  The result of a position depends on the record, the interval, the flank, the query and the parameters only
+ * (not on the other intervals, their order or the launches).  Refused before any GPU work, the engine stays usable: an interval
+ * outside its record or with end <= start, (end - start) + 2 * flank > 5120, a flank outside [0, FASIM_MAX_FLANK], the record
+ * refusals of fasim_score_variants (FASIM_E_ARG); a query above FASIM_MAX_QUERY, classicSim (FASIM_E_UNSUPPORTED). */
+int fasim_score_mutagenesis(fasim_engine* e, const char* const* rnas, const int32_t* rna_lens, int32_t nq,
+                            const char* dna, const int64_t* rec_off, const int64_t* rec_len, int32_t nrec,
+                            const fasim_interval* intervals, int64_t nint, int32_t flank, const fasim_params* p,
+                            fasim_mut_score* out /* [nq * npos] */, fasim_mutagenesis_stats* stats /* may be NULL */);
+/* The table `fasim --mutagenesis` writes for one query: `# fasim mutagenesis lncRNA=<rna_name> flank=<F>`, the column names of
+ * fasim_variants_tsv, then one line per (position, letter other than the reference letter, in ACGT order), positions ascending,
+ * intervals in the order given: line = regions[k].line, chrom, pos 1-based, id = regions[k].name, ref, alt, per class
+ * <Class>_ref <Class>_alt, max_ref max_alt delta rule_ref rule_alt clipped as fasim_variants_tsv prints them.  scores: the positions
+ * of interval k are scores[offsets[k] .. offsets[k + 1]) (an interval that was not scored has none); a position with ref == -1 gets
+ * no lines.  Free with fasim_free. */
+int fasim_mutagenesis_tsv(const fasim_region* regions, const int64_t* offsets /* [n + 1] */, int64_t n, const fasim_mut_score* scores,
+                          int32_t flank, const char* rna_name, char** text, int64_t* text_len);
 /* ingest helper: upper-cases a DNA record in place (soft-masked genomes such as UCSC hg38 carry repeats in lower
  * case; the reference does not upper-case and treats such letters as unknown, rules.h:286-312, 82-83). */
 void fasim_upper_case(char* seq, int64_t n);
