@@ -96,6 +96,8 @@ MAX_OLIGO = 112
 # FASIM_MAX_ALLELE / FASIM_MAX_FLANK (include/fasim_hip.h): longest allele and widest flank of a scored variant (Engine.score_variants)
 MAX_ALLELE = 1024
 MAX_FLANK = 2048
+# FASIM_MAX_DELETION_LENGTHS (include/fasim_hip.h): deletion lengths of one Engine.score_deletions() call
+MAX_DELETION_LENGTHS = 16
 
 
 class _Region(C.Structure):
@@ -139,6 +141,16 @@ class _MutScore(C.Structure):
 class _MutagenesisStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("intervals", "positions", "prefix_problems", "problems", "launches", "prefix_cols", "cont_cols",
                                          "cont_cols_bound")] + [(k, C.c_double) for k in ("prefix_s", "cont_s", "total_s")]
+
+
+class _DelScore(C.Structure):
+    _fields_ = [("value", (C.c_int32 * 4) * 2), ("enc", (C.c_int8 * 4) * 2), ("clipped", C.c_uint8 * 2), ("valid", C.c_uint8),
+                ("clean", C.c_uint8), ("reserved", C.c_uint8 * 4)]
+
+
+class _DeletionStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("intervals", "positions", "deletions", "launches", "prefix_problems", "prefix_cols", "own_problems",
+                                         "alt_problems", "cont_cols", "cont_cols_bound")] + [(k, C.c_double) for k in ("prefix_s", "cont_s", "total_s")]
 
 
 class _Result(C.Structure):
@@ -222,7 +234,7 @@ EXPORTS = ["fasim_params_default", "fasim_engine_create", "fasim_engine_create_e
            "fasim_read_vcf", "fasim_score_variants", "fasim_variants_tsv",
            "fasim_score_variants_aligned", "fasim_variant_hit_span", "fasim_variant_hits_tsv",
            "fasim_read_vcf_sample", "fasim_haplotype_window", "fasim_haplotype_info", "fasim_score_haplotypes", "fasim_haplotypes_tsv",
-           "fasim_score_mutagenesis", "fasim_mutagenesis_tsv",
+           "fasim_score_mutagenesis", "fasim_mutagenesis_tsv", "fasim_score_deletions", "fasim_deletions_tsv",
            # the reference's own ssw.h ABI (include/ssw.h)
            "ssw_init", "init_destroy", "ssw_pre_align", "ssw_align", "align_destroy", "encoded_ops"]
 
@@ -417,6 +429,11 @@ def lib():
                                           C.POINTER(Params), C.POINTER(_MutScore), C.POINTER(_MutagenesisStats)]
     L.fasim_mutagenesis_tsv.argtypes = [C.POINTER(_Region), C.POINTER(C.c_int64), C.c_int64, C.POINTER(_MutScore), C.c_int32, C.c_char_p,
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.fasim_score_deletions.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_char_p,
+                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.POINTER(_Interval), C.c_int64, C.c_int32,
+                                        C.POINTER(C.c_int32), C.c_int32, C.POINTER(Params), C.POINTER(_DelScore), C.POINTER(_DeletionStats)]
+    L.fasim_deletions_tsv.argtypes = [C.POINTER(_Region), C.POINTER(C.c_int64), C.c_int64, C.POINTER(_DelScore), C.POINTER(C.c_char_p),
+                                      C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     _lib = L
     return L
 
@@ -1897,6 +1914,39 @@ class Engine:
         ref = flat["ref"][0].copy() if nq else np.zeros(npos, dtype=np.int8)
         return flat["value"].copy(), flat["enc"].copy(), ref, flat["clipped"].copy(), offsets
 
+    def score_deletions(self, intervals, dnas, p: Params | None = None, flank: int = 300, lengths=(1,), queries=None):
+        """Every deletion inside intervals, from the shared pass of score_mutagenesis() (fasim_score_deletions): `(values, encs,
+        clipped, valid, clean, offsets)`.  intervals, dnas, flank, queries and offsets as for score_mutagenesis(); `lengths`: 1 to
+        MAX_DELETION_LENGTHS strictly ascending integers in [1, MAX_ALLELE - 1].  The deletion (x, d) keeps base x, the anchor of its
+        VCF line, and takes out the d bases behind it; it exists where x + d < end.  values and encs (nq, npos, nlen, 2, 4): per
+        query, position, length, allele (0 REF, 1 ALT) and strand class what score_variants() defines for pos = x, REF =
+        record[x:x + d + 1], ALT = record[x] in the window [start - flank, end + flank), and the smallest encoding that attains it
+        (-1: value 0).  clipped (nq, npos, nlen, 2): bit 0 of the allele's largest 2 * value + bit.  valid (npos, nlen): the pair is
+        a deletion (else zeros).  clean (npos, nlen): it is one and its d + 1 bytes are upper-case ACGT.  Counters of the call:
+        `self.last_deletion_stats`."""
+        import numpy as np
+        p = p or default_params()
+        if queries is None:
+            if self.rna is None:
+                raise FasimError("score_deletions: no queries given and no query set", E_ARG)
+            queries = [self.rna]
+        queries = [bytes(x) for x in queries]
+        blob, offs, lens, nrec = _pack_records(dnas, rec_lens=[self.resident_len()] if dnas is None else None)
+        arr, qlens, nq, _ = _pack_queries(queries)
+        ivs, offsets = _intervals_to_c(intervals)
+        nint, npos = len(intervals), int(offsets[-1])
+        lengths = [int(d) for d in lengths]
+        nlen = len(lengths)
+        ln = (C.c_int32 * max(1, nlen))(*lengths)
+        out = (_DelScore * max(1, nq * npos * nlen))()
+        st = _DeletionStats()
+        self._check(self._L.fasim_score_deletions(self._h, arr, qlens, nq, blob, offs, lens, nrec, ivs, nint, flank, ln, nlen, C.byref(p), out, C.byref(st)))
+        self.last_deletion_stats = {k: getattr(st, k) for k, _ in _DeletionStats._fields_}
+        flat = np.frombuffer(out, dtype=_del_dtype())[:nq * npos * nlen].reshape(nq, npos, nlen)
+        valid = flat["valid"][0].copy() if nq else np.zeros((npos, nlen), dtype=np.uint8)
+        clean = flat["clean"][0].copy() if nq else np.zeros((npos, nlen), dtype=np.uint8)
+        return flat["value"].copy(), flat["enc"].copy(), flat["clipped"].copy(), valid, clean, offsets
+
     def _records_track(self, blob, offs, lens, nrec, p, rnas, bin, records, seg_first, seg_count):
         arr, qlens, nq, nqo = _pack_queries(rnas)
         nout = nqo * max(1, nrec)
@@ -2265,6 +2315,59 @@ def mutagenesis_tsv(regions, values, encs, ref, clipped, offsets, flank: int, rn
     flat["ref"][:npos] = np.asarray(ref, dtype=np.int8).reshape(npos)
     flat["clipped"][:npos] = np.asarray(clipped, dtype=np.uint8).reshape(npos, 4)
     return _text_call(L.fasim_mutagenesis_tsv, rg, offs.ctypes.data_as(C.POINTER(C.c_int64)), n, sc, flank, rna_name.encode())
+
+
+def _del_dtype():
+    """fasim_del_score as a numpy record."""
+    import numpy as np
+    return np.dtype([("value", "<i4", (2, 4)), ("enc", "i1", (2, 4)), ("clipped", "u1", (2,)), ("valid", "u1"), ("clean", "u1"),
+                     ("reserved", "u1", (4,))])
+
+
+def deletion_variants(intervals, dnas, lengths) -> list:
+    """The clean deletions that Engine.score_deletions() scores for `intervals` and `lengths`, as Variants in the order of its table
+    -- intervals, positions ascending, lengths in their order; REF the d + 1 letters from the anchor on, ALT the anchor -- with line =
+    the interval's index + 1, chrom = "rec<rec>" and id ".".  Any of them can go to Engine.score_variants_aligned() for the
+    alignment behind its value."""
+    if isinstance(dnas, (bytes, bytearray)):
+        dnas = [bytes(dnas)]
+    out = []
+    for k, (rec, start, end) in enumerate(intervals):
+        for x in range(start, end):
+            for d in lengths:
+                ref = bytes(dnas[rec][x:x + d + 1]).decode("latin-1")
+                if x + d < end and all(c in "ACGT" for c in ref):
+                    out.append(Variant(k + 1, f"rec{rec}", x, ".", ref, ref[0], rec))
+    return out
+
+
+def deletions_tsv(regions, values, encs, clipped, valid, clean, offsets, seqs, lengths, flank: int, rna_name: str) -> bytes:
+    """The bytes of `fasim --mutagenesis --deletions`' table for one query (fasim_deletions_tsv): `regions` the intervals as Region
+    tuples (read_bed()); values and encs (npos, nlen, 2, 4), clipped (npos, nlen, 2), valid and clean (npos, nlen) and offsets
+    (len(regions) + 1,) as Engine.score_deletions() returns them per query; seqs[k] the end - start letters of interval k (None for
+    an interval without positions in offsets, which gets no lines); lengths as in the call."""
+    import numpy as np
+    L = lib()
+    n = len(regions)
+    rg = (_Region * max(1, n))()
+    keep = []
+    for k, r in enumerate(regions):
+        keep.append((r.chrom.encode(), r.name.encode()))
+        rg[k].line, rg[k].start, rg[k].end, rg[k].chrom, rg[k].name = r.line, r.start, r.end, keep[-1][0], keep[-1][1]
+    sq = (C.c_char_p * max(1, n))(*[None if x is None else bytes(x) for x in seqs])
+    lengths = [int(d) for d in lengths]
+    nlen = len(lengths)
+    ln = (C.c_int32 * max(1, nlen))(*lengths)
+    offs = np.ascontiguousarray(offsets, dtype=np.int64).reshape(n + 1)
+    npair = int(offs[-1]) * nlen
+    sc = (_DelScore * max(1, npair))()
+    flat = np.frombuffer(sc, dtype=_del_dtype())
+    flat["value"][:npair] = np.asarray(values, dtype=np.int32).reshape(npair, 2, 4)
+    flat["enc"][:npair] = np.asarray(encs, dtype=np.int8).reshape(npair, 2, 4)
+    flat["clipped"][:npair] = np.asarray(clipped, dtype=np.uint8).reshape(npair, 2)
+    flat["valid"][:npair] = np.asarray(valid, dtype=np.uint8).reshape(npair)
+    flat["clean"][:npair] = np.asarray(clean, dtype=np.uint8).reshape(npair)
+    return _text_call(L.fasim_deletions_tsv, rg, offs.ctypes.data_as(C.POINTER(C.c_int64)), n, sc, sq, ln, nlen, flank, rna_name.encode())
 
 
 def variant_hit_index(v: int, allele: int, cls: int) -> int:

@@ -338,7 +338,7 @@ void fasim_engine_destroy(fasim_engine* e)
 		&e->bprev, &e->lane_ub, &e->fzones, &e->fubslot, &e->bdec, &e->btab, &e->swin, &e->unit_ovf, &e->track, &e->track_phase, &e->track_sat, &e->track_peaks, &e->sites_counts, &e->sites_offsets, &e->sites_runs, &e->sites_sat, &e->sa_q, &e->sa_tcodes, &e->sa_probs, &e->sa_ends, &e->sa_rows, &e->sa_items, &e->sa_dirs, &e->sa_cigar, &e->sa_ciglen,
 		&e->rowmax16, &e->row_out, &e->row_gfirst, &e->row_sat, &e->oligo_q, &e->rowpart16, &e->hist, &e->hist_zone, &e->hist_zones, &e->hist_sat, &e->hist_pairs, &e->hist_border,
 		&e->vr_q, &e->vr_dna, &e->vr_alt, &e->vr_probs, &e->vr_tcodes, &e->vr_rows, &e->vr_touch, &e->vr_out,
-		&e->vr_items, &e->vr_dirs, &e->vr_cigar, &e->vr_paths, &e->vr_hwins, &e->vr_pieces, &e->vr_ends, &e->mu_first, &e->mu_groups, &e->mu_snap, &e->mu_cols, &e->fmask, &e->flist, &e->fmarks, &e->seg_clean };
+		&e->vr_items, &e->vr_dirs, &e->vr_cigar, &e->vr_paths, &e->vr_hwins, &e->vr_pieces, &e->vr_ends, &e->mu_first, &e->mu_groups, &e->mu_snap, &e->mu_cols, &e->mu_pm, &e->fmask, &e->flist, &e->fmarks, &e->seg_clean };
 	for (auto& t : e->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
 	for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
 	for (DevBuf* b : bufs) b->release();

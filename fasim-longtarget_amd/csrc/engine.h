@@ -146,7 +146,7 @@ struct fasim_engine {
 	DevBuf vr_q, vr_dna, vr_alt, vr_probs, vr_tcodes, vr_rows, vr_touch, vr_out;   // the chunks of fasim_score_variants and fasim_score_haplotypes only: query codes, streamed window letters, ALT letters, problems, target codes, row state of long queries, k_touch's words, k_touch_reduce's words
 	DevBuf vr_items, vr_dirs, vr_cigar, vr_paths;   // fasim_score_variants_aligned only: k_touch_path's items, direction bytes, CIGAR words and results
 	DevBuf vr_hwins, vr_pieces, vr_ends;           // the same chunks: the windows, pieces and piece ends of k_hap_encode
-	DevBuf mu_first, mu_groups, mu_snap, mu_cols;   // fasim_score_mutagenesis only (its launches use vr_q, vr_dna, vr_alt, vr_probs, vr_tcodes, vr_rows, vr_touch, vr_out, vr_hwins, vr_pieces and vr_ends as the chunks above do): the units' column counts, the groups, the snapshots, the columns run
+	DevBuf mu_first, mu_groups, mu_snap, mu_cols, mu_pm;   // fasim_score_mutagenesis and fasim_score_deletions only: the units' column counts, the groups, the snapshots, the columns run and, for deletions, the column maxima.  Their launches use vr_q, vr_dna, vr_alt, vr_probs, vr_tcodes, vr_rows, vr_touch, vr_out, vr_hwins, vr_pieces and vr_ends as the chunks above do.
 	int opt_sim_lds = -1;                        // option "sim_lds": -F re-sweeps always on the L2 variant (0) / the LDS variant where the state fits (1); -1 = by the units in flight
 	int opt_site_short = -1;                     // option "site_short": 1 = the hits of oligo sites end on k_site_ends_short (default), 0 = on k_site_ends (-1 = default / environment FASIM_SITE_SHORT)
 	int opt_site_chunk = 0;                      // option "site_chunk": problems per chunk of the hits phase where lower than the phase's own limit (0 = that limit)

@@ -101,6 +101,12 @@
 //                           nothing written: a bad BED file, an interval too long, a flank out of range or without --mutagenesis,
 //                           --mutagenesis with --variants, --regions, --all-records, --accumulate-records, -F, --track, --screen,
 //                           --tfo-profile, --sites, --oligos, --potential-hist or --devices
+//     --deletions LIST      with --mutagenesis: every deletion of d bases, d of LIST (1 to 16 strictly ascending integers in
+//                           1 ... 1023, comma-separated), behind every position of the intervals and inside them, from a shared
+//                           pass of its own (fasim_score_deletions): one more table per lncRNA, <O>/<lnc>-<f1 minus 3
+//                           chars>.deletions.tsv; the mutagenesis table does not change.  --deletions-only writes only the new table
+//                           and runs no SNV problems.  Status 2, nothing written: either without --mutagenesis, --deletions-only
+//                           without --deletions, a list that is empty, not ascending, not integers, out of range or too long
 //     --screen              with --regions or --all-records: one table per lncRNA, <O>/<lnc>-<f1 stem>.screen.tsv, one line per
 //                           interval (BED order) or record: per strand class the peak of its potential, where it lies (0-based
 //                           genome coordinate) and the rule of the encoding that attains it (fasim_screen_tsv, DESIGN.md section
@@ -806,8 +812,9 @@ static int run_variants(const std::string& vcf_path, int flank, const std::strin
 // Exit status 2: a bad BED file or an interval too long for the flank (nothing written, no device opened); 1: intervals that no
 // record contains (listed as --regions lists them; the others are written).
 static int run_mutagenesis(const std::string& bed_path, int flank, const std::string& f1, const std::string& f2, const std::string& outdir, int device,
-	bool upper, const fasim_params& p)
+	bool upper, const fasim_params& p, const std::vector<int32_t>& del_lengths, bool del_only)
 {
+	const int nlen = (int)del_lengths.size();
 	fasim_region* reg = nullptr; int64_t nreg = 0;
 	if (fasim_read_bed(bed_path.c_str(), &reg, &nreg) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 2; }
 	std::unique_ptr<fasim_region, void (*)(void*)> owner(reg, fasim_free);
@@ -832,6 +839,10 @@ static int run_mutagenesis(const std::string& bed_path, int flank, const std::st
 	for (int q = 0; q < nq; q++) { qp[(size_t)q] = rnas[(size_t)q].seq.data(); ql[(size_t)q] = (int32_t)rnas[(size_t)q].seq.size(); }
 	// per lncRNA and interval the scores of its positions; empty: not met
 	std::vector<std::vector<std::vector<fasim_mut_score>>> scores((size_t)nq, std::vector<std::vector<fasim_mut_score>>((size_t)nreg));
+	// --deletions: per lncRNA and interval the scores of its (position, length) pairs, and per interval its letters
+	std::vector<std::vector<std::vector<fasim_del_score>>> dscores((size_t)nq, std::vector<std::vector<fasim_del_score>>((size_t)nreg));
+	std::vector<std::string> seqs((size_t)nreg);
+	std::vector<char> met((size_t)nreg, 0);
 	std::map<std::string, std::multimap<int64_t, int64_t>> todo;
 	std::set<std::string> chroms_seen;
 	std::vector<char> held_start((size_t)nreg, 0);
@@ -865,17 +876,28 @@ static int run_mutagenesis(const std::string& bed_path, int flank, const std::st
 		}
 		if (!eng && fasim_engine_create(device, &eng) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
 		const int64_t off0 = 0, len0 = (int64_t)rec.seq.size();
-		std::vector<fasim_mut_score> got((size_t)nq * (size_t)npos);
-		if (fasim_score_mutagenesis(eng, qp.data(), ql.data(), nq, rec.seq.data(), &off0, &len0, 1, loc.data(), (int64_t)loc.size(), flank, &p, got.data(), nullptr) != FASIM_OK) {
+		std::vector<fasim_mut_score> got(del_only ? 0 : (size_t)nq * (size_t)npos);
+		if (!del_only && fasim_score_mutagenesis(eng, qp.data(), ql.data(), nq, rec.seq.data(), &off0, &len0, 1, loc.data(), (int64_t)loc.size(), flank, &p, got.data(), nullptr) != FASIM_OK) {
 			fprintf(stderr, "fasim: %s\n", fasim_last_error(eng));
 			fasim_engine_destroy(eng);
 			return 1;
+		}
+		std::vector<fasim_del_score> dgot((size_t)nq * (size_t)npos * (size_t)nlen);
+		if (nlen && fasim_score_deletions(eng, qp.data(), ql.data(), nq, rec.seq.data(), &off0, &len0, 1, loc.data(), (int64_t)loc.size(), flank, del_lengths.data(), nlen, &p, dgot.data(), nullptr) != FASIM_OK) {
+			fprintf(stderr, "fasim: %s\n", fasim_last_error(eng));
+			fasim_engine_destroy(eng);
+			return 1;
+		}
+		for (size_t k = 0; k < mine.size(); k++) {
+			met[(size_t)mine[k]] = 1;
+			if (nlen) seqs[(size_t)mine[k]].assign(rec.seq.data() + loc[k].start, (size_t)(loc[k].end - loc[k].start));
 		}
 		for (int q = 0; q < nq; q++) {
 			size_t at = (size_t)q * (size_t)npos;
 			for (size_t k = 0; k < mine.size(); k++) {
 				const size_t len = (size_t)(reg[mine[k]].end - reg[mine[k]].start);
-				scores[(size_t)q][(size_t)mine[k]].assign(got.begin() + (ptrdiff_t)at, got.begin() + (ptrdiff_t)(at + len));
+				if (!del_only) scores[(size_t)q][(size_t)mine[k]].assign(got.begin() + (ptrdiff_t)at, got.begin() + (ptrdiff_t)(at + len));
+				if (nlen) dscores[(size_t)q][(size_t)mine[k]].assign(dgot.begin() + (ptrdiff_t)(at * (size_t)nlen), dgot.begin() + (ptrdiff_t)((at + len) * (size_t)nlen));
 				at += len;
 			}
 		}
@@ -884,7 +906,21 @@ static int run_mutagenesis(const std::string& bed_path, int flank, const std::st
 	if (nrec == 0) { fprintf(stderr, "fasim: no record in DNA file %s\n", f1.c_str()); return 1; }
 	const std::string base = f1.substr(0, f1.size() >= 3 ? f1.size() - 3 : 0);
 	int bad = 0;
-	for (int q = 0; q < nq; q++) {
+	for (int q = 0; q < nq && nlen; q++) {
+		std::vector<int64_t> offsets((size_t)nreg + 1, 0);
+		std::vector<fasim_del_score> all;
+		std::vector<const char*> letters((size_t)nreg, nullptr);
+		for (int64_t k = 0; k < nreg; k++) {
+			all.insert(all.end(), dscores[(size_t)q][(size_t)k].begin(), dscores[(size_t)q][(size_t)k].end());
+			offsets[(size_t)k + 1] = offsets[(size_t)k] + (met[(size_t)k] ? reg[k].end - reg[k].start : 0);
+			letters[(size_t)k] = seqs[(size_t)k].c_str();
+		}
+		char* text = nullptr; int64_t len = 0;
+		if (fasim_deletions_tsv(reg, offsets.data(), nreg, all.data(), letters.data(), del_lengths.data(), nlen, flank, rnas[(size_t)q].name.c_str(), &text, &len) != FASIM_OK) { fprintf(stderr, "fasim: %s\n", fasim_last_error(nullptr)); return 1; }
+		bad |= write_file(outdir + "/" + rnas[(size_t)q].name + "-" + base + ".deletions.tsv", text, len);
+		fasim_free(text);
+	}
+	for (int q = 0; q < nq && !del_only; q++) {
 		std::vector<int64_t> offsets((size_t)nreg + 1, 0);
 		std::vector<fasim_mut_score> all;
 		for (int64_t k = 0; k < nreg; k++) {
@@ -924,6 +960,7 @@ int main(int argc, char* const* argv)
 	bool sample_given = false;
 	bool devices_given = false, flank_given = false, variant_hits = false; int variant_flank = 300;
 	std::string mut_path; bool mut_flank_given = false; int mut_flank = 300;
+	std::string del_list; bool del_given = false, del_only = false;
 	std::vector<int> devices(1, 0);
 	bool stats = false, all_records = false, accumulate = false, upper = false, track = false, screen = false, screen_only = false;
 	bool sites = false, sites_gap_given = false, hist_arg_given = false, hist_arg_bad = false, hist_shuffle_bad = false;
@@ -946,7 +983,8 @@ int main(int argc, char* const* argv)
 		{ "hist-sites", no_argument, NULL, 1030 }, { "hist-shuffle", required_argument, NULL, 1031 },
 		{ "variants", required_argument, NULL, 1027 }, { "variant-flank", required_argument, NULL, 1028 },
 		{ "variant-hits", no_argument, NULL, 1029 }, { "sample", required_argument, NULL, 1034 },
-		{ "mutagenesis", required_argument, NULL, 1035 }, { "mutagenesis-flank", required_argument, NULL, 1036 }, { 0, 0, 0, 0 } };
+		{ "mutagenesis", required_argument, NULL, 1035 }, { "mutagenesis-flank", required_argument, NULL, 1036 },
+		{ "deletions", required_argument, NULL, 1037 }, { "deletions-only", no_argument, NULL, 1038 }, { 0, 0, 0, 0 } };
 	int opt;
 	while ((opt = getopt_long_only(argc, argv, optstring, lo, NULL)) != -1) {
 		switch (opt) {
@@ -978,6 +1016,8 @@ int main(int argc, char* const* argv)
 		case 1034: sample_given = true; sample = optarg; break;
 		case 1035: mut_path = optarg; break;
 		case 1036: mut_flank_given = true; mut_flank = strict_int(optarg, -1); break;
+		case 1037: del_given = true; del_list = optarg; break;
+		case 1038: del_only = true; break;
 		case 1004: devices_given = true; devices = parse_devices(optarg); if (devices.empty()) { fprintf(stderr, "fasim: bad --devices list\n"); return 2; } break;
 		case 1005: accumulate = true; break;
 		case 1006: upper = true; break;
@@ -1005,7 +1045,7 @@ int main(int argc, char* const* argv)
 		case 1025: trk.hist_only = true; break;
 		case 1030: hist_arg_given = true; trk.hist_sites = true; break;
 		case 1031: hist_arg_given = true; if (!strcmp(optarg, "di")) trk.hist_dinuc = true; else if (strcmp(optarg, "mono")) hist_shuffle_bad = true; break;
-		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only] [--sites-align] [--oligos [--oligo-hits]]] [--oligos [--oligo-profile] [--oligo-screen]] [--potential-hist [--hist-controls K] [--hist-seed S] [--hist-fdr Q] [--potential-hist-only] [--hist-sites] [--hist-shuffle mono|di]] [--variants FILE.vcf [--variant-flank F] [--variant-hits] [--sample NAME]] [--mutagenesis FILE.bed [--mutagenesis-flank F]]\n"); return 2;
+		default: fprintf(stderr, "usage: fasim -f1 DNA.fa -f2 RNA.fa [-O outdir] [-r R] [-t T] [-lg L] ... [--devices 0-7] [--all-records | --regions FILE.bed] [--upper] [--track BIN [--track-min V] [--track-only]] [--screen | --screen-only] [--tfo-profile | --tfo-profile-only] [--sites V [--sites-gap G] [--sites-only] [--sites-align] [--oligos [--oligo-hits]]] [--oligos [--oligo-profile] [--oligo-screen]] [--potential-hist [--hist-controls K] [--hist-seed S] [--hist-fdr Q] [--potential-hist-only] [--hist-sites] [--hist-shuffle mono|di]] [--variants FILE.vcf [--variant-flank F] [--variant-hits] [--sample NAME]] [--mutagenesis FILE.bed [--mutagenesis-flank F] [--deletions D,D,... [--deletions-only]]]\n"); return 2;
 		}
 	}
 	if (all_records && accumulate) { fprintf(stderr, "fasim: --all-records and --accumulate-records exclude each other\n"); return 2; }
@@ -1054,7 +1094,25 @@ int main(int argc, char* const* argv)
 		fprintf(stderr, "fasim: --mutagenesis is not available with --variants, --regions, --all-records, --accumulate-records, -F, --track, --screen, --tfo-profile, --sites, --oligos, --potential-hist or --devices\n");
 		return 2;
 	}
-	if (mutagenesis) return run_mutagenesis(mut_path, mut_flank, f1, f2, outdir, devices[0], upper, p);
+	if ((del_given || del_only) && !mutagenesis) { fprintf(stderr, "fasim: --deletions and --deletions-only need --mutagenesis FILE.bed\n"); return 2; }
+	if (del_only && !del_given) { fprintf(stderr, "fasim: --deletions-only needs --deletions LIST\n"); return 2; }
+	std::vector<int32_t> del_lengths;
+	if (del_given) {
+		size_t at = 0;
+		bool ok = !del_list.empty();
+		while (ok && at <= del_list.size()) {
+			const size_t comma = std::min(del_list.find(',', at), del_list.size());
+			const int d = strict_int(del_list.substr(at, comma - at).c_str(), -1);
+			ok = d >= 1 && d <= FASIM_MAX_ALLELE - 1 && (del_lengths.empty() || d > del_lengths.back()) && del_lengths.size() < (size_t)FASIM_MAX_DELETION_LENGTHS;
+			del_lengths.push_back(d);
+			at = comma + 1;
+		}
+		if (!ok) {
+			fprintf(stderr, "fasim: --deletions needs 1 to %d strictly ascending integers in [1, %d], comma-separated\n", FASIM_MAX_DELETION_LENGTHS, FASIM_MAX_ALLELE - 1);
+			return 2;
+		}
+	}
+	if (mutagenesis) return run_mutagenesis(mut_path, mut_flank, f1, f2, outdir, devices[0], upper, p, del_lengths, del_only);
 	if (variants) return run_variants(vcf_path, variant_flank, f1, f2, outdir, devices[0], upper, p, variant_hits, sample);
 	if (trk.oligos) trk.sites_only = true;      // a panel has no triplex records: the sites files and the panel table are all it writes
 	if (trk.oligos && trk.hist) trk.hist_only = true;      // (or the oligos' histograms)

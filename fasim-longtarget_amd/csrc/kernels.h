@@ -317,6 +317,34 @@ constexpr int MUT_WORDS = 20;
 hipError_t launch_mut_prefix(const MutLaunch& L, hipStream_t st);
 hipError_t launch_mut_touch(const MutLaunch& L, hipStream_t st);      // 4 * ncol problems
 hipError_t launch_mut_reduce(const MutReduceLaunch& L, hipStream_t st);
+// Every deletion of an interval from the same shared pass.  A group is again one context and one range of npos
+// positions under the nenc encodings, but its units' [v0, v1) are the columns of `next` >= npos positions: the range's own and, for
+// the deletions that reach beyond it, up to the longest length more, never past the interval's end.  The group's position j (j < next)
+// is column v0 + j of an even and v1 - 1 - j of an odd encoding; (j, lengths[l]) with j < npos is a deletion iff j + lengths[l] < next.
+// k_mut_prefix_pm writes the snapshots as k_mut_prefix does and pm[first[u] + s], the maximum of the plain H over the real rows of
+// column v0 + s as 2 * value + clip bit, for s < v1 - v0 - 1.  A jump problem (s, k, r) loads the snapshot before column s, runs column
+// k in plain mode and then the columns from r on, which only continue.  Problems of a launch: [0, ncol) the own-letter problem
+// (c, c, c + 1) of every snapshot column c -- run only where it is the last mark column of a deletion of the group: the position
+// where one ends (even) or where one is anchored (odd) -- then nalt = npos * nenc *
+// nlen ALT problems, ((pos0 * nenc + k * npos + j) * nlen + l) for deletion (j, l) of the group under its k-th encoding.
+// k_mut_jump: out[problem] = 2 * value + clip bit, cols[problem] = the columns it ran (both 0 for a problem that is not run).
+// k_mut_del_reduce: out[(pos0 + j) * nlen + l][DEL_WORDS]: per (allele, class) k_touch_reduce's word, then the columns run by the
+// deletion's ALT problems and by the own-letter problems it is the first to use (the smallest l of the group with that last mark
+// column), then whether it is a deletion.
+struct DelGroup { int32_t unit0, pos0, npos, next; };
+struct DelLaunch {
+	const uint8_t* tcodes; const uint8_t* qcodes; int32_t m;
+	const TouchProb* units; const int32_t* first /*[nunit + 1]*/; int32_t nunit, ncol /* = first[nunit] */;
+	uint16_t* rows;               // [max(nunit, ncol + nalt)][3][touch_state_rows(m)] where m > TOUCH_LDS_ROWS, else NULL
+	uint16_t* snap; uint32_t* pm /*[ncol]*/; uint32_t* out /*[ncol + nalt]*/; uint32_t* cols /*[ncol + nalt]*/;
+	const DelGroup* groups; int32_t ngroup, npos, nenc, nlen, nalt;
+	int16_t lengths[16]; uint8_t enc[48];
+	uint32_t* words;              // [npos * nlen][DEL_WORDS]
+};
+constexpr int DEL_WORDS = 10;
+hipError_t launch_mut_prefix_pm(const DelLaunch& L, hipStream_t st);
+hipError_t launch_mut_jump(const DelLaunch& L, hipStream_t st);      // ncol + nalt problems
+hipError_t launch_mut_del_reduce(const DelLaunch& L, hipStream_t st);
 
 // ---- rowfold.hip: per-base profile of the lncRNA folded from the row maxima of a batch -------------------------
 // Group g = segments [gfirst[g], gfirst[g + 1]) of the batch (the run of segments of one record, or the whole batch); the result is

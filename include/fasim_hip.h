@@ -915,6 +915,54 @@ int fasim_score_mutagenesis(fasim_engine* e, const char* const* rnas, const int3
  * no lines.  Free with fasim_free. */
 int fasim_mutagenesis_tsv(const fasim_region* regions, const int64_t* offsets /* [n + 1] */, int64_t n, const fasim_mut_score* scores,
                           int32_t flank, const char* rna_name, char** text, int64_t* text_len);
+/* ---- every deletion of an interval from the same shared pass (csrc/mutagenesis.hip) --------------------------- */
+/* Which deletions inside an interval matter?  Interval, flank, context C = record[lo, hi) and the bound (end - start) + 2 * flank <=
+ * 5120 are section 26's.  lengths: 1 to FASIM_MAX_DELETION_LENGTHS strictly ascending integers in [1, FASIM_MAX_ALLELE - 1].  A
+ * deletion is (x, d), d one of the lengths, x in [start, end), x + d < end: base x, the anchor of a VCF line, stays and the bases
+ * [x + 1, x + 1 + d) go, all inside the interval.  A pair with x + d >= end is no deletion: valid 0, values 0, enc -1.  The result of
+ * (x, d) is what fasim_score_variants defines for pos = x, REF = record[x, x + d + 1), ALT = record[x], with the one difference that
+ * the window is the shared context: with c0 = x - lo, REF has the target C, the mark [c0, c0 + d + 1) and the edges (lo > 0, hi <
+ * record length); ALT has the target C without the letters [c0 + 1, c0 + 1 + d), the mark [c0, c0 + 1) and the same edges; the clip
+ * bit sits on the first and last column of the problem's own window.  Scoring, classes, the reduction over encodings and
+ * 2 * value + bit are section 19's, so a value is never below fasim_score_variants' for the same deletion and flank.
+ * value[a][c], enc[a][c]: allele a (0 REF, 1 ALT), strand class c (enc -1: value 0); clipped[a]: bit 0 of the allele's largest
+ * 2 * value + bit; clean: all d + 1 bytes of REF are upper-case ACGT (the others are scored through the encode table all the same). */
+#define FASIM_MAX_DELETION_LENGTHS 16
+typedef struct fasim_del_score {
+	int32_t value[2][FASIM_TRACK_CLASSES];
+	int8_t enc[2][FASIM_TRACK_CLASSES];
+	uint8_t clipped[2]; uint8_t valid, clean;
+	uint8_t reserved[4];
+} fasim_del_score;
+/* deletions: the valid (position, length) pairs; prefix_problems, prefix_cols: as fasim_mutagenesis_stats; own_problems: the
+ * own-letter continuations, one per (column at which a deletion ends, encoding) and launch; alt_problems: one per (deletion,
+ * encoding); cont_cols: the columns both kinds ran until their dead column; cont_cols_bound: what that would be with no early stop;
+ * prefix_s, cont_s: HIP-event seconds of k_mut_prefix_pm and k_mut_jump. */
+typedef struct fasim_deletion_stats {
+	int64_t intervals, positions, deletions, launches, prefix_problems, prefix_cols, own_problems, alt_problems, cont_cols, cont_cols_bound;
+	double prefix_s, cont_s, total_s;
+} fasim_deletion_stats;
+/* Scores every (position, length) of nint intervals for nq >= 1 queries: out[(q * npos + k) * nlen + l], positions as in
+ * fasim_score_mutagenesis, lengths in the order given.  valid and clean do not depend on the query.  The result of a pair depends on
+ * the record, the interval, the flank, the length, the query and the parameters only.  Refused before any GPU work, the engine stays
+ * usable: the refusals of fasim_score_mutagenesis, and nlen outside [1, FASIM_MAX_DELETION_LENGTHS], a length outside
+ * [1, FASIM_MAX_ALLELE - 1] or lengths that do not ascend strictly (FASIM_E_ARG); a call in which one position alone does not fit a
+ * launch (FASIM_E_UNSUPPORTED): with L the longest interval and s = 4 bytes per query row (rounded up to whole workgroup rows),
+ * nenc * min(1 + longest length, L) * s must not exceed 256 MB, e.g. H19 under 48 encodings takes lengths up to 495. */
+int fasim_score_deletions(fasim_engine* e, const char* const* rnas, const int32_t* rna_lens, int32_t nq,
+                          const char* dna, const int64_t* rec_off, const int64_t* rec_len, int32_t nrec,
+                          const fasim_interval* intervals, int64_t nint, int32_t flank, const int32_t* lengths, int32_t nlen,
+                          const fasim_params* p, fasim_del_score* out /* [nq * npos * nlen] */, fasim_deletion_stats* stats /* may be NULL */);
+/* The table `fasim --mutagenesis --deletions` writes for one query: `# fasim deletions lncRNA=<rna_name> flank=<F> lengths=<d,d,...>`,
+ * the column names of fasim_variants_tsv, then one line per clean deletion, intervals in the order given, positions ascending, lengths
+ * in their order: line = regions[k].line, chrom, pos (1-based, of the anchor), id = regions[k].name, ref (d + 1 letters), alt (the
+ * anchor), per class <Class>_ref <Class>_alt, max_ref max_alt delta rule_ref rule_alt clipped as fasim_variants_tsv prints them;
+ * clipped is the bit of the larger of the two alleles' words 2 * max value + clipped.  scores: the pairs of interval k are
+ * scores[offsets[k] * nlen .. offsets[k + 1] * nlen) (an interval that was not scored has none); seqs[k]: the end - start letters of
+ * interval k (not read for an interval without scores).  Free with fasim_free. */
+int fasim_deletions_tsv(const fasim_region* regions, const int64_t* offsets /* [n + 1] */, int64_t n, const fasim_del_score* scores,
+                        const char* const* seqs /* [n] */, const int32_t* lengths, int32_t nlen, int32_t flank, const char* rna_name,
+                        char** text, int64_t* text_len);
 /* ingest helper: upper-cases a DNA record in place (soft-masked genomes such as UCSC hg38 carry repeats in lower
  * case; the reference does not upper-case and treats such letters as unknown, rules.h:286-312, 82-83). */
 void fasim_upper_case(char* seq, int64_t n);
